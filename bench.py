@@ -22,6 +22,13 @@ Scaling (the line's `scaling` key; `scaling_definitions` spells both out):
 After the timed region, for N > 1, rank 0 checks that the rows it received from every rank are the rows that rank computed
 (`gather_verified`; --no-check-gather skips it).
 
+A plain run sets up, warms up, times --steps steps, writes the last timed step's rows when --dump-outputs DIR is given and
+prints the line.  Everything else (the CPU baseline, the end-to-end leg) runs only with --full.
+  --dump-outputs DIR  after the timed region: the rows the last timed step returned (every rank's, in read order), one
+                      DIR/<field>.npy per field of the result row (integers as float64, scores as float32); above 64 MB
+                      a fixed seeded sample of the reads, whose indices go to DIR/read_index.npy.  Inputs are seeded: the
+                      same arguments give the same inputs in every run, so two builds can be compared file by file.
+
 The JSON line also carries
   roofline      of the dominant kernel (sdtw_fill_kernel).  `bound` is "valu": the kernel never materialises the cost matrix,
                 so VALU issue binds, not HBM.  `achieved`/`peak`/`frac` are lane-operations per second: DP
@@ -29,9 +36,11 @@ The JSON line also carries
                 2.4 GHz.  The HBM view north_star asks for sits beside it as `roofline.hbm` (algorithmic bytes per launch /
                 mean kernel duration, measured with HIP events on the kernel's stream, against 8 TB/s), with the counter
                 traffic and `traffic_over_algorithmic`.
+and, with --full only,
   cpu_baseline  sigfish's own CPU alignment stage (the reference sources compiled into oracle/_ref; kind "reference")
                 timed on this box's host cores on a bounded sample of the same workload; falls back to our CPU
                 restatement (kind "port") when that build is absent.
+  end_to_end    raw BLOW5 -> PAF through the command line on files generated in the run (tools/e2e_bench.py).
 """
 import argparse
 import json
@@ -113,6 +122,27 @@ def quote_profile(profiles_dir, workload, reads, opts, build_id):
     return traffic, traffic_src, issue
 
 
+DUMP_LIMIT = 64 * 1024 * 1024  # bytes, all --dump-outputs files together
+
+
+def dump_outputs(out_dir, rows):
+    """rows: RESULT_DTYPE[n], what the timed path returned -> out_dir/<field>.npy (integers float64, scores float32); over
+    DUMP_LIMIT a sorted sample of the reads drawn with a fixed seed, its indices in out_dir/read_index.npy."""
+    fields = [f for f in rows.dtype.names if f != "pad"]
+    conv = {f: (np.float32 if rows.dtype[f].kind == "f" else np.float64) for f in fields}
+    per_row = sum(np.dtype(t).itemsize for t in conv.values())
+    idx = None
+    if len(rows) * per_row > DUMP_LIMIT:
+        k = DUMP_LIMIT // (per_row + 8)
+        idx = np.sort(np.random.default_rng(0).choice(len(rows), k, replace=False))
+        rows = rows[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for f in fields:
+        np.save(os.path.join(out_dir, f + ".npy"), np.ascontiguousarray(rows[f], dtype=conv[f]))
+    if idx is not None:
+        np.save(os.path.join(out_dir, "read_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -134,7 +164,13 @@ def main():
                     help="skip the check after the timed region that rank 0 received exactly the rows every rank computed (checksums)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end leg (raw BLOW5 -> PAF through the command line)")
     ap.add_argument("--e2e-reads", type=int, default=400_000, help="reads in the generated BLOW5 files of the end-to-end leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline and the end-to-end leg (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the rows the last timed step returned to DIR/<field>.npy (float32/float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     # ---- ranks: the launcher's, or our own (never a re-exec of a process that has touched the GPU) ----------------
     from sigfish_amd import launch  # pure Python, loads nothing native
@@ -287,6 +323,14 @@ def main():
     if rank != 0:
         al.close()
         return  # (this rank's GPU is free from here on: rank 0's end-to-end leg below starts one process per GPU)
+    if args.dump_outputs:  # the rows of the last timed step, every rank's, in read order
+        slot = (args.steps - 1) % n_slots
+        if gathered is None:
+            rows = np.frombuffer(d_out[slot * row_bytes:(slot + 1) * row_bytes].cpu().numpy().tobytes(), dtype=S.RESULT_DTYPE)
+        else:  # rank r's slots lie side by side in its block of the gathered rows
+            cuts = np.concatenate([[0], np.cumsum(counts)])
+            rows = np.concatenate([gathered[cuts[r] + slot * c:cuts[r] + (slot + 1) * c] for r, c in enumerate(shard_reads)])
+        dump_outputs(args.dump_outputs, rows)
 
     total_reads = job_reads * args.steps
     value = total_reads / elapsed
@@ -363,7 +407,7 @@ def main():
     # ---- CPU baseline on a bounded sample of this rank's reads, all host cores of this box ---------------------
     # kind "reference": the reference's OWN align_db (dtw_single over work_db), compiled from its sources into
     # oracle/_ref (travels with the repo); kind "port": our CPU restatement, when that build is not there.
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as O  # checker / baseline only
         cores = host_cores()
         oref = O.RefSynth(ref.names, ref.seq_lengths, ref.ref_lengths, ref.st_offset, ref.forward, ref.reverse)
@@ -394,7 +438,7 @@ def main():
     al.close()
     # ---- end to end (SURVEY.md 8d "plus end-to-end wall"): raw BLOW5 -> PAF through `sigfish-amd dtw`, whole process, on files
     # generated here; extra keys, never `value`.  After al.close(): the command line wants the GPU to itself.
-    if world == 1 and not args.no_e2e and args.workload == "ncov_r9_dna_q250":
+    if args.full and world == 1 and not args.no_e2e and args.workload == "ncov_r9_dna_q250":
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import e2e_bench
         try:
@@ -403,7 +447,7 @@ def main():
             out["end_to_end"] = {"error": str(e)[:300]}
     # ... and for N > 1 the same command line as it is meant to run on a node: one process per GPU (`--ranks N --device 0..N-1`),
     # against one process on one GPU, same file, outputs compared.  The other ranks of this bench have released their GPUs.
-    if world > 1 and not args.no_e2e and args.workload == "ncov_r9_dna_q250":
+    if args.full and world > 1 and not args.no_e2e and args.workload == "ncov_r9_dna_q250":
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import e2e_bench
         try:

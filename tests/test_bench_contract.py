@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from tests.util import ROOT, visible_gpus
@@ -12,7 +13,8 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_json_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--reads", "3000", "--cpu-seconds", "2", "--e2e-reads", "2000"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--reads", "3000", "--cpu-seconds", "2", "--e2e-reads", "2000",
+                        "--full"],
                        capture_output=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
@@ -73,3 +75,37 @@ def test_bench_over_rccl_on_every_gpu_the_box_has():
     d = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][0])
     assert d["scaling"] == "strong" and d["config"]["total_reads"] == 30001 and sum(d["config"]["reads_per_rank"]) == 30001
     assert d["gather_verified"] is True and abs(d["value"] - 30001 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-3 * d["value"]
+
+
+def test_plain_line_is_lean_and_dumps_the_last_step(tmp_path, oracle):
+    """A plain run times exactly --steps steps and carries no CPU baseline or end-to-end leg (those are --full); --dump-outputs
+    writes the rows of the last timed step, identical from run to run and equal to the oracle's on the same seeded inputs."""
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--reads", "3000",
+                            "--dump-outputs", str(out)], capture_output=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "reads/s" and d["dtype"] == "f32"
+        assert abs(d["value"] - 3000 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+        assert "cpu_baseline" not in d and "end_to_end" not in d
+        files = sorted(os.listdir(out))
+        assert files == sorted(f + ".npy" for f in ("rid", "pos_st", "pos_end", "score", "score2", "strand", "mapq", "valid"))
+        arrs = {f[:-4]: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and a.shape == (3000,) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 1024 * 1024
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+    # the same inputs bench.py builds (reference model seed 0, reads seed 1000 + rank): the first reads against the oracle
+    from sigfish_amd import synth
+    ref, flag, _, _, _ = synth.workload("ncov_r9_dna_q250", n_reads=8, seed=0)
+    q, q_off, _ = synth.make_reads(ref, 3000, qlen=250, seed=1000)
+    oref = oracle.RefSynth(ref.names, ref.seq_lengths, ref.ref_lengths, ref.st_offset, ref.forward, ref.reverse)
+    m = 64
+    want = oracle.align_batch(q, q_off[:m + 1], oref, flag, threads=8)
+    for f, a in dumps[0].items():
+        assert np.array_equal(a[:m], want[f].astype(a.dtype), equal_nan=True), f

@@ -2,14 +2,16 @@
 # One bench line WITH cpu_baseline (the reference's own align_db on this box's host cores, subsample sizes of BASELINE.md section 3)
 # per BASELINE.json workload shape + the 32-row classes (test/test.sh:70 runs RNA at -q 500).  Run on the GPU box, after
 # `tools/profile_all.sh <tag>` with its summaries copied into profiles/, so that the lines quote counter traffic of THIS build:
-#   bash tools/bench_configs.sh <round tag>   ->  gpurun_out/<tag>_bench_<workload>.json
+#   bash tools/bench_configs.sh <round tag> [output dir, default bench_out]   ->  <output dir>/<tag>_bench_<workload>.json
 R=${1:?round tag}
+OUT=${2:-bench_out}
+mkdir -p "$OUT"
 run() {  # workload cpu_reads [bench args...]
   local w=$1 c=$2; shift 2
-  timeout -k 10 600 python bench.py --workload $w --cpu-reads $c --no-e2e --steps 5 --warmup 1 "$@" 2> gpurun_out/${R}_bench_$w.err | tail -1 > gpurun_out/${R}_bench_$w.json
+  timeout -k 10 600 python bench.py --full --workload $w --cpu-reads $c --no-e2e --steps 5 --warmup 1 "$@" 2> "$OUT/${R}_bench_$w.err" | tail -1 > "$OUT/${R}_bench_$w.json"
   python -c "
 import json
-d = json.load(open('gpurun_out/${R}_bench_$w.json'))
+d = json.load(open('$OUT/${R}_bench_$w.json'))
 print('$w', d['value'], 'reads/s  %.3e cells/s' % d['dp_cells_per_s'], 'valu frac', d['roofline']['frac'], 'cpu', d['cpu_baseline']['value'], d['cpu_baseline']['kind'],
       'parity', d['cpu_baseline']['parity_on_sample'], 'traffic', d['roofline']['traffic'], flush=True)"
 }

@@ -6,7 +6,7 @@
 Generates two files with tools/make_blow5.py from the reference's own DNA fixture replicated --reads/5 times --
 uncompressed, and zlib records + svb-zd signals (what real files look like) -- runs the command line on each at every -K
 (whole process: start-up, reference upload, file mapping, host stages, GPU stages, output) and prints one JSON object.
-bench.py calls measure() for the `end_to_end` key of its line (never `value`)."""
+bench.py --full calls measure() for the `end_to_end` key of its line (never `value`)."""
 import argparse
 import itertools
 import json
