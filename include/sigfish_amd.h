@@ -211,6 +211,11 @@ int sfa_align_events(sfa_ctx_t *ctx, const sfa_event_t *const *events, const int
  * this index never signals; every batch then fails with SFA_EKERNEL after the wait limit; -1 = off). */
 int sfa_set_option(sfa_ctx_t *ctx, const char *key, int64_t value);
 
+/* Pore chemistry, the reference's opt.pore_flag: 0 R9 (default), 1 R10, 2 RNA004; applies to every shard.  It changes rows:
+ * the RNA automatic query start (prefix_size < 0) looks for an adaptor of >= 500 samples below mean - 0.7 sd on RNA004,
+ * of >= 2000 samples below mean - 0.5 sd otherwise (src/jnn.h).  SFA_EINVAL outside 0..2. */
+int sfa_set_pore(sfa_ctx_t *ctx, int pore);
+
 /* Plan a batch without running it: how reads would be grouped.  slot_of_read[n_reads] (may be NULL) receives
  * quad*4+slot per read or -1 for skipped reads; job_len[n_jobs] are the (contig,strand) lengths in processing
  * order.  ckpt_interval / ckpt_budget_bytes / lane_widening as in sfa_set_option (0 = defaults; the device is
@@ -260,14 +265,17 @@ typedef struct {
     int64_t qstart, qend;   /* query window in events (src/sigfish.c:479-480) */
     uint64_t start_raw_idx; /* event[qstart].start */
     uint64_t end_raw_idx;   /* event[qend-1].start + length */
-    int32_t status;         /* bit 0: too short (kept), bit 1: ignored (dropped) */
+    int32_t status;         /* bit 0: too short (kept), bit 1: ignored (dropped), bit 2: automatic query start failed (the
+                               window starts at event 50; the reference's prefix_fail, src/sigfish.c:438-446) */
     int32_t pad;
 } sfa_query_info_t;
 
 /* process_db() for a whole batch on the device (src/sigfish.c:1018-1047 minus parsing): raw ADC samples -> pA ->
  * event detection -> query window -> z-normalisation -> alignment.  raw: concatenated int16 samples, raw_off[n+1];
- * scaling[3*i..]: digitisation, offset, range of read i (slow5 record fields).  prefix_size must be >= 0 (the RNA
- * "-p -1" adaptor/poly-A detection stays on the host path: sfa_detect_events + sfa_select_query).
+ * scaling[3*i..]: digitisation, offset, range of read i (slow5 record fields).  prefix_size < 0 is the RNA automatic query
+ * start ("-p -1", detect_query_start, src/sigfish.c:380-422 + src/jnn.c), also on the device: the window starts at the
+ * first event behind the poly-A tail, or at event 50 where none is found (status bit 2).  It needs an SFA_RNA context
+ * without SFA_END and SFA_INV (else SFA_EINVAL), and follows the context's pore (sfa_set_pore).
  * rows[n] and info[n] are written in input order.  Blocking. */
 int sfa_align_raw(sfa_ctx_t *ctx, const int16_t *raw, const int64_t *raw_off, const double *scaling, int32_t n_reads,
                   int32_t prefix_size, int32_t query_size, sfa_result_t *rows, sfa_query_info_t *info);
@@ -297,7 +305,8 @@ typedef struct {
  * (StreamVByte zig-zag deltas, one wave per record) on the device; the path of sfa_align_raw_ex continues from there.
  * heads[n] receives the fields the output needs.  A record the device decoder declines (malformed, longer read id than
  * sfa_read_head_t holds, inflating to more than 4x its size + 4 KB) sends the batch through the library's host reader
- * instead -- same results, counted in sfa_profile_t.blow5_fallbacks.  Other arguments as for sfa_align_raw_ex. */
+ * instead -- same results, counted in sfa_profile_t.blow5_fallbacks.  Other arguments as for sfa_align_raw_ex (prefix_size < 0
+ * included). */
 int sfa_align_blow5(sfa_ctx_t *ctx, const uint8_t *records, const int64_t *rec_off, int32_t n_reads, int32_t record_zlib,
                     int32_t signal_svb, int32_t prefix_size, int32_t query_size, sfa_result_t *rows, sfa_query_info_t *info,
                     sfa_read_head_t *heads, sfa_event_t *query_events);
@@ -326,6 +335,12 @@ int64_t sfa_detect_events(const int16_t *raw, int64_t n_raw, double digitisation
 int sfa_select_query(sfa_event_t *events, int64_t n_events, const int16_t *raw, int64_t n_raw, double digitisation,
                      double offset, double range, int32_t prefix_size, int32_t query_size, uint32_t flag, int pore,
                      int64_t *qstart, int64_t *qend);
+
+/* detect_query_start (src/sigfish.c:380-422): the RNA automatic query start of one read -- the first event whose start lies at
+ * or behind the end of the poly-A tail that follows the adaptor -- or -1 when the adaptor or the tail is not found (callers
+ * then start at event 50).  events: the read's event table (sfa_detect_events); pore as for sfa_set_pore. */
+int64_t sfa_detect_query_start(const int16_t *raw, int64_t n_raw, double digitisation, double offset, double range,
+                               const sfa_event_t *events, int64_t n_events, int pore);
 
 /* One SAM line for a result row (sam_str, src/sigfish.c:770-794, with path_to_map 530-571 and the "ss" string of
  * r2qevent_map_to_ss 663-768).  The warp path of the winner is rebuilt on the host from the band between its

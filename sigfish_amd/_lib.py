@@ -53,7 +53,7 @@ class SfaEvent(C.Structure):
 # every symbol include/sigfish_amd.h declares (checked by tests/test_capi_host.py::test_library_exports_every_declared_symbol)
 SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "sfa_submit_batch", "sfa_wait_batch", "sfa_align_batch_device", "sfa_align_events", "sfa_align_raw", "sfa_align_raw_ex", "sfa_align_blow5", "sfa_inflate_zlib_device", "sfa_pinned_alloc", "sfa_pinned_free", "sfa_sync",
            "sfa_get_profile", "sfa_stream", "sfa_set_option", "sfa_plan_batch", "sfa_destroy", "sfa_last_error", "sfa_version", "sfa_build_id", "sfa_gen_ref_record",
-           "sfa_znormalise", "sfa_paf_row", "sfa_sam_row", "sfa_r2qevent_map", "sfa_detect_events", "sfa_select_query", "sfa_read_kmer_model",
+           "sfa_znormalise", "sfa_paf_row", "sfa_sam_row", "sfa_r2qevent_map", "sfa_detect_events", "sfa_select_query", "sfa_detect_query_start", "sfa_set_pore", "sfa_read_kmer_model",
            "sfa_blow5_open", "sfa_blow5_attr", "sfa_blow5_next", "sfa_blow5_close", "sfa_blow5_select_shard", "sfa_blow5_select_records", "sfa_inflate_zlib", "sfa_inflate_zlib_pair", "sfa_device_memory"]
 
 _lib = None
@@ -114,6 +114,10 @@ def load():
     L.sfa_detect_events.restype = C.c_int64
     L.sfa_select_query.argtypes = [C.POINTER(SfaEvent), C.c_int64, i16p, C.c_int64, C.c_double, C.c_double, C.c_double,
                                    C.c_int32, C.c_int32, C.c_uint32, C.c_int, i64p, i64p]
+    L.sfa_detect_query_start.argtypes = [i16p, C.c_int64, C.c_double, C.c_double, C.c_double, C.POINTER(SfaEvent), C.c_int64,
+                                         C.c_int]
+    L.sfa_detect_query_start.restype = C.c_int64
+    L.sfa_set_pore.argtypes = [vp, C.c_int]
     L.sfa_read_kmer_model.argtypes = [C.c_char_p, f32p, C.POINTER(C.c_uint32)]
     L.sfa_blow5_open.argtypes = [C.c_char_p]
     L.sfa_blow5_open.restype = vp

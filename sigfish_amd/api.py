@@ -229,9 +229,14 @@ class Aligner:
     def set_option(self, key, value):
         _check(self._L.sfa_set_option(self._h, key.encode(), int(value)), f"sfa_set_option({key})")
 
+    def set_pore(self, pore):
+        """The reference's opt.pore_flag: 0 R9 (default), 1 R10, 2 RNA004 (the RNA automatic query start depends on it)."""
+        _check(self._L.sfa_set_pore(self._h, int(pore)), "sfa_set_pore")
+
     def align_raw(self, raw, raw_off, scaling, prefix_size=50, query_size=250, return_events=False):
         """process_db on the device: raw int16 samples (concatenated) -> (rows, info).  scaling: float64 [n,3] =
-        digitisation, offset, range per read.  return_events: also the query windows' event tables,
+        digitisation, offset, range per read.  prefix_size=-1: RNA automatic query start (info.status bit 2 where
+        it fell back to event 50).  return_events: also the query windows' event tables,
         EVENT_DTYPE[n, query_size] (means z-normalised; read i uses the first info.qend - info.qstart entries)."""
         raw = np.ascontiguousarray(raw, np.int16)
         ro = np.ascontiguousarray(raw_off, np.int64)
@@ -400,6 +405,15 @@ def select_query(events, raw, meta, prefix_size=50, query_size=250, flag=0, pore
                                         meta["offset"], meta["range"], prefix_size, query_size, flag, pore,
                                         C.byref(qs), C.byref(qe))
     return bool(keep), qs.value, qe.value
+
+
+def detect_query_start(raw, meta, events, pore=0):
+    """detect_query_start: the RNA automatic query start of one read (first event behind the poly-A tail), -1 if not found."""
+    raw = np.ascontiguousarray(raw, np.int16)
+    ev = np.ascontiguousarray(events, EVENT_DTYPE)
+    return int(_lib.load().sfa_detect_query_start(raw.ctypes.data_as(C.POINTER(C.c_int16)), len(raw), meta["digitisation"],
+                                                  meta["offset"], meta["range"], C.cast(ev.ctypes.data, C.POINTER(_lib.SfaEvent)),
+                                                  len(ev), int(pore)))
 
 
 def read_kmer_model(path, warnings=None):

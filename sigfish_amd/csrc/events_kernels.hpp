@@ -580,6 +580,255 @@ __global__ void __launch_bounds__(256) ev_stats_kernel(const EvArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// RNA automatic query start ("-p -1"): detect_query_start(), src/sigfish.c:380-422, with the adaptor and poly-A segmenters
+// of src/jnn.c (find_adaptor -> jnnv2, find_polya -> jnn_core).  CPU twin: sfa::detect_query_start, host/events.cpp.
+// Runs after the peak picker (it needs the event starts); the prefix sums and t-statistics are dead by then, so their
+// buffers hold this stage's scratch.
+struct AutoArgs {
+    const int16_t *raw;
+    const int64_t *raw_off;   // [n+1]
+    const float *scale;       // [n][2]: offset, raw_unit (as EvArgs)
+    int64_t *csum;            // [total + n]: prefix sums of the clamped samples, read i owns [raw_off[i] + i, raw_off[i+1] + i + 1)
+    float *tmean;             // [total]: rolling mean of the adaptor segmenter, read i owns [raw_off[i], raw_off[i] + n_i - 2000)
+    const int64_t *ev_off;
+    const int32_t *ev_start;
+    const int32_t *n_events;
+    int32_t *start;           // [n] first event at or after the end of the poly-A tail, -1 = not found (caller falls back to 50)
+    int32_t n_reads;
+    int32_t lo;               // shortest adaptor: 500 for RNA004 (pore 2), else 2000
+    float std_scale;          // 0.7 for RNA004, else 0.5
+};
+
+constexpr int kAdWindow = 2000, kAdSegDist = 1500, kAdHi = 200000;                  // jnnv2() with JNNV2_RNA_*_ADAPTOR
+constexpr int kPaCorrector = 50, kPaSegDist = 200, kPaWindow = 250, kPaError = 30;  // jnn_core() with JNNV1_*_POLYA
+
+// The adaptor segmenter's rolling mean t[j] = mean(clamp(raw[j .. j+2000))).  The reference keeps a running fp32 sum
+// (run -= cur[j-1]; run += cur[j+1999], jnn.c:22-46).  Its addends are clamp_outlier((float)raw): integers in [0, 1200],
+// so every partial sum is an integer of at most 2000 x 1200 = 2.4e6 < 2^24 -- exactly representable, no addition
+// rounds, and the running sum equals the true window sum whatever the order.  An integer prefix sum S per read gives
+// the same values: t[j] = (float)(S[j+2000] - S[j]) / 2000 is the reference's one rounding (the division), bit for bit.
+// One block per read: a block-wide integer scan, then one t[j] per thread.
+__global__ void __launch_bounds__(256) ev_autostart_tmean_kernel(const AutoArgs a) {
+    __shared__ int32_t wsum[4];
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t b = a.raw_off[i], n = a.raw_off[i + 1] - b;
+    if (n <= kAdWindow) return;  // find_adaptor() fails at once
+    const int16_t *raw = a.raw + b;
+    int64_t *S = a.csum + b + i;
+    if (tid == 0) S[0] = 0;
+    int64_t carry = 0;
+    for (int64_t base = 0; base < n; base += 256) {
+        const int64_t j = base + tid;
+        int s = 0;
+        if (j < n) {
+            const int r = raw[j];
+            s = r > 1200 ? 1200 : (r < 0 ? 0 : r);  // clamp_outlier() on an integer-valued float
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int u = __shfl_up(s, o);
+            if (lane >= o) s += u;
+        }
+        if (lane == 63) wsum[w] = s;
+        __syncthreads();
+        int64_t pre = carry;
+        for (int k = 0; k < w; ++k) pre += wsum[k];
+        if (j < n) S[j + 1] = pre + s;
+        carry += static_cast<int64_t>(wsum[0]) + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();  // (also orders this block's stores of S before the reads below)
+    }
+    float *t = a.tmean + b;
+    for (int64_t j = tid; j < n - kAdWindow; j += 256) t[j] = static_cast<float>(S[j + kAdWindow] - S[j]) / 2000.0f;
+}
+
+// One read per lane, the read's sequence [start, start + len) of `base` visited in order: f(j, v) gets element j as a
+// float and returns false to stop early.  The wave stages tiles of 64 sequences x 32 elements through LDS (coalesced, a
+// half-wave per sequence, the next tile in flight while this one is walked), as ev_prefix_kernel does; the loop ends
+// when no lane has anything left.  b0 <= every start of the wave, and a wave with any work holds base[b0].
+template <typename Src, typename F>
+__device__ __forceinline__ void lane_walk(const Src *base, int64_t b0, int64_t start, int32_t len, float (*tile)[kEvTile + 1],
+                                          int64_t *lds_s, int32_t *lds_n, F &&f) {
+    const int lane = threadIdx.x, half = lane >> 5, jl = lane & 31;
+    __syncthreads();  // the previous walk is done with the LDS
+    lds_s[lane] = start - b0;
+    lds_n[lane] = len;
+    int maxn = len;
+#pragma unroll
+    for (int o = 32; o; o >>= 1) maxn = max(maxn, __shfl_xor(maxn, o));
+    __syncthreads();
+    if (maxn <= 0) return;
+    uint32_t rel[32];
+    int32_t ln[32];
+#pragma unroll
+    for (int it = 0; it < 32; ++it) {
+        rel[it] = static_cast<uint32_t>(lds_s[2 * it + half]);
+        ln[it] = lds_n[2 * it + half];
+    }
+    const Src *p = base + b0;
+    float v[32];
+    auto fetch = [&](int tb) {
+        const int bj = tb + jl;
+#pragma unroll
+        for (int it = 0; it < 32; ++it) v[it] = static_cast<float>(p[bj < ln[it] ? rel[it] + static_cast<uint32_t>(bj) : 0u]);
+    };
+    fetch(0);
+    bool go = len > 0;
+    for (int tb = 0; tb < maxn; tb += kEvTile) {
+#pragma unroll
+        for (int it = 0; it < 32; ++it) tile[2 * it + half][jl] = v[it];
+        const bool more = __any(go && tb + kEvTile < len);  // wave-uniform: someone needs the next tile
+        if (more) fetch(tb + kEvTile);
+        __syncthreads();
+        if (go) {
+            const int lim = min(kEvTile, len - tb);
+            for (int jj = 0; jj < lim && go; ++jj) go = f(tb + jj, tile[lane][jj]);
+        }
+        if (!__any(go && tb + kEvTile < len)) break;
+        __syncthreads();
+    }
+}
+
+// Everything after the rolling mean, sequential per read as in the reference: mean_f / stdv_f of t (fp32, in order), the
+// adaptor segmenter over t, m_a = mean_f over the adaptor's pA, the poly-A segmenter over the pA behind the adaptor, and
+// the first event starting at or after the tail's end.  One read per lane over LDS tiles (lane_walk).
+//
+// Early exits, each provably without effect: a segment of either segmenter can still grow by a merge (the next segment
+// starts less than seg_dist past its end) until it is no longer the last one, or until the scan is seg_dist past its end
+// with nothing open that started before that.  Only such a closed segment can be accepted (adaptor: the first closed
+// segment with lo <= length <= hi) or returned (poly-A: the first segment), so the scans stop once the answer is closed.
+__global__ void __launch_bounds__(64) ev_autostart_scan_kernel(const AutoArgs a) {
+    __shared__ float tile[64][kEvTile + 1];
+    __shared__ int64_t lds_s[64];
+    __shared__ int32_t lds_n[64];
+    const int lane = threadIdx.x, i = blockIdx.x * 64 + lane;
+    const bool live = i < a.n_reads;
+    const int64_t b0 = a.raw_off[blockIdx.x * 64];
+    const int64_t b = a.raw_off[live ? i : a.n_reads];
+    const int64_t n = live ? a.raw_off[i + 1] - b : 0;
+    const int32_t m = n > kAdWindow ? static_cast<int32_t>(n - kAdWindow) : 0;
+
+    // mean_f(t), stdv_f(t) (stat.h:17-44): fp32 accumulators, divided by the int count
+    float s = 0.0f;
+    lane_walk(a.tmean, b0, b, m, tile, lds_s, lds_n, [&](int, float x) {
+        s += x;
+        return true;
+    });
+    const float mn = s / static_cast<float>(m);
+    float s2 = 0.0f;
+    lane_walk(a.tmean, b0, b, m, tile, lds_s, lds_n, [&](int, float x) {
+        s2 += (x - mn) * (x - mn);
+        return true;
+    });
+    const float sd = sqrtf(s2 / static_cast<float>(m));
+    const float bot = mn - (sd * a.std_scale);
+
+    // jnnv2()'s segment loop (jnn.c:130-163); only the last segment and the answer are kept
+    bool begin = false, have = false, found = false;
+    int st = 0, en = 0, bx = 0, by = 0, ax = 0, ay = 0;
+    auto valid = [&](int x, int y) { return !(y - x > kAdHi || y - x < a.lo); };
+    lane_walk(a.tmean, b0, b, m, tile, lds_s, lds_n, [&](int j, float v) {
+        if (v < bot && !begin) {
+            st = j;
+            begin = true;
+        } else if (v < bot) {
+            en = j;
+        } else if (v > bot && begin) {
+            if (have && st - by < kAdSegDist) {
+                by = en;
+            } else {
+                if (have && valid(bx, by)) {  // the previous segment is closed: the first valid one is the answer
+                    found = true;
+                    ax = bx;
+                    ay = by;
+                }
+                bx = st;
+                by = en;
+                have = true;
+            }
+            st = en = 0;
+            begin = false;
+        }
+        if (!found && have && (begin ? st : j + 1) - by >= kAdSegDist && valid(bx, by)) {  // the last one can no longer grow
+            found = true;
+            ax = bx;
+            ay = by;
+        }
+        return !found;
+    });
+    if (!found && have && valid(bx, by)) {
+        found = true;
+        ax = bx;
+        ay = by;
+    }
+    const int adx = ax + kAdWindow / 2 - 1, ady = ay + kAdWindow / 2 - 1;  // (found implies ady > 0)
+
+    // m_a = mean_f(pA[ad.x .. ad.y)); pA = ((float)raw + offset) * raw_unit, as event_single()
+    const float off = live ? a.scale[2 * i] : 0.0f, unit = live ? a.scale[2 * i + 1] : 0.0f;
+    float sa = 0.0f;
+    lane_walk(a.raw, b0, b + (found ? adx : 0), found ? ady - adx : 0, tile, lds_s, lds_n, [&](int, float r) {
+        sa += (r + off) * unit;
+        return true;
+    });
+    const float m_a = sa / static_cast<float>(ady - adx);
+    const float top = (m_a + 30.0f) + 20.0f, pbot = (m_a + 30.0f) - 20.0f;  // m_a+30+20, m_a+30-20: left to right
+
+    // jnn_core() (jnn.c:191-279) over pA[ad.y ..); only the first segment matters: it is final once a second one exists or
+    // nothing can merge into it any more
+    bool prev = false;
+    int err = 0, prev_err = 0, c = 0, w = kPaCorrector, pst = 0, nseg = 0, fy = 0;
+    lane_walk(a.raw, b0, b + (found ? ady : 0), found ? static_cast<int32_t>(n - ady) : 0, tile, lds_s, lds_n, [&](int j, float r) {
+        const float pa = (r + off) * unit;
+        const float x = pa > 1200.0f ? 1200.0f : (pa < 0.0f ? 0.0f : pa);  // clamp_outlier(): NaN stays NaN, outside the band
+        if (x < top && x > pbot) {
+            if (!prev) {
+                pst = j;
+                prev = true;
+            }
+            c++;
+            w++;
+            if (prev_err) prev_err = 0;
+            if (c >= kPaWindow && c >= w && !(c % w)) err--;
+        } else {
+            if (prev && err < kPaError) {
+                c++;
+                err++;
+                prev_err++;
+                if (c >= kPaWindow && c >= w && !(c % w)) err--;
+            } else if (prev && c >= kPaWindow) {  // (|| (no segment yet && c >= window * stall_len 1.0): the same test)
+                const int end = j - prev_err;
+                prev = false;
+                if (nseg > 0 && pst - fy < kPaSegDist) {
+                    if (nseg == 1) fy = end;  // (a merge into a later segment leaves the first one alone)
+                } else {
+                    if (nseg == 0) fy = end;
+                    ++nseg;
+                }
+                c = err = prev_err = 0;
+            } else if (prev) {
+                prev = false;
+                c = err = prev_err = 0;
+            }
+        }
+        return !(nseg >= 2 || (nseg == 1 && (prev ? pst : j + 1) - fy >= kPaSegDist));
+    });
+    if (!live) return;
+    int32_t res = -1;
+    if (found && nseg > 0 && fy > 0) {
+        // the first event whose start is >= the tail's end; starts increase, so a binary search equals the reference's walk
+        const int64_t target = static_cast<int64_t>(fy) + ady;
+        const int32_t *es = a.ev_start + a.ev_off[i];
+        int lo = 0, hi = a.n_events[i];
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (static_cast<int64_t>(es[mid]) < target) lo = mid + 1;
+            else hi = mid;
+        }
+        res = lo < a.n_events[i] ? lo : -1;
+    }
+    a.start[i] = res;
+}
+
 // normalise_single(), src/sigfish.c:483-502 + the query extraction of dtw_single (857-867, reversal is done by the
 // fill kernels): z-normalise event means [qstart,qend) with sequential fp32 sums, pack them at q_off.  One read per lane.
 struct QueryArgs {

@@ -651,6 +651,8 @@ static int dtw_run(int argc, char **argv) {
         // threshold (waves per SIMD of a single batch) shrinks accordingly
         const int per_dev = n_ctx / static_cast<int>(o.devices.size()) * o.device_share;  // batches in flight on this device, all processes
         if (sfa_set_option(ctxs[j], "widen_below", std::max(1, 5 / per_dev)) != SFA_OK) die(sfa_last_error());
+        // the pore reaches the device route's automatic query start (-p -1), as it reaches select_and_normalise on the host route
+        if (sfa_set_pore(ctxs[j], o.pore_flag) != SFA_OK) die(sfa_last_error());
         // SFA_OPTS="name=value,name=value": planner / launch options of the library (sfa_set_option) for experiments from the
         // command line; rows do not depend on them (the library's test hooks are not options: refused here whatever the environment)
         if (const char *e = getenv("SFA_OPTS")) {
@@ -714,9 +716,9 @@ static int dtw_run(int argc, char **argv) {
         int64_t bytes = 0;
         bool via_device = false;  // this batch's records go to the device as they are in the file (sfa_align_blow5)
     };
-    // events on the GPU unless the RNA auto prefix is asked for (adaptor/poly-A detection stays on the host); for SAM the
-    // event tables of the query windows come back from the device with the rows
-    const bool gpu_events = !o.host_events && o.prefix >= 0;
+    // events on the GPU (the RNA automatic query start, -p -1, included) unless --host-events; for SAM the event tables of the
+    // query windows come back from the device with the rows
+    const bool gpu_events = !o.host_events;
     // ... and so can the records themselves: inflate, field parsing and signal decoding on the device (sfa_align_blow5), the host
     // only framing the records and copying their bytes into page-locked staging.  Measured on one GPU with 16 host threads
     // (profiles/r02_logs/e2e_compressed_streams_x_batch.log): the two routes are level, 0.49-0.52 M reads/s from a compressed
@@ -774,6 +776,7 @@ static int dtw_run(int argc, char **argv) {
         }
         if (gpu_events)
             for (int32_t i = 0; i < n; ++i) {
+                prefix_fail += (sl.info[i].status & 4) != 0;
                 ignored += (sl.info[i].status & 2) != 0;
                 too_short += (sl.info[i].status & 1) != 0;
             }

@@ -205,6 +205,14 @@ void sfa_destroy(sfa_ctx_t *c) {
     delete c;
 }
 
+int sfa_set_pore(sfa_ctx_t *c, int pore) {
+    if (!c) return fail(SFA_EINVAL, "sfa_set_pore: null context");
+    if (pore < 0 || pore > 2) return fail(SFA_EINVAL, "sfa_set_pore: pore must be 0 (R9), 1 (R10) or 2 (RNA004), not %d", pore);
+    c->pore = pore;
+    for (sfa_ctx *sh : c->shards) sh->pore = pore;
+    return SFA_OK;
+}
+
 int sfa_set_option(sfa_ctx_t *c, const char *key, int64_t value) {
     if (!c || !key) return fail(SFA_EINVAL, "sfa_set_option: null argument");
     if (!c->shards.empty()) {

@@ -181,6 +181,7 @@ struct sfa_ctx {
 
     int device = 0;
     uint32_t flag = 0;
+    int pore = 0;  // sfa_set_pore: 0 R9, 1 R10, 2 RNA004 (the adaptor segmenter of the RNA automatic query start)
     hipStream_t stream = nullptr;
     hipStream_t stream_long = nullptr;       // the row strips of long queries run beside the wave kernels of the same batch
     hipStream_t stream_long2 = nullptr;      // ... their groups alternating between two streams (pass 2 of one under pass 1 of the next)

@@ -181,6 +181,15 @@ int sfa_select_query(sfa_event_t *events, int64_t n_events, const int16_t *raw, 
     return keep ? 1 : 0;
 }
 
+int64_t sfa_detect_query_start(const int16_t *raw, int64_t n_raw, double digitisation, double offset, double range,
+                               const sfa_event_t *events, int64_t n_events, int pore) {
+    if (!raw || n_raw <= 0 || n_events < 0 || (n_events > 0 && !events)) return -1;
+    std::vector<float> pa(static_cast<size_t>(n_raw));
+    sfa::raw_to_picoamps(raw, n_raw, digitisation, offset, range, pa.data());
+    const std::vector<sfa_event_t> ev(events, events + n_events);
+    return sfa::detect_query_start(raw, n_raw, pa.data(), ev, pore);
+}
+
 }  // extern "C"
 namespace {
 // the winner's warp path from its result row: query in DP order, columns of the strand's own array

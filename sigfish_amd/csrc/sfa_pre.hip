@@ -33,7 +33,9 @@ int sfa_align_raw_ex(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_off, c
 // raw == nullptr: the samples are already in c->e_raw (decoded on the device, sfa_align_blow5), laid out by raw_off
 static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_off, const double *scaling, int32_t n, int32_t prefix_size,
                           int32_t query_size, sfa_result_t *rows, sfa_query_info_t *info, sfa_event_t *query_events) {
-    if (prefix_size < 0) return fail(SFA_EINVAL, "sfa_align_raw: automatic query start (-p -1) needs the host stages");
+    // the reference's own checks of -p -1 (src/dtw_main.c:263-276)
+    if (prefix_size < 0 && (!(c->flag & SFA_RNA) || (c->flag & (SFA_END | SFA_INV))))
+        return fail(SFA_EINVAL, "sfa_align_raw: automatic query start (prefix_size < 0) needs an RNA context without SFA_END or SFA_INV");
     if (query_size <= 0) return fail(SFA_EINVAL, "sfa_align_raw: query_size must be positive");
     if (n == 0) return SFA_OK;
     if (!c->shards.empty()) {
@@ -77,7 +79,7 @@ static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_o
         (rc = c->e_t2.reserve(4 * (size_t)std::max<int64_t>(total, 1))) || (rc = c->e_evoff.reserve(8 * (size_t)(n + 1))) ||
         (rc = c->e_evstart.reserve(4 * (size_t)ev_total)) || (rc = c->e_evlen.reserve(4 * (size_t)ev_total)) ||
         (rc = c->e_evmean.reserve(4 * (size_t)ev_total)) || (rc = c->e_evstdv.reserve(4 * (size_t)ev_total)) ||
-        (rc = c->e_nev.reserve(4 * (size_t)n)) || (rc = c->e_qstart.reserve(8 * (size_t)n)) || (rc = c->e_qoff.reserve(8 * (size_t)(n + 1))) ||
+        (rc = c->e_nev.reserve(8 * (size_t)n)) || (rc = c->e_qstart.reserve(8 * (size_t)n)) || (rc = c->e_qoff.reserve(8 * (size_t)(n + 1))) ||
         (rc = c->e_flag.reserve(4 * (size_t)n)) || (rc = c->e_pflag.reserve(4 * (size_t)n)) || (rc = c->e_b0.reserve(4 * (size_t)n)) || (rc = c->e_b1.reserve(4 * (size_t)n)) || (rc = c->e_b2.reserve(4 * (size_t)n)))
         return rc;
     hipStream_t sp = st;
@@ -121,11 +123,32 @@ static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_o
     if (ea.use_peak_flags) hipLaunchKernelGGL(sfa::ev_peaks_spec_kernel, dim3(n), dim3(64), 0, sp, ea);  // wave per read, flags what it cannot certify
     hipLaunchKernelGGL(sfa::ev_peaks_kernel, dim3((n + 31) / 32), dim3(64), 0, sp, ea);  // two lanes per read (all reads, or the flagged ones)
     hipLaunchKernelGGL(sfa::ev_stats_kernel, dim3(n), dim3(256), 0, sp, ea);
+    // RNA automatic query start: adaptor, poly-A tail, first event behind it; e_nev[n + i] (the counts' neighbours, one copy)
+    const bool auto_start = prefix_size < 0;
+    if (auto_start) {
+        sfa::AutoArgs aa{};
+        aa.raw = c->e_raw.as<int16_t>();
+        aa.raw_off = c->e_rawoff.as<int64_t>();
+        aa.scale = c->e_scale.as<float>();
+        aa.csum = c->e_sumsq.as<int64_t>();  // (sums and t-statistics are no longer needed: ev_stats_kernel ran before)
+        aa.tmean = c->e_t1.as<float>();
+        aa.ev_off = c->e_evoff.as<int64_t>();
+        aa.ev_start = c->e_evstart.as<int32_t>();
+        aa.n_events = c->e_nev.as<int32_t>();
+        aa.start = c->e_nev.as<int32_t>() + n;
+        aa.n_reads = n;
+        aa.lo = c->pore == 2 ? 500 : 2000;  // JNNV2_RNA_RNA004_ADAPTOR / JNNV2_RNA_R9_ADAPTOR, src/jnn.h
+        aa.std_scale = c->pore == 2 ? 0.7f : 0.5f;
+        hipLaunchKernelGGL(sfa::ev_autostart_tmean_kernel, dim3(n), dim3(256), 0, sp, aa);
+        hipLaunchKernelGGL(sfa::ev_autostart_scan_kernel, lane_grid, lane_block, 0, sp, aa);
+    }
     KERNEL_TRY();
     HIP_TRY(hipEventRecord(c->eev[1], sp));
-    if ((rc = c->h_small.reserve(16 * (size_t)n))) return rc;  // page-locked: event counts, then the three raw-coordinate columns
+    // page-locked: event counts and automatic starts, then the three raw-coordinate columns
+    if ((rc = c->h_small.reserve(16 * (size_t)n))) return rc;
     int32_t *nev = c->h_small.as<int32_t>();
-    HIP_TRY(hipMemcpyAsync(nev, c->e_nev.p, 4 * (size_t)n, hipMemcpyDeviceToHost, sp));
+    const int32_t *auto_st = nev + n;
+    HIP_TRY(hipMemcpyAsync(nev, c->e_nev.p, (auto_start ? 8 : 4) * (size_t)n, hipMemcpyDeviceToHost, sp));
     HIP_TRY(hipStreamSynchronize(sp));
 
     // query windows on the host (normalise_single, src/sigfish.c:433-480); the arithmetic part runs on the device
@@ -139,6 +162,10 @@ static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_o
         if (keep) {
             if (!(c->flag & SFA_END)) {
                 s0 = prefix_size;
+                if (auto_start) {  // detect_query_start() failed: fall back to 50 events (src/sigfish.c:438-446)
+                    s0 = auto_st[i] >= 0 ? auto_st[i] : 50;
+                    if (auto_st[i] < 0) status |= 4;
+                }
                 e0 = s0 + query_size;
                 if (s0 + 25 > ne) {
                     s0 = e0 = 0;
@@ -227,7 +254,8 @@ int sfa_align_blow5(sfa_ctx_t *c, const uint8_t *records, const int64_t *rec_off
                     int32_t prefix_size, int32_t query_size, sfa_result_t *rows, sfa_query_info_t *info, sfa_read_head_t *heads,
                     sfa_event_t *query_events) {
     if (!c || n < 0 || (n > 0 && (!records || !rec_off || !rows || !info || !heads))) return fail(SFA_EINVAL, "sfa_align_blow5: bad argument");
-    if (prefix_size < 0) return fail(SFA_EINVAL, "sfa_align_blow5: automatic query start (-p -1) needs the host stages");
+    if (prefix_size < 0 && (!(c->flag & SFA_RNA) || (c->flag & (SFA_END | SFA_INV))))
+        return fail(SFA_EINVAL, "sfa_align_blow5: automatic query start (prefix_size < 0) needs an RNA context without SFA_END or SFA_INV");
     if (query_size <= 0) return fail(SFA_EINVAL, "sfa_align_blow5: query_size must be positive");
     if (n == 0) return SFA_OK;
     if (!c->shards.empty()) {

@@ -115,3 +115,94 @@ def workload(name, n_reads=None, seed=0, golden_dir=None):
     alg_bytes = int((4 * (q_off[1:] - q_off[:-1]) + 4 * strands * int(ref.ref_lengths.sum()) + 32).sum())
     meta = dict(name=name, n_reads=n, qlen=qlen, cells=cells, algorithmic_bytes=alg_bytes, truth=truth)
     return ref, flag, q, q_off, meta
+
+
+# ---- raw RNA reads for the automatic query start (-p -1: adaptor, then poly-A tail, src/jnn.c) ----------------------------
+# Calibrated on the 8 reads of tests/golden/data/sequin_rna.blow5: digitisation 2048, range 548.79 (0.268 pA per count),
+# offset -227 .. -253, transcript levels around 90 pA (raw 500 .. 730), 25 k .. 90 k samples, the start found 7 k .. 20 k
+# samples in.
+RNA_POLYA_KINDS = ("normal", "adaptor_edge", "two_low", "polya_edge", "no_adaptor", "no_polya", "polya_at_end", "n2000",
+                   "n2001", "constant", "outside", "nonfinite", "adaptor_hi")
+
+
+def make_rna_polya_reads(n_reads, seed=0, pore=0, kinds=None, body=(5_000, 40_000)):
+    """Seeded raw RNA reads [(read_id, digitisation, offset, range, sampling_rate, int16 samples)] in four parts: a leader
+    near the open level, an adaptor stretch low in raw counts, a poly-A plateau about 30 pA above the adaptor mean (noise
+    and a controlled number of out-of-band excursions), a transcript body of k-mer levels.  `kinds` (default: every kind
+    of RNA_POLYA_KINDS, "normal" weighted up) picks what each read exercises: adaptor lengths around the segmenter's
+    limits for `pore` (lo = 500 for RNA004, else 2000; hi = 200000), two low stretches closer and farther apart than
+    seg_dist, poly-A lengths around 250 with excursions around 30, no adaptor / no poly-A, a tail ending behind the last
+    event, reads of 2000 and 2001 samples, constant reads, samples outside [0, 1200], non-finite scaling."""
+    rng = np.random.default_rng(seed)
+    if kinds is None:
+        kinds = RNA_POLYA_KINDS
+        w = np.array([12.0 if k == "normal" else (0.3 if k == "adaptor_hi" else 1.0) for k in kinds])
+    else:
+        w = np.ones(len(kinds))
+    lo = 500 if pore == 2 else 2000
+    levels = kmer_levels(5, 11, 90.0, 12.0)
+    dig, rng_ = 2048.0, 548.7882690429688
+    unit = np.float32(rng_) / np.float32(dig)
+    out = []
+
+    def steps(n, mu, sd, dwell_lo=5, dwell_hi=40, noise=2.0):  # piecewise-constant pA with noise
+        d = rng.integers(dwell_lo, dwell_hi, size=n // dwell_lo + 2)
+        x = np.repeat(rng.normal(mu, sd, size=len(d)) if sd > 0 else np.full(len(d), mu), d)[:n]
+        return x + rng.normal(0, noise, size=n)
+
+    def kmer_body(n):
+        d = rng.integers(5, 40, size=n // 5 + 2)
+        return np.repeat(levels[rng.integers(0, len(levels), size=len(d))], d)[:n] + rng.normal(0, 2.0, size=n)
+
+    def polya(n, level, n_exc):
+        x = level + rng.normal(0, rng.uniform(1.0, 3.5), size=n)
+        if n_exc > 0 and n > 0:  # excursions out of the +-20 pA band, in short clusters
+            at = rng.choice(n, size=min(n_exc, n), replace=False)
+            x[at] = level + rng.choice([-1, 1], size=len(at)) * rng.uniform(22, 40, size=len(at))
+        return x
+
+    for r in range(n_reads):
+        kind = kinds[rng.choice(len(kinds), p=w / w.sum())]
+        off = float(rng.integers(-253, -226))
+        scale_rng = rng_
+        ad_lvl = rng.uniform(52, 75)
+        leader = steps(int(rng.integers(0, 3000)), rng.uniform(105, 120), 3.0)
+        ad_len = int(rng.integers(lo + 1500, lo + 9000))
+        pa_len = int(rng.integers(300, 2500))
+        n_exc = int(rng.integers(0, 25))
+        bl = int(rng.integers(*body))
+        pa = None
+        if kind == "adaptor_edge":  # the rolling mean stays low for about (adaptor - 2000 + a few hundred) samples
+            ad_len = int(rng.integers(max(lo - 500, 100), lo + 3000))
+        elif kind == "adaptor_hi":
+            ad_len = int(rng.integers(201_000, 203_500))
+            bl = int(rng.integers(3000, 8000))
+        elif kind == "polya_edge":
+            pa_len = int(rng.integers(180, 330))
+            n_exc = int(rng.integers(15, 50))
+        if kind == "two_low":  # a gap at transcript level between two adaptor-like stretches
+            gap = int(rng.integers(200, 4500))
+            a1 = steps(int(rng.integers(lo // 2, lo + 4000)), ad_lvl, 2.0)
+            pa = np.concatenate([leader, a1, kmer_body(gap), steps(ad_len, ad_lvl, 2.0), polya(pa_len, ad_lvl + 30, n_exc), kmer_body(bl)])
+        elif kind == "no_adaptor":
+            pa = np.concatenate([leader, kmer_body(bl + 8000)])
+        elif kind == "no_polya":
+            pa = np.concatenate([leader, steps(ad_len, ad_lvl, 2.0), kmer_body(bl)])
+        elif kind == "polya_at_end":
+            pa = np.concatenate([leader, steps(ad_len, ad_lvl, 2.0), polya(pa_len, ad_lvl + 30, n_exc), kmer_body(int(rng.integers(0, 40)))])
+        elif kind in ("n2000", "n2001"):
+            n = 2000 if kind == "n2000" else 2001
+            pa = np.concatenate([steps(600, ad_lvl, 2.0), polya(400, ad_lvl + 30, 0), kmer_body(n - 1000)])
+        elif kind == "constant":
+            pa = np.full(int(rng.integers(3000, 30000)), rng.uniform(60, 110))
+        else:
+            pa = np.concatenate([leader, steps(ad_len, ad_lvl, 2.0), polya(pa_len, ad_lvl + 30, n_exc), kmer_body(bl)])
+        raw = np.round(pa / unit - off)
+        if kind == "outside":  # clamp_outlier territory: spikes below 0 and above 1200 raw counts
+            at = rng.choice(len(raw), size=max(1, len(raw) // 200), replace=False)
+            raw[at] = rng.choice([-400.0, -5.0, 1250.0, 3000.0], size=len(at))
+        raw = np.clip(raw, -32768, 32767).astype(np.int16)
+        if kind == "nonfinite":  # range beyond fp32: raw_unit = inf, pA = +-inf or NaN
+            scale_rng = 1e39
+        out.append((f"polya_{seed}_{r}_{kind}", dig, off, scale_rng, 3000.0, raw))
+    return out
