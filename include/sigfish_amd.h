@@ -164,6 +164,15 @@ int sfa_align_batch_device(sfa_ctx_t *ctx, const float *d_queries, const int64_t
 int sfa_submit_batch(sfa_ctx_t *ctx, const float *queries, const int64_t *q_off, int32_t n_reads);
 int sfa_wait_batch(sfa_ctx_t *ctx, sfa_result_t *out, int32_t n_reads);
 
+/* Secondary mappings (option "secondary" = 1..4, see sfa_set_option): the candidates behind the primary in the reference's own
+ * sorted list of the 5 best per read (aln[3], aln[2], aln[1], aln[0] of update_aln, src/sigfish.c:575-626; ties: the later
+ * candidate ranks higher), of the most recently completed call (a synchronous call or sfa_wait_batch; call this before the next
+ * batch is submitted).  sec[i*4+k], k = 0 the best secondary: rid, strand, pos_st/pos_end (flipped and offset as the primary),
+ * score, score2 = the score of the next candidate below it (+inf for the last), mapq 0.  Slots beyond the option, slots whose
+ * score is not finite, and every slot of a read of more than SFA_MAX_QUERY events (the row strips keep no list), have valid = 0.
+ * No de-duplication: neighbouring windows of one locus often fill the list.  Returns SFA_EINVAL when the option is 0. */
+int sfa_secondary_rows(sfa_ctx_t *ctx, sfa_result_t *sec, int32_t n_reads);
+
 /* align_db() shaped entry: per-read event tables exactly as db_t holds them (src/sigfish.h:177-178):
  * events[i] -> sfa_event_t array of read i, qstart[i]/qend[i] the window chosen by normalise_single
  * (src/sigfish.c:479-480); reads with n_events[i]==0 are skipped.  The window means are gathered out of the 24-byte event
@@ -203,6 +212,9 @@ int sfa_align_events(sfa_ctx_t *ctx, const sfa_event_t *const *events, const int
  *     "spin_limit_ms"         default 20000: the longest a wave of a launch waits for another wave of the same launch -- pass 2 for
  *                             its quad's fill tasks, a row strip for the strip above -- before the batch fails with SFA_EKERNEL;
  *                             floors apply (about five times the longest fill task; the strips' pipeline depth)
+ *   output
+ *     "secondary"             0..4 (default 0): secondary mappings per read, returned by sfa_secondary_rows; > 0 takes the plain
+ *                             two-pass route (HBM snapshots, no column segments, pass 2 as its own launches).  Rows do not change
  *   raw-signal path
  *     "ev_parallel"           bit 0: wave-per-read prefix sums for every read whose sums are provably exact in any order (the
  *                             sequential kernel for the rest); bit 1: chunk-parallel peak picker accepted where it is certified
@@ -256,6 +268,10 @@ void sfa_znormalise(float *v, uint64_t n);
 int sfa_paf_row(char *buf, size_t cap, const sfa_result_t *r, const char *read_id, const char *rname,
                 uint64_t start_raw_idx, uint64_t end_raw_idx, uint64_t query_size, uint64_t len_raw_signal,
                 uint64_t rlength);
+/* The same with the type tag: tp = 'P' (what sfa_paf_row writes) or 'S' for a row of sfa_secondary_rows. */
+int sfa_paf_row_ex(char *buf, size_t cap, const sfa_result_t *r, const char *read_id, const char *rname,
+                   uint64_t start_raw_idx, uint64_t end_raw_idx, uint64_t query_size, uint64_t len_raw_signal,
+                   uint64_t rlength, char tp);
 
 /* ---- raw signal in, result rows out: the pre-DP stages on the GPU as well --------------------------------- */
 
@@ -350,6 +366,10 @@ int64_t sfa_detect_query_start(const int16_t *raw, int64_t n_raw, double digitis
 int sfa_sam_row(char *buf, size_t cap, const sfa_result_t *r, const char *read_id, const char *rname,
                 const sfa_event_t *events, int64_t qstart, int64_t qend, const float *ref_array, int32_t ref_len,
                 int32_t ref_st_offset, uint32_t flag);
+/* The same; secondary != 0 sets FLAG bit 256 (a row of sfa_secondary_rows). */
+int sfa_sam_row_ex(char *buf, size_t cap, const sfa_result_t *r, const char *read_id, const char *rname,
+                   const sfa_event_t *events, int64_t qstart, int64_t qend, const float *ref_array, int32_t ref_len,
+                   int32_t ref_st_offset, uint32_t flag, int secondary);
 
 /* aln_t.r2qevent_map for a result row (path_to_map, src/sigfish.c:530-571, as update_aln stores it at 610-613): what the
  * reference's own sam_str / r2qevent_map_to_ss (src/sigfish.c:663-794) consume.  The winner's warp path is rebuilt on the

@@ -135,6 +135,7 @@ class Aligner:
         in contiguous read ranges and comes back in input order; a GPU may be listed more than once."""
         self._L = _lib.load()
         self._h = C.c_void_p()
+        self._last_n = 0
         self.ref, self.flag, self.device = ref, int(flag), int(device)
         cref, keep = ref._as_c()
         if devices is None:
@@ -171,6 +172,7 @@ class Aligner:
         qo = np.ascontiguousarray(q_off, np.int64)
         n = len(qo) - 1
         out = np.zeros(n, RESULT_DTYPE)
+        self._last_n = n
         if q.size == 0:
             q = np.zeros(1, np.float32)
         _check(self._L.sfa_align_batch(self._h, q.ctypes.data_as(_lib.f32p), qo.ctypes.data_as(_lib.i64p), n,
@@ -191,6 +193,7 @@ class Aligner:
         q, qo = getattr(self, "_pending", None) or (None, np.zeros(1, np.int64))
         n = len(qo) - 1
         out = np.zeros(n, RESULT_DTYPE)
+        self._last_n = n
         try:
             _check(self._L.sfa_wait_batch(self._h, out.ctypes.data_as(C.c_void_p), n), "sfa_wait_batch")
         finally:
@@ -221,6 +224,7 @@ class Aligner:
         qs = np.ascontiguousarray(qstart, np.int64)
         qe = np.ascontiguousarray(qend, np.int64)
         out = np.zeros(n, RESULT_DTYPE)
+        self._last_n = n
         _check(self._L.sfa_align_events(self._h, ptrs, nev.ctypes.data_as(_lib.i64p), qs.ctypes.data_as(_lib.i64p),
                                         qe.ctypes.data_as(_lib.i64p), n, out.ctypes.data_as(C.c_void_p)),
                "sfa_align_events")
@@ -228,6 +232,17 @@ class Aligner:
 
     def set_option(self, key, value):
         _check(self._L.sfa_set_option(self._h, key.encode(), int(value)), f"sfa_set_option({key})")
+
+    def set_secondary(self, n):
+        """Secondary mappings per read, 0..4 (0: off, the default); read them with secondary_rows() after each call."""
+        self.set_option("secondary", n)
+
+    def secondary_rows(self, n_reads=None):
+        """The secondaries of the most recent call as RESULT_DTYPE[n_reads, 4], best first (valid = 0 for absent slots)."""
+        n = self._last_n if n_reads is None else int(n_reads)
+        out = np.zeros((n, 4), RESULT_DTYPE)
+        _check(self._L.sfa_secondary_rows(self._h, out.ctypes.data_as(C.c_void_p), n), "sfa_secondary_rows")
+        return out
 
     def set_pore(self, pore):
         """The reference's opt.pore_flag: 0 R9 (default), 1 R10, 2 RNA004 (the RNA automatic query start depends on it)."""
@@ -244,6 +259,7 @@ class Aligner:
         n = len(ro) - 1
         rows = np.zeros(n, RESULT_DTYPE)
         info = np.zeros(n, QUERY_INFO_DTYPE)
+        self._last_n = n
         if raw.size == 0:
             raw = np.zeros(1, np.int16)
         qev = np.zeros((n, query_size), EVENT_DTYPE) if return_events else None
@@ -261,6 +277,7 @@ class Aligner:
         n = len(ro) - 1
         rows = np.zeros(n, RESULT_DTYPE)
         info = np.zeros(n, QUERY_INFO_DTYPE)
+        self._last_n = n
         heads = (_lib.SfaReadHead * max(n, 1))()
         qev = np.zeros((n, query_size), EVENT_DTYPE) if return_events else None
         if rec.size == 0:
@@ -315,13 +332,13 @@ def plan_batch(q_off, job_len, ckpt_interval=0, ckpt_budget_bytes=0, lane_wideni
 EVENT_DTYPE = np.dtype([("start", "<u8"), ("length", "<f4"), ("mean", "<f4"), ("stdv", "<f4")], align=True)
 
 
-def paf_row(res, read_id, rname, start_raw, end_raw, query_size, len_raw, rlength):
-    """paf_str (src/sigfish.c:628-660) for one result row."""
+def paf_row(res, read_id, rname, start_raw, end_raw, query_size, len_raw, rlength, tp="P"):
+    """paf_str (src/sigfish.c:628-660) for one result row; tp="S" for a row of Aligner.secondary_rows()."""
     r = _lib.SfaResult(int(res["rid"]), int(res["pos_st"]), int(res["pos_end"]), float(res["score"]),
                        float(res["score2"]), int(res["strand"]), int(res["mapq"]), int(res["valid"]), 0)
     buf = C.create_string_buffer(4096)
-    n = _lib.load().sfa_paf_row(buf, 4096, C.byref(r), str(read_id).encode(), str(rname).encode(), int(start_raw),
-                                int(end_raw), int(query_size), int(len_raw), int(rlength))
+    n = _lib.load().sfa_paf_row_ex(buf, 4096, C.byref(r), str(read_id).encode(), str(rname).encode(), int(start_raw),
+                                   int(end_raw), int(query_size), int(len_raw), int(rlength), str(tp).encode()[:1])
     if n < 0:
         raise SfaError("sfa_paf_row: buffer too small")
     return buf.raw[:n].decode()
@@ -446,15 +463,15 @@ def r2qevent_map(res, events, qstart, qend, ref_array, ref_st_offset, flag):
     return out
 
 
-def sam_row(res, read_id, rname, events, qstart, qend, ref_array, ref_st_offset, flag):
-    """sam_str (src/sigfish.c:770-794) for one result row; `events` normalised as for align_events."""
+def sam_row(res, read_id, rname, events, qstart, qend, ref_array, ref_st_offset, flag, secondary=False):
+    """sam_str (src/sigfish.c:770-794) for one result row; `events` normalised as for align_events; secondary: FLAG | 256."""
     r = _lib.SfaResult(int(res["rid"]), int(res["pos_st"]), int(res["pos_end"]), float(res["score"]),
                        float(res["score2"]), int(res["strand"]), int(res["mapq"]), int(res["valid"]), 0)
     y = _f32(ref_array)
     buf = C.create_string_buffer(1 << 22)
-    n = _lib.load().sfa_sam_row(buf, len(buf), C.byref(r), str(read_id).encode(), str(rname).encode(),
-                                C.cast(events.ctypes.data, C.POINTER(_lib.SfaEvent)), int(qstart), int(qend),
-                                y.ctypes.data_as(_lib.f32p), len(y), int(ref_st_offset), int(flag))
+    n = _lib.load().sfa_sam_row_ex(buf, len(buf), C.byref(r), str(read_id).encode(), str(rname).encode(),
+                                   C.cast(events.ctypes.data, C.POINTER(_lib.SfaEvent)), int(qstart), int(qend),
+                                   y.ctypes.data_as(_lib.f32p), len(y), int(ref_st_offset), int(flag), int(bool(secondary)))
     if n < 0:
         raise SfaError(f"sfa_sam_row failed ({n})")
     return buf.raw[:n].decode()

@@ -61,6 +61,7 @@ struct Opt {
     const char *model_file = nullptr;
     const char *pore = nullptr;
     int pore_flag = 0;  // 0 r9, 1 r10, 2 rna004
+    bool secondary = false;  // --secondary yes: print the candidates behind each primary (sfa_secondary_rows)
 };
 
 double realtime() {
@@ -128,6 +129,7 @@ void help(FILE *fp, const Opt &o) {
     fprintf(fp, "   --full-ref                 map to the full reference\n");
     fprintf(fp, "   --from-end                 map the end portion of the query instead of the beginning\n");
     fprintf(fp, "   --sam                      output in SAM format\n");
+    fprintf(fp, "   --secondary STR            print secondary mappings. yes or no [no]\n");
     fprintf(fp, "   --profile-cpu=yes|no       run the stages one after the other and report Parse/Events/Normalise/DTW time [no]\n");
     fprintf(fp, "   --accel=yes|no             run the alignment on the accelerator [yes]; 'no' is an error: this build has no CPU path\n");
 }
@@ -495,7 +497,11 @@ static int dtw_run(int argc, char **argv) {
                     die("--accel=no: this build has no CPU alignment path (the stage only exists as gfx950 kernels); "
                         "run the reference binary for a CPU run, or drop the option");
                 break;
-            case 12: case 13: break;  // dead options of the reference (--secondary, --meth-model): parsed, no effect
+            case 12:  // src/dtw_main.c:207-208 parses it; here it prints the reference's own candidate list (other values: no effect)
+                if (!strcmp(optarg, "yes")) o.secondary = true;
+                else if (!strcmp(optarg, "no")) o.secondary = false;
+                break;
+            case 13: break;  // dead option of the reference (--meth-model): parsed, no effect
             case 10:
                 o.pore = optarg;
                 if (strcmp(optarg, "r9") && strcmp(optarg, "r10") && strcmp(optarg, "rna004")) die("Pore model should be r9, r10 or rna004");
@@ -556,6 +562,7 @@ static int dtw_run(int argc, char **argv) {
     }
 
     if (o.shard_n > 1 && (o.range_a > 0 || o.range_b >= 0)) die("--shard and --read-range exclude each other");
+    if (o.secondary && o.query > 2048) die("--secondary yes supports -q up to 2048");
     if (o.ranks == 0) {  // one process per DISTINCT device of the list; a device listed twice is two contexts of one process
         std::vector<int> d = o.devices;
         std::sort(d.begin(), d.end());
@@ -653,6 +660,7 @@ static int dtw_run(int argc, char **argv) {
         if (sfa_set_option(ctxs[j], "widen_below", std::max(1, 5 / per_dev)) != SFA_OK) die(sfa_last_error());
         // the pore reaches the device route's automatic query start (-p -1), as it reaches select_and_normalise on the host route
         if (sfa_set_pore(ctxs[j], o.pore_flag) != SFA_OK) die(sfa_last_error());
+        if (o.secondary && sfa_set_option(ctxs[j], "secondary", 4) != SFA_OK) die(sfa_last_error());
         // SFA_OPTS="name=value,name=value": planner / launch options of the library (sfa_set_option) for experiments from the
         // command line; rows do not depend on them (the library's test hooks are not options: refused here whatever the environment)
         if (const char *e = getenv("SFA_OPTS")) {
@@ -700,6 +708,7 @@ static int dtw_run(int argc, char **argv) {
         std::vector<const sfa_event_t *> evp;
         std::vector<int64_t> nev, qs, qe;
         std::vector<sfa_result_t> rows;
+        std::vector<sfa_result_t> sec;  // --secondary yes: [n][4] rows behind each primary, best first
         // device-side event detection: concatenated raw samples + scaling instead of event tables
         int16_t *raw = nullptr;  // page-locked (sfa_pinned_alloc), grown on demand
         size_t raw_cap = 0;
@@ -760,6 +769,10 @@ static int dtw_run(int argc, char **argv) {
         } else if (n > 0 && sfa_align_events(ctx, sl.evp.data(), sl.nev.data(), sl.qs.data(), sl.qe.data(), n, rows.data()) != SFA_OK) {
             die(std::string("alignment failed: ") + sfa_last_error());
         }
+        if (o.secondary && n > 0) {
+            sl.sec.resize(static_cast<size_t>(n) * 4);
+            if (sfa_secondary_rows(ctx, sl.sec.data(), n) != SFA_OK) die(std::string("secondary mappings: ") + sfa_last_error());
+        }
         sfa_profile_t pr{};
         if (prf && n > 0 && sfa_get_profile(ctx, &pr) != SFA_OK) die(std::string("sfa_get_profile failed: ") + sfa_last_error());
         std::lock_guard<std::mutex> lock(stat_mu);
@@ -798,17 +811,22 @@ static int dtw_run(int argc, char **argv) {
                 // the event table and the window inside it: the read's own (host events) or the window alone (device events)
                 const sfa_event_t *ev = gpu_events ? sl.qev.data() + static_cast<size_t>(i) * o.query : r.ev.data();
                 const int64_t qs = gpu_events ? 0 : r.qstart, qe = gpu_events ? sl.info[i].qend - sl.info[i].qstart : r.qend;
-                const float *y = row.strand == '+' ? fwd[row.rid].data() : rev[row.rid].data();
-                std::string buf(1 << 16, '\0');
                 const char *rid = sl.via_device ? sl.heads[i].read_id : r.rec.read_id.c_str();
-                int len = sfa_sam_row(&buf[0], buf.size(), &row, rid, contigs[row.rid].name.c_str(), ev, qs, qe, y,
-                                      ref_len[row.rid], ref_off[row.rid], o.flag);
-                if (len == SFA_ERANGE) {  // very long ss strings (full-reference alignments)
-                    buf.assign(1 << 22, '\0');
-                    len = sfa_sam_row(&buf[0], buf.size(), &row, rid, contigs[row.rid].name.c_str(), ev, qs, qe, y,
-                                      ref_len[row.rid], ref_off[row.rid], o.flag);
+                // the primary, then (--secondary yes) the candidates behind it, best first
+                for (int k = -1; k < (o.secondary ? 4 : 0); ++k) {
+                    const sfa_result_t &w = k < 0 ? row : sl.sec[static_cast<size_t>(i) * 4 + k];
+                    if (!w.valid || w.rid < 0) continue;
+                    const float *y = w.strand == '+' ? fwd[w.rid].data() : rev[w.rid].data();
+                    std::string buf(1 << 16, '\0');
+                    int len = sfa_sam_row_ex(&buf[0], buf.size(), &w, rid, contigs[w.rid].name.c_str(), ev, qs, qe, y,
+                                             ref_len[w.rid], ref_off[w.rid], o.flag, k >= 0);
+                    if (len == SFA_ERANGE) {  // very long ss strings (full-reference alignments)
+                        buf.assign(1 << 22, '\0');
+                        len = sfa_sam_row_ex(&buf[0], buf.size(), &w, rid, contigs[w.rid].name.c_str(), ev, qs, qe, y,
+                                             ref_len[w.rid], ref_off[w.rid], o.flag, k >= 0);
+                    }
+                    if (len > 0) sam_rows[i].append(buf.data(), len);
                 }
-                if (len > 0) sam_rows[i].assign(buf.data(), len);
             });
             for (int32_t i = 0; i < n; ++i) fwrite(sam_rows[i].data(), 1, sam_rows[i].size(), stdout);
         } else {
@@ -834,6 +852,14 @@ static int dtw_run(int argc, char **argv) {
                                             start_raw, end_raw, qsize, n_raw, static_cast<uint64_t>(seq_len[rows[i].rid]));
                 if (len < 0) die("PAF line too long");
                 fwrite(line.data(), 1, len, stdout);
+                for (int k = 0; k < (o.secondary ? 4 : 0); ++k) {  // the candidates behind the primary, best first: tp:A:S, mapq 0
+                    const sfa_result_t &w = sl.sec[static_cast<size_t>(i) * 4 + k];
+                    if (!w.valid || w.rid < 0) continue;
+                    const int l2 = sfa_paf_row_ex(&line[0], line.size(), &w, rid, contigs[w.rid].name.c_str(), start_raw, end_raw, qsize,
+                                                  n_raw, static_cast<uint64_t>(seq_len[w.rid]), 'S');
+                    if (l2 < 0) die("PAF line too long");
+                    fwrite(line.data(), 1, l2, stdout);
+                }
             }
         }
         fflush(stdout);

@@ -86,7 +86,7 @@ std::vector<int32_t> path_to_pairs(const WarpPath &path) {
 }
 
 std::string sam_record(const sfa_result_t &row, const WarpPath &path, const char *read_id, const char *rname, const sfa_event_t *ev,
-                       int64_t qstart, int64_t qend, bool rna) {
+                       int64_t qstart, int64_t qend, bool rna, bool secondary) {
     struct Pair {
         int32_t start, stop;
     };
@@ -147,7 +147,7 @@ std::string sam_record(const sfa_result_t &row, const WarpPath &path, const char
     const uint64_t end_raw = static_cast<uint64_t>(static_cast<float>(e1.start) + e1.length);
     const uint64_t post_st = rna ? row.pos_end : row.pos_st, post_end = rna ? row.pos_st : row.pos_end;
     char head[1024];
-    snprintf(head, sizeof head, "%s\t%d\t%s\t%ld\t%d\t%ldM\t*\t0\t0\t*\t*\tsi:Z:%ld,%ld,%ld,%ld\tss:Z:", read_id, row.strand == '+' ? 0 : 16, rname,
+    snprintf(head, sizeof head, "%s\t%d\t%s\t%ld\t%d\t%ldM\t*\t0\t0\t*\t*\tsi:Z:%ld,%ld,%ld,%ld\tss:Z:", read_id, (row.strand == '+' ? 0 : 16) | (secondary ? 256 : 0), rname,
              static_cast<long>(row.pos_st) + 1, static_cast<int>(row.mapq), static_cast<long>((qend - 1) - qstart), static_cast<long>(start_raw),
              static_cast<long>(end_raw), static_cast<long>(post_st), static_cast<long>(post_end));
     return std::string(head) + ss + "\n";

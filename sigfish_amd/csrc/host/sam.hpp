@@ -30,6 +30,6 @@ std::vector<int32_t> path_to_pairs(const WarpPath &path);
 
 // path_to_map + r2qevent_map_to_ss + sam_str (src/sigfish.c:530-571, 663-794) for one read
 std::string sam_record(const sfa_result_t &row, const WarpPath &path, const char *read_id, const char *rname, const sfa_event_t *events,
-                       int64_t qstart, int64_t qend, bool rna);
+                       int64_t qstart, int64_t qend, bool rna, bool secondary = false);  // secondary: FLAG | 256
 
 }  // namespace sfa

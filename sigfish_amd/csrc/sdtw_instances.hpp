@@ -27,4 +27,8 @@ SFA_LCK_DECL(4) SFA_LCK_DECL(8) SFA_LCK_DECL(16)
 SFA_LCKSTD_DECL(4) SFA_LCKSTD_DECL(8) SFA_LCKSTD_DECL(16)
 // the 32-row fill (snapshots in HBM) with pass 2 by ticket in the same launch: sdtw_inst_fused32.hip
 extern template __global__ void sdtw_fill_kernel<32, false, false, false, true>(const DpArgs);
+// pass 1 with the top-5 candidate lists of secondary mappings: sdtw_inst_sec16.hip / sec32.hip
+#define SFA_SEC_DECL(MR, SD) extern template __global__ void sdtw_sec_fill_kernel<MR, SD>(const DpArgs);
+SFA_FOR_MAXR(SFA_SEC_DECL, false)
+SFA_FOR_MAXR(SFA_SEC_DECL, true)
 }  // namespace sfa

@@ -146,6 +146,9 @@ struct DpArgs {
     long long spin_limit;
     int32_t debug_drop_quad;
     unsigned long long *task_times;  // -DSFA_TASK_TIMES builds only (tools/task_times.py): [task][3] start, end (100 MHz ticks), SIMD position
+    // secondary mappings (sdtw_sec_fill_kernel only): the top-5 list of every (quad, chunk, slot), [(quad*n_chunks+chunk)*4+slot][5][3]
+    // as (score bits, end, job) in the reference's aln[0] (worst) .. aln[4] (best) order
+    int32_t *p_top5;
 };
 
 // physical position of the executing wave: (xcc, se, sh, cu, simd) from HW_REG_XCC_ID / HW_REG_HW_ID, 14 bits.  Measured
@@ -315,6 +318,32 @@ struct Top2 {
         return top;
     }
 };
+
+// The whole sorted candidate list of the reference (SECONDARY_CAP = 5, src/sigfish.h:41), for secondary mappings.  One list of
+// 5 x (score bits, end, job) per read slot in LDS, touched by the owner lane once per window: the 32-row fill has no VGPRs to spare
+// for it.  aln[0] is the worst entry, aln[4] the best; the insertion is update_aln's (src/sigfish.c:575-594), so the LATER of two
+// equal candidates ranks higher and aln[4] is Top2's winner.
+constexpr int kTop5Words = 15;
+__device__ __forceinline__ void top5_init(int *t5) {
+    for (int l = 0; l < 5; ++l) {
+        t5[3 * l] = __float_as_int(INFINITY);
+        t5[3 * l + 1] = -1;
+        t5[3 * l + 2] = -1;
+    }
+}
+__device__ __forceinline__ void top5_offer(int *t5, float sc, int pos, int job) {
+    int l = 0;
+    while (l < 5 && !(sc > __int_as_float(t5[3 * l]))) ++l;
+    if (l == 0) return;
+    for (int m = 0; m + 1 < l; ++m) {
+        t5[3 * m] = t5[3 * m + 3];
+        t5[3 * m + 1] = t5[3 * m + 4];
+        t5[3 * m + 2] = t5[3 * m + 5];
+    }
+    t5[3 * (l - 1)] = __float_as_int(sc);
+    t5[3 * (l - 1) + 1] = pos;
+    t5[3 * (l - 1) + 2] = job;
+}
 
 // MIXED QUADS.  The reads of a wave used to have ONE query length (the planner grouped by length), so a ragged batch -- a few
 // hundred distinct lengths -- left most of the short reads' waves a quarter or half full.  Reads of different lengths can share
@@ -573,11 +602,11 @@ struct LdsCkpt {
 
 // One (contig,strand) sweep of a quad.  RQ >= 0: the register holding the last query row is a compile-time
 // constant (hot specialisation); RQ < 0: it is the wave-uniform value rq (indexed v_mov).
-template <int R, bool STD, int RQ, bool LCK = false, int L = 16, bool WT = false>
+template <int R, bool STD, int RQ, bool LCK = false, int L = 16, bool WT = false, bool SEC = false>
 __device__ __forceinline__ void sweep_job(const DpArgs &a, const float *yp, const int rlen, const int qlen, const int lq, const int rq,
                                           const int t_begin, const float (&x)[R], const bool lane0, Exchange &xc, Top2 &top,
                                           const int job, float *ckp, const int T, IssuePriority &pr, const MixedQuad &mq,
-                                          LdsCkpt *lck = nullptr, const bool owner = false) {
+                                          LdsCkpt *lck = nullptr, const bool owner = false, int *t5 = nullptr) {
     constexpr bool TRACK = false;  // start columns are pass 2's business (dp_step<.., TRACK = true> in trace_core)
     typename Vec<float, R>::type cv;
     typename Vec<int, R>::type sv;  // unused (cost-only), kept for dp_step's signature
@@ -756,6 +785,9 @@ __device__ __forceinline__ void sweep_job(const DpArgs &a, const float *yp, cons
             const bool ending = (endmask >> (threadIdx.x & 63)) & 1;
             // (cost-only, 16-row shapes: the window is identified by its first column)
             const bool became_best = top.offer_if(ending, wmin, CELL ? wpos : wsl, job);
+            if constexpr (SEC) {
+                if (ending && owner) top5_offer(t5, wmin, CELL ? wpos : wsl, job);
+            }
             if (LCK) {
                 const unsigned long long improved = __ballot(became_best && owner);
                 if (improved) lck->template save<R, L, WT>(improved, wmin, wsl + e_main, a.trace_margin, lq, job, a.lck_shift);
@@ -772,6 +804,9 @@ __device__ __forceinline__ void sweep_job(const DpArgs &a, const float *yp, cons
         } else {  // std_dtw: the single candidate C[n-1][m-1]
             const float cl = (RQ >= 0) ? static_cast<float>(cv[RQ >= 0 ? RQ : 0]) : static_cast<float>(cv[rq]);
             top.offer(cl, rlen - 1, job);
+            if constexpr (SEC) {
+                if (owner) top5_offer(t5, cl, rlen - 1, job);
+            }
         }
         col += wl;
     }
@@ -781,24 +816,25 @@ __device__ __forceinline__ void sweep_job(const DpArgs &a, const float *yp, cons
 
 // Dispatch on the register of the last query row: compile-time constant for the cost-only subsequence fill (worth
 // 5-20 % on the small-batch shapes, whose steps are short).
-template <int R, bool STD, bool LCK = false, int L = 16, bool WT = false, int I = 0>
+template <int R, bool STD, bool LCK = false, int L = 16, bool WT = false, int I = 0, bool SEC = false>
 __device__ __forceinline__ void sweep_dispatch(const DpArgs &a, const float *yp, int rlen, int qlen, int lq, int rq, int t_begin,
                                                const float (&x)[R], bool lane0, Exchange &xc, Top2 &top, int job, float *ckp, int T,
-                                               IssuePriority &pr, const MixedQuad &mq, LdsCkpt *lck = nullptr, bool owner = false) {
+                                               IssuePriority &pr, const MixedQuad &mq, LdsCkpt *lck = nullptr, bool owner = false,
+                                               int *t5 = nullptr) {
     if constexpr (STD || R > 16) {  // R = 32 keeps the indexed read: 32 more loop bodies are not worth the build time
-        sweep_job<R, STD, -1, LCK, L, WT>(a, yp, rlen, qlen, lq, rq, t_begin, x, lane0, xc, top, job, ckp, T, pr, mq, lck, owner);
+        sweep_job<R, STD, -1, LCK, L, WT, SEC>(a, yp, rlen, qlen, lq, rq, t_begin, x, lane0, xc, top, job, ckp, T, pr, mq, lck, owner, t5);
     } else {
         if (rq == I) {
-            sweep_job<R, STD, I, LCK, L, WT>(a, yp, rlen, qlen, lq, rq, t_begin, x, lane0, xc, top, job, ckp, T, pr, mq, lck, owner);
+            sweep_job<R, STD, I, LCK, L, WT, SEC>(a, yp, rlen, qlen, lq, rq, t_begin, x, lane0, xc, top, job, ckp, T, pr, mq, lck, owner, t5);
         } else if constexpr (I + 1 < R) {
-            sweep_dispatch<R, STD, LCK, L, WT, I + 1>(a, yp, rlen, qlen, lq, rq, t_begin, x, lane0, xc, top, job, ckp, T, pr, mq, lck, owner);
+            sweep_dispatch<R, STD, LCK, L, WT, I + 1, SEC>(a, yp, rlen, qlen, lq, rq, t_begin, x, lane0, xc, top, job, ckp, T, pr, mq, lck, owner, t5);
         }
     }
 }
 
-template <int R, int L, bool STD, bool LCK = false, bool FUSED = false>
+template <int R, int L, bool STD, bool LCK = false, bool FUSED = false, bool SEC = false>
 __device__ __forceinline__ void fill_body(const DpArgs &a, const ClassDesc cd, const int task_local, float *lds_f, int *lds_i,
-                                          float *lds_ck = nullptr) {
+                                          float *lds_ck = nullptr, int *lds_t5 = nullptr) {
     const int chunk = task_local / cd.n_quads;  // chunk-major: neighbouring waves stream the same reference
     const int quad_local = task_local - chunk * cd.n_quads;
     const int quad = cd.quad_base + quad_local;
@@ -826,6 +862,11 @@ __device__ __forceinline__ void fill_body(const DpArgs &a, const ClassDesc cd, c
 
     Top2 top;
     top.init();
+    int *t5 = nullptr;  // SEC: this read slot's candidate list (LDS)
+    if constexpr (SEC) {
+        t5 = lds_t5 + ((threadIdx.x >> 6) * 4 + slot) * kTop5Words;
+        if (g == lq && read >= 0) top5_init(t5);
+    }
 
     const int T = a.ck_shift ? (1 << a.ck_shift) : 0;
     const int64_t ck_total = T ? a.job_ck_off[a.chunk_begin[a.n_chunks]] : 0;
@@ -860,7 +901,7 @@ __device__ __forceinline__ void fill_body(const DpArgs &a, const ClassDesc cd, c
         const float *yp = a.ref + a.job_off[job] - g + t_begin;  // this lane's column at step t is t-g
         float *ckp = nullptr;
         if (T) ckp = a.ck + cd.ck_base + (static_cast<int64_t>(quad_local) * ck_total + a.job_ck_off[job]) * (ck_planes<R>() * 64) + lane;
-        sweep_dispatch<R, STD, LCK, L, FUSED>(a, yp, rlen, qlen, lq, rq, t_begin, x, lane0, xc, top, job, ckp, T, pr, mq, &lck, g == lq && read >= 0);
+        sweep_dispatch<R, STD, LCK, L, FUSED, 0, SEC>(a, yp, rlen, qlen, lq, rq, t_begin, x, lane0, xc, top, job, ckp, T, pr, mq, &lck, g == lq && read >= 0, t5);
     }
 
     if (g == lq && read >= 0) {
@@ -875,6 +916,9 @@ __device__ __forceinline__ void fill_body(const DpArgs &a, const ClassDesc cd, c
             a.p_second[o] = top.second;
             a.p_end[o] = top.end;
             a.p_job[o] = top.job;
+        }
+        if constexpr (SEC) {
+            for (int w = 0; w < kTop5Words; ++w) a.p_top5[o * kTop5Words + w] = t5[w];
         }
     }
     if (FUSED) {
@@ -1148,6 +1192,38 @@ __global__ void __launch_bounds__(256, LCK ? SFA_LCK_WAVES : (MAXR <= 16 ? SFA_F
             else                                                                         \
                 fill_body<RR, LL, STD, LCK, FUSED>(a, cd, tl, lds_f, lds_i, lds_ck);     \
         }                                                                                \
+        break;
+    switch (cd.R * 256 + cd.lanes) {
+        SFA_SHAPE(32, 64) SFA_SHAPE(32, 32) SFA_SHAPE(32, 16)
+        SFA_SHAPE(16, 64) SFA_SHAPE(16, 32) SFA_SHAPE(16, 16)
+        SFA_SHAPE(8, 64) SFA_SHAPE(8, 32) SFA_SHAPE(8, 16)
+        SFA_SHAPE(4, 64) SFA_SHAPE(4, 32)
+        SFA_SHAPE(4, 16)
+        default:
+            break;
+    }
+#undef SFA_SHAPE
+}
+
+// Pass 1 with secondary mappings: the plain two-pass fill (HBM snapshots, no segments, no pass 2 in the launch) that also keeps
+// every read's top-5 candidate list (top5_offer) and writes it to p_top5.  Its own kernel, so the fill kernels above are untouched.
+template <int MAXR, bool STD>
+// (below the plain fill's occupancy -- one wave per SIMD less, two for the 16-row shapes -- so that the list's offer code does not
+// spill into scratch: at 96 VGPRs the 16-row subsequence fill still took 12 bytes per lane)
+__global__ void __launch_bounds__(256, MAXR == 16 ? SFA_FILL_WAVES - 2 : (MAXR < 16 ? SFA_FILL_WAVES - 1 : (STD ? 1 : SFA_FILL32_WAVES - 1)))
+sdtw_sec_fill_kernel(const DpArgs a) {
+    const int task = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    __shared__ float lds_f[4 * kXchWordsPerWave];
+    __shared__ int lds_i[1];
+    __shared__ int lds_t5[4 * 4 * kTop5Words];
+    if (task >= a.n_tasks) return;  // wave-uniform
+    int ci = 0;
+    while (ci + 1 < a.n_cls && task >= a.cls[ci + 1].task_base) ++ci;
+    const ClassDesc cd = a.cls[ci];
+    const int tl = task - cd.task_base;
+#define SFA_SHAPE(RR, LL)                                                                                  \
+    case (RR) * 256 + (LL):                                                                                \
+        if constexpr (MAXR >= (RR)) fill_body<RR, LL, STD, false, false, true>(a, cd, tl, lds_f, lds_i, nullptr, lds_t5); \
         break;
     switch (cd.R * 256 + cd.lanes) {
         SFA_SHAPE(32, 64) SFA_SHAPE(32, 32) SFA_SHAPE(32, 16)
@@ -1569,7 +1645,105 @@ __device__ __attribute__((noinline)) void fused_trace_dispatch(const DpArgs *pa,
 #undef SFA_TSHAPE
 }
 
+// Secondary mappings around the plain pass 2 (sfa_align.hip): mode 1 merges the chunks' top-5 lists of every read into the winners
+// the trace kernel reads, mode 2 writes the rows of the four secondaries after it.
+struct SecArgs {
+    const int32_t *slot_of_read;  // [n_reads] quad*4+slot, or -1
+    const int32_t *p_top5;        // DpArgs::p_top5
+    const uint8_t *bad;
+    const int64_t *q_off;
+    int32_t max_query;            // as FinalizeArgs: longer reads are the row strips' (no secondaries)
+    int32_t n_reads, n_chunks;
+    int32_t *s_job;               // [5][n_reads] candidate k = the reference's aln[4 - k]; k = 0 is the primary; -1: none
+    int32_t *s_end;               // as DpArgs::w_end
+    float *s_score;
+    const int32_t *t_st;          // [5][2][n_reads] start and end columns traced for candidate k (k >= 1)
+    const int32_t *job_contig;
+    const int8_t *job_strand;
+    const int32_t *ref_len;
+    const int32_t *ref_st_offset;
+    ResultRow *sec;               // [n_reads][4] secondaries, best first
+    int32_t n_sec;                // secondaries asked for (1..4): rows of the ranks behind are valid = 0
+    int32_t mode;
+};
+
 #ifdef SFA_DEFINE_FINALIZE_KERNEL  // plain (non-template) kernels: defined in exactly one translation unit
+// update_aln on a list in registers (aln[0] worst .. aln[4] best).  The entries that are not strictly better than the candidate form
+// a prefix of the sorted list; they move down by one and the candidate takes the last place of the prefix (constant indices only)
+__device__ __forceinline__ void top5_offer_regs(float (&sc)[5], int (&en)[5], int (&jb)[5], float s, int p, int j) {
+    int l = 0;
+#pragma unroll
+    for (int m = 0; m < 5; ++m) l += !(s > sc[m]) ? 1 : 0;
+#pragma unroll
+    for (int m = 0; m < 5; ++m) {
+        const bool nxt = m + 1 < l, put = m == l - 1;
+        const int mn = m < 4 ? m + 1 : 4;
+        sc[m] = nxt ? sc[mn] : (put ? s : sc[m]);
+        en[m] = nxt ? en[mn] : (put ? p : en[m]);
+        jb[m] = nxt ? jb[mn] : (put ? j : jb[m]);
+    }
+}
+
+__global__ void __launch_bounds__(256) sdtw_sec_finalize_kernel(const SecArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_reads) return;
+    const int sl = a.slot_of_read[i];
+    const bool strips = a.max_query > 0 && a.q_off[i + 1] - a.q_off[i] > a.max_query;
+    const bool on = sl >= 0 && !a.bad[i] && !strips;
+    const int n = a.n_reads;
+    if (a.mode == 1) {
+        float sc[5];
+        int en[5], jb[5];
+#pragma unroll
+        for (int m = 0; m < 5; ++m) {
+            sc[m] = INFINITY;
+            en[m] = -1;
+            jb[m] = -1;
+        }
+        if (on) {
+            const int64_t quad = sl >> 2, slot = sl & 3;
+            for (int ch = 0; ch < a.n_chunks; ++ch) {  // chunks in processing order, each list in its own offer order (worst first)
+                const int32_t *t = a.p_top5 + ((quad * a.n_chunks + ch) * 4 + slot) * kTop5Words;
+                for (int e = 0; e < 5; ++e)
+                    if (t[3 * e + 2] >= 0) top5_offer_regs(sc, en, jb, __int_as_float(t[3 * e]), t[3 * e + 1], t[3 * e + 2]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const bool ok = jb[4 - k] >= 0 && isfinite(sc[4 - k]);
+            a.s_job[k * n + i] = ok ? jb[4 - k] : -1;
+            a.s_end[k * n + i] = ok ? en[4 - k] : -1;
+            a.s_score[k * n + i] = sc[4 - k];
+        }
+        return;
+    }
+    for (int k = 1; k < 5; ++k) {
+        ResultRow r;
+        r.rid = -1;
+        r.pos_st = -1;
+        r.pos_end = -1;
+        r.score = INFINITY;
+        r.score2 = INFINITY;
+        r.strand = 0;
+        r.mapq = 0;  // minimap2's convention for secondaries
+        r.valid = 0;
+        r.pad = 0;
+        const int job = (on && k <= a.n_sec) ? a.s_job[k * n + i] : -1;
+        if (job >= 0) {
+            r.valid = 1;
+            r.rid = a.job_contig[job];
+            r.strand = a.job_strand[job];
+            r.score = a.s_score[k * n + i];
+            r.score2 = k < 4 ? a.s_score[(k + 1) * n + i] : INFINITY;
+            const int st = a.t_st[2 * k * n + i], end = a.t_st[(2 * k + 1) * n + i];
+            const int rl = a.ref_len[r.rid], off = a.ref_st_offset[r.rid];
+            r.pos_st = ((r.strand == '+') ? st : rl - end) + off;  // src/sigfish.c:971-975
+            r.pos_end = ((r.strand == '+') ? end : rl - st) + off;
+        }
+        a.sec[static_cast<int64_t>(i) * 4 + (k - 1)] = r;
+    }
+}
+
 // one wave per (quad, job, hand-over between segment s and s+1): the state the later segment assumed against the state
 // the earlier one reached
 __global__ void __launch_bounds__(256) sdtw_verify_kernel(const DpArgs a, const int n_quads_total) {

@@ -50,6 +50,25 @@ void launch_fill(int maxr, bool std_dtw, const DpArgs &a, hipStream_t st) {  // 
 #undef SFA_FILL
 }
 
+void launch_sec_fill(int maxr, bool std_dtw, const DpArgs &a, hipStream_t st) {  // pass 1 with the top-5 lists (secondaries)
+    const dim3 grid((a.n_tasks + 3) / 4), block(256);
+#define SFA_FILL(MR)                                                                       \
+    if (std_dtw)                                                                           \
+        hipLaunchKernelGGL((sfa::sdtw_sec_fill_kernel<MR, true>), grid, block, 0, st, a);  \
+    else                                                                                   \
+        hipLaunchKernelGGL((sfa::sdtw_sec_fill_kernel<MR, false>), grid, block, 0, st, a)
+    if (maxr >= 32) {
+        SFA_FILL(32);
+    } else if (maxr >= 16) {
+        SFA_FILL(16);
+    } else if (maxr >= 8) {
+        SFA_FILL(8);
+    } else {
+        SFA_FILL(4);
+    }
+#undef SFA_FILL
+}
+
 void launch_trace(int maxr, bool std_dtw, const DpArgs &a, int32_t *out_st, hipStream_t st) {
     const dim3 grid((a.n_tasks + 3) / 4), block(256);
 #define SFA_TRACE(MR)                                                                                  \
@@ -308,13 +327,13 @@ int align_long(sfa_ctx *c, const float *d_queries, const int64_t *d_q_off, const
 // of contiguous reads that keep the interval short; slices of >= 64 Ki reads still fill the chip.  Slices run one
 // after the other (each is planned and staged on its own), so such a call is synchronous.
 
-int align_sliced(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32_t n, ResultRow *d_out, int32_t slices) {
+int align_sliced(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32_t n, ResultRow *d_out, ResultRow *d_sec, int32_t slices) {
     sfa_profile_t sum{};
     for (int32_t s = 0; s < slices; ++s) {
         const int32_t lo = static_cast<int32_t>(static_cast<int64_t>(n) * s / slices);
         const int32_t hi = static_cast<int32_t>(static_cast<int64_t>(n) * (s + 1) / slices);
         c->in_slice = true;
-        int rc = align_device(c, d_queries, q_off + lo, hi - lo, d_out + lo);  // q_off holds absolute offsets into d_queries
+        int rc = align_device(c, d_queries, q_off + lo, hi - lo, d_out + lo, d_sec ? d_sec + 4 * static_cast<int64_t>(lo) : nullptr);  // q_off holds absolute offsets into d_queries
         c->in_slice = false;
         if (rc) return rc;
         if ((rc = resolve_profile(c))) return rc;  // waits for the slice: the staging area is reused by the next one
@@ -340,8 +359,17 @@ int align_sliced(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32
 }  // namespace
 
 // Core of every align entry point: queries already in HBM, results left in HBM.
-int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32_t n, ResultRow *d_out) {
+int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32_t n, ResultRow *d_out, ResultRow *d_sec) {
     if (n == 0) return SFA_OK;
+    // secondary mappings: the plain two-pass route (HBM snapshots, no column segments, pass 2 as its own launches), whose fill keeps
+    // every read's top-5 list; the candidates behind the primary are traced by the same pass-2 kernel, one launch per rank
+    const int n_sec = static_cast<int>(c->opt_secondary);
+    const bool own_sec = n_sec > 0 && !d_sec;  // the call's own secondaries: sec_n names them once they are all enqueued
+    if (own_sec) {
+        c->sec_n = -1;  // a call that fails or returns early leaves no rows to be taken for its own
+        if (int rc = c->d_sec.reserve(4 * sizeof(ResultRow) * static_cast<size_t>(n))) return rc;
+        d_sec = c->d_sec.as<ResultRow>();
+    }
     // ---- host: plan the batch (quads, classes, chunks, checkpoint interval) -------------------------------
     sfa::PlanParams pp;
     pp.n_sims = static_cast<int64_t>(c->cu_count) * 4;
@@ -353,8 +381,8 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
     pp.widen_below = c->opt_widen_below;
     pp.column_segments = c->opt_column_segments;
     pp.segment_warm_windows = c->opt_segment_warm;
-    pp.allow_segments = !(c->flag & SFA_DTW) && !c->no_segments_once;
-    pp.lds_ckpt = static_cast<int>(c->opt_lds_ckpt);
+    pp.allow_segments = !(c->flag & SFA_DTW) && !c->no_segments_once && n_sec == 0;
+    pp.lds_ckpt = n_sec > 0 ? 0 : static_cast<int>(c->opt_lds_ckpt);
     pp.std_dtw = (c->flag & SFA_DTW) != 0;
     pp.span_sixteenths = c->span_sixteenths;
     std::vector<int32_t> long_reads;  // queries beyond the wave kernels' 2048 events: row strips, after the rest of the batch
@@ -373,7 +401,11 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
         // checkpoints at T = 512 would take about ck_bytes * T/512
         const int64_t want = (plan.ck_floats * 4 * (1ll << (plan.ck_shift - 9)) + pp.ckpt_budget_bytes - 1) / std::max<int64_t>(pp.ckpt_budget_bytes, 1);
         const int32_t slices = static_cast<int32_t>(std::min<int64_t>(want, n / c->opt_min_slice_reads));
-        if (slices > 1) return align_sliced(c, d_queries, q_off, n, d_out, slices);
+        if (slices > 1) {
+            const int rc = align_sliced(c, d_queries, q_off, n, d_out, d_sec, slices);
+            if (!rc && own_sec) c->sec_n = n;
+            return rc;
+        }
     }
 
     const int32_t n_quads = plan.n_quads, n_chunks = plan.n_chunks, n_jobs = c->n_jobs;
@@ -401,6 +433,9 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
         (rc = c->d_tst.reserve(8 * (size_t)n)) || (rc = c->d_wscore.reserve(4 * (size_t)n)))
         return rc;
     if ((rc = c->d_wchunk.reserve(4 * static_cast<size_t>(n)))) return rc;
+    if (n_sec > 0 && ((rc = c->d_p5.reserve(4 * sfa::kTop5Words * n_part)) || (rc = c->d_swin.reserve(4 * 15 * static_cast<size_t>(n))) ||
+                      (rc = c->d_sts.reserve(4 * 10 * static_cast<size_t>(n)))))
+        return rc;
     // pass 2 inside the fill launch pays when the launch has more tasks than wave slots: its tickets then come up as the fill
     // drains.  With everything resident from the start the pass-2 waves would only sit next to the fill waves and poll
     // (measured: 2 048 reads 2.9 -> 3.3 ms per batch), so small launches keep the separate pass-2 launch.  Two fills can carry
@@ -408,7 +443,7 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
     // to HBM -- write-through in that launch, because its pass-2 waves read them from whatever XCD they land on.
     const bool std_dtw = (c->flag & SFA_DTW) != 0;
     const bool fusable = plan.lds_ckpt || (plan.max_R == 32 && !std_dtw && plan.n_seg == 1 && plan.ck_shift > 0);
-    const bool fused = fusable && c->opt_fused_trace && n_quads > 0 &&
+    const bool fused = fusable && c->opt_fused_trace && n_quads > 0 && n_sec == 0 &&
                        (c->opt_fused_trace > 1 || static_cast<int64_t>(n_quads) * n_chunks > static_cast<int64_t>(c->cu_count) * 4 * SFA_LCK_WAVES);
     if (fused && (rc = c->d_args.reserve(sizeof(DpArgs)))) return rc;
     if (fused && ((rc = c->d_ticket.reserve(64)) || (rc = c->d_quaddone.reserve(4 * static_cast<size_t>(std::max(n_quads, 1)))))) return rc;
@@ -501,6 +536,7 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
         c->quad_limit_ms = da.spin_limit / 100000;
     }
     da.debug_drop_quad = static_cast<int32_t>(c->opt_debug_drop_quad);
+    da.p_top5 = n_sec > 0 ? c->d_p5.as<int32_t>() : nullptr;
 #ifdef SFA_TASK_TIMES
     if ((rc = c->d_times.reserve(24 * static_cast<size_t>(std::max(da.n_tasks, 1))))) return rc;
     da.task_times = c->d_times.as<unsigned long long>();
@@ -570,6 +606,8 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
             launch_fill_fused(plan.max_R, std_dtw, da, st);
         } else if (plan.lds_ckpt) {
             launch_fill_lck(plan.max_R, std_dtw, da, st);
+        } else if (n_sec > 0) {
+            launch_sec_fill(plan.max_R, std_dtw, da, st);
         } else {
             launch_fill(plan.max_R, std_dtw, da, st);
         }
@@ -606,6 +644,42 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
     } else {
         HIP_TRY(hipEventRecord(c->ev[3], st));
     }
+    }
+    if (n_sec > 0) {  // merge the chunks' lists, trace candidates 1..n_sec, write their rows (the long reads' rows: valid = 0)
+        sfa::SecArgs sa{};
+        sa.slot_of_read = fz.slot_of_read;
+        sa.p_top5 = da.p_top5;
+        sa.bad = fz.bad;
+        sa.q_off = fz.q_off;
+        sa.max_query = fz.max_query;
+        sa.n_reads = n;
+        sa.n_chunks = n_chunks;
+        sa.s_job = c->d_swin.as<int32_t>();
+        sa.s_end = sa.s_job + 5 * static_cast<size_t>(n);
+        sa.s_score = reinterpret_cast<float *>(sa.s_end + 5 * static_cast<size_t>(n));
+        sa.t_st = c->d_sts.as<int32_t>();
+        sa.job_contig = fz.job_contig;
+        sa.job_strand = fz.job_strand;
+        sa.ref_len = fz.ref_len;
+        sa.ref_st_offset = fz.ref_st_offset;
+        sa.sec = d_sec;
+        sa.n_sec = n_sec;
+        sa.mode = 1;
+        hipLaunchKernelGGL(sfa::sdtw_sec_finalize_kernel, fgrid, fblock, 0, st, sa);
+        KERNEL_TRY();
+        for (int k = 1; k <= n_sec && n_quads > 0; ++k) {
+            DpArgs ta = da;
+            for (int i = 0; i < ta.n_cls; ++i) ta.cls[i].task_base = ta.cls[i].quad_base;  // one task per quad
+            ta.n_tasks = n_quads;
+            ta.w_job = sa.s_job + static_cast<size_t>(k) * n;
+            ta.w_end = sa.s_end + static_cast<size_t>(k) * n;
+            ta.w_score = sa.s_score + static_cast<size_t>(k) * n;
+            launch_trace(plan.max_R, std_dtw, ta, c->d_sts.as<int32_t>() + 2 * static_cast<size_t>(k) * n, st);
+            KERNEL_TRY();
+        }
+        sa.mode = 2;
+        hipLaunchKernelGGL(sfa::sdtw_sec_finalize_kernel, fgrid, fblock, 0, st, sa);
+        KERNEL_TRY();
     }
     c->prof.fill_launches = (n_quads > 0 ? 1 : 0) + long_launches;
     c->long_pending = !long_reads.empty();
@@ -644,6 +718,7 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
             return rc2;
         }
     }
+    if (own_sec) c->sec_n = n;
     return SFA_OK;
 }
 
@@ -789,6 +864,27 @@ int sfa_wait_batch(sfa_ctx_t *c, sfa_result_t *out, int32_t n) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     memcpy(out, c->h_out.p, sizeof(sfa_result_t) * n);
     return resolve_profile(c);
+}
+
+int sfa_secondary_rows(sfa_ctx_t *c, sfa_result_t *sec, int32_t n) {
+    if (!c || n < 0 || (n > 0 && !sec)) return fail(SFA_EINVAL, "sfa_secondary_rows: bad argument");
+    if (!c->shards.empty()) {  // every entry point splits a call the same way (shard_ranges): shard r holds rows [lo_r, hi_r)
+        if (c->shards[0]->opt_secondary == 0) return fail(SFA_EINVAL, "sfa_secondary_rows: the 'secondary' option is 0");
+        std::vector<int32_t> lo;
+        shard_ranges(n, c->shards.size(), &lo);
+        return for_each_shard(c, [&](size_t r) {
+            const int32_t a = lo[r], b = lo[r + 1];
+            if (a == b) return static_cast<int>(SFA_OK);
+            return sfa_secondary_rows(c->shards[r], sec + 4 * static_cast<size_t>(a), b - a);
+        });
+    }
+    if (c->opt_secondary == 0) return fail(SFA_EINVAL, "sfa_secondary_rows: the 'secondary' option is 0");
+    if (n == 0) return SFA_OK;
+    if (c->sec_n != n) return fail(SFA_EINVAL, "sfa_secondary_rows: the last call aligned %d reads with secondaries, %d asked for", c->sec_n, n);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(sec, c->d_sec.p, 4 * sizeof(sfa_result_t) * static_cast<size_t>(n), hipMemcpyDeviceToHost));
+    return SFA_OK;
 }
 
 int sfa_align_batch(sfa_ctx_t *c, const float *queries, const int64_t *q_off, int32_t n, sfa_result_t *out) {

@@ -254,6 +254,9 @@ int sfa_set_option(sfa_ctx_t *c, const char *key, int64_t value) {
     } else if (k == "lds_ckpt") {
         if (value < 0 || value > 2) return fail(SFA_EINVAL, "lds_ckpt must be 0 (off), 1 (where shapes and batch size suit) or 2 (wherever the shapes allow)");
         c->opt_lds_ckpt = value;
+    } else if (k == "secondary") {
+        if (value < 0 || value > 4) return fail(SFA_EINVAL, "secondary must be 0..4 (secondary mappings per read)");
+        c->opt_secondary = value;
     } else if (k == "prio_unit") {
         if (value < 0 || value > (1 << 28)) return fail(SFA_EINVAL, "prio_unit must be 0 (off) .. 2^28");
         c->opt_prio_unit = value;

@@ -204,6 +204,7 @@ struct sfa_ctx {
     int64_t opt_waves_per_simd = 6;          // target occupancy used when chunking the job list
     int64_t opt_fused_trace = 1;             // 1: pass 2 rides in the fill launch as trailing tickets (fills the drain) where the launch has more tasks than wave slots; 2: always; 0: own launch
     int64_t opt_lds_ckpt = 1;                // 1: rolling checkpoints in LDS where the batch's shapes allow (R <= 16, sDTW); 0: all snapshots to HBM
+    int64_t opt_secondary = 0;               // secondary mappings per read, 0..4 (sfa_secondary_rows); > 0 takes the plain two-pass route
     int64_t opt_prio_unit = 2048;            // longest-remaining-first issue priority of the fill: columns per level, 0 = off
     int32_t span_sixteenths = 0;             // pass 2's head start on the HBM-snapshot route follows the spans of the previous batch's alignments: sixteenths of the query length (0: not known yet -> a whole query length)
     int64_t quad_limit_ms = 0, strip_limit_ms = 0;  // the limits the last batch's waits actually ran with (floors applied), for the error messages
@@ -243,6 +244,8 @@ struct sfa_ctx {
     DevBuf d_bestrec, d_beste, d_gbest, d_wchunk;  // LDS-checkpoint fill: records of the best windows, their step, per-read best score, winning chunk
     DevBuf d_bad, d_badcount;  // sdtw_screen_kernel: per-read flag, number of flagged reads
     PinBuf h_badcount;
+    DevBuf d_p5, d_swin, d_sts, d_sec;  // secondary mappings: top-5 partials, merged candidates, their traced columns, rows [n][4]
+    int32_t sec_n = -1;   // reads of the last call whose secondaries d_sec holds
     DevBuf d_started;     // counter of the fill's tasks that have begun (IssuePriority)
     DevBuf d_times;       // -DSFA_TASK_TIMES builds: start / end / SIMD position of every wave-task of the last fill
     int64_t n_times = 0;
@@ -260,7 +263,8 @@ struct sfa_ctx {
 namespace sfa {
 int resolve_profile(sfa_ctx *c);  // sfa_align.hip: timers + error words of the batch submitted last (waits for it)
 // core of every align entry point: queries already in HBM, results left in HBM (sfa_align.hip)
-int align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32_t n, struct ResultRow *d_out);
+int align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32_t n, struct ResultRow *d_out,
+                 struct ResultRow *d_sec = nullptr);  // d_sec: rows of the secondaries (nullptr: the context's d_sec, when the option is on)
 // contiguous read range of shard r: [r*n/G, (r+1)*n/G)
 inline void shard_ranges(int32_t n, size_t g, std::vector<int32_t> *lo) {
     lo->resize(g + 1);

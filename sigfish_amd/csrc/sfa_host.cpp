@@ -139,15 +139,21 @@ int sfa_plan_batch(const int64_t *q_off, int32_t n_reads, const int32_t *job_len
 int sfa_paf_row(char *buf, size_t cap, const sfa_result_t *r, const char *read_id, const char *rname,
                 uint64_t start_raw_idx, uint64_t end_raw_idx, uint64_t query_size, uint64_t len_raw_signal,
                 uint64_t rlength) {
+    return sfa_paf_row_ex(buf, cap, r, read_id, rname, start_raw_idx, end_raw_idx, query_size, len_raw_signal, rlength, 'P');
+}
+
+int sfa_paf_row_ex(char *buf, size_t cap, const sfa_result_t *r, const char *read_id, const char *rname,
+                   uint64_t start_raw_idx, uint64_t end_raw_idx, uint64_t query_size, uint64_t len_raw_signal,
+                   uint64_t rlength, char tp) {
     // src/sigfish.c:634-635: both in fp32; query_size converts u64 -> float
     const float block_len = static_cast<float>(r->pos_end - r->pos_st);
     const float prod = r->score * block_len;
     const float residue = block_len - prod / static_cast<float>(query_size);
-    const int n = snprintf(buf, cap, "%s\t%ld\t%ld\t%ld\t%c\t%s\t%d\t%d\t%d\t%d\t%d\t%d\ttp:A:P\td1:f:%.2f\td2:f:%.2f\n", read_id,
+    const int n = snprintf(buf, cap, "%s\t%ld\t%ld\t%ld\t%c\t%s\t%d\t%d\t%d\t%d\t%d\t%d\ttp:A:%c\td1:f:%.2f\td2:f:%.2f\n", read_id,
                            static_cast<long>(len_raw_signal), static_cast<long>(start_raw_idx), static_cast<long>(end_raw_idx),
                            static_cast<char>(r->strand), rname, static_cast<int>(rlength), r->pos_st, r->pos_end,
                            static_cast<int>(std::round(static_cast<double>(residue))),
-                           static_cast<int>(std::round(static_cast<double>(block_len))), static_cast<int>(r->mapq),
+                           static_cast<int>(std::round(static_cast<double>(block_len))), static_cast<int>(r->mapq), tp,
                            static_cast<double>(r->score), static_cast<double>(r->score2));
     if (n < 0 || static_cast<size_t>(n) >= cap) return -1;
     return n;
@@ -225,11 +231,17 @@ int32_t sfa_r2qevent_map(const sfa_result_t *r, const sfa_event_t *events, int64
 
 int sfa_sam_row(char *buf, size_t cap, const sfa_result_t *r, const char *read_id, const char *rname, const sfa_event_t *events,
                 int64_t qstart, int64_t qend, const float *ref_array, int32_t ref_len, int32_t ref_st_offset, uint32_t flag) {
+    return sfa_sam_row_ex(buf, cap, r, read_id, rname, events, qstart, qend, ref_array, ref_len, ref_st_offset, flag, 0);
+}
+
+int sfa_sam_row_ex(char *buf, size_t cap, const sfa_result_t *r, const char *read_id, const char *rname, const sfa_event_t *events,
+                   int64_t qstart, int64_t qend, const float *ref_array, int32_t ref_len, int32_t ref_st_offset, uint32_t flag,
+                   int secondary) {
     if (!buf || !r || !read_id || !rname || !events || !ref_array || qend <= qstart || !r->valid || r->rid < 0) return SFA_EINVAL;
     const bool rna = (flag & SFA_RNA) != 0;
     const sfa::WarpPath path = path_of_row(r, events, qstart, qend, ref_array, ref_len, ref_st_offset, flag);
     if (path.px.empty()) return SFA_EINVAL;
-    const std::string line = sfa::sam_record(*r, path, read_id, rname, events, qstart, qend, rna);
+    const std::string line = sfa::sam_record(*r, path, read_id, rname, events, qstart, qend, rna, secondary != 0);
     if (line.size() + 1 > cap) return SFA_ERANGE;
     memcpy(buf, line.c_str(), line.size() + 1);
     return static_cast<int>(line.size());
