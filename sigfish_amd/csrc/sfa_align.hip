@@ -10,132 +10,37 @@
 
 using sfa::DpArgs;
 using sfa::FinalizeArgs;
+using sfa::Route;
+using sfa::SecArgs;
 using sfa::ResultRow;
 using sfa::align_device;
 using sfa::for_each_shard;
+using sfa::for_each_shard_range;
 using sfa::resolve_profile;
-using sfa::shard_ranges;
 
 namespace {
 
 static_assert(sizeof(ResultRow) == sizeof(sfa_result_t), "result row layout");
 
-void launch_fill(int maxr, bool std_dtw, const DpArgs &a, hipStream_t st) {  // snapshots in HBM, pass 2 as its own launch
-    const dim3 grid((a.n_tasks + 3) / 4), block(256);
-    if (a.n_seg > 1) {  // column segments (subsequence DTW, small batches): the SEG kernels
-        if (maxr >= 32)
-            hipLaunchKernelGGL((sfa::sdtw_fill_kernel<32, false, true>), grid, block, 0, st, a);
-        else if (maxr >= 16)
-            hipLaunchKernelGGL((sfa::sdtw_fill_kernel<16, false, true>), grid, block, 0, st, a);
-        else if (maxr >= 8)
-            hipLaunchKernelGGL((sfa::sdtw_fill_kernel<8, false, true>), grid, block, 0, st, a);
-        else
-            hipLaunchKernelGGL((sfa::sdtw_fill_kernel<4, false, true>), grid, block, 0, st, a);
-        return;
+// f(std::integral_constant<int, R>()) for the rows-per-lane class R (4, 8, 16, 32; at most Cap) of a batch whose widest
+// class has maxr rows per lane
+template <int Cap, typename F>
+void by_rows(int maxr, F f) {
+    if constexpr (Cap >= 32) {
+        if (maxr >= 32) return f(std::integral_constant<int, 32>());
     }
-#define SFA_FILL(MR)                                                                     \
-    if (std_dtw)                                                                         \
-        hipLaunchKernelGGL((sfa::sdtw_fill_kernel<MR, true>), grid, block, 0, st, a);    \
-    else                                                                                 \
-        hipLaunchKernelGGL((sfa::sdtw_fill_kernel<MR, false>), grid, block, 0, st, a)
-    if (maxr >= 32) {
-        SFA_FILL(32);
-    } else if (maxr >= 16) {
-        SFA_FILL(16);
-    } else if (maxr >= 8) {
-        SFA_FILL(8);
-    } else {
-        SFA_FILL(4);
-    }
-#undef SFA_FILL
+    if (maxr >= 16) return f(std::integral_constant<int, 16>());
+    if (maxr >= 8) return f(std::integral_constant<int, 8>());
+    f(std::integral_constant<int, 4>());
 }
 
-void launch_sec_fill(int maxr, bool std_dtw, const DpArgs &a, hipStream_t st) {  // pass 1 with the top-5 lists (secondaries)
-    const dim3 grid((a.n_tasks + 3) / 4), block(256);
-#define SFA_FILL(MR)                                                                       \
-    if (std_dtw)                                                                           \
-        hipLaunchKernelGGL((sfa::sdtw_sec_fill_kernel<MR, true>), grid, block, 0, st, a);  \
-    else                                                                                   \
-        hipLaunchKernelGGL((sfa::sdtw_sec_fill_kernel<MR, false>), grid, block, 0, st, a)
-    if (maxr >= 32) {
-        SFA_FILL(32);
-    } else if (maxr >= 16) {
-        SFA_FILL(16);
-    } else if (maxr >= 8) {
-        SFA_FILL(8);
-    } else {
-        SFA_FILL(4);
-    }
-#undef SFA_FILL
-}
-
-void launch_trace(int maxr, bool std_dtw, const DpArgs &a, int32_t *out_st, hipStream_t st) {
-    const dim3 grid((a.n_tasks + 3) / 4), block(256);
-#define SFA_TRACE(MR)                                                                                  \
-    if (std_dtw)                                                                                       \
-        hipLaunchKernelGGL((sfa::sdtw_trace_kernel<MR, true>), grid, block, 0, st, a, out_st);         \
-    else                                                                                               \
-        hipLaunchKernelGGL((sfa::sdtw_trace_kernel<MR, false>), grid, block, 0, st, a, out_st)
-    if (maxr >= 32) {
-        SFA_TRACE(32);
-    } else if (maxr >= 16) {
-        SFA_TRACE(16);
-    } else if (maxr >= 8) {
-        SFA_TRACE(8);
-    } else {
-        SFA_TRACE(4);
-    }
-#undef SFA_TRACE
-}
-
-// the variants with rolling checkpoints in LDS (cost-only fill, R <= 16; std_dtw: the sparse HBM store alone)
-#define SFA_LCK_LAUNCH(KERNEL, ...)                                                       \
-    do {                                                                                  \
-        if (maxr >= 16)                                                                   \
-            hipLaunchKernelGGL((KERNEL(16)), grid, block, 0, st, __VA_ARGS__);            \
-        else if (maxr >= 8)                                                               \
-            hipLaunchKernelGGL((KERNEL(8)), grid, block, 0, st, __VA_ARGS__);             \
-        else                                                                              \
-            hipLaunchKernelGGL((KERNEL(4)), grid, block, 0, st, __VA_ARGS__);             \
-    } while (0)
-void launch_fill_lck(int maxr, bool std_dtw, const DpArgs &a, hipStream_t st) {
-    const dim3 grid((a.n_tasks + 3) / 4), block(256);
-#define K_(MR) sfa::sdtw_fill_kernel<MR, false, false, true>
-#define KS_(MR) sfa::sdtw_fill_kernel<MR, true, false, true>
+// f(std::true_type()) for --dtw-std (the kernels' STD argument), else f(std::false_type())
+template <typename F>
+void by_std(bool std_dtw, F f) {
     if (std_dtw)
-        SFA_LCK_LAUNCH(KS_, a);
+        f(std::true_type());
     else
-        SFA_LCK_LAUNCH(K_, a);
-#undef K_
-#undef KS_
-}
-
-void launch_fill_fused(int maxr, bool std_dtw, const DpArgs &a, hipStream_t st) {  // fill tasks + one pass-2 ticket per quad: one wave per ticket
-    const dim3 grid(static_cast<unsigned>((a.n_tasks + 3) / 4 + (a.n_quads_total + 3) / 4)), block(256);
-    if (maxr >= 32) {  // the 32-row fill keeps its snapshots in HBM (write-through: its pass-2 waves read them in the same launch)
-        hipLaunchKernelGGL((sfa::sdtw_fill_kernel<32, false, false, false, true>), grid, block, 0, st, a);
-        return;
-    }
-#define K_(MR) sfa::sdtw_fill_kernel<MR, false, false, true, true>
-#define KS_(MR) sfa::sdtw_fill_kernel<MR, true, false, true, true>
-    if (std_dtw)
-        SFA_LCK_LAUNCH(KS_, a);
-    else
-        SFA_LCK_LAUNCH(K_, a);
-#undef K_
-#undef KS_
-}
-
-void launch_trace_lck(int maxr, bool std_dtw, const DpArgs &a, int32_t *out_st, hipStream_t st) {
-    const dim3 grid((a.n_tasks + 3) / 4), block(256);
-#define K_(MR) sfa::sdtw_trace_kernel<MR, false, true>
-#define KS_(MR) sfa::sdtw_trace_kernel<MR, true, true>
-    if (std_dtw)
-        SFA_LCK_LAUNCH(KS_, a, out_st);
-    else
-        SFA_LCK_LAUNCH(K_, a, out_st);
-#undef K_
-#undef KS_
+        f(std::false_type());
 }
 
 // Reads of more than SFA_MAX_QUERY events: row strips (sdtw_strips.hpp).  Pass 1, one wave per (read, job, strip), sweeps the
@@ -297,19 +202,14 @@ int align_long(sfa_ctx *c, const float *d_queries, const int64_t *d_q_off, const
             sa.task_times = c->d_ltimes.as<unsigned long long>();
             c->n_ltimes = waves;
 #endif
-            if (std_dtw)
-                hipLaunchKernelGGL((sfa::sdtw_strip_pipe_kernel<true>), gridp, block, 0, st, sa);
-            else
-                hipLaunchKernelGGL((sfa::sdtw_strip_pipe_kernel<false>), gridp, block, 0, st, sa);
+            by_std(std_dtw, [&](auto S) { hipLaunchKernelGGL((sfa::sdtw_strip_pipe_kernel<S>), gridp, block, 0, st, sa); });
         }
         KERNEL_TRY();
         fa.mode = 1;
         hipLaunchKernelGGL(sfa::sdtw_strip_finalize_kernel, fgrid, fblock, 0, st, fa);
         KERNEL_TRY();
-        if (std_dtw)  // pass 2: strip by strip from the last one upwards
-            hipLaunchKernelGGL((sfa::sdtw_strip_chain_kernel<true>), grid2, block, 0, st, sa);
-        else
-            hipLaunchKernelGGL((sfa::sdtw_strip_chain_kernel<false>), grid2, block, 0, st, sa);
+        // pass 2: strip by strip from the last one upwards
+        by_std(std_dtw, [&](auto S) { hipLaunchKernelGGL((sfa::sdtw_strip_chain_kernel<S>), grid2, block, 0, st, sa); });
         KERNEL_TRY();
         fa.mode = 2;
         hipLaunchKernelGGL(sfa::sdtw_strip_finalize_kernel, fgrid, fblock, 0, st, fa);
@@ -356,21 +256,12 @@ int align_sliced(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32
     return SFA_OK;
 }
 
-}  // namespace
+// ---- one batch of the wave kernels: plan -> route -> staging and scratch -> argument blocks -> launches -------------------
 
-// Core of every align entry point: queries already in HBM, results left in HBM.
-int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32_t n, ResultRow *d_out, ResultRow *d_sec) {
-    if (n == 0) return SFA_OK;
-    // secondary mappings: the plain two-pass route (HBM snapshots, no column segments, pass 2 as its own launches), whose fill keeps
-    // every read's top-5 list; the candidates behind the primary are traced by the same pass-2 kernel, one launch per rank
-    const int n_sec = static_cast<int>(c->opt_secondary);
-    const bool own_sec = n_sec > 0 && !d_sec;  // the call's own secondaries: sec_n names them once they are all enqueued
-    if (own_sec) {
-        c->sec_n = -1;  // a call that fails or returns early leaves no rows to be taken for its own
-        if (int rc = c->d_sec.reserve(4 * sizeof(ResultRow) * static_cast<size_t>(n))) return rc;
-        d_sec = c->d_sec.as<ResultRow>();
-    }
-    // ---- host: plan the batch (quads, classes, chunks, checkpoint interval) -------------------------------
+bool fused(Route r) { return r == Route::LdsFused || r == Route::Fused32; }  // pass 2 rides in the fill launch
+bool lds(Route r) { return r == Route::Lds || r == Route::LdsFused; }        // the fill keeps its checkpoints in LDS
+
+sfa::PlanParams plan_params(const sfa_ctx *c) {
     sfa::PlanParams pp;
     pp.n_sims = static_cast<int64_t>(c->cu_count) * 4;
     pp.waves_per_simd = c->opt_waves_per_simd;
@@ -381,99 +272,100 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
     pp.widen_below = c->opt_widen_below;
     pp.column_segments = c->opt_column_segments;
     pp.segment_warm_windows = c->opt_segment_warm;
-    pp.allow_segments = !(c->flag & SFA_DTW) && !c->no_segments_once && n_sec == 0;
-    pp.lds_ckpt = n_sec > 0 ? 0 : static_cast<int>(c->opt_lds_ckpt);
     pp.std_dtw = (c->flag & SFA_DTW) != 0;
     pp.span_sixteenths = c->span_sixteenths;
-    std::vector<int32_t> long_reads;  // queries beyond the wave kernels' 2048 events: row strips, after the rest of the batch
-    int64_t long_events = 0, long_max = 0;
-    for (int32_t i = 0; i < n; ++i)
-        if (q_off[i + 1] - q_off[i] > sfa::kMaxQuery) {
-            long_reads.push_back(i);
-            long_events += q_off[i + 1] - q_off[i];
-            long_max = std::max<int64_t>(long_max, q_off[i + 1] - q_off[i]);
-        }
-    pp.skip_long = !long_reads.empty();
-    sfa::BatchPlan &plan = c->plan;  // kept with the context: its vectors are reused by every batch
-    std::string perr;
-    if (int rc = sfa::plan_batch(q_off, n, c->h_job_len, c->total_cols, pp, &plan, &perr)) return fail(rc, "%s", perr.c_str());
-    if (!c->in_slice && c->opt_ckpt_interval == 0 && plan.ck_shift > 9 && n >= 2 * c->opt_min_slice_reads) {
-        // checkpoints at T = 512 would take about ck_bytes * T/512
-        const int64_t want = (plan.ck_floats * 4 * (1ll << (plan.ck_shift - 9)) + pp.ckpt_budget_bytes - 1) / std::max<int64_t>(pp.ckpt_budget_bytes, 1);
-        const int32_t slices = static_cast<int32_t>(std::min<int64_t>(want, n / c->opt_min_slice_reads));
-        if (slices > 1) {
-            const int rc = align_sliced(c, d_queries, q_off, n, d_out, d_sec, slices);
-            if (!rc && own_sec) c->sec_n = n;
-            return rc;
-        }
-    }
+    // what follows from the route: secondaries take the plain two-pass route (no LDS checkpoints, no column segments); std_dtw
+    // has no column segments (its first row is cumulative: no finite memory), nor has the re-run of a batch whose hand-overs failed
+    pp.allow_segments = !pp.std_dtw && !c->no_segments_once && c->opt_secondary == 0;
+    pp.lds_ckpt = c->opt_secondary > 0 ? 0 : static_cast<int>(c->opt_lds_ckpt);
+    return pp;
+}
 
+struct LongReads {  // queries beyond the wave kernels' 2048 events: row strips, beside the rest of the batch
+    std::vector<int32_t> reads;
+    int64_t events = 0, max = 0;
+};
+
+// staging layout: q_off[n+1] (at 0) | order[4*n_quads] | quad_qlen[n_quads] | slot[n] | chunk_begin[n_chunks+1] | job_ck_off[n_jobs+1]
+struct Staging {
+    size_t order, qq, slot, chunk, ckoff, bytes;
+    Staging(int32_t n, const sfa::BatchPlan &p, int32_t n_jobs) {
+        order = sizeof(int64_t) * (n + 1);
+        qq = order + sizeof(int32_t) * 4 * std::max(p.n_quads, 1);
+        slot = qq + sizeof(int32_t) * std::max(p.n_quads, 1);
+        chunk = slot + sizeof(int32_t) * n;
+        ckoff = chunk + sizeof(int32_t) * (p.n_chunks + 1);
+        bytes = ckoff + sizeof(int32_t) * (n_jobs + 1);
+    }
+};
+
+// the plan into the page-locked staging area, and every scratch buffer of the batch
+int stage_and_reserve(sfa_ctx *c, const int64_t *q_off, int32_t n, Route route, const Staging &sg) {
+    const sfa::BatchPlan &plan = c->plan;
     const int32_t n_quads = plan.n_quads, n_chunks = plan.n_chunks, n_jobs = c->n_jobs;
-    // staging layout: q_off[n+1] | order[4*n_quads] | quad_qlen[n_quads] | slot[n] | chunk_begin[n_chunks+1] | job_ck_off[n_jobs+1]
-    const size_t o_qoff = 0;
-    const size_t o_order = o_qoff + sizeof(int64_t) * (n + 1);
-    const size_t o_qq = o_order + sizeof(int32_t) * 4 * std::max(n_quads, 1);
-    const size_t o_slot = o_qq + sizeof(int32_t) * std::max(n_quads, 1);
-    const size_t o_chunk = o_slot + sizeof(int32_t) * n;
-    const size_t o_ckoff = o_chunk + sizeof(int32_t) * (n_chunks + 1);
-    const size_t stage_bytes = o_ckoff + sizeof(int32_t) * (n_jobs + 1);
     int rc;
-    if ((rc = c->h_stage.reserve(stage_bytes)) || (rc = c->d_stage.reserve(stage_bytes))) return rc;
+    if ((rc = c->h_stage.reserve(sg.bytes)) || (rc = c->d_stage.reserve(sg.bytes))) return rc;
     char *hs = c->h_stage.as<char>();
-    memcpy(hs + o_qoff, q_off, sizeof(int64_t) * (n + 1));
-    memcpy(hs + o_order, plan.order.data(), sizeof(int32_t) * plan.order.size());
-    memcpy(hs + o_qq, plan.quad_qlen.data(), sizeof(int32_t) * plan.quad_qlen.size());
-    memcpy(hs + o_slot, plan.slot_of_read.data(), sizeof(int32_t) * n);
-    memcpy(hs + o_chunk, plan.chunk_begin.data(), sizeof(int32_t) * (n_chunks + 1));
-    memcpy(hs + o_ckoff, plan.job_ck_off.data(), sizeof(int32_t) * (n_jobs + 1));
+    memcpy(hs, q_off, sizeof(int64_t) * (n + 1));
+    memcpy(hs + sg.order, plan.order.data(), sizeof(int32_t) * plan.order.size());
+    memcpy(hs + sg.qq, plan.quad_qlen.data(), sizeof(int32_t) * plan.quad_qlen.size());
+    memcpy(hs + sg.slot, plan.slot_of_read.data(), sizeof(int32_t) * n);
+    memcpy(hs + sg.chunk, plan.chunk_begin.data(), sizeof(int32_t) * (n_chunks + 1));
+    memcpy(hs + sg.ckoff, plan.job_ck_off.data(), sizeof(int32_t) * (n_jobs + 1));
 
     const size_t n_part = static_cast<size_t>(std::max(n_quads, 1)) * n_chunks * 4;
     if ((rc = c->d_pbest.reserve(4 * n_part)) || (rc = c->d_pend.reserve(4 * n_part)) || (rc = c->d_pjob.reserve(4 * n_part)) ||
         (rc = c->d_psecond.reserve(4 * n_part)) || (rc = c->d_wjob.reserve(4 * (size_t)n)) || (rc = c->d_wend.reserve(4 * (size_t)n)) ||
         (rc = c->d_tst.reserve(8 * (size_t)n)) || (rc = c->d_wscore.reserve(4 * (size_t)n)))
         return rc;
-    if ((rc = c->d_wchunk.reserve(4 * static_cast<size_t>(n)))) return rc;
-    if (n_sec > 0 && ((rc = c->d_p5.reserve(4 * sfa::kTop5Words * n_part)) || (rc = c->d_swin.reserve(4 * 15 * static_cast<size_t>(n))) ||
-                      (rc = c->d_sts.reserve(4 * 10 * static_cast<size_t>(n)))))
+    if ((rc = c->d_wchunk.reserve(4 * static_cast<size_t>(n))) || (rc = c->d_started.reserve(64))) return rc;
+    if (c->opt_secondary > 0 && ((rc = c->d_p5.reserve(4 * sfa::kTop5Words * n_part)) || (rc = c->d_swin.reserve(4 * 15 * static_cast<size_t>(n))) ||
+                                 (rc = c->d_sts.reserve(4 * 10 * static_cast<size_t>(n)))))
         return rc;
-    // pass 2 inside the fill launch pays when the launch has more tasks than wave slots: its tickets then come up as the fill
-    // drains.  With everything resident from the start the pass-2 waves would only sit next to the fill waves and poll
-    // (measured: 2 048 reads 2.9 -> 3.3 ms per batch), so small launches keep the separate pass-2 launch.  Two fills can carry
-    // tickets: the LDS-checkpoint fill (R <= 16; std_dtw: its sparse HBM store) and the 32-row subsequence fill, whose snapshots go
-    // to HBM -- write-through in that launch, because its pass-2 waves read them from whatever XCD they land on.
-    const bool std_dtw = (c->flag & SFA_DTW) != 0;
-    const bool fusable = plan.lds_ckpt || (plan.max_R == 32 && !std_dtw && plan.n_seg == 1 && plan.ck_shift > 0);
-    const bool fused = fusable && c->opt_fused_trace && n_quads > 0 && n_sec == 0 &&
-                       (c->opt_fused_trace > 1 || static_cast<int64_t>(n_quads) * n_chunks > static_cast<int64_t>(c->cu_count) * 4 * SFA_LCK_WAVES);
-    if (fused && (rc = c->d_args.reserve(sizeof(DpArgs)))) return rc;
-    if (fused && ((rc = c->d_ticket.reserve(64)) || (rc = c->d_quaddone.reserve(4 * static_cast<size_t>(std::max(n_quads, 1)))))) return rc;
-    if (plan.lds_ckpt && ((rc = c->d_bestrec.reserve(sizeof(float) * sfa::kLdsCkPlanes * 64 * n_part / 4)) || (rc = c->d_beste.reserve(4 * n_part)) ||
-                          (rc = c->d_gbest.reserve(4 * static_cast<size_t>(n)))))
+    if (fused(route) && ((rc = c->d_args.reserve(sizeof(DpArgs))) || (rc = c->d_ticket.reserve(64)) ||
+                         (rc = c->d_quaddone.reserve(4 * static_cast<size_t>(std::max(n_quads, 1))))))
+        return rc;
+    if (lds(route) && ((rc = c->d_bestrec.reserve(sizeof(float) * sfa::kLdsCkPlanes * 64 * n_part / 4)) || (rc = c->d_beste.reserve(4 * n_part)) ||
+                       (rc = c->d_gbest.reserve(4 * static_cast<size_t>(n)))))
         return rc;
     if ((rc = c->d_bad.reserve(static_cast<size_t>(n))) || (rc = c->d_badcount.reserve(256)) || (rc = c->h_badcount.reserve(256))) return rc;
     if (plan.ck_floats > 0 && (rc = c->d_ck.reserve(sizeof(float) * plan.ck_floats))) return rc;
-    const int32_t verify_planes = plan.max_R + 1;
-    if (plan.n_seg > 1) {
-        const size_t vbytes = sizeof(float) * 64 * verify_planes * 2 * static_cast<size_t>(plan.n_seg) * n_jobs * std::max(n_quads, 1);
-        if ((rc = c->d_verify.reserve(vbytes)) || (rc = c->d_segfail.reserve(4 * static_cast<size_t>(std::max(n_quads, 1)))) ||
-            (rc = c->h_flags.reserve(4 * static_cast<size_t>(std::max(n_quads, 1)))))
+    if (route == Route::Segments) {
+        const size_t vbytes = sizeof(float) * 64 * (plan.max_R + 1) * 2 * static_cast<size_t>(plan.n_seg) * n_jobs * n_quads;
+        if ((rc = c->d_verify.reserve(vbytes)) || (rc = c->d_segfail.reserve(4 * static_cast<size_t>(n_quads))) ||
+            (rc = c->h_flags.reserve(4 * static_cast<size_t>(n_quads))))
             return rc;
     }
+#ifdef SFA_TASK_TIMES
+    if ((rc = c->d_times.reserve(24 * static_cast<size_t>(std::max(n_quads * n_chunks, 1))))) return rc;
+    c->n_times = n_quads * n_chunks;
+#endif
+    return SFA_OK;
+}
 
-    hipStream_t st = c->stream;
-    HIP_TRY(hipMemcpyAsync(c->d_stage.p, hs, stage_bytes, hipMemcpyHostToDevice, st));
-    char *ds = c->d_stage.as<char>();
-
+// The kernels' argument blocks: pass 1 (and, one task per quad, pass 2), the finalize, the secondaries' merge
+struct BatchArgs {
     DpArgs da{};
+    FinalizeArgs fz{};
+    SecArgs sa{};
+};
+
+BatchArgs batch_args(sfa_ctx *c, const float *d_queries, int32_t n, ResultRow *d_out, ResultRow *d_sec, Route route, const Staging &sg,
+                     bool has_long) {
+    const sfa::BatchPlan &plan = c->plan;
+    const int32_t n_quads = plan.n_quads, n_chunks = plan.n_chunks, n_jobs = c->n_jobs;
+    const char *ds = c->d_stage.as<char>();
+    BatchArgs a;
+    DpArgs &da = a.da;
     da.queries = d_queries;
-    da.q_off = reinterpret_cast<const int64_t *>(ds + o_qoff);
-    da.order = reinterpret_cast<const int32_t *>(ds + o_order);
-    da.quad_qlen = reinterpret_cast<const int32_t *>(ds + o_qq);
+    da.q_off = reinterpret_cast<const int64_t *>(ds);
+    da.order = reinterpret_cast<const int32_t *>(ds + sg.order);
+    da.quad_qlen = reinterpret_cast<const int32_t *>(ds + sg.qq);
     da.ref = c->d_ref.as<float>();
     da.job_off = c->d_job_off.as<int64_t>();
     da.job_len = c->d_job_len.as<int32_t>();
-    da.chunk_begin = reinterpret_cast<const int32_t *>(ds + o_chunk);
-    da.job_ck_off = reinterpret_cast<const int32_t *>(ds + o_ckoff);
+    da.chunk_begin = reinterpret_cast<const int32_t *>(ds + sg.chunk);
+    da.job_ck_off = reinterpret_cast<const int32_t *>(ds + sg.ckoff);
     da.ck = c->d_ck.as<float>();
     da.p_best = c->d_pbest.as<float>();
     da.p_end = c->d_pend.as<int32_t>();
@@ -500,7 +392,7 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
     da.n_seg = plan.n_seg;
     da.warm_windows = plan.warm_windows;
     da.n_jobs = n_jobs;
-    da.verify_planes = verify_planes;
+    da.verify_planes = plan.max_R + 1;
     da.verify = c->d_verify.as<float>();
     da.seg_fail = c->d_segfail.as<int32_t>();
     da.best_rec = c->d_bestrec.as<float>();
@@ -509,7 +401,7 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
     da.w_chunk = c->d_wchunk.as<int32_t>();
     da.best_planes = sfa::kLdsCkPlanes;
     da.lck_shift = plan.lck_shift;
-    da.coarse_every = (plan.lds_ckpt && plan.ck_shift >= plan.lck_shift) ? (1 << (plan.ck_shift - plan.lck_shift)) : 1;
+    da.coarse_every = (lds(route) && plan.ck_shift >= plan.lck_shift) ? (1 << (plan.ck_shift - plan.lck_shift)) : 1;
     da.ticket = c->d_ticket.as<unsigned>();
     da.quad_done = c->d_quaddone.as<int32_t>();
     da.n_quads_total = n_quads;
@@ -519,9 +411,8 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
     da.ref_st_offset = c->d_ref_off.as<int32_t>();
     da.bad = c->d_bad.as<uint8_t>();
     da.out = d_out;
-    da.span_hist = (fused && !plan.lds_ckpt) ? c->d_badcount.as<unsigned>() + 8 : nullptr;  // (the LDS route caps its head start instead)
+    da.span_hist = route == Route::Fused32 ? c->d_badcount.as<unsigned>() + 8 : nullptr;  // (the LDS route caps its head start instead)
     da.prio_unit = static_cast<int32_t>(c->opt_prio_unit);
-    if ((rc = c->d_started.reserve(64))) return rc;
     da.started = c->d_started.as<unsigned>();
     da.err = c->d_badcount.as<unsigned>() + 4;
     {   // a pass-2 wave legitimately waits for as long as one fill task of its quad runs: never less than ~5x that (1 us per
@@ -536,119 +427,39 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
         c->quad_limit_ms = da.spin_limit / 100000;
     }
     da.debug_drop_quad = static_cast<int32_t>(c->opt_debug_drop_quad);
-    da.p_top5 = n_sec > 0 ? c->d_p5.as<int32_t>() : nullptr;
+    da.p_top5 = route == Route::Secondary ? c->d_p5.as<int32_t>() : nullptr;
+    da.self = fused(route) ? c->d_args.as<DpArgs>() : nullptr;
 #ifdef SFA_TASK_TIMES
-    if ((rc = c->d_times.reserve(24 * static_cast<size_t>(std::max(da.n_tasks, 1))))) return rc;
     da.task_times = c->d_times.as<unsigned long long>();
-    c->n_times = da.n_tasks;
 #endif
 
-    FinalizeArgs fz{};
-    fz.slot_of_read = reinterpret_cast<const int32_t *>(ds + o_slot);
+    FinalizeArgs &fz = a.fz;
+    fz.slot_of_read = reinterpret_cast<const int32_t *>(ds + sg.slot);
     fz.p_best = da.p_best;
     fz.p_end = da.p_end;
     fz.p_job = da.p_job;
     fz.p_second = da.p_second;
-    fz.job_contig = c->d_job_contig.as<int32_t>();
-    fz.job_strand = c->d_job_strand.as<int8_t>();
-    fz.ref_len = c->d_ref_len.as<int32_t>();
-    fz.ref_st_offset = c->d_ref_off.as<int32_t>();
+    fz.job_contig = da.job_contig;
+    fz.job_strand = da.job_strand;
+    fz.ref_len = da.ref_len;
+    fz.ref_st_offset = da.ref_st_offset;
     fz.w_job = da.w_job;
     fz.w_end = da.w_end;
     fz.w_score = da.w_score;
     fz.w_chunk = da.w_chunk;
     fz.t_st = c->d_tst.as<int32_t>();
     fz.out = d_out;
-    fz.bad = c->d_bad.as<uint8_t>();
+    fz.bad = da.bad;
     fz.q_off = da.q_off;
-    fz.max_query = long_reads.empty() ? 0 : sfa::kMaxQuery;
+    fz.max_query = has_long ? sfa::kMaxQuery : 0;
     fz.n_reads = n;
     fz.n_chunks = n_chunks;
     fz.span_hist = c->d_badcount.as<unsigned>() + 8;
-    const dim3 fgrid((n + 255) / 256), fblock(256);
 
-    if (da.prio_unit > 0) HIP_TRY(hipMemsetAsync(c->d_started.p, 0, 4, st));
-    HIP_TRY(hipEventRecord(c->ev[0], st));
-    // reads with a NaN / inf query value are skipped (the reference aborts on them, see sdtw_screen_kernel)
-    HIP_TRY(hipMemsetAsync(c->d_badcount.p, 0, 32 + 4 * sfa::kSpanBuckets, st));  // word 0: non-finite reads; words 4..6: error words of the in-launch waits; words 8..39: span histogram
-    hipLaunchKernelGGL(sfa::sdtw_screen_kernel, dim3((n + 3) / 4), dim3(256), 0, st, d_queries, da.q_off, n, c->d_bad.as<uint8_t>(),
-                       c->d_badcount.as<unsigned>());
-    KERNEL_TRY();
-    // Queries beyond 2048 events: row strips, on their own stream BESIDE the wave kernels of the shorter reads of the batch (a
-    // handful of short reads is one sweep's latency on an empty chip: 6 + 2.5 ms in front of 110 ms of strips when run in a
-    // row).  The two paths write disjoint rows (the finalize kernels here leave the long reads' rows alone).
-    int32_t long_launches = 0;
-    if (!long_reads.empty()) {
-        hipStream_t ls = st;
-        ls = c->stream_long;
-        HIP_TRY(hipEventRecord(c->lev[0], st));  // queries, offsets and the non-finite screen are ready
-        HIP_TRY(hipStreamWaitEvent(ls, c->lev[0], 0));
-        c->prof.fill_launches = 0;  // (counted per group of long reads inside)
-        if ((rc = align_long(c, d_queries, da.q_off, q_off, long_reads, long_max, d_out, ls))) {
-            (void)hipStreamSynchronize(ls);  // nothing of a failed call may still be running when the caller reuses its buffers
-            (void)hipStreamSynchronize(c->stream_long2);
-            return rc;
-        }
-        long_launches = c->prof.fill_launches;
-        HIP_TRY(hipEventRecord(c->lev[1], ls));
-    }
-    if (n_quads > 0) {
-        if (plan.lds_ckpt)
-            HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_gbest.p), 0x7f800000, static_cast<size_t>(n), st));  // +inf: no score seen yet
-        if (fused) {
-            HIP_TRY(hipMemsetAsync(c->d_ticket.p, 0, 4, st));
-            HIP_TRY(hipMemsetAsync(c->d_quaddone.p, 0, 4 * static_cast<size_t>(n_quads), st));
-            fz.mode = 3;  // rows of the reads in no quad; every other row is written by the launch's pass-2 waves
-            hipLaunchKernelGGL(sfa::sdtw_finalize_kernel, fgrid, fblock, 0, st, fz);
-            KERNEL_TRY();
-            da.self = c->d_args.as<DpArgs>();
-            HIP_TRY(hipMemcpyAsync(c->d_args.p, &da, sizeof(DpArgs), hipMemcpyHostToDevice, st));  // (pageable source: staged before the call returns)
-            launch_fill_fused(plan.max_R, std_dtw, da, st);
-        } else if (plan.lds_ckpt) {
-            launch_fill_lck(plan.max_R, std_dtw, da, st);
-        } else if (n_sec > 0) {
-            launch_sec_fill(plan.max_R, std_dtw, da, st);
-        } else {
-            launch_fill(plan.max_R, std_dtw, da, st);
-        }
-        KERNEL_TRY();
-        if (plan.n_seg > 1) {  // every hand-over between consecutive segments: assumed state == reached state?
-            HIP_TRY(hipMemsetAsync(c->d_segfail.p, 0, 4 * static_cast<size_t>(n_quads), st));
-            const int64_t waves = static_cast<int64_t>(n_quads) * n_jobs * (plan.n_seg - 1);
-            hipLaunchKernelGGL(sfa::sdtw_verify_kernel, dim3(static_cast<unsigned>((waves + 3) / 4)), dim3(256), 0, st, da, n_quads);
-            KERNEL_TRY();
-        }
-    }
-    HIP_TRY(hipEventRecord(c->ev[1], st));
-    if (fused && n_quads > 0) {  // nothing left to do: rows are complete
-        HIP_TRY(hipEventRecord(c->ev[2], st));
-        HIP_TRY(hipEventRecord(c->ev[3], st));
-    } else {
-    fz.mode = 1;
-    hipLaunchKernelGGL(sfa::sdtw_finalize_kernel, fgrid, fblock, 0, st, fz);
-    KERNEL_TRY();
-    HIP_TRY(hipEventRecord(c->ev[2], st));
-    if (n_quads > 0) {
-        DpArgs ta = da;
-        for (int i = 0; i < ta.n_cls; ++i) ta.cls[i].task_base = ta.cls[i].quad_base;  // one task per quad
-        ta.n_tasks = n_quads;
-        if (plan.lds_ckpt)
-            launch_trace_lck(plan.max_R, std_dtw, ta, c->d_tst.as<int32_t>(), st);
-        else
-            launch_trace(plan.max_R, std_dtw, ta, c->d_tst.as<int32_t>(), st);
-        KERNEL_TRY();
-        HIP_TRY(hipEventRecord(c->ev[3], st));
-        fz.mode = 2;
-        hipLaunchKernelGGL(sfa::sdtw_finalize_kernel, fgrid, fblock, 0, st, fz);
-        KERNEL_TRY();
-    } else {
-        HIP_TRY(hipEventRecord(c->ev[3], st));
-    }
-    }
-    if (n_sec > 0) {  // merge the chunks' lists, trace candidates 1..n_sec, write their rows (the long reads' rows: valid = 0)
-        sfa::SecArgs sa{};
+    if (c->opt_secondary > 0) {
+        SecArgs &sa = a.sa;
         sa.slot_of_read = fz.slot_of_read;
-        sa.p_top5 = da.p_top5;
+        sa.p_top5 = c->d_p5.as<int32_t>();
         sa.bad = fz.bad;
         sa.q_off = fz.q_off;
         sa.max_query = fz.max_query;
@@ -663,26 +474,144 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
         sa.ref_len = fz.ref_len;
         sa.ref_st_offset = fz.ref_st_offset;
         sa.sec = d_sec;
-        sa.n_sec = n_sec;
-        sa.mode = 1;
-        hipLaunchKernelGGL(sfa::sdtw_sec_finalize_kernel, fgrid, fblock, 0, st, sa);
-        KERNEL_TRY();
-        for (int k = 1; k <= n_sec && n_quads > 0; ++k) {
-            DpArgs ta = da;
-            for (int i = 0; i < ta.n_cls; ++i) ta.cls[i].task_base = ta.cls[i].quad_base;  // one task per quad
-            ta.n_tasks = n_quads;
-            ta.w_job = sa.s_job + static_cast<size_t>(k) * n;
-            ta.w_end = sa.s_end + static_cast<size_t>(k) * n;
-            ta.w_score = sa.s_score + static_cast<size_t>(k) * n;
-            launch_trace(plan.max_R, std_dtw, ta, c->d_sts.as<int32_t>() + 2 * static_cast<size_t>(k) * n, st);
-            KERNEL_TRY();
-        }
-        sa.mode = 2;
-        hipLaunchKernelGGL(sfa::sdtw_sec_finalize_kernel, fgrid, fblock, 0, st, sa);
+        sa.n_sec = static_cast<int32_t>(c->opt_secondary);
+    }
+    return a;
+}
+
+int launch_finalize(FinalizeArgs fz, int mode, hipStream_t st) {
+    fz.mode = mode;
+    hipLaunchKernelGGL(sfa::sdtw_finalize_kernel, dim3((fz.n_reads + 255) / 256), dim3(256), 0, st, fz);
+    KERNEL_TRY();
+    return SFA_OK;
+}
+
+// Pass 1 of the route, with what it needs in front of it and behind it.  The LDS routes cap the rows at 16; the segment fill has
+// no STD variant (std_dtw has no column segments); the fused grid is the fill tasks followed by one pass-2 ticket per quad.
+int enqueue_pass1(sfa_ctx *c, Route route, const BatchArgs &a, hipStream_t st) {
+    if (route == Route::NoQuads) return SFA_OK;
+    const DpArgs &da = a.da;
+    const int32_t n_quads = da.n_quads_total;
+    if (lds(route))
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_gbest.p), 0x7f800000, static_cast<size_t>(da.n_reads_total), st));  // +inf: no score seen yet
+    if (fused(route)) {
+        HIP_TRY(hipMemsetAsync(c->d_ticket.p, 0, 4, st));
+        HIP_TRY(hipMemsetAsync(c->d_quaddone.p, 0, 4 * static_cast<size_t>(n_quads), st));
+        if (int rc = launch_finalize(a.fz, 3, st)) return rc;  // rows of the reads in no quad; every other row is written by the launch's pass-2 waves
+        HIP_TRY(hipMemcpyAsync(c->d_args.p, &da, sizeof(DpArgs), hipMemcpyHostToDevice, st));  // (pageable source: staged before the call returns)
+    }
+    const int maxr = c->plan.max_R;
+    const dim3 block(256), grid((da.n_tasks + 3) / 4), fgrid(static_cast<unsigned>((da.n_tasks + 3) / 4 + (n_quads + 3) / 4));
+    by_std((c->flag & SFA_DTW) != 0, [&](auto S) {
+        if (route == Route::Segments)
+            by_rows<32>(maxr, [&](auto R) { hipLaunchKernelGGL((sfa::sdtw_fill_kernel<R, false, true>), grid, block, 0, st, da); });
+        else if (route == Route::Lds)
+            by_rows<16>(maxr, [&](auto R) { hipLaunchKernelGGL((sfa::sdtw_fill_kernel<R, S, false, true>), grid, block, 0, st, da); });
+        else if (route == Route::LdsFused)
+            by_rows<16>(maxr, [&](auto R) { hipLaunchKernelGGL((sfa::sdtw_fill_kernel<R, S, false, true, true>), fgrid, block, 0, st, da); });
+        else if (route == Route::Fused32)
+            hipLaunchKernelGGL((sfa::sdtw_fill_kernel<32, false, false, false, true>), fgrid, block, 0, st, da);
+        else if (route == Route::Secondary)
+            by_rows<32>(maxr, [&](auto R) { hipLaunchKernelGGL((sfa::sdtw_sec_fill_kernel<R, S>), grid, block, 0, st, da); });
+        else  // Route::TwoPass
+            by_rows<32>(maxr, [&](auto R) { hipLaunchKernelGGL((sfa::sdtw_fill_kernel<R, S>), grid, block, 0, st, da); });
+    });
+    KERNEL_TRY();
+    if (route == Route::Segments) {  // every hand-over between consecutive segments: assumed state == reached state?
+        HIP_TRY(hipMemsetAsync(c->d_segfail.p, 0, 4 * static_cast<size_t>(n_quads), st));
+        const int64_t waves = static_cast<int64_t>(n_quads) * da.n_jobs * (da.n_seg - 1);
+        hipLaunchKernelGGL(sfa::sdtw_verify_kernel, dim3(static_cast<unsigned>((waves + 3) / 4)), dim3(256), 0, st, da, n_quads);
         KERNEL_TRY();
     }
-    c->prof.fill_launches = (n_quads > 0 ? 1 : 0) + long_launches;
-    c->long_pending = !long_reads.empty();
+    return SFA_OK;
+}
+
+// the pass-2 kernel of the route for the winners named by ta (w_job, w_end, w_score): start columns to out_st
+void launch_pass2(sfa_ctx *c, Route route, DpArgs ta, int32_t *out_st, hipStream_t st) {
+    for (int i = 0; i < ta.n_cls; ++i) ta.cls[i].task_base = ta.cls[i].quad_base;  // one task per quad
+    ta.n_tasks = ta.n_quads_total;
+    const int maxr = c->plan.max_R;
+    const dim3 grid((ta.n_tasks + 3) / 4), block(256);
+    by_std((c->flag & SFA_DTW) != 0, [&](auto S) {
+        if (lds(route))
+            by_rows<16>(maxr, [&](auto R) { hipLaunchKernelGGL((sfa::sdtw_trace_kernel<R, S, true>), grid, block, 0, st, ta, out_st); });
+        else
+            by_rows<32>(maxr, [&](auto R) { hipLaunchKernelGGL((sfa::sdtw_trace_kernel<R, S>), grid, block, 0, st, ta, out_st); });
+    });
+}
+
+// From the end of the fill (ev[1]) to complete rows: finalize -> (ev[2]) pass 2 -> (ev[3]) finalize; after a fused fill launch
+// the rows are complete already
+int enqueue_pass2(sfa_ctx *c, Route route, const BatchArgs &a, hipStream_t st) {
+    const bool own_launch = route != Route::NoQuads && !fused(route);
+    if (int rc = fused(route) ? SFA_OK : launch_finalize(a.fz, 1, st)) return rc;
+    HIP_TRY(hipEventRecord(c->ev[2], st));
+    if (own_launch) {
+        launch_pass2(c, route, a.da, c->d_tst.as<int32_t>(), st);
+        KERNEL_TRY();
+    }
+    HIP_TRY(hipEventRecord(c->ev[3], st));
+    return own_launch ? launch_finalize(a.fz, 2, st) : SFA_OK;
+}
+
+// merge the chunks' lists, trace candidates 1..n_sec, write their rows (the long reads' rows: valid = 0)
+int enqueue_secondaries(sfa_ctx *c, Route route, const BatchArgs &a, hipStream_t st) {
+    SecArgs sa = a.sa;
+    const int32_t n = sa.n_reads;
+    const dim3 fgrid((n + 255) / 256), fblock(256);
+    sa.mode = 1;
+    hipLaunchKernelGGL(sfa::sdtw_sec_finalize_kernel, fgrid, fblock, 0, st, sa);
+    KERNEL_TRY();
+    for (int k = 1; k <= sa.n_sec && route == Route::Secondary; ++k) {
+        DpArgs ta = a.da;
+        ta.w_job = sa.s_job + static_cast<size_t>(k) * n;
+        ta.w_end = sa.s_end + static_cast<size_t>(k) * n;
+        ta.w_score = sa.s_score + static_cast<size_t>(k) * n;
+        launch_pass2(c, route, ta, c->d_sts.as<int32_t>() + 2 * static_cast<size_t>(k) * n, st);
+        KERNEL_TRY();
+    }
+    sa.mode = 2;
+    hipLaunchKernelGGL(sfa::sdtw_sec_finalize_kernel, fgrid, fblock, 0, st, sa);
+    KERNEL_TRY();
+    return SFA_OK;
+}
+
+// The batch on the context's stream: screen, row strips beside it, pass 1, pass 2, secondaries, the join and the error words;
+// then its profile
+int enqueue_batch(sfa_ctx *c, Route route, const BatchArgs &a, const int64_t *q_off, const LongReads &lr) {
+    hipStream_t st = c->stream;
+    const DpArgs &da = a.da;
+    int rc;
+    if (da.prio_unit > 0) HIP_TRY(hipMemsetAsync(c->d_started.p, 0, 4, st));
+    HIP_TRY(hipEventRecord(c->ev[0], st));
+    // reads with a NaN / inf query value are skipped (the reference aborts on them, see sdtw_screen_kernel)
+    HIP_TRY(hipMemsetAsync(c->d_badcount.p, 0, 32 + 4 * sfa::kSpanBuckets, st));  // word 0: non-finite reads; words 4..6: error words of the in-launch waits; words 8..39: span histogram
+    hipLaunchKernelGGL(sfa::sdtw_screen_kernel, dim3((da.n_reads_total + 3) / 4), dim3(256), 0, st, da.queries, da.q_off, da.n_reads_total, c->d_bad.as<uint8_t>(),
+                       c->d_badcount.as<unsigned>());
+    KERNEL_TRY();
+    // Queries beyond 2048 events: row strips, on their own stream BESIDE the wave kernels of the shorter reads of the batch (a
+    // handful of short reads is one sweep's latency on an empty chip: 6 + 2.5 ms in front of 110 ms of strips when run in a
+    // row).  The two paths write disjoint rows (the finalize kernels here leave the long reads' rows alone).
+    int32_t long_launches = 0;
+    if (!lr.reads.empty()) {
+        hipStream_t ls = c->stream_long;
+        HIP_TRY(hipEventRecord(c->lev[0], st));  // queries, offsets and the non-finite screen are ready
+        HIP_TRY(hipStreamWaitEvent(ls, c->lev[0], 0));
+        c->prof.fill_launches = 0;  // (counted per group of long reads inside)
+        if ((rc = align_long(c, da.queries, da.q_off, q_off, lr.reads, lr.max, da.out, ls))) {
+            (void)hipStreamSynchronize(ls);  // nothing of a failed call may still be running when the caller reuses its buffers
+            (void)hipStreamSynchronize(c->stream_long2);
+            return rc;
+        }
+        long_launches = c->prof.fill_launches;
+        HIP_TRY(hipEventRecord(c->lev[1], ls));
+    }
+    if ((rc = enqueue_pass1(c, route, a, st))) return rc;
+    HIP_TRY(hipEventRecord(c->ev[1], st));
+    if ((rc = enqueue_pass2(c, route, a, st))) return rc;
+    if (c->opt_secondary > 0 && (rc = enqueue_secondaries(c, route, a, st))) return rc;
+    c->prof.fill_launches = (route != Route::NoQuads ? 1 : 0) + long_launches;
+    c->long_pending = !lr.reads.empty();
     if (c->long_pending) {  // join: what is left of the strips when the wave kernels are through counts as fill time
         HIP_TRY(hipEventRecord(c->ev[5], st));
         HIP_TRY(hipStreamWaitEvent(st, c->lev[1], 0));
@@ -690,32 +619,78 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
     HIP_TRY(hipMemcpyAsync(c->h_badcount.p, c->d_badcount.p, 32 + 4 * sfa::kSpanBuckets, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(c->ev[4], st));
 
-    c->prof.cells = (plan.query_events + long_events) * c->total_cols;
+    const sfa::BatchPlan &plan = c->plan;  // what resolve_profile() completes once the batch is through
+    c->prof.cells = (plan.query_events + lr.events) * c->total_cols;
     c->prof.ckpt_interval = plan.ck_shift ? (1 << plan.ck_shift) : 0;
     c->prof.ckpt_bytes = static_cast<int64_t>(sizeof(float)) * plan.ck_floats;
-    c->prof.lds_ckpt = plan.lds_ckpt ? (fused ? 2 : 1) : 0;
-    c->prof.fused_trace = (fused && n_quads > 0) ? 1 : 0;
+    c->prof.lds_ckpt = route == Route::LdsFused ? 2 : (route == Route::Lds ? 1 : 0);
+    c->prof.fused_trace = fused(route) ? 1 : 0;
     c->prof.trace_margin = plan.trace_margin;
-    c->prof.n_tasks = da.n_tasks;
-    c->prof.n_chunks = n_chunks;
+    c->prof.n_tasks = plan.n_quads * plan.n_chunks;
+    c->prof.n_chunks = plan.n_chunks;
     c->prof.n_segments = plan.n_seg;
     c->prof.segment_reruns = c->seg_reruns;
     c->prof_pending = true;
-    if (plan.n_seg > 1 && n_quads > 0) {
-        // the verdict of the hand-over checks has to be known before anybody uses the rows: wait here (these are
-        // the small, latency-bound batches -- their caller is about to wait for them anyway)
+    return SFA_OK;
+}
+
+}  // namespace
+
+// Core of every align entry point: queries already in HBM, results left in HBM.
+int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32_t n, ResultRow *d_out, ResultRow *d_sec) {
+    if (n == 0) return SFA_OK;
+    // secondary mappings: the plain two-pass route (HBM snapshots, no column segments, pass 2 as its own launches), whose fill keeps
+    // every read's top-5 list; the candidates behind the primary are traced by the same pass-2 kernel, one launch per rank
+    const int n_sec = static_cast<int>(c->opt_secondary);
+    const bool own_sec = n_sec > 0 && !d_sec;  // the call's own secondaries: sec_n names them once they are all enqueued
+    if (own_sec) {
+        c->sec_n = -1;  // a call that fails or returns early leaves no rows to be taken for its own
+        if (int rc = c->d_sec.reserve(4 * sizeof(ResultRow) * static_cast<size_t>(n))) return rc;
+        d_sec = c->d_sec.as<ResultRow>();
+    }
+    LongReads lr;
+    for (int32_t i = 0; i < n; ++i)
+        if (q_off[i + 1] - q_off[i] > sfa::kMaxQuery) {
+            lr.reads.push_back(i);
+            lr.events += q_off[i + 1] - q_off[i];
+            lr.max = std::max<int64_t>(lr.max, q_off[i + 1] - q_off[i]);
+        }
+    sfa::PlanParams pp = plan_params(c);
+    pp.skip_long = !lr.reads.empty();
+    sfa::BatchPlan &plan = c->plan;  // kept with the context: its vectors are reused by every batch
+    std::string perr;
+    if (int rc = sfa::plan_batch(q_off, n, c->h_job_len, c->total_cols, pp, &plan, &perr)) return fail(rc, "%s", perr.c_str());
+    if (!c->in_slice && c->opt_ckpt_interval == 0 && plan.ck_shift > 9 && n >= 2 * c->opt_min_slice_reads) {
+        // checkpoints at T = 512 would take about ck_bytes * T/512
+        const int64_t want = (plan.ck_floats * 4 * (1ll << (plan.ck_shift - 9)) + pp.ckpt_budget_bytes - 1) / std::max<int64_t>(pp.ckpt_budget_bytes, 1);
+        const int32_t slices = static_cast<int32_t>(std::min<int64_t>(want, n / c->opt_min_slice_reads));
+        if (slices > 1) {
+            const int rc = align_sliced(c, d_queries, q_off, n, d_out, d_sec, slices);
+            if (!rc && own_sec) c->sec_n = n;
+            return rc;
+        }
+    }
+    const Route route = sfa::choose_route(plan, pp.std_dtw, n_sec, c->opt_fused_trace, static_cast<int64_t>(c->cu_count) * 4 * SFA_LCK_WAVES);
+    const Staging sg(n, plan, c->n_jobs);
+    int rc;
+    if ((rc = stage_and_reserve(c, q_off, n, route, sg))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_stage.p, c->h_stage.p, sg.bytes, hipMemcpyHostToDevice, c->stream));
+    const BatchArgs a = batch_args(c, d_queries, n, d_out, d_sec, route, sg, !lr.reads.empty());
+    if ((rc = enqueue_batch(c, route, a, q_off, lr))) return rc;
+    if (route == Route::Segments) {
+        // the verdict of the hand-over checks has to be known before anybody uses the rows: wait here (these are the small,
+        // latency-bound batches -- their caller is about to wait for them anyway)
         int32_t *flags = c->h_flags.as<int32_t>();
-        HIP_TRY(hipMemcpyAsync(flags, c->d_segfail.p, 4 * static_cast<size_t>(n_quads), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        bool failed = false;
-        for (int32_t k = 0; k < n_quads && !failed; ++k) failed = flags[k] != 0;
-        if (failed) {  // a guessed state was not the true one somewhere: the batch is walked again, unsegmented
+        HIP_TRY(hipMemcpyAsync(flags, c->d_segfail.p, 4 * static_cast<size_t>(plan.n_quads), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (std::any_of(flags, flags + plan.n_quads, [](int32_t f) { return f != 0; })) {
+            // a guessed state was not the true one somewhere: the batch is walked again, unsegmented
             c->no_segments_once = true;
-            const int rc2 = align_device(c, d_queries, q_off, n, d_out);
+            rc = align_device(c, d_queries, q_off, n, d_out);
             c->no_segments_once = false;
             c->seg_reruns++;
             c->prof.segment_reruns = c->seg_reruns;
-            return rc2;
+            return rc;
         }
     }
     if (own_sec) c->sec_n = n;
@@ -811,12 +786,10 @@ int sfa_align_batch_device(sfa_ctx_t *c, const float *d_queries, const int64_t *
 int sfa_submit_batch(sfa_ctx_t *c, const float *queries, const int64_t *q_off, int32_t n) {
     if (!c || !q_off || n < 0 || (n > 0 && !queries)) return fail(SFA_EINVAL, "sfa_submit_batch: bad argument");
     if (!c->shards.empty()) {  // every shard queues its contiguous range of reads on its own device
-        shard_ranges(n, c->shards.size(), &c->shard_lo);
         c->pending_n = -1;
-        const int rc = for_each_shard(c, [&](size_t r) {
-            const int32_t lo = c->shard_lo[r], hi = c->shard_lo[r + 1];
+        const int rc = for_each_shard_range(c, n, [&](size_t r, int32_t lo, int32_t hi) {
             return sfa_submit_batch(c->shards[r], queries, q_off + lo, hi - lo);  // (q_off holds absolute offsets into queries)
-        });
+        }, &c->shard_lo);  // (sfa_wait_batch collects by the same ranges)
         if (!rc) c->pending_n = n;
         return rc;
     }
@@ -855,9 +828,9 @@ int sfa_wait_batch(sfa_ctx_t *c, sfa_result_t *out, int32_t n) {
     if (c->pending_n != n) return fail(SFA_EINVAL, "sfa_wait_batch: %d reads were submitted, %d asked for", c->pending_n, n);
     c->pending_n = -1;
     if (!c->shards.empty())  // rows of shard r go to out[lo_r, hi_r): input order, no gather step in a single process
-        return for_each_shard(c, [&](size_t r) {
+        return for_each_shard(c, [&](size_t r) {  // (shards without reads were not submitted to)
             const int32_t lo = c->shard_lo[r], hi = c->shard_lo[r + 1];
-            return sfa_wait_batch(c->shards[r], out ? out + lo : nullptr, hi - lo);
+            return lo == hi ? static_cast<int>(SFA_OK) : sfa_wait_batch(c->shards[r], out + lo, hi - lo);
         });
     if (n == 0) return SFA_OK;
     HIP_TRY(hipSetDevice(c->device));
@@ -870,12 +843,8 @@ int sfa_secondary_rows(sfa_ctx_t *c, sfa_result_t *sec, int32_t n) {
     if (!c || n < 0 || (n > 0 && !sec)) return fail(SFA_EINVAL, "sfa_secondary_rows: bad argument");
     if (!c->shards.empty()) {  // every entry point splits a call the same way (shard_ranges): shard r holds rows [lo_r, hi_r)
         if (c->shards[0]->opt_secondary == 0) return fail(SFA_EINVAL, "sfa_secondary_rows: the 'secondary' option is 0");
-        std::vector<int32_t> lo;
-        shard_ranges(n, c->shards.size(), &lo);
-        return for_each_shard(c, [&](size_t r) {
-            const int32_t a = lo[r], b = lo[r + 1];
-            if (a == b) return static_cast<int>(SFA_OK);
-            return sfa_secondary_rows(c->shards[r], sec + 4 * static_cast<size_t>(a), b - a);
+        return for_each_shard_range(c, n, [&](size_t r, int32_t lo, int32_t hi) {
+            return sfa_secondary_rows(c->shards[r], sec + 4 * static_cast<size_t>(lo), hi - lo);
         });
     }
     if (c->opt_secondary == 0) return fail(SFA_EINVAL, "sfa_secondary_rows: the 'secondary' option is 0");

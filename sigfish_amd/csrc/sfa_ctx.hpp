@@ -288,4 +288,13 @@ int for_each_shard(sfa_ctx *g, F fn) {
     if (rc) last_error_slot() = msg;
     return rc;
 }
+// a call over n reads split the way every entry point splits it: fn(r, lo, hi) for every shard r whose range [lo, hi) is not
+// empty (for_each_shard); *ranges (if given) keeps the split
+template <typename F>
+int for_each_shard_range(sfa_ctx *g, int32_t n, F fn, std::vector<int32_t> *ranges = nullptr) {
+    std::vector<int32_t> own;
+    std::vector<int32_t> &lo = ranges ? *ranges : own;
+    shard_ranges(n, g->shards.size(), &lo);
+    return for_each_shard(g, [&](size_t r) { return lo[r] == lo[r + 1] ? static_cast<int>(SFA_OK) : fn(r, lo[r], lo[r + 1]); });
+}
 }  // namespace sfa

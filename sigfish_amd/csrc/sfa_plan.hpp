@@ -316,4 +316,31 @@ inline int plan_batch(const int64_t *q_off, int32_t n, const std::vector<int32_t
     return 0;
 }
 
+// The kernels that run a batch's wave-kernel quads (sfa_align.hip: enqueue_pass1 / enqueue_pass2).  One per batch.
+enum class Route {
+    NoQuads,    // no read for the wave kernels (every query is empty or beyond kMaxQuery: row strips)
+    Segments,   // column segments (small sDTW batches): segment fill + hand-over verification, pass 2 as its own launch
+    Lds,        // rolling checkpoints in LDS (R <= 16), pass 2 as its own launch
+    LdsFused,   // ... pass 2 in the fill launch by ticket
+    Fused32,    // 32-row sDTW fill, snapshots in HBM (write-through), pass 2 in the fill launch by ticket
+    Secondary,  // the plain two-pass route whose fill keeps every read's top-5 list (secondary mappings)
+    TwoPass,    // snapshots in HBM, pass 2 as its own launch
+};
+
+// fused_trace: the option (0, 1, 2); wave_slots: fill waves resident at once on the LDS route (SIMDs * SFA_LCK_WAVES)
+inline Route choose_route(const BatchPlan &p, bool std_dtw, int secondary, int64_t fused_trace, int64_t wave_slots) {
+    if (p.n_quads == 0) return Route::NoQuads;
+    if (secondary > 0) return Route::Secondary;
+    if (p.n_seg > 1) return Route::Segments;
+    // pass 2 inside the fill launch pays when the launch has more tasks than wave slots: its tickets then come up as the fill
+    // drains.  With everything resident from the start the pass-2 waves would only sit next to the fill waves and poll
+    // (measured: 2 048 reads 2.9 -> 3.3 ms per batch), so small launches keep the separate pass-2 launch.  Two fills can carry
+    // tickets: the LDS-checkpoint fill (R <= 16; std_dtw: its sparse HBM store) and the 32-row subsequence fill, whose snapshots
+    // go to HBM -- write-through in that launch, because its pass-2 waves read them from whatever XCD they land on.
+    const bool fused = fused_trace != 0 && (fused_trace > 1 || static_cast<int64_t>(p.n_quads) * p.n_chunks > wave_slots);
+    if (p.lds_ckpt) return fused ? Route::LdsFused : Route::Lds;
+    if (fused && p.max_R == 32 && !std_dtw && p.ck_shift > 0) return Route::Fused32;
+    return Route::TwoPass;
+}
+
 }  // namespace sfa

@@ -11,8 +11,7 @@
 using sfa::ResultRow;
 using sfa::resolve_profile;
 using sfa::align_device;
-using sfa::for_each_shard;
-using sfa::shard_ranges;
+using sfa::for_each_shard_range;
 
 extern "C" {
 
@@ -39,11 +38,7 @@ static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_o
     if (query_size <= 0) return fail(SFA_EINVAL, "sfa_align_raw: query_size must be positive");
     if (n == 0) return SFA_OK;
     if (!c->shards.empty()) {
-        std::vector<int32_t> lo;
-        shard_ranges(n, c->shards.size(), &lo);
-        return for_each_shard(c, [&](size_t r) {
-            const int32_t a = lo[r], b = lo[r + 1];
-            if (a == b) return static_cast<int>(SFA_OK);
+        return for_each_shard_range(c, n, [&](size_t r, int32_t a, int32_t b) {
             std::vector<int64_t> off(b - a + 1);  // the shard's sample offsets start at 0
             for (int32_t i = a; i <= b; ++i) off[i - a] = raw_off[i] - raw_off[a];
             if (!raw) return fail(SFA_EINVAL, "sfa_align_raw: device-resident samples need a single-device context");
@@ -259,11 +254,7 @@ int sfa_align_blow5(sfa_ctx_t *c, const uint8_t *records, const int64_t *rec_off
     if (query_size <= 0) return fail(SFA_EINVAL, "sfa_align_blow5: query_size must be positive");
     if (n == 0) return SFA_OK;
     if (!c->shards.empty()) {
-        std::vector<int32_t> lo;
-        shard_ranges(n, c->shards.size(), &lo);
-        return for_each_shard(c, [&](size_t r) {
-            const int32_t a = lo[r], b = lo[r + 1];
-            if (a == b) return static_cast<int>(SFA_OK);
+        return for_each_shard_range(c, n, [&](size_t r, int32_t a, int32_t b) {
             std::vector<int64_t> off(b - a + 1);
             for (int32_t i = a; i <= b; ++i) off[i - a] = rec_off[i] - rec_off[a];
             return sfa_align_blow5(c->shards[r], records + rec_off[a], off.data(), b - a, record_zlib, signal_svb, prefix_size, query_size,
