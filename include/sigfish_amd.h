@@ -173,6 +173,22 @@ int sfa_wait_batch(sfa_ctx_t *ctx, sfa_result_t *out, int32_t n_reads);
  * No de-duplication: neighbouring windows of one locus often fill the list.  Returns SFA_EINVAL when the option is 0. */
 int sfa_secondary_rows(sfa_ctx_t *ctx, sfa_result_t *sec, int32_t n_reads);
 
+/* The reference-column -> query-event maps (aln_t.r2qevent_map, path_to_map, src/sigfish.c:530-571) of a whole batch of rows from
+ * the device: what sfa_r2qevent_map computes per read on a host thread.  Refers to the most recently completed align call of the
+ * context (sfa_align_batch, sfa_wait_batch, sfa_align_events, sfa_align_raw(_ex), sfa_align_blow5; call this before the next batch
+ * is submitted, as for sfa_secondary_rows): its queries are still resident, nothing is uploaded again.  rows[n_rows]: rows that
+ * call returned -- primaries, or rows of sfa_secondary_rows; read_of_row[k]: the read of row k in that call (NULL: the identity,
+ * and n_rows must be its read count).  map_off[n_rows+1]: the caller's offsets into `pairs`, in pairs; the map of row k --
+ * pos_end - pos_st + 1 pairs, layout exactly sfa_r2qevent_map's -- is written at pairs + 2 * map_off[k].  A smaller gap for a
+ * valid row is SFA_ERANGE; rows with valid = 0 or rid < 0 write nothing, and neither does a row for which sfa_r2qevent_map would
+ * return SFA_EINVAL.  The band of every row is filled again on the device with the arithmetic of the host routine (bit-identical
+ * costs, same tie order) in slices whose packed moves fit "map_scratch_bytes"; a row whose own moves exceed that budget, or whose
+ * read has more than SFA_MAX_QUERY events, is computed by the host routine inside the call -- *n_on_host (may be NULL) counts them.
+ * SFA_EINVAL: no completed call, a read count or read index that does not match it, or the last call was
+ * sfa_align_batch_device (its queries are the caller's).  Group contexts split the rows by the shard that holds their read. */
+int sfa_event_maps(sfa_ctx_t *ctx, const sfa_result_t *rows, const int32_t *read_of_row, int32_t n_rows, const int64_t *map_off,
+                   int32_t *pairs, int32_t *n_on_host);
+
 /* align_db() shaped entry: per-read event tables exactly as db_t holds them (src/sigfish.h:177-178):
  * events[i] -> sfa_event_t array of read i, qstart[i]/qend[i] the window chosen by normalise_single
  * (src/sigfish.c:479-480); reads with n_events[i]==0 are skipped.  The window means are gathered out of the 24-byte event
@@ -180,7 +196,7 @@ int sfa_secondary_rows(sfa_ctx_t *ctx, sfa_result_t *sec, int32_t n_reads);
 int sfa_align_events(sfa_ctx_t *ctx, const sfa_event_t *const *events, const int64_t *n_events,
                      const int64_t *qstart, const int64_t *qend, int32_t n_reads, sfa_result_t *out);
 
-/* Options (all optional; rows never depend on them -- every setting is held to the same parity tests).  14 keys:
+/* Options (all optional; rows never depend on them -- every setting is held to the same parity tests).  15 keys:
  *   planner
  *     "lane_widening"         0 = auto by batch size (default); 1 / 2 / 4 = fixed: rows per lane / w and lanes per read * w -- the
  *                             small-batch latency shapes
@@ -215,6 +231,8 @@ int sfa_align_events(sfa_ctx_t *ctx, const sfa_event_t *const *events, const int
  *   output
  *     "secondary"             0..4 (default 0): secondary mappings per read, returned by sfa_secondary_rows; > 0 takes the plain
  *                             two-pass route (HBM snapshots, no column segments, pass 2 as its own launches).  Rows do not change
+ *     "map_scratch_bytes"     HBM the packed moves of one slice of rows may take in sfa_event_maps (default 2 GiB); rows are processed in
+ *                             slices that fit, a row that does not fit alone goes to the host routine
  *   raw-signal path
  *     "ev_parallel"           bit 0: wave-per-read prefix sums for every read whose sums are provably exact in any order (the
  *                             sequential kernel for the rest); bit 1: chunk-parallel peak picker accepted where it is certified
@@ -370,6 +388,15 @@ int sfa_sam_row(char *buf, size_t cap, const sfa_result_t *r, const char *read_i
 int sfa_sam_row_ex(char *buf, size_t cap, const sfa_result_t *r, const char *read_id, const char *rname,
                    const sfa_event_t *events, int64_t qstart, int64_t qend, const float *ref_array, int32_t ref_len,
                    int32_t ref_st_offset, uint32_t flag, int secondary);
+
+/* The same line from a map instead of a path: pairs[2 * n_pairs] as sfa_r2qevent_map or sfa_event_maps return it for the row.
+ * Host only, no reference array needed.  SFA_EINVAL also for a map whose indices leave the query window, and for a map the ss
+ * string cannot express: with SFA_RNA every index is mirrored about the last column's stop, so a map whose last column is blank
+ * (-1/-1: the path entered it without advancing in the query, common under SFA_DTW) has no record -- r2qevent_map_to_ss asserts
+ * there (src/sigfish.c:668-669).  sfa_sam_row and sfa_sam_row_ex format through this function and refuse the same rows. */
+int sfa_sam_row_from_map(char *buf, size_t cap, const sfa_result_t *r, const char *read_id, const char *rname,
+                         const sfa_event_t *events, int64_t qstart, int64_t qend, const int32_t *pairs, int32_t n_pairs,
+                         uint32_t flag, int secondary);
 
 /* aln_t.r2qevent_map for a result row (path_to_map, src/sigfish.c:530-571, as update_aln stores it at 610-613): what the
  * reference's own sam_str / r2qevent_map_to_ss (src/sigfish.c:663-794) consume.  The winner's warp path is rebuilt on the

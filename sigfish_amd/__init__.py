@@ -5,7 +5,7 @@ sigfish_amd/lib/libsigfish_amd.so).  This package is only a thin ctypes binding 
 it never falls back to a CPU implementation: importing works without a GPU, creating an Aligner does not.
 """
 from .api import (END, DTW, EVENT_DTYPE, INV, REF, RNA, RESULT_DTYPE, Aligner, Blow5File, RefModel, SfaError, build_id,
-                  detect_events, detect_query_start, paf_row, r2qevent_map, read_fasta, read_kmer_model, sam_row, select_query, version, znormalise)
+                  detect_events, detect_query_start, paf_row, r2qevent_map, read_fasta, read_kmer_model, sam_row, sam_row_from_map, select_query, version, znormalise)
 
 __all__ = ["Aligner", "RefModel", "SfaError", "RESULT_DTYPE", "RNA", "DTW", "INV", "REF", "END", "paf_row",
            "read_fasta", "version", "znormalise"]

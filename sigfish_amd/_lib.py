@@ -53,7 +53,7 @@ class SfaEvent(C.Structure):
 # every symbol include/sigfish_amd.h declares (checked by tests/test_capi_host.py::test_library_exports_every_declared_symbol)
 SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "sfa_submit_batch", "sfa_wait_batch", "sfa_align_batch_device", "sfa_align_events", "sfa_align_raw", "sfa_align_raw_ex", "sfa_align_blow5", "sfa_inflate_zlib_device", "sfa_pinned_alloc", "sfa_pinned_free", "sfa_sync",
            "sfa_get_profile", "sfa_stream", "sfa_set_option", "sfa_plan_batch", "sfa_destroy", "sfa_last_error", "sfa_version", "sfa_build_id", "sfa_gen_ref_record",
-           "sfa_znormalise", "sfa_paf_row", "sfa_sam_row", "sfa_paf_row_ex", "sfa_sam_row_ex", "sfa_secondary_rows", "sfa_r2qevent_map", "sfa_detect_events", "sfa_select_query", "sfa_detect_query_start", "sfa_set_pore", "sfa_read_kmer_model",
+           "sfa_znormalise", "sfa_paf_row", "sfa_sam_row", "sfa_paf_row_ex", "sfa_sam_row_ex", "sfa_secondary_rows", "sfa_event_maps", "sfa_sam_row_from_map", "sfa_r2qevent_map", "sfa_detect_events", "sfa_select_query", "sfa_detect_query_start", "sfa_set_pore", "sfa_read_kmer_model",
            "sfa_blow5_open", "sfa_blow5_attr", "sfa_blow5_next", "sfa_blow5_close", "sfa_blow5_select_shard", "sfa_blow5_select_records", "sfa_inflate_zlib", "sfa_inflate_zlib_pair", "sfa_device_memory"]
 
 _lib = None
@@ -109,6 +109,9 @@ def load():
     L.sfa_paf_row_ex.argtypes = L.sfa_paf_row.argtypes + [C.c_char]
     L.sfa_sam_row_ex.argtypes = L.sfa_sam_row.argtypes + [C.c_int]
     L.sfa_secondary_rows.argtypes = [vp, vp, C.c_int32]
+    L.sfa_event_maps.argtypes = [vp, vp, i32p, C.c_int32, i64p, i32p, i32p]
+    L.sfa_sam_row_from_map.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(SfaResult), C.c_char_p, C.c_char_p, C.POINTER(SfaEvent),
+                                       C.c_int64, C.c_int64, i32p, C.c_int32, C.c_uint32, C.c_int]
     L.sfa_r2qevent_map.argtypes = [C.POINTER(SfaResult), C.POINTER(SfaEvent), C.c_int64, C.c_int64, f32p, C.c_int32, C.c_int32,
                                    C.c_uint32, i32p, C.c_int32]
     L.sfa_r2qevent_map.restype = C.c_int32

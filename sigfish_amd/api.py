@@ -136,6 +136,8 @@ class Aligner:
         self._L = _lib.load()
         self._h = C.c_void_p()
         self._last_n = 0
+        self._last_rows = None  # primaries of the most recent call (event_maps' default)
+        self.maps_on_host = 0
         self.ref, self.flag, self.device = ref, int(flag), int(device)
         cref, keep = ref._as_c()
         if devices is None:
@@ -173,6 +175,7 @@ class Aligner:
         n = len(qo) - 1
         out = np.zeros(n, RESULT_DTYPE)
         self._last_n = n
+        self._last_rows = out
         if q.size == 0:
             q = np.zeros(1, np.float32)
         _check(self._L.sfa_align_batch(self._h, q.ctypes.data_as(_lib.f32p), qo.ctypes.data_as(_lib.i64p), n,
@@ -194,6 +197,7 @@ class Aligner:
         n = len(qo) - 1
         out = np.zeros(n, RESULT_DTYPE)
         self._last_n = n
+        self._last_rows = out
         try:
             _check(self._L.sfa_wait_batch(self._h, out.ctypes.data_as(C.c_void_p), n), "sfa_wait_batch")
         finally:
@@ -225,6 +229,7 @@ class Aligner:
         qe = np.ascontiguousarray(qend, np.int64)
         out = np.zeros(n, RESULT_DTYPE)
         self._last_n = n
+        self._last_rows = out
         _check(self._L.sfa_align_events(self._h, ptrs, nev.ctypes.data_as(_lib.i64p), qs.ctypes.data_as(_lib.i64p),
                                         qe.ctypes.data_as(_lib.i64p), n, out.ctypes.data_as(C.c_void_p)),
                "sfa_align_events")
@@ -244,6 +249,37 @@ class Aligner:
         _check(self._L.sfa_secondary_rows(self._h, out.ctypes.data_as(C.c_void_p), n), "sfa_secondary_rows")
         return out
 
+    def event_maps(self, rows=None, read_of_row=None):
+        """aln_t.r2qevent_map of rows of the most recent call, computed on the device: a list of int32 [size, 2] arrays (start, stop
+        per reference column, as r2qevent_map returns for one row; size 0 for a row without a map).  rows: RESULT_DTYPE rows that
+        call returned -- default: its primaries -- or rows of secondary_rows(); read_of_row: the read of each row (default: the
+        identity).  The number of rows the library computed on the host instead is left in `maps_on_host`."""
+        if rows is None:
+            rows = self._last_rows
+            if rows is None:
+                raise SfaError("event_maps: no rows of a previous call to default to")
+        rows = np.ascontiguousarray(rows, RESULT_DTYPE).reshape(-1)
+        n = len(rows)
+        ror = None if read_of_row is None else np.ascontiguousarray(read_of_row, np.int32).reshape(-1)
+        if ror is not None and len(ror) != n:
+            raise SfaError("event_maps: read_of_row must name one read per row")
+        ok = (rows["valid"] != 0) & (rows["rid"] >= 0)
+        size = np.where(ok, rows["pos_end"].astype(np.int64) - rows["pos_st"] + 1, 0)
+        size = np.maximum(size, 0)
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum(size, out=off[1:])
+        pairs = np.full((max(int(off[-1]), 1), 2), np.iinfo(np.int32).min, np.int32)
+        on_host = C.c_int32(0)
+        _check(self._L.sfa_event_maps(self._h, rows.ctypes.data_as(C.c_void_p), None if ror is None else ror.ctypes.data_as(_lib.i32p), n,
+                                      off.ctypes.data_as(_lib.i64p), pairs.ctypes.data_as(_lib.i32p), C.byref(on_host)), "sfa_event_maps")
+        self.maps_on_host = int(on_host.value)
+        out = []
+        for k in range(n):
+            m = pairs[off[k]:off[k + 1]]
+            # a row the library wrote nothing for (no complete map, see sfa_event_maps) keeps the fill value
+            out.append(m.copy() if len(m) and m[0, 0] != np.iinfo(np.int32).min else np.zeros((0, 2), np.int32))
+        return out
+
     def set_pore(self, pore):
         """The reference's opt.pore_flag: 0 R9 (default), 1 R10, 2 RNA004 (the RNA automatic query start depends on it)."""
         _check(self._L.sfa_set_pore(self._h, int(pore)), "sfa_set_pore")
@@ -260,6 +296,7 @@ class Aligner:
         rows = np.zeros(n, RESULT_DTYPE)
         info = np.zeros(n, QUERY_INFO_DTYPE)
         self._last_n = n
+        self._last_rows = rows
         if raw.size == 0:
             raw = np.zeros(1, np.int16)
         qev = np.zeros((n, query_size), EVENT_DTYPE) if return_events else None
@@ -278,6 +315,7 @@ class Aligner:
         rows = np.zeros(n, RESULT_DTYPE)
         info = np.zeros(n, QUERY_INFO_DTYPE)
         self._last_n = n
+        self._last_rows = rows
         heads = (_lib.SfaReadHead * max(n, 1))()
         qev = np.zeros((n, query_size), EVENT_DTYPE) if return_events else None
         if rec.size == 0:
@@ -474,4 +512,18 @@ def sam_row(res, read_id, rname, events, qstart, qend, ref_array, ref_st_offset,
                                    y.ctypes.data_as(_lib.f32p), len(y), int(ref_st_offset), int(flag), int(bool(secondary)))
     if n < 0:
         raise SfaError(f"sfa_sam_row failed ({n})")
+    return buf.raw[:n].decode()
+
+
+def sam_row_from_map(res, read_id, rname, events, qstart, qend, pairs, flag, secondary=False):
+    """sam_row from the row's reference-column -> query-event map (r2qevent_map or Aligner.event_maps) instead of its path."""
+    r = _lib.SfaResult(int(res["rid"]), int(res["pos_st"]), int(res["pos_end"]), float(res["score"]),
+                       float(res["score2"]), int(res["strand"]), int(res["mapq"]), int(res["valid"]), 0)
+    p = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    buf = C.create_string_buffer(1 << 22)
+    n = _lib.load().sfa_sam_row_from_map(buf, len(buf), C.byref(r), str(read_id).encode(), str(rname).encode(),
+                                         C.cast(events.ctypes.data, C.POINTER(_lib.SfaEvent)), int(qstart), int(qend),
+                                         p.ctypes.data_as(_lib.i32p), len(p), int(flag), int(bool(secondary)))
+    if n < 0:
+        raise SfaError(f"sfa_sam_row_from_map failed ({n})")
     return buf.raw[:n].decode()

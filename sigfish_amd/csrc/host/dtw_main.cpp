@@ -61,6 +61,8 @@ struct Opt {
     const char *model_file = nullptr;
     const char *pore = nullptr;
     int pore_flag = 0;  // 0 r9, 1 r10, 2 rna004
+    bool device_paths = false;  // --device-paths: SAM from the event maps of a whole batch, computed on the GPU (sfa_event_maps); --host-paths
+                                // (the default until the device route has been measured): warp paths rebuilt read by read on the host threads
     bool secondary = false;  // --secondary yes: print the candidates behind each primary (sfa_secondary_rows)
 };
 
@@ -129,6 +131,7 @@ void help(FILE *fp, const Opt &o) {
     fprintf(fp, "   --full-ref                 map to the full reference\n");
     fprintf(fp, "   --from-end                 map the end portion of the query instead of the beginning\n");
     fprintf(fp, "   --sam                      output in SAM format\n");
+    fprintf(fp, "   --device-paths | --host-paths  with --sam: warp paths of a whole batch on the GPU | read by read on the host threads [host threads]\n");
     fprintf(fp, "   --secondary STR            print secondary mappings. yes or no [no]\n");
     fprintf(fp, "   --profile-cpu=yes|no       run the stages one after the other and report Parse/Events/Normalise/DTW time [no]\n");
     fprintf(fp, "   --accel=yes|no             run the alignment on the accelerator [yes]; 'no' is an error: this build has no CPU path\n");
@@ -466,7 +469,7 @@ static int dtw_run(int argc, char **argv) {
                           {"window", required_argument, 0, 'w'},    {"meth-model", required_argument, 0, 13},   {"host-events", no_argument, 0, 14},   {"streams", required_argument, 0, 15},   {"host-parse", no_argument, 0, 16},   {"gpu-parse", no_argument, 0, 17},   
                           {"ranks", required_argument, 0, 20},      {"shard", required_argument, 0, 21},
                           {"read-range", required_argument, 0, 22}, {"no-header", no_argument, 0, 23},
-                          {"rank-buffer", required_argument, 0, 25},
+                          {"rank-buffer", required_argument, 0, 25}, {"host-paths", no_argument, 0, 26}, {"device-paths", no_argument, 0, 27},
                           {0, 0, 0, 0}};
     Opt o;
     FILE *fp_help = stderr;
@@ -522,6 +525,8 @@ static int dtw_run(int argc, char **argv) {
                 break;
             }
             case 14: o.host_events = true; break;
+            case 26: o.device_paths = false; break;
+            case 27: o.device_paths = true; break;
             case 16: o.gpu_parse = 0; break;
             case 17: o.gpu_parse = 1; break;
             case 20: o.ranks = atoi(optarg); if (o.ranks < 1 || o.ranks > 64) die("--ranks should be 1..64"); break;
@@ -709,6 +714,11 @@ static int dtw_run(int argc, char **argv) {
         std::vector<int64_t> nev, qs, qe;
         std::vector<sfa_result_t> rows;
         std::vector<sfa_result_t> sec;  // --secondary yes: [n][4] rows behind each primary, best first
+        // --sam --device-paths: the event maps of the batch from the device.  Row i is the primary of read i, row n + 4 i + k
+        // its k-th secondary; map_off in pairs; a map the library left unwritten keeps kNoMap in its first word
+        std::vector<sfa_result_t> map_rows;
+        std::vector<int32_t> map_read, map_pairs;
+        std::vector<int64_t> map_off;
         // device-side event detection: concatenated raw samples + scaling instead of event tables
         int16_t *raw = nullptr;  // page-locked (sfa_pinned_alloc), grown on demand
         size_t raw_cap = 0;
@@ -749,6 +759,11 @@ static int dtw_run(int argc, char **argv) {
         sl.rows.resize(o.batch_size);
     }
     std::mutex stat_mu;  // two GPU stages may finish together
+    const bool device_paths = sam && o.device_paths;
+    constexpr int32_t kNoMap = INT32_MIN;
+    // mapped rows without a SAM record: the writer refuses a map it cannot express (RNA --dtw-std: a warp path that enters the
+    // last reference column without advancing in the query leaves it blank, where r2qevent_map_to_ss asserts, src/sigfish.c:668-669)
+    std::atomic<int64_t> sam_unprintable{0};
     auto align = [&](Slot &sl, sfa_ctx_t *ctx) {
         const int32_t n = sl.n;
         std::vector<sfa_result_t> &rows = sl.rows;
@@ -772,6 +787,23 @@ static int dtw_run(int argc, char **argv) {
         if (o.secondary && n > 0) {
             sl.sec.resize(static_cast<size_t>(n) * 4);
             if (sfa_secondary_rows(ctx, sl.sec.data(), n) != SFA_OK) die(std::string("secondary mappings: ") + sfa_last_error());
+        }
+        if (device_paths && n > 0) {
+            const int32_t per = o.secondary ? 5 : 1, nr = n * per;
+            sl.map_rows.assign(rows.begin(), rows.begin() + n);
+            if (o.secondary) sl.map_rows.insert(sl.map_rows.end(), sl.sec.begin(), sl.sec.begin() + static_cast<size_t>(n) * 4);
+            sl.map_read.resize(nr);
+            sl.map_off.assign(static_cast<size_t>(nr) + 1, 0);
+            for (int32_t k = 0; k < nr; ++k) {
+                const sfa_result_t &w = sl.map_rows[k];
+                sl.map_read[k] = k < n ? k : (k - n) / 4;
+                const int64_t need = (w.valid && w.rid >= 0) ? static_cast<int64_t>(w.pos_end) - w.pos_st + 1 : 0;
+                sl.map_off[k + 1] = sl.map_off[k] + (need > 0 ? need : 0);
+            }
+            sl.map_pairs.resize(2 * static_cast<size_t>(sl.map_off[nr]) + 2);
+            for (int32_t k = 0; k < nr; ++k) sl.map_pairs[2 * sl.map_off[k]] = kNoMap;
+            if (sfa_event_maps(ctx, sl.map_rows.data(), sl.map_read.data(), nr, sl.map_off.data(), sl.map_pairs.data(), nullptr) != SFA_OK)
+                die(std::string("event maps: ") + sfa_last_error());
         }
         sfa_profile_t pr{};
         if (prf && n > 0 && sfa_get_profile(ctx, &pr) != SFA_OK) die(std::string("sfa_get_profile failed: ") + sfa_last_error());
@@ -802,7 +834,8 @@ static int dtw_run(int argc, char **argv) {
         std::vector<sfa_result_t> &rows = sl.rows;
         const double a = realtime();
         if (o.flag & F_SAM) {
-            // the warp path of every winner is rebuilt on the host from its band (sam.hpp), one read per task
+            // formatted from the batch's event maps (device_paths); a row without one, and every row without --device-paths, has its
+            // warp path rebuilt here from its band (sam.hpp).  One read per task
             std::vector<std::string> sam_rows(n);
             pool.run(n, [&](int64_t i) {
                 const Read &r = batch[i];
@@ -818,14 +851,26 @@ static int dtw_run(int argc, char **argv) {
                     if (!w.valid || w.rid < 0) continue;
                     const float *y = w.strand == '+' ? fwd[w.rid].data() : rev[w.rid].data();
                     std::string buf(1 << 16, '\0');
-                    int len = sfa_sam_row_ex(&buf[0], buf.size(), &w, rid, contigs[w.rid].name.c_str(), ev, qs, qe, y,
-                                             ref_len[w.rid], ref_off[w.rid], o.flag, k >= 0);
+                    const int32_t *map = nullptr;
+                    int32_t n_map = 0;
+                    if (device_paths) {
+                        const size_t mk = k < 0 ? static_cast<size_t>(i) : static_cast<size_t>(n) + static_cast<size_t>(i) * 4 + k;
+                        n_map = static_cast<int32_t>(sl.map_off[mk + 1] - sl.map_off[mk]);
+                        map = sl.map_pairs.data() + 2 * sl.map_off[mk];
+                        if (n_map <= 0 || map[0] == kNoMap) map = nullptr;
+                    }
+                    auto format = [&]() {
+                        return map ? sfa_sam_row_from_map(&buf[0], buf.size(), &w, rid, contigs[w.rid].name.c_str(), ev, qs, qe, map, n_map, o.flag, k >= 0)
+                                   : sfa_sam_row_ex(&buf[0], buf.size(), &w, rid, contigs[w.rid].name.c_str(), ev, qs, qe, y, ref_len[w.rid],
+                                                    ref_off[w.rid], o.flag, k >= 0);
+                    };
+                    int len = format();
                     if (len == SFA_ERANGE) {  // very long ss strings (full-reference alignments)
                         buf.assign(1 << 22, '\0');
-                        len = sfa_sam_row_ex(&buf[0], buf.size(), &w, rid, contigs[w.rid].name.c_str(), ev, qs, qe, y,
-                                             ref_len[w.rid], ref_off[w.rid], o.flag, k >= 0);
+                        len = format();
                     }
                     if (len > 0) sam_rows[i].append(buf.data(), len);
+                    else sam_unprintable.fetch_add(1, std::memory_order_relaxed);
                 }
             });
             for (int32_t i = 0; i < n; ++i) fwrite(sam_rows[i].data(), 1, sam_rows[i].size(), stdout);
@@ -1066,6 +1111,9 @@ static int dtw_run(int argc, char **argv) {
         sfa_pinned_free(sl.raw);
         sfa_pinned_free(sl.rec_bytes);
     }
+    if (sam_unprintable.load() > 0 && o.verbosity >= 1)
+        fprintf(stderr, "[sigfish-amd] WARNING: %ld mapped row(s) have no SAM record: the ss string cannot express their warp path (RNA: last reference column without a query event)\n",
+                (long)sam_unprintable.load());
     if (o.verbosity >= 3 && prf) {  // the reference's lines, src/dtw_main.c:331-343
         fprintf(stderr, "[dtw_main] total entries: %ld\tprefix fail: %ld\tignored: %ld\ttoo short: %ld", (long)total, (long)prefix_fail, (long)ignored, (long)too_short);
         fprintf(stderr, "\n[dtw_main] total bytes: %.1f M", sum_bytes / 1e6);

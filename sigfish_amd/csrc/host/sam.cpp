@@ -85,13 +85,12 @@ std::vector<int32_t> path_to_pairs(const WarpPath &path) {
     return pairs;
 }
 
-std::string sam_record(const sfa_result_t &row, const WarpPath &path, const char *read_id, const char *rname, const sfa_event_t *ev,
+std::string sam_record(const sfa_result_t &row, const int32_t *pairs, int32_t n_pairs, const char *read_id, const char *rname, const sfa_event_t *ev,
                        int64_t qstart, int64_t qend, bool rna, bool secondary) {
     struct Pair {
         int32_t start, stop;
     };
-    const std::vector<int32_t> pairs = path_to_pairs(path);
-    const int32_t len = static_cast<int32_t>(pairs.size() / 2);
+    const int32_t len = n_pairs;
     std::vector<Pair> map(len);
     for (int32_t i = 0; i < len; ++i) map[i] = Pair{pairs[2 * i], pairs[2 * i + 1]};
     // r2qevent_map_to_ss(), src/sigfish.c:663-768

@@ -28,8 +28,9 @@ WarpPath band_traceback(const float *query, int32_t qlen, const float *y, int32_
 // pos_st + i (layout of index_pair_t, src/sigfish.h:141-144).  Length = last column - first column + 1.
 std::vector<int32_t> path_to_pairs(const WarpPath &path);
 
-// path_to_map + r2qevent_map_to_ss + sam_str (src/sigfish.c:530-571, 663-794) for one read
-std::string sam_record(const sfa_result_t &row, const WarpPath &path, const char *read_id, const char *rname, const sfa_event_t *events,
+// r2qevent_map_to_ss + sam_str (src/sigfish.c:663-794) for one read from its reference-column -> query-event map: n_pairs (start,
+// stop) pairs as path_to_pairs lays them out (the host's own, or a row of sfa_event_maps)
+std::string sam_record(const sfa_result_t &row, const int32_t *pairs, int32_t n_pairs, const char *read_id, const char *rname, const sfa_event_t *events,
                        int64_t qstart, int64_t qend, bool rna, bool secondary = false);  // secondary: FLAG | 256
 
 }  // namespace sfa

@@ -1,0 +1,11 @@
+// sdtw_inst_path32.hip -- explicit instantiations of the band fill behind sfa_event_maps (sdtw_path.hpp): 32 rows per lane
+#include "sdtw_path.hpp"
+
+namespace sfa {
+template __global__ void sdtw_path_fill_kernel<32, 64, false>(const PathArgs);
+template __global__ void sdtw_path_fill_kernel<32, 32, false>(const PathArgs);
+template __global__ void sdtw_path_fill_kernel<32, 16, false>(const PathArgs);
+template __global__ void sdtw_path_fill_kernel<32, 64, true>(const PathArgs);
+template __global__ void sdtw_path_fill_kernel<32, 32, true>(const PathArgs);
+template __global__ void sdtw_path_fill_kernel<32, 16, true>(const PathArgs);
+}  // namespace sfa

@@ -638,6 +638,11 @@ int enqueue_batch(sfa_ctx *c, Route route, const BatchArgs &a, const int64_t *q_
 
 // Core of every align entry point: queries already in HBM, results left in HBM.
 int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32_t n, ResultRow *d_out, ResultRow *d_sec) {
+    if (!c->in_slice && !c->no_segments_once) {  // the call sfa_event_maps refers to from now on (not: a slice or a re-run of it)
+        c->map_n = n;
+        c->map_q_off.assign(q_off, q_off + n + 1);
+        c->map_queries = d_queries;
+    }
     if (n == 0) return SFA_OK;
     // secondary mappings: the plain two-pass route (HBM snapshots, no column segments, pass 2 as its own launches), whose fill keeps
     // every read's top-5 list; the candidates behind the primary are traced by the same pass-2 kernel, one launch per rank
@@ -791,6 +796,7 @@ int sfa_submit_batch(sfa_ctx_t *c, const float *queries, const int64_t *q_off, i
             return sfa_submit_batch(c->shards[r], queries, q_off + lo, hi - lo);  // (q_off holds absolute offsets into queries)
         }, &c->shard_lo);  // (sfa_wait_batch collects by the same ranges)
         if (!rc) c->pending_n = n;
+        c->map_n = rc ? -1 : n;
         return rc;
     }
     HIP_TRY(hipSetDevice(c->device));

@@ -96,6 +96,8 @@ static int create_context(sfa_ctx **out, const HostRef &h, uint32_t flag, int de
     c->n_jobs = h.n_jobs;
     c->total_cols = h.total_cols;
     c->h_job_len = h.job_len;
+    c->h_job_off = h.job_off;
+    c->h_ref_off = h.ref_off;
     auto bail = [&](int rc) {
         sfa_destroy(c);
         return rc;
@@ -181,7 +183,7 @@ void sfa_destroy(sfa_ctx_t *c) {
                       &c->d_queries, &c->d_stage, &c->d_pbest, &c->d_pend, &c->d_pjob, &c->d_psecond, &c->d_wjob,
                       &c->d_wend, &c->d_wscore, &c->d_tst, &c->d_ck, &c->d_out, &c->e_raw, &c->e_rawoff, &c->e_scale, &c->e_sum,
                       &c->e_sumsq, &c->e_t1, &c->e_t2, &c->e_evoff, &c->e_evstart, &c->e_evlen, &c->e_evmean, &c->e_evstdv, &c->e_nev,
-                      &c->e_qstart, &c->e_qoff, &c->e_b0, &c->e_b1, &c->e_b2, &c->e_flag, &c->e_qev, &c->e_pflag, &c->d_verify, &c->d_segfail, &c->d_bndc, &c->d_long, &c->d_lbest, &c->d_lsecond, &c->d_lend, &c->d_lwin, &c->d_lck, &c->d_lprog, &c->d_lticket, &c->d_times, &c->d_ltimes, &c->d_started, &c->d_bad, &c->d_badcount, &c->d_bestrec, &c->d_beste, &c->d_gbest, &c->d_wchunk, &c->d_ticket, &c->d_quaddone, &c->d_args, &c->b_in, &c->b_inoff, &c->b_out, &c->b_outoff, &c->b_len, &c->b_head, &c->b_bad})
+                      &c->e_qstart, &c->e_qoff, &c->e_b0, &c->e_b1, &c->e_b2, &c->e_flag, &c->e_qev, &c->e_pflag, &c->d_verify, &c->d_segfail, &c->d_bndc, &c->d_long, &c->d_lbest, &c->d_lsecond, &c->d_lend, &c->d_lwin, &c->d_lck, &c->d_lprog, &c->d_lticket, &c->d_times, &c->d_ltimes, &c->d_started, &c->d_bad, &c->d_badcount, &c->d_bestrec, &c->d_beste, &c->d_gbest, &c->d_wchunk, &c->d_ticket, &c->d_quaddone, &c->d_args, &c->b_in, &c->b_inoff, &c->b_out, &c->b_outoff, &c->b_len, &c->b_head, &c->b_bad, &c->d_mv, &c->d_prow, &c->d_pairs, &c->d_pfirst})
         b->release();
     c->h_stage.release();
     c->h_out.release();
@@ -191,6 +193,7 @@ void sfa_destroy(sfa_ctx_t *c) {
     c->h_long.release();
     c->h_badcount.release();
     c->h_head.release();
+    c->h_pairs.release();
     for (auto &e : c->bev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : c->ev)
@@ -257,6 +260,9 @@ int sfa_set_option(sfa_ctx_t *c, const char *key, int64_t value) {
     } else if (k == "secondary") {
         if (value < 0 || value > 4) return fail(SFA_EINVAL, "secondary must be 0..4 (secondary mappings per read)");
         c->opt_secondary = value;
+    } else if (k == "map_scratch_bytes") {
+        if (value < 0) return fail(SFA_EINVAL, "map_scratch_bytes must be >= 0");
+        c->opt_map_scratch = value;
     } else if (k == "prio_unit") {
         if (value < 0 || value > (1 << 28)) return fail(SFA_EINVAL, "prio_unit must be 0 (off) .. 2^28");
         c->opt_prio_unit = value;

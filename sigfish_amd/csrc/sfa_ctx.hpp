@@ -2,6 +2,7 @@
 // buffers, the context, and the few internal functions that cross unit boundaries.
 //   sfa_context.hip  contexts: init / destroy, devices, options, profile, small utilities
 //   sfa_align.hip    the alignment stage: planner -> launches (wave kernels, row strips) -> rows; the batch entry points
+//   sfa_maps.hip     event maps of the last call's rows (sdtw_path.hpp)
 //   sfa_pre.hip      the stages in front of it on the device: raw samples / BLOW5 records in (events_kernels.hpp, blow5_kernels.hpp)
 // There is NO CPU fallback: every failure is reported through the return code + sfa_last_error().
 #pragma once
@@ -217,6 +218,8 @@ struct sfa_ctx {
     int32_t num_ref = 0, n_jobs = 0;
     int64_t total_cols = 0;  // sum over jobs of rlen
     std::vector<int32_t> h_job_len;
+    std::vector<int64_t> h_job_off;   // [n_jobs] column 0 of every (contig,strand) array in d_ref
+    std::vector<int32_t> h_ref_off;   // [num_ref] ref_st_offset
     DevBuf d_ref, d_job_off, d_job_len, d_job_contig, d_job_strand, d_ref_len, d_ref_off;
 
     // per-batch scratch
@@ -246,6 +249,14 @@ struct sfa_ctx {
     PinBuf h_badcount;
     DevBuf d_p5, d_swin, d_sts, d_sec;  // secondary mappings: top-5 partials, merged candidates, their traced columns, rows [n][4]
     int32_t sec_n = -1;   // reads of the last call whose secondaries d_sec holds
+    // event maps (sfa_event_maps): what the last align call left behind -- its read count (-1: none), the offsets of its queries and
+    // where they are (the context's d_queries, or the caller's memory after sfa_align_batch_device); a group context keeps the count
+    int32_t map_n = -1;
+    std::vector<int64_t> map_q_off;
+    const float *map_queries = nullptr;
+    int64_t opt_map_scratch = 2ll << 30;  // bytes of HBM the move matrices of one slice of rows may take
+    DevBuf d_mv, d_prow, d_pairs, d_pfirst;  // packed moves of a slice, its row descriptors, its maps, where every walk ended
+    PinBuf h_pairs;
     DevBuf d_started;     // counter of the fill's tasks that have begun (IssuePriority)
     DevBuf d_times;       // -DSFA_TASK_TIMES builds: start / end / SIMD position of every wave-task of the last fill
     int64_t n_times = 0;

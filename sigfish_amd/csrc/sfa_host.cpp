@@ -238,10 +238,31 @@ int sfa_sam_row_ex(char *buf, size_t cap, const sfa_result_t *r, const char *rea
                    int64_t qstart, int64_t qend, const float *ref_array, int32_t ref_len, int32_t ref_st_offset, uint32_t flag,
                    int secondary) {
     if (!buf || !r || !read_id || !rname || !events || !ref_array || qend <= qstart || !r->valid || r->rid < 0) return SFA_EINVAL;
-    const bool rna = (flag & SFA_RNA) != 0;
     const sfa::WarpPath path = path_of_row(r, events, qstart, qend, ref_array, ref_len, ref_st_offset, flag);
     if (path.px.empty()) return SFA_EINVAL;
-    const std::string line = sfa::sam_record(*r, path, read_id, rname, events, qstart, qend, rna, secondary != 0);
+    const std::vector<int32_t> pairs = sfa::path_to_pairs(path);
+    return sfa_sam_row_from_map(buf, cap, r, read_id, rname, events, qstart, qend, pairs.data(), static_cast<int32_t>(pairs.size() / 2),
+                                flag, secondary);
+}
+
+int sfa_sam_row_from_map(char *buf, size_t cap, const sfa_result_t *r, const char *read_id, const char *rname, const sfa_event_t *events,
+                         int64_t qstart, int64_t qend, const int32_t *pairs, int32_t n_pairs, uint32_t flag, int secondary) {
+    if (!buf || !r || !read_id || !rname || !events || !pairs || n_pairs <= 0 || qend <= qstart || !r->valid || r->rid < 0) return SFA_EINVAL;
+    // every index the formatter follows into the event table must lie inside the query window
+    const int32_t qlen = static_cast<int32_t>(qend - qstart);
+    for (int32_t i = 0; i < 2 * n_pairs; ++i)
+        if (pairs[i] < -1 || pairs[i] >= qlen) return SFA_EINVAL;
+    for (int32_t i = 0; i < n_pairs; ++i)
+        if ((pairs[2 * i] < 0) != (pairs[2 * i + 1] < 0)) return SFA_EINVAL;  // a column is mapped or blank, never half of each
+    // RNA: the formatter mirrors every index about the last column's stop (r2qevent_map_to_ss), so that one must be a real row
+    // and no index may lie beyond it; DNA reads the indices as they are (checked above)
+    if (flag & SFA_RNA) {
+        const int32_t end = pairs[2 * (n_pairs - 1) + 1];
+        if (end < 0) return SFA_EINVAL;
+        for (int32_t i = 0; i < 2 * n_pairs; ++i)
+            if (pairs[i] > end) return SFA_EINVAL;
+    }
+    const std::string line = sfa::sam_record(*r, pairs, n_pairs, read_id, rname, events, qstart, qend, (flag & SFA_RNA) != 0, secondary != 0);
     if (line.size() + 1 > cap) return SFA_ERANGE;
     memcpy(buf, line.c_str(), line.size() + 1);
     return static_cast<int>(line.size());

@@ -343,4 +343,49 @@ inline Route choose_route(const BatchPlan &p, bool std_dtw, int secondary, int64
     return Route::TwoPass;
 }
 
+// ---- event maps (sfa_event_maps, sdtw_path.hpp): move matrices of a batch's rows against a scratch budget ----
+
+// 32-bit words of packed moves per (step, lane) for a shape with R rows per lane: 2 bits per cell
+inline int map_words_per_lane(int R) { return R > 16 ? 2 : 1; }
+
+// Move matrix of one row in bytes: the band fill of a read of qlen events (<= kMaxQuery) over m columns runs m + lanes - 1
+// anti-diagonal steps, and every step stores one record of lanes * words 32-bit words
+inline int64_t map_row_bytes(int qlen, int32_t m) {
+    const ClassShape s = kClassShapes[class_for(qlen)];
+    return (static_cast<int64_t>(m) + s.lanes - 1) * s.lanes * map_words_per_lane(s.R) * 4;
+}
+
+struct MapSlices {
+    std::vector<int32_t> slice_begin;  // [n_slices + 1] into `order`
+    std::vector<int32_t> order;        // rows on the device, input order kept
+    std::vector<int32_t> host_rows;    // rows left to the host routine, input order kept
+    std::vector<int64_t> mv_off;       // [order.size()] byte offset of the row's moves inside its slice's scratch
+};
+
+// Cuts rows 0..n-1 (qlen[k] events x m[k] band columns; m[k] <= 0: nothing to do for row k) into consecutive slices whose move
+// matrices fit budget_bytes together.  A row of more than kMaxQuery events, or whose own matrix exceeds the budget, goes to
+// host_rows.  Every other row lands in exactly one slice; order is input order throughout.
+inline MapSlices plan_map_slices(const int32_t *qlen, const int32_t *m, int32_t n, int64_t budget_bytes) {
+    MapSlices s;
+    s.slice_begin.push_back(0);
+    int64_t used = 0;
+    for (int32_t k = 0; k < n; ++k) {
+        if (m[k] <= 0 || qlen[k] <= 0) continue;
+        const int64_t bytes = qlen[k] > kMaxQuery ? -1 : map_row_bytes(qlen[k], m[k]);
+        if (bytes < 0 || bytes > budget_bytes) {
+            s.host_rows.push_back(k);
+            continue;
+        }
+        if (used + bytes > budget_bytes) {
+            s.slice_begin.push_back(static_cast<int32_t>(s.order.size()));
+            used = 0;
+        }
+        s.order.push_back(k);
+        s.mv_off.push_back(used);
+        used += bytes;
+    }
+    if (static_cast<int32_t>(s.order.size()) > s.slice_begin.back()) s.slice_begin.push_back(static_cast<int32_t>(s.order.size()));
+    return s;
+}
+
 }  // namespace sfa

@@ -38,7 +38,8 @@ static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_o
     if (query_size <= 0) return fail(SFA_EINVAL, "sfa_align_raw: query_size must be positive");
     if (n == 0) return SFA_OK;
     if (!c->shards.empty()) {
-        return for_each_shard_range(c, n, [&](size_t r, int32_t a, int32_t b) {
+        c->map_n = -1;
+        const int grc = for_each_shard_range(c, n, [&](size_t r, int32_t a, int32_t b) {
             std::vector<int64_t> off(b - a + 1);  // the shard's sample offsets start at 0
             for (int32_t i = a; i <= b; ++i) off[i - a] = raw_off[i] - raw_off[a];
             if (!raw) return fail(SFA_EINVAL, "sfa_align_raw: device-resident samples need a single-device context");
@@ -46,6 +47,8 @@ static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_o
                                     query_size, rows + a, info + a,
                                     query_events ? query_events + static_cast<size_t>(a) * static_cast<size_t>(query_size) : nullptr);
         });
+        if (!grc) c->map_n = n;  // (sfa_event_maps splits its rows by the same ranges)
+        return grc;
     }
     HIP_TRY(hipSetDevice(c->device));
     if (raw) HIP_TRY(hipStreamSynchronize(c->stream));  // (device-resident samples: their decoder is still in flight on this stream)
@@ -254,13 +257,16 @@ int sfa_align_blow5(sfa_ctx_t *c, const uint8_t *records, const int64_t *rec_off
     if (query_size <= 0) return fail(SFA_EINVAL, "sfa_align_blow5: query_size must be positive");
     if (n == 0) return SFA_OK;
     if (!c->shards.empty()) {
-        return for_each_shard_range(c, n, [&](size_t r, int32_t a, int32_t b) {
+        c->map_n = -1;
+        const int grc = for_each_shard_range(c, n, [&](size_t r, int32_t a, int32_t b) {
             std::vector<int64_t> off(b - a + 1);
             for (int32_t i = a; i <= b; ++i) off[i - a] = rec_off[i] - rec_off[a];
             return sfa_align_blow5(c->shards[r], records + rec_off[a], off.data(), b - a, record_zlib, signal_svb, prefix_size, query_size,
                                    rows + a, info + a, heads + a,
                                    query_events ? query_events + static_cast<size_t>(a) * static_cast<size_t>(query_size) : nullptr);
         });
+        if (!grc) c->map_n = n;
+        return grc;
     }
     if (rec_off[0] != 0) return fail(SFA_EINVAL, "sfa_align_blow5: rec_off must start at 0");
     for (int32_t i = 0; i < n; ++i)
