@@ -109,6 +109,10 @@ typedef struct {
     int64_t trace_margin;  /* head start of pass 2 in steps (a whole query + lanes, or less: see "trace_margin") */
     int64_t fused_trace;   /* 1: pass 2 ran inside the fill launch by ticket (fill_ms covers both, trace_ms is 0) -- the LDS-checkpoint
                               fill or the 32-row fill */
+    int64_t lck_fallbacks; /* with lds_ckpt: reads of the batch whose path began before the snapshot the fill saved for their winning
+                              window, so that pass 2 went on to the sparse HBM store (thousands of steps each) */
+    int64_t lck_from_scratch; /* with lds_ckpt: reads whose winning window is one of the first two of its strand: no snapshot, pass 2
+                                 walks the strand from its start (at most two windows) */
 } sfa_profile_t;
 
 /* How a batch is laid out on the device (host logic only; needs no GPU). */
@@ -210,8 +214,9 @@ int sfa_align_events(sfa_ctx_t *ctx, const sfa_event_t *const *events, const int
  *                             least this many reads, run back to back (default 65536)
  *   pass 1 -> pass 2 hand-over
  *     "lds_ckpt"              1 = default: where every shape of the batch has <= 16 rows per lane (queries up to 256 events) the fill
- *                             keeps its last two snapshots in LDS and writes one to HBM only when a window becomes a read's best so
- *                             far, plus a sparse store every 32768 steps for pass 2 to back off to (--dtw-std: the sparse store
+ *                             keeps every read's last two snapshots in LDS, taken where the read's own windows end, and writes the
+ *                             older one to HBM only when a window becomes the read's best so far (pass 2 then starts one own window
+ *                             in front of it), plus a sparse store every 32768 steps for pass 2 to back off to (--dtw-std: the sparse store
  *                             alone); 2 = the same whatever the batch size and up to 1024 events at 16 rows per lane; 0 = every
  *                             snapshot to HBM.  Shapes with 32 rows per lane always keep their snapshots in HBM.
  *     "fused_trace"           1 = default: pass 2 runs inside the fill launch (tickets) when the launch has more wave-tasks than the
@@ -221,7 +226,9 @@ int sfa_align_events(sfa_ctx_t *ctx, const sfa_event_t *const *events, const int
  *     "trace_margin"          -1 = auto: pass 2 starts a query length (+ lanes) in front of the winning window -- on the HBM-snapshot
  *                             route as far as 99.9 % of the PREVIOUS batch's alignments spanned, rounded up to the next sixteenth of
  *                             the query, + 1/16 query + lanes + 16; a read whose path is longer backs off one snapshot; >= 0: that
- *                             many steps
+ *                             many steps.  On the LDS route the head start follows from the windows (one own window less the lane
+ *                             skew: sfa_profile_t.trace_margin reports the longest read's) and the option only bounds what pass 2
+ *                             asks of the sparse store when it backs off
  *   launch
  *     "prio_unit"             columns per level of the fill's longest-remaining-first issue priority in the tail of a launch
  *                             (default 2048; 0 = off)

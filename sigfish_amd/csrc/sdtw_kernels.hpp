@@ -121,8 +121,8 @@ struct DpArgs {
     unsigned *g_best;
     int32_t *w_chunk;
     int32_t best_planes;   // planes per record (R of the largest class + 1)
-    int32_t coarse_every;  // every coarse_every-th LDS snapshot also goes to the HBM checkpoint store (ck_shift = lck_shift + log2 of it)
-    int32_t lck_shift;     // LDS snapshots every 1 << lck_shift steps (9, 10 or 11 by the longest query of the batch)
+    unsigned *lck_stats;   // [2] reads of the batch whose pass 2 left the saved record for the sparse store / started from scratch
+                           // because their window is one of the first two of its strand (sfa_profile_t.lck_fallbacks, lck_from_scratch)
     // fused launch (FUSED kernels): waves claim tickets; tickets < n_tasks are fill tasks, ticket n_tasks + q is pass 2 of quad q,
     // which waits until quad_done[q] == n_chunks.  Rows are written by the pass-2 waves (tables as FinalizeArgs).
     const struct DpArgs *self;  // this very block in device memory: what the pass-2 function of the fused launch reads (see there)
@@ -531,42 +531,42 @@ __device__ __forceinline__ constexpr int ck_planes() { return R + 2; }
 
 // Rolling checkpoints in LDS (the LCK kernels).  Pass 2 only ever restores ONE snapshot per read -- the one in front of the
 // window that finally wins -- yet the plain scheme spills every snapshot of every quad to HBM (13 GB per 100 000-read
-// launch).  Here a wave keeps its last two snapshots (every 512 steps) in LDS and copies one to HBM only when a window has
-// just become a read's best so far (a handful of times per read): the snapshot pass 2 would pick for that window, i.e. the
-// last one taken at least trace_margin + 3 steps before the window's first cell.  The host caps the margin at
-// 512 - qlen - 3, so that snapshot is always one of the two on hand (see save()).  A save is skipped when another task of
-// the same read has already seen a strictly better score (g_best, atomic min over float bits): that window cannot win.
-// What the record of a (quad, chunk) holds at the end is the snapshot for the chunk's best window whenever that window can
-// be the read's winner.  If the path turns out to start before the snapshot, pass 2 backs off to the sparse HBM
-// checkpoints (every coarse_every-th snapshot is also stored there, as before) and finally to the start of the strand.
-constexpr int kLdsCkShift = 9;   // the SHORTEST interval between two LDS snapshots (queries up to 256 events); DpArgs::lck_shift is the batch's: the
-                                 // smallest of 512 / 1024 / 2048 steps that holds a window + the head start of pass 2 (see LdsCkpt::save)
+// launch).  Here every read keeps its last two snapshots in LDS, taken where ITS OWN windows end: the sweep is cut there anyway
+// (sweep_job), blocks of four restart at a cut, so the state before the next step is a legal snapshot, and only the lanes of the
+// read whose window ends write it.  When a window has just become a read's best so far (a handful of times per read) the OLDER
+// of the two goes to HBM: it was taken where the window before this one began, i.e. with the last query row at column ws - q and
+// row 0 at about ws - q + q/R, so pass 2 starts exactly one own window -- less the lane skew -- in front of its window, whatever
+// the window.  The first two windows of a job have no such snapshot and start from scratch (rec_e = -1).  A save is skipped when
+// another task of the same read has already seen a strictly better score (g_best, atomic min over float bits): that window
+// cannot win.  What the record of a (quad, chunk) holds at the end is the snapshot for the chunk's best window whenever that
+// window can be the read's winner.  If the path turns out to start before the snapshot, pass 2 backs off to the sparse HBM
+// checkpoints (sweep_job stores one per interval T, as before) and finally to the start of the strand.
 constexpr int kLdsCkPlanes = 17;  // R <= 16 costs + dprev
 struct LdsCkpt {
-    float *buf;        // this lane's column of the wave's two buffers: buf[(j & 1) * kLdsCkPlanes * 64 + plane * 64]
-    int count;         // snapshots taken in the current job (1-based index of the last one)
-    int e0, e1;        // step index of the snapshot held by buffer 0 / 1
-    float *rec;        // this lane's column of the task's HBM record
-    int32_t *rec_e;    // [4] per slot
-    unsigned *g_best;  // this lane's read (valid where owner)
-    __device__ __forceinline__ void begin_job() { count = 0; }
+    float *buf;              // this lane's column of the wave's two buffers: buf[j * kLdsCkPlanes * 64 + plane * 64]
+    unsigned long long par;  // lanes whose read writes its NEXT snapshot to buffer 1 (whole slots; wave-uniform)
+    float *rec;              // this lane's column of the task's HBM record
+    int32_t *rec_e;          // [4] per slot
+    unsigned *g_best;        // this lane's read (valid where owner)
+    __device__ __forceinline__ void begin_job() { par = 0; }
+    // at a cut of the sweep, after save(): the lanes of the reads whose window ends there (endmask, whole slots) store their
+    // state -- the one before the next step -- over the older of their two snapshots
     template <int R, typename CV>
-    __device__ __forceinline__ void snapshot(const CV &cv, float dprev, int e) {
-        count += 1;
-        float *b = buf + (count & 1) * (kLdsCkPlanes * 64);
+    __device__ __forceinline__ void snapshot(const unsigned long long endmask, const CV &cv, const float dprev) {
+        const int lane = threadIdx.x & 63;
+        if ((endmask >> lane) & 1) {
+            float *b = buf + static_cast<int>((par >> lane) & 1) * (kLdsCkPlanes * 64);
 #pragma unroll
-        for (int r = 0; r < R; ++r) b[r * 64] = cv[r];
-        b[R * 64] = dprev;
-        if (count & 1)
-            e1 = e;
-        else
-            e0 = e;
+            for (int r = 0; r < R; ++r) b[r * 64] = cv[r];
+            b[R * 64] = dprev;
+        }
+        par ^= endmask;
     }
-    // at the end of a window that began at step e_ws (steps since t_begin; per lane: the value of the lane's read) and became the
-    // best of some read(s) of the quad: improved = ballot of the lanes owning the last query row of those reads.  All 64 lanes
-    // are active here.
+    // at the end of a window that began at last-row column ws (per lane: the value of the lane's read, whose own length is myq) and
+    // became the best of some read(s) of the quad: improved = ballot of the lanes owning the last query row of those reads.
+    // e_main: steps from the sweep's origin to last-row column 0.  All 64 lanes are active here.
     template <int R, int L, bool WT = false>  // WT: write-through stores (the fused launch reads the record in the same launch)
-    __device__ __forceinline__ void save(unsigned long long improved, float wmin, int e_ws, int margin, int lq, int job, int shift) {
+    __device__ __forceinline__ void save(unsigned long long improved, float wmin, int ws, int myq, int e_main, int lq) {
         const int lane = threadIdx.x & 63;
         const int owner_lane = (lane & ~(L - 1)) + lq;
         const bool mine = (improved >> owner_lane) & 1;
@@ -575,12 +575,11 @@ struct LdsCkpt {
         if (mine && lane == owner_lane) old = atomicMin(g_best, wb);
         old = __shfl(old, owner_lane);
         if (!(mine && wb <= old)) return;
-        // the snapshot pass 2 would choose: index kk = floor((e_ws - margin - 3) / S), S = 1 << shift, taken at the first block
-        // boundary at or after kk * S.  margin <= S - wl - 3, hence kk >= count - 1: still in its buffer.
-        const int from = e_ws - margin - 3;
-        const int kk = from > 0 ? (from >> shift) : 0;
-        if (kk > 0) {
-            const float *b = buf + (kk & 1) * (kLdsCkPlanes * 64);
+        // the read's snapshots were taken where its windows began: the newer one at column ws, the older one at ws - myq -- the one
+        // pass 2 wants, in the buffer the next snapshot will overwrite.  It exists from the third window of a job on.
+        const bool have = ws >= 2 * myq;
+        if (have) {
+            const float *b = buf + static_cast<int>((par >> lane) & 1) * (kLdsCkPlanes * 64);
 #pragma unroll
             for (int r = 0; r <= R; ++r) {
                 if (WT)
@@ -590,13 +589,12 @@ struct LdsCkpt {
             }
         }
         if (lane == owner_lane) {
-            const int ev = kk > 0 ? ((kk & 1) ? e1 : e0) : -1;
+            const int ev = have ? e_main + ws - myq : -1;  // steps elapsed since t_begin when that snapshot was taken
             if (WT)
                 __hip_atomic_store(rec_e + lane / L, ev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             else
                 rec_e[lane / L] = ev;
         }
-        (void)job;
     }
 };
 
@@ -626,34 +624,11 @@ __device__ __forceinline__ void sweep_job(const DpArgs &a, const float *yp, cons
     // begin anywhere in the strand, so the state a few hundred steps in front of it is no use; pass 2 starts from the sparse HBM
     // store (interval T, tens of thousands of steps) or from the start of the strand, which for a transcriptome is the same
     constexpr bool SNAP = LCK && !STD;
-    if (SNAP) {
-        lck->begin_job();
-        ck_next = 1 << a.lck_shift;
-    }
+    if (SNAP) lck->begin_job();
+    // SNAP: every snapshot is taken at a cut of the window loop below (the reads' own in LDS, the sparse HBM store's), so the
+    // blocks of four steps carry no checkpoint test at all
     auto maybe_checkpoint = [&]() {  // at a block boundary: snapshot the state BEFORE step t_begin + e
-        if (SNAP) {
-            if (e >= ck_next) {
-                lck->template snapshot<R>(cv, dprev, e);
-                ck_next += 1 << a.lck_shift;
-                // every coarse_every-th one also goes to the sparse HBM store (what pass 2 backs off to), same format as below;
-                // write-through in the fused launch, whose pass 2 reads it in the same launch, possibly from another XCD (found by
-                // the fuzz campaign: a stale record there sent pass 2 off with a garbage step index)
-                if (T && (lck->count & (a.coarse_every - 1)) == 0 && (lck->count << a.lck_shift) <= ck_last) {
-                    if (WT) {
-#pragma unroll
-                        for (int r = 0; r < R; ++r) __hip_atomic_store(ckp + r * 64, static_cast<float>(cv[r]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(ckp + R * 64, dprev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(ckp + (R + 1) * 64, __int_as_float(e), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < R; ++r) ckp[r * 64] = cv[r];
-                        ckp[R * 64] = dprev;
-                        ckp[(R + 1) * 64] = __int_as_float(e);
-                    }
-                    ckp += ck_planes<R>() * 64;
-                }
-            }
-        } else if (T) {
+        if (!SNAP && T) {
             if (e >= ck_next && ck_next <= ck_last) {
                 if (WT) {  // read by the pass-2 waves of the same launch
                     store_record_wt<R>(ckp, cv, dprev, e);
@@ -723,6 +698,28 @@ __device__ __forceinline__ void sweep_job(const DpArgs &a, const float *yp, cons
         for (int sl = 1; sl < NS; ++sl) nxt = min(nxt, we_s[sl]);
         const int wl = STD ? rlen : nxt - col;  // std_dtw has a single candidate: one "window"
         const int nb = wl >> 2, rm = wl & 3;
+        if (SNAP && T) {
+            // sparse HBM store (what pass 2 backs off to): record k is the state at the LAST cut of the wave at or before step k*T
+            // since t_begin -- the next cut lies beyond it -- so it is never later than pass 2 assumes when it picks k (trace_core)
+            // and at most a window earlier.  Same format as the plain scheme's; write-through in the fused launch, whose pass 2
+            // reads it in the same launch, possibly from another XCD (found by the fuzz campaign: a stale record there sent pass 2
+            // off with a garbage step index)
+            while (e + wl > ck_next && ck_next <= ck_last) {
+                if (WT) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) __hip_atomic_store(ckp + r * 64, static_cast<float>(cv[r]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(ckp + R * 64, dprev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(ckp + (R + 1) * 64, __int_as_float(e), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) ckp[r * 64] = cv[r];
+                    ckp[R * 64] = dprev;
+                    ckp[(R + 1) * 64] = __int_as_float(e);
+                }
+                ckp += ck_planes<R>() * 64;
+                ck_next += T;
+            }
+        }
         // 16-row shapes: only the window MINIMUM is kept (one v_min per step); which column attains it first is settled in pass 2
         // for the single window that wins.  32-row shapes (CELL) also keep the column of the first strict minimum
         // (src/sigfish.c:892-899).
@@ -788,9 +785,10 @@ __device__ __forceinline__ void sweep_job(const DpArgs &a, const float *yp, cons
             if constexpr (SEC) {
                 if (ending && owner) top5_offer(t5, wmin, CELL ? wpos : wsl, job);
             }
-            if (LCK) {
+            if (SNAP) {  // the older snapshot of a read whose window became its best goes to HBM; only then the new one replaces it
                 const unsigned long long improved = __ballot(became_best && owner);
-                if (improved) lck->template save<R, L, WT>(improved, wmin, wsl + e_main, a.trace_margin, lq, job, a.lck_shift);
+                if (improved) lck->template save<R, L, WT>(improved, wmin, wsl, mq.myq, e_main, lq);
+                lck->template snapshot<R>(endmask, cv, dprev);
             }
             wmin = ending ? INFINITY : wmin;
             if (CELL) wpos = ending ? nxt : wpos;
@@ -888,7 +886,6 @@ __device__ __forceinline__ void fill_body(const DpArgs &a, const ClassDesc cd, c
         lck.rec = a.best_rec + task * a.best_planes * 64 + lane;
         lck.rec_e = a.best_e + task * 4;
         lck.g_best = a.g_best + (read >= 0 ? read : 0);
-        lck.e0 = lck.e1 = 0;
         if (g == lq && read >= 0) {  // nothing saved yet: pass 2 starts the strand from scratch
             if (FUSED)
                 __hip_atomic_store(lck.rec_e + slot, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1143,7 +1140,7 @@ __device__ __forceinline__ void fill_body_seg(const DpArgs &a, const ClassDesc c
 template <int MAXR, bool STD, bool LCK>
 __device__ __attribute__((noinline)) void fused_trace_dispatch(const DpArgs *pa, const int quad, float *lds_f, int *lds_i, float *lds_x);
 
-// LCK: rolling checkpoints in LDS (LdsCkpt) -- two snapshots of 17 planes per wave, 34 KB per block, four blocks per CU.
+// LCK: rolling checkpoints in LDS (LdsCkpt) -- two snapshots of 17 planes per read, 34 KB per block, four blocks per CU.
 // FUSED (with LCK, or on the 32-row fill, whose snapshots go to HBM write-through): pass 2 rides in the same launch.  Waves claim TICKETS from a counter instead of deriving their task from
 // blockIdx: tickets below n_tasks are the fill tasks, in the usual order; ticket n_tasks + q is pass 2 of quad q, which waits
 // until every fill task of that quad has signalled completion, merges their partial results (what sdtw_finalize_kernel
@@ -1362,7 +1359,8 @@ __device__ __forceinline__ void trace_core(const DpArgs &a, const ClassDesc cd, 
         rec_e = a.best_e[task * 4 + slot];
         recp = a.best_rec + task * a.best_planes * 64 + lane;
         use_rec = rec_e >= 0;
-        if (!use_rec) k = 0;  // the fill chose "from scratch" for this window (it lies within the first 512 + margin steps)
+        if (!use_rec && g == lq) atomicAdd(a.lck_stats + 1, 1u);
+        if (!use_rec) k = 0;  // the fill chose "from scratch" for this window (one of the first two of its strand)
     }
 
     for (int attempt = 0; attempt < 48; ++attempt) {  // bounded: k reaches 0 after <= 32 halvings
@@ -1451,6 +1449,7 @@ __device__ __forceinline__ void trace_core(const DpArgs &a, const ClassDesc cd, 
                 done = true;
             } else if (LCK && use_rec) {  // the path starts before the saved snapshot: on to the sparse store (k), then 0
                 use_rec = false;
+                if (g == lq) atomicAdd(a.lck_stats, 1u);
             } else {  // the path starts before this checkpoint: back off (1, 2, 4, ... checkpoints)
                 k = max(0, k - back);
                 back <<= 1;

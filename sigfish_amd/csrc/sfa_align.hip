@@ -251,6 +251,8 @@ int align_sliced(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32
         sum.n_tasks += c->prof.n_tasks;
         sum.n_chunks = std::max(sum.n_chunks, c->prof.n_chunks);
         sum.non_finite_reads += c->prof.non_finite_reads;
+        sum.lck_fallbacks += c->prof.lck_fallbacks;
+        sum.lck_from_scratch += c->prof.lck_from_scratch;
     }
     c->prof = sum;
     return SFA_OK;
@@ -400,8 +402,6 @@ BatchArgs batch_args(sfa_ctx *c, const float *d_queries, int32_t n, ResultRow *d
     da.g_best = c->d_gbest.as<unsigned>();
     da.w_chunk = c->d_wchunk.as<int32_t>();
     da.best_planes = sfa::kLdsCkPlanes;
-    da.lck_shift = plan.lck_shift;
-    da.coarse_every = (lds(route) && plan.ck_shift >= plan.lck_shift) ? (1 << (plan.ck_shift - plan.lck_shift)) : 1;
     da.ticket = c->d_ticket.as<unsigned>();
     da.quad_done = c->d_quaddone.as<int32_t>();
     da.n_quads_total = n_quads;
@@ -415,6 +415,7 @@ BatchArgs batch_args(sfa_ctx *c, const float *d_queries, int32_t n, ResultRow *d
     da.prio_unit = static_cast<int32_t>(c->opt_prio_unit);
     da.started = c->d_started.as<unsigned>();
     da.err = c->d_badcount.as<unsigned>() + 4;
+    da.lck_stats = c->d_badcount.as<unsigned>() + 2;
     {   // a pass-2 wave legitimately waits for as long as one fill task of its quad runs: never less than ~5x that (1 us per
         // column of the longest chunk, against 0.2 measured), however small the option -- a 250 Mb strand is minutes, not a hang
         int64_t longest = 0;
@@ -585,7 +586,7 @@ int enqueue_batch(sfa_ctx *c, Route route, const BatchArgs &a, const int64_t *q_
     if (da.prio_unit > 0) HIP_TRY(hipMemsetAsync(c->d_started.p, 0, 4, st));
     HIP_TRY(hipEventRecord(c->ev[0], st));
     // reads with a NaN / inf query value are skipped (the reference aborts on them, see sdtw_screen_kernel)
-    HIP_TRY(hipMemsetAsync(c->d_badcount.p, 0, 32 + 4 * sfa::kSpanBuckets, st));  // word 0: non-finite reads; words 4..6: error words of the in-launch waits; words 8..39: span histogram
+    HIP_TRY(hipMemsetAsync(c->d_badcount.p, 0, 32 + 4 * sfa::kSpanBuckets, st));  // word 0: non-finite reads; words 4..6: error words of the in-launch waits; words 2..3: LDS route, reads that left their record / started from scratch; words 8..39: span histogram
     hipLaunchKernelGGL(sfa::sdtw_screen_kernel, dim3((da.n_reads_total + 3) / 4), dim3(256), 0, st, da.queries, da.q_off, da.n_reads_total, c->d_bad.as<uint8_t>(),
                        c->d_badcount.as<unsigned>());
     KERNEL_TRY();
@@ -737,6 +738,8 @@ int sfa::resolve_profile(sfa_ctx *c) {
         c->eev_pending = false;
     }
     c->prof.non_finite_reads = c->h_badcount.p ? *c->h_badcount.as<unsigned>() : 0;  // (copied before ev[4], which has been waited for)
+    c->prof.lck_fallbacks = c->h_badcount.p ? c->h_badcount.as<unsigned>()[2] : 0;
+    c->prof.lck_from_scratch = c->h_badcount.p ? c->h_badcount.as<unsigned>()[3] : 0;
     c->prof.fill_ms = a;
     c->prof.trace_ms = d;
     c->prof.finalize_ms = t - a - d;

@@ -341,6 +341,8 @@ int sfa_get_profile(sfa_ctx_t *c, sfa_profile_t *p) {
             sum.ckpt_bytes += q.ckpt_bytes;
             sum.segment_reruns += q.segment_reruns;
             sum.non_finite_reads += q.non_finite_reads;
+            sum.lck_fallbacks += q.lck_fallbacks;
+            sum.lck_from_scratch += q.lck_from_scratch;
             sum.ckpt_interval = std::max(sum.ckpt_interval, q.ckpt_interval);
             sum.n_chunks = std::max(sum.n_chunks, q.n_chunks);
             sum.n_segments = std::max(sum.n_segments, q.n_segments);

@@ -65,7 +65,7 @@ struct PlanParams {
     bool allow_segments = true;     // false for std_dtw (its first row is cumulative: no finite memory)
     int lds_ckpt = 0;               // 1: rolling checkpoints in LDS + sparse HBM checkpoints (sdtw_kernels.hpp, LdsCkpt) where the shapes allow (queries up to
                                     // 256 events: the measured regime) and the batch size suits; 2: wherever the shapes allow (up to 1024 events at 16 rows per lane)
-    bool std_dtw = false;           // --dtw-std: with lds_ckpt the fill keeps NO LDS snapshots, only the sparse HBM store (the margin is not capped)
+    bool std_dtw = false;           // --dtw-std: with lds_ckpt the fill keeps NO LDS snapshots, only the sparse HBM store (the margin stays the option's)
     bool skip_long = false;         // true: reads of more than kMaxQuery events are left out (the caller runs them in row strips, sdtw_strips.hpp)
 };
 
@@ -76,7 +76,6 @@ struct PlanClass {
 
 struct BatchPlan {
     int32_t n_quads = 0, n_chunks = 1, max_R = 4, max_lanes = 16, widening = 1, ck_shift = 0, trace_margin = 0;
-    int32_t lck_shift = 9;  // with lds_ckpt: log2 of the interval between two LDS snapshots (9, 10, 11 for queries up to 256, 512, 1024 events)
     int32_t n_seg = 1, warm_windows = 4;  // column segments per job (sdtw_kernels.hpp, sweep_segment)
     bool lds_ckpt = false;  // the fill keeps its snapshots in LDS; ck_shift is then the interval of the sparse HBM store
     int64_t ck_floats = 0, query_events = 0;
@@ -92,7 +91,7 @@ struct BatchPlan {
     std::vector<int32_t> s_qlen, s_count, s_fill_pos, s_slot_start, s_len_quad_base;
     std::vector<int8_t> s_per_shift;
     void reset() {  // scalars back to their defaults; vectors keep their capacity
-        n_quads = 0; n_chunks = 1; max_R = 4; max_lanes = 16; widening = 1; ck_shift = 0; trace_margin = 0; lck_shift = 9;
+        n_quads = 0; n_chunks = 1; max_R = 4; max_lanes = 16; widening = 1; ck_shift = 0; trace_margin = 0;
         n_seg = 1; warm_windows = 4;
         lds_ckpt = false;
         ck_floats = 0; query_events = 0;
@@ -268,18 +267,19 @@ inline int plan_batch(const int64_t *q_off, int32_t n, const std::vector<int32_t
     p.job_ck_off.assign(n_jobs + 1, 0);
     p.trace_margin = static_cast<int32_t>(pp.trace_margin >= 0 ? pp.trace_margin : maxq + p.max_lanes);
     const bool adapt = pp.trace_margin < 0 && pp.span_sixteenths > 0;  // (applied below, once the checkpoint route is known)
-    // LDS checkpoints: every shape of the batch must hold its state in 17 planes (R <= 16), one sweep per (quad, job); the
-    // margin is capped so that the snapshot pass 2 wants for a window is one of the last two (LdsCkpt::save):
-    // interval (512 / 1024 / 2048 by the longest query) >= window length + margin + 3
+    // LDS checkpoints: every shape of the batch must hold its state in 17 planes (R <= 16), one sweep per (quad, job).  The
+    // head start of pass 2 is no parameter there: every read's snapshots are taken where its own windows end and the one saved
+    // for a window is the one taken a window before it began (LdsCkpt::save), so query row 0 starts one own window less the lane
+    // skew (rows / rows per lane) in front of the window.  trace_margin says so -- the longest read's -- and is what pass 2 asks of
+    // the sparse HBM store when it backs off; a smaller option value still applies to that store.
     p.lds_ckpt = pp.lds_ckpt && pp.ckpt_interval == 0 && p.max_R <= 16 && p.n_seg == 1 && n_quads > 0 && maxq <= (pp.lds_ckpt >= 2 ? 1024 : 256);
-    p.lck_shift = maxq <= 256 ? 9 : (maxq <= 512 ? 10 : 11);
     {   // the LDS buffers cap the fill at four waves per SIMD instead of six: a batch whose tasks are all resident at six
         // but not at four would need a second round (measured: 8 192 reads 7.35 -> 7.65 ms); everything else gains
         // (16 384 reads 13.7 -> 13.4 ms, 100 000 reads 74.6 -> 73.5 ms)
         const int64_t tasks = static_cast<int64_t>(n_quads) * p.n_chunks;
         if (pp.lds_ckpt < 2 && tasks > 4 * pp.n_sims && tasks <= 6 * pp.n_sims) p.lds_ckpt = false;
     }
-    if (p.lds_ckpt && !pp.std_dtw) p.trace_margin = std::min<int32_t>(p.trace_margin, (1 << p.lck_shift) - maxq - 3);
+    if (p.lds_ckpt && !pp.std_dtw) p.trace_margin = std::min<int32_t>(p.trace_margin, maxq - (maxq - 1) / p.max_R);
     // Snapshots in HBM every 512 steps (the 32-row shapes): a head start that turns out too short costs one more attempt from the
     // snapshot before, so it can follow what alignments actually span (event detection over-segments: ~2/3 of a column per event)
     // instead of a whole query length.  Not on the LDS route: there a miss falls back to the sparse store or the strand's start.
