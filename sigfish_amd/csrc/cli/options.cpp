@@ -1,0 +1,201 @@
+// options.cpp -- the options of `sigfish-amd dtw` (src/dtw_main.c:125-277): table, help and the checks between options.
+// Nothing here opens a file or touches a device, so -V and help may exit() from here.
+#include <getopt.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "../../../include/sigfish_amd.h"
+#include "cli.hpp"
+
+namespace cli {
+namespace {
+
+// long options without a letter (getopt_long returns these; the letters return themselves)
+enum LongOpt {
+    O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
+    O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
+    O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS
+};
+
+const option kLongOptions[] = {
+    {"threads", required_argument, 0, 't'}, {"batchsize", required_argument, 0, 'K'}, {"max-bytes", required_argument, 0, 'B'},
+    {"verbose", required_argument, 0, 'v'}, {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'V'},
+    {"kmer-model", required_argument, 0, O_KMER_MODEL}, {"output", required_argument, 0, 'o'}, {"rna", no_argument, 0, O_RNA},
+    {"prefix", required_argument, 0, 'p'}, {"query-size", required_argument, 0, 'q'}, {"debug-break", required_argument, 0, O_DEBUG_BREAK},
+    {"dtw-std", no_argument, 0, O_DTW_STD}, {"invert", no_argument, 0, O_INVERT}, {"full-ref", no_argument, 0, O_FULL_REF},
+    {"from-end", no_argument, 0, O_FROM_END}, {"profile-cpu", required_argument, 0, O_PROFILE_CPU}, {"accel", required_argument, 0, O_ACCEL},
+    {"sam", no_argument, 0, 'a'}, {"pore", required_argument, 0, O_PORE}, {"device", required_argument, 0, O_DEVICE},
+    {"secondary", required_argument, 0, O_SECONDARY}, {"window", required_argument, 0, 'w'}, {"meth-model", required_argument, 0, O_METH_MODEL},
+    {"host-events", no_argument, 0, O_HOST_EVENTS}, {"streams", required_argument, 0, O_STREAMS}, {"host-parse", no_argument, 0, O_HOST_PARSE},
+    {"gpu-parse", no_argument, 0, O_GPU_PARSE}, {"ranks", required_argument, 0, O_RANKS}, {"shard", required_argument, 0, O_SHARD},
+    {"read-range", required_argument, 0, O_READ_RANGE}, {"no-header", no_argument, 0, O_NO_HEADER},
+    {"rank-buffer", required_argument, 0, O_RANK_BUFFER}, {"host-paths", no_argument, 0, O_HOST_PATHS},
+    {"device-paths", no_argument, 0, O_DEVICE_PATHS},
+    {0, 0, 0, 0}};
+
+bool yes_or_no(const char *arg, const char *what) {  // yes_or_no(), src/dtw_main.c:92-113
+    if (!strcmp(arg, "yes") || !strcmp(arg, "y")) return true;
+    if (!strcmp(arg, "no") || !strcmp(arg, "n")) return false;
+    die(std::string("option '--") + what + "' only accepts 'yes' or 'no'.");
+}
+
+int64_t parse_num(const char *s) {  // K/M/G suffixes as src/dtw_main.c:46-58
+    char *e;
+    double x = strtod(s, &e);
+    if (*e == 'G' || *e == 'g')
+        x *= 1e9;
+    else if (*e == 'M' || *e == 'm')
+        x *= 1e6;
+    else if (*e == 'K' || *e == 'k')
+        x *= 1e3;
+    return static_cast<int64_t>(x + .499);
+}
+
+void help(FILE *fp, const Opt &o) {
+    fprintf(fp, "Usage: sigfish-amd dtw [OPTIONS] genome.fa reads.blow5|reads.slow5\n\nbasic options:\n");
+    fprintf(fp, "   -t INT                     number of host threads for parsing and event detection [%d]\n", o.threads);
+    fprintf(fp, "   -K INT                     batch size (max number of reads loaded at once) [%d]\n", o.batch_size);
+    fprintf(fp, "   -B FLOAT[K/M/G]            max number of bytes loaded at once [%.1fM]\n", o.batch_bytes / 1e6);
+    fprintf(fp, "   -h                         help\n   -o FILE                    output to file [stdout]\n");
+    fprintf(fp, "   --verbose INT              verbosity level [%d]\n   --version                  print version\n", o.verbosity);
+    fprintf(fp, "   --pore STR                 set the pore chemistry (r9, r10 or rna004) [auto]\n");
+    fprintf(fp, "   --device INT[,INT...]      GPU(s) to use; batches are dealt to them in turn [0]\n   --host-events              detect events on host threads instead of the GPU\n   --gpu-parse | --host-parse decompress and parse the records on the GPU | on host threads [host threads up to 2 GPUs per process, GPU beyond]\n   --streams INT              device contexts taking batches in turn [2]\n");
+    fprintf(fp, "   --ranks INT                read-shard the run over INT processes (rank r: device r of the list, -t/INT threads, the r-th\n"
+                "                              byte slice of the file, which must be a regular file); output is printed in rank order = file\n"
+                "                              order [one per distinct device]\n"
+                "   --shard r/G                map only the records starting in the r-th of G equal byte slices of the file\n"
+                "   --read-range A:B           map only records A..B-1 of the file (B omitted: to the end)\n"
+                "   --rank-buffer FLOAT[K/M/G] gathered output kept in memory per rank; the rest waits in an unnamed temporary file [%.0fM]\n"
+                "   --no-header                do not print the SAM header (ranks after the first)\n\nadvanced options:\n", o.rank_buffer / 1e6);
+    fprintf(fp, "   --kmer-model FILE          nucleotide k-mer model file (required: builtin models are not bundled)\n");
+    fprintf(fp, "   --rna                      the dataset is direct RNA\n");
+    fprintf(fp, "   -q INT                     the number of events in query signal to align [%d]\n", o.query);
+    fprintf(fp, "   -p INT                     the number of events to trim at query signal start [%d]\n", o.prefix);
+    fprintf(fp, "   --debug-break INT          break after processing the specified no. of batches\n");
+    fprintf(fp, "   --dtw-std                  use DTW standard instead of DTW subsequence\n");
+    fprintf(fp, "   --invert                   reverse the reference events instead of query\n");
+    fprintf(fp, "   --full-ref                 map to the full reference\n");
+    fprintf(fp, "   --from-end                 map the end portion of the query instead of the beginning\n");
+    fprintf(fp, "   --sam                      output in SAM format\n");
+    fprintf(fp, "   --device-paths | --host-paths  with --sam: warp paths of a whole batch on the GPU | read by read on the host threads [host threads]\n");
+    fprintf(fp, "   --secondary STR            print secondary mappings. yes or no [no]\n");
+    fprintf(fp, "   --profile-cpu=yes|no       run the stages one after the other and report Parse/Events/Normalise/DTW time [no]\n");
+    fprintf(fp, "   --accel=yes|no             run the alignment on the accelerator [yes]; 'no' is an error: this build has no CPU path\n");
+}
+
+void parse_device_list(const char *arg, std::vector<int> *devices) {
+    devices->clear();
+    for (const char *p = arg; *p;) {
+        char *e = nullptr;
+        const long d = strtol(p, &e, 10);
+        if (e == p || d < 0) die("--device takes a comma separated list of GPU indices");
+        devices->push_back(static_cast<int>(d));
+        p = (*e == ',') ? e + 1 : e;
+        if (*e && *e != ',') die("--device takes a comma separated list of GPU indices");
+    }
+    if (devices->empty()) die("--device takes a comma separated list of GPU indices");
+}
+
+}  // namespace
+
+Opt parse_options(int argc, char **argv) {
+    Opt o;
+    FILE *fp_help = stderr;
+    int c, li = 0;
+    while ((c = getopt_long(argc, argv, "p:q:t:B:K:v:o:w:ahV", kLongOptions, &li)) >= 0) {
+        switch (c) {
+            case 'B': o.batch_bytes = parse_num(optarg); if (o.batch_bytes <= 0) die("Maximum number of bytes should be larger than 0."); break;
+            case 'K': o.batch_size = atoi(optarg); if (o.batch_size < 1) die("Batch size should larger than 0."); break;
+            case 't': o.threads = atoi(optarg); if (o.threads < 1) die("Number of threads should larger than 0."); break;
+            case 'v': o.verbosity = atoi(optarg); break;
+            case 'V': fprintf(stdout, "sigfish-amd %s\n", sfa_version()); exit(EXIT_SUCCESS);
+            case 'h': fp_help = stdout; break;
+            case 'p': o.prefix = atoi(optarg); break;
+            case 'q': o.query = atoi(optarg); if (o.query < 1) die("Query size should larger than 0."); break;
+            case 'o': if (strcmp(optarg, "-") != 0 && !freopen(optarg, "wb", stdout)) die(std::string("failed to write the output to file ") + optarg); break;
+            case 'a': o.flag |= F_SAM; break;
+            case 'w': break;  // parsed and unused by the reference as well
+            case O_KMER_MODEL: o.model_file = optarg; break;
+            case O_RNA: o.flag |= F_RNA; break;
+            case O_DEBUG_BREAK: o.debug_break = atoi(optarg); break;
+            case O_DTW_STD: o.flag |= F_DTW; break;
+            case O_INVERT: o.flag |= F_INV; break;
+            case O_FULL_REF: o.flag |= F_REF; break;
+            case O_FROM_END: o.flag |= F_END; break;
+            case O_PROFILE_CPU: if (yes_or_no(optarg, "profile-cpu")) o.flag |= F_PRF; else o.flag &= ~F_PRF; break;  // src/dtw_main.c:213-214
+            case O_ACCEL:  // src/dtw_main.c:215-220: the reference falls back to work_db(dtw_single) on its CPU; there is none here
+                if (!yes_or_no(optarg, "accel"))
+                    die("--accel=no: this build has no CPU alignment path (the stage only exists as gfx950 kernels); "
+                        "run the reference binary for a CPU run, or drop the option");
+                break;
+            case O_SECONDARY:  // src/dtw_main.c:207-208 parses it; here it prints the reference's own candidate list (other values: no effect)
+                if (!strcmp(optarg, "yes")) o.secondary = true;
+                else if (!strcmp(optarg, "no")) o.secondary = false;
+                break;
+            case O_METH_MODEL: break;  // dead option of the reference (--meth-model): parsed, no effect
+            case O_PORE:
+                o.pore = optarg;
+                if (strcmp(optarg, "r9") && strcmp(optarg, "r10") && strcmp(optarg, "rna004")) die("Pore model should be r9, r10 or rna004");
+                if (!strcmp(optarg, "r10")) { o.flag |= F_R10; o.pore_flag = 1; }
+                if (!strcmp(optarg, "rna004")) { o.flag |= F_RNA | F_R10; o.pore_flag = 2; }
+                break;
+            case O_DEVICE: parse_device_list(optarg, &o.devices); break;
+            case O_HOST_EVENTS: o.host_events = true; break;
+            case O_HOST_PATHS: case O_DEVICE_PATHS: o.device_paths = c == O_DEVICE_PATHS; break;
+            case O_HOST_PARSE: case O_GPU_PARSE: o.gpu_parse = c == O_GPU_PARSE; break;
+            case O_RANKS: o.ranks = atoi(optarg); if (o.ranks < 1 || o.ranks > 64) die("--ranks should be 1..64"); break;
+            case O_SHARD:
+                if (sscanf(optarg, "%d/%d", &o.shard_r, &o.shard_n) != 2 || o.shard_n < 1 || o.shard_r < 0 || o.shard_r >= o.shard_n)
+                    die("--shard takes r/G with 0 <= r < G");
+                break;
+            case O_READ_RANGE: {
+                char *e = nullptr;
+                o.range_a = strtoll(optarg, &e, 10);
+                if (e == optarg || *e != ':' || o.range_a < 0) die("--read-range takes A:B (records A up to, not including, B; B may be omitted)");
+                ++e;  // past the colon
+                o.range_b = *e ? strtoll(e, &e, 10) : -1;
+                if (*e || (o.range_b >= 0 && o.range_b < o.range_a)) die("--read-range takes A:B (records A up to, not including, B; B may be omitted)");
+                break;
+            }
+            case O_NO_HEADER: o.no_header = true; break;
+            case O_RANK_BUFFER: o.rank_buffer = parse_num(optarg); if (o.rank_buffer < 0) die("--rank-buffer should not be negative"); break;
+            case O_STREAMS: o.streams = atoi(optarg); if (o.streams < 1 || o.streams > 8) die("--streams should be 1..8"); break;
+            default: help(stderr, o); exit(EXIT_FAILURE);
+        }
+    }
+    if (argc - optind != 2 || fp_help == stdout) {
+        help(fp_help, o);
+        exit(fp_help == stdout ? EXIT_SUCCESS : EXIT_FAILURE);
+    }
+    o.fasta = argv[optind];
+    o.blow5 = argv[optind + 1];
+    // same order of checks as src/dtw_main.c:248-277 (before RNA auto-detection)
+    if (!(o.flag & F_RNA)) {
+        if (o.flag & F_DTW) die("DTW is only available for RNA.");
+        if (o.flag & F_INV) die("Inversion is only available for RNA.");
+        if (o.flag & F_REF) die("--full-ref is only available for RNA.");
+    }
+    if (o.prefix < 0) {
+        if (!(o.flag & F_RNA)) die("DNA does not support auto query start detection.");
+        if (o.flag & F_INV) die("Inversion is not compatible with auto query start detection.");
+        if (o.flag & F_END) die("Mapping from query end is not compatible with auto query start detection.");
+    }
+
+    if (o.shard_n > 1 && (o.range_a > 0 || o.range_b >= 0)) die("--shard and --read-range exclude each other");
+    if (o.secondary && o.query > 2048) die("--secondary yes supports -q up to 2048");
+    if (o.ranks == 0) {  // one process per DISTINCT device of the list; a device listed twice is two contexts of one process
+        std::vector<int> d = o.devices;
+        std::sort(d.begin(), d.end());
+        o.ranks = static_cast<int>(std::unique(d.begin(), d.end()) - d.begin());
+    }
+    if (o.ranks > 1) {
+        if (o.shard_n > 1 || o.range_a > 0 || o.range_b >= 0) die("--ranks shards the whole file: it cannot be combined with --shard or --read-range");
+        if (o.debug_break >= 0) die("--debug-break counts the batches of one process: use --ranks 1 with it");
+    }
+    return o;
+}
+
+}  // namespace cli

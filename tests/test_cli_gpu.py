@@ -302,3 +302,39 @@ def test_cli_verbose_4_reports_where_the_main_thread_waited(models):
     assert m, err
     assert all(float(x) >= 0 for x in m.groups())
     assert err.count("Entries") >= 6  # three batches of 2 + 2 + 1 reads: a `loaded` and a `processed` line each
+
+
+def test_cli_sfa_opts(models):
+    """SFA_OPTS="name=value,...": library options from the environment.  A planner option leaves the rows as they are; an item
+    without a value, a test hook of the library and an unknown name are refused before any row is printed."""
+    c = load_case("dna_default")
+    cmd = [BIN, "dtw", "--kmer-model", models[6], "--verbose", "0", c["fasta"], c["blow5"]]
+
+    def run(opts):
+        return subprocess.run(cmd, capture_output=True, timeout=300, env={**os.environ, "SFA_OPTS": opts})
+    ok = run("widen_below=1")
+    assert ok.returncode == 0, ok.stderr.decode()
+    assert ok.stdout.decode() == c["out_text"]
+    for opts, check in (("widen_below", lambda e: "name=value" in e), ("debug_drop_quad=0", lambda e: "test hook of the library" in e),
+                        ("no_such_option=1", lambda e: e.startswith("SFA_OPTS: "))):
+        bad = run(opts)
+        err = bad.stderr.decode()
+        assert bad.returncode != 0 and "[sigfish-amd] ERROR: " in err, (opts, err)
+        assert check(err.split("[sigfish-amd] ERROR: ", 1)[1]), (opts, err)
+        assert bad.stdout == b"", opts
+
+
+@pytest.mark.parametrize("extra", [[], ["--gpu-parse"]])
+def test_cli_one_process_fails_cleanly_mid_run(models, tmp_path, extra):
+    """A file cut inside a record, read by ONE process at -K 1: batches are in flight on the helper threads when the reader
+    fails on the main thread.  The run ends with status 1 and one error line (no abort, no signal), and what it printed before
+    is whole lines from the front of the golden output.  (A host-side file error; nothing happens on the device.)"""
+    c = load_case("dna_default")
+    data = open(c["blow5"], "rb").read()
+    cut = str(tmp_path / "cut.blow5")
+    open(cut, "wb").write(data[:len(data) * 3 // 4])
+    r = subprocess.run([BIN, "dtw", "--kmer-model", models[6], "--verbose", "0", "-K", "1", *extra, c["fasta"], cut], capture_output=True, timeout=120)
+    assert r.returncode == 1, (r.returncode, r.stderr.decode())
+    assert r.stderr.decode().count("[sigfish-amd] ERROR:") == 1, r.stderr.decode()
+    out = r.stdout.decode()
+    assert (out == "" or out.endswith("\n")) and c["out_text"].startswith(out), out
