@@ -39,6 +39,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace sfa {
@@ -62,6 +63,22 @@ constexpr int kRefPad = 128;       // floats of +inf padding on both sides of ev
 constexpr int kStepsPerLoad = SFA_STEPS_PER_LOAD;  // reference levels fetched per load (4 = one 16-byte load)
 constexpr int kSpanBuckets = 32;   // histogram of alignment spans in sixteenths of the query length (FinalizeArgs::span_hist)
 constexpr int kMaxClasses = 6;     // query-length classes; base shapes (R, lanes) = (32,64) (32,32) (32,16) (16,16) (8,16) (4,16)
+
+// What a batch reports about itself: one block of words in device memory, zeroed in front of the batch and copied to the host
+// behind it.  The kernels get pointers to its fields (sdtw_screen_kernel's counter, DpArgs / StripArgs::err, DpArgs::lck_stats,
+// DpArgs / FinalizeArgs::span_hist); the host reads it by name.
+struct BatchStatus {
+    unsigned non_finite;        // reads with a NaN / inf query value (sdtw_screen_kernel)
+    unsigned spare0;
+    unsigned lck_fallbacks;     // LDS route (lck_stats[0], [1]): reads that left their saved record ...
+    unsigned lck_from_scratch;  // ... and reads that started pass 2 from scratch
+    unsigned err[3];            // error words of the in-launch waits: code (kErrQuadWait, ...), two of detail (report_device_error)
+    unsigned spare1;
+    unsigned span_hist[kSpanBuckets];  // alignment spans in sixteenths of the query length
+};
+static_assert(offsetof(BatchStatus, non_finite) == 0 && offsetof(BatchStatus, lck_fallbacks) == 4 * 2 && offsetof(BatchStatus, lck_from_scratch) == 4 * 3 &&
+                  offsetof(BatchStatus, err) == 4 * 4 && offsetof(BatchStatus, span_hist) == 4 * 8 && sizeof(BatchStatus) == 32 + 4 * kSpanBuckets,
+              "the words the kernels were built around");
 
 struct __attribute__((packed, aligned(4))) float4u {
     float v[kStepsPerLoad];

@@ -2,9 +2,8 @@
 // align_db() (src/sigfish.c:1003-1015).  Host work: group reads into "quads" (reads of one length class share a wavefront;
 // sfa_plan.hpp), pick the rows-per-lane class, size the checkpoint interval, launch fill (+ pass 2 by ticket, or fill ->
 // finalize -> trace -> finalize), row strips for queries beyond 2048 events, and hand back one row per read in input order.
+#define SFA_DEFINE_FINALIZE_KERNEL  // (of sdtw_kernels.hpp and sdtw_strips.hpp: this unit holds the plain kernels)
 #include "sfa_ctx.hpp"
-#define SFA_DEFINE_FINALIZE_KERNEL
-#include "sdtw_kernels.hpp"
 #include "sdtw_instances.hpp"
 #include "sdtw_strips.hpp"
 
@@ -55,7 +54,7 @@ void by_std(bool std_dtw, F f) {
 // profiles/r04_logs/strips_groups_ab*.log, rejected_strip_pass2_rows_in_lds_three_waves.log.
 int align_long(sfa_ctx *c, const float *d_queries, const int64_t *d_q_off, const int64_t *q_off_host, const std::vector<int32_t> &reads, int64_t max_qlen,
                ResultRow *d_out, hipStream_t st) {
-    const int32_t n_long = static_cast<int32_t>(reads.size()), n_jobs = c->n_jobs;
+    const int32_t n_long = static_cast<int32_t>(reads.size()), n_jobs = c->model.n_jobs;
     const size_t o_reads = 0, o_bnd = (sizeof(int32_t) * n_long + 7) & ~size_t(7);
     const size_t o_ck = o_bnd + sizeof(int64_t) * (n_jobs + 1);
     const size_t o_soff = o_ck + sizeof(int64_t) * (n_jobs + 1);  // per-group prefix sums of the reads' strip counts: group g0 at word g0 + (its index)
@@ -63,13 +62,13 @@ int align_long(sfa_ctx *c, const float *d_queries, const int64_t *d_q_off, const
     std::vector<int32_t> n_strips_of(n_long);
     for (int32_t i = 0; i < n_long; ++i) n_strips_of[i] = static_cast<int32_t>((q_off_host[reads[i] + 1] - q_off_host[reads[i]] + sfa::kStripRows - 1) / sfa::kStripRows);
     int rc;
-    if ((rc = c->h_long.reserve(stage_bytes)) || (rc = c->d_long.reserve(stage_bytes))) return rc;
-    char *hs = c->h_long.as<char>();
+    if ((rc = c->strips.reserve_staging(stage_bytes))) return rc;
+    char *hs = c->strips.h_long.as<char>();
     memcpy(hs + o_reads, reads.data(), sizeof(int32_t) * n_long);
     int64_t *bnd_off = reinterpret_cast<int64_t *>(hs + o_bnd);
     int64_t per = 0;
     for (int32_t j = 0; j < n_jobs; ++j) {
-        const int64_t row = (static_cast<int64_t>(c->h_job_len[j]) + sfa::kBndPad + 3) & ~int64_t(3);
+        const int64_t row = (static_cast<int64_t>(c->model.h_job_len[j]) + sfa::kBndPad + 3) & ~int64_t(3);
         bnd_off[j] = per;
         per += row;
     }
@@ -86,7 +85,7 @@ int align_long(sfa_ctx *c, const float *d_queries, const int64_t *d_q_off, const
         int64_t recs = 0;
         for (int32_t j = 0; j < n_jobs; ++j) {
             ck_off[j] = recs;
-            recs += static_cast<int64_t>(max_strips) * ((c->h_job_len[j] - 1) >> ck_shift);
+            recs += static_cast<int64_t>(max_strips) * ((c->model.h_job_len[j] - 1) >> ck_shift);
         }
         ck_off[n_jobs] = recs;
         if (c->opt_ckpt_interval > 0 || recs * rec_floats * 4 * n_long <= c->opt_ckpt_budget || ck_shift >= 14) break;
@@ -106,14 +105,7 @@ int align_long(sfa_ctx *c, const float *d_queries, const int64_t *d_q_off, const
     const size_t prog_bytes = sizeof(int32_t) * static_cast<size_t>(group) * n_jobs * max_strips;
     const size_t bndc_floats = static_cast<size_t>(cost_rows) * per * group, lck_floats = static_cast<size_t>(std::max<int64_t>(ck_floats_per_read, 1)) * group;
     const int sets = two_sets ? 2 : 1;
-    const size_t bndc_cap = c->d_bndc.cap;
-    if ((rc = c->d_lprog.reserve(prog_bytes * sets)) || (rc = c->d_lticket.reserve(128))) return rc;
-    if ((rc = c->d_bndc.reserve(sizeof(float) * bndc_floats * sets)) ||
-        (rc = c->d_lbest.reserve(4 * n_part)) || (rc = c->d_lsecond.reserve(4 * n_part)) || (rc = c->d_lend.reserve(4 * n_part)) ||
-        (rc = c->d_lwin.reserve(4 * 5 * static_cast<size_t>(n_long))) ||
-        (rc = c->d_lck.reserve(sizeof(float) * lck_floats * sets)))
-        return rc;
-    if (c->d_bndc.cap != bndc_cap) HIP_TRY(hipMemsetAsync(c->d_bndc.p, 0x7f, c->d_bndc.cap, st));  // fresh allocation: 3.4e38 everywhere (see the pad note in sdtw_strips.hpp)
+    if ((rc = c->strips.reserve(prog_bytes * sets, bndc_floats * sets, lck_floats * sets, n_part, n_long, st))) return rc;
     {  // the prefix sums of every group, each in its own words: one upload for all groups, no host wait between them
         int32_t *soff = reinterpret_cast<int32_t *>(hs + o_soff);
         for (int32_t g0 = 0, gi = 0; g0 < n_long; g0 += group, ++gi) {
@@ -123,10 +115,10 @@ int align_long(sfa_ctx *c, const float *d_queries, const int64_t *d_q_off, const
             for (int32_t i = 0; i < gn; ++i) so[i + 1] = so[i] + n_strips_of[g0 + i];
         }
     }
-    HIP_TRY(hipMemcpyAsync(c->d_long.p, hs, stage_bytes, hipMemcpyHostToDevice, st));
-    const char *ds = c->d_long.as<char>();
+    HIP_TRY(hipMemcpyAsync(c->strips.d_long.p, hs, stage_bytes, hipMemcpyHostToDevice, st));
+    const char *ds = c->strips.d_long.as<char>();
     const bool std_dtw = (c->flag & SFA_DTW) != 0;
-    int32_t *win = c->d_lwin.as<int32_t>();  // [5][n_long]: w_job, w_ws, w_score, t_st, t_end
+    int32_t *win = c->strips.d_lwin.as<int32_t>();  // [5][n_long]: w_job, w_ws, w_score, t_st, t_end
     hipStream_t const first = st;
     if (two_sets) {  // the second stream starts behind the staging upload (and whatever `first` waited for)
         HIP_TRY(hipEventRecord(c->lev[2], first));
@@ -140,21 +132,21 @@ int align_long(sfa_ctx *c, const float *d_queries, const int64_t *d_q_off, const
         sa.queries = d_queries;
         sa.q_off = d_q_off;
         sa.reads = reinterpret_cast<const int32_t *>(ds + o_reads) + g0;
-        sa.ref = c->d_ref.as<float>();
-        sa.job_off = c->d_job_off.as<int64_t>();
-        sa.job_len = c->d_job_len.as<int32_t>();
+        sa.ref = c->model.d_ref.as<float>();
+        sa.job_off = c->model.d_job_off.as<int64_t>();
+        sa.job_len = c->model.d_job_len.as<int32_t>();
         sa.bnd_off = reinterpret_cast<const int64_t *>(ds + o_bnd);
-        sa.bnd_cost = c->d_bndc.as<float>() + set * bndc_floats;
+        sa.bnd_cost = c->strips.d_bndc.as<float>() + set * bndc_floats;
         sa.bnd_stride = cost_rows * per;
-        sa.p_best = c->d_lbest.as<float>() + static_cast<size_t>(g0) * n_jobs;
-        sa.p_second = c->d_lsecond.as<float>() + static_cast<size_t>(g0) * n_jobs;
-        sa.p_end = c->d_lend.as<int32_t>() + static_cast<size_t>(g0) * n_jobs;
+        sa.p_best = c->strips.d_lbest.as<float>() + static_cast<size_t>(g0) * n_jobs;
+        sa.p_second = c->strips.d_lsecond.as<float>() + static_cast<size_t>(g0) * n_jobs;
+        sa.p_end = c->strips.d_lend.as<int32_t>() + static_cast<size_t>(g0) * n_jobs;
         sa.w_job = win + g0;
         sa.w_ws = win + n_long + g0;
         sa.w_score = reinterpret_cast<const float *>(win + 2 * static_cast<size_t>(n_long) + g0);
         sa.t_st = win + 3 * static_cast<size_t>(n_long) + g0;
         sa.t_end = win + 4 * static_cast<size_t>(n_long) + g0;
-        sa.ck = c->d_lck.as<float>() + set * lck_floats;
+        sa.ck = c->strips.d_lck.as<float>() + set * lck_floats;
         sa.ck_off = reinterpret_cast<const int64_t *>(ds + o_ck);
         sa.ck_shift = ck_shift;
         sa.max_strips = max_strips;
@@ -162,45 +154,45 @@ int align_long(sfa_ctx *c, const float *d_queries, const int64_t *d_q_off, const
         sa.n_long = gn;
         sa.n_jobs = n_jobs;
         sa.rev_query = ((c->flag & SFA_RNA) && !(c->flag & SFA_INV)) ? 1 : 0;
-        sa.err = c->d_badcount.as<unsigned>() + 4;
+        sa.err = c->status.dev()->err;
         // a strip legitimately waits for the strip above to get kPipeBlock + 72 columns ahead, behind every strip above that one: never
         // less than ~10 us per such column and strip (0.2 us measured), however small the option or busy the device
         sa.spin_limit = std::max<int64_t>(c->opt_spin_limit_ms, (static_cast<int64_t>(sfa::kPipeBlock + 72) * max_strips) / 100 + 1) * 100000;  // 100 MHz ticks
-        c->strip_limit_ms = sa.spin_limit / 100000;
+        c->strips.strip_limit_ms = sa.spin_limit / 100000;
         sa.debug_drop_strip = (c->opt_debug_drop_strip >= g0 && c->opt_debug_drop_strip < g0 + gn) ? static_cast<int32_t>(c->opt_debug_drop_strip - g0) : -1;
         sfa::StripFinalizeArgs fa{};
         fa.reads = sa.reads;
         fa.p_best = sa.p_best;
         fa.p_second = sa.p_second;
         fa.p_end = sa.p_end;
-        fa.job_contig = c->d_job_contig.as<int32_t>();
-        fa.job_strand = c->d_job_strand.as<int8_t>();
-        fa.ref_len = c->d_ref_len.as<int32_t>();
-        fa.ref_st_offset = c->d_ref_off.as<int32_t>();
+        fa.job_contig = c->model.d_job_contig.as<int32_t>();
+        fa.job_strand = c->model.d_job_strand.as<int8_t>();
+        fa.ref_len = c->model.d_ref_len.as<int32_t>();
+        fa.ref_st_offset = c->model.d_ref_off.as<int32_t>();
         fa.w_job = win + g0;
         fa.w_ws = win + n_long + g0;
         fa.w_score = reinterpret_cast<float *>(win + 2 * static_cast<size_t>(n_long) + g0);
         fa.t_st = sa.t_st;
         fa.t_end = sa.t_end;
         fa.out = d_out;
-        fa.bad = c->d_bad.as<uint8_t>();
+        fa.bad = c->status.d_bad.as<uint8_t>();
         fa.n_long = gn;
         fa.n_jobs = n_jobs;
         const dim3 block(256), fgrid((gn + 63) / 64), fblock(64);
         const dim3 grid2((gn + 3) / 4);
         {  // pass 1: one wave per (job, read, strip), tickets in that order
             const int32_t *soff = reinterpret_cast<const int32_t *>(hs + o_soff) + g0 + gi;  // (uploaded with the staging area, before the loop)
-            sa.progress = reinterpret_cast<int32_t *>(c->d_lprog.as<char>() + set * prog_bytes);
-            sa.ticket = c->d_lticket.as<unsigned>() + set * 16;  // (words 8.. of a set's 64 bytes: where a dropped strip publishes, see strip_pipe_task)
+            sa.progress = reinterpret_cast<int32_t *>(c->strips.d_lprog.as<char>() + set * prog_bytes);
+            sa.ticket = c->strips.d_lticket.as<unsigned>() + set * 16;  // (words 8.. of a set's 64 bytes: where a dropped strip publishes, see strip_pipe_task)
             HIP_TRY(hipMemsetAsync(sa.progress, 0, sizeof(int32_t) * static_cast<size_t>(gn) * n_jobs * max_strips, st));
             HIP_TRY(hipMemsetAsync(sa.ticket, 0, 4, st));
             sa.strip_off = reinterpret_cast<const int32_t *>(ds + o_soff) + g0 + gi;
             const int64_t waves = static_cast<int64_t>(soff[gn]) * n_jobs;
             const dim3 gridp(static_cast<unsigned>((waves + 3) / 4));
 #ifdef SFA_TASK_TIMES
-            if ((rc = c->d_ltimes.reserve(24 * static_cast<size_t>(waves)))) return rc;
-            sa.task_times = c->d_ltimes.as<unsigned long long>();
-            c->n_ltimes = waves;
+            if ((rc = c->times.d_ltimes.reserve(24 * static_cast<size_t>(waves)))) return rc;
+            sa.task_times = c->times.d_ltimes.as<unsigned long long>();
+            c->times.n_ltimes = waves;
 #endif
             by_std(std_dtw, [&](auto S) { hipLaunchKernelGGL((sfa::sdtw_strip_pipe_kernel<S>), gridp, block, 0, st, sa); });
         }
@@ -275,10 +267,10 @@ sfa::PlanParams plan_params(const sfa_ctx *c) {
     pp.column_segments = c->opt_column_segments;
     pp.segment_warm_windows = c->opt_segment_warm;
     pp.std_dtw = (c->flag & SFA_DTW) != 0;
-    pp.span_sixteenths = c->span_sixteenths;
+    pp.span_sixteenths = c->wave.span_sixteenths;
     // what follows from the route: secondaries take the plain two-pass route (no LDS checkpoints, no column segments); std_dtw
     // has no column segments (its first row is cumulative: no finite memory), nor has the re-run of a batch whose hand-overs failed
-    pp.allow_segments = !pp.std_dtw && !c->no_segments_once && c->opt_secondary == 0;
+    pp.allow_segments = !pp.std_dtw && !c->seg.no_segments_once && c->opt_secondary == 0;
     pp.lds_ckpt = c->opt_secondary > 0 ? 0 : static_cast<int>(c->opt_lds_ckpt);
     return pp;
 }
@@ -301,46 +293,27 @@ struct Staging {
     }
 };
 
-// the plan into the page-locked staging area, and every scratch buffer of the batch
+// every scratch buffer of the batch (each on the conditions of its route), and the plan into the page-locked staging area
 int stage_and_reserve(sfa_ctx *c, const int64_t *q_off, int32_t n, Route route, const Staging &sg) {
-    const sfa::BatchPlan &plan = c->plan;
-    const int32_t n_quads = plan.n_quads, n_chunks = plan.n_chunks, n_jobs = c->n_jobs;
+    const sfa::BatchPlan &plan = c->wave.plan;
+    const int32_t n_quads = plan.n_quads, n_chunks = plan.n_chunks, n_jobs = c->model.n_jobs;
+    const size_t n_part = static_cast<size_t>(std::max(n_quads, 1)) * n_chunks * 4, nr = static_cast<size_t>(n);
     int rc;
-    if ((rc = c->h_stage.reserve(sg.bytes)) || (rc = c->d_stage.reserve(sg.bytes))) return rc;
-    char *hs = c->h_stage.as<char>();
+    if ((rc = c->wave.reserve(sg.bytes, n_part, nr, plan.ck_floats)) || (rc = c->status.reserve(nr))) return rc;
+    if (c->opt_secondary > 0 && (rc = c->sec.reserve(n_part, nr))) return rc;
+    if (fused(route) && (rc = c->fused.reserve(static_cast<size_t>(std::max(n_quads, 1))))) return rc;
+    if (lds(route) && (rc = c->lds.reserve(n_part, nr))) return rc;
+    if (route == Route::Segments && (rc = c->seg.reserve(plan, n_jobs))) return rc;
+    char *hs = c->wave.h_stage.as<char>();
     memcpy(hs, q_off, sizeof(int64_t) * (n + 1));
     memcpy(hs + sg.order, plan.order.data(), sizeof(int32_t) * plan.order.size());
     memcpy(hs + sg.qq, plan.quad_qlen.data(), sizeof(int32_t) * plan.quad_qlen.size());
     memcpy(hs + sg.slot, plan.slot_of_read.data(), sizeof(int32_t) * n);
     memcpy(hs + sg.chunk, plan.chunk_begin.data(), sizeof(int32_t) * (n_chunks + 1));
     memcpy(hs + sg.ckoff, plan.job_ck_off.data(), sizeof(int32_t) * (n_jobs + 1));
-
-    const size_t n_part = static_cast<size_t>(std::max(n_quads, 1)) * n_chunks * 4;
-    if ((rc = c->d_pbest.reserve(4 * n_part)) || (rc = c->d_pend.reserve(4 * n_part)) || (rc = c->d_pjob.reserve(4 * n_part)) ||
-        (rc = c->d_psecond.reserve(4 * n_part)) || (rc = c->d_wjob.reserve(4 * (size_t)n)) || (rc = c->d_wend.reserve(4 * (size_t)n)) ||
-        (rc = c->d_tst.reserve(8 * (size_t)n)) || (rc = c->d_wscore.reserve(4 * (size_t)n)))
-        return rc;
-    if ((rc = c->d_wchunk.reserve(4 * static_cast<size_t>(n))) || (rc = c->d_started.reserve(64))) return rc;
-    if (c->opt_secondary > 0 && ((rc = c->d_p5.reserve(4 * sfa::kTop5Words * n_part)) || (rc = c->d_swin.reserve(4 * 15 * static_cast<size_t>(n))) ||
-                                 (rc = c->d_sts.reserve(4 * 10 * static_cast<size_t>(n)))))
-        return rc;
-    if (fused(route) && ((rc = c->d_args.reserve(sizeof(DpArgs))) || (rc = c->d_ticket.reserve(64)) ||
-                         (rc = c->d_quaddone.reserve(4 * static_cast<size_t>(std::max(n_quads, 1))))))
-        return rc;
-    if (lds(route) && ((rc = c->d_bestrec.reserve(sizeof(float) * sfa::kLdsCkPlanes * 64 * n_part / 4)) || (rc = c->d_beste.reserve(4 * n_part)) ||
-                       (rc = c->d_gbest.reserve(4 * static_cast<size_t>(n)))))
-        return rc;
-    if ((rc = c->d_bad.reserve(static_cast<size_t>(n))) || (rc = c->d_badcount.reserve(256)) || (rc = c->h_badcount.reserve(256))) return rc;
-    if (plan.ck_floats > 0 && (rc = c->d_ck.reserve(sizeof(float) * plan.ck_floats))) return rc;
-    if (route == Route::Segments) {
-        const size_t vbytes = sizeof(float) * 64 * (plan.max_R + 1) * 2 * static_cast<size_t>(plan.n_seg) * n_jobs * n_quads;
-        if ((rc = c->d_verify.reserve(vbytes)) || (rc = c->d_segfail.reserve(4 * static_cast<size_t>(n_quads))) ||
-            (rc = c->h_flags.reserve(4 * static_cast<size_t>(n_quads))))
-            return rc;
-    }
 #ifdef SFA_TASK_TIMES
-    if ((rc = c->d_times.reserve(24 * static_cast<size_t>(std::max(n_quads * n_chunks, 1))))) return rc;
-    c->n_times = n_quads * n_chunks;
+    if ((rc = c->times.d_times.reserve(24 * static_cast<size_t>(std::max(n_quads * n_chunks, 1))))) return rc;
+    c->times.n_times = n_quads * n_chunks;
 #endif
     return SFA_OK;
 }
@@ -354,28 +327,28 @@ struct BatchArgs {
 
 BatchArgs batch_args(sfa_ctx *c, const float *d_queries, int32_t n, ResultRow *d_out, ResultRow *d_sec, Route route, const Staging &sg,
                      bool has_long) {
-    const sfa::BatchPlan &plan = c->plan;
-    const int32_t n_quads = plan.n_quads, n_chunks = plan.n_chunks, n_jobs = c->n_jobs;
-    const char *ds = c->d_stage.as<char>();
+    const sfa::BatchPlan &plan = c->wave.plan;
+    const int32_t n_quads = plan.n_quads, n_chunks = plan.n_chunks, n_jobs = c->model.n_jobs;
+    const char *ds = c->wave.d_stage.as<char>();
     BatchArgs a;
     DpArgs &da = a.da;
     da.queries = d_queries;
     da.q_off = reinterpret_cast<const int64_t *>(ds);
     da.order = reinterpret_cast<const int32_t *>(ds + sg.order);
     da.quad_qlen = reinterpret_cast<const int32_t *>(ds + sg.qq);
-    da.ref = c->d_ref.as<float>();
-    da.job_off = c->d_job_off.as<int64_t>();
-    da.job_len = c->d_job_len.as<int32_t>();
+    da.ref = c->model.d_ref.as<float>();
+    da.job_off = c->model.d_job_off.as<int64_t>();
+    da.job_len = c->model.d_job_len.as<int32_t>();
     da.chunk_begin = reinterpret_cast<const int32_t *>(ds + sg.chunk);
     da.job_ck_off = reinterpret_cast<const int32_t *>(ds + sg.ckoff);
-    da.ck = c->d_ck.as<float>();
-    da.p_best = c->d_pbest.as<float>();
-    da.p_end = c->d_pend.as<int32_t>();
-    da.p_job = c->d_pjob.as<int32_t>();
-    da.p_second = c->d_psecond.as<float>();
-    da.w_job = c->d_wjob.as<int32_t>();
-    da.w_end = c->d_wend.as<int32_t>();
-    da.w_score = c->d_wscore.as<float>();
+    da.ck = c->wave.d_ck.as<float>();
+    da.p_best = c->wave.d_pbest.as<float>();
+    da.p_end = c->wave.d_pend.as<int32_t>();
+    da.p_job = c->wave.d_pjob.as<int32_t>();
+    da.p_second = c->wave.d_psecond.as<float>();
+    da.w_job = c->wave.d_wjob.as<int32_t>();
+    da.w_end = c->wave.d_wend.as<int32_t>();
+    da.w_score = c->wave.d_wscore.as<float>();
     da.n_reads_total = n;
     da.n_cls = static_cast<int32_t>(plan.classes.size());
     for (int i = 0; i < da.n_cls; ++i) {
@@ -395,43 +368,43 @@ BatchArgs batch_args(sfa_ctx *c, const float *d_queries, int32_t n, ResultRow *d
     da.warm_windows = plan.warm_windows;
     da.n_jobs = n_jobs;
     da.verify_planes = plan.max_R + 1;
-    da.verify = c->d_verify.as<float>();
-    da.seg_fail = c->d_segfail.as<int32_t>();
-    da.best_rec = c->d_bestrec.as<float>();
-    da.best_e = c->d_beste.as<int32_t>();
-    da.g_best = c->d_gbest.as<unsigned>();
-    da.w_chunk = c->d_wchunk.as<int32_t>();
+    da.verify = c->seg.d_verify.as<float>();
+    da.seg_fail = c->seg.d_segfail.as<int32_t>();
+    da.best_rec = c->lds.d_bestrec.as<float>();
+    da.best_e = c->lds.d_beste.as<int32_t>();
+    da.g_best = c->lds.d_gbest.as<unsigned>();
+    da.w_chunk = c->wave.d_wchunk.as<int32_t>();
     da.best_planes = sfa::kLdsCkPlanes;
-    da.ticket = c->d_ticket.as<unsigned>();
-    da.quad_done = c->d_quaddone.as<int32_t>();
+    da.ticket = c->fused.d_ticket.as<unsigned>();
+    da.quad_done = c->fused.d_quaddone.as<int32_t>();
     da.n_quads_total = n_quads;
-    da.job_contig = c->d_job_contig.as<int32_t>();
-    da.job_strand = c->d_job_strand.as<int8_t>();
-    da.ref_len = c->d_ref_len.as<int32_t>();
-    da.ref_st_offset = c->d_ref_off.as<int32_t>();
-    da.bad = c->d_bad.as<uint8_t>();
+    da.job_contig = c->model.d_job_contig.as<int32_t>();
+    da.job_strand = c->model.d_job_strand.as<int8_t>();
+    da.ref_len = c->model.d_ref_len.as<int32_t>();
+    da.ref_st_offset = c->model.d_ref_off.as<int32_t>();
+    da.bad = c->status.d_bad.as<uint8_t>();
     da.out = d_out;
-    da.span_hist = route == Route::Fused32 ? c->d_badcount.as<unsigned>() + 8 : nullptr;  // (the LDS route caps its head start instead)
+    da.span_hist = route == Route::Fused32 ? c->status.dev()->span_hist : nullptr;  // (the LDS route caps its head start instead)
     da.prio_unit = static_cast<int32_t>(c->opt_prio_unit);
-    da.started = c->d_started.as<unsigned>();
-    da.err = c->d_badcount.as<unsigned>() + 4;
-    da.lck_stats = c->d_badcount.as<unsigned>() + 2;
+    da.started = c->wave.d_started.as<unsigned>();
+    da.err = c->status.dev()->err;
+    da.lck_stats = &c->status.dev()->lck_fallbacks;  // (and lck_from_scratch behind it)
     {   // a pass-2 wave legitimately waits for as long as one fill task of its quad runs: never less than ~5x that (1 us per
         // column of the longest chunk, against 0.2 measured), however small the option -- a 250 Mb strand is minutes, not a hang
         int64_t longest = 0;
         for (int32_t ch = 0; ch < n_chunks; ++ch) {
             int64_t cols = 0;
-            for (int32_t j = plan.chunk_begin[ch]; j < plan.chunk_begin[ch + 1] && j < n_jobs; ++j) cols += c->h_job_len[j];
+            for (int32_t j = plan.chunk_begin[ch]; j < plan.chunk_begin[ch + 1] && j < n_jobs; ++j) cols += c->model.h_job_len[j];
             longest = std::max(longest, cols);
         }
         da.spin_limit = std::max<int64_t>(c->opt_spin_limit_ms, longest / 1000) * 100000;  // 100 MHz ticks
-        c->quad_limit_ms = da.spin_limit / 100000;
+        c->wave.quad_limit_ms = da.spin_limit / 100000;
     }
     da.debug_drop_quad = static_cast<int32_t>(c->opt_debug_drop_quad);
-    da.p_top5 = route == Route::Secondary ? c->d_p5.as<int32_t>() : nullptr;
-    da.self = fused(route) ? c->d_args.as<DpArgs>() : nullptr;
+    da.p_top5 = route == Route::Secondary ? c->sec.d_p5.as<int32_t>() : nullptr;
+    da.self = fused(route) ? c->fused.d_args.as<DpArgs>() : nullptr;
 #ifdef SFA_TASK_TIMES
-    da.task_times = c->d_times.as<unsigned long long>();
+    da.task_times = c->times.d_times.as<unsigned long long>();
 #endif
 
     FinalizeArgs &fz = a.fz;
@@ -448,28 +421,28 @@ BatchArgs batch_args(sfa_ctx *c, const float *d_queries, int32_t n, ResultRow *d
     fz.w_end = da.w_end;
     fz.w_score = da.w_score;
     fz.w_chunk = da.w_chunk;
-    fz.t_st = c->d_tst.as<int32_t>();
+    fz.t_st = c->wave.d_tst.as<int32_t>();
     fz.out = d_out;
     fz.bad = da.bad;
     fz.q_off = da.q_off;
     fz.max_query = has_long ? sfa::kMaxQuery : 0;
     fz.n_reads = n;
     fz.n_chunks = n_chunks;
-    fz.span_hist = c->d_badcount.as<unsigned>() + 8;
+    fz.span_hist = c->status.dev()->span_hist;
 
     if (c->opt_secondary > 0) {
         SecArgs &sa = a.sa;
         sa.slot_of_read = fz.slot_of_read;
-        sa.p_top5 = c->d_p5.as<int32_t>();
+        sa.p_top5 = c->sec.d_p5.as<int32_t>();
         sa.bad = fz.bad;
         sa.q_off = fz.q_off;
         sa.max_query = fz.max_query;
         sa.n_reads = n;
         sa.n_chunks = n_chunks;
-        sa.s_job = c->d_swin.as<int32_t>();
+        sa.s_job = c->sec.d_swin.as<int32_t>();
         sa.s_end = sa.s_job + 5 * static_cast<size_t>(n);
         sa.s_score = reinterpret_cast<float *>(sa.s_end + 5 * static_cast<size_t>(n));
-        sa.t_st = c->d_sts.as<int32_t>();
+        sa.t_st = c->sec.d_sts.as<int32_t>();
         sa.job_contig = fz.job_contig;
         sa.job_strand = fz.job_strand;
         sa.ref_len = fz.ref_len;
@@ -494,14 +467,14 @@ int enqueue_pass1(sfa_ctx *c, Route route, const BatchArgs &a, hipStream_t st) {
     const DpArgs &da = a.da;
     const int32_t n_quads = da.n_quads_total;
     if (lds(route))
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_gbest.p), 0x7f800000, static_cast<size_t>(da.n_reads_total), st));  // +inf: no score seen yet
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->lds.d_gbest.p), 0x7f800000, static_cast<size_t>(da.n_reads_total), st));  // +inf: no score seen yet
     if (fused(route)) {
-        HIP_TRY(hipMemsetAsync(c->d_ticket.p, 0, 4, st));
-        HIP_TRY(hipMemsetAsync(c->d_quaddone.p, 0, 4 * static_cast<size_t>(n_quads), st));
+        HIP_TRY(hipMemsetAsync(c->fused.d_ticket.p, 0, 4, st));
+        HIP_TRY(hipMemsetAsync(c->fused.d_quaddone.p, 0, 4 * static_cast<size_t>(n_quads), st));
         if (int rc = launch_finalize(a.fz, 3, st)) return rc;  // rows of the reads in no quad; every other row is written by the launch's pass-2 waves
-        HIP_TRY(hipMemcpyAsync(c->d_args.p, &da, sizeof(DpArgs), hipMemcpyHostToDevice, st));  // (pageable source: staged before the call returns)
+        HIP_TRY(hipMemcpyAsync(c->fused.d_args.p, &da, sizeof(DpArgs), hipMemcpyHostToDevice, st));  // (pageable source: staged before the call returns)
     }
-    const int maxr = c->plan.max_R;
+    const int maxr = c->wave.plan.max_R;
     const dim3 block(256), grid((da.n_tasks + 3) / 4), fgrid(static_cast<unsigned>((da.n_tasks + 3) / 4 + (n_quads + 3) / 4));
     by_std((c->flag & SFA_DTW) != 0, [&](auto S) {
         if (route == Route::Segments)
@@ -519,7 +492,7 @@ int enqueue_pass1(sfa_ctx *c, Route route, const BatchArgs &a, hipStream_t st) {
     });
     KERNEL_TRY();
     if (route == Route::Segments) {  // every hand-over between consecutive segments: assumed state == reached state?
-        HIP_TRY(hipMemsetAsync(c->d_segfail.p, 0, 4 * static_cast<size_t>(n_quads), st));
+        HIP_TRY(hipMemsetAsync(c->seg.d_segfail.p, 0, 4 * static_cast<size_t>(n_quads), st));
         const int64_t waves = static_cast<int64_t>(n_quads) * da.n_jobs * (da.n_seg - 1);
         hipLaunchKernelGGL(sfa::sdtw_verify_kernel, dim3(static_cast<unsigned>((waves + 3) / 4)), dim3(256), 0, st, da, n_quads);
         KERNEL_TRY();
@@ -531,7 +504,7 @@ int enqueue_pass1(sfa_ctx *c, Route route, const BatchArgs &a, hipStream_t st) {
 void launch_pass2(sfa_ctx *c, Route route, DpArgs ta, int32_t *out_st, hipStream_t st) {
     for (int i = 0; i < ta.n_cls; ++i) ta.cls[i].task_base = ta.cls[i].quad_base;  // one task per quad
     ta.n_tasks = ta.n_quads_total;
-    const int maxr = c->plan.max_R;
+    const int maxr = c->wave.plan.max_R;
     const dim3 grid((ta.n_tasks + 3) / 4), block(256);
     by_std((c->flag & SFA_DTW) != 0, [&](auto S) {
         if (lds(route))
@@ -548,7 +521,7 @@ int enqueue_pass2(sfa_ctx *c, Route route, const BatchArgs &a, hipStream_t st) {
     if (int rc = fused(route) ? SFA_OK : launch_finalize(a.fz, 1, st)) return rc;
     HIP_TRY(hipEventRecord(c->ev[2], st));
     if (own_launch) {
-        launch_pass2(c, route, a.da, c->d_tst.as<int32_t>(), st);
+        launch_pass2(c, route, a.da, c->wave.d_tst.as<int32_t>(), st);
         KERNEL_TRY();
     }
     HIP_TRY(hipEventRecord(c->ev[3], st));
@@ -568,7 +541,7 @@ int enqueue_secondaries(sfa_ctx *c, Route route, const BatchArgs &a, hipStream_t
         ta.w_job = sa.s_job + static_cast<size_t>(k) * n;
         ta.w_end = sa.s_end + static_cast<size_t>(k) * n;
         ta.w_score = sa.s_score + static_cast<size_t>(k) * n;
-        launch_pass2(c, route, ta, c->d_sts.as<int32_t>() + 2 * static_cast<size_t>(k) * n, st);
+        launch_pass2(c, route, ta, c->sec.d_sts.as<int32_t>() + 2 * static_cast<size_t>(k) * n, st);
         KERNEL_TRY();
     }
     sa.mode = 2;
@@ -583,12 +556,12 @@ int enqueue_batch(sfa_ctx *c, Route route, const BatchArgs &a, const int64_t *q_
     hipStream_t st = c->stream;
     const DpArgs &da = a.da;
     int rc;
-    if (da.prio_unit > 0) HIP_TRY(hipMemsetAsync(c->d_started.p, 0, 4, st));
+    if (da.prio_unit > 0) HIP_TRY(hipMemsetAsync(c->wave.d_started.p, 0, 4, st));
     HIP_TRY(hipEventRecord(c->ev[0], st));
     // reads with a NaN / inf query value are skipped (the reference aborts on them, see sdtw_screen_kernel)
-    HIP_TRY(hipMemsetAsync(c->d_badcount.p, 0, 32 + 4 * sfa::kSpanBuckets, st));  // word 0: non-finite reads; words 4..6: error words of the in-launch waits; words 2..3: LDS route, reads that left their record / started from scratch; words 8..39: span histogram
-    hipLaunchKernelGGL(sfa::sdtw_screen_kernel, dim3((da.n_reads_total + 3) / 4), dim3(256), 0, st, da.queries, da.q_off, da.n_reads_total, c->d_bad.as<uint8_t>(),
-                       c->d_badcount.as<unsigned>());
+    HIP_TRY(hipMemsetAsync(c->status.dev(), 0, sizeof(sfa::BatchStatus), st));
+    hipLaunchKernelGGL(sfa::sdtw_screen_kernel, dim3((da.n_reads_total + 3) / 4), dim3(256), 0, st, da.queries, da.q_off, da.n_reads_total, c->status.d_bad.as<uint8_t>(),
+                       &c->status.dev()->non_finite);
     KERNEL_TRY();
     // Queries beyond 2048 events: row strips, on their own stream BESIDE the wave kernels of the shorter reads of the batch (a
     // handful of short reads is one sweep's latency on an empty chip: 6 + 2.5 ms in front of 110 ms of strips when run in a
@@ -612,16 +585,16 @@ int enqueue_batch(sfa_ctx *c, Route route, const BatchArgs &a, const int64_t *q_
     if ((rc = enqueue_pass2(c, route, a, st))) return rc;
     if (c->opt_secondary > 0 && (rc = enqueue_secondaries(c, route, a, st))) return rc;
     c->prof.fill_launches = (route != Route::NoQuads ? 1 : 0) + long_launches;
-    c->long_pending = !lr.reads.empty();
-    if (c->long_pending) {  // join: what is left of the strips when the wave kernels are through counts as fill time
+    c->strips.long_pending = !lr.reads.empty();
+    if (c->strips.long_pending) {  // join: what is left of the strips when the wave kernels are through counts as fill time
         HIP_TRY(hipEventRecord(c->ev[5], st));
         HIP_TRY(hipStreamWaitEvent(st, c->lev[1], 0));
     }
-    HIP_TRY(hipMemcpyAsync(c->h_badcount.p, c->d_badcount.p, 32 + 4 * sfa::kSpanBuckets, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c->status.h_block.p, c->status.dev(), sizeof(sfa::BatchStatus), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(c->ev[4], st));
 
-    const sfa::BatchPlan &plan = c->plan;  // what resolve_profile() completes once the batch is through
-    c->prof.cells = (plan.query_events + lr.events) * c->total_cols;
+    const sfa::BatchPlan &plan = c->wave.plan;  // what resolve_profile() completes once the batch is through
+    c->prof.cells = (plan.query_events + lr.events) * c->model.total_cols;
     c->prof.ckpt_interval = plan.ck_shift ? (1 << plan.ck_shift) : 0;
     c->prof.ckpt_bytes = static_cast<int64_t>(sizeof(float)) * plan.ck_floats;
     c->prof.lds_ckpt = route == Route::LdsFused ? 2 : (route == Route::Lds ? 1 : 0);
@@ -630,7 +603,7 @@ int enqueue_batch(sfa_ctx *c, Route route, const BatchArgs &a, const int64_t *q_
     c->prof.n_tasks = plan.n_quads * plan.n_chunks;
     c->prof.n_chunks = plan.n_chunks;
     c->prof.n_segments = plan.n_seg;
-    c->prof.segment_reruns = c->seg_reruns;
+    c->prof.segment_reruns = c->seg.seg_reruns;
     c->prof_pending = true;
     return SFA_OK;
 }
@@ -639,10 +612,10 @@ int enqueue_batch(sfa_ctx *c, Route route, const BatchArgs &a, const int64_t *q_
 
 // Core of every align entry point: queries already in HBM, results left in HBM.
 int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32_t n, ResultRow *d_out, ResultRow *d_sec) {
-    if (!c->in_slice && !c->no_segments_once) {  // the call sfa_event_maps refers to from now on (not: a slice or a re-run of it)
-        c->map_n = n;
-        c->map_q_off.assign(q_off, q_off + n + 1);
-        c->map_queries = d_queries;
+    if (!c->in_slice && !c->seg.no_segments_once) {  // the call sfa_event_maps refers to from now on (not: a slice or a re-run of it)
+        c->maps.map_n = n;
+        c->maps.map_q_off.assign(q_off, q_off + n + 1);
+        c->maps.map_queries = d_queries;
     }
     if (n == 0) return SFA_OK;
     // secondary mappings: the plain two-pass route (HBM snapshots, no column segments, pass 2 as its own launches), whose fill keeps
@@ -650,9 +623,9 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
     const int n_sec = static_cast<int>(c->opt_secondary);
     const bool own_sec = n_sec > 0 && !d_sec;  // the call's own secondaries: sec_n names them once they are all enqueued
     if (own_sec) {
-        c->sec_n = -1;  // a call that fails or returns early leaves no rows to be taken for its own
-        if (int rc = c->d_sec.reserve(4 * sizeof(ResultRow) * static_cast<size_t>(n))) return rc;
-        d_sec = c->d_sec.as<ResultRow>();
+        c->sec.sec_n = -1;  // a call that fails or returns early leaves no rows to be taken for its own
+        if (int rc = c->sec.reserve_rows(static_cast<size_t>(n))) return rc;
+        d_sec = c->sec.d_sec.as<ResultRow>();
     }
     LongReads lr;
     for (int32_t i = 0; i < n; ++i)
@@ -663,43 +636,43 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
         }
     sfa::PlanParams pp = plan_params(c);
     pp.skip_long = !lr.reads.empty();
-    sfa::BatchPlan &plan = c->plan;  // kept with the context: its vectors are reused by every batch
+    sfa::BatchPlan &plan = c->wave.plan;  // kept with the context: its vectors are reused by every batch
     std::string perr;
-    if (int rc = sfa::plan_batch(q_off, n, c->h_job_len, c->total_cols, pp, &plan, &perr)) return fail(rc, "%s", perr.c_str());
+    if (int rc = sfa::plan_batch(q_off, n, c->model.h_job_len, c->model.total_cols, pp, &plan, &perr)) return fail(rc, "%s", perr.c_str());
     if (!c->in_slice && c->opt_ckpt_interval == 0 && plan.ck_shift > 9 && n >= 2 * c->opt_min_slice_reads) {
         // checkpoints at T = 512 would take about ck_bytes * T/512
         const int64_t want = (plan.ck_floats * 4 * (1ll << (plan.ck_shift - 9)) + pp.ckpt_budget_bytes - 1) / std::max<int64_t>(pp.ckpt_budget_bytes, 1);
         const int32_t slices = static_cast<int32_t>(std::min<int64_t>(want, n / c->opt_min_slice_reads));
         if (slices > 1) {
             const int rc = align_sliced(c, d_queries, q_off, n, d_out, d_sec, slices);
-            if (!rc && own_sec) c->sec_n = n;
+            if (!rc && own_sec) c->sec.sec_n = n;
             return rc;
         }
     }
     const Route route = sfa::choose_route(plan, pp.std_dtw, n_sec, c->opt_fused_trace, static_cast<int64_t>(c->cu_count) * 4 * SFA_LCK_WAVES);
-    const Staging sg(n, plan, c->n_jobs);
+    const Staging sg(n, plan, c->model.n_jobs);
     int rc;
     if ((rc = stage_and_reserve(c, q_off, n, route, sg))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_stage.p, c->h_stage.p, sg.bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->wave.d_stage.p, c->wave.h_stage.p, sg.bytes, hipMemcpyHostToDevice, c->stream));
     const BatchArgs a = batch_args(c, d_queries, n, d_out, d_sec, route, sg, !lr.reads.empty());
     if ((rc = enqueue_batch(c, route, a, q_off, lr))) return rc;
     if (route == Route::Segments) {
         // the verdict of the hand-over checks has to be known before anybody uses the rows: wait here (these are the small,
         // latency-bound batches -- their caller is about to wait for them anyway)
-        int32_t *flags = c->h_flags.as<int32_t>();
-        HIP_TRY(hipMemcpyAsync(flags, c->d_segfail.p, 4 * static_cast<size_t>(plan.n_quads), hipMemcpyDeviceToHost, c->stream));
+        int32_t *flags = c->seg.h_flags.as<int32_t>();
+        HIP_TRY(hipMemcpyAsync(flags, c->seg.d_segfail.p, 4 * static_cast<size_t>(plan.n_quads), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (std::any_of(flags, flags + plan.n_quads, [](int32_t f) { return f != 0; })) {
             // a guessed state was not the true one somewhere: the batch is walked again, unsegmented
-            c->no_segments_once = true;
+            c->seg.no_segments_once = true;
             rc = align_device(c, d_queries, q_off, n, d_out);
-            c->no_segments_once = false;
-            c->seg_reruns++;
-            c->prof.segment_reruns = c->seg_reruns;
+            c->seg.no_segments_once = false;
+            c->seg.seg_reruns++;
+            c->prof.segment_reruns = c->seg.seg_reruns;
             return rc;
         }
     }
-    if (own_sec) c->sec_n = n;
+    if (own_sec) c->sec.sec_n = n;
     return SFA_OK;
 }
 
@@ -712,62 +685,61 @@ int sfa::resolve_profile(sfa_ctx *c) {
     HIP_TRY(hipEventElapsedTime(&d, c->ev[2], c->ev[3]));
     HIP_TRY(hipEventElapsedTime(&t, c->ev[0], c->ev[4]));
     if (c->prof.fused_trace) d = 0;  // pass 2 ran inside the fill launch: there was no trace launch to time
-    if (c->long_pending) {  // the row-strip sweeps of long queries are fills
+    if (c->strips.long_pending) {  // the row-strip sweeps of long queries are fills
         float l = 0;
         HIP_TRY(hipEventElapsedTime(&l, c->ev[5], c->ev[4]));
         a += l;
         a = t;  // ... and ran BESIDE the wave kernels: the intervals on this stream say nothing about stages
         d = 0;
-        c->long_pending = false;
+        c->strips.long_pending = false;
     }
     c->prof.events_ms = c->prof.normalise_ms = 0;
     c->prof.decode_ms = 0;
-    c->prof.blow5_fallbacks = c->blow5_fallbacks;
-    if (c->bev_pending) {
+    c->prof.blow5_fallbacks = c->blow5.blow5_fallbacks;
+    if (c->blow5.bev_pending) {
         float d1 = 0;
         HIP_TRY(hipEventElapsedTime(&d1, c->bev[0], c->bev[1]));
         c->prof.decode_ms = d1;
-        c->bev_pending = false;
+        c->blow5.bev_pending = false;
     }
-    if (c->eev_pending) {
+    if (c->raw.eev_pending) {
         float e1 = 0, e2 = 0;
         HIP_TRY(hipEventElapsedTime(&e1, c->eev[0], c->eev[1]));
         HIP_TRY(hipEventElapsedTime(&e2, c->eev[2], c->eev[3]));
         c->prof.events_ms = e1;
         c->prof.normalise_ms = e2;
-        c->eev_pending = false;
+        c->raw.eev_pending = false;
     }
-    c->prof.non_finite_reads = c->h_badcount.p ? *c->h_badcount.as<unsigned>() : 0;  // (copied before ev[4], which has been waited for)
-    c->prof.lck_fallbacks = c->h_badcount.p ? c->h_badcount.as<unsigned>()[2] : 0;
-    c->prof.lck_from_scratch = c->h_badcount.p ? c->h_badcount.as<unsigned>()[3] : 0;
+    const sfa::BatchStatus *bs = c->status.host();  // (copied before ev[4], which has been waited for)
+    c->prof.non_finite_reads = bs ? bs->non_finite : 0;
+    c->prof.lck_fallbacks = bs ? bs->lck_fallbacks : 0;
+    c->prof.lck_from_scratch = bs ? bs->lck_from_scratch : 0;
     c->prof.fill_ms = a;
     c->prof.trace_ms = d;
     c->prof.finalize_ms = t - a - d;
     c->prof.total_ms = t;
     c->prof_pending = false;
-    if (c->h_badcount.p) {  // a wave of the batch gave up waiting for another one (bounded_wait_ge): the rows are not to be used
-        const unsigned *e = c->h_badcount.as<unsigned>() + 4;
-        if (e[0] == sfa::kErrQuadWait)
-            return fail(SFA_EKERNEL, "fused launch: pass 2 of quad %u waited %lld ms for its fill tasks (%u of them had completed); rows of this batch are invalid",
-                        e[1], (long long)c->quad_limit_ms, e[2]);
-        if (e[0] == sfa::kErrStripWait)
-            return fail(SFA_EKERNEL, "row strips: a strip waited %lld ms for column %u of the row above (column %u was published); rows of this batch are invalid",
-                        (long long)c->strip_limit_ms, e[1], e[2]);
-        if (e[0]) return fail(SFA_EKERNEL, "device error word %u (%u, %u)", e[0], e[1], e[2]);
-    }
-    if (c->h_badcount.p) {  // spans of this (valid) batch's alignments -> head start of the next batch's pass 2 (sfa_plan.hpp)
-        const unsigned *h = c->h_badcount.as<unsigned>() + 8;
-        uint64_t total = 0;
-        for (int b = 0; b < sfa::kSpanBuckets; ++b) total += h[b];
-        if (total >= 64) {  // the bucket below which 99.9 % of the alignments lie (its upper edge: b + 1 sixteenths) and one more, never above a whole query
-            uint64_t acc = 0;
-            int b = 0;
-            for (; b < sfa::kSpanBuckets; ++b) {
-                acc += h[b];
-                if (acc * 1000 >= total * 999) break;
-            }
-            c->span_sixteenths = std::min(16, b + 2);
+    if (!bs) return SFA_OK;
+    const unsigned *e = bs->err;  // a wave of the batch gave up waiting for another one (bounded_wait_ge): the rows are not to be used
+    if (e[0] == sfa::kErrQuadWait)
+        return fail(SFA_EKERNEL, "fused launch: pass 2 of quad %u waited %lld ms for its fill tasks (%u of them had completed); rows of this batch are invalid",
+                    e[1], (long long)c->wave.quad_limit_ms, e[2]);
+    if (e[0] == sfa::kErrStripWait)
+        return fail(SFA_EKERNEL, "row strips: a strip waited %lld ms for column %u of the row above (column %u was published); rows of this batch are invalid",
+                    (long long)c->strips.strip_limit_ms, e[1], e[2]);
+    if (e[0]) return fail(SFA_EKERNEL, "device error word %u (%u, %u)", e[0], e[1], e[2]);
+    // spans of this (valid) batch's alignments -> head start of the next batch's pass 2 (sfa_plan.hpp)
+    const unsigned *h = bs->span_hist;
+    uint64_t total = 0;
+    for (int b = 0; b < sfa::kSpanBuckets; ++b) total += h[b];
+    if (total >= 64) {  // the bucket below which 99.9 % of the alignments lie (its upper edge: b + 1 sixteenths) and one more, never above a whole query
+        uint64_t acc = 0;
+        int b = 0;
+        for (; b < sfa::kSpanBuckets; ++b) {
+            acc += h[b];
+            if (acc * 1000 >= total * 999) break;
         }
+        c->wave.span_sixteenths = std::min(16, b + 2);
     }
     return SFA_OK;
 }
@@ -794,20 +766,20 @@ int sfa_align_batch_device(sfa_ctx_t *c, const float *d_queries, const int64_t *
 int sfa_submit_batch(sfa_ctx_t *c, const float *queries, const int64_t *q_off, int32_t n) {
     if (!c || !q_off || n < 0 || (n > 0 && !queries)) return fail(SFA_EINVAL, "sfa_submit_batch: bad argument");
     if (!c->shards.empty()) {  // every shard queues its contiguous range of reads on its own device
-        c->pending_n = -1;
+        c->io.pending_n = -1;
         const int rc = for_each_shard_range(c, n, [&](size_t r, int32_t lo, int32_t hi) {
             return sfa_submit_batch(c->shards[r], queries, q_off + lo, hi - lo);  // (q_off holds absolute offsets into queries)
         }, &c->shard_lo);  // (sfa_wait_batch collects by the same ranges)
-        if (!rc) c->pending_n = n;
-        c->map_n = rc ? -1 : n;
+        if (!rc) c->io.pending_n = n;
+        c->maps.map_n = rc ? -1 : n;
         return rc;
     }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));  // one batch in flight per context
     if (int rc = resolve_profile(c)) return rc;  // a batch submitted and never waited for: its error words are this call's
-    c->pending_n = -1;
+    c->io.pending_n = -1;
     if (n == 0) {
-        c->pending_n = 0;
+        c->io.pending_n = 0;
         return SFA_OK;
     }
     const int64_t nq = q_off[n] - q_off[0];
@@ -821,21 +793,19 @@ int sfa_submit_batch(sfa_ctx_t *c, const float *queries, const int64_t *q_off, i
         for (int32_t i = 0; i <= n; ++i) rebased[i] = q_off[i] - q_off[0];
         qo = rebased.data();
     }
-    if ((rc = c->d_queries.reserve(sizeof(float) * std::max<int64_t>(nq, 1))) || (rc = c->d_out.reserve(sizeof(sfa_result_t) * n)) ||
-        (rc = c->h_out.reserve(sizeof(sfa_result_t) * n)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_queries.p, queries + q_off[0], sizeof(float) * nq, hipMemcpyHostToDevice, c->stream));
-    if ((rc = align_device(c, c->d_queries.as<float>(), qo, n, c->d_out.as<ResultRow>()))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->h_out.p, c->d_out.p, sizeof(sfa_result_t) * n, hipMemcpyDeviceToHost, c->stream));
-    c->pending_n = n;
+    if ((rc = c->io.reserve(nq, static_cast<size_t>(n)))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->io.d_queries.p, queries + q_off[0], sizeof(float) * nq, hipMemcpyHostToDevice, c->stream));
+    if ((rc = align_device(c, c->io.d_queries.as<float>(), qo, n, c->io.d_out.as<ResultRow>()))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->io.h_out.p, c->io.d_out.p, sizeof(sfa_result_t) * n, hipMemcpyDeviceToHost, c->stream));
+    c->io.pending_n = n;
     return SFA_OK;
 }
 
 int sfa_wait_batch(sfa_ctx_t *c, sfa_result_t *out, int32_t n) {
     if (!c || n < 0 || (n > 0 && !out)) return fail(SFA_EINVAL, "sfa_wait_batch: bad argument");
-    if (c->pending_n < 0) return fail(SFA_EINVAL, "sfa_wait_batch: no batch was submitted");
-    if (c->pending_n != n) return fail(SFA_EINVAL, "sfa_wait_batch: %d reads were submitted, %d asked for", c->pending_n, n);
-    c->pending_n = -1;
+    if (c->io.pending_n < 0) return fail(SFA_EINVAL, "sfa_wait_batch: no batch was submitted");
+    if (c->io.pending_n != n) return fail(SFA_EINVAL, "sfa_wait_batch: %d reads were submitted, %d asked for", c->io.pending_n, n);
+    c->io.pending_n = -1;
     if (!c->shards.empty())  // rows of shard r go to out[lo_r, hi_r): input order, no gather step in a single process
         return for_each_shard(c, [&](size_t r) {  // (shards without reads were not submitted to)
             const int32_t lo = c->shard_lo[r], hi = c->shard_lo[r + 1];
@@ -844,7 +814,7 @@ int sfa_wait_batch(sfa_ctx_t *c, sfa_result_t *out, int32_t n) {
     if (n == 0) return SFA_OK;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    memcpy(out, c->h_out.p, sizeof(sfa_result_t) * n);
+    memcpy(out, c->io.h_out.p, sizeof(sfa_result_t) * n);
     return resolve_profile(c);
 }
 
@@ -858,10 +828,10 @@ int sfa_secondary_rows(sfa_ctx_t *c, sfa_result_t *sec, int32_t n) {
     }
     if (c->opt_secondary == 0) return fail(SFA_EINVAL, "sfa_secondary_rows: the 'secondary' option is 0");
     if (n == 0) return SFA_OK;
-    if (c->sec_n != n) return fail(SFA_EINVAL, "sfa_secondary_rows: the last call aligned %d reads with secondaries, %d asked for", c->sec_n, n);
+    if (c->sec.sec_n != n) return fail(SFA_EINVAL, "sfa_secondary_rows: the last call aligned %d reads with secondaries, %d asked for", c->sec.sec_n, n);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(sec, c->d_sec.p, 4 * sizeof(sfa_result_t) * static_cast<size_t>(n), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sec, c->sec.d_sec.p, 4 * sizeof(sfa_result_t) * static_cast<size_t>(n), hipMemcpyDeviceToHost));
     return SFA_OK;
 }
 
@@ -896,8 +866,8 @@ int sfa_align_events(sfa_ctx_t *c, const sfa_event_t *const *events, const int64
     if (c->shards.empty()) {
         HIP_TRY(hipSetDevice(c->device));
         HIP_TRY(hipStreamSynchronize(c->stream));  // the previous batch may still be uploading from the buffer
-        if (int rc = c->h_queries.reserve(sizeof(float) * static_cast<size_t>(std::max<int64_t>(total, 1)))) return rc;
-        dst = c->h_queries.as<float>();
+        if (int rc = c->io.h_queries.reserve(sizeof(float) * static_cast<size_t>(std::max<int64_t>(total, 1)))) return rc;
+        dst = c->io.h_queries.as<float>();
     } else {
         heap.reset(new float[static_cast<size_t>(std::max<int64_t>(total, 1))]);
         dst = heap.get();

@@ -2,7 +2,6 @@
 // 221-225).  Packs the reference event arrays into one padded HBM buffer per device, owns streams / events / scratch, options,
 // profile, and the small device utilities.
 #include "sfa_ctx.hpp"
-#include "sdtw_kernels.hpp"  // kRefPad, the debug task-time layout
 
 namespace sfa {
 std::string &last_error_slot() {
@@ -92,48 +91,42 @@ static int create_context(sfa_ctx **out, const HostRef &h, uint32_t flag, int de
     c->device = device;
     c->flag = flag;
     c->cu_count = prop.multiProcessorCount;
-    c->num_ref = h.num_ref;
-    c->n_jobs = h.n_jobs;
-    c->total_cols = h.total_cols;
-    c->h_job_len = h.job_len;
-    c->h_job_off = h.job_off;
-    c->h_ref_off = h.ref_off;
+    c->model.num_ref = h.num_ref;
+    c->model.n_jobs = h.n_jobs;
+    c->model.total_cols = h.total_cols;
+    c->model.h_job_len = h.job_len;
+    c->model.h_job_off = h.job_off;
+    c->model.h_ref_off = h.ref_off;
     auto bail = [&](int rc) {
         sfa_destroy(c);
         return rc;
     };
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(SFA_ENODEV, "hipStreamCreate failed"));
-    if (hipStreamCreateWithFlags(&c->stream_long, hipStreamNonBlocking) != hipSuccess) return bail(fail(SFA_ENODEV, "hipStreamCreate failed"));
-    if (hipStreamCreateWithFlags(&c->stream_long2, hipStreamNonBlocking) != hipSuccess) return bail(fail(SFA_ENODEV, "hipStreamCreate failed"));
-    for (auto &e : c->lev)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return bail(fail(SFA_ENODEV, "hipEventCreate failed"));
-    for (auto &e : c->ev)
-        if (hipEventCreate(&e) != hipSuccess) return bail(fail(SFA_ENODEV, "hipEventCreate failed"));
-    for (auto &e : c->eev)
-        if (hipEventCreate(&e) != hipSuccess) return bail(fail(SFA_ENODEV, "hipEventCreate failed"));
-    for (auto &e : c->bev)
-        if (hipEventCreate(&e) != hipSuccess) return bail(fail(SFA_ENODEV, "hipEventCreate failed"));
-    int rc;
+    for (Stream *s : {&c->stream, &c->stream_long, &c->stream_long2})
+        if (hipStreamCreateWithFlags(&s->h, hipStreamNonBlocking) != hipSuccess) return bail(fail(SFA_ENODEV, "hipStreamCreate failed"));
+    for (Event &e : c->lev)
+        if (hipEventCreateWithFlags(&e.h, hipEventDisableTiming) != hipSuccess) return bail(fail(SFA_ENODEV, "hipEventCreate failed"));
+    for (Event &e : c->ev)
+        if (hipEventCreate(&e.h) != hipSuccess) return bail(fail(SFA_ENODEV, "hipEventCreate failed"));
+    for (Event &e : c->eev)
+        if (hipEventCreate(&e.h) != hipSuccess) return bail(fail(SFA_ENODEV, "hipEventCreate failed"));
+    for (Event &e : c->bev)
+        if (hipEventCreate(&e.h) != hipSuccess) return bail(fail(SFA_ENODEV, "hipEventCreate failed"));
     const size_t ref_bytes = sizeof(float) * h.packed.size();
-    if ((rc = c->d_ref.reserve(ref_bytes)) || (rc = c->d_job_off.reserve(sizeof(int64_t) * c->n_jobs)) ||
-        (rc = c->d_job_len.reserve(sizeof(int32_t) * c->n_jobs)) || (rc = c->d_job_contig.reserve(sizeof(int32_t) * c->n_jobs)) ||
-        (rc = c->d_job_strand.reserve(c->n_jobs)) || (rc = c->d_ref_len.reserve(sizeof(int32_t) * h.num_ref)) ||
-        (rc = c->d_ref_off.reserve(sizeof(int32_t) * h.num_ref)))
-        return bail(rc);
+    if (int rc = c->model.reserve(ref_bytes)) return bail(rc);
 #define UP(dst, src, bytes) \
     if (hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return bail(fail(SFA_ENODEV, "upload of reference model failed"))
     if (peer) {
-        if (hipMemcpyPeer(c->d_ref.p, device, peer->d_ref.p, peer->device, ref_bytes) != hipSuccess)
+        if (hipMemcpyPeer(c->model.d_ref.p, device, peer->model.d_ref.p, peer->device, ref_bytes) != hipSuccess)
             return bail(fail(SFA_ENODEV, "device-to-device copy of the reference model (%d -> %d) failed", peer->device, device));
     } else {
-        UP(c->d_ref.p, h.packed.data(), ref_bytes);
+        UP(c->model.d_ref.p, h.packed.data(), ref_bytes);
     }
-    UP(c->d_job_off.p, h.job_off.data(), sizeof(int64_t) * c->n_jobs);
-    UP(c->d_job_len.p, h.job_len.data(), sizeof(int32_t) * c->n_jobs);
-    UP(c->d_job_contig.p, h.job_contig.data(), sizeof(int32_t) * c->n_jobs);
-    UP(c->d_job_strand.p, h.job_strand.data(), c->n_jobs);
-    UP(c->d_ref_len.p, h.ref_len.data(), sizeof(int32_t) * h.num_ref);
-    UP(c->d_ref_off.p, h.ref_off.data(), sizeof(int32_t) * h.num_ref);
+    UP(c->model.d_job_off.p, h.job_off.data(), sizeof(int64_t) * c->model.n_jobs);
+    UP(c->model.d_job_len.p, h.job_len.data(), sizeof(int32_t) * c->model.n_jobs);
+    UP(c->model.d_job_contig.p, h.job_contig.data(), sizeof(int32_t) * c->model.n_jobs);
+    UP(c->model.d_job_strand.p, h.job_strand.data(), c->model.n_jobs);
+    UP(c->model.d_ref_len.p, h.ref_len.data(), sizeof(int32_t) * h.num_ref);
+    UP(c->model.d_ref_off.p, h.ref_off.data(), sizeof(int32_t) * h.num_ref);
 #undef UP
     *out = c;
     return SFA_OK;
@@ -179,33 +172,7 @@ void sfa_destroy(sfa_ctx_t *c) {
     }
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (DevBuf *b : {&c->d_ref, &c->d_job_off, &c->d_job_len, &c->d_job_contig, &c->d_job_strand, &c->d_ref_len, &c->d_ref_off,
-                      &c->d_queries, &c->d_stage, &c->d_pbest, &c->d_pend, &c->d_pjob, &c->d_psecond, &c->d_wjob,
-                      &c->d_wend, &c->d_wscore, &c->d_tst, &c->d_ck, &c->d_out, &c->e_raw, &c->e_rawoff, &c->e_scale, &c->e_sum,
-                      &c->e_sumsq, &c->e_t1, &c->e_t2, &c->e_evoff, &c->e_evstart, &c->e_evlen, &c->e_evmean, &c->e_evstdv, &c->e_nev,
-                      &c->e_qstart, &c->e_qoff, &c->e_b0, &c->e_b1, &c->e_b2, &c->e_flag, &c->e_qev, &c->e_pflag, &c->d_verify, &c->d_segfail, &c->d_bndc, &c->d_long, &c->d_lbest, &c->d_lsecond, &c->d_lend, &c->d_lwin, &c->d_lck, &c->d_lprog, &c->d_lticket, &c->d_times, &c->d_ltimes, &c->d_started, &c->d_bad, &c->d_badcount, &c->d_bestrec, &c->d_beste, &c->d_gbest, &c->d_wchunk, &c->d_ticket, &c->d_quaddone, &c->d_args, &c->b_in, &c->b_inoff, &c->b_out, &c->b_outoff, &c->b_len, &c->b_head, &c->b_bad, &c->d_mv, &c->d_prow, &c->d_pairs, &c->d_pfirst})
-        b->release();
-    c->h_stage.release();
-    c->h_out.release();
-    c->h_small.release();
-    c->h_flags.release();
-    c->h_queries.release();
-    c->h_long.release();
-    c->h_badcount.release();
-    c->h_head.release();
-    c->h_pairs.release();
-    for (auto &e : c->bev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->eev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->lev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->stream_long2) (void)hipStreamDestroy(c->stream_long2);
-    if (c->stream_long) (void)hipStreamDestroy(c->stream_long);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // buffers, then events, then streams (the order of the members of sfa_ctx)
 }
 
 int sfa_set_pore(sfa_ctx_t *c, int pore) {
@@ -367,15 +334,15 @@ int sfa_n_devices(sfa_ctx_t *c) { return !c ? 0 : (c->shards.empty() ? 1 : stati
 int64_t sfa_debug_task_times(sfa_ctx_t *c, unsigned long long *out, int64_t cap_tasks) {
     if (!c || !out) return -1;
     if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return -1;
-    const int64_t n = std::min<int64_t>(cap_tasks, c->n_times);
-    if (n > 0 && hipMemcpy(out, c->d_times.p, 24 * static_cast<size_t>(n), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    const int64_t n = std::min<int64_t>(cap_tasks, c->times.n_times);
+    if (n > 0 && hipMemcpy(out, c->times.d_times.p, 24 * static_cast<size_t>(n), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return n;
 }
 int64_t sfa_debug_task_times_long(sfa_ctx_t *c, unsigned long long *out, int64_t cap_tasks) {
     if (!c || !out) return -1;
     if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;
-    const int64_t n = std::min<int64_t>(cap_tasks, c->n_ltimes);
-    if (n > 0 && hipMemcpy(out, c->d_ltimes.p, 24 * static_cast<size_t>(n), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    const int64_t n = std::min<int64_t>(cap_tasks, c->times.n_ltimes);
+    if (n > 0 && hipMemcpy(out, c->times.d_ltimes.p, 24 * static_cast<size_t>(n), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return n;
 }
 #endif

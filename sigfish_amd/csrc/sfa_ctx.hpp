@@ -1,5 +1,8 @@
-// sfa_ctx.hpp -- what the units of the C-ABI share (include/sigfish_amd.h): error reporting, grow-only device / page-locked
-// buffers, the context, and the few internal functions that cross unit boundaries.
+// sfa_ctx.hpp -- what the units of the C-ABI share (include/sigfish_amd.h): error reporting, the buffer, stream and event types
+// that free themselves (sfa_buf.hpp: Buf<Mem>; here its two allocators, DevBuf / PinBuf), the context, and the few internal
+// functions that cross unit boundaries.  The context (sfa_ctx) is its streams and events, the options, and one struct per stage
+// (namespace ctx) holding that stage's buffers, what it keeps between calls and reserve(), the sizes of its buffers; sfa_destroy
+// names none of them.
 //   sfa_context.hip  contexts: init / destroy, devices, options, profile, small utilities
 //   sfa_align.hip    the alignment stage: planner -> launches (wave kernels, row strips) -> rows; the batch entry points
 //   sfa_maps.hip     event maps of the last call's rows (sdtw_path.hpp)
@@ -23,11 +26,9 @@
 #include <vector>
 
 #include "../../include/sigfish_amd.h"
+#include "sdtw_kernels.hpp"  // BatchStatus, the sizes of the kernels' records
+#include "sfa_buf.hpp"
 #include "sfa_plan.hpp"
-
-namespace sfa {
-std::string &last_error_slot();  // this thread's sfa_last_error() text (sfa_context.hip)
-}
 
 namespace {
 
@@ -57,60 +58,47 @@ int fail(int code, const char *fmt, ...) {
         if (e_ != hipSuccess) return fail(SFA_EKERNEL, "kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-// A device buffer that only ever grows (batches reuse it; nothing is allocated inside a steady-state call).
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return SFA_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 8 + 256;
-        if (hipMalloc(&p, want) != hipSuccess) {
-            p = nullptr;
-            return fail(SFA_ENOMEM, "hipMalloc(%zu bytes) failed", want);
-        }
-        cap = want;
-        return SFA_OK;
+// The context's buffers (sfa_buf.hpp): device memory and page-locked host memory
+struct DevMem {
+    static constexpr const char *name = "hipMalloc";
+    static void *alloc(size_t bytes) {
+        void *p = nullptr;
+        return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr;
     }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <typename T>
-    T *as() const {
-        return static_cast<T *>(p);
-    }
+    static void free(void *p) { (void)hipFree(p); }
 };
+struct PinMem {
+    static constexpr const char *name = "hipHostMalloc";
+    static void *alloc(size_t bytes) {
+        void *p = nullptr;
+        return hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+    }
+    static void free(void *p) { (void)hipHostFree(p); }
+};
+using DevBuf = sfa::Buf<DevMem>;
+using PinBuf = sfa::Buf<PinMem>;
 
-struct PinBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return SFA_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 8 + 256;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
-            p = nullptr;
-            return fail(SFA_ENOMEM, "hipHostMalloc(%zu bytes) failed", want);
-        }
-        cap = want;
-        return SFA_OK;
+// reserve(bytes) of every (buffer, bytes) pair in turn; the first failure ends it and is the result
+template <class B, class... Rest>
+int reserve_all(B &buf, size_t bytes, Rest &&...rest) {
+    if (int rc = buf.reserve(bytes)) return rc;
+    if constexpr (sizeof...(rest) > 0) return reserve_all(rest...);
+    return SFA_OK;
+}
+
+// A stream / an event of the context: created by create_context (sfa_context.hip), destroyed with the context
+template <class T, hipError_t (*Destroy)(T)>
+struct Owned {
+    T h = nullptr;
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    ~Owned() {
+        if (h) (void)Destroy(h);
     }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <typename T>
-    T *as() const {
-        return static_cast<T *>(p);
-    }
+    operator T() const { return h; }
 };
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
 
 // One host thread per shard of a group context (sfa_init_devices), alive as long as the context: HIP's current device and
 // sfa_last_error are per thread, so every shard's calls are made from its own thread -- but not from a fresh one per call
@@ -173,6 +161,161 @@ class ShardWorker {
 
 }  // namespace
 
+// ---- the context's state, one struct per stage that owns it: its buffers, what it keeps between calls, and reserve(), the one
+// place that says how large each buffer has to be.  Every buffer frees itself with the context. ----
+namespace ctx {
+
+struct RefModel {  // the reference event model (immutable after init)
+    int32_t num_ref = 0, n_jobs = 0;
+    int64_t total_cols = 0;  // sum over jobs of rlen
+    std::vector<int32_t> h_job_len;
+    std::vector<int64_t> h_job_off;   // [n_jobs] column 0 of every (contig,strand) array in d_ref
+    std::vector<int32_t> h_ref_off;   // [num_ref] ref_st_offset
+    DevBuf d_ref, d_job_off, d_job_len, d_job_contig, d_job_strand, d_ref_len, d_ref_off;
+    int reserve(size_t ref_bytes) {
+        const size_t j = n_jobs, r = num_ref;
+        return reserve_all(d_ref, ref_bytes, d_job_off, sizeof(int64_t) * j, d_job_len, sizeof(int32_t) * j, d_job_contig, sizeof(int32_t) * j,
+                           d_job_strand, j, d_ref_len, sizeof(int32_t) * r, d_ref_off, sizeof(int32_t) * r);
+    }
+};
+
+struct CallerIO {  // queries in, rows out, of the entry points that take host memory
+    DevBuf d_queries, d_out;
+    PinBuf h_out, h_small;
+    PinBuf h_queries;  // sfa_align_events: the gathered event means (page-locked: the upload from here is asynchronous)
+    int32_t pending_n = -1;  // reads of the batch submitted with sfa_submit_batch and not yet collected
+    int reserve(int64_t query_floats, size_t n) {
+        return reserve_all(d_queries, sizeof(float) * static_cast<size_t>(std::max<int64_t>(query_floats, 1)), d_out, sizeof(sfa_result_t) * n,
+                           h_out, sizeof(sfa_result_t) * n);
+    }
+};
+
+struct Status {  // what a batch reports about itself
+    DevBuf d_bad;    // sdtw_screen_kernel: per-read flag
+    DevBuf d_block;  // the batch's sfa::BatchStatus (sdtw_kernels.hpp) ...
+    PinBuf h_block;  // ... and where it is copied once the batch is through (resolve_profile reads it)
+    int reserve(size_t n) { return reserve_all(d_bad, n, d_block, sizeof(sfa::BatchStatus), h_block, sizeof(sfa::BatchStatus)); }
+    sfa::BatchStatus *dev() const { return d_block.as<sfa::BatchStatus>(); }
+    const sfa::BatchStatus *host() const { return h_block.as<sfa::BatchStatus>(); }  // nullptr: no batch yet
+};
+
+struct WaveKernels {  // every route: the plan in the staging area, partial results of the fill tasks, the winners
+    DevBuf d_stage, d_pbest, d_pend, d_pjob, d_psecond, d_wjob, d_wend, d_wscore, d_tst, d_ck;
+    DevBuf d_wchunk;   // winning chunk of every read
+    DevBuf d_started;  // counter of the fill's tasks that have begun (IssuePriority)
+    PinBuf h_stage;
+    sfa::BatchPlan plan;  // plan of the batch being submitted (scratch included)
+    int32_t span_sixteenths = 0;  // pass 2's head start on the HBM-snapshot route follows the spans of the previous batch's alignments: sixteenths of the query length (0: not known yet -> a whole query length)
+    int64_t quad_limit_ms = 0;    // the limit the last batch's waits actually ran with (floor applied), for the error message
+    // n_part: partial results, four per (quad, chunk)
+    int reserve(size_t stage_bytes, size_t n_part, size_t n, int64_t ck_floats) {
+        if (int rc = reserve_all(h_stage, stage_bytes, d_stage, stage_bytes, d_pbest, 4 * n_part, d_pend, 4 * n_part, d_pjob, 4 * n_part,
+                                 d_psecond, 4 * n_part, d_wjob, 4 * n, d_wend, 4 * n, d_tst, 8 * n, d_wscore, 4 * n, d_wchunk, 4 * n, d_started, 64))
+            return rc;
+        return ck_floats > 0 ? d_ck.reserve(sizeof(float) * ck_floats) : SFA_OK;
+    }
+};
+
+struct FusedLaunch {  // the kernel's argument block in device memory (DpArgs::self), ticket counter, completed fill tasks per quad
+    DevBuf d_args, d_ticket, d_quaddone;
+    int reserve(size_t n_quads) { return reserve_all(d_args, sizeof(sfa::DpArgs), d_ticket, 64, d_quaddone, 4 * n_quads); }
+};
+
+struct LdsRoute {  // LDS-checkpoint fill: records of the best windows, their step, per-read best score
+    DevBuf d_bestrec, d_beste, d_gbest;
+    int reserve(size_t n_part, size_t n) {
+        return reserve_all(d_bestrec, sizeof(float) * sfa::kLdsCkPlanes * 64 * n_part / 4, d_beste, 4 * n_part, d_gbest, 4 * n);
+    }
+};
+
+struct Segments {  // column segments: the states at the hand-overs, one verdict per quad
+    DevBuf d_verify, d_segfail;
+    PinBuf h_flags;
+    int64_t seg_reruns = 0;         // batches walked again because a segment hand-over did not verify
+    bool no_segments_once = false;  // re-run of a batch whose segment hand-overs did not verify
+    int reserve(const sfa::BatchPlan &p, size_t n_jobs) {
+        const size_t q = p.n_quads;
+        return reserve_all(d_verify, sizeof(float) * 64 * (p.max_R + 1) * 2 * static_cast<size_t>(p.n_seg) * n_jobs * q, d_segfail, 4 * q, h_flags, 4 * q);
+    }
+};
+
+struct Strips {  // row strips (queries beyond SFA_MAX_QUERY, sdtw_strips.hpp)
+    DevBuf d_lprog, d_lticket;  // pipelined strips: progress counters, ticket
+    DevBuf d_bndc, d_long, d_lbest, d_lsecond, d_lend, d_lwin, d_lck;
+    PinBuf h_long;
+    bool long_pending = false;
+    int64_t strip_limit_ms = 0;  // the limit the last batch's waits actually ran with (floor applied), for the error message
+    int reserve_staging(size_t bytes) { return reserve_all(h_long, bytes, d_long, bytes); }
+    // n_part: (read, job) pairs; a freshly grown d_bndc is set to 3.4e38 everywhere on `st` (see the pad note in sdtw_strips.hpp)
+    int reserve(size_t prog_bytes, size_t bndc_floats, size_t lck_floats, size_t n_part, size_t n_long, hipStream_t st) {
+        const size_t bndc_cap = d_bndc.cap;
+        if (int rc = reserve_all(d_lprog, prog_bytes, d_lticket, 128, d_bndc, sizeof(float) * bndc_floats, d_lbest, 4 * n_part, d_lsecond, 4 * n_part,
+                                 d_lend, 4 * n_part, d_lwin, 4 * 5 * n_long, d_lck, sizeof(float) * lck_floats))
+            return rc;
+        if (d_bndc.cap != bndc_cap) HIP_TRY(hipMemsetAsync(d_bndc.p, 0x7f, d_bndc.cap, st));
+        return SFA_OK;
+    }
+};
+
+struct Secondaries {  // secondary mappings: top-5 partials, merged candidates, their traced columns, rows [n][4]
+    DevBuf d_p5, d_swin, d_sts, d_sec;
+    int32_t sec_n = -1;  // reads of the last call whose secondaries d_sec holds
+    int reserve(size_t n_part, size_t n) { return reserve_all(d_p5, 4 * sfa::kTop5Words * n_part, d_swin, 4 * 15 * n, d_sts, 4 * 10 * n); }
+    int reserve_rows(size_t n) { return d_sec.reserve(4 * sizeof(sfa::ResultRow) * n); }  // (only a call that keeps its own rows)
+};
+
+struct RawSignal {  // sfa_align_raw: samples, prefix sums, t-statistics, events, query windows, raw-coordinate columns
+    DevBuf e_raw, e_rawoff, e_scale, e_sum, e_sumsq, e_t1, e_t2, e_evoff, e_evstart, e_evlen, e_evmean, e_evstdv, e_nev, e_qstart,
+        e_qoff, e_b0, e_b1, e_b2, e_flag, e_qev, e_pflag;
+    bool eev_pending = false;
+    int reserve_samples(int64_t total, size_t n) { return reserve_all(e_raw, 2 * static_cast<size_t>(std::max<int64_t>(total, 1)), e_rawoff, 8 * (n + 1)); }
+    int reserve(int64_t total, size_t n, size_t ev_total) {
+        const size_t t1 = static_cast<size_t>(std::max<int64_t>(total, 1));
+        if (int rc = reserve_samples(total, n)) return rc;
+        return reserve_all(e_scale, 8 * n, e_sum, 8 * (total + n), e_sumsq, 8 * (total + n), e_t1, 4 * t1, e_t2, 4 * t1, e_evoff, 8 * (n + 1),
+                           e_evstart, 4 * ev_total, e_evlen, 4 * ev_total, e_evmean, 4 * ev_total, e_evstdv, 4 * ev_total, e_nev, 8 * n,
+                           e_qstart, 8 * n, e_qoff, 8 * (n + 1), e_flag, 4 * n, e_pflag, 4 * n, e_b0, 4 * n, e_b1, 4 * n, e_b2, 4 * n);
+    }
+};
+
+struct Blow5 {  // sfa_align_blow5: record bytes, inflated payloads, field rows
+    DevBuf b_in, b_inoff, b_out, b_outoff, b_len, b_head, b_bad;
+    PinBuf h_head;
+    bool bev_pending = false;
+    int64_t blow5_fallbacks = 0;  // batches handed to the host reader because the device declined a record
+    // the inflate's own buffers; out_bytes < 0: records that are not compressed
+    int reserve_inflate(size_t in_bytes, int64_t out_bytes, size_t n) {
+        if (int rc = reserve_all(b_in, in_bytes + 128, b_inoff, 8 * (n + 1), b_len, 4 * n)) return rc;
+        return out_bytes < 0 ? SFA_OK : reserve_all(b_out, static_cast<size_t>(out_bytes) + 64, b_outoff, 8 * (n + 1));
+    }
+    int reserve(size_t in_bytes, int64_t out_bytes, size_t n, size_t head_bytes) {
+        if (int rc = reserve_inflate(in_bytes, out_bytes, n)) return rc;
+        return reserve_all(b_head, n * head_bytes, h_head, n * head_bytes + 8 * n, b_bad, 4 * n);
+    }
+};
+
+// sfa_event_maps: what the last align call left behind -- its read count (-1: none), the offsets of its queries and where they
+// are (the context's d_queries, or the caller's memory after sfa_align_batch_device); a group context keeps the count
+struct EventMaps {
+    int32_t map_n = -1;
+    std::vector<int64_t> map_q_off;
+    const float *map_queries = nullptr;
+    DevBuf d_mv, d_prow, d_pairs, d_pfirst;  // packed moves of a slice, its row descriptors, its maps, where every walk ended
+    PinBuf h_pairs;
+    int reserve(size_t mv_bytes, size_t prow_bytes, size_t n_rows, size_t out_pairs) {
+        return reserve_all(d_mv, mv_bytes, d_prow, prow_bytes, d_pairs, 8 * out_pairs, d_pfirst, 4 * n_rows, h_pairs, 8 * out_pairs + 4 * n_rows);
+    }
+};
+
+struct TaskTimes {  // -DSFA_TASK_TIMES builds
+    DevBuf d_times;   // start / end / SIMD position of every wave-task of the last fill
+    int64_t n_times = 0;
+    DevBuf d_ltimes;  // ... and of the last pipelined pass 1 over row strips (tools/strip_task_times.py)
+    int64_t n_ltimes = 0;
+};
+
+}  // namespace ctx
+
 struct sfa_ctx {
     // A GROUP context (sfa_init_devices) owns one ordinary context per listed device and nothing else: every batch is cut
     // into contiguous read ranges, one per shard, which run concurrently; rows land in the caller's array in input order.
@@ -183,14 +326,16 @@ struct sfa_ctx {
     int device = 0;
     uint32_t flag = 0;
     int pore = 0;  // sfa_set_pore: 0 R9, 1 R10, 2 RNA004 (the adaptor segmenter of the RNA automatic query start)
-    hipStream_t stream = nullptr;
-    hipStream_t stream_long = nullptr;       // the row strips of long queries run beside the wave kernels of the same batch
-    hipStream_t stream_long2 = nullptr;      // ... their groups alternating between two streams (pass 2 of one under pass 1 of the next)
-    hipEvent_t lev[4] = {nullptr, nullptr, nullptr, nullptr};  // inputs of the batch ready on `stream` / strips done on `stream_long` / fork and join of `stream_long2`
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // fill start/end, finalize1 end, trace end, end, row strips start
-    hipEvent_t eev[4] = {nullptr, nullptr, nullptr, nullptr};  // sfa_align_raw: event detection start/end, normalisation start/end
-    bool eev_pending = false;
     int cu_count = 256;
+    // Streams and events of every stage sit here, in front of the buffers: members go in reverse order of declaration, so the
+    // buffers are freed while the streams exist, then the events, then stream_long2, stream_long, stream.
+    Stream stream;
+    Stream stream_long;   // the row strips of long queries run beside the wave kernels of the same batch
+    Stream stream_long2;  // ... their groups alternating between two streams (pass 2 of one under pass 1 of the next)
+    Event lev[4];  // inputs of the batch ready on `stream` / strips done on `stream_long` / fork and join of `stream_long2`
+    Event eev[4];  // sfa_align_raw: event detection start/end, normalisation start/end
+    Event ev[6];   // fill start/end, finalize1 end, trace end, end, row strips start
+    Event bev[2];  // sfa_align_blow5: record decoding start / end
 
     // tunables (sfa_set_option)
     int64_t opt_ckpt_interval = 0;           // force the checkpoint interval (power of two >= 4); 0 = auto
@@ -207,67 +352,28 @@ struct sfa_ctx {
     int64_t opt_lds_ckpt = 1;                // 1: rolling checkpoints in LDS where the batch's shapes allow (R <= 16, sDTW); 0: all snapshots to HBM
     int64_t opt_secondary = 0;               // secondary mappings per read, 0..4 (sfa_secondary_rows); > 0 takes the plain two-pass route
     int64_t opt_prio_unit = 2048;            // longest-remaining-first issue priority of the fill: columns per level, 0 = off
-    int32_t span_sixteenths = 0;             // pass 2's head start on the HBM-snapshot route follows the spans of the previous batch's alignments: sixteenths of the query length (0: not known yet -> a whole query length)
-    int64_t quad_limit_ms = 0, strip_limit_ms = 0;  // the limits the last batch's waits actually ran with (floors applied), for the error messages
     int64_t opt_spin_limit_ms = 20000;       // bound of every in-launch wait (fused pass 2, pipelined strips); beyond it the batch fails with SFA_EKERNEL
     // test hooks (sfa_set_option refuses them unless SFA_TEST_HOOKS=1 is in the environment)
     int64_t opt_debug_drop_quad = -1;        // the fill tasks of this quad never signal completion
     int64_t opt_debug_drop_strip = -1;       // strip 0 of this long read (job 0) never publishes its progress
-
-    // reference model (immutable after init)
-    int32_t num_ref = 0, n_jobs = 0;
-    int64_t total_cols = 0;  // sum over jobs of rlen
-    std::vector<int32_t> h_job_len;
-    std::vector<int64_t> h_job_off;   // [n_jobs] column 0 of every (contig,strand) array in d_ref
-    std::vector<int32_t> h_ref_off;   // [num_ref] ref_st_offset
-    DevBuf d_ref, d_job_off, d_job_len, d_job_contig, d_job_strand, d_ref_len, d_ref_off;
-
-    // per-batch scratch
-    DevBuf d_verify, d_segfail;
-    DevBuf d_lprog, d_lticket;  // pipelined strips: progress counters, ticket
-    DevBuf d_bndc, d_long, d_lbest, d_lsecond, d_lend, d_lwin, d_lck;  // row strips (queries beyond SFA_MAX_QUERY, sdtw_strips.hpp)
-    PinBuf h_long;
-    bool long_pending = false;
-    int64_t seg_reruns = 0;  // batches walked again because a segment hand-over did not verify
-    DevBuf d_queries, d_stage, d_pbest, d_pend, d_pjob, d_psecond, d_wjob, d_wend, d_wscore, d_tst, d_ck, d_out;
-    PinBuf h_stage, h_out, h_small, h_flags;
-    PinBuf h_queries;  // sfa_align_events: the gathered event means (page-locked: the upload from here is asynchronous)
-
-    // raw-signal path (sfa_align_raw)
-    DevBuf e_raw, e_rawoff, e_scale, e_sum, e_sumsq, e_t1, e_t2, e_evoff, e_evstart, e_evlen, e_evmean, e_evstdv, e_nev, e_qstart,
-        e_qoff, e_b0, e_b1, e_b2, e_flag, e_qev, e_pflag;
-
-    DevBuf b_in, b_inoff, b_out, b_outoff, b_len, b_head, b_bad;  // sfa_align_blow5: record bytes, inflated payloads, field rows
-    PinBuf h_head;
-    hipEvent_t bev[2] = {nullptr, nullptr};  // record decoding start / end
-    bool bev_pending = false;
-    int64_t blow5_fallbacks = 0;  // batches handed to the host reader because the device declined a record
-    DevBuf d_args;  // fused launch: the kernel's argument block in device memory (DpArgs::self)
-    DevBuf d_ticket, d_quaddone;  // fused launch: ticket counter, completed fill tasks per quad
-    DevBuf d_bestrec, d_beste, d_gbest, d_wchunk;  // LDS-checkpoint fill: records of the best windows, their step, per-read best score, winning chunk
-    DevBuf d_bad, d_badcount;  // sdtw_screen_kernel: per-read flag, number of flagged reads
-    PinBuf h_badcount;
-    DevBuf d_p5, d_swin, d_sts, d_sec;  // secondary mappings: top-5 partials, merged candidates, their traced columns, rows [n][4]
-    int32_t sec_n = -1;   // reads of the last call whose secondaries d_sec holds
-    // event maps (sfa_event_maps): what the last align call left behind -- its read count (-1: none), the offsets of its queries and
-    // where they are (the context's d_queries, or the caller's memory after sfa_align_batch_device); a group context keeps the count
-    int32_t map_n = -1;
-    std::vector<int64_t> map_q_off;
-    const float *map_queries = nullptr;
     int64_t opt_map_scratch = 2ll << 30;  // bytes of HBM the move matrices of one slice of rows may take
-    DevBuf d_mv, d_prow, d_pairs, d_pfirst;  // packed moves of a slice, its row descriptors, its maps, where every walk ended
-    PinBuf h_pairs;
-    DevBuf d_started;     // counter of the fill's tasks that have begun (IssuePriority)
-    DevBuf d_times;       // -DSFA_TASK_TIMES builds: start / end / SIMD position of every wave-task of the last fill
-    int64_t n_times = 0;
-    DevBuf d_ltimes;      // ... and of the last pipelined pass 1 over row strips (tools/strip_task_times.py)
-    int64_t n_ltimes = 0;
-    sfa::BatchPlan plan;  // plan of the batch being submitted (scratch included)
+
+    ctx::RefModel model;
+    ctx::CallerIO io;
+    ctx::Status status;
+    ctx::WaveKernels wave;
+    ctx::FusedLaunch fused;
+    ctx::LdsRoute lds;
+    ctx::Segments seg;
+    ctx::Strips strips;
+    ctx::Secondaries sec;
+    ctx::RawSignal raw;
+    ctx::Blow5 blow5;
+    ctx::EventMaps maps;
+    ctx::TaskTimes times;
     sfa_profile_t prof{};
     bool prof_pending = false;
-    bool no_segments_once = false;  // re-run of a batch whose segment hand-overs did not verify
-    bool in_slice = false;   // align_device is running one slice of a cut-up batch
-    int32_t pending_n = -1;  // reads of the batch submitted with sfa_submit_batch and not yet collected
+    bool in_slice = false;  // align_device is running one slice of a cut-up batch
 };
 
 // ---- internal functions that cross unit boundaries ----

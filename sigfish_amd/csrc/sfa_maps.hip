@@ -49,8 +49,8 @@ int event_maps_one(sfa_ctx *c, const sfa_result_t *rows, const int32_t *read_of_
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (int rc = sfa::resolve_profile(c)) return rc;
-    if (c->map_n < 0) return fail(SFA_EINVAL, "sfa_event_maps: no align call has completed on this context");
-    if (c->map_n > 0 && c->map_queries != c->d_queries.as<float>())
+    if (c->maps.map_n < 0) return fail(SFA_EINVAL, "sfa_event_maps: no align call has completed on this context");
+    if (c->maps.map_n > 0 && c->maps.map_queries != c->io.d_queries.as<float>())
         return fail(SFA_EINVAL, "sfa_event_maps: the last call was sfa_align_batch_device, whose queries are the caller's; the context kept none");
     const int strands = (c->flag & SFA_RNA) ? 1 : 2;
     const bool std_dtw = (c->flag & SFA_DTW) != 0;
@@ -62,16 +62,16 @@ int event_maps_one(sfa_ctx *c, const sfa_result_t *rows, const int32_t *read_of_
         const sfa_result_t &r = rows[k];
         if (!r.valid || r.rid < 0) continue;  // unaligned: nothing is written
         const int64_t read = static_cast<int64_t>(read_of_row ? read_of_row[k] : k) - read_base;
-        if (read < 0 || read >= c->map_n) return fail(SFA_EINVAL, "sfa_event_maps: row %d names read %lld, the last call had %d", k, (long long)(read + read_base), c->map_n);
-        if (r.rid >= c->num_ref || (r.strand != '+' && r.strand != '-') || (strands == 1 && r.strand != '+'))
+        if (read < 0 || read >= c->maps.map_n) return fail(SFA_EINVAL, "sfa_event_maps: row %d names read %lld, the last call had %d", k, (long long)(read + read_base), c->maps.map_n);
+        if (r.rid >= c->model.num_ref || (r.strand != '+' && r.strand != '-') || (strands == 1 && r.strand != '+'))
             return fail(SFA_EINVAL, "sfa_event_maps: row %d (contig %d, strand %d) is not a row of this reference", k, r.rid, (int)r.strand);
         RowBand &b = band[t];
         b.job = r.rid * strands + (r.strand == '+' ? 0 : 1);
-        const int32_t rlen = c->h_job_len[b.job], off = c->h_ref_off[r.rid];
+        const int32_t rlen = c->model.h_job_len[b.job], off = c->model.h_ref_off[r.rid];
         const bool plus = r.strand == '+';
         const int64_t st = plus ? static_cast<int64_t>(r.pos_st) - off : static_cast<int64_t>(rlen) - (static_cast<int64_t>(r.pos_end) - off);
         const int64_t en = plus ? static_cast<int64_t>(r.pos_end) - off : static_cast<int64_t>(rlen) - (static_cast<int64_t>(r.pos_st) - off);
-        const int64_t ql = c->map_q_off[read + 1] - c->map_q_off[read];
+        const int64_t ql = c->maps.map_q_off[read + 1] - c->maps.map_q_off[read];
         if (st < 0 || en < st || en >= rlen || ql <= 0)
             return fail(SFA_EINVAL, "sfa_event_maps: row %d (columns %d..%d of contig %d, read %lld of %lld events) is not a row of the last call", k,
                         r.pos_st, r.pos_end, r.rid, (long long)(read + read_base), (long long)ql);
@@ -119,27 +119,24 @@ int event_maps_one(sfa_ctx *c, const sfa_result_t *rows, const int32_t *read_of_
         cls_begin[6] = static_cast<int32_t>(prow.size());
         const int32_t n = cls_begin[6];
         int rc;
-        const size_t qoff_bytes = sizeof(int64_t) * (static_cast<size_t>(c->map_n) + 1);
-        if ((rc = c->d_mv.reserve(static_cast<size_t>(mv_bytes))) || (rc = c->d_prow.reserve(sizeof(PathRow) * n + qoff_bytes + 8)) ||
-            (rc = c->d_pairs.reserve(8 * static_cast<size_t>(out_pairs))) || (rc = c->d_pfirst.reserve(4 * static_cast<size_t>(n))) ||
-            (rc = c->h_pairs.reserve(8 * static_cast<size_t>(out_pairs) + 4 * static_cast<size_t>(n))))
-            return rc;
+        const size_t qoff_bytes = sizeof(int64_t) * (static_cast<size_t>(c->maps.map_n) + 1);
+        if ((rc = c->maps.reserve(static_cast<size_t>(mv_bytes), sizeof(PathRow) * n + qoff_bytes + 8, static_cast<size_t>(n), static_cast<size_t>(out_pairs)))) return rc;
         static_assert(sizeof(PathRow) % 8 == 0, "the query offsets follow the rows in one buffer");
-        int64_t *d_qoff = reinterpret_cast<int64_t *>(c->d_prow.as<char>() + sizeof(PathRow) * n);
-        HIP_TRY(hipMemcpyAsync(c->d_prow.p, prow.data(), sizeof(PathRow) * n, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_qoff, c->map_q_off.data(), qoff_bytes, hipMemcpyHostToDevice, st));
+        int64_t *d_qoff = reinterpret_cast<int64_t *>(c->maps.d_prow.as<char>() + sizeof(PathRow) * n);
+        HIP_TRY(hipMemcpyAsync(c->maps.d_prow.p, prow.data(), sizeof(PathRow) * n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_qoff, c->maps.map_q_off.data(), qoff_bytes, hipMemcpyHostToDevice, st));
         for (int ci = 0; ci < 6; ++ci) {
             const int32_t nc = cls_begin[ci + 1] - cls_begin[ci];
             if (nc == 0) continue;
             PathArgs pa{};
-            pa.queries = c->map_queries;
+            pa.queries = c->maps.map_queries;
             pa.q_off = d_qoff;
-            pa.ref = c->d_ref.as<float>();
-            pa.job_off = c->d_job_off.as<int64_t>();
-            pa.rows = c->d_prow.as<PathRow>() + cls_begin[ci];
-            pa.moves = c->d_mv.as<uint32_t>();
-            pa.pairs = c->d_pairs.as<int32_t>();
-            pa.first_col = c->d_pfirst.as<int32_t>() + cls_begin[ci];
+            pa.ref = c->model.d_ref.as<float>();
+            pa.job_off = c->model.d_job_off.as<int64_t>();
+            pa.rows = c->maps.d_prow.as<PathRow>() + cls_begin[ci];
+            pa.moves = c->maps.d_mv.as<uint32_t>();
+            pa.pairs = c->maps.d_pairs.as<int32_t>();
+            pa.first_col = c->maps.d_pfirst.as<int32_t>() + cls_begin[ci];
             pa.n_rows = nc;
             pa.rev_query = reversed ? 1 : 0;
             if (std_dtw)
@@ -152,10 +149,10 @@ int event_maps_one(sfa_ctx *c, const sfa_result_t *rows, const int32_t *read_of_
             hipLaunchKernelGGL(sfa::sdtw_path_walk_kernel, dim3((nc + 255) / 256), dim3(256), 0, st, pa, rshift, sh.lanes);
             KERNEL_TRY();
         }
-        int32_t *h_pairs = c->h_pairs.as<int32_t>();
+        int32_t *h_pairs = c->maps.h_pairs.as<int32_t>();
         int32_t *h_first = h_pairs + 2 * out_pairs;
-        HIP_TRY(hipMemcpyAsync(h_pairs, c->d_pairs.p, 8 * static_cast<size_t>(out_pairs), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_first, c->d_pfirst.p, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_pairs, c->maps.d_pairs.p, 8 * static_cast<size_t>(out_pairs), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_first, c->maps.d_pfirst.p, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         for (int32_t i = 0; i < n; ++i) {
             // a walk that met query row 0 behind the row's first column has no complete map; like sfa_r2qevent_map, nothing is written
@@ -170,16 +167,16 @@ int event_maps_one(sfa_ctx *c, const sfa_result_t *rows, const int32_t *read_of_
     for (const int32_t t : ms.host_rows) {
         const RowBand &b = band[t];
         const int32_t k = idx ? idx[t] : t;
-        const int64_t ql = c->map_q_off[b.read + 1] - c->map_q_off[b.read];
+        const int64_t ql = c->maps.map_q_off[b.read + 1] - c->maps.map_q_off[b.read];
         q.resize(static_cast<size_t>(ql));
         qdp.resize(static_cast<size_t>(ql));
-        HIP_TRY(hipMemcpy(q.data(), c->map_queries + c->map_q_off[b.read], sizeof(float) * static_cast<size_t>(ql), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(q.data(), c->maps.map_queries + c->maps.map_q_off[b.read], sizeof(float) * static_cast<size_t>(ql), hipMemcpyDeviceToHost));
         for (int64_t j = 0; j < ql; ++j) qdp[reversed ? ql - 1 - j : j] = q[j];
         std::vector<float> &y = ref_of_job[b.job];
-        const int32_t rlen = c->h_job_len[b.job];
+        const int32_t rlen = c->model.h_job_len[b.job];
         if (y.empty()) {
             y.resize(static_cast<size_t>(rlen));
-            HIP_TRY(hipMemcpy(y.data(), c->d_ref.as<float>() + c->h_job_off[b.job], sizeof(float) * static_cast<size_t>(rlen), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(y.data(), c->model.d_ref.as<float>() + c->model.h_job_off[b.job], sizeof(float) * static_cast<size_t>(rlen), hipMemcpyDeviceToHost));
         }
         const sfa::WarpPath path = sfa::band_traceback(qdp.data(), static_cast<int32_t>(ql), y.data(), rlen, b.col_st, b.col_st + b.m - 1, std_dtw);
         if (path.px.empty()) continue;
@@ -200,11 +197,11 @@ extern "C" int sfa_event_maps(sfa_ctx_t *c, const sfa_result_t *rows, const int3
     for (int32_t k = 0; k < n_rows; ++k)
         if (map_off[k + 1] < map_off[k] || map_off[k] < 0) return fail(SFA_EINVAL, "sfa_event_maps: map_off not monotone at row %d", k);
     if (c->shards.empty()) {
-        if (!read_of_row && c->map_n >= 0 && n_rows != c->map_n)
-            return fail(SFA_EINVAL, "sfa_event_maps: the last call aligned %d reads, %d rows given without read_of_row", c->map_n, n_rows);
+        if (!read_of_row && c->maps.map_n >= 0 && n_rows != c->maps.map_n)
+            return fail(SFA_EINVAL, "sfa_event_maps: the last call aligned %d reads, %d rows given without read_of_row", c->maps.map_n, n_rows);
         return event_maps_one(c, rows, read_of_row, nullptr, n_rows, 0, map_off, pairs, n_on_host);
     }
-    const int32_t n_reads = c->map_n;
+    const int32_t n_reads = c->maps.map_n;
     if (n_reads < 0) return fail(SFA_EINVAL, "sfa_event_maps: no align call has completed on this context");
     if (!read_of_row && n_rows != n_reads)
         return fail(SFA_EINVAL, "sfa_event_maps: the last call aligned %d reads, %d rows given without read_of_row", n_reads, n_rows);

@@ -2,7 +2,6 @@
 // query window, normalisation: sfa_align_raw) and BLOW5 records in (inflate, field parsing, StreamVByte: sfa_align_blow5), each
 // ending in the alignment stage of sfa_align.hip.
 #include "sfa_ctx.hpp"
-#include "sdtw_kernels.hpp"
 #include "events_kernels.hpp"
 #define SFA_DEFINE_BLOW5_KERNELS
 #include "blow5_kernels.hpp"
@@ -29,7 +28,7 @@ int sfa_align_raw_ex(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_off, c
     return align_raw_impl(c, raw, raw_off, scaling, n, prefix_size, query_size, rows, info, query_events);
 }
 
-// raw == nullptr: the samples are already in c->e_raw (decoded on the device, sfa_align_blow5), laid out by raw_off
+// raw == nullptr: the samples are already in c->raw.e_raw (decoded on the device, sfa_align_blow5), laid out by raw_off
 static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_off, const double *scaling, int32_t n, int32_t prefix_size,
                           int32_t query_size, sfa_result_t *rows, sfa_query_info_t *info, sfa_event_t *query_events) {
     // the reference's own checks of -p -1 (src/dtw_main.c:263-276)
@@ -38,7 +37,7 @@ static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_o
     if (query_size <= 0) return fail(SFA_EINVAL, "sfa_align_raw: query_size must be positive");
     if (n == 0) return SFA_OK;
     if (!c->shards.empty()) {
-        c->map_n = -1;
+        c->maps.map_n = -1;
         const int grc = for_each_shard_range(c, n, [&](size_t r, int32_t a, int32_t b) {
             std::vector<int64_t> off(b - a + 1);  // the shard's sample offsets start at 0
             for (int32_t i = a; i <= b; ++i) off[i - a] = raw_off[i] - raw_off[a];
@@ -47,7 +46,7 @@ static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_o
                                     query_size, rows + a, info + a,
                                     query_events ? query_events + static_cast<size_t>(a) * static_cast<size_t>(query_size) : nullptr);
         });
-        if (!grc) c->map_n = n;  // (sfa_event_maps splits its rows by the same ranges)
+        if (!grc) c->maps.map_n = n;  // (sfa_event_maps splits its rows by the same ranges)
         return grc;
     }
     HIP_TRY(hipSetDevice(c->device));
@@ -71,35 +70,27 @@ static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_o
     }
     const int64_t ev_total = ev_off[n];
     int rc;
-    if ((rc = c->e_raw.reserve(2 * (size_t)std::max<int64_t>(total, 1))) || (rc = c->e_rawoff.reserve(8 * (size_t)(n + 1))) ||
-        (rc = c->e_scale.reserve(8 * (size_t)n)) || (rc = c->e_sum.reserve(8 * (size_t)(total + n))) ||
-        (rc = c->e_sumsq.reserve(8 * (size_t)(total + n))) || (rc = c->e_t1.reserve(4 * (size_t)std::max<int64_t>(total, 1))) ||
-        (rc = c->e_t2.reserve(4 * (size_t)std::max<int64_t>(total, 1))) || (rc = c->e_evoff.reserve(8 * (size_t)(n + 1))) ||
-        (rc = c->e_evstart.reserve(4 * (size_t)ev_total)) || (rc = c->e_evlen.reserve(4 * (size_t)ev_total)) ||
-        (rc = c->e_evmean.reserve(4 * (size_t)ev_total)) || (rc = c->e_evstdv.reserve(4 * (size_t)ev_total)) ||
-        (rc = c->e_nev.reserve(8 * (size_t)n)) || (rc = c->e_qstart.reserve(8 * (size_t)n)) || (rc = c->e_qoff.reserve(8 * (size_t)(n + 1))) ||
-        (rc = c->e_flag.reserve(4 * (size_t)n)) || (rc = c->e_pflag.reserve(4 * (size_t)n)) || (rc = c->e_b0.reserve(4 * (size_t)n)) || (rc = c->e_b1.reserve(4 * (size_t)n)) || (rc = c->e_b2.reserve(4 * (size_t)n)))
-        return rc;
+    if ((rc = c->raw.reserve(total, static_cast<size_t>(n), static_cast<size_t>(ev_total)))) return rc;
     hipStream_t sp = st;
-    if (raw) HIP_TRY(hipMemcpyAsync(c->e_raw.p, raw, 2 * (size_t)total, hipMemcpyHostToDevice, sp));
-    HIP_TRY(hipMemcpyAsync(c->e_rawoff.p, raw_off, 8 * (size_t)(n + 1), hipMemcpyHostToDevice, sp));
-    HIP_TRY(hipMemcpyAsync(c->e_scale.p, scale.data(), 8 * (size_t)n, hipMemcpyHostToDevice, sp));
-    HIP_TRY(hipMemcpyAsync(c->e_evoff.p, ev_off.data(), 8 * (size_t)(n + 1), hipMemcpyHostToDevice, sp));
+    if (raw) HIP_TRY(hipMemcpyAsync(c->raw.e_raw.p, raw, 2 * (size_t)total, hipMemcpyHostToDevice, sp));
+    HIP_TRY(hipMemcpyAsync(c->raw.e_rawoff.p, raw_off, 8 * (size_t)(n + 1), hipMemcpyHostToDevice, sp));
+    HIP_TRY(hipMemcpyAsync(c->raw.e_scale.p, scale.data(), 8 * (size_t)n, hipMemcpyHostToDevice, sp));
+    HIP_TRY(hipMemcpyAsync(c->raw.e_evoff.p, ev_off.data(), 8 * (size_t)(n + 1), hipMemcpyHostToDevice, sp));
 
     sfa::EvArgs ea{};
-    ea.raw = c->e_raw.as<int16_t>();
-    ea.raw_off = c->e_rawoff.as<int64_t>();
-    ea.scale = c->e_scale.as<float>();
-    ea.sum = c->e_sum.as<double>();
-    ea.sumsq = c->e_sumsq.as<double>();
-    ea.t1 = c->e_t1.as<float>();
-    ea.t2 = c->e_t2.as<float>();
-    ea.ev_off = c->e_evoff.as<int64_t>();
-    ea.ev_start = c->e_evstart.as<int32_t>();
-    ea.ev_length = c->e_evlen.as<float>();
-    ea.ev_mean = c->e_evmean.as<float>();
-    ea.ev_stdv = c->e_evstdv.as<float>();
-    ea.n_events = c->e_nev.as<int32_t>();
+    ea.raw = c->raw.e_raw.as<int16_t>();
+    ea.raw_off = c->raw.e_rawoff.as<int64_t>();
+    ea.scale = c->raw.e_scale.as<float>();
+    ea.sum = c->raw.e_sum.as<double>();
+    ea.sumsq = c->raw.e_sumsq.as<double>();
+    ea.t1 = c->raw.e_t1.as<float>();
+    ea.t2 = c->raw.e_t2.as<float>();
+    ea.ev_off = c->raw.e_evoff.as<int64_t>();
+    ea.ev_start = c->raw.e_evstart.as<int32_t>();
+    ea.ev_length = c->raw.e_evlen.as<float>();
+    ea.ev_mean = c->raw.e_evmean.as<float>();
+    ea.ev_stdv = c->raw.e_evstdv.as<float>();
+    ea.n_events = c->raw.e_nev.as<int32_t>();
     ea.n_reads = n;
     // detector parameters, src/events.c:47-58
     ea.w1 = rna ? 7 : 3;
@@ -108,9 +99,9 @@ static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_o
     ea.thr2 = 9.0f;
     ea.peak_height = rna ? 1.0f : 0.2f;
     const dim3 lane_grid((n + 63) / 64), lane_block(64);
-    ea.seq_flag = c->e_flag.as<int32_t>();
+    ea.seq_flag = c->raw.e_flag.as<int32_t>();
     ea.use_flags = (c->opt_ev_parallel & 1) ? 1 : 0;
-    ea.peak_flag = c->e_pflag.as<int32_t>();
+    ea.peak_flag = c->raw.e_pflag.as<int32_t>();
     // measured: 76 us against 1.5 ms for a 512-read batch, 2.1 ms against 1.3 ms for 16 Ki reads (it does ~1.3x the work of
     // the sequential walk, in 64x more waves): used while the batch cannot fill the chip with one read per lane pair
     ea.use_peak_flags = ((c->opt_ev_parallel & 2) && n <= 8192) ? 1 : 0;
@@ -125,15 +116,15 @@ static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_o
     const bool auto_start = prefix_size < 0;
     if (auto_start) {
         sfa::AutoArgs aa{};
-        aa.raw = c->e_raw.as<int16_t>();
-        aa.raw_off = c->e_rawoff.as<int64_t>();
-        aa.scale = c->e_scale.as<float>();
-        aa.csum = c->e_sumsq.as<int64_t>();  // (sums and t-statistics are no longer needed: ev_stats_kernel ran before)
-        aa.tmean = c->e_t1.as<float>();
-        aa.ev_off = c->e_evoff.as<int64_t>();
-        aa.ev_start = c->e_evstart.as<int32_t>();
-        aa.n_events = c->e_nev.as<int32_t>();
-        aa.start = c->e_nev.as<int32_t>() + n;
+        aa.raw = c->raw.e_raw.as<int16_t>();
+        aa.raw_off = c->raw.e_rawoff.as<int64_t>();
+        aa.scale = c->raw.e_scale.as<float>();
+        aa.csum = c->raw.e_sumsq.as<int64_t>();  // (sums and t-statistics are no longer needed: ev_stats_kernel ran before)
+        aa.tmean = c->raw.e_t1.as<float>();
+        aa.ev_off = c->raw.e_evoff.as<int64_t>();
+        aa.ev_start = c->raw.e_evstart.as<int32_t>();
+        aa.n_events = c->raw.e_nev.as<int32_t>();
+        aa.start = c->raw.e_nev.as<int32_t>() + n;
         aa.n_reads = n;
         aa.lo = c->pore == 2 ? 500 : 2000;  // JNNV2_RNA_RNA004_ADAPTOR / JNNV2_RNA_R9_ADAPTOR, src/jnn.h
         aa.std_scale = c->pore == 2 ? 0.7f : 0.5f;
@@ -143,10 +134,10 @@ static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_o
     KERNEL_TRY();
     HIP_TRY(hipEventRecord(c->eev[1], sp));
     // page-locked: event counts and automatic starts, then the three raw-coordinate columns
-    if ((rc = c->h_small.reserve(16 * (size_t)n))) return rc;
-    int32_t *nev = c->h_small.as<int32_t>();
+    if ((rc = c->io.h_small.reserve(16 * (size_t)n))) return rc;
+    int32_t *nev = c->io.h_small.as<int32_t>();
     const int32_t *auto_st = nev + n;
-    HIP_TRY(hipMemcpyAsync(nev, c->e_nev.p, (auto_start ? 8 : 4) * (size_t)n, hipMemcpyDeviceToHost, sp));
+    HIP_TRY(hipMemcpyAsync(nev, c->raw.e_nev.p, (auto_start ? 8 : 4) * (size_t)n, hipMemcpyDeviceToHost, sp));
     HIP_TRY(hipStreamSynchronize(sp));
 
     // query windows on the host (normalise_single, src/sigfish.c:433-480); the arithmetic part runs on the device
@@ -197,40 +188,38 @@ static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_o
         info[i].pad = 0;
     }
     const int64_t nq = q_off[n];
-    if ((rc = c->d_queries.reserve(4 * (size_t)std::max<int64_t>(nq, 1))) || (rc = c->d_out.reserve(sizeof(sfa_result_t) * (size_t)n)) ||
-        (rc = c->h_out.reserve(sizeof(sfa_result_t) * (size_t)n)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(c->e_qstart.p, qstart.data(), 8 * (size_t)n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(c->e_qoff.p, q_off.data(), 8 * (size_t)(n + 1), hipMemcpyHostToDevice, st));
+    if ((rc = c->io.reserve(nq, static_cast<size_t>(n)))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->raw.e_qstart.p, qstart.data(), 8 * (size_t)n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->raw.e_qoff.p, q_off.data(), 8 * (size_t)(n + 1), hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(c->eev[2], st));
-    sfa::QueryArgs qa{c->e_evmean.as<float>(), c->e_evoff.as<int64_t>(), c->e_qstart.as<int64_t>(), c->e_qoff.as<int64_t>(),
-                      c->d_queries.as<float>(), n};
+    sfa::QueryArgs qa{c->raw.e_evmean.as<float>(), c->raw.e_evoff.as<int64_t>(), c->raw.e_qstart.as<int64_t>(), c->raw.e_qoff.as<int64_t>(),
+                      c->io.d_queries.as<float>(), n};
     hipLaunchKernelGGL(sfa::ev_query_kernel, dim3(n), dim3(64), 0, st, qa);  // one wave per read
-    sfa::BoundsArgs ba{c->e_evstart.as<int32_t>(), c->e_evlen.as<float>(), c->e_evoff.as<int64_t>(), c->e_qstart.as<int64_t>(),
-                       c->e_qoff.as<int64_t>(), c->e_b0.as<int32_t>(), c->e_b1.as<int32_t>(), c->e_b2.as<float>(), n};
+    sfa::BoundsArgs ba{c->raw.e_evstart.as<int32_t>(), c->raw.e_evlen.as<float>(), c->raw.e_evoff.as<int64_t>(), c->raw.e_qstart.as<int64_t>(),
+                       c->raw.e_qoff.as<int64_t>(), c->raw.e_b0.as<int32_t>(), c->raw.e_b1.as<int32_t>(), c->raw.e_b2.as<float>(), n};
     hipLaunchKernelGGL(sfa::ev_bounds_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ba);
     if (query_events) {  // the query windows' event tables, for SAM output on the host
         static_assert(sizeof(sfa_event_t) == 24, "event record layout");
         const size_t qe_bytes = sizeof(sfa_event_t) * static_cast<size_t>(n) * static_cast<size_t>(query_size);
-        if ((rc = c->e_qev.reserve(qe_bytes))) return rc;
-        sfa::PackArgs pa{c->e_evstart.as<int32_t>(), c->e_evlen.as<float>(), c->e_evstdv.as<float>(), c->e_evoff.as<int64_t>(),
-                         c->e_qstart.as<int64_t>(), c->e_qoff.as<int64_t>(), c->d_queries.as<float>(), c->e_qev.as<uint64_t>(), query_size};
+        if ((rc = c->raw.e_qev.reserve(qe_bytes))) return rc;
+        sfa::PackArgs pa{c->raw.e_evstart.as<int32_t>(), c->raw.e_evlen.as<float>(), c->raw.e_evstdv.as<float>(), c->raw.e_evoff.as<int64_t>(),
+                         c->raw.e_qstart.as<int64_t>(), c->raw.e_qoff.as<int64_t>(), c->io.d_queries.as<float>(), c->raw.e_qev.as<uint64_t>(), query_size};
         hipLaunchKernelGGL(sfa::ev_pack_events_kernel, dim3(n), dim3(128), 0, st, pa);
-        HIP_TRY(hipMemcpyAsync(query_events, c->e_qev.p, qe_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(query_events, c->raw.e_qev.p, qe_bytes, hipMemcpyDeviceToHost, st));
     }
     KERNEL_TRY();
     HIP_TRY(hipEventRecord(c->eev[3], st));
-    c->eev_pending = true;
+    c->raw.eev_pending = true;
     // the queries must be complete before align_device's uploads reuse the pinned staging area; same stream, in order
-    if ((rc = align_device(c, c->d_queries.as<float>(), q_off.data(), n, c->d_out.as<ResultRow>()))) return rc;
-    int32_t *b0 = c->h_small.as<int32_t>(), *b1 = b0 + n;
+    if ((rc = align_device(c, c->io.d_queries.as<float>(), q_off.data(), n, c->io.d_out.as<ResultRow>()))) return rc;
+    int32_t *b0 = c->io.h_small.as<int32_t>(), *b1 = b0 + n;
     float *b2 = reinterpret_cast<float *>(b1 + n);
-    HIP_TRY(hipMemcpyAsync(c->h_out.p, c->d_out.p, sizeof(sfa_result_t) * (size_t)n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(b0, c->e_b0.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(b1, c->e_b1.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(b2, c->e_b2.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c->io.h_out.p, c->io.d_out.p, sizeof(sfa_result_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(b0, c->raw.e_b0.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(b1, c->raw.e_b1.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(b2, c->raw.e_b2.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    memcpy(rows, c->h_out.p, sizeof(sfa_result_t) * (size_t)n);
+    memcpy(rows, c->io.h_out.p, sizeof(sfa_result_t) * (size_t)n);
     for (int32_t i = 0; i < n; ++i) {
         info[i].start_raw_idx = static_cast<uint64_t>(b0[i]);
         info[i].end_raw_idx = static_cast<uint64_t>(static_cast<float>(static_cast<uint64_t>(b1[i])) + b2[i]);  // u64 + float, as in C
@@ -257,7 +246,7 @@ int sfa_align_blow5(sfa_ctx_t *c, const uint8_t *records, const int64_t *rec_off
     if (query_size <= 0) return fail(SFA_EINVAL, "sfa_align_blow5: query_size must be positive");
     if (n == 0) return SFA_OK;
     if (!c->shards.empty()) {
-        c->map_n = -1;
+        c->maps.map_n = -1;
         const int grc = for_each_shard_range(c, n, [&](size_t r, int32_t a, int32_t b) {
             std::vector<int64_t> off(b - a + 1);
             for (int32_t i = a; i <= b; ++i) off[i - a] = rec_off[i] - rec_off[a];
@@ -265,7 +254,7 @@ int sfa_align_blow5(sfa_ctx_t *c, const uint8_t *records, const int64_t *rec_off
                                    rows + a, info + a, heads + a,
                                    query_events ? query_events + static_cast<size_t>(a) * static_cast<size_t>(query_size) : nullptr);
         });
-        if (!grc) c->map_n = n;
+        if (!grc) c->maps.map_n = n;
         return grc;
     }
     if (rec_off[0] != 0) return fail(SFA_EINVAL, "sfa_align_blow5: rec_off must start at 0");
@@ -281,38 +270,34 @@ int sfa_align_blow5(sfa_ctx_t *c, const uint8_t *records, const int64_t *rec_off
     std::vector<int64_t> slot(n + 1);
     slot[0] = 0;
     for (int32_t i = 0; i < n; ++i) slot[i + 1] = slot[i] + (record_zlib ? (((rec_off[i + 1] - rec_off[i]) * 4 + 4096 + 15) & ~int64_t(15)) : 0);
-    if ((rc = c->b_in.reserve(static_cast<size_t>(in_bytes) + 128)) || (rc = c->b_inoff.reserve(8 * static_cast<size_t>(n + 1))) ||
-        (rc = c->b_head.reserve(static_cast<size_t>(n) * sfa::kBlow5HeadBytes)) || (rc = c->h_head.reserve(static_cast<size_t>(n) * sfa::kBlow5HeadBytes + 8 * static_cast<size_t>(n))) ||
-        (rc = c->b_len.reserve(4 * static_cast<size_t>(n))) || (rc = c->b_bad.reserve(4 * static_cast<size_t>(n))))
-        return rc;
-    if (record_zlib && ((rc = c->b_out.reserve(static_cast<size_t>(slot[n]) + 64)) || (rc = c->b_outoff.reserve(8 * static_cast<size_t>(n + 1))))) return rc;
+    if ((rc = c->blow5.reserve(static_cast<size_t>(in_bytes), record_zlib ? slot[n] : -1, static_cast<size_t>(n), sfa::kBlow5HeadBytes))) return rc;
     hipStream_t sp = st;
-    HIP_TRY(hipMemcpyAsync(c->b_in.p, records, static_cast<size_t>(in_bytes), hipMemcpyHostToDevice, sp));
-    HIP_TRY(hipMemcpyAsync(c->b_inoff.p, rec_off, 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, sp));
-    HIP_TRY(hipMemsetAsync(c->b_bad.p, 0, 4 * static_cast<size_t>(n), sp));
+    HIP_TRY(hipMemcpyAsync(c->blow5.b_in.p, records, static_cast<size_t>(in_bytes), hipMemcpyHostToDevice, sp));
+    HIP_TRY(hipMemcpyAsync(c->blow5.b_inoff.p, rec_off, 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, sp));
+    HIP_TRY(hipMemsetAsync(c->blow5.b_bad.p, 0, 4 * static_cast<size_t>(n), sp));
     HIP_TRY(hipEventRecord(c->bev[0], sp));
     sfa::FieldsArgs fa{};
     if (record_zlib) {
-        HIP_TRY(hipMemcpyAsync(c->b_outoff.p, slot.data(), 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, sp));
-        sfa::InflateArgs ia{c->b_in.as<uint8_t>(), c->b_inoff.as<int64_t>(), c->b_out.as<uint8_t>(), c->b_outoff.as<int64_t>(), c->b_len.as<int32_t>(), n};
+        HIP_TRY(hipMemcpyAsync(c->blow5.b_outoff.p, slot.data(), 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, sp));
+        sfa::InflateArgs ia{c->blow5.b_in.as<uint8_t>(), c->blow5.b_inoff.as<int64_t>(), c->blow5.b_out.as<uint8_t>(), c->blow5.b_outoff.as<int64_t>(), c->blow5.b_len.as<int32_t>(), n};
         const int lanes = inflate_lanes(n, c->cu_count);
         hipLaunchKernelGGL(sfa::blow5_inflate_kernel, dim3((n + lanes - 1) / lanes), dim3(64), sizeof(sfa::InflateLds) * lanes, sp, ia, lanes);
         KERNEL_TRY();
-        fa.payload = c->b_out.as<uint8_t>();
-        fa.payload_off = c->b_outoff.as<int64_t>();
-        fa.payload_len = c->b_len.as<int32_t>();
+        fa.payload = c->blow5.b_out.as<uint8_t>();
+        fa.payload_off = c->blow5.b_outoff.as<int64_t>();
+        fa.payload_len = c->blow5.b_len.as<int32_t>();
     } else {
-        fa.payload = c->b_in.as<uint8_t>();
-        fa.payload_off = c->b_inoff.as<int64_t>();
+        fa.payload = c->blow5.b_in.as<uint8_t>();
+        fa.payload_off = c->blow5.b_inoff.as<int64_t>();
         fa.payload_len = nullptr;
     }
-    fa.head = c->b_head.as<uint8_t>();
+    fa.head = c->blow5.b_head.as<uint8_t>();
     fa.signal_svb = signal_svb ? 1 : 0;
     fa.n = n;
     hipLaunchKernelGGL(sfa::blow5_fields_kernel, dim3((n + 63) / 64), dim3(64), 0, sp, fa);
     KERNEL_TRY();
-    uint8_t *hh = c->h_head.as<uint8_t>();
-    HIP_TRY(hipMemcpyAsync(hh, c->b_head.p, static_cast<size_t>(n) * sfa::kBlow5HeadBytes, hipMemcpyDeviceToHost, sp));
+    uint8_t *hh = c->blow5.h_head.as<uint8_t>();
+    HIP_TRY(hipMemcpyAsync(hh, c->blow5.b_head.p, static_cast<size_t>(n) * sfa::kBlow5HeadBytes, hipMemcpyDeviceToHost, sp));
     HIP_TRY(hipStreamSynchronize(sp));
     // the fields of every record; anything the device declined sends the whole batch to the host reader
     std::vector<int64_t> raw_off(n + 1);
@@ -347,14 +332,14 @@ int sfa_align_blow5(sfa_ctx_t *c, const uint8_t *records, const int64_t *rec_off
     }
     if (!fallback) {
         const int64_t total = raw_off[n];
-        if ((rc = c->e_raw.reserve(2 * static_cast<size_t>(std::max<int64_t>(total, 1)))) || (rc = c->e_rawoff.reserve(8 * static_cast<size_t>(n + 1)))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->e_rawoff.p, raw_off.data(), 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, sp));
-        sfa::SvbArgs sa{fa.payload, fa.payload_off, c->b_head.as<uint8_t>(), c->e_rawoff.as<int64_t>(), c->e_raw.as<int16_t>(), c->b_bad.as<int32_t>(),
+        if ((rc = c->raw.reserve_samples(total, static_cast<size_t>(n)))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->raw.e_rawoff.p, raw_off.data(), 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, sp));
+        sfa::SvbArgs sa{fa.payload, fa.payload_off, c->blow5.b_head.as<uint8_t>(), c->raw.e_rawoff.as<int64_t>(), c->raw.e_raw.as<int16_t>(), c->blow5.b_bad.as<int32_t>(),
                         signal_svb ? 1 : 0, n};
         hipLaunchKernelGGL(sfa::blow5_svb_kernel, dim3((n + 3) / 4), dim3(256), 0, sp, sa);
         KERNEL_TRY();
         int32_t *bad = reinterpret_cast<int32_t *>(hh + static_cast<size_t>(n) * sfa::kBlow5HeadBytes);
-        HIP_TRY(hipMemcpyAsync(bad, c->b_bad.p, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, sp));
+        HIP_TRY(hipMemcpyAsync(bad, c->blow5.b_bad.p, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, sp));
         HIP_TRY(hipEventRecord(c->bev[1], sp));
         HIP_TRY(hipStreamSynchronize(sp));
         for (int32_t i = 0; i < n && !fallback; ++i)
@@ -363,12 +348,12 @@ int sfa_align_blow5(sfa_ctx_t *c, const uint8_t *records, const int64_t *rec_off
                 fallback = true;
             }
         if (!fallback) {
-            c->bev_pending = true;
+            c->blow5.bev_pending = true;
             return align_raw_impl(c, nullptr, raw_off.data(), scaling.data(), n, prefix_size, query_size, rows, info, query_events);
         }
     }
     // host reader for the whole batch (own inflate / zlib, SSSE3 StreamVByte): malformed records are reported from there
-    c->blow5_fallbacks++;
+    c->blow5.blow5_fallbacks++;
     std::vector<int16_t> raw;
     raw_off[0] = 0;
     for (int32_t i = 0; i < n; ++i) {
@@ -403,19 +388,16 @@ int sfa_inflate_zlib_device(sfa_ctx_t *c, const uint8_t *in, const int64_t *in_o
     HIP_TRY(hipStreamSynchronize(c->stream));
     hipStream_t st = c->stream;
     int rc;
-    if ((rc = c->b_in.reserve(static_cast<size_t>(in_off[n]) + 128)) || (rc = c->b_inoff.reserve(8 * static_cast<size_t>(n + 1))) ||
-        (rc = c->b_out.reserve(static_cast<size_t>(out_off[n]) + 64)) || (rc = c->b_outoff.reserve(8 * static_cast<size_t>(n + 1))) ||
-        (rc = c->b_len.reserve(4 * static_cast<size_t>(n))))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(c->b_in.p, in, static_cast<size_t>(in_off[n]), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(c->b_inoff.p, in_off, 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(c->b_outoff.p, out_off, 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, st));
-    sfa::InflateArgs ia{c->b_in.as<uint8_t>(), c->b_inoff.as<int64_t>(), c->b_out.as<uint8_t>(), c->b_outoff.as<int64_t>(), c->b_len.as<int32_t>(), n};
+    if ((rc = c->blow5.reserve_inflate(static_cast<size_t>(in_off[n]), out_off[n], static_cast<size_t>(n)))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->blow5.b_in.p, in, static_cast<size_t>(in_off[n]), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->blow5.b_inoff.p, in_off, 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->blow5.b_outoff.p, out_off, 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, st));
+    sfa::InflateArgs ia{c->blow5.b_in.as<uint8_t>(), c->blow5.b_inoff.as<int64_t>(), c->blow5.b_out.as<uint8_t>(), c->blow5.b_outoff.as<int64_t>(), c->blow5.b_len.as<int32_t>(), n};
     const int lanes = inflate_lanes(n, c->cu_count);
     hipLaunchKernelGGL(sfa::blow5_inflate_kernel, dim3((n + lanes - 1) / lanes), dim3(64), sizeof(sfa::InflateLds) * lanes, st, ia, lanes);
     KERNEL_TRY();
-    HIP_TRY(hipMemcpyAsync(out, c->b_out.p, static_cast<size_t>(out_off[n]), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out_len, c->b_len.p, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out, c->blow5.b_out.p, static_cast<size_t>(out_off[n]), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_len, c->blow5.b_len.p, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return SFA_OK;
 }

@@ -84,6 +84,27 @@ def test_host_units_under_sanitizers(tmp_path):
     assert b"ERROR: AddressSanitizer" not in run.stderr and b"runtime error" not in run.stderr, run.stderr.decode()[-3000:]
 
 
+def test_buffer_type_under_sanitizers(tmp_path):
+    """sfa::Buf (sfa_buf.hpp), the context's one buffer type, on a counting malloc / free policy under ASan + UBSan
+    (tests/c/buf_host.cpp): no allocation below the capacity, growth by bytes + bytes / 8 + 256 with the old block freed once,
+    a failing allocator leaves an empty buffer and SFA_ENOMEM with the message, moves transfer ownership, a scope of buffers
+    ends with nothing live."""
+    import shutil
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    exe = str(tmp_path / "buf_host")
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-I",
+                            os.path.join(ROOT, "sigfish_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "c", "buf_host.cpp")],
+                           capture_output=True, timeout=600)
+    if build.returncode != 0 and b"sanitize" in build.stderr:
+        pytest.skip("toolchain without sanitizer runtimes")
+    assert build.returncode == 0, build.stderr.decode()[-2000:]
+    run = subprocess.run([exe], capture_output=True, timeout=120)
+    assert run.returncode == 0 and b"0 live, 0 failures" in run.stdout, (run.stdout + run.stderr).decode()[-3000:]
+    assert b"ERROR: AddressSanitizer" not in run.stderr and b"runtime error" not in run.stderr, run.stderr.decode()[-3000:]
+    assert b"LeakSanitizer" not in run.stderr, run.stderr.decode()[-3000:]
+
+
 def test_device_inflate_lane_decoder_on_the_host_with_sanitizers(tmp_path):
     """The per-lane DEFLATE decoder of the device-side BLOW5 reader (blow5_kernels.hpp: the body of blow5_inflate_kernel),
     compiled for the host: against zlib on 4 000 random streams (every block type, encoder setting and window size,
