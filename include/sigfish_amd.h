@@ -193,6 +193,47 @@ int sfa_secondary_rows(sfa_ctx_t *ctx, sfa_result_t *sec, int32_t n_reads);
 int sfa_event_maps(sfa_ctx_t *ctx, const sfa_result_t *rows, const int32_t *read_of_row, int32_t n_rows, const int64_t *map_off,
                    int32_t *pairs, int32_t *n_on_host);
 
+/* ---- alignment sessions: a read's alignment extended as its events arrive (real-time use) -------------------------------
+ * A session has n_slots SLOTS, each one growing read (a sequencing channel, say).  Of every (slot, contig, strand) sweep it keeps
+ * the last query row in device memory -- the accumulated cost of every reference column and, unless SFA_SESSION_NO_START, the
+ * start column of the path into it -- so a chunk of new events costs its own rows of the recurrence, however long the read has
+ * become, instead of sfa_align_batch over the whole prefix again.  The caller keeps its normalisation fixed over a slot's life:
+ * the events of all chunks are taken as ONE query (to re-normalise, reset the slot and send its events again).
+ * Single-device contexts without SFA_DTW, and not SFA_RNA without SFA_INV (the query rows are then the events reversed: new events
+ * would become row 0); SFA_EINVAL otherwise.  A session belongs to its context and uses its stream; its buffers are its own, so
+ * batch calls on the context between two extends do not disturb it, and sfa_secondary_rows / sfa_event_maps keep referring to
+ * the last BATCH call.  sfa_destroy frees the sessions a context still has: their handles are dead after it. */
+typedef struct sfa_session sfa_session_t;
+#define SFA_SESSION_NO_START 0x1 /* carry costs only: half the memory, the fill's cheap cell; the start side is not reported */
+
+/* SFA_ENOMEM when the carried rows do not fit. */
+int sfa_session_create(sfa_ctx_t *ctx, int32_t n_slots, uint32_t session_flags, sfa_session_t **s);
+
+/* Append events[ev_off[i] .. ev_off[i+1]) -- z-normalised means in event order, as for sfa_align_batch -- to slot slot[i], i < n,
+ * and write to out[i] the row sfa_align_batch returns for ALL events the slot has received since its last reset: every field,
+ * bit for bit.  With SFA_SESSION_NO_START the coordinate that needs the start column is -1 instead: pos_st on '+', pos_end on
+ * '-' (the flip).  Chunks may have any length (one of more than SFA_MAX_QUERY events runs as consecutive pieces inside the
+ * call); an empty chunk returns the slot's current row, valid = 0 for a slot without events.  A chunk with a NaN or +-inf
+ * poisons its slot: its rows are valid = 0 until it is reset, and it counts in sfa_profile_t.non_finite_reads.  Blocking, on the
+ * context's stream.  SFA_EINVAL: a slot out of range or named twice in the call.  sfa_get_profile afterwards reports this call:
+ * fill_ms (the sweeps), total_ms, cells (new events x reference columns), n_tasks. */
+int sfa_session_extend(sfa_session_t *s, const int32_t *slot, const float *events, const int64_t *ev_off, int32_t n,
+                       sfa_result_t *out);
+
+/* Forget the events of slot[0..n) (slot == NULL: of every slot); a poisoned slot is clean again. */
+int sfa_session_reset(sfa_session_t *s, const int32_t *slot, int32_t n);
+
+/* len[i] = events slot[i] has received since its last reset (slot == NULL: all slots in order, n must be n_slots). */
+int sfa_session_lengths(sfa_session_t *s, const int32_t *slot, int32_t n, int64_t *len);
+
+void sfa_session_destroy(sfa_session_t *s);
+
+/* Device memory sfa_session_create takes for the carried rows of n_slots slots over a reference of total_columns columns
+ * (sum of ref_lengths, twice that for DNA): one row per slot, updated in place -- total_columns x n_slots x 8 bytes, x 4 with
+ * SFA_SESSION_NO_START (the allocator adds an eighth of headroom; bookkeeping is some 50 bytes per slot).  Host arithmetic, no
+ * device needed; negative (an SFA_E* code) for arguments that are not positive, unknown flags or a product beyond 2^63. */
+int64_t sfa_session_bytes(int64_t total_columns, int32_t n_slots, uint32_t session_flags);
+
 /* align_db() shaped entry: per-read event tables exactly as db_t holds them (src/sigfish.h:177-178):
  * events[i] -> sfa_event_t array of read i, qstart[i]/qend[i] the window chosen by normalise_single
  * (src/sigfish.c:479-480); reads with n_events[i]==0 are skipped.  The window means are gathered out of the 24-byte event

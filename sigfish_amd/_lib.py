@@ -54,7 +54,8 @@ class SfaEvent(C.Structure):
 SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "sfa_submit_batch", "sfa_wait_batch", "sfa_align_batch_device", "sfa_align_events", "sfa_align_raw", "sfa_align_raw_ex", "sfa_align_blow5", "sfa_inflate_zlib_device", "sfa_pinned_alloc", "sfa_pinned_free", "sfa_sync",
            "sfa_get_profile", "sfa_stream", "sfa_set_option", "sfa_plan_batch", "sfa_destroy", "sfa_last_error", "sfa_version", "sfa_build_id", "sfa_gen_ref_record",
            "sfa_znormalise", "sfa_paf_row", "sfa_sam_row", "sfa_paf_row_ex", "sfa_sam_row_ex", "sfa_secondary_rows", "sfa_event_maps", "sfa_sam_row_from_map", "sfa_r2qevent_map", "sfa_detect_events", "sfa_select_query", "sfa_detect_query_start", "sfa_set_pore", "sfa_read_kmer_model",
-           "sfa_blow5_open", "sfa_blow5_attr", "sfa_blow5_next", "sfa_blow5_close", "sfa_blow5_select_shard", "sfa_blow5_select_records", "sfa_inflate_zlib", "sfa_inflate_zlib_pair", "sfa_device_memory"]
+           "sfa_blow5_open", "sfa_blow5_attr", "sfa_blow5_next", "sfa_blow5_close", "sfa_blow5_select_shard", "sfa_blow5_select_records", "sfa_inflate_zlib", "sfa_inflate_zlib_pair", "sfa_device_memory",
+           "sfa_session_create", "sfa_session_extend", "sfa_session_reset", "sfa_session_lengths", "sfa_session_destroy", "sfa_session_bytes"]
 
 _lib = None
 
@@ -139,5 +140,13 @@ def load():
     L.sfa_inflate_zlib_pair.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, i64p]
     L.sfa_inflate_zlib.restype = C.c_int64
     L.sfa_device_memory.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.sfa_session_create.argtypes = [vp, C.c_int32, C.c_uint32, C.POINTER(vp)]
+    L.sfa_session_extend.argtypes = [vp, i32p, f32p, i64p, C.c_int32, vp]
+    L.sfa_session_reset.argtypes = [vp, i32p, C.c_int32]
+    L.sfa_session_lengths.argtypes = [vp, i32p, C.c_int32, i64p]
+    L.sfa_session_destroy.argtypes = [vp]
+    L.sfa_session_destroy.restype = None
+    L.sfa_session_bytes.argtypes = [C.c_int64, C.c_int32, C.c_uint32]
+    L.sfa_session_bytes.restype = C.c_int64
     _lib = L
     return L

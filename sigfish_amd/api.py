@@ -235,6 +235,11 @@ class Aligner:
                "sfa_align_events")
         return out
 
+    def session(self, n_slots, starts=True):
+        """An alignment session of n_slots growing reads on this aligner (sfa_session_create); starts=False carries costs only
+        (SFA_SESSION_NO_START: half the memory, the coordinate on the start side of every row is -1)."""
+        return Session(self, n_slots, starts)
+
     def set_option(self, key, value):
         _check(self._L.sfa_set_option(self._h, key.encode(), int(value)), f"sfa_set_option({key})")
 
@@ -351,6 +356,89 @@ class Aligner:
 
     def stream(self):
         return self._L.sfa_stream(self._h)
+
+
+SESSION_NO_START = 0x1
+
+
+class Session:
+    """Slots whose alignment is extended as their events arrive: after every extend() a slot's row is the row align_db returns
+    for all events the slot has received since its last reset.  Belongs to its Aligner: close it first (closing the Aligner frees
+    the native session as well, this object is then closed)."""
+
+    def __init__(self, aligner, n_slots, starts=True):
+        self._al = aligner
+        self._L = aligner._L
+        self._h = C.c_void_p()
+        self.n_slots, self.starts = int(n_slots), bool(starts)
+        _check(self._L.sfa_session_create(aligner._h, self.n_slots, 0 if starts else SESSION_NO_START, C.byref(self._h)),
+               "sfa_session_create")
+        self._al_h = aligner._h.value  # the native context this session belongs to
+
+    def _live(self):
+        if not self._h or self._al._h.value != self._al_h:
+            raise SfaError("the session is closed (or its Aligner is)")
+
+    def extend(self, slots, events, ev_off):
+        """Append events[ev_off[i]:ev_off[i+1]] (z-normalised means, event order) to slot slots[i]. -> RESULT_DTYPE[len(slots)]"""
+        self._live()
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        ev = _f32(events)
+        eo = np.ascontiguousarray(ev_off, np.int64)
+        n = len(sl)
+        if len(eo) != n + 1:
+            raise SfaError("extend: ev_off must have one entry more than slots")
+        out = np.zeros(n, RESULT_DTYPE)
+        if ev.size == 0:
+            ev = np.zeros(1, np.float32)
+        _check(self._L.sfa_session_extend(self._h, sl.ctypes.data_as(_lib.i32p), ev.ctypes.data_as(_lib.f32p),
+                                          eo.ctypes.data_as(_lib.i64p), n, out.ctypes.data_as(C.c_void_p)), "sfa_session_extend")
+        return out
+
+    def reset(self, slots=None):
+        """Forget the events of `slots` (None: of every slot)."""
+        self._live()
+        if slots is None:
+            _check(self._L.sfa_session_reset(self._h, None, 0), "sfa_session_reset")
+            return
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        _check(self._L.sfa_session_reset(self._h, sl.ctypes.data_as(_lib.i32p), len(sl)), "sfa_session_reset")
+
+    def lengths(self, slots=None):
+        """Events received since the last reset, int64 per slot of `slots` (None: every slot in order)."""
+        self._live()
+        sl = None if slots is None else np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = self.n_slots if sl is None else len(sl)
+        out = np.zeros(n, np.int64)
+        _check(self._L.sfa_session_lengths(self._h, None if sl is None else sl.ctypes.data_as(_lib.i32p), n,
+                                           out.ctypes.data_as(_lib.i64p)), "sfa_session_lengths")
+        return out
+
+    def close(self):
+        if self._h and self._al._h.value == self._al_h:  # (an Aligner that was closed took its sessions with it)
+            self._L.sfa_session_destroy(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def session_bytes(total_columns, n_slots, starts=True):
+    """Device memory the carried rows of a session take (sfa_session_bytes; host arithmetic, no GPU needed): RefModel.total_columns()
+    x n_slots x 8 bytes, x 4 without starts."""
+    b = int(_lib.load().sfa_session_bytes(int(total_columns), int(n_slots), 0 if starts else SESSION_NO_START))
+    if b < 0:
+        raise SfaError(f"sfa_session_bytes failed ({b}): total_columns and n_slots must be positive")
+    return b
 
 
 def plan_batch(q_off, job_len, ckpt_interval=0, ckpt_budget_bytes=0, lane_widening=0):

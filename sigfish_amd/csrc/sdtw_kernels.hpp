@@ -1549,6 +1549,22 @@ __device__ __forceinline__ uint8_t mapq_from_scores(float score, float score2) {
     return static_cast<uint8_t>(q);
 }
 
+// One partial top-2 (b, s2) merged into the running (best, second), partials in processing order: the second smallest of the
+// four stays, and a later partial wins ties (src/sigfish.c:577-583).  True when b is the new best.
+__device__ __forceinline__ bool merge_top2(float &best, float &second, const float b, const float s2) {
+    const float hi = fmaxf(best, b);
+    const float lo2 = fminf(second, s2);
+    const bool take = !(b > best);
+    second = fminf(hi, lo2);  // second smallest of {best, second, b, s2}
+    if (take) best = b;
+    return take;
+}
+// Positions of a row from the columns its alignment starts and ends in: strand flip and offset (src/sigfish.c:971-975)
+__device__ __forceinline__ void place_row(ResultRow &r, const int st, const int end, const int rl, const int off) {
+    r.pos_st = ((r.strand == '+') ? st : rl - end) + off;
+    r.pos_end = ((r.strand == '+') ? end : rl - st) + off;
+}
+
 template <int R, int L, bool STD, bool LCK>
 __device__ __forceinline__ void fused_trace_task(const DpArgs &a, const ClassDesc cd, const int quad_local, float *lds_f, int *lds_i, float *lds_x) {
     const int quad = cd.quad_base + quad_local;
@@ -1831,10 +1847,7 @@ __global__ void __launch_bounds__(256) sdtw_finalize_kernel(const FinalizeArgs a
         if (r.rid < 0) return;
         const int st = a.t_st[i];
         const int end = a.t_st[a.n_reads + i];
-        const int rl = a.ref_len[r.rid];
-        const int off = a.ref_st_offset[r.rid];
-        r.pos_st = ((r.strand == '+') ? st : rl - end) + off;  // src/sigfish.c:971-975
-        r.pos_end = ((r.strand == '+') ? end : rl - st) + off;
+        place_row(r, st, end, a.ref_len[r.rid], a.ref_st_offset[r.rid]);
         a.out[i] = r;
         if (a.span_hist && st >= 0 && end >= st) {
             const int64_t ql = a.q_off[i + 1] - a.q_off[i];
@@ -1862,13 +1875,7 @@ __global__ void __launch_bounds__(256) sdtw_finalize_kernel(const FinalizeArgs a
         int end = -1, job = -1;
         for (int ch = 0; ch < a.n_chunks; ++ch) {  // chunks in processing order: a later chunk wins ties
             const int64_t o = (quad * a.n_chunks + ch) * 4 + slot;
-            const float b = a.p_best[o], s2 = a.p_second[o];
-            const float hi = fmaxf(best, b);
-            const float lo2 = fminf(second, s2);
-            const bool take = !(b > best);
-            second = fminf(hi, lo2);  // second smallest of {best, second, b, s2}
-            if (take) {
-                best = b;
+            if (merge_top2(best, second, a.p_best[o], a.p_second[o])) {
                 end = a.p_end[o];
                 job = a.p_job[o];
                 wchunk = ch;

@@ -1,0 +1,336 @@
+// sdtw_session.hpp -- alignment sessions: a read's subsequence DTW extended as its events arrive (sfa_session_extend).
+//
+// Dependencies of the recurrence (src/cdtw.c:171-189) flow downwards and to the right only, so the LAST query row of a (read,
+// contig, strand) sweep is all the rows below it need: one f32 per reference column, plus one i32 per column when the start
+// column of every cell is propagated forwards (the rule of pass 2 and of the row strips, sdtw_strips.hpp).  A session keeps
+// that row per slot (a growing read) in HBM between calls -- the CARRIED ROW.  A call sweeps the new events (a chunk) of its
+// slots below it, reports the window scan of the new last row and leaves that row in the carried row's place.
+//
+//   * one wave-task = (group of slots, contig, strand), all columns in one sweep.  The lane layout is a base class shape of
+//     the fill (kClassShapes), chosen by the CHUNK length; 64 / L slots share a wave; chunks of different lengths share a
+//     wave when they agree modulo R and are laid out from the end (MixedQuad): lane and register of the last row are the
+//     wave's, a shorter chunk begins in a later lane g0.
+//   * the step is strip_step: FIRST = true for a slot's first chunk (constant boundary 0, a path starts in its own column:
+//     exactly the fill's sweep), FIRST = false below a carried row -- lane g0 takes `up` (and its start column) from the
+//     carried row at its column, its diagonal is the previous step's `up`.  The host never mixes the two kinds in a wave.
+//     Column 0 needs no special case: there is no column -1 (the diagonal input is +inf) and its `up` carries start 0.
+//   * the carried row is loaded four columns per 16-byte access, one block of four steps ahead, like the reference levels;
+//     the new last row (lane lq, register rq) is collected four columns at a time and stored with ordinary vector stores IN
+//     PLACE: column j is read for step j + g0 at the latest and written at step j + lq >= j + g0 by the same wave, memory
+//     operations of a wave are issued in order, and no other wave touches the row of this (slot, contig, strand).
+//   * rows of all (slot, job) pairs lie back to back, total_columns per slot and no padding in between (sfa_session_bytes is
+//     exactly rows x columns); the block loads of a sweep over-run its row by up to 70 columns on both sides.  What they find
+//     there -- another row, maybe while its wave rewrites it, or the pads around the allocation -- is a cost (never a NaN:
+//     slots with non-finite events are not swept) and only reaches cells of columns < 0, which are forced to +inf, or
+//     >= rlen, whose reference level is the +inf padding and which nothing of a column < rlen depends on.
+//   * the window scan of the new last row (src/sigfish.c:891-901) uses windows of the slot's TOTAL length, not the chunk's;
+//     every window's first strict minimum, its column and (TRACK) its start column are kept, the top-2 per (slot, job) goes
+//     to HBM and sdtw_session_rows_kernel merges the jobs in processing order and writes the rows.
+// All arithmetic is the fill's: every cell is the same pure fp32 function of its three neighbours, so rows equal those of
+// sfa_align_batch over the concatenated events bit for bit.
+#pragma once
+
+#include "sdtw_strips.hpp"
+
+namespace sfa {
+
+constexpr int kSessionPad = 256;       // words in front of and behind the carried rows of a session (over-run of the block loads)
+constexpr int kSessionMaxClasses = 12;  // (first chunk or not) x the six base shapes
+
+struct SessionClass {
+    int32_t R, lanes;     // kClassShapes[...]
+    int32_t first;        // 1: first chunks (constant boundary), 0: below a carried row
+    int32_t group_base;   // first group (a group is one wave's worth of slots: 64 / lanes of them)
+    int32_t n_groups;
+    int32_t task_base;    // first task; the class has n_groups * n_jobs of them, job-major
+};
+
+// Everything a launch reads.  "Entry" k: a slot's piece of this launch (a chunk of up to 2048 events, or a piece of a longer one).
+struct SessionArgs {
+    const float *events;      // the call's events, concatenated
+    const int32_t *w_entry;   // [n_groups * 4] entry per (group, wave slot) or -1
+    const int32_t *g_qlen;    // [n_groups] longest piece of the group
+    const int32_t *k_call;    // [n_entries] index of the slot in the call (bad flag, partial results)
+    const int32_t *k_slot;    // [n_entries] slot of the session
+    const int64_t *k_off;     // [n_entries] first event of the piece in `events`
+    const int32_t *k_len;     // [n_entries] events of the piece
+    const int32_t *k_total;   // [n_entries] events of the slot up to and including the piece: the window length
+    const uint8_t *bad;       // [n_call] the slot's chunk holds a NaN / inf (sdtw_screen_kernel): not swept
+    const float *ref;         // as DpArgs
+    const int64_t *job_off;
+    const int32_t *job_len;
+    const int64_t *col_off;   // [n_jobs] first column of job j inside a slot's carried row
+    float *row_c;             // carried costs [n_slots][row_stride], kSessionPad words in front
+    int32_t *row_s;           // carried start columns, same layout (TRACK)
+    int64_t row_stride;       // total_columns
+    float *p_best, *p_second; // [n_call][n_jobs] top-2 of the windows of the new last row
+    int32_t *p_end, *p_st;    // column of the best window's first strict minimum, start column of the path into it
+    SessionClass cls[kSessionMaxClasses];
+    int32_t n_cls, n_jobs, n_tasks;
+};
+
+template <typename T>
+struct __attribute__((packed, aligned(4))) Quad4 {
+    T v[4];
+};
+
+// last row of the lane's R rows: register rq (wave-uniform)
+template <int R, bool TRACK, typename CF, typename CI>
+__device__ __forceinline__ void session_last_row(const CF &c, const CI &s, const int rq, float &cl, int &sl) {
+    if constexpr (R >= 32) {
+        pick_row<R>(c, s, rq, cl, sl);
+    } else {
+        cl = c[rq];
+        sl = TRACK ? static_cast<int>(s[rq]) : 0;
+    }
+}
+
+template <int R, int L, bool TRACK, bool FIRST>
+__device__ __forceinline__ void session_body(const SessionArgs &a, const SessionClass cd, const int task_local, float *lds_f, int *lds_i) {
+    constexpr int NS = 64 / L;
+    const int job = task_local / cd.n_groups;  // job-major: neighbouring waves stream the same reference
+    const int group = cd.group_base + (task_local - job * cd.n_groups);
+    const int lane = threadIdx.x & 63;
+    const int g = lane & (L - 1);
+    const int ws = lane / L;
+
+    const int qlen = __builtin_amdgcn_readfirstlane(a.g_qlen[group]);
+    const int lq = (qlen - 1) / R;  // lane / register of everybody's last row
+    const int rq = (qlen - 1) - lq * R;
+    const int t_begin = sweep_begin(lq);
+    const int k = a.w_entry[group * 4 + ws];
+    const int call = k >= 0 ? a.k_call[k] : 0;
+    const bool live = k >= 0 && !a.bad[call];
+    const int myq = live ? a.k_len[k] : qlen;
+    const int g0 = (qlen - myq) / R;  // (lengths of a group agree modulo R)
+    const bool lane0 = g == g0;
+    const int total = live ? a.k_total[k] : qlen;  // window length of the last-row scan
+    const int64_t slot = live ? a.k_slot[k] : 0;   // (a wave slot without work reads slot 0's row and writes nothing)
+    const bool owner = live && g == lq;
+
+    float x[R];
+    {
+        const float *q = a.events + (live ? a.k_off[k] : 0);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int i = (g - g0) * R + r;
+            x[r] = (live && i >= 0 && i < myq) ? q[i] : 0.0f;
+        }
+    }
+    Exchange xc;
+    xc.init(lds_f, lds_i, threadIdx.x >> 6, ws, g, L, g0);
+    xc.template set_boundary<TRACK>(lane0, 0.0f);
+
+    const int rlen = a.job_len[job];
+    const float *yp = a.ref + a.job_off[job] - g + t_begin;  // this lane's column at step t is t - g
+    const int64_t row0 = kSessionPad + slot * a.row_stride + a.col_off[job];
+    float *crow = a.row_c + row0;
+    int32_t *srow = TRACK ? a.row_s + row0 : nullptr;
+    const float *cin = crow + (t_begin - g0);  // lane g0's column at step t is t - g0
+    const int32_t *sin = TRACK ? srow + (t_begin - g0) : nullptr;
+
+    typename Vec<float, R>::type c;
+    typename Vec<int, R>::type s;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        c[r] = INFINITY;
+        s[r] = 0;
+    }
+    float dprev = INFINITY;
+    int sdprev = 0;
+
+    Top2 top;
+    top.init();
+    int top_st = -1;
+    float wmin = INFINITY;
+    int wpos = -1, wst = -1;
+    int wend = min(total, rlen);  // end of this slot's current window
+    auto next_end = [&]() {
+        int n = __builtin_amdgcn_readlane(wend, 0);
+#pragma unroll
+        for (int sl = 1; sl < NS; ++sl) n = min(n, __builtin_amdgcn_readlane(wend, sl * L));
+        return n;
+    };
+    int nxt = next_end();  // wave-uniform: the column behind which the next window of any slot ends
+
+    typedef Quad4<float> F4;
+    typedef Quad4<int32_t> I4;
+    F4 ycur = *reinterpret_cast<const F4 *>(yp);
+    F4 bcur = {{0.0f, 0.0f, 0.0f, 0.0f}};
+    I4 scur = {{0, 0, 0, 0}};
+    if (!FIRST) {
+        bcur = *reinterpret_cast<const F4 *>(cin);
+        if (TRACK) scur = *reinterpret_cast<const I4 *>(sin);
+    }
+    int e = 0;  // steps executed; the next step is t = t_begin + e
+    // ---- prologue: the last row has not reached column 0.  Lane g0 may still be in front of column 0: there is no carried
+    // value there, the boundary is +inf (as the cells of those columns are) ----
+    const int e_main = lq - t_begin;
+    for (; e < e_main; e += 4) {
+        const F4 ynext = *reinterpret_cast<const F4 *>(yp + e + 4);
+        F4 bnext = bcur;
+        I4 snext = scur;
+        if (!FIRST) {
+            bnext = *reinterpret_cast<const F4 *>(cin + e + 4);
+            if (TRACK) snext = *reinterpret_cast<const I4 *>(sin + e + 4);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int col0 = t_begin + e + u - g0;  // column of the lane that holds the chunk's first row
+            const float bup = col0 >= 0 ? bcur.v[u] : INFINITY;
+            strip_step<false, FIRST, TRACK, R>(c, s, dprev, sdprev, x, ycur.v[u], col0, lane0, xc, bup, scur.v[u]);
+        }
+        ycur = ynext;
+        bcur = bnext;
+        scur = snext;
+    }
+    // ---- main: block b covers last-row columns 4b .. 4b + 3 ----
+    for (int cb = 0; cb < rlen; cb += 4, e += 4) {
+        const F4 ynext = *reinterpret_cast<const F4 *>(yp + e + 4);
+        F4 bnext = bcur;
+        I4 snext = scur;
+        if (!FIRST) {
+            bnext = *reinterpret_cast<const F4 *>(cin + e + 4);
+            if (TRACK) snext = *reinterpret_cast<const I4 *>(sin + e + 4);
+        }
+        F4 oc;
+        I4 os;
+        const bool edge = cb + 4 > rlen;  // wave-uniform: the last block of a row whose length is no multiple of four
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int col0 = t_begin + e + u - g0;
+            strip_step<false, FIRST, TRACK, R>(c, s, dprev, sdprev, x, ycur.v[u], col0, lane0, xc, bcur.v[u], scur.v[u]);
+            const int col = cb + u;  // of the last row
+            float cl;
+            int sl;
+            session_last_row<R, TRACK>(c, s, rq, cl, sl);
+            oc.v[u] = cl;
+            os.v[u] = sl;
+            if (edge && col >= rlen) continue;  // (wave-uniform)
+            const bool lt = cl < wmin;  // first strict minimum of the window (src/sigfish.c:892-899)
+            wmin = lt ? cl : wmin;
+            wpos = lt ? col : wpos;
+            if (TRACK) wst = lt ? sl : wst;
+            if (__builtin_expect(col + 1 == nxt, 0)) {  // a window of some slot ends behind this column
+                const bool ending = wend == col + 1;
+                const bool became_best = top.offer_if(ending, wmin, wpos, job);
+                top_st = became_best ? wst : top_st;
+                wmin = ending ? INFINITY : wmin;
+                wpos = ending ? -1 : wpos;
+                wst = ending ? -1 : wst;
+                wend = ending ? wend + min(total, rlen - wend) : wend;
+                nxt = next_end();
+            }
+        }
+        if (owner) {  // the new last row takes the carried row's place
+            if (!edge) {
+                *reinterpret_cast<F4 *>(crow + cb) = oc;
+                if (TRACK) *reinterpret_cast<I4 *>(srow + cb) = os;
+            } else {
+#pragma unroll
+                for (int u = 0; u < 3; ++u) {
+                    if (cb + u < rlen) {
+                        crow[cb + u] = oc.v[u];
+                        if (TRACK) srow[cb + u] = os.v[u];
+                    }
+                }
+            }
+        }
+        ycur = ynext;
+        bcur = bnext;
+        scur = snext;
+    }
+    if (owner) {
+        const int64_t o = static_cast<int64_t>(call) * a.n_jobs + job;
+        a.p_best[o] = top.best;
+        a.p_second[o] = top.second;
+        a.p_end[o] = top.end;
+        a.p_st[o] = top_st;
+    }
+}
+
+// grid: ceil(n_tasks / 4) blocks of 256 threads, one task per wave.  TRACK: start columns are carried and propagated
+// (strip_step's tracking branch); else costs only (SFA_SESSION_NO_START).
+template <bool TRACK>
+__global__ void __launch_bounds__(256, TRACK ? 2 : 3) sdtw_session_kernel(const SessionArgs a) {
+    const int task = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    __shared__ float lds_f[4 * kXchWordsPerWave];
+    __shared__ int lds_i[TRACK ? 4 * kXchWordsPerWave : 1];
+    if (task >= a.n_tasks) return;  // wave-uniform
+    int ci = 0;
+    while (ci + 1 < a.n_cls && task >= a.cls[ci + 1].task_base) ++ci;
+    const SessionClass cd = a.cls[ci];
+    const int tl = task - cd.task_base;
+#define SFA_SHAPE(RR, LL)                                                     \
+    case (RR) * 256 + (LL):                                                   \
+        if (cd.first)                                                         \
+            session_body<RR, LL, TRACK, true>(a, cd, tl, lds_f, lds_i);       \
+        else                                                                  \
+            session_body<RR, LL, TRACK, false>(a, cd, tl, lds_f, lds_i);      \
+        break;
+    switch (cd.R * 256 + cd.lanes) {
+        SFA_SHAPE(32, 64) SFA_SHAPE(32, 32) SFA_SHAPE(32, 16)
+        SFA_SHAPE(16, 16) SFA_SHAPE(8, 16) SFA_SHAPE(4, 16)
+        default:
+            break;
+    }
+#undef SFA_SHAPE
+}
+
+// instantiated in sdtw_inst_session_track.hip / sdtw_inst_session_cost.hip
+extern template __global__ void sdtw_session_kernel<true>(const SessionArgs);
+extern template __global__ void sdtw_session_kernel<false>(const SessionArgs);
+
+struct SessionRowsArgs {
+    const int32_t *call_slot;  // [n_call] slot of the session, -1: no row to write (no new events, or the slot is poisoned)
+    const uint8_t *bad;        // [n_call]
+    const float *p_best, *p_second;
+    const int32_t *p_end, *p_st;
+    const int32_t *job_contig;
+    const int8_t *job_strand;
+    const int32_t *ref_len, *ref_st_offset;
+    ResultRow *rows;           // [n_slots] the current row of every slot
+    int32_t n_call, n_jobs;
+    int32_t track;             // 0: SFA_SESSION_NO_START -- the coordinate that needs the start column is -1
+};
+
+#ifdef SFA_DEFINE_SESSION_KERNELS  // plain kernel: defined in exactly one translation unit (sfa_session.hip)
+// the jobs' partial top-2 of every slot of the call merged in processing order (a later job wins ties), then contig, strand,
+// mapq, flip and offset (src/sigfish.c:969-983): what sdtw_finalize_kernel does for a batch
+__global__ void __launch_bounds__(64) sdtw_session_rows_kernel(const SessionRowsArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_call) return;
+    const int slot = a.call_slot[i];
+    if (slot < 0 || a.bad[i]) return;
+    float best = INFINITY, second = INFINITY;
+    int end = -1, st = -1, job = -1;
+    for (int j = 0; j < a.n_jobs; ++j) {
+        const int64_t o = static_cast<int64_t>(i) * a.n_jobs + j;
+        if (merge_top2(best, second, a.p_best[o], a.p_second[o])) {
+            end = a.p_end[o];
+            st = a.p_st[o];
+            job = j;
+        }
+    }
+    ResultRow r;
+    r.rid = -1;
+    r.pos_st = -1;
+    r.pos_end = -1;
+    r.score = best;
+    r.score2 = second;
+    r.strand = 0;
+    r.mapq = 0;
+    r.valid = 1;
+    r.pad = 0;
+    if (job >= 0) {
+        r.rid = a.job_contig[job];
+        r.strand = a.job_strand[job];
+        r.mapq = mapq_from_scores(best, second);
+        place_row(r, st, end, a.ref_len[r.rid], a.ref_st_offset[r.rid]);
+        if (!a.track) (r.strand == '+' ? r.pos_st : r.pos_end) = -1;
+    }
+    a.rows[slot] = r;
+}
+#endif
+
+}  // namespace sfa

@@ -555,9 +555,7 @@ __global__ void __launch_bounds__(64) sdtw_strip_finalize_kernel(const StripFina
         ResultRow r = a.out[a.reads[li]];
         const int st = a.t_st[li], end = a.t_end[li];
         if (r.rid < 0 || end < 0) return;
-        const int rl = a.ref_len[r.rid], off = a.ref_st_offset[r.rid];
-        r.pos_st = ((r.strand == '+') ? st : rl - end) + off;  // src/sigfish.c:971-975
-        r.pos_end = ((r.strand == '+') ? end : rl - st) + off;
+        place_row(r, st, end, a.ref_len[r.rid], a.ref_st_offset[r.rid]);
         a.out[a.reads[li]] = r;
         return;
     }
@@ -565,13 +563,7 @@ __global__ void __launch_bounds__(64) sdtw_strip_finalize_kernel(const StripFina
     int ws = -1, job = -1;
     for (int j = 0; j < a.n_jobs; ++j) {
         const int64_t o = static_cast<int64_t>(li) * a.n_jobs + j;
-        const float b = a.p_best[o], s2 = a.p_second[o];
-        const float hi = fmaxf(best, b);
-        const float lo2 = fminf(second, s2);
-        const bool take = !(b > best);
-        second = fminf(hi, lo2);
-        if (take) {
-            best = b;
+        if (merge_top2(best, second, a.p_best[o], a.p_second[o])) {
             ws = a.p_end[o];
             job = j;
         }

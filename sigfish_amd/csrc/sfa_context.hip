@@ -172,6 +172,7 @@ void sfa_destroy(sfa_ctx_t *c) {
     }
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    sfa::destroy_sessions(c);  // (their handles die with the context)
     delete c;  // buffers, then events, then streams (the order of the members of sfa_ctx)
 }
 

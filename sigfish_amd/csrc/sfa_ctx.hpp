@@ -6,6 +6,7 @@
 //   sfa_context.hip  contexts: init / destroy, devices, options, profile, small utilities
 //   sfa_align.hip    the alignment stage: planner -> launches (wave kernels, row strips) -> rows; the batch entry points
 //   sfa_maps.hip     event maps of the last call's rows (sdtw_path.hpp)
+//   sfa_session.hip  alignment sessions: a slot's sweep extended chunk by chunk below its carried row (sdtw_session.hpp)
 //   sfa_pre.hip      the stages in front of it on the device: raw samples / BLOW5 records in (events_kernels.hpp, blow5_kernels.hpp)
 // There is NO CPU fallback: every failure is reported through the return code + sfa_last_error().
 #pragma once
@@ -374,10 +375,12 @@ struct sfa_ctx {
     sfa_profile_t prof{};
     bool prof_pending = false;
     bool in_slice = false;  // align_device is running one slice of a cut-up batch
+    std::vector<struct sfa_session *> sessions;  // live sessions of this context (sfa_session.hip); sfa_destroy frees them first
 };
 
 // ---- internal functions that cross unit boundaries ----
 namespace sfa {
+void destroy_sessions(sfa_ctx *c);  // sfa_session.hip: every live session of the context (sfa_destroy)
 int resolve_profile(sfa_ctx *c);  // sfa_align.hip: timers + error words of the batch submitted last (waits for it)
 // core of every align entry point: queries already in HBM, results left in HBM (sfa_align.hip)
 int align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32_t n, struct ResultRow *d_out,

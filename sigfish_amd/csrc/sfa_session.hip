@@ -1,0 +1,382 @@
+// sfa_session.hip -- alignment sessions of the C-ABI (include/sigfish_amd.h): a slot's subsequence DTW extended chunk by chunk
+// (sdtw_session.hpp).  The session owns the carried rows, the slots' lengths and poison flags, the current row of every slot and
+// the staging of a call; it belongs to its context, runs on the context's stream and is freed with it at the latest.
+#include "sfa_ctx.hpp"
+#define SFA_DEFINE_SESSION_KERNELS  // (this unit holds the plain kernel of sdtw_session.hpp)
+#include "sdtw_session.hpp"
+
+namespace sfa {
+// defined in sfa_align.hip, the unit that holds the plain kernels of sdtw_kernels.hpp
+__global__ void sdtw_screen_kernel(const float *queries, const int64_t *q_off, const int n, uint8_t *bad, unsigned *count);
+}  // namespace sfa
+
+struct sfa_session {
+    sfa_ctx *c = nullptr;
+    int32_t n_slots = 0;
+    bool track = true;  // start columns are carried (no SFA_SESSION_NO_START)
+    std::vector<int64_t> len;     // events every slot has received since its last reset
+    std::vector<uint8_t> poison;  // a chunk of the slot held a NaN / inf: no rows until reset
+    std::vector<int32_t> stamp;   // call in which the slot was named last (duplicates inside one call)
+    int32_t call_no = 0;
+    DevBuf d_row_c, d_row_s;      // carried rows: costs, start columns
+    DevBuf d_col_off;             // [n_jobs] first column of every job inside a slot's row
+    DevBuf d_rows;                // [n_slots] the slots' current rows
+    PinBuf h_rows;
+    DevBuf d_events, d_stage, d_bad, d_count, d_pbest, d_psecond, d_pend, d_pst;  // of a call
+    PinBuf h_stage, h_bad;
+    Event ev[4];  // first kernel, sweeps start / end, rows written
+};
+
+namespace {
+
+int64_t row_words(int64_t total_columns, int32_t n_slots) { return total_columns * n_slots + 2 * sfa::kSessionPad; }
+
+const sfa_result_t kNoRow = {-1, -1, -1, INFINITY, INFINITY, 0, 0, 0, 0};
+
+// A piece of a slot's chunk inside one launch, and where the planner put it
+struct Piece {
+    int32_t call, slot, len, total, first, cls;
+    int64_t off;
+};
+
+// One launch: the staging words of its tables, in the order of SessionArgs
+struct Launch {
+    std::vector<Piece> k;         // entries, in group order
+    std::vector<int32_t> w_entry, g_qlen;
+    sfa::SessionClass cls[sfa::kSessionMaxClasses];
+    int32_t n_cls = 0, n_tasks = 0;
+};
+
+// groups of one launch: pieces sorted by (first chunk or not, class, length modulo R, length descending), 64 / lanes of them
+// per wave as long as kind, class and length modulo R agree (MixedQuad's rule: every last row in the same lane and register)
+void plan_launch(std::vector<Piece> &pieces, int32_t n_jobs, Launch *l) {
+    for (Piece &p : pieces) p.cls = sfa::class_for(p.len);
+    std::sort(pieces.begin(), pieces.end(), [](const Piece &a, const Piece &b) {
+        if (a.first != b.first) return a.first > b.first;
+        if (a.cls != b.cls) return a.cls < b.cls;
+        const int R = sfa::kClassShapes[a.cls].R;
+        if (a.len % R != b.len % R) return a.len % R < b.len % R;
+        if (a.len != b.len) return a.len > b.len;
+        return a.call < b.call;
+    });
+    l->k = pieces;
+    l->n_cls = 0;
+    int32_t n_groups = 0;
+    for (size_t i = 0; i < pieces.size();) {
+        const Piece &p = pieces[i];
+        const sfa::ClassShape sh = sfa::kClassShapes[p.cls];
+        if (l->n_cls == 0 || l->cls[l->n_cls - 1].first != p.first || l->cls[l->n_cls - 1].R != sh.R || l->cls[l->n_cls - 1].lanes != sh.lanes) {
+            sfa::SessionClass &c = l->cls[l->n_cls++];
+            c.R = sh.R;
+            c.lanes = sh.lanes;
+            c.first = p.first;
+            c.group_base = n_groups;
+            c.n_groups = 0;
+            c.task_base = n_groups * n_jobs;
+        }
+        const int ns = 64 / sh.lanes;
+        int32_t w[4] = {-1, -1, -1, -1};
+        int m = 0;
+        while (m < ns && i < pieces.size() && pieces[i].first == p.first && pieces[i].cls == p.cls && pieces[i].len % sh.R == p.len % sh.R) {
+            w[m++] = static_cast<int32_t>(i++);
+        }
+        l->w_entry.insert(l->w_entry.end(), w, w + 4);
+        l->g_qlen.push_back(p.len);  // (descending inside the run: the first is the longest)
+        l->cls[l->n_cls - 1].n_groups++;
+        ++n_groups;
+    }
+    l->n_tasks = n_groups * n_jobs;
+}
+
+size_t align8(size_t x) { return (x + 7) & ~static_cast<size_t>(7); }
+
+}  // namespace
+
+namespace sfa {
+void destroy_sessions(sfa_ctx *c) {
+    while (!c->sessions.empty()) sfa_session_destroy(c->sessions.back());
+}
+}  // namespace sfa
+
+extern "C" {
+
+int64_t sfa_session_bytes(int64_t total_columns, int32_t n_slots, uint32_t session_flags) {
+    if (total_columns <= 0 || n_slots <= 0 || (session_flags & ~static_cast<uint32_t>(SFA_SESSION_NO_START))) return SFA_EINVAL;
+    const int64_t per_column = (session_flags & SFA_SESSION_NO_START) ? 4 : 8;
+    if (total_columns > INT64_MAX / per_column / n_slots) return SFA_ERANGE;
+    return total_columns * n_slots * per_column;  // one row per slot, updated in place
+}
+
+int sfa_session_create(sfa_ctx_t *c, int32_t n_slots, uint32_t session_flags, sfa_session_t **out) {
+    if (!c || !out) return fail(SFA_EINVAL, "sfa_session_create: null argument");
+    if (!c->shards.empty()) return fail(SFA_EINVAL, "sfa_session_create: a session's rows live on one device; use a single-device context (sfa_init)");
+    if (c->flag & SFA_DTW) return fail(SFA_EINVAL, "sfa_session_create: sessions extend the subsequence DTW; the context has SFA_DTW");
+    if ((c->flag & SFA_RNA) && !(c->flag & SFA_INV))
+        return fail(SFA_EINVAL, "sfa_session_create: with SFA_RNA and without SFA_INV the query rows are the events reversed, so new events "
+                                "would become row 0; nothing carried over could be kept");
+    if (n_slots <= 0) return fail(SFA_EINVAL, "sfa_session_create: n_slots must be positive, not %d", n_slots);
+    if (session_flags & ~static_cast<uint32_t>(SFA_SESSION_NO_START)) return fail(SFA_EINVAL, "sfa_session_create: unknown flag bits 0x%x", session_flags);
+    if (sfa_session_bytes(c->model.total_cols, n_slots, session_flags) < 0) return fail(SFA_ENOMEM, "sfa_session_create: the carried rows do not fit");
+    HIP_TRY(hipSetDevice(c->device));
+    std::unique_ptr<sfa_session> s(new sfa_session());
+    s->c = c;
+    s->n_slots = n_slots;
+    s->track = !(session_flags & SFA_SESSION_NO_START);
+    s->len.assign(n_slots, 0);
+    s->poison.assign(n_slots, 0);
+    s->stamp.assign(n_slots, 0);
+    const size_t words = static_cast<size_t>(row_words(c->model.total_cols, n_slots));
+    const size_t nj = c->model.n_jobs;
+    if (int rc = reserve_all(s->d_row_c, 4 * words, s->d_col_off, 8 * nj, s->d_rows, sizeof(sfa_result_t) * n_slots, s->h_rows,
+                             sizeof(sfa_result_t) * n_slots, s->d_count, 64))
+        return rc;
+    if (s->track)
+        if (int rc = s->d_row_s.reserve(4 * words)) return rc;
+    for (Event &e : s->ev)
+        if (hipEventCreate(&e.h) != hipSuccess) return fail(SFA_ENODEV, "hipEventCreate failed");
+    // every word the block loads of a sweep can see holds a cost (a large finite one), never a NaN (sdtw_session.hpp)
+    HIP_TRY(hipMemsetAsync(s->d_row_c.p, 0x7f, s->d_row_c.cap, c->stream));
+    if (s->track) HIP_TRY(hipMemsetAsync(s->d_row_s.p, 0, s->d_row_s.cap, c->stream));
+    std::vector<int64_t> col_off(nj);
+    int64_t acc = 0;
+    for (size_t j = 0; j < nj; ++j) {
+        col_off[j] = acc;
+        acc += c->model.h_job_len[j];
+    }
+    HIP_TRY(hipMemcpyAsync(s->d_col_off.p, col_off.data(), 8 * nj, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (col_off leaves scope)
+    c->sessions.push_back(s.get());
+    *out = s.release();
+    return SFA_OK;
+}
+
+void sfa_session_destroy(sfa_session_t *s) {
+    if (!s) return;
+    sfa_ctx *c = s->c;
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    c->sessions.erase(std::remove(c->sessions.begin(), c->sessions.end(), s), c->sessions.end());
+    delete s;
+}
+
+int sfa_session_reset(sfa_session_t *s, const int32_t *slot, int32_t n) {
+    if (!s) return fail(SFA_EINVAL, "sfa_session_reset: null session");
+    if (!slot) {  // every slot
+        std::fill(s->len.begin(), s->len.end(), 0);
+        std::fill(s->poison.begin(), s->poison.end(), 0);
+        return SFA_OK;
+    }
+    if (n < 0) return fail(SFA_EINVAL, "sfa_session_reset: negative count");
+    for (int32_t i = 0; i < n; ++i)
+        if (slot[i] < 0 || slot[i] >= s->n_slots) return fail(SFA_EINVAL, "sfa_session_reset: slot %d out of range (the session has %d)", slot[i], s->n_slots);
+    for (int32_t i = 0; i < n; ++i) {  // (a slot's next chunk is a first chunk: nothing of its carried row is read)
+        s->len[slot[i]] = 0;
+        s->poison[slot[i]] = 0;
+    }
+    return SFA_OK;
+}
+
+int sfa_session_lengths(sfa_session_t *s, const int32_t *slot, int32_t n, int64_t *len) {
+    if (!s || !len || n < 0) return fail(SFA_EINVAL, "sfa_session_lengths: bad argument");
+    if (!slot) {
+        if (n != s->n_slots) return fail(SFA_EINVAL, "sfa_session_lengths: without a slot list n must be the session's %d slots, not %d", s->n_slots, n);
+        std::copy(s->len.begin(), s->len.end(), len);
+        return SFA_OK;
+    }
+    for (int32_t i = 0; i < n; ++i) {
+        if (slot[i] < 0 || slot[i] >= s->n_slots) return fail(SFA_EINVAL, "sfa_session_lengths: slot %d out of range (the session has %d)", slot[i], s->n_slots);
+        len[i] = s->len[slot[i]];
+    }
+    return SFA_OK;
+}
+
+int sfa_session_extend(sfa_session_t *s, const int32_t *slot, const float *events, const int64_t *ev_off, int32_t n, sfa_result_t *out) {
+    if (!s || n < 0 || (n > 0 && (!slot || !ev_off || !out))) return fail(SFA_EINVAL, "sfa_session_extend: bad argument");
+    if (n == 0) return SFA_OK;
+    sfa_ctx *c = s->c;
+    if (++s->call_no == INT32_MAX) {
+        std::fill(s->stamp.begin(), s->stamp.end(), 0);
+        s->call_no = 1;
+    }
+    for (int32_t i = 0; i < n; ++i) {
+        if (slot[i] < 0 || slot[i] >= s->n_slots) return fail(SFA_EINVAL, "sfa_session_extend: slot %d out of range (the session has %d)", slot[i], s->n_slots);
+        if (s->stamp[slot[i]] == s->call_no) return fail(SFA_EINVAL, "sfa_session_extend: slot %d is named twice in one call", slot[i]);
+        s->stamp[slot[i]] = s->call_no;
+        const int64_t l = ev_off[i + 1] - ev_off[i];
+        if (l < 0) return fail(SFA_EINVAL, "sfa_session_extend: ev_off not monotone");
+        if (s->len[slot[i]] + l > INT32_MAX / 2) return fail(SFA_ERANGE, "sfa_session_extend: slot %d would hold more than 2^30 events", slot[i]);
+    }
+    const int64_t nq = ev_off[n] - ev_off[0];
+    if (nq > 0 && !events) return fail(SFA_EINVAL, "sfa_session_extend: null events");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = sfa::resolve_profile(c)) return rc;  // a batch submitted and never waited for: its error words are this call's
+    hipStream_t st = c->stream;
+    const int32_t nj = c->model.n_jobs;
+
+    // pieces: launch p holds events [p * 2048, (p + 1) * 2048) of every chunk that is that long
+    std::vector<Launch> launches;
+    std::vector<int32_t> call_slot(n, -1);
+    int64_t new_events = 0;
+    for (int32_t p = 0;; ++p) {
+        std::vector<Piece> pieces;
+        for (int32_t i = 0; i < n; ++i) {
+            const int64_t l = ev_off[i + 1] - ev_off[i], done = static_cast<int64_t>(p) * sfa::kMaxQuery;
+            if (l <= done || s->poison[slot[i]]) continue;
+            Piece k;
+            k.call = i;
+            k.slot = slot[i];
+            k.len = static_cast<int32_t>(std::min<int64_t>(sfa::kMaxQuery, l - done));
+            k.total = static_cast<int32_t>(s->len[slot[i]] + done + k.len);
+            k.first = (s->len[slot[i]] + done == 0) ? 1 : 0;
+            k.off = ev_off[i] - ev_off[0] + done;
+            k.cls = 0;
+            pieces.push_back(k);
+            if (p == 0) call_slot[i] = slot[i];
+            new_events += k.len;
+        }
+        if (pieces.empty()) break;
+        launches.emplace_back();
+        plan_launch(pieces, nj, &launches.back());
+    }
+
+    // staging: [ev_off re-based (n + 1) x i64 | call_slot n x i32 | per launch: k_off i64, w_entry, g_qlen, k_call, k_slot, k_len, k_total]
+    size_t bytes = align8(8 * static_cast<size_t>(n + 1)) + align8(4 * static_cast<size_t>(n));
+    for (const Launch &l : launches) bytes += 8 * l.k.size() + align8(4 * (l.w_entry.size() + l.g_qlen.size() + 4 * l.k.size()));
+    const size_t n_part = static_cast<size_t>(n) * nj;
+    if (int rc = reserve_all(s->h_stage, bytes, s->d_stage, bytes, s->d_events, sizeof(float) * static_cast<size_t>(std::max<int64_t>(nq, 1)), s->d_bad,
+                             static_cast<size_t>(n), s->h_bad, static_cast<size_t>(n) + 8, s->d_pbest, 4 * n_part, s->d_psecond, 4 * n_part, s->d_pend, 4 * n_part,
+                             s->d_pst, 4 * n_part))
+        return rc;
+    char *h = s->h_stage.as<char>();
+    const char *d = s->d_stage.as<char>();
+    size_t at = 0;
+    auto put = [&](const void *src, size_t nbytes) {
+        const size_t here = at;
+        if (nbytes) memcpy(h + at, src, nbytes);
+        at += nbytes;
+        return here;
+    };
+    std::vector<int64_t> rebased(n + 1);
+    for (int32_t i = 0; i <= n; ++i) rebased[i] = ev_off[i] - ev_off[0];
+    const size_t o_evoff = put(rebased.data(), 8 * static_cast<size_t>(n + 1));
+    at = align8(at);
+    const size_t o_cslot = put(call_slot.data(), 4 * static_cast<size_t>(n));
+    at = align8(at);
+    std::vector<sfa::SessionArgs> args(launches.size());
+    for (size_t li = 0; li < launches.size(); ++li) {
+        const Launch &l = launches[li];
+        const size_t m = l.k.size();
+        std::vector<int64_t> k_off(m);
+        std::vector<int32_t> k_call(m), k_slot(m), k_len(m), k_total(m);
+        for (size_t i = 0; i < m; ++i) {
+            k_off[i] = l.k[i].off;
+            k_call[i] = l.k[i].call;
+            k_slot[i] = l.k[i].slot;
+            k_len[i] = l.k[i].len;
+            k_total[i] = l.k[i].total;
+        }
+        sfa::SessionArgs &a = args[li];
+        memset(&a, 0, sizeof a);
+        a.k_off = reinterpret_cast<const int64_t *>(d + put(k_off.data(), 8 * m));
+        a.w_entry = reinterpret_cast<const int32_t *>(d + put(l.w_entry.data(), 4 * l.w_entry.size()));
+        a.g_qlen = reinterpret_cast<const int32_t *>(d + put(l.g_qlen.data(), 4 * l.g_qlen.size()));
+        a.k_call = reinterpret_cast<const int32_t *>(d + put(k_call.data(), 4 * m));
+        a.k_slot = reinterpret_cast<const int32_t *>(d + put(k_slot.data(), 4 * m));
+        a.k_len = reinterpret_cast<const int32_t *>(d + put(k_len.data(), 4 * m));
+        a.k_total = reinterpret_cast<const int32_t *>(d + put(k_total.data(), 4 * m));
+        at = align8(at);
+        a.events = s->d_events.as<float>();
+        a.bad = s->d_bad.as<uint8_t>();
+        a.ref = c->model.d_ref.as<float>();
+        a.job_off = c->model.d_job_off.as<int64_t>();
+        a.job_len = c->model.d_job_len.as<int32_t>();
+        a.col_off = s->d_col_off.as<int64_t>();
+        a.row_c = s->d_row_c.as<float>();
+        a.row_s = s->track ? s->d_row_s.as<int32_t>() : nullptr;
+        a.row_stride = c->model.total_cols;
+        a.p_best = s->d_pbest.as<float>();
+        a.p_second = s->d_psecond.as<float>();
+        a.p_end = s->d_pend.as<int32_t>();
+        a.p_st = s->d_pst.as<int32_t>();
+        for (int ci = 0; ci < l.n_cls; ++ci) a.cls[ci] = l.cls[ci];
+        a.n_cls = l.n_cls;
+        a.n_jobs = nj;
+        a.n_tasks = l.n_tasks;
+    }
+    if (at > bytes) return fail(SFA_EKERNEL, "sfa_session_extend: staging overrun (%zu > %zu)", at, bytes);
+    HIP_TRY(hipMemcpyAsync(s->d_stage.p, h, at, hipMemcpyHostToDevice, st));
+    if (nq > 0) HIP_TRY(hipMemcpyAsync(s->d_events.p, events + ev_off[0], sizeof(float) * nq, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(s->d_count.p, 0, 4, st));
+
+    HIP_TRY(hipEventRecord(s->ev[0], st));
+    // chunks with a NaN / inf event are not swept: the slot is poisoned (rows valid = 0 until reset)
+    hipLaunchKernelGGL(sfa::sdtw_screen_kernel, dim3((n + 3) / 4), dim3(256), 0, st, s->d_events.as<float>(), reinterpret_cast<const int64_t *>(d + o_evoff), n,
+                       s->d_bad.as<uint8_t>(), s->d_count.as<unsigned>());
+    KERNEL_TRY();
+    HIP_TRY(hipEventRecord(s->ev[1], st));
+    int64_t n_tasks = 0;
+    for (const sfa::SessionArgs &a : args) {
+        const dim3 grid((a.n_tasks + 3) / 4), block(256);
+        if (s->track)
+            hipLaunchKernelGGL(sfa::sdtw_session_kernel<true>, grid, block, 0, st, a);
+        else
+            hipLaunchKernelGGL(sfa::sdtw_session_kernel<false>, grid, block, 0, st, a);
+        KERNEL_TRY();
+        n_tasks += a.n_tasks;
+    }
+    HIP_TRY(hipEventRecord(s->ev[2], st));
+    {
+        sfa::SessionRowsArgs ra;
+        ra.call_slot = reinterpret_cast<const int32_t *>(d + o_cslot);
+        ra.bad = s->d_bad.as<uint8_t>();
+        ra.p_best = s->d_pbest.as<float>();
+        ra.p_second = s->d_psecond.as<float>();
+        ra.p_end = s->d_pend.as<int32_t>();
+        ra.p_st = s->d_pst.as<int32_t>();
+        ra.job_contig = c->model.d_job_contig.as<int32_t>();
+        ra.job_strand = c->model.d_job_strand.as<int8_t>();
+        ra.ref_len = c->model.d_ref_len.as<int32_t>();
+        ra.ref_st_offset = c->model.d_ref_off.as<int32_t>();
+        ra.rows = s->d_rows.as<sfa::ResultRow>();
+        ra.n_call = n;
+        ra.n_jobs = nj;
+        ra.track = s->track ? 1 : 0;
+        hipLaunchKernelGGL(sfa::sdtw_session_rows_kernel, dim3((n + 63) / 64), dim3(64), 0, st, ra);
+        KERNEL_TRY();
+    }
+    HIP_TRY(hipEventRecord(s->ev[3], st));
+    HIP_TRY(hipMemcpyAsync(s->h_rows.p, s->d_rows.p, sizeof(sfa_result_t) * s->n_slots, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(s->h_bad.p, s->d_bad.p, static_cast<size_t>(n), hipMemcpyDeviceToHost, st));
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "sfa_session_extend: the launches failed: %s", hipGetErrorString(hipGetLastError()));
+
+    const uint8_t *bad = s->h_bad.as<uint8_t>();
+    const sfa_result_t *rows = s->h_rows.as<sfa_result_t>();
+    int64_t non_finite = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t sl = slot[i];
+        s->len[sl] += ev_off[i + 1] - ev_off[i];
+        if (bad[i]) s->poison[sl] = 1;
+        non_finite += s->poison[sl];
+        out[i] = (s->poison[sl] || s->len[sl] == 0) ? kNoRow : rows[sl];
+    }
+    float t_fill = 0, t_total = 0;
+    HIP_TRY(hipEventElapsedTime(&t_fill, s->ev[1], s->ev[2]));
+    HIP_TRY(hipEventElapsedTime(&t_total, s->ev[0], s->ev[3]));
+    sfa_profile_t pr{};
+    pr.fill_ms = t_fill;
+    pr.total_ms = t_total;
+    pr.finalize_ms = t_total - t_fill;
+    pr.cells = new_events * c->model.total_cols;
+    pr.fill_launches = static_cast<int64_t>(args.size());
+    pr.n_tasks = n_tasks;
+    pr.n_chunks = nj;
+    pr.n_segments = 1;
+    pr.non_finite_reads = non_finite;
+    pr.segment_reruns = c->seg.seg_reruns;
+    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
+    c->prof = pr;
+    return SFA_OK;
+}
+
+}  // extern "C"
