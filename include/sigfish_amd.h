@@ -234,6 +234,55 @@ void sfa_session_destroy(sfa_session_t *s);
  * device needed; negative (an SFA_E* code) for arguments that are not positive, unknown flags or a product beyond 2^63. */
 int64_t sfa_session_bytes(int64_t total_columns, int32_t n_slots, uint32_t session_flags);
 
+/* ---- raw-signal sessions: a slot's samples in, its row out ----------------------------------------------------------------
+ * A real-time caller has raw ADC samples per channel, a few hundred to a few thousand at a time, not normalised events.  In raw
+ * mode a session runs the stages in front of the sweep on the device as well, and carries their state per slot:
+ *   events         the streaming detector of sfa_event_stream_* (same arithmetic, same events, bit for bit), its state, the slot's
+ *                  table of final events (means in pA) in device memory; detector parameters follow the context's SFA_RNA
+ *   normalisation  final events 0 .. skip_events - 1 are dropped (the -p of the batch path).  Once final event skip + norm - 1
+ *                  exists, mean and sd over the pA means of events [skip, skip + norm) are computed exactly as sfa_znormalise
+ *                  does (two sequential fp32 loops, sqrt in double) and FROZEN until the slot is reset; event e >= skip enters the
+ *                  slot's query as (mean_e - mean) / sd in fp32
+ *   sweep          the new query events are handed to the session sweep straight from device memory; only the per-slot counts
+ *                  cross PCIe in between (the planner of the sweep is host code)
+ * At query_events query events (skip + query final events) the slot is FULL: its detector stops, later samples are only counted.
+ * A frozen sd that is zero or not finite, or a query event that is not finite, POISONS the slot as a non-finite chunk does in
+ * sfa_session_extend: rows valid = 0 until it is reset.
+ * sfa_session_raw_config switches a session to raw mode (or changes the three sizes); allowed only while every slot is empty,
+ * needs skip >= 0 and 25 <= norm <= query, SFA_EINVAL otherwise.  sfa_session_extend on a raw-mode session is SFA_EINVAL, and so
+ * is sfa_session_extend_raw on a session that is not.  sfa_session_reset clears a slot's detector, events, normalisation and
+ * scaling too; sfa_session_lengths reports the query events swept. */
+int sfa_session_raw_config(sfa_session_t *s, int32_t skip_events, int32_t norm_events, int32_t query_events);
+
+typedef struct {
+    int64_t n_samples; /* samples the slot has received since its last reset */
+    int64_t n_events;  /* final events (at most skip + query) */
+    int64_t q_events;  /* query events swept: the length of the query out[i] is the row of */
+    float norm_mean, norm_sd; /* the frozen normalisation, 0 before calibration */
+    int32_t status;    /* bit 0 calibrated, bit 1 full, bit 2 ended (end of read seen), bit 3 poisoned */
+    int32_t pad;
+} sfa_session_raw_info_t;
+
+/* Append raw[raw_off[i] .. raw_off[i+1]) to slot slot[i], i < n.  scaling[3*i..]: digitisation, offset, range as for sfa_align_raw;
+ * the triple is latched by a slot's first chunk after a reset, another one later is SFA_EINVAL.  end_of_read (may be NULL):
+ * end_of_read[i] != 0 runs the detector's finish step for the slot behind the chunk's samples (the chunk may be empty): the
+ * remaining positions are walked as the batch detector walks them and the last event runs to the end of the signal; the slot
+ * then takes no samples until it is reset (SFA_EINVAL).  out[i]: valid = 0 before calibration; afterwards, bit for bit, the row
+ * sfa_align_batch gives for the slot's normalised query so far (with SFA_SESSION_NO_START as for sfa_session_extend).  Slot range
+ * and duplicates as for sfa_session_extend; SFA_ERANGE beyond 2^30 samples per slot or per call.  Blocking.  sfa_get_profile
+ * afterwards reports events_ms (the detector) and normalise_ms beside fill_ms; total_ms includes them. */
+int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t *raw, const int64_t *raw_off, const double *scaling,
+                           const uint8_t *end_of_read, int32_t n, sfa_result_t *out, sfa_session_raw_info_t *info);
+
+/* The slot's final events [first, first + cap) (means in pA, `start` in samples since the reset) copied to out; returns the
+ * number of final events the slot has, or < 0. */
+int64_t sfa_session_events(sfa_session_t *s, int32_t slot, int64_t first, sfa_event_t *out, int64_t cap);
+
+/* Device memory raw mode adds to sfa_session_bytes: per slot an event table of (skip + query) x 24 bytes, the query of
+ * query x 4 bytes and 592 bytes of detector state.  Host arithmetic; negative (an SFA_E* code) for n_slots <= 0, skip < 0,
+ * query <= 0 or a product beyond 2^63. */
+int64_t sfa_session_raw_bytes(int32_t n_slots, int32_t skip_events, int32_t query_events);
+
 /* align_db() shaped entry: per-read event tables exactly as db_t holds them (src/sigfish.h:177-178):
  * events[i] -> sfa_event_t array of read i, qstart[i]/qend[i] the window chosen by normalise_single
  * (src/sigfish.c:479-480); reads with n_events[i]==0 are skipped.  The window means are gathered out of the 24-byte event
@@ -410,6 +459,24 @@ void sfa_pinned_free(void *p);
  * the return value exceeds cap), or <0 on error. */
 int64_t sfa_detect_events(const int16_t *raw, int64_t n_raw, double digitisation, double offset, double range, int rna,
                           sfa_event_t *out, int64_t cap);
+
+/* The same detector fed a read in chunks (a sequencing channel delivers its samples a few hundred at a time).  With N samples
+ * seen and N >= 2 w_long (w_long = 6 DNA / 14 RNA) both t-statistics of every position j <= N - w_long are already what the whole
+ * read will give, and the peak picker is causal: so a push walks the picker over exactly those positions, and every event whose
+ * closing peak has fired is FINAL -- equal in all four fields, bit for bit, to the same event of sfa_detect_events over the
+ * complete read.  Nothing is withheld and nothing is processed while N < 2 w_long.  sfa_event_stream_finish walks the remaining
+ * positions as the batch code does and closes the last event at the end of the signal: everything push returned plus what
+ * finish returns IS the table of sfa_detect_events.  `start` counts samples since creation.  The state is a constant number of
+ * words (a ring of the last 2 w_long + 1 prefix sums, the two detectors, the sums at their candidate peaks and at the open
+ * event's start); it does not grow with the read.
+ * push / finish write the events that became final to out (at most cap) and return their number; when that exceeds cap nothing
+ * is consumed -- call again with a larger buffer (push: and the same samples).  SFA_EINVAL: null arguments, samples after finish,
+ * a second finish. */
+typedef struct sfa_event_stream sfa_event_stream_t;
+sfa_event_stream_t *sfa_event_stream_create(double digitisation, double offset, double range, int rna);
+int64_t sfa_event_stream_push(sfa_event_stream_t *es, const int16_t *raw, int64_t n, sfa_event_t *out, int64_t cap);
+int64_t sfa_event_stream_finish(sfa_event_stream_t *es, sfa_event_t *out, int64_t cap);
+void sfa_event_stream_destroy(sfa_event_stream_t *es);
 
 /* normalise_single (src/sigfish.c:424-505): choose the query window [qstart,qend) from -p/-q/--from-end
  * (prefix_size < 0: RNA adaptor/poly-A auto detection, src/sigfish.c:380-422 + src/jnn.c) and z-normalise those

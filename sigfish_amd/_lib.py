@@ -50,12 +50,19 @@ class SfaEvent(C.Structure):
     _fields_ = [("start", C.c_uint64), ("length", C.c_float), ("mean", C.c_float), ("stdv", C.c_float)]
 
 
+class SfaSessionRawInfo(C.Structure):
+    _fields_ = [("n_samples", C.c_int64), ("n_events", C.c_int64), ("q_events", C.c_int64), ("norm_mean", C.c_float),
+                ("norm_sd", C.c_float), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
 # every symbol include/sigfish_amd.h declares (checked by tests/test_capi_host.py::test_library_exports_every_declared_symbol)
 SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "sfa_submit_batch", "sfa_wait_batch", "sfa_align_batch_device", "sfa_align_events", "sfa_align_raw", "sfa_align_raw_ex", "sfa_align_blow5", "sfa_inflate_zlib_device", "sfa_pinned_alloc", "sfa_pinned_free", "sfa_sync",
            "sfa_get_profile", "sfa_stream", "sfa_set_option", "sfa_plan_batch", "sfa_destroy", "sfa_last_error", "sfa_version", "sfa_build_id", "sfa_gen_ref_record",
            "sfa_znormalise", "sfa_paf_row", "sfa_sam_row", "sfa_paf_row_ex", "sfa_sam_row_ex", "sfa_secondary_rows", "sfa_event_maps", "sfa_sam_row_from_map", "sfa_r2qevent_map", "sfa_detect_events", "sfa_select_query", "sfa_detect_query_start", "sfa_set_pore", "sfa_read_kmer_model",
            "sfa_blow5_open", "sfa_blow5_attr", "sfa_blow5_next", "sfa_blow5_close", "sfa_blow5_select_shard", "sfa_blow5_select_records", "sfa_inflate_zlib", "sfa_inflate_zlib_pair", "sfa_device_memory",
-           "sfa_session_create", "sfa_session_extend", "sfa_session_reset", "sfa_session_lengths", "sfa_session_destroy", "sfa_session_bytes"]
+           "sfa_session_create", "sfa_session_extend", "sfa_session_reset", "sfa_session_lengths", "sfa_session_destroy", "sfa_session_bytes",
+           "sfa_event_stream_create", "sfa_event_stream_push", "sfa_event_stream_finish", "sfa_event_stream_destroy",
+           "sfa_session_raw_config", "sfa_session_extend_raw", "sfa_session_events", "sfa_session_raw_bytes"]
 
 _lib = None
 
@@ -148,5 +155,19 @@ def load():
     L.sfa_session_destroy.restype = None
     L.sfa_session_bytes.argtypes = [C.c_int64, C.c_int32, C.c_uint32]
     L.sfa_session_bytes.restype = C.c_int64
+    L.sfa_event_stream_create.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int]
+    L.sfa_event_stream_create.restype = vp
+    L.sfa_event_stream_push.argtypes = [vp, i16p, C.c_int64, C.POINTER(SfaEvent), C.c_int64]
+    L.sfa_event_stream_push.restype = C.c_int64
+    L.sfa_event_stream_finish.argtypes = [vp, C.POINTER(SfaEvent), C.c_int64]
+    L.sfa_event_stream_finish.restype = C.c_int64
+    L.sfa_event_stream_destroy.argtypes = [vp]
+    L.sfa_event_stream_destroy.restype = None
+    L.sfa_session_raw_config.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    L.sfa_session_extend_raw.argtypes = [vp, i32p, i16p, i64p, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_int32, vp, vp]
+    L.sfa_session_events.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(SfaEvent), C.c_int64]
+    L.sfa_session_events.restype = C.c_int64
+    L.sfa_session_raw_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.sfa_session_raw_bytes.restype = C.c_int64
     _lib = L
     return L

@@ -24,6 +24,12 @@ QUERY_INFO_DTYPE = np.dtype([("n_events", "<i8"), ("qstart", "<i8"), ("qend", "<
 assert QUERY_INFO_DTYPE.itemsize == C.sizeof(_lib.SfaQueryInfo)
 
 
+SESSION_RAW_INFO_DTYPE = np.dtype([("n_samples", "<i8"), ("n_events", "<i8"), ("q_events", "<i8"), ("norm_mean", "<f4"), ("norm_sd", "<f4"),
+                                   ("status", "<i4"), ("pad", "<i4")])
+assert SESSION_RAW_INFO_DTYPE.itemsize == C.sizeof(_lib.SfaSessionRawInfo)
+RAW_CALIBRATED, RAW_FULL, RAW_ENDED, RAW_POISONED = 1, 2, 4, 8  # bits of SESSION_RAW_INFO_DTYPE's status
+
+
 class SfaError(RuntimeError):
     pass
 
@@ -395,8 +401,52 @@ class Session:
                                           eo.ctypes.data_as(_lib.i64p), n, out.ctypes.data_as(C.c_void_p)), "sfa_session_extend")
         return out
 
+    def configure_raw(self, skip=50, norm=100, query=2048):
+        """Raw mode (sfa_session_raw_config): the session takes samples (extend_raw) and runs event detection and normalisation on
+        the device.  The first `skip` final events of a slot are dropped, mean and sd over the next `norm` are frozen, the slot is
+        full at `query` query events.  Only while every slot is empty."""
+        self._live()
+        _check(self._L.sfa_session_raw_config(self._h, int(skip), int(norm), int(query)), "sfa_session_raw_config")
+        self.raw_shape = (int(skip), int(norm), int(query))
+
+    def extend_raw(self, slots, raw, raw_off, scaling, end=None):
+        """Append raw[raw_off[i]:raw_off[i+1]] (int16 samples) to slot slots[i]; scaling[i] = (digitisation, offset, range); end[i]
+        true: the read of slot i ends behind these samples. -> (RESULT_DTYPE[len(slots)], SESSION_RAW_INFO_DTYPE[len(slots)])"""
+        self._live()
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = len(sl)
+        rw = np.ascontiguousarray(raw, np.int16).reshape(-1)
+        ro = np.ascontiguousarray(raw_off, np.int64)
+        sc = np.ascontiguousarray(scaling, np.float64).reshape(-1)
+        if len(ro) != n + 1 or len(sc) != 3 * n:
+            raise SfaError("extend_raw: raw_off must have one entry more than slots, scaling three per slot")
+        en = None if end is None else np.ascontiguousarray(end, np.uint8).reshape(-1)
+        if en is not None and len(en) != n:
+            raise SfaError("extend_raw: end must have one entry per slot")
+        if rw.size == 0:
+            rw = np.zeros(1, np.int16)
+        out, info = np.zeros(n, RESULT_DTYPE), np.zeros(n, SESSION_RAW_INFO_DTYPE)
+        _check(self._L.sfa_session_extend_raw(self._h, sl.ctypes.data_as(_lib.i32p), rw.ctypes.data_as(C.POINTER(C.c_int16)),
+                                              ro.ctypes.data_as(_lib.i64p), sc.ctypes.data_as(C.POINTER(C.c_double)),
+                                              None if en is None else en.ctypes.data_as(C.POINTER(C.c_uint8)), n,
+                                              out.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p)), "sfa_session_extend_raw")
+        return out, info
+
+    def events(self, slot):
+        """The final events of `slot` (raw mode) as an EVENT_DTYPE array: means in pA, `start` in samples since the slot's reset."""
+        self._live()
+        n = int(self._L.sfa_session_events(self._h, int(slot), 0, None, 0))
+        if n < 0:
+            _check(n, "sfa_session_events")
+        out = np.zeros(n, EVENT_DTYPE)
+        if n:
+            n = int(self._L.sfa_session_events(self._h, int(slot), 0, C.cast(out.ctypes.data, C.POINTER(_lib.SfaEvent)), n))
+            if n < 0:
+                _check(n, "sfa_session_events")
+        return out
+
     def reset(self, slots=None):
-        """Forget the events of `slots` (None: of every slot)."""
+        """Forget the events of `slots` (None: of every slot); in raw mode the detector, normalisation and scaling as well."""
         self._live()
         if slots is None:
             _check(self._L.sfa_session_reset(self._h, None, 0), "sfa_session_reset")
@@ -439,6 +489,62 @@ def session_bytes(total_columns, n_slots, starts=True):
     if b < 0:
         raise SfaError(f"sfa_session_bytes failed ({b}): total_columns and n_slots must be positive")
     return b
+
+
+def session_raw_bytes(n_slots, skip=50, query=2048):
+    """Device memory raw mode adds to session_bytes (sfa_session_raw_bytes; host arithmetic): per slot (skip + query) x 24 bytes of
+    events, query x 4 bytes of query, 592 bytes of detector state."""
+    b = int(_lib.load().sfa_session_raw_bytes(int(n_slots), int(skip), int(query)))
+    if b < 0:
+        raise SfaError(f"sfa_session_raw_bytes failed ({b}): n_slots and query must be positive, skip not negative")
+    return b
+
+
+class EventStream:
+    """The event detector fed a read in chunks, on the host (sfa_event_stream_*): push() returns the events the new samples made
+    final -- each equal, bit for bit, to the same event of detect_events over the complete read -- and finish() the rest."""
+
+    def __init__(self, meta, rna=False):
+        self._L = _lib.load()
+        self._h = self._L.sfa_event_stream_create(meta["digitisation"], meta["offset"], meta["range"], int(rna))
+        if not self._h:
+            raise SfaError("sfa_event_stream_create failed")
+
+    def _call(self, fn, *args):
+        cap = 64
+        while True:
+            out = np.zeros(cap, EVENT_DTYPE)
+            n = int(fn(self._h, *args, C.cast(out.ctypes.data, C.POINTER(_lib.SfaEvent)), cap))
+            if n < 0:
+                raise SfaError(f"the event stream refused the call ({n}): it has finished")
+            if n <= cap:
+                return out[:n]
+            cap = n  # nothing was consumed
+
+    def push(self, raw):
+        raw = np.ascontiguousarray(raw, np.int16).reshape(-1)
+        keep = raw if raw.size else np.zeros(1, np.int16)
+        return self._call(self._L.sfa_event_stream_push, keep.ctypes.data_as(C.POINTER(C.c_int16)), len(raw))
+
+    def finish(self):
+        return self._call(self._L.sfa_event_stream_finish)
+
+    def close(self):
+        if self._h:
+            self._L.sfa_event_stream_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def plan_batch(q_off, job_len, ckpt_interval=0, ckpt_budget_bytes=0, lane_widening=0):

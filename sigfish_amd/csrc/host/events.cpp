@@ -146,6 +146,148 @@ std::vector<sfa_event_t> detect_events(const float *pa, int64_t n_, bool rna) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// the detector as a stream (events.hpp); every expression is the one of tstat / pick_peaks / make_event above
+// ---------------------------------------------------------------------------------------------------------
+EventStream::EventStream(double digitisation, double offset, double range, bool rna) {
+    const DetectorParam &p = rna ? kRna : kDna;
+    w1_ = static_cast<int>(p.w1);
+    w2_ = static_cast<int>(p.w2);
+    ring_ = 2 * w2_ + 1;
+    thr1_ = p.thr1;
+    thr2_ = p.thr2;
+    peak_height_ = p.peak_height;
+    const float rangef = static_cast<float>(range), digf = static_cast<float>(digitisation);  // raw_to_picoamps()
+    offf_ = static_cast<float>(offset);
+    unit_ = rangef / digf;
+    for (int i = 0; i < kRing; ++i) st_.ring_s[i] = st_.ring_q[i] = 0.0;  // (sum[0] = sumsq[0] = 0)
+}
+
+namespace {
+
+// tstat()[i] of a signal of n samples (so far: any n >= i + w gives the same value) from the ring
+float tstat_ring(const EventStream::State &s, int ring, int64_t n, int w, int64_t i) {
+    if (n < 2 * w || i < w || i > n - w) return 0.0f;
+    const float wf = static_cast<float>(w);
+    double s1 = s.ring_s[i % ring], q1 = s.ring_q[i % ring];
+    if (i > w) {
+        s1 -= s.ring_s[(i - w) % ring];
+        q1 -= s.ring_q[(i - w) % ring];
+    }
+    const float s2 = static_cast<float>(s.ring_s[(i + w) % ring] - s.ring_s[i % ring]);
+    const float q2 = static_cast<float>(s.ring_q[(i + w) % ring] - s.ring_q[i % ring]);
+    const float mean1 = static_cast<float>(s1 / static_cast<double>(wf));
+    const float mean2 = s2 / wf;
+    double cv = q1 / static_cast<double>(wf);
+    cv -= static_cast<double>(mean1 * mean1);
+    cv += static_cast<double>(q2 / wf);
+    cv -= static_cast<double>(mean2 * mean2);
+    float combined = static_cast<float>(cv);
+    combined = std::fmax(combined, FLT_MIN);
+    const float delta = mean2 - mean1;
+    return static_cast<float>(std::fabs(static_cast<double>(delta)) / std::sqrt(static_cast<double>(combined / wf)));
+}
+
+sfa_event_t stream_event(int64_t start, int64_t end, double s0, double q0, double s1, double q1) {  // make_event()
+    sfa_event_t e;
+    e.start = static_cast<uint64_t>(start);
+    e.length = static_cast<float>(static_cast<size_t>(end - start));
+    e.mean = static_cast<float>(s1 - s0) / e.length;
+    const float dsq = static_cast<float>(q1 - q0);
+    const float var = dsq / e.length - e.mean * e.mean;
+    e.stdv = std::sqrt(std::fmax(var, 0.0f));
+    return e;
+}
+
+}  // namespace
+
+// pick_peaks() over the positions [s.next, upto] of a signal that has n_final samples (while the read goes on: any value
+// >= upto + w_long); a peak closes the open event at once.  Returns emitted + the events made; those below cap are written.
+int64_t EventStream::walk(State &s, int64_t upto, int64_t n_final, sfa_event_t *out, int64_t cap, int64_t emitted) const {
+    for (int64_t i = s.next; i <= upto; ++i) {
+        const double si = s.ring_s[i % ring_], qi = s.ring_q[i % ring_];
+        for (int k = 0; k < 2; ++k) {
+            Det &d = s.det[k];
+            if (d.masked_to >= i) continue;
+            const int w = k ? w2_ : w1_;
+            const float threshold = k ? thr2_ : thr1_;
+            const float cur = tstat_ring(s, ring_, n_final, w, i);
+            if (d.peak_pos == -1) {
+                if (cur < d.peak_value) {
+                    d.peak_value = cur;
+                } else if (cur - d.peak_value > peak_height_) {
+                    d.peak_value = cur;
+                    d.peak_pos = i;
+                    d.ps = si;
+                    d.pq = qi;
+                }
+            } else {
+                if (cur > d.peak_value) {
+                    d.peak_value = cur;
+                    d.peak_pos = i;
+                    d.ps = si;
+                    d.pq = qi;
+                }
+                if (k == 0 && d.peak_value > threshold) {
+                    Det &ld = s.det[1];
+                    ld.masked_to = d.peak_pos + w;
+                    ld.peak_pos = -1;
+                    ld.peak_value = FLT_MAX;
+                    ld.valid_peak = false;
+                }
+                if (d.peak_value - cur > peak_height_ && d.peak_value > threshold) d.valid_peak = true;
+                if (d.valid_peak && (i - d.peak_pos) > w / 2) {
+                    // create_events(): a peak inside (0, n) closes the open event (a walked position is always < n, and a
+                    // candidate is never at 0: position 0 is masked)
+                    if (emitted < cap) out[emitted] = stream_event(s.ev_start, d.peak_pos, s.es, s.eq, d.ps, d.pq);
+                    ++emitted;
+                    s.ev_start = d.peak_pos;
+                    s.es = d.ps;
+                    s.eq = d.pq;
+                    s.any_cut = true;
+                    d.peak_pos = -1;
+                    d.peak_value = cur;
+                    d.valid_peak = false;
+                }
+            }
+        }
+    }
+    if (upto >= s.next) s.next = upto + 1;
+    return emitted;
+}
+
+int64_t EventStream::push(const int16_t *raw, int64_t n, sfa_event_t *out, int64_t cap) {
+    if (st_.finished) return -1;
+    State s = st_;  // committed only when everything fits
+    int64_t emitted = 0;
+    for (int64_t j = 0; j < n; ++j) {
+        const float pa = (static_cast<float>(raw[j]) + offf_) * unit_;
+        s.acc = s.acc + static_cast<double>(pa);
+        s.acc2 = s.acc2 + static_cast<double>(pa * pa);
+        ++s.n;
+        s.ring_s[s.n % ring_] = s.acc;
+        s.ring_q[s.n % ring_] = s.acc2;
+        if (s.n >= 2 * w2_) emitted = walk(s, s.n - w2_, s.n, out, cap, emitted);
+    }
+    if (emitted > cap) return emitted;
+    st_ = s;
+    return emitted;
+}
+
+int64_t EventStream::finish(sfa_event_t *out, int64_t cap) {
+    if (st_.finished) return -1;
+    State s = st_;
+    int64_t emitted = walk(s, s.n - 1, s.n, out, cap, 0);
+    if (s.any_cut) {  // the last event runs to the end of the signal; no peak at all: no events
+        if (emitted < cap) out[emitted] = stream_event(s.ev_start, s.n, s.es, s.eq, s.acc, s.acc2);
+        ++emitted;
+    }
+    if (emitted > cap) return emitted;
+    s.finished = true;
+    st_ = s;
+    return emitted;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // adaptor / poly-A segmenters (src/jnn.c), only reached with RNA and -p -1
 // ---------------------------------------------------------------------------------------------------------
 namespace {

@@ -25,4 +25,43 @@ int64_t detect_query_start(const int16_t *raw, int64_t n, const float *pa, const
 bool select_and_normalise(std::vector<sfa_event_t> &ev, const int16_t *raw, int64_t nraw, const float *pa, int32_t prefix_size,
                           int32_t query_size, uint32_t flag, int pore, int64_t *qstart, int64_t *qend, int *status);
 
+// The same detector fed a read in chunks.  After a push the peak picker has walked every position j <= N - w_long (N samples
+// seen, N >= 2 w_long): there both t-statistics are what the whole read will give, so every event whose closing peak has fired
+// equals the event detect_events() reports over the complete read, all four fields bit for bit; finish() walks the remaining
+// positions as the batch code does (zeros past n - w) and closes the last event at the end of the signal.  The state is a
+// constant number of words: a ring of the last 2 w_long + 1 prefix sums, the two detectors, the sums at each detector's candidate
+// peak and at the open event's start.
+class EventStream {
+   public:
+    EventStream(double digitisation, double offset, double range, bool rna);
+    // the events the samples raw[0..n) make final are written to out (at most cap); returns their number.  When that exceeds cap
+    // nothing is consumed: the stream is as before the call
+    int64_t push(const int16_t *raw, int64_t n, sfa_event_t *out, int64_t cap);
+    int64_t finish(sfa_event_t *out, int64_t cap);  // end of the read: the rest, by the same rule; -1 once it has delivered
+    int64_t samples() const { return st_.n; }
+
+    static constexpr int kRing = 29;  // 2 * 14 + 1: the RNA long window
+    struct Det {
+        int64_t masked_to = 0, peak_pos = -1;
+        float peak_value = 3.402823466e+38f;  // FLT_MAX
+        bool valid_peak = false;
+        double ps = 0.0, pq = 0.0;  // sum, sumsq at peak_pos
+    };
+    struct State {
+        int64_t n = 0, next = 0;  // samples seen, first position the picker has not walked
+        double acc = 0.0, acc2 = 0.0;
+        double ring_s[kRing], ring_q[kRing];  // sum[i], sumsq[i] at i % ring
+        Det det[2];                           // short, long
+        int64_t ev_start = 0;                 // the open event
+        double es = 0.0, eq = 0.0;
+        bool any_cut = false, finished = false;
+    };
+
+   private:
+    int64_t walk(State &s, int64_t upto, int64_t n_final, sfa_event_t *out, int64_t cap, int64_t emitted) const;
+    State st_;
+    int w1_, w2_, ring_;
+    float thr1_, thr2_, peak_height_, offf_, unit_;
+};
+
 }  // namespace sfa

@@ -171,6 +171,30 @@ int64_t sfa_detect_events(const int16_t *raw, int64_t n_raw, double digitisation
     return n;
 }
 
+}  // extern "C"
+struct sfa_event_stream {
+    sfa::EventStream s;
+};
+extern "C" {
+
+sfa_event_stream_t *sfa_event_stream_create(double digitisation, double offset, double range, int rna) {
+    return new sfa_event_stream{sfa::EventStream(digitisation, offset, range, rna != 0)};
+}
+
+int64_t sfa_event_stream_push(sfa_event_stream_t *es, const int16_t *raw, int64_t n, sfa_event_t *out, int64_t cap) {
+    if (!es || n < 0 || cap < 0 || (n > 0 && !raw) || (cap > 0 && !out)) return SFA_EINVAL;
+    const int64_t got = es->s.push(raw, n, out, cap);
+    return got < 0 ? SFA_EINVAL : got;  // (a stream that has finished takes no samples)
+}
+
+int64_t sfa_event_stream_finish(sfa_event_stream_t *es, sfa_event_t *out, int64_t cap) {
+    if (!es || cap < 0 || (cap > 0 && !out)) return SFA_EINVAL;
+    const int64_t got = es->s.finish(out, cap);
+    return got < 0 ? SFA_EINVAL : got;
+}
+
+void sfa_event_stream_destroy(sfa_event_stream_t *es) { delete es; }
+
 int sfa_select_query(sfa_event_t *events, int64_t n_events, const int16_t *raw, int64_t n_raw, double digitisation,
                      double offset, double range, int32_t prefix_size, int32_t query_size, uint32_t flag, int pore,
                      int64_t *qstart, int64_t *qend) {

@@ -1,9 +1,12 @@
 // sfa_session.hip -- alignment sessions of the C-ABI (include/sigfish_amd.h): a slot's subsequence DTW extended chunk by chunk
 // (sdtw_session.hpp).  The session owns the carried rows, the slots' lengths and poison flags, the current row of every slot and
-// the staging of a call; it belongs to its context, runs on the context's stream and is freed with it at the latest.
+// the staging of a call; it belongs to its context, runs on the context's stream and is freed with it at the latest.  In raw mode
+// (sfa_session_raw_config) it also owns the slots' detector states, event tables and normalised queries (events_stream.hpp):
+// samples go in, the events and the query stay on the device, and the sweep reads the new query events from there.
 #include "sfa_ctx.hpp"
 #define SFA_DEFINE_SESSION_KERNELS  // (this unit holds the plain kernel of sdtw_session.hpp)
 #include "sdtw_session.hpp"
+#include "events_stream.hpp"
 
 namespace sfa {
 // defined in sfa_align.hip, the unit that holds the plain kernels of sdtw_kernels.hpp
@@ -25,6 +28,19 @@ struct sfa_session {
     DevBuf d_events, d_stage, d_bad, d_count, d_pbest, d_psecond, d_pend, d_pst;  // of a call
     PinBuf h_stage, h_bad;
     Event ev[4];  // first kernel, sweeps start / end, rows written
+    // ---- raw mode ----
+    bool raw = false;
+    int32_t skip = 0, norm = 0, query = 0;
+    std::vector<int64_t> raw_n;        // samples every slot has received since its last reset
+    std::vector<int32_t> raw_nev;      // its final events
+    std::vector<int32_t> raw_status;   // bits of sfa_session_raw_info_t.status
+    std::vector<float> raw_mean, raw_sd;
+    std::vector<double> raw_scaling;   // [n_slots][3] latched by the first chunk after a reset
+    std::vector<uint8_t> raw_fresh;    // no chunk since the last reset: the next one initialises the detector state
+    DevBuf d_state, d_evtab, d_query;  // [n_slots] EvStreamSlot, [n_slots][skip + query] EvRecord, [n_slots][query] float
+    DevBuf d_raw, d_rstage, d_rout;    // of a call: samples, entry tables, EvStreamOut per entry
+    PinBuf h_rstage, h_rout;
+    Event ev_raw[3];                   // detector start / end, normalisation end
 };
 
 namespace {
@@ -32,6 +48,11 @@ namespace {
 int64_t row_words(int64_t total_columns, int32_t n_slots) { return total_columns * n_slots + 2 * sfa::kSessionPad; }
 
 const sfa_result_t kNoRow = {-1, -1, -1, INFINITY, INFINITY, 0, 0, 0, 0};
+
+// Where a slot's chunk lies in the device-resident event buffer of a call
+struct Chunk {
+    int64_t off, len;
+};
 
 // A piece of a slot's chunk inside one launch, and where the planner put it
 struct Piece {
@@ -90,6 +111,15 @@ void plan_launch(std::vector<Piece> &pieces, int32_t n_jobs, Launch *l) {
 
 size_t align8(size_t x) { return (x + 7) & ~static_cast<size_t>(7); }
 
+// raw mode: the slot's next chunk is marked fresh, and ev_stream_kernel then starts from the initial detector state
+void reset_raw_slot(sfa_session *s, int32_t sl) {
+    s->raw_n[sl] = 0;
+    s->raw_nev[sl] = 0;
+    s->raw_status[sl] = 0;
+    s->raw_mean[sl] = s->raw_sd[sl] = 0.0f;
+    s->raw_fresh[sl] = 1;
+}
+
 }  // namespace
 
 namespace sfa {
@@ -97,6 +127,186 @@ void destroy_sessions(sfa_ctx *c) {
     while (!c->sessions.empty()) sfa_session_destroy(c->sessions.back());
 }
 }  // namespace sfa
+
+// The core of both extend entry points: chunk i of the call, ch[i], is swept below the carried row of slot[i], and out[i] is the
+// slot's row.  screen: the chunks are the nq host floats behind h_events (may be NULL when nq is 0), back to back; they are
+// uploaded and screened for NaN / inf here.  Else they lie in d_events already (offsets of any kind), and d_bad holds the
+// call's poison flags.
+static int sweep_chunks(sfa_session *s, const int32_t *slot, const Chunk *ch, int32_t n, const float *h_events, int64_t nq, const float *d_events,
+                        sfa_result_t *out) {
+    sfa_ctx *c = s->c;
+    const bool screen = d_events == nullptr;
+    hipStream_t st = c->stream;
+    const int32_t nj = c->model.n_jobs;
+
+    // pieces: launch p holds events [p * 2048, (p + 1) * 2048) of every chunk that is that long
+    std::vector<Launch> launches;
+    std::vector<int32_t> call_slot(n, -1);
+    int64_t new_events = 0;
+    for (int32_t p = 0;; ++p) {
+        std::vector<Piece> pieces;
+        for (int32_t i = 0; i < n; ++i) {
+            const int64_t l = ch[i].len, done = static_cast<int64_t>(p) * sfa::kMaxQuery;
+            if (l <= done || s->poison[slot[i]]) continue;
+            Piece k;
+            k.call = i;
+            k.slot = slot[i];
+            k.len = static_cast<int32_t>(std::min<int64_t>(sfa::kMaxQuery, l - done));
+            k.total = static_cast<int32_t>(s->len[slot[i]] + done + k.len);
+            k.first = (s->len[slot[i]] + done == 0) ? 1 : 0;
+            k.off = ch[i].off + done;
+            k.cls = 0;
+            pieces.push_back(k);
+            if (p == 0) call_slot[i] = slot[i];
+            new_events += k.len;
+        }
+        if (pieces.empty()) break;
+        launches.emplace_back();
+        plan_launch(pieces, nj, &launches.back());
+    }
+
+    // staging: [chunk offsets (n + 1) x i64 | call_slot n x i32 | per launch: k_off i64, w_entry, g_qlen, k_call, k_slot, k_len, k_total]
+    size_t bytes = align8(8 * static_cast<size_t>(n + 1)) + align8(4 * static_cast<size_t>(n));
+    for (const Launch &l : launches) bytes += 8 * l.k.size() + align8(4 * (l.w_entry.size() + l.g_qlen.size() + 4 * l.k.size()));
+    const size_t n_part = static_cast<size_t>(n) * nj;
+    // (d_bad: a raw call has reserved it for n entries and written it already; nothing is dropped here then)
+    if (int rc = reserve_all(s->h_stage, bytes, s->d_stage, bytes, s->d_events, sizeof(float) * static_cast<size_t>(std::max<int64_t>(nq, 1)), s->d_bad,
+                             static_cast<size_t>(n), s->h_bad, static_cast<size_t>(n) + 8, s->d_pbest, 4 * n_part, s->d_psecond, 4 * n_part, s->d_pend, 4 * n_part,
+                             s->d_pst, 4 * n_part))
+        return rc;
+    char *h = s->h_stage.as<char>();
+    const char *d = s->d_stage.as<char>();
+    size_t at = 0;
+    auto put = [&](const void *src, size_t nbytes) {
+        const size_t here = at;
+        if (nbytes) memcpy(h + at, src, nbytes);
+        at += nbytes;
+        return here;
+    };
+    std::vector<int64_t> rebased(n + 1);
+    for (int32_t i = 0; i < n; ++i) rebased[i] = ch[i].off;  // (read by the screen only)
+    rebased[n] = nq;
+    const size_t o_evoff = put(rebased.data(), 8 * static_cast<size_t>(n + 1));
+    at = align8(at);
+    const size_t o_cslot = put(call_slot.data(), 4 * static_cast<size_t>(n));
+    at = align8(at);
+    std::vector<sfa::SessionArgs> args(launches.size());
+    for (size_t li = 0; li < launches.size(); ++li) {
+        const Launch &l = launches[li];
+        const size_t m = l.k.size();
+        std::vector<int64_t> k_off(m);
+        std::vector<int32_t> k_call(m), k_slot(m), k_len(m), k_total(m);
+        for (size_t i = 0; i < m; ++i) {
+            k_off[i] = l.k[i].off;
+            k_call[i] = l.k[i].call;
+            k_slot[i] = l.k[i].slot;
+            k_len[i] = l.k[i].len;
+            k_total[i] = l.k[i].total;
+        }
+        sfa::SessionArgs &a = args[li];
+        memset(&a, 0, sizeof a);
+        a.k_off = reinterpret_cast<const int64_t *>(d + put(k_off.data(), 8 * m));
+        a.w_entry = reinterpret_cast<const int32_t *>(d + put(l.w_entry.data(), 4 * l.w_entry.size()));
+        a.g_qlen = reinterpret_cast<const int32_t *>(d + put(l.g_qlen.data(), 4 * l.g_qlen.size()));
+        a.k_call = reinterpret_cast<const int32_t *>(d + put(k_call.data(), 4 * m));
+        a.k_slot = reinterpret_cast<const int32_t *>(d + put(k_slot.data(), 4 * m));
+        a.k_len = reinterpret_cast<const int32_t *>(d + put(k_len.data(), 4 * m));
+        a.k_total = reinterpret_cast<const int32_t *>(d + put(k_total.data(), 4 * m));
+        at = align8(at);
+        a.events = screen ? s->d_events.as<float>() : d_events;
+        a.bad = s->d_bad.as<uint8_t>();
+        a.ref = c->model.d_ref.as<float>();
+        a.job_off = c->model.d_job_off.as<int64_t>();
+        a.job_len = c->model.d_job_len.as<int32_t>();
+        a.col_off = s->d_col_off.as<int64_t>();
+        a.row_c = s->d_row_c.as<float>();
+        a.row_s = s->track ? s->d_row_s.as<int32_t>() : nullptr;
+        a.row_stride = c->model.total_cols;
+        a.p_best = s->d_pbest.as<float>();
+        a.p_second = s->d_psecond.as<float>();
+        a.p_end = s->d_pend.as<int32_t>();
+        a.p_st = s->d_pst.as<int32_t>();
+        for (int ci = 0; ci < l.n_cls; ++ci) a.cls[ci] = l.cls[ci];
+        a.n_cls = l.n_cls;
+        a.n_jobs = nj;
+        a.n_tasks = l.n_tasks;
+    }
+    if (at > bytes) return fail(SFA_EKERNEL, "session sweep: staging overrun (%zu > %zu)", at, bytes);
+    HIP_TRY(hipMemcpyAsync(s->d_stage.p, h, at, hipMemcpyHostToDevice, st));
+    if (screen && nq > 0) HIP_TRY(hipMemcpyAsync(s->d_events.p, h_events, sizeof(float) * nq, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(s->d_count.p, 0, 4, st));
+
+    HIP_TRY(hipEventRecord(s->ev[0], st));
+    // chunks with a NaN / inf event are not swept: the slot is poisoned (rows valid = 0 until reset)
+    if (screen) {
+        hipLaunchKernelGGL(sfa::sdtw_screen_kernel, dim3((n + 3) / 4), dim3(256), 0, st, s->d_events.as<float>(), reinterpret_cast<const int64_t *>(d + o_evoff), n,
+                           s->d_bad.as<uint8_t>(), s->d_count.as<unsigned>());
+        KERNEL_TRY();
+    }
+    HIP_TRY(hipEventRecord(s->ev[1], st));
+    int64_t n_tasks = 0;
+    for (const sfa::SessionArgs &a : args) {
+        const dim3 grid((a.n_tasks + 3) / 4), block(256);
+        if (s->track)
+            hipLaunchKernelGGL(sfa::sdtw_session_kernel<true>, grid, block, 0, st, a);
+        else
+            hipLaunchKernelGGL(sfa::sdtw_session_kernel<false>, grid, block, 0, st, a);
+        KERNEL_TRY();
+        n_tasks += a.n_tasks;
+    }
+    HIP_TRY(hipEventRecord(s->ev[2], st));
+    {
+        sfa::SessionRowsArgs ra;
+        ra.call_slot = reinterpret_cast<const int32_t *>(d + o_cslot);
+        ra.bad = s->d_bad.as<uint8_t>();
+        ra.p_best = s->d_pbest.as<float>();
+        ra.p_second = s->d_psecond.as<float>();
+        ra.p_end = s->d_pend.as<int32_t>();
+        ra.p_st = s->d_pst.as<int32_t>();
+        ra.job_contig = c->model.d_job_contig.as<int32_t>();
+        ra.job_strand = c->model.d_job_strand.as<int8_t>();
+        ra.ref_len = c->model.d_ref_len.as<int32_t>();
+        ra.ref_st_offset = c->model.d_ref_off.as<int32_t>();
+        ra.rows = s->d_rows.as<sfa::ResultRow>();
+        ra.n_call = n;
+        ra.n_jobs = nj;
+        ra.track = s->track ? 1 : 0;
+        hipLaunchKernelGGL(sfa::sdtw_session_rows_kernel, dim3((n + 63) / 64), dim3(64), 0, st, ra);
+        KERNEL_TRY();
+    }
+    HIP_TRY(hipEventRecord(s->ev[3], st));
+    HIP_TRY(hipMemcpyAsync(s->h_rows.p, s->d_rows.p, sizeof(sfa_result_t) * s->n_slots, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(s->h_bad.p, s->d_bad.p, static_cast<size_t>(n), hipMemcpyDeviceToHost, st));
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "session sweep: the launches failed: %s", hipGetErrorString(hipGetLastError()));
+
+    const uint8_t *bad = s->h_bad.as<uint8_t>();
+    const sfa_result_t *rows = s->h_rows.as<sfa_result_t>();
+    int64_t non_finite = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t sl = slot[i];
+        s->len[sl] += ch[i].len;
+        if (bad[i]) s->poison[sl] = 1;
+        non_finite += s->poison[sl];
+        out[i] = (s->poison[sl] || s->len[sl] == 0) ? kNoRow : rows[sl];
+    }
+    float t_fill = 0, t_total = 0;
+    HIP_TRY(hipEventElapsedTime(&t_fill, s->ev[1], s->ev[2]));
+    HIP_TRY(hipEventElapsedTime(&t_total, s->ev[0], s->ev[3]));
+    sfa_profile_t pr{};
+    pr.fill_ms = t_fill;
+    pr.total_ms = t_total;
+    pr.finalize_ms = t_total - t_fill;
+    pr.cells = new_events * c->model.total_cols;
+    pr.fill_launches = static_cast<int64_t>(args.size());
+    pr.n_tasks = n_tasks;
+    pr.n_chunks = nj;
+    pr.n_segments = 1;
+    pr.non_finite_reads = non_finite;
+    pr.segment_reruns = c->seg.seg_reruns;
+    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
+    c->prof = pr;
+    return SFA_OK;
+}
 
 extern "C" {
 
@@ -164,6 +374,8 @@ int sfa_session_reset(sfa_session_t *s, const int32_t *slot, int32_t n) {
     if (!slot) {  // every slot
         std::fill(s->len.begin(), s->len.end(), 0);
         std::fill(s->poison.begin(), s->poison.end(), 0);
+        if (s->raw)
+            for (int32_t sl = 0; sl < s->n_slots; ++sl) reset_raw_slot(s, sl);
         return SFA_OK;
     }
     if (n < 0) return fail(SFA_EINVAL, "sfa_session_reset: negative count");
@@ -172,6 +384,7 @@ int sfa_session_reset(sfa_session_t *s, const int32_t *slot, int32_t n) {
     for (int32_t i = 0; i < n; ++i) {  // (a slot's next chunk is a first chunk: nothing of its carried row is read)
         s->len[slot[i]] = 0;
         s->poison[slot[i]] = 0;
+        if (s->raw) reset_raw_slot(s, slot[i]);
     }
     return SFA_OK;
 }
@@ -192,6 +405,7 @@ int sfa_session_lengths(sfa_session_t *s, const int32_t *slot, int32_t n, int64_
 
 int sfa_session_extend(sfa_session_t *s, const int32_t *slot, const float *events, const int64_t *ev_off, int32_t n, sfa_result_t *out) {
     if (!s || n < 0 || (n > 0 && (!slot || !ev_off || !out))) return fail(SFA_EINVAL, "sfa_session_extend: bad argument");
+    if (s->raw) return fail(SFA_EINVAL, "sfa_session_extend: the session is in raw mode (sfa_session_raw_config): it takes samples, sfa_session_extend_raw");
     if (n == 0) return SFA_OK;
     sfa_ctx *c = s->c;
     if (++s->call_no == INT32_MAX) {
@@ -211,171 +425,190 @@ int sfa_session_extend(sfa_session_t *s, const int32_t *slot, const float *event
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (int rc = sfa::resolve_profile(c)) return rc;  // a batch submitted and never waited for: its error words are this call's
-    hipStream_t st = c->stream;
-    const int32_t nj = c->model.n_jobs;
+    std::vector<Chunk> ch(n);
+    for (int32_t i = 0; i < n; ++i) ch[i] = Chunk{ev_off[i] - ev_off[0], ev_off[i + 1] - ev_off[i]};
+    return sweep_chunks(s, slot, ch.data(), n, events ? events + ev_off[0] : nullptr, nq, nullptr, out);
+}
 
-    // pieces: launch p holds events [p * 2048, (p + 1) * 2048) of every chunk that is that long
-    std::vector<Launch> launches;
-    std::vector<int32_t> call_slot(n, -1);
-    int64_t new_events = 0;
-    for (int32_t p = 0;; ++p) {
-        std::vector<Piece> pieces;
-        for (int32_t i = 0; i < n; ++i) {
-            const int64_t l = ev_off[i + 1] - ev_off[i], done = static_cast<int64_t>(p) * sfa::kMaxQuery;
-            if (l <= done || s->poison[slot[i]]) continue;
-            Piece k;
-            k.call = i;
-            k.slot = slot[i];
-            k.len = static_cast<int32_t>(std::min<int64_t>(sfa::kMaxQuery, l - done));
-            k.total = static_cast<int32_t>(s->len[slot[i]] + done + k.len);
-            k.first = (s->len[slot[i]] + done == 0) ? 1 : 0;
-            k.off = ev_off[i] - ev_off[0] + done;
-            k.cls = 0;
-            pieces.push_back(k);
-            if (p == 0) call_slot[i] = slot[i];
-            new_events += k.len;
-        }
-        if (pieces.empty()) break;
-        launches.emplace_back();
-        plan_launch(pieces, nj, &launches.back());
-    }
+// ---- raw mode: samples in, rows out (events_stream.hpp) ----
 
-    // staging: [ev_off re-based (n + 1) x i64 | call_slot n x i32 | per launch: k_off i64, w_entry, g_qlen, k_call, k_slot, k_len, k_total]
-    size_t bytes = align8(8 * static_cast<size_t>(n + 1)) + align8(4 * static_cast<size_t>(n));
-    for (const Launch &l : launches) bytes += 8 * l.k.size() + align8(4 * (l.w_entry.size() + l.g_qlen.size() + 4 * l.k.size()));
-    const size_t n_part = static_cast<size_t>(n) * nj;
-    if (int rc = reserve_all(s->h_stage, bytes, s->d_stage, bytes, s->d_events, sizeof(float) * static_cast<size_t>(std::max<int64_t>(nq, 1)), s->d_bad,
-                             static_cast<size_t>(n), s->h_bad, static_cast<size_t>(n) + 8, s->d_pbest, 4 * n_part, s->d_psecond, 4 * n_part, s->d_pend, 4 * n_part,
-                             s->d_pst, 4 * n_part))
+int64_t sfa_session_raw_bytes(int32_t n_slots, int32_t skip_events, int32_t query_events) {
+    if (n_slots <= 0 || skip_events < 0 || query_events <= 0) return SFA_EINVAL;
+    const int64_t cap = static_cast<int64_t>(skip_events) + query_events;
+    const int64_t per_slot = cap * static_cast<int64_t>(sizeof(sfa::EvRecord)) + 4 * static_cast<int64_t>(query_events) + static_cast<int64_t>(sizeof(sfa::EvStreamSlot));
+    if (per_slot > INT64_MAX / n_slots) return SFA_ERANGE;
+    return per_slot * n_slots;
+}
+
+int sfa_session_raw_config(sfa_session_t *s, int32_t skip_events, int32_t norm_events, int32_t query_events) {
+    if (!s) return fail(SFA_EINVAL, "sfa_session_raw_config: null session");
+    if (skip_events < 0 || norm_events < 25 || norm_events > query_events)
+        return fail(SFA_EINVAL, "sfa_session_raw_config: need skip >= 0 and 25 <= norm <= query, not skip %d, norm %d, query %d", skip_events, norm_events, query_events);
+    if (static_cast<int64_t>(skip_events) + query_events > INT32_MAX / 2) return fail(SFA_ERANGE, "sfa_session_raw_config: more than 2^30 events per slot");
+    for (int32_t sl = 0; sl < s->n_slots; ++sl)
+        if (s->len[sl] != 0 || s->poison[sl] || (s->raw && !s->raw_fresh[sl]))
+            return fail(SFA_EINVAL, "sfa_session_raw_config: slot %d is not empty; the mode of a session changes only while every slot is (sfa_session_reset)", sl);
+    sfa_ctx *c = s->c;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t ns = static_cast<size_t>(s->n_slots), cap = static_cast<size_t>(skip_events) + query_events;
+    if (sfa_session_raw_bytes(s->n_slots, skip_events, query_events) < 0) return fail(SFA_ENOMEM, "sfa_session_raw_config: the event tables do not fit");
+    if (int rc = reserve_all(s->d_state, sizeof(sfa::EvStreamSlot) * ns, s->d_evtab, sizeof(sfa::EvRecord) * cap * ns, s->d_query, 4 * static_cast<size_t>(query_events) * ns))
         return rc;
-    char *h = s->h_stage.as<char>();
-    const char *d = s->d_stage.as<char>();
-    size_t at = 0;
-    auto put = [&](const void *src, size_t nbytes) {
-        const size_t here = at;
-        if (nbytes) memcpy(h + at, src, nbytes);
-        at += nbytes;
-        return here;
-    };
-    std::vector<int64_t> rebased(n + 1);
-    for (int32_t i = 0; i <= n; ++i) rebased[i] = ev_off[i] - ev_off[0];
-    const size_t o_evoff = put(rebased.data(), 8 * static_cast<size_t>(n + 1));
-    at = align8(at);
-    const size_t o_cslot = put(call_slot.data(), 4 * static_cast<size_t>(n));
-    at = align8(at);
-    std::vector<sfa::SessionArgs> args(launches.size());
-    for (size_t li = 0; li < launches.size(); ++li) {
-        const Launch &l = launches[li];
-        const size_t m = l.k.size();
-        std::vector<int64_t> k_off(m);
-        std::vector<int32_t> k_call(m), k_slot(m), k_len(m), k_total(m);
-        for (size_t i = 0; i < m; ++i) {
-            k_off[i] = l.k[i].off;
-            k_call[i] = l.k[i].call;
-            k_slot[i] = l.k[i].slot;
-            k_len[i] = l.k[i].len;
-            k_total[i] = l.k[i].total;
-        }
-        sfa::SessionArgs &a = args[li];
-        memset(&a, 0, sizeof a);
-        a.k_off = reinterpret_cast<const int64_t *>(d + put(k_off.data(), 8 * m));
-        a.w_entry = reinterpret_cast<const int32_t *>(d + put(l.w_entry.data(), 4 * l.w_entry.size()));
-        a.g_qlen = reinterpret_cast<const int32_t *>(d + put(l.g_qlen.data(), 4 * l.g_qlen.size()));
-        a.k_call = reinterpret_cast<const int32_t *>(d + put(k_call.data(), 4 * m));
-        a.k_slot = reinterpret_cast<const int32_t *>(d + put(k_slot.data(), 4 * m));
-        a.k_len = reinterpret_cast<const int32_t *>(d + put(k_len.data(), 4 * m));
-        a.k_total = reinterpret_cast<const int32_t *>(d + put(k_total.data(), 4 * m));
-        at = align8(at);
-        a.events = s->d_events.as<float>();
-        a.bad = s->d_bad.as<uint8_t>();
-        a.ref = c->model.d_ref.as<float>();
-        a.job_off = c->model.d_job_off.as<int64_t>();
-        a.job_len = c->model.d_job_len.as<int32_t>();
-        a.col_off = s->d_col_off.as<int64_t>();
-        a.row_c = s->d_row_c.as<float>();
-        a.row_s = s->track ? s->d_row_s.as<int32_t>() : nullptr;
-        a.row_stride = c->model.total_cols;
-        a.p_best = s->d_pbest.as<float>();
-        a.p_second = s->d_psecond.as<float>();
-        a.p_end = s->d_pend.as<int32_t>();
-        a.p_st = s->d_pst.as<int32_t>();
-        for (int ci = 0; ci < l.n_cls; ++ci) a.cls[ci] = l.cls[ci];
-        a.n_cls = l.n_cls;
-        a.n_jobs = nj;
-        a.n_tasks = l.n_tasks;
-    }
-    if (at > bytes) return fail(SFA_EKERNEL, "sfa_session_extend: staging overrun (%zu > %zu)", at, bytes);
-    HIP_TRY(hipMemcpyAsync(s->d_stage.p, h, at, hipMemcpyHostToDevice, st));
-    if (nq > 0) HIP_TRY(hipMemcpyAsync(s->d_events.p, events + ev_off[0], sizeof(float) * nq, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(s->d_count.p, 0, 4, st));
+    for (Event &e : s->ev_raw)
+        if (!e.h && hipEventCreate(&e.h) != hipSuccess) return fail(SFA_ENODEV, "hipEventCreate failed");
+    s->raw = true;
+    s->skip = skip_events;
+    s->norm = norm_events;
+    s->query = query_events;
+    s->raw_n.assign(ns, 0);
+    s->raw_nev.assign(ns, 0);
+    s->raw_status.assign(ns, 0);
+    s->raw_mean.assign(ns, 0.0f);
+    s->raw_sd.assign(ns, 0.0f);
+    s->raw_scaling.assign(3 * ns, 0.0);
+    s->raw_fresh.assign(ns, 1);
+    return SFA_OK;
+}
 
-    HIP_TRY(hipEventRecord(s->ev[0], st));
-    // chunks with a NaN / inf event are not swept: the slot is poisoned (rows valid = 0 until reset)
-    hipLaunchKernelGGL(sfa::sdtw_screen_kernel, dim3((n + 3) / 4), dim3(256), 0, st, s->d_events.as<float>(), reinterpret_cast<const int64_t *>(d + o_evoff), n,
-                       s->d_bad.as<uint8_t>(), s->d_count.as<unsigned>());
-    KERNEL_TRY();
-    HIP_TRY(hipEventRecord(s->ev[1], st));
-    int64_t n_tasks = 0;
-    for (const sfa::SessionArgs &a : args) {
-        const dim3 grid((a.n_tasks + 3) / 4), block(256);
-        if (s->track)
-            hipLaunchKernelGGL(sfa::sdtw_session_kernel<true>, grid, block, 0, st, a);
-        else
-            hipLaunchKernelGGL(sfa::sdtw_session_kernel<false>, grid, block, 0, st, a);
-        KERNEL_TRY();
-        n_tasks += a.n_tasks;
+int64_t sfa_session_events(sfa_session_t *s, int32_t slot, int64_t first, sfa_event_t *out, int64_t cap) {
+    if (!s || !s->raw || first < 0 || cap < 0 || (cap > 0 && !out)) return fail(SFA_EINVAL, "sfa_session_events: bad argument (or the session is not in raw mode)");
+    if (slot < 0 || slot >= s->n_slots) return fail(SFA_EINVAL, "sfa_session_events: slot %d out of range (the session has %d)", slot, s->n_slots);
+    static_assert(sizeof(sfa_event_t) == sizeof(sfa::EvRecord), "the device table is copied out as it is");
+    const int64_t nev = s->raw_nev[slot], m = std::min<int64_t>(cap, nev - first);
+    if (m > 0) {
+        sfa_ctx *c = s->c;
+        HIP_TRY(hipSetDevice(c->device));
+        const sfa::EvRecord *src = s->d_evtab.as<sfa::EvRecord>() + static_cast<int64_t>(slot) * (s->skip + s->query) + first;
+        HIP_TRY(hipMemcpyAsync(out, src, sizeof(sfa::EvRecord) * static_cast<size_t>(m), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    HIP_TRY(hipEventRecord(s->ev[2], st));
-    {
-        sfa::SessionRowsArgs ra;
-        ra.call_slot = reinterpret_cast<const int32_t *>(d + o_cslot);
-        ra.bad = s->d_bad.as<uint8_t>();
-        ra.p_best = s->d_pbest.as<float>();
-        ra.p_second = s->d_psecond.as<float>();
-        ra.p_end = s->d_pend.as<int32_t>();
-        ra.p_st = s->d_pst.as<int32_t>();
-        ra.job_contig = c->model.d_job_contig.as<int32_t>();
-        ra.job_strand = c->model.d_job_strand.as<int8_t>();
-        ra.ref_len = c->model.d_ref_len.as<int32_t>();
-        ra.ref_st_offset = c->model.d_ref_off.as<int32_t>();
-        ra.rows = s->d_rows.as<sfa::ResultRow>();
-        ra.n_call = n;
-        ra.n_jobs = nj;
-        ra.track = s->track ? 1 : 0;
-        hipLaunchKernelGGL(sfa::sdtw_session_rows_kernel, dim3((n + 63) / 64), dim3(64), 0, st, ra);
-        KERNEL_TRY();
-    }
-    HIP_TRY(hipEventRecord(s->ev[3], st));
-    HIP_TRY(hipMemcpyAsync(s->h_rows.p, s->d_rows.p, sizeof(sfa_result_t) * s->n_slots, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(s->h_bad.p, s->d_bad.p, static_cast<size_t>(n), hipMemcpyDeviceToHost, st));
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "sfa_session_extend: the launches failed: %s", hipGetErrorString(hipGetLastError()));
+    return nev;
+}
 
-    const uint8_t *bad = s->h_bad.as<uint8_t>();
-    const sfa_result_t *rows = s->h_rows.as<sfa_result_t>();
-    int64_t non_finite = 0;
+int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t *raw, const int64_t *raw_off, const double *scaling,
+                           const uint8_t *end_of_read, int32_t n, sfa_result_t *out, sfa_session_raw_info_t *info) {
+    if (!s || n < 0 || (n > 0 && (!slot || !raw_off || !scaling || !out || !info))) return fail(SFA_EINVAL, "sfa_session_extend_raw: bad argument");
+    if (!s->raw) return fail(SFA_EINVAL, "sfa_session_extend_raw: the session takes events (sfa_session_extend) until sfa_session_raw_config");
+    if (n == 0) return SFA_OK;
+    sfa_ctx *c = s->c;
+    if (++s->call_no == INT32_MAX) {
+        std::fill(s->stamp.begin(), s->stamp.end(), 0);
+        s->call_no = 1;
+    }
+    std::vector<float> scale(2 * static_cast<size_t>(n));
     for (int32_t i = 0; i < n; ++i) {
         const int32_t sl = slot[i];
-        s->len[sl] += ev_off[i + 1] - ev_off[i];
-        if (bad[i]) s->poison[sl] = 1;
-        non_finite += s->poison[sl];
-        out[i] = (s->poison[sl] || s->len[sl] == 0) ? kNoRow : rows[sl];
+        if (sl < 0 || sl >= s->n_slots) return fail(SFA_EINVAL, "sfa_session_extend_raw: slot %d out of range (the session has %d)", sl, s->n_slots);
+        if (s->stamp[sl] == s->call_no) return fail(SFA_EINVAL, "sfa_session_extend_raw: slot %d is named twice in one call", sl);
+        s->stamp[sl] = s->call_no;
+        const int64_t l = raw_off[i + 1] - raw_off[i];
+        if (l < 0) return fail(SFA_EINVAL, "sfa_session_extend_raw: raw_off not monotone");
+        if (l > 0 && (s->raw_status[sl] & sfa::kRawEnded)) return fail(SFA_EINVAL, "sfa_session_extend_raw: slot %d has seen its end of read; it takes no samples until it is reset", sl);
+        if (s->raw_n[sl] + l > INT32_MAX / 2) return fail(SFA_ERANGE, "sfa_session_extend_raw: slot %d would hold more than 2^30 samples", sl);
+        const double *sc = scaling + 3 * static_cast<size_t>(i);
+        if (!s->raw_fresh[sl] && memcmp(sc, &s->raw_scaling[3 * static_cast<size_t>(sl)], 3 * sizeof(double)) != 0)
+            return fail(SFA_EINVAL, "sfa_session_extend_raw: slot %d: digitisation, offset and range are fixed by a slot's first chunk after a reset", sl);
+        const float dig = static_cast<float>(sc[0]), range = static_cast<float>(sc[2]);  // event_single(), src/sigfish.c:343
+        scale[2 * static_cast<size_t>(i)] = static_cast<float>(sc[1]);
+        scale[2 * static_cast<size_t>(i) + 1] = range / dig;
+        if (!std::isfinite(scale[2 * static_cast<size_t>(i)]) || !std::isfinite(scale[2 * static_cast<size_t>(i) + 1]))
+            return fail(SFA_EINVAL, "sfa_session_extend_raw: slot %d: the scaling is not finite", sl);
     }
-    float t_fill = 0, t_total = 0;
-    HIP_TRY(hipEventElapsedTime(&t_fill, s->ev[1], s->ev[2]));
-    HIP_TRY(hipEventElapsedTime(&t_total, s->ev[0], s->ev[3]));
-    sfa_profile_t pr{};
-    pr.fill_ms = t_fill;
-    pr.total_ms = t_total;
-    pr.finalize_ms = t_total - t_fill;
-    pr.cells = new_events * c->model.total_cols;
-    pr.fill_launches = static_cast<int64_t>(args.size());
-    pr.n_tasks = n_tasks;
-    pr.n_chunks = nj;
-    pr.n_segments = 1;
-    pr.non_finite_reads = non_finite;
-    pr.segment_reruns = c->seg.seg_reruns;
-    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
-    c->prof = pr;
+    const int64_t total = raw_off[n] - raw_off[0];
+    if (total > INT32_MAX / 2) return fail(SFA_ERANGE, "sfa_session_extend_raw: more than 2^30 samples in one call");
+    if (total > 0 && !raw) return fail(SFA_EINVAL, "sfa_session_extend_raw: null samples");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = sfa::resolve_profile(c)) return rc;
+    hipStream_t st = c->stream;
+
+    // entry tables: [raw_off re-based (n + 1) x i64 | slot n x i32 | flags n x i32 | scale 2n x f32]
+    const size_t nn = static_cast<size_t>(n);
+    const size_t o_off = 0, o_slot = align8(8 * (nn + 1)), o_flag = o_slot + align8(4 * nn), o_scale = o_flag + align8(4 * nn), bytes = o_scale + 8 * nn;
+    if (int rc = reserve_all(s->h_rstage, bytes, s->d_rstage, bytes, s->d_raw, 2 * static_cast<size_t>(std::max<int64_t>(total, 1)), s->d_rout, sizeof(sfa::EvStreamOut) * nn,
+                             s->h_rout, sizeof(sfa::EvStreamOut) * nn, s->d_bad, nn, s->h_bad, nn + 8))
+        return rc;
+    char *h = s->h_rstage.as<char>();
+    const char *d = s->d_rstage.as<char>();
+    for (int32_t i = 0; i <= n; ++i) reinterpret_cast<int64_t *>(h + o_off)[i] = raw_off[i] - raw_off[0];
+    for (int32_t i = 0; i < n; ++i) {
+        reinterpret_cast<int32_t *>(h + o_slot)[i] = slot[i];
+        reinterpret_cast<int32_t *>(h + o_flag)[i] = (s->raw_fresh[slot[i]] ? sfa::kEntryFresh : 0) | ((end_of_read && end_of_read[i]) ? sfa::kEntryEnd : 0);
+    }
+    memcpy(h + o_scale, scale.data(), 8 * nn);
+    HIP_TRY(hipMemcpyAsync(s->d_rstage.p, h, bytes, hipMemcpyHostToDevice, st));
+    if (total > 0) HIP_TRY(hipMemcpyAsync(s->d_raw.p, raw + raw_off[0], 2 * static_cast<size_t>(total), hipMemcpyHostToDevice, st));
+
+    const bool rna = (c->flag & SFA_RNA) != 0;  // detector parameters, src/events.c:47-58
+    sfa::EvStreamArgs ea;
+    ea.raw = s->d_raw.as<int16_t>();
+    ea.raw_off = reinterpret_cast<const int64_t *>(d + o_off);
+    ea.slot = reinterpret_cast<const int32_t *>(d + o_slot);
+    ea.e_flags = reinterpret_cast<const int32_t *>(d + o_flag);
+    ea.scale = reinterpret_cast<const float *>(d + o_scale);
+    ea.state = s->d_state.as<sfa::EvStreamSlot>();
+    ea.events = s->d_evtab.as<sfa::EvRecord>();
+    ea.n = n;
+    ea.ev_cap = s->skip + s->query;
+    ea.w1 = rna ? 7 : 3;
+    ea.w2 = rna ? 14 : 6;
+    ea.thr1 = rna ? 2.5f : 1.4f;
+    ea.thr2 = 9.0f;
+    ea.peak_height = rna ? 1.0f : 0.2f;
+    HIP_TRY(hipEventRecord(s->ev_raw[0], st));
+    hipLaunchKernelGGL(sfa::ev_stream_kernel, dim3((n + 63) / 64), dim3(64), 0, st, ea);
+    KERNEL_TRY();
+    HIP_TRY(hipEventRecord(s->ev_raw[1], st));
+    sfa::EvNormArgs na;
+    na.slot = ea.slot;
+    na.state = ea.state;
+    na.events = ea.events;
+    na.query = s->d_query.as<float>();
+    na.out = s->d_rout.as<sfa::EvStreamOut>();
+    na.bad = s->d_bad.as<uint8_t>();
+    na.n = n;
+    na.ev_cap = ea.ev_cap;
+    na.skip = s->skip;
+    na.norm = s->norm;
+    na.query_cap = s->query;
+    hipLaunchKernelGGL(sfa::ev_stream_norm_kernel, dim3(n), dim3(64), 0, st, na);
+    KERNEL_TRY();
+    HIP_TRY(hipEventRecord(s->ev_raw[2], st));
+    // the counts of new events are all that comes back: the planner of the sweep is host code
+    HIP_TRY(hipMemcpyAsync(s->h_rout.p, s->d_rout.p, sizeof(sfa::EvStreamOut) * nn, hipMemcpyDeviceToHost, st));
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "sfa_session_extend_raw: the detector failed: %s", hipGetErrorString(hipGetLastError()));
+
+    const sfa::EvStreamOut *ro = s->h_rout.as<sfa::EvStreamOut>();
+    std::vector<Chunk> ch(n);
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t sl = slot[i];
+        if (s->raw_fresh[sl]) memcpy(&s->raw_scaling[3 * static_cast<size_t>(sl)], scaling + 3 * static_cast<size_t>(i), 3 * sizeof(double));
+        s->raw_fresh[sl] = 0;
+        s->raw_n[sl] += raw_off[i + 1] - raw_off[i];
+        s->raw_nev[sl] = ro[i].n_events;
+        s->raw_status[sl] = ro[i].status;
+        s->raw_mean[sl] = ro[i].mean;
+        s->raw_sd[sl] = ro[i].sd;
+        ch[i] = Chunk{static_cast<int64_t>(sl) * s->query + ro[i].q_first, ro[i].q_new};
+    }
+    float t_ev = 0, t_norm = 0;
+    HIP_TRY(hipEventElapsedTime(&t_ev, s->ev_raw[0], s->ev_raw[1]));
+    HIP_TRY(hipEventElapsedTime(&t_norm, s->ev_raw[1], s->ev_raw[2]));
+    if (int rc = sweep_chunks(s, slot, ch.data(), n, nullptr, 0, s->d_query.as<float>(), out)) return rc;
+    c->prof.events_ms = t_ev;
+    c->prof.normalise_ms = t_norm;
+    c->prof.total_ms += t_ev + t_norm;
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t sl = slot[i];
+        sfa_session_raw_info_t &f = info[i];
+        f.n_samples = s->raw_n[sl];
+        f.n_events = s->raw_nev[sl];
+        f.q_events = s->len[sl];
+        f.norm_mean = s->raw_mean[sl];
+        f.norm_sd = s->raw_sd[sl];
+        f.status = s->raw_status[sl];
+        f.pad = 0;
+    }
     return SFA_OK;
 }
 
