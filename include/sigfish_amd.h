@@ -278,6 +278,14 @@ int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t 
  * number of final events the slot has, or < 0. */
 int64_t sfa_session_events(sfa_session_t *s, int32_t slot, int64_t first, sfa_event_t *out, int64_t cap);
 
+/* For slot[i], i < n, of a raw-mode session: start_raw[i] = start of final event `skip`, end_raw[i] = start + length of the last
+ * query event swept (event skip + q_events - 1), in samples since the slot's reset; both 0 for a slot that is not calibrated.
+ * These are the start_raw_idx / end_raw_idx sfa_paf_row takes (the sum is start + (uint64_t)length; the batch path adds in fp32,
+ * the same number below 2^24 samples).  One gather on the device, one copy back: a tick's decided slots cost one call, where
+ * sfa_session_events is a copy per slot and per end.  Blocking, on the context's stream.
+ * SFA_EINVAL: not a raw-mode session, slot out of range. */
+int sfa_session_query_span(sfa_session_t *s, const int32_t *slot, int32_t n, uint64_t *start_raw, uint64_t *end_raw);
+
 /* Device memory raw mode adds to sfa_session_bytes: per slot an event table of (skip + query) x 24 bytes, the query of
  * query x 4 bytes and 592 bytes of detector state.  Host arithmetic; negative (an SFA_E* code) for n_slots <= 0, skip < 0,
  * query <= 0 or a product beyond 2^63. */

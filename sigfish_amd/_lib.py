@@ -62,7 +62,7 @@ SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "
            "sfa_blow5_open", "sfa_blow5_attr", "sfa_blow5_next", "sfa_blow5_close", "sfa_blow5_select_shard", "sfa_blow5_select_records", "sfa_inflate_zlib", "sfa_inflate_zlib_pair", "sfa_device_memory",
            "sfa_session_create", "sfa_session_extend", "sfa_session_reset", "sfa_session_lengths", "sfa_session_destroy", "sfa_session_bytes",
            "sfa_event_stream_create", "sfa_event_stream_push", "sfa_event_stream_finish", "sfa_event_stream_destroy",
-           "sfa_session_raw_config", "sfa_session_extend_raw", "sfa_session_events", "sfa_session_raw_bytes"]
+           "sfa_session_raw_config", "sfa_session_extend_raw", "sfa_session_events", "sfa_session_raw_bytes", "sfa_session_query_span"]
 
 _lib = None
 
@@ -169,5 +169,6 @@ def load():
     L.sfa_session_events.restype = C.c_int64
     L.sfa_session_raw_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.sfa_session_raw_bytes.restype = C.c_int64
+    L.sfa_session_query_span.argtypes = [vp, i32p, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L

@@ -445,6 +445,18 @@ class Session:
                 _check(n, "sfa_session_events")
         return out
 
+    def query_span(self, slots):
+        """Raw coordinates of the queries of `slots` (raw mode, sfa_session_query_span): (start, end) as uint64 arrays -- the start
+        of final event `skip` and start + length of the last query event swept, in samples since the slot's reset; 0 / 0 for a slot
+        that is not calibrated.  What paf_row takes as start_raw / end_raw."""
+        self._live()
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        a, b = np.zeros(len(sl), np.uint64), np.zeros(len(sl), np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        _check(self._L.sfa_session_query_span(self._h, sl.ctypes.data_as(_lib.i32p), len(sl), a.ctypes.data_as(u64p), b.ctypes.data_as(u64p)),
+               "sfa_session_query_span")
+        return a, b
+
     def reset(self, slots=None):
         """Forget the events of `slots` (None: of every slot); in raw mode the detector, normalisation and scaling as well."""
         self._live()

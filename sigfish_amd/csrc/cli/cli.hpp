@@ -62,8 +62,21 @@ struct Fatal : std::runtime_error {
 };
 [[noreturn]] inline void die(const std::string &msg) { throw Fatal(msg); }
 
+// `sigfish-amd realtime`: the options it shares with dtw (flag, prefix = skip, query, threads, devices, model, pore, verbosity,
+// the two files) and its own
+struct RealtimeOpt {
+    Opt o;
+    int32_t channels = 512;        // --channels: slots of the session, reads in flight
+    int64_t chunk_samples = 1600;  // --chunk-samples: samples a channel sends per tick
+    int32_t norm_events = -1;      // --norm-events: calibration window (-1: the value of -q, the batch normalisation)
+    int32_t min_events = -1;       // --min-events: no early decision below this many query events (-1: the value of -q)
+    int32_t min_mapq = 61;         // --min-mapq: early decision at this mapq (61: never, mapq ends at 60)
+    bool pace = false;             // --pace yes: tick t does not start before t x chunk_samples / sampling_rate seconds
+};
+
 // options.cpp: the option table, help and every check that needs no file and no device (exits for -V and help)
 Opt parse_options(int argc, char **argv);
+RealtimeOpt parse_realtime_options(int argc, char **argv);
 // ranks.cpp
 int supervise_ranks(Opt &o, double t0);
 

@@ -186,7 +186,8 @@ int dtw_main(int argc, char **argv) {
     }
 }
 
-int eval_main(int argc, char **argv);  // eval_main.cpp
+int eval_main(int argc, char **argv);      // eval_main.cpp
+int realtime_main(int argc, char **argv);  // realtime_main.cpp
 
 int main(int argc, char **argv) {
     if (argc >= 2 && (!strcmp(argv[1], "--version") || !strcmp(argv[1], "-V"))) {
@@ -195,7 +196,8 @@ int main(int argc, char **argv) {
     }
     if (argc >= 2 && !strcmp(argv[1], "dtw")) return dtw_main(argc - 1, argv + 1);
     if (argc >= 2 && !strcmp(argv[1], "eval")) return eval_main(argc - 1, argv + 1);
+    if (argc >= 2 && !strcmp(argv[1], "realtime")) return realtime_main(argc - 1, argv + 1);
     fprintf(argc >= 2 && (!strcmp(argv[1], "--help") || !strcmp(argv[1], "-h")) ? stdout : stderr,
-            "Usage: sigfish-amd <command> [options]\n\ncommand:\n         dtw           map raw signal reads to a reference with subsequence DTW on an MI355X\n         eval          compare a test PAF with a truth PAF (mapping accuracy)\n\n");
+            "Usage: sigfish-amd <command> [options]\n\ncommand:\n         dtw           map raw signal reads to a reference with subsequence DTW on an MI355X\n         eval          compare a test PAF with a truth PAF (mapping accuracy)\n         realtime      replay a BLOW5 file through a raw-signal session, channel by channel, a PAF line per decided read\n\n");
     return (argc >= 2 && (!strcmp(argv[1], "--help") || !strcmp(argv[1], "-h"))) ? 0 : 1;
 }

@@ -17,7 +17,7 @@ namespace {
 enum LongOpt {
     O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
     O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
-    O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS
+    O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE
 };
 
 const option kLongOptions[] = {
@@ -99,7 +99,113 @@ void parse_device_list(const char *arg, std::vector<int> *devices) {
     if (devices->empty()) die("--device takes a comma separated list of GPU indices");
 }
 
+// `realtime`: its own options, those of dtw it shares, and those of dtw it refuses by name (a session has no such mode)
+const option kRealtimeOptions[] = {
+    {"threads", required_argument, 0, 't'}, {"verbose", required_argument, 0, 'v'}, {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'V'},
+    {"kmer-model", required_argument, 0, O_KMER_MODEL}, {"output", required_argument, 0, 'o'}, {"rna", no_argument, 0, O_RNA},
+    {"prefix", required_argument, 0, 'p'}, {"query-size", required_argument, 0, 'q'}, {"invert", no_argument, 0, O_INVERT},
+    {"pore", required_argument, 0, O_PORE}, {"device", required_argument, 0, O_DEVICE},
+    {"channels", required_argument, 0, O_CHANNELS}, {"chunk-samples", required_argument, 0, O_CHUNK_SAMPLES},
+    {"norm-events", required_argument, 0, O_NORM_EVENTS}, {"min-events", required_argument, 0, O_MIN_EVENTS},
+    {"min-mapq", required_argument, 0, O_MIN_MAPQ}, {"pace", required_argument, 0, O_PACE},
+    {"dtw-std", no_argument, 0, O_DTW_STD}, {"from-end", no_argument, 0, O_FROM_END}, {"sam", no_argument, 0, 'a'},
+    {"secondary", required_argument, 0, O_SECONDARY}, {"ranks", required_argument, 0, O_RANKS},
+    {0, 0, 0, 0}};
+
+void realtime_help(FILE *fp, const RealtimeOpt &r) {
+    fprintf(fp, "Usage: sigfish-amd realtime [OPTIONS] genome.fa reads.blow5|reads.slow5\n\n"
+                "Replays the file as a flow cell would deliver it, through a raw-signal session (sfa_session_extend_raw): read i starts on\n"
+                "channel i; at every tick each busy channel sends its next --chunk-samples samples, all channels in one call; a read is\n"
+                "decided early (E: --min-events query events and mapq >= --min-mapq), when its query is full (F) or at its end (R), its\n"
+                "PAF line is printed at that moment, and the channel takes the next read of the file.  The schedule counts ticks, not\n"
+                "seconds: the output does not depend on the machine's speed.\n\n"
+                "With the defaults (--norm-events = -q, never early) a read's line, without the three tags at its end, is the line\n"
+                "`sigfish-amd dtw -p P -q Q` prints for it whenever the read has P + Q events: the same events, the window [P, P + Q),\n"
+                "the same normalisation over that window, the same row.  The one difference: a read with fewer than P + norm events is\n"
+                "never calibrated and prints nothing, where dtw shortens its window.\n\nbasic options:\n");
+    fprintf(fp, "   -t INT                     number of host threads decoding the records ahead of need [%d]\n", r.o.threads);
+    fprintf(fp, "   -h                         help\n   -o FILE                    output to file [stdout]\n");
+    fprintf(fp, "   --verbose INT              verbosity level [%d]\n   --version                  print version\n", r.o.verbosity);
+    fprintf(fp, "   --pore STR                 set the pore chemistry (r9, r10 or rna004) [auto]\n");
+    fprintf(fp, "   --device INT               the GPU to use (a session lives on one device) [0]\n");
+    fprintf(fp, "   --kmer-model FILE          nucleotide k-mer model file (required: builtin models are not bundled)\n");
+    fprintf(fp, "   --rna                      the dataset is direct RNA (needs --invert: a session cannot take the query reversed)\n");
+    fprintf(fp, "   --invert                   reverse the reference events instead of query\n");
+    fprintf(fp, "   -q INT                     query events at which a read is full [%d]\n", r.o.query);
+    fprintf(fp, "   -p INT                     the number of events to trim at query signal start, >= 0 [%d]\n\nreplay options:\n", r.o.prefix);
+    fprintf(fp, "   --channels INT             channels of the flow cell = slots of the session [%d]\n", r.channels);
+    fprintf(fp, "   --chunk-samples INT        samples a channel sends per tick [%ld]\n", static_cast<long>(r.chunk_samples));
+    fprintf(fp, "   --norm-events INT          events the normalisation is frozen over, 25..q [the value of -q]\n");
+    fprintf(fp, "   --min-events INT           no early decision below this many query events [the value of -q]\n");
+    fprintf(fp, "   --min-mapq INT             decide early at this mapq; 61 = never [%d]\n", r.min_mapq);
+    fprintf(fp, "   --pace yes|no              sleep so that tick t does not start before t x chunk-samples / sampling_rate seconds;\n"
+                "                              changes the timing report on stderr only, never the output [no]\n\n"
+                "output: PAF as dtw prints it, then ne:i:<query events at the decision> ns:i:<samples sent> dc:A:<E|F|R>\n");
+}
+
 }  // namespace
+
+RealtimeOpt parse_realtime_options(int argc, char **argv) {
+    RealtimeOpt r;
+    Opt &o = r.o;
+    FILE *fp_help = stderr;
+    int c, li = 0;
+    bool secondary = false;
+    while ((c = getopt_long(argc, argv, "p:q:t:v:o:ahV", kRealtimeOptions, &li)) >= 0) {
+        switch (c) {
+            case 't': o.threads = atoi(optarg); if (o.threads < 1) die("Number of threads should larger than 0."); break;
+            case 'v': o.verbosity = atoi(optarg); break;
+            case 'V': fprintf(stdout, "sigfish-amd %s\n", sfa_version()); exit(EXIT_SUCCESS);
+            case 'h': fp_help = stdout; break;
+            case 'p': o.prefix = atoi(optarg); break;
+            case 'q': o.query = atoi(optarg); if (o.query < 1) die("Query size should larger than 0."); break;
+            case 'o': if (strcmp(optarg, "-") != 0 && !freopen(optarg, "wb", stdout)) die(std::string("failed to write the output to file ") + optarg); break;
+            case 'a': o.flag |= F_SAM; break;
+            case O_KMER_MODEL: o.model_file = optarg; break;
+            case O_RNA: o.flag |= F_RNA; break;
+            case O_DTW_STD: o.flag |= F_DTW; break;
+            case O_INVERT: o.flag |= F_INV; break;
+            case O_FROM_END: o.flag |= F_END; break;
+            case O_SECONDARY: secondary = yes_or_no(optarg, "secondary"); break;
+            case O_RANKS: o.ranks = atoi(optarg); break;
+            case O_PORE:
+                o.pore = optarg;
+                if (strcmp(optarg, "r9") && strcmp(optarg, "r10") && strcmp(optarg, "rna004")) die("Pore model should be r9, r10 or rna004");
+                if (!strcmp(optarg, "r10")) { o.flag |= F_R10; o.pore_flag = 1; }
+                if (!strcmp(optarg, "rna004")) { o.flag |= F_RNA | F_R10; o.pore_flag = 2; }
+                break;
+            case O_DEVICE: parse_device_list(optarg, &o.devices); break;
+            case O_CHANNELS: r.channels = atoi(optarg); if (r.channels < 1) die("--channels should be larger than 0"); break;
+            case O_CHUNK_SAMPLES: r.chunk_samples = parse_num(optarg); if (r.chunk_samples < 1 || r.chunk_samples > (1 << 20)) die("--chunk-samples should be 1..1048576"); break;
+            case O_NORM_EVENTS: r.norm_events = atoi(optarg); if (r.norm_events < 0) die("--norm-events should be 25..q"); break;
+            case O_MIN_EVENTS: r.min_events = atoi(optarg); if (r.min_events < 0) die("--min-events should not be negative"); break;
+            case O_MIN_MAPQ: r.min_mapq = atoi(optarg); break;
+            case O_PACE: r.pace = yes_or_no(optarg, "pace"); break;
+            default: realtime_help(stderr, r); exit(EXIT_FAILURE);
+        }
+    }
+    if (argc - optind != 2 || fp_help == stdout) {
+        realtime_help(fp_help, r);
+        exit(fp_help == stdout ? EXIT_SUCCESS : EXIT_FAILURE);
+    }
+    o.fasta = argv[optind];
+    o.blow5 = argv[optind + 1];
+    // what a session cannot do, by name (sfa_session_create would refuse some of it later, with a device open)
+    if (o.flag & F_DTW) die("realtime: --dtw-std is not available: a session extends the subsequence DTW");
+    if (o.flag & F_END) die("realtime: --from-end is not available: the end of a read is not known while it arrives");
+    if (o.prefix < 0) die("realtime: -p -1 (automatic query start) is not available: -p must be >= 0");
+    if (o.flag & F_SAM) die("realtime: --sam is not available: sessions keep no warp path");
+    if (secondary) die("realtime: --secondary yes is not available: sessions keep one row per slot");
+    if (o.ranks != 0) die("realtime: --ranks is not available: a replay is one process on one device");
+    if (o.devices.size() != 1) die("realtime: --device takes exactly one GPU: a session's rows live on one device");
+    if ((o.flag & F_INV) && !(o.flag & F_RNA)) die("Inversion is only available for RNA.");
+    if ((o.flag & F_RNA) && !(o.flag & F_INV)) die("realtime: --rna needs --invert: without it the query rows are the events reversed, and a session cannot take new events as row 0");
+    if (r.norm_events < 0) r.norm_events = o.query;
+    if (r.min_events < 0) r.min_events = o.query;
+    if (r.norm_events < 25 || r.norm_events > o.query) die("realtime: --norm-events should be 25..q (the value of -q)");
+    o.ranks = 1;
+    return r;
+}
 
 Opt parse_options(int argc, char **argv) {
     Opt o;

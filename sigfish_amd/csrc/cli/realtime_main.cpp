@@ -1,0 +1,266 @@
+// realtime_main.cpp -- `sigfish-amd realtime`: a BLOW5 file replayed through a raw-signal session as a flow cell would deliver
+// it (the schedule: replay.hpp), a PAF line at the moment a read is decided, and the time a tick takes against the signal time
+// it stands for.  The hot path is the library's (sfa_session_extend_raw: detector, frozen normalisation, sweep); what runs here
+// is the staging of a tick's samples, the decision rule and the printing.
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <future>
+#include <thread>
+
+#include "replay.hpp"
+#include "run.hpp"
+
+namespace cli {
+namespace {
+
+struct Context {  // destroyed on every way out, after the helper thread that decodes ahead
+    sfa_ctx_t *c = nullptr;
+    ~Context() { sfa_destroy(c); }
+};
+
+// Records of upcoming reads, decoded on the -t host threads ahead of need: at most `window` of them are decoded and waiting (or
+// being decoded), so the whole file is never resident.  The reader is touched by one helper at a time; the main thread only
+// collects what a helper has finished.
+class ReadAhead {
+  public:
+    ReadAhead(sfa::Blow5Reader &reader, WorkerPool &pool, size_t window) : reader_(reader), pool_(pool), window_(window) {}
+    // start decoding more when half the window is free and nothing is on its way
+    void top_up() {
+        if (pending_.valid() || eof_ || ready_.size() > window_ / 2) return;
+        const size_t want = window_ - ready_.size();
+        pending_ = std::async(std::launch::async, [this, want] { return fetch(want); });
+    }
+    // the next record of the file (false: there is none)
+    bool pop(sfa::Blow5Record *out) {
+        while (ready_.empty()) {
+            if (!pending_.valid()) {
+                if (eof_) return false;
+                top_up();
+            }
+            Fetched f = pending_.get();
+            eof_ = f.eof;
+            for (auto &r : f.recs) ready_.push_back(std::move(r));
+        }
+        *out = std::move(ready_.front());
+        ready_.pop_front();
+        return true;
+    }
+
+  private:
+    struct Fetched {
+        std::vector<sfa::Blow5Record> recs;
+        bool eof = false;
+    };
+    Fetched fetch(size_t want) {
+        Fetched f;
+        std::vector<const uint8_t *> view;
+        std::vector<size_t> size;
+        std::vector<std::vector<uint8_t>> mem;
+        while (view.size() < want) {
+            const uint8_t *v = nullptr;
+            size_t n = 0;
+            int rc = reader_.next_view(&v, &n);
+            if (rc == -2) {  // not mappable: copy the record
+                mem.emplace_back();
+                rc = reader_.next_mem(&mem.back());
+                n = mem.back().size();
+            }
+            if (rc < 0) die(reader_.error());
+            if (rc == 0) {
+                f.eof = true;
+                break;
+            }
+            view.push_back(v);
+            size.push_back(n);
+        }
+        for (size_t i = 0, m = 0; i < view.size(); ++i)
+            if (!view[i]) view[i] = mem[m++].data();  // (after the last emplace_back: the vectors no longer move)
+        f.recs.resize(view.size());
+        std::atomic<int> bad(0);
+        pool_.run(static_cast<int64_t>(view.size()), [&](int64_t i) {
+            std::string err;
+            if (!reader_.parse(view[i], size[i], &f.recs[i], &err)) bad = 1;
+        });
+        if (bad) die("error parsing a BLOW5 record");
+        return f;
+    }
+    sfa::Blow5Reader &reader_;
+    WorkerPool &pool_;
+    const size_t window_;
+    std::deque<sfa::Blow5Record> ready_;
+    bool eof_ = false;
+    std::future<Fetched> pending_;  // (last: its thread is joined before the queue goes)
+};
+
+// the reads on the channels, and where the schedule gets the next one from
+struct Channels {
+    ReadAhead &ahead;
+    std::vector<sfa::Blow5Record> rec;
+    int64_t reads = 0, samples_in_file = 0;
+    double sampling_rate = 0;  // of the first read
+    bool take(int32_t channel, int64_t *n_samples) {
+        if (!ahead.pop(&rec[channel])) return false;
+        if (reads++ == 0) sampling_rate = rec[channel].sampling_rate;
+        samples_in_file += static_cast<int64_t>(rec[channel].raw.size());
+        *n_samples = static_cast<int64_t>(rec[channel].raw.size());
+        return true;
+    }
+};
+
+struct Report {
+    int64_t lines[3] = {0, 0, 0};  // E, F, R
+    int64_t unmapped = 0, decided = 0, sum_ne = 0, samples_sent = 0;
+    std::vector<double> tick_s;
+    void print(const RealtimeOpt &r, const Channels &ch, double tick_signal_s) const {
+        std::vector<double> t = tick_s;
+        std::sort(t.begin(), t.end());
+        const size_t n = t.size();
+        double sum = 0;
+        for (double x : t) sum += x;
+        auto pct = [&](double p) { return n ? t[std::min(n - 1, static_cast<size_t>(p * static_cast<double>(n)))] : 0.0; };
+        int64_t over = 0;
+        for (double x : t) over += tick_signal_s > 0 && x > tick_signal_s;
+        fprintf(stderr, "[realtime] reads: %ld\tlines: %ld early (E), %ld full (F), %ld at the end of the read (R)\tunmapped: %ld\n", (long)ch.reads,
+                (long)lines[0], (long)lines[1], (long)lines[2], (long)unmapped);
+        fprintf(stderr, "[realtime] mean query events at decision (ne): %.1f\n", decided ? static_cast<double>(sum_ne) / static_cast<double>(decided) : 0.0);
+        fprintf(stderr, "[realtime] samples sent: %ld of %ld in the file (%.1f%% not sent)\n", (long)samples_sent, (long)ch.samples_in_file,
+                ch.samples_in_file ? 100.0 * static_cast<double>(ch.samples_in_file - samples_sent) / static_cast<double>(ch.samples_in_file) : 0.0);
+        fprintf(stderr, "[realtime] ticks: %zu of %ld samples on %d channels\ttick wall time: mean %.6f s, median %.6f s, p99 %.6f s, max %.6f s\n", n,
+                (long)r.chunk_samples, r.channels, n ? sum / static_cast<double>(n) : 0.0, pct(0.5), pct(0.99), n ? t[n - 1] : 0.0);
+        if (tick_signal_s > 0)
+            fprintf(stderr, "[realtime] a tick is %.6f s of signal (%ld samples at %.0f Hz); %ld tick(s) took longer\n", tick_signal_s, (long)r.chunk_samples,
+                    ch.sampling_rate, (long)over);
+        else
+            fprintf(stderr, "[realtime] the file gives no sampling rate: a tick's signal time is unknown\n");
+    }
+};
+
+int realtime_run(int argc, char **argv, double t0) {
+    RealtimeOpt r = parse_realtime_options(argc, argv);
+    Opt &o = r.o;
+    sfa::Blow5Reader reader;
+    if (!reader.open(o.blow5)) die(reader.error());
+    detect_chemistry(reader, &o);
+    if ((o.flag & F_RNA) && !(o.flag & F_INV)) die("realtime: the file holds direct RNA: pass --rna --invert (a session cannot take the query reversed)");
+    const Reference ref(o);
+    Context ctx;
+    if (sfa_init(&ctx.c, &ref.view, o.flag, o.devices[0]) != SFA_OK) die(std::string("accelerator init failed: ") + sfa_last_error());
+    if (sfa_set_pore(ctx.c, o.pore_flag) != SFA_OK) die(sfa_last_error());
+    sfa_session_t *se = nullptr;  // (freed with its context)
+    if (sfa_session_create(ctx.c, r.channels, 0, &se) != SFA_OK) die(std::string("session: ") + sfa_last_error());
+    if (sfa_session_raw_config(se, o.prefix, r.norm_events, o.query) != SFA_OK) die(std::string("session: ") + sfa_last_error());
+    if (o.verbosity >= 4)
+        fprintf(stderr, "[realtime::%.3f] initialised: %d channels, %ld samples per tick, skip %d, norm %d, query %d, early at %d events and mapq %d\n", realtime() - t0,
+                r.channels, (long)r.chunk_samples, o.prefix, r.norm_events, o.query, r.min_events, r.min_mapq);
+
+    const int32_t C = r.channels;
+    WorkerPool pool(o.threads);
+    reader.start_prefault();
+    ReadAhead ahead(reader, pool, 2 * static_cast<size_t>(C));
+    Channels ch{ahead, std::vector<sfa::Blow5Record>(C)};
+    replay::Schedule sch(C, r.chunk_samples);
+    const replay::Rule rule{r.min_events, r.min_mapq};
+    Report rep;
+
+    double t_pin = 0;
+    PinnedBuffer raw("sample");
+    raw.grow(sizeof(int16_t) * (static_cast<size_t>(C) * static_cast<size_t>(r.chunk_samples) + 1), &t_pin);
+    std::vector<int32_t> slot(C), decided_slot;
+    std::vector<int64_t> raw_off(C + 1);
+    std::vector<double> scaling(3 * static_cast<size_t>(C));
+    std::vector<uint8_t> end(C);
+    std::vector<sfa_result_t> rows(C);
+    std::vector<sfa_session_raw_info_t> info(C);
+    std::vector<char> reason(C), line(C);
+    std::vector<uint64_t> span_a(C), span_b(C);
+    std::string text(4096, '\0');
+
+    ahead.top_up();
+    sch.start(ch);
+    const auto start = std::chrono::steady_clock::now();
+    while (sch.busy()) {
+        if (r.pace && ch.sampling_rate > 0)  // (stderr timing only: nothing below reads a clock to decide anything)
+            std::this_thread::sleep_until(start + std::chrono::duration<double>(static_cast<double>(sch.tick()) * static_cast<double>(r.chunk_samples) / ch.sampling_rate));
+        const double a = realtime();
+        ahead.top_up();  // decodes beside this tick's call
+        const std::vector<replay::Entry> &es = sch.begin_tick();
+        const int32_t n = static_cast<int32_t>(es.size());
+        int16_t *dst = static_cast<int16_t *>(raw.data());
+        raw_off[0] = 0;
+        for (int32_t i = 0; i < n; ++i) {
+            const replay::Entry &e = es[i];
+            const sfa::Blow5Record &rec = ch.rec[e.channel];
+            slot[i] = e.channel;
+            if (e.count) memcpy(dst + raw_off[i], rec.raw.data() + e.first, sizeof(int16_t) * static_cast<size_t>(e.count));
+            raw_off[i + 1] = raw_off[i] + e.count;
+            scaling[3 * i] = rec.digitisation, scaling[3 * i + 1] = rec.offset, scaling[3 * i + 2] = rec.range;
+            end[i] = e.end ? 1 : 0;
+            rep.samples_sent += e.count;
+        }
+        if (sfa_session_extend_raw(se, slot.data(), dst, raw_off.data(), scaling.data(), end.data(), n, rows.data(), info.data()) != SFA_OK)
+            die(std::string("tick ") + std::to_string(sch.tick()) + ": " + sfa_last_error());
+        decided_slot.clear();
+        for (int32_t i = 0; i < n; ++i) {
+            replay::Status s;
+            s.calibrated = info[i].status & 1, s.full = info[i].status & 2, s.ended = info[i].status & 4, s.poisoned = info[i].status & 8;
+            s.mapped = rows[i].valid && rows[i].rid >= 0;
+            s.q_events = info[i].q_events;
+            s.mapq = rows[i].mapq;
+            reason[i] = replay::decide(rule, s);
+            line[i] = reason[i] && s.mapped;
+            if (reason[i]) decided_slot.push_back(slot[i]);
+        }
+        const int32_t nd = static_cast<int32_t>(decided_slot.size());
+        if (nd > 0) {
+            if (sfa_session_query_span(se, decided_slot.data(), nd, span_a.data(), span_b.data()) != SFA_OK) die(std::string("query span: ") + sfa_last_error());
+            for (int32_t i = 0, d = 0; i < n; ++i) {  // ascending channels
+                if (!reason[i]) continue;
+                const int32_t k = d++;
+                ++rep.decided;
+                rep.sum_ne += info[i].q_events;
+                if (!line[i]) {
+                    ++rep.unmapped;
+                    continue;
+                }
+                const sfa::Blow5Record &rec = ch.rec[slot[i]];
+                const sfa_result_t &w = rows[i];
+                // query_size as dtw passes it: last query event - first (src/sigfish.c:801-807)
+                int len = sfa_paf_row(&text[0], text.size(), &w, rec.read_id.c_str(), ref.contigs[w.rid].name.c_str(), span_a[k], span_b[k],
+                                      static_cast<uint64_t>(info[i].q_events - 1), rec.raw.size(), static_cast<uint64_t>(ref.seq_len[w.rid]));
+                if (len > 0) {
+                    const int more = snprintf(&text[len - 1], text.size() - static_cast<size_t>(len - 1), "\tne:i:%ld\tns:i:%ld\tdc:A:%c\n", (long)info[i].q_events,
+                                              (long)info[i].n_samples, reason[i]);
+                    len = (more < 0 || static_cast<size_t>(len - 1 + more) >= text.size()) ? -1 : len - 1 + more;
+                }
+                if (len < 0) die("PAF line too long");
+                fwrite(text.data(), 1, static_cast<size_t>(len), stdout);
+                ++rep.lines[reason[i] == 'E' ? 0 : reason[i] == 'F' ? 1 : 2];
+            }
+            fflush(stdout);  // a line is out at the moment of its decision
+            if (sfa_session_reset(se, decided_slot.data(), nd) != SFA_OK) die(std::string("reset: ") + sfa_last_error());
+        }
+        sch.end_tick(reason, line, ch);
+        rep.tick_s.push_back(realtime() - a);
+    }
+    if (o.verbosity >= 3) rep.print(r, ch, ch.sampling_rate > 0 ? static_cast<double>(r.chunk_samples) / ch.sampling_rate : 0.0);
+    return 0;
+}
+
+}  // namespace
+}  // namespace cli
+
+int realtime_main(int argc, char **argv) {
+    using namespace cli;
+    const double t0 = realtime();
+    try {
+        return realtime_run(argc, argv, t0);
+    } catch (const Fatal &e) {  // the helper that decodes ahead has been joined by the unwinding
+        fflush(stdout);
+        fprintf(stderr, "[sigfish-amd] ERROR: %s\n", e.what());
+        return EXIT_FAILURE;
+    }
+}

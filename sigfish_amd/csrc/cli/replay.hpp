@@ -1,0 +1,123 @@
+// replay.hpp -- the schedule of `sigfish-amd realtime`: which read is on which channel, which samples go out at which tick,
+// what happens on a decision.  No device call and no file here: the run (realtime_main.cpp) and tests/c/replay_schedule.cpp
+// drive it, the latter with a stub in place of the session.  Python twin: sigfish_amd/realtime.py (Schedule, decide); both
+// print the same trace, line for line.
+//
+// The schedule is defined on ticks, never on wall-clock time:
+//   setup     read i of the file goes to channel i, i < channels
+//   tick t    every busy channel sends the next chunk_samples samples of its read, channels in ascending order, in ONE call.
+//             A chunk shorter than chunk_samples (empty when the read's length is a multiple of it) is the read's last and
+//             carries end_of_read
+//   decision  after the call every named channel is tested (decide()): early, full, end of read
+//   after it  decided channels are reset in one call and each takes the next unread record of the file, lowest channel
+//             first, from tick t + 1 on; what is left of a decided read is never sent
+//   the end   no channel is busy
+#pragma once
+#include <cstdint>
+#include <cstdio>
+#include <vector>
+
+namespace cli {
+namespace replay {
+
+// what the decision rule reads of a channel's row and raw info after a call
+struct Status {
+    bool calibrated = false, full = false, ended = false, poisoned = false;
+    bool mapped = false;  // the row is valid and names a contig
+    int64_t q_events = 0;
+    int mapq = 0;
+};
+
+struct Rule {
+    int64_t min_events;
+    int min_mapq;
+};
+
+// 'E' early, 'F' full, 'R' end of read (a poisoned slot as well: it can never have a row), 0: the read goes on.
+// A decision prints a line when the row is mapped; 'E' always is.
+inline char decide(const Rule &r, const Status &s) {
+    if (s.calibrated && s.q_events >= r.min_events && s.mapped && s.mapq >= r.min_mapq) return 'E';
+    if (s.full) return 'F';
+    if (s.ended || s.poisoned) return 'R';
+    return 0;
+}
+
+// one channel's part of a tick's call
+struct Entry {
+    int32_t channel;
+    int64_t read;          // position of the read in the file
+    int64_t first, count;  // samples [first, first + count) of it
+    bool end;              // end_of_read
+};
+
+// Source: bool take(int32_t channel, int64_t *n_samples) -- the next unread record of the file goes to `channel`
+// (false: the file has no more).  The schedule numbers the records in the order it takes them.
+class Schedule {
+  public:
+    Schedule(int32_t channels, int64_t chunk_samples, FILE *trace = nullptr) : chunk_(chunk_samples), trace_(trace), ch_(channels) {}
+
+    template <class Source>
+    void start(Source &src) {
+        for (int32_t c = 0; c < static_cast<int32_t>(ch_.size()); ++c)
+            if (!take(c, src)) break;
+    }
+    bool busy() const { return n_busy_ > 0; }
+    int64_t tick() const { return tick_; }
+    int64_t reads_taken() const { return next_read_; }
+    int64_t sent(int32_t channel) const { return ch_[channel].sent; }
+    int64_t length(int32_t channel) const { return ch_[channel].len; }
+
+    // the entries of the next call, ascending channels; their samples count as sent
+    const std::vector<Entry> &begin_tick() {
+        entries_.clear();
+        for (int32_t c = 0; c < static_cast<int32_t>(ch_.size()); ++c) {
+            Channel &k = ch_[c];
+            if (k.read < 0) continue;
+            const int64_t left = k.len - k.sent, n = left < chunk_ ? left : chunk_;
+            entries_.push_back(Entry{c, k.read, k.sent, n, n < chunk_});
+            k.sent += n;
+            if (trace_)
+                fprintf(trace_, "tick %ld send ch=%d read=%ld first=%ld n=%ld end=%d\n", (long)tick_, c, (long)k.read, (long)entries_.back().first, (long)n, n < chunk_ ? 1 : 0);
+        }
+        return entries_;
+    }
+
+    // reason[i] (decide()) and line[i] for entry i of begin_tick(); decided channels take the next records, lowest channel first
+    template <class Source>
+    void end_tick(const std::vector<char> &reason, const std::vector<char> &line, Source &src) {
+        for (size_t i = 0; i < entries_.size(); ++i) {
+            if (!reason[i]) continue;
+            const Entry &e = entries_[i];
+            if (trace_)
+                fprintf(trace_, "tick %ld decide ch=%d read=%ld reason=%c line=%d sent=%ld\n", (long)tick_, e.channel, (long)e.read, reason[i], line[i] ? 1 : 0, (long)ch_[e.channel].sent);
+            ch_[e.channel].read = -1;
+            --n_busy_;
+        }
+        for (size_t i = 0; i < entries_.size(); ++i)
+            if (reason[i] && !take(entries_[i].channel, src)) break;
+        ++tick_;
+    }
+
+  private:
+    struct Channel {
+        int64_t read = -1, len = 0, sent = 0;
+    };
+    template <class Source>
+    bool take(int32_t c, Source &src) {
+        int64_t len = 0;
+        if (!src.take(c, &len)) return false;
+        ch_[c] = Channel{next_read_++, len, 0};
+        ++n_busy_;
+        if (trace_) fprintf(trace_, "tick %ld take ch=%d read=%ld len=%ld\n", (long)tick_, c, (long)ch_[c].read, (long)len);
+        return true;
+    }
+    const int64_t chunk_;
+    FILE *trace_;
+    std::vector<Channel> ch_;
+    std::vector<Entry> entries_;
+    int64_t tick_ = 0, next_read_ = 0;
+    int32_t n_busy_ = 0;
+};
+
+}  // namespace replay
+}  // namespace cli

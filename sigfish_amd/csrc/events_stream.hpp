@@ -348,4 +348,28 @@ __global__ void __launch_bounds__(64) ev_stream_norm_kernel(const EvNormArgs a) 
     }
 }
 
+// sfa_session_query_span: the raw coordinates of a slot's query, gathered from its event table.  One lane per named slot, two
+// records each; q_events comes from the host (0: the slot is not calibrated, or has been reset since -- its table is stale).
+struct EvSpanArgs {
+    const int32_t *slot;     // [n]
+    const int32_t *q_events; // [n] query events swept
+    const EvRecord *events;  // [n_slots][ev_cap]
+    uint64_t *span;          // [n][2] start of event skip | start + length of event skip + q_events - 1
+    int32_t n, ev_cap, skip, query_cap;
+};
+
+__global__ void __launch_bounds__(64) ev_query_span_kernel(const EvSpanArgs a) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= a.n) return;
+    const int q = min(a.q_events[i], a.query_cap);
+    uint64_t first = 0, last = 0;
+    if (q > 0) {
+        const EvRecord *ev = a.events + static_cast<int64_t>(a.slot[i]) * a.ev_cap + a.skip;
+        first = ev[0].start;
+        last = ev[q - 1].start + static_cast<uint64_t>(ev[q - 1].length);
+    }
+    a.span[2 * i] = first;
+    a.span[2 * i + 1] = last;
+}
+
 }  // namespace sfa

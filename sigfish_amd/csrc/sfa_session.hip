@@ -41,6 +41,8 @@ struct sfa_session {
     DevBuf d_raw, d_rstage, d_rout;    // of a call: samples, entry tables, EvStreamOut per entry
     PinBuf h_rstage, h_rout;
     Event ev_raw[3];                   // detector start / end, normalisation end
+    DevBuf d_span_in, d_span;          // of a sfa_session_query_span call: [slot n | q_events n] x i32, [n][2] u64
+    PinBuf h_span_in, h_span;
 };
 
 namespace {
@@ -483,6 +485,45 @@ int64_t sfa_session_events(sfa_session_t *s, int32_t slot, int64_t first, sfa_ev
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return nev;
+}
+
+int sfa_session_query_span(sfa_session_t *s, const int32_t *slot, int32_t n, uint64_t *start_raw, uint64_t *end_raw) {
+    if (!s || n < 0 || (n > 0 && (!slot || !start_raw || !end_raw))) return fail(SFA_EINVAL, "sfa_session_query_span: bad argument");
+    if (!s->raw) return fail(SFA_EINVAL, "sfa_session_query_span: the session is not in raw mode (sfa_session_raw_config): it holds no event tables");
+    for (int32_t i = 0; i < n; ++i)
+        if (slot[i] < 0 || slot[i] >= s->n_slots) return fail(SFA_EINVAL, "sfa_session_query_span: slot %d out of range (the session has %d)", slot[i], s->n_slots);
+    if (n == 0) return SFA_OK;
+    sfa_ctx *c = s->c;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t nn = static_cast<size_t>(n);
+    if (int rc = reserve_all(s->h_span_in, 8 * nn, s->d_span_in, 8 * nn, s->d_span, 16 * nn, s->h_span, 16 * nn)) return rc;
+    int32_t *h = s->h_span_in.as<int32_t>();
+    for (int32_t i = 0; i < n; ++i) {  // (a slot reset since its last chunk has a stale table and no query)
+        const int32_t sl = slot[i];
+        h[i] = sl;
+        h[nn + i] = (!s->raw_fresh[sl] && (s->raw_status[sl] & sfa::kRawCalibrated)) ? static_cast<int32_t>(s->len[sl]) : 0;
+    }
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemcpyAsync(s->d_span_in.p, h, 8 * nn, hipMemcpyHostToDevice, st));
+    sfa::EvSpanArgs a;
+    a.slot = s->d_span_in.as<int32_t>();
+    a.q_events = a.slot + nn;
+    a.events = s->d_evtab.as<sfa::EvRecord>();
+    a.span = s->d_span.as<uint64_t>();
+    a.n = n;
+    a.ev_cap = s->skip + s->query;
+    a.skip = s->skip;
+    a.query_cap = s->query;
+    hipLaunchKernelGGL(sfa::ev_query_span_kernel, dim3((n + 63) / 64), dim3(64), 0, st, a);
+    KERNEL_TRY();
+    HIP_TRY(hipMemcpyAsync(s->h_span.p, s->d_span.p, 16 * nn, hipMemcpyDeviceToHost, st));
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "sfa_session_query_span: the gather failed: %s", hipGetErrorString(hipGetLastError()));
+    const uint64_t *sp = s->h_span.as<uint64_t>();
+    for (int32_t i = 0; i < n; ++i) {
+        start_raw[i] = sp[2 * i];
+        end_raw[i] = sp[2 * i + 1];
+    }
+    return SFA_OK;
 }
 
 int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t *raw, const int64_t *raw_off, const double *scaling,

@@ -1,0 +1,147 @@
+"""The replay of `sigfish-amd realtime` in Python: reads go through a raw-signal Session as a flow cell would deliver them.
+
+Twin of sigfish_amd/csrc/cli/replay.hpp (the schedule and the decision rule) and cli/realtime_main.cpp (the run): the same
+ticks, the same calls, the same lines.  The schedule counts ticks, never seconds.
+
+  setup     read i goes to channel i, i < channels
+  tick t    every busy channel sends the next chunk_samples samples of its read, ascending channels, in ONE extend_raw call; a
+            chunk shorter than chunk_samples (empty when the read's length is a multiple of it) is the last and carries the end
+  decision  decide(): 'E' early (calibrated, q_events >= min_events, mapped, mapq >= min_mapq), 'F' full, 'R' end of read (or a
+            poisoned slot); a decision has a line when its row is mapped
+  after it  decided channels are reset in one call and take the next unread reads, lowest channel first, from tick t + 1 on
+"""
+import numpy as np
+
+from . import api
+
+
+def mapped(row):
+    return bool(row["valid"]) and int(row["rid"]) >= 0
+
+
+def decide(row, info, min_events, min_mapq):
+    """'E', 'F', 'R' or None for one channel after a call (replay::decide)."""
+    st = int(info["status"])
+    if st & api.RAW_CALIBRATED and int(info["q_events"]) >= min_events and mapped(row) and int(row["mapq"]) >= min_mapq:
+        return "E"
+    if st & api.RAW_FULL:
+        return "F"
+    if st & (api.RAW_ENDED | api.RAW_POISONED):
+        return "R"
+    return None
+
+
+class Schedule:
+    """replay::Schedule: which read is on which channel and which samples go out at which tick.  `source.take(channel)` puts the
+    next unread record of the file on the channel and returns its length (None: the file has no more); `trace`, a list, receives
+    the lines the C++ schedule prints."""
+
+    def __init__(self, channels, chunk_samples, trace=None):
+        self.chunk, self.trace = int(chunk_samples), trace
+        self.read, self.len, self.sent = [-1] * channels, [0] * channels, [0] * channels
+        self.tick, self.next_read, self.entries = 0, 0, []
+
+    def _take(self, c, source):
+        n = source.take(c)
+        if n is None:
+            return False
+        self.read[c], self.len[c], self.sent[c] = self.next_read, int(n), 0
+        self.next_read += 1
+        if self.trace is not None:
+            self.trace.append(f"tick {self.tick} take ch={c} read={self.read[c]} len={self.len[c]}")
+        return True
+
+    def start(self, source):
+        for c in range(len(self.read)):
+            if not self._take(c, source):
+                break
+
+    def busy(self):
+        return any(r >= 0 for r in self.read)
+
+    def begin_tick(self):
+        """[(channel, read, first, count, end)], ascending channels; the samples count as sent"""
+        self.entries = []
+        for c, r in enumerate(self.read):
+            if r < 0:
+                continue
+            n = min(self.chunk, self.len[c] - self.sent[c])
+            self.entries.append((c, r, self.sent[c], n, n < self.chunk))
+            self.sent[c] += n
+            if self.trace is not None:
+                self.trace.append(f"tick {self.tick} send ch={c} read={r} first={self.entries[-1][2]} n={n} end={int(n < self.chunk)}")
+        return self.entries
+
+    def end_tick(self, reason, line, source):
+        for (c, r, _, _, _), why, ln in zip(self.entries, reason, line):
+            if not why:
+                continue
+            if self.trace is not None:
+                self.trace.append(f"tick {self.tick} decide ch={c} read={r} reason={why} line={int(bool(ln))} sent={self.sent[c]}")
+            self.read[c] = -1
+        for (c, _, _, _, _), why in zip(self.entries, reason):
+            if why and not self._take(c, source):
+                break
+        self.tick += 1
+
+
+def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None):
+    """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
+
+    reads: iterable of (read_id, meta, samples) in file order, as Blow5File yields them (taken lazily: at most `channels` reads are
+    held).  row / info: the channel's entries of Session.extend_raw at the decision; span: (start_raw, end_raw) of
+    Session.query_span; reason: 'E', 'F' or 'R'.  A decision has a line when mapped(row): format_line().  `session`: an object with
+    extend_raw / query_span / reset in place of aligner.session(channels) in raw mode (the schedule's tests pass a stub)."""
+    reads = iter(reads)
+    on = [None] * channels  # (index, read_id, meta, samples) per channel
+
+    class Source:
+        index = 0
+
+        def take(self, channel):
+            nxt = next(reads, None)
+            if nxt is None:
+                return None
+            raw = np.ascontiguousarray(nxt[2], np.int16).reshape(-1)
+            on[channel] = (self.index, nxt[0], nxt[1], raw)
+            self.index += 1
+            return len(raw)
+
+    src = Source()
+    sch = Schedule(channels, chunk_samples, trace)
+    own = session is None
+    se = aligner.session(channels) if own else session
+    try:
+        if own:
+            se.configure_raw(skip, norm, query)
+        sch.start(src)
+        while sch.busy():
+            es = sch.begin_tick()
+            slots = [e[0] for e in es]
+            chunks = [on[c][3][first:first + n] for c, _, first, n, _ in es]
+            raw_off = np.concatenate([[0], np.cumsum([len(x) for x in chunks])]).astype(np.int64)
+            scaling = [(on[c][2]["digitisation"], on[c][2]["offset"], on[c][2]["range"]) for c in slots]
+            rows, info = se.extend_raw(slots, np.concatenate(chunks) if chunks else np.zeros(0, np.int16), raw_off, scaling, [e[4] for e in es])
+            reason = [decide(rows[i], info[i], min_events, min_mapq) for i in range(len(es))]
+            line = [bool(why) and mapped(rows[i]) for i, why in enumerate(reason)]
+            decided = [i for i, why in enumerate(reason) if why]
+            if decided:
+                d_slots = [slots[i] for i in decided]
+                a, b = se.query_span(d_slots)
+                for k, i in enumerate(decided):
+                    yield sch.tick, slots[i], on[slots[i]][0], rows[i].copy(), info[i].copy(), (int(a[k]), int(b[k])), reason[i]
+                se.reset(d_slots)
+            sch.end_tick(reason, line, src)
+    finally:
+        if own:
+            se.close()
+
+
+def format_line(read_id, n_samples, names, seq_lengths, row, info, span, reason):
+    """The line `sigfish-amd realtime` prints for a decision, or "" when its row is not mapped: paf_row (query_size as dtw passes
+    it, last query event - first), then ne:i:<query events> ns:i:<samples sent> dc:A:<reason>.  n_samples: of the whole read."""
+    if not mapped(row):
+        return ""
+    rid = int(row["rid"])
+    base = api.paf_row(row, read_id, names[rid], span[0], span[1], int(info["q_events"]) - 1, int(n_samples), int(seq_lengths[rid]))
+    return f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}\n"

@@ -206,3 +206,72 @@ def make_rna_polya_reads(n_reads, seed=0, pore=0, kinds=None, body=(5_000, 40_00
             scale_rng = 1e39
         out.append((f"polya_{seed}_{r}_{kind}", dig, off, scale_rng, 3000.0, raw))
     return out
+
+
+# ---- raw DNA reads and a BLOW5 file of them (the replay of `sigfish-amd realtime`, tools/realtime_replay.py) ---------------
+R9_DNA_META = dict(digitisation=8192.0, offset=6.0, range=1467.61, sampling_rate=4000.0)
+RAW_DNA_KINDS = ("mapped", "random", "stalled", "flat")
+
+
+def make_dna_raw_reads(records, level_mean, k, n_reads, seed=0, samples=(2000, 9000), dwell=(6, 13), noise=1.5, kinds=("mapped",), meta=R9_DNA_META):
+    """Seeded raw DNA reads [(read_id, digitisation, offset, range, sampling_rate, int16 samples)] over [(name, sequence)] and a
+    4^k table of level means (pA).  Read r is of kind kinds[r % len(kinds)]:
+      mapped  the levels of consecutive k-mers from a random (contig, strand, start), each held for dwell[0] .. dwell[1] - 1
+              samples, plus N(0, noise); behind the contig's end the read goes on with random k-mers
+      random  random k-mers all the way: a signal that belongs nowhere
+      stalled random k-mers for 200 .. 330 samples, then one level without noise: the events stop long before the read does
+      flat    one level, no noise: the detector finds no event"""
+    rng = np.random.default_rng(seed)
+    lv = np.asarray(level_mean, np.float32)
+    code = np.full(256, 0, np.int64)
+    for i, c in enumerate("ACGT"):
+        code[ord(c)] = i
+    comp = str.maketrans("ACGT", "TGCA")
+    w = 4 ** np.arange(k - 1, -1, -1)
+
+    def kmers(seq):
+        b = code[np.frombuffer(seq.encode(), np.uint8)]
+        return np.lib.stride_tricks.sliding_window_view(b, k) @ w
+
+    fwd = [kmers(s.upper()) for _, s in records]
+    rev = [kmers(s.upper().translate(comp)[::-1]) for _, s in records]
+    lens = np.array([len(x) for x in fwd], np.float64)
+    out = []
+    for r in range(n_reads):
+        kind = kinds[r % len(kinds)]
+        n = int(rng.integers(samples[0], samples[1] + 1))
+        d = rng.integers(dwell[0], dwell[1], n // dwell[0] + 2)
+        idx = rng.integers(0, len(lv), len(d))
+        if kind == "mapped":
+            c = int(rng.choice(len(fwd), p=lens / lens.sum()))
+            along = (rev if rng.integers(0, 2) else fwd)[c]
+            at = int(rng.integers(0, max(len(along) - 100, 1)))
+            m = min(len(along) - at, len(d))
+            idx[:m] = along[at:at + m]
+        pa = np.full(n, lv[idx[0]], np.float64) if kind == "flat" else np.repeat(lv[idx].astype(np.float64), d)[:n]
+        if kind != "flat":
+            pa = pa + rng.normal(0, noise, n)
+        if kind == "stalled":
+            pa[int(rng.integers(200, 331)):] = lv[idx[-1]]
+        raw = np.clip(np.round(pa * meta["digitisation"] / meta["range"] - meta["offset"]), -32768, 32767).astype(np.int16)
+        out.append((f"raw_{seed}_{r}_{kind}", meta["digitisation"], meta["offset"], meta["range"], meta["sampling_rate"], raw))
+    return out
+
+
+def write_blow5(path, reads, attrs=(("experiment_type", "genomic_dna"), ("sequencing_kit", "unknown"))):
+    """An uncompressed BLOW5 file (layout: csrc/host/blow5.hpp) of reads = [(read_id, digitisation, offset, range, sampling_rate,
+    int16 samples)], as make_dna_raw_reads and make_rna_polya_reads return them."""
+    import struct
+    text = "".join(f"@{k}\t{v}\n" for k, v in attrs)
+    text += "#char*\tuint32_t\tdouble\tdouble\tdouble\tdouble\tuint64_t\tint16_t*\n"
+    text += "#read_id\tread_group\tdigitisation\toffset\trange\tsampling_rate\tlen_raw_signal\traw_signal\n"
+    hdr = b"BLOW5\x01" + bytes([0, 2, 0, 0]) + struct.pack("<I", 1) + bytes([0])
+    hdr += b"\0" * (64 - len(hdr)) + struct.pack("<I", len(text)) + text.encode()
+    with open(path, "wb") as out:
+        out.write(hdr)
+        for rid, dig, off, rng_, rate, raw in reads:
+            name = rid.encode()
+            raw = np.ascontiguousarray(raw, np.int16)
+            payload = struct.pack("<H", len(name)) + name + struct.pack("<I4dQ", 0, dig, off, rng_, rate, len(raw)) + raw.tobytes()
+            out.write(struct.pack("<Q", len(payload)) + payload)
+        out.write(b"5WOLB")
