@@ -226,6 +226,15 @@ int sfa_session_reset(sfa_session_t *s, const int32_t *slot, int32_t n);
 /* len[i] = events slot[i] has received since its last reset (slot == NULL: all slots in order, n must be n_slots). */
 int sfa_session_lengths(sfa_session_t *s, const int32_t *slot, int32_t n, int64_t *len);
 
+/* The carried row of (slot, contig, strand_char '+' or '-') read back: cost[j] = accumulated cost of the last query row at column
+ * j of that strand's array, start[j] (start may be NULL) = the column in which the path into that cell begins.  Both are given as
+ * stored: columns of the strand's OWN array, before the flip of '-' and before ref_st_offset that the rows of sfa_session_extend
+ * have applied.  Returns the number of columns (the contig's ref_length); the caller's arrays hold at least that many.  A
+ * device-to-host copy on the context's stream, blocking; for checking and debugging, not for the hot path.  SFA_EINVAL: a slot,
+ * contig or strand that does not exist (SFA_RNA has no '-'), start != NULL on a SFA_SESSION_NO_START session, a slot without
+ * events, a poisoned slot. */
+int64_t sfa_session_row(sfa_session_t *s, int32_t slot, int32_t contig, int32_t strand_char, float *cost, int32_t *start);
+
 void sfa_session_destroy(sfa_session_t *s);
 
 /* Device memory sfa_session_create takes for the carried rows of n_slots slots over a reference of total_columns columns

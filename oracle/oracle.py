@@ -69,6 +69,7 @@ def lib():
                                          _f32p, _i32p]
         L.orc_gen_ref_record.restype = C.c_int32
         L.orc_dtw_single.argtypes = [_f32p, C.c_int32, C.POINTER(RefC), C.c_uint32, C.POINTER(Result)]
+        L.orc_last_row.argtypes = [_f32p, C.c_int32, _f32p, C.c_int32, C.c_uint32, _f32p, _i32p]
         L.orc_align_batch.argtypes = [_f32p, C.POINTER(C.c_int64), C.c_int32, C.POINTER(RefC), C.c_uint32,
                                       C.c_int32, C.c_void_p]
         L.orc_mapq.argtypes = [C.c_float, C.c_float]
@@ -206,6 +207,26 @@ def align_batch(events, q_off, ref, flag, threads=1):
     rc = ref.as_c()
     lib().orc_align_batch(_fp(ev), q_off.ctypes.data_as(C.POINTER(C.c_int64)), n, C.byref(rc), flag, threads,
                           out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def last_row(events, y, flag):
+    """The last query row of `events` (event order) against ONE strand array y: (cost float32[len(y)], start int32[len(y)]),
+    start[j] = path_start(matrix, j) for every column, each backtracked on its own (orc_last_row)."""
+    ev, y = _f32(events), _f32(y)
+    cost, start = np.empty(len(y), np.float32), np.empty(len(y), np.int32)
+    lib().orc_last_row(_fp(ev), len(ev), _fp(y), len(y), flag, _fp(cost), start.ctypes.data_as(_i32p))
+    return cost, start
+
+
+def last_rows(events, ref, flag):
+    """last_row for every (contig, strand) of `ref` in processing order (sigfish.c:868-952: per contig '+', then '-' for DNA).
+    -> [(contig, strand char, cost, start)]"""
+    out = []
+    for c in range(ref.num_ref):
+        out.append((c, "+") + last_row(events, ref.forward[c], flag))
+        if not flag & RNA:
+            out.append((c, "-") + last_row(events, ref.reverse[c], flag))
     return out
 
 

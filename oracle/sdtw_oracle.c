@@ -259,6 +259,30 @@ uint8_t orc_mapq(float score, float score2) {
     return (uint8_t)q;
 }
 
+/* ---- src/sigfish.c:857-866: the query rows of a read's events ---- */
+static float *query_rows(const float *events, int32_t qlen, uint32_t flag) {
+    float *query = (float *)malloc(sizeof(float) * qlen);
+    for (int32_t j = 0; j < qlen; j++) {
+        if ((flag & ORC_RNA) && !(flag & ORC_INV))
+            query[qlen - 1 - j] = events[j]; /* sigfish.c:861-863 */
+        else
+            query[j] = events[j];
+    }
+    return query;
+}
+
+/* the last row of one (read, strand array) matrix and the traceback from every one of its columns */
+void orc_last_row(const float *events, int32_t qlen, const float *y, int32_t rlen, uint32_t flag, float *cost_out,
+                  int32_t *start) {
+    float *query = query_rows(events, qlen, flag);
+    float *cost = (float *)malloc(sizeof(float) * (size_t)qlen * rlen);
+    orc_subsequence(query, y, qlen, rlen, cost);
+    memcpy(cost_out, cost + (size_t)(qlen - 1) * rlen, sizeof(float) * rlen);
+    for (int32_t j = 0; j < rlen; j++) start[j] = orc_path_start(cost, qlen, rlen, j);
+    free(cost);
+    free(query);
+}
+
 /* ---- src/sigfish.c:828-992 ---- */
 void orc_dtw_single(const float *events, int32_t qlen, const orc_ref_t *ref, uint32_t flag, orc_result_t *out) {
     memset(out, 0, sizeof(*out));
@@ -267,13 +291,7 @@ void orc_dtw_single(const float *events, int32_t qlen, const orc_ref_t *ref, uin
     cand_t top[TOPN];
     top_init(top);
 
-    float *query = (float *)malloc(sizeof(float) * qlen);
-    for (int32_t j = 0; j < qlen; j++) {
-        if (rna && !(flag & ORC_INV))
-            query[qlen - 1 - j] = events[j]; /* sigfish.c:861-863 */
-        else
-            query[j] = events[j];
-    }
+    float *query = query_rows(events, qlen, flag);
     for (int32_t c = 0; c < ref->num_ref; c++) {
         const int32_t rlen = ref->ref_lengths[c];
         float *cost = (float *)malloc(sizeof(float) * (size_t)qlen * rlen);

@@ -62,7 +62,7 @@ SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "
            "sfa_blow5_open", "sfa_blow5_attr", "sfa_blow5_next", "sfa_blow5_close", "sfa_blow5_select_shard", "sfa_blow5_select_records", "sfa_inflate_zlib", "sfa_inflate_zlib_pair", "sfa_device_memory",
            "sfa_session_create", "sfa_session_extend", "sfa_session_reset", "sfa_session_lengths", "sfa_session_destroy", "sfa_session_bytes",
            "sfa_event_stream_create", "sfa_event_stream_push", "sfa_event_stream_finish", "sfa_event_stream_destroy",
-           "sfa_session_raw_config", "sfa_session_extend_raw", "sfa_session_events", "sfa_session_raw_bytes", "sfa_session_query_span"]
+           "sfa_session_raw_config", "sfa_session_extend_raw", "sfa_session_events", "sfa_session_raw_bytes", "sfa_session_query_span", "sfa_session_row"]
 
 _lib = None
 
@@ -153,6 +153,8 @@ def load():
     L.sfa_session_lengths.argtypes = [vp, i32p, C.c_int32, i64p]
     L.sfa_session_destroy.argtypes = [vp]
     L.sfa_session_destroy.restype = None
+    L.sfa_session_row.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, f32p, i32p]
+    L.sfa_session_row.restype = C.c_int64
     L.sfa_session_bytes.argtypes = [C.c_int64, C.c_int32, C.c_uint32]
     L.sfa_session_bytes.restype = C.c_int64
     L.sfa_event_stream_create.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int]

@@ -476,6 +476,21 @@ class Session:
                                            out.ctypes.data_as(_lib.i64p)), "sfa_session_lengths")
         return out
 
+    def row(self, slot, contig, strand):
+        """The carried row of (slot, contig, strand '+' or '-') read back (sfa_session_row): (cost float32[ref_length], start
+        int32[ref_length] or None without starts).  Start columns are as stored: columns of the strand's own array, before the
+        flip of '-' and before ref_st_offset."""
+        self._live()
+        ch = ord(strand) if isinstance(strand, str) else int(strand)
+        n = int(self._al.ref.ref_lengths[contig]) if 0 <= int(contig) < len(self._al.ref.ref_lengths) else 1
+        cost = np.zeros(n, np.float32)
+        start = np.zeros(n, np.int32) if self.starts else None
+        got = int(self._L.sfa_session_row(self._h, int(slot), int(contig), ch, cost.ctypes.data_as(_lib.f32p),
+                                          None if start is None else start.ctypes.data_as(_lib.i32p)))
+        if got < 0:
+            _check(got, "sfa_session_row")
+        return cost, start
+
     def close(self):
         if self._h and self._al._h.value == self._al_h:  # (an Aligner that was closed took its sessions with it)
             self._L.sfa_session_destroy(self._h)

@@ -362,6 +362,28 @@ int sfa_session_create(sfa_ctx_t *c, int32_t n_slots, uint32_t session_flags, sf
     return SFA_OK;
 }
 
+int64_t sfa_session_row(sfa_session_t *s, int32_t slot, int32_t contig, int32_t strand_char, float *cost, int32_t *start) {
+    if (!s || !cost) return fail(SFA_EINVAL, "sfa_session_row: null session or null cost");
+    sfa_ctx *c = s->c;
+    if (slot < 0 || slot >= s->n_slots) return fail(SFA_EINVAL, "sfa_session_row: slot %d out of range (the session has %d)", slot, s->n_slots);
+    if (contig < 0 || contig >= c->model.num_ref) return fail(SFA_EINVAL, "sfa_session_row: contig %d out of range (the reference has %d)", contig, c->model.num_ref);
+    const int strands = c->model.n_jobs / c->model.num_ref;  // 1: RNA, forward arrays only
+    if (strand_char != '+' && !(strand_char == '-' && strands == 2))
+        return fail(SFA_EINVAL, "sfa_session_row: strand %d is neither '+' nor '-' (RNA has no '-')", strand_char);
+    if (start && !s->track) return fail(SFA_EINVAL, "sfa_session_row: the session carries no start columns (SFA_SESSION_NO_START)");
+    if (s->poison[slot]) return fail(SFA_EINVAL, "sfa_session_row: slot %d is poisoned (a chunk held a NaN or inf); it has no row until it is reset", slot);
+    if (s->len[slot] == 0) return fail(SFA_EINVAL, "sfa_session_row: slot %d has no events, so no carried row", slot);
+    const int32_t job = contig * strands + (strand_char == '-' ? 1 : 0);
+    int64_t col_off = 0;
+    for (int32_t j = 0; j < job; ++j) col_off += c->model.h_job_len[j];
+    const int64_t n = c->model.h_job_len[job], row0 = sfa::kSessionPad + static_cast<int64_t>(slot) * c->model.total_cols + col_off;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(cost, s->d_row_c.as<float>() + row0, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, c->stream));
+    if (start) HIP_TRY(hipMemcpyAsync(start, s->d_row_s.as<int32_t>() + row0, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return n;
+}
+
 void sfa_session_destroy(sfa_session_t *s) {
     if (!s) return;
     sfa_ctx *c = s->c;

@@ -1,4 +1,4 @@
-"""Alignment sessions without a GPU: the six symbols are declared and exported, sfa_session_bytes is host arithmetic, and the
+"""Alignment sessions without a GPU: the symbols are declared and exported, sfa_session_bytes is host arithmetic, and the
 Python names exist."""
 import ctypes as C
 import os
@@ -11,7 +11,7 @@ from sigfish_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ["sfa_session_create", "sfa_session_extend", "sfa_session_reset", "sfa_session_lengths", "sfa_session_destroy",
-        "sfa_session_bytes"]
+        "sfa_session_bytes", "sfa_session_row"]
 
 
 def test_symbols_declared_and_exported():
@@ -53,7 +53,7 @@ def test_session_bytes_refuses(cols, slots, flags):
 
 def test_python_names():
     assert callable(S.Aligner.session)
-    for name in ("extend", "reset", "lengths", "close", "__enter__", "__exit__"):
+    for name in ("extend", "reset", "lengths", "row", "close", "__enter__", "__exit__"):
         assert callable(getattr(S.Session, name)), name
     assert callable(S.session_bytes)
     assert S.SESSION_NO_START == 1
@@ -66,4 +66,5 @@ def test_null_arguments_are_einval():
     assert L.sfa_session_extend(None, None, None, None, 1, None) == -1
     assert L.sfa_session_reset(None, None, 0) == -1
     assert L.sfa_session_lengths(None, None, 0, None) == -1
+    assert L.sfa_session_row(None, 0, 0, ord("+"), None, None) == -1
     L.sfa_session_destroy(None)
