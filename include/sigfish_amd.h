@@ -250,8 +250,9 @@ int64_t sfa_session_bytes(int64_t total_columns, int32_t n_slots, uint32_t sessi
  *                  table of final events (means in pA) in device memory; detector parameters follow the context's SFA_RNA
  *   normalisation  final events 0 .. skip_events - 1 are dropped (the -p of the batch path).  Once final event skip + norm - 1
  *                  exists, mean and sd over the pA means of events [skip, skip + norm) are computed exactly as sfa_znormalise
- *                  does (two sequential fp32 loops, sqrt in double) and FROZEN until the slot is reset; event e >= skip enters the
- *                  slot's query as (mean_e - mean) / sd in fp32
+ *                  does (two sequential fp32 loops, sqrt in double) and FROZEN until the slot is reset (unless
+ *                  sfa_session_raw_recalibrate lets the window grow); event e >= skip enters the slot's query as
+ *                  (mean_e - mean) / sd in fp32
  *   sweep          the new query events are handed to the session sweep straight from device memory; only the per-slot counts
  *                  cross PCIe in between (the planner of the sweep is host code)
  * At query_events query events (skip + query final events) the slot is FULL: its detector stops, later samples are only counted.
@@ -267,10 +268,30 @@ typedef struct {
     int64_t n_samples; /* samples the slot has received since its last reset */
     int64_t n_events;  /* final events (at most skip + query) */
     int64_t q_events;  /* query events swept: the length of the query out[i] is the row of */
-    float norm_mean, norm_sd; /* the frozen normalisation, 0 before calibration */
-    int32_t status;    /* bit 0 calibrated, bit 1 full, bit 2 ended (end of read seen), bit 3 poisoned */
-    int32_t pad;
+    float norm_mean, norm_sd; /* the slot's normalisation, 0 before calibration */
+    int32_t status;    /* bit 0 calibrated, bit 1 full, bit 2 ended (end of read seen), bit 3 poisoned, bit 4 (of this call only):
+                          the slot was recalibrated and events an earlier call had swept were swept again */
+    int32_t norm_window; /* W: norm_mean and norm_sd span final events [skip, skip + W); 0 before calibration */
 } sfa_session_raw_info_t;
+
+/* Recalibration: let a slot's normalisation window grow with its read instead of freezing it at norm events.
+ * With q_avail = min(n_events - skip, query) query events available, the window W a slot has after a call is
+ *   q_avail                        with SFA_RECAL_AT_END, once its end of read has been seen, when 25 <= q_avail < query -- the
+ *                                  window the batch path gives a read that is too short (normalise_single, src/sigfish.c:450-461)
+ *   the largest at[k] <= q_avail   otherwise, if there is one
+ *   norm                           otherwise, if q_avail >= norm
+ *   0                              otherwise: not calibrated
+ * W never shrinks.  When a call leaves a slot with another W than its normalisation spans, the device computes mean and sd over
+ * [skip, skip + W) (sfa_znormalise's arithmetic, as at the first calibration), rewrites the slot's whole query and sweeps it
+ * again from event 0 inside that call -- a first chunk, which overwrites the carried row; a call that passes several points takes
+ * the last.  So after ANY call out[i] is, bit for bit, sfa_align_batch's row for the slot's q_avail query events normalised over
+ * [skip, skip + W), and state and rows depend on the samples a slot has received, not on how they were cut into calls.  Under a
+ * doubling list (norm, 2 norm, 4 norm, ..., query) a read is swept at most twice.
+ * Allowed on a raw-mode session while every slot is empty; needs norm < at[0] < ... < at[n_at - 1] <= query and n_at <= 32;
+ * unknown flags, a bad list, a session that is not in raw mode or a slot in use are SFA_EINVAL.  n_at = 0 with flags = 0
+ * switches it off (at may be NULL then), and so does sfa_session_raw_config. */
+#define SFA_RECAL_AT_END 0x1
+int sfa_session_raw_recalibrate(sfa_session_t *s, const int32_t *at, int32_t n_at, uint32_t flags);
 
 /* Append raw[raw_off[i] .. raw_off[i+1]) to slot slot[i], i < n.  scaling[3*i..]: digitisation, offset, range as for sfa_align_raw;
  * the triple is latched by a slot's first chunk after a reset, another one later is SFA_EINVAL.  end_of_read (may be NULL):
@@ -296,7 +317,8 @@ int64_t sfa_session_events(sfa_session_t *s, int32_t slot, int64_t first, sfa_ev
 int sfa_session_query_span(sfa_session_t *s, const int32_t *slot, int32_t n, uint64_t *start_raw, uint64_t *end_raw);
 
 /* Device memory raw mode adds to sfa_session_bytes: per slot an event table of (skip + query) x 24 bytes, the query of
- * query x 4 bytes and 592 bytes of detector state.  Host arithmetic; negative (an SFA_E* code) for n_slots <= 0, skip < 0,
+ * query x 4 bytes and 592 bytes of detector state (the slot's window length, 4 bytes in a side array, counts as bookkeeping).
+ * Host arithmetic; negative (an SFA_E* code) for n_slots <= 0, skip < 0,
  * query <= 0 or a product beyond 2^63. */
 int64_t sfa_session_raw_bytes(int32_t n_slots, int32_t skip_events, int32_t query_events);
 

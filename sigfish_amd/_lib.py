@@ -52,7 +52,7 @@ class SfaEvent(C.Structure):
 
 class SfaSessionRawInfo(C.Structure):
     _fields_ = [("n_samples", C.c_int64), ("n_events", C.c_int64), ("q_events", C.c_int64), ("norm_mean", C.c_float),
-                ("norm_sd", C.c_float), ("status", C.c_int32), ("pad", C.c_int32)]
+                ("norm_sd", C.c_float), ("status", C.c_int32), ("norm_window", C.c_int32)]
 
 
 # every symbol include/sigfish_amd.h declares (checked by tests/test_capi_host.py::test_library_exports_every_declared_symbol)
@@ -62,7 +62,8 @@ SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "
            "sfa_blow5_open", "sfa_blow5_attr", "sfa_blow5_next", "sfa_blow5_close", "sfa_blow5_select_shard", "sfa_blow5_select_records", "sfa_inflate_zlib", "sfa_inflate_zlib_pair", "sfa_device_memory",
            "sfa_session_create", "sfa_session_extend", "sfa_session_reset", "sfa_session_lengths", "sfa_session_destroy", "sfa_session_bytes",
            "sfa_event_stream_create", "sfa_event_stream_push", "sfa_event_stream_finish", "sfa_event_stream_destroy",
-           "sfa_session_raw_config", "sfa_session_extend_raw", "sfa_session_events", "sfa_session_raw_bytes", "sfa_session_query_span", "sfa_session_row"]
+           "sfa_session_raw_config", "sfa_session_extend_raw", "sfa_session_events", "sfa_session_raw_bytes", "sfa_session_query_span", "sfa_session_row",
+           "sfa_session_raw_recalibrate"]
 
 _lib = None
 
@@ -166,6 +167,7 @@ def load():
     L.sfa_event_stream_destroy.argtypes = [vp]
     L.sfa_event_stream_destroy.restype = None
     L.sfa_session_raw_config.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    L.sfa_session_raw_recalibrate.argtypes = [vp, i32p, C.c_int32, C.c_uint32]
     L.sfa_session_extend_raw.argtypes = [vp, i32p, i16p, i64p, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_int32, vp, vp]
     L.sfa_session_events.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(SfaEvent), C.c_int64]
     L.sfa_session_events.restype = C.c_int64

@@ -25,9 +25,37 @@ assert QUERY_INFO_DTYPE.itemsize == C.sizeof(_lib.SfaQueryInfo)
 
 
 SESSION_RAW_INFO_DTYPE = np.dtype([("n_samples", "<i8"), ("n_events", "<i8"), ("q_events", "<i8"), ("norm_mean", "<f4"), ("norm_sd", "<f4"),
-                                   ("status", "<i4"), ("pad", "<i4")])
+                                   ("status", "<i4"), ("norm_window", "<i4")])
 assert SESSION_RAW_INFO_DTYPE.itemsize == C.sizeof(_lib.SfaSessionRawInfo)
 RAW_CALIBRATED, RAW_FULL, RAW_ENDED, RAW_POISONED = 1, 2, 4, 8  # bits of SESSION_RAW_INFO_DTYPE's status
+RAW_RECALIBRATED = 16  # ... and the bit of one call: the slot was recalibrated and swept again from event 0
+RECAL_AT_END = 0x1     # SFA_RECAL_AT_END
+RECAL_MAX_POINTS = 32
+
+
+def recal_window(q_avail, ended, norm, query, at=(), at_end=False):
+    """The window a raw-session slot is normalised over (sfa::recal_window, csrc/recal_rule.hpp): q_avail = min(n_events - skip,
+    query) query events are available, `ended` tells whether the end of the read has been seen.  0: not calibrated."""
+    if at_end and ended and 25 <= q_avail < query:
+        return q_avail
+    w = 0
+    for p in at:
+        if p <= q_avail:
+            w = p
+    if w > 0:
+        return w
+    return norm if q_avail >= norm else 0
+
+
+def recal_double(norm, query):
+    """The doubling list (sfa::recal_double): 2 norm, 4 norm, ... below query, then query; empty when norm == query."""
+    if norm < 1 or norm >= query:
+        return ()
+    at, w = [], 2 * norm
+    while w < query and len(at) < RECAL_MAX_POINTS - 1:
+        at.append(w)
+        w *= 2
+    return tuple(at + [query])
 
 
 class SfaError(RuntimeError):
@@ -401,13 +429,26 @@ class Session:
                                           eo.ctypes.data_as(_lib.i64p), n, out.ctypes.data_as(C.c_void_p)), "sfa_session_extend")
         return out
 
-    def configure_raw(self, skip=50, norm=100, query=2048):
+    def configure_raw(self, skip=50, norm=100, query=2048, recalibrate=(), at_end=False):
         """Raw mode (sfa_session_raw_config): the session takes samples (extend_raw) and runs event detection and normalisation on
         the device.  The first `skip` final events of a slot are dropped, mean and sd over the next `norm` are frozen, the slot is
-        full at `query` query events.  Only while every slot is empty."""
+        full at `query` query events.  Only while every slot is empty.
+        recalibrate: ascending window lengths, norm < ... <= query (sfa_session_raw_recalibrate): when a slot reaches one, it is
+        normalised over that many events and swept again from event 0 inside the call; at_end: a read that ends with 25 <= events -
+        skip < query is normalised over all of them.  The window after any call is recal_window(); info["norm_window"] reports it."""
         self._live()
         _check(self._L.sfa_session_raw_config(self._h, int(skip), int(norm), int(query)), "sfa_session_raw_config")
         self.raw_shape = (int(skip), int(norm), int(query))
+        if len(recalibrate) or at_end:
+            self.recalibrate(recalibrate, at_end)
+
+    def recalibrate(self, at=(), at_end=False, flags=None):
+        """sfa_session_raw_recalibrate on a raw-mode session whose slots are all empty; at=() and at_end=False switch it off.
+        flags: the raw flag word in place of at_end."""
+        self._live()
+        pts = np.ascontiguousarray(at, np.int32).reshape(-1)
+        fl = (RECAL_AT_END if at_end else 0) if flags is None else int(flags)
+        _check(self._L.sfa_session_raw_recalibrate(self._h, pts.ctypes.data_as(_lib.i32p) if len(pts) else None, len(pts), fl), "sfa_session_raw_recalibrate")
 
     def extend_raw(self, slots, raw, raw_off, scaling, end=None):
         """Append raw[raw_off[i]:raw_off[i+1]] (int16 samples) to slot slots[i]; scaling[i] = (digitisation, offset, range); end[i]

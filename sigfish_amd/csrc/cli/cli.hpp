@@ -72,6 +72,9 @@ struct RealtimeOpt {
     int32_t min_events = -1;       // --min-events: no early decision below this many query events (-1: the value of -q)
     int32_t min_mapq = 61;         // --min-mapq: early decision at this mapq (61: never, mapq ends at 60)
     bool pace = false;             // --pace yes: tick t does not start before t x chunk_samples / sampling_rate seconds
+    std::vector<int32_t> recal_at; // --recalibrate: window lengths at which a slot is renormalised ("double" is expanded)
+    bool recal_at_end = false;     // --recalibrate-at-end: a read that ends short is normalised over all its query events
+                                   // (SFA_RECAL_AT_END), and q is the last of recal_at, so a full read over q
 };
 
 // options.cpp: the option table, help and every check that needs no file and no device (exits for -V and help)

@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "../../../include/sigfish_amd.h"
+#include "../recal_rule.hpp"
 #include "cli.hpp"
 
 namespace cli {
@@ -17,7 +18,8 @@ namespace {
 enum LongOpt {
     O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
     O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
-    O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE
+    O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE,
+    O_RECALIBRATE, O_RECALIBRATE_AT_END
 };
 
 const option kLongOptions[] = {
@@ -108,6 +110,7 @@ const option kRealtimeOptions[] = {
     {"channels", required_argument, 0, O_CHANNELS}, {"chunk-samples", required_argument, 0, O_CHUNK_SAMPLES},
     {"norm-events", required_argument, 0, O_NORM_EVENTS}, {"min-events", required_argument, 0, O_MIN_EVENTS},
     {"min-mapq", required_argument, 0, O_MIN_MAPQ}, {"pace", required_argument, 0, O_PACE},
+    {"recalibrate", required_argument, 0, O_RECALIBRATE}, {"recalibrate-at-end", no_argument, 0, O_RECALIBRATE_AT_END},
     {"dtw-std", no_argument, 0, O_DTW_STD}, {"from-end", no_argument, 0, O_FROM_END}, {"sam", no_argument, 0, 'a'},
     {"secondary", required_argument, 0, O_SECONDARY}, {"ranks", required_argument, 0, O_RANKS},
     {0, 0, 0, 0}};
@@ -122,7 +125,9 @@ void realtime_help(FILE *fp, const RealtimeOpt &r) {
                 "With the defaults (--norm-events = -q, never early) a read's line, without the three tags at its end, is the line\n"
                 "`sigfish-amd dtw -p P -q Q` prints for it whenever the read has P + Q events: the same events, the window [P, P + Q),\n"
                 "the same normalisation over that window, the same row.  The one difference: a read with fewer than P + norm events is\n"
-                "never calibrated and prints nothing, where dtw shortens its window.\n\nbasic options:\n");
+                "never calibrated and prints nothing, where dtw shortens its window.\n"
+                "With --recalibrate and --recalibrate-at-end a read may be calibrated on few events, decided early, and still print dtw's\n"
+                "line when it is not: the window grows with the read, up to -q or, for a read that ends short, to all its events.\n\nbasic options:\n");
     fprintf(fp, "   -t INT                     number of host threads decoding the records ahead of need [%d]\n", r.o.threads);
     fprintf(fp, "   -h                         help\n   -o FILE                    output to file [stdout]\n");
     fprintf(fp, "   --verbose INT              verbosity level [%d]\n   --version                  print version\n", r.o.verbosity);
@@ -136,6 +141,12 @@ void realtime_help(FILE *fp, const RealtimeOpt &r) {
     fprintf(fp, "   --channels INT             channels of the flow cell = slots of the session [%d]\n", r.channels);
     fprintf(fp, "   --chunk-samples INT        samples a channel sends per tick [%ld]\n", static_cast<long>(r.chunk_samples));
     fprintf(fp, "   --norm-events INT          events the normalisation is frozen over, 25..q [the value of -q]\n");
+    fprintf(fp, "   --recalibrate LIST|double  window lengths, ascending, above --norm-events and up to q: a read that reaches one is\n"
+                "                              normalised over that many events and swept again from its first event inside the tick;\n"
+                "                              double = 2 x norm-events, 4 x, ... below q, then q (at most twice the sweep work) [off]\n");
+    fprintf(fp, "   --recalibrate-at-end       a read's last line is dtw's: a read that ends with 25 .. q - 1 events behind -p is normalised\n"
+                "                              over all of them, as dtw normalises a read that is too short, and q joins the --recalibrate\n"
+                "                              points (if it is not the last already), so that a full read is normalised over q events [off]\n");
     fprintf(fp, "   --min-events INT           no early decision below this many query events [the value of -q]\n");
     fprintf(fp, "   --min-mapq INT             decide early at this mapq; 61 = never [%d]\n", r.min_mapq);
     fprintf(fp, "   --pace yes|no              sleep so that tick t does not start before t x chunk-samples / sampling_rate seconds;\n"
@@ -151,6 +162,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     FILE *fp_help = stderr;
     int c, li = 0;
     bool secondary = false;
+    const char *recal = nullptr;
     while ((c = getopt_long(argc, argv, "p:q:t:v:o:ahV", kRealtimeOptions, &li)) >= 0) {
         switch (c) {
             case 't': o.threads = atoi(optarg); if (o.threads < 1) die("Number of threads should larger than 0."); break;
@@ -181,6 +193,8 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
             case O_MIN_EVENTS: r.min_events = atoi(optarg); if (r.min_events < 0) die("--min-events should not be negative"); break;
             case O_MIN_MAPQ: r.min_mapq = atoi(optarg); break;
             case O_PACE: r.pace = yes_or_no(optarg, "pace"); break;
+            case O_RECALIBRATE: recal = optarg; break;
+            case O_RECALIBRATE_AT_END: r.recal_at_end = true; break;
             default: realtime_help(stderr, r); exit(EXIT_FAILURE);
         }
     }
@@ -203,6 +217,30 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     if (r.norm_events < 0) r.norm_events = o.query;
     if (r.min_events < 0) r.min_events = o.query;
     if (r.norm_events < 25 || r.norm_events > o.query) die("realtime: --norm-events should be 25..q (the value of -q)");
+    if (recal && !strcmp(recal, "double")) {
+        int32_t at[sfa::kRecalMaxPoints];
+        r.recal_at.assign(at, at + sfa::recal_double(r.norm_events, o.query, at));
+    } else if (recal) {
+        for (const char *p = recal; *p;) {
+            char *e = nullptr;
+            const long v = strtol(p, &e, 10);
+            if (e == p || (*e && *e != ',') || v < 0 || v > INT32_MAX) die("realtime: --recalibrate takes 'double' or a comma separated list of window lengths");
+            if (r.recal_at.size() > static_cast<size_t>(sfa::kRecalMaxPoints)) break;  // (refused below)
+            r.recal_at.push_back(static_cast<int32_t>(v));
+            p = *e ? e + 1 : e;
+            if (*e && !*p) die("realtime: --recalibrate takes 'double' or a comma separated list of window lengths");
+        }
+        if (r.recal_at.empty()) die("realtime: --recalibrate takes 'double' or a comma separated list of window lengths");
+    }
+    if (const char *why = sfa::recal_list_error(r.recal_at.data(), static_cast<int64_t>(r.recal_at.size()), r.norm_events, o.query))
+        die(std::string("realtime: --recalibrate: ") + why + " (the list must ascend from above --norm-events up to q, at most 32 points)");
+    // --recalibrate-at-end is about the line a read ends with, whichever way it ends: a read that ends short gets the session's
+    // end-of-read window (SFA_RECAL_AT_END), a read that ends full must be normalised over [p, p + q), so q joins the points
+    if (r.recal_at_end && o.query > r.norm_events && (r.recal_at.empty() || r.recal_at.back() != o.query)) {
+        r.recal_at.push_back(o.query);
+        if (const char *why = sfa::recal_list_error(r.recal_at.data(), static_cast<int64_t>(r.recal_at.size()), r.norm_events, o.query))
+            die(std::string("realtime: --recalibrate with --recalibrate-at-end (which adds q as the last point): ") + why);
+    }
     o.ranks = 1;
     return r;
 }

@@ -1,6 +1,7 @@
 // realtime_main.cpp -- `sigfish-amd realtime`: a BLOW5 file replayed through a raw-signal session as a flow cell would deliver
 // it (the schedule: replay.hpp), a PAF line at the moment a read is decided, and the time a tick takes against the signal time
-// it stands for.  The hot path is the library's (sfa_session_extend_raw: detector, frozen normalisation, sweep); what runs here
+// it stands for.  The hot path is the library's (sfa_session_extend_raw: detector, normalisation -- frozen, or growing with the
+// read under --recalibrate --, sweep); what runs here
 // is the staging of a tick's samples, the decision rule and the printing.
 #include <algorithm>
 #include <chrono>
@@ -153,6 +154,9 @@ int realtime_run(int argc, char **argv, double t0) {
     sfa_session_t *se = nullptr;  // (freed with its context)
     if (sfa_session_create(ctx.c, r.channels, 0, &se) != SFA_OK) die(std::string("session: ") + sfa_last_error());
     if (sfa_session_raw_config(se, o.prefix, r.norm_events, o.query) != SFA_OK) die(std::string("session: ") + sfa_last_error());
+    if (!r.recal_at.empty() || r.recal_at_end)
+        if (sfa_session_raw_recalibrate(se, r.recal_at.data(), static_cast<int32_t>(r.recal_at.size()), r.recal_at_end ? SFA_RECAL_AT_END : 0) != SFA_OK)
+            die(std::string("session: ") + sfa_last_error());
     if (o.verbosity >= 4)
         fprintf(stderr, "[realtime::%.3f] initialised: %d channels, %ld samples per tick, skip %d, norm %d, query %d, early at %d events and mapq %d\n", realtime() - t0,
                 r.channels, (long)r.chunk_samples, o.prefix, r.norm_events, o.query, r.min_events, r.min_mapq);

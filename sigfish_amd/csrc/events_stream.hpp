@@ -16,20 +16,25 @@
 // the kernel runs ([index][lane] doubles: a lane's 8-byte access falls on banks 2 * lane, 2 * lane + 1 whatever its index,
 // so the 32 lanes of a half never collide although every lane is at another index).  Chunks of one call have different
 // lengths: the wave walks to the longest and masks the others.
-// ev_stream_norm_kernel: one wave per slot of the call; freezes mean and sd over the slot's calibration window once it is
+// ev_stream_norm_kernel: one wave per slot of the call; computes mean and sd over the slot's calibration window once it is
 // complete (the two sequential fp32 loops and the double sqrt of sfa_znormalise / ev_query_kernel) and appends the
-// normalised means of the new events to the slot's device-resident query, from where the session sweep takes them.
+// normalised means of the new events to the slot's device-resident query, from where the session sweep takes them.  With
+// recalibration points (sfa_session_raw_recalibrate, recal_rule.hpp) the window grows with the read: when it does, the
+// statistics are computed again over the longer window and the whole query is rewritten, to be swept from event 0.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "recal_rule.hpp"
+
 namespace sfa {
 
 constexpr int kEvRing = 29;  // 2 * 14 + 1: the RNA long window (DNA uses 13 of them)
 
-// status bits of a slot (0..3 are those of sfa_session_raw_info_t)
-constexpr int kRawCalibrated = 1, kRawFull = 2, kRawEnded = 4, kRawPoisoned = 8, kRawAnyCut = 16;
+// status bits of a slot: 0..3 are those of sfa_session_raw_info_t and kRawResweep is its bit 4, which belongs to a call (this
+// call swept events again that an earlier one had swept) and is never stored in a slot; kRawAnyCut is internal
+constexpr int kRawCalibrated = 1, kRawFull = 2, kRawEnded = 4, kRawPoisoned = 8, kRawResweep = 16, kRawAnyCut = 32;
 
 // the carried state of a slot: plain device memory, loaded at the start of a call and stored at its end
 struct EvStreamSlot {
@@ -267,23 +272,37 @@ __global__ void __launch_bounds__(64) ev_stream_kernel(const EvStreamArgs a) {
     }
 }
 
-// what a call brings back to the host per slot: counts and the frozen normalisation
+// what a call brings back to the host per slot: counts and the normalisation the slot has now
 struct EvStreamOut {
-    int32_t n_events, q_first, q_new, status;
+    int32_t n_events, q_first, q_new, status;  // status: bits 0..3 of the slot | kRawResweep for this call
     float mean, sd;
+    int32_t window, pad;                       // events the mean and sd span (0: not calibrated)
 };
 
 struct EvNormArgs {
     const int32_t *slot;     // [n]
     EvStreamSlot *state;
+    int32_t *window;         // [n_slots] W_cur, the window a calibrated slot's normalisation spans: a side array of the session,
+                             // since EvStreamSlot keeps its 592 bytes; it means something only while kRawCalibrated is set
     const EvRecord *events;  // [n_slots][ev_cap]
     float *query;            // [n_slots][query] the slots' normalised queries
     EvStreamOut *out;        // [n]
     uint8_t *bad;            // [n] the slot is poisoned: not swept
     int32_t n, ev_cap, skip, norm, query_cap;
+    int32_t n_at;            // recalibration points (recal_rule.hpp); 0 and no flags: the window is frozen at norm
+    uint32_t flags;          // kRecalAtEnd
+    int32_t at[kRecalMaxPoints];
 };
 
+constexpr int kNormTile = 2048;  // pA means staged per tile of the statistics: 8 KB of LDS
+
+// One wave per slot of the call.  The window W the slot must have now follows from its counts (recal_window).  Where it differs
+// from the window its normalisation spans -- the first calibration is the case W_cur = 0 -- mean and sd are computed over events
+// [skip, skip + W): all lanes stage the window's pA means from the 24-byte records into LDS, tile by tile, and lane 0 runs
+// sfa_znormalise's two sequential fp32 loops over them (so the result is the host's bit for bit); then all lanes rewrite the
+// WHOLE query [0, q_avail) and the host sweeps it as a first chunk.  Otherwise the new events are appended as before.
 __global__ void __launch_bounds__(64) ev_stream_norm_kernel(const EvNormArgs a) {
+    __shared__ float tile[kNormTile];
     __shared__ float stat[2];
     __shared__ int s_status;
     const int i = blockIdx.x, lane = threadIdx.x;
@@ -293,16 +312,35 @@ __global__ void __launch_bounds__(64) ev_stream_norm_kernel(const EvNormArgs a) 
     const int nev = st->n_events, q_done = st->q_done;
     int status = st->status;
     float mean = st->mean, sd = st->sd;
-    if (!(status & kRawCalibrated) && nev >= a.skip + a.norm) {  // (block-uniform)
-        if (lane == 0) {  // sfa_znormalise's sums, in its order
-            const float cnt = static_cast<float>(a.norm);
-            float m = 0.0f, var = 0.0f;
-            for (int j = 0; j < a.norm; ++j) m += ev[a.skip + j].mean;
-            m /= cnt;
-            for (int j = 0; j < a.norm; ++j) {
-                const float dv = ev[a.skip + j].mean - m;
-                var += dv * dv;
+    const int q_avail = recal_q_avail(nev, a.skip, a.query_cap);
+    const int w_cur = (status & kRawCalibrated) ? a.window[slot] : 0;
+    int w = w_cur;
+    if (!(status & kRawPoisoned))  // (a poisoned slot keeps what poisoned it until it is reset)
+        w = max(w_cur, recal_window(q_avail, (status & kRawEnded) != 0, a.norm, a.query_cap, a.at, a.n_at, a.flags));
+    const bool recal = w != w_cur;  // (block-uniform, as everything above)
+    if (recal) {
+        const float cnt = static_cast<float>(w);
+        float m = 0.0f, var = 0.0f;  // lane 0's
+        for (int pass = 0; pass < 2; ++pass) {
+            for (int base = 0; base < w; base += kNormTile) {
+                const int len = min(kNormTile, w - base);
+                for (int j = lane; j < len; j += 64) tile[j] = ev[a.skip + base + j].mean;
+                __syncthreads();
+                if (lane == 0) {  // sfa_znormalise's sums, in its order
+                    if (pass == 0) {
+                        for (int j = 0; j < len; ++j) m += tile[j];
+                    } else {
+                        for (int j = 0; j < len; ++j) {
+                            const float dv = tile[j] - m;
+                            var += dv * dv;
+                        }
+                    }
+                }
+                __syncthreads();
             }
+            if (pass == 0) m /= cnt;
+        }
+        if (lane == 0) {
             var /= cnt;
             stat[0] = m;
             stat[1] = static_cast<float>(sqrt(static_cast<double>(var)));
@@ -313,15 +351,15 @@ __global__ void __launch_bounds__(64) ev_stream_norm_kernel(const EvNormArgs a) 
         status |= kRawCalibrated;
         if (!(sd > 0.0f) || sd > 3.402823466e+38f) status |= kRawPoisoned;  // zero, NaN or inf: no query can be made of it
     }
+    const int q_first = recal ? 0 : q_done;
     int q_new = 0;
     if (lane == 0) s_status = 0;
     __syncthreads();
     if ((status & kRawCalibrated) && !(status & kRawPoisoned)) {
-        const int q_avail = min(nev - a.skip, a.query_cap);
-        q_new = q_avail - q_done;
+        q_new = q_avail - q_first;
         float *q = a.query + static_cast<int64_t>(slot) * a.query_cap;
         bool bad = false;
-        for (int e = q_done + lane; e < q_avail; e += 64) {
+        for (int e = q_first + lane; e < q_avail; e += 64) {
             const float v = (ev[a.skip + e].mean - mean) / sd;
             q[e] = v;
             bad = bad || !(fabsf(v) <= 3.402823466e+38f);
@@ -335,14 +373,17 @@ __global__ void __launch_bounds__(64) ev_stream_norm_kernel(const EvNormArgs a) 
         st->status = status;
         st->mean = mean;
         st->sd = sd;
-        st->q_done = q_done + q_new;
+        if (!(status & kRawPoisoned)) st->q_done = q_first + q_new;
+        a.window[slot] = w;
         EvStreamOut o;
         o.n_events = nev;
-        o.q_first = q_done;
+        o.q_first = (status & kRawPoisoned) ? q_done : q_first;
         o.q_new = q_new;
-        o.status = status & 15;
+        o.status = (status & 15) | ((recal && q_done > 0 && q_new > 0) ? kRawResweep : 0);
         o.mean = mean;
         o.sd = sd;
+        o.window = w;
+        o.pad = 0;
         a.out[i] = o;
         a.bad[i] = (status & kRawPoisoned) ? 1 : 0;
     }

@@ -35,9 +35,14 @@ struct sfa_session {
     std::vector<int32_t> raw_nev;      // its final events
     std::vector<int32_t> raw_status;   // bits of sfa_session_raw_info_t.status
     std::vector<float> raw_mean, raw_sd;
+    std::vector<int32_t> raw_window;   // events the slot's mean and sd span (0: not calibrated)
     std::vector<double> raw_scaling;   // [n_slots][3] latched by the first chunk after a reset
     std::vector<uint8_t> raw_fresh;    // no chunk since the last reset: the next one initialises the detector state
     DevBuf d_state, d_evtab, d_query;  // [n_slots] EvStreamSlot, [n_slots][skip + query] EvRecord, [n_slots][query] float
+    DevBuf d_window;                   // [n_slots] i32: the window a calibrated slot's normalisation spans (EvNormArgs.window)
+    int32_t recal_at[sfa::kRecalMaxPoints] = {0};  // sfa_session_raw_recalibrate: the points, their number, the flags
+    int32_t recal_n = 0;
+    uint32_t recal_flags = 0;
     DevBuf d_raw, d_rstage, d_rout;    // of a call: samples, entry tables, EvStreamOut per entry
     PinBuf h_rstage, h_rout;
     Event ev_raw[3];                   // detector start / end, normalisation end
@@ -119,6 +124,7 @@ void reset_raw_slot(sfa_session *s, int32_t sl) {
     s->raw_nev[sl] = 0;
     s->raw_status[sl] = 0;
     s->raw_mean[sl] = s->raw_sd[sl] = 0.0f;
+    s->raw_window[sl] = 0;
     s->raw_fresh[sl] = 1;
 }
 
@@ -476,7 +482,8 @@ int sfa_session_raw_config(sfa_session_t *s, int32_t skip_events, int32_t norm_e
     HIP_TRY(hipSetDevice(c->device));
     const size_t ns = static_cast<size_t>(s->n_slots), cap = static_cast<size_t>(skip_events) + query_events;
     if (sfa_session_raw_bytes(s->n_slots, skip_events, query_events) < 0) return fail(SFA_ENOMEM, "sfa_session_raw_config: the event tables do not fit");
-    if (int rc = reserve_all(s->d_state, sizeof(sfa::EvStreamSlot) * ns, s->d_evtab, sizeof(sfa::EvRecord) * cap * ns, s->d_query, 4 * static_cast<size_t>(query_events) * ns))
+    if (int rc = reserve_all(s->d_state, sizeof(sfa::EvStreamSlot) * ns, s->d_evtab, sizeof(sfa::EvRecord) * cap * ns, s->d_query, 4 * static_cast<size_t>(query_events) * ns,
+                             s->d_window, 4 * ns))
         return rc;
     for (Event &e : s->ev_raw)
         if (!e.h && hipEventCreate(&e.h) != hipSuccess) return fail(SFA_ENODEV, "hipEventCreate failed");
@@ -489,8 +496,28 @@ int sfa_session_raw_config(sfa_session_t *s, int32_t skip_events, int32_t norm_e
     s->raw_status.assign(ns, 0);
     s->raw_mean.assign(ns, 0.0f);
     s->raw_sd.assign(ns, 0.0f);
+    s->raw_window.assign(ns, 0);
+    s->recal_n = 0;  // (the points were checked against the sizes that go)
+    s->recal_flags = 0;
     s->raw_scaling.assign(3 * ns, 0.0);
     s->raw_fresh.assign(ns, 1);
+    return SFA_OK;
+}
+
+int sfa_session_raw_recalibrate(sfa_session_t *s, const int32_t *at, int32_t n_at, uint32_t flags) {
+    if (!s) return fail(SFA_EINVAL, "sfa_session_raw_recalibrate: null session");
+    if (!s->raw) return fail(SFA_EINVAL, "sfa_session_raw_recalibrate: the session is not in raw mode (sfa_session_raw_config)");
+    if (flags & ~static_cast<uint32_t>(SFA_RECAL_AT_END)) return fail(SFA_EINVAL, "sfa_session_raw_recalibrate: unknown flag bits 0x%x", flags);
+    if (const char *why = sfa::recal_list_error(at, n_at, s->norm, s->query))
+        return fail(SFA_EINVAL, "sfa_session_raw_recalibrate: %s; need norm < at[0] < ... < at[n - 1] <= query, at most %d points (norm %d, query %d)", why,
+                    sfa::kRecalMaxPoints, s->norm, s->query);
+    for (int32_t sl = 0; sl < s->n_slots; ++sl)
+        if (s->len[sl] != 0 || s->poison[sl] || !s->raw_fresh[sl])
+            return fail(SFA_EINVAL, "sfa_session_raw_recalibrate: slot %d is not empty; the rule changes only while every slot is (sfa_session_reset)", sl);
+    static_assert(SFA_RECAL_AT_END == sfa::kRecalAtEnd, "the flag of the header is the rule's");
+    for (int32_t k = 0; k < n_at; ++k) s->recal_at[k] = at[k];
+    s->recal_n = n_at;
+    s->recal_flags = flags;
     return SFA_OK;
 }
 
@@ -625,6 +652,7 @@ int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t 
     sfa::EvNormArgs na;
     na.slot = ea.slot;
     na.state = ea.state;
+    na.window = s->d_window.as<int32_t>();
     na.events = ea.events;
     na.query = s->d_query.as<float>();
     na.out = s->d_rout.as<sfa::EvStreamOut>();
@@ -634,6 +662,9 @@ int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t 
     na.skip = s->skip;
     na.norm = s->norm;
     na.query_cap = s->query;
+    na.n_at = s->recal_n;
+    na.flags = s->recal_flags;
+    for (int32_t k = 0; k < sfa::kRecalMaxPoints; ++k) na.at[k] = k < s->recal_n ? s->recal_at[k] : 0;
     hipLaunchKernelGGL(sfa::ev_stream_norm_kernel, dim3(n), dim3(64), 0, st, na);
     KERNEL_TRY();
     HIP_TRY(hipEventRecord(s->ev_raw[2], st));
@@ -649,9 +680,13 @@ int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t 
         s->raw_fresh[sl] = 0;
         s->raw_n[sl] += raw_off[i + 1] - raw_off[i];
         s->raw_nev[sl] = ro[i].n_events;
-        s->raw_status[sl] = ro[i].status;
+        s->raw_status[sl] = ro[i].status & 15;
         s->raw_mean[sl] = ro[i].mean;
         s->raw_sd[sl] = ro[i].sd;
+        s->raw_window[sl] = ro[i].window;
+        // a recalibrated slot: its whole query was rewritten, so it is swept as a first chunk, which reads no carried row and
+        // writes a new one (the planner never puts first and carried chunks into one wave)
+        if (ro[i].q_new > 0 && ro[i].q_first == 0) s->len[sl] = 0;
         ch[i] = Chunk{static_cast<int64_t>(sl) * s->query + ro[i].q_first, ro[i].q_new};
     }
     float t_ev = 0, t_norm = 0;
@@ -669,8 +704,8 @@ int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t 
         f.q_events = s->len[sl];
         f.norm_mean = s->raw_mean[sl];
         f.norm_sd = s->raw_sd[sl];
-        f.status = s->raw_status[sl];
-        f.pad = 0;
+        f.status = s->raw_status[sl] | (ro[i].status & sfa::kRawResweep);
+        f.norm_window = s->raw_window[sl];
     }
     return SFA_OK;
 }

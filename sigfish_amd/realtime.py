@@ -6,6 +6,8 @@ ticks, the same calls, the same lines.  The schedule counts ticks, never seconds
   setup     read i goes to channel i, i < channels
   tick t    every busy channel sends the next chunk_samples samples of its read, ascending channels, in ONE extend_raw call; a
             chunk shorter than chunk_samples (empty when the read's length is a multiple of it) is the last and carries the end
+  windows   with recalibrate / at_end the session renormalises a slot over a longer window as it grows (api.recal_window) and sweeps
+            it again inside the call; the schedule and the decision rule do not change
   decision  decide(): 'E' early (calibrated, q_events >= min_events, mapped, mapq >= min_mapq), 'F' full, 'R' end of read (or a
             poisoned slot); a decision has a line when its row is mapped
   after it  decided channels are reset in one call and take the next unread reads, lowest channel first, from tick t + 1 on
@@ -85,13 +87,25 @@ class Schedule:
         self.tick += 1
 
 
-def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None):
+def recal_points(norm, query, recalibrate=(), at_end=False):
+    """The points `sigfish-amd realtime` hands its session: the list (or api.recal_double for "double"); with at_end the query size
+    joins them unless it is the last already, so that a read that ends FULL is normalised over the query as one that ends short is
+    over all it has (the session's RECAL_AT_END)."""
+    at = tuple(api.recal_double(norm, query) if isinstance(recalibrate, str) and recalibrate == "double" else recalibrate)
+    if at_end and query > norm and (not at or at[-1] != query):
+        at += (query,)
+    return at
+
+
+def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False):
     """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
 
     reads: iterable of (read_id, meta, samples) in file order, as Blow5File yields them (taken lazily: at most `channels` reads are
     held).  row / info: the channel's entries of Session.extend_raw at the decision; span: (start_raw, end_raw) of
     Session.query_span; reason: 'E', 'F' or 'R'.  A decision has a line when mapped(row): format_line().  `session`: an object with
-    extend_raw / query_span / reset in place of aligner.session(channels) in raw mode (the schedule's tests pass a stub)."""
+    extend_raw / query_span / reset in place of aligner.session(channels) in raw mode (the schedule's tests pass a stub).
+    recalibrate / at_end: --recalibrate (a list of window lengths, or "double": api.recal_double(norm, query)) and
+    --recalibrate-at-end, turned into the session's points by recal_points(); schedule and decision rule are the same with them."""
     reads = iter(reads)
     on = [None] * channels  # (index, read_id, meta, samples) per channel
 
@@ -113,7 +127,7 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     se = aligner.session(channels) if own else session
     try:
         if own:
-            se.configure_raw(skip, norm, query)
+            se.configure_raw(skip, norm, query, recal_points(norm, query, recalibrate, at_end), at_end)
         sch.start(src)
         while sch.busy():
             es = sch.begin_tick()
