@@ -200,11 +200,14 @@ int sfa_event_maps(sfa_ctx_t *ctx, const sfa_result_t *rows, const int32_t *read
  * become, instead of sfa_align_batch over the whole prefix again.  The caller keeps its normalisation fixed over a slot's life:
  * the events of all chunks are taken as ONE query (to re-normalise, reset the slot and send its events again).
  * Single-device contexts without SFA_DTW, and not SFA_RNA without SFA_INV (the query rows are then the events reversed: new events
- * would become row 0); SFA_EINVAL otherwise.  A session belongs to its context and uses its stream; its buffers are its own, so
+ * would become row 0) unless the session is created with SFA_SESSION_RESWEEP; SFA_EINVAL otherwise.  A session belongs to its context and uses its stream; its buffers are its own, so
  * batch calls on the context between two extends do not disturb it, and sfa_secondary_rows / sfa_event_maps keep referring to
  * the last BATCH call.  sfa_destroy frees the sessions a context still has: their handles are dead after it. */
 typedef struct sfa_session sfa_session_t;
 #define SFA_SESSION_NO_START 0x1 /* carry costs only: half the memory, the fill's cheap cell; the start side is not reported */
+/* 0x2 is not assigned: sfa_session_bytes and sfa_session_create refuse it as an unknown bit. */
+#define SFA_SESSION_RESWEEP 0x4  /* raw mode only: a slot is swept when its normalisation window changes, over the window's events
+                                    (see "resweep sessions" below); accepts SFA_RNA without SFA_INV */
 
 /* SFA_ENOMEM when the carried rows do not fit. */
 int sfa_session_create(sfa_ctx_t *ctx, int32_t n_slots, uint32_t session_flags, sfa_session_t **s);
@@ -240,7 +243,8 @@ void sfa_session_destroy(sfa_session_t *s);
 /* Device memory sfa_session_create takes for the carried rows of n_slots slots over a reference of total_columns columns
  * (sum of ref_lengths, twice that for DNA): one row per slot, updated in place -- total_columns x n_slots x 8 bytes, x 4 with
  * SFA_SESSION_NO_START (the allocator adds an eighth of headroom; bookkeeping is some 50 bytes per slot).  Host arithmetic, no
- * device needed; negative (an SFA_E* code) for arguments that are not positive, unknown flags or a product beyond 2^63. */
+ * device needed; negative (an SFA_E* code) for arguments that are not positive, unknown flags or a product beyond 2^63.
+ * SFA_SESSION_RESWEEP changes nothing: the carried rows are still needed (a window beyond SFA_MAX_QUERY events runs as pieces). */
 int64_t sfa_session_bytes(int64_t total_columns, int32_t n_slots, uint32_t session_flags);
 
 /* ---- raw-signal sessions: a slot's samples in, its row out ----------------------------------------------------------------
@@ -261,7 +265,30 @@ int64_t sfa_session_bytes(int64_t total_columns, int32_t n_slots, uint32_t sessi
  * sfa_session_raw_config switches a session to raw mode (or changes the three sizes); allowed only while every slot is empty,
  * needs skip >= 0 and 25 <= norm <= query, SFA_EINVAL otherwise.  sfa_session_extend on a raw-mode session is SFA_EINVAL, and so
  * is sfa_session_extend_raw on a session that is not.  sfa_session_reset clears a slot's detector, events, normalisation and
- * scaling too; sfa_session_lengths reports the query events swept. */
+ * scaling too; sfa_session_lengths reports the query events swept.
+ *
+ * Resweep sessions (SFA_SESSION_RESWEEP).  With SFA_RNA and without SFA_INV the query rows are the events REVERSED
+ * (src/sigfish.c:860-863): a new event becomes row 0, every cell below it changes, and no carried row can be extended.  Such a
+ * query can only be swept again, and a resweep session does that at the points where the normalisation changes anyway:
+ *   - the window W of a slot is the rule of sfa_session_raw_recalibrate below, unchanged (frozen at norm without a list;
+ *     SFA_RECAL_AT_END included);
+ *   - when a call leaves the slot with another W than its row spans -- the first calibration is the case "from 0" -- the device
+ *     computes mean and sd over final events [skip, skip + W), writes the query of W events,
+ *     q[i] = z(event[skip + W - 1 - i]) for SFA_RNA without SFA_INV and q[i] = z(event[skip + i]) otherwise, and sweeps it as a
+ *     first chunk inside that call (beyond SFA_MAX_QUERY events as consecutive pieces); a call that passes several points takes
+ *     the last;
+ *   - a call that does not change W sweeps nothing: out[i] is the slot's current row, and events beyond skip + W wait in the
+ *     event table for the next point.
+ * So after ANY call out[i] is, bit for bit, the row sfa_align_batch gives on the same context for the pA means of events
+ * [skip, skip + W), z-normalised over themselves and given in event order (SFA_SESSION_NO_START as documented); info.q_events,
+ * info.norm_window and sfa_session_lengths report W, sfa_session_query_span ends at event skip + W - 1, and status bit 4 marks
+ * every call that swept a slot again: every change of W after the first.  State and rows depend on the samples received, not
+ * on how they were cut into calls.  Poisoning, full and end of read are as on any raw session.  Under a doubling list
+ * (norm, 2 norm, ..., q = norm x 2^m) a read is swept over 2 q - norm events in all.
+ * A resweep session accepts every context a session accepts, and SFA_RNA without SFA_INV as well (still not SFA_DTW, not group
+ * contexts).  It is raw mode only: sfa_session_extend on it is SFA_EINVAL before and after sfa_session_raw_config -- the caller's
+ * events are not kept, so nothing could be swept again.  sfa_session_raw_config, sfa_session_raw_recalibrate, sfa_session_reset,
+ * sfa_session_events, sfa_session_query_span and sfa_session_row work as on any raw session. */
 int sfa_session_raw_config(sfa_session_t *s, int32_t skip_events, int32_t norm_events, int32_t query_events);
 
 typedef struct {

@@ -269,10 +269,13 @@ class Aligner:
                "sfa_align_events")
         return out
 
-    def session(self, n_slots, starts=True):
+    def session(self, n_slots, starts=True, resweep=False, flags=None):
         """An alignment session of n_slots growing reads on this aligner (sfa_session_create); starts=False carries costs only
-        (SFA_SESSION_NO_START: half the memory, the coordinate on the start side of every row is -1)."""
-        return Session(self, n_slots, starts)
+        (SFA_SESSION_NO_START: half the memory, the coordinate on the start side of every row is -1).  resweep=True
+        (SFA_SESSION_RESWEEP): a raw-mode-only session that sweeps a slot only when its normalisation window changes, over the
+        window's events -- the one kind of session an RNA aligner without INV can have (its query is the events reversed).
+        flags: the raw flag word in place of starts / resweep."""
+        return Session(self, n_slots, starts, resweep, flags)
 
     def set_option(self, key, value):
         _check(self._L.sfa_set_option(self._h, key.encode(), int(value)), f"sfa_set_option({key})")
@@ -393,20 +396,29 @@ class Aligner:
 
 
 SESSION_NO_START = 0x1
+SESSION_RESWEEP = 0x4  # (0x2 is unassigned)
+
+
+def _session_flags(starts, resweep):
+    return (0 if starts else SESSION_NO_START) | (SESSION_RESWEEP if resweep else 0)
 
 
 class Session:
     """Slots whose alignment is extended as their events arrive: after every extend() a slot's row is the row align_db returns
     for all events the slot has received since its last reset.  Belongs to its Aligner: close it first (closing the Aligner frees
-    the native session as well, this object is then closed)."""
+    the native session as well, this object is then closed).
+    resweep=True: raw mode only (extend() is refused).  A slot is swept when the window W of its normalisation changes
+    (recal_window), over events [skip, skip + W) -- reversed on an RNA aligner without INV -- and between such calls its row
+    stands: after every extend_raw() the row is align_db of those W events normalised over themselves, and info["q_events"] and
+    lengths() report W."""
 
-    def __init__(self, aligner, n_slots, starts=True):
+    def __init__(self, aligner, n_slots, starts=True, resweep=False, flags=None):
         self._al = aligner
         self._L = aligner._L
         self._h = C.c_void_p()
-        self.n_slots, self.starts = int(n_slots), bool(starts)
-        _check(self._L.sfa_session_create(aligner._h, self.n_slots, 0 if starts else SESSION_NO_START, C.byref(self._h)),
-               "sfa_session_create")
+        fl = _session_flags(starts, resweep) if flags is None else int(flags)
+        self.n_slots, self.starts, self.resweep = int(n_slots), not fl & SESSION_NO_START, bool(fl & SESSION_RESWEEP)
+        _check(self._L.sfa_session_create(aligner._h, self.n_slots, fl, C.byref(self._h)), "sfa_session_create")
         self._al_h = aligner._h.value  # the native context this session belongs to
 
     def _live(self):
@@ -550,10 +562,10 @@ class Session:
         self.close()
 
 
-def session_bytes(total_columns, n_slots, starts=True):
+def session_bytes(total_columns, n_slots, starts=True, resweep=False):
     """Device memory the carried rows of a session take (sfa_session_bytes; host arithmetic, no GPU needed): RefModel.total_columns()
-    x n_slots x 8 bytes, x 4 without starts."""
-    b = int(_lib.load().sfa_session_bytes(int(total_columns), int(n_slots), 0 if starts else SESSION_NO_START))
+    x n_slots x 8 bytes, x 4 without starts; the same with resweep (a window beyond 2048 events runs as pieces over a carried row)."""
+    b = int(_lib.load().sfa_session_bytes(int(total_columns), int(n_slots), _session_flags(starts, resweep)))
     if b < 0:
         raise SfaError(f"sfa_session_bytes failed ({b}): total_columns and n_slots must be positive")
     return b

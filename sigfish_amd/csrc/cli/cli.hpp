@@ -75,6 +75,7 @@ struct RealtimeOpt {
     std::vector<int32_t> recal_at; // --recalibrate: window lengths at which a slot is renormalised ("double" is expanded)
     bool recal_at_end = false;     // --recalibrate-at-end: a read that ends short is normalised over all its query events
                                    // (SFA_RECAL_AT_END), and q is the last of recal_at, so a full read over q
+    bool resweep = false;          // --resweep: the session is created with SFA_SESSION_RESWEEP (lifts --rna's need for --invert)
 };
 
 // options.cpp: the option table, help and every check that needs no file and no device (exits for -V and help)

@@ -19,7 +19,7 @@ enum LongOpt {
     O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
     O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
     O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE,
-    O_RECALIBRATE, O_RECALIBRATE_AT_END
+    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP
 };
 
 const option kLongOptions[] = {
@@ -111,7 +111,7 @@ const option kRealtimeOptions[] = {
     {"norm-events", required_argument, 0, O_NORM_EVENTS}, {"min-events", required_argument, 0, O_MIN_EVENTS},
     {"min-mapq", required_argument, 0, O_MIN_MAPQ}, {"pace", required_argument, 0, O_PACE},
     {"recalibrate", required_argument, 0, O_RECALIBRATE}, {"recalibrate-at-end", no_argument, 0, O_RECALIBRATE_AT_END},
-    {"dtw-std", no_argument, 0, O_DTW_STD}, {"from-end", no_argument, 0, O_FROM_END}, {"sam", no_argument, 0, 'a'},
+    {"resweep", no_argument, 0, O_RESWEEP}, {"dtw-std", no_argument, 0, O_DTW_STD}, {"from-end", no_argument, 0, O_FROM_END}, {"sam", no_argument, 0, 'a'},
     {"secondary", required_argument, 0, O_SECONDARY}, {"ranks", required_argument, 0, O_RANKS},
     {0, 0, 0, 0}};
 
@@ -134,8 +134,11 @@ void realtime_help(FILE *fp, const RealtimeOpt &r) {
     fprintf(fp, "   --pore STR                 set the pore chemistry (r9, r10 or rna004) [auto]\n");
     fprintf(fp, "   --device INT               the GPU to use (a session lives on one device) [0]\n");
     fprintf(fp, "   --kmer-model FILE          nucleotide k-mer model file (required: builtin models are not bundled)\n");
-    fprintf(fp, "   --rna                      the dataset is direct RNA (needs --invert: a session cannot take the query reversed)\n");
+    fprintf(fp, "   --rna                      the dataset is direct RNA (needs --invert or --resweep: a session cannot extend a reversed query)\n");
     fprintf(fp, "   --invert                   reverse the reference events instead of query\n");
+    fprintf(fp, "   --resweep                  sweep a read only when its normalisation window changes (calibration, every --recalibrate point,\n"
+                "                              --recalibrate-at-end), over the window's events: with --rna the query is the events reversed,\n"
+                "                              as dtw takes it without --invert; ne:i and --min-events count the window [off]\n");
     fprintf(fp, "   -q INT                     query events at which a read is full [%d]\n", r.o.query);
     fprintf(fp, "   -p INT                     the number of events to trim at query signal start, >= 0 [%d]\n\nreplay options:\n", r.o.prefix);
     fprintf(fp, "   --channels INT             channels of the flow cell = slots of the session [%d]\n", r.channels);
@@ -195,6 +198,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
             case O_PACE: r.pace = yes_or_no(optarg, "pace"); break;
             case O_RECALIBRATE: recal = optarg; break;
             case O_RECALIBRATE_AT_END: r.recal_at_end = true; break;
+            case O_RESWEEP: r.resweep = true; break;
             default: realtime_help(stderr, r); exit(EXIT_FAILURE);
         }
     }
@@ -213,7 +217,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     if (o.ranks != 0) die("realtime: --ranks is not available: a replay is one process on one device");
     if (o.devices.size() != 1) die("realtime: --device takes exactly one GPU: a session's rows live on one device");
     if ((o.flag & F_INV) && !(o.flag & F_RNA)) die("Inversion is only available for RNA.");
-    if ((o.flag & F_RNA) && !(o.flag & F_INV)) die("realtime: --rna needs --invert: without it the query rows are the events reversed, and a session cannot take new events as row 0");
+    if ((o.flag & F_RNA) && !(o.flag & F_INV) && !r.resweep) die("realtime: --rna needs --invert (or --resweep): without it the query rows are the events reversed, and a session cannot take new events as row 0");
     if (r.norm_events < 0) r.norm_events = o.query;
     if (r.min_events < 0) r.min_events = o.query;
     if (r.norm_events < 25 || r.norm_events > o.query) die("realtime: --norm-events should be 25..q (the value of -q)");

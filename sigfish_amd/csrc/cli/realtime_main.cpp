@@ -1,7 +1,8 @@
 // realtime_main.cpp -- `sigfish-amd realtime`: a BLOW5 file replayed through a raw-signal session as a flow cell would deliver
 // it (the schedule: replay.hpp), a PAF line at the moment a read is decided, and the time a tick takes against the signal time
 // it stands for.  The hot path is the library's (sfa_session_extend_raw: detector, normalisation -- frozen, or growing with the
-// read under --recalibrate --, sweep); what runs here
+// read under --recalibrate; with --resweep swept only when that window changes, which is what direct RNA without --invert
+// needs --, sweep); what runs here
 // is the staging of a tick's samples, the decision rule and the printing.
 #include <algorithm>
 #include <chrono>
@@ -146,13 +147,14 @@ int realtime_run(int argc, char **argv, double t0) {
     sfa::Blow5Reader reader;
     if (!reader.open(o.blow5)) die(reader.error());
     detect_chemistry(reader, &o);
-    if ((o.flag & F_RNA) && !(o.flag & F_INV)) die("realtime: the file holds direct RNA: pass --rna --invert (a session cannot take the query reversed)");
+    if ((o.flag & F_RNA) && !(o.flag & F_INV) && !r.resweep)
+        die("realtime: the file holds direct RNA: pass --rna --invert, or --rna --resweep (a session cannot extend a reversed query)");
     const Reference ref(o);
     Context ctx;
     if (sfa_init(&ctx.c, &ref.view, o.flag, o.devices[0]) != SFA_OK) die(std::string("accelerator init failed: ") + sfa_last_error());
     if (sfa_set_pore(ctx.c, o.pore_flag) != SFA_OK) die(sfa_last_error());
     sfa_session_t *se = nullptr;  // (freed with its context)
-    if (sfa_session_create(ctx.c, r.channels, 0, &se) != SFA_OK) die(std::string("session: ") + sfa_last_error());
+    if (sfa_session_create(ctx.c, r.channels, r.resweep ? SFA_SESSION_RESWEEP : 0, &se) != SFA_OK) die(std::string("session: ") + sfa_last_error());
     if (sfa_session_raw_config(se, o.prefix, r.norm_events, o.query) != SFA_OK) die(std::string("session: ") + sfa_last_error());
     if (!r.recal_at.empty() || r.recal_at_end)
         if (sfa_session_raw_recalibrate(se, r.recal_at.data(), static_cast<int32_t>(r.recal_at.size()), r.recal_at_end ? SFA_RECAL_AT_END : 0) != SFA_OK)

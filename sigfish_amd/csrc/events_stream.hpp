@@ -21,6 +21,8 @@
 // normalised means of the new events to the slot's device-resident query, from where the session sweep takes them.  With
 // recalibration points (sfa_session_raw_recalibrate, recal_rule.hpp) the window grows with the read: when it does, the
 // statistics are computed again over the longer window and the whole query is rewritten, to be swept from event 0.
+// In resweep mode (SFA_SESSION_RESWEEP) that is the only way a query is written: nothing is appended, a change of the window
+// writes the window's events -- reversed, for RNA without SFA_INV -- and between two changes the query and its row stand.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -292,6 +294,8 @@ struct EvNormArgs {
     int32_t n_at;            // recalibration points (recal_rule.hpp); 0 and no flags: the window is frozen at norm
     uint32_t flags;          // kRecalAtEnd
     int32_t at[kRecalMaxPoints];
+    int32_t resweep;         // SFA_SESSION_RESWEEP: the query is the window's W events, written only when W changes
+    int32_t reversed;        // (with resweep) q[i] = z(event[skip + W - 1 - i]): SFA_RNA without SFA_INV
 };
 
 constexpr int kNormTile = 2048;  // pA means staged per tile of the statistics: 8 KB of LDS
@@ -301,6 +305,9 @@ constexpr int kNormTile = 2048;  // pA means staged per tile of the statistics: 
 // [skip, skip + W): all lanes stage the window's pA means from the 24-byte records into LDS, tile by tile, and lane 0 runs
 // sfa_znormalise's two sequential fp32 loops over them (so the result is the host's bit for bit); then all lanes rewrite the
 // WHOLE query [0, q_avail) and the host sweeps it as a first chunk.  Otherwise the new events are appended as before.
+// Resweep mode (a.resweep, block-uniform like a.reversed): no append.  A change of W writes q[0, W) -- lane l stores q[i] from
+// record skip + i, or skip + W - 1 - i when reversed: consecutive lanes still read consecutive records -- and reports q_first = 0,
+// q_new = W; any other call reports q_new = 0 and leaves q_done = W.  Events beyond skip + W wait in the table for the next point.
 __global__ void __launch_bounds__(64) ev_stream_norm_kernel(const EvNormArgs a) {
     __shared__ float tile[kNormTile];
     __shared__ float stat[2];
@@ -352,15 +359,17 @@ __global__ void __launch_bounds__(64) ev_stream_norm_kernel(const EvNormArgs a) 
         if (!(sd > 0.0f) || sd > 3.402823466e+38f) status |= kRawPoisoned;  // zero, NaN or inf: no query can be made of it
     }
     const int q_first = recal ? 0 : q_done;
+    const int q_end = a.resweep ? (recal ? w : q_first) : q_avail;  // one behind the last query event this call writes
+    const int q_top = a.reversed ? q_end - 1 : 0;                   // reversed: the event that goes to q[0]
     int q_new = 0;
     if (lane == 0) s_status = 0;
     __syncthreads();
     if ((status & kRawCalibrated) && !(status & kRawPoisoned)) {
-        q_new = q_avail - q_first;
+        q_new = q_end - q_first;
         float *q = a.query + static_cast<int64_t>(slot) * a.query_cap;
         bool bad = false;
-        for (int e = q_first + lane; e < q_avail; e += 64) {
-            const float v = (ev[a.skip + e].mean - mean) / sd;
+        for (int e = q_first + lane; e < q_end; e += 64) {
+            const float v = (ev[a.skip + (a.reversed ? q_top - e : e)].mean - mean) / sd;
             q[e] = v;
             bad = bad || !(fabsf(v) <= 3.402823466e+38f);
         }

@@ -17,6 +17,7 @@ struct sfa_session {
     sfa_ctx *c = nullptr;
     int32_t n_slots = 0;
     bool track = true;  // start columns are carried (no SFA_SESSION_NO_START)
+    bool resweep = false;  // SFA_SESSION_RESWEEP: raw mode only; a slot is swept when its window changes, over the window's events
     std::vector<int64_t> len;     // events every slot has received since its last reset
     std::vector<uint8_t> poison;  // a chunk of the slot held a NaN / inf: no rows until reset
     std::vector<int32_t> stamp;   // call in which the slot was named last (duplicates inside one call)
@@ -117,6 +118,8 @@ void plan_launch(std::vector<Piece> &pieces, int32_t n_jobs, Launch *l) {
 }
 
 size_t align8(size_t x) { return (x + 7) & ~static_cast<size_t>(7); }
+
+constexpr uint32_t kSessionFlags = SFA_SESSION_NO_START | SFA_SESSION_RESWEEP;  // (0x2 is not assigned)
 
 // raw mode: the slot's next chunk is marked fresh, and ev_stream_kernel then starts from the initial detector state
 void reset_raw_slot(sfa_session *s, int32_t sl) {
@@ -319,7 +322,8 @@ static int sweep_chunks(sfa_session *s, const int32_t *slot, const Chunk *ch, in
 extern "C" {
 
 int64_t sfa_session_bytes(int64_t total_columns, int32_t n_slots, uint32_t session_flags) {
-    if (total_columns <= 0 || n_slots <= 0 || (session_flags & ~static_cast<uint32_t>(SFA_SESSION_NO_START))) return SFA_EINVAL;
+    if (total_columns <= 0 || n_slots <= 0 || (session_flags & ~kSessionFlags)) return SFA_EINVAL;
+    // (SFA_SESSION_RESWEEP changes nothing here: a window beyond SFA_MAX_QUERY events runs as pieces over the carried row)
     const int64_t per_column = (session_flags & SFA_SESSION_NO_START) ? 4 : 8;
     if (total_columns > INT64_MAX / per_column / n_slots) return SFA_ERANGE;
     return total_columns * n_slots * per_column;  // one row per slot, updated in place
@@ -329,17 +333,19 @@ int sfa_session_create(sfa_ctx_t *c, int32_t n_slots, uint32_t session_flags, sf
     if (!c || !out) return fail(SFA_EINVAL, "sfa_session_create: null argument");
     if (!c->shards.empty()) return fail(SFA_EINVAL, "sfa_session_create: a session's rows live on one device; use a single-device context (sfa_init)");
     if (c->flag & SFA_DTW) return fail(SFA_EINVAL, "sfa_session_create: sessions extend the subsequence DTW; the context has SFA_DTW");
-    if ((c->flag & SFA_RNA) && !(c->flag & SFA_INV))
+    const bool resweep = (session_flags & SFA_SESSION_RESWEEP) != 0;  // (unknown bits beside it are refused below)
+    if ((c->flag & SFA_RNA) && !(c->flag & SFA_INV) && !resweep)
         return fail(SFA_EINVAL, "sfa_session_create: with SFA_RNA and without SFA_INV the query rows are the events reversed, so new events "
                                 "would become row 0; nothing carried over could be kept");
     if (n_slots <= 0) return fail(SFA_EINVAL, "sfa_session_create: n_slots must be positive, not %d", n_slots);
-    if (session_flags & ~static_cast<uint32_t>(SFA_SESSION_NO_START)) return fail(SFA_EINVAL, "sfa_session_create: unknown flag bits 0x%x", session_flags);
+    if (session_flags & ~kSessionFlags) return fail(SFA_EINVAL, "sfa_session_create: unknown flag bits 0x%x", session_flags);
     if (sfa_session_bytes(c->model.total_cols, n_slots, session_flags) < 0) return fail(SFA_ENOMEM, "sfa_session_create: the carried rows do not fit");
     HIP_TRY(hipSetDevice(c->device));
     std::unique_ptr<sfa_session> s(new sfa_session());
     s->c = c;
     s->n_slots = n_slots;
     s->track = !(session_flags & SFA_SESSION_NO_START);
+    s->resweep = resweep;
     s->len.assign(n_slots, 0);
     s->poison.assign(n_slots, 0);
     s->stamp.assign(n_slots, 0);
@@ -435,6 +441,9 @@ int sfa_session_lengths(sfa_session_t *s, const int32_t *slot, int32_t n, int64_
 
 int sfa_session_extend(sfa_session_t *s, const int32_t *slot, const float *events, const int64_t *ev_off, int32_t n, sfa_result_t *out) {
     if (!s || n < 0 || (n > 0 && (!slot || !ev_off || !out))) return fail(SFA_EINVAL, "sfa_session_extend: bad argument");
+    if (s->resweep)
+        return fail(SFA_EINVAL, "sfa_session_extend: the session was created with SFA_SESSION_RESWEEP: the caller's events are not kept, so nothing could be "
+                                "swept again; it takes samples (sfa_session_raw_config, sfa_session_extend_raw)");
     if (s->raw) return fail(SFA_EINVAL, "sfa_session_extend: the session is in raw mode (sfa_session_raw_config): it takes samples, sfa_session_extend_raw");
     if (n == 0) return SFA_OK;
     sfa_ctx *c = s->c;
@@ -665,6 +674,8 @@ int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t 
     na.n_at = s->recal_n;
     na.flags = s->recal_flags;
     for (int32_t k = 0; k < sfa::kRecalMaxPoints; ++k) na.at[k] = k < s->recal_n ? s->recal_at[k] : 0;
+    na.resweep = s->resweep ? 1 : 0;
+    na.reversed = (s->resweep && (c->flag & SFA_RNA) && !(c->flag & SFA_INV)) ? 1 : 0;
     hipLaunchKernelGGL(sfa::ev_stream_norm_kernel, dim3(n), dim3(64), 0, st, na);
     KERNEL_TRY();
     HIP_TRY(hipEventRecord(s->ev_raw[2], st));
@@ -685,7 +696,8 @@ int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t 
         s->raw_sd[sl] = ro[i].sd;
         s->raw_window[sl] = ro[i].window;
         // a recalibrated slot: its whole query was rewritten, so it is swept as a first chunk, which reads no carried row and
-        // writes a new one (the planner never puts first and carried chunks into one wave)
+        // writes a new one (the planner never puts first and carried chunks into one wave).  A resweep session knows no other
+        // sweep: q_new is the window then, and 0 in every call that leaves the window as it is
         if (ro[i].q_new > 0 && ro[i].q_first == 0) s->len[sl] = 0;
         ch[i] = Chunk{static_cast<int64_t>(sl) * s->query + ro[i].q_first, ro[i].q_new};
     }

@@ -8,6 +8,8 @@ ticks, the same calls, the same lines.  The schedule counts ticks, never seconds
             chunk shorter than chunk_samples (empty when the read's length is a multiple of it) is the last and carries the end
   windows   with recalibrate / at_end the session renormalises a slot over a longer window as it grows (api.recal_window) and sweeps
             it again inside the call; the schedule and the decision rule do not change
+  resweep   --resweep: the session is created with SESSION_RESWEEP (a slot is swept only when its window changes, over the
+            window's events; what direct RNA without --invert needs); schedule and rule are the same, q_events counts the window
   decision  decide(): 'E' early (calibrated, q_events >= min_events, mapped, mapq >= min_mapq), 'F' full, 'R' end of read (or a
             poisoned slot); a decision has a line when its row is mapped
   after it  decided channels are reset in one call and take the next unread reads, lowest channel first, from tick t + 1 on
@@ -38,8 +40,9 @@ class Schedule:
     next unread record of the file on the channel and returns its length (None: the file has no more); `trace`, a list, receives
     the lines the C++ schedule prints."""
 
-    def __init__(self, channels, chunk_samples, trace=None):
+    def __init__(self, channels, chunk_samples, trace=None, resweep=False):
         self.chunk, self.trace = int(chunk_samples), trace
+        self.resweep = bool(resweep)  # of the session; nothing here reads it: the schedule does not depend on it
         self.read, self.len, self.sent = [-1] * channels, [0] * channels, [0] * channels
         self.tick, self.next_read, self.entries = 0, 0, []
 
@@ -97,7 +100,7 @@ def recal_points(norm, query, recalibrate=(), at_end=False):
     return at
 
 
-def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False):
+def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False, resweep=False):
     """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
 
     reads: iterable of (read_id, meta, samples) in file order, as Blow5File yields them (taken lazily: at most `channels` reads are
@@ -105,7 +108,9 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     Session.query_span; reason: 'E', 'F' or 'R'.  A decision has a line when mapped(row): format_line().  `session`: an object with
     extend_raw / query_span / reset in place of aligner.session(channels) in raw mode (the schedule's tests pass a stub).
     recalibrate / at_end: --recalibrate (a list of window lengths, or "double": api.recal_double(norm, query)) and
-    --recalibrate-at-end, turned into the session's points by recal_points(); schedule and decision rule are the same with them."""
+    --recalibrate-at-end, turned into the session's points by recal_points(); schedule and decision rule are the same with them.
+    resweep: --resweep, the session is aligner.session(channels, resweep=True); info["q_events"], which the rule and the line read,
+    is then the slot's window."""
     reads = iter(reads)
     on = [None] * channels  # (index, read_id, meta, samples) per channel
 
@@ -122,9 +127,9 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
             return len(raw)
 
     src = Source()
-    sch = Schedule(channels, chunk_samples, trace)
+    sch = Schedule(channels, chunk_samples, trace, resweep)
     own = session is None
-    se = aligner.session(channels) if own else session
+    se = aligner.session(channels, resweep=resweep) if own else session
     try:
         if own:
             se.configure_raw(skip, norm, query, recal_points(norm, query, recalibrate, at_end), at_end)

@@ -213,14 +213,16 @@ R9_DNA_META = dict(digitisation=8192.0, offset=6.0, range=1467.61, sampling_rate
 RAW_DNA_KINDS = ("mapped", "random", "stalled", "flat")
 
 
-def make_dna_raw_reads(records, level_mean, k, n_reads, seed=0, samples=(2000, 9000), dwell=(6, 13), noise=1.5, kinds=("mapped",), meta=R9_DNA_META):
+def make_dna_raw_reads(records, level_mean, k, n_reads, seed=0, samples=(2000, 9000), dwell=(6, 13), noise=1.5, kinds=("mapped",), meta=R9_DNA_META, rna=False):
     """Seeded raw DNA reads [(read_id, digitisation, offset, range, sampling_rate, int16 samples)] over [(name, sequence)] and a
     4^k table of level means (pA).  Read r is of kind kinds[r % len(kinds)]:
       mapped  the levels of consecutive k-mers from a random (contig, strand, start), each held for dwell[0] .. dwell[1] - 1
               samples, plus N(0, noise); behind the contig's end the read goes on with random k-mers
       random  random k-mers all the way: a signal that belongs nowhere
       stalled random k-mers for 200 .. 330 samples, then one level without noise: the events stop long before the read does
-      flat    one level, no noise: the detector finds no event"""
+      flat    one level, no noise: the detector finds no event
+    rna: direct RNA instead -- a mapped read follows the forward strand only, from its start k-mer BACKWARDS (the molecule passes
+    the pore 3' to 5', which is why the reference takes the query reversed, src/sigfish.c:860-863)."""
     rng = np.random.default_rng(seed)
     lv = np.asarray(level_mean, np.float32)
     code = np.full(256, 0, np.int64)
@@ -244,7 +246,7 @@ def make_dna_raw_reads(records, level_mean, k, n_reads, seed=0, samples=(2000, 9
         idx = rng.integers(0, len(lv), len(d))
         if kind == "mapped":
             c = int(rng.choice(len(fwd), p=lens / lens.sum()))
-            along = (rev if rng.integers(0, 2) else fwd)[c]
+            along = fwd[c][::-1] if rna else (rev if rng.integers(0, 2) else fwd)[c]
             at = int(rng.integers(0, max(len(along) - 100, 1)))
             m = min(len(along) - at, len(d))
             idx[:m] = along[at:at + m]

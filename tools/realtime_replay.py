@@ -10,7 +10,11 @@ Every run is its own process under its own `timeout -k 10`; the driver stops at 
 prints on stderr (reads, lines by reason, samples sent, per-tick wall time: mean, median, 99th percentile, maximum, ticks beyond the
 tick's signal time) is stored as profiles/realtime_<build id>/<name>.log, the PAF next to the BLOW5 file.  The condition to read it
 against: the 99th percentile of the tick time must stay under chunk-samples / sampling rate ("Replaying a file in real
-time")."""
+time").
+With --rna the reads are direct RNA instead (they follow the forward strand of the RNA sequin reference backwards, dwell 10 .. 24
+samples per k-mer for the RNA detector's longer windows) and there is one run, through a resweep session:
+  rna_resweep  --rna --resweep --norm-events 25 --recalibrate double: calibrated on 25 events, swept again at 50, 100, 200 and 250
+Its log goes to profiles/realtime_resweep_<build id>/."""
 import argparse
 import os
 import subprocess
@@ -26,6 +30,8 @@ from sigfish_amd import synth  # noqa: E402
 BIN = os.path.join(ROOT, "sigfish_amd", "bin", "sigfish-amd")
 FASTA = os.path.join(ROOT, "tests", "golden", "data", "nCoV-2019.reference.fasta")
 RUNS = (("defaults", []), ("early", ["-q", "1000", "--norm-events", "100", "--min-events", "100", "--min-mapq", "20"]))
+RNA_FASTA = os.path.join(ROOT, "tests", "golden", "data", "rnasequin_sequences_2.4.fa")
+RNA_RUNS = (("rna_resweep", ["--rna", "--resweep", "--norm-events", "25", "--recalibrate", "double"]),)
 
 
 def main():
@@ -37,11 +43,13 @@ def main():
     ap.add_argument("--timeout", type=int, default=420, help="seconds per replay")
     ap.add_argument("--workdir", default=None, help="where the BLOW5 file and the PAFs go [a temporary directory]")
     ap.add_argument("--no-log", action="store_true")
+    ap.add_argument("--rna", action="store_true", help="direct RNA reads through a resweep session (one run: rna_resweep)")
     a = ap.parse_args()
     work = a.workdir or tempfile.mkdtemp(prefix="realtime_replay_")
     os.makedirs(work, exist_ok=True)
-    k = 6
-    model = os.path.join(work, "syn6.model")
+    k = 5 if a.rna else 6
+    fasta, runs = (RNA_FASTA, RNA_RUNS) if a.rna else (FASTA, RUNS)
+    model = os.path.join(work, f"syn{k}.model")
     with open(model, "w") as f:
         import itertools
         f.write(f"#k\t{k}\nkmer\tlevel_mean\tlevel_stdv\tsd_mean\tsd_stdv\n")
@@ -49,16 +57,16 @@ def main():
             f.write("%s\t%.4f\t1.5000\t1.0\t1.0\n" % ("".join(kmer), v))
     levels, _ = S.read_kmer_model(model)
     t0 = time.perf_counter()
-    reads = synth.make_dna_raw_reads(S.read_fasta(FASTA), levels, k, a.reads, seed=5)
+    reads = synth.make_dna_raw_reads(S.read_fasta(fasta), levels, k, a.reads, seed=5, **(dict(dwell=(10, 25), rna=True) if a.rna else {}))
     blow5 = os.path.join(work, "reads.blow5")
     synth.write_blow5(blow5, reads)
     n_samples = sum(len(r[5]) for r in reads)
     del reads
     print(f"[{S.build_id()}] {a.reads} reads, {n_samples} samples written to {blow5} in {time.perf_counter() - t0:.1f} s", flush=True)
-    logdir = os.path.join(ROOT, "profiles", f"realtime_{S.build_id()}")
-    for name, extra in RUNS:
+    logdir = os.path.join(ROOT, "profiles", f"realtime_{'resweep_' if a.rna else ''}{S.build_id()}")
+    for name, extra in runs:
         cmd = ["timeout", "-k", "10", str(a.timeout), BIN, "realtime", "--kmer-model", model, "--verbose", "3", "-t", str(a.threads), "--channels", str(a.channels),
-               "--chunk-samples", str(a.chunk_samples), *extra, "-o", os.path.join(work, name + ".paf"), FASTA, blow5]
+               "--chunk-samples", str(a.chunk_samples), *extra, "-o", os.path.join(work, name + ".paf"), fasta, blow5]
         t0 = time.perf_counter()
         r = subprocess.run(cmd, capture_output=True)
         head = f"[{S.build_id()}] {name}: {' '.join(cmd[4:])}\n[{S.build_id()}] exit status {r.returncode} after {time.perf_counter() - t0:.1f} s\n"
