@@ -513,6 +513,15 @@ int sfa_align_blow5(sfa_ctx_t *ctx, const uint8_t *records, const int64_t *rec_o
 int sfa_inflate_zlib_device(sfa_ctx_t *ctx, const uint8_t *in, const int64_t *in_off, int32_t n, uint8_t *out, const int64_t *out_off,
                             int32_t *out_len);
 
+/* The event detection of sfa_align_raw on its own (tests): every read's WHOLE event table instead of the query window, means in
+ * pA (not normalised).  raw, raw_off[n_reads+1], scaling as for sfa_align_raw; the context's flag selects the DNA or RNA detector
+ * and option "ev_parallel" is honoured.  Read i owns events[raw_off[i] + 2 * i ...], room for its samples + 2 records (the
+ * device's own capacity rule), of which the first n_events[i] are written.  route[i]: bit 0 = the sequential prefix-sum kernel
+ * summed this read, bit 1 = the sequential peak picker walked it (clear: the wave-per-read kernel certified its own result).
+ * t_short / t_long: NULL, or raw_off[n_reads] floats each, the two t-statistics of every sample.  Single-device context. */
+int sfa_detect_events_device(sfa_ctx_t *ctx, const int16_t *raw, const int64_t *raw_off, const double *scaling, int32_t n_reads,
+                             sfa_event_t *events, int32_t *n_events, int32_t *route, float *t_short, float *t_long);
+
 /* Page-locked host memory for the buffers handed to sfa_align_raw / sfa_align_batch (uploads from pageable memory
  * run at a fraction of the PCIe rate).  Plain malloc-style pair; NULL on failure. */
 void *sfa_pinned_alloc(size_t bytes);

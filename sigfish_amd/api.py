@@ -383,6 +383,30 @@ class Aligner:
                                                lens.ctypes.data_as(_lib.i32p)), "sfa_inflate_zlib_device")
         return [None if lens[i] < 0 else out[out_off[i]:out_off[i] + lens[i]].tobytes() for i in range(n)]
 
+    def detect_events_device(self, raw, raw_off, scaling, tstats=False):
+        """The event detection of align_raw alone (tests): -> (tables, routes[, t_short, t_long]).  tables: one EVENT_DTYPE
+        array per read, the whole table, means in pA; routes int32[n]: bit 0 = sequential prefix sums, bit 1 = sequential
+        peak picker; tstats: also the two t-statistics, float32[raw_off[n]] each."""
+        raw = np.ascontiguousarray(raw, np.int16)
+        ro = np.ascontiguousarray(raw_off, np.int64)
+        sc = np.ascontiguousarray(scaling, np.float64).reshape(-1)
+        n = len(ro) - 1
+        total = int(ro[-1]) if n > 0 else 0
+        ev = np.zeros(max(total, 0) + 2 * n, EVENT_DTYPE)
+        nev = np.zeros(max(n, 1), np.int32)
+        routes = np.zeros(max(n, 1), np.int32)
+        t1 = np.zeros(max(total, 1), np.float32) if tstats else None
+        t2 = np.zeros(max(total, 1), np.float32) if tstats else None
+        if raw.size == 0:
+            raw = np.zeros(1, np.int16)
+        _check(self._L.sfa_detect_events_device(self._h, raw.ctypes.data_as(C.POINTER(C.c_int16)), ro.ctypes.data_as(_lib.i64p),
+                                                sc.ctypes.data_as(C.POINTER(C.c_double)), n, ev.ctypes.data_as(C.c_void_p),
+                                                nev.ctypes.data_as(_lib.i32p), routes.ctypes.data_as(_lib.i32p),
+                                                t1.ctypes.data_as(_lib.f32p) if tstats else None,
+                                                t2.ctypes.data_as(_lib.f32p) if tstats else None), "sfa_detect_events_device")
+        tables = [ev[int(ro[i]) + 2 * i:int(ro[i]) + 2 * i + int(nev[i])] for i in range(n)]
+        return (tables, routes[:n], t1[:total], t2[:total]) if tstats else (tables, routes[:n])
+
     def sync(self):
         _check(self._L.sfa_sync(self._h), "sfa_sync")
 

@@ -28,55 +28,17 @@ int sfa_align_raw_ex(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_off, c
     return align_raw_impl(c, raw, raw_off, scaling, n, prefix_size, query_size, rows, info, query_events);
 }
 
-// raw == nullptr: the samples are already in c->raw.e_raw (decoded on the device, sfa_align_blow5), laid out by raw_off
-static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_off, const double *scaling, int32_t n, int32_t prefix_size,
-                          int32_t query_size, sfa_result_t *rows, sfa_query_info_t *info, sfa_event_t *query_events) {
-    // the reference's own checks of -p -1 (src/dtw_main.c:263-276)
-    if (prefix_size < 0 && (!(c->flag & SFA_RNA) || (c->flag & (SFA_END | SFA_INV))))
-        return fail(SFA_EINVAL, "sfa_align_raw: automatic query start (prefix_size < 0) needs an RNA context without SFA_END or SFA_INV");
-    if (query_size <= 0) return fail(SFA_EINVAL, "sfa_align_raw: query_size must be positive");
-    if (n == 0) return SFA_OK;
-    if (!c->shards.empty()) {
-        c->maps.map_n = -1;
-        const int grc = for_each_shard_range(c, n, [&](size_t r, int32_t a, int32_t b) {
-            std::vector<int64_t> off(b - a + 1);  // the shard's sample offsets start at 0
-            for (int32_t i = a; i <= b; ++i) off[i - a] = raw_off[i] - raw_off[a];
-            if (!raw) return fail(SFA_EINVAL, "sfa_align_raw: device-resident samples need a single-device context");
-            return sfa_align_raw_ex(c->shards[r], raw + raw_off[a], off.data(), scaling + 3 * static_cast<size_t>(a), b - a, prefix_size,
-                                    query_size, rows + a, info + a,
-                                    query_events ? query_events + static_cast<size_t>(a) * static_cast<size_t>(query_size) : nullptr);
-        });
-        if (!grc) c->maps.map_n = n;  // (sfa_event_maps splits its rows by the same ranges)
-        return grc;
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    if (raw) HIP_TRY(hipStreamSynchronize(c->stream));  // (device-resident samples: their decoder is still in flight on this stream)
-    const int64_t total = raw_off[n] - raw_off[0];
-    if (total < 0 || raw_off[0] != 0) return fail(SFA_EINVAL, "sfa_align_raw: raw_off must start at 0 and be monotone");
-    const bool rna = (c->flag & SFA_RNA) != 0;
-    hipStream_t st = c->stream;
-    // event capacity per read: every sample can close at most one event per detector, each detector at most every
-    // second sample -> n samples bound the count
-    std::vector<int64_t> ev_off(n + 1);
-    std::vector<float> scale(2 * static_cast<size_t>(n));
-    ev_off[0] = 0;
-    for (int32_t i = 0; i < n; ++i) {
-        const int64_t len = raw_off[i + 1] - raw_off[i];
-        if (len < 0) return fail(SFA_EINVAL, "sfa_align_raw: raw_off not monotone at read %d", i);
-        ev_off[i + 1] = ev_off[i] + len + 2;
-        const float range = static_cast<float>(scaling[3 * i + 2]), dig = static_cast<float>(scaling[3 * i]);
-        scale[2 * i] = static_cast<float>(scaling[3 * i + 1]);
-        scale[2 * i + 1] = range / dig;  // event_single(), src/sigfish.c:343
-    }
-    const int64_t ev_total = ev_off[n];
-    int rc;
-    if ((rc = c->raw.reserve(total, static_cast<size_t>(n), static_cast<size_t>(ev_total)))) return rc;
-    hipStream_t sp = st;
-    if (raw) HIP_TRY(hipMemcpyAsync(c->raw.e_raw.p, raw, 2 * (size_t)total, hipMemcpyHostToDevice, sp));
-    HIP_TRY(hipMemcpyAsync(c->raw.e_rawoff.p, raw_off, 8 * (size_t)(n + 1), hipMemcpyHostToDevice, sp));
-    HIP_TRY(hipMemcpyAsync(c->raw.e_scale.p, scale.data(), 8 * (size_t)n, hipMemcpyHostToDevice, sp));
-    HIP_TRY(hipMemcpyAsync(c->raw.e_evoff.p, ev_off.data(), 8 * (size_t)(n + 1), hipMemcpyHostToDevice, sp));
+// which reads the wave-per-read kernels of the event detection are offered (option "ev_parallel")
+static bool ev_par_prefix(const sfa_ctx_t *c) { return (c->opt_ev_parallel & 1) != 0; }
+// measured: 76 us against 1.5 ms for a 512-read batch, 2.1 ms against 1.3 ms for 16 Ki reads (it does ~1.3x the work of
+// the sequential walk, in 64x more waves): used while the batch cannot fill the chip with one read per lane pair
+static bool ev_par_peaks(const sfa_ctx_t *c, int32_t n) { return (c->opt_ev_parallel & 2) != 0 && n <= 8192; }
 
+// Event detection of the n reads whose samples, offsets, scaling and event offsets are in c->raw: prefix sums, t-statistics, peak
+// picker, event statistics, each read by the wave-per-read kernels where they certify their result (option "ev_parallel") and by
+// the sequential ones otherwise.  Launches only.
+static void launch_event_detection(sfa_ctx_t *c, int32_t n, hipStream_t sp) {
+    const bool rna = (c->flag & SFA_RNA) != 0;
     sfa::EvArgs ea{};
     ea.raw = c->raw.e_raw.as<int16_t>();
     ea.raw_off = c->raw.e_rawoff.as<int64_t>();
@@ -100,21 +62,79 @@ static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_o
     ea.peak_height = rna ? 1.0f : 0.2f;
     const dim3 lane_grid((n + 63) / 64), lane_block(64);
     ea.seq_flag = c->raw.e_flag.as<int32_t>();
-    ea.use_flags = (c->opt_ev_parallel & 1) ? 1 : 0;
+    ea.use_flags = ev_par_prefix(c) ? 1 : 0;
     ea.peak_flag = c->raw.e_pflag.as<int32_t>();
-    // measured: 76 us against 1.5 ms for a 512-read batch, 2.1 ms against 1.3 ms for 16 Ki reads (it does ~1.3x the work of
-    // the sequential walk, in 64x more waves): used while the batch cannot fill the chip with one read per lane pair
-    ea.use_peak_flags = ((c->opt_ev_parallel & 2) && n <= 8192) ? 1 : 0;
-    HIP_TRY(hipEventRecord(c->eev[0], sp));
+    ea.use_peak_flags = ev_par_peaks(c, n) ? 1 : 0;
     if (ea.use_flags) hipLaunchKernelGGL(sfa::ev_prefix_par_kernel, dim3(n), dim3(64), 0, sp, ea);  // flags what it cannot do exactly
     hipLaunchKernelGGL(sfa::ev_prefix_kernel, lane_grid, lane_block, 0, sp, ea);
     hipLaunchKernelGGL(sfa::ev_tstat_kernel, dim3(n), dim3(256), 0, sp, ea);
     if (ea.use_peak_flags) hipLaunchKernelGGL(sfa::ev_peaks_spec_kernel, dim3(n), dim3(64), 0, sp, ea);  // wave per read, flags what it cannot certify
     hipLaunchKernelGGL(sfa::ev_peaks_kernel, dim3((n + 31) / 32), dim3(64), 0, sp, ea);  // two lanes per read (all reads, or the flagged ones)
     hipLaunchKernelGGL(sfa::ev_stats_kernel, dim3(n), dim3(256), 0, sp, ea);
+}
+
+// The inputs of the event detection into c->raw: the samples (raw == nullptr: they are there already), their offsets, the fp32
+// scaling of event_single() (src/sigfish.c:343) and the event offsets.  ev_off and scale are the caller's: the copies are
+// asynchronous, so both live until the caller has synchronised.  `what` names the caller.
+static int upload_raw_batch(sfa_ctx_t *c, const char *what, const int16_t *raw, const int64_t *raw_off, const double *scaling, int32_t n,
+                            hipStream_t sp, std::vector<int64_t> &ev_off, std::vector<float> &scale) {
+    const int64_t total = raw_off[n] - raw_off[0];
+    if (total < 0 || raw_off[0] != 0) return fail(SFA_EINVAL, "%s: raw_off must start at 0 and be monotone", what);
+    // event capacity per read: every sample can close at most one event per detector, each detector at most every
+    // second sample -> n samples bound the count
+    ev_off.resize(n + 1);
+    scale.resize(2 * static_cast<size_t>(n));
+    ev_off[0] = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const int64_t len = raw_off[i + 1] - raw_off[i];
+        if (len < 0) return fail(SFA_EINVAL, "%s: raw_off not monotone at read %d", what, i);
+        ev_off[i + 1] = ev_off[i] + len + 2;
+        const float range = static_cast<float>(scaling[3 * i + 2]), dig = static_cast<float>(scaling[3 * i]);
+        scale[2 * i] = static_cast<float>(scaling[3 * i + 1]);
+        scale[2 * i + 1] = range / dig;  // event_single(), src/sigfish.c:343
+    }
+    if (int rc = c->raw.reserve(total, static_cast<size_t>(n), static_cast<size_t>(ev_off[n]))) return rc;
+    if (raw) HIP_TRY(hipMemcpyAsync(c->raw.e_raw.p, raw, 2 * (size_t)total, hipMemcpyHostToDevice, sp));
+    HIP_TRY(hipMemcpyAsync(c->raw.e_rawoff.p, raw_off, 8 * (size_t)(n + 1), hipMemcpyHostToDevice, sp));
+    HIP_TRY(hipMemcpyAsync(c->raw.e_scale.p, scale.data(), 8 * (size_t)n, hipMemcpyHostToDevice, sp));
+    HIP_TRY(hipMemcpyAsync(c->raw.e_evoff.p, ev_off.data(), 8 * (size_t)(n + 1), hipMemcpyHostToDevice, sp));
+    return SFA_OK;
+}
+
+// raw == nullptr: the samples are already in c->raw.e_raw (decoded on the device, sfa_align_blow5), laid out by raw_off
+static int align_raw_impl(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_off, const double *scaling, int32_t n, int32_t prefix_size,
+                          int32_t query_size, sfa_result_t *rows, sfa_query_info_t *info, sfa_event_t *query_events) {
+    // the reference's own checks of -p -1 (src/dtw_main.c:263-276)
+    if (prefix_size < 0 && (!(c->flag & SFA_RNA) || (c->flag & (SFA_END | SFA_INV))))
+        return fail(SFA_EINVAL, "sfa_align_raw: automatic query start (prefix_size < 0) needs an RNA context without SFA_END or SFA_INV");
+    if (query_size <= 0) return fail(SFA_EINVAL, "sfa_align_raw: query_size must be positive");
+    if (n == 0) return SFA_OK;
+    if (!c->shards.empty()) {
+        c->maps.map_n = -1;
+        const int grc = for_each_shard_range(c, n, [&](size_t r, int32_t a, int32_t b) {
+            std::vector<int64_t> off(b - a + 1);  // the shard's sample offsets start at 0
+            for (int32_t i = a; i <= b; ++i) off[i - a] = raw_off[i] - raw_off[a];
+            if (!raw) return fail(SFA_EINVAL, "sfa_align_raw: device-resident samples need a single-device context");
+            return sfa_align_raw_ex(c->shards[r], raw + raw_off[a], off.data(), scaling + 3 * static_cast<size_t>(a), b - a, prefix_size,
+                                    query_size, rows + a, info + a,
+                                    query_events ? query_events + static_cast<size_t>(a) * static_cast<size_t>(query_size) : nullptr);
+        });
+        if (!grc) c->maps.map_n = n;  // (sfa_event_maps splits its rows by the same ranges)
+        return grc;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (raw) HIP_TRY(hipStreamSynchronize(c->stream));  // (device-resident samples: their decoder is still in flight on this stream)
+    hipStream_t st = c->stream, sp = st;
+    std::vector<int64_t> ev_off;
+    std::vector<float> scale;
+    int rc;
+    if ((rc = upload_raw_batch(c, "sfa_align_raw", raw, raw_off, scaling, n, sp, ev_off, scale))) return rc;
+    HIP_TRY(hipEventRecord(c->eev[0], sp));
+    launch_event_detection(c, n, sp);
     // RNA automatic query start: adaptor, poly-A tail, first event behind it; e_nev[n + i] (the counts' neighbours, one copy)
     const bool auto_start = prefix_size < 0;
     if (auto_start) {
+        const dim3 lane_grid((n + 63) / 64), lane_block(64);
         sfa::AutoArgs aa{};
         aa.raw = c->raw.e_raw.as<int16_t>();
         aa.raw_off = c->raw.e_rawoff.as<int64_t>();
@@ -399,6 +419,55 @@ int sfa_inflate_zlib_device(sfa_ctx_t *c, const uint8_t *in, const int64_t *in_o
     HIP_TRY(hipMemcpyAsync(out, c->blow5.b_out.p, static_cast<size_t>(out_off[n]), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(out_len, c->blow5.b_len.p, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return SFA_OK;
+}
+
+// (testing hook of the event detection alone: every read's whole event table, the route each read took and the two t-statistics;
+// see include/sigfish_amd.h)
+int sfa_detect_events_device(sfa_ctx_t *c, const int16_t *raw, const int64_t *raw_off, const double *scaling, int32_t n, sfa_event_t *events,
+                             int32_t *n_events, int32_t *route, float *t_short, float *t_long) {
+    if (!c || !c->shards.empty() || n < 0 || (n > 0 && (!raw || !raw_off || !scaling || !events || !n_events || !route)))
+        return fail(SFA_EINVAL, "sfa_detect_events_device: bad argument (single-device context needed)");
+    if (n == 0) return SFA_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    hipStream_t st = c->stream;
+    std::vector<int64_t> ev_off;  // as align_raw_impl: room for len + 2 records per read
+    std::vector<float> scale;
+    int rc;
+    if ((rc = upload_raw_batch(c, "sfa_detect_events_device", raw, raw_off, scaling, n, st, ev_off, scale))) return rc;
+    const int64_t total = raw_off[n];
+    const size_t ev_total = static_cast<size_t>(ev_off[n]);
+    launch_event_detection(c, n, st);
+    KERNEL_TRY();
+    std::vector<int32_t> start(ev_total), seq(n), peak(n);
+    std::vector<float> length(ev_total), mean(ev_total), stdv(ev_total);
+    HIP_TRY(hipMemcpyAsync(start.data(), c->raw.e_evstart.p, 4 * ev_total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(length.data(), c->raw.e_evlen.p, 4 * ev_total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(mean.data(), c->raw.e_evmean.p, 4 * ev_total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(stdv.data(), c->raw.e_evstdv.p, 4 * ev_total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(n_events, c->raw.e_nev.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    const bool par_prefix = ev_par_prefix(c), par_peaks = ev_par_peaks(c, n);  // (a kernel that did not run left its flags stale)
+    if (par_prefix) HIP_TRY(hipMemcpyAsync(seq.data(), c->raw.e_flag.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (par_peaks) HIP_TRY(hipMemcpyAsync(peak.data(), c->raw.e_pflag.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (t_short && total > 0) HIP_TRY(hipMemcpyAsync(t_short, c->raw.e_t1.p, 4 * (size_t)total, hipMemcpyDeviceToHost, st));
+    if (t_long && total > 0) HIP_TRY(hipMemcpyAsync(t_long, c->raw.e_t2.p, 4 * (size_t)total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int32_t i = 0; i < n; ++i) {
+        route[i] = ((!par_prefix || seq[i] != 0) ? 1 : 0) | ((!par_peaks || peak[i] != 0) ? 2 : 0);
+        const int64_t cap = ev_off[i + 1] - ev_off[i];
+        if (n_events[i] < 0 || n_events[i] > cap) return fail(SFA_EKERNEL, "sfa_detect_events_device: read %d reports %d events, room for %lld", i, n_events[i], (long long)cap);
+        for (int64_t e = 0; e < n_events[i]; ++e) {
+            const size_t k = static_cast<size_t>(ev_off[i] + e);
+            sfa_event_t rec;
+            memset(&rec, 0, sizeof rec);
+            rec.start = static_cast<uint64_t>(start[k]);
+            rec.length = length[k];
+            rec.mean = mean[k];
+            rec.stdv = stdv[k];
+            events[k] = rec;
+        }
+    }
     return SFA_OK;
 }
 

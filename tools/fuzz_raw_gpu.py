@@ -2,7 +2,9 @@
 """fuzz_raw_gpu.py -- randomised parity of the device-side pre-DP stages (sfa_align_raw: prefix sums, t-statistics, peak
 picker, event statistics, query window, normalisation, then the alignment) against the host stages, which are pinned
 bit-exactly to the compiled reference by tests/test_host_stages.py.  Synthetic step signals with random dwell, noise,
-length (incl. empty / too short reads), scaling and DNA / RNA detector parameters.
+length (incl. empty / too short reads), scaling and DNA / RNA detector parameters.  Every read's WHOLE event table (start,
+length, mean, stdv as bits) is compared through the testing hook sfa_detect_events_device, and every iteration prints how many
+reads went through each kernel (par = wave-per-read, seq = sequential; prefix sums / peak picker).
 Usage (MI355X box): python tools/fuzz_raw_gpu.py [iterations] [seed]"""
 import os
 import sys
@@ -26,6 +28,10 @@ def signal(rng, n):
     if rng.integers(0, 6) == 0:
         x[:] = np.round(x / 8) * 8  # coarse quantisation: exact ties in the t-statistics
     return np.clip(np.round(x), -2000, 4000).astype(np.int16)
+
+
+def same_bits(a, b):
+    return bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
 
 
 def main():
@@ -53,11 +59,16 @@ def main():
         cat = np.concatenate(raws) if off[-1] else np.zeros(0, np.int16)
         with S.Aligner(ref, flag) as al:
             al.set_option("ev_parallel", int(rng.choice([3, 3, 3, 2, 1, 0])))  # wave-per-read prefix sums (bit 0) / peak picker (bit 1), or the sequential kernels
+            full, routes = al.detect_events_device(cat, off, np.array(scs))
             rows, info, qev = al.align_raw(cat, off, np.array(scs), prefix, query, return_events=True)
+            print(f"  it={it} {'rna' if rna else 'dna'} {n} reads: prefix par/seq {int(np.sum(routes & 1 == 0))}/{int(np.sum(routes & 1 != 0))}, "
+                  f"peaks par/seq {int(np.sum(routes & 2 == 0))}/{int(np.sum(routes & 2 != 0))}", flush=True)
             tabs, qs, qe = [], [], []
             for k, r in enumerate(raws):
                 meta = dict(digitisation=scs[k][0], offset=scs[k][1], range=scs[k][2])
                 ev = S.detect_events(r, meta, rna) if len(r) else np.zeros(0, S.EVENT_DTYPE)
+                whole = len(full[k]) == len(ev) and np.array_equal(full[k]["start"], ev["start"]) and all(
+                    same_bits(full[k][f], ev[f]) for f in ("length", "mean", "stdv"))  # (before select_query normalises ev's means)
                 keep, a, b = (False, 0, 0)
                 if len(ev):
                     keep, a, b = S.select_query(ev, r, meta, prefix, query, flag, 0)
@@ -65,7 +76,11 @@ def main():
                     bad += 1
                     print(f"MISMATCH it={it} read {k} (len {len(r)}): {info['n_events'][k]} events on the device, {len(ev)} on the host")
                     break
-                if keep and not all(np.array_equal(qev[k][:b - a][f], ev[f][a:b]) for f in ("start", "length", "mean")):
+                if not whole:
+                    bad += 1
+                    print(f"MISMATCH it={it} read {k} (len {len(r)}, route {routes[k]}): whole event table differs")
+                    break
+                if keep and not all(np.array_equal(qev[k][:b - a][f], ev[f][a:b]) for f in ("start", "length", "mean", "stdv")):
                     bad += 1
                     print(f"MISMATCH it={it} read {k}: query window events differ")
                     break
