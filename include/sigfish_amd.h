@@ -238,11 +238,34 @@ int sfa_session_lengths(sfa_session_t *s, const int32_t *slot, int32_t n, int64_
  * events, a poisoned slot. */
 int64_t sfa_session_row(sfa_session_t *s, int32_t slot, int32_t contig, int32_t strand_char, float *cost, int32_t *start);
 
+/* Session candidates: the secondary mappings of the real-time path.  With n_candidates = 1..4 a session keeps, behind every
+ * slot's row, the next n_candidates entries of the reference's sorted list of the 5 best windows (update_aln, src/sigfish.c:575-626;
+ * ties: the later candidate ranks higher) over ALL events the slot has received: what sfa_secondary_rows returns for a batch.  The
+ * sweep keeps each window's first strict minimum with its start column in a list per (slot, contig, strand), and a merge over the
+ * jobs in processing order writes the rows: no second pass, and, unlike sfa_secondary_rows, NO SFA_MAX_QUERY cut-off -- a slot with
+ * more than SFA_MAX_QUERY events has valid candidates.  n_candidates = 0 switches the lists off: the session launches the kernels
+ * it launched before.  Rows, carried rows and everything else a session returns are the same bytes with and without.  Allowed only
+ * while every slot is empty, as for sfa_session_raw_config (SFA_EINVAL otherwise, and for n_candidates outside 0..4); works on
+ * event-mode, raw-mode and resweep sessions, with or without SFA_SESSION_NO_START.  It is no session flag. */
+int sfa_session_candidates_config(sfa_session_t *s, int32_t n_candidates);
+
+/* sec[i*4+k], k = 0 the best: the candidates behind the row slot[i] currently has -- the row sfa_session_extend /
+ * sfa_session_extend_raw last returned for it, or would return for an empty chunk (on a resweep session: of the window the row
+ * spans).  Layout exactly as sfa_secondary_rows: rid, strand, pos_st / pos_end flipped and offset as the primary (with
+ * SFA_SESSION_NO_START the coordinate that needs the start column is -1, as in the primary), score, score2 = the score of the
+ * next candidate below (+inf for the last), mapq 0; valid = 0 for ranks beyond n_candidates and for entries that are empty or not
+ * finite (a slot with fewer windows than ranks).  Where sec[i*4] is valid its score is the primary's score2.  A slot without events
+ * and a poisoned slot give four rows with valid = 0.  No de-duplication: neighbouring windows of one locus often fill the list --
+ * which is what a caller looks at to tell a depressed mapq from a second locus.  Blocking, on the context's stream.  SFA_EINVAL:
+ * the session keeps no candidates, a slot out of range. */
+int sfa_session_candidates(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_result_t *sec);
+
 void sfa_session_destroy(sfa_session_t *s);
 
 /* Device memory sfa_session_create takes for the carried rows of n_slots slots over a reference of total_columns columns
  * (sum of ref_lengths, twice that for DNA): one row per slot, updated in place -- total_columns x n_slots x 8 bytes, x 4 with
- * SFA_SESSION_NO_START (the allocator adds an eighth of headroom; bookkeeping is some 50 bytes per slot).  Host arithmetic, no
+ * SFA_SESSION_NO_START (the allocator adds an eighth of headroom; bookkeeping is some 50 bytes per slot, and 96 more -- four rows -- on a
+ * session that keeps candidates, sfa_session_candidates_config: not counted here).  Host arithmetic, no
  * device needed; negative (an SFA_E* code) for arguments that are not positive, unknown flags or a product beyond 2^63.
  * SFA_SESSION_RESWEEP changes nothing: the carried rows are still needed (a window beyond SFA_MAX_QUERY events runs as pieces). */
 int64_t sfa_session_bytes(int64_t total_columns, int32_t n_slots, uint32_t session_flags);

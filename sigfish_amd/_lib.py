@@ -63,7 +63,7 @@ SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "
            "sfa_session_create", "sfa_session_extend", "sfa_session_reset", "sfa_session_lengths", "sfa_session_destroy", "sfa_session_bytes",
            "sfa_event_stream_create", "sfa_event_stream_push", "sfa_event_stream_finish", "sfa_event_stream_destroy",
            "sfa_session_raw_config", "sfa_session_extend_raw", "sfa_session_events", "sfa_session_raw_bytes", "sfa_session_query_span", "sfa_session_row",
-           "sfa_session_raw_recalibrate"]
+           "sfa_session_raw_recalibrate", "sfa_session_candidates_config", "sfa_session_candidates"]
 
 _lib = None
 
@@ -157,6 +157,8 @@ def load():
     L.sfa_session_destroy.restype = None
     L.sfa_session_row.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, f32p, i32p]
     L.sfa_session_row.restype = C.c_int64
+    L.sfa_session_candidates_config.argtypes = [vp, C.c_int32]
+    L.sfa_session_candidates.argtypes = [vp, i32p, C.c_int32, vp]
     L.sfa_session_bytes.argtypes = [C.c_int64, C.c_int32, C.c_uint32]
     L.sfa_session_bytes.restype = C.c_int64
     L.sfa_event_stream_create.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int]

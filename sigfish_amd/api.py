@@ -269,13 +269,20 @@ class Aligner:
                "sfa_align_events")
         return out
 
-    def session(self, n_slots, starts=True, resweep=False, flags=None):
+    def session(self, n_slots, starts=True, resweep=False, flags=None, candidates=0):
         """An alignment session of n_slots growing reads on this aligner (sfa_session_create); starts=False carries costs only
         (SFA_SESSION_NO_START: half the memory, the coordinate on the start side of every row is -1).  resweep=True
         (SFA_SESSION_RESWEEP): a raw-mode-only session that sweeps a slot only when its normalisation window changes, over the
         window's events -- the one kind of session an RNA aligner without INV can have (its query is the events reversed).
-        flags: the raw flag word in place of starts / resweep."""
-        return Session(self, n_slots, starts, resweep, flags)
+        flags: the raw flag word in place of starts / resweep.  candidates=1..4: configure_candidates() on the new session."""
+        s = Session(self, n_slots, starts, resweep, flags)
+        if candidates:
+            try:
+                s.configure_candidates(candidates)
+            except Exception:
+                s.close()
+                raise
+        return s
 
     def set_option(self, key, value):
         _check(self._L.sfa_set_option(self._h, key.encode(), int(value)), f"sfa_set_option({key})")
@@ -463,6 +470,21 @@ class Session:
             ev = np.zeros(1, np.float32)
         _check(self._L.sfa_session_extend(self._h, sl.ctypes.data_as(_lib.i32p), ev.ctypes.data_as(_lib.f32p),
                                           eo.ctypes.data_as(_lib.i64p), n, out.ctypes.data_as(C.c_void_p)), "sfa_session_extend")
+        return out
+
+    def configure_candidates(self, n):
+        """Keep the n = 1..4 candidates behind every slot's row (sfa_session_candidates_config): the secondaries of the batch path,
+        for all events a slot has received, however many.  0 switches them off.  Only while every slot is empty."""
+        self._live()
+        _check(self._L.sfa_session_candidates_config(self._h, int(n)), "sfa_session_candidates_config")
+
+    def candidates(self, slots):
+        """The candidates behind the current rows of `slots` -> RESULT_DTYPE[len(slots), 4], best first; valid = 0 for ranks that
+        are absent or beyond the configured count, and for slots without events or poisoned."""
+        self._live()
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        out = np.zeros((len(sl), 4), RESULT_DTYPE)
+        _check(self._L.sfa_session_candidates(self._h, sl.ctypes.data_as(_lib.i32p), len(sl), out.ctypes.data_as(C.c_void_p)), "sfa_session_candidates")
         return out
 
     def configure_raw(self, skip=50, norm=100, query=2048, recalibrate=(), at_end=False):

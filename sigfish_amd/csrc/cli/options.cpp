@@ -19,7 +19,7 @@ enum LongOpt {
     O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
     O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
     O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE,
-    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP
+    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES
 };
 
 const option kLongOptions[] = {
@@ -113,6 +113,7 @@ const option kRealtimeOptions[] = {
     {"recalibrate", required_argument, 0, O_RECALIBRATE}, {"recalibrate-at-end", no_argument, 0, O_RECALIBRATE_AT_END},
     {"resweep", no_argument, 0, O_RESWEEP}, {"dtw-std", no_argument, 0, O_DTW_STD}, {"from-end", no_argument, 0, O_FROM_END}, {"sam", no_argument, 0, 'a'},
     {"secondary", required_argument, 0, O_SECONDARY}, {"ranks", required_argument, 0, O_RANKS},
+    {"candidates", required_argument, 0, O_CANDIDATES},
     {0, 0, 0, 0}};
 
 void realtime_help(FILE *fp, const RealtimeOpt &r) {
@@ -152,6 +153,9 @@ void realtime_help(FILE *fp, const RealtimeOpt &r) {
                 "                              points (if it is not the last already), so that a full read is normalised over q events [off]\n");
     fprintf(fp, "   --min-events INT           no early decision below this many query events [the value of -q]\n");
     fprintf(fp, "   --min-mapq INT             decide early at this mapq; 61 = never [%d]\n", r.min_mapq);
+    fprintf(fp, "   --candidates INT           behind every primary line, the channel's next 1..4 candidates of the sorted list of the 5 best\n"
+                "                              windows (tp:A:S lines, best first, same span and tags): what dtw --secondary yes prints, for\n"
+                "                              the events the read has at its decision [off]\n");
     fprintf(fp, "   --pace yes|no              sleep so that tick t does not start before t x chunk-samples / sampling_rate seconds;\n"
                 "                              changes the timing report on stderr only, never the output [no]\n\n"
                 "output: PAF as dtw prints it, then ne:i:<query events at the decision> ns:i:<samples sent> dc:A:<E|F|R>\n");
@@ -165,7 +169,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     FILE *fp_help = stderr;
     int c, li = 0;
     bool secondary = false;
-    const char *recal = nullptr;
+    const char *recal = nullptr, *candidates = nullptr;
     while ((c = getopt_long(argc, argv, "p:q:t:v:o:ahV", kRealtimeOptions, &li)) >= 0) {
         switch (c) {
             case 't': o.threads = atoi(optarg); if (o.threads < 1) die("Number of threads should larger than 0."); break;
@@ -199,6 +203,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
             case O_RECALIBRATE: recal = optarg; break;
             case O_RECALIBRATE_AT_END: r.recal_at_end = true; break;
             case O_RESWEEP: r.resweep = true; break;
+            case O_CANDIDATES: candidates = optarg; break;
             default: realtime_help(stderr, r); exit(EXIT_FAILURE);
         }
     }
@@ -213,7 +218,13 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     if (o.flag & F_END) die("realtime: --from-end is not available: the end of a read is not known while it arrives");
     if (o.prefix < 0) die("realtime: -p -1 (automatic query start) is not available: -p must be >= 0");
     if (o.flag & F_SAM) die("realtime: --sam is not available: sessions keep no warp path");
-    if (secondary) die("realtime: --secondary yes is not available: sessions keep one row per slot");
+    if (secondary) die("realtime: --secondary yes is not available: sessions keep one row per slot; --candidates N prints a slot's candidate list");
+    if (candidates) {
+        char *e = nullptr;
+        const long v = strtol(candidates, &e, 10);
+        if (e == candidates || *e || v < 1 || v > 4) die("realtime: --candidates should be 1..4");
+        r.candidates = static_cast<int32_t>(v);
+    }
     if (o.ranks != 0) die("realtime: --ranks is not available: a replay is one process on one device");
     if (o.devices.size() != 1) die("realtime: --device takes exactly one GPU: a session's rows live on one device");
     if ((o.flag & F_INV) && !(o.flag & F_RNA)) die("Inversion is only available for RNA.");

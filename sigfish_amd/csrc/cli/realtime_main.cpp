@@ -159,6 +159,7 @@ int realtime_run(int argc, char **argv, double t0) {
     if (!r.recal_at.empty() || r.recal_at_end)
         if (sfa_session_raw_recalibrate(se, r.recal_at.data(), static_cast<int32_t>(r.recal_at.size()), r.recal_at_end ? SFA_RECAL_AT_END : 0) != SFA_OK)
             die(std::string("session: ") + sfa_last_error());
+    if (r.candidates > 0 && sfa_session_candidates_config(se, r.candidates) != SFA_OK) die(std::string("session: ") + sfa_last_error());
     if (o.verbosity >= 4)
         fprintf(stderr, "[realtime::%.3f] initialised: %d channels, %ld samples per tick, skip %d, norm %d, query %d, early at %d events and mapq %d\n", realtime() - t0,
                 r.channels, (long)r.chunk_samples, o.prefix, r.norm_events, o.query, r.min_events, r.min_mapq);
@@ -183,6 +184,7 @@ int realtime_run(int argc, char **argv, double t0) {
     std::vector<sfa_session_raw_info_t> info(C);
     std::vector<char> reason(C), line(C);
     std::vector<uint64_t> span_a(C), span_b(C);
+    std::vector<sfa_result_t> cand(r.candidates > 0 ? 4 * static_cast<size_t>(C) : 0);
     std::string text(4096, '\0');
 
     ahead.top_up();
@@ -223,6 +225,8 @@ int realtime_run(int argc, char **argv, double t0) {
         const int32_t nd = static_cast<int32_t>(decided_slot.size());
         if (nd > 0) {
             if (sfa_session_query_span(se, decided_slot.data(), nd, span_a.data(), span_b.data()) != SFA_OK) die(std::string("query span: ") + sfa_last_error());
+            // the candidates of every channel decided in this tick, in one call and before the reset
+            if (r.candidates > 0 && sfa_session_candidates(se, decided_slot.data(), nd, cand.data()) != SFA_OK) die(std::string("candidates: ") + sfa_last_error());
             for (int32_t i = 0, d = 0; i < n; ++i) {  // ascending channels
                 if (!reason[i]) continue;
                 const int32_t k = d++;
@@ -233,17 +237,21 @@ int realtime_run(int argc, char **argv, double t0) {
                     continue;
                 }
                 const sfa::Blow5Record &rec = ch.rec[slot[i]];
-                const sfa_result_t &w = rows[i];
-                // query_size as dtw passes it: last query event - first (src/sigfish.c:801-807)
-                int len = sfa_paf_row(&text[0], text.size(), &w, rec.read_id.c_str(), ref.contigs[w.rid].name.c_str(), span_a[k], span_b[k],
-                                      static_cast<uint64_t>(info[i].q_events - 1), rec.raw.size(), static_cast<uint64_t>(ref.seq_len[w.rid]));
-                if (len > 0) {
-                    const int more = snprintf(&text[len - 1], text.size() - static_cast<size_t>(len - 1), "\tne:i:%ld\tns:i:%ld\tdc:A:%c\n", (long)info[i].q_events,
-                                              (long)info[i].n_samples, reason[i]);
-                    len = (more < 0 || static_cast<size_t>(len - 1 + more) >= text.size()) ? -1 : len - 1 + more;
+                // the primary, then the channel's valid candidates, best first: same span, same tags
+                for (int32_t m = 0; m <= r.candidates; ++m) {
+                    const sfa_result_t &w = m == 0 ? rows[i] : cand[4 * static_cast<size_t>(k) + (m - 1)];
+                    if (m > 0 && !(w.valid && w.rid >= 0)) continue;
+                    // query_size as dtw passes it: last query event - first (src/sigfish.c:801-807)
+                    int len = sfa_paf_row_ex(&text[0], text.size(), &w, rec.read_id.c_str(), ref.contigs[w.rid].name.c_str(), span_a[k], span_b[k],
+                                             static_cast<uint64_t>(info[i].q_events - 1), rec.raw.size(), static_cast<uint64_t>(ref.seq_len[w.rid]), m == 0 ? 'P' : 'S');
+                    if (len > 0) {
+                        const int more = snprintf(&text[len - 1], text.size() - static_cast<size_t>(len - 1), "\tne:i:%ld\tns:i:%ld\tdc:A:%c\n", (long)info[i].q_events,
+                                                  (long)info[i].n_samples, reason[i]);
+                        len = (more < 0 || static_cast<size_t>(len - 1 + more) >= text.size()) ? -1 : len - 1 + more;
+                    }
+                    if (len < 0) die("PAF line too long");
+                    fwrite(text.data(), 1, static_cast<size_t>(len), stdout);
                 }
-                if (len < 0) die("PAF line too long");
-                fwrite(text.data(), 1, static_cast<size_t>(len), stdout);
                 ++rep.lines[reason[i] == 'E' ? 0 : reason[i] == 'F' ? 1 : 2];
             }
             fflush(stdout);  // a line is out at the moment of its decision

@@ -67,6 +67,8 @@ struct SessionArgs {
     int32_t *p_end, *p_st;    // column of the best window's first strict minimum, start column of the path into it
     SessionClass cls[kSessionMaxClasses];
     int32_t n_cls, n_jobs, n_tasks;
+    int32_t *p_top5;          // [n_call][n_jobs][kTop5Words] SEC: the candidate list of the new last row's windows (behind all else: the
+                              // kernels without SEC read the layout they always have)
 };
 
 template <typename T>
@@ -85,8 +87,13 @@ __device__ __forceinline__ void session_last_row(const CF &c, const CI &s, const
     }
 }
 
-template <int R, int L, bool TRACK, bool FIRST>
-__device__ __forceinline__ void session_body(const SessionArgs &a, const SessionClass cd, const int task_local, float *lds_f, int *lds_i) {
+// SEC: the sorted list of the 5 best windows (top5_offer: update_aln's rule) per (wave, wave slot) in LDS, as lds_t5 of
+// sdtw_sec_fill_kernel -- the tracked kernel has no VGPRs to spare.  An entry is (score bits, column of the window's first strict
+// minimum, start column of the path into it; -1 without TRACK): the job is the task's own.  Only the owner lane touches its list,
+// once per window; Top2 and what it writes are as without SEC.
+template <int R, int L, bool TRACK, bool FIRST, bool SEC = false>
+__device__ __forceinline__ void session_body(const SessionArgs &a, const SessionClass cd, const int task_local, float *lds_f, int *lds_i,
+                                             int *lds_t5 = nullptr) {
     constexpr int NS = 64 / L;
     const int job = task_local / cd.n_groups;  // job-major: neighbouring waves stream the same reference
     const int group = cd.group_base + (task_local - job * cd.n_groups);
@@ -142,6 +149,11 @@ __device__ __forceinline__ void session_body(const SessionArgs &a, const Session
     Top2 top;
     top.init();
     int top_st = -1;
+    int *t5 = nullptr;
+    if constexpr (SEC) {
+        t5 = lds_t5 + ((threadIdx.x >> 6) * 4 + ws) * kTop5Words;
+        if (owner) top5_init(t5);  // (an empty entry: column -1)
+    }
     float wmin = INFINITY;
     int wpos = -1, wst = -1;
     int wend = min(total, rlen);  // end of this slot's current window
@@ -215,6 +227,9 @@ __device__ __forceinline__ void session_body(const SessionArgs &a, const Session
                 const bool ending = wend == col + 1;
                 const bool became_best = top.offer_if(ending, wmin, wpos, job);
                 top_st = became_best ? wst : top_st;
+                if constexpr (SEC) {
+                    if (ending && owner) top5_offer(t5, wmin, wpos, TRACK ? wst : -1);
+                }
                 wmin = ending ? INFINITY : wmin;
                 wpos = ending ? -1 : wpos;
                 wst = ending ? -1 : wst;
@@ -246,16 +261,25 @@ __device__ __forceinline__ void session_body(const SessionArgs &a, const Session
         a.p_second[o] = top.second;
         a.p_end[o] = top.end;
         a.p_st[o] = top_st;
+        if constexpr (SEC) {  // (a chunk of several pieces: the last launch's list stays)
+            for (int w = 0; w < kTop5Words; ++w) a.p_top5[o * kTop5Words + w] = t5[w];
+        }
     }
 }
 
 // grid: ceil(n_tasks / 4) blocks of 256 threads, one task per wave.  TRACK: start columns are carried and propagated
-// (strip_step's tracking branch); else costs only (SFA_SESSION_NO_START).
-template <bool TRACK>
+// (strip_step's tracking branch); else costs only (SFA_SESSION_NO_START).  SEC: the windows' candidate lists as well
+// (sfa_session_candidates_config); sessions that do not ask for them launch the kernels without.
+template <bool TRACK, bool SEC = false>
 __global__ void __launch_bounds__(256, TRACK ? 2 : 3) sdtw_session_kernel(const SessionArgs a) {
     const int task = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     __shared__ float lds_f[4 * kXchWordsPerWave];
     __shared__ int lds_i[TRACK ? 4 * kXchWordsPerWave : 1];
+    int *lds_t5 = nullptr;
+    if constexpr (SEC) {
+        __shared__ int t5[4 * 4 * kTop5Words];
+        lds_t5 = t5;
+    }
     if (task >= a.n_tasks) return;  // wave-uniform
     int ci = 0;
     while (ci + 1 < a.n_cls && task >= a.cls[ci + 1].task_base) ++ci;
@@ -264,9 +288,9 @@ __global__ void __launch_bounds__(256, TRACK ? 2 : 3) sdtw_session_kernel(const 
 #define SFA_SHAPE(RR, LL)                                                     \
     case (RR) * 256 + (LL):                                                   \
         if (cd.first)                                                         \
-            session_body<RR, LL, TRACK, true>(a, cd, tl, lds_f, lds_i);       \
+            session_body<RR, LL, TRACK, true, SEC>(a, cd, tl, lds_f, lds_i, lds_t5);  \
         else                                                                  \
-            session_body<RR, LL, TRACK, false>(a, cd, tl, lds_f, lds_i);      \
+            session_body<RR, LL, TRACK, false, SEC>(a, cd, tl, lds_f, lds_i, lds_t5); \
         break;
     switch (cd.R * 256 + cd.lanes) {
         SFA_SHAPE(32, 64) SFA_SHAPE(32, 32) SFA_SHAPE(32, 16)
@@ -277,9 +301,12 @@ __global__ void __launch_bounds__(256, TRACK ? 2 : 3) sdtw_session_kernel(const 
 #undef SFA_SHAPE
 }
 
-// instantiated in sdtw_inst_session_track.hip / sdtw_inst_session_cost.hip
+// instantiated in sdtw_inst_session_track.hip / sdtw_inst_session_cost.hip, with SEC in sdtw_inst_session_track_sec.hip /
+// sdtw_inst_session_cost_sec.hip
 extern template __global__ void sdtw_session_kernel<true>(const SessionArgs);
 extern template __global__ void sdtw_session_kernel<false>(const SessionArgs);
+extern template __global__ void sdtw_session_kernel<true, true>(const SessionArgs);
+extern template __global__ void sdtw_session_kernel<false, true>(const SessionArgs);
 
 struct SessionRowsArgs {
     const int32_t *call_slot;  // [n_call] slot of the session, -1: no row to write (no new events, or the slot is poisoned)
@@ -294,7 +321,20 @@ struct SessionRowsArgs {
     int32_t track;             // 0: SFA_SESSION_NO_START -- the coordinate that needs the start column is -1
 };
 
-#ifdef SFA_DEFINE_SESSION_KERNELS  // plain kernel: defined in exactly one translation unit (sfa_session.hip)
+struct SessionCandArgs {
+    const int32_t *call_slot;  // as SessionRowsArgs
+    const uint8_t *bad;
+    const int32_t *p_top5;     // SessionArgs::p_top5
+    const int32_t *job_contig;
+    const int8_t *job_strand;
+    const int32_t *ref_len, *ref_st_offset;
+    ResultRow *cand;           // [n_slots][4] the candidates behind every slot's current row, best first
+    int32_t n_call, n_jobs;
+    int32_t n_cand;            // ranks asked for (1..4): rows of the ranks behind are valid = 0
+    int32_t track;             // as SessionRowsArgs
+};
+
+#ifdef SFA_DEFINE_SESSION_KERNELS  // plain kernels: defined in exactly one translation unit (sfa_session.hip)
 // the jobs' partial top-2 of every slot of the call merged in processing order (a later job wins ties), then contig, strand,
 // mapq, flip and offset (src/sigfish.c:969-983): what sdtw_finalize_kernel does for a batch
 __global__ void __launch_bounds__(64) sdtw_session_rows_kernel(const SessionRowsArgs a) {
@@ -330,6 +370,70 @@ __global__ void __launch_bounds__(64) sdtw_session_rows_kernel(const SessionRows
         if (!a.track) (r.strand == '+' ? r.pos_st : r.pos_end) = -1;
     }
     a.rows[slot] = r;
+}
+
+// update_aln on a list in registers (aln[0] worst .. aln[4] best), as top5_offer_regs: the entries that are not strictly better
+// than the candidate form a prefix; they move down by one and the candidate takes the last place of the prefix
+__device__ __forceinline__ void session_offer_regs(float (&sc)[5], int (&ix)[5], const float s, const int i) {
+    int l = 0;
+#pragma unroll
+    for (int m = 0; m < 5; ++m) l += !(s > sc[m]) ? 1 : 0;
+#pragma unroll
+    for (int m = 0; m < 5; ++m) {
+        const bool nxt = m + 1 < l, put = m == l - 1;
+        const int mn = m < 4 ? m + 1 : 4;
+        sc[m] = nxt ? sc[mn] : (put ? s : sc[m]);
+        ix[m] = nxt ? ix[mn] : (put ? i : ix[m]);
+    }
+}
+
+// Session candidates: the jobs' lists of every slot of the call merged in processing order, each list worst entry first (the
+// order of sdtw_sec_finalize_kernel over chunks), and the four candidates behind the winner written as rows, best first: the
+// layout of sfa_secondary_rows.  Slots the rows kernel skips keep their stored candidates.  One lane per slot of the call.
+__global__ void __launch_bounds__(64) sdtw_session_cand_kernel(const SessionCandArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_call) return;
+    const int slot = a.call_slot[i];
+    if (slot < 0 || a.bad[i]) return;
+    float sc[5];
+    int ix[5];  // job * 5 + entry: where the candidate's columns are
+#pragma unroll
+    for (int m = 0; m < 5; ++m) {
+        sc[m] = INFINITY;
+        ix[m] = -1;
+    }
+    const int32_t *lists = a.p_top5 + static_cast<int64_t>(i) * a.n_jobs * kTop5Words;
+    for (int j = 0; j < a.n_jobs; ++j) {
+        const int32_t *t = lists + j * kTop5Words;
+        for (int e = 0; e < 5; ++e)
+            if (t[3 * e + 1] >= 0) session_offer_regs(sc, ix, __int_as_float(t[3 * e]), j * 5 + e);
+    }
+#pragma unroll
+    for (int k = 1; k < 5; ++k) {
+        ResultRow r;
+        r.rid = -1;
+        r.pos_st = -1;
+        r.pos_end = -1;
+        r.score = INFINITY;
+        r.score2 = INFINITY;
+        r.strand = 0;
+        r.mapq = 0;  // (secondaries, as in sfa_secondary_rows)
+        r.valid = 0;
+        r.pad = 0;
+        const int x = ix[4 - k];
+        if (k <= a.n_cand && x >= 0 && isfinite(sc[4 - k])) {
+            const int job = x / 5;
+            const int32_t *t = lists + job * kTop5Words + 3 * (x - job * 5);
+            r.valid = 1;
+            r.rid = a.job_contig[job];
+            r.strand = a.job_strand[job];
+            r.score = sc[4 - k];
+            r.score2 = k < 4 ? sc[3 - k] : INFINITY;
+            place_row(r, t[2], t[1], a.ref_len[r.rid], a.ref_st_offset[r.rid]);
+            if (!a.track) (r.strand == '+' ? r.pos_st : r.pos_end) = -1;
+        }
+        a.cand[static_cast<int64_t>(slot) * 4 + (k - 1)] = r;
+    }
 }
 #endif
 

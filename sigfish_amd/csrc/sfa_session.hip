@@ -29,6 +29,9 @@ struct sfa_session {
     DevBuf d_events, d_stage, d_bad, d_count, d_pbest, d_psecond, d_pend, d_pst;  // of a call
     PinBuf h_stage, h_bad;
     Event ev[4];  // first kernel, sweeps start / end, rows written
+    int32_t n_cand = 0;           // sfa_session_candidates_config: candidates kept behind every slot's row (0: none, the plain kernels)
+    DevBuf d_cand, d_p5;          // [n_slots][4] the slots' candidates; of a call: [n][n_jobs] lists of kTop5Words words
+    PinBuf h_cand;
     // ---- raw mode ----
     bool raw = false;
     int32_t skip = 0, norm = 0, query = 0;
@@ -185,6 +188,8 @@ static int sweep_chunks(sfa_session *s, const int32_t *slot, const Chunk *ch, in
                              static_cast<size_t>(n), s->h_bad, static_cast<size_t>(n) + 8, s->d_pbest, 4 * n_part, s->d_psecond, 4 * n_part, s->d_pend, 4 * n_part,
                              s->d_pst, 4 * n_part))
         return rc;
+    if (s->n_cand > 0)
+        if (int rc = s->d_p5.reserve(4 * sfa::kTop5Words * n_part)) return rc;
     char *h = s->h_stage.as<char>();
     const char *d = s->d_stage.as<char>();
     size_t at = 0;
@@ -241,6 +246,7 @@ static int sweep_chunks(sfa_session *s, const int32_t *slot, const Chunk *ch, in
         a.n_cls = l.n_cls;
         a.n_jobs = nj;
         a.n_tasks = l.n_tasks;
+        a.p_top5 = s->n_cand > 0 ? s->d_p5.as<int32_t>() : nullptr;
     }
     if (at > bytes) return fail(SFA_EKERNEL, "session sweep: staging overrun (%zu > %zu)", at, bytes);
     HIP_TRY(hipMemcpyAsync(s->d_stage.p, h, at, hipMemcpyHostToDevice, st));
@@ -258,7 +264,12 @@ static int sweep_chunks(sfa_session *s, const int32_t *slot, const Chunk *ch, in
     int64_t n_tasks = 0;
     for (const sfa::SessionArgs &a : args) {
         const dim3 grid((a.n_tasks + 3) / 4), block(256);
-        if (s->track)
+        if (s->n_cand > 0) {  // (every piece of a long chunk: the last one's list stays)
+            if (s->track)
+                hipLaunchKernelGGL((sfa::sdtw_session_kernel<true, true>), grid, block, 0, st, a);
+            else
+                hipLaunchKernelGGL((sfa::sdtw_session_kernel<false, true>), grid, block, 0, st, a);
+        } else if (s->track)
             hipLaunchKernelGGL(sfa::sdtw_session_kernel<true>, grid, block, 0, st, a);
         else
             hipLaunchKernelGGL(sfa::sdtw_session_kernel<false>, grid, block, 0, st, a);
@@ -284,6 +295,23 @@ static int sweep_chunks(sfa_session *s, const int32_t *slot, const Chunk *ch, in
         ra.track = s->track ? 1 : 0;
         hipLaunchKernelGGL(sfa::sdtw_session_rows_kernel, dim3((n + 63) / 64), dim3(64), 0, st, ra);
         KERNEL_TRY();
+        if (s->n_cand > 0 && !args.empty()) {  // (nothing swept: every slot keeps its candidates)
+            sfa::SessionCandArgs ca;
+            ca.call_slot = ra.call_slot;
+            ca.bad = ra.bad;
+            ca.p_top5 = s->d_p5.as<int32_t>();
+            ca.job_contig = ra.job_contig;
+            ca.job_strand = ra.job_strand;
+            ca.ref_len = ra.ref_len;
+            ca.ref_st_offset = ra.ref_st_offset;
+            ca.cand = s->d_cand.as<sfa::ResultRow>();
+            ca.n_call = n;
+            ca.n_jobs = nj;
+            ca.n_cand = s->n_cand;
+            ca.track = ra.track;
+            hipLaunchKernelGGL(sfa::sdtw_session_cand_kernel, dim3((n + 63) / 64), dim3(64), 0, st, ca);
+            KERNEL_TRY();
+        }
     }
     HIP_TRY(hipEventRecord(s->ev[3], st));
     HIP_TRY(hipMemcpyAsync(s->h_rows.p, s->d_rows.p, sizeof(sfa_result_t) * s->n_slots, hipMemcpyDeviceToHost, st));
@@ -371,6 +399,44 @@ int sfa_session_create(sfa_ctx_t *c, int32_t n_slots, uint32_t session_flags, sf
     HIP_TRY(hipStreamSynchronize(c->stream));  // (col_off leaves scope)
     c->sessions.push_back(s.get());
     *out = s.release();
+    return SFA_OK;
+}
+
+int sfa_session_candidates_config(sfa_session_t *s, int32_t n_candidates) {
+    if (!s) return fail(SFA_EINVAL, "sfa_session_candidates_config: null session");
+    if (n_candidates < 0 || n_candidates > 4) return fail(SFA_EINVAL, "sfa_session_candidates_config: n_candidates must be 0..4, not %d", n_candidates);
+    for (int32_t sl = 0; sl < s->n_slots; ++sl)
+        if (s->len[sl] != 0 || s->poison[sl] || (s->raw && !s->raw_fresh[sl]))
+            return fail(SFA_EINVAL, "sfa_session_candidates_config: slot %d is not empty; the lists are switched only while every slot is (sfa_session_reset)", sl);
+    if (n_candidates > 0) {
+        sfa_ctx *c = s->c;
+        HIP_TRY(hipSetDevice(c->device));
+        const size_t bytes = sizeof(sfa_result_t) * 4 * static_cast<size_t>(s->n_slots);
+        if (int rc = reserve_all(s->d_cand, bytes, s->h_cand, bytes)) return rc;
+        HIP_TRY(hipMemsetAsync(s->d_cand.p, 0, bytes, c->stream));  // (valid = 0; a slot's rows are written by its first sweep)
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    s->n_cand = n_candidates;
+    return SFA_OK;
+}
+
+int sfa_session_candidates(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_result_t *sec) {
+    if (!s) return fail(SFA_EINVAL, "sfa_session_candidates: null session");
+    if (n < 0 || (n > 0 && (!slot || !sec))) return fail(SFA_EINVAL, "sfa_session_candidates: bad argument");
+    if (s->n_cand == 0) return fail(SFA_EINVAL, "sfa_session_candidates: the session keeps no candidates (sfa_session_candidates_config)");
+    for (int32_t i = 0; i < n; ++i)
+        if (slot[i] < 0 || slot[i] >= s->n_slots) return fail(SFA_EINVAL, "sfa_session_candidates: slot %d out of range (the session has %d)", slot[i], s->n_slots);
+    if (n == 0) return SFA_OK;
+    sfa_ctx *c = s->c;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(s->h_cand.p, s->d_cand.p, sizeof(sfa_result_t) * 4 * static_cast<size_t>(s->n_slots), hipMemcpyDeviceToHost, c->stream));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(SFA_EKERNEL, "sfa_session_candidates: the copy failed: %s", hipGetErrorString(hipGetLastError()));
+    const sfa_result_t *cand = s->h_cand.as<sfa_result_t>();
+    for (int32_t i = 0; i < n; ++i) {  // (the reset is host-only: lengths and poison flags decide, as for the rows)
+        const int32_t sl = slot[i];
+        const bool none = s->poison[sl] || s->len[sl] == 0;
+        for (int k = 0; k < 4; ++k) sec[4 * static_cast<size_t>(i) + k] = none ? kNoRow : cand[4 * static_cast<size_t>(sl) + k];
+    }
     return SFA_OK;
 }
 

@@ -12,6 +12,9 @@ ticks, the same calls, the same lines.  The schedule counts ticks, never seconds
             window's events; what direct RNA without --invert needs); schedule and rule are the same, q_events counts the window
   decision  decide(): 'E' early (calibrated, q_events >= min_events, mapped, mapq >= min_mapq), 'F' full, 'R' end of read (or a
             poisoned slot); a decision has a line when its row is mapped
+  candidates --candidates N: the session keeps N candidates per slot (Session.configure_candidates); those of all channels
+            decided in a tick are fetched in one Session.candidates call before the reset, and a channel's valid ones follow its
+            primary line, best first (format_candidates)
   after it  decided channels are reset in one call and take the next unread reads, lowest channel first, from tick t + 1 on
 """
 import numpy as np
@@ -100,8 +103,12 @@ def recal_points(norm, query, recalibrate=(), at_end=False):
     return at
 
 
-def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False, resweep=False):
+def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False, resweep=False,
+           candidates=0):
     """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
+    candidates=1..4 (--candidates): an eighth element, RESULT_DTYPE[4], the channel's candidates at the decision, best first.
+    A `session` of the caller's is taken as it is, in this as in its raw mode: it must keep that many candidates already
+    (Session.configure_candidates), which is checked before the first tick.
 
     reads: iterable of (read_id, meta, samples) in file order, as Blow5File yields them (taken lazily: at most `channels` reads are
     held).  row / info: the channel's entries of Session.extend_raw at the decision; span: (start_raw, end_raw) of
@@ -132,7 +139,11 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     se = aligner.session(channels, resweep=resweep) if own else session
     try:
         if own:
+            if candidates:
+                se.configure_candidates(candidates)
             se.configure_raw(skip, norm, query, recal_points(norm, query, recalibrate, at_end), at_end)
+        if candidates and not own:
+            se.candidates([])  # (raises unless the caller's session keeps candidates)
         sch.start(src)
         while sch.busy():
             es = sch.begin_tick()
@@ -147,8 +158,10 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
             if decided:
                 d_slots = [slots[i] for i in decided]
                 a, b = se.query_span(d_slots)
+                cand = se.candidates(d_slots) if candidates else None
                 for k, i in enumerate(decided):
-                    yield sch.tick, slots[i], on[slots[i]][0], rows[i].copy(), info[i].copy(), (int(a[k]), int(b[k])), reason[i]
+                    item = (sch.tick, slots[i], on[slots[i]][0], rows[i].copy(), info[i].copy(), (int(a[k]), int(b[k])), reason[i])
+                    yield item + (cand[k].copy(),) if candidates else item
                 se.reset(d_slots)
             sch.end_tick(reason, line, src)
     finally:
@@ -164,3 +177,19 @@ def format_line(read_id, n_samples, names, seq_lengths, row, info, span, reason)
     rid = int(row["rid"])
     base = api.paf_row(row, read_id, names[rid], span[0], span[1], int(info["q_events"]) - 1, int(n_samples), int(seq_lengths[rid]))
     return f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}\n"
+
+
+def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, span, reason):
+    """The candidate lines that follow a decision's primary line under --candidates: one per valid row of `cand`, best first, each
+    the tp:A:S line of paf_row_ex with the primary's span and query_size and the primary's three tags; "" when the primary has no
+    line."""
+    if not mapped(row):
+        return ""
+    out = []
+    for r in cand:
+        if not mapped(r):
+            continue
+        rid = int(r["rid"])
+        base = api.paf_row(r, read_id, names[rid], span[0], span[1], int(info["q_events"]) - 1, int(n_samples), int(seq_lengths[rid]), tp="S")
+        out.append(f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}\n")
+    return "".join(out)
