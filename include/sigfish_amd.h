@@ -372,6 +372,60 @@ int sfa_session_query_span(sfa_session_t *s, const int32_t *slot, int32_t n, uin
  * query <= 0 or a product beyond 2^63. */
 int64_t sfa_session_raw_bytes(int32_t n_slots, int32_t skip_events, int32_t query_events);
 
+/* ---- automatic query start in a raw session: the RNA "-p -1" of sfa_align_raw, found while the read streams ----------------
+ * The adaptor segmenter of detect_query_start is not causal (its threshold is taken over the whole signal), so a session has a
+ * rule of its own, stated on samples; state depends on the samples a slot has received, never on how they were cut into calls.
+ *   target(N)   what detect_query_start computes before it looks at events, applied to the slot's first N samples: polya.y + ad.y,
+ *               a sample index, or -1 when either segmenter fails (sfa_auto_start_target; needs N > 2000).
+ *   points      every N_k = k * every_samples <= max_samples, counted from the slot's first sample after its reset
+ *               (every_samples = 0: none), and one FINAL point at min(samples received, max_samples), taken when the slot's end of
+ *               read is seen or when it has received max_samples samples, whichever comes first.  A call that carries a slot
+ *               past several points evaluates them in ascending order, each on its own prefix.
+ *   freezing    the target is frozen at the first point with target(N_k) >= 0; later points are not evaluated.  (A poly-A stretch
+ *               still open at N_k gives -1, so a frozen target lies in front of N_k.)
+ *   skip        the index of the first final event whose start >= target, resolved in the call in which that event becomes final.
+ *               Until then the slot has no query: q_events = 0, not calibrated.
+ *   failure     the final point gives -1; or the read ends with no event at or behind the frozen target; or the resolved skip
+ *               is beyond the largest allowed.  The slot then takes skip = 50, the reference's fallback, and reports why.
+ * After that everything is the rule of the raw session with the slot's own skip: windows, SFA_RECAL_AT_END and resweep unchanged,
+ * "full" is n_events >= skip + query; the detector stops at the table's capacity only, so n_events may run to max skip + query.
+ * With every_samples = 0 and max_samples >= the read's length the only point is the whole read: target, skip and the fallback
+ * are those of sfa_align_raw(prefix_size = -1), and with norm = query and SFA_RECAL_AT_END so is the row after the end of read.
+ *
+ * sfa_session_raw_auto_start: allowed on a raw-mode session created with SFA_SESSION_RESWEEP, on an SFA_RNA context without
+ * SFA_END / SFA_INV, while every slot is empty.  The skip_events given to sfa_session_raw_config becomes the LARGEST skip a slot
+ * may resolve (it stays the table size: skip + query records) and must be >= 50.  max_samples <= 2^20; max_samples = 0 switches
+ * the feature off, and so does sfa_session_raw_config.  flags must be 0.  Everything else is SFA_EINVAL.  The segmenter constants
+ * follow the context's pore (sfa_set_pore), as for sfa_align_raw. */
+int sfa_session_raw_auto_start(sfa_session_t *s, int32_t every_samples, int32_t max_samples, uint32_t flags);
+
+#define SFA_AUTO_PENDING 0     /* no skip yet (a target may be frozen already) */
+#define SFA_AUTO_RESOLVED 1    /* skip is the first event at or behind the target */
+#define SFA_AUTO_NO_TARGET 2   /* failed: the final point gave no target; skip = 50 */
+#define SFA_AUTO_NO_EVENT 3    /* failed: the read ended with no event at or behind the target; skip = 50 */
+#define SFA_AUTO_BEYOND_MAX 4  /* failed: the event lies beyond the largest skip; skip = 50 */
+#define SFA_AUTO_AT_FINAL 16   /* (bit) frozen_at is the slot's final point */
+typedef struct {
+    int64_t target;    /* the frozen target sample, -1 before (and after a failure without one) */
+    int64_t frozen_at; /* the point N_k at which the target was frozen, or the final point that gave none; 0 before */
+    int32_t skip;      /* the slot's skip, -1 while unresolved */
+    int32_t status;    /* SFA_AUTO_* in the low four bits | SFA_AUTO_AT_FINAL */
+} sfa_session_auto_t;
+
+/* The automatic start of slot[i], i < n, as the last call left it (host memory, no device work).  SFA_EINVAL on a session without
+ * the feature or a slot out of range. */
+int sfa_session_auto_start(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_session_auto_t *out);
+
+/* Device time, in ms, that retention and evaluation (the two kernels the feature adds in front of the normaliser) took in the
+ * session's last sfa_session_extend_raw call, from events on the context's stream; sfa_profile_t.normalise_ms of that call
+ * includes it.  0 before the first call, -1 on a session without the feature. */
+double sfa_session_auto_ms(sfa_session_t *s);
+
+/* Device memory the feature adds: per slot max_samples x 2 bytes of retained samples, 16 bytes of state, and (max_samples + 1)
+ * x 4 bytes of prefix sums for a call in which every slot has a pending point (the scratch grows to the largest such call).
+ * Host arithmetic; negative for n_slots <= 0, max_samples <= 0 or > 2^20. */
+int64_t sfa_session_auto_bytes(int32_t n_slots, int32_t max_samples);
+
 /* align_db() shaped entry: per-read event tables exactly as db_t holds them (src/sigfish.h:177-178):
  * events[i] -> sfa_event_t array of read i, qstart[i]/qend[i] the window chosen by normalise_single
  * (src/sigfish.c:479-480); reads with n_events[i]==0 are skipped.  The window means are gathered out of the 24-byte event
@@ -588,6 +642,11 @@ int sfa_select_query(sfa_event_t *events, int64_t n_events, const int16_t *raw, 
  * then start at event 50).  events: the read's event table (sfa_detect_events); pore as for sfa_set_pore. */
 int64_t sfa_detect_query_start(const int16_t *raw, int64_t n_raw, double digitisation, double offset, double range,
                                const sfa_event_t *events, int64_t n_events, int pore);
+
+/* What detect_query_start computes before it looks at events, for the first n samples of a read: the sample index behind the
+ * poly-A tail that follows the adaptor (polya.y + ad.y), or -1 when the adaptor or the tail is not found (n <= 2000 among the
+ * causes).  The host twin of a session's automatic query start (sfa_session_raw_auto_start). */
+int64_t sfa_auto_start_target(const int16_t *raw, int64_t n, double digitisation, double offset, double range, int pore);
 
 /* One SAM line for a result row (sam_str, src/sigfish.c:770-794, with path_to_map 530-571 and the "ss" string of
  * r2qevent_map_to_ss 663-768).  The warp path of the winner is rebuilt on the host from the band between its

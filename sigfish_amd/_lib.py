@@ -55,6 +55,10 @@ class SfaSessionRawInfo(C.Structure):
                 ("norm_sd", C.c_float), ("status", C.c_int32), ("norm_window", C.c_int32)]
 
 
+class SfaSessionAuto(C.Structure):
+    _fields_ = [("target", C.c_int64), ("frozen_at", C.c_int64), ("skip", C.c_int32), ("status", C.c_int32)]
+
+
 # every symbol include/sigfish_amd.h declares (checked by tests/test_capi_host.py::test_library_exports_every_declared_symbol)
 SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "sfa_submit_batch", "sfa_wait_batch", "sfa_align_batch_device", "sfa_align_events", "sfa_align_raw", "sfa_align_raw_ex", "sfa_align_blow5", "sfa_inflate_zlib_device", "sfa_detect_events_device", "sfa_pinned_alloc", "sfa_pinned_free", "sfa_sync",
            "sfa_get_profile", "sfa_stream", "sfa_set_option", "sfa_plan_batch", "sfa_destroy", "sfa_last_error", "sfa_version", "sfa_build_id", "sfa_gen_ref_record",
@@ -63,7 +67,8 @@ SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "
            "sfa_session_create", "sfa_session_extend", "sfa_session_reset", "sfa_session_lengths", "sfa_session_destroy", "sfa_session_bytes",
            "sfa_event_stream_create", "sfa_event_stream_push", "sfa_event_stream_finish", "sfa_event_stream_destroy",
            "sfa_session_raw_config", "sfa_session_extend_raw", "sfa_session_events", "sfa_session_raw_bytes", "sfa_session_query_span", "sfa_session_row",
-           "sfa_session_raw_recalibrate", "sfa_session_candidates_config", "sfa_session_candidates"]
+           "sfa_session_raw_recalibrate", "sfa_session_candidates_config", "sfa_session_candidates",
+           "sfa_session_raw_auto_start", "sfa_session_auto_start", "sfa_session_auto_bytes", "sfa_auto_start_target", "sfa_session_auto_ms"]
 
 _lib = None
 
@@ -177,5 +182,13 @@ def load():
     L.sfa_session_raw_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.sfa_session_raw_bytes.restype = C.c_int64
     L.sfa_session_query_span.argtypes = [vp, i32p, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.sfa_session_raw_auto_start.argtypes = [vp, C.c_int32, C.c_int32, C.c_uint32]
+    L.sfa_session_auto_start.argtypes = [vp, i32p, C.c_int32, vp]
+    L.sfa_session_auto_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.sfa_session_auto_bytes.restype = C.c_int64
+    L.sfa_auto_start_target.argtypes = [i16p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int]
+    L.sfa_auto_start_target.restype = C.c_int64
+    L.sfa_session_auto_ms.argtypes = [vp]
+    L.sfa_session_auto_ms.restype = C.c_double
     _lib = L
     return L

@@ -28,6 +28,8 @@ SESSION_RAW_INFO_DTYPE = np.dtype([("n_samples", "<i8"), ("n_events", "<i8"), ("
                                    ("status", "<i4"), ("norm_window", "<i4")])
 assert SESSION_RAW_INFO_DTYPE.itemsize == C.sizeof(_lib.SfaSessionRawInfo)
 RAW_CALIBRATED, RAW_FULL, RAW_ENDED, RAW_POISONED = 1, 2, 4, 8  # bits of SESSION_RAW_INFO_DTYPE's status
+SESSION_AUTO_DTYPE = np.dtype([("target", "<i8"), ("frozen_at", "<i8"), ("skip", "<i4"), ("status", "<i4")])  # sfa_session_auto_t
+AUTO_PENDING, AUTO_RESOLVED, AUTO_NO_TARGET, AUTO_NO_EVENT, AUTO_BEYOND_MAX, AUTO_AT_FINAL = 0, 1, 2, 3, 4, 16  # SFA_AUTO_*
 RAW_RECALIBRATED = 16  # ... and the bit of one call: the slot was recalibrated and swept again from event 0
 RECAL_AT_END = 0x1     # SFA_RECAL_AT_END
 RECAL_MAX_POINTS = 32
@@ -269,13 +271,24 @@ class Aligner:
                "sfa_align_events")
         return out
 
-    def session(self, n_slots, starts=True, resweep=False, flags=None, candidates=0):
+    def session(self, n_slots, starts=True, resweep=False, flags=None, candidates=0, auto_start=None):
         """An alignment session of n_slots growing reads on this aligner (sfa_session_create); starts=False carries costs only
         (SFA_SESSION_NO_START: half the memory, the coordinate on the start side of every row is -1).  resweep=True
         (SFA_SESSION_RESWEEP): a raw-mode-only session that sweeps a slot only when its normalisation window changes, over the
         window's events -- the one kind of session an RNA aligner without INV can have (its query is the events reversed).
-        flags: the raw flag word in place of starts / resweep.  candidates=1..4: configure_candidates() on the new session."""
+        flags: the raw flag word in place of starts / resweep.  candidates=1..4: configure_candidates() on the new session.
+        auto_start=dict(skip=, norm=, query=, every=, max_samples=[, recalibrate=, at_end=]): configure_raw() with skip as the
+        largest skip, then configure_auto_start(every, max_samples), on the new session."""
         s = Session(self, n_slots, starts, resweep, flags)
+        if auto_start is not None:
+            try:
+                a = dict(auto_start)
+                every, max_samples = a.pop("every"), a.pop("max_samples")
+                s.configure_raw(**a)
+                s.configure_auto_start(every, max_samples)
+            except Exception:
+                s.close()
+                raise
         if candidates:
             try:
                 s.configure_candidates(candidates)
@@ -508,6 +521,29 @@ class Session:
         fl = (RECAL_AT_END if at_end else 0) if flags is None else int(flags)
         _check(self._L.sfa_session_raw_recalibrate(self._h, pts.ctypes.data_as(_lib.i32p) if len(pts) else None, len(pts), fl), "sfa_session_raw_recalibrate")
 
+    def configure_auto_start(self, every, max_samples):
+        """The RNA automatic query start (-p -1) as the read streams (sfa_session_raw_auto_start), on a resweep session in raw mode
+        over an RNA aligner without INV / END, while every slot is empty: the target of a slot is auto_start_target() of its
+        first N samples at N = every, 2 every, ... <= max_samples and at one final point (end of read, or max_samples samples),
+        frozen at the first point that gives one; its skip is the first event at or behind the target, or the fallback 50.  The
+        skip given to configure_raw() is the largest skip a slot may resolve.  max_samples=0 switches it off."""
+        self._live()
+        _check(self._L.sfa_session_raw_auto_start(self._h, int(every), int(max_samples), 0), "sfa_session_raw_auto_start")
+
+    def auto_start(self, slots):
+        """The automatic start of `slots` as the last call left it -> SESSION_AUTO_DTYPE[len(slots)]: target sample (-1), the point
+        it was frozen at, skip (-1 while unresolved), status (AUTO_* | AUTO_AT_FINAL)."""
+        self._live()
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        out = np.zeros(len(sl), SESSION_AUTO_DTYPE)
+        _check(self._L.sfa_session_auto_start(self._h, sl.ctypes.data_as(_lib.i32p), len(sl), out.ctypes.data_as(C.c_void_p)), "sfa_session_auto_start")
+        return out
+
+    def auto_ms(self):
+        """Device ms the feature's own kernels (retention, evaluation) took in the last extend_raw call (sfa_session_auto_ms)."""
+        self._live()
+        return float(self._L.sfa_session_auto_ms(self._h))
+
     def extend_raw(self, slots, raw, raw_off, scaling, end=None):
         """Append raw[raw_off[i]:raw_off[i+1]] (int16 samples) to slot slots[i]; scaling[i] = (digitisation, offset, range); end[i]
         true: the read of slot i ends behind these samples. -> (RESULT_DTYPE[len(slots)], SESSION_RAW_INFO_DTYPE[len(slots)])"""
@@ -623,6 +659,15 @@ def session_raw_bytes(n_slots, skip=50, query=2048):
     b = int(_lib.load().sfa_session_raw_bytes(int(n_slots), int(skip), int(query)))
     if b < 0:
         raise SfaError(f"sfa_session_raw_bytes failed ({b}): n_slots and query must be positive, skip not negative")
+    return b
+
+
+def session_auto_bytes(n_slots, max_samples):
+    """Device memory the automatic query start adds to a session (sfa_session_auto_bytes; host arithmetic): per slot max_samples x 2
+    bytes of samples, 16 bytes of state, (max_samples + 1) x 4 bytes of prefix sums for a call in which every slot has a point."""
+    b = int(_lib.load().sfa_session_auto_bytes(int(n_slots), int(max_samples)))
+    if b < 0:
+        raise SfaError(f"sfa_session_auto_bytes failed ({b}): n_slots and max_samples must be positive, max_samples at most 2^20")
     return b
 
 
@@ -789,6 +834,14 @@ def detect_query_start(raw, meta, events, pore=0):
     return int(_lib.load().sfa_detect_query_start(raw.ctypes.data_as(C.POINTER(C.c_int16)), len(raw), meta["digitisation"],
                                                   meta["offset"], meta["range"], C.cast(ev.ctypes.data, C.POINTER(_lib.SfaEvent)),
                                                   len(ev), int(pore)))
+
+
+def auto_start_target(raw, meta, pore=0):
+    """What detect_query_start computes before it looks at events, for the samples `raw` (a read or a prefix of one): the sample
+    index behind the poly-A tail that follows the adaptor, or -1 (sfa_auto_start_target)."""
+    raw = np.ascontiguousarray(raw, np.int16)
+    return int(_lib.load().sfa_auto_start_target(raw.ctypes.data_as(C.POINTER(C.c_int16)), len(raw), meta["digitisation"], meta["offset"],
+                                                 meta["range"], int(pore)))
 
 
 def read_kmer_model(path, warnings=None):

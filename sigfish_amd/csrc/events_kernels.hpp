@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "jnn_consts.hpp"
+
 namespace sfa {
 
 struct EvArgs {
@@ -600,8 +602,7 @@ struct AutoArgs {
     float std_scale;          // 0.7 for RNA004, else 0.5
 };
 
-constexpr int kAdWindow = 2000, kAdSegDist = 1500, kAdHi = 200000;                  // jnnv2() with JNNV2_RNA_*_ADAPTOR
-constexpr int kPaCorrector = 50, kPaSegDist = 200, kPaWindow = 250, kPaError = 30;  // jnn_core() with JNNV1_*_POLYA
+// (kAdWindow, kAdSegDist, kAdHi and kPa*: jnn_consts.hpp, shared with the session kernels)
 
 // The adaptor segmenter's rolling mean t[j] = mean(clamp(raw[j .. j+2000))).  The reference keeps a running fp32 sum
 // (run -= cur[j-1]; run += cur[j+1999], jnn.c:22-46).  Its addends are clamp_outlier((float)raw): integers in [0, 1200],

@@ -281,6 +281,46 @@ struct EvStreamOut {
     int32_t window, pad;                       // events the mean and sd span (0: not calibrated)
 };
 
+// status of a slot's automatic start: the low nibble is the state, kAutoAtFinal says the target was frozen (or given up) at
+// the slot's final point (sfa_session_auto_t.status)
+constexpr int kAutoPending = 0, kAutoResolved = 1, kAutoNoTarget = 2, kAutoNoEvent = 3, kAutoBeyondMax = 4, kAutoAtFinal = 16;
+constexpr int kAutoFallback = 50;                 // the reference's fallback skip, src/sigfish.c:438-446
+constexpr int32_t kAutoMaxSamples = 1 << 20;      // 1200 x 2^20 < 2^31: the prefix sums of a slot fit 32 bits
+
+struct EvAutoSlot {   // per slot, device memory; sfa_session_auto_t is made of it
+    int32_t target;     // frozen target sample, -1 before
+    int32_t skip;       // resolved skip, -1 before
+    int32_t frozen_at;  // the point N_k at which the target was frozen (or the final point that gave none), 0 before
+    int32_t status;     // kAuto*
+};
+
+// what ev_stream_norm_kernel does for a session with the automatic start before anything else: the slot's skip.  Block-uniform.
+// A frozen target is resolved to the first final event whose start is >= target (starts ascend, so the binary search equals the
+// reference's walk) in the call in which that event is in the table; *au is updated where something changed.
+__device__ __forceinline__ bool auto_resolve(EvAutoSlot *au, const EvRecord *ev, int nev, int ev_cap, int max_skip, bool ended) {
+    if (au->skip >= 0 || au->target < 0) return false;
+    const uint64_t target = static_cast<uint64_t>(au->target);
+    int lo = 0, hi = nev;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (ev[mid].start < target) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo < nev && lo <= max_skip) {
+        au->skip = lo;
+        au->status = (au->status & ~15) | kAutoResolved;
+    } else if (lo < nev || nev >= ev_cap) {  // the table is full below the target: the event would lie beyond it
+        au->skip = kAutoFallback;
+        au->status = (au->status & ~15) | kAutoBeyondMax;
+    } else if (ended) {
+        au->skip = kAutoFallback;
+        au->status = (au->status & ~15) | kAutoNoEvent;
+    } else {
+        return false;
+    }
+    return true;
+}
+
 struct EvNormArgs {
     const int32_t *slot;     // [n]
     EvStreamSlot *state;
@@ -298,6 +338,13 @@ struct EvNormArgs {
     int32_t reversed;        // (with resweep) q[i] = z(event[skip + W - 1 - i]): SFA_RNA without SFA_INV
 };
 
+// the second argument of ev_stream_norm_kernel: read by the <true> instantiation only (automatic query start), so that the
+// argument block and the code of the <false> one stay what they were.  EvNormArgs.skip is then the largest skip a slot may resolve
+struct EvNormAutoArgs {
+    EvAutoSlot *state;  // [n_slots] the slots' targets and skips
+    EvAutoSlot *out;    // [n] what the call's slots hold after it
+};
+
 constexpr int kNormTile = 2048;  // pA means staged per tile of the statistics: 8 KB of LDS
 
 // One wave per slot of the call.  The window W the slot must have now follows from its counts (recal_window).  Where it differs
@@ -308,7 +355,12 @@ constexpr int kNormTile = 2048;  // pA means staged per tile of the statistics: 
 // Resweep mode (a.resweep, block-uniform like a.reversed): no append.  A change of W writes q[0, W) -- lane l stores q[i] from
 // record skip + i, or skip + W - 1 - i when reversed: consecutive lanes still read consecutive records -- and reports q_first = 0,
 // q_new = W; any other call reports q_new = 0 and leaves q_done = W.  Events beyond skip + W wait in the table for the next point.
-__global__ void __launch_bounds__(64) ev_stream_norm_kernel(const EvNormArgs a) {
+//
+// AUTO (sfa_session_raw_auto_start): the slot's skip is its own.  It is resolved here first (auto_resolve), and until it is the
+// slot has no query: q_avail = 0, not calibrated.  Everything behind that is the rule above with the slot's skip in place of
+// a.skip, and "full" is n_events >= skip + query.  The instantiation without AUTO is the kernel as it was.
+template <bool AUTO>
+__global__ void __launch_bounds__(64) ev_stream_norm_kernel(const EvNormArgs a, const EvNormAutoArgs x) {
     __shared__ float tile[kNormTile];
     __shared__ float stat[2];
     __shared__ int s_status;
@@ -319,7 +371,13 @@ __global__ void __launch_bounds__(64) ev_stream_norm_kernel(const EvNormArgs a) 
     const int nev = st->n_events, q_done = st->q_done;
     int status = st->status;
     float mean = st->mean, sd = st->sd;
-    const int q_avail = recal_q_avail(nev, a.skip, a.query_cap);
+    EvAutoSlot au{};
+    bool au_changed = false;
+    if constexpr (AUTO) {
+        au = x.state[slot];
+        au_changed = auto_resolve(&au, ev, nev, a.ev_cap, a.skip, (status & kRawEnded) != 0);
+    }
+    const int q_avail = (AUTO && au.skip < 0) ? 0 : recal_q_avail(nev, AUTO ? au.skip : a.skip, a.query_cap);
     const int w_cur = (status & kRawCalibrated) ? a.window[slot] : 0;
     int w = w_cur;
     if (!(status & kRawPoisoned))  // (a poisoned slot keeps what poisoned it until it is reset)
@@ -331,7 +389,7 @@ __global__ void __launch_bounds__(64) ev_stream_norm_kernel(const EvNormArgs a) 
         for (int pass = 0; pass < 2; ++pass) {
             for (int base = 0; base < w; base += kNormTile) {
                 const int len = min(kNormTile, w - base);
-                for (int j = lane; j < len; j += 64) tile[j] = ev[a.skip + base + j].mean;
+                for (int j = lane; j < len; j += 64) tile[j] = ev[(AUTO ? au.skip : a.skip) + base + j].mean;
                 __syncthreads();
                 if (lane == 0) {  // sfa_znormalise's sums, in its order
                     if (pass == 0) {
@@ -369,7 +427,7 @@ __global__ void __launch_bounds__(64) ev_stream_norm_kernel(const EvNormArgs a) 
         float *q = a.query + static_cast<int64_t>(slot) * a.query_cap;
         bool bad = false;
         for (int e = q_first + lane; e < q_end; e += 64) {
-            const float v = (ev[a.skip + (a.reversed ? q_top - e : e)].mean - mean) / sd;
+            const float v = (ev[(AUTO ? au.skip : a.skip) + (a.reversed ? q_top - e : e)].mean - mean) / sd;
             q[e] = v;
             bad = bad || !(fabsf(v) <= 3.402823466e+38f);
         }
@@ -389,6 +447,12 @@ __global__ void __launch_bounds__(64) ev_stream_norm_kernel(const EvNormArgs a) 
         o.q_first = (status & kRawPoisoned) ? q_done : q_first;
         o.q_new = q_new;
         o.status = (status & 15) | ((recal && q_done > 0 && q_new > 0) ? kRawResweep : 0);
+        if constexpr (AUTO) {
+            o.status &= ~kRawFull;  // (the detector's bit means the TABLE is full; a slot is full at skip + query events)
+            if (au.skip >= 0 && nev >= au.skip + a.query_cap) o.status |= kRawFull;
+            if (au_changed) x.state[slot] = au;
+            x.out[i] = au;
+        }
         o.mean = mean;
         o.sd = sd;
         o.window = w;
@@ -406,15 +470,17 @@ struct EvSpanArgs {
     const EvRecord *events;  // [n_slots][ev_cap]
     uint64_t *span;          // [n][2] start of event skip | start + length of event skip + q_events - 1
     int32_t n, ev_cap, skip, query_cap;
+    const int32_t *skips;    // [n] PER_SLOT only (automatic query start): each slot's own skip in place of `skip`
 };
 
+template <bool PER_SLOT>
 __global__ void __launch_bounds__(64) ev_query_span_kernel(const EvSpanArgs a) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= a.n) return;
     const int q = min(a.q_events[i], a.query_cap);
     uint64_t first = 0, last = 0;
     if (q > 0) {
-        const EvRecord *ev = a.events + static_cast<int64_t>(a.slot[i]) * a.ev_cap + a.skip;
+        const EvRecord *ev = a.events + static_cast<int64_t>(a.slot[i]) * a.ev_cap + (PER_SLOT ? a.skips[i] : a.skip);
         first = ev[0].start;
         last = ev[q - 1].start + static_cast<uint64_t>(ev[q - 1].length);
     }

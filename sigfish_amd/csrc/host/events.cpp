@@ -403,15 +403,20 @@ Seg find_polya(const float *pa, int64_t n, float top, float bot) {
 
 }  // namespace
 
-int64_t detect_query_start(const int16_t *raw, int64_t n, const float *pa, const std::vector<sfa_event_t> &ev, int pore) {
+int64_t auto_start_target(const int16_t *raw, int64_t n, const float *pa, int pore) {
     const Seg ad = find_adaptor(raw, n, pore);
     if (ad.y <= 0) return -1;
     const float m_a = mean_f(pa + ad.x, static_cast<int>(ad.y - ad.x));
     Seg polya = find_polya(pa + ad.y, n - ad.y, m_a + 30 + 20, m_a + 30 - 20);
     if (polya.y <= 0) return -1;
-    polya.y += ad.y;
+    return polya.y + ad.y;
+}
+
+int64_t detect_query_start(const int16_t *raw, int64_t n, const float *pa, const std::vector<sfa_event_t> &ev, int pore) {
+    const int64_t target = auto_start_target(raw, n, pa, pore);
+    if (target < 0) return -1;
     uint64_t i = 0;
-    while (i < ev.size() && ev[i].start < static_cast<uint64_t>(polya.y)) i++;
+    while (i < ev.size() && ev[i].start < static_cast<uint64_t>(target)) i++;
     return i >= ev.size() ? -1 : static_cast<int64_t>(i);
 }
 

@@ -19,6 +19,11 @@ std::vector<sfa_event_t> detect_events(const float *pa, int64_t n, bool rna);
 // returns the first event index after the poly-A tail or -1
 int64_t detect_query_start(const int16_t *raw, int64_t n, const float *pa, const std::vector<sfa_event_t> &ev, int pore);
 
+// what detect_query_start() computes before it looks at events: the sample index polya.y + ad.y behind the poly-A tail that
+// follows the adaptor, or -1 when either segmenter fails (n <= 2000 among the causes).  Applied to a PREFIX of a read it is the
+// target of a raw session's automatic query start (sfa_session_raw_auto_start)
+int64_t auto_start_target(const int16_t *raw, int64_t n, const float *pa, int pore);
+
 // normalise_single(), src/sigfish.c:424-505: choose [qstart,qend), z-normalise the event means in place.
 // Returns false when the read is dropped (et.n = 0 in the reference).  *status: 0 ok, 1 too short (kept),
 // 2 ignored, |4 when the automatic prefix detection failed (fallback 50).

@@ -220,6 +220,13 @@ int64_t sfa_detect_query_start(const int16_t *raw, int64_t n_raw, double digitis
     return sfa::detect_query_start(raw, n_raw, pa.data(), ev, pore);
 }
 
+int64_t sfa_auto_start_target(const int16_t *raw, int64_t n, double digitisation, double offset, double range, int pore) {
+    if (!raw || n <= 0) return -1;
+    std::vector<float> pa(static_cast<size_t>(n));
+    sfa::raw_to_picoamps(raw, n, digitisation, offset, range, pa.data());
+    return sfa::auto_start_target(raw, n, pa.data(), pore);
+}
+
 }  // extern "C"
 namespace {
 // the winner's warp path from its result row: query in DP order, columns of the strand's own array

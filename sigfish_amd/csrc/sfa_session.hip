@@ -7,6 +7,7 @@
 #define SFA_DEFINE_SESSION_KERNELS  // (this unit holds the plain kernel of sdtw_session.hpp)
 #include "sdtw_session.hpp"
 #include "events_stream.hpp"
+#include "events_auto_stream.hpp"
 
 namespace sfa {
 // defined in sfa_align.hip, the unit that holds the plain kernels of sdtw_kernels.hpp
@@ -50,8 +51,17 @@ struct sfa_session {
     DevBuf d_raw, d_rstage, d_rout;    // of a call: samples, entry tables, EvStreamOut per entry
     PinBuf h_rstage, h_rout;
     Event ev_raw[3];                   // detector start / end, normalisation end
-    DevBuf d_span_in, d_span;          // of a sfa_session_query_span call: [slot n | q_events n] x i32, [n][2] u64
+    DevBuf d_span_in, d_span;          // of a sfa_session_query_span call: [slot n | q_events n (| skip n)] x i32, [n][2] u64
     PinBuf h_span_in, h_span;
+    // ---- automatic query start (sfa_session_raw_auto_start); `skip` is then the largest skip a slot may resolve ----
+    int32_t auto_every = 0, auto_max = 0;  // auto_max 0: off
+    std::vector<sfa::EvAutoSlot> auto_h;   // what every slot's device state holds (read back by each call)
+    std::vector<int32_t> auto_k;           // periodic points N_k a slot has passed
+    std::vector<uint8_t> auto_final;       // its final point has been taken
+    DevBuf d_auto, d_keep, d_csum, d_aout; // [n_slots] EvAutoSlot, [n_slots][auto_max] i16, of a call: prefix sums, EvAutoSlot per entry
+    PinBuf h_aout;
+    Event ev_auto[2];                      // retention + evaluation of a call: start, end
+    double auto_ms = 0.0;                  // ... their time in the last call (sfa_session_auto_ms)
 };
 
 namespace {
@@ -132,6 +142,11 @@ void reset_raw_slot(sfa_session *s, int32_t sl) {
     s->raw_mean[sl] = s->raw_sd[sl] = 0.0f;
     s->raw_window[sl] = 0;
     s->raw_fresh[sl] = 1;
+    if (s->auto_max > 0) {
+        s->auto_h[sl] = sfa::EvAutoSlot{-1, -1, 0, sfa::kAutoPending};
+        s->auto_k[sl] = 0;
+        s->auto_final[sl] = 0;
+    }
 }
 
 }  // namespace
@@ -576,6 +591,68 @@ int sfa_session_raw_config(sfa_session_t *s, int32_t skip_events, int32_t norm_e
     s->recal_flags = 0;
     s->raw_scaling.assign(3 * ns, 0.0);
     s->raw_fresh.assign(ns, 1);
+    s->auto_max = s->auto_every = 0;  // (the automatic start was checked against the sizes that go)
+    return SFA_OK;
+}
+
+int64_t sfa_session_auto_bytes(int32_t n_slots, int32_t max_samples) {
+    if (n_slots <= 0 || max_samples <= 0 || max_samples > sfa::kAutoMaxSamples) return SFA_EINVAL;
+    // retention (int16), the slot's state, and the prefix sums of a call in which every slot has a pending point
+    const int64_t per_slot = 2 * static_cast<int64_t>(max_samples) + static_cast<int64_t>(sizeof(sfa::EvAutoSlot)) + 4 * (static_cast<int64_t>(max_samples) + 1);
+    if (per_slot > INT64_MAX / n_slots) return SFA_ERANGE;
+    return per_slot * n_slots;
+}
+
+int sfa_session_raw_auto_start(sfa_session_t *s, int32_t every_samples, int32_t max_samples, uint32_t flags) {
+    if (!s) return fail(SFA_EINVAL, "sfa_session_raw_auto_start: null session");
+    if (!s->raw) return fail(SFA_EINVAL, "sfa_session_raw_auto_start: the session is not in raw mode (sfa_session_raw_config)");
+    if (flags) return fail(SFA_EINVAL, "sfa_session_raw_auto_start: unknown flag bits 0x%x", flags);
+    if (every_samples < 0 || max_samples < 0 || max_samples > sfa::kAutoMaxSamples)
+        return fail(SFA_EINVAL, "sfa_session_raw_auto_start: need every_samples >= 0 and 0 <= max_samples <= %d, not %d and %d", sfa::kAutoMaxSamples, every_samples,
+                    max_samples);
+    for (int32_t sl = 0; sl < s->n_slots; ++sl)
+        if (s->len[sl] != 0 || s->poison[sl] || !s->raw_fresh[sl])
+            return fail(SFA_EINVAL, "sfa_session_raw_auto_start: slot %d is not empty; the rule changes only while every slot is (sfa_session_reset)", sl);
+    if (max_samples == 0) {  // off
+        s->auto_max = s->auto_every = 0;
+        return SFA_OK;
+    }
+    sfa_ctx *c = s->c;
+    // the reference's own conditions of -p -1 (src/dtw_main.c:263-276), and the one kind of session that context can have
+    if (!(c->flag & SFA_RNA)) return fail(SFA_EINVAL, "sfa_session_raw_auto_start: DNA does not support auto query start detection (the context has no SFA_RNA)");
+    if (c->flag & SFA_INV) return fail(SFA_EINVAL, "sfa_session_raw_auto_start: inversion (SFA_INV) is not compatible with auto query start detection");
+    if (c->flag & SFA_END) return fail(SFA_EINVAL, "sfa_session_raw_auto_start: mapping from query end (SFA_END) is not compatible with auto query start detection");
+    if (!s->resweep) return fail(SFA_EINVAL, "sfa_session_raw_auto_start: the session was not created with SFA_SESSION_RESWEEP");
+    if (s->skip < sfa::kAutoFallback)
+        return fail(SFA_EINVAL, "sfa_session_raw_auto_start: skip_events of sfa_session_raw_config is the largest skip a slot may resolve and must hold the fallback: need >= %d, not %d",
+                    sfa::kAutoFallback, s->skip);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t ns = static_cast<size_t>(s->n_slots);
+    if (int rc = reserve_all(s->d_auto, sizeof(sfa::EvAutoSlot) * ns, s->d_keep, 2 * static_cast<size_t>(max_samples) * ns)) return rc;
+    for (Event &e : s->ev_auto)
+        if (!e.h && hipEventCreate(&e.h) != hipSuccess) return fail(SFA_ENODEV, "hipEventCreate failed");
+    s->auto_every = every_samples;
+    s->auto_max = max_samples;
+    s->auto_ms = 0.0;
+    s->auto_h.assign(ns, sfa::EvAutoSlot{-1, -1, 0, sfa::kAutoPending});
+    s->auto_k.assign(ns, 0);
+    s->auto_final.assign(ns, 0);
+    return SFA_OK;
+}
+
+double sfa_session_auto_ms(sfa_session_t *s) { return (s && s->auto_max > 0) ? s->auto_ms : -1.0; }
+
+int sfa_session_auto_start(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_session_auto_t *out) {
+    if (!s || n < 0 || (n > 0 && (!slot || !out))) return fail(SFA_EINVAL, "sfa_session_auto_start: bad argument");
+    if (s->auto_max == 0) return fail(SFA_EINVAL, "sfa_session_auto_start: the session has no automatic query start (sfa_session_raw_auto_start)");
+    for (int32_t i = 0; i < n; ++i) {
+        if (slot[i] < 0 || slot[i] >= s->n_slots) return fail(SFA_EINVAL, "sfa_session_auto_start: slot %d out of range (the session has %d)", slot[i], s->n_slots);
+        const sfa::EvAutoSlot &a = s->auto_h[slot[i]];
+        out[i].target = a.target;
+        out[i].frozen_at = a.frozen_at;
+        out[i].skip = a.skip;
+        out[i].status = a.status;
+    }
     return SFA_OK;
 }
 
@@ -620,15 +697,18 @@ int sfa_session_query_span(sfa_session_t *s, const int32_t *slot, int32_t n, uin
     sfa_ctx *c = s->c;
     HIP_TRY(hipSetDevice(c->device));
     const size_t nn = static_cast<size_t>(n);
-    if (int rc = reserve_all(s->h_span_in, 8 * nn, s->d_span_in, 8 * nn, s->d_span, 16 * nn, s->h_span, 16 * nn)) return rc;
+    const bool per_slot = s->auto_max > 0;
+    const size_t in_bytes = (per_slot ? 12 : 8) * nn;  // (the third table, the slots' own skips, only with the automatic start)
+    if (int rc = reserve_all(s->h_span_in, in_bytes, s->d_span_in, in_bytes, s->d_span, 16 * nn, s->h_span, 16 * nn)) return rc;
     int32_t *h = s->h_span_in.as<int32_t>();
     for (int32_t i = 0; i < n; ++i) {  // (a slot reset since its last chunk has a stale table and no query)
         const int32_t sl = slot[i];
         h[i] = sl;
         h[nn + i] = (!s->raw_fresh[sl] && (s->raw_status[sl] & sfa::kRawCalibrated)) ? static_cast<int32_t>(s->len[sl]) : 0;
+        if (per_slot) h[2 * nn + i] = std::max(s->auto_h[sl].skip, 0);  // (a calibrated slot has resolved its skip)
     }
     hipStream_t st = c->stream;
-    HIP_TRY(hipMemcpyAsync(s->d_span_in.p, h, 8 * nn, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->d_span_in.p, h, in_bytes, hipMemcpyHostToDevice, st));
     sfa::EvSpanArgs a;
     a.slot = s->d_span_in.as<int32_t>();
     a.q_events = a.slot + nn;
@@ -638,7 +718,11 @@ int sfa_session_query_span(sfa_session_t *s, const int32_t *slot, int32_t n, uin
     a.ev_cap = s->skip + s->query;
     a.skip = s->skip;
     a.query_cap = s->query;
-    hipLaunchKernelGGL(sfa::ev_query_span_kernel, dim3((n + 63) / 64), dim3(64), 0, st, a);
+    a.skips = per_slot ? a.slot + 2 * nn : nullptr;
+    if (per_slot)
+        hipLaunchKernelGGL(sfa::ev_query_span_kernel<true>, dim3((n + 63) / 64), dim3(64), 0, st, a);
+    else
+        hipLaunchKernelGGL(sfa::ev_query_span_kernel<false>, dim3((n + 63) / 64), dim3(64), 0, st, a);
     KERNEL_TRY();
     HIP_TRY(hipMemcpyAsync(s->h_span.p, s->d_span.p, 16 * nn, hipMemcpyDeviceToHost, st));
     if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "sfa_session_query_span: the gather failed: %s", hipGetErrorString(hipGetLastError()));
@@ -689,7 +773,10 @@ int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t 
 
     // entry tables: [raw_off re-based (n + 1) x i64 | slot n x i32 | flags n x i32 | scale 2n x f32]
     const size_t nn = static_cast<size_t>(n);
-    const size_t o_off = 0, o_slot = align8(8 * (nn + 1)), o_flag = o_slot + align8(4 * nn), o_scale = o_flag + align8(4 * nn), bytes = o_scale + 8 * nn;
+    const bool auto_on = s->auto_max > 0;
+    const size_t o_off = 0, o_slot = align8(8 * (nn + 1)), o_flag = o_slot + align8(4 * nn), o_scale = o_flag + align8(4 * nn);
+    // (automatic query start: | have n x i32 | EvAutoEntry n)
+    const size_t o_have = o_scale + 8 * nn, o_aent = o_have + align8(4 * nn), bytes = auto_on ? o_aent + sizeof(sfa::EvAutoEntry) * nn : o_have;
     if (int rc = reserve_all(s->h_rstage, bytes, s->d_rstage, bytes, s->d_raw, 2 * static_cast<size_t>(std::max<int64_t>(total, 1)), s->d_rout, sizeof(sfa::EvStreamOut) * nn,
                              s->h_rout, sizeof(sfa::EvStreamOut) * nn, s->d_bad, nn, s->h_bad, nn + 8))
         return rc;
@@ -701,6 +788,37 @@ int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t 
         reinterpret_cast<int32_t *>(h + o_flag)[i] = (s->raw_fresh[slot[i]] ? sfa::kEntryFresh : 0) | ((end_of_read && end_of_read[i]) ? sfa::kEntryEnd : 0);
     }
     memcpy(h + o_scale, scale.data(), 8 * nn);
+    // automatic query start: the points this call carries every slot past (each slot's count of samples decides, not the calls)
+    int32_t n_aent = 0;
+    std::vector<int32_t> auto_k_after;
+    std::vector<uint8_t> auto_final_now;
+    if (auto_on) {
+        auto_k_after.assign(nn, 0);
+        auto_final_now.assign(nn, 0);
+        sfa::EvAutoEntry *ent = reinterpret_cast<sfa::EvAutoEntry *>(h + o_aent);
+        const int64_t M = s->auto_max;
+        for (int32_t i = 0; i < n; ++i) {
+            const int32_t sl = slot[i];
+            const int64_t have = s->raw_n[sl], after = have + (raw_off[i + 1] - raw_off[i]);
+            reinterpret_cast<int32_t *>(h + o_have)[i] = static_cast<int32_t>(have);
+            auto_k_after[i] = s->auto_k[sl];
+            if (s->auto_h[sl].target >= 0 || s->auto_final[sl]) continue;  // frozen, or given up: later points are not evaluated
+            const int32_t k_hi = s->auto_every > 0 ? static_cast<int32_t>(std::min(after, M) / s->auto_every) : 0;
+            const bool ended_now = end_of_read && end_of_read[i] && !(s->raw_status[sl] & sfa::kRawEnded);
+            const bool final_now = ended_now || (after >= M && have < M);
+            sfa::EvAutoEntry e;
+            e.entry = i;
+            e.n0 = (s->auto_k[sl] + 1) * s->auto_every;
+            e.n_periodic = k_hi - s->auto_k[sl];
+            e.n_final = final_now ? static_cast<int32_t>(std::min(after, M)) : -1;
+            auto_k_after[i] = k_hi;
+            auto_final_now[i] = final_now ? 1 : 0;
+            if (e.n_periodic > 0 || final_now) ent[n_aent++] = e;
+        }
+        if (int rc = reserve_all(s->d_csum, 4 * (static_cast<size_t>(M) + 1) * static_cast<size_t>(std::max(n_aent, 1)), s->d_aout, sizeof(sfa::EvAutoSlot) * nn, s->h_aout,
+                                 sizeof(sfa::EvAutoSlot) * nn))
+            return rc;
+    }
     HIP_TRY(hipMemcpyAsync(s->d_rstage.p, h, bytes, hipMemcpyHostToDevice, st));
     if (total > 0) HIP_TRY(hipMemcpyAsync(s->d_raw.p, raw + raw_off[0], 2 * static_cast<size_t>(total), hipMemcpyHostToDevice, st));
 
@@ -742,7 +860,45 @@ int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t 
     for (int32_t k = 0; k < sfa::kRecalMaxPoints; ++k) na.at[k] = k < s->recal_n ? s->recal_at[k] : 0;
     na.resweep = s->resweep ? 1 : 0;
     na.reversed = (s->resweep && (c->flag & SFA_RNA) && !(c->flag & SFA_INV)) ? 1 : 0;
-    hipLaunchKernelGGL(sfa::ev_stream_norm_kernel, dim3(n), dim3(64), 0, st, na);
+    sfa::EvNormAutoArgs nx{nullptr, nullptr};
+    if (auto_on) {
+        sfa::EvAutoAppendArgs ap;
+        ap.raw = ea.raw;
+        ap.raw_off = ea.raw_off;
+        ap.slot = ea.slot;
+        ap.e_flags = ea.e_flags;
+        ap.have = reinterpret_cast<const int32_t *>(d + o_have);
+        ap.keep = s->d_keep.as<int16_t>();
+        ap.state = s->d_auto.as<sfa::EvAutoSlot>();
+        ap.n = n;
+        ap.max_samples = s->auto_max;
+        HIP_TRY(hipEventRecord(s->ev_auto[0], st));
+        hipLaunchKernelGGL(sfa::ev_auto_append_kernel, dim3(n), dim3(256), 0, st, ap);
+        KERNEL_TRY();
+        if (n_aent > 0) {  // slots without a pending point cost nothing
+            sfa::EvAutoEvalArgs va;
+            va.entries = reinterpret_cast<const sfa::EvAutoEntry *>(d + o_aent);
+            va.slot = ea.slot;
+            va.scale = ea.scale;
+            va.keep = ap.keep;
+            va.csum = s->d_csum.as<int32_t>();
+            va.state = ap.state;
+            va.n_entries = n_aent;
+            va.max_samples = s->auto_max;
+            va.every = s->auto_every;
+            va.lo = c->pore == 2 ? 500 : 2000;  // JNNV2_RNA_RNA004_ADAPTOR / JNNV2_RNA_R9_ADAPTOR, as sfa_align_raw
+            va.std_scale = c->pore == 2 ? 0.7f : 0.5f;
+            hipLaunchKernelGGL(sfa::ev_auto_eval_kernel, dim3(n_aent), dim3(64), 0, st, va);
+            KERNEL_TRY();
+        }
+        HIP_TRY(hipEventRecord(s->ev_auto[1], st));
+        nx.state = ap.state;
+        nx.out = s->d_aout.as<sfa::EvAutoSlot>();
+        hipLaunchKernelGGL(sfa::ev_stream_norm_kernel<true>, dim3(n), dim3(64), 0, st, na, nx);
+        HIP_TRY(hipMemcpyAsync(s->h_aout.p, s->d_aout.p, sizeof(sfa::EvAutoSlot) * nn, hipMemcpyDeviceToHost, st));
+    } else {
+        hipLaunchKernelGGL(sfa::ev_stream_norm_kernel<false>, dim3(n), dim3(64), 0, st, na, nx);
+    }
     KERNEL_TRY();
     HIP_TRY(hipEventRecord(s->ev_raw[2], st));
     // the counts of new events are all that comes back: the planner of the sweep is host code
@@ -761,6 +917,11 @@ int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t 
         s->raw_mean[sl] = ro[i].mean;
         s->raw_sd[sl] = ro[i].sd;
         s->raw_window[sl] = ro[i].window;
+        if (auto_on) {
+            s->auto_h[sl] = s->h_aout.as<sfa::EvAutoSlot>()[i];
+            s->auto_k[sl] = auto_k_after[i];
+            s->auto_final[sl] |= auto_final_now[i];
+        }
         // a recalibrated slot: its whole query was rewritten, so it is swept as a first chunk, which reads no carried row and
         // writes a new one (the planner never puts first and carried chunks into one wave).  A resweep session knows no other
         // sweep: q_new is the window then, and 0 in every call that leaves the window as it is
@@ -770,6 +931,11 @@ int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t 
     float t_ev = 0, t_norm = 0;
     HIP_TRY(hipEventElapsedTime(&t_ev, s->ev_raw[0], s->ev_raw[1]));
     HIP_TRY(hipEventElapsedTime(&t_norm, s->ev_raw[1], s->ev_raw[2]));
+    if (auto_on) {
+        float t_auto = 0;
+        HIP_TRY(hipEventElapsedTime(&t_auto, s->ev_auto[0], s->ev_auto[1]));
+        s->auto_ms = t_auto;
+    }
     if (int rc = sweep_chunks(s, slot, ch.data(), n, nullptr, 0, s->d_query.as<float>(), out)) return rc;
     c->prof.events_ms = t_ev;
     c->prof.normalise_ms = t_norm;

@@ -15,6 +15,11 @@ ticks, the same calls, the same lines.  The schedule counts ticks, never seconds
   candidates --candidates N: the session keeps N candidates per slot (Session.configure_candidates); those of all channels
             decided in a tick are fetched in one Session.candidates call before the reset, and a channel's valid ones follow its
             primary line, best first (format_candidates)
+  auto start skip = -1 (-p -1, with resweep on an RNA aligner without INV): the session finds each read's query start behind the
+            adaptor and the poly-A tail as it streams (Session.configure_auto_start: a point every auto_start_every samples, the
+            final point at the end of the read or at auto_start_max_samples); max_skip_events is the largest skip.  Schedule and
+            rule are unchanged: a channel with no skip yet is simply not calibrated.  A decision carries the channel's automatic
+            start, and its line two more tags, qs:i:<skip> as:A:<P|E|F> (found at a mid-read point, at the final point, fallback)
   after it  decided channels are reset in one call and take the next unread reads, lowest channel first, from tick t + 1 on
 """
 import numpy as np
@@ -103,8 +108,11 @@ def recal_points(norm, query, recalibrate=(), at_end=False):
     return at
 
 
+AUTO_START_MAX_SAMPLES, MAX_SKIP_EVENTS = 131072, 4096  # the defaults of --auto-start-max-samples and --max-skip-events
+
+
 def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False, resweep=False,
-           candidates=0):
+           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS):
     """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
     candidates=1..4 (--candidates): an eighth element, RESULT_DTYPE[4], the channel's candidates at the decision, best first.
     A `session` of the caller's is taken as it is, in this as in its raw mode: it must keep that many candidates already
@@ -117,7 +125,13 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     recalibrate / at_end: --recalibrate (a list of window lengths, or "double": api.recal_double(norm, query)) and
     --recalibrate-at-end, turned into the session's points by recal_points(); schedule and decision rule are the same with them.
     resweep: --resweep, the session is aligner.session(channels, resweep=True); info["q_events"], which the rule and the line read,
-    is then the slot's window."""
+    is then the slot's window.
+    skip = -1 (-p -1): the automatic query start; needs resweep.  auto_start_every (None: chunk_samples; 0: the final point only),
+    auto_start_max_samples and max_skip_events configure it on a session of replay's own; every item then ends with one more
+    element, the channel's SESSION_AUTO_DTYPE record at the decision, which format_line takes as auto=."""
+    auto = skip < 0
+    if auto and not resweep:
+        raise api.SfaError("replay: skip = -1 (automatic query start) needs resweep=True on an RNA aligner without INV")
     reads = iter(reads)
     on = [None] * channels  # (index, read_id, meta, samples) per channel
 
@@ -141,7 +155,9 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
         if own:
             if candidates:
                 se.configure_candidates(candidates)
-            se.configure_raw(skip, norm, query, recal_points(norm, query, recalibrate, at_end), at_end)
+            se.configure_raw(max_skip_events if auto else skip, norm, query, recal_points(norm, query, recalibrate, at_end), at_end)
+            if auto:
+                se.configure_auto_start(chunk_samples if auto_start_every is None else auto_start_every, auto_start_max_samples)
         if candidates and not own:
             se.candidates([])  # (raises unless the caller's session keeps candidates)
         sch.start(src)
@@ -159,9 +175,12 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                 d_slots = [slots[i] for i in decided]
                 a, b = se.query_span(d_slots)
                 cand = se.candidates(d_slots) if candidates else None
+                au = se.auto_start(d_slots) if auto else None
                 for k, i in enumerate(decided):
                     item = (sch.tick, slots[i], on[slots[i]][0], rows[i].copy(), info[i].copy(), (int(a[k]), int(b[k])), reason[i])
-                    yield item + (cand[k].copy(),) if candidates else item
+                    if candidates:
+                        item += (cand[k].copy(),)
+                    yield item + (au[k].copy(),) if auto else item
                 se.reset(d_slots)
             sch.end_tick(reason, line, src)
     finally:
@@ -169,14 +188,22 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
             se.close()
 
 
-def format_line(read_id, n_samples, names, seq_lengths, row, info, span, reason):
+def auto_tags(auto):
+    """qs:i:<skip> as:A:<P|E|F> for a SESSION_AUTO_DTYPE record: found at a mid-read point, found at the final point, fallback"""
+    st = int(auto["status"])
+    how = "F" if (st & 15) != api.AUTO_RESOLVED else ("E" if st & api.AUTO_AT_FINAL else "P")
+    return f"\tqs:i:{int(auto['skip'])}\tas:A:{how}"
+
+
+def format_line(read_id, n_samples, names, seq_lengths, row, info, span, reason, auto=None):
     """The line `sigfish-amd realtime` prints for a decision, or "" when its row is not mapped: paf_row (query_size as dtw passes
-    it, last query event - first), then ne:i:<query events> ns:i:<samples sent> dc:A:<reason>.  n_samples: of the whole read."""
+    it, last query event - first), then ne:i:<query events> ns:i:<samples sent> dc:A:<reason>.  n_samples: of the whole read.
+    auto: the decision's automatic start (replay with skip = -1): qs:i and as:A follow the three tags."""
     if not mapped(row):
         return ""
     rid = int(row["rid"])
     base = api.paf_row(row, read_id, names[rid], span[0], span[1], int(info["q_events"]) - 1, int(n_samples), int(seq_lengths[rid]))
-    return f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}\n"
+    return f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}{'' if auto is None else auto_tags(auto)}\n"
 
 
 def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, span, reason):
