@@ -31,19 +31,11 @@
 #pragma once
 
 #include "sdtw_strips.hpp"
+#include "session_plan.hpp"  // SessionClass, kSessionMaxClasses: the class table is the host planner's
 
 namespace sfa {
 
 constexpr int kSessionPad = 256;       // words in front of and behind the carried rows of a session (over-run of the block loads)
-constexpr int kSessionMaxClasses = 12;  // (first chunk or not) x the six base shapes
-
-struct SessionClass {
-    int32_t R, lanes;     // kClassShapes[...]
-    int32_t first;        // 1: first chunks (constant boundary), 0: below a carried row
-    int32_t group_base;   // first group (a group is one wave's worth of slots: 64 / lanes of them)
-    int32_t n_groups;
-    int32_t task_base;    // first task; the class has n_groups * n_jobs of them, job-major
-};
 
 // Everything a launch reads.  "Entry" k: a slot's piece of this launch (a chunk of up to 2048 events, or a piece of a longer one).
 struct SessionArgs {

@@ -7,6 +7,7 @@
 //   sfa_align.hip    the alignment stage: planner -> launches (wave kernels, row strips) -> rows; the batch entry points
 //   sfa_maps.hip     event maps of the last call's rows (sdtw_path.hpp)
 //   sfa_session.hip  alignment sessions: a slot's sweep extended chunk by chunk below its carried row (sdtw_session.hpp)
+//                    -- its state one struct per feature (namespace sess), its host rules in session_plan.hpp (pure C++, as sfa_plan.hpp)
 //   sfa_pre.hip      the stages in front of it on the device: raw samples / BLOW5 records in (events_kernels.hpp, blow5_kernels.hpp)
 // There is NO CPU fallback: every failure is reported through the return code + sfa_last_error().
 #pragma once

@@ -2,7 +2,9 @@
 
 target(N) is the library's host twin api.auto_start_target on the slot's first N samples; the events are the host stream's
 (api.EventStream).  Everything else -- the points, freezing, the skip, the fallback, the cap -- is restated here from the
-samples a slot has received: feed() takes the chunks of a schedule, but every decision is a function of sample counts."""
+samples a slot has received: feed() takes the chunks of a schedule, but every decision is a function of sample counts.
+points_between() is the twin of auto_points (sigfish_amd/csrc/session_plan.hpp), the rule the library schedules a call's points
+with; test_session_plan_cpu.py compares the two."""
 import numpy as np
 
 import sigfish_amd as S

@@ -1,7 +1,8 @@
 """Which waves a session call runs (helpers of test_session_waves_cpu.py / test_session_waves_gpu.py; no test, no fixture).
 
 plan_call() restates the grouping rule of the session sweep in Python -- class_for (sfa_plan.hpp), the launch split at 2048
-events (sweep_chunks) and the sort key and wave filling of plan_launch (sfa_session.hip) -- so that a test can say which
+events (plan_session_call) and the sort key and wave filling of plan_launch (both in sigfish_amd/csrc/session_plan.hpp, the pure
+header sfa_session.hip plans with; test_session_plan_cpu.py compares that C++ with plan_call) -- so that a test can say which
 (class shape, first chunk or carried row, occupancy, g0) combinations a schedule reaches, and what the planner's task and
 launch counts must be.  build_matrix() is a schedule of ONE call that reaches all of them; test_session_waves_cpu.py asserts
 that it does, and that the hand-written SCHED of test_session_gpu.py does not.
@@ -63,7 +64,7 @@ class Group:
 
 
 def plan_launch(pieces):
-    """-> [Group] in task order (plan_launch of sfa_session.hip)."""
+    """-> [Group] in task order (plan_launch of session_plan.hpp)."""
     def key(p):
         ci = class_for(p.len)
         return (-p.first, ci, p.len % SHAPES[ci][0], -p.len, p.call)
