@@ -349,11 +349,12 @@ __global__ void __launch_bounds__(64) blow5_inflate_kernel(const InflateArgs a, 
 }
 
 // Primary fields of a record (slow5.c:2806-2925): u16 id_len, id, u32 read_group, f64 digitisation, offset, range,
-// sampling_rate, u64 len, signal.  One lane per record; `head` gets a fixed-size row for the host:
-//   [0] i32 status (0 ok, -1 malformed)  [4] i32 id_len  [8] i64 n_samples  [16] f64 x3 digitisation, offset, range
-//   [40] i64 signal offset inside the payload  [48] i64 signal bytes  [56..] the read id (up to kBlow5IdMax bytes)
+// sampling_rate, u64 len, signal.  One lane per record; `head` gets a fixed-size row for the host, its fields at kHead*:
+//   i32 status (0 ok, -1 malformed), i32 id_len, i64 n_samples, f64 x3 digitisation, offset, range,
+//   i64 signal offset inside the payload, i64 signal bytes, the read id (up to kBlow5IdMax bytes)
 constexpr int kBlow5HeadBytes = 192;
-constexpr int kBlow5IdMax = kBlow5HeadBytes - 56;
+constexpr int kHeadStatus = 0, kHeadIdLen = 4, kHeadSamples = 8, kHeadScaling = 16, kHeadSigOff = 40, kHeadSigBytes = 48, kHeadId = 56;
+constexpr int kBlow5IdMax = kBlow5HeadBytes - kHeadId;
 struct FieldsArgs {
     const uint8_t *payload;      // inflated payloads (or the records themselves when they are not compressed)
     const int64_t *payload_off;  // [n+1] slots
@@ -380,7 +381,7 @@ __global__ void __launch_bounds__(64) blow5_fields_kernel(const FieldsArgs a) {
         if (id_len > kBlow5IdMax || len < fixed) {
             status = -1;
         } else {
-            for (int k = 0; k < id_len; ++k) h[56 + k] = p[2 + k];
+            for (int k = 0; k < id_len; ++k) h[kHeadId + k] = p[2 + k];
             const uint8_t *q = p + 2 + id_len + 4;
             __builtin_memcpy(&f[0], q, 8);
             __builtin_memcpy(&f[1], q + 8, 8);
@@ -406,12 +407,12 @@ __global__ void __launch_bounds__(64) blow5_fields_kernel(const FieldsArgs a) {
             }
         }
     }
-    __builtin_memcpy(h, &status, 4);
-    __builtin_memcpy(h + 4, &id_len, 4);
-    __builtin_memcpy(h + 8, &n_samples, 8);
-    __builtin_memcpy(h + 16, f, 24);
-    __builtin_memcpy(h + 40, &sig_off, 8);
-    __builtin_memcpy(h + 48, &sig_bytes, 8);
+    __builtin_memcpy(h + kHeadStatus, &status, 4);
+    __builtin_memcpy(h + kHeadIdLen, &id_len, 4);
+    __builtin_memcpy(h + kHeadSamples, &n_samples, 8);
+    __builtin_memcpy(h + kHeadScaling, f, 24);
+    __builtin_memcpy(h + kHeadSigOff, &sig_off, 8);
+    __builtin_memcpy(h + kHeadSigBytes, &sig_bytes, 8);
 }
 
 // svb-zd -> int16 samples (slow5_press.c:1085-1135: StreamVByte with 1-4 byte values, zig-zag, delta against the previous
@@ -445,10 +446,10 @@ __global__ void __launch_bounds__(256) blow5_svb_kernel(const SvbArgs a) {
     const uint8_t *h = a.head + static_cast<int64_t>(i) * kBlow5HeadBytes;
     int32_t status;
     int64_t n_samples, sig_off, sig_bytes;
-    __builtin_memcpy(&status, h, 4);
-    __builtin_memcpy(&n_samples, h + 8, 8);
-    __builtin_memcpy(&sig_off, h + 40, 8);
-    __builtin_memcpy(&sig_bytes, h + 48, 8);
+    __builtin_memcpy(&status, h + kHeadStatus, 4);
+    __builtin_memcpy(&n_samples, h + kHeadSamples, 8);
+    __builtin_memcpy(&sig_off, h + kHeadSigOff, 8);
+    __builtin_memcpy(&sig_bytes, h + kHeadSigBytes, 8);
     if (status != 0) return;
     int16_t *out = a.raw + a.raw_off[i];
     const uint8_t *sig = a.payload + a.payload_off[i] + sig_off;

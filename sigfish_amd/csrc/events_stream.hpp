@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pre_rules.hpp"  // kAutoFallback, the reference's fallback skip
 #include "recal_rule.hpp"
 
 namespace sfa {
@@ -284,7 +285,6 @@ struct EvStreamOut {
 // status of a slot's automatic start: the low nibble is the state, kAutoAtFinal says the target was frozen (or given up) at
 // the slot's final point (sfa_session_auto_t.status)
 constexpr int kAutoPending = 0, kAutoResolved = 1, kAutoNoTarget = 2, kAutoNoEvent = 3, kAutoBeyondMax = 4, kAutoAtFinal = 16;
-constexpr int kAutoFallback = 50;                 // the reference's fallback skip, src/sigfish.c:438-446
 constexpr int32_t kAutoMaxSamples = 1 << 20;      // 1200 x 2^20 < 2^31: the prefix sums of a slot fit 32 bits
 
 struct EvAutoSlot {   // per slot, device memory; sfa_session_auto_t is made of it

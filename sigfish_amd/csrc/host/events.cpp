@@ -2,6 +2,9 @@
 // for x86-64 (no FMA contraction, float expressions evaluated in float, FLT_EVAL_METHOD 0).
 #include "events.hpp"
 
+#include "../jnn_consts.hpp"
+#include "../pre_rules.hpp"
+
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -10,20 +13,11 @@
 namespace sfa {
 
 void raw_to_picoamps(const int16_t *raw, int64_t n, double digitisation, double offset, double range, float *out) {
-    const float rangef = static_cast<float>(range), digf = static_cast<float>(digitisation), offf = static_cast<float>(offset);
-    const float unit = rangef / digf;
-    for (int64_t i = 0; i < n; ++i) out[i] = (static_cast<float>(raw[i]) + offf) * unit;
+    const RawScale sc = raw_scale(digitisation, offset, range);
+    for (int64_t i = 0; i < n; ++i) out[i] = (static_cast<float>(raw[i]) + sc.offset) * sc.unit;
 }
 
 namespace {
-
-struct DetectorParam {
-    size_t w1, w2;
-    float thr1, thr2, peak_height;
-};
-// src/events.c:47-58
-const DetectorParam kDna = {3, 6, 1.4f, 9.0f, 0.2f};
-const DetectorParam kRna = {7, 14, 2.5f, 9.0f, 1.0f};
 
 // windowed two-sample t statistic from prefix sums, src/events.c:319-368
 std::vector<float> tstat(const std::vector<double> &sum, const std::vector<double> &sumsq, size_t n, size_t w) {
@@ -120,7 +114,8 @@ std::vector<sfa_event_t> detect_events(const float *pa, int64_t n_, bool rna) {
     std::vector<sfa_event_t> out;
     if (n_ <= 0) return out;
     const size_t n = static_cast<size_t>(n_);
-    const DetectorParam &p = rna ? kRna : kDna;
+    const DetectorParams p = detector_params(rna);
+    const size_t w1 = static_cast<size_t>(p.w1), w2 = static_cast<size_t>(p.w2);
     // prefix sums in double; the square is a FLOAT product promoted afterwards (src/events.c:297-307)
     std::vector<double> sum(n + 1), sumsq(n + 1);
     sum[0] = 0.0;
@@ -129,8 +124,8 @@ std::vector<sfa_event_t> detect_events(const float *pa, int64_t n_, bool rna) {
         sum[i + 1] = sum[i] + static_cast<double>(pa[i]);
         sumsq[i + 1] = sumsq[i] + static_cast<double>(pa[i] * pa[i]);
     }
-    const std::vector<float> t1 = tstat(sum, sumsq, n, p.w1), t2 = tstat(sum, sumsq, n, p.w2);
-    Detector sd{t1.data(), p.thr1, p.w1}, ld{t2.data(), p.thr2, p.w2};
+    const std::vector<float> t1 = tstat(sum, sumsq, n, w1), t2 = tstat(sum, sumsq, n, w2);
+    Detector sd{t1.data(), p.thr1, w1}, ld{t2.data(), p.thr2, w2};
     std::vector<size_t> peaks = pick_peaks(sd, ld, n, p.peak_height);
     // create_events(), src/events.c:479-508: peaks equal to 0 or >= n do not open an event
     std::vector<size_t> cuts;
@@ -149,16 +144,16 @@ std::vector<sfa_event_t> detect_events(const float *pa, int64_t n_, bool rna) {
 // the detector as a stream (events.hpp); every expression is the one of tstat / pick_peaks / make_event above
 // ---------------------------------------------------------------------------------------------------------
 EventStream::EventStream(double digitisation, double offset, double range, bool rna) {
-    const DetectorParam &p = rna ? kRna : kDna;
-    w1_ = static_cast<int>(p.w1);
-    w2_ = static_cast<int>(p.w2);
+    const DetectorParams p = detector_params(rna);
+    w1_ = p.w1;
+    w2_ = p.w2;
     ring_ = 2 * w2_ + 1;
     thr1_ = p.thr1;
     thr2_ = p.thr2;
     peak_height_ = p.peak_height;
-    const float rangef = static_cast<float>(range), digf = static_cast<float>(digitisation);  // raw_to_picoamps()
-    offf_ = static_cast<float>(offset);
-    unit_ = rangef / digf;
+    const RawScale sc = raw_scale(digitisation, offset, range);  // raw_to_picoamps()
+    offf_ = sc.offset;
+    unit_ = sc.unit;
     for (int i = 0; i < kRing; ++i) st_.ring_s[i] = st_.ring_q[i] = 0.0;  // (sum[0] = sumsq[0] = 0)
 }
 
@@ -312,8 +307,8 @@ float stdv_f(const float *x, int n) {  // stat.h:36-44
 
 // jnnv2(), src/jnn.c:100-180: first low-mean stretch of plausible length in a rolling mean = the adaptor
 Seg find_adaptor(const int16_t *raw, int64_t n, int pore) {
-    const float std_scale = pore == 2 ? 0.7f : 0.5f;     // JNNV2_RNA_RNA004_ADAPTOR / JNNV2_RNA_R9_ADAPTOR
-    const int seg_dist = 1500, window = 2000, hi = 200000, lo = pore == 2 ? 500 : 2000;
+    const float std_scale = adaptor_params(pore).std_scale;
+    const int seg_dist = kAdSegDist, window = kAdWindow, hi = kAdHi, lo = adaptor_params(pore).lo;
     if (n <= window) return Seg{-1, -1};
     std::vector<float> cur(n);
     for (int64_t i = 0; i < n; ++i) cur[i] = clamp_outlier(static_cast<float>(raw[i]));
@@ -362,7 +357,7 @@ Seg find_adaptor(const int16_t *raw, int64_t n, int pore) {
 // jnn_core() with JNNV1_R9_POLYA / JNNV1_RNA004_POLYA (identical), src/jnn.c:191-279: first stretch that stays
 // inside (bot, top) for >= window samples, tolerating `error` excursions
 Seg find_polya(const float *pa, int64_t n, float top, float bot) {
-    const int corrector = 50, seg_dist = 200, window = 250, error = 30;
+    const int corrector = kPaCorrector, seg_dist = kPaSegDist, window = kPaWindow, error = kPaError;
     const float stall_len = 1.0f;
     std::vector<Seg> segs;
     bool prev = false;
@@ -422,44 +417,13 @@ int64_t detect_query_start(const int16_t *raw, int64_t n, const float *pa, const
 
 bool select_and_normalise(std::vector<sfa_event_t> &ev, const int16_t *raw, int64_t nraw, const float *pa, int32_t prefix_size,
                           int32_t query_size, uint32_t flag, int pore, int64_t *qstart, int64_t *qend, int *status) {
-    const int64_t n = static_cast<int64_t>(ev.size());
-    int64_t st, en;
-    *status = 0;
-    bool keep = true;
-    if (!(flag & SFA_END)) {  // src/sigfish.c:435-463
-        st = prefix_size;
-        if (prefix_size < 0) {
-            st = detect_query_start(raw, nraw, pa, ev, pore);
-            if (st < 0) {
-                *status |= 4;
-                st = 50;
-            }
-        }
-        en = st + query_size;
-        if (st + 25 > n) {
-            st = en = 0;
-            keep = false;
-            *status |= 2;
-        } else if (en > n) {
-            en = n;
-            *status |= 1;
-        }
-    } else {  // src/sigfish.c:464-478
-        st = n - prefix_size - query_size;
-        en = n - prefix_size;
-        if (st < 0) {
-            st = 0;
-            *status |= 1;
-        }
-        if (en < 0) {
-            en = 0;
-            keep = false;
-            *status |= 2;
-        }
-    }
-    *qstart = st;
-    *qend = en;
-    if (!keep) return false;
+    // (a caller only comes here with events, and events imply samples: sfa_select_query takes no raw signal with a fixed prefix)
+    const bool from_end = (flag & SFA_END) != 0, auto_start = prefix_size < 0 && !from_end;
+    const int64_t auto_event = auto_start ? detect_query_start(raw, nraw, pa, ev, pore) : -1;
+    const QueryWindow w = query_window(static_cast<int64_t>(ev.size()), 1, prefix_size, query_size, from_end, auto_start, auto_event);
+    const int64_t st = *qstart = w.start, en = *qend = w.end;
+    *status = w.status;
+    if (!w.keep) return false;
     // z-normalise event[st..en).mean in place (src/sigfish.c:483-502), sequential fp32
     const float cnt = static_cast<float>(en - st);
     float mean = 0.0f, var = 0.0f;

@@ -163,6 +163,11 @@ class ShardWorker {
 
 }  // namespace
 
+namespace sfa {
+struct EvArgs;    // events_kernels.hpp: argument blocks of the event detection and of the automatic query start, which
+struct AutoArgs;  // ctx::RawSignal fills from its buffers (defined in sfa_pre.hip, the one unit that launches those kernels)
+}  // namespace sfa
+
 // ---- the context's state, one struct per stage that owns it: its buffers, what it keeps between calls, and reserve(), the one
 // place that says how large each buffer has to be.  Every buffer frees itself with the context. ----
 namespace ctx {
@@ -270,6 +275,8 @@ struct RawSignal {  // sfa_align_raw: samples, prefix sums, t-statistics, events
     DevBuf e_raw, e_rawoff, e_scale, e_sum, e_sumsq, e_t1, e_t2, e_evoff, e_evstart, e_evlen, e_evmean, e_evstdv, e_nev, e_qstart,
         e_qoff, e_b0, e_b1, e_b2, e_flag, e_qev, e_pflag;
     bool eev_pending = false;
+    sfa::EvArgs detector_args(int32_t n) const;  // every buffer of the detection; the caller adds parameters and routes
+    sfa::AutoArgs auto_args(int32_t n) const;    // the automatic start reuses e_sumsq / e_t1 and writes behind the counts in e_nev
     int reserve_samples(int64_t total, size_t n) { return reserve_all(e_raw, 2 * static_cast<size_t>(std::max<int64_t>(total, 1)), e_rawoff, 8 * (n + 1)); }
     int reserve(int64_t total, size_t n, size_t ev_total) {
         const size_t t1 = static_cast<size_t>(std::max<int64_t>(total, 1));

@@ -393,11 +393,10 @@ int raw_check(sfa_session *s, const int32_t *slot, const int16_t *raw, const int
         const double *sc = scaling + 3 * static_cast<size_t>(i);
         if (!r.slots[sl].fresh && memcmp(sc, r.slots[sl].scaling, 3 * sizeof(double)) != 0)
             return fail(SFA_EINVAL, "sfa_session_extend_raw: slot %d: digitisation, offset and range are fixed by a slot's first chunk after a reset", sl);
-        const float dig = static_cast<float>(sc[0]), range = static_cast<float>(sc[2]);  // event_single(), src/sigfish.c:343
-        float *out = &r.scale[2 * static_cast<size_t>(i)];
-        out[0] = static_cast<float>(sc[1]);
-        out[1] = range / dig;
-        if (!std::isfinite(out[0]) || !std::isfinite(out[1])) return fail(SFA_EINVAL, "sfa_session_extend_raw: slot %d: the scaling is not finite", sl);
+        const sfa::RawScale rs = sfa::raw_scale(sc[0], sc[1], sc[2]);
+        r.scale[2 * static_cast<size_t>(i)] = rs.offset;
+        r.scale[2 * static_cast<size_t>(i) + 1] = rs.unit;
+        if (!std::isfinite(rs.offset) || !std::isfinite(rs.unit)) return fail(SFA_EINVAL, "sfa_session_extend_raw: slot %d: the scaling is not finite", sl);
     }
     const int64_t total = raw_off[n] - raw_off[0];
     if (total > INT32_MAX / 2) return fail(SFA_ERANGE, "sfa_session_extend_raw: more than 2^30 samples in one call");
@@ -452,18 +451,15 @@ int raw_launch_detector(sfa_session *s, const int16_t *raw, const int64_t *raw_o
     const int64_t total = raw_off[n] - raw_off[0];
     HIP_TRY(hipMemcpyAsync(r.d_rstage.p, r.h_rstage.p, r.staged, hipMemcpyHostToDevice, st));
     if (total > 0) HIP_TRY(hipMemcpyAsync(r.d_raw.p, raw + raw_off[0], 2 * static_cast<size_t>(total), hipMemcpyHostToDevice, st));
-    const bool rna = (s->c->flag & SFA_RNA) != 0;  // detector parameters, src/events.c:47-58
+    const sfa::DetectorParams dp = sfa::detector_params((s->c->flag & SFA_RNA) != 0);
     sfa::EvStreamArgs &ea = r.ea;
     ea.raw = r.d_raw.as<int16_t>();
     ea.state = r.d_state.as<sfa::EvStreamSlot>();
     ea.events = r.d_evtab.as<sfa::EvRecord>();
     ea.n = n;
     ea.ev_cap = r.ev_cap();
-    ea.w1 = rna ? 7 : 3;
-    ea.w2 = rna ? 14 : 6;
-    ea.thr1 = rna ? 2.5f : 1.4f;
-    ea.thr2 = 9.0f;
-    ea.peak_height = rna ? 1.0f : 0.2f;
+    ea.w1 = dp.w1, ea.w2 = dp.w2;
+    ea.thr1 = dp.thr1, ea.thr2 = dp.thr2, ea.peak_height = dp.peak_height;
     HIP_TRY(hipEventRecord(r.ev_raw[0], st));
     hipLaunchKernelGGL(sfa::ev_stream_kernel, dim3((n + 63) / 64), dim3(64), 0, st, ea);
     KERNEL_TRY();
@@ -502,8 +498,8 @@ int raw_launch_auto(sfa_session *s, int32_t n) {
         va.n_entries = au.n_pending;
         va.max_samples = au.max_samples;
         va.every = au.every;
-        va.lo = s->c->pore == 2 ? 500 : 2000;  // JNNV2_RNA_RNA004_ADAPTOR / JNNV2_RNA_R9_ADAPTOR, as sfa_align_raw
-        va.std_scale = s->c->pore == 2 ? 0.7f : 0.5f;
+        va.lo = sfa::adaptor_params(s->c->pore).lo;
+        va.std_scale = sfa::adaptor_params(s->c->pore).std_scale;
         hipLaunchKernelGGL(sfa::ev_auto_eval_kernel, dim3(au.n_pending), dim3(64), 0, st, va);
         KERNEL_TRY();
     }

@@ -163,3 +163,53 @@ def test_parallel_peak_picker_and_its_fallback():
     for k in (0, 1, 2, 3, 64, 69):
         meta = dict(digitisation=scs[k][0], offset=scs[k][1], range=scs[k][2])
         assert info_par["n_events"][k] == len(S.detect_events(raws[k], meta, False))
+
+
+# (fixture read, samples kept) -> events the host detector finds (checked with S.detect_events on the CPU): the edges of the window
+# rule for prefix 50, query 250 -- from the front 75 events keep a read and 300 fill the window, from the end 50 and 300
+WINDOW_EDGE_CUTS = [(0, 285, 49), (1, 355, 74), (2, 326, 75), (2, 0, 0), (3, 785, 150), (4, 1578, 299), (0, 1556, 300), (1, 1470, 301)]
+
+
+@pytest.mark.parametrize("flag", [0, S.END], ids=["front", "from_end"])
+def test_query_windows_at_the_edges_of_the_rule(flag):
+    """Eight reads whose event counts sit on the edges of normalise_single's window rule, one of them without samples: windows
+    as oracle.query_window gives them for the host's event counts, status bits by the rule stated here, and the rows of the
+    kept reads equal to align_db on the host route's queries."""
+    from oracle import oracle as O
+
+    c = load_case("dna_default")
+    ref = S.RefModel.from_fasta(c["fasta"], c["levels"], c["k"], flag, c["query_size"])
+    ids, raw, off, scal = _load_raw(c["blow5"])
+    prefix, query = 50, 250
+    raws = [raw[off[i]:off[i] + cut] for i, cut, _ in WINDOW_EDGE_CUTS]
+    scs = np.array([scal[i] for i, _, _ in WINDOW_EDGE_CUTS])
+    off2 = np.concatenate([[0], np.cumsum([len(r) for r in raws])]).astype(np.int64)
+    queries, q_off, kept = [], [0], []
+    for k, ((i, cut, n_events), r) in enumerate(zip(WINDOW_EDGE_CUTS, raws)):
+        meta = dict(digitisation=scs[k][0], offset=scs[k][1], range=scs[k][2])
+        ev = S.detect_events(r, meta, False) if len(r) else np.zeros(0, S.EVENT_DTYPE)
+        assert len(ev) == n_events, (k, len(ev))
+        keep, a, b = S.select_query(ev, r, meta, prefix, query, flag, 0) if len(ev) else (False, 0, 0)
+        kept.append(keep)
+        if keep:
+            queries.append(ev["mean"][a:b])
+        q_off.append(q_off[-1] + (b - a if keep else 0))
+    with S.Aligner(ref, flag) as al:
+        rows, info = al.align_raw(np.concatenate(raws), off2, scs, prefix, query)
+        want = al.align_db(np.concatenate(queries), np.array(q_off, np.int64))
+    for k, (_, _, n) in enumerate(WINDOW_EDGE_CUTS):
+        o_keep, o_start, o_end = O.query_window(n, prefix, query, flag)
+        keep = bool(o_keep) and n > 0  # (a read without events reports nothing)
+        assert (info["n_events"][k], info["qstart"][k], info["qend"][k]) == (n, o_start, o_end), k
+        assert keep == kept[k] == bool(rows["valid"][k]), k
+        if n == 0:
+            want_status = 0
+        elif not flag:  # dropped: not kept although it has events and samples; short: kept with fewer than `query` events
+            want_status = (0 if keep else 2) | (1 if keep and o_end - o_start < query else 0)
+        else:
+            want_status = (1 if n - prefix - query < 0 else 0) | (2 if n - prefix < 0 else 0)
+        assert info["status"][k] == want_status, (k, info["status"][k], want_status)
+    assert [k for k in range(8) if kept[k]] == ([2, 4, 5, 6, 7] if not flag else [1, 2, 4, 5, 6, 7])  # (both sides of every edge are here)
+    assert np.array_equal(rows["valid"], want["valid"])
+    m = np.array(kept)
+    assert rows[m].tobytes() == want[m].tobytes()
