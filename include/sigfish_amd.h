@@ -270,6 +270,40 @@ void sfa_session_destroy(sfa_session_t *s);
  * SFA_SESSION_RESWEEP changes nothing: the carried rows are still needed (a window beyond SFA_MAX_QUERY events runs as pieces). */
 int64_t sfa_session_bytes(int64_t total_columns, int32_t n_slots, uint32_t session_flags);
 
+/* ---- event maps of a slot's row: the warp path of the real-time path -------------------------------------------------------
+ * sfa_session_event_maps is sfa_event_maps for rows a SESSION returned: the reference-column -> query-event map
+ * (aln_t.r2qevent_map, the ss string of a SAM record) of every row, from the device, with nothing uploaded again.  rows[k] is a
+ * row the session returned for slot slot_of_row[k] in the slot's CURRENT state: the primary of its last sfa_session_extend /
+ * sfa_session_extend_raw (or of an empty chunk), or one of the four rows of sfa_session_candidates; one slot may be named any
+ * number of times in a call.  map_off, pairs, the layout of a map (pos_end - pos_st + 1 pairs) and *n_on_host are exactly
+ * sfa_event_maps's: rows with valid = 0 or rid < 0 write nothing (the rows of an empty or poisoned slot are such rows), a row for
+ * which sfa_r2qevent_map returns SFA_EINVAL is left unwritten, a gap too small for a valid row is SFA_ERANGE.
+ * The query of row k is the slot's query as swept, events [0, q_events): in raw mode the slot's normalised query where it lies in
+ * device memory (on a resweep session the W events of the window as stored -- already reversed for SFA_RNA without SFA_INV); in
+ * event mode the events the session kept (sfa_session_keep_events).  The band comes from the row, the flip and offset undone as
+ * for sfa_event_maps; the same fill and walk kernels run it, in slices that follow "map_scratch_bytes".  A slot with more than
+ * SFA_MAX_QUERY query events, or a row whose own moves exceed the budget, takes the host routine inside the call (that slot's
+ * query is copied back; there is no device route beyond SFA_MAX_QUERY events) and counts in *n_on_host.
+ * Blocking, on the context's stream.  The scratch is the session's own: sfa_event_maps keeps referring to the last BATCH call and
+ * returns the same bytes whether or not a session call came in between, and the reverse.
+ * SFA_EINVAL: a SFA_SESSION_NO_START session (no start column, no band); an event-mode session that keeps no events, or a slot
+ * that has outgrown max_events; a slot out of range; a valid row for a slot that is empty or poisoned; a row whose contig or
+ * strand does not exist or whose band leaves its array. */
+int sfa_session_event_maps(sfa_session_t *s, const sfa_result_t *rows, const int32_t *slot_of_row, int32_t n_rows,
+                           const int64_t *map_off, int32_t *pairs, int32_t *n_on_host);
+
+/* An event-mode session does not keep the caller's events.  With max_events > 0 every sfa_session_extend call also appends its
+ * chunks to a per-slot copy in device memory (one more kernel in front of the sweep, no further copy or wait), the query
+ * sfa_session_event_maps reads.  A slot that receives more than max_events events keeps sweeping and returning rows as before;
+ * only its maps are refused (SFA_EINVAL) until it is reset.  0 switches it off: the session launches the kernels it launched
+ * before.  Allowed while every slot is empty; SFA_EINVAL otherwise, and on a raw-mode or resweep session, whose query is kept
+ * already (sfa_session_raw_config switches it off).  It is no session flag. */
+int sfa_session_keep_events(sfa_session_t *s, int32_t max_events);
+
+/* Device memory sfa_session_keep_events takes: n_slots x max_events x 4 bytes (one flag byte per slot counts as bookkeeping).
+ * Host arithmetic; negative (an SFA_E* code) for arguments that are not positive or a product beyond 2^63. */
+int64_t sfa_session_keep_bytes(int32_t n_slots, int32_t max_events);
+
 /* ---- raw-signal sessions: a slot's samples in, its row out ----------------------------------------------------------------
  * A real-time caller has raw ADC samples per channel, a few hundred to a few thousand at a time, not normalised events.  In raw
  * mode a session runs the stages in front of the sweep on the device as well, and carries their state per slot:

@@ -68,7 +68,8 @@ SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "
            "sfa_event_stream_create", "sfa_event_stream_push", "sfa_event_stream_finish", "sfa_event_stream_destroy",
            "sfa_session_raw_config", "sfa_session_extend_raw", "sfa_session_events", "sfa_session_raw_bytes", "sfa_session_query_span", "sfa_session_row",
            "sfa_session_raw_recalibrate", "sfa_session_candidates_config", "sfa_session_candidates",
-           "sfa_session_raw_auto_start", "sfa_session_auto_start", "sfa_session_auto_bytes", "sfa_auto_start_target", "sfa_session_auto_ms"]
+           "sfa_session_raw_auto_start", "sfa_session_auto_start", "sfa_session_auto_bytes", "sfa_auto_start_target", "sfa_session_auto_ms",
+           "sfa_session_event_maps", "sfa_session_keep_events", "sfa_session_keep_bytes"]
 
 _lib = None
 
@@ -190,5 +191,9 @@ def load():
     L.sfa_auto_start_target.restype = C.c_int64
     L.sfa_session_auto_ms.argtypes = [vp]
     L.sfa_session_auto_ms.restype = C.c_double
+    L.sfa_session_event_maps.argtypes = [vp, vp, i32p, C.c_int32, i64p, i32p, i32p]
+    L.sfa_session_keep_events.argtypes = [vp, C.c_int32]
+    L.sfa_session_keep_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.sfa_session_keep_bytes.restype = C.c_int64
     _lib = L
     return L

@@ -271,15 +271,22 @@ class Aligner:
                "sfa_align_events")
         return out
 
-    def session(self, n_slots, starts=True, resweep=False, flags=None, candidates=0, auto_start=None):
+    def session(self, n_slots, starts=True, resweep=False, flags=None, candidates=0, auto_start=None, keep_events=0):
         """An alignment session of n_slots growing reads on this aligner (sfa_session_create); starts=False carries costs only
         (SFA_SESSION_NO_START: half the memory, the coordinate on the start side of every row is -1).  resweep=True
         (SFA_SESSION_RESWEEP): a raw-mode-only session that sweeps a slot only when its normalisation window changes, over the
         window's events -- the one kind of session an RNA aligner without INV can have (its query is the events reversed).
         flags: the raw flag word in place of starts / resweep.  candidates=1..4: configure_candidates() on the new session.
         auto_start=dict(skip=, norm=, query=, every=, max_samples=[, recalibrate=, at_end=]): configure_raw() with skip as the
-        largest skip, then configure_auto_start(every, max_samples), on the new session."""
+        largest skip, then configure_auto_start(every, max_samples), on the new session.  keep_events=N: keep_events(N) on the
+        new (event-mode) session, so that event_maps() has the slots' events."""
         s = Session(self, n_slots, starts, resweep, flags)
+        if keep_events:
+            try:
+                s.keep_events(keep_events)
+            except Exception:
+                s.close()
+                raise
         if auto_start is not None:
             try:
                 a = dict(auto_start)
@@ -485,6 +492,34 @@ class Session:
                                           eo.ctypes.data_as(_lib.i64p), n, out.ctypes.data_as(C.c_void_p)), "sfa_session_extend")
         return out
 
+    def keep_events(self, max_events):
+        """Event mode: keep up to max_events events per slot in device memory (sfa_session_keep_events), the query event_maps()
+        reads; n_slots x max_events x 4 bytes (session_keep_bytes).  A slot that outgrows it keeps its rows and loses its maps
+        until it is reset.  0 switches it off.  Only while every slot is empty; a raw-mode session keeps its query already."""
+        self._live()
+        _check(self._L.sfa_session_keep_events(self._h, int(max_events)), "sfa_session_keep_events")
+
+    def event_maps(self, rows, slots):
+        """aln_t.r2qevent_map of rows this session returned, computed on the device from the slots' resident queries
+        (sfa_session_event_maps): rows[k] is a row of slot slots[k] in its current state -- the primary of the last extend() /
+        extend_raw(), or a row of candidates(); a slot may be named several times.  -> (pairs int32 [total, 2], map_off int64
+        [len(rows) + 1], n_on_host): the map of row k is pairs[map_off[k]:map_off[k + 1]], start and stop per reference column as
+        r2qevent_map returns them; rows without a row (valid = 0) have an empty slice; a row the library wrote nothing for (no
+        complete map) keeps INT32_MIN.  n_on_host: rows computed by the host routine inside the call (a slot beyond 2048 query
+        events, or moves beyond the "map_scratch_bytes" budget)."""
+        self._live()
+        rows = np.ascontiguousarray(rows, RESULT_DTYPE).reshape(-1)
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = len(rows)
+        if len(sl) != n:
+            raise SfaError("event_maps: slots must name one slot per row")
+        off = map_offsets(rows)
+        pairs = np.full((max(int(off[-1]), 1), 2), np.iinfo(np.int32).min, np.int32)
+        on_host = C.c_int32(0)
+        _check(self._L.sfa_session_event_maps(self._h, rows.ctypes.data_as(C.c_void_p), sl.ctypes.data_as(_lib.i32p), n, off.ctypes.data_as(_lib.i64p),
+                                              pairs.ctypes.data_as(_lib.i32p), C.byref(on_host)), "sfa_session_event_maps")
+        return pairs[:int(off[-1])], off, int(on_host.value)
+
     def configure_candidates(self, n):
         """Keep the n = 1..4 candidates behind every slot's row (sfa_session_candidates_config): the secondaries of the batch path,
         for all events a slot has received, however many.  0 switches them off.  Only while every slot is empty."""
@@ -650,6 +685,24 @@ def session_bytes(total_columns, n_slots, starts=True, resweep=False):
     b = int(_lib.load().sfa_session_bytes(int(total_columns), int(n_slots), _session_flags(starts, resweep)))
     if b < 0:
         raise SfaError(f"sfa_session_bytes failed ({b}): total_columns and n_slots must be positive")
+    return b
+
+
+def map_offsets(rows):
+    """The map_off of rows for event_maps: int64 [len(rows) + 1], pos_end - pos_st + 1 pairs for every mapped row, none otherwise."""
+    rows = np.ascontiguousarray(rows, RESULT_DTYPE).reshape(-1)
+    ok = (rows["valid"] != 0) & (rows["rid"] >= 0)
+    size = np.maximum(np.where(ok, rows["pos_end"].astype(np.int64) - rows["pos_st"] + 1, 0), 0)
+    off = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum(size, out=off[1:])
+    return off
+
+
+def session_keep_bytes(n_slots, max_events):
+    """Device memory Session.keep_events takes (sfa_session_keep_bytes; host arithmetic): n_slots x max_events x 4 bytes."""
+    b = int(_lib.load().sfa_session_keep_bytes(int(n_slots), int(max_events)))
+    if b < 0:
+        raise SfaError(f"sfa_session_keep_bytes failed ({b}): n_slots and max_events must be positive, their product x 4 below 2^63")
     return b
 
 

@@ -326,7 +326,36 @@ struct SessionCandArgs {
     int32_t track;             // as SessionRowsArgs
 };
 
+// sfa_session_keep_events: an event-mode session that keeps its slots' events for sfa_session_event_maps
+struct SessionKeepArgs {
+    const float *events;      // the call's events as staged for the sweep, concatenated
+    const int64_t *ch_off;    // [n + 1] first event of every entry of the call
+    const int32_t *slot;      // [n] slot of the session
+    const int32_t *have;      // [n] events the slot held before the call
+    float *keep;              // [n_slots][max_events] the slots' events since their last reset
+    uint8_t *over;            // [n_slots] 1: the slot has received more than max_events events (its kept events are the first max_events)
+    int32_t n, max_events;
+};
+
 #ifdef SFA_DEFINE_SESSION_KERNELS  // plain kernels: defined in exactly one translation unit (sfa_session.hip)
+// Appends every entry's events to its slot's kept events, d_keep[slot][have, have + len), clipped at max_events; a slot's first
+// chunk after a reset clears its overflow flag, a clipped one sets it.  One block per entry; consecutive lanes copy
+// consecutive words.  The host has checked the slots' range and names a slot once per call.
+__global__ void __launch_bounds__(256) sdtw_session_keep_kernel(const SessionKeepArgs a) {
+    const int i = blockIdx.x;
+    if (i >= a.n) return;
+    const int64_t off = a.ch_off[i];
+    const int64_t len = a.ch_off[i + 1] - off;
+    const int have = a.have[i];
+    const int64_t slot = a.slot[i];
+    const int64_t room = have < a.max_events ? a.max_events - have : 0;
+    const int take = static_cast<int>(len < room ? len : room);
+    const float *src = a.events + off;
+    float *dst = a.keep + slot * a.max_events + have;
+    for (int j = threadIdx.x; j < take; j += 256) dst[j] = src[j];
+    if (threadIdx.x == 0 && (have == 0 || len > room)) a.over[slot] = len > room ? 1 : 0;
+}
+
 // the jobs' partial top-2 of every slot of the call merged in processing order (a later job wins ties), then contig, strand,
 // mapq, flip and offset (src/sigfish.c:969-983): what sdtw_finalize_kernel does for a batch
 __global__ void __launch_bounds__(64) sdtw_session_rows_kernel(const SessionRowsArgs a) {

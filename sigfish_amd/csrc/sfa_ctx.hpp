@@ -5,7 +5,7 @@
 // names none of them.
 //   sfa_context.hip  contexts: init / destroy, devices, options, profile, small utilities
 //   sfa_align.hip    the alignment stage: planner -> launches (wave kernels, row strips) -> rows; the batch entry points
-//   sfa_maps.hip     event maps of the last call's rows (sdtw_path.hpp)
+//   sfa_maps.hip     event maps of the last call's rows, and the core sfa_session_event_maps shares with it (sdtw_path.hpp)
 //   sfa_session.hip  alignment sessions: a slot's sweep extended chunk by chunk below its carried row (sdtw_session.hpp)
 //                    -- its state one struct per feature (namespace sess), its host rules in session_plan.hpp (pure C++, as sfa_plan.hpp)
 //   sfa_pre.hip      the stages in front of it on the device: raw samples / BLOW5 records in (events_kernels.hpp, blow5_kernels.hpp)
@@ -303,17 +303,23 @@ struct Blow5 {  // sfa_align_blow5: record bytes, inflated payloads, field rows
     }
 };
 
-// sfa_event_maps: what the last align call left behind -- its read count (-1: none), the offsets of its queries and where they
-// are (the context's d_queries, or the caller's memory after sfa_align_batch_device); a group context keeps the count
-struct EventMaps {
-    int32_t map_n = -1;
-    std::vector<int64_t> map_q_off;
-    const float *map_queries = nullptr;
-    DevBuf d_mv, d_prow, d_pairs, d_pfirst;  // packed moves of a slice, its row descriptors, its maps, where every walk ended
+// The scratch of one event-maps call (sdtw_path.hpp): packed moves of a slice of rows, its row descriptors (the query offsets
+// behind them), its maps, where every walk ended.  A context has one for sfa_event_maps, every session its own for
+// sfa_session_event_maps: neither call disturbs the other's.
+struct MapScratch {
+    DevBuf d_mv, d_prow, d_pairs, d_pfirst;
     PinBuf h_pairs;
     int reserve(size_t mv_bytes, size_t prow_bytes, size_t n_rows, size_t out_pairs) {
         return reserve_all(d_mv, mv_bytes, d_prow, prow_bytes, d_pairs, 8 * out_pairs, d_pfirst, 4 * n_rows, h_pairs, 8 * out_pairs + 4 * n_rows);
     }
+};
+
+// sfa_event_maps: what the last align call left behind -- its read count (-1: none), the offsets of its queries and where they
+// are (the context's d_queries, or the caller's memory after sfa_align_batch_device); a group context keeps the count
+struct EventMaps : MapScratch {
+    int32_t map_n = -1;
+    std::vector<int64_t> map_q_off;
+    const float *map_queries = nullptr;
 };
 
 struct TaskTimes {  // -DSFA_TASK_TIMES builds
@@ -393,6 +399,20 @@ int resolve_profile(sfa_ctx *c);  // sfa_align.hip: timers + error words of the 
 // core of every align entry point: queries already in HBM, results left in HBM (sfa_align.hip)
 int align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, int32_t n, struct ResultRow *d_out,
                  struct ResultRow *d_sec = nullptr);  // d_sec: rows of the secondaries (nullptr: the context's d_sec, when the option is on)
+// ---- the core of both event-maps entry points (sfa_maps.hip) ----
+struct MapRow {  // one row of a call, as the core takes it
+    int32_t k = 0;                                             // the caller's number of the row: its map goes to pairs + 2 * map_off[k]
+    int32_t query = -1, job = 0, col_st = 0, m = 0, qlen = 0;  // m = 0: nothing to write for this row
+};
+// The band of row k in columns of its strand's own array: the flip and offset of src/sigfish.c:971-975 undone.  qlen: events of
+// the query the row aligns; gap: the pairs map_off leaves for it.  SFA_EINVAL for a row that is not one of this reference (what:
+// ends the message, "a row of ..."), SFA_ERANGE for a gap too small
+int map_row_band(const sfa_ctx *c, const sfa_result_t &r, int32_t k, int64_t qlen, int64_t gap, const char *who, const char *what, MapRow *b);
+// Maps of band[0..n) on the context's device and stream, into the caller's pairs.  The query of a row lies at d_queries +
+// q_off[row.query], row.qlen events in DP order (reversed: in event order, the DP takes them back to front); q_off[n_q_off] is
+// host memory.  Scratch: sc.  Rows beyond SFA_MAX_QUERY events or the "map_scratch_bytes" budget take the host routine.
+int event_maps_core(sfa_ctx *c, ctx::MapScratch &sc, const float *d_queries, const int64_t *q_off, size_t n_q_off, bool reversed, const MapRow *band, int32_t n,
+                    const int64_t *map_off, int32_t *pairs, int32_t *n_on_host);
 // contiguous read range of shard r: [r*n/G, (r+1)*n/G)
 inline void shard_ranges(int32_t n, size_t g, std::vector<int32_t> *lo) {
     lo->resize(g + 1);

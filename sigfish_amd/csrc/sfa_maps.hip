@@ -1,5 +1,6 @@
 // sfa_maps.hip -- sfa_event_maps: the reference-column -> query-event maps (aln_t.r2qevent_map) of rows of the last align call,
-// a whole batch at a time on the device (sdtw_path.hpp).  Host work: band of every row in columns of its strand's array (the
+// a whole batch at a time on the device (sdtw_path.hpp); and the core it shares with sfa_session_event_maps (sfa_session.hip),
+// which takes a device query base, per-row query offsets and lengths, the rows' bands and the scratch of its caller.  Host work: band of every row in columns of its strand's array (the
 // flip and offset of src/sigfish.c:971-975 undone, as path_of_row does for the per-read host routine), slices of rows whose move
 // matrices fit the scratch budget (sfa_plan.hpp, plan_map_slices), one fill + one walk launch per rows-per-lane class of a
 // slice, maps back through page-locked memory.  Rows the device does not take -- queries beyond SFA_MAX_QUERY, a move matrix
@@ -39,51 +40,35 @@ void launch_path_fill(int ci, const PathArgs &pa, hipStream_t st) {
     }
 }
 
-struct RowBand {
-    int32_t read = -1, job = 0, col_st = 0, m = 0, qlen = 0;  // m = 0: nothing to write for this row
-};
+}  // namespace
 
-// maps of the rows idx[0..n_idx) (caller's numbering; nullptr: 0..n_idx-1) on one device; reads are numbered from read_base
-int event_maps_one(sfa_ctx *c, const sfa_result_t *rows, const int32_t *read_of_row, const int32_t *idx, int32_t n_idx, int32_t read_base,
-                   const int64_t *map_off, int32_t *pairs, int32_t *n_on_host) {
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int rc = sfa::resolve_profile(c)) return rc;
-    if (c->maps.map_n < 0) return fail(SFA_EINVAL, "sfa_event_maps: no align call has completed on this context");
-    if (c->maps.map_n > 0 && c->maps.map_queries != c->io.d_queries.as<float>())
-        return fail(SFA_EINVAL, "sfa_event_maps: the last call was sfa_align_batch_device, whose queries are the caller's; the context kept none");
+namespace sfa {
+
+int map_row_band(const sfa_ctx *c, const sfa_result_t &r, int32_t k, int64_t ql, int64_t gap, const char *who, const char *what, MapRow *b) {
     const int strands = (c->flag & SFA_RNA) ? 1 : 2;
+    if (r.rid >= c->model.num_ref || (r.strand != '+' && r.strand != '-') || (strands == 1 && r.strand != '+'))
+        return fail(SFA_EINVAL, "%s: row %d (contig %d, strand %d) is not a row of this reference", who, k, r.rid, (int)r.strand);
+    b->k = k;
+    b->job = r.rid * strands + (r.strand == '+' ? 0 : 1);
+    const int32_t rlen = c->model.h_job_len[b->job], off = c->model.h_ref_off[r.rid];
+    const bool plus = r.strand == '+';
+    const int64_t st = plus ? static_cast<int64_t>(r.pos_st) - off : static_cast<int64_t>(rlen) - (static_cast<int64_t>(r.pos_end) - off);
+    const int64_t en = plus ? static_cast<int64_t>(r.pos_end) - off : static_cast<int64_t>(rlen) - (static_cast<int64_t>(r.pos_st) - off);
+    if (st < 0 || en < st || en >= rlen || ql <= 0)
+        return fail(SFA_EINVAL, "%s: row %d (columns %d..%d of contig %d, %lld events) is not a row of %s", who, k, r.pos_st, r.pos_end, r.rid, (long long)ql, what);
+    const int64_t need = en - st + 1;
+    if (gap < need) return fail(SFA_ERANGE, "%s: row %d needs %lld pairs, map_off leaves %lld", who, k, (long long)need, (long long)gap);
+    b->col_st = static_cast<int32_t>(st);
+    b->m = static_cast<int32_t>(need);
+    b->qlen = static_cast<int32_t>(std::min<int64_t>(ql, INT32_MAX));
+    return SFA_OK;
+}
+
+int event_maps_core(sfa_ctx *c, ctx::MapScratch &sc, const float *d_queries, const int64_t *q_off, size_t n_q_off, bool reversed, const MapRow *band, int32_t n_idx,
+                    const int64_t *map_off, int32_t *pairs, int32_t *n_on_host) {
     const bool std_dtw = (c->flag & SFA_DTW) != 0;
-    const bool reversed = (c->flag & SFA_RNA) && !(c->flag & SFA_INV);  // src/sigfish.c:860-866
-    std::vector<RowBand> band(n_idx);
-    std::vector<int32_t> qlen(n_idx, 0), m(n_idx, 0);
-    for (int32_t t = 0; t < n_idx; ++t) {
-        const int32_t k = idx ? idx[t] : t;
-        const sfa_result_t &r = rows[k];
-        if (!r.valid || r.rid < 0) continue;  // unaligned: nothing is written
-        const int64_t read = static_cast<int64_t>(read_of_row ? read_of_row[k] : k) - read_base;
-        if (read < 0 || read >= c->maps.map_n) return fail(SFA_EINVAL, "sfa_event_maps: row %d names read %lld, the last call had %d", k, (long long)(read + read_base), c->maps.map_n);
-        if (r.rid >= c->model.num_ref || (r.strand != '+' && r.strand != '-') || (strands == 1 && r.strand != '+'))
-            return fail(SFA_EINVAL, "sfa_event_maps: row %d (contig %d, strand %d) is not a row of this reference", k, r.rid, (int)r.strand);
-        RowBand &b = band[t];
-        b.job = r.rid * strands + (r.strand == '+' ? 0 : 1);
-        const int32_t rlen = c->model.h_job_len[b.job], off = c->model.h_ref_off[r.rid];
-        const bool plus = r.strand == '+';
-        const int64_t st = plus ? static_cast<int64_t>(r.pos_st) - off : static_cast<int64_t>(rlen) - (static_cast<int64_t>(r.pos_end) - off);
-        const int64_t en = plus ? static_cast<int64_t>(r.pos_end) - off : static_cast<int64_t>(rlen) - (static_cast<int64_t>(r.pos_st) - off);
-        const int64_t ql = c->maps.map_q_off[read + 1] - c->maps.map_q_off[read];
-        if (st < 0 || en < st || en >= rlen || ql <= 0)
-            return fail(SFA_EINVAL, "sfa_event_maps: row %d (columns %d..%d of contig %d, read %lld of %lld events) is not a row of the last call", k,
-                        r.pos_st, r.pos_end, r.rid, (long long)(read + read_base), (long long)ql);
-        const int64_t need = en - st + 1;
-        if (map_off[k + 1] - map_off[k] < need)
-            return fail(SFA_ERANGE, "sfa_event_maps: row %d needs %lld pairs, map_off leaves %lld", k, (long long)need, (long long)(map_off[k + 1] - map_off[k]));
-        b.read = static_cast<int32_t>(read);
-        b.col_st = static_cast<int32_t>(st);
-        b.m = m[t] = static_cast<int32_t>(need);
-        b.qlen = static_cast<int32_t>(std::min<int64_t>(ql, INT32_MAX));
-        qlen[t] = b.qlen;
-    }
+    std::vector<int32_t> qlen(n_idx), m(n_idx);
+    for (int32_t t = 0; t < n_idx; ++t) qlen[t] = band[t].qlen, m[t] = band[t].m;
     const sfa::MapSlices ms = sfa::plan_map_slices(qlen.data(), m.data(), n_idx, c->opt_map_scratch);
     hipStream_t st = c->stream;
     // the query offsets of the call live in the staging area of its launches only; the walks need them again
@@ -100,12 +85,12 @@ int event_maps_one(sfa_ctx *c, const sfa_result_t *rows, const int32_t *read_of_
             cls_begin[ci] = static_cast<int32_t>(prow.size());
             for (int32_t o = lo; o < hi; ++o) {
                 const int32_t t = ms.order[o];
-                const RowBand &b = band[t];
+                const MapRow &b = band[t];
                 if (sfa::class_for(b.qlen) != ci) continue;
                 PathRow p{};
                 p.mv_off = ms.mv_off[o] / 4;
                 p.out_off = out_pairs;
-                p.read = b.read;
+                p.read = b.query;
                 p.job = b.job;
                 p.col_st = b.col_st;
                 p.m = b.m;
@@ -119,24 +104,24 @@ int event_maps_one(sfa_ctx *c, const sfa_result_t *rows, const int32_t *read_of_
         cls_begin[6] = static_cast<int32_t>(prow.size());
         const int32_t n = cls_begin[6];
         int rc;
-        const size_t qoff_bytes = sizeof(int64_t) * (static_cast<size_t>(c->maps.map_n) + 1);
-        if ((rc = c->maps.reserve(static_cast<size_t>(mv_bytes), sizeof(PathRow) * n + qoff_bytes + 8, static_cast<size_t>(n), static_cast<size_t>(out_pairs)))) return rc;
+        const size_t qoff_bytes = sizeof(int64_t) * n_q_off;
+        if ((rc = sc.reserve(static_cast<size_t>(mv_bytes), sizeof(PathRow) * n + qoff_bytes + 8, static_cast<size_t>(n), static_cast<size_t>(out_pairs)))) return rc;
         static_assert(sizeof(PathRow) % 8 == 0, "the query offsets follow the rows in one buffer");
-        int64_t *d_qoff = reinterpret_cast<int64_t *>(c->maps.d_prow.as<char>() + sizeof(PathRow) * n);
-        HIP_TRY(hipMemcpyAsync(c->maps.d_prow.p, prow.data(), sizeof(PathRow) * n, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_qoff, c->maps.map_q_off.data(), qoff_bytes, hipMemcpyHostToDevice, st));
+        int64_t *d_qoff = reinterpret_cast<int64_t *>(sc.d_prow.as<char>() + sizeof(PathRow) * n);
+        HIP_TRY(hipMemcpyAsync(sc.d_prow.p, prow.data(), sizeof(PathRow) * n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_qoff, q_off, qoff_bytes, hipMemcpyHostToDevice, st));
         for (int ci = 0; ci < 6; ++ci) {
             const int32_t nc = cls_begin[ci + 1] - cls_begin[ci];
             if (nc == 0) continue;
             PathArgs pa{};
-            pa.queries = c->maps.map_queries;
+            pa.queries = d_queries;
             pa.q_off = d_qoff;
             pa.ref = c->model.d_ref.as<float>();
             pa.job_off = c->model.d_job_off.as<int64_t>();
-            pa.rows = c->maps.d_prow.as<PathRow>() + cls_begin[ci];
-            pa.moves = c->maps.d_mv.as<uint32_t>();
-            pa.pairs = c->maps.d_pairs.as<int32_t>();
-            pa.first_col = c->maps.d_pfirst.as<int32_t>() + cls_begin[ci];
+            pa.rows = sc.d_prow.as<PathRow>() + cls_begin[ci];
+            pa.moves = sc.d_mv.as<uint32_t>();
+            pa.pairs = sc.d_pairs.as<int32_t>();
+            pa.first_col = sc.d_pfirst.as<int32_t>() + cls_begin[ci];
             pa.n_rows = nc;
             pa.rev_query = reversed ? 1 : 0;
             if (std_dtw)
@@ -149,28 +134,26 @@ int event_maps_one(sfa_ctx *c, const sfa_result_t *rows, const int32_t *read_of_
             hipLaunchKernelGGL(sfa::sdtw_path_walk_kernel, dim3((nc + 255) / 256), dim3(256), 0, st, pa, rshift, sh.lanes);
             KERNEL_TRY();
         }
-        int32_t *h_pairs = c->maps.h_pairs.as<int32_t>();
+        int32_t *h_pairs = sc.h_pairs.as<int32_t>();
         int32_t *h_first = h_pairs + 2 * out_pairs;
-        HIP_TRY(hipMemcpyAsync(h_pairs, c->maps.d_pairs.p, 8 * static_cast<size_t>(out_pairs), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_first, c->maps.d_pfirst.p, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_pairs, sc.d_pairs.p, 8 * static_cast<size_t>(out_pairs), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_first, sc.d_pfirst.p, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         for (int32_t i = 0; i < n; ++i) {
             // a walk that met query row 0 behind the row's first column has no complete map; like sfa_r2qevent_map, nothing is written
             if (h_first[i] != 0) continue;
-            const int32_t k = idx ? idx[t_of[i]] : t_of[i];
-            memcpy(pairs + 2 * map_off[k], h_pairs + 2 * prow[i].out_off, 8 * static_cast<size_t>(prow[i].m));
+            memcpy(pairs + 2 * map_off[band[t_of[i]].k], h_pairs + 2 * prow[i].out_off, 8 * static_cast<size_t>(prow[i].m));
         }
     }
     // rows left to the host routine: query and (contig,strand) array come back from the device
     std::map<int32_t, std::vector<float>> ref_of_job;
     std::vector<float> q, qdp;
     for (const int32_t t : ms.host_rows) {
-        const RowBand &b = band[t];
-        const int32_t k = idx ? idx[t] : t;
-        const int64_t ql = c->maps.map_q_off[b.read + 1] - c->maps.map_q_off[b.read];
+        const MapRow &b = band[t];
+        const int64_t ql = b.qlen;
         q.resize(static_cast<size_t>(ql));
         qdp.resize(static_cast<size_t>(ql));
-        HIP_TRY(hipMemcpy(q.data(), c->maps.map_queries + c->maps.map_q_off[b.read], sizeof(float) * static_cast<size_t>(ql), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(q.data(), d_queries + q_off[b.query], sizeof(float) * static_cast<size_t>(ql), hipMemcpyDeviceToHost));
         for (int64_t j = 0; j < ql; ++j) qdp[reversed ? ql - 1 - j : j] = q[j];
         std::vector<float> &y = ref_of_job[b.job];
         const int32_t rlen = c->model.h_job_len[b.job];
@@ -182,10 +165,41 @@ int event_maps_one(sfa_ctx *c, const sfa_result_t *rows, const int32_t *read_of_
         if (path.px.empty()) continue;
         const std::vector<int32_t> p = sfa::path_to_pairs(path);
         if (static_cast<int32_t>(p.size() / 2) != b.m) continue;  // (sfa_r2qevent_map: SFA_EINVAL, nothing written)
-        memcpy(pairs + 2 * map_off[k], p.data(), sizeof(int32_t) * p.size());
+        memcpy(pairs + 2 * map_off[b.k], p.data(), sizeof(int32_t) * p.size());
     }
     if (n_on_host) *n_on_host = static_cast<int32_t>(ms.host_rows.size());
     return SFA_OK;
+}
+
+}  // namespace sfa
+
+namespace {
+
+// sfa_event_maps on one device: what is about the context's last batch -- where its queries lie, the host copy of their offsets,
+// which read a row names -- in front of the core.  Rows idx[0..n_idx) (caller's numbering; nullptr: 0..n_idx-1); reads are
+// numbered from read_base
+int event_maps_one(sfa_ctx *c, const sfa_result_t *rows, const int32_t *read_of_row, const int32_t *idx, int32_t n_idx, int32_t read_base,
+                   const int64_t *map_off, int32_t *pairs, int32_t *n_on_host) {
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = sfa::resolve_profile(c)) return rc;
+    if (c->maps.map_n < 0) return fail(SFA_EINVAL, "sfa_event_maps: no align call has completed on this context");
+    if (c->maps.map_n > 0 && c->maps.map_queries != c->io.d_queries.as<float>())
+        return fail(SFA_EINVAL, "sfa_event_maps: the last call was sfa_align_batch_device, whose queries are the caller's; the context kept none");
+    const bool reversed = (c->flag & SFA_RNA) && !(c->flag & SFA_INV);  // src/sigfish.c:860-866
+    std::vector<sfa::MapRow> band(n_idx);
+    for (int32_t t = 0; t < n_idx; ++t) {
+        const int32_t k = idx ? idx[t] : t;
+        band[t].k = k;
+        const sfa_result_t &r = rows[k];
+        if (!r.valid || r.rid < 0) continue;  // unaligned: nothing is written
+        const int64_t read = static_cast<int64_t>(read_of_row ? read_of_row[k] : k) - read_base;
+        if (read < 0 || read >= c->maps.map_n) return fail(SFA_EINVAL, "sfa_event_maps: row %d names read %lld, the last call had %d", k, (long long)(read + read_base), c->maps.map_n);
+        if (int rc = sfa::map_row_band(c, r, k, c->maps.map_q_off[read + 1] - c->maps.map_q_off[read], map_off[k + 1] - map_off[k], "sfa_event_maps", "the last call", &band[t])) return rc;
+        band[t].query = static_cast<int32_t>(read);
+    }
+    return sfa::event_maps_core(c, c->maps, c->maps.map_queries, c->maps.map_q_off.data(), static_cast<size_t>(c->maps.map_n) + 1, reversed, band.data(), n_idx, map_off, pairs,
+                                n_on_host);
 }
 
 }  // namespace

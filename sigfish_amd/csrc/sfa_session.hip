@@ -7,6 +7,8 @@
 //   sess::Raw         raw mode (sfa_session_raw_config, events_stream.hpp): detector states, event tables, normalised queries, the
 //                     recalibration rule, the tables of a call -- samples go in, events and query stay on the device
 //   sess::AutoStart   sfa_session_raw_auto_start (events_auto_stream.hpp): retained samples, the slots' targets and skips
+//   sess::Keep        sfa_session_keep_events: the events of an event-mode session's slots, kept for their maps
+//   sess::Maps        sfa_session_event_maps: the scratch of a call (the core is sfa_maps.hip's), where every slot's query begins
 // The host rules -- which waves a call becomes, which points of the automatic start it passes -- are session_plan.hpp's.
 #include "sfa_ctx.hpp"
 #define SFA_DEFINE_SESSION_KERNELS  // (this unit holds the plain kernel of sdtw_session.hpp)
@@ -53,6 +55,7 @@ struct Sweep {  // of a call of the sweep
     std::vector<int32_t> call_slot;
     std::vector<sfa::SessionArgs> args;
     size_t staged = 0;
+    size_t keep_at = 0;  // where the keep kernel's tables lie in the staging (0: the call keeps nothing)
     Event ev[4];  // first kernel, sweeps start / end, rows written
     // the call's poison flags: the screen writes them, or the raw path's normalisation before the sweep (same n: nothing is dropped)
     int reserve_bad(size_t n) { return reserve_all(d_bad, n, h_bad, n + 8); }
@@ -142,6 +145,29 @@ struct AutoStart {  // automatic query start (sfa_session_raw_auto_start)
     void reset_slot(int32_t sl) { slots[sl] = Slot{}; }
 };
 
+struct Keep {  // sfa_session_keep_events (event mode)
+    int32_t max_events = 0;  // 0: off
+    DevBuf d_keep, d_over;   // [n_slots][max_events] float, [n_slots] u8: the slot outgrew max_events
+    PinBuf h_over;
+    bool on() const { return max_events > 0; }
+    static int64_t slot_bytes(int32_t max) { return 4 * static_cast<int64_t>(max); }
+    int reserve(int32_t n_slots, int32_t max) {
+        const size_t ns = static_cast<size_t>(n_slots);
+        return reserve_all(d_keep, static_cast<size_t>(slot_bytes(max)) * ns, d_over, ns, h_over, ns);
+    }
+};
+
+struct Maps {  // sfa_session_event_maps
+    ctx::MapScratch scratch;      // moves, row table, device output of a call: the session's own, never the context's
+    std::vector<int64_t> q_off;   // [n_slots] where every slot's query begins behind the query base
+    std::vector<sfa::MapRow> band;  // of a call
+    int reserve(int32_t n_slots, size_t n_rows) {  // (the scratch grows slice by slice inside the core)
+        q_off.resize(static_cast<size_t>(n_slots));
+        band.assign(n_rows, sfa::MapRow{});
+        return SFA_OK;
+    }
+};
+
 }  // namespace sess
 
 // `delete` frees every buffer and event of the session, in whatever order the members stand.  That relies on two things only:
@@ -158,6 +184,8 @@ struct sfa_session {
     sess::Candidates cand;
     sess::Raw raw;
     sess::AutoStart autos;
+    sess::Keep keep;
+    sess::Maps maps;
 };
 
 namespace {
@@ -216,13 +244,16 @@ void launch_sweep_kernel(const sfa_session *s, hipStream_t st, const sfa::Sessio
 // they lie in d_events already (offsets of any kind), and sweep.d_bad holds the call's poison flags.
 
 // staging: [chunk offsets (n + 1) x i64 | call_slot n x i32 | per launch: k_off i64, w_entry, g_qlen, k_call, k_slot, k_len, k_total]
+// and, on a session that keeps its events, behind all that: [slot n x i32 | events the slot had n x i32]
 size_t sweep_cslot_at(int32_t n) { return align8(8 * static_cast<size_t>(n + 1)); }
 
-int sweep_stage(sfa_session *s, const sfa::Chunk *ch, int32_t n, int64_t nq, const float *d_events) {
+int sweep_stage(sfa_session *s, const int32_t *slot, const sfa::Chunk *ch, int32_t n, int64_t nq, const float *d_events) {
     sfa_ctx *c = s->c;
     sess::Sweep &w = s->sweep;
     size_t bytes = sweep_cslot_at(n) + align8(4 * static_cast<size_t>(n));
     for (const sfa::Launch &l : w.launches) bytes += 8 * l.k_off.size() + align8(4 * (l.w_entry.size() + l.g_qlen.size() + 4 * l.k_off.size()));
+    const bool keep = s->keep.on() && !d_events;
+    if (keep) bytes += 2 * align8(4 * static_cast<size_t>(n));
     const size_t n_part = static_cast<size_t>(n) * c->model.n_jobs;
     if (int rc = w.reserve(bytes, nq, static_cast<size_t>(n), n_part)) return rc;
     if (int rc = s->cand.reserve_call(n_part)) return rc;
@@ -271,6 +302,13 @@ int sweep_stage(sfa_session *s, const sfa::Chunk *ch, int32_t n, int64_t nq, con
         a.n_tasks = l.n_tasks;
         a.p_top5 = s->cand.n_cand > 0 ? s->cand.d_p5.as<int32_t>() : nullptr;
     }
+    w.keep_at = 0;
+    if (keep) {  // (rows.len is still what the slots held before this call: sweep_collect adds the chunks)
+        w.keep_at = at;
+        int32_t *ks = reinterpret_cast<int32_t *>(h + at), *kh = reinterpret_cast<int32_t *>(h + at + align8(4 * static_cast<size_t>(n)));
+        for (int32_t i = 0; i < n; ++i) ks[i] = slot[i], kh[i] = static_cast<int32_t>(s->rows.len[slot[i]]);
+        at += 2 * align8(4 * static_cast<size_t>(n));
+    }
     if (at > bytes) return fail(SFA_EKERNEL, "session sweep: staging overrun (%zu > %zu)", at, bytes);
     w.staged = at;
     return SFA_OK;
@@ -284,6 +322,19 @@ int sweep_launch(sfa_session *s, int32_t n, const float *h_events, int64_t nq, b
     if (screen && nq > 0) HIP_TRY(hipMemcpyAsync(w.d_events.p, h_events, sizeof(float) * nq, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(w.d_count.p, 0, 4, st));
     HIP_TRY(hipEventRecord(w.ev[0], st));
+    if (w.keep_at) {  // a session that keeps its events: the chunks into the slots' kept events, in front of the sweep
+        sfa::SessionKeepArgs ka;
+        ka.events = w.d_events.as<float>();
+        ka.ch_off = w.d_stage.as<int64_t>();
+        ka.slot = reinterpret_cast<const int32_t *>(w.d_stage.as<char>() + w.keep_at);
+        ka.have = reinterpret_cast<const int32_t *>(w.d_stage.as<char>() + w.keep_at + align8(4 * static_cast<size_t>(n)));
+        ka.keep = s->keep.d_keep.as<float>();
+        ka.over = s->keep.d_over.as<uint8_t>();
+        ka.n = n;
+        ka.max_events = s->keep.max_events;
+        hipLaunchKernelGGL(sfa::sdtw_session_keep_kernel, dim3(n), dim3(256), 0, st, ka);
+        KERNEL_TRY();
+    }
     // chunks with a NaN / inf event are not swept: the slot is poisoned (rows valid = 0 until reset)
     if (screen) {
         hipLaunchKernelGGL(sfa::sdtw_screen_kernel, dim3((n + 3) / 4), dim3(256), 0, st, w.d_events.as<float>(), w.d_stage.as<int64_t>(), n, w.d_bad.as<uint8_t>(),
@@ -372,7 +423,7 @@ int sweep_collect(sfa_session *s, const int32_t *slot, const sfa::Chunk *ch, int
 int sweep_chunks(sfa_session *s, const int32_t *slot, const sfa::Chunk *ch, int32_t n, const float *h_events, int64_t nq, const float *d_events, sfa_result_t *out) {
     int64_t new_events = 0;
     sfa::plan_session_call(ch, slot, s->rows.len.data(), s->rows.poison.data(), n, s->c->model.n_jobs, &s->sweep.launches, &s->sweep.call_slot, &new_events);
-    if (int rc = sweep_stage(s, ch, n, nq, d_events)) return rc;
+    if (int rc = sweep_stage(s, slot, ch, n, nq, d_events)) return rc;
     if (int rc = sweep_launch(s, n, h_events, nq, d_events == nullptr)) return rc;
     return sweep_collect(s, slot, ch, n, new_events, out);
 }
@@ -761,6 +812,74 @@ int sfa_session_extend(sfa_session_t *s, const int32_t *slot, const float *event
     return sweep_chunks(s, slot, ch.data(), n, events ? events + ev_off[0] : nullptr, nq, nullptr, out);
 }
 
+// ---- event maps of a slot's row (the core: sfa_maps.hip) ----
+
+int64_t sfa_session_keep_bytes(int32_t n_slots, int32_t max_events) {
+    if (n_slots <= 0 || max_events <= 0) return SFA_EINVAL;
+    const int64_t per_slot = sess::Keep::slot_bytes(max_events);
+    if (per_slot > INT64_MAX / n_slots) return SFA_ERANGE;
+    return per_slot * n_slots;
+}
+
+int sfa_session_keep_events(sfa_session_t *s, int32_t max_events) {
+    if (!s) return fail(SFA_EINVAL, "sfa_session_keep_events: null session");
+    if (s->resweep || s->raw.on)
+        return fail(SFA_EINVAL, "sfa_session_keep_events: a raw-mode session keeps its slots' queries already (sfa_session_raw_config); this is for event-mode sessions");
+    if (max_events < 0 || max_events > INT32_MAX / 2) return fail(SFA_EINVAL, "sfa_session_keep_events: max_events must be 0 .. 2^30, not %d", max_events);
+    if (const int32_t sl = first_busy_slot(s); sl >= 0)
+        return fail(SFA_EINVAL, "sfa_session_keep_events: slot %d is not empty; events are kept from a slot's first chunk on, so it is switched only while every slot is empty (sfa_session_reset)", sl);
+    if (max_events > 0) {
+        sfa_ctx *c = s->c;
+        if (sfa_session_keep_bytes(s->n_slots, max_events) < 0) return fail(SFA_ENOMEM, "sfa_session_keep_events: the kept events do not fit");
+        HIP_TRY(hipSetDevice(c->device));
+        if (int rc = s->keep.reserve(s->n_slots, max_events)) return rc;
+        HIP_TRY(hipMemsetAsync(s->keep.d_over.p, 0, static_cast<size_t>(s->n_slots), c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    s->keep.max_events = max_events;
+    return SFA_OK;
+}
+
+int sfa_session_event_maps(sfa_session_t *s, const sfa_result_t *rows, const int32_t *slot_of_row, int32_t n_rows, const int64_t *map_off, int32_t *pairs,
+                           int32_t *n_on_host) {
+    static const char *const who = "sfa_session_event_maps";
+    if (!s || n_rows < 0 || (n_rows > 0 && (!rows || !slot_of_row || !map_off || !pairs))) return fail(SFA_EINVAL, "%s: bad argument", who);
+    if (n_on_host) *n_on_host = 0;
+    if (!s->track) return fail(SFA_EINVAL, "%s: the session carries no start columns (SFA_SESSION_NO_START), so its rows have no band", who);
+    if (!s->raw.on && !s->keep.on())
+        return fail(SFA_EINVAL, "%s: an event-mode session does not keep the caller's events unless asked to (sfa_session_keep_events)", who);
+    if (int rc = check_slots(s, slot_of_row, n_rows, who)) return rc;
+    for (int32_t k = 0; k < n_rows; ++k)
+        if (map_off[k + 1] < map_off[k] || map_off[k] < 0) return fail(SFA_EINVAL, "%s: map_off not monotone at row %d", who, k);
+    if (n_rows == 0) return SFA_OK;
+    sfa_ctx *c = s->c;
+    HIP_TRY(hipSetDevice(c->device));
+    if (s->keep.on())  // (the flags the keep kernel wrote; the wait below is the call's own)
+        HIP_TRY(hipMemcpyAsync(s->keep.h_over.p, s->keep.d_over.p, static_cast<size_t>(s->n_slots), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = sfa::resolve_profile(c)) return rc;
+    sess::Maps &mp = s->maps;
+    if (int rc = mp.reserve(s->n_slots, static_cast<size_t>(n_rows))) return rc;
+    // the query of a slot as swept: raw mode, its row of d_query (a resweep session stores the window in DP order already, so
+    // nothing is reversed here); event mode, its kept events
+    const int64_t stride = s->raw.on ? s->raw.query : s->keep.max_events;
+    const float *base = s->raw.on ? s->raw.d_query.as<float>() : s->keep.d_keep.as<float>();
+    for (int32_t sl = 0; sl < s->n_slots; ++sl) mp.q_off[sl] = sl * stride;
+    for (int32_t k = 0; k < n_rows; ++k) {
+        mp.band[k].k = k;
+        const sfa_result_t &r = rows[k];
+        if (!r.valid || r.rid < 0) continue;  // no row (an empty or poisoned slot gives such rows): nothing is written
+        const int32_t sl = slot_of_row[k];
+        if (s->rows.poison[sl] || s->rows.len[sl] == 0) return fail(SFA_EINVAL, "%s: row %d: slot %d is empty or poisoned; it has no row in its current state", who, k, sl);
+        if (s->keep.on() && (s->keep.h_over.as<uint8_t>()[sl] || s->rows.len[sl] > s->keep.max_events))
+            return fail(SFA_EINVAL, "%s: row %d: slot %d has received %lld events, more than the %d the session keeps; it has no maps until it is reset", who, k, sl,
+                        (long long)s->rows.len[sl], s->keep.max_events);
+        if (int rc = sfa::map_row_band(c, r, k, s->rows.len[sl], map_off[k + 1] - map_off[k], who, "this reference", &mp.band[k])) return rc;
+        mp.band[k].query = sl;
+    }
+    return sfa::event_maps_core(c, mp.scratch, base, mp.q_off.data(), mp.q_off.size(), false, mp.band.data(), n_rows, map_off, pairs, n_on_host);
+}
+
 // ---- raw mode: samples in, rows out (events_stream.hpp) ----
 
 int64_t sfa_session_raw_bytes(int32_t n_slots, int32_t skip_events, int32_t query_events) {
@@ -789,6 +908,7 @@ int sfa_session_raw_config(sfa_session_t *s, int32_t skip_events, int32_t norm_e
     r.recal_n = 0;  // (the points were checked against the sizes that go)
     r.recal_flags = 0;
     s->autos.max_samples = s->autos.every = 0;  // (the automatic start was checked against the sizes that go)
+    s->keep.max_events = 0;                     // (raw mode keeps the query itself)
     r.slots.assign(s->n_slots, sess::Raw::Slot{});
     return SFA_OK;
 }

@@ -20,6 +20,10 @@ ticks, the same calls, the same lines.  The schedule counts ticks, never seconds
             final point at the end of the read or at auto_start_max_samples); max_skip_events is the largest skip.  Schedule and
             rule are unchanged: a channel with no skip yet is simply not calibrated.  A decision carries the channel's automatic
             start, and its line two more tags, qs:i:<skip> as:A:<P|E|F> (found at a mid-read point, at the final point, fallback)
+  sam       sam=True (Python only; the binary refuses --sam): a decided channel prints the SAM record of its row instead of the PAF
+            line.  The maps of all rows decided in a tick -- primaries, and candidates under candidates=N -- come from ONE
+            Session.event_maps call before the reset, on the slots' resident queries; the record is sam_row_from_map over the slot's
+            events (Session.events) and is followed by the same tags (format_sam_line, format_sam).  Schedule and rule are unchanged
   after it  decided channels are reset in one call and take the next unread reads, lowest channel first, from tick t + 1 on
 """
 import numpy as np
@@ -112,7 +116,7 @@ AUTO_START_MAX_SAMPLES, MAX_SKIP_EVENTS = 131072, 4096  # the defaults of --auto
 
 
 def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False, resweep=False,
-           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS):
+           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False):
     """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
     candidates=1..4 (--candidates): an eighth element, RESULT_DTYPE[4], the channel's candidates at the decision, best first.
     A `session` of the caller's is taken as it is, in this as in its raw mode: it must keep that many candidates already
@@ -128,8 +132,15 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     is then the slot's window.
     skip = -1 (-p -1): the automatic query start; needs resweep.  auto_start_every (None: chunk_samples; 0: the final point only),
     auto_start_max_samples and max_skip_events configure it on a session of replay's own; every item then ends with one more
-    element, the channel's SESSION_AUTO_DTYPE record at the decision, which format_line takes as auto=."""
+    element, the channel's SESSION_AUTO_DTYPE record at the decision, which format_line takes as auto=.
+    sam=True: every item ends with one element more, behind all others, what format_sam() needs for the decision's SAM records: a
+    dict with `events` (Session.events of the slot), `qstart` / `qend` (the query inside them: the slot's skip and skip + q_events),
+    `map` (the primary's int32 [n, 2] event map from Session.event_maps, None when it has none) and `cand_maps` (the four
+    candidates' maps with candidates=N, else None).  A session that carries no start columns (starts=False) has no maps: refused
+    before any call."""
     auto = skip < 0
+    if sam and session is not None and not getattr(session, "starts", True):
+        raise api.SfaError("replay: sam=True needs the rows' start columns; the session was created with starts=False (SESSION_NO_START)")
     if auto and not resweep:
         raise api.SfaError("replay: skip = -1 (automatic query start) needs resweep=True on an RNA aligner without INV")
     reads = iter(reads)
@@ -176,16 +187,37 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                 a, b = se.query_span(d_slots)
                 cand = se.candidates(d_slots) if candidates else None
                 au = se.auto_start(d_slots) if auto else None
+                maps = None
+                if sam:  # one call for the tick: every decided channel's primary, then its four candidate rows
+                    per = 5 if candidates else 1
+                    m_rows = np.zeros(per * len(decided), api.RESULT_DTYPE)
+                    for k, i in enumerate(decided):
+                        m_rows[per * k] = rows[i]
+                        if candidates:
+                            m_rows[per * k + 1:per * k + 5] = cand[k]
+                    pairs, off, _ = se.event_maps(m_rows, np.repeat(np.asarray(d_slots, np.int32), per))
+                    maps = [_map_or_none(pairs[off[j]:off[j + 1]]) for j in range(len(m_rows))]
                 for k, i in enumerate(decided):
                     item = (sch.tick, slots[i], on[slots[i]][0], rows[i].copy(), info[i].copy(), (int(a[k]), int(b[k])), reason[i])
                     if candidates:
                         item += (cand[k].copy(),)
-                    yield item + (au[k].copy(),) if auto else item
+                    if auto:
+                        item += (au[k].copy(),)
+                    if sam:
+                        qs = int(au[k]["skip"]) if auto else skip
+                        item += (dict(events=se.events(slots[i]) if mapped(rows[i]) else None, qstart=qs, qend=qs + int(info[i]["q_events"]), map=maps[per * k],
+                                      cand_maps=maps[per * k + 1:per * k + 5] if candidates else None),)
+                    yield item
                 se.reset(d_slots)
             sch.end_tick(reason, line, src)
     finally:
         if own:
             se.close()
+
+
+def _map_or_none(m):
+    """a row's slice of Session.event_maps: None when the row has no map (not mapped, or the library wrote nothing for it)"""
+    return m.copy() if len(m) and m[0, 0] != np.iinfo(np.int32).min else None
 
 
 def auto_tags(auto):
@@ -220,3 +252,32 @@ def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, s
         base = api.paf_row(r, read_id, names[rid], span[0], span[1], int(info["q_events"]) - 1, int(n_samples), int(seq_lengths[rid]), tp="S")
         out.append(f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}\n")
     return "".join(out)
+
+
+def format_sam_line(read_id, names, row, info, reason, events, qstart, qend, pairs, flag, secondary=False, auto=None):
+    """The SAM record of a decision's row in place of format_line's PAF line: api.sam_row_from_map over the slot's events
+    [qstart, qend) and the row's event map, then the same ne:i / ns:i / dc:A tags (and qs:i / as:A with auto=).  "" when the row is
+    not mapped, has no map, or sam_row_from_map refuses the map (RNA: a last reference column without a query event -- the ss
+    string cannot express it; `dtw --sam` leaves such rows out too and counts them)."""
+    if not mapped(row) or pairs is None or len(pairs) == 0:
+        return ""
+    try:
+        base = api.sam_row_from_map(row, read_id, names[int(row["rid"])], events, qstart, qend, pairs, flag, secondary)
+    except api.SfaError:
+        return ""
+    return f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}{'' if auto is None else auto_tags(auto)}\n"
+
+
+def format_sam(read_id, names, row, info, reason, sam, flag, cand=None, auto=None):
+    """(text, refused) for one item of replay(sam=True): the primary's record and, with cand= (the item's candidates), the records
+    of its valid candidates behind it, best first, as secondaries (FLAG | 256); `sam` is the item's last element.  refused: mapped
+    rows left out because they have no printable map.  ("", 0) when the primary is not mapped: a decision without a line."""
+    if not mapped(row):
+        return "", 0
+    out, refused = [], 0
+    todo = [(row, sam["map"], False)] + ([(r, m, True) for r, m in zip(cand, sam["cand_maps"]) if mapped(r)] if cand is not None else [])
+    for r, m, secondary in todo:
+        line = format_sam_line(read_id, names, r, info, reason, sam["events"], sam["qstart"], sam["qend"], m, flag, secondary, None if secondary else auto)
+        out.append(line)
+        refused += line == ""
+    return "".join(out), refused
