@@ -188,6 +188,9 @@ int sfa_secondary_rows(sfa_ctx_t *ctx, sfa_result_t *sec, int32_t n_reads);
  * return SFA_EINVAL.  The band of every row is filled again on the device with the arithmetic of the host routine (bit-identical
  * costs, same tie order) in slices whose packed moves fit "map_scratch_bytes"; a row whose own moves exceed that budget, or whose
  * read has more than SFA_MAX_QUERY events, is computed by the host routine inside the call -- *n_on_host (may be NULL) counts them.
+ * With the option "map_strips" a read of more than SFA_MAX_QUERY events stays on the device: its band is filled in strips of
+ * SFA_MAX_QUERY query rows, one launch per strip level, each strip starting from the bottom row of the one above; only a row
+ * whose own moves exceed the budget then goes to the host routine and counts.  The maps are the same bytes either way.
  * SFA_EINVAL: no completed call, a read count or read index that does not match it, or the last call was
  * sfa_align_batch_device (its queries are the caller's).  Group contexts split the rows by the shard that holds their read. */
 int sfa_event_maps(sfa_ctx_t *ctx, const sfa_result_t *rows, const int32_t *read_of_row, int32_t n_rows, const int64_t *map_off,
@@ -283,7 +286,8 @@ int64_t sfa_session_bytes(int64_t total_columns, int32_t n_slots, uint32_t sessi
  * event mode the events the session kept (sfa_session_keep_events).  The band comes from the row, the flip and offset undone as
  * for sfa_event_maps; the same fill and walk kernels run it, in slices that follow "map_scratch_bytes".  A slot with more than
  * SFA_MAX_QUERY query events, or a row whose own moves exceed the budget, takes the host routine inside the call (that slot's
- * query is copied back; there is no device route beyond SFA_MAX_QUERY events) and counts in *n_on_host.
+ * query is copied back) and counts in *n_on_host; with the context's option "map_strips" a slot beyond SFA_MAX_QUERY events runs
+ * on the device in row strips, as for sfa_event_maps, and only a row beyond the budget is the host's.
  * Blocking, on the context's stream.  The scratch is the session's own: sfa_event_maps keeps referring to the last BATCH call and
  * returns the same bytes whether or not a session call came in between, and the reverse.
  * SFA_EINVAL: a SFA_SESSION_NO_START session (no start column, no band); an event-mode session that keeps no events, or a slot
@@ -507,6 +511,10 @@ int sfa_align_events(sfa_ctx_t *ctx, const sfa_event_t *const *events, const int
  *                             two-pass route (HBM snapshots, no column segments, pass 2 as its own launches).  Rows do not change
  *     "map_scratch_bytes"     HBM the packed moves of one slice of rows may take in sfa_event_maps (default 2 GiB); rows are processed in
  *                             slices that fit, a row that does not fit alone goes to the host routine
+ *     "map_strips"            0 (default) or 1: sfa_event_maps and sfa_session_event_maps run a row of more than SFA_MAX_QUERY events on
+ *                             the device, in strips of SFA_MAX_QUERY query rows (ceil(events / 2048) strips of (m + 63) * 512 bytes of
+ *                             moves for a band of m columns, plus two hand-over rows of m floats: all of it counts against
+ *                             "map_scratch_bytes"), instead of on the host inside the call.  Same maps; 0 launches what it always did
  *   raw-signal path
  *     "ev_parallel"           bit 0: wave-per-read prefix sums for every read whose sums are provably exact in any order (the
  *                             sequential kernel for the rest); bit 1: chunk-parallel peak picker accepted where it is certified

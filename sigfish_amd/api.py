@@ -322,7 +322,9 @@ class Aligner:
         """aln_t.r2qevent_map of rows of the most recent call, computed on the device: a list of int32 [size, 2] arrays (start, stop
         per reference column, as r2qevent_map returns for one row; size 0 for a row without a map).  rows: RESULT_DTYPE rows that
         call returned -- default: its primaries -- or rows of secondary_rows(); read_of_row: the read of each row (default: the
-        identity).  The number of rows the library computed on the host instead is left in `maps_on_host`."""
+        identity).  The number of rows the library computed on the host instead is left in `maps_on_host`: rows whose moves exceed
+        the "map_scratch_bytes" budget, and rows of reads beyond 2048 events unless set_option("map_strips", 1) is in force, which
+        runs those on the device in row strips (same maps)."""
         if rows is None:
             rows = self._last_rows
             if rows is None:
@@ -505,8 +507,9 @@ class Session:
         extend_raw(), or a row of candidates(); a slot may be named several times.  -> (pairs int32 [total, 2], map_off int64
         [len(rows) + 1], n_on_host): the map of row k is pairs[map_off[k]:map_off[k + 1]], start and stop per reference column as
         r2qevent_map returns them; rows without a row (valid = 0) have an empty slice; a row the library wrote nothing for (no
-        complete map) keeps INT32_MIN.  n_on_host: rows computed by the host routine inside the call (a slot beyond 2048 query
-        events, or moves beyond the "map_scratch_bytes" budget)."""
+        complete map) keeps INT32_MIN.  n_on_host: rows computed by the host routine inside the call (moves beyond the
+        "map_scratch_bytes" budget; a slot beyond 2048 query events too, unless the aligner's option "map_strips" is 1, which runs
+        such slots on the device in row strips)."""
         self._live()
         rows = np.ascontiguousarray(rows, RESULT_DTYPE).reshape(-1)
         sl = np.ascontiguousarray(slots, np.int32).reshape(-1)

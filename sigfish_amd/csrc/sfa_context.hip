@@ -231,6 +231,9 @@ int sfa_set_option(sfa_ctx_t *c, const char *key, int64_t value) {
     } else if (k == "map_scratch_bytes") {
         if (value < 0) return fail(SFA_EINVAL, "map_scratch_bytes must be >= 0");
         c->opt_map_scratch = value;
+    } else if (k == "map_strips") {
+        if (value != 0 && value != 1) return fail(SFA_EINVAL, "map_strips must be 0 (rows beyond SFA_MAX_QUERY events on the host) or 1 (on the device, in row strips)");
+        c->opt_map_strips = value;
     } else if (k == "prio_unit") {
         if (value < 0 || value > (1 << 28)) return fail(SFA_EINVAL, "prio_unit must be 0 (off) .. 2^28");
         c->opt_prio_unit = value;

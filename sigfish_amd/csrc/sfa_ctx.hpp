@@ -372,6 +372,7 @@ struct sfa_ctx {
     int64_t opt_debug_drop_quad = -1;        // the fill tasks of this quad never signal completion
     int64_t opt_debug_drop_strip = -1;       // strip 0 of this long read (job 0) never publishes its progress
     int64_t opt_map_scratch = 2ll << 30;  // bytes of HBM the move matrices of one slice of rows may take
+    int64_t opt_map_strips = 0;           // 1: event maps of rows beyond SFA_MAX_QUERY events on the device, in row strips (sdtw_path.hpp)
 
     ctx::RefModel model;
     ctx::CallerIO io;
@@ -410,7 +411,8 @@ struct MapRow {  // one row of a call, as the core takes it
 int map_row_band(const sfa_ctx *c, const sfa_result_t &r, int32_t k, int64_t qlen, int64_t gap, const char *who, const char *what, MapRow *b);
 // Maps of band[0..n) on the context's device and stream, into the caller's pairs.  The query of a row lies at d_queries +
 // q_off[row.query], row.qlen events in DP order (reversed: in event order, the DP takes them back to front); q_off[n_q_off] is
-// host memory.  Scratch: sc.  Rows beyond SFA_MAX_QUERY events or the "map_scratch_bytes" budget take the host routine.
+// host memory.  Scratch: sc.  Rows beyond the "map_scratch_bytes" budget take the host routine; so do rows beyond SFA_MAX_QUERY
+// events unless "map_strips" is on, which runs them in row strips.
 int event_maps_core(sfa_ctx *c, ctx::MapScratch &sc, const float *d_queries, const int64_t *q_off, size_t n_q_off, bool reversed, const MapRow *band, int32_t n,
                     const int64_t *map_off, int32_t *pairs, int32_t *n_on_host);
 // contiguous read range of shard r: [r*n/G, (r+1)*n/G)

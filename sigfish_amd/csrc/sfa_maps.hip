@@ -3,8 +3,10 @@
 // which takes a device query base, per-row query offsets and lengths, the rows' bands and the scratch of its caller.  Host work: band of every row in columns of its strand's array (the
 // flip and offset of src/sigfish.c:971-975 undone, as path_of_row does for the per-read host routine), slices of rows whose move
 // matrices fit the scratch budget (sfa_plan.hpp, plan_map_slices), one fill + one walk launch per rows-per-lane class of a
-// slice, maps back through page-locked memory.  Rows the device does not take -- queries beyond SFA_MAX_QUERY, a move matrix
-// beyond the budget -- are computed by the host routine (band_traceback) inside the same call, from the same resident data.
+// slice, maps back through page-locked memory.  With the option "map_strips" rows of more than SFA_MAX_QUERY events run in strips
+// of 2048 query rows (plan_map_slices_strips; one launch per strip level of a slice, then one walk through the strips).  Rows the
+// device does not take -- a move matrix beyond the budget, and without that option queries beyond SFA_MAX_QUERY -- are computed by
+// the host routine (band_traceback) inside the same call, from the same resident data.
 #include "sfa_ctx.hpp"
 #define SFA_DEFINE_PATH_WALK_KERNEL
 #include "sdtw_path.hpp"
@@ -20,6 +22,10 @@ namespace sfa {
 SFA_PATH_SHAPES(SFA_PATH_DECL, false)
 SFA_PATH_SHAPES(SFA_PATH_DECL, true)
 #undef SFA_PATH_DECL
+extern template __global__ void sdtw_path_strip_kernel<false, false>(const PathArgs);
+extern template __global__ void sdtw_path_strip_kernel<false, true>(const PathArgs);
+extern template __global__ void sdtw_path_strip_kernel<true, false>(const PathArgs);
+extern template __global__ void sdtw_path_strip_kernel<true, true>(const PathArgs);
 }  // namespace sfa
 
 namespace {
@@ -38,6 +44,17 @@ void launch_path_fill(int ci, const PathArgs &pa, hipStream_t st) {
         SFA_PATH_CASE(3, 16, 16) SFA_PATH_CASE(4, 8, 16) SFA_PATH_CASE(5, 4, 16)
 #undef SFA_PATH_CASE
     }
+}
+
+// strip level pa.strip of the long rows of a slice, one row per wave; level 0 starts from the boundary, every other one from the
+// row the level before handed over
+template <bool STD>
+void launch_path_strip(const PathArgs &pa, hipStream_t st) {
+    const dim3 grid((pa.n_rows + 3) / 4), block(256);
+    if (pa.strip == 0)
+        hipLaunchKernelGGL((sfa::sdtw_path_strip_kernel<STD, false>), grid, block, 0, st, pa);
+    else
+        hipLaunchKernelGGL((sfa::sdtw_path_strip_kernel<STD, true>), grid, block, 0, st, pa);
 }
 
 }  // namespace
@@ -69,19 +86,22 @@ int event_maps_core(sfa_ctx *c, ctx::MapScratch &sc, const float *d_queries, con
     const bool std_dtw = (c->flag & SFA_DTW) != 0;
     std::vector<int32_t> qlen(n_idx), m(n_idx);
     for (int32_t t = 0; t < n_idx; ++t) qlen[t] = band[t].qlen, m[t] = band[t].m;
-    const sfa::MapSlices ms = sfa::plan_map_slices(qlen.data(), m.data(), n_idx, c->opt_map_scratch);
+    const sfa::MapSlices ms = c->opt_map_strips ? sfa::plan_map_slices_strips(qlen.data(), m.data(), n_idx, c->opt_map_scratch)
+                                                : sfa::plan_map_slices(qlen.data(), m.data(), n_idx, c->opt_map_scratch);
     hipStream_t st = c->stream;
     // the query offsets of the call live in the staging area of its launches only; the walks need them again
     std::vector<PathRow> prow;
     std::vector<int32_t> t_of;  // position in prow -> t
     for (size_t s = 0; s + 1 < ms.slice_begin.size(); ++s) {
         const int32_t lo = ms.slice_begin[s], hi = ms.slice_begin[s + 1];
-        // rows of the slice by class (long first, as the fill runs them), input order inside a class
+        // rows of the slice by class (long first, as the fill runs them), input order inside a class; in front of the six classes
+        // the rows beyond kMaxQuery events ("map_strips"; class_for gives -1), which run in row strips
         prow.clear();
         t_of.clear();
-        int32_t cls_begin[7];
+        int32_t cls_store[8], *const cls_begin = cls_store + 1;
         int64_t out_pairs = 0, mv_bytes = 0;
-        for (int ci = 0; ci < 6; ++ci) {
+        int32_t strip_levels = 0;
+        for (int ci = -1; ci < 6; ++ci) {
             cls_begin[ci] = static_cast<int32_t>(prow.size());
             for (int32_t o = lo; o < hi; ++o) {
                 const int32_t t = ms.order[o];
@@ -96,7 +116,8 @@ int event_maps_core(sfa_ctx *c, ctx::MapScratch &sc, const float *d_queries, con
                 p.m = b.m;
                 p.qlen = b.qlen;
                 out_pairs += b.m;
-                mv_bytes = std::max(mv_bytes, ms.mv_off[o] + sfa::map_row_bytes(b.qlen, b.m));
+                mv_bytes = std::max(mv_bytes, ms.mv_off[o] + sfa::map_row_bytes_strips(b.qlen, b.m));
+                if (ci < 0) strip_levels = std::max(strip_levels, sfa::map_strip_count(b.qlen));
                 prow.push_back(p);
                 t_of.push_back(t);
             }
@@ -110,7 +131,7 @@ int event_maps_core(sfa_ctx *c, ctx::MapScratch &sc, const float *d_queries, con
         int64_t *d_qoff = reinterpret_cast<int64_t *>(sc.d_prow.as<char>() + sizeof(PathRow) * n);
         HIP_TRY(hipMemcpyAsync(sc.d_prow.p, prow.data(), sizeof(PathRow) * n, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_qoff, q_off, qoff_bytes, hipMemcpyHostToDevice, st));
-        for (int ci = 0; ci < 6; ++ci) {
+        for (int ci = -1; ci < 6; ++ci) {
             const int32_t nc = cls_begin[ci + 1] - cls_begin[ci];
             if (nc == 0) continue;
             PathArgs pa{};
@@ -124,6 +145,18 @@ int event_maps_core(sfa_ctx *c, ctx::MapScratch &sc, const float *d_queries, con
             pa.first_col = sc.d_pfirst.as<int32_t>() + cls_begin[ci];
             pa.n_rows = nc;
             pa.rev_query = reversed ? 1 : 0;
+            if (ci < 0) {  // one launch per strip level; a level reads what the one before handed over, in stream order
+                for (pa.strip = 0; pa.strip < strip_levels; ++pa.strip) {
+                    if (std_dtw)
+                        launch_path_strip<true>(pa, st);
+                    else
+                        launch_path_strip<false>(pa, st);
+                    KERNEL_TRY();
+                }
+                hipLaunchKernelGGL(sfa::sdtw_path_walk_strips_kernel, dim3((nc + 255) / 256), dim3(256), 0, st, pa);
+                KERNEL_TRY();
+                continue;
+            }
             if (std_dtw)
                 launch_path_fill<true>(ci, pa, st);
             else

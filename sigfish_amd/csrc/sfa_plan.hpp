@@ -388,4 +388,48 @@ inline MapSlices plan_map_slices(const int32_t *qlen, const int32_t *m, int32_t 
     return s;
 }
 
+// ---- rows of more than kMaxQuery events on the device ("map_strips"): the band fill in row strips ----
+// Such a row is cut into strips of kMaxQuery query rows (the last one shorter).  Every strip runs in the 32 rows x 64 lanes shape,
+// one row per wave, and stores its own m + 63 records of 64 x 2 words; strip s + 1 starts from the bottom row of strip s, which
+// lies in one of two hand-over rows of m floats behind the row's moves (used ping-pong, strips run in stream order).
+
+inline int32_t map_strip_count(int qlen) { return (qlen + kMaxQuery - 1) / kMaxQuery; }
+
+// packed moves of ONE strip of a long row, in 32-bit words
+inline int64_t map_strip_words(int32_t m) { return (static_cast<int64_t>(m) + 63) * 64 * 2; }
+
+// packed moves of a long row in bytes: n_strips x (m + 63) x 512
+inline int64_t map_long_move_bytes(int qlen, int32_t m) { return map_strip_count(qlen) * map_strip_words(m) * 4; }
+
+// everything the row takes of a slice's scratch: its moves, then the two hand-over rows.  THIS is what counts against the budget.
+inline int64_t map_long_row_bytes(int qlen, int32_t m) { return map_long_move_bytes(qlen, m) + 2 * 4 * static_cast<int64_t>(m); }
+
+// scratch of a row on either route
+inline int64_t map_row_bytes_strips(int qlen, int32_t m) { return qlen > kMaxQuery ? map_long_row_bytes(qlen, m) : map_row_bytes(qlen, m); }
+
+// plan_map_slices with long rows admitted: the same slicing, a row of more than kMaxQuery events counting map_long_row_bytes.
+// Only a row whose own bytes exceed the budget goes to host_rows.  Without long rows the result is plan_map_slices'.
+inline MapSlices plan_map_slices_strips(const int32_t *qlen, const int32_t *m, int32_t n, int64_t budget_bytes) {
+    MapSlices s;
+    s.slice_begin.push_back(0);
+    int64_t used = 0;
+    for (int32_t k = 0; k < n; ++k) {
+        if (m[k] <= 0 || qlen[k] <= 0) continue;
+        const int64_t bytes = map_row_bytes_strips(qlen[k], m[k]);
+        if (bytes > budget_bytes) {
+            s.host_rows.push_back(k);
+            continue;
+        }
+        if (used + bytes > budget_bytes) {
+            s.slice_begin.push_back(static_cast<int32_t>(s.order.size()));
+            used = 0;
+        }
+        s.order.push_back(k);
+        s.mv_off.push_back(used);
+        used += bytes;
+    }
+    if (static_cast<int32_t>(s.order.size()) > s.slice_begin.back()) s.slice_begin.push_back(static_cast<int32_t>(s.order.size()));
+    return s;
+}
+
 }  // namespace sfa
