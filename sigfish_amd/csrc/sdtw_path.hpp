@@ -17,6 +17,7 @@
 // from above only, as on the host.
 #pragma once
 #include "sdtw_kernels.hpp"
+#include "sfa_plan.hpp"  // kStripRows
 
 namespace sfa {
 
@@ -157,8 +158,6 @@ __global__ void __launch_bounds__(256) sdtw_path_fill_kernel(const PathArgs a) {
 // lane 63 of a full strip stores the cost of its bottom row (query row s * 2048 + 2047) at every band column into row s & 1, lane 0
 // of the strip below reads row (s - 1) & 1 four columns ahead: `up` of band column j is top[j], the diagonal top[j - 1] (the `up`
 // of the step before, +inf at j = 0: the column in front of the band is +inf on the host too).  std_dtw's prefix rule is strip 0's.
-constexpr int kStripRows = 2048;
-
 __device__ __forceinline__ int64_t path_strip_words(const int m) { return (static_cast<int64_t>(m) + 63) * 128; }
 
 template <bool STD, bool TOP>

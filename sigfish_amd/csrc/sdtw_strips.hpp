@@ -27,13 +27,11 @@
 #pragma once
 
 #include "sdtw_kernels.hpp"
+#include "sfa_plan.hpp"  // the strips' geometry: kStripR, kStripRows, kCkRec, kBndPad, kPipeBlock (SFA_PIPE_BLOCK)
 
 namespace sfa {
 
-constexpr int kStripR = 32;                 // query rows per lane, at most
-constexpr int kStripRows = 64 * kStripR;    // query rows per strip, at most: a query has ceil(qlen / 2048) strips
-constexpr int kCkRec = (kStripR + 1) * 64;  // floats per checkpoint record: a plane of 64 lanes per row of a lane (up to 32) ...
-constexpr int kCkDprev = kStripR * 64;      // ... and the plane of the diagonal inputs
+constexpr int kCkDprev = kStripR * 64;      // where a checkpoint record (kCkRec floats) keeps the plane of the diagonal inputs
 
 // BALANCED STRIPS.  The strips of a query all have the same height, 64 lanes x R rows with the smallest R of {20, 24, 28, 32}
 // that covers the query: 3 000 events are 2 strips of 64 x 24 rows (1 536 + 1 464) instead of 2 048 + 952 rows at R = 32 -- the
@@ -46,7 +44,6 @@ __host__ __device__ inline int strip_rows_per_lane(const int qlen) {
     const int R = per_lane <= 20 ? 20 : (per_lane <= 24 ? 24 : (per_lane <= 28 ? 28 : 32));
     return 64 * R * (n_strips - 1) < qlen ? R : kStripR;  // (always: the last strip holds at least one row)
 }
-constexpr int kBndPad = 256;                // words behind every boundary row (block over-run of the sweep + prefetch)
 
 struct StripArgs {
     const float *queries;     // HBM: concatenated z-normalised event means
@@ -83,11 +80,6 @@ struct StripArgs {
     unsigned long long *task_times;  // measurement builds (tools/strip_task_times.py): [task][3] start, end (100 MHz ticks), SIMD position | strip << 32
 #endif
 };
-
-#ifndef SFA_PIPE_BLOCK
-#define SFA_PIPE_BLOCK 256
-#endif
-constexpr int kPipeBlock = SFA_PIPE_BLOCK;  // columns between two hand-overs of a boundary row (one release / acquire pair each)
 
 // One anti-diagonal step of a strip: dp_step<R, TRACK> with the handling of query row 0 made conditional on FIRST (the
 // strip that contains it).

@@ -2,6 +2,9 @@
 // align_db() (src/sigfish.c:1003-1015).  Host work: group reads into "quads" (reads of one length class share a wavefront;
 // sfa_plan.hpp), pick the rows-per-lane class, size the checkpoint interval, launch fill (+ pass 2 by ticket, or fill ->
 // finalize -> trace -> finalize), row strips for queries beyond 2048 events, and hand back one row per read in input order.
+// Both paths have one shape: a plan that is plain C++ (sfa_plan.hpp: plan_batch + choose_route, plan_long_reads), then stages that
+// hand it on -- stage_and_reserve / batch_args / enqueue_pass1, 2 for the wave kernels, stage_long / long_args / enqueue_long_group
+// for the row strips -- under enqueue_batch.
 #define SFA_DEFINE_FINALIZE_KERNEL  // (of sdtw_kernels.hpp and sdtw_strips.hpp: this unit holds the plain kernels)
 #include "sfa_ctx.hpp"
 #include "sdtw_instances.hpp"
@@ -42,173 +45,153 @@ void by_std(bool std_dtw, F f) {
         f(std::false_type());
 }
 
-// Reads of more than SFA_MAX_QUERY events: row strips (sdtw_strips.hpp).  Pass 1, one wave per (read, job, strip), sweeps the
-// query in strips of 64 x R rows, cost only, handing the last row of a strip to the next one through HBM; the strip finalize
-// names each read's winning (job, cell, score); pass 2, one wave per read, traces the winning job strip by strip from the last
-// one upwards with start-column tracking.  Runs on `st`: the context's second stream, beside the wave kernels of the batch; it
-// writes the rows of these reads, which the wave kernels' finalize leaves alone.  Reads are taken in groups whose boundary rows
-// and checkpoints fit the checkpoint budget -- and, when there are enough of them, in two groups on two streams with two sets of
-// scratch: pass 2 of a group is one wave per read (0.8 waves per SIMD for 3 125 reads: bound by one wave's dependent chain, 12 ms
-// at 8 000 events) and runs beside the other group's work instead of behind everything.  Measured on one box, ms per step at
-// 3 000 / 8 000 events: one group 99.9 / 103.5, two 97.4 / 99.2, four 104.7 / 118.8 (more drains than they hide):
-// profiles/r04_logs/strips_groups_ab*.log, rejected_strip_pass2_rows_in_lds_three_waves.log.
-int align_long(sfa_ctx *c, const float *d_queries, const int64_t *d_q_off, const int64_t *q_off_host, const std::vector<int32_t> &reads, int64_t max_qlen,
-               ResultRow *d_out, hipStream_t st) {
-    const int32_t n_long = static_cast<int32_t>(reads.size()), n_jobs = c->model.n_jobs;
-    const size_t o_reads = 0, o_bnd = (sizeof(int32_t) * n_long + 7) & ~size_t(7);
-    const size_t o_ck = o_bnd + sizeof(int64_t) * (n_jobs + 1);
-    const size_t o_soff = o_ck + sizeof(int64_t) * (n_jobs + 1);  // per-group prefix sums of the reads' strip counts: group g0 at word g0 + (its index)
-    const size_t stage_bytes = o_soff + sizeof(int32_t) * (2 * static_cast<size_t>(n_long) + 2);  // (at most n_long groups)
-    std::vector<int32_t> n_strips_of(n_long);
-    for (int32_t i = 0; i < n_long; ++i) n_strips_of[i] = static_cast<int32_t>((q_off_host[reads[i] + 1] - q_off_host[reads[i]] + sfa::kStripRows - 1) / sfa::kStripRows);
+// ---- reads of more than SFA_MAX_QUERY events, row strips (sdtw_strips.hpp): plan -> staging and scratch -> argument blocks -> launches
+// Pass 1, one wave per (read, job, strip), sweeps the query in strips of 64 x R rows, cost only, handing the last row of a strip to
+// the next one through HBM; the strip finalize names each read's winning (job, cell, score); pass 2, one wave per read, traces the
+// winning job strip by strip from the last one upwards with start-column tracking.  Every count, offset and size, the checkpoint
+// interval, the groups and the limit of the waits are sfa::plan_long_reads' (sfa_plan.hpp: no HIP in it, tests/c/long_plan.cpp).
+
+// staging and every scratch buffer of the long reads, the plan into the page-locked staging area and up, on `st`
+int stage_long(sfa_ctx *c, const sfa::LongPlan &lp, hipStream_t st) {
+    const int sets = lp.two_sets ? 2 : 1;
+    const size_t n_long = static_cast<size_t>(lp.n_long());
     int rc;
-    if ((rc = c->strips.reserve_staging(stage_bytes))) return rc;
+    if ((rc = c->strips.reserve_staging(lp.sg.bytes))) return rc;
+    if ((rc = c->strips.reserve(lp.prog_bytes * sets, lp.bndc_floats * sets, lp.lck_floats * sets, lp.n_part, n_long, st))) return rc;
+#ifdef SFA_TASK_TIMES
+    if ((rc = c->times.d_ltimes.reserve(24 * lp.n_part * lp.max_strips))) return rc;  // (room for any group: no growth under one that is running)
+#endif
     char *hs = c->strips.h_long.as<char>();
-    memcpy(hs + o_reads, reads.data(), sizeof(int32_t) * n_long);
-    int64_t *bnd_off = reinterpret_cast<int64_t *>(hs + o_bnd);
-    int64_t per = 0;
-    for (int32_t j = 0; j < n_jobs; ++j) {
-        const int64_t row = (static_cast<int64_t>(c->model.h_job_len[j]) + sfa::kBndPad + 3) & ~int64_t(3);
-        bnd_off[j] = per;
-        per += row;
-    }
-    bnd_off[n_jobs] = per;
-    // checkpoints: every strip of every job, every T steps, 33 planes of 64 lanes; T = 512 unless that takes more than the
-    // budget for the whole set of long reads
-    const int32_t max_strips = static_cast<int32_t>((max_qlen + sfa::kStripRows - 1) / sfa::kStripRows);
-    int64_t *ck_off = reinterpret_cast<int64_t *>(hs + o_ck);
-    const int64_t rec_floats = (sfa::kStripR + 1) * 64;
-    int ck_shift = c->opt_ckpt_interval > 0 ? 2 : 9;
-    if (c->opt_ckpt_interval > 0)
-        while ((1ll << ck_shift) < c->opt_ckpt_interval) ++ck_shift;  // (the option's values are powers of two >= 4)
-    for (;; ++ck_shift) {
-        int64_t recs = 0;
-        for (int32_t j = 0; j < n_jobs; ++j) {
-            ck_off[j] = recs;
-            recs += static_cast<int64_t>(max_strips) * ((c->model.h_job_len[j] - 1) >> ck_shift);
-        }
-        ck_off[n_jobs] = recs;
-        if (c->opt_ckpt_interval > 0 || recs * rec_floats * 4 * n_long <= c->opt_ckpt_budget || ck_shift >= 14) break;
-    }
-    const int64_t ck_floats_per_read = ck_off[n_jobs] * rec_floats;
-    // cost rows of every job, one per strip boundary (pass 1 writes them, pass 2 reads them) + the checkpoints
-    const int64_t cost_rows = std::max<int64_t>(1, max_strips - 1);
-    const int64_t bytes_per_read = per * cost_rows * 4 + ck_floats_per_read * 4;
-    int64_t waves_total = 0;
-    for (int32_t i = 0; i < n_long; ++i) waves_total += static_cast<int64_t>(n_strips_of[i]) * n_jobs;
-    // two groups when each still has two rounds of the device's wave slots (16 per CU) to fill the chip with its pipeline of strips
-    const int64_t want_groups = waves_total >= 4 * 16 * static_cast<int64_t>(c->cu_count) ? 2 : 1;
-    const int64_t by_budget = c->opt_ckpt_budget / (2 * std::max<int64_t>(bytes_per_read, 1));  // (two sets of scratch)
-    const int32_t group = static_cast<int32_t>(std::max<int64_t>(1, std::min<int64_t>((n_long + want_groups - 1) / want_groups, by_budget)));
-    const bool two_sets = group < n_long;
-    const size_t n_part = static_cast<size_t>(n_long) * n_jobs;
-    const size_t prog_bytes = sizeof(int32_t) * static_cast<size_t>(group) * n_jobs * max_strips;
-    const size_t bndc_floats = static_cast<size_t>(cost_rows) * per * group, lck_floats = static_cast<size_t>(std::max<int64_t>(ck_floats_per_read, 1)) * group;
-    const int sets = two_sets ? 2 : 1;
-    if ((rc = c->strips.reserve(prog_bytes * sets, bndc_floats * sets, lck_floats * sets, n_part, n_long, st))) return rc;
-    {  // the prefix sums of every group, each in its own words: one upload for all groups, no host wait between them
-        int32_t *soff = reinterpret_cast<int32_t *>(hs + o_soff);
-        for (int32_t g0 = 0, gi = 0; g0 < n_long; g0 += group, ++gi) {
-            const int32_t gn = std::min(group, n_long - g0);
-            int32_t *so = soff + g0 + gi;
-            so[0] = 0;
-            for (int32_t i = 0; i < gn; ++i) so[i + 1] = so[i] + n_strips_of[g0 + i];
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(c->strips.d_long.p, hs, stage_bytes, hipMemcpyHostToDevice, st));
+    memcpy(hs + lp.sg.reads, lp.reads.data(), sizeof(int32_t) * n_long);
+    memcpy(hs + lp.sg.bnd, lp.bnd_off.data(), sizeof(int64_t) * lp.bnd_off.size());
+    memcpy(hs + lp.sg.ck, lp.ck_off.data(), sizeof(int64_t) * lp.ck_off.size());
+    memcpy(hs + lp.sg.soff, lp.strip_off.data(), sizeof(int32_t) * lp.strip_off.size());
+    HIP_TRY(hipMemcpyAsync(c->strips.d_long.p, hs, lp.sg.bytes, hipMemcpyHostToDevice, st));
+    return SFA_OK;
+}
+
+struct LongWinners {  // d_lwin, [5][n_long] words: a group's part of every row, from its first read g0
+    int32_t *w_job, *w_ws;
+    float *w_score;
+    int32_t *t_st, *t_end;
+    LongWinners(int32_t *win, size_t n_long, size_t g0)
+        : w_job(win + g0), w_ws(win + n_long + g0), w_score(reinterpret_cast<float *>(win + 2 * n_long + g0)), t_st(win + 3 * n_long + g0), t_end(win + 4 * n_long + g0) {}
+};
+
+struct LongArgs {  // the argument blocks of a group: pass 1 and pass 2, the strip finalize
+    sfa::StripArgs sa{};
+    sfa::StripFinalizeArgs fa{};
+};
+
+// the finalize of the group that sa describes: what the two blocks share comes from sa
+sfa::StripFinalizeArgs strip_finalize_args(const sfa_ctx *c, const sfa::StripArgs &sa, const LongWinners &w, ResultRow *d_out) {
+    sfa::StripFinalizeArgs fa{};
+    fa.reads = sa.reads;
+    fa.p_best = sa.p_best;
+    fa.p_second = sa.p_second;
+    fa.p_end = sa.p_end;
+    fa.job_contig = c->model.d_job_contig.as<int32_t>();
+    fa.job_strand = c->model.d_job_strand.as<int8_t>();
+    fa.ref_len = c->model.d_ref_len.as<int32_t>();
+    fa.ref_st_offset = c->model.d_ref_off.as<int32_t>();
+    fa.w_job = w.w_job;
+    fa.w_ws = w.w_ws;
+    fa.w_score = w.w_score;
+    fa.t_st = sa.t_st;
+    fa.t_end = sa.t_end;
+    fa.out = d_out;
+    fa.bad = c->status.d_bad.as<uint8_t>();
+    fa.n_long = sa.n_long;
+    fa.n_jobs = sa.n_jobs;
+    return fa;
+}
+
+LongArgs long_args(sfa_ctx *c, const sfa::LongPlan &lp, int32_t gi, const float *d_queries, const int64_t *d_q_off, ResultRow *d_out) {
+    const int32_t g0 = lp.begin(gi), gn = lp.size(gi), n_jobs = c->model.n_jobs;
+    const int set = lp.set(gi);
     const char *ds = c->strips.d_long.as<char>();
-    const bool std_dtw = (c->flag & SFA_DTW) != 0;
-    int32_t *win = c->strips.d_lwin.as<int32_t>();  // [5][n_long]: w_job, w_ws, w_score, t_st, t_end
-    hipStream_t const first = st;
-    if (two_sets) {  // the second stream starts behind the staging upload (and whatever `first` waited for)
+    const LongWinners w(c->strips.d_lwin.as<int32_t>(), static_cast<size_t>(lp.n_long()), static_cast<size_t>(g0));
+    LongArgs a;
+    sfa::StripArgs &sa = a.sa;
+    sa.queries = d_queries;
+    sa.q_off = d_q_off;
+    sa.reads = reinterpret_cast<const int32_t *>(ds + lp.sg.reads) + g0;
+    sa.ref = c->model.d_ref.as<float>();
+    sa.job_off = c->model.d_job_off.as<int64_t>();
+    sa.job_len = c->model.d_job_len.as<int32_t>();
+    sa.bnd_off = reinterpret_cast<const int64_t *>(ds + lp.sg.bnd);
+    sa.bnd_cost = c->strips.d_bndc.as<float>() + set * lp.bndc_floats;
+    sa.bnd_stride = lp.bnd_stride;
+    sa.p_best = c->strips.d_lbest.as<float>() + static_cast<size_t>(g0) * n_jobs;
+    sa.p_second = c->strips.d_lsecond.as<float>() + static_cast<size_t>(g0) * n_jobs;
+    sa.p_end = c->strips.d_lend.as<int32_t>() + static_cast<size_t>(g0) * n_jobs;
+    sa.w_job = w.w_job;
+    sa.w_ws = w.w_ws;
+    sa.w_score = w.w_score;
+    sa.t_st = w.t_st;
+    sa.t_end = w.t_end;
+    sa.ck = c->strips.d_lck.as<float>() + set * lp.lck_floats;
+    sa.ck_off = reinterpret_cast<const int64_t *>(ds + lp.sg.ck);
+    sa.ck_shift = lp.ck_shift;
+    sa.max_strips = lp.max_strips;
+    sa.trace_margin = static_cast<int32_t>(c->opt_trace_margin);
+    sa.n_long = gn;
+    sa.n_jobs = n_jobs;
+    sa.rev_query = ((c->flag & SFA_RNA) && !(c->flag & SFA_INV)) ? 1 : 0;
+    sa.strip_off = reinterpret_cast<const int32_t *>(ds + lp.sg.soff) + lp.off_word(gi);
+    sa.progress = reinterpret_cast<int32_t *>(c->strips.d_lprog.as<char>() + set * lp.prog_bytes);
+    sa.ticket = c->strips.d_lticket.as<unsigned>() + set * 16;  // (words 8.. of a set's 64 bytes: where a dropped strip publishes, see strip_pipe_task)
+    sa.err = c->status.dev()->err;
+    sa.spin_limit = lp.limit_ms * 100000;  // 100 MHz ticks
+    c->strips.strip_limit_ms = lp.limit_ms;
+    sa.debug_drop_strip = (c->opt_debug_drop_strip >= g0 && c->opt_debug_drop_strip < g0 + gn) ? static_cast<int32_t>(c->opt_debug_drop_strip - g0) : -1;
+#ifdef SFA_TASK_TIMES
+    sa.task_times = c->times.d_ltimes.as<unsigned long long>();
+    c->times.n_ltimes = static_cast<int64_t>(lp.strips_of(gi)) * n_jobs;
+#endif
+    a.fa = strip_finalize_args(c, sa, w, d_out);
+    return a;
+}
+
+// a group of `strips` strips on its stream: pass 1 (one wave per (job, read, strip), tickets in that order), winners, pass 2, rows
+int enqueue_long_group(const LongArgs &a, int64_t strips, bool std_dtw, hipStream_t st) {
+    const sfa::StripArgs &sa = a.sa;
+    sfa::StripFinalizeArgs fa = a.fa;
+    const int64_t waves = strips * sa.n_jobs;
+    const dim3 block(256), gridp(static_cast<unsigned>((waves + 3) / 4)), grid2((sa.n_long + 3) / 4), fgrid((sa.n_long + 63) / 64), fblock(64);
+    HIP_TRY(hipMemsetAsync(sa.progress, 0, sizeof(int32_t) * static_cast<size_t>(sa.n_long) * sa.n_jobs * sa.max_strips, st));
+    HIP_TRY(hipMemsetAsync(sa.ticket, 0, 4, st));
+    by_std(std_dtw, [&](auto S) { hipLaunchKernelGGL((sfa::sdtw_strip_pipe_kernel<S>), gridp, block, 0, st, sa); });
+    KERNEL_TRY();
+    fa.mode = 1;
+    hipLaunchKernelGGL(sfa::sdtw_strip_finalize_kernel, fgrid, fblock, 0, st, fa);
+    KERNEL_TRY();
+    by_std(std_dtw, [&](auto S) { hipLaunchKernelGGL((sfa::sdtw_strip_chain_kernel<S>), grid2, block, 0, st, sa); });
+    KERNEL_TRY();
+    fa.mode = 2;
+    hipLaunchKernelGGL(sfa::sdtw_strip_finalize_kernel, fgrid, fblock, 0, st, fa);
+    KERNEL_TRY();
+    return SFA_OK;
+}
+
+// The long reads of a batch on `first`, the context's second stream, beside the wave kernels of the batch; it writes the rows of
+// these reads, which the wave kernels' finalize leaves alone.  Reads are taken in groups whose boundary rows and checkpoints fit
+// the checkpoint budget -- and, when there are enough of them, in two groups on two streams with two sets of scratch: pass 2 of a
+// group is one wave per read (0.8 waves per SIMD for 3 125 reads: bound by one wave's dependent chain, 12 ms at 8 000 events) and
+// runs beside the other group's work instead of behind everything.  Measured on one box, ms per step at 3 000 / 8 000 events: one
+// group 99.9 / 103.5, two 97.4 / 99.2, four 104.7 / 118.8 (more drains than they hide): profiles/r04_logs/strips_groups_ab*.log,
+// rejected_strip_pass2_rows_in_lds_three_waves.log.
+int align_long(sfa_ctx *c, const sfa::LongPlan &lp, const float *d_queries, const int64_t *d_q_off, ResultRow *d_out, hipStream_t first) {
+    if (int rc = stage_long(c, lp, first)) return rc;
+    if (lp.two_sets) {  // the second stream starts behind the staging upload (and whatever `first` waited for)
         HIP_TRY(hipEventRecord(c->lev[2], first));
         HIP_TRY(hipStreamWaitEvent(c->stream_long2, c->lev[2], 0));
     }
-    for (int32_t g0 = 0, gi = 0; g0 < n_long; g0 += group, ++gi) {
-        const int32_t gn = std::min(group, n_long - g0);
-        const int set = two_sets ? (gi & 1) : 0;  // groups of one set run on one stream: its scratch is free when the next one starts
-        st = set ? c->stream_long2 : first;
-        sfa::StripArgs sa{};
-        sa.queries = d_queries;
-        sa.q_off = d_q_off;
-        sa.reads = reinterpret_cast<const int32_t *>(ds + o_reads) + g0;
-        sa.ref = c->model.d_ref.as<float>();
-        sa.job_off = c->model.d_job_off.as<int64_t>();
-        sa.job_len = c->model.d_job_len.as<int32_t>();
-        sa.bnd_off = reinterpret_cast<const int64_t *>(ds + o_bnd);
-        sa.bnd_cost = c->strips.d_bndc.as<float>() + set * bndc_floats;
-        sa.bnd_stride = cost_rows * per;
-        sa.p_best = c->strips.d_lbest.as<float>() + static_cast<size_t>(g0) * n_jobs;
-        sa.p_second = c->strips.d_lsecond.as<float>() + static_cast<size_t>(g0) * n_jobs;
-        sa.p_end = c->strips.d_lend.as<int32_t>() + static_cast<size_t>(g0) * n_jobs;
-        sa.w_job = win + g0;
-        sa.w_ws = win + n_long + g0;
-        sa.w_score = reinterpret_cast<const float *>(win + 2 * static_cast<size_t>(n_long) + g0);
-        sa.t_st = win + 3 * static_cast<size_t>(n_long) + g0;
-        sa.t_end = win + 4 * static_cast<size_t>(n_long) + g0;
-        sa.ck = c->strips.d_lck.as<float>() + set * lck_floats;
-        sa.ck_off = reinterpret_cast<const int64_t *>(ds + o_ck);
-        sa.ck_shift = ck_shift;
-        sa.max_strips = max_strips;
-        sa.trace_margin = static_cast<int32_t>(c->opt_trace_margin);
-        sa.n_long = gn;
-        sa.n_jobs = n_jobs;
-        sa.rev_query = ((c->flag & SFA_RNA) && !(c->flag & SFA_INV)) ? 1 : 0;
-        sa.err = c->status.dev()->err;
-        // a strip legitimately waits for the strip above to get kPipeBlock + 72 columns ahead, behind every strip above that one: never
-        // less than ~10 us per such column and strip (0.2 us measured), however small the option or busy the device
-        sa.spin_limit = std::max<int64_t>(c->opt_spin_limit_ms, (static_cast<int64_t>(sfa::kPipeBlock + 72) * max_strips) / 100 + 1) * 100000;  // 100 MHz ticks
-        c->strips.strip_limit_ms = sa.spin_limit / 100000;
-        sa.debug_drop_strip = (c->opt_debug_drop_strip >= g0 && c->opt_debug_drop_strip < g0 + gn) ? static_cast<int32_t>(c->opt_debug_drop_strip - g0) : -1;
-        sfa::StripFinalizeArgs fa{};
-        fa.reads = sa.reads;
-        fa.p_best = sa.p_best;
-        fa.p_second = sa.p_second;
-        fa.p_end = sa.p_end;
-        fa.job_contig = c->model.d_job_contig.as<int32_t>();
-        fa.job_strand = c->model.d_job_strand.as<int8_t>();
-        fa.ref_len = c->model.d_ref_len.as<int32_t>();
-        fa.ref_st_offset = c->model.d_ref_off.as<int32_t>();
-        fa.w_job = win + g0;
-        fa.w_ws = win + n_long + g0;
-        fa.w_score = reinterpret_cast<float *>(win + 2 * static_cast<size_t>(n_long) + g0);
-        fa.t_st = sa.t_st;
-        fa.t_end = sa.t_end;
-        fa.out = d_out;
-        fa.bad = c->status.d_bad.as<uint8_t>();
-        fa.n_long = gn;
-        fa.n_jobs = n_jobs;
-        const dim3 block(256), fgrid((gn + 63) / 64), fblock(64);
-        const dim3 grid2((gn + 3) / 4);
-        {  // pass 1: one wave per (job, read, strip), tickets in that order
-            const int32_t *soff = reinterpret_cast<const int32_t *>(hs + o_soff) + g0 + gi;  // (uploaded with the staging area, before the loop)
-            sa.progress = reinterpret_cast<int32_t *>(c->strips.d_lprog.as<char>() + set * prog_bytes);
-            sa.ticket = c->strips.d_lticket.as<unsigned>() + set * 16;  // (words 8.. of a set's 64 bytes: where a dropped strip publishes, see strip_pipe_task)
-            HIP_TRY(hipMemsetAsync(sa.progress, 0, sizeof(int32_t) * static_cast<size_t>(gn) * n_jobs * max_strips, st));
-            HIP_TRY(hipMemsetAsync(sa.ticket, 0, 4, st));
-            sa.strip_off = reinterpret_cast<const int32_t *>(ds + o_soff) + g0 + gi;
-            const int64_t waves = static_cast<int64_t>(soff[gn]) * n_jobs;
-            const dim3 gridp(static_cast<unsigned>((waves + 3) / 4));
-#ifdef SFA_TASK_TIMES
-            if ((rc = c->times.d_ltimes.reserve(24 * static_cast<size_t>(waves)))) return rc;
-            sa.task_times = c->times.d_ltimes.as<unsigned long long>();
-            c->times.n_ltimes = waves;
-#endif
-            by_std(std_dtw, [&](auto S) { hipLaunchKernelGGL((sfa::sdtw_strip_pipe_kernel<S>), gridp, block, 0, st, sa); });
-        }
-        KERNEL_TRY();
-        fa.mode = 1;
-        hipLaunchKernelGGL(sfa::sdtw_strip_finalize_kernel, fgrid, fblock, 0, st, fa);
-        KERNEL_TRY();
-        // pass 2: strip by strip from the last one upwards
-        by_std(std_dtw, [&](auto S) { hipLaunchKernelGGL((sfa::sdtw_strip_chain_kernel<S>), grid2, block, 0, st, sa); });
-        KERNEL_TRY();
-        fa.mode = 2;
-        hipLaunchKernelGGL(sfa::sdtw_strip_finalize_kernel, fgrid, fblock, 0, st, fa);
-        KERNEL_TRY();
-        c->prof.fill_launches++;
+    for (int32_t gi = 0; gi < lp.n_groups; ++gi) {
+        const LongArgs a = long_args(c, lp, gi, d_queries, d_q_off, d_out);
+        if (int rc = enqueue_long_group(a, lp.strips_of(gi), (c->flag & SFA_DTW) != 0, lp.set(gi) ? c->stream_long2 : first)) return rc;
     }
-    if (two_sets) {  // whoever waits for `first` waits for both
+    if (lp.two_sets) {  // whoever waits for `first` waits for both
         HIP_TRY(hipEventRecord(c->lev[3], c->stream_long2));
         HIP_TRY(hipStreamWaitEvent(first, c->lev[3], 0));
     }
@@ -274,11 +257,6 @@ sfa::PlanParams plan_params(const sfa_ctx *c) {
     pp.lds_ckpt = c->opt_secondary > 0 ? 0 : static_cast<int>(c->opt_lds_ckpt);
     return pp;
 }
-
-struct LongReads {  // queries beyond the wave kernels' 2048 events: row strips, beside the rest of the batch
-    std::vector<int32_t> reads;
-    int64_t events = 0, max = 0;
-};
 
 // staging layout: q_off[n+1] (at 0) | order[4*n_quads] | quad_qlen[n_quads] | slot[n] | chunk_begin[n_chunks+1] | job_ck_off[n_jobs+1]
 struct Staging {
@@ -552,7 +530,7 @@ int enqueue_secondaries(sfa_ctx *c, Route route, const BatchArgs &a, hipStream_t
 
 // The batch on the context's stream: screen, row strips beside it, pass 1, pass 2, secondaries, the join and the error words;
 // then its profile
-int enqueue_batch(sfa_ctx *c, Route route, const BatchArgs &a, const int64_t *q_off, const LongReads &lr) {
+int enqueue_batch(sfa_ctx *c, Route route, const BatchArgs &a, const sfa::LongPlan &lp) {
     hipStream_t st = c->stream;
     const DpArgs &da = a.da;
     int rc;
@@ -566,26 +544,23 @@ int enqueue_batch(sfa_ctx *c, Route route, const BatchArgs &a, const int64_t *q_
     // Queries beyond 2048 events: row strips, on their own stream BESIDE the wave kernels of the shorter reads of the batch (a
     // handful of short reads is one sweep's latency on an empty chip: 6 + 2.5 ms in front of 110 ms of strips when run in a
     // row).  The two paths write disjoint rows (the finalize kernels here leave the long reads' rows alone).
-    int32_t long_launches = 0;
-    if (!lr.reads.empty()) {
+    if (!lp.reads.empty()) {
         hipStream_t ls = c->stream_long;
         HIP_TRY(hipEventRecord(c->lev[0], st));  // queries, offsets and the non-finite screen are ready
         HIP_TRY(hipStreamWaitEvent(ls, c->lev[0], 0));
-        c->prof.fill_launches = 0;  // (counted per group of long reads inside)
-        if ((rc = align_long(c, da.queries, da.q_off, q_off, lr.reads, lr.max, da.out, ls))) {
+        if ((rc = align_long(c, lp, da.queries, da.q_off, da.out, ls))) {
             (void)hipStreamSynchronize(ls);  // nothing of a failed call may still be running when the caller reuses its buffers
             (void)hipStreamSynchronize(c->stream_long2);
             return rc;
         }
-        long_launches = c->prof.fill_launches;
         HIP_TRY(hipEventRecord(c->lev[1], ls));
     }
     if ((rc = enqueue_pass1(c, route, a, st))) return rc;
     HIP_TRY(hipEventRecord(c->ev[1], st));
     if ((rc = enqueue_pass2(c, route, a, st))) return rc;
     if (c->opt_secondary > 0 && (rc = enqueue_secondaries(c, route, a, st))) return rc;
-    c->prof.fill_launches = (route != Route::NoQuads ? 1 : 0) + long_launches;
-    c->strips.long_pending = !lr.reads.empty();
+    c->prof.fill_launches = (route != Route::NoQuads ? 1 : 0) + lp.n_groups;  // (a pass-1 launch per group of long reads)
+    c->strips.long_pending = !lp.reads.empty();
     if (c->strips.long_pending) {  // join: what is left of the strips when the wave kernels are through counts as fill time
         HIP_TRY(hipEventRecord(c->ev[5], st));
         HIP_TRY(hipStreamWaitEvent(st, c->lev[1], 0));
@@ -594,7 +569,7 @@ int enqueue_batch(sfa_ctx *c, Route route, const BatchArgs &a, const int64_t *q_
     HIP_TRY(hipEventRecord(c->ev[4], st));
 
     const sfa::BatchPlan &plan = c->wave.plan;  // what resolve_profile() completes once the batch is through
-    c->prof.cells = (plan.query_events + lr.events) * c->model.total_cols;
+    c->prof.cells = (plan.query_events + lp.events) * c->model.total_cols;
     c->prof.ckpt_interval = plan.ck_shift ? (1 << plan.ck_shift) : 0;
     c->prof.ckpt_bytes = static_cast<int64_t>(sizeof(float)) * plan.ck_floats;
     c->prof.lds_ckpt = route == Route::LdsFused ? 2 : (route == Route::Lds ? 1 : 0);
@@ -627,15 +602,10 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
         if (int rc = c->sec.reserve_rows(static_cast<size_t>(n))) return rc;
         d_sec = c->sec.d_sec.as<ResultRow>();
     }
-    LongReads lr;
-    for (int32_t i = 0; i < n; ++i)
-        if (q_off[i + 1] - q_off[i] > sfa::kMaxQuery) {
-            lr.reads.push_back(i);
-            lr.events += q_off[i + 1] - q_off[i];
-            lr.max = std::max<int64_t>(lr.max, q_off[i + 1] - q_off[i]);
-        }
+    // queries beyond the wave kernels' 2048 events: row strips, beside the rest of the batch
+    const sfa::LongPlan lp = sfa::plan_long_reads(q_off, n, c->model.h_job_len, c->opt_ckpt_interval, c->opt_ckpt_budget, c->cu_count, c->opt_spin_limit_ms);
     sfa::PlanParams pp = plan_params(c);
-    pp.skip_long = !lr.reads.empty();
+    pp.skip_long = !lp.reads.empty();
     sfa::BatchPlan &plan = c->wave.plan;  // kept with the context: its vectors are reused by every batch
     std::string perr;
     if (int rc = sfa::plan_batch(q_off, n, c->model.h_job_len, c->model.total_cols, pp, &plan, &perr)) return fail(rc, "%s", perr.c_str());
@@ -654,8 +624,8 @@ int sfa::align_device(sfa_ctx *c, const float *d_queries, const int64_t *q_off, 
     int rc;
     if ((rc = stage_and_reserve(c, q_off, n, route, sg))) return rc;
     HIP_TRY(hipMemcpyAsync(c->wave.d_stage.p, c->wave.h_stage.p, sg.bytes, hipMemcpyHostToDevice, c->stream));
-    const BatchArgs a = batch_args(c, d_queries, n, d_out, d_sec, route, sg, !lr.reads.empty());
-    if ((rc = enqueue_batch(c, route, a, q_off, lr))) return rc;
+    const BatchArgs a = batch_args(c, d_queries, n, d_out, d_sec, route, sg, !lp.reads.empty());
+    if ((rc = enqueue_batch(c, route, a, lp))) return rc;
     if (route == Route::Segments) {
         // the verdict of the hand-over checks has to be known before anybody uses the rows: wait here (these are the small,
         // latency-bound batches -- their caller is about to wait for them anyway)

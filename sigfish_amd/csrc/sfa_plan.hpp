@@ -11,6 +11,8 @@
 //   * the (contig,strand) job list is cut into contiguous chunks of similar size when there are too few quads
 //     to fill the chip; a wave-task is (quad, chunk);
 //   * the checkpoint interval T of pass 1 is the smallest power of two >= 512 whose checkpoints fit the budget.
+// Behind it: the route of a batch (choose_route), the slices of the event maps (plan_map_slices*), and the geometry and plan of
+// the row strips for queries beyond kMaxQuery events (plan_long_reads).
 #pragma once
 
 #include <algorithm>
@@ -430,6 +432,123 @@ inline MapSlices plan_map_slices_strips(const int32_t *qlen, const int32_t *m, i
     }
     if (static_cast<int32_t>(s.order.size()) > s.slice_begin.back()) s.slice_begin.push_back(static_cast<int32_t>(s.order.size()));
     return s;
+}
+
+// ---- queries of more than kMaxQuery events: row strips (sdtw_strips.hpp).  Their geometry and the plan of a batch's long reads ----
+
+constexpr int kStripR = 32;                 // query rows per lane, at most
+constexpr int kStripRows = 64 * kStripR;    // query rows per strip, at most: a query has ceil(qlen / 2048) strips
+constexpr int kCkRec = (kStripR + 1) * 64;  // floats per checkpoint record: a plane of 64 lanes per row of a lane (up to 32) and the plane of the diagonal inputs
+constexpr int kBndPad = 256;                // words behind every boundary row (block over-run of the sweep + prefetch)
+#ifndef SFA_PIPE_BLOCK
+#define SFA_PIPE_BLOCK 256
+#endif
+constexpr int kPipeBlock = SFA_PIPE_BLOCK;  // columns between two hand-overs of a boundary row (one release / acquire pair each)
+static_assert(kStripRows == kMaxQuery, "a strip holds what the wave kernels hold of a query");
+
+// staging layout: reads[n_long] (at 0) | bnd_off[n_jobs+1] | ck_off[n_jobs+1] | strip_off[2*n_long+2] (room for n_long groups of one read)
+struct LongStaging {
+    size_t reads = 0, bnd, ck, soff, bytes;
+    LongStaging(int32_t n_long, int32_t n_jobs) {
+        bnd = (sizeof(int32_t) * n_long + 7) & ~size_t(7);
+        ck = bnd + sizeof(int64_t) * (n_jobs + 1);
+        soff = ck + sizeof(int64_t) * (n_jobs + 1);
+        bytes = soff + sizeof(int32_t) * (2 * static_cast<size_t>(n_long) + 2);
+    }
+};
+
+// Everything the driver of the row strips (sfa_align.hip: stage_long, long_args, enqueue_long_group) needs of a batch.  The reads
+// are taken in groups of `group` consecutive long reads, group gi holding reads begin(gi) ... begin(gi) + size(gi) - 1 of `reads`.
+struct LongPlan {
+    std::vector<int32_t> reads, n_strips;  // [n_long] batch index and strip count of every long read, input order
+    int64_t events = 0, max = 0;           // events of all long reads, of the longest one
+    int32_t max_strips = 0;                // strips of the longest one
+    std::vector<int64_t> bnd_off;          // [n_jobs+1] word offset of job j's boundary row (multiples of 4): rows of job_len + kBndPad words
+    int64_t cost_rows = 0, bnd_stride = 0; // boundary rows of a read and job (one per strip boundary), floats between two reads' boundary rows
+    int32_t ck_shift = 0;                  // checkpoints every 1 << ck_shift steps
+    std::vector<int64_t> ck_off;           // [n_jobs+1] prefix sum of max_strips * ((job_len - 1) >> ck_shift): the records of one read
+    int32_t group = 0, n_groups = 0;
+    bool two_sets = false;                 // two sets of scratch on two streams, the groups alternating between them
+    std::vector<int32_t> strip_off;        // prefix sums of the strip counts, group by group: group gi at words off_word(gi) ... + size(gi)
+    LongStaging sg{0, 0};
+    size_t prog_bytes = 0, bndc_floats = 0, lck_floats = 0;  // scratch of ONE set: progress words, boundary rows, checkpoints
+    size_t n_part = 0;                                       // (read, job) pairs of all groups
+    int64_t limit_ms = 0;                                    // the bounded wait of a strip for the strip above
+
+    int32_t n_long() const { return static_cast<int32_t>(reads.size()); }
+    int32_t begin(int32_t gi) const { return gi * group; }
+    int32_t size(int32_t gi) const { return std::min(group, n_long() - begin(gi)); }
+    int set(int32_t gi) const { return two_sets ? (gi & 1) : 0; }  // groups of one set run on one stream: its scratch is free when the next one starts
+    int32_t off_word(int32_t gi) const { return begin(gi) + gi; }
+    int32_t strips_of(int32_t gi) const { return strip_off[off_word(gi) + size(gi)]; }
+};
+
+// checkpoints: every strip of every job, every T steps, 33 planes of 64 lanes; T = 512 (or the option's: a power of two >= 4)
+// unless that takes more than the budget for the whole set of long reads, 16 384 at most
+inline void plan_long_checkpoints(const std::vector<int32_t> &job_len, int64_t ckpt_interval, int64_t ckpt_budget_bytes, LongPlan *p) {
+    const int32_t n_jobs = static_cast<int32_t>(job_len.size());
+    p->ck_off.assign(n_jobs + 1, 0);
+    p->ck_shift = ckpt_interval > 0 ? 2 : 9;
+    while (ckpt_interval > 0 && (1ll << p->ck_shift) < ckpt_interval) ++p->ck_shift;
+    for (;; ++p->ck_shift) {
+        for (int32_t j = 0; j < n_jobs; ++j) p->ck_off[j + 1] = p->ck_off[j] + static_cast<int64_t>(p->max_strips) * ((job_len[j] - 1) >> p->ck_shift);
+        if (ckpt_interval > 0 || p->ck_off[n_jobs] * kCkRec * 4 * p->n_long() <= ckpt_budget_bytes || p->ck_shift >= 14) return;
+    }
+}
+
+// Groups whose boundary rows and checkpoints fit the budget in two sets of scratch; two groups at least when each still has two
+// rounds of the device's wave slots (16 per CU) to fill the chip with its pipeline of strips.  Then the scratch of a set, and every
+// group's prefix sums in words of its own: one upload for all groups, no host wait between them.
+inline void plan_long_groups(int32_t n_jobs, int64_t ckpt_budget_bytes, int64_t cu_count, LongPlan *p) {
+    const int32_t n_long = p->n_long();
+    const int64_t ck_floats_per_read = p->ck_off[n_jobs] * kCkRec;
+    const int64_t bytes_per_read = p->bnd_stride * 4 + ck_floats_per_read * 4;
+    int64_t waves_total = 0;
+    for (int32_t s : p->n_strips) waves_total += static_cast<int64_t>(s) * n_jobs;
+    const int64_t want_groups = waves_total >= 4 * 16 * cu_count ? 2 : 1;
+    const int64_t by_budget = ckpt_budget_bytes / (2 * std::max<int64_t>(bytes_per_read, 1));
+    p->group = static_cast<int32_t>(std::max<int64_t>(1, std::min<int64_t>((n_long + want_groups - 1) / want_groups, by_budget)));
+    p->n_groups = (n_long + p->group - 1) / p->group;
+    p->two_sets = p->group < n_long;
+    p->prog_bytes = sizeof(int32_t) * static_cast<size_t>(p->group) * n_jobs * p->max_strips;
+    p->bndc_floats = static_cast<size_t>(p->bnd_stride) * p->group;
+    p->lck_floats = static_cast<size_t>(std::max<int64_t>(ck_floats_per_read, 1)) * p->group;
+    p->n_part = static_cast<size_t>(n_long) * n_jobs;
+    p->strip_off.assign(2 * static_cast<size_t>(n_long) + 2, 0);
+    for (int32_t gi = 0; gi < p->n_groups; ++gi) {
+        int32_t *so = p->strip_off.data() + p->off_word(gi);
+        for (int32_t i = 0; i < p->size(gi); ++i) so[i + 1] = so[i] + p->n_strips[p->begin(gi) + i];
+    }
+}
+
+// The long reads of a batch (q_off[0..n], more than kMaxQuery events) against jobs of job_len columns; the options "ckpt_interval",
+// "ckpt_budget_bytes" and "spin_limit_ms", the device's compute units.  A batch without long reads: reads is empty, nothing else set.
+inline LongPlan plan_long_reads(const int64_t *q_off, int32_t n, const std::vector<int32_t> &job_len, int64_t ckpt_interval, int64_t ckpt_budget_bytes,
+                                int64_t cu_count, int64_t spin_limit_ms) {
+    LongPlan p;
+    for (int32_t i = 0; i < n; ++i) {
+        const int64_t l = q_off[i + 1] - q_off[i];
+        if (l <= kMaxQuery) continue;
+        p.reads.push_back(i);
+        p.n_strips.push_back(static_cast<int32_t>((l + kStripRows - 1) / kStripRows));
+        p.events += l;
+        p.max = std::max(p.max, l);
+    }
+    if (p.reads.empty()) return p;
+    const int32_t n_jobs = static_cast<int32_t>(job_len.size());
+    p.max_strips = static_cast<int32_t>((p.max + kStripRows - 1) / kStripRows);
+    p.bnd_off.assign(n_jobs + 1, 0);
+    for (int32_t j = 0; j < n_jobs; ++j) p.bnd_off[j + 1] = p.bnd_off[j] + ((static_cast<int64_t>(job_len[j]) + kBndPad + 3) & ~int64_t(3));
+    // cost rows of every job, one per strip boundary (pass 1 writes them, pass 2 reads them)
+    p.cost_rows = std::max<int64_t>(1, p.max_strips - 1);
+    p.bnd_stride = p.cost_rows * p.bnd_off[n_jobs];
+    plan_long_checkpoints(job_len, ckpt_interval, ckpt_budget_bytes, &p);
+    plan_long_groups(n_jobs, ckpt_budget_bytes, cu_count, &p);
+    p.sg = LongStaging(p.n_long(), n_jobs);
+    // a strip legitimately waits for the strip above to get kPipeBlock + 72 columns ahead, behind every strip above that one: never
+    // less than ~10 us per such column and strip (0.2 us measured), however small the option or busy the device
+    p.limit_ms = std::max<int64_t>(spin_limit_ms, (static_cast<int64_t>(kPipeBlock + 72) * p.max_strips) / 100 + 1);
+    return p;
 }
 
 }  // namespace sfa
