@@ -173,7 +173,9 @@ int sfa_wait_batch(sfa_ctx_t *ctx, sfa_result_t *out, int32_t n_reads);
  * candidate ranks higher), of the most recently completed call (a synchronous call or sfa_wait_batch; call this before the next
  * batch is submitted).  sec[i*4+k], k = 0 the best secondary: rid, strand, pos_st/pos_end (flipped and offset as the primary),
  * score, score2 = the score of the next candidate below it (+inf for the last), mapq 0.  Slots beyond the option, slots whose
- * score is not finite, and every slot of a read of more than SFA_MAX_QUERY events (the row strips keep no list), have valid = 0.
+ * score is not finite, and -- unless the option "secondary_strips" is 1 -- every slot of a read of more than SFA_MAX_QUERY events
+ * have valid = 0.  With "secondary_strips" the row strips keep such a read's list as well: its slots are filled by the same rule,
+ * through every entry point, and sfa_event_maps takes its rows like any others.
  * No de-duplication: neighbouring windows of one locus often fill the list.  Returns SFA_EINVAL when the option is 0. */
 int sfa_secondary_rows(sfa_ctx_t *ctx, sfa_result_t *sec, int32_t n_reads);
 
@@ -509,6 +511,10 @@ int sfa_align_events(sfa_ctx_t *ctx, const sfa_event_t *const *events, const int
  *   output
  *     "secondary"             0..4 (default 0): secondary mappings per read, returned by sfa_secondary_rows; > 0 takes the plain
  *                             two-pass route (HBM snapshots, no column segments, pass 2 as its own launches).  Rows do not change
+ *     "secondary_strips"      0 (default) or 1, with an effect only while "secondary" is 1..4: reads of more than SFA_MAX_QUERY events
+ *                             have secondaries too.  Pass 1 of the row strips then runs as a kernel of its own that keeps each (read,
+ *                             contig, strand)'s list of its 5 best windows, a merge ranks them, and pass 2 runs once more per rank.
+ *                             Primaries do not change; 0 launches what it always did and leaves those reads' slots at valid = 0
  *     "map_scratch_bytes"     HBM the packed moves of one slice of rows may take in sfa_event_maps (default 2 GiB); rows are processed in
  *                             slices that fit, a row that does not fit alone goes to the host routine
  *     "map_strips"            0 (default) or 1: sfa_event_maps and sfa_session_event_maps run a row of more than SFA_MAX_QUERY events on

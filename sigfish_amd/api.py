@@ -308,11 +308,13 @@ class Aligner:
         _check(self._L.sfa_set_option(self._h, key.encode(), int(value)), f"sfa_set_option({key})")
 
     def set_secondary(self, n):
-        """Secondary mappings per read, 0..4 (0: off, the default); read them with secondary_rows() after each call."""
+        """Secondary mappings per read, 0..4 (0: off, the default); read them with secondary_rows() after each call.  Reads of more
+        than 2048 events have none unless set_option("secondary_strips", 1) is in force as well."""
         self.set_option("secondary", n)
 
     def secondary_rows(self, n_reads=None):
-        """The secondaries of the most recent call as RESULT_DTYPE[n_reads, 4], best first (valid = 0 for absent slots)."""
+        """The secondaries of the most recent call as RESULT_DTYPE[n_reads, 4], best first (valid = 0 for absent slots, and for every
+        slot of a read of more than 2048 events unless set_option("secondary_strips", 1) was in force for that call)."""
         n = self._last_n if n_reads is None else int(n_reads)
         out = np.zeros((n, 4), RESULT_DTYPE)
         _check(self._L.sfa_secondary_rows(self._h, out.ctypes.data_as(C.c_void_p), n), "sfa_secondary_rows")

@@ -38,6 +38,7 @@ struct Opt {
     bool device_paths = false;  // --device-paths: SAM from the event maps of a whole batch, computed on the GPU (sfa_event_maps); --host-paths
                                 // (the default until the device route has been measured): warp paths rebuilt read by read on the host threads
     bool secondary = false;  // --secondary yes: print the candidates behind each primary (sfa_secondary_rows)
+    bool secondary_strips = false;  // --secondary-strips: ... also for reads beyond 2048 events (the option "secondary_strips"; lifts the refusal of -q > 2048)
     const char *fasta = nullptr, *blow5 = nullptr;  // the two positional arguments
 };
 

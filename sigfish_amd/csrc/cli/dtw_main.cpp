@@ -60,6 +60,7 @@ void open_contexts(Contexts &ctxs, const Opt &o, const Reference &ref) {
         // the pore reaches the device route's automatic query start (-p -1), as it reaches select_and_normalise on the host route
         if (sfa_set_pore(ctxs[j], o.pore_flag) != SFA_OK) die(sfa_last_error());
         if (o.secondary && sfa_set_option(ctxs[j], "secondary", 4) != SFA_OK) die(sfa_last_error());
+        if (o.secondary_strips && sfa_set_option(ctxs[j], "secondary_strips", 1) != SFA_OK) die(sfa_last_error());
         // --sam --device-paths: queries beyond 2048 events (-q) keep their event maps on the device too, in row strips
         if (o.device_paths && sfa_set_option(ctxs[j], "map_strips", 1) != SFA_OK) die(sfa_last_error());
         for (const auto &nv : from_env)

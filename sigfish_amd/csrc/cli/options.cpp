@@ -19,7 +19,7 @@ enum LongOpt {
     O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
     O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
     O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE,
-    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES
+    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS
 };
 
 const option kLongOptions[] = {
@@ -35,7 +35,7 @@ const option kLongOptions[] = {
     {"gpu-parse", no_argument, 0, O_GPU_PARSE}, {"ranks", required_argument, 0, O_RANKS}, {"shard", required_argument, 0, O_SHARD},
     {"read-range", required_argument, 0, O_READ_RANGE}, {"no-header", no_argument, 0, O_NO_HEADER},
     {"rank-buffer", required_argument, 0, O_RANK_BUFFER}, {"host-paths", no_argument, 0, O_HOST_PATHS},
-    {"device-paths", no_argument, 0, O_DEVICE_PATHS},
+    {"device-paths", no_argument, 0, O_DEVICE_PATHS}, {"secondary-strips", no_argument, 0, O_SECONDARY_STRIPS},
     {0, 0, 0, 0}};
 
 bool yes_or_no(const char *arg, const char *what) {  // yes_or_no(), src/dtw_main.c:92-113
@@ -84,6 +84,8 @@ void help(FILE *fp, const Opt &o) {
     fprintf(fp, "   --sam                      output in SAM format\n");
     fprintf(fp, "   --device-paths | --host-paths  with --sam: warp paths of a whole batch on the GPU | read by read on the host threads [host threads]\n");
     fprintf(fp, "   --secondary STR            print secondary mappings. yes or no [no]\n");
+    fprintf(fp, "   --secondary-strips         with --secondary yes: secondary mappings also for -q beyond 2048 events, whose reads run in row\n"
+                "                              strips (the library's option \"secondary_strips\"); without it such a -q is refused [off]\n");
     fprintf(fp, "   --profile-cpu=yes|no       run the stages one after the other and report Parse/Events/Normalise/DTW time [no]\n");
     fprintf(fp, "   --accel=yes|no             run the alignment on the accelerator [yes]; 'no' is an error: this build has no CPU path\n");
 }
@@ -303,6 +305,7 @@ Opt parse_options(int argc, char **argv) {
                 break;
             case O_DEVICE: parse_device_list(optarg, &o.devices); break;
             case O_HOST_EVENTS: o.host_events = true; break;
+            case O_SECONDARY_STRIPS: o.secondary_strips = true; break;
             case O_HOST_PATHS: case O_DEVICE_PATHS: o.device_paths = c == O_DEVICE_PATHS; break;
             case O_HOST_PARSE: case O_GPU_PARSE: o.gpu_parse = c == O_GPU_PARSE; break;
             case O_RANKS: o.ranks = atoi(optarg); if (o.ranks < 1 || o.ranks > 64) die("--ranks should be 1..64"); break;
@@ -344,7 +347,8 @@ Opt parse_options(int argc, char **argv) {
     }
 
     if (o.shard_n > 1 && (o.range_a > 0 || o.range_b >= 0)) die("--shard and --read-range exclude each other");
-    if (o.secondary && o.query > 2048) die("--secondary yes supports -q up to 2048");
+    if (o.secondary_strips && !o.secondary) die("--secondary-strips needs --secondary yes");
+    if (o.secondary && o.query > 2048 && !o.secondary_strips) die("--secondary yes supports -q up to 2048");
     if (o.ranks == 0) {  // one process per DISTINCT device of the list; a device listed twice is two contexts of one process
         std::vector<int> d = o.devices;
         std::sort(d.begin(), d.end());

@@ -1684,7 +1684,8 @@ struct SecArgs {
     const int32_t *p_top5;        // DpArgs::p_top5
     const uint8_t *bad;
     const int64_t *q_off;
-    int32_t max_query;            // as FinalizeArgs: longer reads are the row strips' (no secondaries)
+    int32_t max_query;            // as FinalizeArgs: longer reads are the row strips'.  Their rows are written valid = 0 here; with the option
+                                  // "secondary_strips" the strips' own finalize (sdtw_strips.hpp) writes them again behind this kernel
     int32_t n_reads, n_chunks;
     int32_t *s_job;               // [5][n_reads] candidate k = the reference's aln[4 - k]; k = 0 is the primary; -1: none
     int32_t *s_end;               // as DpArgs::w_end

@@ -31,6 +31,7 @@
 
 namespace sfa {
 
+static_assert(kSecListWords == kTop5Words, "the planner sizes the strips' candidate lists");
 constexpr int kCkDprev = kStripR * 64;      // where a checkpoint record (kCkRec floats) keeps the plane of the diagonal inputs
 
 // BALANCED STRIPS.  The strips of a query all have the same height, 64 lanes x R rows with the smallest R of {20, 24, 28, 32}
@@ -146,14 +147,17 @@ struct StripResult {
 
 // One strip over columns [0, ncols) of one (contig,strand).  LAST: the strip holds the last query row (lane lq,
 // register rq) -- in pass 2 (TRACK) always: the row of the cell to reach.  Pass 2: column ws is the cell to reach, `best` its cost.
-template <bool STD, bool FIRST, bool TRACK, bool LAST, int R, typename XT>
+// SEC (pass 1, final strip): every window's (wmin, wpos, job) is also offered to the candidate list t5 of secondary mappings, 5 x (score
+// bits, end, job) in LDS (top5_offer, sdtw_kernels.hpp), by the lane that holds the last query row, where the window ends.
+template <bool STD, bool FIRST, bool TRACK, bool LAST, int R, bool SEC = false, typename XT>
 __device__ __forceinline__ void strip_sweep(const float *yp, const int rlen, const int ncols, const int qlen,
                                             const XT &x, const int lq, const int rq, const int lane, Exchange &xc,
                                             const float *bin_c, float *bout_c, StripResult &res,
                                             const int job, const int ws, const float best, const int t_begin, float *ckp,
                                             const int ck_shift, const int nck, const int32_t *prog_in = nullptr, int32_t *prog_out = nullptr,
-                                            unsigned *err = nullptr, const long long spin_limit = 0) {
+                                            unsigned *err = nullptr, const long long spin_limit = 0, int *t5 = nullptr) {
     static_assert(!TRACK || LAST, "pass 2 sweeps a strip up to a cell of its last row");
+    static_assert(!SEC || (LAST && !TRACK), "the candidate list is kept where the windows are scanned: pass 1, final strip");
     constexpr bool PIPE = !TRACK;  // pass 1 is pipelined: strips of one (read, job) follow each other through HBM
     // PIPE, prog_in / prog_out: how far the strip above has got with the row this sweep reads / where to say
     // how far this sweep has got with the row it writes.  Both wave-uniform.  Pass 2: the rows are complete / nobody is waiting.
@@ -283,13 +287,23 @@ __device__ __forceinline__ void strip_sweep(const float *yp, const int rlen, con
                     wmin = lt ? cv : wmin;
                     wpos = lt ? col : wpos;
                     if (__builtin_expect(col + 1 == wend, 0)) {  // (wend <= ncols: never outside)
-                        res.top.offer(wmin, wpos, job);
+                        if constexpr (SEC) {  // (the list's two best entries ARE the top-2: strip_pipe_task reads them there)
+                            // lane lq's window, wave-uniform: the insertion then runs on uniform values and addresses, every lane
+                            // writing the same words (no exec mask, no divergent temporaries: the sweep is at its 128 VGPRs)
+                            top5_offer(t5, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wmin), lq)), __builtin_amdgcn_readlane(wpos, lq), job);
+                        } else {
+                            res.top.offer(wmin, wpos, job);
+                        }
                         wmin = INFINITY;
                         wpos = -1;
                         wend = min(wend + qlen, rlen);
                     }
                 } else if (__builtin_expect(col == rlen - 1, 0)) {
-                    res.top.offer(cl, col, job);
+                    if constexpr (SEC) {
+                        top5_offer(t5, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cl), lq)), col, job);
+                    } else {
+                        res.top.offer(cl, col, job);
+                    }
                 }
             }
         }
@@ -342,10 +356,11 @@ __device__ __forceinline__ void strip_rows(const StripArgs &a, const StripRead &
 // columns behind, reading the boundary row strip s writes (one row per strip boundary).  Waves claim tickets in the order job,
 // read, strip: a strip's predecessor always holds a lower ticket, i.e. is running or done whenever the strip waits for it -- no
 // deadlock whatever order the hardware starts blocks in.  Every strip drops its checkpoints, the final strip scans the windows
-// and leaves the partial top-2 of its (read, job).
-template <bool STD, int R>
+// and leaves the partial top-2 of its (read, job) -- with SEC also its candidate list (t5: this wave's 15 words of LDS), which lane
+// lq writes to p_top5[(read, job)] beside the top-2.
+template <bool STD, int R, bool SEC = false>
 __device__ __forceinline__ void strip_pipe_task(const StripArgs &a, const StripRead &rd, const int li, const int job, const int sidx, const int lane,
-                                                Exchange &xc) {
+                                                Exchange &xc, int *t5 = nullptr, int32_t *p_top5 = nullptr) {
     const int qlen = rd.qlen;
     const int rlen = a.job_len[job];
     const float *yp = a.ref + a.job_off[job] - lane;
@@ -364,6 +379,9 @@ __device__ __forceinline__ void strip_pipe_task(const StripArgs &a, const StripR
     res.top.init();
     res.cap_end = -1;
     res.cap_st = -1;
+    if constexpr (SEC) {
+        if (last) top5_init(t5);  // (every lane the same words: the list is the wave's, see strip_sweep)
+    }
     float *bout_c = last ? nullptr : rows + static_cast<int64_t>(sidx) * per;
     const float *bin_c = sidx > 0 ? rows + static_cast<int64_t>(sidx - 1) * per : nullptr;
     if (sidx == 0) {  // (queries of this path have more than one strip: the first is never the last)
@@ -375,13 +393,22 @@ __device__ __forceinline__ void strip_pipe_task(const StripArgs &a, const StripR
         strip_sweep<STD, false, false, false, R>(yp, rlen, rlen, qlen, x, lq, rq, lane, xc, bin_c, bout_c, res, job, 0, 0.0f, 0, ckp, a.ck_shift, nck,
                                                  prog + sidx - 1, prog + sidx, a.err, a.spin_limit);
     else
-        strip_sweep<STD, false, false, true, R>(yp, rlen, rlen, qlen, x, lq, rq, lane, xc, bin_c, nullptr, res, job, 0, 0.0f, 0, ckp, a.ck_shift, nck,
-                                                prog + sidx - 1, nullptr, a.err, a.spin_limit);
+        strip_sweep<STD, false, false, true, R, SEC>(yp, rlen, rlen, qlen, x, lq, rq, lane, xc, bin_c, nullptr, res, job, 0, 0.0f, 0, ckp, a.ck_shift, nck,
+                                                     prog + sidx - 1, nullptr, a.err, a.spin_limit, t5);
     if (last && lane == lq) {
         const int64_t o = static_cast<int64_t>(li) * a.n_jobs + job;
-        a.p_best[o] = res.top.best;
-        a.p_second[o] = res.top.second;
-        a.p_end[o] = res.top.end;
+        if constexpr (SEC) {
+            // The sweep kept no Top2 beside the list (four VGPRs the 32-row sweep does not have): aln[4] and aln[3] of the list are
+            // what Top2 holds -- the same candidates went through the same insertion rule, a later one in front of its equals.
+            a.p_best[o] = __int_as_float(t5[12]);
+            a.p_second[o] = __int_as_float(t5[9]);
+            a.p_end[o] = t5[13];
+            for (int w = 0; w < kTop5Words; ++w) p_top5[o * kTop5Words + w] = t5[w];
+        } else {
+            a.p_best[o] = res.top.best;
+            a.p_second[o] = res.top.second;
+            a.p_end[o] = res.top.end;
+        }
     }
 }
 
@@ -419,6 +446,44 @@ __global__ void __launch_bounds__(256, 4) sdtw_strip_pipe_kernel(const StripArgs
         a.task_times[3 * static_cast<int64_t>(task) + 2] = simd_position() | (static_cast<unsigned long long>(sidx) << 32);
     }
 #endif
+}
+
+// Pass 1 with the candidate lists of secondary mappings ("secondary_strips"): the same waves, tickets and hand-overs; the final
+// strip of every (read, job) also keeps the list of its 5 best windows and leaves it in p_top5, [n_long][n_jobs][kTop5Words].  Its
+// own kernel with its own copy of the body, so the one above keeps its code to the instruction (sharing the body through a helper
+// changed its schedule); the strips above the final one run the same sweeps in both.
+template <bool STD>
+__global__ void __launch_bounds__(256, 4) sdtw_strip_sec_pipe_kernel(const StripArgs a, int32_t *p_top5) {
+    const int lane = threadIdx.x & 63;
+    unsigned t = 0;
+    if (lane == 0) t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int task = __builtin_amdgcn_readfirstlane(t);
+    const int total = a.strip_off[a.n_long];
+    if (task >= total * a.n_jobs) return;
+    const int job = task / total;
+    const int r = task - job * total;
+    int lo = 0, hi = a.n_long;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (a.strip_off[mid] <= r)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const int li = lo, sidx = r - a.strip_off[li];
+    __shared__ float lds_f[4 * kXchWordsPerWave];
+    __shared__ int lds_i[1];
+    __shared__ int lds_t5[4 * kTop5Words];  // in LDS, as in sdtw_sec_fill_kernel: the sweep has no VGPRs to spare at four waves per SIMD
+    int *t5 = lds_t5 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * kTop5Words;  // (wave-uniform: the address stays out of the VGPRs)
+    Exchange xc;
+    xc.init(lds_f, lds_i, threadIdx.x >> 6, 0, lane, 64);
+    const StripRead rd = strip_read(a, li);
+    switch (strip_rows_per_lane(rd.qlen)) {
+        case 20: strip_pipe_task<STD, 20, true>(a, rd, li, job, sidx, lane, xc, t5, p_top5); break;
+        case 24: strip_pipe_task<STD, 24, true>(a, rd, li, job, sidx, lane, xc, t5, p_top5); break;
+        case 28: strip_pipe_task<STD, 28, true>(a, rd, li, job, sidx, lane, xc, t5, p_top5); break;
+        default: strip_pipe_task<STD, 32, true>(a, rd, li, job, sidx, lane, xc, t5, p_top5); break;
+    }
 }
 
 // Pass 2 (one wave per long read, its winning job): the strips are traced from the LAST one upwards, each over its own
@@ -515,7 +580,9 @@ __global__ void __launch_bounds__(256, 1) sdtw_strip_chain_kernel(const StripArg
     SFA_STRIP_DISPATCH(strip_chain_task, rd.qlen, a, rd, li, job, lane, xc)
 }
 
-// instantiated in sdtw_inst_strips_pipe.hip / sdtw_inst_strips_chain.hip
+// instantiated in sdtw_inst_strips_pipe.hip / sdtw_inst_strips_chain.hip / sdtw_inst_strips_pipe_sec.hip
+extern template __global__ void sdtw_strip_sec_pipe_kernel<false>(const StripArgs, int32_t *);
+extern template __global__ void sdtw_strip_sec_pipe_kernel<true>(const StripArgs, int32_t *);
 extern template __global__ void sdtw_strip_chain_kernel<false>(const StripArgs);
 extern template __global__ void sdtw_strip_chain_kernel<true>(const StripArgs);
 extern template __global__ void sdtw_strip_pipe_kernel<false>(const StripArgs);
@@ -586,6 +653,80 @@ __global__ void __launch_bounds__(64) sdtw_strip_finalize_kernel(const StripFina
     a.w_ws[li] = ws;
     a.w_score[li] = best;
     a.out[a.reads[li]] = r;
+}
+#endif
+
+// Secondary mappings of the long reads, around the pass-2 launches of ranks 1..n_sec (sfa_align.hip): the strip-side twin of
+// sdtw_sec_finalize_kernel.  The rank arrays are [kSecRanks][n_total] over the long reads of the whole batch; a launch covers n_long
+// of them, from the one the pointers are set to.
+struct StripSecArgs {
+    const int32_t *reads;    // [n_long] batch index
+    const int32_t *p_top5;   // [n_long][n_jobs][kTop5Words] (sdtw_strip_sec_pipe_kernel)
+    const uint8_t *bad;      // [reads of the batch]
+    int32_t *s_job, *s_ws;   // rank k of long read li at [k * n_total + li]: the reference's aln[4 - k]; k = 0 is the primary; -1: none
+    float *s_score;
+    int32_t *t_st, *t_end;   // columns traced for rank k (k >= 1) by its pass-2 launch, -1 where nothing was: mode 2 reads them
+    const int32_t *job_contig;
+    const int8_t *job_strand;
+    const int32_t *ref_len, *ref_st_offset;
+    ResultRow *sec;          // [reads of the batch][4] secondaries, best first
+    int32_t n_long, n_total, n_jobs;
+    int32_t n_sec;           // secondaries asked for (1..4): rows of the ranks behind are valid = 0
+    int32_t mode;            // 1: after pass 1 -> the ranks; 2: after pass 2 of every rank -> rows
+};
+
+#ifdef SFA_DEFINE_FINALIZE_KERNEL
+__global__ void __launch_bounds__(64) sdtw_strip_sec_finalize_kernel(const StripSecArgs a) {
+    const int li = blockIdx.x * blockDim.x + threadIdx.x;
+    if (li >= a.n_long) return;
+    const int read = a.reads[li];
+    const int n = a.n_total;
+    const bool on = !a.bad[read];
+    if (a.mode == 1) {  // the jobs' lists in processing order, each in its own offer order (worst first): update_aln over all windows
+        float sc[5];
+        int en[5], jb[5];
+#pragma unroll
+        for (int m = 0; m < 5; ++m) {
+            sc[m] = INFINITY;
+            en[m] = -1;
+            jb[m] = -1;
+        }
+        for (int j = 0; on && j < a.n_jobs; ++j) {
+            const int32_t *t = a.p_top5 + (static_cast<int64_t>(li) * a.n_jobs + j) * kTop5Words;
+            for (int e = 0; e < 5; ++e)
+                if (t[3 * e + 2] >= 0) top5_offer_regs(sc, en, jb, __int_as_float(t[3 * e]), t[3 * e + 1], t[3 * e + 2]);
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const bool ok = jb[4 - k] >= 0 && isfinite(sc[4 - k]);
+            a.s_job[k * n + li] = ok ? jb[4 - k] : -1;
+            a.s_ws[k * n + li] = ok ? en[4 - k] : -1;
+            a.s_score[k * n + li] = sc[4 - k];
+        }
+        return;
+    }
+    for (int k = 1; k < 5; ++k) {  // the rows, as sdtw_sec_finalize_kernel writes them
+        ResultRow r;
+        r.rid = -1;
+        r.pos_st = -1;
+        r.pos_end = -1;
+        r.score = INFINITY;
+        r.score2 = INFINITY;
+        r.strand = 0;
+        r.mapq = 0;
+        r.valid = 0;
+        r.pad = 0;
+        const int job = (on && k <= a.n_sec) ? a.s_job[k * n + li] : -1;
+        if (job >= 0) {
+            r.valid = 1;
+            r.rid = a.job_contig[job];
+            r.strand = a.job_strand[job];
+            r.score = a.s_score[k * n + li];
+            r.score2 = k < 4 ? a.s_score[(k + 1) * n + li] : INFINITY;
+            place_row(r, a.t_st[k * n + li], a.t_end[k * n + li], a.ref_len[r.rid], a.ref_st_offset[r.rid]);
+        }
+        a.sec[static_cast<int64_t>(read) * 4 + (k - 1)] = r;
+    }
 }
 #endif
 

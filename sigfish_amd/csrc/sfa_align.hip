@@ -51,6 +51,9 @@ void by_std(bool std_dtw, F f) {
 // winning job strip by strip from the last one upwards with start-column tracking.  Every count, offset and size, the checkpoint
 // interval, the groups and the limit of the waits are sfa::plan_long_reads' (sfa_plan.hpp: no HIP in it, tests/c/long_plan.cpp).
 
+// "secondary_strips": the long reads of a batch keep their candidate lists (it has an effect only while "secondary" is 1..4)
+bool strip_secondaries(const sfa_ctx *c) { return c->opt_secondary > 0 && c->opt_secondary_strips != 0; }
+
 // staging and every scratch buffer of the long reads, the plan into the page-locked staging area and up, on `st`
 int stage_long(sfa_ctx *c, const sfa::LongPlan &lp, hipStream_t st) {
     const int sets = lp.two_sets ? 2 : 1;
@@ -58,6 +61,10 @@ int stage_long(sfa_ctx *c, const sfa::LongPlan &lp, hipStream_t st) {
     int rc;
     if ((rc = c->strips.reserve_staging(lp.sg.bytes))) return rc;
     if ((rc = c->strips.reserve(lp.prog_bytes * sets, lp.bndc_floats * sets, lp.lck_floats * sets, lp.n_part, n_long, st))) return rc;
+    if (strip_secondaries(c)) {  // (no rank has been traced yet: -1)
+        if ((rc = c->strips.reserve_secondary(lp.sec_list_words, lp.sec_rank_words))) return rc;
+        HIP_TRY(hipMemsetAsync(c->strips.d_lranks.as<int32_t>() + lp.sec_traced(), 0xff, 4 * lp.sec_traced_words(), st));
+    }
 #ifdef SFA_TASK_TIMES
     if ((rc = c->times.d_ltimes.reserve(24 * lp.n_part * lp.max_strips))) return rc;  // (room for any group: no growth under one that is running)
 #endif
@@ -78,10 +85,45 @@ struct LongWinners {  // d_lwin, [5][n_long] words: a group's part of every row,
         : w_job(win + g0), w_ws(win + n_long + g0), w_score(reinterpret_cast<float *>(win + 2 * n_long + g0)), t_st(win + 3 * n_long + g0), t_end(win + 4 * n_long + g0) {}
 };
 
-struct LongArgs {  // the argument blocks of a group: pass 1 and pass 2, the strip finalize
+struct LongRanks {  // d_lranks (LongPlan::sec_rank): rank k of a group's reads, from its first read g0
+    int32_t *job, *col;
+    float *score;
+    int32_t *st, *end;
+    LongRanks(int32_t *w, const sfa::LongPlan &lp, int k, int32_t g0)
+        : job(w + lp.sec_rank(lp.kSecJob, k, g0)), col(w + lp.sec_rank(lp.kSecCol, k, g0)), score(reinterpret_cast<float *>(w + lp.sec_rank(lp.kSecScore, k, g0))),
+          st(w + lp.sec_rank(lp.kSecStart, k, g0)), end(w + lp.sec_rank(lp.kSecEnd, k, g0)) {}
+};
+
+struct LongArgs {  // the argument blocks of a group: pass 1 and pass 2, the strip finalize; with secondaries their lists and merge
     sfa::StripArgs sa{};
     sfa::StripFinalizeArgs fa{};
+    int32_t *p_top5 = nullptr;  // nullptr: no secondaries for the long reads
+    sfa::StripSecArgs xa{};
 };
+
+// the secondaries' finalize over long reads g0 ... g0 + gn - 1 of the batch (sa: any group's block, for what all groups share)
+sfa::StripSecArgs strip_sec_args(const sfa_ctx *c, const sfa::LongPlan &lp, int32_t g0, int32_t gn, ResultRow *d_sec) {
+    const LongRanks r(c->strips.d_lranks.as<int32_t>(), lp, 0, g0);
+    sfa::StripSecArgs xa{};
+    xa.reads = reinterpret_cast<const int32_t *>(c->strips.d_long.as<char>() + lp.sg.reads) + g0;
+    xa.p_top5 = c->strips.d_lp5.as<int32_t>() + static_cast<size_t>(g0) * c->model.n_jobs * sfa::kSecListWords;
+    xa.bad = c->status.d_bad.as<uint8_t>();
+    xa.s_job = r.job;
+    xa.s_ws = r.col;
+    xa.s_score = r.score;
+    xa.t_st = r.st;
+    xa.t_end = r.end;
+    xa.job_contig = c->model.d_job_contig.as<int32_t>();
+    xa.job_strand = c->model.d_job_strand.as<int8_t>();
+    xa.ref_len = c->model.d_ref_len.as<int32_t>();
+    xa.ref_st_offset = c->model.d_ref_off.as<int32_t>();
+    xa.sec = d_sec;
+    xa.n_long = gn;
+    xa.n_total = lp.n_long();
+    xa.n_jobs = c->model.n_jobs;
+    xa.n_sec = static_cast<int32_t>(c->opt_secondary);
+    return xa;
+}
 
 // the finalize of the group that sa describes: what the two blocks share comes from sa
 sfa::StripFinalizeArgs strip_finalize_args(const sfa_ctx *c, const sfa::StripArgs &sa, const LongWinners &w, ResultRow *d_out) {
@@ -106,7 +148,7 @@ sfa::StripFinalizeArgs strip_finalize_args(const sfa_ctx *c, const sfa::StripArg
     return fa;
 }
 
-LongArgs long_args(sfa_ctx *c, const sfa::LongPlan &lp, int32_t gi, const float *d_queries, const int64_t *d_q_off, ResultRow *d_out) {
+LongArgs long_args(sfa_ctx *c, const sfa::LongPlan &lp, int32_t gi, const float *d_queries, const int64_t *d_q_off, ResultRow *d_out, ResultRow *d_sec) {
     const int32_t g0 = lp.begin(gi), gn = lp.size(gi), n_jobs = c->model.n_jobs;
     const int set = lp.set(gi);
     const char *ds = c->strips.d_long.as<char>();
@@ -150,10 +192,17 @@ LongArgs long_args(sfa_ctx *c, const sfa::LongPlan &lp, int32_t gi, const float 
     c->times.n_ltimes = static_cast<int64_t>(lp.strips_of(gi)) * n_jobs;
 #endif
     a.fa = strip_finalize_args(c, sa, w, d_out);
+    if (strip_secondaries(c) && d_sec) {
+        a.p_top5 = c->strips.d_lp5.as<int32_t>() + static_cast<size_t>(g0) * n_jobs * sfa::kSecListWords;
+        a.xa = strip_sec_args(c, lp, g0, gn, d_sec);
+    }
     return a;
 }
 
-// a group of `strips` strips on its stream: pass 1 (one wave per (job, read, strip), tickets in that order), winners, pass 2, rows
+// a group of `strips` strips on its stream: pass 1 (one wave per (job, read, strip), tickets in that order), winners, pass 2, rows.
+// With secondaries pass 1 is the kernel that keeps the lists, and behind the rows come the merge of the lists and pass 2 once more
+// per rank 1..n_sec, the same kernel pointed at that rank's (job, column, score) and columns: the boundary rows and checkpoints of the
+// group stay where they are until the next group of this stream starts.  (The secondaries' rows: enqueue_batch, behind the join.)
 int enqueue_long_group(const LongArgs &a, int64_t strips, bool std_dtw, hipStream_t st) {
     const sfa::StripArgs &sa = a.sa;
     sfa::StripFinalizeArgs fa = a.fa;
@@ -161,7 +210,10 @@ int enqueue_long_group(const LongArgs &a, int64_t strips, bool std_dtw, hipStrea
     const dim3 block(256), gridp(static_cast<unsigned>((waves + 3) / 4)), grid2((sa.n_long + 3) / 4), fgrid((sa.n_long + 63) / 64), fblock(64);
     HIP_TRY(hipMemsetAsync(sa.progress, 0, sizeof(int32_t) * static_cast<size_t>(sa.n_long) * sa.n_jobs * sa.max_strips, st));
     HIP_TRY(hipMemsetAsync(sa.ticket, 0, 4, st));
-    by_std(std_dtw, [&](auto S) { hipLaunchKernelGGL((sfa::sdtw_strip_pipe_kernel<S>), gridp, block, 0, st, sa); });
+    if (a.p_top5)
+        by_std(std_dtw, [&](auto S) { hipLaunchKernelGGL((sfa::sdtw_strip_sec_pipe_kernel<S>), gridp, block, 0, st, sa, a.p_top5); });
+    else
+        by_std(std_dtw, [&](auto S) { hipLaunchKernelGGL((sfa::sdtw_strip_pipe_kernel<S>), gridp, block, 0, st, sa); });
     KERNEL_TRY();
     fa.mode = 1;
     hipLaunchKernelGGL(sfa::sdtw_strip_finalize_kernel, fgrid, fblock, 0, st, fa);
@@ -171,6 +223,22 @@ int enqueue_long_group(const LongArgs &a, int64_t strips, bool std_dtw, hipStrea
     fa.mode = 2;
     hipLaunchKernelGGL(sfa::sdtw_strip_finalize_kernel, fgrid, fblock, 0, st, fa);
     KERNEL_TRY();
+    if (!a.p_top5) return SFA_OK;
+    sfa::StripSecArgs xa = a.xa;
+    xa.mode = 1;
+    hipLaunchKernelGGL(sfa::sdtw_strip_sec_finalize_kernel, fgrid, fblock, 0, st, xa);
+    KERNEL_TRY();
+    for (int k = 1; k <= xa.n_sec; ++k) {
+        const size_t o = static_cast<size_t>(k) * xa.n_total;
+        sfa::StripArgs ra = sa;
+        ra.w_job = xa.s_job + o;
+        ra.w_ws = xa.s_ws + o;
+        ra.w_score = xa.s_score + o;
+        ra.t_st = xa.t_st + o;
+        ra.t_end = xa.t_end + o;
+        by_std(std_dtw, [&](auto S) { hipLaunchKernelGGL((sfa::sdtw_strip_chain_kernel<S>), grid2, block, 0, st, ra); });
+        KERNEL_TRY();
+    }
     return SFA_OK;
 }
 
@@ -181,14 +249,14 @@ int enqueue_long_group(const LongArgs &a, int64_t strips, bool std_dtw, hipStrea
 // runs beside the other group's work instead of behind everything.  Measured on one box, ms per step at 3 000 / 8 000 events: one
 // group 99.9 / 103.5, two 97.4 / 99.2, four 104.7 / 118.8 (more drains than they hide): profiles/r04_logs/strips_groups_ab*.log,
 // rejected_strip_pass2_rows_in_lds_three_waves.log.
-int align_long(sfa_ctx *c, const sfa::LongPlan &lp, const float *d_queries, const int64_t *d_q_off, ResultRow *d_out, hipStream_t first) {
+int align_long(sfa_ctx *c, const sfa::LongPlan &lp, const float *d_queries, const int64_t *d_q_off, ResultRow *d_out, ResultRow *d_sec, hipStream_t first) {
     if (int rc = stage_long(c, lp, first)) return rc;
     if (lp.two_sets) {  // the second stream starts behind the staging upload (and whatever `first` waited for)
         HIP_TRY(hipEventRecord(c->lev[2], first));
         HIP_TRY(hipStreamWaitEvent(c->stream_long2, c->lev[2], 0));
     }
     for (int32_t gi = 0; gi < lp.n_groups; ++gi) {
-        const LongArgs a = long_args(c, lp, gi, d_queries, d_q_off, d_out);
+        const LongArgs a = long_args(c, lp, gi, d_queries, d_q_off, d_out, d_sec);
         if (int rc = enqueue_long_group(a, lp.strips_of(gi), (c->flag & SFA_DTW) != 0, lp.set(gi) ? c->stream_long2 : first)) return rc;
     }
     if (lp.two_sets) {  // whoever waits for `first` waits for both
@@ -506,7 +574,8 @@ int enqueue_pass2(sfa_ctx *c, Route route, const BatchArgs &a, hipStream_t st) {
     return own_launch ? launch_finalize(a.fz, 2, st) : SFA_OK;
 }
 
-// merge the chunks' lists, trace candidates 1..n_sec, write their rows (the long reads' rows: valid = 0)
+// merge the chunks' lists, trace candidates 1..n_sec, write their rows (the long reads' rows: valid = 0; with "secondary_strips"
+// enqueue_batch writes them again behind the join with the row strips)
 int enqueue_secondaries(sfa_ctx *c, Route route, const BatchArgs &a, hipStream_t st) {
     SecArgs sa = a.sa;
     const int32_t n = sa.n_reads;
@@ -548,7 +617,7 @@ int enqueue_batch(sfa_ctx *c, Route route, const BatchArgs &a, const sfa::LongPl
         hipStream_t ls = c->stream_long;
         HIP_TRY(hipEventRecord(c->lev[0], st));  // queries, offsets and the non-finite screen are ready
         HIP_TRY(hipStreamWaitEvent(ls, c->lev[0], 0));
-        if ((rc = align_long(c, lp, da.queries, da.q_off, da.out, ls))) {
+        if ((rc = align_long(c, lp, da.queries, da.q_off, da.out, a.sa.sec, ls))) {
             (void)hipStreamSynchronize(ls);  // nothing of a failed call may still be running when the caller reuses its buffers
             (void)hipStreamSynchronize(c->stream_long2);
             return rc;
@@ -564,6 +633,14 @@ int enqueue_batch(sfa_ctx *c, Route route, const BatchArgs &a, const sfa::LongPl
     if (c->strips.long_pending) {  // join: what is left of the strips when the wave kernels are through counts as fill time
         HIP_TRY(hipEventRecord(c->ev[5], st));
         HIP_TRY(hipStreamWaitEvent(st, c->lev[1], 0));
+        // the secondaries of the long reads, behind the join: every rank of every group has been traced, and the wave path's own
+        // finalize, which wrote valid = 0 into these rows, is in front of this launch on this stream
+        if (strip_secondaries(c) && a.sa.sec) {
+            sfa::StripSecArgs xa = strip_sec_args(c, lp, 0, lp.n_long(), a.sa.sec);
+            xa.mode = 2;
+            hipLaunchKernelGGL(sfa::sdtw_strip_sec_finalize_kernel, dim3((xa.n_long + 63) / 64), dim3(64), 0, st, xa);
+            KERNEL_TRY();
+        }
     }
     HIP_TRY(hipMemcpyAsync(c->status.h_block.p, c->status.dev(), sizeof(sfa::BatchStatus), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(c->ev[4], st));

@@ -228,6 +228,9 @@ int sfa_set_option(sfa_ctx_t *c, const char *key, int64_t value) {
     } else if (k == "secondary") {
         if (value < 0 || value > 4) return fail(SFA_EINVAL, "secondary must be 0..4 (secondary mappings per read)");
         c->opt_secondary = value;
+    } else if (k == "secondary_strips") {
+        if (value != 0 && value != 1) return fail(SFA_EINVAL, "secondary_strips must be 0 (reads beyond SFA_MAX_QUERY events have no secondaries) or 1 (the row strips keep their lists)");
+        c->opt_secondary_strips = value;
     } else if (k == "map_scratch_bytes") {
         if (value < 0) return fail(SFA_EINVAL, "map_scratch_bytes must be >= 0");
         c->opt_map_scratch = value;

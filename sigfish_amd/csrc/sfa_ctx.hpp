@@ -262,6 +262,10 @@ struct Strips {  // row strips (queries beyond SFA_MAX_QUERY, sdtw_strips.hpp)
         if (d_bndc.cap != bndc_cap) HIP_TRY(hipMemsetAsync(d_bndc.p, 0x7f, d_bndc.cap, st));
         return SFA_OK;
     }
+    // secondary mappings of the long reads ("secondary_strips"): the candidate lists of pass 1, the ranks of the merge with their
+    // traced columns; sizes in words, from sfa::LongPlan
+    DevBuf d_lp5, d_lranks;
+    int reserve_secondary(size_t list_words, size_t rank_words) { return reserve_all(d_lp5, 4 * list_words, d_lranks, 4 * rank_words); }
 };
 
 struct Secondaries {  // secondary mappings: top-5 partials, merged candidates, their traced columns, rows [n][4]
@@ -366,6 +370,7 @@ struct sfa_ctx {
     int64_t opt_fused_trace = 1;             // 1: pass 2 rides in the fill launch as trailing tickets (fills the drain) where the launch has more tasks than wave slots; 2: always; 0: own launch
     int64_t opt_lds_ckpt = 1;                // 1: rolling checkpoints in LDS where the batch's shapes allow (R <= 16, sDTW); 0: all snapshots to HBM
     int64_t opt_secondary = 0;               // secondary mappings per read, 0..4 (sfa_secondary_rows); > 0 takes the plain two-pass route
+    int64_t opt_secondary_strips = 0;        // 1: with opt_secondary > 0, reads beyond SFA_MAX_QUERY events have secondaries too (the row strips keep the lists)
     int64_t opt_prio_unit = 2048;            // longest-remaining-first issue priority of the fill: columns per level, 0 = off
     int64_t opt_spin_limit_ms = 20000;       // bound of every in-launch wait (fused pass 2, pipelined strips); beyond it the batch fails with SFA_EKERNEL
     // test hooks (sfa_set_option refuses them unless SFA_TEST_HOOKS=1 is in the environment)

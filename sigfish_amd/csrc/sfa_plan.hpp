@@ -445,6 +445,9 @@ constexpr int kBndPad = 256;                // words behind every boundary row (
 #endif
 constexpr int kPipeBlock = SFA_PIPE_BLOCK;  // columns between two hand-overs of a boundary row (one release / acquire pair each)
 static_assert(kStripRows == kMaxQuery, "a strip holds what the wave kernels hold of a query");
+constexpr int kSecRanks = 5;                    // entries of a candidate list (SECONDARY_CAP, src/sigfish.h:41): the primary and four secondaries
+constexpr int kSecListWords = 3 * kSecRanks;    // one list: 5 x (score bits, end column, job)
+constexpr int kSecArrays = 5;                   // what is kept per rank and long read: job, column, score, traced start, traced end
 
 // staging layout: reads[n_long] (at 0) | bnd_off[n_jobs+1] | ck_off[n_jobs+1] | strip_off[2*n_long+2] (room for n_long groups of one read)
 struct LongStaging {
@@ -474,6 +477,14 @@ struct LongPlan {
     size_t prog_bytes = 0, bndc_floats = 0, lck_floats = 0;  // scratch of ONE set: progress words, boundary rows, checkpoints
     size_t n_part = 0;                                       // (read, job) pairs of all groups
     int64_t limit_ms = 0;                                    // the bounded wait of a strip for the strip above
+    // secondary mappings of the long reads ("secondary_strips"), words of 4 bytes: the lists pass 1 leaves per (read, job) pair of
+    // all groups, [n_long][n_jobs][kSecListWords]; the ranks, five arrays of [kSecRanks][n_long] -- job, column, score (the merge
+    // writes them), then start and end column (pass 2 of rank k writes them; -1 until then)
+    size_t sec_list_words = 0, sec_rank_words = 0;
+    enum SecArray { kSecJob = 0, kSecCol, kSecScore, kSecStart, kSecEnd };
+    size_t sec_rank(SecArray a, int k, int32_t li = 0) const { return (static_cast<size_t>(a) * kSecRanks + k) * reads.size() + li; }  // word of long read li, rank k
+    size_t sec_traced() const { return sec_rank(kSecStart, 0); }                                    // first word of the traced columns ...
+    size_t sec_traced_words() const { return sec_rank_words - sec_traced(); }                       // ... which run to the end
 
     int32_t n_long() const { return static_cast<int32_t>(reads.size()); }
     int32_t begin(int32_t gi) const { return gi * group; }
@@ -545,6 +556,8 @@ inline LongPlan plan_long_reads(const int64_t *q_off, int32_t n, const std::vect
     plan_long_checkpoints(job_len, ckpt_interval, ckpt_budget_bytes, &p);
     plan_long_groups(n_jobs, ckpt_budget_bytes, cu_count, &p);
     p.sg = LongStaging(p.n_long(), n_jobs);
+    p.sec_list_words = p.n_part * kSecListWords;
+    p.sec_rank_words = static_cast<size_t>(kSecArrays) * kSecRanks * p.n_long();
     // a strip legitimately waits for the strip above to get kPipeBlock + 72 columns ahead, behind every strip above that one: never
     // less than ~10 us per such column and strip (0.2 us measured), however small the option or busy the device
     p.limit_ms = std::max<int64_t>(spin_limit_ms, (static_cast<int64_t>(kPipeBlock + 72) * p.max_strips) / 100 + 1);
