@@ -626,9 +626,9 @@ typedef struct {
  * is inflated (own DEFLATE decoder, one lane per record), its primary fields are parsed and its signal decoded
  * (StreamVByte zig-zag deltas, one wave per record) on the device; the path of sfa_align_raw_ex continues from there.
  * heads[n] receives the fields the output needs.  A record the device decoder declines (malformed, longer read id than
- * sfa_read_head_t holds, inflating to more than 4x its size + 4 KB) sends the batch through the library's host reader
- * instead -- same results, counted in sfa_profile_t.blow5_fallbacks.  Other arguments as for sfa_align_raw_ex (prefix_size < 0
- * included). */
+ * sfa_read_head_t holds, inflating to more than 4x its size + 4 KB, signal stream longer or shorter than its keys say) sends
+ * the batch through the library's host reader instead -- same results, counted in sfa_profile_t.blow5_fallbacks; a record the
+ * host reader rejects as well is SFA_EINVAL naming it.  Other arguments as for sfa_align_raw_ex (prefix_size < 0 included). */
 int sfa_align_blow5(sfa_ctx_t *ctx, const uint8_t *records, const int64_t *rec_off, int32_t n_reads, int32_t record_zlib,
                     int32_t signal_svb, int32_t prefix_size, int32_t query_size, sfa_result_t *rows, sfa_query_info_t *info,
                     sfa_read_head_t *heads, sfa_event_t *query_events);
@@ -637,6 +637,21 @@ int sfa_align_blow5(sfa_ctx_t *ctx, const uint8_t *records, const int64_t *rec_o
  * out_len[i] = bytes produced or -1 (malformed, or larger than its slot).  Single-device context. */
 int sfa_inflate_zlib_device(sfa_ctx_t *ctx, const uint8_t *in, const int64_t *in_off, int32_t n, uint8_t *out, const int64_t *out_off,
                             int32_t *out_len);
+
+/* The device-side record decoder on its own (tests): the stages sfa_align_blow5 runs before the alignment -- inflate, field
+ * parser, signal decoder -- and what they left on the device, with NO host reader behind them.  records, rec_off, n, record_zlib,
+ * signal_svb as for sfa_align_blow5.  status[n]: 0 decoded, or why the device declined the record (one declined record is what
+ * sends a batch of sfa_align_blow5 to the host reader).  raw_off[n+1]: where every record's samples lie in samples[]; a record
+ * with SFA_BLOW5_INFLATE or SFA_BLOW5_FIELDS counts no samples and gets a zeroed head (record_bytes apart), one with
+ * SFA_BLOW5_STREAM keeps its head and its n_samples places, whose contents are undefined; all others are decoded whatever their
+ * neighbours are.  samples: room for `capacity` int16; SFA_ERANGE when raw_off[n] exceeds it (status, heads and raw_off are
+ * written by then).  Single-device context. */
+#define SFA_BLOW5_INFLATE 1 /* the record does not inflate (malformed, truncated, or more than 4x its size + 4 KB) */
+#define SFA_BLOW5_FIELDS 2  /* the primary fields: payload too short for them or for the signal they announce, read id too long */
+#define SFA_BLOW5_STREAM 3  /* svb-zd: the data stream is longer or shorter than its keys say */
+int sfa_decode_blow5_device(sfa_ctx_t *ctx, const uint8_t *records, const int64_t *rec_off, int32_t n, int32_t record_zlib,
+                            int32_t signal_svb, int32_t *status, sfa_read_head_t *heads, int64_t *raw_off, int16_t *samples,
+                            int64_t capacity);
 
 /* The event detection of sfa_align_raw on its own (tests): every read's WHOLE event table instead of the query window, means in
  * pA (not normalised).  raw, raw_off[n_reads+1], scaling as for sfa_align_raw; the context's flag selects the DNA or RNA detector

@@ -60,7 +60,7 @@ class SfaSessionAuto(C.Structure):
 
 
 # every symbol include/sigfish_amd.h declares (checked by tests/test_capi_host.py::test_library_exports_every_declared_symbol)
-SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "sfa_submit_batch", "sfa_wait_batch", "sfa_align_batch_device", "sfa_align_events", "sfa_align_raw", "sfa_align_raw_ex", "sfa_align_blow5", "sfa_inflate_zlib_device", "sfa_detect_events_device", "sfa_pinned_alloc", "sfa_pinned_free", "sfa_sync",
+SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "sfa_submit_batch", "sfa_wait_batch", "sfa_align_batch_device", "sfa_align_events", "sfa_align_raw", "sfa_align_raw_ex", "sfa_align_blow5", "sfa_inflate_zlib_device", "sfa_decode_blow5_device", "sfa_detect_events_device", "sfa_pinned_alloc", "sfa_pinned_free", "sfa_sync",
            "sfa_get_profile", "sfa_stream", "sfa_set_option", "sfa_plan_batch", "sfa_destroy", "sfa_last_error", "sfa_version", "sfa_build_id", "sfa_gen_ref_record",
            "sfa_znormalise", "sfa_paf_row", "sfa_sam_row", "sfa_paf_row_ex", "sfa_sam_row_ex", "sfa_secondary_rows", "sfa_event_maps", "sfa_sam_row_from_map", "sfa_r2qevent_map", "sfa_detect_events", "sfa_select_query", "sfa_detect_query_start", "sfa_set_pore", "sfa_read_kmer_model",
            "sfa_blow5_open", "sfa_blow5_attr", "sfa_blow5_next", "sfa_blow5_close", "sfa_blow5_select_shard", "sfa_blow5_select_records", "sfa_inflate_zlib", "sfa_inflate_zlib_pair", "sfa_device_memory",
@@ -96,6 +96,7 @@ def load():
     L.sfa_align_raw_ex.argtypes = [vp, C.POINTER(C.c_int16), i64p, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
     L.sfa_align_blow5.argtypes = [vp, vp, i64p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
     L.sfa_inflate_zlib_device.argtypes = [vp, vp, i64p, C.c_int32, vp, i64p, i32p]
+    L.sfa_decode_blow5_device.argtypes = [vp, vp, i64p, C.c_int32, C.c_int32, C.c_int32, i32p, vp, i64p, C.POINTER(C.c_int16), C.c_int64]
     L.sfa_detect_events_device.argtypes = [vp, C.POINTER(C.c_int16), i64p, C.POINTER(C.c_double), C.c_int32, vp, i32p, i32p, f32p, f32p]
     L.sfa_pinned_alloc.argtypes = [C.c_size_t]
     L.sfa_pinned_alloc.restype = vp

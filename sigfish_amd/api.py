@@ -13,6 +13,7 @@ from . import _lib
 
 # opt.flag bits (src/sigfish.h:30-39)
 RNA, DTW, INV, REF, END = 0x001, 0x002, 0x004, 0x010, 0x020
+BLOW5_INFLATE, BLOW5_FIELDS, BLOW5_STREAM = 1, 2, 3  # SFA_BLOW5_*: why decode_blow5_device's device stages declined a record
 
 RESULT_DTYPE = np.dtype([("rid", "<i4"), ("pos_st", "<i4"), ("pos_end", "<i4"), ("score", "<f4"), ("score2", "<f4"),
                          ("strand", "i1"), ("mapq", "u1"), ("valid", "u1"), ("pad", "u1")])
@@ -413,6 +414,30 @@ class Aligner:
                                                out.ctypes.data_as(C.c_void_p), out_off.ctypes.data_as(_lib.i64p),
                                                lens.ctypes.data_as(_lib.i32p)), "sfa_inflate_zlib_device")
         return [None if lens[i] < 0 else out[out_off[i]:out_off[i] + lens[i]].tobytes() for i in range(n)]
+
+    def decode_blow5_device(self, records, rec_off, record_zlib, signal_svb, capacity=None):
+        """The device-side record decoder alone (tests): the stages of align_blow5 before the alignment, no host reader behind
+        them.  -> (status int32[n], heads, raw_off int64[n+1], samples int16[raw_off[n]]).  status: 0 decoded, BLOW5_INFLATE /
+        BLOW5_FIELDS (no samples counted, empty head) or BLOW5_STREAM (samples undefined).  capacity: room for that many
+        samples (default: what any record of these sizes can hold); SfaError (SFA_ERANGE) where the records announce more."""
+        rec = np.frombuffer(records, np.uint8) if isinstance(records, (bytes, bytearray, memoryview)) else np.ascontiguousarray(records, np.uint8)
+        ro = np.ascontiguousarray(rec_off, np.int64)
+        n = len(ro) - 1
+        if capacity is None:  # svb-zd: at most 4 samples per byte; inflated: 4x + 4 KB per record
+            capacity = 4 * (4 * int(ro[-1]) + 4096 * n if record_zlib else int(ro[-1]))
+        status = np.zeros(max(n, 1), np.int32)
+        heads = (_lib.SfaReadHead * max(n, 1))()
+        raw_off = np.zeros(n + 1, np.int64)
+        samples = np.zeros(max(int(capacity), 1), np.int16)
+        if rec.size == 0:
+            rec = np.zeros(1, np.uint8)
+        _check(self._L.sfa_decode_blow5_device(self._h, rec.ctypes.data_as(C.c_void_p), ro.ctypes.data_as(_lib.i64p), n, int(bool(record_zlib)),
+                                               int(bool(signal_svb)), status.ctypes.data_as(_lib.i32p), C.cast(heads, C.c_void_p),
+                                               raw_off.ctypes.data_as(_lib.i64p), samples.ctypes.data_as(C.POINTER(C.c_int16)), int(capacity)),
+               "sfa_decode_blow5_device")
+        hs = [dict(read_id=heads[i].read_id.decode(), n_samples=heads[i].n_samples, digitisation=heads[i].digitisation,
+                   offset=heads[i].offset, range=heads[i].range, record_bytes=heads[i].record_bytes) for i in range(n)]
+        return status[:n], hs, raw_off, samples[:int(raw_off[-1])]
 
     def detect_events_device(self, raw, raw_off, scaling, tstats=False):
         """The event detection of align_raw alone (tests): -> (tables, routes[, t_short, t_long]).  tables: one EVENT_DTYPE

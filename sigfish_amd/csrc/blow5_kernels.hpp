@@ -13,10 +13,15 @@
 //     buffer in registers.  Stored, fixed and dynamic blocks; the Adler-32 trailer is checked.  Anything malformed marks
 //     the record failed (length -1) and the caller falls back to the host reader for the batch.
 //   * blow5_fields_kernel: the primary fields of every inflated record (read id, digitisation, offset, range, sample
-//     count; slow5.c:2806-2925) into fixed-size rows for the host, which needs them for the output lines.
+//     count; slow5.c:2806-2925) into fixed-size rows for the host, which needs them for the output lines.  A row with status 0
+//     promises: n_samples, signal offset and signal bytes are >= 0, the signal lies inside the payload, its bytes are
+//     2 n_samples (plain) or hold the count and its keys (svb-zd) -- whatever the length fields of a corrupt record say.
 //   * blow5_svb_kernel: ONE WAVE PER RECORD.  Lane l of round r owns key byte 64 r + l, i.e. four values whose byte
 //     lengths are the key's four 2-bit fields; a wave scan of the lanes' byte totals gives every lane its place in the data
-//     stream, a second scan of the zig-zag decoded deltas gives the samples, stored 8 bytes per lane, coalesced.
+//     stream, a second scan of the zig-zag decoded deltas gives the samples, stored 8 bytes per lane, coalesced.  A data
+//     stream that the keys do not consume exactly -- shorter or longer -- is flagged, as the host reader rejects it.
+// Same results as the host reader (host/blow5.cpp) means: a record is decoded here only if parse_blow5_record accepts it, to the
+// same fields and samples; everything else is declined and the host reader has the word.
 #pragma once
 
 #ifdef SFA_HOST_HARNESS  // tests/c/device_inflate_host.cpp compiles the lane decoder below with g++ (sanitizers, against zlib)
@@ -329,6 +334,63 @@ __device__ inline int inflate_zlib_lane(const uint8_t *in, int64_t n_in, uint8_t
     return static_cast<int>(op);
 }
 
+// The field row of one record and the parser that fills it (the body of blow5_fields_kernel; tests/c/blow5_fields_host.cpp runs
+// it on the host beside the host reader): the row's layout is described at the kernel below.  `len`: valid bytes at p.
+constexpr int kBlow5HeadBytes = 192;
+constexpr int kHeadStatus = 0, kHeadIdLen = 4, kHeadSamples = 8, kHeadScaling = 16, kHeadSigOff = 40, kHeadSigBytes = 48, kHeadId = 56;
+constexpr int kBlow5IdMax = kBlow5HeadBytes - kHeadId;
+__device__ __forceinline__ int32_t blow5_parse_fields(const uint8_t *p, int64_t len, int signal_svb, uint8_t *h) {
+    int32_t status = 0, id_len = 0;
+    int64_t n_samples = 0, sig_off = 0, sig_bytes = 0;
+    double f[3] = {0, 0, 0};
+    if (len < 2) {
+        status = -1;
+    } else {
+        id_len = p[0] | (p[1] << 8);
+        const int64_t fixed = 2 + id_len + 4 + 8 * 4 + 8;
+        if (id_len > kBlow5IdMax || len < fixed) {
+            status = -1;
+        } else {
+            for (int k = 0; k < id_len; ++k) h[kHeadId + k] = p[2 + k];
+            const uint8_t *q = p + 2 + id_len + 4;
+            __builtin_memcpy(&f[0], q, 8);
+            __builtin_memcpy(&f[1], q + 8, 8);
+            __builtin_memcpy(&f[2], q + 16, 8);
+            uint64_t l;
+            __builtin_memcpy(&l, q + 32, 8);
+            sig_off = fixed;
+            // every length is compared with what lies behind the fixed fields, never as a sum: a corrupt length must not wrap around
+            const uint64_t room = static_cast<uint64_t>(len - fixed);
+            if (signal_svb) {  // l = compressed bytes; the sample count is the u32 in front of the keys
+                if (l < 4 || l > room) {  // (so room >= 4: the count is inside the payload)
+                    status = -1;
+                } else {
+                    sig_bytes = static_cast<int64_t>(l);
+                    uint32_t ns;
+                    __builtin_memcpy(&ns, p + fixed, 4);
+                    n_samples = ns;
+                    const int64_t keys = (n_samples + 3) / 4;
+                    if (keys > sig_bytes - 4 || n_samples > (int64_t(1) << 31)) status = -1;
+                }
+            } else {
+                if (l > room / 2) {
+                    status = -1;
+                } else {
+                    n_samples = static_cast<int64_t>(l);
+                    sig_bytes = 2 * n_samples;
+                }
+            }
+        }
+    }
+    __builtin_memcpy(h + kHeadStatus, &status, 4);
+    __builtin_memcpy(h + kHeadIdLen, &id_len, 4);
+    __builtin_memcpy(h + kHeadSamples, &n_samples, 8);
+    __builtin_memcpy(h + kHeadScaling, f, 24);
+    __builtin_memcpy(h + kHeadSigOff, &sig_off, 8);
+    __builtin_memcpy(h + kHeadSigBytes, &sig_bytes, 8);
+    return status;
+}
+
 #ifdef SFA_DEFINE_BLOW5_KERNELS  // plain kernels: defined in exactly one translation unit (sfa_pre.hip)
 // `lanes` records per wave (one wave per block, the other lanes idle), chosen by the host from the batch size
 // (inflate_lanes()).  A wave of independent decoders executes every lane's path: whenever ONE lane meets a code longer than
@@ -352,9 +414,6 @@ __global__ void __launch_bounds__(64) blow5_inflate_kernel(const InflateArgs a, 
 // sampling_rate, u64 len, signal.  One lane per record; `head` gets a fixed-size row for the host, its fields at kHead*:
 //   i32 status (0 ok, -1 malformed), i32 id_len, i64 n_samples, f64 x3 digitisation, offset, range,
 //   i64 signal offset inside the payload, i64 signal bytes, the read id (up to kBlow5IdMax bytes)
-constexpr int kBlow5HeadBytes = 192;
-constexpr int kHeadStatus = 0, kHeadIdLen = 4, kHeadSamples = 8, kHeadScaling = 16, kHeadSigOff = 40, kHeadSigBytes = 48, kHeadId = 56;
-constexpr int kBlow5IdMax = kBlow5HeadBytes - kHeadId;
 struct FieldsArgs {
     const uint8_t *payload;      // inflated payloads (or the records themselves when they are not compressed)
     const int64_t *payload_off;  // [n+1] slots
@@ -367,52 +426,8 @@ struct FieldsArgs {
 __global__ void __launch_bounds__(64) blow5_fields_kernel(const FieldsArgs a) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= a.n) return;
-    uint8_t *h = a.head + static_cast<int64_t>(i) * kBlow5HeadBytes;
-    const uint8_t *p = a.payload + a.payload_off[i];
     const int64_t len = a.payload_len ? a.payload_len[i] : (a.payload_off[i + 1] - a.payload_off[i]);
-    int32_t status = 0, id_len = 0;
-    int64_t n_samples = 0, sig_off = 0, sig_bytes = 0;
-    double f[3] = {0, 0, 0};
-    if (len < 2) {
-        status = -1;
-    } else {
-        id_len = p[0] | (p[1] << 8);
-        const int64_t fixed = 2 + id_len + 4 + 8 * 4 + 8;
-        if (id_len > kBlow5IdMax || len < fixed) {
-            status = -1;
-        } else {
-            for (int k = 0; k < id_len; ++k) h[kHeadId + k] = p[2 + k];
-            const uint8_t *q = p + 2 + id_len + 4;
-            __builtin_memcpy(&f[0], q, 8);
-            __builtin_memcpy(&f[1], q + 8, 8);
-            __builtin_memcpy(&f[2], q + 16, 8);
-            uint64_t l;
-            __builtin_memcpy(&l, q + 32, 8);
-            sig_off = fixed;
-            if (a.signal_svb) {  // l = compressed bytes; the sample count is the u32 in front of the keys
-                sig_bytes = static_cast<int64_t>(l);
-                if (sig_bytes < 4 || fixed + sig_bytes > len) {
-                    status = -1;
-                } else {
-                    uint32_t ns;
-                    __builtin_memcpy(&ns, p + fixed, 4);
-                    n_samples = ns;
-                    const int64_t keys = (n_samples + 3) / 4;
-                    if (4 + keys > sig_bytes || n_samples > (int64_t(1) << 31)) status = -1;
-                }
-            } else {
-                n_samples = static_cast<int64_t>(l);
-                sig_bytes = 2 * n_samples;
-                if (n_samples < 0 || fixed + sig_bytes > len) status = -1;
-            }
-        }
-    }
-    __builtin_memcpy(h + kHeadStatus, &status, 4);
-    __builtin_memcpy(h + kHeadIdLen, &id_len, 4);
-    __builtin_memcpy(h + kHeadSamples, &n_samples, 8);
-    __builtin_memcpy(h + kHeadScaling, f, 24);
-    __builtin_memcpy(h + kHeadSigOff, &sig_off, 8);
-    __builtin_memcpy(h + kHeadSigBytes, &sig_bytes, 8);
+    blow5_parse_fields(a.payload + a.payload_off[i], len, a.signal_svb, a.head + static_cast<int64_t>(i) * kBlow5HeadBytes);
 }
 
 // svb-zd -> int16 samples (slow5_press.c:1085-1135: StreamVByte with 1-4 byte values, zig-zag, delta against the previous
@@ -423,7 +438,7 @@ struct SvbArgs {
     const uint8_t *head;         // rows of blow5_fields_kernel
     const int64_t *raw_off;      // [n+1] sample offsets of the output
     int16_t *raw;
-    int32_t *bad;                // [n] set to 1 when the data stream is shorter than its keys say
+    int32_t *bad;                // [n] set to 1 when the data stream is shorter or longer than its keys say
     int32_t signal_svb;
     int32_t n;
 };
@@ -450,7 +465,8 @@ __global__ void __launch_bounds__(256) blow5_svb_kernel(const SvbArgs a) {
     __builtin_memcpy(&n_samples, h + kHeadSamples, 8);
     __builtin_memcpy(&sig_off, h + kHeadSigOff, 8);
     __builtin_memcpy(&sig_bytes, h + kHeadSigBytes, 8);
-    if (status != 0) return;
+    // (a record the host counted other samples for than its row says -- none, where it declined the record -- has no slot to write)
+    if (status != 0 || a.raw_off[i + 1] - a.raw_off[i] != n_samples) return;
     int16_t *out = a.raw + a.raw_off[i];
     const uint8_t *sig = a.payload + a.payload_off[i] + sig_off;
     if (!a.signal_svb) {  // plain int16 samples (unaligned in the payload)
@@ -514,7 +530,8 @@ __global__ void __launch_bounds__(256) blow5_svb_kernel(const SvbArgs a) {
         prev += tot;
         dpos += total;
     }
-    if (__any(short_data) && lane == 0) a.bad[i] = 1;
+    // the stream must be consumed exactly, as the host reader demands (host/blow5.cpp: decode_svb_zd returns data == end)
+    if ((__any(short_data) || dpos != data_bytes) && lane == 0) a.bad[i] = 1;
 }
 #endif
 

@@ -154,8 +154,9 @@ bool decode_svb_zd(const uint8_t *p, size_t nbytes, std::vector<int16_t> *out) {
         memcpy(&v, data, code + 1);  // little endian
         data += code + 1;
         const int32_t delta = static_cast<int32_t>(v >> 1) ^ -static_cast<int32_t>(v & 1);
-        (*out)[i] = static_cast<int16_t>(delta + prev);
-        prev += delta;
+        // (unsigned sum: a corrupt stream's deltas may leave int32, where the SSSE3 loop above wraps and a signed sum is undefined)
+        prev = static_cast<int32_t>(static_cast<uint32_t>(prev) + static_cast<uint32_t>(delta));
+        (*out)[i] = static_cast<int16_t>(prev);
     }
     return data == end;
 }
@@ -686,7 +687,7 @@ bool parse_payload(const uint8_t *p, const uint8_t *end, int signal_svb, Blow5Re
             ok = len <= static_cast<uint64_t>(end - p) / 2;  // (not len * 2: a corrupt length must not wrap around)
             if (ok) {
                 rec->raw.resize(len);
-                memcpy(rec->raw.data(), p, len * 2);
+                if (len) memcpy(rec->raw.data(), p, len * 2);  // (an empty vector's data() may be null, which memcpy must not get)
             }
         } else {
             ok = static_cast<uint64_t>(end - p) >= len && decode_svb_zd(p, len, &rec->raw);

@@ -242,8 +242,17 @@ struct Blow5Call {
     std::vector<int64_t> raw_off;  // [n + 1] samples of every read, and their
     std::vector<double> scaling;   // [n][3] digitisation, offset, range: the arguments of the raw path
     std::vector<int16_t> raw;      // the host reader's samples (the device route leaves them on the device)
+    std::vector<int32_t> status;   // [n] what the device stages made of every record: 0 decoded, or one of kRec* (include/sigfish_amd.h)
 };
-constexpr int kDeclined = 1;  // a device stage's answer beside SFA_OK and errors: the host reader takes the batch (sfa_last_error() says why)
+constexpr int kDeclined = 1;  // a device route's answer beside SFA_OK and errors: the host reader takes the batch (sfa_last_error() says why)
+constexpr int32_t kRecInflate = SFA_BLOW5_INFLATE, kRecFields = SFA_BLOW5_FIELDS, kRecStream = SFA_BLOW5_STREAM;
+constexpr int64_t kMaxSampleTotal = INT64_MAX / 2;  // samples of a batch: their bytes are still an int64_t
+
+static bool any_declined(const Blow5Call &k) {
+    for (int32_t st : k.status)
+        if (st != 0) return true;
+    return false;
+}
 
 // records per wave of the device inflate: about one wave per SIMD (blow5_inflate_kernel)
 static int inflate_lanes(int32_t n, int cu_count) {
@@ -294,30 +303,54 @@ static int blow5_launch_fields(sfa_ctx_t *c, Blow5Call &k) {
     return SFA_OK;
 }
 
-// the head rows back and into the caller's heads; a record the device declined sends the whole batch to the host reader
+// the head rows back and into the caller's heads, every record's verdict into k.status.  A record the device declined counts no
+// samples (blow5_svb_kernel leaves out whatever its slot does not match) and leaves an empty head; the first one's reason is
+// kept in sfa_last_error() for whoever wants to know why.  Behind the parser's own checks, the host takes no count on trust:
+// not one beyond what the record's bytes can hold, not a total whose bytes would leave int64_t.
 static int blow5_heads_back(sfa_ctx_t *c, Blow5Call &k) {
+    const int32_t n = k.n;
     const uint8_t *hh = c->blow5.h_head.as<uint8_t>();
-    HIP_TRY(hipMemcpyAsync(c->blow5.h_head.p, c->blow5.b_head.p, static_cast<size_t>(k.n) * sfa::kBlow5HeadBytes, hipMemcpyDeviceToHost, c->stream));
+    // (behind the rows: n words for blow5_decode_signals' flags, then n for the inflated lengths)
+    const int32_t *inflated = reinterpret_cast<const int32_t *>(hh + static_cast<size_t>(n) * sfa::kBlow5HeadBytes) + n;
+    HIP_TRY(hipMemcpyAsync(c->blow5.h_head.p, c->blow5.b_head.p, static_cast<size_t>(n) * sfa::kBlow5HeadBytes, hipMemcpyDeviceToHost, c->stream));
+    if (k.record_zlib) HIP_TRY(hipMemcpyAsync(const_cast<int32_t *>(inflated), c->blow5.b_len.p, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int32_t i = 0; i < k.n; ++i) {
+    bool said = false;
+    for (int32_t i = 0; i < n; ++i) {
         const uint8_t *h = hh + static_cast<size_t>(i) * sfa::kBlow5HeadBytes;
         int32_t status, id_len;
         int64_t ns;
         memcpy(&status, h + sfa::kHeadStatus, 4);
         memcpy(&id_len, h + sfa::kHeadIdLen, 4);
         memcpy(&ns, h + sfa::kHeadSamples, 8);
-        if (status != 0 || id_len < 0 || id_len > static_cast<int32_t>(sizeof(k.heads[i].read_id)) - 1 || ns < 0) {
-            (void)fail(SFA_OK, "sfa_align_blow5: device declined record %d (status %d, id of %d bytes, %lld samples): host reader takes the batch", i,
-                       status, id_len, static_cast<long long>(ns));  // kept in sfa_last_error() for whoever wants to know why
-            return kDeclined;
+        const int64_t bytes = k.rec_off[i + 1] - k.rec_off[i];
+        const int64_t payload = k.record_zlib ? inflated[i] : bytes;
+        // a plain sample takes two bytes, four svb-zd samples at least their key byte
+        const int64_t room = k.signal_svb ? 4 * std::max<int64_t>(payload, 0) : payload / 2;
+        int32_t verdict = 0;
+        if (k.record_zlib && inflated[i] < 0)
+            verdict = kRecInflate;
+        else if (status != 0 || id_len < 0 || id_len > static_cast<int32_t>(sizeof(k.heads[i].read_id)) - 1 || ns < 0 || ns > room || ns > kMaxSampleTotal - k.raw_off[i])
+            verdict = kRecFields;
+        k.status[i] = verdict;
+        if (verdict != 0) {
+            if (!said)
+                (void)fail(SFA_OK, "sfa_align_blow5: device declined record %d (status %d, id of %d bytes, %lld samples): host reader takes the batch", i,
+                           status, id_len, static_cast<long long>(ns));
+            said = true;
+            memset(&k.heads[i], 0, sizeof k.heads[i]);
+            k.heads[i].record_bytes = bytes;
+            k.raw_off[i + 1] = k.raw_off[i];
+            continue;
         }
-        fill_head(k.heads[i], &k.scaling[3 * static_cast<size_t>(i)], h + sfa::kHeadId, id_len, ns, h + sfa::kHeadScaling, k.rec_off[i + 1] - k.rec_off[i]);
+        fill_head(k.heads[i], &k.scaling[3 * static_cast<size_t>(i)], h + sfa::kHeadId, id_len, ns, h + sfa::kHeadScaling, bytes);
         k.raw_off[i + 1] = k.raw_off[i] + ns;
     }
     return SFA_OK;
 }
 
-// the signals into c->raw.e_raw, where the raw path takes them from
+// the signals into c->raw.e_raw, where the raw path takes them from; a signal whose data stream is longer or shorter than its keys
+// say gets kRecStream in k.status (its samples are then not to be used)
 static int blow5_decode_signals(sfa_ctx_t *c, Blow5Call &k) {
     const int32_t n = k.n;
     hipStream_t sp = c->stream;
@@ -331,18 +364,19 @@ static int blow5_decode_signals(sfa_ctx_t *c, Blow5Call &k) {
     HIP_TRY(hipMemcpyAsync(bad, c->blow5.b_bad.p, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, sp));
     HIP_TRY(hipEventRecord(c->bev[1], sp));
     HIP_TRY(hipStreamSynchronize(sp));
+    bool said = false;
     for (int32_t i = 0; i < n; ++i)
-        if (bad[i] != 0) {
-            (void)fail(SFA_OK, "sfa_align_blow5: signal of record %d is shorter than its keys say: host reader takes the batch", i);
-            return kDeclined;
+        if (bad[i] != 0 && k.status[i] == 0) {
+            k.status[i] = kRecStream;
+            if (!said) (void)fail(SFA_OK, "sfa_align_blow5: signal of record %d is longer or shorter than its keys say: host reader takes the batch", i);
+            said = true;
         }
-    c->blow5.bev_pending = true;
     return SFA_OK;
 }
 
 // host reader for the whole batch (own inflate / zlib, SSSE3 StreamVByte): malformed records are reported from here
 static int blow5_host_reader(sfa_ctx_t *c, Blow5Call &k) {
-    c->blow5.blow5_fallbacks++;
+    c->prof.blow5_fallbacks = ++c->blow5.blow5_fallbacks;  // (visible at once: a batch the host reader refuses as well resolves no profile)
     for (int32_t i = 0; i < k.n; ++i) {
         sfa::Blow5Record rec;
         std::string err;
@@ -390,13 +424,42 @@ int sfa_align_blow5(sfa_ctx_t *c, const uint8_t *records, const int64_t *rec_off
         if (rec_off[i + 1] < rec_off[i]) return fail(SFA_EINVAL, "sfa_align_blow5: rec_off not monotone at record %d", i);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    Blow5Call k{records, rec_off, n, record_zlib, signal_svb, heads, {}, std::vector<int64_t>(n + 1, 0), std::vector<int64_t>(n + 1, 0), std::vector<double>(3 * static_cast<size_t>(n))};
+    Blow5Call k{records, rec_off, n, record_zlib, signal_svb, heads, {}, std::vector<int64_t>(n + 1, 0), std::vector<int64_t>(n + 1, 0), std::vector<double>(3 * static_cast<size_t>(n)), {}, std::vector<int32_t>(n, 0)};
+    // one declined record and the host reader takes the batch: the signals are not even launched behind declined fields
     int rc = blow5_launch_fields(c, k);
     if (!rc) rc = blow5_heads_back(c, k);
+    if (!rc && any_declined(k)) rc = kDeclined;
     if (!rc) rc = blow5_decode_signals(c, k);
+    if (!rc && any_declined(k)) rc = kDeclined;
+    if (!rc) c->blow5.bev_pending = true;
     if (rc == kDeclined) rc = blow5_host_reader(c, k);  // the one place where a batch changes routes
     if (rc) return rc;
     return align_raw_impl(c, RawCall{k.raw.empty() ? nullptr : k.raw.data(), k.raw_off.data(), k.scaling.data(), n, prefix_size, query_size, rows, info, query_events});
+}
+
+// (testing hook of the device-side record decoder: the stages of sfa_align_blow5 above and what they left on the device, no host
+// reader behind them; see include/sigfish_amd.h)
+int sfa_decode_blow5_device(sfa_ctx_t *c, const uint8_t *records, const int64_t *rec_off, int32_t n, int32_t record_zlib, int32_t signal_svb,
+                            int32_t *status, sfa_read_head_t *heads, int64_t *raw_off, int16_t *samples, int64_t capacity) {
+    if (!c || !c->shards.empty() || n < 0 || capacity < 0 || (n > 0 && (!records || !rec_off || !status || !heads || !raw_off || (capacity > 0 && !samples))))
+        return fail(SFA_EINVAL, "sfa_decode_blow5_device: bad argument (single-device context needed)");
+    if (n == 0) return SFA_OK;
+    if (rec_off[0] != 0) return fail(SFA_EINVAL, "sfa_decode_blow5_device: rec_off must start at 0");
+    for (int32_t i = 0; i < n; ++i)
+        if (rec_off[i + 1] < rec_off[i]) return fail(SFA_EINVAL, "sfa_decode_blow5_device: rec_off not monotone at record %d", i);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    Blow5Call k{records, rec_off, n, record_zlib, signal_svb, heads, {}, std::vector<int64_t>(n + 1, 0), std::vector<int64_t>(n + 1, 0), std::vector<double>(3 * static_cast<size_t>(n)), {}, std::vector<int32_t>(n, 0)};
+    if (int rc = blow5_launch_fields(c, k)) return rc;
+    if (int rc = blow5_heads_back(c, k)) return rc;
+    memcpy(raw_off, k.raw_off.data(), 8 * static_cast<size_t>(n + 1));
+    memcpy(status, k.status.data(), 4 * static_cast<size_t>(n));
+    if (k.raw_off[n] > capacity) return fail(SFA_ERANGE, "sfa_decode_blow5_device: %lld samples, room for %lld", static_cast<long long>(k.raw_off[n]), static_cast<long long>(capacity));
+    if (int rc = blow5_decode_signals(c, k)) return rc;
+    memcpy(status, k.status.data(), 4 * static_cast<size_t>(n));
+    if (k.raw_off[n] > 0) HIP_TRY(hipMemcpyAsync(samples, c->raw.e_raw.p, 2 * static_cast<size_t>(k.raw_off[n]), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SFA_OK;
 }
 
 // (testing hook of the device-side inflate alone: n zlib streams in, their bytes out; see include/sigfish_amd.h)

@@ -123,6 +123,30 @@ def test_device_inflate_lane_decoder_on_the_host_with_sanitizers(tmp_path):
     assert run.returncode == 0 and b"4000 iterations, 0 failures" in run.stdout, (run.stdout + run.stderr).decode()[-3000:]
 
 
+@pytest.mark.parametrize("sanitizers", [False, True])
+def test_device_field_parser_on_the_host_beside_the_host_reader(tmp_path, sanitizers):
+    """The field parser of the device-side BLOW5 reader (blow5_kernels.hpp: blow5_parse_fields, the body of blow5_fields_kernel),
+    compiled for the host beside the host reader (tests/c/blow5_fields_host.cpp): payload lengths around the fixed fields, id
+    lengths around the row, length fields up to 2^64-1 for both signal methods, 4 000 seeded mutations -- every payload in a
+    heap block of exactly its length.  An accepted record has its signal inside the payload and the host reader's fields; a
+    rejected one the host reader rejects as well.  Plain, and under ASan + UBSan, which the GPU pool cannot run."""
+    import shutil
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    csrc = os.path.join(ROOT, "sigfish_amd", "csrc")
+    exe = str(tmp_path / "blow5_fields_host")
+    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitizers else []
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", *flags, "-o", exe, os.path.join(ROOT, "tests", "c", "blow5_fields_host.cpp"),
+                            os.path.join(csrc, "host", "blow5.cpp"), os.path.join(csrc, "host", "inflate.cpp"), "-lz", "-lpthread"],
+                           capture_output=True, timeout=600)
+    if sanitizers and build.returncode != 0 and b"sanitize" in build.stderr:
+        pytest.skip("toolchain without sanitizer runtimes")
+    assert build.returncode == 0, build.stderr.decode()[-2000:]
+    run = subprocess.run([exe, "4000", "1"], capture_output=True, timeout=600)
+    assert run.returncode == 0 and b"4148 cases, 0 failures" in run.stdout, (run.stdout + run.stderr).decode()[-3000:]
+    assert b"ERROR: AddressSanitizer" not in run.stderr and b"runtime error" not in run.stderr, run.stderr.decode()[-3000:]
+
+
 def test_strip_heights_cover_every_query_length(tmp_path):
     """sfa::strip_rows_per_lane (sdtw_strips.hpp), compiled for the host with hipcc: for every query length from 2049 to 400 000
     events the strips cover the query, the last one holds at least one row, the height is an instantiated one -- a violation
