@@ -204,7 +204,7 @@ int sfa_event_maps(sfa_ctx_t *ctx, const sfa_result_t *rows, const int32_t *read
  * start column of the path into it -- so a chunk of new events costs its own rows of the recurrence, however long the read has
  * become, instead of sfa_align_batch over the whole prefix again.  The caller keeps its normalisation fixed over a slot's life:
  * the events of all chunks are taken as ONE query (to re-normalise, reset the slot and send its events again).
- * Single-device contexts without SFA_DTW, and not SFA_RNA without SFA_INV (the query rows are then the events reversed: new events
+ * Single-device contexts (or, with SFA_SESSION_SPREAD, the devices of sfa_init_devices) without SFA_DTW, and not SFA_RNA without SFA_INV (the query rows are then the events reversed: new events
  * would become row 0) unless the session is created with SFA_SESSION_RESWEEP; SFA_EINVAL otherwise.  A session belongs to its context and uses its stream; its buffers are its own, so
  * batch calls on the context between two extends do not disturb it, and sfa_secondary_rows / sfa_event_maps keep referring to
  * the last BATCH call.  sfa_destroy frees the sessions a context still has: their handles are dead after it. */
@@ -213,6 +213,33 @@ typedef struct sfa_session sfa_session_t;
 /* 0x2 is not assigned: sfa_session_bytes and sfa_session_create refuse it as an unknown bit. */
 #define SFA_SESSION_RESWEEP 0x4  /* raw mode only: a slot is swept when its normalisation window changes, over the window's events
                                     (see "resweep sessions" below); accepts SFA_RNA without SFA_INV */
+/* 0x8 is not assigned either. */
+#define SFA_SESSION_SPREAD 0x10  /* on a context of sfa_init_devices: the slots are dealt over its devices (see below) */
+/* Spread sessions.  Without SFA_SESSION_SPREAD a session needs a single-device context.  With it, on a context of G shards
+ * (sfa_init_devices), the session is one ordinary session per shard that holds slots, created with the caller's other flags:
+ * slot i lives on shard i % G as that shard's slot i / G, so consecutive channels balance, and device r holds the bytes of
+ * (n_slots - r + G - 1) / G slots -- carried rows (sfa_session_bytes), and the same share of everything the configuration calls
+ * add.  With n_slots < G the trailing shards hold nothing.  If one shard cannot create its part (SFA_ENOMEM on one device), the
+ * parts already made are freed and the call fails with that shard's code and message.  On a single-device context the flag is
+ * accepted and changes nothing.
+ * Every entry point below works on a spread session with the same arguments and the same results, byte for byte, as on a plain
+ * session fed the same calls; slot numbers are always the caller's, and the forms without a slot list answer in slot order.  A
+ * call's entries are dealt to the shards (the caller's order kept inside each), the shards run side by side on the context's
+ * shard threads -- shard 0 on the caller's -- and the answers are put back in the caller's order.  The chunks of
+ * sfa_session_extend and sfa_session_extend_raw are packed per shard into host buffers the session owns and reuses: a tick
+ * allocates nothing once they have grown to its size.  sfa_session_event_maps writes every shard's maps straight into the caller's
+ * pairs.  sfa_session_row and sfa_session_events go to the shard that owns the slot.
+ * Refusals: a slot out of range or named twice is refused for the whole call before any shard hears of it, and so is whatever
+ * else an extend call is refused for (a slot past its end of read, another scaling, ...): every shard is asked before any shard
+ * works, so a refused call changes nothing on any shard.  An error a shard meets while it works is the call's error, the first in
+ * shard order; the other shards have then done their part of the call.
+ * Configuration (sfa_session_raw_config, sfa_session_raw_recalibrate, sfa_session_raw_auto_start, sfa_session_candidates_config,
+ * sfa_session_keep_events) goes to every shard.  What it is refused for -- the arguments, the session's kind, a slot in use
+ * anywhere -- is the same on every shard, and every shard refuses.  If one shard fails for a reason of its own (memory) after
+ * another has taken the call, the call returns that error and the session takes nothing but sfa_session_destroy from then on
+ * (SFA_EINVAL).
+ * sfa_get_profile on the context afterwards reports the call as it reports a sharded batch: the slowest shard's times, the summed
+ * counts; a shard the call had nothing for adds nothing.  sfa_destroy frees a context's spread sessions before its shards. */
 
 /* SFA_ENOMEM when the carried rows do not fit. */
 int sfa_session_create(sfa_ctx_t *ctx, int32_t n_slots, uint32_t session_flags, sfa_session_t **s);
@@ -272,7 +299,8 @@ void sfa_session_destroy(sfa_session_t *s);
  * SFA_SESSION_NO_START (the allocator adds an eighth of headroom; bookkeeping is some 50 bytes per slot, and 96 more -- four rows -- on a
  * session that keeps candidates, sfa_session_candidates_config: not counted here).  Host arithmetic, no
  * device needed; negative (an SFA_E* code) for arguments that are not positive, unknown flags or a product beyond 2^63.
- * SFA_SESSION_RESWEEP changes nothing: the carried rows are still needed (a window beyond SFA_MAX_QUERY events runs as pieces). */
+ * SFA_SESSION_RESWEEP changes nothing: the carried rows are still needed (a window beyond SFA_MAX_QUERY events runs as pieces).
+ * Neither does SFA_SESSION_SPREAD: the session holds the same rows, device r of G those of (n_slots - r + G - 1) / G slots. */
 int64_t sfa_session_bytes(int64_t total_columns, int32_t n_slots, uint32_t session_flags);
 
 /* ---- event maps of a slot's row: the warp path of the real-time path -------------------------------------------------------

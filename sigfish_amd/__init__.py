@@ -4,7 +4,7 @@ The product is the C-ABI shared library (include/sigfish_amd.h, built from sigfi
 sigfish_amd/lib/libsigfish_amd.so).  This package is only a thin ctypes binding used by bench.py and the tests;
 it never falls back to a CPU implementation: importing works without a GPU, creating an Aligner does not.
 """
-from .api import (END, DTW, EVENT_DTYPE, INV, REF, RNA, RESULT_DTYPE, SESSION_NO_START, SESSION_RESWEEP, Aligner, Blow5File, RefModel, SfaError, build_id,
+from .api import (END, DTW, EVENT_DTYPE, INV, REF, RNA, RESULT_DTYPE, SESSION_NO_START, SESSION_RESWEEP, SESSION_SPREAD, Aligner, Blow5File, RefModel, SfaError, build_id,
                   detect_events, detect_query_start, paf_row, r2qevent_map, read_fasta, read_kmer_model, sam_row, sam_row_from_map, select_query, session_bytes, version, znormalise, Session,
                   EventStream, session_raw_bytes, SESSION_RAW_INFO_DTYPE, RAW_CALIBRATED, RAW_FULL, RAW_ENDED, RAW_POISONED, RAW_RECALIBRATED, RECAL_AT_END,
                   recal_window, recal_double, auto_start_target, session_auto_bytes, SESSION_AUTO_DTYPE, AUTO_PENDING, AUTO_RESOLVED, AUTO_NO_TARGET,

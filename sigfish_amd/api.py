@@ -272,7 +272,7 @@ class Aligner:
                "sfa_align_events")
         return out
 
-    def session(self, n_slots, starts=True, resweep=False, flags=None, candidates=0, auto_start=None, keep_events=0):
+    def session(self, n_slots, starts=True, resweep=False, flags=None, candidates=0, auto_start=None, keep_events=0, spread=False):
         """An alignment session of n_slots growing reads on this aligner (sfa_session_create); starts=False carries costs only
         (SFA_SESSION_NO_START: half the memory, the coordinate on the start side of every row is -1).  resweep=True
         (SFA_SESSION_RESWEEP): a raw-mode-only session that sweeps a slot only when its normalisation window changes, over the
@@ -280,8 +280,11 @@ class Aligner:
         flags: the raw flag word in place of starts / resweep.  candidates=1..4: configure_candidates() on the new session.
         auto_start=dict(skip=, norm=, query=, every=, max_samples=[, recalibrate=, at_end=]): configure_raw() with skip as the
         largest skip, then configure_auto_start(every, max_samples), on the new session.  keep_events=N: keep_events(N) on the
-        new (event-mode) session, so that event_maps() has the slots' events."""
-        s = Session(self, n_slots, starts, resweep, flags)
+        new (event-mode) session, so that event_maps() has the slots' events.
+        spread=True (SFA_SESSION_SPREAD): on an Aligner made with devices= the slots are dealt over its devices, slot i on the
+        i % G-th; every method keeps the caller's slot numbers and returns the same bytes.  Without it such an Aligner has no
+        sessions; on a single device it changes nothing."""
+        s = Session(self, n_slots, starts, resweep, flags, spread)
         if keep_events:
             try:
                 s.keep_events(keep_events)
@@ -477,6 +480,7 @@ class Aligner:
 
 SESSION_NO_START = 0x1
 SESSION_RESWEEP = 0x4  # (0x2 is unassigned)
+SESSION_SPREAD = 0x10  # (and so is 0x8): the slots dealt over the devices of an Aligner made with devices=
 
 
 def _session_flags(starts, resweep):
@@ -492,11 +496,11 @@ class Session:
     stands: after every extend_raw() the row is align_db of those W events normalised over themselves, and info["q_events"] and
     lengths() report W."""
 
-    def __init__(self, aligner, n_slots, starts=True, resweep=False, flags=None):
+    def __init__(self, aligner, n_slots, starts=True, resweep=False, flags=None, spread=False):
         self._al = aligner
         self._L = aligner._L
         self._h = C.c_void_p()
-        fl = _session_flags(starts, resweep) if flags is None else int(flags)
+        fl = (_session_flags(starts, resweep) if flags is None else int(flags)) | (SESSION_SPREAD if spread else 0)
         self.n_slots, self.starts, self.resweep = int(n_slots), not fl & SESSION_NO_START, bool(fl & SESSION_RESWEEP)
         _check(self._L.sfa_session_create(aligner._h, self.n_slots, fl, C.byref(self._h)), "sfa_session_create")
         self._al_h = aligner._h.value  # the native context this session belongs to

@@ -78,6 +78,7 @@ struct RealtimeOpt {
                                    // (SFA_RECAL_AT_END), and q is the last of recal_at, so a full read over q
     bool resweep = false;          // --resweep: the session is created with SFA_SESSION_RESWEEP (lifts --rna's need for --invert)
     int32_t candidates = 0;        // --candidates: candidate lines (tp:A:S) behind every primary line, 1..4 (0: none)
+    bool spread = false;           // --spread: one context over the whole --device list (sfa_init_devices), the session with SFA_SESSION_SPREAD
 };
 
 // options.cpp: the option table, help and every check that needs no file and no device (exits for -V and help)

@@ -19,7 +19,7 @@ enum LongOpt {
     O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
     O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
     O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE,
-    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS
+    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD
 };
 
 const option kLongOptions[] = {
@@ -115,7 +115,7 @@ const option kRealtimeOptions[] = {
     {"recalibrate", required_argument, 0, O_RECALIBRATE}, {"recalibrate-at-end", no_argument, 0, O_RECALIBRATE_AT_END},
     {"resweep", no_argument, 0, O_RESWEEP}, {"dtw-std", no_argument, 0, O_DTW_STD}, {"from-end", no_argument, 0, O_FROM_END}, {"sam", no_argument, 0, 'a'},
     {"secondary", required_argument, 0, O_SECONDARY}, {"ranks", required_argument, 0, O_RANKS},
-    {"candidates", required_argument, 0, O_CANDIDATES},
+    {"candidates", required_argument, 0, O_CANDIDATES}, {"spread", no_argument, 0, O_SPREAD},
     {0, 0, 0, 0}};
 
 void realtime_help(FILE *fp, const RealtimeOpt &r) {
@@ -135,7 +135,9 @@ void realtime_help(FILE *fp, const RealtimeOpt &r) {
     fprintf(fp, "   -h                         help\n   -o FILE                    output to file [stdout]\n");
     fprintf(fp, "   --verbose INT              verbosity level [%d]\n   --version                  print version\n", r.o.verbosity);
     fprintf(fp, "   --pore STR                 set the pore chemistry (r9, r10 or rna004) [auto]\n");
-    fprintf(fp, "   --device INT               the GPU to use (a session lives on one device) [0]\n");
+    fprintf(fp, "   --device INT[,INT...]      the GPU to use; a list needs --spread [0]\n");
+    fprintf(fp, "   --spread                   deal the channels over every GPU of --device (channel i on the i %% G-th; a GPU listed twice\n"
+                "                              counts twice): the session is created with SFA_SESSION_SPREAD.  Same output [off]\n");
     fprintf(fp, "   --kmer-model FILE          nucleotide k-mer model file (required: builtin models are not bundled)\n");
     fprintf(fp, "   --rna                      the dataset is direct RNA (needs --invert or --resweep: a session cannot extend a reversed query)\n");
     fprintf(fp, "   --invert                   reverse the reference events instead of query\n");
@@ -206,6 +208,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
             case O_RECALIBRATE_AT_END: r.recal_at_end = true; break;
             case O_RESWEEP: r.resweep = true; break;
             case O_CANDIDATES: candidates = optarg; break;
+            case O_SPREAD: r.spread = true; break;
             default: realtime_help(stderr, r); exit(EXIT_FAILURE);
         }
     }
@@ -228,7 +231,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
         r.candidates = static_cast<int32_t>(v);
     }
     if (o.ranks != 0) die("realtime: --ranks is not available: a replay is one process on one device");
-    if (o.devices.size() != 1) die("realtime: --device takes exactly one GPU: a session's rows live on one device");
+    if (o.devices.size() != 1 && !r.spread) die("realtime: --device takes exactly one GPU: a session's rows live on one device (--spread deals the channels over a list)");
     if ((o.flag & F_INV) && !(o.flag & F_RNA)) die("Inversion is only available for RNA.");
     if ((o.flag & F_RNA) && !(o.flag & F_INV) && !r.resweep) die("realtime: --rna needs --invert (or --resweep): without it the query rows are the events reversed, and a session cannot take new events as row 0");
     if (r.norm_events < 0) r.norm_events = o.query;

@@ -3,7 +3,8 @@
 // it stands for.  The hot path is the library's (sfa_session_extend_raw: detector, normalisation -- frozen, or growing with the
 // read under --recalibrate; with --resweep swept only when that window changes, which is what direct RNA without --invert
 // needs --, sweep); what runs here
-// is the staging of a tick's samples, the decision rule and the printing.
+// is the staging of a tick's samples, the decision rule and the printing.  With --spread the session's channels are dealt over
+// every GPU of --device (SFA_SESSION_SPREAD); the schedule counts ticks, so the output is the same bytes.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -151,10 +152,12 @@ int realtime_run(int argc, char **argv, double t0) {
         die("realtime: the file holds direct RNA: pass --rna --invert, or --rna --resweep (a session cannot extend a reversed query)");
     const Reference ref(o);
     Context ctx;
-    if (sfa_init(&ctx.c, &ref.view, o.flag, o.devices[0]) != SFA_OK) die(std::string("accelerator init failed: ") + sfa_last_error());
+    // --spread: one context over the whole device list, the channels dealt over its devices; else the first device
+    const int inited = r.spread ? sfa_init_devices(&ctx.c, &ref.view, o.flag, o.devices.data(), static_cast<int>(o.devices.size())) : sfa_init(&ctx.c, &ref.view, o.flag, o.devices[0]);
+    if (inited != SFA_OK) die(std::string("accelerator init failed: ") + sfa_last_error());
     if (sfa_set_pore(ctx.c, o.pore_flag) != SFA_OK) die(sfa_last_error());
     sfa_session_t *se = nullptr;  // (freed with its context)
-    if (sfa_session_create(ctx.c, r.channels, r.resweep ? SFA_SESSION_RESWEEP : 0, &se) != SFA_OK) die(std::string("session: ") + sfa_last_error());
+    if (sfa_session_create(ctx.c, r.channels, (r.resweep ? SFA_SESSION_RESWEEP : 0) | (r.spread ? SFA_SESSION_SPREAD : 0), &se) != SFA_OK) die(std::string("session: ") + sfa_last_error());
     if (sfa_session_raw_config(se, o.prefix, r.norm_events, o.query) != SFA_OK) die(std::string("session: ") + sfa_last_error());
     if (!r.recal_at.empty() || r.recal_at_end)
         if (sfa_session_raw_recalibrate(se, r.recal_at.data(), static_cast<int32_t>(r.recal_at.size()), r.recal_at_end ? SFA_RECAL_AT_END : 0) != SFA_OK)

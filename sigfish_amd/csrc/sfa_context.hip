@@ -165,6 +165,7 @@ int sfa_init_devices(sfa_ctx_t **out, const sfa_ref_t *ref, uint32_t flag, const
 void sfa_destroy(sfa_ctx_t *c) {
     if (!c) return;
     if (!c->shards.empty()) {
+        sfa::destroy_sessions(c);  // spread sessions: their sub-sessions leave the shards' lists here, while the shards exist
         c->workers.clear();  // joins the shard threads (none has a job: every entry point waits for its shards)
         for (sfa_ctx *sh : c->shards) sfa_destroy(sh);
         delete c;

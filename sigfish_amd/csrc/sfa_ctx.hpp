@@ -7,7 +7,8 @@
 //   sfa_align.hip    the alignment stage: planner -> launches (wave kernels, row strips) -> rows; the batch entry points
 //   sfa_maps.hip     event maps of the last call's rows, and the core sfa_session_event_maps shares with it (sdtw_path.hpp)
 //   sfa_session.hip  alignment sessions: a slot's sweep extended chunk by chunk below its carried row (sdtw_session.hpp)
-//                    -- its state one struct per feature (namespace sess), its host rules in session_plan.hpp (pure C++, as sfa_plan.hpp)
+//                    -- its state one struct per feature (namespace sess), its host rules in session_plan.hpp (pure C++, as sfa_plan.hpp);
+//                    on a group context a session spread over the shards (session_spread.hpp: placement and partition)
 //   sfa_pre.hip      the stages in front of it on the device: raw samples / BLOW5 records in (events_kernels.hpp, blow5_kernels.hpp)
 // There is NO CPU fallback: every failure is reported through the return code + sfa_last_error().
 #pragma once
@@ -395,7 +396,8 @@ struct sfa_ctx {
     sfa_profile_t prof{};
     bool prof_pending = false;
     bool in_slice = false;  // align_device is running one slice of a cut-up batch
-    std::vector<struct sfa_session *> sessions;  // live sessions of this context (sfa_session.hip); sfa_destroy frees them first
+    std::vector<struct sfa_session *> sessions;  // live sessions of this context (sfa_session.hip); sfa_destroy frees them first (a group
+                                                 // context's are its spread sessions: freed before the shards their sub-sessions live on)
 };
 
 // ---- internal functions that cross unit boundaries ----

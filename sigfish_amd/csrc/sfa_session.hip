@@ -9,12 +9,15 @@
 //   sess::AutoStart   sfa_session_raw_auto_start (events_auto_stream.hpp): retained samples, the slots' targets and skips
 //   sess::Keep        sfa_session_keep_events: the events of an event-mode session's slots, kept for their maps
 //   sess::Maps        sfa_session_event_maps: the scratch of a call (the core is sfa_maps.hip's), where every slot's query begins
-// The host rules -- which waves a call becomes, which points of the automatic start it passes -- are session_plan.hpp's.
+//   sess::Spread      SFA_SESSION_SPREAD on a group context: one sub-session per shard, a call's entries dealt to them
+// The host rules -- which waves a call becomes, which points of the automatic start it passes -- are session_plan.hpp's; where a
+// spread session's slots live and how a call is dealt to the shards, session_spread.hpp's.
 #include "sfa_ctx.hpp"
 #define SFA_DEFINE_SESSION_KERNELS  // (this unit holds the plain kernel of sdtw_session.hpp)
 #include "sdtw_session.hpp"
 #include "events_stream.hpp"
 #include "events_auto_stream.hpp"
+#include "session_spread.hpp"
 
 namespace sfa {
 // defined in sfa_align.hip, the unit that holds the plain kernels of sdtw_kernels.hpp
@@ -168,6 +171,29 @@ struct Maps {  // sfa_session_event_maps
     }
 };
 
+// SFA_SESSION_SPREAD on a group context: the session is one ordinary session per shard that holds slots (global slot i: local
+// slot i / G of subs[i % G]); every entry point deals its entries to them (session_spread.hpp), runs the shards side by side
+// (for_each_shard) and puts the answers back in the caller's order.  What a call packs or collects per shard lies here and is
+// reused from call to call: a tick allocates nothing once the buffers have grown to its size.
+struct Spread {
+    std::vector<sfa_session *> subs;  // [G]; nullptr: a trailing shard of a session with fewer slots than shards
+    sfa::SpreadPart part;             // of a call
+    struct Shard {                    // of a call, per shard: the payload packed, per-entry arguments gathered, answers
+        std::vector<float> events;
+        std::vector<int16_t> raw;
+        std::vector<double> scaling;
+        std::vector<uint8_t> end;
+        std::vector<sfa_result_t> rows;
+        std::vector<sfa_session_raw_info_t> info;
+        std::vector<sfa_session_auto_t> autos;
+        std::vector<int64_t> len;
+        std::vector<uint64_t> span;
+        int32_t on_host = 0;
+    };
+    std::vector<Shard> shard;  // [G]
+    bool broken = false;       // a configuration call went through on some shards and failed on another: only sfa_session_destroy is left
+};
+
 }  // namespace sess
 
 // `delete` frees every buffer and event of the session, in whatever order the members stand.  That relies on two things only:
@@ -186,13 +212,18 @@ struct sfa_session {
     sess::AutoStart autos;
     sess::Keep keep;
     sess::Maps maps;
+    std::unique_ptr<sess::Spread> spread;  // SFA_SESSION_SPREAD on a group context: `c` is the group, everything above is unused
+    int32_t name_first = 0, name_step = 1;  // a sub-session of a spread session: local slot l is the caller's slot l * step + first (messages)
 };
 
 namespace {
 
 const sfa_result_t kNoRow = {-1, -1, -1, INFINITY, INFINITY, 0, 0, 0, 0};
 size_t align8(size_t x) { return (x + 7) & ~static_cast<size_t>(7); }
-constexpr uint32_t kSessionFlags = SFA_SESSION_NO_START | SFA_SESSION_RESWEEP;  // (0x2 is not assigned)
+constexpr uint32_t kSessionFlags = SFA_SESSION_NO_START | SFA_SESSION_RESWEEP | SFA_SESSION_SPREAD;  // (0x2 is not assigned)
+
+// the number the caller knows slot sl by (a sub-session of a spread session holds every G-th slot)
+int32_t slot_name(const sfa_session *s, int32_t sl) { return sl * s->name_step + s->name_first; }
 
 // the first slot that is not empty (events, a poison flag, or samples in raw mode), -1: every slot is
 int32_t first_busy_slot(const sfa_session *s) {
@@ -439,15 +470,15 @@ int raw_check(sfa_session *s, const int32_t *slot, const int16_t *raw, const int
         if (int rc = claim_slot(s, sl, "sfa_session_extend_raw")) return rc;
         const int64_t l = raw_off[i + 1] - raw_off[i];
         if (l < 0) return fail(SFA_EINVAL, "sfa_session_extend_raw: raw_off not monotone");
-        if (l > 0 && (r.slots[sl].status & sfa::kRawEnded)) return fail(SFA_EINVAL, "sfa_session_extend_raw: slot %d has seen its end of read; it takes no samples until it is reset", sl);
-        if (r.slots[sl].n + l > INT32_MAX / 2) return fail(SFA_ERANGE, "sfa_session_extend_raw: slot %d would hold more than 2^30 samples", sl);
+        if (l > 0 && (r.slots[sl].status & sfa::kRawEnded)) return fail(SFA_EINVAL, "sfa_session_extend_raw: slot %d has seen its end of read; it takes no samples until it is reset", slot_name(s, sl));
+        if (r.slots[sl].n + l > INT32_MAX / 2) return fail(SFA_ERANGE, "sfa_session_extend_raw: slot %d would hold more than 2^30 samples", slot_name(s, sl));
         const double *sc = scaling + 3 * static_cast<size_t>(i);
         if (!r.slots[sl].fresh && memcmp(sc, r.slots[sl].scaling, 3 * sizeof(double)) != 0)
-            return fail(SFA_EINVAL, "sfa_session_extend_raw: slot %d: digitisation, offset and range are fixed by a slot's first chunk after a reset", sl);
+            return fail(SFA_EINVAL, "sfa_session_extend_raw: slot %d: digitisation, offset and range are fixed by a slot's first chunk after a reset", slot_name(s, sl));
         const sfa::RawScale rs = sfa::raw_scale(sc[0], sc[1], sc[2]);
         r.scale[2 * static_cast<size_t>(i)] = rs.offset;
         r.scale[2 * static_cast<size_t>(i) + 1] = rs.unit;
-        if (!std::isfinite(rs.offset) || !std::isfinite(rs.unit)) return fail(SFA_EINVAL, "sfa_session_extend_raw: slot %d: the scaling is not finite", sl);
+        if (!std::isfinite(rs.offset) || !std::isfinite(rs.unit)) return fail(SFA_EINVAL, "sfa_session_extend_raw: slot %d: the scaling is not finite", slot_name(s, sl));
     }
     const int64_t total = raw_off[n] - raw_off[0];
     if (total > INT32_MAX / 2) return fail(SFA_ERANGE, "sfa_session_extend_raw: more than 2^30 samples in one call");
@@ -646,6 +677,354 @@ int raw_fill_info(sfa_session *s, const int32_t *slot, int32_t n, sfa_session_ra
     return SFA_OK;
 }
 
+// ---- the two extend entry points in two halves: what a call is refused for, on the host alone, and the work.  A plain session
+// runs one behind the other; a spread session asks every shard before any shard works, so a refused call changes no shard ----
+
+int extend_check(sfa_session *s, const int32_t *slot, const float *events, const int64_t *ev_off, int32_t n) {
+    if (s->resweep)
+        return fail(SFA_EINVAL, "sfa_session_extend: the session was created with SFA_SESSION_RESWEEP: the caller's events are not kept, so nothing could be "
+                                "swept again; it takes samples (sfa_session_raw_config, sfa_session_extend_raw)");
+    if (s->raw.on) return fail(SFA_EINVAL, "sfa_session_extend: the session is in raw mode (sfa_session_raw_config): it takes samples, sfa_session_extend_raw");
+    if (n == 0) return SFA_OK;
+    begin_call(s);
+    for (int32_t i = 0; i < n; ++i) {
+        if (int rc = claim_slot(s, slot[i], "sfa_session_extend")) return rc;
+        const int64_t l = ev_off[i + 1] - ev_off[i];
+        if (l < 0) return fail(SFA_EINVAL, "sfa_session_extend: ev_off not monotone");
+        if (s->rows.len[slot[i]] + l > INT32_MAX / 2) return fail(SFA_ERANGE, "sfa_session_extend: slot %d would hold more than 2^30 events", slot_name(s, slot[i]));
+    }
+    if (ev_off[n] - ev_off[0] > 0 && !events) return fail(SFA_EINVAL, "sfa_session_extend: null events");
+    return SFA_OK;
+}
+
+int extend_run(sfa_session *s, const int32_t *slot, const float *events, const int64_t *ev_off, int32_t n, sfa_result_t *out) {
+    sfa_ctx *c = s->c;
+    const int64_t nq = ev_off[n] - ev_off[0];
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = sfa::resolve_profile(c)) return rc;  // a batch submitted and never waited for: its error words are this call's
+    std::vector<sfa::Chunk> ch(n);
+    for (int32_t i = 0; i < n; ++i) ch[i] = sfa::Chunk{ev_off[i] - ev_off[0], ev_off[i + 1] - ev_off[i]};
+    return sweep_chunks(s, slot, ch.data(), n, events ? events + ev_off[0] : nullptr, nq, nullptr, out);
+}
+
+int extend_raw_check(sfa_session *s, const int32_t *slot, const int16_t *raw, const int64_t *raw_off, const double *scaling, int32_t n) {
+    if (!s->raw.on) return fail(SFA_EINVAL, "sfa_session_extend_raw: the session takes events (sfa_session_extend) until sfa_session_raw_config");
+    return n == 0 ? static_cast<int>(SFA_OK) : raw_check(s, slot, raw, raw_off, scaling, n);
+}
+
+int extend_raw_run(sfa_session *s, const int32_t *slot, const int16_t *raw, const int64_t *raw_off, const double *scaling, const uint8_t *end_of_read, int32_t n,
+                   sfa_result_t *out, sfa_session_raw_info_t *info) {
+    sfa_ctx *c = s->c;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = sfa::resolve_profile(c)) return rc;
+    if (int rc = raw_stage_tables(s, slot, raw_off, end_of_read, n)) return rc;
+    if (int rc = raw_plan_points(s, slot, raw_off, end_of_read, n)) return rc;
+    if (int rc = raw_launch_detector(s, raw, raw_off, n)) return rc;
+    if (int rc = raw_launch_auto(s, n)) return rc;  // (retention and evaluation)
+    if (int rc = raw_launch_norm(s, n)) return rc;
+    std::vector<sfa::Chunk> ch(n);
+    raw_take_results(s, slot, raw_off, scaling, n, ch.data());
+    if (int rc = sweep_chunks(s, slot, ch.data(), n, nullptr, 0, s->raw.d_query.as<float>(), out)) return rc;
+    return raw_fill_info(s, slot, n, info);
+}
+
+// ---- sfa_session_event_maps behind its argument checks: the rows idx[0..n_idx) of the caller's (nullptr: 0..n_idx-1), row
+// idx[t] of slot slot_of[t]; its map goes to pairs + 2 * map_off[idx[t]] ----
+int session_maps_rows(sfa_session *s, const sfa_result_t *rows, const int32_t *slot_of, const int32_t *idx, int32_t n_idx, const int64_t *map_off, int32_t *pairs,
+                      int32_t *n_on_host) {
+    static const char *const who = "sfa_session_event_maps";
+    sfa_ctx *c = s->c;
+    HIP_TRY(hipSetDevice(c->device));
+    if (s->keep.on())  // (the flags the keep kernel wrote; the wait below is the call's own)
+        HIP_TRY(hipMemcpyAsync(s->keep.h_over.p, s->keep.d_over.p, static_cast<size_t>(s->n_slots), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = sfa::resolve_profile(c)) return rc;
+    sess::Maps &mp = s->maps;
+    if (int rc = mp.reserve(s->n_slots, static_cast<size_t>(n_idx))) return rc;
+    // the query of a slot as swept: raw mode, its row of d_query (a resweep session stores the window in DP order already, so
+    // nothing is reversed here); event mode, its kept events
+    const int64_t stride = s->raw.on ? s->raw.query : s->keep.max_events;
+    const float *base = s->raw.on ? s->raw.d_query.as<float>() : s->keep.d_keep.as<float>();
+    for (int32_t sl = 0; sl < s->n_slots; ++sl) mp.q_off[sl] = sl * stride;
+    for (int32_t t = 0; t < n_idx; ++t) {
+        const int32_t k = idx ? idx[t] : t;
+        mp.band[t].k = k;
+        const sfa_result_t &r = rows[k];
+        if (!r.valid || r.rid < 0) continue;  // no row (an empty or poisoned slot gives such rows): nothing is written
+        const int32_t sl = slot_of[t];
+        if (s->rows.poison[sl] || s->rows.len[sl] == 0)
+            return fail(SFA_EINVAL, "%s: row %d: slot %d is empty or poisoned; it has no row in its current state", who, k, slot_name(s, sl));
+        if (s->keep.on() && (s->keep.h_over.as<uint8_t>()[sl] || s->rows.len[sl] > s->keep.max_events))
+            return fail(SFA_EINVAL, "%s: row %d: slot %d has received %lld events, more than the %d the session keeps; it has no maps until it is reset", who, k,
+                        slot_name(s, sl), (long long)s->rows.len[sl], s->keep.max_events);
+        if (int rc = sfa::map_row_band(c, r, k, s->rows.len[sl], map_off[k + 1] - map_off[k], who, "this reference", &mp.band[t])) return rc;
+        mp.band[t].query = sl;
+    }
+    return sfa::event_maps_core(c, mp.scratch, base, mp.q_off.data(), mp.q_off.size(), false, mp.band.data(), n_idx, map_off, pairs, n_on_host);
+}
+
+// ---- spread sessions (SFA_SESSION_SPREAD on a group context): every entry point dealt to the shards' sub-sessions.  The rules
+// are session_spread.hpp's; here the prologue of each entry point: partition, the sub-calls side by side on the context's shard
+// threads (for_each_shard: shard 0 on the caller's), the answers back in the caller's order.  Calls that touch no device
+// (reset, lengths, the automatic start's records) visit the shards in turn on the caller's thread ----
+
+int spread_create(sfa_ctx *g, int32_t n_slots, uint32_t flags, sfa_session **out) {
+    if (n_slots <= 0) return fail(SFA_EINVAL, "sfa_session_create: n_slots must be positive, not %d", n_slots);
+    if (flags & ~kSessionFlags) return fail(SFA_EINVAL, "sfa_session_create: unknown flag bits 0x%x", flags | SFA_SESSION_SPREAD);
+    const int32_t G = static_cast<int32_t>(g->shards.size());
+    std::unique_ptr<sfa_session> s(new sfa_session());
+    s->c = g;
+    s->n_slots = n_slots;
+    s->track = !(flags & SFA_SESSION_NO_START);
+    s->resweep = (flags & SFA_SESSION_RESWEEP) != 0;
+    s->spread.reset(new sess::Spread());
+    sess::Spread &sp = *s->spread;
+    sp.subs.assign(static_cast<size_t>(G), nullptr);
+    sp.shard.resize(static_cast<size_t>(G));
+    for (int32_t r = 0; r < G; ++r) {
+        const int32_t m = sfa::spread_slots_of(n_slots, r, G);
+        if (m == 0) continue;  // (a session with fewer slots than shards: the trailing shards hold none)
+        if (int rc = sfa_session_create(g->shards[r], m, flags, &sp.subs[r])) {  // this shard's code and message are the call's
+            const std::string msg = sfa::last_error_slot();
+            for (int32_t q = r - 1; q >= 0; --q) sfa_session_destroy(sp.subs[q]);
+            sfa::last_error_slot() = msg;
+            return rc;
+        }
+        sp.subs[r]->name_first = r;
+        sp.subs[r]->name_step = G;
+    }
+    g->sessions.push_back(s.get());
+    *out = s.release();
+    return SFA_OK;
+}
+
+int spread_live(const sfa_session *s, const char *who) {
+    if (s->spread->broken)
+        return fail(SFA_EINVAL, "%s: a configuration call of this spread session failed on one shard after others had taken it; the session takes nothing but "
+                                "sfa_session_destroy",
+                    who);
+    return SFA_OK;
+}
+
+// the call's entries by shard (left in spread->part), after the refusals a session makes by itself -- for the whole call, before
+// any shard hears of it
+int spread_deal(sfa_session *s, const int32_t *slot, int32_t n, bool once, const char *who) {
+    const sfa::SpreadRefusal bad = sfa::spread_partition(slot, n, s->n_slots, static_cast<int32_t>(s->c->shards.size()), once, &s->spread->part);
+    if (bad.why == sfa::kSpreadRange) return fail(SFA_EINVAL, "%s: slot %d out of range (the session has %d)", who, bad.slot, s->n_slots);
+    if (bad.why == sfa::kSpreadTwice) return fail(SFA_EINVAL, "%s: slot %d is named twice in one call", who, bad.slot);
+    return SFA_OK;
+}
+
+// fn(the shard's sub-session, its part of the call, its buffers) on every shard that has entries, side by side
+template <typename F>
+int spread_run(sfa_session *s, F fn) {
+    sess::Spread &sp = *s->spread;
+    return sfa::for_each_shard(s->c, [&](size_t r) { return sp.part.shard[r].n() == 0 ? static_cast<int>(SFA_OK) : fn(sp.subs[r], sp.part.shard[r], sp.shard[r]); });
+}
+// the same in turn on the caller's thread, for calls that are host arithmetic
+template <typename F>
+int spread_visit(sfa_session *s, F fn) {
+    sess::Spread &sp = *s->spread;
+    for (size_t r = 0; r < sp.subs.size(); ++r)
+        if (sp.part.shard[r].n() > 0)
+            if (int rc = fn(sp.subs[r], sp.part.shard[r], sp.shard[r])) return rc;
+    return SFA_OK;
+}
+
+// A shard an extend call has nothing for does what a session call does in front of its work (a batch submitted and never waited
+// for: its error is this call's) and leaves a profile that adds nothing: sfa_get_profile on the group is the slowest shard's
+// times and the summed counts of THIS call
+int spread_idle(sfa_ctx *c) {
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = sfa::resolve_profile(c)) return rc;
+    sfa_profile_t pr{};
+    pr.segment_reruns = c->seg.seg_reruns;
+    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
+    c->prof = pr;
+    return SFA_OK;
+}
+
+int spread_extend(sfa_session *s, const int32_t *slot, const float *events, const int64_t *ev_off, int32_t n, sfa_result_t *out) {
+    static const char *const who = "sfa_session_extend";
+    if (int rc = spread_live(s, who)) return rc;
+    sess::Spread &sp = *s->spread;
+    if (int rc = extend_check(sp.subs[0], nullptr, nullptr, nullptr, 0)) return rc;  // (the session's kind: the same on every shard)
+    if (n == 0) return SFA_OK;
+    if (int rc = spread_deal(s, slot, n, true, who)) return rc;
+    sfa::spread_offsets(ev_off, &sp.part);
+    if (int rc = spread_visit(s, [&](sfa_session *sub, const sfa::SpreadShardPart &p, sess::Spread::Shard &) {
+            return extend_check(sub, p.local.data(), events, p.off.data(), p.n());
+        }))
+        return rc;
+    // events + absolute offsets cannot name a subset that is not contiguous: every shard's chunks are packed back to back
+    return sfa::for_each_shard(s->c, [&](size_t r) {
+        const sfa::SpreadShardPart &p = sp.part.shard[r];
+        sess::Spread::Shard &b = sp.shard[r];
+        if (p.n() == 0) return spread_idle(s->c->shards[r]);
+        b.events.resize(static_cast<size_t>(std::max<int64_t>(p.off.back(), 1)));
+        sfa::spread_pack(p, events, ev_off, b.events.data());
+        b.rows.resize(p.local.size());
+        if (int rc = extend_run(sp.subs[r], p.local.data(), b.events.data(), p.off.data(), p.n(), b.rows.data())) return rc;
+        sfa::spread_scatter(p, b.rows.data(), out);
+        return static_cast<int>(SFA_OK);
+    });
+}
+
+int spread_extend_raw(sfa_session *s, const int32_t *slot, const int16_t *raw, const int64_t *raw_off, const double *scaling, const uint8_t *end_of_read, int32_t n,
+                      sfa_result_t *out, sfa_session_raw_info_t *info) {
+    static const char *const who = "sfa_session_extend_raw";
+    if (int rc = spread_live(s, who)) return rc;
+    sess::Spread &sp = *s->spread;
+    if (int rc = extend_raw_check(sp.subs[0], nullptr, nullptr, nullptr, nullptr, 0)) return rc;
+    if (n == 0) return SFA_OK;
+    if (int rc = spread_deal(s, slot, n, true, who)) return rc;
+    sfa::spread_offsets(raw_off, &sp.part);
+    if (int rc = spread_visit(s, [&](sfa_session *sub, const sfa::SpreadShardPart &p, sess::Spread::Shard &b) {
+            b.scaling.resize(3 * p.local.size());
+            sfa::spread_gather(p, scaling, b.scaling.data(), 3);
+            return extend_raw_check(sub, p.local.data(), raw, p.off.data(), b.scaling.data(), p.n());
+        }))
+        return rc;
+    // (samples + absolute offsets: as for the events, a shard's chunks are packed back to back)
+    return sfa::for_each_shard(s->c, [&](size_t r) {
+        const sfa::SpreadShardPart &p = sp.part.shard[r];
+        sess::Spread::Shard &b = sp.shard[r];
+        if (p.n() == 0) return spread_idle(s->c->shards[r]);
+        b.raw.resize(static_cast<size_t>(std::max<int64_t>(p.off.back(), 1)));
+        sfa::spread_pack(p, raw, raw_off, b.raw.data());
+        if (end_of_read) {
+            b.end.resize(p.local.size());
+            sfa::spread_gather(p, end_of_read, b.end.data());
+        }
+        b.rows.resize(p.local.size());
+        b.info.resize(p.local.size());
+        if (int rc = extend_raw_run(sp.subs[r], p.local.data(), b.raw.data(), p.off.data(), b.scaling.data(), end_of_read ? b.end.data() : nullptr, p.n(), b.rows.data(),
+                                    b.info.data()))
+            return rc;
+        sfa::spread_scatter(p, b.rows.data(), out);
+        sfa::spread_scatter(p, b.info.data(), info);
+        return static_cast<int>(SFA_OK);
+    });
+}
+
+int spread_reset(sfa_session *s, const int32_t *slot, int32_t n) {
+    static const char *const who = "sfa_session_reset";
+    if (int rc = spread_live(s, who)) return rc;
+    if (!slot) {
+        for (sfa_session *sub : s->spread->subs)
+            if (sub) (void)sfa_session_reset(sub, nullptr, 0);
+        return SFA_OK;
+    }
+    if (n < 0) return fail(SFA_EINVAL, "sfa_session_reset: negative count");
+    if (int rc = spread_deal(s, slot, n, false, who)) return rc;
+    return spread_visit(s, [&](sfa_session *sub, const sfa::SpreadShardPart &p, sess::Spread::Shard &) { return sfa_session_reset(sub, p.local.data(), p.n()); });
+}
+
+int spread_lengths(sfa_session *s, const int32_t *slot, int32_t n, int64_t *len) {
+    static const char *const who = "sfa_session_lengths";
+    if (int rc = spread_live(s, who)) return rc;
+    if (!slot && n != s->n_slots) return fail(SFA_EINVAL, "sfa_session_lengths: without a slot list n must be the session's %d slots, not %d", s->n_slots, n);
+    if (int rc = spread_deal(s, slot, n, false, who)) return rc;  // (no list: every slot, in order)
+    return spread_visit(s, [&](sfa_session *sub, const sfa::SpreadShardPart &p, sess::Spread::Shard &b) {
+        b.len.resize(p.local.size());
+        if (int rc = sfa_session_lengths(sub, p.local.data(), p.n(), b.len.data())) return rc;
+        sfa::spread_scatter(p, b.len.data(), len);
+        return static_cast<int>(SFA_OK);
+    });
+}
+
+int spread_candidates(sfa_session *s, const int32_t *slot, int32_t n, sfa_result_t *sec) {
+    static const char *const who = "sfa_session_candidates";
+    if (int rc = spread_live(s, who)) return rc;
+    if (int rc = sfa_session_candidates(s->spread->subs[0], nullptr, 0, nullptr)) return rc;  // (a session that keeps none)
+    if (int rc = spread_deal(s, slot, n, false, who)) return rc;
+    return spread_run(s, [&](sfa_session *sub, const sfa::SpreadShardPart &p, sess::Spread::Shard &b) {
+        b.rows.resize(4 * p.local.size());
+        if (int rc = sfa_session_candidates(sub, p.local.data(), p.n(), b.rows.data())) return rc;
+        sfa::spread_scatter(p, b.rows.data(), sec, 4);
+        return static_cast<int>(SFA_OK);
+    });
+}
+
+int spread_query_span(sfa_session *s, const int32_t *slot, int32_t n, uint64_t *start_raw, uint64_t *end_raw) {
+    static const char *const who = "sfa_session_query_span";
+    if (int rc = spread_live(s, who)) return rc;
+    if (int rc = sfa_session_query_span(s->spread->subs[0], nullptr, 0, nullptr, nullptr)) return rc;  // (a session that is not in raw mode)
+    if (int rc = spread_deal(s, slot, n, false, who)) return rc;
+    return spread_run(s, [&](sfa_session *sub, const sfa::SpreadShardPart &p, sess::Spread::Shard &b) {
+        const size_t m = p.local.size();
+        b.span.resize(2 * m);
+        if (int rc = sfa_session_query_span(sub, p.local.data(), p.n(), b.span.data(), b.span.data() + m)) return rc;
+        sfa::spread_scatter(p, b.span.data(), start_raw);
+        sfa::spread_scatter(p, b.span.data() + m, end_raw);
+        return static_cast<int>(SFA_OK);
+    });
+}
+
+int spread_auto_start(sfa_session *s, const int32_t *slot, int32_t n, sfa_session_auto_t *out) {
+    static const char *const who = "sfa_session_auto_start";
+    if (int rc = spread_live(s, who)) return rc;
+    if (int rc = sfa_session_auto_start(s->spread->subs[0], nullptr, 0, nullptr)) return rc;  // (a session without the feature)
+    if (int rc = spread_deal(s, slot, n, false, who)) return rc;
+    return spread_visit(s, [&](sfa_session *sub, const sfa::SpreadShardPart &p, sess::Spread::Shard &b) {
+        b.autos.resize(p.local.size());
+        if (int rc = sfa_session_auto_start(sub, p.local.data(), p.n(), b.autos.data())) return rc;
+        sfa::spread_scatter(p, b.autos.data(), out);
+        return static_cast<int>(SFA_OK);
+    });
+}
+
+// the sub-session that owns *slot, which becomes its local number there (the one-slot calls: sfa_session_row, sfa_session_events)
+int spread_owner(sfa_session *s, int32_t *slot, const char *who, sfa_session **sub) {
+    if (int rc = spread_live(s, who)) return rc;
+    if (*slot < 0 || *slot >= s->n_slots) return fail(SFA_EINVAL, "%s: slot %d out of range (the session has %d)", who, *slot, s->n_slots);
+    const sfa::SpreadPlace at = sfa::spread_place(*slot, static_cast<int32_t>(s->c->shards.size()));
+    *sub = s->spread->subs[at.shard];
+    *slot = at.local;
+    return SFA_OK;
+}
+
+// A configuration call goes to every sub-session.  What it is refused for is the same on every shard -- the arguments, the
+// session's kind -- but for a slot in use, which is looked for on all of them first.  A shard that fails for a reason of its own
+// (memory) after others have taken the call leaves the session in two minds: it is broken
+template <typename F>
+int spread_config(sfa_session *s, const char *who, F fn) {
+    if (int rc = spread_live(s, who)) return rc;
+    sess::Spread &sp = *s->spread;
+    for (const sfa_session *sub : sp.subs)
+        if (sub)
+            if (const int32_t sl = first_busy_slot(sub); sl >= 0)
+                return fail(SFA_EINVAL, "%s: slot %d is not empty; a session is configured only while every slot is (sfa_session_reset)", who, slot_name(sub, sl));
+    std::vector<int> rcs(sp.subs.size(), 0);
+    const int rc = sfa::for_each_shard(s->c, [&](size_t r) { return sp.subs[r] ? (rcs[r] = fn(sp.subs[r])) : static_cast<int>(SFA_OK); });
+    size_t have = 0, failed = 0;
+    for (size_t r = 0; r < sp.subs.size(); ++r) have += sp.subs[r] != nullptr, failed += rcs[r] != SFA_OK;
+    if (failed != 0 && failed != have) sp.broken = true;
+    return rc;
+}
+
+int spread_event_maps(sfa_session *s, const sfa_result_t *rows, const int32_t *slot_of_row, int32_t n_rows, const int64_t *map_off, int32_t *pairs, int32_t *n_on_host) {
+    static const char *const who = "sfa_session_event_maps";
+    if (int rc = spread_live(s, who)) return rc;
+    sess::Spread &sp = *s->spread;
+    if (int rc = sfa_session_event_maps(sp.subs[0], nullptr, nullptr, 0, nullptr, nullptr, nullptr)) return rc;  // (a session that has no maps)
+    if (int rc = spread_deal(s, slot_of_row, n_rows, false, who)) return rc;
+    for (int32_t k = 0; k < n_rows; ++k)
+        if (map_off[k + 1] < map_off[k] || map_off[k] < 0) return fail(SFA_EINVAL, "%s: map_off not monotone at row %d", who, k);
+    // every shard writes its rows' pairs straight into the caller's, at the caller's map_off (as sfa_event_maps on a group context)
+    const int rc = spread_run(s, [&](sfa_session *sub, const sfa::SpreadShardPart &p, sess::Spread::Shard &b) {
+        b.on_host = 0;
+        return session_maps_rows(sub, rows, p.local.data(), p.index.data(), p.n(), map_off, pairs, &b.on_host);
+    });
+    if (!rc && n_on_host)
+        for (size_t r = 0; r < sp.subs.size(); ++r)
+            if (sp.part.shard[r].n() > 0) *n_on_host += sp.shard[r].on_host;
+    return rc;
+}
+
 }  // namespace
 
 namespace sfa {
@@ -666,7 +1045,12 @@ int64_t sfa_session_bytes(int64_t total_columns, int32_t n_slots, uint32_t sessi
 
 int sfa_session_create(sfa_ctx_t *c, int32_t n_slots, uint32_t session_flags, sfa_session_t **out) {
     if (!c || !out) return fail(SFA_EINVAL, "sfa_session_create: null argument");
-    if (!c->shards.empty()) return fail(SFA_EINVAL, "sfa_session_create: a session's rows live on one device; use a single-device context (sfa_init)");
+    if (!c->shards.empty()) {
+        if (!(session_flags & SFA_SESSION_SPREAD))
+            return fail(SFA_EINVAL, "sfa_session_create: a session's rows live on one device; use a single-device context (sfa_init), or SFA_SESSION_SPREAD");
+        return spread_create(c, n_slots, session_flags & ~static_cast<uint32_t>(SFA_SESSION_SPREAD), out);
+    }
+    // (on a single device SFA_SESSION_SPREAD changes nothing: the session is the plain one)
     if (c->flag & SFA_DTW) return fail(SFA_EINVAL, "sfa_session_create: sessions extend the subsequence DTW; the context has SFA_DTW");
     const bool resweep = (session_flags & SFA_SESSION_RESWEEP) != 0;  // (unknown bits beside it are refused below)
     if ((c->flag & SFA_RNA) && !(c->flag & SFA_INV) && !resweep)
@@ -700,8 +1084,9 @@ int sfa_session_create(sfa_ctx_t *c, int32_t n_slots, uint32_t session_flags, sf
 int sfa_session_candidates_config(sfa_session_t *s, int32_t n_candidates) {
     if (!s) return fail(SFA_EINVAL, "sfa_session_candidates_config: null session");
     if (n_candidates < 0 || n_candidates > 4) return fail(SFA_EINVAL, "sfa_session_candidates_config: n_candidates must be 0..4, not %d", n_candidates);
+    if (s->spread) return spread_config(s, "sfa_session_candidates_config", [&](sfa_session *sub) { return sfa_session_candidates_config(sub, n_candidates); });
     if (const int32_t sl = first_busy_slot(s); sl >= 0)
-        return fail(SFA_EINVAL, "sfa_session_candidates_config: slot %d is not empty; the lists are switched only while every slot is (sfa_session_reset)", sl);
+        return fail(SFA_EINVAL, "sfa_session_candidates_config: slot %d is not empty; the lists are switched only while every slot is (sfa_session_reset)", slot_name(s, sl));
     if (n_candidates > 0) {
         sfa_ctx *c = s->c;
         HIP_TRY(hipSetDevice(c->device));
@@ -716,6 +1101,7 @@ int sfa_session_candidates_config(sfa_session_t *s, int32_t n_candidates) {
 int sfa_session_candidates(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_result_t *sec) {
     if (!s) return fail(SFA_EINVAL, "sfa_session_candidates: null session");
     if (n < 0 || (n > 0 && (!slot || !sec))) return fail(SFA_EINVAL, "sfa_session_candidates: bad argument");
+    if (s->spread) return spread_candidates(s, slot, n, sec);
     if (s->cand.n_cand == 0) return fail(SFA_EINVAL, "sfa_session_candidates: the session keeps no candidates (sfa_session_candidates_config)");
     if (int rc = check_slots(s, slot, n, "sfa_session_candidates")) return rc;
     if (n == 0) return SFA_OK;
@@ -734,6 +1120,11 @@ int sfa_session_candidates(sfa_session_t *s, const int32_t *slot, int32_t n, sfa
 
 int64_t sfa_session_row(sfa_session_t *s, int32_t slot, int32_t contig, int32_t strand_char, float *cost, int32_t *start) {
     if (!s || !cost) return fail(SFA_EINVAL, "sfa_session_row: null session or null cost");
+    if (s->spread) {  // (the owning shard's)
+        sfa_session *sub = nullptr;
+        if (int rc = spread_owner(s, &slot, "sfa_session_row", &sub)) return rc;
+        return sfa_session_row(sub, slot, contig, strand_char, cost, start);
+    }
     sfa_ctx *c = s->c;
     if (int rc = check_slots(s, &slot, 1, "sfa_session_row")) return rc;
     if (contig < 0 || contig >= c->model.num_ref) return fail(SFA_EINVAL, "sfa_session_row: contig %d out of range (the reference has %d)", contig, c->model.num_ref);
@@ -741,8 +1132,8 @@ int64_t sfa_session_row(sfa_session_t *s, int32_t slot, int32_t contig, int32_t 
     if (strand_char != '+' && !(strand_char == '-' && strands == 2))
         return fail(SFA_EINVAL, "sfa_session_row: strand %d is neither '+' nor '-' (RNA has no '-')", strand_char);
     if (start && !s->track) return fail(SFA_EINVAL, "sfa_session_row: the session carries no start columns (SFA_SESSION_NO_START)");
-    if (s->rows.poison[slot]) return fail(SFA_EINVAL, "sfa_session_row: slot %d is poisoned (a chunk held a NaN or inf); it has no row until it is reset", slot);
-    if (s->rows.len[slot] == 0) return fail(SFA_EINVAL, "sfa_session_row: slot %d has no events, so no carried row", slot);
+    if (s->rows.poison[slot]) return fail(SFA_EINVAL, "sfa_session_row: slot %d is poisoned (a chunk held a NaN or inf); it has no row until it is reset", slot_name(s, slot));
+    if (s->rows.len[slot] == 0) return fail(SFA_EINVAL, "sfa_session_row: slot %d has no events, so no carried row", slot_name(s, slot));
     const int32_t job = contig * strands + (strand_char == '-' ? 1 : 0);
     const int64_t n = c->model.h_job_len[job], row0 = sfa::kSessionPad + static_cast<int64_t>(slot) * c->model.total_cols + s->rows.h_col_off[job];
     HIP_TRY(hipSetDevice(c->device));
@@ -754,6 +1145,8 @@ int64_t sfa_session_row(sfa_session_t *s, int32_t slot, int32_t contig, int32_t 
 
 void sfa_session_destroy(sfa_session_t *s) {
     if (!s) return;
+    if (s->spread)  // (the sub-sessions first, each from its shard's list; then this one from the group's)
+        for (sfa_session *sub : s->spread->subs) sfa_session_destroy(sub);
     sfa_ctx *c = s->c;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
@@ -763,6 +1156,7 @@ void sfa_session_destroy(sfa_session_t *s) {
 
 int sfa_session_reset(sfa_session_t *s, const int32_t *slot, int32_t n) {
     if (!s) return fail(SFA_EINVAL, "sfa_session_reset: null session");
+    if (s->spread) return spread_reset(s, slot, n);
     if (!slot) {  // every slot
         for (int32_t sl = 0; sl < s->n_slots; ++sl) reset_slot(s, sl);
         return SFA_OK;
@@ -775,6 +1169,7 @@ int sfa_session_reset(sfa_session_t *s, const int32_t *slot, int32_t n) {
 
 int sfa_session_lengths(sfa_session_t *s, const int32_t *slot, int32_t n, int64_t *len) {
     if (!s || !len || n < 0) return fail(SFA_EINVAL, "sfa_session_lengths: bad argument");
+    if (s->spread) return spread_lengths(s, slot, n, len);
     if (!slot) {
         if (n != s->n_slots) return fail(SFA_EINVAL, "sfa_session_lengths: without a slot list n must be the session's %d slots, not %d", s->n_slots, n);
         std::copy(s->rows.len.begin(), s->rows.len.end(), len);
@@ -789,27 +1184,9 @@ int sfa_session_lengths(sfa_session_t *s, const int32_t *slot, int32_t n, int64_
 
 int sfa_session_extend(sfa_session_t *s, const int32_t *slot, const float *events, const int64_t *ev_off, int32_t n, sfa_result_t *out) {
     if (!s || n < 0 || (n > 0 && (!slot || !ev_off || !out))) return fail(SFA_EINVAL, "sfa_session_extend: bad argument");
-    if (s->resweep)
-        return fail(SFA_EINVAL, "sfa_session_extend: the session was created with SFA_SESSION_RESWEEP: the caller's events are not kept, so nothing could be "
-                                "swept again; it takes samples (sfa_session_raw_config, sfa_session_extend_raw)");
-    if (s->raw.on) return fail(SFA_EINVAL, "sfa_session_extend: the session is in raw mode (sfa_session_raw_config): it takes samples, sfa_session_extend_raw");
-    if (n == 0) return SFA_OK;
-    sfa_ctx *c = s->c;
-    begin_call(s);
-    for (int32_t i = 0; i < n; ++i) {
-        if (int rc = claim_slot(s, slot[i], "sfa_session_extend")) return rc;
-        const int64_t l = ev_off[i + 1] - ev_off[i];
-        if (l < 0) return fail(SFA_EINVAL, "sfa_session_extend: ev_off not monotone");
-        if (s->rows.len[slot[i]] + l > INT32_MAX / 2) return fail(SFA_ERANGE, "sfa_session_extend: slot %d would hold more than 2^30 events", slot[i]);
-    }
-    const int64_t nq = ev_off[n] - ev_off[0];
-    if (nq > 0 && !events) return fail(SFA_EINVAL, "sfa_session_extend: null events");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int rc = sfa::resolve_profile(c)) return rc;  // a batch submitted and never waited for: its error words are this call's
-    std::vector<sfa::Chunk> ch(n);
-    for (int32_t i = 0; i < n; ++i) ch[i] = sfa::Chunk{ev_off[i] - ev_off[0], ev_off[i + 1] - ev_off[i]};
-    return sweep_chunks(s, slot, ch.data(), n, events ? events + ev_off[0] : nullptr, nq, nullptr, out);
+    if (s->spread) return spread_extend(s, slot, events, ev_off, n, out);
+    if (int rc = extend_check(s, slot, events, ev_off, n)) return rc;
+    return n == 0 ? static_cast<int>(SFA_OK) : extend_run(s, slot, events, ev_off, n, out);
 }
 
 // ---- event maps of a slot's row (the core: sfa_maps.hip) ----
@@ -823,11 +1200,12 @@ int64_t sfa_session_keep_bytes(int32_t n_slots, int32_t max_events) {
 
 int sfa_session_keep_events(sfa_session_t *s, int32_t max_events) {
     if (!s) return fail(SFA_EINVAL, "sfa_session_keep_events: null session");
+    if (s->spread) return spread_config(s, "sfa_session_keep_events", [&](sfa_session *sub) { return sfa_session_keep_events(sub, max_events); });
     if (s->resweep || s->raw.on)
         return fail(SFA_EINVAL, "sfa_session_keep_events: a raw-mode session keeps its slots' queries already (sfa_session_raw_config); this is for event-mode sessions");
     if (max_events < 0 || max_events > INT32_MAX / 2) return fail(SFA_EINVAL, "sfa_session_keep_events: max_events must be 0 .. 2^30, not %d", max_events);
     if (const int32_t sl = first_busy_slot(s); sl >= 0)
-        return fail(SFA_EINVAL, "sfa_session_keep_events: slot %d is not empty; events are kept from a slot's first chunk on, so it is switched only while every slot is empty (sfa_session_reset)", sl);
+        return fail(SFA_EINVAL, "sfa_session_keep_events: slot %d is not empty; events are kept from a slot's first chunk on, so it is switched only while every slot is empty (sfa_session_reset)", slot_name(s, sl));
     if (max_events > 0) {
         sfa_ctx *c = s->c;
         if (sfa_session_keep_bytes(s->n_slots, max_events) < 0) return fail(SFA_ENOMEM, "sfa_session_keep_events: the kept events do not fit");
@@ -845,6 +1223,7 @@ int sfa_session_event_maps(sfa_session_t *s, const sfa_result_t *rows, const int
     static const char *const who = "sfa_session_event_maps";
     if (!s || n_rows < 0 || (n_rows > 0 && (!rows || !slot_of_row || !map_off || !pairs))) return fail(SFA_EINVAL, "%s: bad argument", who);
     if (n_on_host) *n_on_host = 0;
+    if (s->spread) return spread_event_maps(s, rows, slot_of_row, n_rows, map_off, pairs, n_on_host);
     if (!s->track) return fail(SFA_EINVAL, "%s: the session carries no start columns (SFA_SESSION_NO_START), so its rows have no band", who);
     if (!s->raw.on && !s->keep.on())
         return fail(SFA_EINVAL, "%s: an event-mode session does not keep the caller's events unless asked to (sfa_session_keep_events)", who);
@@ -852,32 +1231,7 @@ int sfa_session_event_maps(sfa_session_t *s, const sfa_result_t *rows, const int
     for (int32_t k = 0; k < n_rows; ++k)
         if (map_off[k + 1] < map_off[k] || map_off[k] < 0) return fail(SFA_EINVAL, "%s: map_off not monotone at row %d", who, k);
     if (n_rows == 0) return SFA_OK;
-    sfa_ctx *c = s->c;
-    HIP_TRY(hipSetDevice(c->device));
-    if (s->keep.on())  // (the flags the keep kernel wrote; the wait below is the call's own)
-        HIP_TRY(hipMemcpyAsync(s->keep.h_over.p, s->keep.d_over.p, static_cast<size_t>(s->n_slots), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int rc = sfa::resolve_profile(c)) return rc;
-    sess::Maps &mp = s->maps;
-    if (int rc = mp.reserve(s->n_slots, static_cast<size_t>(n_rows))) return rc;
-    // the query of a slot as swept: raw mode, its row of d_query (a resweep session stores the window in DP order already, so
-    // nothing is reversed here); event mode, its kept events
-    const int64_t stride = s->raw.on ? s->raw.query : s->keep.max_events;
-    const float *base = s->raw.on ? s->raw.d_query.as<float>() : s->keep.d_keep.as<float>();
-    for (int32_t sl = 0; sl < s->n_slots; ++sl) mp.q_off[sl] = sl * stride;
-    for (int32_t k = 0; k < n_rows; ++k) {
-        mp.band[k].k = k;
-        const sfa_result_t &r = rows[k];
-        if (!r.valid || r.rid < 0) continue;  // no row (an empty or poisoned slot gives such rows): nothing is written
-        const int32_t sl = slot_of_row[k];
-        if (s->rows.poison[sl] || s->rows.len[sl] == 0) return fail(SFA_EINVAL, "%s: row %d: slot %d is empty or poisoned; it has no row in its current state", who, k, sl);
-        if (s->keep.on() && (s->keep.h_over.as<uint8_t>()[sl] || s->rows.len[sl] > s->keep.max_events))
-            return fail(SFA_EINVAL, "%s: row %d: slot %d has received %lld events, more than the %d the session keeps; it has no maps until it is reset", who, k, sl,
-                        (long long)s->rows.len[sl], s->keep.max_events);
-        if (int rc = sfa::map_row_band(c, r, k, s->rows.len[sl], map_off[k + 1] - map_off[k], who, "this reference", &mp.band[k])) return rc;
-        mp.band[k].query = sl;
-    }
-    return sfa::event_maps_core(c, mp.scratch, base, mp.q_off.data(), mp.q_off.size(), false, mp.band.data(), n_rows, map_off, pairs, n_on_host);
+    return session_maps_rows(s, rows, slot_of_row, nullptr, n_rows, map_off, pairs, n_on_host);
 }
 
 // ---- raw mode: samples in, rows out (events_stream.hpp) ----
@@ -891,11 +1245,12 @@ int64_t sfa_session_raw_bytes(int32_t n_slots, int32_t skip_events, int32_t quer
 
 int sfa_session_raw_config(sfa_session_t *s, int32_t skip_events, int32_t norm_events, int32_t query_events) {
     if (!s) return fail(SFA_EINVAL, "sfa_session_raw_config: null session");
+    if (s->spread) return spread_config(s, "sfa_session_raw_config", [&](sfa_session *sub) { return sfa_session_raw_config(sub, skip_events, norm_events, query_events); });
     if (skip_events < 0 || norm_events < 25 || norm_events > query_events)
         return fail(SFA_EINVAL, "sfa_session_raw_config: need skip >= 0 and 25 <= norm <= query, not skip %d, norm %d, query %d", skip_events, norm_events, query_events);
     if (static_cast<int64_t>(skip_events) + query_events > INT32_MAX / 2) return fail(SFA_ERANGE, "sfa_session_raw_config: more than 2^30 events per slot");
     if (const int32_t sl = first_busy_slot(s); sl >= 0)
-        return fail(SFA_EINVAL, "sfa_session_raw_config: slot %d is not empty; the mode of a session changes only while every slot is (sfa_session_reset)", sl);
+        return fail(SFA_EINVAL, "sfa_session_raw_config: slot %d is not empty; the mode of a session changes only while every slot is (sfa_session_reset)", slot_name(s, sl));
     HIP_TRY(hipSetDevice(s->c->device));
     if (sfa_session_raw_bytes(s->n_slots, skip_events, query_events) < 0) return fail(SFA_ENOMEM, "sfa_session_raw_config: the event tables do not fit");
     sess::Raw &r = s->raw;
@@ -922,13 +1277,14 @@ int64_t sfa_session_auto_bytes(int32_t n_slots, int32_t max_samples) {
 
 int sfa_session_raw_auto_start(sfa_session_t *s, int32_t every_samples, int32_t max_samples, uint32_t flags) {
     if (!s) return fail(SFA_EINVAL, "sfa_session_raw_auto_start: null session");
+    if (s->spread) return spread_config(s, "sfa_session_raw_auto_start", [&](sfa_session *sub) { return sfa_session_raw_auto_start(sub, every_samples, max_samples, flags); });
     if (!s->raw.on) return fail(SFA_EINVAL, "sfa_session_raw_auto_start: the session is not in raw mode (sfa_session_raw_config)");
     if (flags) return fail(SFA_EINVAL, "sfa_session_raw_auto_start: unknown flag bits 0x%x", flags);
     if (every_samples < 0 || max_samples < 0 || max_samples > sfa::kAutoMaxSamples)
         return fail(SFA_EINVAL, "sfa_session_raw_auto_start: need every_samples >= 0 and 0 <= max_samples <= %d, not %d and %d", sfa::kAutoMaxSamples, every_samples,
                     max_samples);
     if (const int32_t sl = first_busy_slot(s); sl >= 0)
-        return fail(SFA_EINVAL, "sfa_session_raw_auto_start: slot %d is not empty; the rule changes only while every slot is (sfa_session_reset)", sl);
+        return fail(SFA_EINVAL, "sfa_session_raw_auto_start: slot %d is not empty; the rule changes only while every slot is (sfa_session_reset)", slot_name(s, sl));
     sess::AutoStart &au = s->autos;
     if (max_samples == 0) {  // off
         au.max_samples = au.every = 0;
@@ -954,10 +1310,18 @@ int sfa_session_raw_auto_start(sfa_session_t *s, int32_t every_samples, int32_t 
     return SFA_OK;
 }
 
-double sfa_session_auto_ms(sfa_session_t *s) { return (s && s->autos.on()) ? s->autos.ms : -1.0; }
+double sfa_session_auto_ms(sfa_session_t *s) {
+    if (s && s->spread) {  // (the shards run side by side: the slowest)
+        double ms = -1.0;
+        for (sfa_session *sub : s->spread->subs) ms = std::max(ms, sfa_session_auto_ms(sub));
+        return ms;
+    }
+    return (s && s->autos.on()) ? s->autos.ms : -1.0;
+}
 
 int sfa_session_auto_start(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_session_auto_t *out) {
     if (!s || n < 0 || (n > 0 && (!slot || !out))) return fail(SFA_EINVAL, "sfa_session_auto_start: bad argument");
+    if (s->spread) return spread_auto_start(s, slot, n, out);
     if (!s->autos.on()) return fail(SFA_EINVAL, "sfa_session_auto_start: the session has no automatic query start (sfa_session_raw_auto_start)");
     for (int32_t i = 0; i < n; ++i) {
         if (int rc = check_slots(s, slot + i, 1, "sfa_session_auto_start")) return rc;
@@ -972,13 +1336,14 @@ int sfa_session_auto_start(sfa_session_t *s, const int32_t *slot, int32_t n, sfa
 
 int sfa_session_raw_recalibrate(sfa_session_t *s, const int32_t *at, int32_t n_at, uint32_t flags) {
     if (!s) return fail(SFA_EINVAL, "sfa_session_raw_recalibrate: null session");
+    if (s->spread) return spread_config(s, "sfa_session_raw_recalibrate", [&](sfa_session *sub) { return sfa_session_raw_recalibrate(sub, at, n_at, flags); });
     if (!s->raw.on) return fail(SFA_EINVAL, "sfa_session_raw_recalibrate: the session is not in raw mode (sfa_session_raw_config)");
     if (flags & ~static_cast<uint32_t>(SFA_RECAL_AT_END)) return fail(SFA_EINVAL, "sfa_session_raw_recalibrate: unknown flag bits 0x%x", flags);
     if (const char *why = sfa::recal_list_error(at, n_at, s->raw.norm, s->raw.query))
         return fail(SFA_EINVAL, "sfa_session_raw_recalibrate: %s; need norm < at[0] < ... < at[n - 1] <= query, at most %d points (norm %d, query %d)", why,
                     sfa::kRecalMaxPoints, s->raw.norm, s->raw.query);
     if (const int32_t sl = first_busy_slot(s); sl >= 0)
-        return fail(SFA_EINVAL, "sfa_session_raw_recalibrate: slot %d is not empty; the rule changes only while every slot is (sfa_session_reset)", sl);
+        return fail(SFA_EINVAL, "sfa_session_raw_recalibrate: slot %d is not empty; the rule changes only while every slot is (sfa_session_reset)", slot_name(s, sl));
     static_assert(SFA_RECAL_AT_END == sfa::kRecalAtEnd, "the flag of the header is the rule's");
     for (int32_t k = 0; k < n_at; ++k) s->raw.recal_at[k] = at[k];
     s->raw.recal_n = n_at;
@@ -987,6 +1352,11 @@ int sfa_session_raw_recalibrate(sfa_session_t *s, const int32_t *at, int32_t n_a
 }
 
 int64_t sfa_session_events(sfa_session_t *s, int32_t slot, int64_t first, sfa_event_t *out, int64_t cap) {
+    if (s && s->spread) {  // (the owning shard's)
+        sfa_session *sub = nullptr;
+        if (int rc = spread_owner(s, &slot, "sfa_session_events", &sub)) return rc;
+        return sfa_session_events(sub, slot, first, out, cap);
+    }
     if (!s || !s->raw.on || first < 0 || cap < 0 || (cap > 0 && !out)) return fail(SFA_EINVAL, "sfa_session_events: bad argument (or the session is not in raw mode)");
     if (int rc = check_slots(s, &slot, 1, "sfa_session_events")) return rc;
     static_assert(sizeof(sfa_event_t) == sizeof(sfa::EvRecord), "the device table is copied out as it is");
@@ -1003,6 +1373,7 @@ int64_t sfa_session_events(sfa_session_t *s, int32_t slot, int64_t first, sfa_ev
 
 int sfa_session_query_span(sfa_session_t *s, const int32_t *slot, int32_t n, uint64_t *start_raw, uint64_t *end_raw) {
     if (!s || n < 0 || (n > 0 && (!slot || !start_raw || !end_raw))) return fail(SFA_EINVAL, "sfa_session_query_span: bad argument");
+    if (s->spread) return spread_query_span(s, slot, n, start_raw, end_raw);
     if (!s->raw.on) return fail(SFA_EINVAL, "sfa_session_query_span: the session is not in raw mode (sfa_session_raw_config): it holds no event tables");
     if (int rc = check_slots(s, slot, n, "sfa_session_query_span")) return rc;
     if (n == 0) return SFA_OK;
@@ -1050,22 +1421,9 @@ int sfa_session_query_span(sfa_session_t *s, const int32_t *slot, int32_t n, uin
 int sfa_session_extend_raw(sfa_session_t *s, const int32_t *slot, const int16_t *raw, const int64_t *raw_off, const double *scaling,
                            const uint8_t *end_of_read, int32_t n, sfa_result_t *out, sfa_session_raw_info_t *info) {
     if (!s || n < 0 || (n > 0 && (!slot || !raw_off || !scaling || !out || !info))) return fail(SFA_EINVAL, "sfa_session_extend_raw: bad argument");
-    if (!s->raw.on) return fail(SFA_EINVAL, "sfa_session_extend_raw: the session takes events (sfa_session_extend) until sfa_session_raw_config");
-    if (n == 0) return SFA_OK;
-    sfa_ctx *c = s->c;
-    if (int rc = raw_check(s, slot, raw, raw_off, scaling, n)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int rc = sfa::resolve_profile(c)) return rc;
-    if (int rc = raw_stage_tables(s, slot, raw_off, end_of_read, n)) return rc;
-    if (int rc = raw_plan_points(s, slot, raw_off, end_of_read, n)) return rc;
-    if (int rc = raw_launch_detector(s, raw, raw_off, n)) return rc;
-    if (int rc = raw_launch_auto(s, n)) return rc;  // (retention and evaluation)
-    if (int rc = raw_launch_norm(s, n)) return rc;
-    std::vector<sfa::Chunk> ch(n);
-    raw_take_results(s, slot, raw_off, scaling, n, ch.data());
-    if (int rc = sweep_chunks(s, slot, ch.data(), n, nullptr, 0, s->raw.d_query.as<float>(), out)) return rc;
-    return raw_fill_info(s, slot, n, info);
+    if (s->spread) return spread_extend_raw(s, slot, raw, raw_off, scaling, end_of_read, n, out, info);
+    if (int rc = extend_raw_check(s, slot, raw, raw_off, scaling, n)) return rc;
+    return n == 0 ? static_cast<int>(SFA_OK) : extend_raw_run(s, slot, raw, raw_off, scaling, end_of_read, n, out, info);
 }
 
 }  // extern "C"

@@ -24,6 +24,7 @@ ticks, the same calls, the same lines.  The schedule counts ticks, never seconds
             line.  The maps of all rows decided in a tick -- primaries, and candidates under candidates=N -- come from ONE
             Session.event_maps call before the reset, on the slots' resident queries; the record is sam_row_from_map over the slot's
             events (Session.events) and is followed by the same tags (format_sam_line, format_sam).  Schedule and rule are unchanged
+  spread    --spread: the session is created with SESSION_SPREAD on an Aligner over several devices; nothing else changes
   after it  decided channels are reset in one call and take the next unread reads, lowest channel first, from tick t + 1 on
 """
 import numpy as np
@@ -116,7 +117,7 @@ AUTO_START_MAX_SAMPLES, MAX_SKIP_EVENTS = 131072, 4096  # the defaults of --auto
 
 
 def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False, resweep=False,
-           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False):
+           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False):
     """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
     candidates=1..4 (--candidates): an eighth element, RESULT_DTYPE[4], the channel's candidates at the decision, best first.
     A `session` of the caller's is taken as it is, in this as in its raw mode: it must keep that many candidates already
@@ -137,7 +138,9 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     dict with `events` (Session.events of the slot), `qstart` / `qend` (the query inside them: the slot's skip and skip + q_events),
     `map` (the primary's int32 [n, 2] event map from Session.event_maps, None when it has none) and `cand_maps` (the four
     candidates' maps with candidates=N, else None).  A session that carries no start columns (starts=False) has no maps: refused
-    before any call."""
+    before any call.
+    spread=True (--spread): the session of replay's own is aligner.session(channels, spread=True) -- on an Aligner made with
+    devices= the channels are dealt over its devices; the items are the same."""
     auto = skip < 0
     if sam and session is not None and not getattr(session, "starts", True):
         raise api.SfaError("replay: sam=True needs the rows' start columns; the session was created with starts=False (SESSION_NO_START)")
@@ -161,7 +164,7 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     src = Source()
     sch = Schedule(channels, chunk_samples, trace, resweep)
     own = session is None
-    se = aligner.session(channels, resweep=resweep) if own else session
+    se = aligner.session(channels, resweep=resweep, spread=spread) if own else session
     try:
         if own:
             if candidates:
