@@ -42,6 +42,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "row_rules.hpp"  // ResultRow and the rule that fills it: update_aln's lists, mapq, flip and offset
+
 namespace sfa {
 
 constexpr int kRefPad = 128;       // floats of +inf padding on both sides of every (contig,strand) array in HBM (>= 64 lanes + 2 loads)
@@ -61,7 +63,6 @@ constexpr int kRefPad = 128;       // floats of +inf padding on both sides of ev
 #define SFA_TRACE_WAVES 4  // waves per SIMD pass 2 (R <= 16) is register-budgeted for: 128 VGPRs; 3.49 -> 3.28 ms per 100 k reads against 144 VGPRs / 3 waves
 #endif
 constexpr int kStepsPerLoad = SFA_STEPS_PER_LOAD;  // reference levels fetched per load (4 = one 16-byte load)
-constexpr int kSpanBuckets = 32;   // histogram of alignment spans in sixteenths of the query length (FinalizeArgs::span_hist)
 constexpr int kMaxClasses = 6;     // query-length classes; base shapes (R, lanes) = (32,64) (32,32) (32,16) (16,16) (8,16) (4,16)
 
 // What a batch reports about itself: one block of words in device memory, zeroed in front of the batch and copied to the host
@@ -336,31 +337,7 @@ struct Top2 {
     }
 };
 
-// The whole sorted candidate list of the reference (SECONDARY_CAP = 5, src/sigfish.h:41), for secondary mappings.  One list of
-// 5 x (score bits, end, job) per read slot in LDS, touched by the owner lane once per window: the 32-row fill has no VGPRs to spare
-// for it.  aln[0] is the worst entry, aln[4] the best; the insertion is update_aln's (src/sigfish.c:575-594), so the LATER of two
-// equal candidates ranks higher and aln[4] is Top2's winner.
-constexpr int kTop5Words = 15;
-__device__ __forceinline__ void top5_init(int *t5) {
-    for (int l = 0; l < 5; ++l) {
-        t5[3 * l] = __float_as_int(INFINITY);
-        t5[3 * l + 1] = -1;
-        t5[3 * l + 2] = -1;
-    }
-}
-__device__ __forceinline__ void top5_offer(int *t5, float sc, int pos, int job) {
-    int l = 0;
-    while (l < 5 && !(sc > __int_as_float(t5[3 * l]))) ++l;
-    if (l == 0) return;
-    for (int m = 0; m + 1 < l; ++m) {
-        t5[3 * m] = t5[3 * m + 3];
-        t5[3 * m + 1] = t5[3 * m + 4];
-        t5[3 * m + 2] = t5[3 * m + 5];
-    }
-    t5[3 * (l - 1)] = __float_as_int(sc);
-    t5[3 * (l - 1) + 1] = pos;
-    t5[3 * (l - 1) + 2] = job;
-}
+// (the sorted candidate list of the secondary mappings, one per read slot in LDS: top5_init / top5_offer, row_rules.hpp)
 
 // MIXED QUADS.  The reads of a wave used to have ONE query length (the planner grouped by length), so a ragged batch -- a few
 // hundred distinct lengths -- left most of the short reads' waves a quarter or half full.  Reads of different lengths can share
@@ -1274,8 +1251,6 @@ __device__ __forceinline__ void pick_row(const CF &c, const CI &s, const int rq,
 // Pass 2: start-column recovery for each read's winning candidate.  One wave = one quad; each 16-lane row
 // follows its own (job, end column, checkpoint), so the step index is per lane.
 // ---------------------------------------------------------------------------------------------------------
-struct ResultRow;  // below
-
 // the winner of a read as pass 2 needs it (per lane: the value of the lane's read)
 struct Winner {
     int job;     // -1: nothing to trace
@@ -1476,24 +1451,13 @@ __device__ __forceinline__ void trace_core(const DpArgs &a, const ClassDesc cd, 
     }
 }
 
-// One result row per read, POD mirror of sfa_result_t (include/sigfish_amd.h).
-struct ResultRow {
-    int32_t rid, pos_st, pos_end;
-    float score, score2;
-    int8_t strand;
-    uint8_t mapq, valid, pad;
-};
-
 struct FinalizeArgs {
     const int32_t *slot_of_read;  // [n_reads] quad*4+slot, or -1 for skipped reads
     const float *p_best;
     const int32_t *p_end;
     const int32_t *p_job;
     const float *p_second;
-    const int32_t *job_contig;  // [n_jobs]
-    const int8_t *job_strand;   // [n_jobs] '+' / '-'
-    const int32_t *ref_len;     // [num_ref]
-    const int32_t *ref_st_offset;
+    RefTables ref;
     int32_t *w_job;  // winners for the trace kernel
     int32_t *w_end;
     float *w_score;
@@ -1536,35 +1500,6 @@ __global__ void __launch_bounds__(256, MAXR <= 16 ? SFA_TRACE_WAVES : 1) sdtw_tr
 #undef SFA_SHAPE
 }
 
-// src/sigfish.c:979-983: (int)round(500*(score2-score)/score) with x86 cvttsd2si saturation, cap 60, store u8
-__device__ __forceinline__ uint8_t mapq_from_scores(float score, float score2) {
-    const float v = 500.0f * (score2 - score) / score;
-    const float r = roundf(v);  // == round((double)v) for float inputs
-    int q;
-    if (!(r >= -2147483648.0f && r < 2147483648.0f))
-        q = INT32_MIN;
-    else
-        q = static_cast<int>(r);
-    if (q > 60) q = 60;
-    return static_cast<uint8_t>(q);
-}
-
-// One partial top-2 (b, s2) merged into the running (best, second), partials in processing order: the second smallest of the
-// four stays, and a later partial wins ties (src/sigfish.c:577-583).  True when b is the new best.
-__device__ __forceinline__ bool merge_top2(float &best, float &second, const float b, const float s2) {
-    const float hi = fmaxf(best, b);
-    const float lo2 = fminf(second, s2);
-    const bool take = !(b > best);
-    second = fminf(hi, lo2);  // second smallest of {best, second, b, s2}
-    if (take) best = b;
-    return take;
-}
-// Positions of a row from the columns its alignment starts and ends in: strand flip and offset (src/sigfish.c:971-975)
-__device__ __forceinline__ void place_row(ResultRow &r, const int st, const int end, const int rl, const int off) {
-    r.pos_st = ((r.strand == '+') ? st : rl - end) + off;
-    r.pos_end = ((r.strand == '+') ? end : rl - st) + off;
-}
-
 template <int R, int L, bool STD, bool LCK>
 __device__ __forceinline__ void fused_trace_task(const DpArgs &a, const ClassDesc cd, const int quad_local, float *lds_f, int *lds_i, float *lds_x) {
     const int quad = cd.quad_base + quad_local;
@@ -1584,17 +1519,9 @@ __device__ __forceinline__ void fused_trace_task(const DpArgs &a, const ClassDes
     const int lq = (qlen - 1) / R;
     const int read = a.order[quad * 4 + slot];
     const bool owner = (g == lq) && read >= 0;
-    // merge of the chunks' partial top-2 in processing order (sdtw_finalize_kernel, mode 1), one lane per read
-    ResultRow r;
-    r.rid = -1;
-    r.pos_st = -1;
-    r.pos_end = -1;
-    r.score = INFINITY;
-    r.score2 = INFINITY;
-    r.strand = 0;
-    r.mapq = 0;
-    r.valid = 0;
-    r.pad = 0;
+    // merge of the chunks' partial top-2 in processing order, one lane per read.  This function restates Top2Merge, primary_row, place_row and
+    // span_bucket (row_rules.hpp) in its own words: calling them changes the instructions of the fused fill launches, which stay as they are
+    ResultRow r = no_row();
     Winner w;
     w.job = -1;
     w.ws = -1;
@@ -1691,90 +1618,29 @@ struct SecArgs {
     int32_t *s_end;               // as DpArgs::w_end
     float *s_score;
     const int32_t *t_st;          // [5][2][n_reads] start and end columns traced for candidate k (k >= 1)
-    const int32_t *job_contig;
-    const int8_t *job_strand;
-    const int32_t *ref_len;
-    const int32_t *ref_st_offset;
+    RefTables ref;
     ResultRow *sec;               // [n_reads][4] secondaries, best first
     int32_t n_sec;                // secondaries asked for (1..4): rows of the ranks behind are valid = 0
     int32_t mode;
 };
 
 #ifdef SFA_DEFINE_FINALIZE_KERNEL  // plain (non-template) kernels: defined in exactly one translation unit
-// update_aln on a list in registers (aln[0] worst .. aln[4] best).  The entries that are not strictly better than the candidate form
-// a prefix of the sorted list; they move down by one and the candidate takes the last place of the prefix (constant indices only)
-__device__ __forceinline__ void top5_offer_regs(float (&sc)[5], int (&en)[5], int (&jb)[5], float s, int p, int j) {
-    int l = 0;
-#pragma unroll
-    for (int m = 0; m < 5; ++m) l += !(s > sc[m]) ? 1 : 0;
-#pragma unroll
-    for (int m = 0; m < 5; ++m) {
-        const bool nxt = m + 1 < l, put = m == l - 1;
-        const int mn = m < 4 ? m + 1 : 4;
-        sc[m] = nxt ? sc[mn] : (put ? s : sc[m]);
-        en[m] = nxt ? en[mn] : (put ? p : en[m]);
-        jb[m] = nxt ? jb[mn] : (put ? j : jb[m]);
-    }
-}
-
+// the chunks' lists of a read merged into its ranks (mode 1), the rows of ranks 1..4 behind pass 2 (mode 2): row_rules.hpp
 __global__ void __launch_bounds__(256) sdtw_sec_finalize_kernel(const SecArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n_reads) return;
     const int sl = a.slot_of_read[i];
     const bool strips = a.max_query > 0 && a.q_off[i + 1] - a.q_off[i] > a.max_query;
     const bool on = sl >= 0 && !a.bad[i] && !strips;
-    const int n = a.n_reads;
-    if (a.mode == 1) {
-        float sc[5];
-        int en[5], jb[5];
-#pragma unroll
-        for (int m = 0; m < 5; ++m) {
-            sc[m] = INFINITY;
-            en[m] = -1;
-            jb[m] = -1;
-        }
-        if (on) {
-            const int64_t quad = sl >> 2, slot = sl & 3;
-            for (int ch = 0; ch < a.n_chunks; ++ch) {  // chunks in processing order, each list in its own offer order (worst first)
-                const int32_t *t = a.p_top5 + ((quad * a.n_chunks + ch) * 4 + slot) * kTop5Words;
-                for (int e = 0; e < 5; ++e)
-                    if (t[3 * e + 2] >= 0) top5_offer_regs(sc, en, jb, __int_as_float(t[3 * e]), t[3 * e + 1], t[3 * e + 2]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const bool ok = jb[4 - k] >= 0 && isfinite(sc[4 - k]);
-            a.s_job[k * n + i] = ok ? jb[4 - k] : -1;
-            a.s_end[k * n + i] = ok ? en[4 - k] : -1;
-            a.s_score[k * n + i] = sc[4 - k];
-        }
+    const int64_t n = a.n_reads;
+    if (a.mode == 1) {  // chunks in processing order: the lists of (quad, chunk, slot) lie 4 lists apart
+        const int64_t first = on ? (static_cast<int64_t>(sl >> 2) * a.n_chunks * 4 + (sl & 3)) * kTop5Words : 0;
+        ranks_from_lists(a.p_top5 + first, on ? a.n_chunks : 0, 4 * kTop5Words, a.s_job, a.s_end, a.s_score, n, i);
         return;
     }
-    for (int k = 1; k < 5; ++k) {
-        ResultRow r;
-        r.rid = -1;
-        r.pos_st = -1;
-        r.pos_end = -1;
-        r.score = INFINITY;
-        r.score2 = INFINITY;
-        r.strand = 0;
-        r.mapq = 0;  // minimap2's convention for secondaries
-        r.valid = 0;
-        r.pad = 0;
-        const int job = (on && k <= a.n_sec) ? a.s_job[k * n + i] : -1;
-        if (job >= 0) {
-            r.valid = 1;
-            r.rid = a.job_contig[job];
-            r.strand = a.job_strand[job];
-            r.score = a.s_score[k * n + i];
-            r.score2 = k < 4 ? a.s_score[(k + 1) * n + i] : INFINITY;
-            const int st = a.t_st[2 * k * n + i], end = a.t_st[(2 * k + 1) * n + i];
-            const int rl = a.ref_len[r.rid], off = a.ref_st_offset[r.rid];
-            r.pos_st = ((r.strand == '+') ? st : rl - end) + off;  // src/sigfish.c:971-975
-            r.pos_end = ((r.strand == '+') ? end : rl - st) + off;
-        }
-        a.sec[static_cast<int64_t>(i) * 4 + (k - 1)] = r;
-    }
+    for (int k = 1; k < 5; ++k)
+        a.sec[static_cast<int64_t>(i) * 4 + (k - 1)] =
+            row_from_ranks(k, on && k <= a.n_sec, a.s_job, a.s_score, n, i, a.t_st + 2 * k * n + i, a.t_st + (2 * k + 1) * n + i, a.ref);
 }
 
 // one wave per (quad, job, hand-over between segment s and s+1): the state the later segment assumed against the state
@@ -1821,25 +1687,18 @@ __global__ void __launch_bounds__(256) sdtw_screen_kernel(const float *queries, 
     }
 }
 
+struct ChunkWin {  // what the merge over chunks keeps of the best partial
+    int end, job, chunk;
+};
 __global__ void __launch_bounds__(256) sdtw_finalize_kernel(const FinalizeArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n_reads) return;
     const int sl = a.slot_of_read[i];
-    const bool strips = a.max_query > 0 && a.q_off[i + 1] - a.q_off[i] > a.max_query;
+    const int64_t qlen = a.q_off[i + 1] - a.q_off[i];
+    const bool strips = a.max_query > 0 && qlen > a.max_query;
     if (strips && a.mode != 1) return;
     if (a.mode == 3) {  // fused launch: its pass-2 waves write the rows of every read they handle; the others are skipped reads
-        if (sl >= 0) return;
-        ResultRow r;
-        r.rid = -1;
-        r.pos_st = -1;
-        r.pos_end = -1;
-        r.score = INFINITY;
-        r.score2 = INFINITY;
-        r.strand = 0;
-        r.mapq = 0;
-        r.valid = 0;
-        r.pad = 0;
-        a.out[i] = r;
+        if (sl < 0) a.out[i] = no_row();
         return;
     }
     if (a.mode == 2) {  // positions from the traced start column
@@ -1848,58 +1707,24 @@ __global__ void __launch_bounds__(256) sdtw_finalize_kernel(const FinalizeArgs a
         if (r.rid < 0) return;
         const int st = a.t_st[i];
         const int end = a.t_st[a.n_reads + i];
-        place_row(r, st, end, a.ref_len[r.rid], a.ref_st_offset[r.rid]);
+        place_row(r, st, end, a.ref);
         a.out[i] = r;
-        if (a.span_hist && st >= 0 && end >= st) {
-            const int64_t ql = a.q_off[i + 1] - a.q_off[i];
-            if (ql > 0) {
-                const int64_t b = (static_cast<int64_t>(end - st + 1) * 16) / ql;
-                atomicAdd(a.span_hist + (b < kSpanBuckets - 1 ? static_cast<int>(b) : kSpanBuckets - 1), 1u);
-            }
-        }
+        const int b = a.span_hist ? span_bucket(st, end, qlen) : -1;
+        if (b >= 0) atomicAdd(a.span_hist + b, 1u);
         return;
     }
-    ResultRow r;
-    r.rid = -1;
-    r.pos_st = -1;
-    r.pos_end = -1;
-    r.score = INFINITY;
-    r.score2 = INFINITY;
-    r.strand = 0;
-    r.mapq = 0;
-    r.valid = 0;
-    r.pad = 0;
-    int wjob = -1, wend = -1, wchunk = 0;
-    if (sl >= 0 && !a.bad[i]) {
-        const int64_t quad = sl >> 2, slot = sl & 3;
-        float best = INFINITY, second = INFINITY;
-        int end = -1, job = -1;
-        for (int ch = 0; ch < a.n_chunks; ++ch) {  // chunks in processing order: a later chunk wins ties
-            const int64_t o = (quad * a.n_chunks + ch) * 4 + slot;
-            if (merge_top2(best, second, a.p_best[o], a.p_second[o])) {
-                end = a.p_end[o];
-                job = a.p_job[o];
-                wchunk = ch;
-            }
-        }
-        r.valid = 1;
-        r.score = best;
-        r.score2 = second;
-        if (job >= 0) {
-            const int rid = a.job_contig[job];
-            const int8_t d = a.job_strand[job];
-            r.rid = rid;
-            r.strand = d;
-            r.mapq = mapq_from_scores(best, second);
-            wjob = job;
-            wend = end;
-        }
+    const bool on = sl >= 0 && !a.bad[i];
+    Top2Merge<ChunkWin> m({-1, -1, 0});
+    for (int ch = 0; on && ch < a.n_chunks; ++ch) {  // chunks in processing order: a later chunk wins ties
+        const int64_t o = (static_cast<int64_t>(sl >> 2) * a.n_chunks + ch) * 4 + (sl & 3);
+        m.offer(a.p_best[o], a.p_second[o], {a.p_end[o], a.p_job[o], ch});
     }
+    const ResultRow r = on ? primary_row(m.best, m.second, m.pay.job, a.ref) : no_row();
     if (a.mode == 1) {
-        a.w_job[i] = wjob;
-        a.w_end[i] = wend;
+        a.w_job[i] = m.pay.job;
+        a.w_end[i] = m.pay.job >= 0 ? m.pay.end : -1;
         a.w_score[i] = r.score;
-        a.w_chunk[i] = wchunk;
+        a.w_chunk[i] = m.pay.chunk;
     }
     if (!strips) a.out[i] = r;
 }

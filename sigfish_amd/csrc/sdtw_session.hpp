@@ -79,7 +79,7 @@ __device__ __forceinline__ void session_last_row(const CF &c, const CI &s, const
     }
 }
 
-// SEC: the sorted list of the 5 best windows (top5_offer: update_aln's rule) per (wave, wave slot) in LDS, as lds_t5 of
+// SEC: the sorted list of the 5 best windows (top5_offer, row_rules.hpp: update_aln's rule) per (wave, wave slot) in LDS, as lds_t5 of
 // sdtw_sec_fill_kernel -- the tracked kernel has no VGPRs to spare.  An entry is (score bits, column of the window's first strict
 // minimum, start column of the path into it; -1 without TRACK): the job is the task's own.  Only the owner lane touches its list,
 // once per window; Top2 and what it writes are as without SEC.
@@ -305,9 +305,7 @@ struct SessionRowsArgs {
     const uint8_t *bad;        // [n_call]
     const float *p_best, *p_second;
     const int32_t *p_end, *p_st;
-    const int32_t *job_contig;
-    const int8_t *job_strand;
-    const int32_t *ref_len, *ref_st_offset;
+    RefTables ref;
     ResultRow *rows;           // [n_slots] the current row of every slot
     int32_t n_call, n_jobs;
     int32_t track;             // 0: SFA_SESSION_NO_START -- the coordinate that needs the start column is -1
@@ -317,9 +315,7 @@ struct SessionCandArgs {
     const int32_t *call_slot;  // as SessionRowsArgs
     const uint8_t *bad;
     const int32_t *p_top5;     // SessionArgs::p_top5
-    const int32_t *job_contig;
-    const int8_t *job_strand;
-    const int32_t *ref_len, *ref_st_offset;
+    RefTables ref;
     ResultRow *cand;           // [n_slots][4] the candidates behind every slot's current row, best first
     int32_t n_call, n_jobs;
     int32_t n_cand;            // ranks asked for (1..4): rows of the ranks behind are valid = 0
@@ -363,49 +359,20 @@ __global__ void __launch_bounds__(64) sdtw_session_rows_kernel(const SessionRows
     if (i >= a.n_call) return;
     const int slot = a.call_slot[i];
     if (slot < 0 || a.bad[i]) return;
-    float best = INFINITY, second = INFINITY;
-    int end = -1, st = -1, job = -1;
+    struct Win {
+        int end, st, job;
+    };
+    Top2Merge<Win> m({-1, -1, -1});
     for (int j = 0; j < a.n_jobs; ++j) {
         const int64_t o = static_cast<int64_t>(i) * a.n_jobs + j;
-        if (merge_top2(best, second, a.p_best[o], a.p_second[o])) {
-            end = a.p_end[o];
-            st = a.p_st[o];
-            job = j;
-        }
+        m.offer(a.p_best[o], a.p_second[o], {a.p_end[o], a.p_st[o], j});
     }
-    ResultRow r;
-    r.rid = -1;
-    r.pos_st = -1;
-    r.pos_end = -1;
-    r.score = best;
-    r.score2 = second;
-    r.strand = 0;
-    r.mapq = 0;
-    r.valid = 1;
-    r.pad = 0;
-    if (job >= 0) {
-        r.rid = a.job_contig[job];
-        r.strand = a.job_strand[job];
-        r.mapq = mapq_from_scores(best, second);
-        place_row(r, st, end, a.ref_len[r.rid], a.ref_st_offset[r.rid]);
-        if (!a.track) (r.strand == '+' ? r.pos_st : r.pos_end) = -1;
+    ResultRow r = primary_row(m.best, m.second, m.pay.job, a.ref);
+    if (m.pay.job >= 0) {
+        place_row(r, m.pay.st, m.pay.end, a.ref);
+        if (!a.track) drop_start(r);
     }
     a.rows[slot] = r;
-}
-
-// update_aln on a list in registers (aln[0] worst .. aln[4] best), as top5_offer_regs: the entries that are not strictly better
-// than the candidate form a prefix; they move down by one and the candidate takes the last place of the prefix
-__device__ __forceinline__ void session_offer_regs(float (&sc)[5], int (&ix)[5], const float s, const int i) {
-    int l = 0;
-#pragma unroll
-    for (int m = 0; m < 5; ++m) l += !(s > sc[m]) ? 1 : 0;
-#pragma unroll
-    for (int m = 0; m < 5; ++m) {
-        const bool nxt = m + 1 < l, put = m == l - 1;
-        const int mn = m < 4 ? m + 1 : 4;
-        sc[m] = nxt ? sc[mn] : (put ? s : sc[m]);
-        ix[m] = nxt ? ix[mn] : (put ? i : ix[m]);
-    }
 }
 
 // Session candidates: the jobs' lists of every slot of the call merged in processing order, each list worst entry first (the
@@ -416,42 +383,23 @@ __global__ void __launch_bounds__(64) sdtw_session_cand_kernel(const SessionCand
     if (i >= a.n_call) return;
     const int slot = a.call_slot[i];
     if (slot < 0 || a.bad[i]) return;
-    float sc[5];
-    int ix[5];  // job * 5 + entry: where the candidate's columns are
-#pragma unroll
-    for (int m = 0; m < 5; ++m) {
-        sc[m] = INFINITY;
-        ix[m] = -1;
-    }
+    Top5<1> t;  // the payload is job * 5 + entry: where the candidate's columns are
     const int32_t *lists = a.p_top5 + static_cast<int64_t>(i) * a.n_jobs * kTop5Words;
-    for (int j = 0; j < a.n_jobs; ++j) {
-        const int32_t *t = lists + j * kTop5Words;
-        for (int e = 0; e < 5; ++e)
-            if (t[3 * e + 1] >= 0) session_offer_regs(sc, ix, __int_as_float(t[3 * e]), j * 5 + e);
-    }
-#pragma unroll
+    for (int j = 0; j < a.n_jobs; ++j)
+        for (int e = 0; e < 5; ++e) {
+            const int32_t *w = lists + j * kTop5Words + 3 * e;
+            if (w[1] >= 0) t.offer(row_float(w[0]), j * 5 + e);
+        }
+    SFA_ROW_UNROLL
     for (int k = 1; k < 5; ++k) {
-        ResultRow r;
-        r.rid = -1;
-        r.pos_st = -1;
-        r.pos_end = -1;
-        r.score = INFINITY;
-        r.score2 = INFINITY;
-        r.strand = 0;
-        r.mapq = 0;  // (secondaries, as in sfa_secondary_rows)
-        r.valid = 0;
-        r.pad = 0;
-        const int x = ix[4 - k];
-        if (k <= a.n_cand && x >= 0 && isfinite(sc[4 - k])) {
+        ResultRow r = no_row();
+        int x;
+        const float score = t.rank(k, x);
+        if (k <= a.n_cand && x >= 0) {
             const int job = x / 5;
-            const int32_t *t = lists + job * kTop5Words + 3 * (x - job * 5);
-            r.valid = 1;
-            r.rid = a.job_contig[job];
-            r.strand = a.job_strand[job];
-            r.score = sc[4 - k];
-            r.score2 = k < 4 ? sc[3 - k] : INFINITY;
-            place_row(r, t[2], t[1], a.ref_len[r.rid], a.ref_st_offset[r.rid]);
-            if (!a.track) (r.strand == '+' ? r.pos_st : r.pos_end) = -1;
+            const int32_t *w = lists + job * kTop5Words + 3 * (x - job * 5);  // (score bits, end, start)
+            r = secondary_row(score, t.score(k + 1), job, w[2], w[1], a.ref);
+            if (!a.track) drop_start(r);
         }
         a.cand[static_cast<int64_t>(slot) * 4 + (k - 1)] = r;
     }

@@ -148,7 +148,7 @@ struct StripResult {
 // One strip over columns [0, ncols) of one (contig,strand).  LAST: the strip holds the last query row (lane lq,
 // register rq) -- in pass 2 (TRACK) always: the row of the cell to reach.  Pass 2: column ws is the cell to reach, `best` its cost.
 // SEC (pass 1, final strip): every window's (wmin, wpos, job) is also offered to the candidate list t5 of secondary mappings, 5 x (score
-// bits, end, job) in LDS (top5_offer, sdtw_kernels.hpp), by the lane that holds the last query row, where the window ends.
+// bits, end, job) in LDS (top5_offer, row_rules.hpp), by the lane that holds the last query row, where the window ends.
 template <bool STD, bool FIRST, bool TRACK, bool LAST, int R, bool SEC = false, typename XT>
 __device__ __forceinline__ void strip_sweep(const float *yp, const int rlen, const int ncols, const int qlen,
                                             const XT &x, const int lq, const int rq, const int lane, Exchange &xc,
@@ -592,9 +592,7 @@ struct StripFinalizeArgs {
     const int32_t *reads;  // [n_long]
     const float *p_best, *p_second;
     const int32_t *p_end;
-    const int32_t *job_contig;
-    const int8_t *job_strand;
-    const int32_t *ref_len, *ref_st_offset;
+    RefTables ref;
     int32_t *w_job, *w_ws;  // mode 1 out: winners for pass 2
     float *w_score;
     const int32_t *t_st, *t_end;  // mode 2 in
@@ -614,45 +612,25 @@ __global__ void __launch_bounds__(64) sdtw_strip_finalize_kernel(const StripFina
         ResultRow r = a.out[a.reads[li]];
         const int st = a.t_st[li], end = a.t_end[li];
         if (r.rid < 0 || end < 0) return;
-        place_row(r, st, end, a.ref_len[r.rid], a.ref_st_offset[r.rid]);
+        place_row(r, st, end, a.ref);
         a.out[a.reads[li]] = r;
         return;
     }
-    float best = INFINITY, second = INFINITY;
-    int ws = -1, job = -1;
+    struct Win {
+        int ws, job;
+    };
+    Top2Merge<Win> m({-1, -1});
     for (int j = 0; j < a.n_jobs; ++j) {
         const int64_t o = static_cast<int64_t>(li) * a.n_jobs + j;
-        if (merge_top2(best, second, a.p_best[o], a.p_second[o])) {
-            ws = a.p_end[o];
-            job = j;
-        }
+        m.offer(a.p_best[o], a.p_second[o], {a.p_end[o], j});
     }
-    ResultRow r;
-    r.rid = -1;
-    r.pos_st = -1;
-    r.pos_end = -1;
-    r.score = best;
-    r.score2 = second;
-    r.strand = 0;
-    r.mapq = 0;
-    r.valid = 1;
-    r.pad = 0;
-    if (a.bad[a.reads[li]]) {  // the reference aborts on such a read (see sdtw_screen_kernel): skipped, like a read without events
-        r.valid = 0;
-        r.score = r.score2 = INFINITY;
-        job = -1;
-    }
-    if (job >= 0 && ws >= 0) {
-        r.rid = a.job_contig[job];
-        r.strand = a.job_strand[job];
-        r.mapq = mapq_from_scores(best, second);
-    } else {
-        job = -1;
-    }
+    // the reference aborts on a non-finite read (see sdtw_screen_kernel): skipped, like a read without events
+    const bool bad = a.bad[a.reads[li]];
+    const int job = (bad || m.pay.ws < 0) ? -1 : m.pay.job;
     a.w_job[li] = job;
-    a.w_ws[li] = ws;
-    a.w_score[li] = best;
-    a.out[a.reads[li]] = r;
+    a.w_ws[li] = m.pay.ws;
+    a.w_score[li] = m.best;
+    a.out[a.reads[li]] = bad ? no_row() : primary_row(m.best, m.second, job, a.ref);
 }
 #endif
 
@@ -666,9 +644,7 @@ struct StripSecArgs {
     int32_t *s_job, *s_ws;   // rank k of long read li at [k * n_total + li]: the reference's aln[4 - k]; k = 0 is the primary; -1: none
     float *s_score;
     int32_t *t_st, *t_end;   // columns traced for rank k (k >= 1) by its pass-2 launch, -1 where nothing was: mode 2 reads them
-    const int32_t *job_contig;
-    const int8_t *job_strand;
-    const int32_t *ref_len, *ref_st_offset;
+    RefTables ref;
     ResultRow *sec;          // [reads of the batch][4] secondaries, best first
     int32_t n_long, n_total, n_jobs;
     int32_t n_sec;           // secondaries asked for (1..4): rows of the ranks behind are valid = 0
@@ -680,53 +656,15 @@ __global__ void __launch_bounds__(64) sdtw_strip_sec_finalize_kernel(const Strip
     const int li = blockIdx.x * blockDim.x + threadIdx.x;
     if (li >= a.n_long) return;
     const int read = a.reads[li];
-    const int n = a.n_total;
+    const int64_t n = a.n_total;
     const bool on = !a.bad[read];
-    if (a.mode == 1) {  // the jobs' lists in processing order, each in its own offer order (worst first): update_aln over all windows
-        float sc[5];
-        int en[5], jb[5];
-#pragma unroll
-        for (int m = 0; m < 5; ++m) {
-            sc[m] = INFINITY;
-            en[m] = -1;
-            jb[m] = -1;
-        }
-        for (int j = 0; on && j < a.n_jobs; ++j) {
-            const int32_t *t = a.p_top5 + (static_cast<int64_t>(li) * a.n_jobs + j) * kTop5Words;
-            for (int e = 0; e < 5; ++e)
-                if (t[3 * e + 2] >= 0) top5_offer_regs(sc, en, jb, __int_as_float(t[3 * e]), t[3 * e + 1], t[3 * e + 2]);
-        }
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const bool ok = jb[4 - k] >= 0 && isfinite(sc[4 - k]);
-            a.s_job[k * n + li] = ok ? jb[4 - k] : -1;
-            a.s_ws[k * n + li] = ok ? en[4 - k] : -1;
-            a.s_score[k * n + li] = sc[4 - k];
-        }
+    if (a.mode == 1) {  // the jobs' lists in processing order, one behind the other
+        ranks_from_lists(a.p_top5 + static_cast<int64_t>(li) * a.n_jobs * kTop5Words, on ? a.n_jobs : 0, kTop5Words, a.s_job, a.s_ws, a.s_score, n, li);
         return;
     }
-    for (int k = 1; k < 5; ++k) {  // the rows, as sdtw_sec_finalize_kernel writes them
-        ResultRow r;
-        r.rid = -1;
-        r.pos_st = -1;
-        r.pos_end = -1;
-        r.score = INFINITY;
-        r.score2 = INFINITY;
-        r.strand = 0;
-        r.mapq = 0;
-        r.valid = 0;
-        r.pad = 0;
-        const int job = (on && k <= a.n_sec) ? a.s_job[k * n + li] : -1;
-        if (job >= 0) {
-            r.valid = 1;
-            r.rid = a.job_contig[job];
-            r.strand = a.job_strand[job];
-            r.score = a.s_score[k * n + li];
-            r.score2 = k < 4 ? a.s_score[(k + 1) * n + li] : INFINITY;
-            place_row(r, a.t_st[k * n + li], a.t_end[k * n + li], a.ref_len[r.rid], a.ref_st_offset[r.rid]);
-        }
-        a.sec[static_cast<int64_t>(read) * 4 + (k - 1)] = r;
-    }
+    for (int k = 1; k < 5; ++k)
+        a.sec[static_cast<int64_t>(read) * 4 + (k - 1)] =
+            row_from_ranks(k, on && k <= a.n_sec, a.s_job, a.s_score, n, li, a.t_st + k * n + li, a.t_end + k * n + li, a.ref);
 }
 #endif
 

@@ -22,8 +22,6 @@ using sfa::resolve_profile;
 
 namespace {
 
-static_assert(sizeof(ResultRow) == sizeof(sfa_result_t), "result row layout");
-
 // f(std::integral_constant<int, R>()) for the rows-per-lane class R (4, 8, 16, 32; at most Cap) of a batch whose widest
 // class has maxr rows per lane
 template <int Cap, typename F>
@@ -113,10 +111,7 @@ sfa::StripSecArgs strip_sec_args(const sfa_ctx *c, const sfa::LongPlan &lp, int3
     xa.s_score = r.score;
     xa.t_st = r.st;
     xa.t_end = r.end;
-    xa.job_contig = c->model.d_job_contig.as<int32_t>();
-    xa.job_strand = c->model.d_job_strand.as<int8_t>();
-    xa.ref_len = c->model.d_ref_len.as<int32_t>();
-    xa.ref_st_offset = c->model.d_ref_off.as<int32_t>();
+    xa.ref = c->model.tables();
     xa.sec = d_sec;
     xa.n_long = gn;
     xa.n_total = lp.n_long();
@@ -132,10 +127,7 @@ sfa::StripFinalizeArgs strip_finalize_args(const sfa_ctx *c, const sfa::StripArg
     fa.p_best = sa.p_best;
     fa.p_second = sa.p_second;
     fa.p_end = sa.p_end;
-    fa.job_contig = c->model.d_job_contig.as<int32_t>();
-    fa.job_strand = c->model.d_job_strand.as<int8_t>();
-    fa.ref_len = c->model.d_ref_len.as<int32_t>();
-    fa.ref_st_offset = c->model.d_ref_off.as<int32_t>();
+    fa.ref = c->model.tables();
     fa.w_job = w.w_job;
     fa.w_ws = w.w_ws;
     fa.w_score = w.w_score;
@@ -424,10 +416,11 @@ BatchArgs batch_args(sfa_ctx *c, const float *d_queries, int32_t n, ResultRow *d
     da.ticket = c->fused.d_ticket.as<unsigned>();
     da.quad_done = c->fused.d_quaddone.as<int32_t>();
     da.n_quads_total = n_quads;
-    da.job_contig = c->model.d_job_contig.as<int32_t>();
-    da.job_strand = c->model.d_job_strand.as<int8_t>();
-    da.ref_len = c->model.d_ref_len.as<int32_t>();
-    da.ref_st_offset = c->model.d_ref_off.as<int32_t>();
+    const sfa::RefTables ref = c->model.tables();
+    da.job_contig = ref.job_contig;  // (DpArgs keeps its own words: the DP kernels were built around them)
+    da.job_strand = ref.job_strand;
+    da.ref_len = ref.ref_len;
+    da.ref_st_offset = ref.ref_st_offset;
     da.bad = c->status.d_bad.as<uint8_t>();
     da.out = d_out;
     da.span_hist = route == Route::Fused32 ? c->status.dev()->span_hist : nullptr;  // (the LDS route caps its head start instead)
@@ -459,10 +452,7 @@ BatchArgs batch_args(sfa_ctx *c, const float *d_queries, int32_t n, ResultRow *d
     fz.p_end = da.p_end;
     fz.p_job = da.p_job;
     fz.p_second = da.p_second;
-    fz.job_contig = da.job_contig;
-    fz.job_strand = da.job_strand;
-    fz.ref_len = da.ref_len;
-    fz.ref_st_offset = da.ref_st_offset;
+    fz.ref = ref;
     fz.w_job = da.w_job;
     fz.w_end = da.w_end;
     fz.w_score = da.w_score;
@@ -489,10 +479,7 @@ BatchArgs batch_args(sfa_ctx *c, const float *d_queries, int32_t n, ResultRow *d
         sa.s_end = sa.s_job + 5 * static_cast<size_t>(n);
         sa.s_score = reinterpret_cast<float *>(sa.s_end + 5 * static_cast<size_t>(n));
         sa.t_st = c->sec.d_sts.as<int32_t>();
-        sa.job_contig = fz.job_contig;
-        sa.job_strand = fz.job_strand;
-        sa.ref_len = fz.ref_len;
-        sa.ref_st_offset = fz.ref_st_offset;
+        sa.ref = ref;
         sa.sec = d_sec;
         sa.n_sec = static_cast<int32_t>(c->opt_secondary);
     }

@@ -167,6 +167,18 @@ class ShardWorker {
 namespace sfa {
 struct EvArgs;    // events_kernels.hpp: argument blocks of the event detection and of the automatic query start, which
 struct AutoArgs;  // ctx::RawSignal fills from its buffers (defined in sfa_pre.hip, the one unit that launches those kernels)
+
+// the kernels' row (row_rules.hpp) is the C-ABI's, field for field
+#define SFA_SAME_FIELD(f) (offsetof(ResultRow, f) == offsetof(sfa_result_t, f) && sizeof(ResultRow::f) == sizeof(sfa_result_t::f))
+static_assert(sizeof(ResultRow) == sizeof(sfa_result_t) && SFA_SAME_FIELD(rid) && SFA_SAME_FIELD(pos_st) && SFA_SAME_FIELD(pos_end) && SFA_SAME_FIELD(score) &&
+                  SFA_SAME_FIELD(score2) && SFA_SAME_FIELD(strand) && SFA_SAME_FIELD(mapq) && SFA_SAME_FIELD(valid) && SFA_SAME_FIELD(pad),
+              "result row layout");
+#undef SFA_SAME_FIELD
+inline sfa_result_t to_result(const ResultRow &r) {
+    sfa_result_t o;
+    memcpy(&o, &r, sizeof o);
+    return o;
+}
 }  // namespace sfa
 
 // ---- the context's state, one struct per stage that owns it: its buffers, what it keeps between calls, and reserve(), the one
@@ -185,6 +197,8 @@ struct RefModel {  // the reference event model (immutable after init)
         return reserve_all(d_ref, ref_bytes, d_job_off, sizeof(int64_t) * j, d_job_len, sizeof(int32_t) * j, d_job_contig, sizeof(int32_t) * j,
                            d_job_strand, j, d_ref_len, sizeof(int32_t) * r, d_ref_off, sizeof(int32_t) * r);
     }
+    // what the finalize kernels read of the model (row_rules.hpp)
+    sfa::RefTables tables() const { return {d_job_contig.as<int32_t>(), d_job_strand.as<int8_t>(), d_ref_len.as<int32_t>(), d_ref_off.as<int32_t>()}; }
 };
 
 struct CallerIO {  // queries in, rows out, of the entry points that take host memory

@@ -218,7 +218,7 @@ struct sfa_session {
 
 namespace {
 
-const sfa_result_t kNoRow = {-1, -1, -1, INFINITY, INFINITY, 0, 0, 0, 0};
+const sfa_result_t kNoRow = sfa::to_result(sfa::no_row());
 size_t align8(size_t x) { return (x + 7) & ~static_cast<size_t>(7); }
 constexpr uint32_t kSessionFlags = SFA_SESSION_NO_START | SFA_SESSION_RESWEEP | SFA_SESSION_SPREAD;  // (0x2 is not assigned)
 
@@ -385,10 +385,7 @@ int sweep_launch(sfa_session *s, int32_t n, const float *h_events, int64_t nq, b
     ra.p_second = w.d_psecond.as<float>();
     ra.p_end = w.d_pend.as<int32_t>();
     ra.p_st = w.d_pst.as<int32_t>();
-    ra.job_contig = c->model.d_job_contig.as<int32_t>();
-    ra.job_strand = c->model.d_job_strand.as<int8_t>();
-    ra.ref_len = c->model.d_ref_len.as<int32_t>();
-    ra.ref_st_offset = c->model.d_ref_off.as<int32_t>();
+    ra.ref = c->model.tables();
     ra.rows = s->rows.d_rows.as<sfa::ResultRow>();
     ra.n_call = n;
     ra.n_jobs = c->model.n_jobs;
@@ -400,10 +397,7 @@ int sweep_launch(sfa_session *s, int32_t n, const float *h_events, int64_t nq, b
         ca.call_slot = ra.call_slot;
         ca.bad = ra.bad;
         ca.p_top5 = s->cand.d_p5.as<int32_t>();
-        ca.job_contig = ra.job_contig;
-        ca.job_strand = ra.job_strand;
-        ca.ref_len = ra.ref_len;
-        ca.ref_st_offset = ra.ref_st_offset;
+        ca.ref = ra.ref;
         ca.cand = s->cand.d_cand.as<sfa::ResultRow>();
         ca.n_call = n;
         ca.n_jobs = ra.n_jobs;

@@ -1,14 +1,12 @@
 """Secondary mappings of reads beyond 2048 events ("secondary_strips"), the parts that need no GPU: the command line's checks, the
 option in the header, the planner's sizes and offsets (the stand-alone program tests/c/long_plan_sec.cpp, built with -Wall -Werror
-and once more under ASan + UBSan), and the merge rule of the strips' lists restated against update_aln."""
+and once more under ASan + UBSan).  The merge rule of the strips' lists against update_aln: tests/test_row_rules_cpu.py."""
 import os
 import shutil
 import subprocess
 
-import numpy as np
 import pytest
 
-from tests.secondary_oracle import CAP, _update_aln
 from tests.util import ROOT
 
 CSRC = os.path.join(ROOT, "sigfish_amd", "csrc")
@@ -94,34 +92,3 @@ def test_plan_sizes_and_offsets(outputs):
     # the budget of tests/test_secondary_strips_gpu.py::test_groups_on_two_scratch_sets: two reads per set, three groups
     assert (got["three_groups"]["group"], got["three_groups"]["n_groups"], got["three_groups"]["two_sets"]) == (2, 3, 1)
     assert (got["one_per_group"]["group"], got["one_per_group"]["n_groups"]) == (1, 3)
-
-
-def _offer(lst, sc, pos, job):
-    """top5_offer / top5_offer_regs (sdtw_kernels.hpp) on a list of (score, pos, job), worst first: the entries that are not strictly
-    better than the candidate move down by one, the candidate takes the last of their places."""
-    l = sum(1 for e in lst if not (sc > e[0]))  # they form a prefix of the sorted list
-    if l == 0:
-        return
-    lst[:l] = lst[1:l] + [(np.float32(sc), pos, job)]
-
-
-@pytest.mark.parametrize("seed", range(6))
-def test_merge_of_the_jobs_lists_is_update_aln(seed):
-    """Pass 1 keeps a list per (read, job) -- update_aln over that job's windows -- and the merge offers the jobs' lists to one list
-    in job order, each in its own order (worst first, empty entries skipped).  That is update_aln over all windows in processing
-    order, ties included: scores from a handful of values so that equals are frequent, and +inf among them."""
-    rng = np.random.default_rng(seed)
-    n_jobs = int(rng.integers(1, 7))
-    values = np.array([1.0, 1.25, 1.5, 2.0, 2.0, np.inf], np.float32)
-    whole = [(np.float32(np.inf), -1, -1, -1, 0)] * CAP  # the reference's list over every window
-    merged = [(np.float32(np.inf), -1, -1)] * CAP
-    for job in range(n_jobs):
-        per_job = [(np.float32(np.inf), -1, -1)] * CAP
-        for w in range(int(rng.integers(0, 9))):
-            sc, pos = values[rng.integers(len(values))], 100 * job + w
-            _update_aln(whole, sc, job, pos, "+", 0)
-            _offer(per_job, sc, pos, job)
-        for e in per_job:
-            if e[2] >= 0:
-                _offer(merged, *e)
-    assert [(e[0], e[3], e[1]) for e in whole] == merged
