@@ -650,16 +650,25 @@ typedef struct {
 
 /* load_db()'s records straight to the device (src/sigfish.c:274-314 hands them to parse_single, 317-328, on host threads):
  * records: the BLOW5 records of a batch back to back WITHOUT their u64 size prefixes, rec_off[n+1] their offsets;
- * record_zlib / signal_svb: the file's compression methods (record_press == zlib, signal_press == svb-zd).  Every record
- * is inflated (own DEFLATE decoder, one lane per record), its primary fields are parsed and its signal decoded
+ * record_zlib / signal_svb: the file's compression methods: record_zlib is the file's record_press -- SFA_PRESS_NONE (0),
+ * SFA_PRESS_ZLIB (1) or SFA_PRESS_ZSTD (2) -- and signal_svb says signal_press == svb-zd.  Every record is decompressed
+ * (own DEFLATE decoder or own zstd decoder, one lane per record), its primary fields are parsed and its signal decoded
  * (StreamVByte zig-zag deltas, one wave per record) on the device; the path of sfa_align_raw_ex continues from there.
  * heads[n] receives the fields the output needs.  A record the device decoder declines (malformed, longer read id than
- * sfa_read_head_t holds, inflating to more than 4x its size + 4 KB, signal stream longer or shorter than its keys say) sends
+ * sfa_read_head_t holds, decompressing to more than 4x its size + 4 KB, signal stream longer or shorter than its keys say) sends
  * the batch through the library's host reader instead -- same results, counted in sfa_profile_t.blow5_fallbacks; a record the
  * host reader rejects as well is SFA_EINVAL naming it.  Other arguments as for sfa_align_raw_ex (prefix_size < 0 included). */
+#define SFA_PRESS_NONE 0 /* record_zlib: the records are not compressed */
+#define SFA_PRESS_ZLIB 1 /* ... every record is a zlib stream */
+#define SFA_PRESS_ZSTD 2 /* ... every record is a zstd frame */
 int sfa_align_blow5(sfa_ctx_t *ctx, const uint8_t *records, const int64_t *rec_off, int32_t n_reads, int32_t record_zlib,
                     int32_t signal_svb, int32_t prefix_size, int32_t query_size, sfa_result_t *rows, sfa_query_info_t *info,
                     sfa_read_head_t *heads, sfa_event_t *query_events);
+
+/* The device-side zstd decoder on its own (tests): n zstd records in[in_off[i]..in_off[i+1]) -> out[out_off[i]..),
+ * out_len[i] = bytes produced or -1 (malformed, or larger than its slot).  Single-device context. */
+int sfa_zstd_device(sfa_ctx_t *ctx, const uint8_t *in, const int64_t *in_off, int32_t n, uint8_t *out, const int64_t *out_off,
+                    int32_t *out_len);
 
 /* The device-side DEFLATE decoder on its own (tests): n zlib streams in[in_off[i]..in_off[i+1]) -> out[out_off[i]..),
  * out_len[i] = bytes produced or -1 (malformed, or larger than its slot).  Single-device context. */
@@ -674,7 +683,7 @@ int sfa_inflate_zlib_device(sfa_ctx_t *ctx, const uint8_t *in, const int64_t *in
  * SFA_BLOW5_STREAM keeps its head and its n_samples places, whose contents are undefined; all others are decoded whatever their
  * neighbours are.  samples: room for `capacity` int16; SFA_ERANGE when raw_off[n] exceeds it (status, heads and raw_off are
  * written by then).  Single-device context. */
-#define SFA_BLOW5_INFLATE 1 /* the record does not inflate (malformed, truncated, or more than 4x its size + 4 KB) */
+#define SFA_BLOW5_INFLATE 1 /* the record does not decompress (malformed, truncated, or more than 4x its size + 4 KB) */
 #define SFA_BLOW5_FIELDS 2  /* the primary fields: payload too short for them or for the signal they announce, read id too long */
 #define SFA_BLOW5_STREAM 3  /* svb-zd: the data stream is longer or shorter than its keys say */
 int sfa_decode_blow5_device(sfa_ctx_t *ctx, const uint8_t *records, const int64_t *rec_off, int32_t n, int32_t record_zlib,
@@ -809,6 +818,11 @@ int64_t sfa_inflate_zlib(const uint8_t *in, size_t n, uint8_t *out, size_t cap);
  * SFA_EINVAL for null arguments. */
 int sfa_inflate_zlib_pair(const uint8_t *in0, size_t n0, const uint8_t *in1, size_t n1, uint8_t *out0, size_t cap0, uint8_t *out1,
                           size_t cap1, int64_t len[2]);
+
+/* The zstd record decompressor of the BLOW5 reader on its own (the library's own decoder, written from RFC 8878: frames back to
+ * back, skippable frames, content checksum; no dictionaries): src[0..n) -> dst[0..cap).  Returns the number of bytes produced,
+ * or -1 when the frames are malformed or hold more than cap bytes. */
+int64_t sfa_zstd_decompress(const uint8_t *src, size_t n, uint8_t *dst, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -60,10 +60,10 @@ class SfaSessionAuto(C.Structure):
 
 
 # every symbol include/sigfish_amd.h declares (checked by tests/test_capi_host.py::test_library_exports_every_declared_symbol)
-SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "sfa_submit_batch", "sfa_wait_batch", "sfa_align_batch_device", "sfa_align_events", "sfa_align_raw", "sfa_align_raw_ex", "sfa_align_blow5", "sfa_inflate_zlib_device", "sfa_decode_blow5_device", "sfa_detect_events_device", "sfa_pinned_alloc", "sfa_pinned_free", "sfa_sync",
+SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "sfa_submit_batch", "sfa_wait_batch", "sfa_align_batch_device", "sfa_align_events", "sfa_align_raw", "sfa_align_raw_ex", "sfa_align_blow5", "sfa_zstd_device", "sfa_inflate_zlib_device", "sfa_decode_blow5_device", "sfa_detect_events_device", "sfa_pinned_alloc", "sfa_pinned_free", "sfa_sync",
            "sfa_get_profile", "sfa_stream", "sfa_set_option", "sfa_plan_batch", "sfa_destroy", "sfa_last_error", "sfa_version", "sfa_build_id", "sfa_gen_ref_record",
            "sfa_znormalise", "sfa_paf_row", "sfa_sam_row", "sfa_paf_row_ex", "sfa_sam_row_ex", "sfa_secondary_rows", "sfa_event_maps", "sfa_sam_row_from_map", "sfa_r2qevent_map", "sfa_detect_events", "sfa_select_query", "sfa_detect_query_start", "sfa_set_pore", "sfa_read_kmer_model",
-           "sfa_blow5_open", "sfa_blow5_attr", "sfa_blow5_next", "sfa_blow5_close", "sfa_blow5_select_shard", "sfa_blow5_select_records", "sfa_inflate_zlib", "sfa_inflate_zlib_pair", "sfa_device_memory",
+           "sfa_blow5_open", "sfa_blow5_attr", "sfa_blow5_next", "sfa_blow5_close", "sfa_blow5_select_shard", "sfa_blow5_select_records", "sfa_inflate_zlib", "sfa_inflate_zlib_pair", "sfa_zstd_decompress", "sfa_device_memory",
            "sfa_session_create", "sfa_session_extend", "sfa_session_reset", "sfa_session_lengths", "sfa_session_destroy", "sfa_session_bytes",
            "sfa_event_stream_create", "sfa_event_stream_push", "sfa_event_stream_finish", "sfa_event_stream_destroy",
            "sfa_session_raw_config", "sfa_session_extend_raw", "sfa_session_events", "sfa_session_raw_bytes", "sfa_session_query_span", "sfa_session_row",
@@ -96,6 +96,7 @@ def load():
     L.sfa_align_raw_ex.argtypes = [vp, C.POINTER(C.c_int16), i64p, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
     L.sfa_align_blow5.argtypes = [vp, vp, i64p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
     L.sfa_inflate_zlib_device.argtypes = [vp, vp, i64p, C.c_int32, vp, i64p, i32p]
+    L.sfa_zstd_device.argtypes = [vp, vp, i64p, C.c_int32, vp, i64p, i32p]
     L.sfa_decode_blow5_device.argtypes = [vp, vp, i64p, C.c_int32, C.c_int32, C.c_int32, i32p, vp, i64p, C.POINTER(C.c_int16), C.c_int64]
     L.sfa_detect_events_device.argtypes = [vp, C.POINTER(C.c_int16), i64p, C.POINTER(C.c_double), C.c_int32, vp, i32p, i32p, f32p, f32p]
     L.sfa_pinned_alloc.argtypes = [C.c_size_t]
@@ -155,6 +156,8 @@ def load():
     L.sfa_inflate_zlib_pair.restype = C.c_int
     L.sfa_inflate_zlib_pair.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, i64p]
     L.sfa_inflate_zlib.restype = C.c_int64
+    L.sfa_zstd_decompress.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t]
+    L.sfa_zstd_decompress.restype = C.c_int64
     L.sfa_device_memory.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.sfa_session_create.argtypes = [vp, C.c_int32, C.c_uint32, C.POINTER(vp)]
     L.sfa_session_extend.argtypes = [vp, i32p, f32p, i64p, C.c_int32, vp]

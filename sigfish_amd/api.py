@@ -13,6 +13,7 @@ from . import _lib
 
 # opt.flag bits (src/sigfish.h:30-39)
 RNA, DTW, INV, REF, END = 0x001, 0x002, 0x004, 0x010, 0x020
+PRESS_NONE, PRESS_ZLIB, PRESS_ZSTD = 0, 1, 2  # SFA_PRESS_*: the record_zlib argument of align_blow5 / decode_blow5_device (True = zlib)
 BLOW5_INFLATE, BLOW5_FIELDS, BLOW5_STREAM = 1, 2, 3  # SFA_BLOW5_*: why decode_blow5_device's device stages declined a record
 
 RESULT_DTYPE = np.dtype([("rid", "<i4"), ("pos_st", "<i4"), ("pos_end", "<i4"), ("score", "<f4"), ("score2", "<f4"),
@@ -63,6 +64,11 @@ def recal_double(norm, query):
 
 class SfaError(RuntimeError):
     pass
+
+
+def _press(record_zlib):
+    """record_zlib as the C-ABI takes it: 0 none, 1 zlib (any flag that is true), 2 zstd"""
+    return PRESS_ZSTD if (record_zlib is not True and record_zlib == PRESS_ZSTD) else int(bool(record_zlib))
 
 
 def _check(rc, what):
@@ -397,7 +403,7 @@ class Aligner:
         qev = np.zeros((n, query_size), EVENT_DTYPE) if return_events else None
         if rec.size == 0:
             rec = np.zeros(1, np.uint8)
-        _check(self._L.sfa_align_blow5(self._h, rec.ctypes.data_as(C.c_void_p), ro.ctypes.data_as(_lib.i64p), n, int(bool(record_zlib)),
+        _check(self._L.sfa_align_blow5(self._h, rec.ctypes.data_as(C.c_void_p), ro.ctypes.data_as(_lib.i64p), n, _press(record_zlib),
                                        int(bool(signal_svb)), prefix_size, query_size, rows.ctypes.data_as(C.c_void_p),
                                        info.ctypes.data_as(C.c_void_p), C.cast(heads, C.c_void_p),
                                        qev.ctypes.data_as(C.c_void_p) if return_events else None), "sfa_align_blow5")
@@ -418,6 +424,19 @@ class Aligner:
                                                lens.ctypes.data_as(_lib.i32p)), "sfa_inflate_zlib_device")
         return [None if lens[i] < 0 else out[out_off[i]:out_off[i] + lens[i]].tobytes() for i in range(n)]
 
+    def zstd_device(self, streams, cap_factor=4, cap_extra=4096):
+        """The device-side zstd decoder alone: list of zstd records -> list of bytes (None where the decoder declined)."""
+        n = len(streams)
+        in_off = np.concatenate([[0], np.cumsum([len(x) for x in streams])]).astype(np.int64)
+        blob = np.frombuffer(b"".join(streams) + b"\0" * 8, np.uint8)
+        out_off = np.concatenate([[0], np.cumsum([(len(x) * cap_factor + cap_extra + 15) & ~15 for x in streams])]).astype(np.int64)
+        out = np.zeros(int(out_off[-1]) + 8, np.uint8)
+        lens = np.zeros(max(n, 1), np.int32)
+        _check(self._L.sfa_zstd_device(self._h, blob.ctypes.data_as(C.c_void_p), in_off.ctypes.data_as(_lib.i64p), n,
+                                       out.ctypes.data_as(C.c_void_p), out_off.ctypes.data_as(_lib.i64p),
+                                       lens.ctypes.data_as(_lib.i32p)), "sfa_zstd_device")
+        return [None if lens[i] < 0 else out[out_off[i]:out_off[i] + lens[i]].tobytes() for i in range(n)]
+
     def decode_blow5_device(self, records, rec_off, record_zlib, signal_svb, capacity=None):
         """The device-side record decoder alone (tests): the stages of align_blow5 before the alignment, no host reader behind
         them.  -> (status int32[n], heads, raw_off int64[n+1], samples int16[raw_off[n]]).  status: 0 decoded, BLOW5_INFLATE /
@@ -434,7 +453,7 @@ class Aligner:
         samples = np.zeros(max(int(capacity), 1), np.int16)
         if rec.size == 0:
             rec = np.zeros(1, np.uint8)
-        _check(self._L.sfa_decode_blow5_device(self._h, rec.ctypes.data_as(C.c_void_p), ro.ctypes.data_as(_lib.i64p), n, int(bool(record_zlib)),
+        _check(self._L.sfa_decode_blow5_device(self._h, rec.ctypes.data_as(C.c_void_p), ro.ctypes.data_as(_lib.i64p), n, _press(record_zlib),
                                                int(bool(signal_svb)), status.ctypes.data_as(_lib.i32p), C.cast(heads, C.c_void_p),
                                                raw_off.ctypes.data_as(_lib.i64p), samples.ctypes.data_as(C.POINTER(C.c_int16)), int(capacity)),
                "sfa_decode_blow5_device")
@@ -884,6 +903,18 @@ class Blow5File:
             self.close()
         except Exception:
             pass
+
+
+def zstd_decompress(data, cap=None):
+    """The zstd record decompressor of the BLOW5 reader on its own (the library's decoder, no libzstd): bytes -> bytes, or None
+    where the frames are malformed or hold more than `cap` bytes (default: 4x the input + 4 KB, the reader's rule)."""
+    L = _lib.load()
+    data = bytes(data)
+    if cap is None:
+        cap = 4 * len(data) + 4096
+    out = np.zeros(max(int(cap), 1), np.uint8)
+    got = L.sfa_zstd_decompress(data, len(data), out.ctypes.data_as(C.c_void_p), int(cap))
+    return None if got < 0 else out[:got].tobytes()
 
 
 def detect_events(raw, meta, rna=False):

@@ -239,7 +239,9 @@ void write_paf(const Run &run, const Slot &sl) {
 // from the host: a node's cores do not grow with its GPUs, so it is the default from three devices on.
 bool choose_gpu_parse(const Opt &o, const sfa::Blow5Reader &reader) {
     if (reader.ascii() && o.gpu_parse == 1) die("--gpu-parse decodes BLOW5 records: a SLOW5 ASCII file is parsed on the host threads");
-    return !o.host_events && !reader.ascii() && (o.gpu_parse < 0 ? o.devices.size() > 2 : o.gpu_parse == 1);
+    // zstd records (record_press 2): the host threads unless --gpu-parse asks for the device (DESIGN.md section 6 has the measurement)
+    const bool by_default = reader.record_press() == 2 ? false : o.devices.size() > 2;
+    return !o.host_events && !reader.ascii() && (o.gpu_parse < 0 ? by_default : o.gpu_parse == 1);
 }
 
 bool load_batch(Run &run, Slot &sl) {
@@ -309,7 +311,7 @@ void align_stage(Run &run, Slot &sl, sfa_ctx_t *ctx) {
         int rc;
         if (run.gpu_parse) {
             sl.heads.resize(n);
-            rc = sfa_align_blow5(ctx, static_cast<const uint8_t *>(sl.rec_bytes.data()), sl.rec_off.data(), n, run.reader.records_zlib(),
+            rc = sfa_align_blow5(ctx, static_cast<const uint8_t *>(sl.rec_bytes.data()), sl.rec_off.data(), n, run.reader.record_press(),
                                  run.reader.signal_svb(), o.prefix, o.query, rows, sl.info.data(), sl.heads.data(), qev);
         } else if (run.gpu_events) {
             rc = sfa_align_raw_ex(ctx, static_cast<const int16_t *>(sl.raw.data()), sl.raw_off.data(), sl.scaling.data(), n, o.prefix, o.query, rows,

@@ -1,8 +1,12 @@
-// blow5.cpp -- see blow5.hpp.  zlib is the only dependency (zstd-compressed files are rejected with a message,
-// like a reference binary built without zstd=1).
+// blow5.cpp -- see blow5.hpp.  zlib is the only dependency: zstd records are decoded by the project's own decoder
+// (../zstd_lane.hpp, the text the device compiles as well).
 #include "blow5.hpp"
 
 #include "inflate.hpp"
+#ifndef SFA_HOST_HARNESS
+#define SFA_HOST_HARNESS  // zstd_lane.hpp as host code
+#endif
+#include "../zstd_lane.hpp"
 
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -76,6 +80,24 @@ bool inflate_all(const uint8_t *src, size_t n, const uint8_t **out, size_t *len)
     if (rc != Z_STREAM_END) return false;
     *out = inf.buf.data();
     *len = have;
+    return true;
+}
+
+// One zstd record -> this thread's buffer.  The buffer follows the rule of the device route: 4x the record + 4 KB, or what the
+// frame header states where it states a size; a record that needs (or states) more does not decompress.
+bool zstd_all(const uint8_t *src, size_t n, const uint8_t **out, size_t *len) {
+    thread_local std::vector<uint8_t> buf, scratch;
+    const int64_t limit = static_cast<int64_t>(n) * 4 + 4096, stated = zstd_stated_size(src, static_cast<int64_t>(n));
+    if (stated > limit) return false;
+    // (a file may hold frames behind the first: only a record of one frame is sized by its header)
+    const int64_t cap = limit;
+    if (buf.size() < static_cast<size_t>(cap)) buf.resize(static_cast<size_t>(cap));
+    const size_t need = static_cast<size_t>(zstd_scratch_bytes(cap));
+    if (scratch.size() < need) scratch.resize(need);
+    const int got = zstd_frame_lane(src, static_cast<int64_t>(n), buf.data(), cap, scratch.data());
+    if (got < 0) return false;
+    *out = buf.data();
+    *len = static_cast<size_t>(got);
     return true;
 }
 
@@ -243,8 +265,8 @@ bool Blow5Reader::open(const std::string &path) {
     }
     data_begin_ = pos_ = 68 + static_cast<uint64_t>(hsize);
     limit_pos_ = limit_records_ = UINT64_MAX;
-    if (record_press_ > 1) {
-        err_ = path + ": record compression method " + std::to_string(record_press_) + " is not supported (zlib or none only)";
+    if (record_press_ > 2) {
+        err_ = path + ": record compression method " + std::to_string(record_press_) + " is not supported (zlib, zstd or none only)";
         return false;
     }
     if (signal_press_ > 1) {
@@ -623,7 +645,7 @@ bool Blow5Reader::parse(const std::vector<uint8_t> &mem, Blow5Record *rec, std::
 
 bool Blow5Reader::parse(const uint8_t *mem, size_t size, Blow5Record *rec, std::string *err) const {
     if (ascii_) return parse_slow5_line(mem, size, n_aux_, rec, err);
-    return parse_blow5_record(mem, size, record_press_ == 1, signal_press_ == 1, rec, err);
+    return parse_blow5_record(mem, size, record_press_, signal_press_ == 1, rec, err);
 }
 
 namespace {
@@ -631,10 +653,26 @@ namespace {
 bool parse_payload(const uint8_t *p, const uint8_t *end, int signal_svb, Blow5Record *rec, std::string *err);
 }  // namespace
 
-bool parse_blow5_record(const uint8_t *mem, size_t size, int record_zlib, int signal_svb, Blow5Record *rec, std::string *err) {
+int64_t zstd_decompress(const uint8_t *src, size_t n, uint8_t *dst, size_t cap) {
+    thread_local std::vector<uint8_t> scratch;
+    const size_t need = static_cast<size_t>(zstd_scratch_bytes(static_cast<int64_t>(cap)));
+    if (scratch.size() < need) scratch.resize(need);
+    return zstd_frame_lane(src, static_cast<int64_t>(n), dst, static_cast<int64_t>(cap), scratch.data());
+}
+
+bool parse_blow5_record(const uint8_t *mem, size_t size, int record_press, int signal_svb, Blow5Record *rec, std::string *err) {
     rec->record_bytes = size;
     const uint8_t *p = mem, *end = p + size;
-    if (record_zlib) {
+    if (record_press == 2) {
+        const uint8_t *plain = nullptr;  // this thread's buffer, valid until its next record
+        size_t plain_len = 0;
+        if (!zstd_all(mem, size, &plain, &plain_len)) {
+            *err = "malformed BLOW5: record does not decompress (zstd)";
+            return false;
+        }
+        p = plain;
+        end = p + plain_len;
+    } else if (record_press) {
         const uint8_t *inflated = nullptr;  // this thread's buffer, valid until its next record
         size_t inflated_len = 0;
         if (!inflate_all(mem, size, &inflated, &inflated_len)) {
@@ -650,10 +688,11 @@ bool parse_blow5_record(const uint8_t *mem, size_t size, int record_zlib, int si
 // Two records by one thread: their zlib streams are inflated side by side (inflate.hpp: two dependence chains keep a core busier
 // than one); everything else is parse_blow5_record's, and so is the result -- a record the paired decoder declines goes through
 // the single-record path (own decoder, then zlib), errors are reported per record.
-void parse_blow5_record_pair(const uint8_t *const mem[2], const size_t size[2], int record_zlib, int signal_svb, Blow5Record *const rec[2],
+void parse_blow5_record_pair(const uint8_t *const mem[2], const size_t size[2], int record_press, int signal_svb, Blow5Record *const rec[2],
                              std::string *const err[2], bool ok[2]) {
-    if (!record_zlib) {
-        for (int k = 0; k < 2; ++k) ok[k] = parse_blow5_record(mem[k], size[k], record_zlib, signal_svb, rec[k], err[k]);
+    const int record_zlib = record_press;
+    if (!record_press || record_press == 2) {  // (only zlib streams have a paired decoder)
+        for (int k = 0; k < 2; ++k) ok[k] = parse_blow5_record(mem[k], size[k], record_press, signal_svb, rec[k], err[k]);
         return;
     }
     thread_local std::vector<uint8_t> buf0, buf1;
@@ -703,7 +742,7 @@ void Blow5Reader::parse_pair(const uint8_t *const mem[2], const size_t size[2], 
         for (int k = 0; k < 2; ++k) ok[k] = parse_slow5_line(mem[k], size[k], n_aux_, rec[k], err[k]);
         return;
     }
-    parse_blow5_record_pair(mem, size, record_press_ == 1, signal_press_ == 1, rec, err, ok);
+    parse_blow5_record_pair(mem, size, record_press_, signal_press_ == 1, rec, err, ok);
 }
 
 int Blow5Reader::next(Blow5Record *rec) {

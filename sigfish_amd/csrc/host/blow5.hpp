@@ -5,7 +5,7 @@
 //   magic "BLOW5\1" | version u8[3] | record_press u8 | num_read_groups u32 | signal_press u8 (>= 0.2.0) |
 //   zero pad to byte 64 | ascii_header_size u32 | ascii header ("@attr\tv0[\tv1..]" lines, "#types", "#names") |
 //   records: [u64 size][payload] ... | EOF marker "5WOLB"
-//   payload (after inflating the whole record when record_press == zlib):
+//   payload (after decompressing the whole record when record_press == zlib (1) or zstd (2)):
 //   u16 id_len, id, u32 read_group, f64 digitisation, f64 offset, f64 range, f64 sampling_rate, u64 len,
 //   signal bytes, auxiliary fields (ignored here).  With signal_press == svb-zd, `len` is the compressed byte
 //   count and the signal is u32 n + StreamVByte(keys ceil(n/4) B, data 1-4 B little endian) of zig-zag deltas.
@@ -37,13 +37,16 @@ struct Blow5Record {
 
 // One record's bytes -> fields + samples, given the file's compression methods (what Blow5Reader::parse does; free-standing
 // for callers that hold record bytes without a reader, e.g. the fallback of the device-side decoder)
-bool parse_blow5_record(const uint8_t *mem, size_t size, int record_zlib, int signal_svb, Blow5Record *rec, std::string *err);
+// record_press: the file's method -- 0 none, 2 zstd, any other value zlib (what callers that pass a flag mean by it)
+bool parse_blow5_record(const uint8_t *mem, size_t size, int record_press, int signal_svb, Blow5Record *rec, std::string *err);
+// The zstd decoder of the reader on its own (zstd_lane.hpp): frames in src[0..n) -> dst[0..cap); bytes produced, or -1
+int64_t zstd_decompress(const uint8_t *src, size_t n, uint8_t *dst, size_t cap);
 // One line of a SLOW5 ASCII file (without its newline) -> fields + samples, with slow5lib's acceptance rules for the numbers
 // (slow5_misc.c:103-156: no signs or leading zeros on the unsigned columns, digits '.' '-' only in the doubles);
 // `n_aux`: auxiliary columns the header announced -- the line must carry exactly that many more
 bool parse_slow5_line(const uint8_t *mem, size_t size, uint32_t n_aux, Blow5Record *rec, std::string *err);
 // ... and two of them by one thread, their zlib streams inflated side by side (same results, record by record)
-void parse_blow5_record_pair(const uint8_t *const mem[2], const size_t size[2], int record_zlib, int signal_svb, Blow5Record *const rec[2],
+void parse_blow5_record_pair(const uint8_t *const mem[2], const size_t size[2], int record_press, int signal_svb, Blow5Record *const rec[2],
                              std::string *const err[2], bool ok[2]);
 
 class Blow5Reader {
@@ -68,6 +71,7 @@ class Blow5Reader {
     bool mapped() const { return map_ != nullptr; }           // next_view() works (regular file, mmap succeeded)
     bool ascii() const { return ascii_; }                     // SLOW5 ASCII: records are lines (host parsing only)
     bool records_zlib() const { return record_press_ == 1; }  // the whole record is a zlib stream
+    int record_press() const { return record_press_; }        // 0 none, 1 zlib, 2 zstd
     bool signal_svb() const { return signal_press_ == 1; }    // the signal is StreamVByte of zig-zag deltas
     const std::string &error() const { return err_; }
     // Walk the mapping ahead of next_view() on a helper thread, one byte per page, at most `window` bytes ahead: the first

@@ -247,6 +247,9 @@ int sfa_set_option(sfa_ctx_t *c, const char *key, int64_t value) {
     } else if (k == "ev_parallel") {
         if (value < 0 || value > 3) return fail(SFA_EINVAL, "ev_parallel must be 0..3 (bit 0: prefix sums, bit 1: peak picker)");
         c->opt_ev_parallel = value;
+    } else if (k == "zstd_tables") {
+        if (value != 0 && value != 1) return fail(SFA_EINVAL, "zstd_tables must be 0 (the device zstd decoder keeps its tables in HBM scratch) or 1 (in LDS)");
+        c->opt_zstd_tables = value;
     } else if (k == "debug_drop_quad" || k == "debug_drop_strip") {
         // test hooks (tests/test_bounded_waits_gpu.py): a hand-over that never comes.  Every batch then FAILS after the wait limit, so
         // they are not options: refused unless the process asks for them in its environment.

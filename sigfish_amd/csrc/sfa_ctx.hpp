@@ -308,16 +308,19 @@ struct RawSignal {  // sfa_align_raw: samples, prefix sums, t-statistics, events
 
 struct Blow5 {  // sfa_align_blow5: record bytes, inflated payloads, field rows
     DevBuf b_in, b_inoff, b_out, b_outoff, b_len, b_head, b_bad;
+    DevBuf b_zscratch, b_zoff;  // zstd records: every decoder's tables and literals (zstd_kernels.hpp), and where they start
     PinBuf h_head;
     bool bev_pending = false;
     int64_t blow5_fallbacks = 0;  // batches handed to the host reader because the device declined a record
-    // the inflate's own buffers; out_bytes < 0: records that are not compressed
-    int reserve_inflate(size_t in_bytes, int64_t out_bytes, size_t n) {
+    // the decompressor's own buffers; out_bytes < 0: records that are not compressed; scratch_bytes > 0: zstd records
+    int reserve_inflate(size_t in_bytes, int64_t out_bytes, size_t n, int64_t scratch_bytes = 0) {
         if (int rc = reserve_all(b_in, in_bytes + 128, b_inoff, 8 * (n + 1), b_len, 4 * n)) return rc;
+        if (scratch_bytes > 0)
+            if (int rc = reserve_all(b_zscratch, static_cast<size_t>(scratch_bytes) + 64, b_zoff, 8 * (n + 1))) return rc;
         return out_bytes < 0 ? SFA_OK : reserve_all(b_out, static_cast<size_t>(out_bytes) + 64, b_outoff, 8 * (n + 1));
     }
-    int reserve(size_t in_bytes, int64_t out_bytes, size_t n, size_t head_bytes) {
-        if (int rc = reserve_inflate(in_bytes, out_bytes, n)) return rc;
+    int reserve(size_t in_bytes, int64_t out_bytes, size_t n, size_t head_bytes, int64_t scratch_bytes = 0) {
+        if (int rc = reserve_inflate(in_bytes, out_bytes, n, scratch_bytes)) return rc;
         return reserve_all(b_head, n * head_bytes, h_head, n * head_bytes + 8 * n, b_bad, 4 * n);
     }
 };
@@ -375,7 +378,8 @@ struct sfa_ctx {
     int64_t opt_ckpt_interval = 0;           // force the checkpoint interval (power of two >= 4); 0 = auto
     int64_t opt_ckpt_budget = 32ll << 30;    // bytes of HBM the checkpoints of one batch may take
     int64_t opt_ev_parallel = 3;             // sfa_align_raw: bit 0 wave-per-read prefix sums where they are provably exact, bit 1 wave-per-read peak picker where its result is certified
-    int64_t opt_min_slice_reads = 65536;     // a batch is only cut into slices of at least this many reads
+    int64_t opt_zstd_tables = 1;             // device zstd decoder: 1 tables in LDS (at most 4 records per block; measured faster), 0 in the records' scratch areas in HBM
+    int64_t opt_min_slice_reads = 65536;    // a batch is only cut into slices of at least this many reads
     int64_t opt_segment_warm = 4;            // query lengths of warm-up in front of a segment
     int64_t opt_column_segments = 0;         // 0 = auto, 1 = off, N = segments per job for small batches (sweep_segment)
     int64_t opt_lane_widening = 0;           // 0 = by batch size; 1, 2, 4 = fixed (rows per lane / w, lanes per read * w)

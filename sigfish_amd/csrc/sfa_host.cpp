@@ -384,6 +384,12 @@ int64_t sfa_inflate_zlib(const uint8_t *in, size_t n, uint8_t *out, size_t cap) 
     return static_cast<int64_t>(len);
 }
 
+int64_t sfa_zstd_decompress(const uint8_t *src, size_t n, uint8_t *dst, size_t cap) {
+    if (!src || (!dst && cap)) return SFA_EINVAL;
+    uint8_t none = 0;
+    return sfa::zstd_decompress(src, n, dst ? dst : &none, cap);
+}
+
 int sfa_inflate_zlib_pair(const uint8_t *in0, size_t n0, const uint8_t *in1, size_t n1, uint8_t *out0, size_t cap0, uint8_t *out1,
                           size_t cap1, int64_t len[2]) {
     if (!in0 || !in1 || !len || (!out0 && cap0) || (!out1 && cap1)) return SFA_EINVAL;

@@ -5,6 +5,7 @@
 #include "events_kernels.hpp"
 #define SFA_DEFINE_BLOW5_KERNELS
 #include "blow5_kernels.hpp"
+#include "zstd_kernels.hpp"
 #include "host/blow5.hpp"
 #include "pre_rules.hpp"
 
@@ -243,6 +244,7 @@ struct Blow5Call {
     std::vector<double> scaling;   // [n][3] digitisation, offset, range: the arguments of the raw path
     std::vector<int16_t> raw;      // the host reader's samples (the device route leaves them on the device)
     std::vector<int32_t> status;   // [n] what the device stages made of every record: 0 decoded, or one of kRec* (include/sigfish_amd.h)
+    std::vector<int64_t> zoff;     // zstd records: [n + 1] where every decoder's scratch area starts (read by an asynchronous copy, as slot is)
 };
 constexpr int kDeclined = 1;  // a device route's answer beside SFA_OK and errors: the host reader takes the batch (sfa_last_error() says why)
 constexpr int32_t kRecInflate = SFA_BLOW5_INFLATE, kRecFields = SFA_BLOW5_FIELDS, kRecStream = SFA_BLOW5_STREAM;
@@ -273,7 +275,7 @@ static void fill_head(sfa_read_head_t &h, double *scaling, const void *id, int32
     h.record_bytes = record_bytes;
 }
 
-// records up, inflated (zlib) and their fields parsed into head rows: launches only
+// records up, decompressed (zlib: blow5_inflate_kernel, zstd: blow5_zstd_kernel) and their fields parsed into head rows: launches only
 static int blow5_launch_fields(sfa_ctx_t *c, Blow5Call &k) {
     const int32_t n = k.n;
     ctx::Blow5 &b = c->blow5;
@@ -283,12 +285,24 @@ static int blow5_launch_fields(sfa_ctx_t *c, Blow5Call &k) {
     // more is handed to the host reader with the rest of the batch)
     std::vector<int64_t> &slot = k.slot;
     for (int32_t i = 0; i < n; ++i) slot[i + 1] = slot[i] + (k.record_zlib ? (((k.rec_off[i + 1] - k.rec_off[i]) * 4 + 4096 + 15) & ~int64_t(15)) : 0);
-    if (int rc = b.reserve(static_cast<size_t>(in_bytes), k.record_zlib ? slot[n] : -1, static_cast<size_t>(n), sfa::kBlow5HeadBytes)) return rc;
+    // zstd records: every decoder's tables and the literals of a block (at most the slot, at most 128 KB) in an area of its own
+    const bool zstd = k.record_zlib == SFA_PRESS_ZSTD;
+    std::vector<int64_t> &zoff = k.zoff;
+    zoff.assign(zstd ? n + 1 : 0, 0);
+    for (int32_t i = 0; zstd && i < n; ++i) zoff[i + 1] = zoff[i] + sfa::blow5_zstd_scratch_bytes(slot[i + 1] - slot[i]);
+    if (int rc = b.reserve(static_cast<size_t>(in_bytes), k.record_zlib ? slot[n] : -1, static_cast<size_t>(n), sfa::kBlow5HeadBytes, zstd ? zoff[n] : 0)) return rc;
     HIP_TRY(hipMemcpyAsync(b.b_in.p, k.records, static_cast<size_t>(in_bytes), hipMemcpyHostToDevice, sp));
     HIP_TRY(hipMemcpyAsync(b.b_inoff.p, k.rec_off, 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, sp));
     HIP_TRY(hipMemsetAsync(b.b_bad.p, 0, 4 * static_cast<size_t>(n), sp));
     HIP_TRY(hipEventRecord(c->bev[0], sp));
-    if (k.record_zlib) {
+    if (zstd) {
+        HIP_TRY(hipMemcpyAsync(b.b_outoff.p, slot.data(), 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, sp));
+        HIP_TRY(hipMemcpyAsync(b.b_zoff.p, zoff.data(), 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, sp));
+        sfa::launch_blow5_zstd(sfa::ZstdArgs{b.b_in.as<uint8_t>(), b.b_inoff.as<int64_t>(), b.b_out.as<uint8_t>(), b.b_outoff.as<int64_t>(), b.b_len.as<int32_t>(),
+                                             b.b_zscratch.as<uint8_t>(), b.b_zoff.as<int64_t>(), n},
+                               c->cu_count, c->opt_zstd_tables == 1, sp);
+        KERNEL_TRY();
+    } else if (k.record_zlib) {
         HIP_TRY(hipMemcpyAsync(b.b_outoff.p, slot.data(), 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, sp));
         sfa::InflateArgs ia{b.b_in.as<uint8_t>(), b.b_inoff.as<int64_t>(), b.b_out.as<uint8_t>(), b.b_outoff.as<int64_t>(), b.b_len.as<int32_t>(), n};
         const int lanes = inflate_lanes(n, c->cu_count);
@@ -481,6 +495,36 @@ int sfa_inflate_zlib_device(sfa_ctx_t *c, const uint8_t *in, const int64_t *in_o
     KERNEL_TRY();
     HIP_TRY(hipMemcpyAsync(out, c->blow5.b_out.p, static_cast<size_t>(out_off[n]), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(out_len, c->blow5.b_len.p, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return SFA_OK;
+}
+
+// (testing hook of the device-side zstd decoder alone: n records in, their bytes out; see include/sigfish_amd.h)
+int sfa_zstd_device(sfa_ctx_t *c, const uint8_t *in, const int64_t *in_off, int32_t n, uint8_t *out, const int64_t *out_off, int32_t *out_len) {
+    if (!c || !c->shards.empty() || n < 0 || (n > 0 && (!in || !in_off || !out || !out_off || !out_len)))
+        return fail(SFA_EINVAL, "sfa_zstd_device: bad argument (single-device context needed)");
+    if (n == 0) return SFA_OK;
+    if (in_off[0] != 0 || out_off[0] != 0) return fail(SFA_EINVAL, "sfa_zstd_device: offsets must start at 0");
+    std::vector<int64_t> zoff(n + 1, 0);
+    for (int32_t i = 0; i < n; ++i) {
+        if (in_off[i + 1] < in_off[i] || out_off[i + 1] < out_off[i]) return fail(SFA_EINVAL, "sfa_zstd_device: offsets not monotone at record %d", i);
+        zoff[i + 1] = zoff[i] + sfa::blow5_zstd_scratch_bytes(out_off[i + 1] - out_off[i]);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    hipStream_t st = c->stream;
+    ctx::Blow5 &b = c->blow5;
+    if (int rc = b.reserve_inflate(static_cast<size_t>(in_off[n]), out_off[n], static_cast<size_t>(n), zoff[n])) return rc;
+    HIP_TRY(hipMemcpyAsync(b.b_in.p, in, static_cast<size_t>(in_off[n]), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b.b_inoff.p, in_off, 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b.b_outoff.p, out_off, 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b.b_zoff.p, zoff.data(), 8 * static_cast<size_t>(n + 1), hipMemcpyHostToDevice, st));
+    sfa::launch_blow5_zstd(sfa::ZstdArgs{b.b_in.as<uint8_t>(), b.b_inoff.as<int64_t>(), b.b_out.as<uint8_t>(), b.b_outoff.as<int64_t>(), b.b_len.as<int32_t>(),
+                                         b.b_zscratch.as<uint8_t>(), b.b_zoff.as<int64_t>(), n},
+                           c->cu_count, c->opt_zstd_tables == 1, st);
+    KERNEL_TRY();
+    HIP_TRY(hipMemcpyAsync(out, b.b_out.p, static_cast<size_t>(out_off[n]), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_len, b.b_len.p, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return SFA_OK;
 }
