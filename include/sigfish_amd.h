@@ -113,6 +113,7 @@ typedef struct {
                               window, so that pass 2 went on to the sparse HBM store (thousands of steps each) */
     int64_t lck_from_scratch; /* with lds_ckpt: reads whose winning window is one of the first two of its strand: no snapshot, pass 2
                                  walks the strand from its start (at most two windows) */
+    double class_ms;       /* sfa_session_classes only (0 otherwise): the masked reduction over the carried rows and its merge */
 } sfa_profile_t;
 
 /* How a batch is laid out on the device (host logic only; needs no GPU). */
@@ -302,6 +303,62 @@ void sfa_session_destroy(sfa_session_t *s);
  * SFA_SESSION_RESWEEP changes nothing: the carried rows are still needed (a window beyond SFA_MAX_QUERY events runs as pieces).
  * Neither does SFA_SESSION_SPREAD: the session holds the same rows, device r of G those of (n_slots - r + G - 1) / G slots. */
 int64_t sfa_session_bytes(int64_t total_columns, int32_t n_slots, uint32_t session_flags);
+
+/* ---- target classes: the best on-target and the best off-target score of a slot ----------------------------------------------
+ * Adaptive sampling asks whether a read comes from a region the user wants, not where exactly it maps.  The mapq of a row is
+ * built from the two best windows anywhere, so two good windows inside one target depress it, and a read with nothing good on
+ * target never reaches it.  What answers the question is the lowest cost among the carried row's on-target columns against the
+ * lowest among the others -- data the session holds already (the rows sfa_session_row copies back).
+ * A target is an interval [begin, end) of one contig in the coordinates a row reports (sfa_result_t.pos_st / pos_end: after
+ * the strand flip and ref_st_offset).  Column j of job (contig, strand) is ON target when the coordinate a row reports for an
+ * alignment that ENDS in column j lies in an interval of that contig: j + ref_st_offset on '+' (the row's pos_end) and
+ * ref_length - j + ref_st_offset on '-' (there the end column is the row's pos_st; its pos_end needs the start column, which a
+ * SFA_SESSION_NO_START session does not carry).  Intervals may overlap, touch and come in any order.
+ * The mask is one bit per column of a slot's row -- total_columns / 8 bytes per SESSION, shared by all slots, not counted by
+ * sfa_session_bytes; a call adds 16 bytes per named slot and 8192 columns, and 40 bytes per named slot. */
+typedef struct {
+    int32_t contig, begin, end;
+} sfa_target_t;
+
+/* A slot's class result: cost, contig, coordinate (as above) and strand of the best on-target and the best off-target column.
+ * Ties: the lowest cost, then the lowest column of the slot's row -- jobs in their order, '+' before '-', then the lowest column
+ * of the job.  A class without columns: score +inf, rid -1, pos_end -1, strand 0.  n_events: events the slot has received;
+ * valid 0: the slot is empty or poisoned (scores +inf, rids -1). */
+typedef struct {
+    float on_score, off_score;
+    /* on_pos_end / off_pos_end: the END-COLUMN coordinate of the class's best column -- where an alignment ending in that column
+     * ends in the coordinates rows report.  On '+' that is the pos_end a finalized row reports; on '-' the flip makes it the
+     * row's pos_st (the row's pos_end there is built from the START column, which a class does not know). */
+    int32_t on_rid, on_pos_end, off_rid, off_pos_end;
+    int8_t on_strand, off_strand;
+    int8_t pad[2];
+    int32_t n_events;
+    int32_t valid;
+} sfa_class_t;
+
+/* Sets the session's targets: the mask is built on the host and uploaded.  n = 0 switches the feature off and frees the mask.
+ * Allowed at any time (the mask does not depend on the slots' state).  On a spread session it goes to every sub-session.
+ * SFA_EINVAL: a contig out of range, begin < 0, end <= begin, end beyond the contig (the largest coordinate a row of the contig
+ * reports is ref_st_offset + ref_length, so end may be one more); a SFA_SESSION_RESWEEP session (its carried row belongs to the
+ * reversed query; what its minimum means has not been looked into).  SFA_ERANGE: a reference of 2^31 columns or more. */
+int sfa_session_targets(sfa_session_t *s, const sfa_target_t *targets, int32_t n);
+
+/* Columns of a slot's row that are on target (0 without targets; on a spread session every sub-session holds the same mask). */
+int64_t sfa_session_target_columns(sfa_session_t *s);
+
+/* The class results of slot[0..n) into out[0..n).  One masked min-reduction over the slots' carried cost rows (no sweep kernel
+ * changes, a session without targets launches what it always launched), event mode and raw mode, with and without
+ * SFA_SESSION_NO_START.  Blocking, on the context's stream; sfa_profile_t.class_ms is its device time (the other fields of the
+ * profile are zero).  A spread session partitions the call by shard and answers in the caller's order.
+ * SFA_EINVAL: no targets, a slot out of range or named twice. */
+int sfa_session_classes(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_class_t *out);
+
+/* The decision from a class result (host only): with n = n_events >= min_events, off_score - on_score >= margin * n says ON
+ * target, on_score - off_score >= margin * n says OFF target; an empty class counts as +inf, both empty decide nothing.
+ * mode 0 (enrich): on -> 'A' (accept), off -> 'U' (unblock); mode 1 (deplete): the other way round.  0: no decision (also for
+ * valid = 0, an unknown mode, a margin that is negative or not finite).  Queries are z-normalised, so a per-event margin has no
+ * unit.  Nobody has measured a good margin: there is no default. */
+int sfa_target_decide(const sfa_class_t *cls, int32_t mode, int32_t min_events, float margin);
 
 /* ---- event maps of a slot's row: the warp path of the real-time path -------------------------------------------------------
  * sfa_session_event_maps is sfa_event_maps for rows a SESSION returned: the reference-column -> query-event map

@@ -26,7 +26,8 @@ class SfaProfile(C.Structure):
                 ("total_ms", C.c_double), ("cells", C.c_int64), ("fill_launches", C.c_int64),
                 ("ckpt_interval", C.c_int64), ("ckpt_bytes", C.c_int64), ("n_tasks", C.c_int64),
                 ("n_chunks", C.c_int64), ("n_segments", C.c_int64), ("segment_reruns", C.c_int64),
-                ("events_ms", C.c_double), ("normalise_ms", C.c_double), ("non_finite_reads", C.c_int64), ("decode_ms", C.c_double), ("blow5_fallbacks", C.c_int64), ("lds_ckpt", C.c_int64), ("trace_margin", C.c_int64), ("fused_trace", C.c_int64), ("lck_fallbacks", C.c_int64), ("lck_from_scratch", C.c_int64)]
+                ("events_ms", C.c_double), ("normalise_ms", C.c_double), ("non_finite_reads", C.c_int64), ("decode_ms", C.c_double), ("blow5_fallbacks", C.c_int64), ("lds_ckpt", C.c_int64), ("trace_margin", C.c_int64), ("fused_trace", C.c_int64), ("lck_fallbacks", C.c_int64), ("lck_from_scratch", C.c_int64),
+                ("class_ms", C.c_double)]
 
 
 class SfaPlanInfo(C.Structure):
@@ -55,6 +56,16 @@ class SfaSessionRawInfo(C.Structure):
                 ("norm_sd", C.c_float), ("status", C.c_int32), ("norm_window", C.c_int32)]
 
 
+class SfaTarget(C.Structure):
+    _fields_ = [("contig", C.c_int32), ("begin", C.c_int32), ("end", C.c_int32)]
+
+
+class SfaClass(C.Structure):
+    _fields_ = [("on_score", C.c_float), ("off_score", C.c_float), ("on_rid", C.c_int32), ("on_pos_end", C.c_int32), ("off_rid", C.c_int32),
+                ("off_pos_end", C.c_int32), ("on_strand", C.c_int8), ("off_strand", C.c_int8), ("pad", C.c_int8 * 2), ("n_events", C.c_int32),
+                ("valid", C.c_int32)]
+
+
 class SfaSessionAuto(C.Structure):
     _fields_ = [("target", C.c_int64), ("frozen_at", C.c_int64), ("skip", C.c_int32), ("status", C.c_int32)]
 
@@ -69,7 +80,8 @@ SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "
            "sfa_session_raw_config", "sfa_session_extend_raw", "sfa_session_events", "sfa_session_raw_bytes", "sfa_session_query_span", "sfa_session_row",
            "sfa_session_raw_recalibrate", "sfa_session_candidates_config", "sfa_session_candidates",
            "sfa_session_raw_auto_start", "sfa_session_auto_start", "sfa_session_auto_bytes", "sfa_auto_start_target", "sfa_session_auto_ms",
-           "sfa_session_event_maps", "sfa_session_keep_events", "sfa_session_keep_bytes"]
+           "sfa_session_event_maps", "sfa_session_keep_events", "sfa_session_keep_bytes",
+           "sfa_session_targets", "sfa_session_target_columns", "sfa_session_classes", "sfa_target_decide"]
 
 _lib = None
 
@@ -199,5 +211,10 @@ def load():
     L.sfa_session_keep_events.argtypes = [vp, C.c_int32]
     L.sfa_session_keep_bytes.argtypes = [C.c_int32, C.c_int32]
     L.sfa_session_keep_bytes.restype = C.c_int64
+    L.sfa_session_targets.argtypes = [vp, C.POINTER(SfaTarget), C.c_int32]
+    L.sfa_session_target_columns.argtypes = [vp]
+    L.sfa_session_target_columns.restype = C.c_int64
+    L.sfa_session_classes.argtypes = [vp, i32p, C.c_int32, vp]
+    L.sfa_target_decide.argtypes = [C.POINTER(SfaClass), C.c_int32, C.c_int32, C.c_float]
     _lib = L
     return L

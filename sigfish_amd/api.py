@@ -32,6 +32,11 @@ assert SESSION_RAW_INFO_DTYPE.itemsize == C.sizeof(_lib.SfaSessionRawInfo)
 RAW_CALIBRATED, RAW_FULL, RAW_ENDED, RAW_POISONED = 1, 2, 4, 8  # bits of SESSION_RAW_INFO_DTYPE's status
 SESSION_AUTO_DTYPE = np.dtype([("target", "<i8"), ("frozen_at", "<i8"), ("skip", "<i4"), ("status", "<i4")])  # sfa_session_auto_t
 AUTO_PENDING, AUTO_RESOLVED, AUTO_NO_TARGET, AUTO_NO_EVENT, AUTO_BEYOND_MAX, AUTO_AT_FINAL = 0, 1, 2, 3, 4, 16  # SFA_AUTO_*
+TARGET_DTYPE = np.dtype([("contig", "<i4"), ("begin", "<i4"), ("end", "<i4")])  # sfa_target_t
+CLASS_DTYPE = np.dtype([("on_score", "<f4"), ("off_score", "<f4"), ("on_rid", "<i4"), ("on_pos_end", "<i4"), ("off_rid", "<i4"), ("off_pos_end", "<i4"),
+                        ("on_strand", "i1"), ("off_strand", "i1"), ("pad", "i1", (2,)), ("n_events", "<i4"), ("valid", "<i4")])  # sfa_class_t
+assert TARGET_DTYPE.itemsize == C.sizeof(_lib.SfaTarget) and CLASS_DTYPE.itemsize == C.sizeof(_lib.SfaClass)
+ENRICH, DEPLETE = 0, 1  # the modes of target_decide
 RAW_RECALIBRATED = 16  # ... and the bit of one call: the slot was recalibrated and swept again from event 0
 RECAL_AT_END = 0x1     # SFA_RECAL_AT_END
 RECAL_MAX_POINTS = 32
@@ -680,6 +685,35 @@ class Session:
                "sfa_session_query_span")
         return a, b
 
+    def set_targets(self, intervals):
+        """The session's targets (sfa_session_targets): (contig, begin, end) triples or a TARGET_DTYPE array, [begin, end) in the
+        coordinates rows report (pos_st / pos_end: after the strand flip and ref_st_offset); they may overlap, touch and come in
+        any order.  A column is on target when the coordinate a row reports for an alignment ENDING in it lies in an interval of
+        its contig.  An empty list switches the feature off.  Allowed at any time; refused on a resweep session.  The mask takes
+        total_columns / 8 bytes of device memory, once per session."""
+        self._live()
+        t = _targets(intervals)
+        _check(self._L.sfa_session_targets(self._h, t.ctypes.data_as(C.POINTER(_lib.SfaTarget)) if len(t) else None, len(t)), "sfa_session_targets")
+
+    def target_columns(self):
+        """Columns of a slot's row that are on target (0 without targets)."""
+        self._live()
+        n = int(self._L.sfa_session_target_columns(self._h))
+        if n < 0:
+            _check(n, "sfa_session_target_columns")
+        return n
+
+    def classes(self, slots):
+        """The best on-target and the best off-target column of the carried rows of `slots` (sfa_session_classes) ->
+        CLASS_DTYPE[len(slots)]: score, contig, coordinate and strand of either; an empty class has score +inf and rid -1; ties go
+        to the lowest cost, then the lowest column of the row (jobs in order, '+' before '-').  valid = 0: the slot is empty or
+        poisoned.  A slot may be named once."""
+        self._live()
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        out = np.zeros(len(sl), CLASS_DTYPE)
+        _check(self._L.sfa_session_classes(self._h, sl.ctypes.data_as(_lib.i32p), len(sl), out.ctypes.data_as(C.c_void_p)), "sfa_session_classes")
+        return out
+
     def reset(self, slots=None):
         """Forget the events of `slots` (None: of every slot); in raw mode the detector, normalisation and scaling as well."""
         self._live()
@@ -730,6 +764,51 @@ class Session:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def _targets(intervals):
+    if isinstance(intervals, np.ndarray) and intervals.dtype == TARGET_DTYPE:
+        return np.ascontiguousarray(intervals).reshape(-1)
+    t = np.zeros(len(intervals), TARGET_DTYPE)
+    for k, (contig, begin, end) in enumerate(intervals):
+        t[k] = (int(contig), int(begin), int(end))
+    return t
+
+
+def target_decide(cls, mode, min_events, margin):
+    """The decision from one CLASS_DTYPE record (sfa_target_decide; host arithmetic): with n = n_events >= min_events,
+    off_score - on_score >= margin * n says on target and on_score - off_score >= margin * n off target; mode ENRICH: on target
+    -> 'A' (accept), off target -> 'U' (unblock); DEPLETE the other way round; None: no decision.  margin is a cost per
+    z-normalised event; no good value has been measured, so there is no default."""
+    rec = np.ascontiguousarray(cls, CLASS_DTYPE).reshape(-1)
+    if len(rec) != 1:
+        raise SfaError("target_decide: one class record at a time")
+    got = int(_lib.load().sfa_target_decide(C.cast(rec.ctypes.data, C.POINTER(_lib.SfaClass)), int(mode), int(min_events), float(margin)))
+    return chr(got) if got else None
+
+
+def read_targets(path, names):
+    """A BED file as targets for Session.set_targets -> TARGET_DTYPE array: three columns (name, begin, end; further columns are
+    ignored), blank lines and lines that begin with '#', 'track' or 'browser' skipped.  names: the reference's contig names in
+    order (RefModel.names).  A contig that is not among them, a line with fewer than three columns or a coordinate that is no
+    integer is an error; the intervals themselves are checked by set_targets."""
+    index = {str(n): i for i, n in enumerate(names)}
+    out = []
+    with open(path) as fh:
+        for no, line in enumerate(fh, 1):
+            text = line.strip()
+            if not text or text.startswith("#") or text.split()[0] in ("track", "browser"):
+                continue
+            f = text.split("\t") if "\t" in text else text.split()
+            if len(f) < 3:
+                raise SfaError(f"read_targets: {path}:{no}: a BED line has at least three columns")
+            if f[0] not in index:
+                raise SfaError(f"read_targets: {path}:{no}: contig {f[0]!r} is not in the reference")
+            try:
+                out.append((index[f[0]], int(f[1]), int(f[2])))
+            except ValueError:
+                raise SfaError(f"read_targets: {path}:{no}: begin and end must be integers") from None
+    return _targets(out)
 
 
 def session_bytes(total_columns, n_slots, starts=True, resweep=False):

@@ -79,6 +79,10 @@ struct RealtimeOpt {
     bool resweep = false;          // --resweep: the session is created with SFA_SESSION_RESWEEP (lifts --rna's need for --invert)
     int32_t candidates = 0;        // --candidates: candidate lines (tp:A:S) behind every primary line, 1..4 (0: none)
     bool spread = false;           // --spread: one context over the whole --device list (sfa_init_devices), the session with SFA_SESSION_SPREAD
+    std::string targets;           // --targets FILE.bed: the session's targets; the early decision is the class decision (replay.hpp)
+    int32_t target_mode = -1;      // --enrich: 0, --deplete: 1 (exactly one of them with --targets)
+    float margin = 0.0f;           // --margin X: cost per query event between the classes (required with --targets: no default)
+    std::string trace;             // --trace FILE: the schedule's trace lines (replay.hpp)
 };
 
 // options.cpp: the option table, help and every check that needs no file and no device (exits for -V and help)

@@ -1,5 +1,6 @@
 // options.cpp -- the options of `sigfish-amd dtw` (src/dtw_main.c:125-277): table, help and the checks between options.
 // Nothing here opens a file or touches a device, so -V and help may exit() from here.
+#include <cmath>
 #include <getopt.h>
 
 #include <algorithm>
@@ -19,7 +20,7 @@ enum LongOpt {
     O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
     O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
     O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE,
-    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD
+    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_TRACE
 };
 
 const option kLongOptions[] = {
@@ -116,6 +117,8 @@ const option kRealtimeOptions[] = {
     {"resweep", no_argument, 0, O_RESWEEP}, {"dtw-std", no_argument, 0, O_DTW_STD}, {"from-end", no_argument, 0, O_FROM_END}, {"sam", no_argument, 0, 'a'},
     {"secondary", required_argument, 0, O_SECONDARY}, {"ranks", required_argument, 0, O_RANKS},
     {"candidates", required_argument, 0, O_CANDIDATES}, {"spread", no_argument, 0, O_SPREAD},
+    {"targets", required_argument, 0, O_TARGETS}, {"enrich", no_argument, 0, O_ENRICH}, {"deplete", no_argument, 0, O_DEPLETE},
+    {"margin", required_argument, 0, O_MARGIN}, {"trace", required_argument, 0, O_TRACE},
     {0, 0, 0, 0}};
 
 void realtime_help(FILE *fp, const RealtimeOpt &r) {
@@ -160,6 +163,15 @@ void realtime_help(FILE *fp, const RealtimeOpt &r) {
     fprintf(fp, "   --candidates INT           behind every primary line, the channel's next 1..4 candidates of the sorted list of the 5 best\n"
                 "                              windows (tp:A:S lines, best first, same span and tags): what dtw --secondary yes prints, for\n"
                 "                              the events the read has at its decision [off]\n");
+    fprintf(fp, "   --targets FILE.bed         adaptive sampling: the early decision is the class decision -- the best on-target column of the\n"
+                "                              read's carried row against the best off-target one (sfa_session_classes) -- in place of mapq;\n"
+                "                              needs --enrich or --deplete, and --margin; lines gain tc:A:<T|O|N> ac:A:<A|U|P> tm:f:<margin met>;\n"
+                "                              an accepted or proceeding read keeps its channel until it has passed, an unblocked one frees it;\n"
+                "                              not with --resweep [off]\n");
+    fprintf(fp, "   --enrich | --deplete       accept on-target reads and unblock off-target ones | the other way round\n");
+    fprintf(fp, "   --margin FLOAT             cost per query event by which one class must beat the other; nobody has measured a good value:\n"
+                "                              no default\n");
+    fprintf(fp, "   --trace FILE               write the schedule's trace (take / send / hold / decide lines) to FILE [off]\n");
     fprintf(fp, "   --pace yes|no              sleep so that tick t does not start before t x chunk-samples / sampling_rate seconds;\n"
                 "                              changes the timing report on stderr only, never the output [no]\n\n"
                 "output: PAF as dtw prints it, then ne:i:<query events at the decision> ns:i:<samples sent> dc:A:<E|F|R>\n");
@@ -173,7 +185,8 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     FILE *fp_help = stderr;
     int c, li = 0;
     bool secondary = false;
-    const char *recal = nullptr, *candidates = nullptr;
+    const char *recal = nullptr, *candidates = nullptr, *margin = nullptr;
+    bool enrich = false, deplete = false;
     while ((c = getopt_long(argc, argv, "p:q:t:v:o:ahV", kRealtimeOptions, &li)) >= 0) {
         switch (c) {
             case 't': o.threads = atoi(optarg); if (o.threads < 1) die("Number of threads should larger than 0."); break;
@@ -209,6 +222,11 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
             case O_RESWEEP: r.resweep = true; break;
             case O_CANDIDATES: candidates = optarg; break;
             case O_SPREAD: r.spread = true; break;
+            case O_TARGETS: r.targets = optarg; break;
+            case O_ENRICH: enrich = true; break;
+            case O_DEPLETE: deplete = true; break;
+            case O_MARGIN: margin = optarg; break;
+            case O_TRACE: r.trace = optarg; break;
             default: realtime_help(stderr, r); exit(EXIT_FAILURE);
         }
     }
@@ -234,6 +252,17 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     if (o.devices.size() != 1 && !r.spread) die("realtime: --device takes exactly one GPU: a session's rows live on one device (--spread deals the channels over a list)");
     if ((o.flag & F_INV) && !(o.flag & F_RNA)) die("Inversion is only available for RNA.");
     if ((o.flag & F_RNA) && !(o.flag & F_INV) && !r.resweep) die("realtime: --rna needs --invert (or --resweep): without it the query rows are the events reversed, and a session cannot take new events as row 0");
+    // adaptive sampling: everything that needs no file
+    if (r.targets.empty() && (enrich || deplete || margin)) die("realtime: --enrich, --deplete and --margin belong to --targets FILE.bed");
+    if (!r.targets.empty()) {
+        if (enrich == deplete) die("realtime: --targets needs exactly one of --enrich and --deplete");
+        if (!margin) die("realtime: --targets needs --margin: nobody has measured a good value, there is no default");
+        char *e = nullptr;
+        r.margin = strtof(margin, &e);
+        if (e == margin || *e || !(r.margin >= 0.0f) || !std::isfinite(r.margin)) die("realtime: --margin should be a number >= 0");
+        if (r.resweep) die("realtime: --targets is not available with --resweep: a resweep session's carried row belongs to the reversed query");
+        r.target_mode = enrich ? 0 : 1;
+    }
     if (r.norm_events < 0) r.norm_events = o.query;
     if (r.min_events < 0) r.min_events = o.query;
     if (r.norm_events < 25 || r.norm_events > o.query) die("realtime: --norm-events should be 25..q (the value of -q)");

@@ -5,12 +5,17 @@
 // needs --, sweep); what runs here
 // is the staging of a tick's samples, the decision rule and the printing.  With --spread the session's channels are dealt over
 // every GPU of --device (SFA_SESSION_SPREAD); the schedule counts ticks, so the output is the same bytes.
+// With --targets the early decision is the class decision (sfa_session_classes + sfa_target_decide, one call per tick), lines
+// gain the tc / ac / tm tags (target_tags) and accepted reads hold their channels (replay.hpp).
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
 #include <deque>
+#include <fstream>
+#include <sstream>
 #include <future>
 #include <thread>
 
@@ -114,10 +119,51 @@ struct Channels {
     }
 };
 
+// --targets: the BED file as the session's targets -- three columns, `#` / track / browser lines skipped, an unknown contig is an error
+std::vector<sfa_target_t> read_targets(const std::string &path, const Reference &ref) {
+    std::ifstream in(path);
+    if (!in) die("realtime: cannot open the targets file " + path);
+    std::vector<sfa_target_t> out;
+    std::string ln;
+    for (int no = 1; std::getline(in, ln); ++no) {
+        std::istringstream f(ln);
+        std::string name;
+        if (!(f >> name) || name[0] == '#' || name == "track" || name == "browser") continue;
+        long b = 0, e = 0;
+        if (!(f >> b >> e)) die("realtime: " + path + ":" + std::to_string(no) + ": a BED line has three columns: contig, begin, end");
+        int32_t rid = -1;
+        for (size_t r = 0; r < ref.contigs.size(); ++r)
+            if (ref.contigs[r].name == name) rid = static_cast<int32_t>(r);
+        if (rid < 0) die("realtime: " + path + ":" + std::to_string(no) + ": contig '" + name + "' is not in the reference");
+        if (b < INT32_MIN || b > INT32_MAX || e < INT32_MIN || e > INT32_MAX) die("realtime: " + path + ":" + std::to_string(no) + ": coordinate out of range");
+        out.push_back(sfa_target_t{rid, static_cast<int32_t>(b), static_cast<int32_t>(e)});
+    }
+    return out;
+}
+
+// the three tags a line gains with --targets (Python twin: realtime.target_tags): class, action, the per-event margin it had
+std::string target_tags(const sfa_class_t &c, const RealtimeOpt &r) {
+    const int dec = sfa_target_decide(&c, r.target_mode, r.min_events, r.margin);
+    const char tc = !dec ? 'N' : (((dec == 'A') == (r.target_mode == 0)) ? 'T' : 'O');
+    const double mine = r.target_mode == 0 ? c.on_score : c.off_score, other = r.target_mode == 0 ? c.off_score : c.on_score;
+    const double tm = c.n_events > 0 ? (other - mine) / static_cast<double>(c.n_events) : NAN;
+    char buf[96];
+    if (std::isnan(tm))
+        snprintf(buf, sizeof buf, "\ttc:A:%c\tac:A:%c\ttm:f:nan", tc, dec ? dec : 'P');
+    else
+        snprintf(buf, sizeof buf, "\ttc:A:%c\tac:A:%c\ttm:f:%.4f", tc, dec ? dec : 'P', tm);
+    return buf;
+}
+
 struct Report {
     int64_t lines[3] = {0, 0, 0};  // E, F, R
     int64_t unmapped = 0, decided = 0, sum_ne = 0, samples_sent = 0;
     std::vector<double> tick_s;
+    int64_t act_reads[3] = {0, 0, 0}, act_samples[3] = {0, 0, 0};  // --targets: A, U, P -- reads, samples sent plus held
+    void print_targets() const {
+        fprintf(stderr, "[realtime] targets: accepted (A) %ld reads, %ld samples\tunblocked (U) %ld reads, %ld samples\tproceeded (P) %ld reads, %ld samples (sent + held)\n",
+                (long)act_reads[0], (long)act_samples[0], (long)act_reads[1], (long)act_samples[1], (long)act_reads[2], (long)act_samples[2]);
+    }
     void print(const RealtimeOpt &r, const Channels &ch, double tick_signal_s) const {
         std::vector<double> t = tick_s;
         std::sort(t.begin(), t.end());
@@ -163,6 +209,14 @@ int realtime_run(int argc, char **argv, double t0) {
         if (sfa_session_raw_recalibrate(se, r.recal_at.data(), static_cast<int32_t>(r.recal_at.size()), r.recal_at_end ? SFA_RECAL_AT_END : 0) != SFA_OK)
             die(std::string("session: ") + sfa_last_error());
     if (r.candidates > 0 && sfa_session_candidates_config(se, r.candidates) != SFA_OK) die(std::string("session: ") + sfa_last_error());
+    const bool targets = !r.targets.empty();
+    if (targets) {
+        const std::vector<sfa_target_t> t = read_targets(r.targets, ref);
+        if (t.empty()) die("realtime: the targets file " + r.targets + " holds no interval");
+        if (sfa_session_targets(se, t.data(), static_cast<int32_t>(t.size())) != SFA_OK) die(std::string("targets: ") + sfa_last_error());
+    }
+    FILE *trace = nullptr;
+    if (!r.trace.empty() && !(trace = fopen(r.trace.c_str(), "w"))) die("realtime: cannot write the trace to " + r.trace);
     if (o.verbosity >= 4)
         fprintf(stderr, "[realtime::%.3f] initialised: %d channels, %ld samples per tick, skip %d, norm %d, query %d, early at %d events and mapq %d\n", realtime() - t0,
                 r.channels, (long)r.chunk_samples, o.prefix, r.norm_events, o.query, r.min_events, r.min_mapq);
@@ -172,7 +226,7 @@ int realtime_run(int argc, char **argv, double t0) {
     reader.start_prefault();
     ReadAhead ahead(reader, pool, 2 * static_cast<size_t>(C));
     Channels ch{ahead, std::vector<sfa::Blow5Record>(C)};
-    replay::Schedule sch(C, r.chunk_samples);
+    replay::Schedule sch(C, r.chunk_samples, trace, targets);
     const replay::Rule rule{r.min_events, r.min_mapq};
     Report rep;
 
@@ -185,7 +239,9 @@ int realtime_run(int argc, char **argv, double t0) {
     std::vector<uint8_t> end(C);
     std::vector<sfa_result_t> rows(C);
     std::vector<sfa_session_raw_info_t> info(C);
-    std::vector<char> reason(C), line(C);
+    std::vector<char> reason(C), line(C), action(C);
+    std::vector<sfa_class_t> cls(targets ? C : 0);
+    std::vector<int64_t> held;
     std::vector<uint64_t> span_a(C), span_b(C);
     std::vector<sfa_result_t> cand(r.candidates > 0 ? 4 * static_cast<size_t>(C) : 0);
     std::string text(4096, '\0');
@@ -215,13 +271,20 @@ int realtime_run(int argc, char **argv, double t0) {
         if (sfa_session_extend_raw(se, slot.data(), dst, raw_off.data(), scaling.data(), end.data(), n, rows.data(), info.data()) != SFA_OK)
             die(std::string("tick ") + std::to_string(sch.tick()) + ": " + sfa_last_error());
         decided_slot.clear();
+        if (targets && n > 0 && sfa_session_classes(se, slot.data(), n, cls.data()) != SFA_OK) die(std::string("classes: ") + sfa_last_error());
         for (int32_t i = 0; i < n; ++i) {
             replay::Status s;
             s.calibrated = info[i].status & 1, s.full = info[i].status & 2, s.ended = info[i].status & 4, s.poisoned = info[i].status & 8;
             s.mapped = rows[i].valid && rows[i].rid >= 0;
             s.q_events = info[i].q_events;
             s.mapq = rows[i].mapq;
-            reason[i] = replay::decide(rule, s);
+            if (targets) {
+                const char dec = static_cast<char>(sfa_target_decide(&cls[i], r.target_mode, r.min_events, r.margin));
+                reason[i] = replay::decide_targets(s, dec);
+                action[i] = reason[i] ? replay::action_of(reason[i], dec) : 0;
+            } else {
+                reason[i] = replay::decide(rule, s);
+            }
             line[i] = reason[i] && s.mapped;
             if (reason[i]) decided_slot.push_back(slot[i]);
         }
@@ -248,8 +311,8 @@ int realtime_run(int argc, char **argv, double t0) {
                     int len = sfa_paf_row_ex(&text[0], text.size(), &w, rec.read_id.c_str(), ref.contigs[w.rid].name.c_str(), span_a[k], span_b[k],
                                              static_cast<uint64_t>(info[i].q_events - 1), rec.raw.size(), static_cast<uint64_t>(ref.seq_len[w.rid]), m == 0 ? 'P' : 'S');
                     if (len > 0) {
-                        const int more = snprintf(&text[len - 1], text.size() - static_cast<size_t>(len - 1), "\tne:i:%ld\tns:i:%ld\tdc:A:%c\n", (long)info[i].q_events,
-                                                  (long)info[i].n_samples, reason[i]);
+                        const int more = snprintf(&text[len - 1], text.size() - static_cast<size_t>(len - 1), "\tne:i:%ld\tns:i:%ld\tdc:A:%c%s\n", (long)info[i].q_events,
+                                                  (long)info[i].n_samples, reason[i], targets ? target_tags(cls[i], r).c_str() : "");
                         len = (more < 0 || static_cast<size_t>(len - 1 + more) >= text.size()) ? -1 : len - 1 + more;
                     }
                     if (len < 0) die("PAF line too long");
@@ -260,9 +323,23 @@ int realtime_run(int argc, char **argv, double t0) {
             fflush(stdout);  // a line is out at the moment of its decision
             if (sfa_session_reset(se, decided_slot.data(), nd) != SFA_OK) die(std::string("reset: ") + sfa_last_error());
         }
-        sch.end_tick(reason, line, ch);
+        if (targets) {
+            std::vector<int64_t> sent_now(n);
+            for (int32_t i = 0; i < n; ++i) sent_now[i] = sch.sent(slot[i]);
+            sch.end_tick(reason, line, ch, &action, &held);
+            for (int32_t i = 0; i < n; ++i) {
+                if (!reason[i]) continue;
+                const int a = action[i] == 'A' ? 0 : action[i] == 'U' ? 1 : 2;
+                ++rep.act_reads[a];
+                rep.act_samples[a] += sent_now[i] + held[i];
+            }
+        } else {
+            sch.end_tick(reason, line, ch);
+        }
         rep.tick_s.push_back(realtime() - a);
     }
+    if (trace) fclose(trace);
+    if (targets) rep.print_targets();
     if (o.verbosity >= 3) rep.print(r, ch, ch.sampling_rate > 0 ? static_cast<double>(r.chunk_samples) / ch.sampling_rate : 0.0);
     return 0;
 }

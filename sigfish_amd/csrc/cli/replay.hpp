@@ -11,6 +11,11 @@
 //   decision  after the call every named channel is tested (decide()): early, full, end of read
 //   after it  decided channels are reset in one call and each takes the next unread record of the file, lowest channel
 //             first, from tick t + 1 on; what is left of a decided read is never sent
+//   targets   only with --targets (Schedule's `targets`, end_tick's `action`): a read that is accepted ('A') or proceeds ('P': full
+//             or ended without a class decision) keeps its channel for ceil((len - sent) / chunk_samples) further ticks without
+//             sending anything -- the pore goes on reading it -- one trace line `hold ... left=K` per such tick, K counting down to
+//             1; the channel takes its next read at the end of the last one.  An unblocked read ('U') frees its channel at once.
+//             Channels freed in a tick, by a decision or by a hold that ends, take the next records lowest channel first
 //   the end   no channel is busy
 #pragma once
 #include <cstdint>
@@ -42,6 +47,17 @@ inline char decide(const Rule &r, const Status &s) {
     return 0;
 }
 
+// ---- with targets (target_rules.hpp decides; nothing of it is restated here) ----
+// The 'E' test of decide() replaced: `decision` is target_decide() of the slot's class result ('A', 'U' or 0).  'F' and 'R' as above.
+inline char decide_targets(const Status &s, char decision) {
+    if (s.calibrated && decision) return 'E';
+    if (s.full) return 'F';
+    if (s.ended || s.poisoned) return 'R';
+    return 0;
+}
+// what happens to a decided read: the class decision when it was early, else it proceeds
+inline char action_of(char reason, char decision) { return reason == 'E' ? decision : 'P'; }
+
 // one channel's part of a tick's call
 struct Entry {
     int32_t channel;
@@ -54,7 +70,7 @@ struct Entry {
 // (false: the file has no more).  The schedule numbers the records in the order it takes them.
 class Schedule {
   public:
-    Schedule(int32_t channels, int64_t chunk_samples, FILE *trace = nullptr) : chunk_(chunk_samples), trace_(trace), ch_(channels) {}
+    Schedule(int32_t channels, int64_t chunk_samples, FILE *trace = nullptr, bool targets = false) : chunk_(chunk_samples), trace_(trace), targets_(targets), ch_(channels) {}
 
     template <class Source>
     void start(Source &src) {
@@ -73,6 +89,10 @@ class Schedule {
         for (int32_t c = 0; c < static_cast<int32_t>(ch_.size()); ++c) {
             Channel &k = ch_[c];
             if (k.read < 0) continue;
+            if (k.hold > 0) {  // (only with targets)
+                if (trace_) fprintf(trace_, "tick %ld hold ch=%d read=%ld left=%ld\n", (long)tick_, c, (long)k.read, (long)k.hold);
+                continue;
+            }
             const int64_t left = k.len - k.sent, n = left < chunk_ ? left : chunk_;
             entries_.push_back(Entry{c, k.read, k.sent, n, n < chunk_});
             k.sent += n;
@@ -82,37 +102,70 @@ class Schedule {
         return entries_;
     }
 
-    // reason[i] (decide()) and line[i] for entry i of begin_tick(); decided channels take the next records, lowest channel first
+    // reason[i] (decide()) and line[i] for entry i of begin_tick(); decided channels take the next records, lowest channel first.
+    // With targets, action[i] (action_of) says what happens to a decided read; *held (if given) receives the samples a read
+    // decided in this tick is held for.
     template <class Source>
-    void end_tick(const std::vector<char> &reason, const std::vector<char> &line, Source &src) {
+    void end_tick(const std::vector<char> &reason, const std::vector<char> &line, Source &src, const std::vector<char> *action = nullptr, std::vector<int64_t> *held = nullptr) {
+        if (!targets_ || !action) {
+            for (size_t i = 0; i < entries_.size(); ++i) {
+                if (!reason[i]) continue;
+                const Entry &e = entries_[i];
+                if (trace_)
+                    fprintf(trace_, "tick %ld decide ch=%d read=%ld reason=%c line=%d sent=%ld\n", (long)tick_, e.channel, (long)e.read, reason[i], line[i] ? 1 : 0, (long)ch_[e.channel].sent);
+                ch_[e.channel].read = -1;
+                --n_busy_;
+            }
+            for (size_t i = 0; i < entries_.size(); ++i)
+                if (reason[i] && !take(entries_[i].channel, src)) break;
+            ++tick_;
+            return;
+        }
+        if (held) held->assign(entries_.size(), 0);
+        std::vector<char> freed(ch_.size(), 0);
+        for (int32_t c = 0; c < static_cast<int32_t>(ch_.size()); ++c)  // holds of earlier ticks: one tick less, the last one frees
+            if (ch_[c].read >= 0 && ch_[c].hold > 0 && --ch_[c].hold == 0) freed[c] = 1;
         for (size_t i = 0; i < entries_.size(); ++i) {
             if (!reason[i]) continue;
             const Entry &e = entries_[i];
+            Channel &k = ch_[e.channel];
             if (trace_)
-                fprintf(trace_, "tick %ld decide ch=%d read=%ld reason=%c line=%d sent=%ld\n", (long)tick_, e.channel, (long)e.read, reason[i], line[i] ? 1 : 0, (long)ch_[e.channel].sent);
-            ch_[e.channel].read = -1;
-            --n_busy_;
+                fprintf(trace_, "tick %ld decide ch=%d read=%ld reason=%c line=%d sent=%ld\n", (long)tick_, e.channel, (long)e.read, reason[i], line[i] ? 1 : 0, (long)k.sent);
+            const int64_t ticks = (*action)[i] == 'U' ? 0 : (k.len - k.sent + chunk_ - 1) / chunk_;
+            if (ticks > 0) {
+                k.hold = ticks;
+                if (held) (*held)[i] = k.len - k.sent;
+            } else {
+                freed[e.channel] = 1;
+            }
         }
-        for (size_t i = 0; i < entries_.size(); ++i)
-            if (reason[i] && !take(entries_[i].channel, src)) break;
+        bool more = true;
+        for (int32_t c = 0; c < static_cast<int32_t>(ch_.size()); ++c) {
+            if (!freed[c]) continue;
+            ch_[c] = Channel{};
+            --n_busy_;
+            if (more) more = take(c, src);
+        }
         ++tick_;
     }
 
   private:
     struct Channel {
         int64_t read = -1, len = 0, sent = 0;
+        int64_t hold = 0;  // ticks the channel still keeps a decided read without sending (targets)
     };
     template <class Source>
     bool take(int32_t c, Source &src) {
         int64_t len = 0;
         if (!src.take(c, &len)) return false;
-        ch_[c] = Channel{next_read_++, len, 0};
+        ch_[c] = Channel{next_read_++, len, 0, 0};
         ++n_busy_;
         if (trace_) fprintf(trace_, "tick %ld take ch=%d read=%ld len=%ld\n", (long)tick_, c, (long)ch_[c].read, (long)len);
         return true;
     }
     const int64_t chunk_;
     FILE *trace_;
+    const bool targets_;
     std::vector<Channel> ch_;
     std::vector<Entry> entries_;
     int64_t tick_ = 0, next_read_ = 0;

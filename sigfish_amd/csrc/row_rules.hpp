@@ -160,9 +160,12 @@ struct RefTables {
 };
 
 // Positions of a row from the columns its alignment starts and ends in: strand flip and offset (src/sigfish.c:971-975)
+// One column of a strand's array as the coordinate a row reports for it: '-' counts from the contig's other end.  The column an
+// alignment ENDS in becomes pos_end on '+' and pos_st on '-' (target_rules.hpp classes a column by this coordinate).
+SFA_ROW_HD int place_col(const int strand, const int col, const int rl, const int off) { return ((strand == '+') ? col : rl - col) + off; }
 SFA_ROW_HD void place_row(ResultRow &r, const int st, const int end, const int rl, const int off) {
-    r.pos_st = ((r.strand == '+') ? st : rl - end) + off;
-    r.pos_end = ((r.strand == '+') ? end : rl - st) + off;
+    r.pos_st = place_col(r.strand, (r.strand == '+') ? st : end, rl, off);
+    r.pos_end = place_col(r.strand, (r.strand == '+') ? end : st, rl, off);
 }
 SFA_ROW_HD void place_row(ResultRow &r, const int st, const int end, const RefTables &t) { place_row(r, st, end, t.ref_len[r.rid], t.ref_st_offset[r.rid]); }
 // SFA_SESSION_NO_START: no start column was carried, so the coordinate that needs it is -1

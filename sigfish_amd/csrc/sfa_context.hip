@@ -310,6 +310,7 @@ int sfa_get_profile(sfa_ctx_t *c, sfa_profile_t *p) {
             sum.finalize_ms = std::max(sum.finalize_ms, q.finalize_ms);
             sum.total_ms = std::max(sum.total_ms, q.total_ms);
             sum.events_ms = std::max(sum.events_ms, q.events_ms);
+            sum.class_ms = std::max(sum.class_ms, q.class_ms);
             sum.decode_ms = std::max(sum.decode_ms, q.decode_ms);
             sum.blow5_fallbacks += q.blow5_fallbacks;
             sum.normalise_ms = std::max(sum.normalise_ms, q.normalise_ms);

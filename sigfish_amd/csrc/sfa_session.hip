@@ -9,6 +9,7 @@
 //   sess::AutoStart   sfa_session_raw_auto_start (events_auto_stream.hpp): retained samples, the slots' targets and skips
 //   sess::Keep        sfa_session_keep_events: the events of an event-mode session's slots, kept for their maps
 //   sess::Maps        sfa_session_event_maps: the scratch of a call (the core is sfa_maps.hip's), where every slot's query begins
+//   sess::Targets     sfa_session_targets: the column mask, and of a sfa_session_classes call the slot list, partial minima, results
 //   sess::Spread      SFA_SESSION_SPREAD on a group context: one sub-session per shard, a call's entries dealt to them
 // The host rules -- which waves a call becomes, which points of the automatic start it passes -- are session_plan.hpp's; where a
 // spread session's slots live and how a call is dealt to the shards, session_spread.hpp's.
@@ -18,6 +19,7 @@
 #include "events_stream.hpp"
 #include "events_auto_stream.hpp"
 #include "session_spread.hpp"
+#include "sdtw_session_class.hpp"
 
 namespace sfa {
 // defined in sfa_align.hip, the unit that holds the plain kernels of sdtw_kernels.hpp
@@ -171,6 +173,23 @@ struct Maps {  // sfa_session_event_maps
     }
 };
 
+struct Targets {  // sfa_session_targets, sfa_session_classes
+    bool on = false;
+    int64_t on_cols = 0;                  // on-target columns of a slot's row
+    int32_t first_on = -1, first_off = -1;  // lowest column of either class (-1: the class is empty)
+    std::vector<uint32_t> h_mask;         // of the last sfa_session_targets call (the upload is synchronous: pageable is fine)
+    DevBuf d_mask;                        // target_mask_words(total_cols) words
+    DevBuf d_slot, d_part, d_cls;         // of a call: [n] i32, [n][parts] ClassPartial, [n] sfa_class_t
+    PinBuf h_slot, h_cls;
+    std::vector<int32_t> live;            // ... which entries of the call were launched
+    Event ev[2];
+    static size_t mask_bytes(int64_t total_cols) { return 4 * sfa::target_mask_words(total_cols); }  // one bit per column, and a word
+    int reserve(int64_t total_cols) { return d_mask.reserve(mask_bytes(total_cols)); }
+    int reserve_call(size_t n, size_t parts) {
+        return reserve_all(d_slot, 4 * n, h_slot, 4 * n, d_part, sizeof(sfa::ClassPartial) * n * parts, d_cls, sizeof(sfa_class_t) * n, h_cls, sizeof(sfa_class_t) * n);
+    }
+};
+
 // SFA_SESSION_SPREAD on a group context: the session is one ordinary session per shard that holds slots (global slot i: local
 // slot i / G of subs[i % G]); every entry point deals its entries to them (session_spread.hpp), runs the shards side by side
 // (for_each_shard) and puts the answers back in the caller's order.  What a call packs or collects per shard lies here and is
@@ -188,6 +207,7 @@ struct Spread {
         std::vector<sfa_session_auto_t> autos;
         std::vector<int64_t> len;
         std::vector<uint64_t> span;
+        std::vector<sfa_class_t> cls;
         int32_t on_host = 0;
     };
     std::vector<Shard> shard;  // [G]
@@ -212,6 +232,7 @@ struct sfa_session {
     sess::AutoStart autos;
     sess::Keep keep;
     sess::Maps maps;
+    sess::Targets targets;
     std::unique_ptr<sess::Spread> spread;  // SFA_SESSION_SPREAD on a group context: `c` is the group, everything above is unused
     int32_t name_first = 0, name_step = 1;  // a sub-session of a spread session: local slot l is the caller's slot l * step + first (messages)
 };
@@ -971,6 +992,23 @@ int spread_auto_start(sfa_session *s, const int32_t *slot, int32_t n, sfa_sessio
     });
 }
 
+int spread_classes(sfa_session *s, const int32_t *slot, int32_t n, sfa_class_t *out) {
+    static const char *const who = "sfa_session_classes";
+    if (int rc = spread_live(s, who)) return rc;
+    // (sub-session 0 exists: spread_create refuses n_slots <= 0, and shard 0 holds slot 0; every sub-session holds the same mask)
+    if (!s->spread->subs[0]->targets.on) return fail(SFA_EINVAL, "%s: the session has no targets (sfa_session_targets)", who);
+    if (int rc = spread_deal(s, slot, n, true, who)) return rc;
+    return sfa::for_each_shard(s->c, [&](size_t r) {
+        const sfa::SpreadShardPart &p = s->spread->part.shard[r];
+        sess::Spread::Shard &b = s->spread->shard[r];
+        if (p.n() == 0) return spread_idle(s->c->shards[r]);  // (the group's profile is this call's on every shard)
+        b.cls.resize(p.local.size());
+        if (int rc = sfa_session_classes(s->spread->subs[r], p.local.data(), p.n(), b.cls.data())) return rc;
+        sfa::spread_scatter(p, b.cls.data(), out);
+        return static_cast<int>(SFA_OK);
+    });
+}
+
 // the sub-session that owns *slot, which becomes its local number there (the one-slot calls: sfa_session_row, sfa_session_events)
 int spread_owner(sfa_session *s, int32_t *slot, const char *who, sfa_session **sub) {
     if (int rc = spread_live(s, who)) return rc;
@@ -1181,6 +1219,145 @@ int sfa_session_extend(sfa_session_t *s, const int32_t *slot, const float *event
     if (s->spread) return spread_extend(s, slot, events, ev_off, n, out);
     if (int rc = extend_check(s, slot, events, ev_off, n)) return rc;
     return n == 0 ? static_cast<int>(SFA_OK) : extend_run(s, slot, events, ev_off, n, out);
+}
+
+// ---- target classes (target_rules.hpp, sdtw_session_class.hpp) ----
+
+int sfa_session_targets(sfa_session_t *s, const sfa_target_t *targets, int32_t n) {
+    static const char *const who = "sfa_session_targets";
+    if (!s || n < 0 || (n > 0 && !targets)) return fail(SFA_EINVAL, "%s: bad argument", who);
+    if (s->resweep)
+        return fail(SFA_EINVAL, "%s: the session was created with SFA_SESSION_RESWEEP: its carried row belongs to the reversed query, and what its minimum means has "
+                                "not been looked into",
+                    who);
+    if (s->spread) {  // every sub-session holds the mask (no slot needs to be empty: spread_config's check does not apply)
+        if (int rc = spread_live(s, who)) return rc;
+        sess::Spread &sp = *s->spread;
+        std::vector<int> rcs(sp.subs.size(), 0);
+        const int rc = sfa::for_each_shard(s->c, [&](size_t r) { return sp.subs[r] ? (rcs[r] = sfa_session_targets(sp.subs[r], targets, n)) : static_cast<int>(SFA_OK); });
+        size_t have = 0, failed = 0;
+        for (size_t r = 0; r < sp.subs.size(); ++r) have += sp.subs[r] != nullptr, failed += rcs[r] != SFA_OK;
+        if (failed != 0 && failed != have) sp.broken = true;
+        return rc;
+    }
+    sfa_ctx *c = s->c;
+    sess::Targets &t = s->targets;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (a mask in use is not replaced under a kernel)
+    if (n == 0) {
+        t.on = false;
+        t.on_cols = 0;
+        t.first_on = t.first_off = -1;
+        std::vector<uint32_t>().swap(t.h_mask);
+        t.d_mask = DevBuf{};  // (freed; the buffers of a call stay for the next mask)
+        return SFA_OK;
+    }
+    if (c->model.total_cols >= INT32_MAX) return fail(SFA_ERANGE, "%s: the reference has %lld columns; the classes count them in 31 bits", who, (long long)c->model.total_cols);
+    // the model's tables on the host: jobs are contig-major, '+' before '-' (sfa_context.hip)
+    const int32_t nj = c->model.n_jobs, strands = nj / c->model.num_ref;
+    std::vector<int32_t> job_contig(nj), ref_len(c->model.num_ref);
+    std::vector<int8_t> job_strand(nj);
+    for (int32_t j = 0; j < nj; ++j) job_contig[j] = j / strands, job_strand[j] = (j % strands) ? '-' : '+';
+    for (int32_t r = 0; r < c->model.num_ref; ++r) ref_len[r] = c->model.h_job_len[static_cast<size_t>(r) * strands];
+    const sfa::TargetModel m{c->model.num_ref, nj, job_contig.data(), job_strand.data(), c->model.h_job_len.data(), s->rows.h_col_off.data(), ref_len.data(),
+                             c->model.h_ref_off.data(), c->model.total_cols};
+    char msg[192];
+    if (sfa::target_list_error(targets, n, m, msg, sizeof msg)) return fail(SFA_EINVAL, "%s: %s", who, msg);
+    std::vector<uint32_t> mask;
+    const int64_t on_cols = sfa::target_mask(targets, n, m, &mask);
+    if (int rc = t.reserve(c->model.total_cols)) return rc;
+    if (int rc = sess::create_events(t.ev, 2)) return rc;
+    t.h_mask.swap(mask);
+    HIP_TRY(hipMemcpyAsync(t.d_mask.p, t.h_mask.data(), 4 * t.h_mask.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    t.on_cols = on_cols;
+    t.first_on = sfa::target_first_of_class(t.h_mask, c->model.total_cols, true);
+    t.first_off = sfa::target_first_of_class(t.h_mask, c->model.total_cols, false);
+    t.on = true;
+    return SFA_OK;
+}
+
+int64_t sfa_session_target_columns(sfa_session_t *s) {
+    if (!s) return fail(SFA_EINVAL, "sfa_session_target_columns: null session");
+    if (s->spread) return sfa_session_target_columns(s->spread->subs[0]);  // (sub-session 0 always exists, as in spread_classes)
+    return s->targets.on ? s->targets.on_cols : 0;
+}
+
+int sfa_session_classes(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_class_t *out) {
+    static const char *const who = "sfa_session_classes";
+    if (!s || n < 0 || (n > 0 && (!slot || !out))) return fail(SFA_EINVAL, "%s: bad argument", who);
+    if (s->spread) return spread_classes(s, slot, n, out);
+    sess::Targets &t = s->targets;
+    if (!t.on) return fail(SFA_EINVAL, "%s: the session has no targets (sfa_session_targets)", who);
+    if (int rc = check_slots(s, slot, n, who)) return rc;
+    begin_call(s);  // (the stamps say which slots this call has named)
+    for (int32_t i = 0; i < n; ++i)
+        if (int rc = claim_slot(s, slot[i], who)) return rc;
+    if (n == 0) return SFA_OK;
+    sfa_ctx *c = s->c;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = sfa::resolve_profile(c)) return rc;
+    sfa_class_t none{};
+    none.on_score = none.off_score = INFINITY;
+    none.on_rid = none.on_pos_end = none.off_rid = none.off_pos_end = -1;
+    t.live.clear();
+    for (int32_t i = 0; i < n; ++i)  // empty and poisoned slots are not launched
+        if (!s->rows.poison[slot[i]] && s->rows.len[slot[i]] > 0) t.live.push_back(i);
+    const int32_t m = static_cast<int32_t>(t.live.size()), parts = sfa::class_parts(c->model.total_cols);
+    // (every refusal in front of the first write to the caller's records)
+    if (static_cast<int64_t>(m) * parts > INT32_MAX) return fail(SFA_ERANGE, "%s: %d slots x %d parts of a row are more blocks than a launch takes", who, m, parts);
+    if (m > 0)
+        if (int rc = t.reserve_call(static_cast<size_t>(m), static_cast<size_t>(parts))) return rc;
+    for (int32_t i = 0; i < n; ++i) out[i] = none;
+    sfa_profile_t pr{};
+    pr.segment_reruns = c->seg.seg_reruns;
+    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
+    if (m > 0) {
+        int32_t *hs = t.h_slot.as<int32_t>();
+        for (int32_t k = 0; k < m; ++k) hs[k] = slot[t.live[k]];
+        hipStream_t st = c->stream;
+        HIP_TRY(hipMemcpyAsync(t.d_slot.p, hs, 4 * static_cast<size_t>(m), hipMemcpyHostToDevice, st));
+        sfa::SessionClassArgs a;
+        a.slot = t.d_slot.as<int32_t>();
+        a.rows = s->rows.d_row_c.as<float>() + sfa::kSessionPad;
+        a.mask = t.d_mask.as<uint32_t>();
+        a.part = t.d_part.as<sfa::ClassPartial>();
+        a.total_cols = c->model.total_cols;
+        a.n = m;
+        a.n_parts = parts;
+        sfa::SessionClassRowsArgs ra;
+        ra.part = a.part;
+        ra.col_off = s->rows.d_col_off.as<int64_t>();
+        ra.ref = c->model.tables();
+        ra.out = t.d_cls.as<sfa_class_t>();
+        ra.n = m;
+        ra.n_parts = parts;
+        ra.n_jobs = c->model.n_jobs;
+        ra.first_on = t.first_on;
+        ra.first_off = t.first_off;
+        HIP_TRY(hipEventRecord(t.ev[0], st));
+        hipLaunchKernelGGL(sfa::sdtw_session_class_kernel, dim3(static_cast<unsigned>(m) * parts), dim3(sfa::kClassThreads), 0, st, a);
+        KERNEL_TRY();
+        hipLaunchKernelGGL(sfa::sdtw_session_class_rows_kernel, dim3(m), dim3(64), 0, st, ra);
+        KERNEL_TRY();
+        HIP_TRY(hipEventRecord(t.ev[1], st));
+        HIP_TRY(hipMemcpyAsync(t.h_cls.p, t.d_cls.p, sizeof(sfa_class_t) * static_cast<size_t>(m), hipMemcpyDeviceToHost, st));
+        if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+        pr.class_ms = pr.total_ms = ms;
+        for (int32_t k = 0; k < m; ++k) {
+            out[t.live[k]] = t.h_cls.as<sfa_class_t>()[k];
+            out[t.live[k]].n_events = static_cast<int32_t>(s->rows.len[slot[t.live[k]]]);
+        }
+    }
+    c->prof = pr;
+    return SFA_OK;
+}
+
+int sfa_target_decide(const sfa_class_t *cls, int32_t mode, int32_t min_events, float margin) {
+    return cls ? sfa::target_decide(*cls, mode, min_events, margin) : 0;
 }
 
 // ---- event maps of a slot's row (the core: sfa_maps.hip) ----

@@ -25,6 +25,12 @@ ticks, the same calls, the same lines.  The schedule counts ticks, never seconds
             Session.event_maps call before the reset, on the slots' resident queries; the record is sam_row_from_map over the slot's
             events (Session.events) and is followed by the same tags (format_sam_line, format_sam).  Schedule and rule are unchanged
   spread    --spread: the session is created with SESSION_SPREAD on an Aligner over several devices; nothing else changes
+  targets   targets= (--targets FILE.bed with --enrich or --deplete and --margin X): the session gets the intervals
+            (Session.set_targets), every tick ends with ONE Session.classes call over the tick's channels, and the 'E' test of
+            decide() is replaced by api.target_decide on the channel's class record (decide_targets); 'F' and 'R' stay.  Every line
+            gains tc:A:<T|O|N> ac:A:<A|U|P> tm:f:<(other - mine) / n_events> (target_tags).  An accepted ('A') or proceeding ('P')
+            read keeps its channel for ceil((len - sent) / chunk) further ticks without sending (trace: `hold ... left=K`); an
+            unblocked one frees it at once.  Refused with resweep (the session refuses targets there).  margin has no default
   after it  decided channels are reset in one call and take the next unread reads, lowest channel first, from tick t + 1 on
 """
 import numpy as np
@@ -48,13 +54,31 @@ def decide(row, info, min_events, min_mapq):
     return None
 
 
+def decide_targets(info, decision):
+    """replay::decide_targets: `decision` is api.target_decide of the channel's class record ('A', 'U' or None)"""
+    st = int(info["status"])
+    if st & api.RAW_CALIBRATED and decision:
+        return "E"
+    if st & api.RAW_FULL:
+        return "F"
+    if st & (api.RAW_ENDED | api.RAW_POISONED):
+        return "R"
+    return None
+
+
+def action_of(reason, decision):
+    """what happens to a decided read: the class decision when it was early, else it proceeds ('P')"""
+    return decision if reason == "E" else "P"
+
+
 class Schedule:
     """replay::Schedule: which read is on which channel and which samples go out at which tick.  `source.take(channel)` puts the
     next unread record of the file on the channel and returns its length (None: the file has no more); `trace`, a list, receives
     the lines the C++ schedule prints."""
 
-    def __init__(self, channels, chunk_samples, trace=None, resweep=False):
+    def __init__(self, channels, chunk_samples, trace=None, resweep=False, targets=False):
         self.chunk, self.trace = int(chunk_samples), trace
+        self.targets, self.hold = bool(targets), [0] * channels  # hold: ticks a channel still keeps a decided read without sending
         self.resweep = bool(resweep)  # of the session; nothing here reads it: the schedule does not depend on it
         self.read, self.len, self.sent = [-1] * channels, [0] * channels, [0] * channels
         self.tick, self.next_read, self.entries = 0, 0, []
@@ -83,6 +107,10 @@ class Schedule:
         for c, r in enumerate(self.read):
             if r < 0:
                 continue
+            if self.hold[c] > 0:  # (only with targets)
+                if self.trace is not None:
+                    self.trace.append(f"tick {self.tick} hold ch={c} read={r} left={self.hold[c]}")
+                continue
             n = min(self.chunk, self.len[c] - self.sent[c])
             self.entries.append((c, r, self.sent[c], n, n < self.chunk))
             self.sent[c] += n
@@ -90,7 +118,10 @@ class Schedule:
                 self.trace.append(f"tick {self.tick} send ch={c} read={r} first={self.entries[-1][2]} n={n} end={int(n < self.chunk)}")
         return self.entries
 
-    def end_tick(self, reason, line, source):
+    def end_tick(self, reason, line, source, action=None):
+        """action (with targets): action_of per entry; -> samples every entry's read is held for (0 without targets)"""
+        if self.targets and action is not None:
+            return self._end_tick_targets(reason, line, source, action)
         for (c, r, _, _, _), why, ln in zip(self.entries, reason, line):
             if not why:
                 continue
@@ -101,6 +132,33 @@ class Schedule:
             if why and not self._take(c, source):
                 break
         self.tick += 1
+        return [0] * len(self.entries)
+
+    def _end_tick_targets(self, reason, line, source, action):
+        held = [0] * len(self.entries)
+        freed = [False] * len(self.read)
+        for c in range(len(self.read)):  # holds of earlier ticks: one tick less, the last one frees
+            if self.read[c] >= 0 and self.hold[c] > 0:
+                self.hold[c] -= 1
+                freed[c] = self.hold[c] == 0
+        for i, ((c, r, _, _, _), why, ln) in enumerate(zip(self.entries, reason, line)):
+            if not why:
+                continue
+            if self.trace is not None:
+                self.trace.append(f"tick {self.tick} decide ch={c} read={r} reason={why} line={int(bool(ln))} sent={self.sent[c]}")
+            ticks = 0 if action[i] == "U" else -(-(self.len[c] - self.sent[c]) // self.chunk)
+            if ticks > 0:
+                self.hold[c], held[i] = ticks, self.len[c] - self.sent[c]
+            else:
+                freed[c] = True
+        more = True
+        for c in range(len(self.read)):
+            if freed[c]:
+                self.read[c], self.hold[c] = -1, 0
+                if more:
+                    more = self._take(c, source)
+        self.tick += 1
+        return held
 
 
 def recal_points(norm, query, recalibrate=(), at_end=False):
@@ -117,7 +175,7 @@ AUTO_START_MAX_SAMPLES, MAX_SKIP_EVENTS = 131072, 4096  # the defaults of --auto
 
 
 def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False, resweep=False,
-           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False):
+           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None):
     """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
     candidates=1..4 (--candidates): an eighth element, RESULT_DTYPE[4], the channel's candidates at the decision, best first.
     A `session` of the caller's is taken as it is, in this as in its raw mode: it must keep that many candidates already
@@ -142,6 +200,15 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     spread=True (--spread): the session of replay's own is aligner.session(channels, spread=True) -- on an Aligner made with
     devices= the channels are dealt over its devices; the items are the same."""
     auto = skip < 0
+    if targets is None and (mode is not None or margin is not None):
+        raise api.SfaError("replay: mode and margin belong to targets=")
+    if targets is not None:  # (all of it before any session exists)
+        if mode not in (api.ENRICH, api.DEPLETE):
+            raise api.SfaError("replay: targets= needs mode=ENRICH or mode=DEPLETE")
+        if margin is None:
+            raise api.SfaError("replay: targets= needs margin=: nobody has measured a good value, there is no default")
+        if resweep:
+            raise api.SfaError("replay: targets= is not available with resweep=True: a resweep session's carried row belongs to the reversed query")
     if sam and session is not None and not getattr(session, "starts", True):
         raise api.SfaError("replay: sam=True needs the rows' start columns; the session was created with starts=False (SESSION_NO_START)")
     if auto and not resweep:
@@ -162,7 +229,7 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
             return len(raw)
 
     src = Source()
-    sch = Schedule(channels, chunk_samples, trace, resweep)
+    sch = Schedule(channels, chunk_samples, trace, resweep, targets is not None)
     own = session is None
     se = aligner.session(channels, resweep=resweep, spread=spread) if own else session
     try:
@@ -172,6 +239,8 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
             se.configure_raw(max_skip_events if auto else skip, norm, query, recal_points(norm, query, recalibrate, at_end), at_end)
             if auto:
                 se.configure_auto_start(chunk_samples if auto_start_every is None else auto_start_every, auto_start_max_samples)
+        if targets is not None:
+            se.set_targets(targets)
         if candidates and not own:
             se.candidates([])  # (raises unless the caller's session keeps candidates)
         sch.start(src)
@@ -181,8 +250,16 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
             chunks = [on[c][3][first:first + n] for c, _, first, n, _ in es]
             raw_off = np.concatenate([[0], np.cumsum([len(x) for x in chunks])]).astype(np.int64)
             scaling = [(on[c][2]["digitisation"], on[c][2]["offset"], on[c][2]["range"]) for c in slots]
+            sch_sent = [first + n for _, _, first, n, _ in es]  # samples of every entry's read sent so far
             rows, info = se.extend_raw(slots, np.concatenate(chunks) if chunks else np.zeros(0, np.int16), raw_off, scaling, [e[4] for e in es])
-            reason = [decide(rows[i], info[i], min_events, min_mapq) for i in range(len(es))]
+            cls = action = None
+            if targets is not None:  # one call for the tick, before any reset
+                cls = se.classes(slots)
+                dec = [api.target_decide(cls[i], mode, min_events, margin) for i in range(len(es))]
+                reason = [decide_targets(info[i], dec[i]) for i in range(len(es))]
+                action = [action_of(why, dec[i]) if why else None for i, why in enumerate(reason)]
+            else:
+                reason = [decide(rows[i], info[i], min_events, min_mapq) for i in range(len(es))]
             line = [bool(why) and mapped(rows[i]) for i, why in enumerate(reason)]
             decided = [i for i, why in enumerate(reason) if why]
             if decided:
@@ -204,6 +281,8 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                     item = (sch.tick, slots[i], on[slots[i]][0], rows[i].copy(), info[i].copy(), (int(a[k]), int(b[k])), reason[i])
                     if candidates:
                         item += (cand[k].copy(),)
+                    if targets is not None:
+                        item += (cls[i].copy(), action[i])
                     if auto:
                         item += (au[k].copy(),)
                     if sam:
@@ -212,7 +291,13 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                                       cand_maps=maps[per * k + 1:per * k + 5] if candidates else None),)
                     yield item
                 se.reset(d_slots)
-            sch.end_tick(reason, line, src)
+            held = sch.end_tick(reason, line, src, action)
+            if summary is not None and targets is not None:
+                for i, why in enumerate(reason):
+                    if why:
+                        n = summary.setdefault(action[i], [0, 0])
+                        n[0] += 1
+                        n[1] += sch_sent[i] + held[i]
     finally:
         if own:
             se.close()
@@ -223,6 +308,26 @@ def _map_or_none(m):
     return m.copy() if len(m) and m[0, 0] != np.iinfo(np.int32).min else None
 
 
+def target_tags(cls, mode, min_events, margin):
+    """tc:A:<T|O|N> ac:A:<A|U|P> tm:f:<(other - mine) / n_events> for a CLASS_DTYPE record at a decision: the target class (N: no
+    class decision), the action (P: the read proceeds) and the per-event margin it had -- mine is the on-target score under
+    ENRICH and the off-target score under DEPLETE; nan when it is undefined (both classes empty, no events)."""
+    dec = api.target_decide(cls, mode, min_events, margin)
+    tc = "N" if dec is None else ("T" if (dec == "A") == (mode == api.ENRICH) else "O")
+    on, off, n = float(cls["on_score"]), float(cls["off_score"]), int(cls["n_events"])
+    mine, other = (on, off) if mode == api.ENRICH else (off, on)
+    with np.errstate(all="ignore"):
+        tm = float(np.float64(other) - np.float64(mine)) / n if n > 0 else float("nan")
+    return f"\ttc:A:{tc}\tac:A:{dec or 'P'}\ttm:f:{'nan' if tm != tm else '%.4f' % tm}"
+
+
+def format_summary(summary):
+    """the line `sigfish-amd realtime --targets` ends its stderr with, from the dict replay(summary=) filled"""
+    get = lambda a: summary.get(a, [0, 0])
+    return ("[realtime] targets: accepted (A) %d reads, %d samples\tunblocked (U) %d reads, %d samples\tproceeded (P) %d reads, %d samples (sent + held)\n"
+            % (*get("A"), *get("U"), *get("P")))
+
+
 def auto_tags(auto):
     """qs:i:<skip> as:A:<P|E|F> for a SESSION_AUTO_DTYPE record: found at a mid-read point, found at the final point, fallback"""
     st = int(auto["status"])
@@ -230,18 +335,20 @@ def auto_tags(auto):
     return f"\tqs:i:{int(auto['skip'])}\tas:A:{how}"
 
 
-def format_line(read_id, n_samples, names, seq_lengths, row, info, span, reason, auto=None):
+def format_line(read_id, n_samples, names, seq_lengths, row, info, span, reason, auto=None, target=None):
     """The line `sigfish-amd realtime` prints for a decision, or "" when its row is not mapped: paf_row (query_size as dtw passes
     it, last query event - first), then ne:i:<query events> ns:i:<samples sent> dc:A:<reason>.  n_samples: of the whole read.
-    auto: the decision's automatic start (replay with skip = -1): qs:i and as:A follow the three tags."""
+    auto: the decision's automatic start (replay with skip = -1): qs:i and as:A follow the three tags.
+    target: (class record, mode, min_events, margin) of a replay with targets=: target_tags() follow."""
     if not mapped(row):
         return ""
     rid = int(row["rid"])
     base = api.paf_row(row, read_id, names[rid], span[0], span[1], int(info["q_events"]) - 1, int(n_samples), int(seq_lengths[rid]))
-    return f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}{'' if auto is None else auto_tags(auto)}\n"
+    tail = ("" if auto is None else auto_tags(auto)) + ("" if target is None else target_tags(*target))
+    return f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}{tail}\n"
 
 
-def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, span, reason):
+def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, span, reason, target=None):
     """The candidate lines that follow a decision's primary line under --candidates: one per valid row of `cand`, best first, each
     the tp:A:S line of paf_row_ex with the primary's span and query_size and the primary's three tags; "" when the primary has no
     line."""
@@ -253,7 +360,7 @@ def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, s
             continue
         rid = int(r["rid"])
         base = api.paf_row(r, read_id, names[rid], span[0], span[1], int(info["q_events"]) - 1, int(n_samples), int(seq_lengths[rid]), tp="S")
-        out.append(f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}\n")
+        out.append(f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}{'' if target is None else target_tags(*target)}\n")
     return "".join(out)
 
 
