@@ -31,6 +31,18 @@ def mask_of(targets, ref_lengths, offsets, strands):
     return mask
 
 
+def mask_of_wide(targets, ref_lengths, offsets, strands):
+    """mask_of for rows of 10^5 columns: a job's coordinates as one array (test_class_shapes_cpu.py compares the two)"""
+    jobs = jobs_of(ref_lengths, strands)
+    mask = np.zeros(sum(j[2] for j in jobs), bool)
+    for r, strand, n, at in jobs:
+        x = coordinate(strand, np.arange(n, dtype=np.int64), n, int(offsets[r]))
+        for contig, begin, end in targets:
+            if contig == r:
+                mask[at:at + n] |= (begin <= x) & (x < end)
+    return mask
+
+
 def words_of(mask):
     bits = np.zeros((len(mask) + 31) // 32 * 32, np.uint8)
     bits[:len(mask)] = mask

@@ -1,8 +1,13 @@
 """Target classes of a session on the GPU (sfa_session_targets / sfa_session_classes: target_rules.hpp, sdtw_session_class.hpp).
 The yardstick is numpy over the carried rows Session.row() reads back, under the Python restatement of the mask
 (tests/targets_oracle.py): scores bit for bit, contig, coordinate and strand equal, after EVERY extend call.  Reference: contigs
-of 37, 64, 65 and 300 k-mers, so a slot's row (DNA: 932 columns, RNA: 466) begins at every alignment modulo 4 as the slot number
-runs, jobs begin inside mask words and inside 16-byte quads, and the head, body and tail paths of the kernel all run; 9 slots.
+of 37, 64, 65 and 300 k-mers, 9 slots.  Jobs begin inside mask words and inside 16-byte quads, but of the kernel's paths these
+shapes reach few (tests/test_class_shapes_cpu.py::test_what_the_existing_shapes_reach): a DNA row has 932 columns, a multiple of 4,
+so every slot begins on a 16-byte boundary and has neither head nor tail; an RNA row has 466, so slots begin 0 or 2 words behind a
+boundary, with a head of 0 or 2 columns and a tail of 2 or 0, and a quad's mask bits straddle two words at shift 30 only.  A row is
+one part, and only the first of a lane's eight quads (u == 0) has a column.  Every other alignment, heads and tails of 1 and 3
+columns, shifts 29 and 31, u >= 1, several parts, ties across lanes, waves and parts, and the classes whose every column costs +inf
+are tests/test_session_class_edges_gpu.py's.
 A twin session without targets takes the same calls: its rows must be the same bytes.
 The class coordinate is tied to what a finalized row reports (pos_end on '+', pos_st on '-'), and one replay(targets=...) run of 12
 synthetic reads on 4 channels, with enrich and with deplete, is compared with `sigfish-amd realtime --targets`: stdout, trace and
@@ -44,13 +49,15 @@ def target_sets(ref, strands):
     return sets
 
 
-def slot_row(se, sl, strands):
-    return np.concatenate([se.row(sl, r, s)[0] for r in range(4) for s in "+-"[:strands]])
+def slot_row(se, sl, strands, n_ref=4):
+    return np.concatenate([se.row(sl, r, s)[0] for r in range(n_ref) for s in "+-"[:strands]])
 
 
-def check_classes(se, slots, targets, ref, strands, what, dead=()):
-    """Session.classes of `slots` against numpy over the rows; -> the records"""
-    mask = T.mask_of(targets, ref.ref_lengths, ref.st_offset, strands)
+def check_classes(se, slots, targets, ref, strands, what, dead=(), mask=None):
+    """Session.classes of `slots` against numpy over the rows; -> the records.  mask: T.mask_of's answer for `targets`, where
+    the caller has it already (rows of 10^5 columns)"""
+    if mask is None:
+        mask = T.mask_of(targets, ref.ref_lengths, ref.st_offset, strands)
     assert se.target_columns() == int(mask.sum()), what
     got = se.classes(slots)
     lens = se.lengths(slots)
@@ -60,7 +67,7 @@ def check_classes(se, slots, targets, ref, strands, what, dead=()):
             assert g["valid"] == 0 and np.isinf(g["on_score"]) and np.isinf(g["off_score"]) and g["on_rid"] == -1 and g["off_rid"] == -1, (what, sl, g)
             continue
         assert g["valid"] == 1 and g["n_events"] == lens[i], (what, sl, g)
-        want = T.classes_of_rows(slot_row(se, sl, strands), mask, ref.ref_lengths, ref.st_offset, strands)
+        want = T.classes_of_rows(slot_row(se, sl, strands, ref.num_ref), mask, ref.ref_lengths, ref.st_offset, strands)
         for side in ("on", "off"):
             assert np.float32(g[f"{side}_score"]).view(np.uint32) == np.float32(want[f"{side}_score"]).view(np.uint32), (what, sl, side, g, want)
             for f in FIELDS:
