@@ -360,6 +360,53 @@ int sfa_session_classes(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_cl
  * unit.  Nobody has measured a good margin: there is no default. */
 int sfa_target_decide(const sfa_class_t *cls, int32_t mode, int32_t min_events, float margin);
 
+/* ---- target groups: the best score per named group of targets (WHICH target a read hits) --------------------------------------
+ * A group target is a target with a group id in [0, n_groups), 1 <= n_groups <= 1023.  Every column of a slot's row carries one
+ * label: the lowest group id among the intervals that cover it (covered as for the mask above: the coordinate of an alignment
+ * ENDING in the column), or n_groups -- the background -- when none does.  A group may have no column.  The label table is one
+ * uint16 per column, 2 * total_columns bytes per SESSION, shared by all slots, not counted by sfa_session_bytes; a call adds
+ * 8 * (n_groups + 1) bytes of keys and 16 * (n_groups + 1) + 24 bytes of results per named slot.  A session may hold a mask and
+ * a label table side by side; neither knows of the other. */
+typedef struct {
+    int32_t contig, begin, end, group;
+} sfa_group_target_t;
+
+/* The best column of one entry (a group, or the background at index n_groups) of a slot: cost, contig, END-COLUMN coordinate
+ * and strand as in sfa_class_t; ties as there.  An entry without columns: +inf, -1, -1, 0. */
+typedef struct {
+    float score;
+    int32_t rid, pos_end;
+    int8_t strand;
+    int8_t pad[3];
+} sfa_group_best_t;
+
+/* The two best entries of a slot, indices into [0, n_groups]; -1: no such entry (no entry has a column / only one has).  Equal
+ * scores: the entry holding the lower column is `best`.  valid 0: the slot is empty or poisoned (-1, -1, +inf, +inf). */
+typedef struct {
+    int32_t best, second;
+    float best_score, second_score;
+    int32_t n_events, valid;
+} sfa_group_head_t;
+
+/* Sets the session's group targets; n = 0 switches the feature off and frees the table.  Allowed at any time; refusals as for
+ * sfa_session_targets (a SFA_SESSION_RESWEEP session included), and SFA_EINVAL for n_groups outside 1 .. 1023 or a group id
+ * outside [0, n_groups).  On a spread session it goes to every sub-session. */
+int sfa_session_target_groups(sfa_session_t *s, const sfa_group_target_t *targets, int32_t n, int32_t n_groups);
+
+/* n_groups of the session, 0 without groups. */
+int32_t sfa_session_group_count(sfa_session_t *s);
+
+/* The group results of slot[0..n): bests[n][n_groups + 1] (may be NULL) and heads[n].  One labelled min-reduction over the
+ * slots' carried cost rows; event mode and raw mode, with and without SFA_SESSION_NO_START.  Blocking, on the context's stream;
+ * sfa_profile_t.class_ms is its device time.  A spread session partitions the call by shard and answers in the caller's order.
+ * SFA_EINVAL: no groups, a slot out of range or named twice. */
+int sfa_session_group_bests(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_group_best_t *bests, sfa_group_head_t *heads);
+
+/* The decision from a head (host only): the index of the best entry (a group, or n_groups for the background) when
+ * n_events >= min_events and second_score - best_score >= margin * n_events, an empty runner-up (second < 0) counting as +inf;
+ * otherwise -1 -- also for valid = 0, no best entry, a margin that is negative or not finite.  No default margin, as above. */
+int sfa_group_decide(const sfa_group_head_t *h, int32_t min_events, float margin);
+
 /* ---- event maps of a slot's row: the warp path of the real-time path -------------------------------------------------------
  * sfa_session_event_maps is sfa_event_maps for rows a SESSION returned: the reference-column -> query-event map
  * (aln_t.r2qevent_map, the ss string of a SAM record) of every row, from the device, with nothing uploaded again.  rows[k] is a

@@ -66,6 +66,19 @@ class SfaClass(C.Structure):
                 ("valid", C.c_int32)]
 
 
+class SfaGroupTarget(C.Structure):
+    _fields_ = [("contig", C.c_int32), ("begin", C.c_int32), ("end", C.c_int32), ("group", C.c_int32)]
+
+
+class SfaGroupBest(C.Structure):
+    _fields_ = [("score", C.c_float), ("rid", C.c_int32), ("pos_end", C.c_int32), ("strand", C.c_int8), ("pad", C.c_int8 * 3)]
+
+
+class SfaGroupHead(C.Structure):
+    _fields_ = [("best", C.c_int32), ("second", C.c_int32), ("best_score", C.c_float), ("second_score", C.c_float), ("n_events", C.c_int32),
+                ("valid", C.c_int32)]
+
+
 class SfaSessionAuto(C.Structure):
     _fields_ = [("target", C.c_int64), ("frozen_at", C.c_int64), ("skip", C.c_int32), ("status", C.c_int32)]
 
@@ -81,7 +94,8 @@ SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "
            "sfa_session_raw_recalibrate", "sfa_session_candidates_config", "sfa_session_candidates",
            "sfa_session_raw_auto_start", "sfa_session_auto_start", "sfa_session_auto_bytes", "sfa_auto_start_target", "sfa_session_auto_ms",
            "sfa_session_event_maps", "sfa_session_keep_events", "sfa_session_keep_bytes",
-           "sfa_session_targets", "sfa_session_target_columns", "sfa_session_classes", "sfa_target_decide"]
+           "sfa_session_targets", "sfa_session_target_columns", "sfa_session_classes", "sfa_target_decide",
+           "sfa_session_target_groups", "sfa_session_group_count", "sfa_session_group_bests", "sfa_group_decide"]
 
 _lib = None
 
@@ -216,5 +230,10 @@ def load():
     L.sfa_session_target_columns.restype = C.c_int64
     L.sfa_session_classes.argtypes = [vp, i32p, C.c_int32, vp]
     L.sfa_target_decide.argtypes = [C.POINTER(SfaClass), C.c_int32, C.c_int32, C.c_float]
+    L.sfa_session_target_groups.argtypes = [vp, C.POINTER(SfaGroupTarget), C.c_int32, C.c_int32]
+    L.sfa_session_group_count.argtypes = [vp]
+    L.sfa_session_group_count.restype = C.c_int32
+    L.sfa_session_group_bests.argtypes = [vp, i32p, C.c_int32, vp, vp]
+    L.sfa_group_decide.argtypes = [C.POINTER(SfaGroupHead), C.c_int32, C.c_float]
     _lib = L
     return L

@@ -37,6 +37,13 @@ CLASS_DTYPE = np.dtype([("on_score", "<f4"), ("off_score", "<f4"), ("on_rid", "<
                         ("on_strand", "i1"), ("off_strand", "i1"), ("pad", "i1", (2,)), ("n_events", "<i4"), ("valid", "<i4")])  # sfa_class_t
 assert TARGET_DTYPE.itemsize == C.sizeof(_lib.SfaTarget) and CLASS_DTYPE.itemsize == C.sizeof(_lib.SfaClass)
 ENRICH, DEPLETE = 0, 1  # the modes of target_decide
+GROUP_TARGET_DTYPE = np.dtype([("contig", "<i4"), ("begin", "<i4"), ("end", "<i4"), ("group", "<i4")])  # sfa_group_target_t
+GROUP_BEST_DTYPE = np.dtype([("score", "<f4"), ("rid", "<i4"), ("pos_end", "<i4"), ("strand", "i1"), ("pad", "i1", (3,))])  # sfa_group_best_t
+GROUP_HEAD_DTYPE = np.dtype([("best", "<i4"), ("second", "<i4"), ("best_score", "<f4"), ("second_score", "<f4"), ("n_events", "<i4"),
+                             ("valid", "<i4")])  # sfa_group_head_t
+assert GROUP_TARGET_DTYPE.itemsize == C.sizeof(_lib.SfaGroupTarget) and GROUP_BEST_DTYPE.itemsize == C.sizeof(_lib.SfaGroupBest) == 16
+assert GROUP_HEAD_DTYPE.itemsize == C.sizeof(_lib.SfaGroupHead)
+GROUP_MAX = 1023  # n_groups at most
 RAW_RECALIBRATED = 16  # ... and the bit of one call: the slot was recalibrated and swept again from event 0
 RECAL_AT_END = 0x1     # SFA_RECAL_AT_END
 RECAL_MAX_POINTS = 32
@@ -714,6 +721,37 @@ class Session:
         _check(self._L.sfa_session_classes(self._h, sl.ctypes.data_as(_lib.i32p), len(sl), out.ctypes.data_as(C.c_void_p)), "sfa_session_classes")
         return out
 
+    def set_target_groups(self, intervals, n_groups):
+        """The session's target groups (sfa_session_target_groups): (contig, begin, end, group) tuples or a GROUP_TARGET_DTYPE
+        array with 0 <= group < n_groups <= 1023, intervals as for set_targets.  A column belongs to the lowest group id among
+        the intervals that cover it, or to the background (index n_groups).  An empty list switches the feature off.  Allowed at
+        any time, beside a mask or without one; refused on a resweep session.  The label table takes 2 * total_columns bytes of
+        device memory, once per session."""
+        self._live()
+        t = _group_targets(intervals)
+        _check(self._L.sfa_session_target_groups(self._h, t.ctypes.data_as(C.POINTER(_lib.SfaGroupTarget)) if len(t) else None, len(t), int(n_groups)),
+               "sfa_session_target_groups")
+
+    def group_count(self):
+        """n_groups of the session (0 without groups)."""
+        self._live()
+        n = int(self._L.sfa_session_group_count(self._h))
+        if n < 0:
+            _check(n, "sfa_session_group_count")
+        return n
+
+    def group_bests(self, slots):
+        """The best column of every group and of the background in the carried rows of `slots` (sfa_session_group_bests) ->
+        (GROUP_BEST_DTYPE[len(slots), n_groups + 1], GROUP_HEAD_DTYPE[len(slots)]): an entry without columns has score +inf and
+        rid -1; a head names the two best entries (-1: none); ties as for classes.  valid = 0: the slot is empty or poisoned."""
+        self._live()
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        bests = np.zeros((len(sl), self.group_count() + 1), GROUP_BEST_DTYPE)
+        heads = np.zeros(len(sl), GROUP_HEAD_DTYPE)
+        _check(self._L.sfa_session_group_bests(self._h, sl.ctypes.data_as(_lib.i32p), len(sl), bests.ctypes.data_as(C.c_void_p), heads.ctypes.data_as(C.c_void_p)),
+               "sfa_session_group_bests")
+        return bests, heads
+
     def reset(self, slots=None):
         """Forget the events of `slots` (None: of every slot); in raw mode the detector, normalisation and scaling as well."""
         self._live()
@@ -775,6 +813,26 @@ def _targets(intervals):
     return t
 
 
+def _group_targets(intervals):
+    if isinstance(intervals, np.ndarray) and intervals.dtype == GROUP_TARGET_DTYPE:
+        return np.ascontiguousarray(intervals).reshape(-1)
+    t = np.zeros(len(intervals), GROUP_TARGET_DTYPE)
+    for k, (contig, begin, end, group) in enumerate(intervals):
+        t[k] = (int(contig), int(begin), int(end), int(group))
+    return t
+
+
+def group_decide(head, min_events, margin):
+    """The decision from one GROUP_HEAD_DTYPE record (sfa_group_decide; host arithmetic): the index of the best entry (a group,
+    or n_groups for the background) when n_events >= min_events and second_score - best_score >= margin * n_events (no
+    runner-up counts as +inf); None otherwise.  margin is a cost per z-normalised event; there is no default."""
+    rec = np.ascontiguousarray(head, GROUP_HEAD_DTYPE).reshape(-1)
+    if len(rec) != 1:
+        raise SfaError("group_decide: one head record at a time")
+    got = int(_lib.load().sfa_group_decide(C.cast(rec.ctypes.data, C.POINTER(_lib.SfaGroupHead)), int(min_events), float(margin)))
+    return got if got >= 0 else None
+
+
 def target_decide(cls, mode, min_events, margin):
     """The decision from one CLASS_DTYPE record (sfa_target_decide; host arithmetic): with n = n_events >= min_events,
     off_score - on_score >= margin * n says on target and on_score - off_score >= margin * n off target; mode ENRICH: on target
@@ -809,6 +867,36 @@ def read_targets(path, names):
             except ValueError:
                 raise SfaError(f"read_targets: {path}:{no}: begin and end must be integers") from None
     return _targets(out)
+
+
+def read_target_groups(path, names):
+    """A BED file as group targets for Session.set_target_groups -> (GROUP_TARGET_DTYPE array, group names): the dialect of
+    read_targets, with column 4 the group's name; groups are numbered by first appearance.  A line without a fourth column and
+    more than 1023 names are errors, beside those of read_targets."""
+    index = {str(n): i for i, n in enumerate(names)}
+    out, groups = [], {}
+    with open(path) as fh:
+        for no, line in enumerate(fh, 1):
+            text = line.strip()
+            if not text or text.startswith("#") or text.split()[0] in ("track", "browser"):
+                continue
+            f = text.split("\t") if "\t" in text else text.split()
+            if len(f) < 3:
+                raise SfaError(f"read_target_groups: {path}:{no}: a BED line has at least three columns")
+            if len(f) < 4 or not f[3].strip():
+                raise SfaError(f"read_target_groups: {path}:{no}: the line has no fourth column (the group's name)")
+            if f[0] not in index:
+                raise SfaError(f"read_target_groups: {path}:{no}: contig {f[0]!r} is not in the reference")
+            name = f[3].strip()
+            if name not in groups:
+                if len(groups) == GROUP_MAX:
+                    raise SfaError(f"read_target_groups: {path}:{no}: more than {GROUP_MAX} group names")
+                groups[name] = len(groups)
+            try:
+                out.append((index[f[0]], int(f[1]), int(f[2]), groups[name]))
+            except ValueError:
+                raise SfaError(f"read_target_groups: {path}:{no}: begin and end must be integers") from None
+    return _group_targets(out), list(groups)
 
 
 def session_bytes(total_columns, n_slots, starts=True, resweep=False):

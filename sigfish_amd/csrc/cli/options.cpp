@@ -20,7 +20,7 @@ enum LongOpt {
     O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
     O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
     O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE,
-    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_TRACE
+    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_BY_NAME, O_TRACE
 };
 
 const option kLongOptions[] = {
@@ -118,7 +118,7 @@ const option kRealtimeOptions[] = {
     {"secondary", required_argument, 0, O_SECONDARY}, {"ranks", required_argument, 0, O_RANKS},
     {"candidates", required_argument, 0, O_CANDIDATES}, {"spread", no_argument, 0, O_SPREAD},
     {"targets", required_argument, 0, O_TARGETS}, {"enrich", no_argument, 0, O_ENRICH}, {"deplete", no_argument, 0, O_DEPLETE},
-    {"margin", required_argument, 0, O_MARGIN}, {"trace", required_argument, 0, O_TRACE},
+    {"margin", required_argument, 0, O_MARGIN}, {"by-name", no_argument, 0, O_BY_NAME}, {"trace", required_argument, 0, O_TRACE},
     {0, 0, 0, 0}};
 
 void realtime_help(FILE *fp, const RealtimeOpt &r) {
@@ -171,6 +171,9 @@ void realtime_help(FILE *fp, const RealtimeOpt &r) {
     fprintf(fp, "   --enrich | --deplete       accept on-target reads and unblock off-target ones | the other way round\n");
     fprintf(fp, "   --margin FLOAT             cost per query event by which one class must beat the other; nobody has measured a good value:\n"
                 "                              no default\n");
+    fprintf(fp, "   --by-name                  with --targets: column 4 of the BED file names each interval's group (at most 1023 names); lines gain\n"
+                "                              tg:Z:<group of the read's best column, * for none> gm:f:<(runner-up - best) / events>, the summary\n"
+                "                              one line per group; decisions stay the class decision's [off]\n");
     fprintf(fp, "   --trace FILE               write the schedule's trace (take / send / hold / decide lines) to FILE [off]\n");
     fprintf(fp, "   --pace yes|no              sleep so that tick t does not start before t x chunk-samples / sampling_rate seconds;\n"
                 "                              changes the timing report on stderr only, never the output [no]\n\n"
@@ -226,6 +229,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
             case O_ENRICH: enrich = true; break;
             case O_DEPLETE: deplete = true; break;
             case O_MARGIN: margin = optarg; break;
+            case O_BY_NAME: r.by_name = true; break;
             case O_TRACE: r.trace = optarg; break;
             default: realtime_help(stderr, r); exit(EXIT_FAILURE);
         }
@@ -254,6 +258,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     if ((o.flag & F_RNA) && !(o.flag & F_INV) && !r.resweep) die("realtime: --rna needs --invert (or --resweep): without it the query rows are the events reversed, and a session cannot take new events as row 0");
     // adaptive sampling: everything that needs no file
     if (r.targets.empty() && (enrich || deplete || margin)) die("realtime: --enrich, --deplete and --margin belong to --targets FILE.bed");
+    if (r.targets.empty() && r.by_name) die("realtime: --by-name belongs to --targets FILE.bed");
     if (!r.targets.empty()) {
         if (enrich == deplete) die("realtime: --targets needs exactly one of --enrich and --deplete");
         if (!margin) die("realtime: --targets needs --margin: nobody has measured a good value, there is no default");

@@ -5,6 +5,8 @@
 // needs --, sweep); what runs here
 // is the staging of a tick's samples, the decision rule and the printing.  With --spread the session's channels are dealt over
 // every GPU of --device (SFA_SESSION_SPREAD); the schedule counts ticks, so the output is the same bytes.
+// With --by-name the BED file's name column also sets the session's target groups: each tick ends with one
+// sfa_session_group_bests call over the channels that print a line, and their lines gain tg / gm (replay::group_tags).
 // With --targets the early decision is the class decision (sfa_session_classes + sfa_target_decide, one call per tick), lines
 // gain the tc / ac / tm tags (target_tags) and accepted reads hold their channels (replay.hpp).
 #include <algorithm>
@@ -119,8 +121,10 @@ struct Channels {
     }
 };
 
-// --targets: the BED file as the session's targets -- three columns, `#` / track / browser lines skipped, an unknown contig is an error
-std::vector<sfa_target_t> read_targets(const std::string &path, const Reference &ref) {
+// --targets: the BED file as the session's targets -- three columns, `#` / track / browser lines skipped, an unknown contig is an error.
+// --by-name (groups, names given): column 4 names the interval's group, numbered by first appearance
+std::vector<sfa_target_t> read_targets(const std::string &path, const Reference &ref, std::vector<sfa_group_target_t> *groups = nullptr,
+                                       std::vector<std::string> *names = nullptr) {
     std::ifstream in(path);
     if (!in) die("realtime: cannot open the targets file " + path);
     std::vector<sfa_target_t> out;
@@ -137,6 +141,26 @@ std::vector<sfa_target_t> read_targets(const std::string &path, const Reference 
         if (rid < 0) die("realtime: " + path + ":" + std::to_string(no) + ": contig '" + name + "' is not in the reference");
         if (b < INT32_MIN || b > INT32_MAX || e < INT32_MIN || e > INT32_MAX) die("realtime: " + path + ":" + std::to_string(no) + ": coordinate out of range");
         out.push_back(sfa_target_t{rid, static_cast<int32_t>(b), static_cast<int32_t>(e)});
+        if (groups) {
+            std::string group;
+            if (ln.find('\t') != std::string::npos) {  // (tab-separated: the name is the fourth field, blanks and all)
+                std::istringstream g(ln);
+                for (int k = 0; k < 4; ++k)
+                    if (!std::getline(g, group, '\t')) group.clear();
+                const size_t a = group.find_first_not_of(" \r"), z = group.find_last_not_of(" \r");
+                group = a == std::string::npos ? "" : group.substr(a, z - a + 1);
+            } else if (!(f >> group)) {
+                group.clear();
+            }
+            if (group.empty()) die("realtime: " + path + ":" + std::to_string(no) + ": --by-name needs a fourth column, the group's name");
+            size_t id = 0;
+            while (id < names->size() && (*names)[id] != group) ++id;
+            if (id == names->size()) {
+                if (names->size() == 1023) die("realtime: " + path + ":" + std::to_string(no) + ": more than 1023 group names");
+                names->push_back(group);
+            }
+            groups->push_back(sfa_group_target_t{rid, static_cast<int32_t>(b), static_cast<int32_t>(e), static_cast<int32_t>(id)});
+        }
     }
     return out;
 }
@@ -160,6 +184,11 @@ struct Report {
     int64_t unmapped = 0, decided = 0, sum_ne = 0, samples_sent = 0;
     std::vector<double> tick_s;
     int64_t act_reads[3] = {0, 0, 0}, act_samples[3] = {0, 0, 0};  // --targets: A, U, P -- reads, samples sent plus held
+    std::vector<int64_t> group_accepted;  // --by-name: accepted reads per best entry, the background last
+    void print_groups(const std::vector<std::string> &names) const {
+        for (size_t g = 0; g < group_accepted.size(); ++g)
+            fprintf(stderr, "[realtime] group %s: accepted %ld reads\n", g < names.size() ? names[g].c_str() : "*", (long)group_accepted[g]);
+    }
     void print_targets() const {
         fprintf(stderr, "[realtime] targets: accepted (A) %ld reads, %ld samples\tunblocked (U) %ld reads, %ld samples\tproceeded (P) %ld reads, %ld samples (sent + held)\n",
                 (long)act_reads[0], (long)act_samples[0], (long)act_reads[1], (long)act_samples[1], (long)act_reads[2], (long)act_samples[2]);
@@ -210,10 +239,14 @@ int realtime_run(int argc, char **argv, double t0) {
             die(std::string("session: ") + sfa_last_error());
     if (r.candidates > 0 && sfa_session_candidates_config(se, r.candidates) != SFA_OK) die(std::string("session: ") + sfa_last_error());
     const bool targets = !r.targets.empty();
+    std::vector<std::string> group_names;
     if (targets) {
-        const std::vector<sfa_target_t> t = read_targets(r.targets, ref);
+        std::vector<sfa_group_target_t> gt;
+        const std::vector<sfa_target_t> t = read_targets(r.targets, ref, r.by_name ? &gt : nullptr, r.by_name ? &group_names : nullptr);
         if (t.empty()) die("realtime: the targets file " + r.targets + " holds no interval");
         if (sfa_session_targets(se, t.data(), static_cast<int32_t>(t.size())) != SFA_OK) die(std::string("targets: ") + sfa_last_error());
+        if (r.by_name && sfa_session_target_groups(se, gt.data(), static_cast<int32_t>(gt.size()), static_cast<int32_t>(group_names.size())) != SFA_OK)
+            die(std::string("target groups: ") + sfa_last_error());
     }
     FILE *trace = nullptr;
     if (!r.trace.empty() && !(trace = fopen(r.trace.c_str(), "w"))) die("realtime: cannot write the trace to " + r.trace);
@@ -229,6 +262,9 @@ int realtime_run(int argc, char **argv, double t0) {
     replay::Schedule sch(C, r.chunk_samples, trace, targets);
     const replay::Rule rule{r.min_events, r.min_mapq};
     Report rep;
+    if (r.by_name) rep.group_accepted.assign(group_names.size() + 1, 0);
+    std::vector<int32_t> lined_slot, head_of(r.by_name ? C : 0);
+    std::vector<sfa_group_head_t> heads(r.by_name ? C : 0);
 
     double t_pin = 0;
     PinnedBuffer raw("sample");
@@ -293,6 +329,15 @@ int realtime_run(int argc, char **argv, double t0) {
             if (sfa_session_query_span(se, decided_slot.data(), nd, span_a.data(), span_b.data()) != SFA_OK) die(std::string("query span: ") + sfa_last_error());
             // the candidates of every channel decided in this tick, in one call and before the reset
             if (r.candidates > 0 && sfa_session_candidates(se, decided_slot.data(), nd, cand.data()) != SFA_OK) die(std::string("candidates: ") + sfa_last_error());
+            if (r.by_name) {  // one call over the channels that print a line in this tick, before the reset
+                lined_slot.clear();
+                for (int32_t i = 0; i < n; ++i) {
+                    head_of[i] = reason[i] && line[i] ? static_cast<int32_t>(lined_slot.size()) : -1;
+                    if (head_of[i] >= 0) lined_slot.push_back(slot[i]);
+                }
+                if (!lined_slot.empty() && sfa_session_group_bests(se, lined_slot.data(), static_cast<int32_t>(lined_slot.size()), nullptr, heads.data()) != SFA_OK)
+                    die(std::string("group bests: ") + sfa_last_error());
+            }
             for (int32_t i = 0, d = 0; i < n; ++i) {  // ascending channels
                 if (!reason[i]) continue;
                 const int32_t k = d++;
@@ -303,6 +348,12 @@ int realtime_run(int argc, char **argv, double t0) {
                     continue;
                 }
                 const sfa::Blow5Record &rec = ch.rec[slot[i]];
+                std::string tail = targets ? target_tags(cls[i], r) : std::string();
+                if (r.by_name) {
+                    const sfa_group_head_t &h = heads[head_of[i]];
+                    tail += replay::group_tags(h.best, h.second, h.best_score, h.second_score, h.n_events, group_names);
+                    if (action[i] == 'A' && h.best >= 0) ++rep.group_accepted[h.best];
+                }
                 // the primary, then the channel's valid candidates, best first: same span, same tags
                 for (int32_t m = 0; m <= r.candidates; ++m) {
                     const sfa_result_t &w = m == 0 ? rows[i] : cand[4 * static_cast<size_t>(k) + (m - 1)];
@@ -312,7 +363,7 @@ int realtime_run(int argc, char **argv, double t0) {
                                              static_cast<uint64_t>(info[i].q_events - 1), rec.raw.size(), static_cast<uint64_t>(ref.seq_len[w.rid]), m == 0 ? 'P' : 'S');
                     if (len > 0) {
                         const int more = snprintf(&text[len - 1], text.size() - static_cast<size_t>(len - 1), "\tne:i:%ld\tns:i:%ld\tdc:A:%c%s\n", (long)info[i].q_events,
-                                                  (long)info[i].n_samples, reason[i], targets ? target_tags(cls[i], r).c_str() : "");
+                                                  (long)info[i].n_samples, reason[i], tail.c_str());
                         len = (more < 0 || static_cast<size_t>(len - 1 + more) >= text.size()) ? -1 : len - 1 + more;
                     }
                     if (len < 0) die("PAF line too long");
@@ -340,6 +391,7 @@ int realtime_run(int argc, char **argv, double t0) {
     }
     if (trace) fclose(trace);
     if (targets) rep.print_targets();
+    if (r.by_name) rep.print_groups(group_names);
     if (o.verbosity >= 3) rep.print(r, ch, ch.sampling_rate > 0 ? static_cast<double>(r.chunk_samples) / ch.sampling_rate : 0.0);
     return 0;
 }

@@ -18,8 +18,10 @@
 //             Channels freed in a tick, by a decision or by a hold that ends, take the next records lowest channel first
 //   the end   no channel is busy
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <string>
 #include <vector>
 
 namespace cli {
@@ -57,6 +59,22 @@ inline char decide_targets(const Status &s, char decision) {
 }
 // what happens to a decided read: the class decision when it was early, else it proceeds
 inline char action_of(char reason, char decision) { return reason == 'E' ? decision : 'P'; }
+
+// ---- with --by-name: the two tags a line gains behind tm:f: (Python twin: realtime.group_tags) ----
+// The fields are sfa_group_head_t's: tg:Z: names the best entry (`*`: the background, index names.size(), or no entry), gm:f: is
+// (second_score - best_score) / n_events to four decimals with a missing runner-up counting as +inf; nan where undefined (no
+// events, no best entry, +inf against +inf).
+inline std::string group_tags(int32_t best, int32_t second, float best_score, float second_score, int32_t n_events, const std::vector<std::string> &names) {
+    const std::string name = best >= 0 && static_cast<size_t>(best) < names.size() ? names[static_cast<size_t>(best)] : "*";
+    const double runner = second < 0 ? static_cast<double>(INFINITY) : static_cast<double>(second_score);
+    const double gm = n_events > 0 && best >= 0 ? (runner - static_cast<double>(best_score)) / static_cast<double>(n_events) : static_cast<double>(NAN);
+    char buf[64];
+    if (std::isnan(gm))
+        snprintf(buf, sizeof buf, "\tgm:f:nan");
+    else
+        snprintf(buf, sizeof buf, "\tgm:f:%.4f", gm);
+    return "\ttg:Z:" + name + buf;
+}
 
 // one channel's part of a tick's call
 struct Entry {

@@ -10,6 +10,7 @@
 //   sess::Keep        sfa_session_keep_events: the events of an event-mode session's slots, kept for their maps
 //   sess::Maps        sfa_session_event_maps: the scratch of a call (the core is sfa_maps.hip's), where every slot's query begins
 //   sess::Targets     sfa_session_targets: the column mask, and of a sfa_session_classes call the slot list, partial minima, results
+//   sess::Groups      sfa_session_target_groups: the label table, and of a sfa_session_group_bests call the slot list, keys, results
 //   sess::Spread      SFA_SESSION_SPREAD on a group context: one sub-session per shard, a call's entries dealt to them
 // The host rules -- which waves a call becomes, which points of the automatic start it passes -- are session_plan.hpp's; where a
 // spread session's slots live and how a call is dealt to the shards, session_spread.hpp's.
@@ -20,6 +21,7 @@
 #include "events_auto_stream.hpp"
 #include "session_spread.hpp"
 #include "sdtw_session_class.hpp"
+#include "sdtw_session_group.hpp"
 
 namespace sfa {
 // defined in sfa_align.hip, the unit that holds the plain kernels of sdtw_kernels.hpp
@@ -190,6 +192,24 @@ struct Targets {  // sfa_session_targets, sfa_session_classes
     }
 };
 
+struct Groups {  // sfa_session_target_groups, sfa_session_group_bests
+    int32_t n_groups = 0;                 // 0: off
+    std::vector<uint16_t> h_label;        // of the last sfa_session_target_groups call (the upload is synchronous: pageable is fine)
+    DevBuf d_label;                       // group_label_words(total_cols) words of four labels
+    DevBuf d_slot, d_key, d_best, d_head;  // of a call: [n] i32, [n][n_groups + 1] u64, [n][n_groups + 1] sfa_group_best_t, [n] sfa_group_head_t
+    PinBuf h_slot, h_best, h_head;
+    std::vector<int32_t> live;            // ... which entries of the call were launched
+    Event ev[2];
+    bool on() const { return n_groups > 0; }
+    int reserve(int64_t total_cols) { return d_label.reserve(8 * sfa::group_label_words(total_cols)); }
+    int reserve_call(size_t n, size_t entries, bool bests) {
+        const size_t nb = bests ? sizeof(sfa_group_best_t) * n * entries : 0;
+        if (nb)
+            if (int rc = reserve_all(d_best, nb, h_best, nb)) return rc;
+        return reserve_all(d_slot, 4 * n, h_slot, 4 * n, d_key, 8 * n * entries, d_head, sizeof(sfa_group_head_t) * n, h_head, sizeof(sfa_group_head_t) * n);
+    }
+};
+
 // SFA_SESSION_SPREAD on a group context: the session is one ordinary session per shard that holds slots (global slot i: local
 // slot i / G of subs[i % G]); every entry point deals its entries to them (session_spread.hpp), runs the shards side by side
 // (for_each_shard) and puts the answers back in the caller's order.  What a call packs or collects per shard lies here and is
@@ -208,6 +228,8 @@ struct Spread {
         std::vector<int64_t> len;
         std::vector<uint64_t> span;
         std::vector<sfa_class_t> cls;
+        std::vector<sfa_group_best_t> gbest;
+        std::vector<sfa_group_head_t> ghead;
         int32_t on_host = 0;
     };
     std::vector<Shard> shard;  // [G]
@@ -233,6 +255,7 @@ struct sfa_session {
     sess::Keep keep;
     sess::Maps maps;
     sess::Targets targets;
+    sess::Groups groups;
     std::unique_ptr<sess::Spread> spread;  // SFA_SESSION_SPREAD on a group context: `c` is the group, everything above is unused
     int32_t name_first = 0, name_step = 1;  // a sub-session of a spread session: local slot l is the caller's slot l * step + first (messages)
 };
@@ -1009,6 +1032,26 @@ int spread_classes(sfa_session *s, const int32_t *slot, int32_t n, sfa_class_t *
     });
 }
 
+int spread_group_bests(sfa_session *s, const int32_t *slot, int32_t n, sfa_group_best_t *bests, sfa_group_head_t *heads) {
+    static const char *const who = "sfa_session_group_bests";
+    if (int rc = spread_live(s, who)) return rc;
+    // (sub-session 0 exists and every sub-session holds the same label table, as in spread_classes)
+    const int32_t entries = s->spread->subs[0]->groups.n_groups + 1;
+    if (entries == 1) return fail(SFA_EINVAL, "%s: the session has no groups (sfa_session_target_groups)", who);
+    if (int rc = spread_deal(s, slot, n, true, who)) return rc;
+    return sfa::for_each_shard(s->c, [&](size_t r) {
+        const sfa::SpreadShardPart &p = s->spread->part.shard[r];
+        sess::Spread::Shard &b = s->spread->shard[r];
+        if (p.n() == 0) return spread_idle(s->c->shards[r]);  // (the group's profile is this call's on every shard)
+        b.ghead.resize(p.local.size());
+        if (bests) b.gbest.resize(p.local.size() * static_cast<size_t>(entries));
+        if (int rc = sfa_session_group_bests(s->spread->subs[r], p.local.data(), p.n(), bests ? b.gbest.data() : nullptr, b.ghead.data())) return rc;
+        if (bests) sfa::spread_scatter(p, b.gbest.data(), bests, entries);
+        sfa::spread_scatter(p, b.ghead.data(), heads);
+        return static_cast<int>(SFA_OK);
+    });
+}
+
 // the sub-session that owns *slot, which becomes its local number there (the one-slot calls: sfa_session_row, sfa_session_events)
 int spread_owner(sfa_session *s, int32_t *slot, const char *who, sfa_session **sub) {
     if (int rc = spread_live(s, who)) return rc;
@@ -1359,6 +1402,145 @@ int sfa_session_classes(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_cl
 int sfa_target_decide(const sfa_class_t *cls, int32_t mode, int32_t min_events, float margin) {
     return cls ? sfa::target_decide(*cls, mode, min_events, margin) : 0;
 }
+
+// ---- target groups (group_rules.hpp, sdtw_session_group.hpp) ----
+
+int sfa_session_target_groups(sfa_session_t *s, const sfa_group_target_t *targets, int32_t n, int32_t n_groups) {
+    static const char *const who = "sfa_session_target_groups";
+    if (!s || n < 0 || (n > 0 && !targets)) return fail(SFA_EINVAL, "%s: bad argument", who);
+    if (s->resweep)
+        return fail(SFA_EINVAL, "%s: the session was created with SFA_SESSION_RESWEEP: its carried row belongs to the reversed query, and what its minimum means has "
+                                "not been looked into",
+                    who);
+    if (s->spread) {  // every sub-session holds the table (no slot needs to be empty: spread_config's check does not apply)
+        if (int rc = spread_live(s, who)) return rc;
+        sess::Spread &sp = *s->spread;
+        std::vector<int> rcs(sp.subs.size(), 0);
+        const int rc = sfa::for_each_shard(s->c, [&](size_t r) { return sp.subs[r] ? (rcs[r] = sfa_session_target_groups(sp.subs[r], targets, n, n_groups)) : static_cast<int>(SFA_OK); });
+        size_t have = 0, failed = 0;
+        for (size_t r = 0; r < sp.subs.size(); ++r) have += sp.subs[r] != nullptr, failed += rcs[r] != SFA_OK;
+        if (failed != 0 && failed != have) sp.broken = true;
+        return rc;
+    }
+    sfa_ctx *c = s->c;
+    sess::Groups &g = s->groups;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (a table in use is not replaced under a kernel)
+    if (n == 0) {
+        g.n_groups = 0;
+        std::vector<uint16_t>().swap(g.h_label);
+        g.d_label = DevBuf{};  // (freed; the buffers of a call stay for the next table)
+        return SFA_OK;
+    }
+    if (c->model.total_cols >= INT32_MAX) return fail(SFA_ERANGE, "%s: the reference has %lld columns; the groups count them in 31 bits", who, (long long)c->model.total_cols);
+    // the model's tables on the host: jobs are contig-major, '+' before '-' (sfa_context.hip)
+    const int32_t nj = c->model.n_jobs, strands = nj / c->model.num_ref;
+    std::vector<int32_t> job_contig(nj), ref_len(c->model.num_ref);
+    std::vector<int8_t> job_strand(nj);
+    for (int32_t j = 0; j < nj; ++j) job_contig[j] = j / strands, job_strand[j] = (j % strands) ? '-' : '+';
+    for (int32_t r = 0; r < c->model.num_ref; ++r) ref_len[r] = c->model.h_job_len[static_cast<size_t>(r) * strands];
+    const sfa::TargetModel m{c->model.num_ref, nj, job_contig.data(), job_strand.data(), c->model.h_job_len.data(), s->rows.h_col_off.data(), ref_len.data(),
+                             c->model.h_ref_off.data(), c->model.total_cols};
+    char msg[256];
+    if (sfa::group_list_error(targets, n, n_groups, m, msg, sizeof msg)) return fail(SFA_EINVAL, "%s: %s", who, msg);
+    std::vector<uint16_t> label;
+    sfa::group_labels(targets, n, n_groups, m, &label);
+    if (int rc = g.reserve(c->model.total_cols)) return rc;
+    if (int rc = sess::create_events(g.ev, 2)) return rc;
+    g.n_groups = 0;  // (off until the new table is up)
+    g.h_label.swap(label);
+    HIP_TRY(hipMemcpyAsync(g.d_label.p, g.h_label.data(), 2 * g.h_label.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    g.n_groups = n_groups;
+    return SFA_OK;
+}
+
+int32_t sfa_session_group_count(sfa_session_t *s) {
+    if (!s) return fail(SFA_EINVAL, "sfa_session_group_count: null session");
+    if (s->spread) return sfa_session_group_count(s->spread->subs[0]);  // (sub-session 0 always exists, as in spread_classes)
+    return s->groups.n_groups;
+}
+
+int sfa_session_group_bests(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_group_best_t *bests, sfa_group_head_t *heads) {
+    static const char *const who = "sfa_session_group_bests";
+    if (!s || n < 0 || (n > 0 && (!slot || !heads))) return fail(SFA_EINVAL, "%s: bad argument", who);
+    if (s->spread) return spread_group_bests(s, slot, n, bests, heads);
+    sess::Groups &g = s->groups;
+    if (!g.on()) return fail(SFA_EINVAL, "%s: the session has no groups (sfa_session_target_groups)", who);
+    if (int rc = check_slots(s, slot, n, who)) return rc;
+    begin_call(s);  // (the stamps say which slots this call has named)
+    for (int32_t i = 0; i < n; ++i)
+        if (int rc = claim_slot(s, slot[i], who)) return rc;
+    if (n == 0) return SFA_OK;
+    sfa_ctx *c = s->c;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = sfa::resolve_profile(c)) return rc;
+    g.live.clear();
+    for (int32_t i = 0; i < n; ++i)  // empty and poisoned slots are not launched
+        if (!s->rows.poison[slot[i]] && s->rows.len[slot[i]] > 0) g.live.push_back(i);
+    const int32_t m = static_cast<int32_t>(g.live.size()), parts = sfa::class_parts(c->model.total_cols), entries = g.n_groups + 1;
+    // (every refusal in front of the first write to the caller's records)
+    if (static_cast<int64_t>(m) * parts > INT32_MAX) return fail(SFA_ERANGE, "%s: %d slots x %d parts of a row are more blocks than a launch takes", who, m, parts);
+    if (m > 0)
+        if (int rc = g.reserve_call(static_cast<size_t>(m), static_cast<size_t>(entries), bests != nullptr)) return rc;
+    sfa_group_best_t no_best{};
+    no_best.score = INFINITY;
+    no_best.rid = no_best.pos_end = -1;
+    for (int32_t i = 0; i < n; ++i) heads[i] = sfa::group_head_none();
+    if (bests)
+        for (size_t k = 0; k < static_cast<size_t>(n) * entries; ++k) bests[k] = no_best;
+    sfa_profile_t pr{};
+    pr.segment_reruns = c->seg.seg_reruns;
+    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
+    if (m > 0) {
+        int32_t *hs = g.h_slot.as<int32_t>();
+        for (int32_t k = 0; k < m; ++k) hs[k] = slot[g.live[k]];
+        hipStream_t st = c->stream;
+        const size_t n_keys = static_cast<size_t>(m) * entries;
+        HIP_TRY(hipMemcpyAsync(g.d_slot.p, hs, 4 * static_cast<size_t>(m), hipMemcpyHostToDevice, st));
+        sfa::SessionGroupArgs a;
+        a.slot = g.d_slot.as<int32_t>();
+        a.rows = s->rows.d_row_c.as<float>() + sfa::kSessionPad;
+        a.label = g.d_label.as<uint64_t>();
+        a.key = g.d_key.as<unsigned long long>();
+        a.total_cols = c->model.total_cols;
+        a.n = m;
+        a.n_parts = parts;
+        a.n_entries = entries;
+        sfa::SessionGroupRowsArgs ra;
+        ra.key = a.key;
+        ra.col_off = s->rows.d_col_off.as<int64_t>();
+        ra.ref = c->model.tables();
+        ra.best = bests ? g.d_best.as<sfa_group_best_t>() : nullptr;
+        ra.head = g.d_head.as<sfa_group_head_t>();
+        ra.n = m;
+        ra.n_entries = entries;
+        ra.n_jobs = c->model.n_jobs;
+        HIP_TRY(hipEventRecord(g.ev[0], st));
+        HIP_TRY(hipMemsetAsync(g.d_key.p, 0xff, 8 * n_keys, st));  // all-ones: no column met
+        hipLaunchKernelGGL(sfa::sdtw_session_group_kernel, dim3(static_cast<unsigned>(m) * parts), dim3(sfa::kClassThreads), 0, st, a);
+        KERNEL_TRY();
+        hipLaunchKernelGGL(sfa::sdtw_session_group_rows_kernel, dim3(m), dim3(64), 0, st, ra);
+        KERNEL_TRY();
+        HIP_TRY(hipEventRecord(g.ev[1], st));
+        HIP_TRY(hipMemcpyAsync(g.h_head.p, g.d_head.p, sizeof(sfa_group_head_t) * static_cast<size_t>(m), hipMemcpyDeviceToHost, st));
+        if (bests) HIP_TRY(hipMemcpyAsync(g.h_best.p, g.d_best.p, sizeof(sfa_group_best_t) * n_keys, hipMemcpyDeviceToHost, st));
+        if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, g.ev[0], g.ev[1]));
+        pr.class_ms = pr.total_ms = ms;
+        for (int32_t k = 0; k < m; ++k) {
+            heads[g.live[k]] = g.h_head.as<sfa_group_head_t>()[k];
+            heads[g.live[k]].n_events = static_cast<int32_t>(s->rows.len[slot[g.live[k]]]);
+            if (bests) memcpy(bests + static_cast<size_t>(g.live[k]) * entries, g.h_best.as<sfa_group_best_t>() + static_cast<size_t>(k) * entries, sizeof(sfa_group_best_t) * entries);
+        }
+    }
+    c->prof = pr;
+    return SFA_OK;
+}
+
+int sfa_group_decide(const sfa_group_head_t *h, int32_t min_events, float margin) { return h ? sfa::group_decide(*h, min_events, margin) : -1; }
 
 // ---- event maps of a slot's row (the core: sfa_maps.hip) ----
 

@@ -175,7 +175,7 @@ AUTO_START_MAX_SAMPLES, MAX_SKIP_EVENTS = 131072, 4096  # the defaults of --auto
 
 
 def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False, resweep=False,
-           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None):
+           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None, by_name=False):
     """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
     candidates=1..4 (--candidates): an eighth element, RESULT_DTYPE[4], the channel's candidates at the decision, best first.
     A `session` of the caller's is taken as it is, in this as in its raw mode: it must keep that many candidates already
@@ -198,8 +198,22 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     candidates' maps with candidates=N, else None).  A session that carries no start columns (starts=False) has no maps: refused
     before any call.
     spread=True (--spread): the session of replay's own is aligner.session(channels, spread=True) -- on an Aligner made with
-    devices= the channels are dealt over its devices; the items are the same."""
+    devices= the channels are dealt over its devices; the items are the same.
+    by_name=True (--by-name): targets= is the pair api.read_target_groups returns, (GROUP_TARGET_DTYPE array, group names): its
+    intervals are the targets, and its groups become the session's (Session.set_target_groups).  Decisions stay the class
+    record's; every tick ends with ONE Session.group_bests call over the channels that have a line in it, and an item gains, behind
+    the class record and the action, the channel's GROUP_HEAD_DTYPE record (None without a line), which format_line takes as
+    group=(head, names).  summary gains ("group", index) -> accepted reads whose best entry that is."""
     auto = skip < 0
+    if by_name and targets is None:
+        raise api.SfaError("replay: by_name belongs to targets=")
+    group_targets = group_names = None
+    if by_name:
+        group_targets, group_names = targets
+        group_targets = api._group_targets(group_targets)
+        targets = np.zeros(len(group_targets), api.TARGET_DTYPE)
+        for f in ("contig", "begin", "end"):
+            targets[f] = group_targets[f]
     if targets is None and (mode is not None or margin is not None):
         raise api.SfaError("replay: mode and margin belong to targets=")
     if targets is not None:  # (all of it before any session exists)
@@ -241,6 +255,8 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                 se.configure_auto_start(chunk_samples if auto_start_every is None else auto_start_every, auto_start_max_samples)
         if targets is not None:
             se.set_targets(targets)
+        if by_name:
+            se.set_target_groups(group_targets, len(group_names))
         if candidates and not own:
             se.candidates([])  # (raises unless the caller's session keeps candidates)
         sch.start(src)
@@ -277,12 +293,23 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                             m_rows[per * k + 1:per * k + 5] = cand[k]
                     pairs, off, _ = se.event_maps(m_rows, np.repeat(np.asarray(d_slots, np.int32), per))
                     maps = [_map_or_none(pairs[off[j]:off[j + 1]]) for j in range(len(m_rows))]
+                heads = {}
+                if by_name:  # one call for the tick, over the channels that have a line, before the reset
+                    lined = [i for i in decided if line[i]]
+                    if lined:
+                        heads = dict(zip(lined, se.group_bests([slots[i] for i in lined])[1]))
+                    if summary is not None:
+                        for i in lined:
+                            if action[i] == "A" and heads[i]["best"] >= 0:
+                                summary[("group", int(heads[i]["best"]))] = summary.get(("group", int(heads[i]["best"])), 0) + 1
                 for k, i in enumerate(decided):
                     item = (sch.tick, slots[i], on[slots[i]][0], rows[i].copy(), info[i].copy(), (int(a[k]), int(b[k])), reason[i])
                     if candidates:
                         item += (cand[k].copy(),)
                     if targets is not None:
                         item += (cls[i].copy(), action[i])
+                    if by_name:
+                        item += (heads[i].copy() if i in heads else None,)
                     if auto:
                         item += (au[k].copy(),)
                     if sam:
@@ -321,6 +348,23 @@ def target_tags(cls, mode, min_events, margin):
     return f"\ttc:A:{tc}\tac:A:{dec or 'P'}\ttm:f:{'nan' if tm != tm else '%.4f' % tm}"
 
 
+def group_tags(head, names):
+    """tg:Z:<name of the best entry, * for the background> gm:f:<(second - best) / n_events> for a GROUP_HEAD_DTYPE record at a
+    decision (replay::group_tags): a missing runner-up counts as +inf; nan where undefined (no events, no best entry, +inf
+    against +inf)."""
+    best, second, n = int(head["best"]), int(head["second"]), int(head["n_events"])
+    name = names[best] if 0 <= best < len(names) else "*"
+    runner = float("inf") if second < 0 else float(head["second_score"])
+    with np.errstate(all="ignore"):
+        gm = float((np.float64(runner) - np.float64(float(head["best_score"]))) / n) if n > 0 and best >= 0 else float("nan")
+    return f"\ttg:Z:{name}\tgm:f:{'nan' if gm != gm else '%.4f' % gm}"
+
+
+def format_group_summary(summary, names):
+    """the lines `sigfish-amd realtime --by-name` ends its stderr with: accepted reads per best entry, the background last"""
+    return "".join("[realtime] group %s: accepted %d reads\n" % (names[g] if g < len(names) else "*", summary.get(("group", g), 0)) for g in range(len(names) + 1))
+
+
 def format_summary(summary):
     """the line `sigfish-amd realtime --targets` ends its stderr with, from the dict replay(summary=) filled"""
     get = lambda a: summary.get(a, [0, 0])
@@ -335,20 +379,21 @@ def auto_tags(auto):
     return f"\tqs:i:{int(auto['skip'])}\tas:A:{how}"
 
 
-def format_line(read_id, n_samples, names, seq_lengths, row, info, span, reason, auto=None, target=None):
+def format_line(read_id, n_samples, names, seq_lengths, row, info, span, reason, auto=None, target=None, group=None):
     """The line `sigfish-amd realtime` prints for a decision, or "" when its row is not mapped: paf_row (query_size as dtw passes
     it, last query event - first), then ne:i:<query events> ns:i:<samples sent> dc:A:<reason>.  n_samples: of the whole read.
     auto: the decision's automatic start (replay with skip = -1): qs:i and as:A follow the three tags.
-    target: (class record, mode, min_events, margin) of a replay with targets=: target_tags() follow."""
+    target: (class record, mode, min_events, margin) of a replay with targets=: target_tags() follow.
+    group: (head record, group names) of a replay with by_name=True: group_tags() follow those."""
     if not mapped(row):
         return ""
     rid = int(row["rid"])
     base = api.paf_row(row, read_id, names[rid], span[0], span[1], int(info["q_events"]) - 1, int(n_samples), int(seq_lengths[rid]))
-    tail = ("" if auto is None else auto_tags(auto)) + ("" if target is None else target_tags(*target))
+    tail = ("" if auto is None else auto_tags(auto)) + ("" if target is None else target_tags(*target)) + ("" if group is None else group_tags(*group))
     return f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}{tail}\n"
 
 
-def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, span, reason, target=None):
+def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, span, reason, target=None, group=None):
     """The candidate lines that follow a decision's primary line under --candidates: one per valid row of `cand`, best first, each
     the tp:A:S line of paf_row_ex with the primary's span and query_size and the primary's three tags; "" when the primary has no
     line."""
@@ -360,7 +405,7 @@ def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, s
             continue
         rid = int(r["rid"])
         base = api.paf_row(r, read_id, names[rid], span[0], span[1], int(info["q_events"]) - 1, int(n_samples), int(seq_lengths[rid]), tp="S")
-        out.append(f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}{'' if target is None else target_tags(*target)}\n")
+        out.append(f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}{'' if target is None else target_tags(*target)}{'' if group is None else group_tags(*group)}\n")
     return "".join(out)
 
 
