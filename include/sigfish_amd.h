@@ -407,6 +407,31 @@ int sfa_session_group_bests(sfa_session_t *s, const int32_t *slot, int32_t n, sf
  * otherwise -1 -- also for valid = 0, no best entry, a margin that is negative or not finite.  No default margin, as above. */
 int sfa_group_decide(const sfa_group_head_t *h, int32_t min_events, float margin);
 
+/* ---- open and closed groups: the class decision over groups that are still wanted (quotas) -------------------------------------
+ * A bitmap of open groups comes with every call: (n_groups + 31) / 32 words of 32 bits, bit g % 32 of word g / 32 set: group g
+ * is open -- still wanted.  Bits at or above n_groups are ignored; a NULL bitmap says every group is open.  A column is ON when
+ * its label (above: the lowest group id that covers it) is a group and that group's bit is set; every other column is OFF -- the
+ * background and every closed group.  Closing a group is clearing a bit on the host: no mask is rebuilt, nothing is uploaded.
+ * cls is filled exactly as sfa_session_classes fills it for the mask of the open groups' columns (ties, empty classes and classes
+ * of +inf columns as there), so sfa_target_decide applies unchanged.  on_group: the label of the best ON column; off_group: the
+ * label of the best OFF column, a closed group's id or n_groups for the background; -1: the class has no column.
+ * valid 0 (an empty or poisoned slot): scores +inf, rids, coordinates and groups -1. */
+typedef struct {
+    sfa_class_t cls;
+    int32_t on_group, off_group;
+} sfa_open_class_t;
+
+/* The open-class results of slot[0..n) into out[0..n) under `open` (n_words words, or NULL).  One two-class min-reduction over
+ * the slots' carried cost rows whose classes come from the session's label table (sfa_session_target_groups) and the bitmap; no
+ * mask (sfa_session_targets) is needed, a session may hold one anyway.  Event mode and raw mode, with and without
+ * SFA_SESSION_NO_START.  Blocking, on the context's stream; sfa_profile_t.class_ms is its device time.  A spread session
+ * partitions the call by shard, every shard gets the bitmap, and answers come in the caller's order.  A call adds 16 bytes per
+ * named slot and 8192 columns and 48 bytes per named slot of session scratch; once per label table the host finds the lowest
+ * column of every label (4 * (n_groups + 1) bytes).  A session that never calls it launches what it launched before.
+ * SFA_EINVAL (before anything is written to out): no groups, a slot out of range or named twice, `open` given with n_words other
+ * than (n_groups + 31) / 32. */
+int sfa_session_open_classes(sfa_session_t *s, const int32_t *slot, int32_t n, const uint32_t *open, int32_t n_words, sfa_open_class_t *out);
+
 /* ---- event maps of a slot's row: the warp path of the real-time path -------------------------------------------------------
  * sfa_session_event_maps is sfa_event_maps for rows a SESSION returned: the reference-column -> query-event map
  * (aln_t.r2qevent_map, the ss string of a SAM record) of every row, from the device, with nothing uploaded again.  rows[k] is a

@@ -95,7 +95,8 @@ SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "
            "sfa_session_raw_auto_start", "sfa_session_auto_start", "sfa_session_auto_bytes", "sfa_auto_start_target", "sfa_session_auto_ms",
            "sfa_session_event_maps", "sfa_session_keep_events", "sfa_session_keep_bytes",
            "sfa_session_targets", "sfa_session_target_columns", "sfa_session_classes", "sfa_target_decide",
-           "sfa_session_target_groups", "sfa_session_group_count", "sfa_session_group_bests", "sfa_group_decide"]
+           "sfa_session_target_groups", "sfa_session_group_count", "sfa_session_group_bests", "sfa_group_decide",
+           "sfa_session_open_classes"]
 
 _lib = None
 
@@ -235,5 +236,6 @@ def load():
     L.sfa_session_group_count.restype = C.c_int32
     L.sfa_session_group_bests.argtypes = [vp, i32p, C.c_int32, vp, vp]
     L.sfa_group_decide.argtypes = [C.POINTER(SfaGroupHead), C.c_int32, C.c_float]
+    L.sfa_session_open_classes.argtypes = [vp, i32p, C.c_int32, C.POINTER(C.c_uint32), C.c_int32, vp]
     _lib = L
     return L

@@ -44,6 +44,8 @@ GROUP_HEAD_DTYPE = np.dtype([("best", "<i4"), ("second", "<i4"), ("best_score", 
 assert GROUP_TARGET_DTYPE.itemsize == C.sizeof(_lib.SfaGroupTarget) and GROUP_BEST_DTYPE.itemsize == C.sizeof(_lib.SfaGroupBest) == 16
 assert GROUP_HEAD_DTYPE.itemsize == C.sizeof(_lib.SfaGroupHead)
 GROUP_MAX = 1023  # n_groups at most
+OPEN_CLASS_DTYPE = np.dtype([("cls", CLASS_DTYPE), ("on_group", "<i4"), ("off_group", "<i4")])  # sfa_open_class_t
+assert OPEN_CLASS_DTYPE.itemsize == CLASS_DTYPE.itemsize + 8
 RAW_RECALIBRATED = 16  # ... and the bit of one call: the slot was recalibrated and swept again from event 0
 RECAL_AT_END = 0x1     # SFA_RECAL_AT_END
 RECAL_MAX_POINTS = 32
@@ -752,6 +754,20 @@ class Session:
                "sfa_session_group_bests")
         return bests, heads
 
+    def open_classes(self, slots, open=None):
+        """The class results of `slots` under a bitmap of open groups (sfa_session_open_classes) -> OPEN_CLASS_DTYPE[len(slots)].
+        open: uint32[open_words(n_groups)], bit g % 32 of word g // 32 set: group g is open; None: every group is.  A column is ON
+        when its label is a group whose bit is set, OFF otherwise (closed groups, the background).  `cls` is a CLASS_DTYPE record
+        filled as classes() fills it (target_decide takes it); on_group / off_group are the labels of the two best columns
+        (off_group n_groups: the background; -1: the class has no column).  Needs target groups, no mask."""
+        self._live()
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        out = np.zeros(len(sl), OPEN_CLASS_DTYPE)
+        bits = None if open is None else np.ascontiguousarray(open, np.uint32).reshape(-1)
+        _check(self._L.sfa_session_open_classes(self._h, sl.ctypes.data_as(_lib.i32p), len(sl), None if bits is None else bits.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                0 if bits is None else len(bits), out.ctypes.data_as(C.c_void_p)), "sfa_session_open_classes")
+        return out
+
     def reset(self, slots=None):
         """Forget the events of `slots` (None: of every slot); in raw mode the detector, normalisation and scaling as well."""
         self._live()
@@ -831,6 +847,37 @@ def group_decide(head, min_events, margin):
         raise SfaError("group_decide: one head record at a time")
     got = int(_lib.load().sfa_group_decide(C.cast(rec.ctypes.data, C.POINTER(_lib.SfaGroupHead)), int(min_events), float(margin)))
     return got if got >= 0 else None
+
+
+def open_words(n_groups):
+    """Words of 32 bits in the bitmap of open groups of a session with n_groups groups."""
+    return (int(n_groups) + 31) // 32
+
+
+class QuotaBook:
+    """Who has enough (the twin of quota_rules.hpp's QuotaBook; host arithmetic only): a quota and an accepted count per group and
+    the bitmap of open groups Session.open_classes takes.  A quota of 0 is unlimited."""
+
+    def __init__(self, n_groups, quota=0):
+        self.n_groups = int(n_groups)
+        self.quota = [int(quota)] * self.n_groups
+        self.accepted = [0] * self.n_groups
+        self.open = np.zeros(open_words(self.n_groups), np.uint32)
+        for g in range(self.n_groups):
+            self.open[g >> 5] |= np.uint32(1 << (g & 31))
+
+    def is_open(self, group):
+        return 0 <= group < self.n_groups and bool((int(self.open[group >> 5]) >> (group & 31)) & 1)
+
+    def note_accept(self, group):
+        """One accepted read of `group` (the background and -1 count nowhere) -> True when this read closed the group."""
+        if not 0 <= group < self.n_groups:
+            return False
+        self.accepted[group] += 1
+        if self.quota[group] <= 0 or self.accepted[group] < self.quota[group] or not self.is_open(group):
+            return False
+        self.open[group >> 5] &= np.uint32(~(1 << (group & 31)) & 0xffffffff)
+        return True
 
 
 def target_decide(cls, mode, min_events, margin):

@@ -82,6 +82,7 @@ struct RealtimeOpt {
     std::string targets;           // --targets FILE.bed: the session's targets; the early decision is the class decision (replay.hpp)
     int32_t target_mode = -1;      // --enrich: 0, --deplete: 1 (exactly one of them with --targets)
     bool by_name = false;          // --by-name: the BED file's name column sets the session's target groups; lines gain tg / gm (replay.hpp)
+    int64_t quota = 0;             // --quota N: accepted reads after which a named group is closed (needs --by-name --enrich; 0: off)
     float margin = 0.0f;           // --margin X: cost per query event between the classes (required with --targets: no default)
     std::string trace;             // --trace FILE: the schedule's trace lines (replay.hpp)
 };

@@ -20,7 +20,7 @@ enum LongOpt {
     O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
     O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
     O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE,
-    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_BY_NAME, O_TRACE
+    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_BY_NAME, O_TRACE, O_QUOTA
 };
 
 const option kLongOptions[] = {
@@ -118,7 +118,7 @@ const option kRealtimeOptions[] = {
     {"secondary", required_argument, 0, O_SECONDARY}, {"ranks", required_argument, 0, O_RANKS},
     {"candidates", required_argument, 0, O_CANDIDATES}, {"spread", no_argument, 0, O_SPREAD},
     {"targets", required_argument, 0, O_TARGETS}, {"enrich", no_argument, 0, O_ENRICH}, {"deplete", no_argument, 0, O_DEPLETE},
-    {"margin", required_argument, 0, O_MARGIN}, {"by-name", no_argument, 0, O_BY_NAME}, {"trace", required_argument, 0, O_TRACE},
+    {"margin", required_argument, 0, O_MARGIN}, {"by-name", no_argument, 0, O_BY_NAME}, {"quota", required_argument, 0, O_QUOTA}, {"trace", required_argument, 0, O_TRACE},
     {0, 0, 0, 0}};
 
 void realtime_help(FILE *fp, const RealtimeOpt &r) {
@@ -174,6 +174,12 @@ void realtime_help(FILE *fp, const RealtimeOpt &r) {
     fprintf(fp, "   --by-name                  with --targets: column 4 of the BED file names each interval's group (at most 1023 names); lines gain\n"
                 "                              tg:Z:<group of the read's best column, * for none> gm:f:<(runner-up - best) / events>, the summary\n"
                 "                              one line per group; decisions stay the class decision's [off]\n");
+    fprintf(fp, "   --quota INT                with --by-name --enrich: every named group wants INT accepted reads.  A group that has them is\n"
+                "                              closed from the next tick on: its columns count as off target, so its reads are unblocked (one\n"
+                "                              sfa_session_open_classes call per tick in place of the class call; nothing is uploaded when a\n"
+                "                              group closes).  A tick decides under the groups open at its start, so a group may overshoot by the\n"
+                "                              reads accepted in its closing tick.  Lines gain og:Z:<open group of the read's best on-target\n"
+                "                              column, * for none>, the trace `close` lines, the summary quota= and closed_at= [off]\n");
     fprintf(fp, "   --trace FILE               write the schedule's trace (take / send / hold / decide lines) to FILE [off]\n");
     fprintf(fp, "   --pace yes|no              sleep so that tick t does not start before t x chunk-samples / sampling_rate seconds;\n"
                 "                              changes the timing report on stderr only, never the output [no]\n\n"
@@ -188,7 +194,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     FILE *fp_help = stderr;
     int c, li = 0;
     bool secondary = false;
-    const char *recal = nullptr, *candidates = nullptr, *margin = nullptr;
+    const char *recal = nullptr, *candidates = nullptr, *margin = nullptr, *quota = nullptr;
     bool enrich = false, deplete = false;
     while ((c = getopt_long(argc, argv, "p:q:t:v:o:ahV", kRealtimeOptions, &li)) >= 0) {
         switch (c) {
@@ -230,6 +236,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
             case O_DEPLETE: deplete = true; break;
             case O_MARGIN: margin = optarg; break;
             case O_BY_NAME: r.by_name = true; break;
+            case O_QUOTA: quota = optarg; break;
             case O_TRACE: r.trace = optarg; break;
             default: realtime_help(stderr, r); exit(EXIT_FAILURE);
         }
@@ -259,6 +266,14 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     // adaptive sampling: everything that needs no file
     if (r.targets.empty() && (enrich || deplete || margin)) die("realtime: --enrich, --deplete and --margin belong to --targets FILE.bed");
     if (r.targets.empty() && r.by_name) die("realtime: --by-name belongs to --targets FILE.bed");
+    if (quota) {
+        if (!r.by_name) die("realtime: --quota counts accepted reads per named group: pass --targets FILE.bed --by-name --enrich with it");
+        if (deplete) die("realtime: --quota is not available with --deplete (a closed group's reads would be accepted): use --enrich");
+        char *e = nullptr;
+        const long long v = strtoll(quota, &e, 10);
+        if (e == quota || *e || v < 1) die("realtime: --quota should be an integer >= 1 (leave the option out for no quota)");
+        r.quota = v;
+    }
     if (!r.targets.empty()) {
         if (enrich == deplete) die("realtime: --targets needs exactly one of --enrich and --deplete");
         if (!margin) die("realtime: --targets needs --margin: nobody has measured a good value, there is no default");

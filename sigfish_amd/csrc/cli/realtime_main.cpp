@@ -7,6 +7,8 @@
 // every GPU of --device (SFA_SESSION_SPREAD); the schedule counts ticks, so the output is the same bytes.
 // With --by-name the BED file's name column also sets the session's target groups: each tick ends with one
 // sfa_session_group_bests call over the channels that print a line, and their lines gain tg / gm (replay::group_tags).
+// With --quota N the tick's class call is sfa_session_open_classes under the bitmap of the groups that still want reads, as it stood
+// when the tick began; the schedule credits the accepted reads and closes groups (replay.hpp), lines gain og (replay::quota_tags).
 // With --targets the early decision is the class decision (sfa_session_classes + sfa_target_decide, one call per tick), lines
 // gain the tc / ac / tm tags (target_tags) and accepted reads hold their channels (replay.hpp).
 #include <algorithm>
@@ -185,9 +187,16 @@ struct Report {
     std::vector<double> tick_s;
     int64_t act_reads[3] = {0, 0, 0}, act_samples[3] = {0, 0, 0};  // --targets: A, U, P -- reads, samples sent plus held
     std::vector<int64_t> group_accepted;  // --by-name: accepted reads per best entry, the background last
-    void print_groups(const std::vector<std::string> &names) const {
-        for (size_t g = 0; g < group_accepted.size(); ++g)
-            fprintf(stderr, "[realtime] group %s: accepted %ld reads\n", g < names.size() ? names[g].c_str() : "*", (long)group_accepted[g]);
+    // quota > 0 (--quota): the named groups' lines gain quota=N closed_at=<tick whose credit closed the group, - for an open one>
+    void print_groups(const std::vector<std::string> &names, int64_t quota = 0, const replay::Schedule *sch = nullptr) const {
+        for (size_t g = 0; g < group_accepted.size(); ++g) {
+            fprintf(stderr, "[realtime] group %s: accepted %ld reads", g < names.size() ? names[g].c_str() : "*", (long)group_accepted[g]);
+            if (quota > 0 && g < names.size()) {
+                const int64_t at = sch->closed_at(static_cast<int32_t>(g));
+                fprintf(stderr, " quota=%ld closed_at=%s", (long)quota, at < 0 ? "-" : std::to_string(at).c_str());
+            }
+            fprintf(stderr, "\n");
+        }
     }
     void print_targets() const {
         fprintf(stderr, "[realtime] targets: accepted (A) %ld reads, %ld samples\tunblocked (U) %ld reads, %ld samples\tproceeded (P) %ld reads, %ld samples (sent + held)\n",
@@ -260,6 +269,8 @@ int realtime_run(int argc, char **argv, double t0) {
     ReadAhead ahead(reader, pool, 2 * static_cast<size_t>(C));
     Channels ch{ahead, std::vector<sfa::Blow5Record>(C)};
     replay::Schedule sch(C, r.chunk_samples, trace, targets);
+    sfa::QuotaBook book(r.quota > 0 ? static_cast<int32_t>(group_names.size()) : 1, r.quota);
+    if (r.quota > 0) sch.set_quota(&book, &group_names);
     const replay::Rule rule{r.min_events, r.min_mapq};
     Report rep;
     if (r.by_name) rep.group_accepted.assign(group_names.size() + 1, 0);
@@ -277,6 +288,8 @@ int realtime_run(int argc, char **argv, double t0) {
     std::vector<sfa_session_raw_info_t> info(C);
     std::vector<char> reason(C), line(C), action(C);
     std::vector<sfa_class_t> cls(targets ? C : 0);
+    std::vector<sfa_open_class_t> ocls(r.quota > 0 ? C : 0);
+    std::vector<int32_t> on_group(r.quota > 0 ? C : 0);
     std::vector<int64_t> held;
     std::vector<uint64_t> span_a(C), span_b(C);
     std::vector<sfa_result_t> cand(r.candidates > 0 ? 4 * static_cast<size_t>(C) : 0);
@@ -307,7 +320,12 @@ int realtime_run(int argc, char **argv, double t0) {
         if (sfa_session_extend_raw(se, slot.data(), dst, raw_off.data(), scaling.data(), end.data(), n, rows.data(), info.data()) != SFA_OK)
             die(std::string("tick ") + std::to_string(sch.tick()) + ": " + sfa_last_error());
         decided_slot.clear();
-        if (targets && n > 0 && sfa_session_classes(se, slot.data(), n, cls.data()) != SFA_OK) die(std::string("classes: ") + sfa_last_error());
+        if (r.quota > 0 && n > 0) {  // the tick's classes under the groups open at its start (the book changes in end_tick only)
+            if (sfa_session_open_classes(se, slot.data(), n, book.open(), book.n_words(), ocls.data()) != SFA_OK) die(std::string("open classes: ") + sfa_last_error());
+            for (int32_t i = 0; i < n; ++i) cls[i] = ocls[i].cls, on_group[i] = ocls[i].on_group;
+        } else if (targets && n > 0 && sfa_session_classes(se, slot.data(), n, cls.data()) != SFA_OK) {
+            die(std::string("classes: ") + sfa_last_error());
+        }
         for (int32_t i = 0; i < n; ++i) {
             replay::Status s;
             s.calibrated = info[i].status & 1, s.full = info[i].status & 2, s.ended = info[i].status & 4, s.poisoned = info[i].status & 8;
@@ -354,6 +372,7 @@ int realtime_run(int argc, char **argv, double t0) {
                     tail += replay::group_tags(h.best, h.second, h.best_score, h.second_score, h.n_events, group_names);
                     if (action[i] == 'A' && h.best >= 0) ++rep.group_accepted[h.best];
                 }
+                if (r.quota > 0) tail += replay::quota_tags(on_group[i], group_names);
                 // the primary, then the channel's valid candidates, best first: same span, same tags
                 for (int32_t m = 0; m <= r.candidates; ++m) {
                     const sfa_result_t &w = m == 0 ? rows[i] : cand[4 * static_cast<size_t>(k) + (m - 1)];
@@ -377,7 +396,7 @@ int realtime_run(int argc, char **argv, double t0) {
         if (targets) {
             std::vector<int64_t> sent_now(n);
             for (int32_t i = 0; i < n; ++i) sent_now[i] = sch.sent(slot[i]);
-            sch.end_tick(reason, line, ch, &action, &held);
+            sch.end_tick(reason, line, ch, &action, &held, r.quota > 0 ? &on_group : nullptr);
             for (int32_t i = 0; i < n; ++i) {
                 if (!reason[i]) continue;
                 const int a = action[i] == 'A' ? 0 : action[i] == 'U' ? 1 : 2;
@@ -391,7 +410,7 @@ int realtime_run(int argc, char **argv, double t0) {
     }
     if (trace) fclose(trace);
     if (targets) rep.print_targets();
-    if (r.by_name) rep.print_groups(group_names);
+    if (r.by_name) rep.print_groups(group_names, r.quota, &sch);
     if (o.verbosity >= 3) rep.print(r, ch, ch.sampling_rate > 0 ? static_cast<double>(r.chunk_samples) / ch.sampling_rate : 0.0);
     return 0;
 }

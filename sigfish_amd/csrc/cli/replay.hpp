@@ -16,6 +16,12 @@
 //             sending anything -- the pore goes on reading it -- one trace line `hold ... left=K` per such tick, K counting down to
 //             1; the channel takes its next read at the end of the last one.  An unblocked read ('U') frees its channel at once.
 //             Channels freed in a tick, by a decision or by a hold that ends, take the next records lowest channel first
+//   quota     only with --quota (set_quota, end_tick's `on_group`): every read accepted ('A') with a line in the tick is credited to
+//             the open group of its best on-target column, ascending channels, in the quota book (quota_rules.hpp; host arithmetic).
+//             The credit that fills a group's quota closes it -- trace line `close group=NAME accepted=K` behind the read's
+//             `decide` line -- for the ticks that follow: the run asks for a tick's classes under the bitmap as it stood when the
+//             tick began, so a tick does not depend on the order of its decisions and a group may overshoot by the reads accepted in
+//             its closing tick.  Proceeding reads ('P') are not credited
 //   the end   no channel is busy
 #pragma once
 #include <cmath>
@@ -23,6 +29,8 @@
 #include <cstdio>
 #include <string>
 #include <vector>
+
+#include "../quota_rules.hpp"
 
 namespace cli {
 namespace replay {
@@ -76,6 +84,12 @@ inline std::string group_tags(int32_t best, int32_t second, float best_score, fl
     return "\ttg:Z:" + name + buf;
 }
 
+// ---- with --quota: the tag a line gains behind gm:f: (Python twin: realtime.quota_tags) ----
+// og:Z: names sfa_open_class_t's on_group, the open group the read's best on-target column belongs to; `*`: the ON class is empty
+inline std::string quota_tags(int32_t on_group, const std::vector<std::string> &names) {
+    return "\tog:Z:" + (on_group >= 0 && static_cast<size_t>(on_group) < names.size() ? names[static_cast<size_t>(on_group)] : std::string("*"));
+}
+
 // one channel's part of a tick's call
 struct Entry {
     int32_t channel;
@@ -95,6 +109,12 @@ class Schedule {
         for (int32_t c = 0; c < static_cast<int32_t>(ch_.size()); ++c)
             if (!take(c, src)) break;
     }
+    // --quota: the book the accepted reads are credited in and the groups' names (both outlive the schedule)
+    void set_quota(sfa::QuotaBook *book, const std::vector<std::string> *names) {
+        book_ = book, names_ = names;
+        closed_at_.assign(static_cast<size_t>(book->n_groups()), -1);
+    }
+    int64_t closed_at(int32_t group) const { return closed_at_[static_cast<size_t>(group)]; }  // the tick whose credit closed the group, -1: open
     bool busy() const { return n_busy_ > 0; }
     int64_t tick() const { return tick_; }
     int64_t reads_taken() const { return next_read_; }
@@ -124,7 +144,8 @@ class Schedule {
     // With targets, action[i] (action_of) says what happens to a decided read; *held (if given) receives the samples a read
     // decided in this tick is held for.
     template <class Source>
-    void end_tick(const std::vector<char> &reason, const std::vector<char> &line, Source &src, const std::vector<char> *action = nullptr, std::vector<int64_t> *held = nullptr) {
+    void end_tick(const std::vector<char> &reason, const std::vector<char> &line, Source &src, const std::vector<char> *action = nullptr, std::vector<int64_t> *held = nullptr,
+                  const std::vector<int32_t> *on_group = nullptr) {
         if (!targets_ || !action) {
             for (size_t i = 0; i < entries_.size(); ++i) {
                 if (!reason[i]) continue;
@@ -149,6 +170,11 @@ class Schedule {
             Channel &k = ch_[e.channel];
             if (trace_)
                 fprintf(trace_, "tick %ld decide ch=%d read=%ld reason=%c line=%d sent=%ld\n", (long)tick_, e.channel, (long)e.read, reason[i], line[i] ? 1 : 0, (long)k.sent);
+            if (book_ && on_group && (*action)[i] == 'A' && line[i] && book_->note_accept((*on_group)[i])) {  // this read filled its group's quota
+                const int32_t g = (*on_group)[i];
+                closed_at_[static_cast<size_t>(g)] = tick_;
+                if (trace_) fprintf(trace_, "tick %ld close group=%s accepted=%ld\n", (long)tick_, (*names_)[static_cast<size_t>(g)].c_str(), (long)book_->accepted(g));
+            }
             const int64_t ticks = (*action)[i] == 'U' ? 0 : (k.len - k.sent + chunk_ - 1) / chunk_;
             if (ticks > 0) {
                 k.hold = ticks;
@@ -184,6 +210,9 @@ class Schedule {
     const int64_t chunk_;
     FILE *trace_;
     const bool targets_;
+    sfa::QuotaBook *book_ = nullptr;  // --quota
+    const std::vector<std::string> *names_ = nullptr;
+    std::vector<int64_t> closed_at_;
     std::vector<Channel> ch_;
     std::vector<Entry> entries_;
     int64_t tick_ = 0, next_read_ = 0;

@@ -11,6 +11,7 @@
 //   sess::Maps        sfa_session_event_maps: the scratch of a call (the core is sfa_maps.hip's), where every slot's query begins
 //   sess::Targets     sfa_session_targets: the column mask, and of a sfa_session_classes call the slot list, partial minima, results
 //   sess::Groups      sfa_session_target_groups: the label table, and of a sfa_session_group_bests call the slot list, keys, results
+//   sess::Open        sfa_session_open_classes: the lowest column of every label, and of a call the slot list, partial minima, results
 //   sess::Spread      SFA_SESSION_SPREAD on a group context: one sub-session per shard, a call's entries dealt to them
 // The host rules -- which waves a call becomes, which points of the automatic start it passes -- are session_plan.hpp's; where a
 // spread session's slots live and how a call is dealt to the shards, session_spread.hpp's.
@@ -22,6 +23,7 @@
 #include "session_spread.hpp"
 #include "sdtw_session_class.hpp"
 #include "sdtw_session_group.hpp"
+#include "sdtw_session_open.hpp"
 
 namespace sfa {
 // defined in sfa_align.hip, the unit that holds the plain kernels of sdtw_kernels.hpp
@@ -210,6 +212,17 @@ struct Groups {  // sfa_session_target_groups, sfa_session_group_bests
     }
 };
 
+struct Open {  // sfa_session_open_classes (the label table is sess::Groups')
+    std::vector<int32_t> first;           // lowest column of every label, [n_groups + 1]; empty: not looked for since the table was set
+    DevBuf d_slot, d_part, d_out;         // of a call: [n] i32, [n][parts] ClassPartial, [n] sfa_open_class_t
+    PinBuf h_slot, h_out;
+    std::vector<int32_t> live;            // ... which entries of the call were launched
+    Event ev[2];
+    int reserve(size_t n, size_t parts) {
+        return reserve_all(d_slot, 4 * n, h_slot, 4 * n, d_part, sizeof(sfa::ClassPartial) * n * parts, d_out, sizeof(sfa_open_class_t) * n, h_out, sizeof(sfa_open_class_t) * n);
+    }
+};
+
 // SFA_SESSION_SPREAD on a group context: the session is one ordinary session per shard that holds slots (global slot i: local
 // slot i / G of subs[i % G]); every entry point deals its entries to them (session_spread.hpp), runs the shards side by side
 // (for_each_shard) and puts the answers back in the caller's order.  What a call packs or collects per shard lies here and is
@@ -230,6 +243,7 @@ struct Spread {
         std::vector<sfa_class_t> cls;
         std::vector<sfa_group_best_t> gbest;
         std::vector<sfa_group_head_t> ghead;
+        std::vector<sfa_open_class_t> ocls;
         int32_t on_host = 0;
     };
     std::vector<Shard> shard;  // [G]
@@ -256,6 +270,7 @@ struct sfa_session {
     sess::Maps maps;
     sess::Targets targets;
     sess::Groups groups;
+    sess::Open open;
     std::unique_ptr<sess::Spread> spread;  // SFA_SESSION_SPREAD on a group context: `c` is the group, everything above is unused
     int32_t name_first = 0, name_step = 1;  // a sub-session of a spread session: local slot l is the caller's slot l * step + first (messages)
 };
@@ -1052,6 +1067,26 @@ int spread_group_bests(sfa_session *s, const int32_t *slot, int32_t n, sfa_group
     });
 }
 
+int spread_open_classes(sfa_session *s, const int32_t *slot, int32_t n, const uint32_t *open, int32_t n_words, sfa_open_class_t *out) {
+    static const char *const who = "sfa_session_open_classes";
+    if (int rc = spread_live(s, who)) return rc;
+    // (sub-session 0 exists and every sub-session holds the same label table, as in spread_classes)
+    const int32_t n_groups = s->spread->subs[0]->groups.n_groups;
+    if (n_groups == 0) return fail(SFA_EINVAL, "%s: the session has no groups (sfa_session_target_groups)", who);
+    if (open && n_words != sfa::open_words(n_groups))
+        return fail(SFA_EINVAL, "%s: the bitmap of %d groups has %d words, not %d", who, n_groups, sfa::open_words(n_groups), n_words);
+    if (int rc = spread_deal(s, slot, n, true, who)) return rc;
+    return sfa::for_each_shard(s->c, [&](size_t r) {
+        const sfa::SpreadShardPart &p = s->spread->part.shard[r];
+        sess::Spread::Shard &b = s->spread->shard[r];
+        if (p.n() == 0) return spread_idle(s->c->shards[r]);  // (the group's profile is this call's on every shard)
+        b.ocls.resize(p.local.size());
+        if (int rc = sfa_session_open_classes(s->spread->subs[r], p.local.data(), p.n(), open, n_words, b.ocls.data())) return rc;
+        sfa::spread_scatter(p, b.ocls.data(), out);
+        return static_cast<int>(SFA_OK);
+    });
+}
+
 // the sub-session that owns *slot, which becomes its local number there (the one-slot calls: sfa_session_row, sfa_session_events)
 int spread_owner(sfa_session *s, int32_t *slot, const char *who, sfa_session **sub) {
     if (int rc = spread_live(s, who)) return rc;
@@ -1426,6 +1461,7 @@ int sfa_session_target_groups(sfa_session_t *s, const sfa_group_target_t *target
     sess::Groups &g = s->groups;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));  // (a table in use is not replaced under a kernel)
+    s->open.first.clear();                     // (sfa_session_open_classes looks for the labels' first columns again)
     if (n == 0) {
         g.n_groups = 0;
         std::vector<uint16_t>().swap(g.h_label);
@@ -1541,6 +1577,85 @@ int sfa_session_group_bests(sfa_session_t *s, const int32_t *slot, int32_t n, sf
 }
 
 int sfa_group_decide(const sfa_group_head_t *h, int32_t min_events, float margin) { return h ? sfa::group_decide(*h, min_events, margin) : -1; }
+
+// ---- open and closed groups (quota_rules.hpp, sdtw_session_open.hpp) ----
+
+int sfa_session_open_classes(sfa_session_t *s, const int32_t *slot, int32_t n, const uint32_t *open, int32_t n_words, sfa_open_class_t *out) {
+    static const char *const who = "sfa_session_open_classes";
+    if (!s || n < 0 || (n > 0 && (!slot || !out))) return fail(SFA_EINVAL, "%s: bad argument", who);
+    if (s->spread) return spread_open_classes(s, slot, n, open, n_words, out);
+    sess::Groups &g = s->groups;
+    sess::Open &o = s->open;
+    if (!g.on()) return fail(SFA_EINVAL, "%s: the session has no groups (sfa_session_target_groups)", who);
+    if (open && n_words != sfa::open_words(g.n_groups))
+        return fail(SFA_EINVAL, "%s: the bitmap of %d groups has %d words, not %d", who, g.n_groups, sfa::open_words(g.n_groups), n_words);
+    if (int rc = check_slots(s, slot, n, who)) return rc;
+    begin_call(s);  // (the stamps say which slots this call has named)
+    for (int32_t i = 0; i < n; ++i)
+        if (int rc = claim_slot(s, slot[i], who)) return rc;
+    if (n == 0) return SFA_OK;
+    sfa_ctx *c = s->c;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = sfa::resolve_profile(c)) return rc;
+    o.live.clear();
+    for (int32_t i = 0; i < n; ++i)  // empty and poisoned slots are not launched
+        if (!s->rows.poison[slot[i]] && s->rows.len[slot[i]] > 0) o.live.push_back(i);
+    const int32_t m = static_cast<int32_t>(o.live.size()), parts = sfa::class_parts(c->model.total_cols);
+    // (every refusal in front of the first write to the caller's records)
+    if (static_cast<int64_t>(m) * parts > INT32_MAX) return fail(SFA_ERANGE, "%s: %d slots x %d parts of a row are more blocks than a launch takes", who, m, parts);
+    if (m > 0) {
+        if (int rc = o.reserve(static_cast<size_t>(m), static_cast<size_t>(parts))) return rc;
+        if (int rc = sess::create_events(o.ev, 2)) return rc;
+    }
+    for (int32_t i = 0; i < n; ++i) out[i] = sfa::open_class_none();
+    sfa_profile_t pr{};
+    pr.segment_reruns = c->seg.seg_reruns;
+    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
+    if (m > 0) {
+        if (o.first.empty()) sfa::open_label_firsts(g.h_label.data(), c->model.total_cols, g.n_groups, &o.first);
+        int32_t *hs = o.h_slot.as<int32_t>();
+        for (int32_t k = 0; k < m; ++k) hs[k] = slot[o.live[k]];
+        hipStream_t st = c->stream;
+        HIP_TRY(hipMemcpyAsync(o.d_slot.p, hs, 4 * static_cast<size_t>(m), hipMemcpyHostToDevice, st));
+        sfa::SessionOpenArgs a;
+        a.slot = o.d_slot.as<int32_t>();
+        a.rows = s->rows.d_row_c.as<float>() + sfa::kSessionPad;
+        a.label = g.d_label.as<uint64_t>();
+        a.part = o.d_part.as<sfa::ClassPartial>();
+        a.total_cols = c->model.total_cols;
+        a.n = m;
+        a.n_parts = parts;
+        sfa::open_normalise(open, g.n_groups, a.open);  // (the bitmap travels in the argument block: nothing is uploaded)
+        sfa::SessionOpenRowsArgs ra;
+        ra.part = a.part;
+        ra.col_off = s->rows.d_col_off.as<int64_t>();
+        ra.ref = c->model.tables();
+        ra.label = g.d_label.as<uint16_t>();
+        ra.out = o.d_out.as<sfa_open_class_t>();
+        ra.n = m;
+        ra.n_parts = parts;
+        ra.n_jobs = c->model.n_jobs;
+        sfa::open_first_cols(o.first, g.n_groups, a.open, &ra.first_on, &ra.first_off);
+        HIP_TRY(hipEventRecord(o.ev[0], st));
+        hipLaunchKernelGGL(sfa::sdtw_session_open_kernel, dim3(static_cast<unsigned>(m) * parts), dim3(sfa::kClassThreads), 0, st, a);
+        KERNEL_TRY();
+        hipLaunchKernelGGL(sfa::sdtw_session_open_rows_kernel, dim3(m), dim3(64), 0, st, ra);
+        KERNEL_TRY();
+        HIP_TRY(hipEventRecord(o.ev[1], st));
+        HIP_TRY(hipMemcpyAsync(o.h_out.p, o.d_out.p, sizeof(sfa_open_class_t) * static_cast<size_t>(m), hipMemcpyDeviceToHost, st));
+        if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, o.ev[0], o.ev[1]));
+        pr.class_ms = pr.total_ms = ms;
+        for (int32_t k = 0; k < m; ++k) {
+            out[o.live[k]] = o.h_out.as<sfa_open_class_t>()[k];
+            out[o.live[k]].cls.n_events = static_cast<int32_t>(s->rows.len[slot[o.live[k]]]);
+        }
+    }
+    c->prof = pr;
+    return SFA_OK;
+}
 
 // ---- event maps of a slot's row (the core: sfa_maps.hip) ----
 

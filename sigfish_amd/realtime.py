@@ -31,6 +31,12 @@ ticks, the same calls, the same lines.  The schedule counts ticks, never seconds
             gains tc:A:<T|O|N> ac:A:<A|U|P> tm:f:<(other - mine) / n_events> (target_tags).  An accepted ('A') or proceeding ('P')
             read keeps its channel for ceil((len - sent) / chunk) further ticks without sending (trace: `hold ... left=K`); an
             unblocked one frees it at once.  Refused with resweep (the session refuses targets there).  margin has no default
+  quota     quota=N with by_name=True and mode=ENRICH (--quota N): every named group wants N accepted reads.  The tick's
+            Session.classes call is replaced by ONE Session.open_classes call under the bitmap of the groups still open when the tick
+            began; decisions run on its `cls` unchanged.  Every read accepted ('A') with a line is credited to its on_group in
+            ascending channel order (api.QuotaBook, in Schedule.end_tick); the credit that fills a quota closes the group from the
+            next tick on (trace: `close group=NAME accepted=K`), so a group may overshoot by the reads accepted in its closing
+            tick.  Proceeding reads are not credited.  Lines gain og:Z:<name of on_group, * for none> (quota_tags)
   after it  decided channels are reset in one call and take the next unread reads, lowest channel first, from tick t + 1 on
 """
 import numpy as np
@@ -82,6 +88,12 @@ class Schedule:
         self.resweep = bool(resweep)  # of the session; nothing here reads it: the schedule does not depend on it
         self.read, self.len, self.sent = [-1] * channels, [0] * channels, [0] * channels
         self.tick, self.next_read, self.entries = 0, 0, []
+        self.book = self.names = None  # set_quota
+        self.closed_at = []
+
+    def set_quota(self, book, names):
+        """replay::Schedule::set_quota: the api.QuotaBook accepted reads are credited in, and the groups' names"""
+        self.book, self.names, self.closed_at = book, names, [-1] * book.n_groups
 
     def _take(self, c, source):
         n = source.take(c)
@@ -118,10 +130,11 @@ class Schedule:
                 self.trace.append(f"tick {self.tick} send ch={c} read={r} first={self.entries[-1][2]} n={n} end={int(n < self.chunk)}")
         return self.entries
 
-    def end_tick(self, reason, line, source, action=None):
-        """action (with targets): action_of per entry; -> samples every entry's read is held for (0 without targets)"""
+    def end_tick(self, reason, line, source, action=None, on_group=None):
+        """action (with targets): action_of per entry; on_group (with a quota): the open-class record's per entry; -> samples every
+        entry's read is held for (0 without targets)"""
         if self.targets and action is not None:
-            return self._end_tick_targets(reason, line, source, action)
+            return self._end_tick_targets(reason, line, source, action, on_group)
         for (c, r, _, _, _), why, ln in zip(self.entries, reason, line):
             if not why:
                 continue
@@ -134,7 +147,7 @@ class Schedule:
         self.tick += 1
         return [0] * len(self.entries)
 
-    def _end_tick_targets(self, reason, line, source, action):
+    def _end_tick_targets(self, reason, line, source, action, on_group=None):
         held = [0] * len(self.entries)
         freed = [False] * len(self.read)
         for c in range(len(self.read)):  # holds of earlier ticks: one tick less, the last one frees
@@ -146,6 +159,11 @@ class Schedule:
                 continue
             if self.trace is not None:
                 self.trace.append(f"tick {self.tick} decide ch={c} read={r} reason={why} line={int(bool(ln))} sent={self.sent[c]}")
+            if self.book is not None and on_group is not None and action[i] == "A" and ln and self.book.note_accept(int(on_group[i])):
+                g = int(on_group[i])  # this read filled its group's quota
+                self.closed_at[g] = self.tick
+                if self.trace is not None:
+                    self.trace.append(f"tick {self.tick} close group={self.names[g]} accepted={self.book.accepted[g]}")
             ticks = 0 if action[i] == "U" else -(-(self.len[c] - self.sent[c]) // self.chunk)
             if ticks > 0:
                 self.hold[c], held[i] = ticks, self.len[c] - self.sent[c]
@@ -175,7 +193,7 @@ AUTO_START_MAX_SAMPLES, MAX_SKIP_EVENTS = 131072, 4096  # the defaults of --auto
 
 
 def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False, resweep=False,
-           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None, by_name=False):
+           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None, by_name=False, quota=None):
     """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
     candidates=1..4 (--candidates): an eighth element, RESULT_DTYPE[4], the channel's candidates at the decision, best first.
     A `session` of the caller's is taken as it is, in this as in its raw mode: it must keep that many candidates already
@@ -203,8 +221,18 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     intervals are the targets, and its groups become the session's (Session.set_target_groups).  Decisions stay the class
     record's; every tick ends with ONE Session.group_bests call over the channels that have a line in it, and an item gains, behind
     the class record and the action, the channel's GROUP_HEAD_DTYPE record (None without a line), which format_line takes as
-    group=(head, names).  summary gains ("group", index) -> accepted reads whose best entry that is."""
+    group=(head, names).  summary gains ("group", index) -> accepted reads whose best entry that is.
+    quota=N (--quota N; needs by_name=True and mode=ENRICH, N >= 1): see `quota` above.  An item's class record is the open-class
+    record's `cls`, and the item gains, behind the head, the record's on_group (format_line takes quota=(on_group, names)).
+    summary gains "quota" -> N and ("closed_at", index) -> the tick whose credit closed the group."""
     auto = skip < 0
+    if quota is not None:  # (before any session exists, each with the fix)
+        if not by_name:
+            raise api.SfaError("replay: quota counts accepted reads per named group: pass targets=(group targets, names), by_name=True and mode=ENRICH with it")
+        if mode == api.DEPLETE:
+            raise api.SfaError("replay: quota is not available with mode=DEPLETE (a closed group's reads would be accepted): use mode=ENRICH")
+        if isinstance(quota, bool) or not isinstance(quota, (int, np.integer)) or quota < 1:
+            raise api.SfaError("replay: quota should be an integer >= 1 (None for no quota)")
     if by_name and targets is None:
         raise api.SfaError("replay: by_name belongs to targets=")
     group_targets = group_names = None
@@ -244,6 +272,12 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
 
     src = Source()
     sch = Schedule(channels, chunk_samples, trace, resweep, targets is not None)
+    book = None
+    if quota is not None and by_name:
+        book = api.QuotaBook(len(group_names), int(quota))
+        sch.set_quota(book, group_names)
+        if summary is not None:
+            summary["quota"] = int(quota)
     own = session is None
     se = aligner.session(channels, resweep=resweep, spread=spread) if own else session
     try:
@@ -268,9 +302,13 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
             scaling = [(on[c][2]["digitisation"], on[c][2]["offset"], on[c][2]["range"]) for c in slots]
             sch_sent = [first + n for _, _, first, n, _ in es]  # samples of every entry's read sent so far
             rows, info = se.extend_raw(slots, np.concatenate(chunks) if chunks else np.zeros(0, np.int16), raw_off, scaling, [e[4] for e in es])
-            cls = action = None
+            cls = action = on_group = None
             if targets is not None:  # one call for the tick, before any reset
-                cls = se.classes(slots)
+                if book is not None:  # under the groups open at the start of the tick (the book changes in end_tick only)
+                    ocls = se.open_classes(slots, book.open)
+                    cls, on_group = ocls["cls"].copy(), ocls["on_group"].copy()
+                else:
+                    cls = se.classes(slots)
                 dec = [api.target_decide(cls[i], mode, min_events, margin) for i in range(len(es))]
                 reason = [decide_targets(info[i], dec[i]) for i in range(len(es))]
                 action = [action_of(why, dec[i]) if why else None for i, why in enumerate(reason)]
@@ -310,6 +348,8 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                         item += (cls[i].copy(), action[i])
                     if by_name:
                         item += (heads[i].copy() if i in heads else None,)
+                    if book is not None:
+                        item += (int(on_group[i]),)
                     if auto:
                         item += (au[k].copy(),)
                     if sam:
@@ -318,7 +358,11 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                                       cand_maps=maps[per * k + 1:per * k + 5] if candidates else None),)
                     yield item
                 se.reset(d_slots)
-            held = sch.end_tick(reason, line, src, action)
+            held = sch.end_tick(reason, line, src, action, on_group)
+            if book is not None and summary is not None:
+                for g, at in enumerate(sch.closed_at):
+                    if at >= 0:
+                        summary[("closed_at", g)] = at
             if summary is not None and targets is not None:
                 for i, why in enumerate(reason):
                     if why:
@@ -360,9 +404,17 @@ def group_tags(head, names):
     return f"\ttg:Z:{name}\tgm:f:{'nan' if gm != gm else '%.4f' % gm}"
 
 
+def quota_tags(on_group, names):
+    """og:Z:<name of the open-class record's on_group, * for none> (replay::quota_tags)"""
+    return "\tog:Z:" + (names[on_group] if 0 <= on_group < len(names) else "*")
+
+
 def format_group_summary(summary, names):
-    """the lines `sigfish-amd realtime --by-name` ends its stderr with: accepted reads per best entry, the background last"""
-    return "".join("[realtime] group %s: accepted %d reads\n" % (names[g] if g < len(names) else "*", summary.get(("group", g), 0)) for g in range(len(names) + 1))
+    """the lines `sigfish-amd realtime --by-name` ends its stderr with: accepted reads per best entry, the background last; with a
+    quota (summary["quota"]) the named groups' lines gain quota=N closed_at=<tick, - for a group still open>"""
+    quota = summary.get("quota", 0)
+    tail = lambda g: " quota=%d closed_at=%s" % (quota, summary.get(("closed_at", g), "-")) if quota and g < len(names) else ""
+    return "".join("[realtime] group %s: accepted %d reads%s\n" % (names[g] if g < len(names) else "*", summary.get(("group", g), 0), tail(g)) for g in range(len(names) + 1))
 
 
 def format_summary(summary):
@@ -379,21 +431,22 @@ def auto_tags(auto):
     return f"\tqs:i:{int(auto['skip'])}\tas:A:{how}"
 
 
-def format_line(read_id, n_samples, names, seq_lengths, row, info, span, reason, auto=None, target=None, group=None):
+def format_line(read_id, n_samples, names, seq_lengths, row, info, span, reason, auto=None, target=None, group=None, quota=None):
     """The line `sigfish-amd realtime` prints for a decision, or "" when its row is not mapped: paf_row (query_size as dtw passes
     it, last query event - first), then ne:i:<query events> ns:i:<samples sent> dc:A:<reason>.  n_samples: of the whole read.
     auto: the decision's automatic start (replay with skip = -1): qs:i and as:A follow the three tags.
     target: (class record, mode, min_events, margin) of a replay with targets=: target_tags() follow.
-    group: (head record, group names) of a replay with by_name=True: group_tags() follow those."""
+    group: (head record, group names) of a replay with by_name=True: group_tags() follow those.
+    quota: (on_group, group names) of a replay with quota=: quota_tags() follows those."""
     if not mapped(row):
         return ""
     rid = int(row["rid"])
     base = api.paf_row(row, read_id, names[rid], span[0], span[1], int(info["q_events"]) - 1, int(n_samples), int(seq_lengths[rid]))
-    tail = ("" if auto is None else auto_tags(auto)) + ("" if target is None else target_tags(*target)) + ("" if group is None else group_tags(*group))
+    tail = ("" if auto is None else auto_tags(auto)) + ("" if target is None else target_tags(*target)) + ("" if group is None else group_tags(*group)) + ("" if quota is None else quota_tags(*quota))
     return f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}{tail}\n"
 
 
-def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, span, reason, target=None, group=None):
+def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, span, reason, target=None, group=None, quota=None):
     """The candidate lines that follow a decision's primary line under --candidates: one per valid row of `cand`, best first, each
     the tp:A:S line of paf_row_ex with the primary's span and query_size and the primary's three tags; "" when the primary has no
     line."""
@@ -405,7 +458,7 @@ def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, s
             continue
         rid = int(r["rid"])
         base = api.paf_row(r, read_id, names[rid], span[0], span[1], int(info["q_events"]) - 1, int(n_samples), int(seq_lengths[rid]), tp="S")
-        out.append(f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}{'' if target is None else target_tags(*target)}{'' if group is None else group_tags(*group)}\n")
+        out.append(f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}{'' if target is None else target_tags(*target)}{'' if group is None else group_tags(*group)}{'' if quota is None else quota_tags(*quota)}\n")
     return "".join(out)
 
 
