@@ -432,6 +432,24 @@ typedef struct {
  * than (n_groups + 31) / 32. */
 int sfa_session_open_classes(sfa_session_t *s, const int32_t *slot, int32_t n, const uint32_t *open, int32_t n_words, sfa_open_class_t *out);
 
+/* ---- truth: a target decision against where a read really came from (host only; no context, no device) --------------------------
+ * A read's truth is the interval [begin, end) of `contig` its bases cover on the forward strand; contig < 0: the read belongs
+ * nowhere.  These are the rules `sigfish-amd realtime --truth` applies (sigfish_amd/csrc/truth_rules.hpp), exported so that no
+ * caller restates them.
+ * sfa_truth_class: 'T' when the interval shares at least one base with a target of its contig, else 'O' (also for contig < 0).
+ * An overlap rule on purpose: a class decision reads the alignment's END coordinate, so a read that straddles a target's edge may
+ * honestly be decided either way; sfa_truth_edge is 1 for such a read -- overlapping, but contained in no single target -- else 0.
+ * sfa_truth_group: the lowest group id among the overlapping group targets (the tie rule of a column's label), else n_groups,
+ * the background.
+ * sfa_truth_verdict: 'C' when the decided class equals the true one, 'W' when it differs, 'N' when either is no class (anything
+ * but 'T' and 'O').  sfa_truth_group_verdict: the same over two entries (a group id, or n_groups for the background); a negative
+ * entry is none, 'N'. */
+int sfa_truth_class(const sfa_target_t *targets, int32_t n, int32_t contig, int32_t begin, int32_t end);
+int sfa_truth_edge(const sfa_target_t *targets, int32_t n, int32_t contig, int32_t begin, int32_t end);
+int32_t sfa_truth_group(const sfa_group_target_t *targets, int32_t n, int32_t n_groups, int32_t contig, int32_t begin, int32_t end);
+int sfa_truth_verdict(int decided, int truth);
+int sfa_truth_group_verdict(int32_t decided, int32_t truth);
+
 /* ---- event maps of a slot's row: the warp path of the real-time path -------------------------------------------------------
  * sfa_session_event_maps is sfa_event_maps for rows a SESSION returned: the reference-column -> query-event map
  * (aln_t.r2qevent_map, the ss string of a SAM record) of every row, from the device, with nothing uploaded again.  rows[k] is a

@@ -96,7 +96,8 @@ SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "
            "sfa_session_event_maps", "sfa_session_keep_events", "sfa_session_keep_bytes",
            "sfa_session_targets", "sfa_session_target_columns", "sfa_session_classes", "sfa_target_decide",
            "sfa_session_target_groups", "sfa_session_group_count", "sfa_session_group_bests", "sfa_group_decide",
-           "sfa_session_open_classes"]
+           "sfa_session_open_classes",
+           "sfa_truth_class", "sfa_truth_edge", "sfa_truth_group", "sfa_truth_verdict", "sfa_truth_group_verdict"]
 
 _lib = None
 
@@ -237,5 +238,10 @@ def load():
     L.sfa_session_group_bests.argtypes = [vp, i32p, C.c_int32, vp, vp]
     L.sfa_group_decide.argtypes = [C.POINTER(SfaGroupHead), C.c_int32, C.c_float]
     L.sfa_session_open_classes.argtypes = [vp, i32p, C.c_int32, C.POINTER(C.c_uint32), C.c_int32, vp]
+    L.sfa_truth_class.argtypes = L.sfa_truth_edge.argtypes = [C.POINTER(SfaTarget), C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.sfa_truth_group.argtypes = [C.POINTER(SfaGroupTarget), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.sfa_truth_group.restype = C.c_int32
+    L.sfa_truth_verdict.argtypes = [C.c_int, C.c_int]
+    L.sfa_truth_group_verdict.argtypes = [C.c_int32, C.c_int32]
     _lib = L
     return L

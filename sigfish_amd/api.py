@@ -946,6 +946,83 @@ def read_target_groups(path, names):
     return _group_targets(out), list(groups)
 
 
+def read_truth(path, names):
+    """A PAF file as the truth of replay(truth=) -> {read id: (contig index, begin, end)}, (-1, 0, 0) for a read that belongs nowhere
+    (the twin of truth_rules.hpp's TruthTable; what `sigfish-amd eval` takes as truth): column 1 the read id, column 6 the contig's
+    name (`*`: the read belongs nowhere, its coordinates are not read), columns 8 and 9 begin and end on the forward strand, 0-based
+    and half open.  Empty lines are skipped.  names: the reference's contig names in order.  Fewer than 9 tab-separated columns, a
+    coordinate that is no integer in 0 .. 2^31 - 1, end <= begin, a contig that is not among the names and a read id that appears
+    twice are errors, each with file name and line number.  A read that is not in the file has no truth."""
+    index = {}
+    for i, n in enumerate(names):
+        index[str(n)] = i  # (a name held twice: the last one, as the binary looks it up)
+    out = {}
+    with open(path, newline="") as fh:
+        for no, line in enumerate(fh.read().split("\n"), 1):
+            if line.endswith("\r"):
+                line = line[:-1]
+            if not line:
+                continue
+            f = line.split("\t")
+            if len(f) < 9:
+                raise SfaError(f"read_truth: {path}:{no}: a PAF line has at least 9 tab-separated columns (this one has {len(f)})")
+            if not f[0]:
+                raise SfaError(f"read_truth: {path}:{no}: the read id (column 1) is empty")
+            if f[5] == "*":
+                rec = (-1, 0, 0)
+            else:
+                if f[5] not in index:
+                    raise SfaError(f"read_truth: {path}:{no}: contig {f[5]!r} is not in the reference")
+                digits = lambda s: 0 < len(s) <= 10 and all("0" <= c <= "9" for c in s) and int(s) <= 2 ** 31 - 1
+                if not digits(f[7]) or not digits(f[8]):
+                    raise SfaError(f"read_truth: {path}:{no}: begin and end (columns 8 and 9) must be integers in 0 .. 2147483647")
+                if int(f[8]) <= int(f[7]):
+                    raise SfaError(f"read_truth: {path}:{no}: the interval [{f[7]}, {f[8]}) is empty")
+                rec = (index[f[5]], int(f[7]), int(f[8]))
+            if f[0] in out:
+                raise SfaError(f"read_truth: {path}:{no}: read id {f[0]!r} appears twice")
+            out[f[0]] = rec
+    return out
+
+
+def _target_ptr(t):
+    return C.cast(t.ctypes.data, C.POINTER(_lib.SfaTarget)) if len(t) else None
+
+
+def truth_class(targets, contig, begin, end):
+    """'T' when [begin, end) of `contig` shares a base with one of `targets` (TARGET_DTYPE, or (contig, begin, end) triples), else 'O'
+    -- also for contig < 0, a read that belongs nowhere (sfa_truth_class; host arithmetic)."""
+    t = _targets(targets)
+    return chr(_lib.load().sfa_truth_class(_target_ptr(t), len(t), int(contig), int(begin), int(end)))
+
+
+def truth_edge(targets, contig, begin, end):
+    """True for a read that overlaps a target but is contained in no single one (sfa_truth_edge): its class decision may honestly
+    go either way."""
+    t = _targets(targets)
+    return bool(_lib.load().sfa_truth_edge(_target_ptr(t), len(t), int(contig), int(begin), int(end)))
+
+
+def truth_group(group_targets, n_groups, contig, begin, end):
+    """The lowest group id among the group targets [begin, end) of `contig` overlaps, else n_groups, the background
+    (sfa_truth_group)."""
+    t = _group_targets(group_targets)
+    ptr = C.cast(t.ctypes.data, C.POINTER(_lib.SfaGroupTarget)) if len(t) else None
+    return int(_lib.load().sfa_truth_group(ptr, len(t), int(n_groups), int(contig), int(begin), int(end)))
+
+
+def truth_verdict(decided, truth):
+    """'C' when the decided class ('T', 'O'; anything else is none) equals the true one, 'W' when it differs, 'N' when either is
+    none (sfa_truth_verdict)."""
+    code = lambda c: ord(c) if isinstance(c, str) and len(c) == 1 else 0
+    return chr(_lib.load().sfa_truth_verdict(code(decided), code(truth)))
+
+
+def truth_group_verdict(decided, truth):
+    """The same over two entries (a group id, or n_groups for the background; negative or None: none) (sfa_truth_group_verdict)."""
+    return chr(_lib.load().sfa_truth_group_verdict(-1 if decided is None else int(decided), -1 if truth is None else int(truth)))
+
+
 def session_bytes(total_columns, n_slots, starts=True, resweep=False):
     """Device memory the carried rows of a session take (sfa_session_bytes; host arithmetic, no GPU needed): RefModel.total_columns()
     x n_slots x 8 bytes, x 4 without starts; the same with resweep (a window beyond 2048 events runs as pieces over a carried row)."""

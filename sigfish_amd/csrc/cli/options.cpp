@@ -20,7 +20,7 @@ enum LongOpt {
     O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
     O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
     O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE,
-    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_BY_NAME, O_TRACE, O_QUOTA
+    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_BY_NAME, O_TRACE, O_QUOTA, O_TRUTH
 };
 
 const option kLongOptions[] = {
@@ -119,6 +119,7 @@ const option kRealtimeOptions[] = {
     {"candidates", required_argument, 0, O_CANDIDATES}, {"spread", no_argument, 0, O_SPREAD},
     {"targets", required_argument, 0, O_TARGETS}, {"enrich", no_argument, 0, O_ENRICH}, {"deplete", no_argument, 0, O_DEPLETE},
     {"margin", required_argument, 0, O_MARGIN}, {"by-name", no_argument, 0, O_BY_NAME}, {"quota", required_argument, 0, O_QUOTA}, {"trace", required_argument, 0, O_TRACE},
+    {"truth", required_argument, 0, O_TRUTH},
     {0, 0, 0, 0}};
 
 void realtime_help(FILE *fp, const RealtimeOpt &r) {
@@ -180,6 +181,11 @@ void realtime_help(FILE *fp, const RealtimeOpt &r) {
                 "                              group closes).  A tick decides under the groups open at its start, so a group may overshoot by the\n"
                 "                              reads accepted in its closing tick.  Lines gain og:Z:<open group of the read's best on-target\n"
                 "                              column, * for none>, the trace `close` lines, the summary quota= and closed_at= [off]\n");
+    fprintf(fp, "   --truth FILE.paf           with --targets: check every decision against where the read came from -- a PAF file, column 1 the\n"
+                "                              read id, 6 the contig (* for a read that belongs nowhere), 8 and 9 begin and end; a read that\n"
+                "                              shares a base with a target is truly on target.  Lines gain tt:A:<true class T|O, N: not in the\n"
+                "                              file> tv:A:<verdict of tc: C correct, W wrong, N> and with --by-name tn:Z:<true group> gv:A:<C|W|N>,\n"
+                "                              the trace `verdict` lines, the summary `truth:` lines.  Changes no decision [off]\n");
     fprintf(fp, "   --trace FILE               write the schedule's trace (take / send / hold / decide lines) to FILE [off]\n");
     fprintf(fp, "   --pace yes|no              sleep so that tick t does not start before t x chunk-samples / sampling_rate seconds;\n"
                 "                              changes the timing report on stderr only, never the output [no]\n\n"
@@ -237,6 +243,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
             case O_MARGIN: margin = optarg; break;
             case O_BY_NAME: r.by_name = true; break;
             case O_QUOTA: quota = optarg; break;
+            case O_TRUTH: r.truth = optarg; break;
             case O_TRACE: r.trace = optarg; break;
             default: realtime_help(stderr, r); exit(EXIT_FAILURE);
         }
@@ -266,6 +273,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     // adaptive sampling: everything that needs no file
     if (r.targets.empty() && (enrich || deplete || margin)) die("realtime: --enrich, --deplete and --margin belong to --targets FILE.bed");
     if (r.targets.empty() && r.by_name) die("realtime: --by-name belongs to --targets FILE.bed");
+    if (r.targets.empty() && !r.truth.empty()) die("realtime: --truth checks target decisions: pass --targets FILE.bed with --enrich or --deplete and --margin with it");
     if (quota) {
         if (!r.by_name) die("realtime: --quota counts accepted reads per named group: pass --targets FILE.bed --by-name --enrich with it");
         if (deplete) die("realtime: --quota is not available with --deplete (a closed group's reads would be accepted): use --enrich");

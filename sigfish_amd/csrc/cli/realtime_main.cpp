@@ -11,6 +11,9 @@
 // when the tick began; the schedule credits the accepted reads and closes groups (replay.hpp), lines gain og (replay::quota_tags).
 // With --targets the early decision is the class decision (sfa_session_classes + sfa_target_decide, one call per tick), lines
 // gain the tc / ac / tm tags (target_tags) and accepted reads hold their channels (replay.hpp).
+// With --truth FILE.paf every decided read is looked up once in the truth table (truth_rules.hpp: the rules and the account), when it
+// is decided: lines gain tt / tv (tn / gv with --by-name), the trace `verdict` lines, the summary `truth:` lines.  The file is read
+// and checked against the FASTA's contig names before the BLOW5 file or a device is opened; no decision reads it.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -23,6 +26,7 @@
 #include <future>
 #include <thread>
 
+#include "../truth_rules.hpp"
 #include "replay.hpp"
 #include "run.hpp"
 
@@ -167,10 +171,28 @@ std::vector<sfa_target_t> read_targets(const std::string &path, const Reference 
     return out;
 }
 
+// --truth: the table of the PAF file, contigs by the names of the FASTA file (read here for its names only: the reference proper is
+// built after the BLOW5 file has told the chemistry)
+sfa::TruthTable read_truth(const std::string &path, const std::string &fasta) {
+    std::vector<sfa::FastaRecord> recs;
+    std::string err;
+    if (!sfa::read_fasta(fasta, &recs, &err)) die(err);
+    std::vector<std::string> names;
+    for (const sfa::FastaRecord &c : recs) names.push_back(c.name);
+    std::ifstream in(path);
+    if (!in) die("realtime: cannot open the truth file " + path);
+    sfa::TruthTable table;
+    if (!table.read(in, path, names, &err)) die("realtime: " + err);
+    return table;
+}
+
+// the class a decision stands for: 'T' on target, 'O' off target, 'N' none (dec: sfa_target_decide's 'A', 'U' or 0)
+char class_of_decision(int dec, int target_mode) { return !dec ? 'N' : (((dec == 'A') == (target_mode == 0)) ? 'T' : 'O'); }
+
 // the three tags a line gains with --targets (Python twin: realtime.target_tags): class, action, the per-event margin it had
 std::string target_tags(const sfa_class_t &c, const RealtimeOpt &r) {
     const int dec = sfa_target_decide(&c, r.target_mode, r.min_events, r.margin);
-    const char tc = !dec ? 'N' : (((dec == 'A') == (r.target_mode == 0)) ? 'T' : 'O');
+    const char tc = class_of_decision(dec, r.target_mode);
     const double mine = r.target_mode == 0 ? c.on_score : c.off_score, other = r.target_mode == 0 ? c.off_score : c.on_score;
     const double tm = c.n_events > 0 ? (other - mine) / static_cast<double>(c.n_events) : NAN;
     char buf[96];
@@ -229,6 +251,8 @@ struct Report {
 int realtime_run(int argc, char **argv, double t0) {
     RealtimeOpt r = parse_realtime_options(argc, argv);
     Opt &o = r.o;
+    const bool with_truth = !r.truth.empty();
+    const sfa::TruthTable truth = with_truth ? read_truth(r.truth, o.fasta) : sfa::TruthTable();
     sfa::Blow5Reader reader;
     if (!reader.open(o.blow5)) die(reader.error());
     detect_chemistry(reader, &o);
@@ -249,9 +273,10 @@ int realtime_run(int argc, char **argv, double t0) {
     if (r.candidates > 0 && sfa_session_candidates_config(se, r.candidates) != SFA_OK) die(std::string("session: ") + sfa_last_error());
     const bool targets = !r.targets.empty();
     std::vector<std::string> group_names;
+    std::vector<sfa_target_t> t;  // (--truth reads both lists again at every decision)
+    std::vector<sfa_group_target_t> gt;
     if (targets) {
-        std::vector<sfa_group_target_t> gt;
-        const std::vector<sfa_target_t> t = read_targets(r.targets, ref, r.by_name ? &gt : nullptr, r.by_name ? &group_names : nullptr);
+        t = read_targets(r.targets, ref, r.by_name ? &gt : nullptr, r.by_name ? &group_names : nullptr);
         if (t.empty()) die("realtime: the targets file " + r.targets + " holds no interval");
         if (sfa_session_targets(se, t.data(), static_cast<int32_t>(t.size())) != SFA_OK) die(std::string("targets: ") + sfa_last_error());
         if (r.by_name && sfa_session_target_groups(se, gt.data(), static_cast<int32_t>(gt.size()), static_cast<int32_t>(group_names.size())) != SFA_OK)
@@ -291,6 +316,12 @@ int realtime_run(int argc, char **argv, double t0) {
     std::vector<sfa_open_class_t> ocls(r.quota > 0 ? C : 0);
     std::vector<int32_t> on_group(r.quota > 0 ? C : 0);
     std::vector<int64_t> held;
+    replay::TruthMarks marks;  // --truth: per entry of the tick
+    std::vector<const sfa::TruthRecord *> truth_of(with_truth ? C : 0);
+    std::vector<int64_t> len_now(with_truth ? C : 0);
+    if (with_truth) marks.tt.assign(C, 'N'), marks.tv.assign(C, 'N');
+    sfa::TruthAccount account;
+    const int32_t n_targets = static_cast<int32_t>(t.size()), n_groups = static_cast<int32_t>(group_names.size());
     std::vector<uint64_t> span_a(C), span_b(C);
     std::vector<sfa_result_t> cand(r.candidates > 0 ? 4 * static_cast<size_t>(C) : 0);
     std::string text(4096, '\0');
@@ -341,6 +372,12 @@ int realtime_run(int argc, char **argv, double t0) {
             }
             line[i] = reason[i] && s.mapped;
             if (reason[i]) decided_slot.push_back(slot[i]);
+            if (reason[i] && with_truth) {  // one look-up per read, at its decision
+                truth_of[i] = truth.find(ch.rec[slot[i]].read_id);
+                marks.tt[i] = sfa::truth_class_of(truth_of[i], t.data(), n_targets);
+                marks.tv[i] = sfa::truth_verdict(class_of_decision(sfa_target_decide(&cls[i], r.target_mode, r.min_events, r.margin), r.target_mode), marks.tt[i]);
+                len_now[i] = sch.length(slot[i]);
+            }
         }
         const int32_t nd = static_cast<int32_t>(decided_slot.size());
         if (nd > 0) {
@@ -373,6 +410,17 @@ int realtime_run(int argc, char **argv, double t0) {
                     if (action[i] == 'A' && h.best >= 0) ++rep.group_accepted[h.best];
                 }
                 if (r.quota > 0) tail += replay::quota_tags(on_group[i], group_names);
+                if (with_truth) {
+                    tail += replay::truth_tags(marks.tt[i], marks.tv[i]);
+                    if (r.by_name) {  // the line's tg names the head's best entry, the background for none
+                        const sfa::TruthRecord *w = truth_of[i];
+                        const int32_t best = heads[head_of[i]].best, said = best >= 0 && best < n_groups ? best : n_groups;
+                        const int32_t true_group = w ? sfa::truth_group(gt.data(), static_cast<int32_t>(gt.size()), n_groups, w->contig, w->begin, w->end) : -1;
+                        const char gv = sfa::truth_group_verdict(said, true_group);
+                        tail += replay::truth_group_tags(true_group, gv, group_names);
+                        account.note_group(gv);
+                    }
+                }
                 // the primary, then the channel's valid candidates, best first: same span, same tags
                 for (int32_t m = 0; m <= r.candidates; ++m) {
                     const sfa_result_t &w = m == 0 ? rows[i] : cand[4 * static_cast<size_t>(k) + (m - 1)];
@@ -396,12 +444,16 @@ int realtime_run(int argc, char **argv, double t0) {
         if (targets) {
             std::vector<int64_t> sent_now(n);
             for (int32_t i = 0; i < n; ++i) sent_now[i] = sch.sent(slot[i]);
-            sch.end_tick(reason, line, ch, &action, &held, r.quota > 0 ? &on_group : nullptr);
+            sch.end_tick(reason, line, ch, &action, &held, r.quota > 0 ? &on_group : nullptr, with_truth ? &marks : nullptr);
             for (int32_t i = 0; i < n; ++i) {
                 if (!reason[i]) continue;
                 const int a = action[i] == 'A' ? 0 : action[i] == 'U' ? 1 : 2;
                 ++rep.act_reads[a];
                 rep.act_samples[a] += sent_now[i] + held[i];
+                if (with_truth) {
+                    const sfa::TruthRecord *w = truth_of[i];
+                    account.note(marks.tt[i], w && sfa::truth_edge(t.data(), n_targets, w->contig, w->begin, w->end), action[i], marks.tv[i], sent_now[i], held[i], len_now[i]);
+                }
             }
         } else {
             sch.end_tick(reason, line, ch);
@@ -412,6 +464,7 @@ int realtime_run(int argc, char **argv, double t0) {
     if (targets) rep.print_targets();
     if (r.by_name) rep.print_groups(group_names, r.quota, &sch);
     if (o.verbosity >= 3) rep.print(r, ch, ch.sampling_rate > 0 ? static_cast<double>(r.chunk_samples) / ch.sampling_rate : 0.0);
+    if (with_truth) fputs(account.format(r.by_name).c_str(), stderr);
     return 0;
 }
 

@@ -22,6 +22,10 @@
 //             `decide` line -- for the ticks that follow: the run asks for a tick's classes under the bitmap as it stood when the
 //             tick began, so a tick does not depend on the order of its decisions and a group may overshoot by the reads accepted in
 //             its closing tick.  Proceeding reads ('P') are not credited
+//   truth     only with --truth (end_tick's `truth`; truth_rules.hpp holds the rules, nothing of them is restated here): behind every
+//             `decide` line one line `verdict ch=C read=R tt=X tv=Y sent=S` -- the read's true class, the verdict of its decided
+//             class and the samples sent, the decide line's own.  Truth changes no decision: the trace without its verdict lines is
+//             the trace of the run without --truth
 //   the end   no channel is busy
 #pragma once
 #include <cmath>
@@ -90,6 +94,19 @@ inline std::string quota_tags(int32_t on_group, const std::vector<std::string> &
     return "\tog:Z:" + (on_group >= 0 && static_cast<size_t>(on_group) < names.size() ? names[static_cast<size_t>(on_group)] : std::string("*"));
 }
 
+// ---- with --truth: the two tags a line gains behind all others, and with --by-name two more (Python twin: realtime.truth_tags) ----
+// tt:A: the read's true class (T, O; N: the read has no truth), tv:A: the verdict of the line's tc (C, W; N: either is N);
+// tn:Z: the true group's name (`*`: the background, `.`: the read has no truth), gv:A: the verdict of the line's tg
+inline std::string truth_tags(char tt, char tv) { return std::string("\ttt:A:") + tt + "\ttv:A:" + tv; }
+inline std::string truth_group_tags(int32_t true_group, char gv, const std::vector<std::string> &names) {
+    const std::string name = true_group < 0 ? "." : (static_cast<size_t>(true_group) < names.size() ? names[static_cast<size_t>(true_group)] : "*");
+    return "\ttn:Z:" + name + "\tgv:A:" + gv;
+}
+// what the schedule prints of a tick's decided reads under --truth: per entry of begin_tick() (undecided entries are not read)
+struct TruthMarks {
+    std::vector<char> tt, tv;
+};
+
 // one channel's part of a tick's call
 struct Entry {
     int32_t channel;
@@ -142,10 +159,10 @@ class Schedule {
 
     // reason[i] (decide()) and line[i] for entry i of begin_tick(); decided channels take the next records, lowest channel first.
     // With targets, action[i] (action_of) says what happens to a decided read; *held (if given) receives the samples a read
-    // decided in this tick is held for.
+    // decided in this tick is held for.  With truth, a `verdict` line follows every `decide` line.
     template <class Source>
     void end_tick(const std::vector<char> &reason, const std::vector<char> &line, Source &src, const std::vector<char> *action = nullptr, std::vector<int64_t> *held = nullptr,
-                  const std::vector<int32_t> *on_group = nullptr) {
+                  const std::vector<int32_t> *on_group = nullptr, const TruthMarks *truth = nullptr) {
         if (!targets_ || !action) {
             for (size_t i = 0; i < entries_.size(); ++i) {
                 if (!reason[i]) continue;
@@ -170,6 +187,7 @@ class Schedule {
             Channel &k = ch_[e.channel];
             if (trace_)
                 fprintf(trace_, "tick %ld decide ch=%d read=%ld reason=%c line=%d sent=%ld\n", (long)tick_, e.channel, (long)e.read, reason[i], line[i] ? 1 : 0, (long)k.sent);
+            if (trace_ && truth) fprintf(trace_, "tick %ld verdict ch=%d read=%ld tt=%c tv=%c sent=%ld\n", (long)tick_, e.channel, (long)e.read, truth->tt[i], truth->tv[i], (long)k.sent);
             if (book_ && on_group && (*action)[i] == 'A' && line[i] && book_->note_accept((*on_group)[i])) {  // this read filled its group's quota
                 const int32_t g = (*on_group)[i];
                 closed_at_[static_cast<size_t>(g)] = tick_;

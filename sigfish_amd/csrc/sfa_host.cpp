@@ -16,6 +16,7 @@
 #include "host/events.hpp"
 #include "host/refio.hpp"
 #include "host/sam.hpp"
+#include "truth_rules.hpp"
 
 extern "C" void sfa_set_error_(const char *msg);
 
@@ -414,5 +415,26 @@ int sfa_inflate_zlib_pair(const uint8_t *in0, size_t n0, const uint8_t *in1, siz
     }
     return SFA_OK;
 }
+
+}  // extern "C"
+
+// ---- truth: the rules of truth_rules.hpp behind the C ABI (null lists read as empty) ----
+extern "C" {
+
+int sfa_truth_class(const sfa_target_t *targets, int32_t n, int32_t contig, int32_t begin, int32_t end) {
+    return sfa::truth_class(targets, targets ? n : 0, contig, begin, end);
+}
+
+int sfa_truth_edge(const sfa_target_t *targets, int32_t n, int32_t contig, int32_t begin, int32_t end) {
+    return sfa::truth_edge(targets, targets ? n : 0, contig, begin, end) ? 1 : 0;
+}
+
+int32_t sfa_truth_group(const sfa_group_target_t *targets, int32_t n, int32_t n_groups, int32_t contig, int32_t begin, int32_t end) {
+    return sfa::truth_group(targets, targets ? n : 0, n_groups, contig, begin, end);
+}
+
+int sfa_truth_verdict(int decided, int truth) { return sfa::truth_verdict(decided, truth); }
+
+int sfa_truth_group_verdict(int32_t decided, int32_t truth) { return sfa::truth_group_verdict(decided, truth); }
 
 }  // extern "C"

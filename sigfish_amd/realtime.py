@@ -37,6 +37,12 @@ ticks, the same calls, the same lines.  The schedule counts ticks, never seconds
             ascending channel order (api.QuotaBook, in Schedule.end_tick); the credit that fills a quota closes the group from the
             next tick on (trace: `close group=NAME accepted=K`), so a group may overshoot by the reads accepted in its closing
             tick.  Proceeding reads are not credited.  Lines gain og:Z:<name of on_group, * for none> (quota_tags)
+  truth     truth= (--truth FILE.paf; needs targets=): {read id: (contig, begin, end)} as api.read_truth returns it.  Every decided read
+            is looked up once, at its decision: its true class (api.truth_class: 'T' when its interval shares a base with a target,
+            'O' when not or when it belongs nowhere, 'N' when it has no truth) and the verdict of the decided class
+            (api.truth_verdict: 'C', 'W', 'N'); with by_name the true group and the verdict of the line's tg.  Lines gain tt:A / tv:A
+            (tn:Z / gv:A) behind all other tags (truth_tags), the trace one `verdict ch=C read=R tt=X tv=Y sent=S` line behind every
+            `decide` line, summary["truth"] the account (format_truth_summary).  Truth changes no decision
   after it  decided channels are reset in one call and take the next unread reads, lowest channel first, from tick t + 1 on
 """
 import numpy as np
@@ -130,11 +136,11 @@ class Schedule:
                 self.trace.append(f"tick {self.tick} send ch={c} read={r} first={self.entries[-1][2]} n={n} end={int(n < self.chunk)}")
         return self.entries
 
-    def end_tick(self, reason, line, source, action=None, on_group=None):
-        """action (with targets): action_of per entry; on_group (with a quota): the open-class record's per entry; -> samples every
-        entry's read is held for (0 without targets)"""
+    def end_tick(self, reason, line, source, action=None, on_group=None, truth=None):
+        """action (with targets): action_of per entry; on_group (with a quota): the open-class record's per entry; truth (with
+        truth): (tt, tv) per entry, None for an undecided one; -> samples every entry's read is held for (0 without targets)"""
         if self.targets and action is not None:
-            return self._end_tick_targets(reason, line, source, action, on_group)
+            return self._end_tick_targets(reason, line, source, action, on_group, truth)
         for (c, r, _, _, _), why, ln in zip(self.entries, reason, line):
             if not why:
                 continue
@@ -147,7 +153,7 @@ class Schedule:
         self.tick += 1
         return [0] * len(self.entries)
 
-    def _end_tick_targets(self, reason, line, source, action, on_group=None):
+    def _end_tick_targets(self, reason, line, source, action, on_group=None, truth=None):
         held = [0] * len(self.entries)
         freed = [False] * len(self.read)
         for c in range(len(self.read)):  # holds of earlier ticks: one tick less, the last one frees
@@ -159,6 +165,8 @@ class Schedule:
                 continue
             if self.trace is not None:
                 self.trace.append(f"tick {self.tick} decide ch={c} read={r} reason={why} line={int(bool(ln))} sent={self.sent[c]}")
+                if truth is not None:
+                    self.trace.append(f"tick {self.tick} verdict ch={c} read={r} tt={truth[i][0]} tv={truth[i][1]} sent={self.sent[c]}")
             if self.book is not None and on_group is not None and action[i] == "A" and ln and self.book.note_accept(int(on_group[i])):
                 g = int(on_group[i])  # this read filled its group's quota
                 self.closed_at[g] = self.tick
@@ -193,7 +201,7 @@ AUTO_START_MAX_SAMPLES, MAX_SKIP_EVENTS = 131072, 4096  # the defaults of --auto
 
 
 def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False, resweep=False,
-           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None, by_name=False, quota=None):
+           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None, by_name=False, quota=None, truth=None):
     """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
     candidates=1..4 (--candidates): an eighth element, RESULT_DTYPE[4], the channel's candidates at the decision, best first.
     A `session` of the caller's is taken as it is, in this as in its raw mode: it must keep that many candidates already
@@ -224,8 +232,14 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     group=(head, names).  summary gains ("group", index) -> accepted reads whose best entry that is.
     quota=N (--quota N; needs by_name=True and mode=ENRICH, N >= 1): see `quota` above.  An item's class record is the open-class
     record's `cls`, and the item gains, behind the head, the record's on_group (format_line takes quota=(on_group, names)).
-    summary gains "quota" -> N and ("closed_at", index) -> the tick whose credit closed the group."""
+    summary gains "quota" -> N and ("closed_at", index) -> the tick whose credit closed the group.
+    truth={read id: (contig, begin, end)} (--truth FILE.paf; api.read_truth; needs targets=): see `truth` above.  An item gains, behind
+    the on_group (or whatever came last of the class record, the head and it), a dict with tt, tv and edge, and with by_name
+    true_group (None: the read has no truth) and gv (None: the read has no line) -- format_line takes it as truth=(that dict, names).
+    summary gains "truth", the account format_truth_summary prints."""
     auto = skip < 0
+    if truth is not None and targets is None:  # (before any session exists)
+        raise api.SfaError("replay: truth= checks target decisions: pass targets= with mode= and margin= with it")
     if quota is not None:  # (before any session exists, each with the fix)
         if not by_name:
             raise api.SfaError("replay: quota counts accepted reads per named group: pass targets=(group targets, names), by_name=True and mode=ENRICH with it")
@@ -278,6 +292,11 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
         sch.set_quota(book, group_names)
         if summary is not None:
             summary["quota"] = int(quota)
+    account = None
+    if truth is not None:
+        account = new_truth_account(by_name)
+        if summary is not None:
+            summary["truth"] = account
     own = session is None
     se = aligner.session(channels, resweep=resweep, spread=spread) if own else session
     try:
@@ -316,6 +335,16 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                 reason = [decide(rows[i], info[i], min_events, min_mapq) for i in range(len(es))]
             line = [bool(why) and mapped(rows[i]) for i, why in enumerate(reason)]
             decided = [i for i, why in enumerate(reason) if why]
+            marks = None
+            if truth is not None:  # one look-up per read, at its decision
+                marks = [None] * len(es)
+                for i in decided:
+                    where = truth.get(on[slots[i]][1])
+                    tt = "N" if where is None else api.truth_class(targets, *where)
+                    marks[i] = dict(tt=tt, tv=api.truth_verdict(class_of_decision(dec[i], mode), tt), edge=where is not None and api.truth_edge(targets, *where), length=sch.len[slots[i]])
+                    if by_name:
+                        marks[i]["true_group"] = None if where is None else api.truth_group(group_targets, len(group_names), *where)
+                        marks[i]["gv"] = None
             if decided:
                 d_slots = [slots[i] for i in decided]
                 a, b = se.query_span(d_slots)
@@ -336,6 +365,11 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                     lined = [i for i in decided if line[i]]
                     if lined:
                         heads = dict(zip(lined, se.group_bests([slots[i] for i in lined])[1]))
+                    if marks is not None:  # the line's tg names the head's best entry, the background for none
+                        for i in lined:
+                            best = int(heads[i]["best"])
+                            marks[i]["gv"] = api.truth_group_verdict(best if 0 <= best < len(group_names) else len(group_names), marks[i]["true_group"])
+                            account["groups"][marks[i]["gv"]] += 1
                     if summary is not None:
                         for i in lined:
                             if action[i] == "A" and heads[i]["best"] >= 0:
@@ -350,6 +384,8 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                         item += (heads[i].copy() if i in heads else None,)
                     if book is not None:
                         item += (int(on_group[i]),)
+                    if marks is not None:
+                        item += (marks[i],)
                     if auto:
                         item += (au[k].copy(),)
                     if sam:
@@ -358,7 +394,10 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                                       cand_maps=maps[per * k + 1:per * k + 5] if candidates else None),)
                     yield item
                 se.reset(d_slots)
-            held = sch.end_tick(reason, line, src, action, on_group)
+            held = sch.end_tick(reason, line, src, action, on_group, None if marks is None else [m and (m["tt"], m["tv"]) for m in marks])
+            if marks is not None:
+                for i in decided:
+                    note_truth(account, marks[i]["tt"], marks[i]["edge"], action[i], marks[i]["tv"], sch_sent[i], held[i], marks[i]["length"])
             if book is not None and summary is not None:
                 for g, at in enumerate(sch.closed_at):
                     if at >= 0:
@@ -379,12 +418,17 @@ def _map_or_none(m):
     return m.copy() if len(m) and m[0, 0] != np.iinfo(np.int32).min else None
 
 
+def class_of_decision(decision, mode):
+    """the class a decision stands for: 'T' on target, 'O' off target, 'N' none (decision: api.target_decide's 'A', 'U' or None)"""
+    return "N" if decision is None else ("T" if (decision == "A") == (mode == api.ENRICH) else "O")
+
+
 def target_tags(cls, mode, min_events, margin):
     """tc:A:<T|O|N> ac:A:<A|U|P> tm:f:<(other - mine) / n_events> for a CLASS_DTYPE record at a decision: the target class (N: no
     class decision), the action (P: the read proceeds) and the per-event margin it had -- mine is the on-target score under
     ENRICH and the off-target score under DEPLETE; nan when it is undefined (both classes empty, no events)."""
     dec = api.target_decide(cls, mode, min_events, margin)
-    tc = "N" if dec is None else ("T" if (dec == "A") == (mode == api.ENRICH) else "O")
+    tc = class_of_decision(dec, mode)
     on, off, n = float(cls["on_score"]), float(cls["off_score"]), int(cls["n_events"])
     mine, other = (on, off) if mode == api.ENRICH else (off, on)
     with np.errstate(all="ignore"):
@@ -409,6 +453,61 @@ def quota_tags(on_group, names):
     return "\tog:Z:" + (names[on_group] if 0 <= on_group < len(names) else "*")
 
 
+def truth_tags(marks, names=None):
+    """tt:A:<true class T|O, N: the read has no truth> tv:A:<verdict of the line's tc: C|W|N> for the truth dict of a replay item
+    (replay::truth_tags); with names (by_name) also tn:Z:<the true group's name, * for the background, . for a read without truth>
+    gv:A:<verdict of the line's tg> (replay::truth_group_tags)."""
+    out = f"\ttt:A:{marks['tt']}\ttv:A:{marks['tv']}"
+    if names is not None:
+        g = marks["true_group"]
+        out += "\ttn:Z:" + ("." if g is None or g < 0 else (names[g] if g < len(names) else "*")) + f"\tgv:A:{marks['gv']}"
+    return out
+
+
+def new_truth_account(groups=False):
+    """the account of a replay with truth= (the twin of truth_rules.hpp's TruthAccount; integer sums only): per true class reads,
+    samples sent / held / in the file, edge reads, counts by action and by verdict; with groups the group verdicts"""
+    acc = {c: dict(reads=0, sent=0, held=0, file=0, edge=0, A=0, U=0, P=0, C=0, W=0, N=0) for c in "TON"}
+    acc["groups"] = dict(C=0, W=0, N=0) if groups else None
+    return acc
+
+
+def note_truth(account, tt, edge, action, tv, sent, held, in_file):
+    """TruthAccount::note: one decided read"""
+    c = account[tt if tt in ("T", "O") else "N"]
+    c["reads"] += 1
+    c["sent"] += int(sent)
+    c["held"] += int(held)
+    c["file"] += int(in_file)
+    c["edge"] += int(bool(edge))
+    c[action if action in ("A", "U") else "P"] += 1
+    c[tv if tv in ("C", "W") else "N"] += 1
+
+
+def truth_enrichment(account):
+    """((on-target sequenced, all sequenced), (on-target in the file, all in the file), enrichment by signal or None) over the reads
+    that have truth; sequenced = sent + held.  The ratio is formed only when neither divisor is 0 (TruthAccount::format)."""
+    seq = [account[c]["sent"] + account[c]["held"] for c in "TO"]
+    fil = [account[c]["file"] for c in "TO"]
+    ok = sum(seq) > 0 and fil[0] > 0
+    return (seq[0], sum(seq)), (fil[0], sum(fil)), (float(seq[0]) * float(sum(fil))) / (float(sum(seq)) * float(fil[0])) if ok else None
+
+
+def format_truth_summary(account):
+    """the `truth:` lines `sigfish-amd realtime --truth` ends its stderr with (TruthAccount::format), from summary["truth"]"""
+    out = ""
+    for k in "TON":
+        c = account[k]
+        out += ("[realtime] truth: %s reads=%d sent=%d held=%d file=%d A=%d U=%d P=%d C=%d W=%d N=%d edge=%d\n"
+                % (k, c["reads"], c["sent"], c["held"], c["file"], c["A"], c["U"], c["P"], c["C"], c["W"], c["N"], c["edge"]))
+    if account["groups"] is not None:
+        out += "[realtime] truth: groups C=%d W=%d N=%d\n" % (account["groups"]["C"], account["groups"]["W"], account["groups"]["N"])
+    (s_on, s_all), (f_on, f_all), ratio = truth_enrichment(account)
+    quotient = lambda a, b: "%.4f" % (float(a) / float(b)) if b > 0 else "-"
+    return out + ("[realtime] truth: on-target share of the sequenced samples (sent + held) %d / %d = %s, of the file's samples %d / %d = %s, enrichment by signal %s\n"
+                  % (s_on, s_all, quotient(s_on, s_all), f_on, f_all, quotient(f_on, f_all), "-" if ratio is None else "%.4f" % ratio))
+
+
 def format_group_summary(summary, names):
     """the lines `sigfish-amd realtime --by-name` ends its stderr with: accepted reads per best entry, the background last; with a
     quota (summary["quota"]) the named groups' lines gain quota=N closed_at=<tick, - for a group still open>"""
@@ -431,22 +530,23 @@ def auto_tags(auto):
     return f"\tqs:i:{int(auto['skip'])}\tas:A:{how}"
 
 
-def format_line(read_id, n_samples, names, seq_lengths, row, info, span, reason, auto=None, target=None, group=None, quota=None):
+def format_line(read_id, n_samples, names, seq_lengths, row, info, span, reason, auto=None, target=None, group=None, quota=None, truth=None):
     """The line `sigfish-amd realtime` prints for a decision, or "" when its row is not mapped: paf_row (query_size as dtw passes
     it, last query event - first), then ne:i:<query events> ns:i:<samples sent> dc:A:<reason>.  n_samples: of the whole read.
     auto: the decision's automatic start (replay with skip = -1): qs:i and as:A follow the three tags.
     target: (class record, mode, min_events, margin) of a replay with targets=: target_tags() follow.
     group: (head record, group names) of a replay with by_name=True: group_tags() follow those.
-    quota: (on_group, group names) of a replay with quota=: quota_tags() follows those."""
+    quota: (on_group, group names) of a replay with quota=: quota_tags() follows those.
+    truth: (truth dict, group names or None) of a replay with truth=: truth_tags() follow all others."""
     if not mapped(row):
         return ""
     rid = int(row["rid"])
     base = api.paf_row(row, read_id, names[rid], span[0], span[1], int(info["q_events"]) - 1, int(n_samples), int(seq_lengths[rid]))
-    tail = ("" if auto is None else auto_tags(auto)) + ("" if target is None else target_tags(*target)) + ("" if group is None else group_tags(*group)) + ("" if quota is None else quota_tags(*quota))
+    tail = ("" if auto is None else auto_tags(auto)) + ("" if target is None else target_tags(*target)) + ("" if group is None else group_tags(*group)) + ("" if quota is None else quota_tags(*quota)) + ("" if truth is None else truth_tags(*truth))
     return f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}{tail}\n"
 
 
-def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, span, reason, target=None, group=None, quota=None):
+def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, span, reason, target=None, group=None, quota=None, truth=None):
     """The candidate lines that follow a decision's primary line under --candidates: one per valid row of `cand`, best first, each
     the tp:A:S line of paf_row_ex with the primary's span and query_size and the primary's three tags; "" when the primary has no
     line."""
@@ -458,7 +558,7 @@ def format_candidates(read_id, n_samples, names, seq_lengths, row, cand, info, s
             continue
         rid = int(r["rid"])
         base = api.paf_row(r, read_id, names[rid], span[0], span[1], int(info["q_events"]) - 1, int(n_samples), int(seq_lengths[rid]), tp="S")
-        out.append(f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}{'' if target is None else target_tags(*target)}{'' if group is None else group_tags(*group)}{'' if quota is None else quota_tags(*quota)}\n")
+        out.append(f"{base[:-1]}\tne:i:{int(info['q_events'])}\tns:i:{int(info['n_samples'])}\tdc:A:{reason}{'' if target is None else target_tags(*target)}{'' if group is None else group_tags(*group)}{'' if quota is None else quota_tags(*quota)}{'' if truth is None else truth_tags(*truth)}\n")
     return "".join(out)
 
 

@@ -223,6 +223,19 @@ def make_dna_raw_reads(records, level_mean, k, n_reads, seed=0, samples=(2000, 9
       flat    one level, no noise: the detector finds no event
     rna: direct RNA instead -- a mapped read follows the forward strand only, from its start k-mer BACKWARDS (the molecule passes
     the pore 3' to 5', which is why the reference takes the query reversed, src/sigfish.c:860-863)."""
+    return _dna_raw_reads(records, level_mean, k, n_reads, seed, samples, dwell, noise, kinds, meta, rna)[0]
+
+
+def make_dna_raw_reads_truth(records, level_mean, k, n_reads, seed=0, samples=(2000, 9000), dwell=(6, 13), noise=1.5, kinds=("mapped",), meta=R9_DNA_META, rna=False):
+    """make_dna_raw_reads that knows where its reads came from -> (reads, truth): the same reads for the same arguments, and per read
+    (contig index, begin, end, strand) or None for the kinds that belong nowhere (random, stalled, flat).  [begin, end) are the bases
+    the k-mers the read was built from cover ON THE FORWARD STRAND, also for a '-' read: the k-mers whose level reached at least one
+    sample, so the interval ends where the read's samples do; a read that runs off its contig's end (and goes on with random
+    k-mers) is clipped to the contig."""
+    return _dna_raw_reads(records, level_mean, k, n_reads, seed, samples, dwell, noise, kinds, meta, rna)
+
+
+def _dna_raw_reads(records, level_mean, k, n_reads, seed, samples, dwell, noise, kinds, meta, rna):
     rng = np.random.default_rng(seed)
     lv = np.asarray(level_mean, np.float32)
     code = np.full(256, 0, np.int64)
@@ -238,18 +251,26 @@ def make_dna_raw_reads(records, level_mean, k, n_reads, seed=0, samples=(2000, 9
     fwd = [kmers(s.upper()) for _, s in records]
     rev = [kmers(s.upper().translate(comp)[::-1]) for _, s in records]
     lens = np.array([len(x) for x in fwd], np.float64)
-    out = []
+    out, truth = [], []
     for r in range(n_reads):
         kind = kinds[r % len(kinds)]
         n = int(rng.integers(samples[0], samples[1] + 1))
         d = rng.integers(dwell[0], dwell[1], n // dwell[0] + 2)
         idx = rng.integers(0, len(lv), len(d))
+        where = None
         if kind == "mapped":
             c = int(rng.choice(len(fwd), p=lens / lens.sum()))
-            along = fwd[c][::-1] if rna else (rev if rng.integers(0, 2) else fwd)[c]
+            minus = False if rna else bool(rng.integers(0, 2))
+            along = fwd[c][::-1] if rna else (rev if minus else fwd)[c]
             at = int(rng.integers(0, max(len(along) - 100, 1)))
             m = min(len(along) - at, len(d))
             idx[:m] = along[at:at + m]
+            # k-mers at .. last of `along` reach a sample; k-mer i of fwd covers bases [i, i + k), k-mer i of rev and of the RNA
+            # order is k-mer len - 1 - i of fwd
+            last = at + min(m, int(np.searchsorted(np.cumsum(d), n)) + 1) - 1
+            nk = len(along)
+            where = (c, nk - 1 - last, nk - 1 - at + k, "-" if minus else "+") if (rna or minus) else (c, at, last + k, "+")
+        truth.append(where)
         pa = np.full(n, lv[idx[0]], np.float64) if kind == "flat" else np.repeat(lv[idx].astype(np.float64), d)[:n]
         if kind != "flat":
             pa = pa + rng.normal(0, noise, n)
@@ -257,7 +278,20 @@ def make_dna_raw_reads(records, level_mean, k, n_reads, seed=0, samples=(2000, 9
             pa[int(rng.integers(200, 331)):] = lv[idx[-1]]
         raw = np.clip(np.round(pa * meta["digitisation"] / meta["range"] - meta["offset"]), -32768, 32767).astype(np.int16)
         out.append((f"raw_{seed}_{r}_{kind}", meta["digitisation"], meta["offset"], meta["range"], meta["sampling_rate"], raw))
-    return out
+    return out, truth
+
+
+def write_truth_paf(path, reads, truth, names, lengths):
+    """The truth of make_dna_raw_reads_truth as the PAF file `sigfish-amd realtime --truth` and api.read_truth take: one line per
+    read -- read id, samples, 0, samples, strand, contig name, contig length, begin, end, end - begin, end - begin, 60 -- and
+    `*` for the contig of a read that belongs nowhere (its coordinates 0).  names / lengths: the contigs' names and base counts."""
+    with open(path, "w") as f:
+        for (rid, _, _, _, _, raw), where in zip(reads, truth):
+            if where is None:
+                f.write(f"{rid}\t{len(raw)}\t0\t{len(raw)}\t*\t*\t0\t0\t0\t0\t0\t0\n")
+            else:
+                c, b, e, strand = where
+                f.write(f"{rid}\t{len(raw)}\t0\t{len(raw)}\t{strand}\t{names[c]}\t{int(lengths[c])}\t{b}\t{e}\t{e - b}\t{e - b}\t60\n")
 
 
 def write_blow5(path, reads, attrs=(("experiment_type", "genomic_dna"), ("sequencing_kit", "unknown"))):
