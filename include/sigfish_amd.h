@@ -360,6 +360,39 @@ int sfa_session_classes(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_cl
  * unit.  Nobody has measured a good margin: there is no default. */
 int sfa_target_decide(const sfa_class_t *cls, int32_t mode, int32_t min_events, float margin);
 
+/* ---- coverage caps: targets that close where they are covered deeply enough ------------------------------------------------------
+ * The session keeps a depth track per contig on the device: one uint32 per coordinate a row of the contig can report, ref_length + 1
+ * entries, entry x - ref_st_offset for coordinate x, both strands sharing it (depth belongs to the position).  The LIVE mask is
+ * derived from the mask of sfa_session_targets (the base mask, which is kept) and the tracks: a column is live when its bit of the
+ * base mask is set and the depth of the coordinate the column reports (as for the mask above) lies below the cap.  While a cap is
+ * set, sfa_session_classes reads the live mask -- a closed coordinate is OFF target on both strands -- and
+ * sfa_session_target_columns reports the live columns.  Memory: 4 bytes per coordinate and a second mask per SESSION
+ * (sfa_session_coverage_bytes), not counted by sfa_session_bytes; a session that never sets a cap allocates nothing and launches
+ * what it launched before.  Depth does not saturate: with caps of at most 2^30 and at most 2^20 intervals a call, a coordinate
+ * wraps only after 2^32 additions, 4096 calls that each cover it 2^20 times -- no run of the front ends, which add at most one
+ * interval per accepted read, comes near.
+ * On a spread session _config and _add go to every sub-session (every shard holds the same mask and tracks); _depth is answered
+ * by shard 0, and open_columns is shard 0's count, not a sum. */
+
+/* cap >= 1 switches the feature on (depth zeroed, live mask = base mask); cap = 0 switches it off and frees both buffers.
+ * Needs targets (sfa_session_targets); allowed at any time, as the mask does not depend on the slots.  sfa_session_targets on a
+ * session with a cap rebuilds the base mask and derives the live mask from the kept depth; with n = 0 it drops the cap too.
+ * SFA_EINVAL: a null session, cap < 0 or cap > 2^30, no targets. */
+int sfa_session_coverage_config(sfa_session_t *s, int32_t cap);
+/* depth += 1 over every interval (sfa_target_t: contig, [begin, end) in the coordinates rows report; the part of an interval
+ * below ref_st_offset, which no row reports, counts nowhere), then the live mask is derived again; *open_columns (may be NULL)
+ * receives the live on-target columns.  Intervals may overlap each other; n = 0 adds nothing and derives the mask.  One call,
+ * blocking, on the context's stream; sfa_profile_t.class_ms is its device time.
+ * SFA_EINVAL, before anything is written: null arguments, no cap set, more than 2^20 intervals, an interval sfa_session_targets
+ * would refuse as a target (same messages). */
+int sfa_session_coverage_add(sfa_session_t *s, const sfa_target_t *iv, int32_t n, int64_t *open_columns);
+/* a contig's track back: out[0 .. ref_length + 1).  SFA_EINVAL: null arguments, no cap set, a contig out of range, n other than
+ * ref_length + 1. */
+int sfa_session_coverage_depth(sfa_session_t *s, int32_t contig, uint32_t *out, int32_t n);
+/* Device memory a cap adds to a session of a context made from (ref, flag): 4 bytes per coordinate and the second mask.  Host
+ * arithmetic; 0 for a null or empty reference. */
+size_t sfa_session_coverage_bytes(const sfa_ref_t *ref, int flag);
+
 /* ---- target groups: the best score per named group of targets (WHICH target a read hits) --------------------------------------
  * A group target is a target with a group id in [0, n_groups), 1 <= n_groups <= 1023.  Every column of a slot's row carries one
  * label: the lowest group id among the intervals that cover it (covered as for the mask above: the coordinate of an alignment

@@ -97,6 +97,7 @@ SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "
            "sfa_session_targets", "sfa_session_target_columns", "sfa_session_classes", "sfa_target_decide",
            "sfa_session_target_groups", "sfa_session_group_count", "sfa_session_group_bests", "sfa_group_decide",
            "sfa_session_open_classes",
+           "sfa_session_coverage_config", "sfa_session_coverage_add", "sfa_session_coverage_depth", "sfa_session_coverage_bytes",
            "sfa_truth_class", "sfa_truth_edge", "sfa_truth_group", "sfa_truth_verdict", "sfa_truth_group_verdict"]
 
 _lib = None
@@ -238,6 +239,11 @@ def load():
     L.sfa_session_group_bests.argtypes = [vp, i32p, C.c_int32, vp, vp]
     L.sfa_group_decide.argtypes = [C.POINTER(SfaGroupHead), C.c_int32, C.c_float]
     L.sfa_session_open_classes.argtypes = [vp, i32p, C.c_int32, C.POINTER(C.c_uint32), C.c_int32, vp]
+    L.sfa_session_coverage_config.argtypes = [vp, C.c_int32]
+    L.sfa_session_coverage_add.argtypes = [vp, C.POINTER(SfaTarget), C.c_int32, i64p]
+    L.sfa_session_coverage_depth.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint32), C.c_int32]
+    L.sfa_session_coverage_bytes.argtypes = [C.POINTER(SfaRef), C.c_int]
+    L.sfa_session_coverage_bytes.restype = C.c_size_t
     L.sfa_truth_class.argtypes = L.sfa_truth_edge.argtypes = [C.POINTER(SfaTarget), C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.sfa_truth_group.argtypes = [C.POINTER(SfaGroupTarget), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.sfa_truth_group.restype = C.c_int32

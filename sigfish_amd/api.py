@@ -768,6 +768,35 @@ class Session:
                                                 0 if bits is None else len(bits), out.ctypes.data_as(C.c_void_p)), "sfa_session_open_classes")
         return out
 
+    def configure_coverage(self, cap):
+        """A coverage cap on the session's targets (sfa_session_coverage_config): cap >= 1 switches it on -- a depth track per
+        contig on the device, zeroed, and a live mask beside the mask of set_targets -- and 0 switches it off and frees both.  A
+        column is live while it is on target and the depth of the coordinate it reports lies below cap; classes() and
+        target_columns() then read the live mask.  Needs targets; allowed at any time.  session_coverage_bytes() of memory."""
+        self._live()
+        _check(self._L.sfa_session_coverage_config(self._h, int(cap)), "sfa_session_coverage_config")
+
+    def add_coverage(self, intervals):
+        """depth += 1 over every interval ((contig, begin, end) triples or a TARGET_DTYPE array, as for set_targets; they may
+        overlap), then the live mask is derived again (sfa_session_coverage_add) -> the live on-target columns.  An empty list
+        adds nothing and derives the mask."""
+        self._live()
+        t = _targets(intervals)
+        n_open = C.c_int64(0)
+        _check(self._L.sfa_session_coverage_add(self._h, t.ctypes.data_as(C.POINTER(_lib.SfaTarget)) if len(t) else None, len(t), C.byref(n_open)),
+               "sfa_session_coverage_add")
+        return int(n_open.value)
+
+    def coverage(self, contig):
+        """The depth track of `contig` (sfa_session_coverage_depth) -> uint32[ref_length + 1]: entry x - st_offset is the depth of
+        coordinate x, both strands together."""
+        self._live()
+        c = int(contig)
+        n = int(self._al.ref.ref_lengths[c]) + 1 if 0 <= c < len(self._al.ref.ref_lengths) else 1
+        out = np.zeros(n, np.uint32)
+        _check(self._L.sfa_session_coverage_depth(self._h, c, out.ctypes.data_as(C.POINTER(C.c_uint32)), n), "sfa_session_coverage_depth")
+        return out
+
     def reset(self, slots=None):
         """Forget the events of `slots` (None: of every slot); in raw mode the detector, normalisation and scaling as well."""
         self._live()
@@ -1048,6 +1077,13 @@ def session_keep_bytes(n_slots, max_events):
     if b < 0:
         raise SfaError(f"sfa_session_keep_bytes failed ({b}): n_slots and max_events must be positive, their product x 4 below 2^63")
     return b
+
+
+def session_coverage_bytes(ref, flag=0):
+    """Device memory Session.configure_coverage takes for a RefModel (sfa_session_coverage_bytes; host arithmetic): 4 bytes per
+    coordinate (ref_length + 1 per contig) and a second mask of total_columns / 8 bytes."""
+    cref, _keep = ref._as_c()
+    return int(_lib.load().sfa_session_coverage_bytes(C.byref(cref), int(flag)))
 
 
 def session_raw_bytes(n_slots, skip=50, query=2048):

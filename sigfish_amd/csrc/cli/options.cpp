@@ -20,7 +20,7 @@ enum LongOpt {
     O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
     O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
     O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE,
-    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_BY_NAME, O_TRACE, O_QUOTA, O_TRUTH
+    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_BY_NAME, O_TRACE, O_QUOTA, O_TRUTH, O_DEPTH_CAP
 };
 
 const option kLongOptions[] = {
@@ -119,7 +119,7 @@ const option kRealtimeOptions[] = {
     {"candidates", required_argument, 0, O_CANDIDATES}, {"spread", no_argument, 0, O_SPREAD},
     {"targets", required_argument, 0, O_TARGETS}, {"enrich", no_argument, 0, O_ENRICH}, {"deplete", no_argument, 0, O_DEPLETE},
     {"margin", required_argument, 0, O_MARGIN}, {"by-name", no_argument, 0, O_BY_NAME}, {"quota", required_argument, 0, O_QUOTA}, {"trace", required_argument, 0, O_TRACE},
-    {"truth", required_argument, 0, O_TRUTH},
+    {"truth", required_argument, 0, O_TRUTH}, {"depth-cap", required_argument, 0, O_DEPTH_CAP},
     {0, 0, 0, 0}};
 
 void realtime_help(FILE *fp, const RealtimeOpt &r) {
@@ -181,6 +181,12 @@ void realtime_help(FILE *fp, const RealtimeOpt &r) {
                 "                              group closes).  A tick decides under the groups open at its start, so a group may overshoot by the\n"
                 "                              reads accepted in its closing tick.  Lines gain og:Z:<open group of the read's best on-target\n"
                 "                              column, * for none>, the trace `close` lines, the summary quota= and closed_at= [off]\n");
+    fprintf(fp, "   --depth-cap INT            with --targets --enrich (mask targets: not with --by-name / --quota): stop asking for reads over\n"
+                "                              positions that are covered INT times.  At the end of a tick every read accepted in it (ac:A:A) adds\n"
+                "                              the target interval of its PAF line to a depth track on the device, all in one\n"
+                "                              sfa_session_coverage_add call; from the next tick on a target column whose coordinate has depth >=\n"
+                "                              INT counts as off target.  The interval is the aligned window of the decided prefix, not the whole\n"
+                "                              molecule.  The trace gains `cover` lines, the summary the open columns and the bases added [off]\n");
     fprintf(fp, "   --truth FILE.paf           with --targets: check every decision against where the read came from -- a PAF file, column 1 the\n"
                 "                              read id, 6 the contig (* for a read that belongs nowhere), 8 and 9 begin and end; a read that\n"
                 "                              shares a base with a target is truly on target.  Lines gain tt:A:<true class T|O, N: not in the\n"
@@ -200,7 +206,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     FILE *fp_help = stderr;
     int c, li = 0;
     bool secondary = false;
-    const char *recal = nullptr, *candidates = nullptr, *margin = nullptr, *quota = nullptr;
+    const char *recal = nullptr, *candidates = nullptr, *margin = nullptr, *quota = nullptr, *depth_cap = nullptr;
     bool enrich = false, deplete = false;
     while ((c = getopt_long(argc, argv, "p:q:t:v:o:ahV", kRealtimeOptions, &li)) >= 0) {
         switch (c) {
@@ -244,6 +250,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
             case O_BY_NAME: r.by_name = true; break;
             case O_QUOTA: quota = optarg; break;
             case O_TRUTH: r.truth = optarg; break;
+            case O_DEPTH_CAP: depth_cap = optarg; break;
             case O_TRACE: r.trace = optarg; break;
             default: realtime_help(stderr, r); exit(EXIT_FAILURE);
         }
@@ -281,6 +288,15 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
         const long long v = strtoll(quota, &e, 10);
         if (e == quota || *e || v < 1) die("realtime: --quota should be an integer >= 1 (leave the option out for no quota)");
         r.quota = v;
+    }
+    if (depth_cap) {  // (a session of this front end always carries start columns: the interval's other end is there)
+        char *e = nullptr;
+        const long long v = strtoll(depth_cap, &e, 10);
+        if (e == depth_cap || *e || v < 1 || v > (1 << 30)) die("realtime: --depth-cap should be an integer 1..1073741824 (leave the option out for no cap)");
+        if (deplete) die("realtime: --depth-cap with --deplete is not built: a covered position would turn on target; use --enrich");
+        if (r.targets.empty() || !enrich) die("realtime: --depth-cap closes covered target positions: pass --targets FILE.bed --enrich --margin X with it");
+        if (r.by_name || quota) die("realtime: --depth-cap is for mask targets: with --by-name / --quota it is not built (per-group base quotas)");
+        r.depth_cap = static_cast<int32_t>(v);
     }
     if (!r.targets.empty()) {
         if (enrich == deplete) die("realtime: --targets needs exactly one of --enrich and --deplete");

@@ -11,6 +11,9 @@
 // when the tick began; the schedule credits the accepted reads and closes groups (replay.hpp), lines gain og (replay::quota_tags).
 // With --targets the early decision is the class decision (sfa_session_classes + sfa_target_decide, one call per tick), lines
 // gain the tc / ac / tm tags (target_tags) and accepted reads hold their channels (replay.hpp).
+// With --depth-cap N (mask targets, --enrich) the session keeps a depth track (sfa_session_coverage_config); at the end of a tick the
+// reads accepted in it add the target interval of the PAF line just printed for them, [pos_st, pos_end) of their contig, in ONE
+// sfa_session_coverage_add call, channels ascending, and the live mask it derives holds from the next tick on (trace: `cover` lines).
 // With --truth FILE.paf every decided read is looked up once in the truth table (truth_rules.hpp: the rules and the account), when it
 // is decided: lines gain tt / tv (tn / gv with --by-name), the trace `verdict` lines, the summary `truth:` lines.  The file is read
 // and checked against the FASTA's contig names before the BLOW5 file or a device is opened; no decision reads it.
@@ -282,6 +285,13 @@ int realtime_run(int argc, char **argv, double t0) {
         if (r.by_name && sfa_session_target_groups(se, gt.data(), static_cast<int32_t>(gt.size()), static_cast<int32_t>(group_names.size())) != SFA_OK)
             die(std::string("target groups: ") + sfa_last_error());
     }
+    int64_t base_cols = 0, open_cols = 0, cover_bases = 0, cover_intervals = 0;  // --depth-cap
+    if (r.depth_cap > 0) {
+        base_cols = sfa_session_target_columns(se);
+        if (sfa_session_coverage_config(se, r.depth_cap) != SFA_OK) die(std::string("coverage: ") + sfa_last_error());
+        open_cols = sfa_session_target_columns(se);
+    }
+    std::vector<sfa_target_t> covered;  // of a tick: what its accepted reads add
     FILE *trace = nullptr;
     if (!r.trace.empty() && !(trace = fopen(r.trace.c_str(), "w"))) die("realtime: cannot write the trace to " + r.trace);
     if (o.verbosity >= 4)
@@ -437,6 +447,8 @@ int realtime_run(int argc, char **argv, double t0) {
                     fwrite(text.data(), 1, static_cast<size_t>(len), stdout);
                 }
                 ++rep.lines[reason[i] == 'E' ? 0 : reason[i] == 'F' ? 1 : 2];
+                // --depth-cap: an accepted read covers the target interval of its line (a row of one column has none)
+                if (r.depth_cap > 0 && action[i] == 'A' && rows[i].pos_st >= 0 && rows[i].pos_end > rows[i].pos_st) covered.push_back(sfa_target_t{rows[i].rid, rows[i].pos_st, rows[i].pos_end});
             }
             fflush(stdout);  // a line is out at the moment of its decision
             if (sfa_session_reset(se, decided_slot.data(), nd) != SFA_OK) die(std::string("reset: ") + sfa_last_error());
@@ -444,7 +456,15 @@ int realtime_run(int argc, char **argv, double t0) {
         if (targets) {
             std::vector<int64_t> sent_now(n);
             for (int32_t i = 0; i < n; ++i) sent_now[i] = sch.sent(slot[i]);
+            const int64_t tick_now = sch.tick();
             sch.end_tick(reason, line, ch, &action, &held, r.quota > 0 ? &on_group : nullptr, with_truth ? &marks : nullptr);
+            if (!covered.empty()) {  // one call for the tick; the new mask holds from the next tick on
+                if (sfa_session_coverage_add(se, covered.data(), static_cast<int32_t>(covered.size()), &open_cols) != SFA_OK) die(std::string("coverage: ") + sfa_last_error());
+                if (trace) fprintf(trace, "tick %ld cover n=%zu open=%ld\n", (long)tick_now, covered.size(), (long)open_cols);
+                cover_intervals += static_cast<int64_t>(covered.size());
+                for (const sfa_target_t &iv : covered) cover_bases += iv.end - iv.begin;
+                covered.clear();
+            }
             for (int32_t i = 0; i < n; ++i) {
                 if (!reason[i]) continue;
                 const int a = action[i] == 'A' ? 0 : action[i] == 'U' ? 1 : 2;
@@ -462,6 +482,9 @@ int realtime_run(int argc, char **argv, double t0) {
     }
     if (trace) fclose(trace);
     if (targets) rep.print_targets();
+    if (r.depth_cap > 0)
+        fprintf(stderr, "[realtime] coverage: cap %d\t%ld intervals, %ld bases added\topen target columns at the end: %ld of %ld\n", r.depth_cap, (long)cover_intervals,
+                (long)cover_bases, (long)open_cols, (long)base_cols);
     if (r.by_name) rep.print_groups(group_names, r.quota, &sch);
     if (o.verbosity >= 3) rep.print(r, ch, ch.sampling_rate > 0 ? static_cast<double>(r.chunk_samples) / ch.sampling_rate : 0.0);
     if (with_truth) fputs(account.format(r.by_name).c_str(), stderr);

@@ -12,6 +12,7 @@
 //   sess::Targets     sfa_session_targets: the column mask, and of a sfa_session_classes call the slot list, partial minima, results
 //   sess::Groups      sfa_session_target_groups: the label table, and of a sfa_session_group_bests call the slot list, keys, results
 //   sess::Open        sfa_session_open_classes: the lowest column of every label, and of a call the slot list, partial minima, results
+//   sess::Coverage    sfa_session_coverage_config: the depth tracks, the live mask, and of a sfa_session_coverage_add call the intervals
 //   sess::Spread      SFA_SESSION_SPREAD on a group context: one sub-session per shard, a call's entries dealt to them
 // The host rules -- which waves a call becomes, which points of the automatic start it passes -- are session_plan.hpp's; where a
 // spread session's slots live and how a call is dealt to the shards, session_spread.hpp's.
@@ -24,6 +25,7 @@
 #include "sdtw_session_class.hpp"
 #include "sdtw_session_group.hpp"
 #include "sdtw_session_open.hpp"
+#include "sdtw_session_cover.hpp"
 
 namespace sfa {
 // defined in sfa_align.hip, the unit that holds the plain kernels of sdtw_kernels.hpp
@@ -223,6 +225,30 @@ struct Open {  // sfa_session_open_classes (the label table is sess::Groups')
     }
 };
 
+struct Coverage {  // sfa_session_coverage_config, sfa_session_coverage_add (coverage_rules.hpp)
+    int32_t cap = 0;                      // 0: off
+    int64_t live_cols = 0;                // live on-target columns of a slot's row
+    int32_t first_on = -1, first_off = -1;  // lowest column of either class under the live mask (-1: the class is empty)
+    std::vector<int64_t> h_cov_off;       // [num_ref + 1] where every contig's track begins
+    DevBuf d_depth, d_live, d_cov_off;    // the tracks, the live mask (target_mask_words words), the offsets
+    DevBuf d_stats, d_iv;                 // the mask launch's CoverStats; of a call: [n] sfa_target_t
+    PinBuf h_stats, h_iv;                 // [0] the record's initial value, [1] what the launch left
+    Event ev[2];
+    float ms = 0.0f;                      // device time of the last add + mask
+    bool on() const { return cap > 0; }
+    int reserve(int64_t entries, int64_t total_cols, int32_t num_ref) {
+        return reserve_all(d_depth, 4 * static_cast<size_t>(entries), d_live, 4 * sfa::target_mask_words(total_cols), d_cov_off, 8 * (static_cast<size_t>(num_ref) + 1), d_stats,
+                           sizeof(sfa::CoverStats), h_stats, 2 * sizeof(sfa::CoverStats));
+    }
+    int reserve_call(size_t n) { return reserve_all(d_iv, sizeof(sfa_target_t) * n, h_iv, sizeof(sfa_target_t) * n); }
+    void free_all() {
+        cap = 0, live_cols = 0, first_on = first_off = -1;
+        std::vector<int64_t>().swap(h_cov_off);
+        d_depth = DevBuf{}, d_live = DevBuf{}, d_cov_off = DevBuf{}, d_stats = DevBuf{}, d_iv = DevBuf{};
+        h_stats = PinBuf{}, h_iv = PinBuf{};
+    }
+};
+
 // SFA_SESSION_SPREAD on a group context: the session is one ordinary session per shard that holds slots (global slot i: local
 // slot i / G of subs[i % G]); every entry point deals its entries to them (session_spread.hpp), runs the shards side by side
 // (for_each_shard) and puts the answers back in the caller's order.  What a call packs or collects per shard lies here and is
@@ -271,6 +297,7 @@ struct sfa_session {
     sess::Targets targets;
     sess::Groups groups;
     sess::Open open;
+    sess::Coverage cover;
     std::unique_ptr<sess::Spread> spread;  // SFA_SESSION_SPREAD on a group context: `c` is the group, everything above is unused
     int32_t name_first = 0, name_step = 1;  // a sub-session of a spread session: local slot l is the caller's slot l * step + first (messages)
 };
@@ -319,6 +346,46 @@ void reset_slot(sfa_session *s, int32_t sl) {
     s->rows.poison[sl] = 0;
     if (s->raw.on) s->raw.reset_slot(sl);
     if (s->autos.on()) s->autos.reset_slot(sl);
+}
+
+// The live mask from the base mask and the depth tracks (session_cover_mask_kernel), on the context's stream; the caller has
+// set the device and synchronises.  The launch in front resets the record the kernel's atomics merge into.
+int cover_enqueue_mask(sfa_session *s) {
+    sfa_ctx *c = s->c;
+    sess::Coverage &v = s->cover;
+    sfa::CoverStats *hs = v.h_stats.as<sfa::CoverStats>();
+    hs[0] = sfa::CoverStats{0ull, sfa::kNoColumn, sfa::kNoColumn};
+    HIP_TRY(hipMemcpyAsync(v.d_stats.p, hs, sizeof(sfa::CoverStats), hipMemcpyHostToDevice, c->stream));
+    sfa::SessionCoverMaskArgs a;
+    a.base = s->targets.d_mask.as<uint32_t>();
+    a.live = v.d_live.as<uint32_t>();
+    a.depth = v.d_depth.as<uint32_t>();
+    a.cov_off = v.d_cov_off.as<int64_t>();
+    a.col_off = s->rows.d_col_off.as<int64_t>();
+    a.ref = c->model.tables();
+    a.stats = v.d_stats.as<sfa::CoverStats>();
+    a.total_cols = c->model.total_cols;
+    a.n_jobs = c->model.n_jobs;
+    a.n_words = static_cast<int32_t>(sfa::target_mask_words(c->model.total_cols));
+    a.cap = static_cast<uint32_t>(v.cap);
+    hipLaunchKernelGGL(sfa::session_cover_mask_kernel, dim3(sfa::cover_mask_blocks(c->model.total_cols)), dim3(sfa::kCoverThreads), 0, c->stream, a);
+    KERNEL_TRY();
+    HIP_TRY(hipMemcpyAsync(hs + 1, v.d_stats.p, sizeof(sfa::CoverStats), hipMemcpyDeviceToHost, c->stream));
+    return SFA_OK;
+}
+// ... and what it left, once the stream is through
+void cover_collect(sfa_session *s) {
+    sess::Coverage &v = s->cover;
+    const sfa::CoverStats &st = v.h_stats.as<sfa::CoverStats>()[1];
+    v.live_cols = static_cast<int64_t>(st.live);
+    v.first_on = st.first_on == sfa::kNoColumn ? -1 : st.first_on;
+    v.first_off = st.first_off == sfa::kNoColumn ? -1 : st.first_off;
+}
+int cover_derive(sfa_session *s, const char *who) {
+    if (int rc = cover_enqueue_mask(s)) return rc;
+    if (hipStreamSynchronize(s->c->stream) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
+    cover_collect(s);
+    return SFA_OK;
 }
 
 // the sweep kernel of the session's kind (with candidates every piece of a long chunk keeps a list: the last one's stays)
@@ -1137,6 +1204,37 @@ int spread_event_maps(sfa_session *s, const sfa_result_t *rows, const int32_t *s
 
 }  // namespace
 
+namespace {
+// a configuration call of a spread session: to every sub-session, as sfa_session_targets goes
+template <class F>
+int cover_spread_all(sfa_session *s, const char *who, F call) {
+    if (int rc = spread_live(s, who)) return rc;
+    sess::Spread &sp = *s->spread;
+    std::vector<int> rcs(sp.subs.size(), 0);
+    const int rc = sfa::for_each_shard(s->c, [&](size_t r) { return sp.subs[r] ? (rcs[r] = call(sp.subs[r])) : static_cast<int>(SFA_OK); });
+    size_t have = 0, failed = 0;
+    for (size_t r = 0; r < sp.subs.size(); ++r) have += sp.subs[r] != nullptr, failed += rcs[r] != SFA_OK;
+    if (failed != 0 && failed != have) sp.broken = true;
+    return rc;
+}
+
+// the reference model as the coverage rules read it (host tables; jobs are contig-major, '+' before '-': sfa_context.hip)
+struct CoverModel {
+    std::vector<int32_t> job_contig, ref_len;
+    std::vector<int8_t> job_strand;
+    sfa::TargetModel m;
+    CoverModel(const sfa_session *s) {
+        const sfa_ctx *c = s->c;
+        const int32_t nj = c->model.n_jobs, strands = nj / c->model.num_ref;
+        job_contig.resize(nj), job_strand.resize(nj), ref_len.resize(c->model.num_ref);
+        for (int32_t j = 0; j < nj; ++j) job_contig[j] = j / strands, job_strand[j] = (j % strands) ? '-' : '+';
+        for (int32_t r = 0; r < c->model.num_ref; ++r) ref_len[r] = c->model.h_job_len[static_cast<size_t>(r) * strands];
+        m = sfa::TargetModel{c->model.num_ref, nj, job_contig.data(), job_strand.data(), c->model.h_job_len.data(), s->rows.h_col_off.data(), ref_len.data(),
+                             c->model.h_ref_off.data(), c->model.total_cols};
+    }
+};
+}  // namespace
+
 namespace sfa {
 void destroy_sessions(sfa_ctx *c) {
     while (!c->sessions.empty()) sfa_session_destroy(c->sessions.back());
@@ -1328,6 +1426,7 @@ int sfa_session_targets(sfa_session_t *s, const sfa_target_t *targets, int32_t n
         t.first_on = t.first_off = -1;
         std::vector<uint32_t>().swap(t.h_mask);
         t.d_mask = DevBuf{};  // (freed; the buffers of a call stay for the next mask)
+        s->cover.free_all();  // (a coverage cap lives on the mask: off with it)
         return SFA_OK;
     }
     if (c->model.total_cols >= INT32_MAX) return fail(SFA_ERANGE, "%s: the reference has %lld columns; the classes count them in 31 bits", who, (long long)c->model.total_cols);
@@ -1352,12 +1451,14 @@ int sfa_session_targets(sfa_session_t *s, const sfa_target_t *targets, int32_t n
     t.first_on = sfa::target_first_of_class(t.h_mask, c->model.total_cols, true);
     t.first_off = sfa::target_first_of_class(t.h_mask, c->model.total_cols, false);
     t.on = true;
+    if (s->cover.on()) return cover_derive(s, who);  // (the depth is kept: the live mask of the new base mask)
     return SFA_OK;
 }
 
 int64_t sfa_session_target_columns(sfa_session_t *s) {
     if (!s) return fail(SFA_EINVAL, "sfa_session_target_columns: null session");
     if (s->spread) return sfa_session_target_columns(s->spread->subs[0]);  // (sub-session 0 always exists, as in spread_classes)
+    if (s->cover.on()) return s->cover.live_cols;
     return s->targets.on ? s->targets.on_cols : 0;
 }
 
@@ -1399,7 +1500,7 @@ int sfa_session_classes(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_cl
         sfa::SessionClassArgs a;
         a.slot = t.d_slot.as<int32_t>();
         a.rows = s->rows.d_row_c.as<float>() + sfa::kSessionPad;
-        a.mask = t.d_mask.as<uint32_t>();
+        a.mask = s->cover.on() ? s->cover.d_live.as<uint32_t>() : t.d_mask.as<uint32_t>();  // (the kernel is the same: another pointer)
         a.part = t.d_part.as<sfa::ClassPartial>();
         a.total_cols = c->model.total_cols;
         a.n = m;
@@ -1412,8 +1513,8 @@ int sfa_session_classes(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_cl
         ra.n = m;
         ra.n_parts = parts;
         ra.n_jobs = c->model.n_jobs;
-        ra.first_on = t.first_on;
-        ra.first_off = t.first_off;
+        ra.first_on = s->cover.on() ? s->cover.first_on : t.first_on;
+        ra.first_off = s->cover.on() ? s->cover.first_off : t.first_off;
         HIP_TRY(hipEventRecord(t.ev[0], st));
         hipLaunchKernelGGL(sfa::sdtw_session_class_kernel, dim3(static_cast<unsigned>(m) * parts), dim3(sfa::kClassThreads), 0, st, a);
         KERNEL_TRY();
@@ -1436,6 +1537,125 @@ int sfa_session_classes(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_cl
 
 int sfa_target_decide(const sfa_class_t *cls, int32_t mode, int32_t min_events, float margin) {
     return cls ? sfa::target_decide(*cls, mode, min_events, margin) : 0;
+}
+
+// ---- coverage caps (coverage_rules.hpp, sdtw_session_cover.hpp) ----
+
+size_t sfa_session_coverage_bytes(const sfa_ref_t *ref, int flag) {
+    if (!ref || ref->num_ref <= 0 || !ref->ref_lengths) return 0;
+    int64_t entries = 0, cols = 0;
+    for (int32_t r = 0; r < ref->num_ref; ++r) {
+        if (ref->ref_lengths[r] <= 0) return 0;
+        entries += sfa::coverage_track_len(ref->ref_lengths[r]);
+        cols += static_cast<int64_t>(ref->ref_lengths[r]) * ((flag & SFA_RNA) ? 1 : 2);
+    }
+    return sfa::coverage_bytes(entries, cols);
+}
+
+int sfa_session_coverage_config(sfa_session_t *s, int32_t cap) {
+    static const char *const who = "sfa_session_coverage_config";
+    if (!s) return fail(SFA_EINVAL, "%s: null session", who);
+    if (cap < 0 || cap > sfa::kCoverCapMax) return fail(SFA_EINVAL, "%s: cap must be 0 (off) .. %d, not %d", who, sfa::kCoverCapMax, cap);
+    if (s->spread) {
+        if (int rc = spread_live(s, who)) return rc;
+        if (cap > 0 && !s->spread->subs[0]->targets.on) return fail(SFA_EINVAL, "%s: the session has no targets (sfa_session_targets)", who);
+        return cover_spread_all(s, who, [&](sfa_session *sub) { return sfa_session_coverage_config(sub, cap); });
+    }
+    sfa_ctx *c = s->c;
+    sess::Coverage &v = s->cover;
+    if (cap > 0 && !s->targets.on) return fail(SFA_EINVAL, "%s: the session has no targets (sfa_session_targets)", who);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (a mask in use is not replaced under a kernel)
+    if (cap == 0) {
+        v.free_all();
+        return SFA_OK;
+    }
+    const CoverModel cm(s);
+    std::vector<int64_t> cov_off;
+    sfa::coverage_offsets(cm.ref_len.data(), c->model.num_ref, &cov_off);
+    if (int rc = v.reserve(cov_off.back(), c->model.total_cols, c->model.num_ref)) return rc;
+    if (int rc = sess::create_events(v.ev, 2)) return rc;
+    v.h_cov_off.swap(cov_off);
+    HIP_TRY(hipMemcpyAsync(v.d_cov_off.p, v.h_cov_off.data(), 8 * v.h_cov_off.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(v.d_depth.p, 0, 4 * static_cast<size_t>(v.h_cov_off.back()), c->stream));
+    HIP_TRY(hipMemsetAsync(v.d_live.p, 0, 4 * sfa::target_mask_words(c->model.total_cols), c->stream));  // (the spare word stays zero)
+    v.cap = cap;
+    if (int rc = cover_derive(s, who)) {  // (depth 0 everywhere: the live mask is the base mask)
+        v.free_all();
+        return rc;
+    }
+    return SFA_OK;
+}
+
+int sfa_session_coverage_add(sfa_session_t *s, const sfa_target_t *iv, int32_t n, int64_t *open_columns) {
+    static const char *const who = "sfa_session_coverage_add";
+    if (!s || n < 0 || (n > 0 && !iv)) return fail(SFA_EINVAL, "%s: bad argument", who);
+    if (n > sfa::kCoverIntervalsMax) return fail(SFA_EINVAL, "%s: %d intervals in one call; at most %d", who, n, sfa::kCoverIntervalsMax);
+    sfa_session *first = s->spread ? s->spread->subs[0] : s;  // (sub-session 0 always exists; every sub-session holds the same state)
+    if (s->spread)
+        if (int rc = spread_live(s, who)) return rc;
+    if (!first->cover.on()) return fail(SFA_EINVAL, "%s: the session has no coverage cap (sfa_session_coverage_config)", who);
+    {
+        const CoverModel cm(first);
+        char msg[192];
+        if (sfa::coverage_list_error(iv, n, cm.m, msg, sizeof msg)) return fail(SFA_EINVAL, "%s: %s", who, msg);
+    }
+    if (s->spread) {
+        if (int rc = cover_spread_all(s, who, [&](sfa_session *sub) { return sfa_session_coverage_add(sub, iv, n, nullptr); })) return rc;
+        if (open_columns) *open_columns = first->cover.live_cols;  // (shard 0's count: every shard holds the same mask)
+        return SFA_OK;
+    }
+    sfa_ctx *c = s->c;
+    sess::Coverage &v = s->cover;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    hipStream_t st = c->stream;
+    HIP_TRY(hipEventRecord(v.ev[0], st));
+    if (n > 0) {
+        if (int rc = v.reserve_call(static_cast<size_t>(n))) return rc;
+        memcpy(v.h_iv.p, iv, sizeof(sfa_target_t) * static_cast<size_t>(n));
+        HIP_TRY(hipMemcpyAsync(v.d_iv.p, v.h_iv.p, sizeof(sfa_target_t) * static_cast<size_t>(n), hipMemcpyHostToDevice, st));
+        sfa::SessionCoverAddArgs a;
+        a.iv = v.d_iv.as<sfa_target_t>();
+        a.cov_off = v.d_cov_off.as<int64_t>();
+        a.ref_len = c->model.d_ref_len.as<int32_t>();
+        a.ref_st_offset = c->model.d_ref_off.as<int32_t>();
+        a.depth = v.d_depth.as<uint32_t>();
+        a.n = n;
+        hipLaunchKernelGGL(sfa::session_cover_add_kernel, dim3(static_cast<unsigned>(n)), dim3(sfa::kCoverThreads), 0, st, a);
+        KERNEL_TRY();
+    }
+    if (int rc = cover_enqueue_mask(s)) return rc;
+    HIP_TRY(hipEventRecord(v.ev[1], st));
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
+    cover_collect(s);
+    HIP_TRY(hipEventElapsedTime(&v.ms, v.ev[0], v.ev[1]));
+    sfa_profile_t pr{};
+    pr.segment_reruns = c->seg.seg_reruns;
+    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
+    pr.class_ms = pr.total_ms = v.ms;
+    c->prof = pr;
+    if (open_columns) *open_columns = v.live_cols;
+    return SFA_OK;
+}
+
+int sfa_session_coverage_depth(sfa_session_t *s, int32_t contig, uint32_t *out, int32_t n) {
+    static const char *const who = "sfa_session_coverage_depth";
+    if (!s || !out) return fail(SFA_EINVAL, "%s: bad argument", who);
+    if (s->spread) {
+        if (int rc = spread_live(s, who)) return rc;
+        return sfa_session_coverage_depth(s->spread->subs[0], contig, out, n);  // (shard 0 answers, on the caller's thread as in for_each_shard)
+    }
+    sfa_ctx *c = s->c;
+    sess::Coverage &v = s->cover;
+    if (!v.on()) return fail(SFA_EINVAL, "%s: the session has no coverage cap (sfa_session_coverage_config)", who);
+    if (contig < 0 || contig >= c->model.num_ref) return fail(SFA_EINVAL, "%s: contig %d out of range (the reference has %d)", who, contig, c->model.num_ref);
+    const int64_t len = v.h_cov_off[static_cast<size_t>(contig) + 1] - v.h_cov_off[static_cast<size_t>(contig)];
+    if (n != len) return fail(SFA_EINVAL, "%s: contig %d has %lld entries (ref_length + 1), not %d", who, contig, static_cast<long long>(len), n);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(out, v.d_depth.as<uint32_t>() + v.h_cov_off[static_cast<size_t>(contig)], 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SFA_OK;
 }
 
 // ---- target groups (group_rules.hpp, sdtw_session_group.hpp) ----

@@ -37,6 +37,10 @@ ticks, the same calls, the same lines.  The schedule counts ticks, never seconds
             ascending channel order (api.QuotaBook, in Schedule.end_tick); the credit that fills a quota closes the group from the
             next tick on (trace: `close group=NAME accepted=K`), so a group may overshoot by the reads accepted in its closing
             tick.  Proceeding reads are not credited.  Lines gain og:Z:<name of on_group, * for none> (quota_tags)
+  depth cap depth_cap=N with mask targets and mode=ENRICH (--depth-cap N; not with by_name / quota): the session keeps a depth track
+            (Session.configure_coverage).  At the end of a tick the reads accepted in it ('A', with a line) add the target interval of
+            their line, [pos_st, pos_end) of the row's contig, in ONE Session.add_coverage call, ascending channels; the live mask
+            it derives holds from the next tick on (trace: `tick T cover n=K open=M`).  summary["cover"]: format_cover_summary
   truth     truth= (--truth FILE.paf; needs targets=): {read id: (contig, begin, end)} as api.read_truth returns it.  Every decided read
             is looked up once, at its decision: its true class (api.truth_class: 'T' when its interval shares a base with a target,
             'O' when not or when it belongs nowhere, 'N' when it has no truth) and the verdict of the decided class
@@ -201,7 +205,7 @@ AUTO_START_MAX_SAMPLES, MAX_SKIP_EVENTS = 131072, 4096  # the defaults of --auto
 
 
 def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False, resweep=False,
-           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None, by_name=False, quota=None, truth=None):
+           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None, by_name=False, quota=None, truth=None, depth_cap=None):
     """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
     candidates=1..4 (--candidates): an eighth element, RESULT_DTYPE[4], the channel's candidates at the decision, best first.
     A `session` of the caller's is taken as it is, in this as in its raw mode: it must keep that many candidates already
@@ -236,8 +240,21 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     truth={read id: (contig, begin, end)} (--truth FILE.paf; api.read_truth; needs targets=): see `truth` above.  An item gains, behind
     the on_group (or whatever came last of the class record, the head and it), a dict with tt, tv and edge, and with by_name
     true_group (None: the read has no truth) and gv (None: the read has no line) -- format_line takes it as truth=(that dict, names).
-    summary gains "truth", the account format_truth_summary prints."""
+    summary gains "truth", the account format_truth_summary prints.
+    depth_cap=N (--depth-cap N; needs mask targets= with mode=ENRICH, N >= 1, a session that carries start columns): see `depth
+    cap` above.  The items are unchanged; summary gains "cover", a dict with cap, intervals, bases, open and base (columns)."""
     auto = skip < 0
+    if depth_cap is not None:  # (before any session exists, each with the fix)
+        if isinstance(depth_cap, bool) or not isinstance(depth_cap, (int, np.integer)) or depth_cap < 1 or depth_cap > 1 << 30:
+            raise api.SfaError("replay: depth_cap should be an integer 1..1073741824 (None for no cap)")
+        if mode == api.DEPLETE:
+            raise api.SfaError("replay: depth_cap with mode=DEPLETE is not built: a covered position would turn on target; use mode=ENRICH")
+        if targets is None or mode != api.ENRICH:
+            raise api.SfaError("replay: depth_cap closes covered target positions: pass targets=, mode=ENRICH and margin= with it")
+        if by_name or quota is not None:
+            raise api.SfaError("replay: depth_cap is for mask targets: with by_name / quota it is not built (per-group base quotas)")
+        if session is not None and not getattr(session, "starts", True):
+            raise api.SfaError("replay: depth_cap needs the rows' start columns for the interval; the session was created with starts=False (SESSION_NO_START)")
     if truth is not None and targets is None:  # (before any session exists)
         raise api.SfaError("replay: truth= checks target decisions: pass targets= with mode= and margin= with it")
     if quota is not None:  # (before any session exists, each with the fix)
@@ -310,6 +327,13 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
             se.set_targets(targets)
         if by_name:
             se.set_target_groups(group_targets, len(group_names))
+        cover = None
+        if depth_cap is not None:
+            cover = dict(cap=int(depth_cap), intervals=0, bases=0, base=se.target_columns())
+            se.configure_coverage(depth_cap)
+            cover["open"] = se.target_columns()
+            if summary is not None:
+                summary["cover"] = cover
         if candidates and not own:
             se.candidates([])  # (raises unless the caller's session keeps candidates)
         sch.start(src)
@@ -394,7 +418,17 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                                       cand_maps=maps[per * k + 1:per * k + 5] if candidates else None),)
                     yield item
                 se.reset(d_slots)
+            tick_now = sch.tick
             held = sch.end_tick(reason, line, src, action, on_group, None if marks is None else [m and (m["tt"], m["tv"]) for m in marks])
+            if cover is not None:  # one call for the tick; the new mask holds from the next tick on
+                covered = [(int(rows[i]["rid"]), int(rows[i]["pos_st"]), int(rows[i]["pos_end"])) for i in decided
+                           if line[i] and action[i] == "A" and 0 <= int(rows[i]["pos_st"]) < int(rows[i]["pos_end"])]
+                if covered:
+                    cover["open"] = se.add_coverage(covered)
+                    cover["intervals"] += len(covered)
+                    cover["bases"] += sum(e - b for _, b, e in covered)
+                    if trace is not None:
+                        trace.append(f"tick {tick_now} cover n={len(covered)} open={cover['open']}")
             if marks is not None:
                 for i in decided:
                     note_truth(account, marks[i]["tt"], marks[i]["edge"], action[i], marks[i]["tv"], sch_sent[i], held[i], marks[i]["length"])
@@ -514,6 +548,12 @@ def format_group_summary(summary, names):
     quota = summary.get("quota", 0)
     tail = lambda g: " quota=%d closed_at=%s" % (quota, summary.get(("closed_at", g), "-")) if quota and g < len(names) else ""
     return "".join("[realtime] group %s: accepted %d reads%s\n" % (names[g] if g < len(names) else "*", summary.get(("group", g), 0), tail(g)) for g in range(len(names) + 1))
+
+
+def format_cover_summary(summary):
+    """the line `sigfish-amd realtime --depth-cap` adds to its stderr, from summary["cover"]"""
+    c = summary["cover"]
+    return "[realtime] coverage: cap %d\t%d intervals, %d bases added\topen target columns at the end: %d of %d\n" % (c["cap"], c["intervals"], c["bases"], c["open"], c["base"])
 
 
 def format_summary(summary):
