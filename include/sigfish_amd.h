@@ -465,6 +465,45 @@ typedef struct {
  * than (n_groups + 31) / 32. */
 int sfa_session_open_classes(sfa_session_t *s, const int32_t *slot, int32_t n, const uint32_t *open, int32_t n_words, sfa_open_class_t *out);
 
+/* ---- group caps: named groups that close, column by column, where they are covered deeply enough -------------------------------
+ * The LIVE label table is derived from the label table of sfa_session_target_groups (the base table, which is kept) and the depth
+ * tracks of the coverage caps above: the live label of a column is its base label while the depth of the coordinate the column
+ * reports lies below the group cap, and the background, n_groups, from then on.  A background column stays background; a column
+ * two groups cover goes to the background with its coordinate, not to the higher group.  While a group cap is set,
+ * sfa_session_open_classes and sfa_session_group_bests read the live table (the same kernels, another pointer): a group whose
+ * every column is capped has no column, as a group without intervals has none.
+ * A session has ONE depth track, shared by the mask's cap (sfa_session_coverage_config) and the group cap, which are two numbers:
+ * whichever is configured first allocates the track, zeroed; it is freed when both are 0.  Configuring either cap again zeroes the
+ * track only while the other cap is off.  sfa_session_coverage_config(s, 0) and sfa_session_targets(s, NULL, 0) keep the track
+ * while a group cap is on; on a session that never sets a group cap every call above does what it did.  With either cap set
+ * sfa_session_coverage_add adds once to the track and derives, in the same call, whichever of the live mask and the live labels
+ * are on (open_columns: sfa_session_target_columns' answer), and sfa_session_coverage_depth answers.
+ * Memory: sfa_session_group_coverage_bytes per SESSION, not counted by sfa_session_bytes.
+ * On a spread session _config goes to every sub-session and sfa_session_group_coverage is answered by shard 0. */
+
+/* The depth of one entry (a group, or the background at index n_groups), taken over the columns of the FORWARD ('+') jobs whose
+ * BASE label is the entry: every coordinate a forward row reports counts once; the one coordinate per contig that only a reverse
+ * row reports (ref_st_offset + ref_length) is left out.  capped: columns whose depth is at or above the group cap.  An entry
+ * without columns: 0, 0, 0, UINT32_MAX, 0 -- form no mean from it. */
+typedef struct {
+    int64_t columns, capped;
+    uint64_t depth_sum;
+    uint32_t depth_min, depth_max;
+} sfa_group_cover_t;
+
+/* cap >= 1 switches the group cap on (live table = base table where the kept depth allows); cap = 0 switches it off and frees the
+ * live table.  Needs groups (sfa_session_target_groups), no mask.  sfa_session_target_groups on a session with a group cap rebuilds
+ * the base table and derives the live one from the kept depth; with n = 0 it drops the group cap too.
+ * SFA_EINVAL: a null session, cap < 0 or cap > 2^30, no groups (so every SFA_SESSION_RESWEEP session). */
+int sfa_session_group_coverage_config(sfa_session_t *s, int32_t cap);
+/* The records of the n_groups + 1 entries into out[0 .. n).  Blocking, on the context's stream; sfa_profile_t.class_ms is its
+ * device time.  SFA_EINVAL, before anything is written: null arguments, no group cap set, n other than n_groups + 1. */
+int sfa_session_group_coverage(sfa_session_t *s, sfa_group_cover_t *out, int32_t n);
+/* Device memory a group cap takes on a session of a context made from (ref, flag) with n_groups groups: the depth tracks (4 bytes
+ * per coordinate; shared with the mask's cap, so not taken twice), the second label table (2 bytes per column) and 36 bytes per
+ * entry.  Host arithmetic; 0 for a null or empty reference or n_groups outside 1 .. 1023. */
+size_t sfa_session_group_coverage_bytes(const sfa_ref_t *ref, int flag, int32_t n_groups);
+
 /* ---- truth: a target decision against where a read really came from (host only; no context, no device) --------------------------
  * A read's truth is the interval [begin, end) of `contig` its bases cover on the forward strand; contig < 0: the read belongs
  * nowhere.  These are the rules `sigfish-amd realtime --truth` applies (sigfish_amd/csrc/truth_rules.hpp), exported so that no

@@ -79,6 +79,10 @@ class SfaGroupHead(C.Structure):
                 ("valid", C.c_int32)]
 
 
+class SfaGroupCover(C.Structure):
+    _fields_ = [("columns", C.c_int64), ("capped", C.c_int64), ("depth_sum", C.c_uint64), ("depth_min", C.c_uint32), ("depth_max", C.c_uint32)]
+
+
 class SfaSessionAuto(C.Structure):
     _fields_ = [("target", C.c_int64), ("frozen_at", C.c_int64), ("skip", C.c_int32), ("status", C.c_int32)]
 
@@ -98,6 +102,7 @@ SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "
            "sfa_session_target_groups", "sfa_session_group_count", "sfa_session_group_bests", "sfa_group_decide",
            "sfa_session_open_classes",
            "sfa_session_coverage_config", "sfa_session_coverage_add", "sfa_session_coverage_depth", "sfa_session_coverage_bytes",
+           "sfa_session_group_coverage_config", "sfa_session_group_coverage", "sfa_session_group_coverage_bytes",
            "sfa_truth_class", "sfa_truth_edge", "sfa_truth_group", "sfa_truth_verdict", "sfa_truth_group_verdict"]
 
 _lib = None
@@ -244,6 +249,10 @@ def load():
     L.sfa_session_coverage_depth.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint32), C.c_int32]
     L.sfa_session_coverage_bytes.argtypes = [C.POINTER(SfaRef), C.c_int]
     L.sfa_session_coverage_bytes.restype = C.c_size_t
+    L.sfa_session_group_coverage_config.argtypes = [vp, C.c_int32]
+    L.sfa_session_group_coverage.argtypes = [vp, C.POINTER(SfaGroupCover), C.c_int32]
+    L.sfa_session_group_coverage_bytes.argtypes = [C.POINTER(SfaRef), C.c_int, C.c_int32]
+    L.sfa_session_group_coverage_bytes.restype = C.c_size_t
     L.sfa_truth_class.argtypes = L.sfa_truth_edge.argtypes = [C.POINTER(SfaTarget), C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.sfa_truth_group.argtypes = [C.POINTER(SfaGroupTarget), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.sfa_truth_group.restype = C.c_int32

@@ -46,6 +46,8 @@ assert GROUP_HEAD_DTYPE.itemsize == C.sizeof(_lib.SfaGroupHead)
 GROUP_MAX = 1023  # n_groups at most
 OPEN_CLASS_DTYPE = np.dtype([("cls", CLASS_DTYPE), ("on_group", "<i4"), ("off_group", "<i4")])  # sfa_open_class_t
 assert OPEN_CLASS_DTYPE.itemsize == CLASS_DTYPE.itemsize + 8
+GROUP_COVER_DTYPE = np.dtype([("columns", "<i8"), ("capped", "<i8"), ("depth_sum", "<u8"), ("depth_min", "<u4"), ("depth_max", "<u4")])  # sfa_group_cover_t
+assert GROUP_COVER_DTYPE.itemsize == C.sizeof(_lib.SfaGroupCover) == 32
 RAW_RECALIBRATED = 16  # ... and the bit of one call: the slot was recalibrated and swept again from event 0
 RECAL_AT_END = 0x1     # SFA_RECAL_AT_END
 RECAL_MAX_POINTS = 32
@@ -797,6 +799,25 @@ class Session:
         _check(self._L.sfa_session_coverage_depth(self._h, c, out.ctypes.data_as(C.POINTER(C.c_uint32)), n), "sfa_session_coverage_depth")
         return out
 
+    def configure_group_coverage(self, cap):
+        """A depth cap on the session's target groups (sfa_session_group_coverage_config): cap >= 1 switches it on -- a live label
+        table beside the table of set_target_groups, derived from the session's one depth track -- and 0 switches it off.  The
+        live label of a column is its base label while the depth of the coordinate it reports lies below cap, the background
+        from then on; open_classes() and group_bests() then read the live table.  Needs groups, no mask; the track is shared with
+        configure_coverage(), whose cap is a number of its own.  add_coverage() and coverage() work with either cap set.
+        session_group_coverage_bytes() of memory."""
+        self._live()
+        _check(self._L.sfa_session_group_coverage_config(self._h, int(cap)), "sfa_session_group_coverage_config")
+
+    def group_coverage(self):
+        """How deep every group is (sfa_session_group_coverage) -> GROUP_COVER_DTYPE[n_groups + 1], the background last: columns,
+        capped (depth >= the group cap), depth_sum, depth_min, depth_max over the forward-strand columns whose BASE label is the
+        entry.  An entry without columns: 0, 0, 0, 2^32 - 1, 0."""
+        self._live()
+        out = np.zeros(self.group_count() + 1, GROUP_COVER_DTYPE)
+        _check(self._L.sfa_session_group_coverage(self._h, out.ctypes.data_as(C.POINTER(_lib.SfaGroupCover)), len(out)), "sfa_session_group_coverage")
+        return out
+
     def reset(self, slots=None):
         """Forget the events of `slots` (None: of every slot); in raw mode the detector, normalisation and scaling as well."""
         self._live()
@@ -1084,6 +1105,13 @@ def session_coverage_bytes(ref, flag=0):
     coordinate (ref_length + 1 per contig) and a second mask of total_columns / 8 bytes."""
     cref, _keep = ref._as_c()
     return int(_lib.load().sfa_session_coverage_bytes(C.byref(cref), int(flag)))
+
+
+def session_group_coverage_bytes(ref, n_groups, flag=0):
+    """Device memory Session.configure_group_coverage takes for a RefModel with n_groups groups (sfa_session_group_coverage_bytes;
+    host arithmetic): the depth tracks (shared with configure_coverage), a second label table and 36 bytes per entry."""
+    cref, _keep = ref._as_c()
+    return int(_lib.load().sfa_session_group_coverage_bytes(C.byref(cref), int(flag), int(n_groups)))
 
 
 def session_raw_bytes(n_slots, skip=50, query=2048):

@@ -83,6 +83,7 @@ struct RealtimeOpt {
     int32_t target_mode = -1;      // --enrich: 0, --deplete: 1 (exactly one of them with --targets)
     bool by_name = false;          // --by-name: the BED file's name column sets the session's target groups; lines gain tg / gm (replay.hpp)
     int64_t quota = 0;             // --quota N: accepted reads after which a named group is closed (needs --by-name --enrich; 0: off)
+    int32_t group_cap = 0;         // --group-cap N: a named group's columns close where accepted reads cover them N times (needs --by-name --enrich; 0: off)
     int32_t depth_cap = 0;         // --depth-cap N: target positions covered N times by accepted reads close (needs --targets --enrich, no --by-name; 0: off)
     float margin = 0.0f;           // --margin X: cost per query event between the classes (required with --targets: no default)
     std::string truth;             // --truth FILE.paf: where every read came from; lines gain tt / tv (tn / gv), the trace verdict lines (needs --targets)

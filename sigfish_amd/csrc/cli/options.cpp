@@ -20,7 +20,7 @@ enum LongOpt {
     O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
     O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
     O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE,
-    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_BY_NAME, O_TRACE, O_QUOTA, O_TRUTH, O_DEPTH_CAP
+    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_BY_NAME, O_TRACE, O_QUOTA, O_TRUTH, O_DEPTH_CAP, O_GROUP_CAP
 };
 
 const option kLongOptions[] = {
@@ -119,7 +119,7 @@ const option kRealtimeOptions[] = {
     {"candidates", required_argument, 0, O_CANDIDATES}, {"spread", no_argument, 0, O_SPREAD},
     {"targets", required_argument, 0, O_TARGETS}, {"enrich", no_argument, 0, O_ENRICH}, {"deplete", no_argument, 0, O_DEPLETE},
     {"margin", required_argument, 0, O_MARGIN}, {"by-name", no_argument, 0, O_BY_NAME}, {"quota", required_argument, 0, O_QUOTA}, {"trace", required_argument, 0, O_TRACE},
-    {"truth", required_argument, 0, O_TRUTH}, {"depth-cap", required_argument, 0, O_DEPTH_CAP},
+    {"truth", required_argument, 0, O_TRUTH}, {"depth-cap", required_argument, 0, O_DEPTH_CAP}, {"group-cap", required_argument, 0, O_GROUP_CAP},
     {0, 0, 0, 0}};
 
 void realtime_help(FILE *fp, const RealtimeOpt &r) {
@@ -187,6 +187,12 @@ void realtime_help(FILE *fp, const RealtimeOpt &r) {
                 "                              sfa_session_coverage_add call; from the next tick on a target column whose coordinate has depth >=\n"
                 "                              INT counts as off target.  The interval is the aligned window of the decided prefix, not the whole\n"
                 "                              molecule.  The trace gains `cover` lines, the summary the open columns and the bases added [off]\n");
+    fprintf(fp, "   --group-cap INT            with --targets --by-name --enrich (optionally --quota; not with --depth-cap, --deplete, --resweep): a\n"
+                "                              named group stops asking for reads, column by column, where it is covered INT times.  One\n"
+                "                              sfa_session_open_classes call per tick decides (lines gain og:Z:); at the end of a tick the accepted\n"
+                "                              reads' intervals go into one sfa_session_coverage_add call, and from the next tick on a column whose\n"
+                "                              coordinate has depth >= INT belongs to the background.  The trace gains `cover` lines and\n"
+                "                              `full group=NAME` when every column of a group is capped, the summary a depth line per group [off]\n");
     fprintf(fp, "   --truth FILE.paf           with --targets: check every decision against where the read came from -- a PAF file, column 1 the\n"
                 "                              read id, 6 the contig (* for a read that belongs nowhere), 8 and 9 begin and end; a read that\n"
                 "                              shares a base with a target is truly on target.  Lines gain tt:A:<true class T|O, N: not in the\n"
@@ -206,7 +212,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     FILE *fp_help = stderr;
     int c, li = 0;
     bool secondary = false;
-    const char *recal = nullptr, *candidates = nullptr, *margin = nullptr, *quota = nullptr, *depth_cap = nullptr;
+    const char *recal = nullptr, *candidates = nullptr, *margin = nullptr, *quota = nullptr, *depth_cap = nullptr, *group_cap = nullptr;
     bool enrich = false, deplete = false;
     while ((c = getopt_long(argc, argv, "p:q:t:v:o:ahV", kRealtimeOptions, &li)) >= 0) {
         switch (c) {
@@ -251,6 +257,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
             case O_QUOTA: quota = optarg; break;
             case O_TRUTH: r.truth = optarg; break;
             case O_DEPTH_CAP: depth_cap = optarg; break;
+            case O_GROUP_CAP: group_cap = optarg; break;
             case O_TRACE: r.trace = optarg; break;
             default: realtime_help(stderr, r); exit(EXIT_FAILURE);
         }
@@ -288,6 +295,16 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
         const long long v = strtoll(quota, &e, 10);
         if (e == quota || *e || v < 1) die("realtime: --quota should be an integer >= 1 (leave the option out for no quota)");
         r.quota = v;
+    }
+    if (group_cap) {  // (a session of this front end always carries start columns, as for --depth-cap)
+        char *e = nullptr;
+        const long long v = strtoll(group_cap, &e, 10);
+        if (e == group_cap || *e || v < 1 || v > (1 << 30)) die("realtime: --group-cap should be an integer 1..1073741824 (leave the option out for no cap)");
+        if (deplete) die("realtime: --group-cap with --deplete is not built: a covered position would turn on target; use --enrich");
+        if (!r.by_name || !enrich) die("realtime: --group-cap closes the covered columns of named groups: pass --targets FILE.bed --by-name --enrich --margin X with it");
+        if (depth_cap) die("realtime: --group-cap and --depth-cap are two caps over one depth track: pass one of them (--depth-cap is for mask targets)");
+        if (r.resweep) die("realtime: --group-cap is not available with --resweep: a resweep session has no target groups");
+        r.group_cap = static_cast<int32_t>(v);
     }
     if (depth_cap) {  // (a session of this front end always carries start columns: the interval's other end is there)
         char *e = nullptr;

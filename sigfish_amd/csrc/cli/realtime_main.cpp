@@ -291,6 +291,13 @@ int realtime_run(int argc, char **argv, double t0) {
         if (sfa_session_coverage_config(se, r.depth_cap) != SFA_OK) die(std::string("coverage: ") + sfa_last_error());
         open_cols = sfa_session_target_columns(se);
     }
+    std::vector<sfa_group_cover_t> gcov(r.group_cap > 0 ? group_names.size() + 1 : 0);  // --group-cap: the groups' depth after every add
+    std::vector<char> group_full(group_names.size(), 0);
+    if (r.group_cap > 0) {
+        if (sfa_session_group_coverage_config(se, r.group_cap) != SFA_OK) die(std::string("group coverage: ") + sfa_last_error());
+        if (sfa_session_group_coverage(se, gcov.data(), static_cast<int32_t>(gcov.size())) != SFA_OK) die(std::string("group coverage: ") + sfa_last_error());
+    }
+    const bool use_open = r.quota > 0 || r.group_cap > 0;  // the tick's class call is sfa_session_open_classes; lines gain og
     std::vector<sfa_target_t> covered;  // of a tick: what its accepted reads add
     FILE *trace = nullptr;
     if (!r.trace.empty() && !(trace = fopen(r.trace.c_str(), "w"))) die("realtime: cannot write the trace to " + r.trace);
@@ -323,8 +330,8 @@ int realtime_run(int argc, char **argv, double t0) {
     std::vector<sfa_session_raw_info_t> info(C);
     std::vector<char> reason(C), line(C), action(C);
     std::vector<sfa_class_t> cls(targets ? C : 0);
-    std::vector<sfa_open_class_t> ocls(r.quota > 0 ? C : 0);
-    std::vector<int32_t> on_group(r.quota > 0 ? C : 0);
+    std::vector<sfa_open_class_t> ocls(use_open ? C : 0);
+    std::vector<int32_t> on_group(use_open ? C : 0);
     std::vector<int64_t> held;
     replay::TruthMarks marks;  // --truth: per entry of the tick
     std::vector<const sfa::TruthRecord *> truth_of(with_truth ? C : 0);
@@ -361,8 +368,8 @@ int realtime_run(int argc, char **argv, double t0) {
         if (sfa_session_extend_raw(se, slot.data(), dst, raw_off.data(), scaling.data(), end.data(), n, rows.data(), info.data()) != SFA_OK)
             die(std::string("tick ") + std::to_string(sch.tick()) + ": " + sfa_last_error());
         decided_slot.clear();
-        if (r.quota > 0 && n > 0) {  // the tick's classes under the groups open at its start (the book changes in end_tick only)
-            if (sfa_session_open_classes(se, slot.data(), n, book.open(), book.n_words(), ocls.data()) != SFA_OK) die(std::string("open classes: ") + sfa_last_error());
+        if (use_open && n > 0) {  // the tick's classes under the groups open at its start (the book changes in end_tick only; no book: every group)
+            if (sfa_session_open_classes(se, slot.data(), n, r.quota > 0 ? book.open() : nullptr, r.quota > 0 ? book.n_words() : 0, ocls.data()) != SFA_OK) die(std::string("open classes: ") + sfa_last_error());
             for (int32_t i = 0; i < n; ++i) cls[i] = ocls[i].cls, on_group[i] = ocls[i].on_group;
         } else if (targets && n > 0 && sfa_session_classes(se, slot.data(), n, cls.data()) != SFA_OK) {
             die(std::string("classes: ") + sfa_last_error());
@@ -419,7 +426,7 @@ int realtime_run(int argc, char **argv, double t0) {
                     tail += replay::group_tags(h.best, h.second, h.best_score, h.second_score, h.n_events, group_names);
                     if (action[i] == 'A' && h.best >= 0) ++rep.group_accepted[h.best];
                 }
-                if (r.quota > 0) tail += replay::quota_tags(on_group[i], group_names);
+                if (use_open) tail += replay::quota_tags(on_group[i], group_names);
                 if (with_truth) {
                     tail += replay::truth_tags(marks.tt[i], marks.tv[i]);
                     if (r.by_name) {  // the line's tg names the head's best entry, the background for none
@@ -448,7 +455,7 @@ int realtime_run(int argc, char **argv, double t0) {
                 }
                 ++rep.lines[reason[i] == 'E' ? 0 : reason[i] == 'F' ? 1 : 2];
                 // --depth-cap: an accepted read covers the target interval of its line (a row of one column has none)
-                if (r.depth_cap > 0 && action[i] == 'A' && rows[i].pos_st >= 0 && rows[i].pos_end > rows[i].pos_st) covered.push_back(sfa_target_t{rows[i].rid, rows[i].pos_st, rows[i].pos_end});
+                if ((r.depth_cap > 0 || r.group_cap > 0) && action[i] == 'A' && rows[i].pos_st >= 0 && rows[i].pos_end > rows[i].pos_st) covered.push_back(sfa_target_t{rows[i].rid, rows[i].pos_st, rows[i].pos_end});
             }
             fflush(stdout);  // a line is out at the moment of its decision
             if (sfa_session_reset(se, decided_slot.data(), nd) != SFA_OK) die(std::string("reset: ") + sfa_last_error());
@@ -464,6 +471,14 @@ int realtime_run(int argc, char **argv, double t0) {
                 cover_intervals += static_cast<int64_t>(covered.size());
                 for (const sfa_target_t &iv : covered) cover_bases += iv.end - iv.begin;
                 covered.clear();
+                if (r.group_cap > 0) {  // how deep every group is now; a group whose every column is capped is reported once
+                    if (sfa_session_group_coverage(se, gcov.data(), static_cast<int32_t>(gcov.size())) != SFA_OK) die(std::string("group coverage: ") + sfa_last_error());
+                    for (size_t g = 0; g < group_names.size(); ++g)
+                        if (!group_full[g] && replay::group_is_full(gcov[g].columns, gcov[g].capped)) {
+                            group_full[g] = 1;
+                            if (trace) fprintf(trace, "tick %ld full group=%s\n", (long)tick_now, group_names[g].c_str());
+                        }
+                }
             }
             for (int32_t i = 0; i < n; ++i) {
                 if (!reason[i]) continue;
@@ -486,6 +501,10 @@ int realtime_run(int argc, char **argv, double t0) {
         fprintf(stderr, "[realtime] coverage: cap %d\t%ld intervals, %ld bases added\topen target columns at the end: %ld of %ld\n", r.depth_cap, (long)cover_intervals,
                 (long)cover_bases, (long)open_cols, (long)base_cols);
     if (r.by_name) rep.print_groups(group_names, r.quota, &sch);
+    if (r.group_cap > 0) {
+        fprintf(stderr, "[realtime] group cap %d\t%ld intervals, %ld bases added\n", r.group_cap, (long)cover_intervals, (long)cover_bases);
+        for (size_t g = 0; g < group_names.size(); ++g) fputs(replay::group_cover_line(group_names[g], gcov[g].columns, gcov[g].capped, gcov[g].depth_sum).c_str(), stderr);
+    }
     if (o.verbosity >= 3) rep.print(r, ch, ch.sampling_rate > 0 ? static_cast<double>(r.chunk_samples) / ch.sampling_rate : 0.0);
     if (with_truth) fputs(account.format(r.by_name).c_str(), stderr);
     return 0;

@@ -88,6 +88,18 @@ inline std::string group_tags(int32_t best, int32_t second, float best_score, fl
     return "\ttg:Z:" + name + buf;
 }
 
+// ---- with --group-cap: when a group counts as full, and its line of the summary (Python twins: realtime.group_is_full,
+// realtime.group_cover_line).  A group without columns is never full and has no mean: the quotient is not formed ----
+inline bool group_is_full(int64_t columns, int64_t capped) { return columns > 0 && capped == columns; }
+inline std::string group_cover_line(const std::string &name, int64_t columns, int64_t capped, uint64_t depth_sum) {
+    char buf[160];
+    if (columns > 0)
+        snprintf(buf, sizeof buf, "\tcolumns=%ld capped=%ld mean_depth=%.3f\n", (long)columns, (long)capped, static_cast<double>(depth_sum) / static_cast<double>(columns));
+    else
+        snprintf(buf, sizeof buf, "\tcolumns=0 capped=0 mean_depth=-\n");
+    return "[realtime] group depth " + name + buf;
+}
+
 // ---- with --quota: the tag a line gains behind gm:f: (Python twin: realtime.quota_tags) ----
 // og:Z: names sfa_open_class_t's on_group, the open group the read's best on-target column belongs to; `*`: the ON class is empty
 inline std::string quota_tags(int32_t on_group, const std::vector<std::string> &names) {

@@ -13,6 +13,7 @@
 //   sess::Groups      sfa_session_target_groups: the label table, and of a sfa_session_group_bests call the slot list, keys, results
 //   sess::Open        sfa_session_open_classes: the lowest column of every label, and of a call the slot list, partial minima, results
 //   sess::Coverage    sfa_session_coverage_config: the depth tracks, the live mask, and of a sfa_session_coverage_add call the intervals
+//   sess::GroupCover  sfa_session_group_coverage_config: the live label table, its labels' first columns, the groups' depth records
 //   sess::Spread      SFA_SESSION_SPREAD on a group context: one sub-session per shard, a call's entries dealt to them
 // The host rules -- which waves a call becomes, which points of the automatic start it passes -- are session_plan.hpp's; where a
 // spread session's slots live and how a call is dealt to the shards, session_spread.hpp's.
@@ -26,6 +27,7 @@
 #include "sdtw_session_group.hpp"
 #include "sdtw_session_open.hpp"
 #include "sdtw_session_cover.hpp"
+#include "sdtw_session_groupcover.hpp"
 
 namespace sfa {
 // defined in sfa_align.hip, the unit that holds the plain kernels of sdtw_kernels.hpp
@@ -236,16 +238,43 @@ struct Coverage {  // sfa_session_coverage_config, sfa_session_coverage_add (cov
     Event ev[2];
     float ms = 0.0f;                      // device time of the last add + mask
     bool on() const { return cap > 0; }
-    int reserve(int64_t entries, int64_t total_cols, int32_t num_ref) {
-        return reserve_all(d_depth, 4 * static_cast<size_t>(entries), d_live, 4 * sfa::target_mask_words(total_cols), d_cov_off, 8 * (static_cast<size_t>(num_ref) + 1), d_stats,
-                           sizeof(sfa::CoverStats), h_stats, 2 * sizeof(sfa::CoverStats));
-    }
+    // The tracks (d_depth, d_cov_off, h_cov_off, the intervals of a call, the events) are the session's ONE depth track: the mask's
+    // cap here and the group cap of sess::GroupCover share them.  Whichever is configured first reserves them; they go when both are off.
+    bool has_track() const { return !h_cov_off.empty(); }
+    int reserve_track(int64_t entries, int32_t num_ref) { return reserve_all(d_depth, 4 * static_cast<size_t>(entries), d_cov_off, 8 * (static_cast<size_t>(num_ref) + 1)); }
+    int reserve_mask(int64_t total_cols) { return reserve_all(d_live, 4 * sfa::target_mask_words(total_cols), d_stats, sizeof(sfa::CoverStats), h_stats, 2 * sizeof(sfa::CoverStats)); }
     int reserve_call(size_t n) { return reserve_all(d_iv, sizeof(sfa_target_t) * n, h_iv, sizeof(sfa_target_t) * n); }
-    void free_all() {
+    void free_mask() {  // the mask's cap and what only it uses
         cap = 0, live_cols = 0, first_on = first_off = -1;
+        d_live = DevBuf{}, d_stats = DevBuf{};
+        h_stats = PinBuf{};
+    }
+    void free_track() {
         std::vector<int64_t>().swap(h_cov_off);
-        d_depth = DevBuf{}, d_live = DevBuf{}, d_cov_off = DevBuf{}, d_stats = DevBuf{}, d_iv = DevBuf{};
-        h_stats = PinBuf{}, h_iv = PinBuf{};
+        d_depth = DevBuf{}, d_cov_off = DevBuf{}, d_iv = DevBuf{};
+        h_iv = PinBuf{};
+    }
+};
+
+struct GroupCover {  // sfa_session_group_coverage_config, sfa_session_group_coverage (group_cover_rules.hpp; the tracks are sess::Coverage's)
+    int32_t cap = 0;                      // 0: off
+    std::vector<int32_t> first;           // lowest column of every LIVE label, [n_groups + 1], -1: none (what open_first_cols reads)
+    DevBuf d_live;                        // the live label table: group_label_words(total_cols) words of four labels
+    DevBuf d_first, d_rec;                // [n_groups + 1] i32; [n_groups + 1] sfa_group_cover_t
+    PinBuf h_first, h_rec;                // [2][n_groups + 1]: the tables' initial values, what the launch left
+    Event ev[2];
+    bool on() const { return cap > 0; }
+    // bytes beside the tracks (sfa_session_group_coverage_bytes adds them): what reserve() asks for, through the one function
+    static size_t bytes(int64_t total_cols, int32_t n_groups) { return sfa::group_cover_bytes(total_cols, n_groups); }
+    int reserve(int64_t total_cols, int32_t n_groups) {
+        const size_t e = static_cast<size_t>(n_groups) + 1;
+        return reserve_all(d_live, 8 * sfa::group_label_words(total_cols), d_first, 4 * e, d_rec, sizeof(sfa_group_cover_t) * e, h_first, 2 * 4 * e, h_rec, 2 * sizeof(sfa_group_cover_t) * e);
+    }
+    void free_all() {
+        cap = 0;
+        std::vector<int32_t>().swap(first);
+        d_live = DevBuf{}, d_first = DevBuf{}, d_rec = DevBuf{};
+        h_first = PinBuf{}, h_rec = PinBuf{};
     }
 };
 
@@ -298,6 +327,7 @@ struct sfa_session {
     sess::Groups groups;
     sess::Open open;
     sess::Coverage cover;
+    sess::GroupCover gcover;
     std::unique_ptr<sess::Spread> spread;  // SFA_SESSION_SPREAD on a group context: `c` is the group, everything above is unused
     int32_t name_first = 0, name_step = 1;  // a sub-session of a spread session: local slot l is the caller's slot l * step + first (messages)
 };
@@ -385,6 +415,57 @@ int cover_derive(sfa_session *s, const char *who) {
     if (int rc = cover_enqueue_mask(s)) return rc;
     if (hipStreamSynchronize(s->c->stream) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
     cover_collect(s);
+    return SFA_OK;
+}
+
+// The mask's cap goes, or the group cap; the one depth track goes with the last of them
+void cover_drop_mask(sfa_session *s) {
+    s->cover.free_mask();
+    if (!s->gcover.on()) s->cover.free_track();
+}
+void gcover_drop(sfa_session *s) {
+    s->gcover.free_all();
+    if (!s->cover.on()) s->cover.free_track();
+}
+
+// The live label table from the base table and the depth tracks (session_cover_label_kernel), on the context's stream; the
+// caller has set the device and synchronises.  The upload in front resets the table of firsts the kernel's atomics merge into.
+int gcover_enqueue_labels(sfa_session *s) {
+    sfa_ctx *c = s->c;
+    sess::GroupCover &gc = s->gcover;
+    const size_t entries = static_cast<size_t>(s->groups.n_groups) + 1;
+    int32_t *hf = gc.h_first.as<int32_t>();
+    std::fill(hf, hf + entries, sfa::kNoColumn);
+    HIP_TRY(hipMemcpyAsync(gc.d_first.p, hf, 4 * entries, hipMemcpyHostToDevice, c->stream));
+    sfa::SessionCoverLabelArgs a;
+    a.base = s->groups.d_label.as<uint64_t>();
+    a.live = gc.d_live.as<uint16_t>();
+    a.depth = s->cover.d_depth.as<uint32_t>();
+    a.cov_off = s->cover.d_cov_off.as<int64_t>();
+    a.col_off = s->rows.d_col_off.as<int64_t>();
+    a.ref = c->model.tables();
+    a.first = gc.d_first.as<int32_t>();
+    a.total_cols = c->model.total_cols;
+    a.n_jobs = c->model.n_jobs;
+    a.n_groups = s->groups.n_groups;
+    a.cap = static_cast<uint32_t>(gc.cap);
+    hipLaunchKernelGGL(sfa::session_cover_label_kernel, dim3(sfa::group_cover_blocks(c->model.total_cols)), dim3(sfa::kGroupCoverThreads), 0, c->stream, a);
+    KERNEL_TRY();
+    HIP_TRY(hipMemcpyAsync(hf + entries, gc.d_first.p, 4 * entries, hipMemcpyDeviceToHost, c->stream));
+    return SFA_OK;
+}
+// ... and what it left, once the stream is through
+void gcover_collect(sfa_session *s) {
+    sess::GroupCover &gc = s->gcover;
+    sfa::group_cover_firsts_for_open(gc.h_first.as<int32_t>() + s->groups.n_groups + 1, s->groups.n_groups, &gc.first);
+}
+// the whole live table anew: the base table's bytes (the words behind the row with them), then the derive
+int gcover_derive(sfa_session *s, const char *who) {
+    sfa_ctx *c = s->c;
+    HIP_TRY(hipMemcpyAsync(s->gcover.d_live.p, s->groups.d_label.p, 8 * sfa::group_label_words(c->model.total_cols), hipMemcpyDeviceToDevice, c->stream));
+    if (int rc = gcover_enqueue_labels(s)) return rc;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
+    gcover_collect(s);
     return SFA_OK;
 }
 
@@ -1233,6 +1314,23 @@ struct CoverModel {
                              c->model.h_ref_off.data(), c->model.total_cols};
     }
 };
+
+// The session's one depth track, for whichever cap is configured: reserved and its offsets uploaded, and zeroed when `zero` (the
+// caller's: the other cap is off, so nobody's depth is lost).  The caller has set the device; the stream is idle.
+int cover_track_up(sfa_session *s, const bool zero) {
+    sfa_ctx *c = s->c;
+    sess::Coverage &v = s->cover;
+    const CoverModel cm(s);
+    std::vector<int64_t> cov_off;
+    sfa::coverage_offsets(cm.ref_len.data(), c->model.num_ref, &cov_off);
+    const bool fresh = !v.has_track();
+    if (int rc = v.reserve_track(cov_off.back(), c->model.num_ref)) return rc;
+    if (int rc = sess::create_events(v.ev, 2)) return rc;
+    v.h_cov_off.swap(cov_off);
+    HIP_TRY(hipMemcpyAsync(v.d_cov_off.p, v.h_cov_off.data(), 8 * v.h_cov_off.size(), hipMemcpyHostToDevice, c->stream));
+    if (zero || fresh) HIP_TRY(hipMemsetAsync(v.d_depth.p, 0, 4 * static_cast<size_t>(v.h_cov_off.back()), c->stream));
+    return SFA_OK;
+}
 }  // namespace
 
 namespace sfa {
@@ -1426,7 +1524,7 @@ int sfa_session_targets(sfa_session_t *s, const sfa_target_t *targets, int32_t n
         t.first_on = t.first_off = -1;
         std::vector<uint32_t>().swap(t.h_mask);
         t.d_mask = DevBuf{};  // (freed; the buffers of a call stay for the next mask)
-        s->cover.free_all();  // (a coverage cap lives on the mask: off with it)
+        cover_drop_mask(s);  // (a coverage cap lives on the mask: off with it; a group cap keeps the depth track)
         return SFA_OK;
     }
     if (c->model.total_cols >= INT32_MAX) return fail(SFA_ERANGE, "%s: the reference has %lld columns; the classes count them in 31 bits", who, (long long)c->model.total_cols);
@@ -1567,21 +1665,18 @@ int sfa_session_coverage_config(sfa_session_t *s, int32_t cap) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));  // (a mask in use is not replaced under a kernel)
     if (cap == 0) {
-        v.free_all();
+        cover_drop_mask(s);
         return SFA_OK;
     }
-    const CoverModel cm(s);
-    std::vector<int64_t> cov_off;
-    sfa::coverage_offsets(cm.ref_len.data(), c->model.num_ref, &cov_off);
-    if (int rc = v.reserve(cov_off.back(), c->model.total_cols, c->model.num_ref)) return rc;
-    if (int rc = sess::create_events(v.ev, 2)) return rc;
-    v.h_cov_off.swap(cov_off);
-    HIP_TRY(hipMemcpyAsync(v.d_cov_off.p, v.h_cov_off.data(), 8 * v.h_cov_off.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(v.d_depth.p, 0, 4 * static_cast<size_t>(v.h_cov_off.back()), c->stream));
+    if (int rc = cover_track_up(s, !s->gcover.on())) return rc;  // (a group cap's depth is kept: the track is the session's one)
+    if (int rc = v.reserve_mask(c->model.total_cols)) {
+        cover_drop_mask(s);
+        return rc;
+    }
     HIP_TRY(hipMemsetAsync(v.d_live.p, 0, 4 * sfa::target_mask_words(c->model.total_cols), c->stream));  // (the spare word stays zero)
     v.cap = cap;
-    if (int rc = cover_derive(s, who)) {  // (depth 0 everywhere: the live mask is the base mask)
-        v.free_all();
+    if (int rc = cover_derive(s, who)) {  // (without a group cap the depth is 0 everywhere: the live mask is the base mask)
+        cover_drop_mask(s);
         return rc;
     }
     return SFA_OK;
@@ -1594,7 +1689,7 @@ int sfa_session_coverage_add(sfa_session_t *s, const sfa_target_t *iv, int32_t n
     sfa_session *first = s->spread ? s->spread->subs[0] : s;  // (sub-session 0 always exists; every sub-session holds the same state)
     if (s->spread)
         if (int rc = spread_live(s, who)) return rc;
-    if (!first->cover.on()) return fail(SFA_EINVAL, "%s: the session has no coverage cap (sfa_session_coverage_config)", who);
+    if (!first->cover.on() && !first->gcover.on()) return fail(SFA_EINVAL, "%s: the session has no coverage cap (sfa_session_coverage_config)", who);
     {
         const CoverModel cm(first);
         char msg[192];
@@ -1602,7 +1697,7 @@ int sfa_session_coverage_add(sfa_session_t *s, const sfa_target_t *iv, int32_t n
     }
     if (s->spread) {
         if (int rc = cover_spread_all(s, who, [&](sfa_session *sub) { return sfa_session_coverage_add(sub, iv, n, nullptr); })) return rc;
-        if (open_columns) *open_columns = first->cover.live_cols;  // (shard 0's count: every shard holds the same mask)
+        if (open_columns) *open_columns = sfa_session_target_columns(first);  // (shard 0's count: every shard holds the same mask)
         return SFA_OK;
     }
     sfa_ctx *c = s->c;
@@ -1625,17 +1720,22 @@ int sfa_session_coverage_add(sfa_session_t *s, const sfa_target_t *iv, int32_t n
         hipLaunchKernelGGL(sfa::session_cover_add_kernel, dim3(static_cast<unsigned>(n)), dim3(sfa::kCoverThreads), 0, st, a);
         KERNEL_TRY();
     }
-    if (int rc = cover_enqueue_mask(s)) return rc;
+    // whichever of the live mask and the live labels are on, from the one track, in this call
+    if (v.on())
+        if (int rc = cover_enqueue_mask(s)) return rc;
+    if (s->gcover.on())
+        if (int rc = gcover_enqueue_labels(s)) return rc;
     HIP_TRY(hipEventRecord(v.ev[1], st));
     if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
-    cover_collect(s);
+    if (v.on()) cover_collect(s);
+    if (s->gcover.on()) gcover_collect(s);
     HIP_TRY(hipEventElapsedTime(&v.ms, v.ev[0], v.ev[1]));
     sfa_profile_t pr{};
     pr.segment_reruns = c->seg.seg_reruns;
     pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
     pr.class_ms = pr.total_ms = v.ms;
     c->prof = pr;
-    if (open_columns) *open_columns = v.live_cols;
+    if (open_columns) *open_columns = sfa_session_target_columns(s);  // (the live columns under a mask cap; without one the mask's own)
     return SFA_OK;
 }
 
@@ -1648,13 +1748,106 @@ int sfa_session_coverage_depth(sfa_session_t *s, int32_t contig, uint32_t *out, 
     }
     sfa_ctx *c = s->c;
     sess::Coverage &v = s->cover;
-    if (!v.on()) return fail(SFA_EINVAL, "%s: the session has no coverage cap (sfa_session_coverage_config)", who);
+    if (!v.on() && !s->gcover.on()) return fail(SFA_EINVAL, "%s: the session has no coverage cap (sfa_session_coverage_config)", who);
     if (contig < 0 || contig >= c->model.num_ref) return fail(SFA_EINVAL, "%s: contig %d out of range (the reference has %d)", who, contig, c->model.num_ref);
     const int64_t len = v.h_cov_off[static_cast<size_t>(contig) + 1] - v.h_cov_off[static_cast<size_t>(contig)];
     if (n != len) return fail(SFA_EINVAL, "%s: contig %d has %lld entries (ref_length + 1), not %d", who, contig, static_cast<long long>(len), n);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemcpyAsync(out, v.d_depth.as<uint32_t>() + v.h_cov_off[static_cast<size_t>(contig)], 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return SFA_OK;
+}
+
+// ---- group caps (group_cover_rules.hpp, sdtw_session_groupcover.hpp) ----
+
+size_t sfa_session_group_coverage_bytes(const sfa_ref_t *ref, int flag, int32_t n_groups) {
+    if (!ref || ref->num_ref <= 0 || !ref->ref_lengths || n_groups < 1 || n_groups > sfa::kGroupMax) return 0;
+    int64_t entries = 0, cols = 0;
+    for (int32_t r = 0; r < ref->num_ref; ++r) {
+        if (ref->ref_lengths[r] <= 0) return 0;
+        entries += sfa::coverage_track_len(ref->ref_lengths[r]);
+        cols += static_cast<int64_t>(ref->ref_lengths[r]) * ((flag & SFA_RNA) ? 1 : 2);
+    }
+    return 4 * static_cast<size_t>(entries) + sess::GroupCover::bytes(cols, n_groups);
+}
+
+int sfa_session_group_coverage_config(sfa_session_t *s, int32_t cap) {
+    static const char *const who = "sfa_session_group_coverage_config";
+    if (!s) return fail(SFA_EINVAL, "%s: null session", who);
+    if (cap < 0 || cap > sfa::kGroupCapMax) return fail(SFA_EINVAL, "%s: cap must be 0 (off) .. %d, not %d", who, sfa::kGroupCapMax, cap);
+    if (s->spread) {
+        if (int rc = spread_live(s, who)) return rc;
+        if (cap > 0 && !s->spread->subs[0]->groups.on()) return fail(SFA_EINVAL, "%s: the session has no groups (sfa_session_target_groups)", who);
+        return cover_spread_all(s, who, [&](sfa_session *sub) { return sfa_session_group_coverage_config(sub, cap); });
+    }
+    sfa_ctx *c = s->c;
+    sess::GroupCover &gc = s->gcover;
+    if (cap > 0 && !s->groups.on()) return fail(SFA_EINVAL, "%s: the session has no groups (sfa_session_target_groups)", who);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (a table in use is not replaced under a kernel)
+    if (cap == 0) {
+        gcover_drop(s);
+        return SFA_OK;
+    }
+    // (a mask cap's depth is kept: the track is the session's one.  Whatever fails from here on leaves the group cap off)
+    int rc = cover_track_up(s, !s->cover.on());
+    if (!rc) rc = gc.reserve(c->model.total_cols, s->groups.n_groups);
+    if (!rc) rc = sess::create_events(gc.ev, 2);
+    if (rc) {
+        gcover_drop(s);
+        return rc;
+    }
+    gc.cap = cap;
+    if (int rc = gcover_derive(s, who)) {
+        gcover_drop(s);
+        return rc;
+    }
+    return SFA_OK;
+}
+
+int sfa_session_group_coverage(sfa_session_t *s, sfa_group_cover_t *out, int32_t n) {
+    static const char *const who = "sfa_session_group_coverage";
+    if (!s || !out) return fail(SFA_EINVAL, "%s: bad argument", who);
+    if (s->spread) {
+        if (int rc = spread_live(s, who)) return rc;
+        return sfa_session_group_coverage(s->spread->subs[0], out, n);  // (shard 0 answers: every shard holds the same tables and tracks)
+    }
+    sfa_ctx *c = s->c;
+    sess::GroupCover &gc = s->gcover;
+    if (!gc.on()) return fail(SFA_EINVAL, "%s: the session has no group cap (sfa_session_group_coverage_config)", who);
+    const int32_t entries = s->groups.n_groups + 1;
+    if (n != entries) return fail(SFA_EINVAL, "%s: the session has %d entries (n_groups + 1), not %d", who, entries, n);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    hipStream_t st = c->stream;
+    sfa_group_cover_t *hr = gc.h_rec.as<sfa_group_cover_t>();
+    std::fill(hr, hr + entries, sfa::group_cover_none());
+    HIP_TRY(hipEventRecord(gc.ev[0], st));
+    HIP_TRY(hipMemcpyAsync(gc.d_rec.p, hr, sizeof(sfa_group_cover_t) * static_cast<size_t>(entries), hipMemcpyHostToDevice, st));  // the reset in front of the launch
+    sfa::SessionCoverGroupArgs a;
+    a.base = s->groups.d_label.as<uint64_t>();
+    a.depth = s->cover.d_depth.as<uint32_t>();
+    a.cov_off = s->cover.d_cov_off.as<int64_t>();
+    a.col_off = s->rows.d_col_off.as<int64_t>();
+    a.ref = c->model.tables();
+    a.rec = gc.d_rec.as<sfa_group_cover_t>();
+    a.total_cols = c->model.total_cols;
+    a.n_jobs = c->model.n_jobs;
+    a.n_groups = s->groups.n_groups;
+    a.cap = static_cast<uint32_t>(gc.cap);
+    hipLaunchKernelGGL(sfa::session_cover_group_kernel, dim3(sfa::group_cover_blocks(c->model.total_cols)), dim3(sfa::kGroupCoverThreads), 0, st, a);
+    KERNEL_TRY();
+    HIP_TRY(hipEventRecord(gc.ev[1], st));
+    HIP_TRY(hipMemcpyAsync(hr + entries, gc.d_rec.p, sizeof(sfa_group_cover_t) * static_cast<size_t>(entries), hipMemcpyDeviceToHost, st));
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, gc.ev[0], gc.ev[1]));
+    sfa_profile_t pr{};
+    pr.segment_reruns = c->seg.seg_reruns;
+    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
+    pr.class_ms = pr.total_ms = ms;
+    c->prof = pr;
+    memcpy(out, hr + entries, sizeof(sfa_group_cover_t) * static_cast<size_t>(entries));
     return SFA_OK;
 }
 
@@ -1686,6 +1879,7 @@ int sfa_session_target_groups(sfa_session_t *s, const sfa_group_target_t *target
         g.n_groups = 0;
         std::vector<uint16_t>().swap(g.h_label);
         g.d_label = DevBuf{};  // (freed; the buffers of a call stay for the next table)
+        if (s->gcover.on()) gcover_drop(s);  // (a group cap lives on the labels: off with them)
         return SFA_OK;
     }
     if (c->model.total_cols >= INT32_MAX) return fail(SFA_ERANGE, "%s: the reference has %lld columns; the groups count them in 31 bits", who, (long long)c->model.total_cols);
@@ -1703,11 +1897,28 @@ int sfa_session_target_groups(sfa_session_t *s, const sfa_group_target_t *target
     sfa::group_labels(targets, n, n_groups, m, &label);
     if (int rc = g.reserve(c->model.total_cols)) return rc;
     if (int rc = sess::create_events(g.ev, 2)) return rc;
+    if (s->gcover.on())  // (the live table's tables follow the new n_groups; a group cap never outlives a failure here)
+        if (int rc = s->gcover.reserve(c->model.total_cols, n_groups)) {
+            gcover_drop(s);
+            return rc;
+        }
     g.n_groups = 0;  // (off until the new table is up)
     g.h_label.swap(label);
-    HIP_TRY(hipMemcpyAsync(g.d_label.p, g.h_label.data(), 2 * g.h_label.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    const auto upload = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(g.d_label.p, g.h_label.data(), 2 * g.h_label.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return SFA_OK;
+    };
+    if (int rc = upload()) {
+        if (s->gcover.on()) gcover_drop(s);  // (no groups: no group cap)
+        return rc;
+    }
     g.n_groups = n_groups;
+    if (s->gcover.on()) {  // (the depth is kept: the live table of the new base table)
+        const int rc = gcover_derive(s, who);
+        if (rc) gcover_drop(s);
+        return rc;
+    }
     return SFA_OK;
 }
 
@@ -1758,7 +1969,7 @@ int sfa_session_group_bests(sfa_session_t *s, const int32_t *slot, int32_t n, sf
         sfa::SessionGroupArgs a;
         a.slot = g.d_slot.as<int32_t>();
         a.rows = s->rows.d_row_c.as<float>() + sfa::kSessionPad;
-        a.label = g.d_label.as<uint64_t>();
+        a.label = s->gcover.on() ? s->gcover.d_live.as<uint64_t>() : g.d_label.as<uint64_t>();  // (the kernel is the same: another pointer)
         a.key = g.d_key.as<unsigned long long>();
         a.total_cols = c->model.total_cols;
         a.n = m;
@@ -1833,7 +2044,8 @@ int sfa_session_open_classes(sfa_session_t *s, const int32_t *slot, int32_t n, c
     pr.segment_reruns = c->seg.seg_reruns;
     pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
     if (m > 0) {
-        if (o.first.empty()) sfa::open_label_firsts(g.h_label.data(), c->model.total_cols, g.n_groups, &o.first);
+        const bool capped = s->gcover.on();  // (the live table and its firsts, which the derive left: the kernels are the same)
+        if (!capped && o.first.empty()) sfa::open_label_firsts(g.h_label.data(), c->model.total_cols, g.n_groups, &o.first);
         int32_t *hs = o.h_slot.as<int32_t>();
         for (int32_t k = 0; k < m; ++k) hs[k] = slot[o.live[k]];
         hipStream_t st = c->stream;
@@ -1841,7 +2053,7 @@ int sfa_session_open_classes(sfa_session_t *s, const int32_t *slot, int32_t n, c
         sfa::SessionOpenArgs a;
         a.slot = o.d_slot.as<int32_t>();
         a.rows = s->rows.d_row_c.as<float>() + sfa::kSessionPad;
-        a.label = g.d_label.as<uint64_t>();
+        a.label = capped ? s->gcover.d_live.as<uint64_t>() : g.d_label.as<uint64_t>();
         a.part = o.d_part.as<sfa::ClassPartial>();
         a.total_cols = c->model.total_cols;
         a.n = m;
@@ -1851,12 +2063,12 @@ int sfa_session_open_classes(sfa_session_t *s, const int32_t *slot, int32_t n, c
         ra.part = a.part;
         ra.col_off = s->rows.d_col_off.as<int64_t>();
         ra.ref = c->model.tables();
-        ra.label = g.d_label.as<uint16_t>();
+        ra.label = capped ? s->gcover.d_live.as<uint16_t>() : g.d_label.as<uint16_t>();
         ra.out = o.d_out.as<sfa_open_class_t>();
         ra.n = m;
         ra.n_parts = parts;
         ra.n_jobs = c->model.n_jobs;
-        sfa::open_first_cols(o.first, g.n_groups, a.open, &ra.first_on, &ra.first_off);
+        sfa::open_first_cols(capped ? s->gcover.first : o.first, g.n_groups, a.open, &ra.first_on, &ra.first_off);
         HIP_TRY(hipEventRecord(o.ev[0], st));
         hipLaunchKernelGGL(sfa::sdtw_session_open_kernel, dim3(static_cast<unsigned>(m) * parts), dim3(sfa::kClassThreads), 0, st, a);
         KERNEL_TRY();

@@ -205,7 +205,7 @@ AUTO_START_MAX_SAMPLES, MAX_SKIP_EVENTS = 131072, 4096  # the defaults of --auto
 
 
 def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False, resweep=False,
-           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None, by_name=False, quota=None, truth=None, depth_cap=None):
+           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None, by_name=False, quota=None, truth=None, depth_cap=None, group_cap=None):
     """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
     candidates=1..4 (--candidates): an eighth element, RESULT_DTYPE[4], the channel's candidates at the decision, best first.
     A `session` of the caller's is taken as it is, in this as in its raw mode: it must keep that many candidates already
@@ -242,8 +242,28 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     true_group (None: the read has no truth) and gv (None: the read has no line) -- format_line takes it as truth=(that dict, names).
     summary gains "truth", the account format_truth_summary prints.
     depth_cap=N (--depth-cap N; needs mask targets= with mode=ENRICH, N >= 1, a session that carries start columns): see `depth
-    cap` above.  The items are unchanged; summary gains "cover", a dict with cap, intervals, bases, open and base (columns)."""
+    cap` above.  The items are unchanged; summary gains "cover", a dict with cap, intervals, bases, open and base (columns).
+    group_cap=N (--group-cap N; needs by_name=True and mode=ENRICH, N >= 1, a session that carries start columns; quota= is
+    optional with it; not with depth_cap, mode=DEPLETE or resweep): the session keeps a depth track and a live label table
+    (Session.configure_group_coverage).  One Session.open_classes call per tick decides -- under the quota book's bitmap, or every
+    group open without a quota -- and the items gain the on_group as with a quota.  At the end of a tick the accepted reads'
+    [pos_st, pos_end) go into ONE Session.add_coverage call, ascending channels (trace: `tick T cover n=K open=M`); the live table
+    holds from the next tick on.  Then one Session.group_coverage call: a group whose every column is capped for the first time
+    is reported as `tick T full group=NAME`.  summary gains "group_cover": cap, intervals, bases and records (format_group_cover_summary)."""
     auto = skip < 0
+    if group_cap is not None:  # (before any session exists, each with the fix)
+        if isinstance(group_cap, bool) or not isinstance(group_cap, (int, np.integer)) or group_cap < 1 or group_cap > 1 << 30:
+            raise api.SfaError("replay: group_cap should be an integer 1..1073741824 (None for no cap)")
+        if mode == api.DEPLETE:
+            raise api.SfaError("replay: group_cap with mode=DEPLETE is not built: a covered position would turn on target; use mode=ENRICH")
+        if not by_name or targets is None or mode != api.ENRICH:
+            raise api.SfaError("replay: group_cap closes the covered columns of named groups: pass targets=(group targets, names), by_name=True, mode=ENRICH and margin= with it")
+        if depth_cap is not None:
+            raise api.SfaError("replay: group_cap and depth_cap are two caps over one depth track: pass one of them (depth_cap is for mask targets)")
+        if resweep:
+            raise api.SfaError("replay: group_cap is not available with resweep=True: a resweep session has no target groups")
+        if session is not None and not getattr(session, "starts", True):
+            raise api.SfaError("replay: group_cap needs the rows' start columns for the interval; the session was created with starts=False (SESSION_NO_START)")
     if depth_cap is not None:  # (before any session exists, each with the fix)
         if isinstance(depth_cap, bool) or not isinstance(depth_cap, (int, np.integer)) or depth_cap < 1 or depth_cap > 1 << 30:
             raise api.SfaError("replay: depth_cap should be an integer 1..1073741824 (None for no cap)")
@@ -334,6 +354,13 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
             cover["open"] = se.target_columns()
             if summary is not None:
                 summary["cover"] = cover
+        gcover = None
+        if group_cap is not None:
+            se.configure_group_coverage(group_cap)
+            gcover = dict(cap=int(group_cap), intervals=0, bases=0, records=se.group_coverage(), full=set())
+            if summary is not None:
+                summary["group_cover"] = gcover
+        use_open = book is not None or gcover is not None  # the tick's class call is open_classes; the items gain on_group
         if candidates and not own:
             se.candidates([])  # (raises unless the caller's session keeps candidates)
         sch.start(src)
@@ -347,8 +374,8 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
             rows, info = se.extend_raw(slots, np.concatenate(chunks) if chunks else np.zeros(0, np.int16), raw_off, scaling, [e[4] for e in es])
             cls = action = on_group = None
             if targets is not None:  # one call for the tick, before any reset
-                if book is not None:  # under the groups open at the start of the tick (the book changes in end_tick only)
-                    ocls = se.open_classes(slots, book.open)
+                if use_open:  # under the groups open at the start of the tick (the book changes in end_tick only; no book: every group)
+                    ocls = se.open_classes(slots, None if book is None else book.open)
                     cls, on_group = ocls["cls"].copy(), ocls["on_group"].copy()
                 else:
                     cls = se.classes(slots)
@@ -406,7 +433,7 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                         item += (cls[i].copy(), action[i])
                     if by_name:
                         item += (heads[i].copy() if i in heads else None,)
-                    if book is not None:
+                    if use_open:
                         item += (int(on_group[i]),)
                     if marks is not None:
                         item += (marks[i],)
@@ -419,7 +446,7 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                     yield item
                 se.reset(d_slots)
             tick_now = sch.tick
-            held = sch.end_tick(reason, line, src, action, on_group, None if marks is None else [m and (m["tt"], m["tv"]) for m in marks])
+            held = sch.end_tick(reason, line, src, action, on_group if book is not None else None, None if marks is None else [m and (m["tt"], m["tv"]) for m in marks])
             if cover is not None:  # one call for the tick; the new mask holds from the next tick on
                 covered = [(int(rows[i]["rid"]), int(rows[i]["pos_st"]), int(rows[i]["pos_end"])) for i in decided
                            if line[i] and action[i] == "A" and 0 <= int(rows[i]["pos_st"]) < int(rows[i]["pos_end"])]
@@ -429,6 +456,21 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
                     cover["bases"] += sum(e - b for _, b, e in covered)
                     if trace is not None:
                         trace.append(f"tick {tick_now} cover n={len(covered)} open={cover['open']}")
+            if gcover is not None:  # one add for the tick, then how deep every group is; the live table holds from the next tick on
+                covered = [(int(rows[i]["rid"]), int(rows[i]["pos_st"]), int(rows[i]["pos_end"])) for i in decided
+                           if line[i] and action[i] == "A" and 0 <= int(rows[i]["pos_st"]) < int(rows[i]["pos_end"])]
+                if covered:
+                    n_open = se.add_coverage(covered)
+                    gcover["intervals"] += len(covered)
+                    gcover["bases"] += sum(e - b for _, b, e in covered)
+                    if trace is not None:
+                        trace.append(f"tick {tick_now} cover n={len(covered)} open={n_open}")
+                    gcover["records"] = se.group_coverage()
+                    for g, name in enumerate(group_names):
+                        if g not in gcover["full"] and group_is_full(int(gcover["records"][g]["columns"]), int(gcover["records"][g]["capped"])):
+                            gcover["full"].add(g)
+                            if trace is not None:
+                                trace.append(f"tick {tick_now} full group={name}")
             if marks is not None:
                 for i in decided:
                     note_truth(account, marks[i]["tt"], marks[i]["edge"], action[i], marks[i]["tv"], sch_sent[i], held[i], marks[i]["length"])
@@ -548,6 +590,24 @@ def format_group_summary(summary, names):
     quota = summary.get("quota", 0)
     tail = lambda g: " quota=%d closed_at=%s" % (quota, summary.get(("closed_at", g), "-")) if quota and g < len(names) else ""
     return "".join("[realtime] group %s: accepted %d reads%s\n" % (names[g] if g < len(names) else "*", summary.get(("group", g), 0), tail(g)) for g in range(len(names) + 1))
+
+
+def group_is_full(columns, capped):
+    """replay::group_is_full: every column of the group is capped; a group without columns is never full"""
+    return columns > 0 and capped == columns
+
+
+def group_cover_line(name, columns, capped, depth_sum):
+    """replay::group_cover_line: a named group's line of the summary; `-` for a group without columns (the quotient is not formed)"""
+    mean = "%.3f" % (int(depth_sum) / int(columns)) if columns > 0 else "-"
+    return "[realtime] group depth %s\tcolumns=%d capped=%d mean_depth=%s\n" % (name, columns if columns > 0 else 0, capped if columns > 0 else 0, mean)
+
+
+def format_group_cover_summary(summary, names):
+    """the lines `sigfish-amd realtime --group-cap` adds to its stderr, from summary["group_cover"]"""
+    c = summary["group_cover"]
+    return "[realtime] group cap %d\t%d intervals, %d bases added\n" % (c["cap"], c["intervals"], c["bases"]) + "".join(
+        group_cover_line(n, int(c["records"][g]["columns"]), int(c["records"][g]["capped"]), int(c["records"][g]["depth_sum"])) for g, n in enumerate(names))
 
 
 def format_cover_summary(summary):
