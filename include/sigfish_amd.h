@@ -504,6 +504,52 @@ int sfa_session_group_coverage(sfa_session_t *s, sfa_group_cover_t *out, int32_t
  * entry.  Host arithmetic; 0 for a null or empty reference or n_groups outside 1 .. 1023. */
 size_t sfa_session_group_coverage_bytes(const sfa_ref_t *ref, int flag, int32_t n_groups);
 
+/* ---- reach targets: stranded targets with a lead-in (will the read REACH a target?) ------------------------------------------------
+ * A plain target (sfa_target_t) asks where a read's alignment ends NOW.  A decision is taken after a few hundred events on a read
+ * that runs on for kilobases, and in a direction: on '+' towards higher coordinates, on '-' towards lower ones.  A reach target
+ * is a target with a strand and a lead, the bases in front of it -- in the read's direction -- that count as on target.
+ * With x the coordinate column j of job (contig c, strand s) reports (as for the mask above), target t ADMITS the column when
+ * t.contig == c, t.strand is 0 or s, and
+ *     on '+':  t.begin - t.lead <= x < t.end          on '-':  t.begin <= x < t.end + t.lead
+ * (64-bit bounds; only the coordinates a row reports clip them).  A column is ON target when some target admits it.  Its ANCHOR
+ * is the first base of a target the read will reach: on '+' the minimum over the admitting targets of max(x, t.begin), on '-' the
+ * maximum of min(x, t.end - 1).  With every lead 0 and every strand 0 the mask is sfa_session_targets' and the anchor is x.  On a
+ * context without '-' jobs (SFA_RNA) a '-' target admits nothing; that is allowed.
+ * Under a depth cap (sfa_session_coverage_config) a column of a reach session is live while its bit of the base mask is set and
+ * the depth of its ANCHOR lies below the cap: a lead-in closes when the bases it leads to are covered, not when it is itself.
+ * The mask and the anchors are built on the device from a sorted form of the list prepared on the host.  Memory: the mask of
+ * sfa_session_targets and 4 bytes per column per SESSION (sfa_session_reach_bytes), not counted by sfa_session_bytes; a session
+ * that never calls sfa_session_targets_reach allocates nothing and launches what it launched before.
+ * Target groups (sfa_session_target_groups, open classes, group caps) work from labels and know no reach. */
+typedef struct {
+    int32_t contig, begin, end; /* [begin, end) in the coordinates rows report, as sfa_target_t */
+    int32_t lead;               /* bases in front of the target, in the read's direction, that count as on target */
+    int8_t strand;              /* '+', '-', or 0: both */
+    int8_t pad[3];              /* zero */
+} sfa_reach_target_t;
+
+/* Sets the session's targets from a reach list; it replaces whatever mask the session held, as a later sfa_session_targets
+ * replaces it in turn (and frees the anchors).  n = 0 switches targets off, as sfa_session_targets(s, NULL, 0) does.  Allowed at
+ * any time; the depth track of a cap is kept across either change and the live mask is derived again.  sfa_session_classes,
+ * sfa_session_target_columns and sfa_session_coverage_config / _add / _depth read whichever mask is current.  On a spread session
+ * it goes to every sub-session.
+ * SFA_EINVAL, before anything is written: everything sfa_session_targets refuses (same messages, a SFA_SESSION_RESWEEP session
+ * included), lead < 0 or lead > 2^30, a strand other than 0, '+', '-', padding that is not zero, more than 2^20 targets.
+ * An allocation or device failure AFTER the list has passed (SFA_ENOMEM, SFA_ENODEV, SFA_EKERNEL) leaves the session without
+ * targets, as sfa_session_targets(s, NULL, 0) does -- a mask cap goes with them, and its depth track unless a group cap holds it.
+ * During the call the prepared runs take 16 bytes each on the device (about three per target and strand); they are freed before
+ * it returns. */
+int sfa_session_targets_reach(sfa_session_t *s, const sfa_reach_target_t *targets, int32_t n);
+/* The base mask (n_words: total_columns / 32 rounded up, and one more word, which is zero; bit j & 31 of word j >> 5 is column
+ * j) and the anchors (n_cols: total_columns; the anchor of column j as an index into its contig's depth track -- coordinate -
+ * ref_st_offset -- or -1: the column is off target, or -2: the anchor lies below ref_st_offset, where no row reports and no
+ * depth is counted) back from the device.  Either pointer may be NULL.  On a spread session shard 0 answers.
+ * SFA_EINVAL: no reach targets, n_words or n_cols other than the above. */
+int sfa_session_reach_tables(sfa_session_t *s, uint32_t *mask, size_t n_words, int32_t *anchor, int64_t n_cols);
+/* Device memory the anchors take on a session of a context made from (ref, flag): 4 bytes per column.  Host arithmetic; 0 for a
+ * null or empty reference. */
+size_t sfa_session_reach_bytes(const sfa_ref_t *ref, int flag);
+
 /* ---- truth: a target decision against where a read really came from (host only; no context, no device) --------------------------
  * A read's truth is the interval [begin, end) of `contig` its bases cover on the forward strand; contig < 0: the read belongs
  * nowhere.  These are the rules `sigfish-amd realtime --truth` applies (sigfish_amd/csrc/truth_rules.hpp), exported so that no

@@ -37,6 +37,10 @@ CLASS_DTYPE = np.dtype([("on_score", "<f4"), ("off_score", "<f4"), ("on_rid", "<
                         ("on_strand", "i1"), ("off_strand", "i1"), ("pad", "i1", (2,)), ("n_events", "<i4"), ("valid", "<i4")])  # sfa_class_t
 assert TARGET_DTYPE.itemsize == C.sizeof(_lib.SfaTarget) and CLASS_DTYPE.itemsize == C.sizeof(_lib.SfaClass)
 ENRICH, DEPLETE = 0, 1  # the modes of target_decide
+REACH_TARGET_DTYPE = np.dtype([("contig", "<i4"), ("begin", "<i4"), ("end", "<i4"), ("lead", "<i4"), ("strand", "i1"), ("pad", "i1", (3,))])  # sfa_reach_target_t
+assert REACH_TARGET_DTYPE.itemsize == C.sizeof(_lib.SfaReachTarget) == 20
+REACH_NONE, REACH_BELOW_TRACK = -1, -2  # anchors of reach_tables(): off target; an anchor below st_offset (no depth is counted there)
+REACH_LEAD_MAX = 1 << 30
 GROUP_TARGET_DTYPE = np.dtype([("contig", "<i4"), ("begin", "<i4"), ("end", "<i4"), ("group", "<i4")])  # sfa_group_target_t
 GROUP_BEST_DTYPE = np.dtype([("score", "<f4"), ("rid", "<i4"), ("pos_end", "<i4"), ("strand", "i1"), ("pad", "i1", (3,))])  # sfa_group_best_t
 GROUP_HEAD_DTYPE = np.dtype([("best", "<i4"), ("second", "<i4"), ("best_score", "<f4"), ("second_score", "<f4"), ("n_events", "<i4"),
@@ -706,6 +710,33 @@ class Session:
         t = _targets(intervals)
         _check(self._L.sfa_session_targets(self._h, t.ctypes.data_as(C.POINTER(_lib.SfaTarget)) if len(t) else None, len(t)), "sfa_session_targets")
 
+    def set_reach_targets(self, targets):
+        """The session's targets from a reach list (sfa_session_targets_reach): (contig, begin, end, lead, strand) tuples -- strand
+        '+', '-', or None / '.' / 0 for both -- or a REACH_TARGET_DTYPE array.  A column of a '+' job is on target when its
+        coordinate x has begin - lead <= x < end for a target of its contig and strand, a column of a '-' job when
+        begin <= x < end + lead: the lead is the stretch IN FRONT of the target, in the direction the read goes on.  Its anchor
+        is the first base of a target the read will reach; under configure_coverage() a column stays live while the depth of its
+        ANCHOR lies below the cap.  It replaces the mask of set_targets(), which replaces it in turn; a depth track is kept
+        across both.  An empty list switches targets off.  session_reach_bytes() of memory beside the mask."""
+        self._live()
+        t = _reach_targets(targets)
+        _check(self._L.sfa_session_targets_reach(self._h, t.ctypes.data_as(C.POINTER(_lib.SfaReachTarget)) if len(t) else None, len(t)), "sfa_session_targets_reach")
+
+    def reach_tables(self):
+        """The base mask and the anchors of a reach session as the device holds them (sfa_session_reach_tables) ->
+        (bool[total columns], int32[total columns]): the anchor of a column as an index into its contig's depth track
+        (coordinate - st_offset), REACH_NONE off target, REACH_BELOW_TRACK for an anchor below st_offset."""
+        self._live()
+        cols = int(np.sum(self._al.ref.ref_lengths)) * (1 if self._al.flag & RNA else 2)
+        words = np.zeros((cols + 31) // 32 + 1, np.uint32)
+        anchor = np.zeros(cols, np.int32)
+        _check(self._L.sfa_session_reach_tables(self._h, words.ctypes.data_as(C.POINTER(C.c_uint32)), len(words), anchor.ctypes.data_as(_lib.i32p), cols),
+               "sfa_session_reach_tables")
+        if words[-1] != 0:
+            raise SfaError("sfa_session_reach_tables: the spare word behind the mask is not zero")
+        bits = (words[:-1, None] >> np.arange(32, dtype=np.uint32)[None, :]) & np.uint32(1)
+        return bits.reshape(-1)[:cols].astype(bool), anchor
+
     def target_columns(self):
         """Columns of a slot's row that are on target (0 without targets)."""
         self._live()
@@ -879,6 +910,18 @@ def _targets(intervals):
     return t
 
 
+def _reach_targets(targets):
+    if isinstance(targets, np.ndarray) and targets.dtype == REACH_TARGET_DTYPE:
+        return np.ascontiguousarray(targets).reshape(-1)
+    t = np.zeros(len(targets), REACH_TARGET_DTYPE)
+    for k, (contig, begin, end, lead, strand) in enumerate(targets):
+        code = 0 if strand in (None, 0, ".", "") else (ord(strand) if isinstance(strand, str) and len(strand) == 1 else int(strand))
+        if not -128 <= code <= 127:
+            raise SfaError(f"reach target {k}: strand {strand!r} is none of None, '+', '-'")
+        t[k] = (int(contig), int(begin), int(end), int(lead), code, (0, 0, 0))
+    return t
+
+
 def _group_targets(intervals):
     if isinstance(intervals, np.ndarray) and intervals.dtype == GROUP_TARGET_DTYPE:
         return np.ascontiguousarray(intervals).reshape(-1)
@@ -964,6 +1007,38 @@ def read_targets(path, names):
             except ValueError:
                 raise SfaError(f"read_targets: {path}:{no}: begin and end must be integers") from None
     return _targets(out)
+
+
+def read_reach_targets(path, names, lead, stranded=False):
+    """A BED file as reach targets for Session.set_reach_targets -> REACH_TARGET_DTYPE array: the dialect of read_targets, every
+    target with the lead `lead` (0 .. 2^30).  stranded: column 6 is the target's strand -- '+', '-', or '.' for both; a line
+    without it, or with anything else there, is an error.  Without `stranded` every target is for both strands."""
+    if isinstance(lead, bool) or not isinstance(lead, (int, np.integer)) or not 0 <= int(lead) <= REACH_LEAD_MAX:
+        raise SfaError(f"read_reach_targets: lead should be an integer 0..{REACH_LEAD_MAX}, not {lead!r}")
+    index = {str(n): i for i, n in enumerate(names)}
+    out = []
+    with open(path) as fh:
+        for no, line in enumerate(fh, 1):
+            text = line.strip()
+            if not text or text.startswith("#") or text.split()[0] in ("track", "browser"):
+                continue
+            f = text.split("\t") if "\t" in text else text.split()
+            if len(f) < 3:
+                raise SfaError(f"read_reach_targets: {path}:{no}: a BED line has at least three columns")
+            if f[0] not in index:
+                raise SfaError(f"read_reach_targets: {path}:{no}: contig {f[0]!r} is not in the reference")
+            strand = None
+            if stranded:
+                if len(f) < 6:
+                    raise SfaError(f"read_reach_targets: {path}:{no}: the line has no sixth column (the strand)")
+                if f[5] not in ("+", "-", "."):
+                    raise SfaError(f"read_reach_targets: {path}:{no}: strand {f[5]!r} is none of '+', '-', '.'")
+                strand = None if f[5] == "." else f[5]
+            try:
+                out.append((index[f[0]], int(f[1]), int(f[2]), int(lead), strand))
+            except ValueError:
+                raise SfaError(f"read_reach_targets: {path}:{no}: begin and end must be integers") from None
+    return _reach_targets(out)
 
 
 def read_target_groups(path, names):
@@ -1105,6 +1180,13 @@ def session_coverage_bytes(ref, flag=0):
     coordinate (ref_length + 1 per contig) and a second mask of total_columns / 8 bytes."""
     cref, _keep = ref._as_c()
     return int(_lib.load().sfa_session_coverage_bytes(C.byref(cref), int(flag)))
+
+
+def session_reach_bytes(ref, flag=0):
+    """Device memory Session.set_reach_targets takes beside the mask for a RefModel (sfa_session_reach_bytes; host arithmetic):
+    4 bytes per column, the anchors."""
+    cref, _keep = ref._as_c()
+    return int(_lib.load().sfa_session_reach_bytes(C.byref(cref), int(flag)))
 
 
 def session_group_coverage_bytes(ref, n_groups, flag=0):

@@ -85,6 +85,8 @@ struct RealtimeOpt {
     int64_t quota = 0;             // --quota N: accepted reads after which a named group is closed (needs --by-name --enrich; 0: off)
     int32_t group_cap = 0;         // --group-cap N: a named group's columns close where accepted reads cover them N times (needs --by-name --enrich; 0: off)
     int32_t depth_cap = 0;         // --depth-cap N: target positions covered N times by accepted reads close (needs --targets --enrich, no --by-name; 0: off)
+    int32_t lead = -1;             // --lead N: reach targets (sfa_session_targets_reach), N bases in front of every target in the read's direction (needs --targets, no --by-name; -1: off)
+    bool stranded = false;         // --stranded: column 6 of the BED file is the target's strand ('+', '-', '.'; needs --lead)
     float margin = 0.0f;           // --margin X: cost per query event between the classes (required with --targets: no default)
     std::string truth;             // --truth FILE.paf: where every read came from; lines gain tt / tv (tn / gv), the trace verdict lines (needs --targets)
     std::string trace;             // --trace FILE: the schedule's trace lines (replay.hpp)

@@ -20,7 +20,7 @@ enum LongOpt {
     O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
     O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
     O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE,
-    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_BY_NAME, O_TRACE, O_QUOTA, O_TRUTH, O_DEPTH_CAP, O_GROUP_CAP
+    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_BY_NAME, O_TRACE, O_QUOTA, O_TRUTH, O_DEPTH_CAP, O_GROUP_CAP, O_LEAD, O_STRANDED
 };
 
 const option kLongOptions[] = {
@@ -120,6 +120,7 @@ const option kRealtimeOptions[] = {
     {"targets", required_argument, 0, O_TARGETS}, {"enrich", no_argument, 0, O_ENRICH}, {"deplete", no_argument, 0, O_DEPLETE},
     {"margin", required_argument, 0, O_MARGIN}, {"by-name", no_argument, 0, O_BY_NAME}, {"quota", required_argument, 0, O_QUOTA}, {"trace", required_argument, 0, O_TRACE},
     {"truth", required_argument, 0, O_TRUTH}, {"depth-cap", required_argument, 0, O_DEPTH_CAP}, {"group-cap", required_argument, 0, O_GROUP_CAP},
+    {"lead", required_argument, 0, O_LEAD}, {"stranded", no_argument, 0, O_STRANDED},
     {0, 0, 0, 0}};
 
 void realtime_help(FILE *fp, const RealtimeOpt &r) {
@@ -193,6 +194,12 @@ void realtime_help(FILE *fp, const RealtimeOpt &r) {
                 "                              reads' intervals go into one sfa_session_coverage_add call, and from the next tick on a column whose\n"
                 "                              coordinate has depth >= INT belongs to the background.  The trace gains `cover` lines and\n"
                 "                              `full group=NAME` when every column of a group is capped, the summary a depth line per group [off]\n");
+    fprintf(fp, "   --lead INT                 with --targets (mask targets: not with --by-name / --quota / --group-cap; allowed with --depth-cap and\n"
+                "                              --truth): the INT bases in front of every target, in the read's direction, count as on target --\n"
+                "                              below its begin for a '+' read, above its end for a '-' read (sfa_session_targets_reach).  With\n"
+                "                              --depth-cap a lead-in closes when the first base of the target it leads to is covered.  Schedule,\n"
+                "                              decision rule and tags are unchanged; the summary gains the on-target columns [off]\n");
+    fprintf(fp, "   --stranded                 with --lead: column 6 of the BED file is the target's strand, '+', '-' or '.' for both [both]\n");
     fprintf(fp, "   --truth FILE.paf           with --targets: check every decision against where the read came from -- a PAF file, column 1 the\n"
                 "                              read id, 6 the contig (* for a read that belongs nowhere), 8 and 9 begin and end; a read that\n"
                 "                              shares a base with a target is truly on target.  Lines gain tt:A:<true class T|O, N: not in the\n"
@@ -212,7 +219,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     FILE *fp_help = stderr;
     int c, li = 0;
     bool secondary = false;
-    const char *recal = nullptr, *candidates = nullptr, *margin = nullptr, *quota = nullptr, *depth_cap = nullptr, *group_cap = nullptr;
+    const char *recal = nullptr, *candidates = nullptr, *margin = nullptr, *quota = nullptr, *depth_cap = nullptr, *group_cap = nullptr, *lead = nullptr;
     bool enrich = false, deplete = false;
     while ((c = getopt_long(argc, argv, "p:q:t:v:o:ahV", kRealtimeOptions, &li)) >= 0) {
         switch (c) {
@@ -258,6 +265,8 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
             case O_TRUTH: r.truth = optarg; break;
             case O_DEPTH_CAP: depth_cap = optarg; break;
             case O_GROUP_CAP: group_cap = optarg; break;
+            case O_LEAD: lead = optarg; break;
+            case O_STRANDED: r.stranded = true; break;
             case O_TRACE: r.trace = optarg; break;
             default: realtime_help(stderr, r); exit(EXIT_FAILURE);
         }
@@ -288,6 +297,15 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     if (r.targets.empty() && (enrich || deplete || margin)) die("realtime: --enrich, --deplete and --margin belong to --targets FILE.bed");
     if (r.targets.empty() && r.by_name) die("realtime: --by-name belongs to --targets FILE.bed");
     if (r.targets.empty() && !r.truth.empty()) die("realtime: --truth checks target decisions: pass --targets FILE.bed with --enrich or --deplete and --margin with it");
+    if (lead || r.stranded) {
+        if (r.targets.empty()) die("realtime: --lead and --stranded widen targets in the read's direction: pass --targets FILE.bed with --enrich or --deplete and --margin with them");
+        if (r.by_name || quota || group_cap) die("realtime: --lead and --stranded are for mask targets: with --by-name / --quota / --group-cap they are not built (groups work from labels)");
+        if (!lead) die("realtime: --stranded belongs to --lead: pass --lead N (0 for no lead-in) with it");
+        char *e = nullptr;
+        const long long v = strtoll(lead, &e, 10);
+        if (e == lead || *e || v < 0 || v > (1 << 30)) die("realtime: --lead should be an integer 0..1073741824");
+        r.lead = static_cast<int32_t>(v);
+    }
     if (quota) {
         if (!r.by_name) die("realtime: --quota counts accepted reads per named group: pass --targets FILE.bed --by-name --enrich with it");
         if (deplete) die("realtime: --quota is not available with --deplete (a closed group's reads would be accepted): use --enrich");

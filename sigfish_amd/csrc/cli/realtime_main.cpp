@@ -174,6 +174,34 @@ std::vector<sfa_target_t> read_targets(const std::string &path, const Reference 
     return out;
 }
 
+// --stranded: column 6 of every interval line of the BED file, in the order read_targets keeps them: '+', '-', or 0 for '.'
+std::vector<int8_t> read_strands(const std::string &path) {
+    std::ifstream in(path);
+    if (!in) die("realtime: cannot open the targets file " + path);
+    std::vector<int8_t> out;
+    std::string ln;
+    for (int no = 1; std::getline(in, ln); ++no) {
+        std::istringstream f(ln);
+        std::string name;
+        if (!(f >> name) || name[0] == '#' || name == "track" || name == "browser") continue;
+        std::string field;
+        bool have = true;
+        if (ln.find('\t') != std::string::npos) {  // (tab-separated, as read_targets takes column 4)
+            std::istringstream g(ln);
+            for (int k = 0; k < 6 && have; ++k) have = static_cast<bool>(std::getline(g, field, '\t'));
+            const size_t a = field.find_first_not_of(" \r"), z = field.find_last_not_of(" \r");
+            field = (!have || a == std::string::npos) ? "" : field.substr(a, z - a + 1);
+        } else {
+            for (int k = 1; k < 6 && have; ++k) have = static_cast<bool>(f >> field);
+            if (!have) field.clear();
+        }
+        if (field.empty()) die("realtime: " + path + ":" + std::to_string(no) + ": --stranded needs a sixth column, the strand");
+        if (field != "+" && field != "-" && field != ".") die("realtime: " + path + ":" + std::to_string(no) + ": strand '" + field + "' is none of '+', '-', '.'");
+        out.push_back(field == "." ? 0 : static_cast<int8_t>(field[0]));
+    }
+    return out;
+}
+
 // --truth: the table of the PAF file, contigs by the names of the FASTA file (read here for its names only: the reference proper is
 // built after the BLOW5 file has told the chemistry)
 sfa::TruthTable read_truth(const std::string &path, const std::string &fasta) {
@@ -275,13 +303,27 @@ int realtime_run(int argc, char **argv, double t0) {
             die(std::string("session: ") + sfa_last_error());
     if (r.candidates > 0 && sfa_session_candidates_config(se, r.candidates) != SFA_OK) die(std::string("session: ") + sfa_last_error());
     const bool targets = !r.targets.empty();
+    int64_t reach_cols = 0;  // --lead: the on-target columns of the reach list
     std::vector<std::string> group_names;
     std::vector<sfa_target_t> t;  // (--truth reads both lists again at every decision)
     std::vector<sfa_group_target_t> gt;
     if (targets) {
         t = read_targets(r.targets, ref, r.by_name ? &gt : nullptr, r.by_name ? &group_names : nullptr);
         if (t.empty()) die("realtime: the targets file " + r.targets + " holds no interval");
-        if (sfa_session_targets(se, t.data(), static_cast<int32_t>(t.size())) != SFA_OK) die(std::string("targets: ") + sfa_last_error());
+        if (r.lead >= 0) {  // --lead: the same intervals as reach targets; `t` stays what --truth reads
+            std::vector<int8_t> strands;
+            if (r.stranded) strands = read_strands(r.targets);
+            std::vector<sfa_reach_target_t> rt(t.size());
+            for (size_t k = 0; k < t.size(); ++k) {
+                rt[k] = sfa_reach_target_t{};
+                rt[k].contig = t[k].contig, rt[k].begin = t[k].begin, rt[k].end = t[k].end, rt[k].lead = r.lead;
+                rt[k].strand = r.stranded ? strands[k] : 0;
+            }
+            if (sfa_session_targets_reach(se, rt.data(), static_cast<int32_t>(rt.size())) != SFA_OK) die(std::string("targets: ") + sfa_last_error());
+            reach_cols = sfa_session_target_columns(se);
+        } else if (sfa_session_targets(se, t.data(), static_cast<int32_t>(t.size())) != SFA_OK) {
+            die(std::string("targets: ") + sfa_last_error());
+        }
         if (r.by_name && sfa_session_target_groups(se, gt.data(), static_cast<int32_t>(gt.size()), static_cast<int32_t>(group_names.size())) != SFA_OK)
             die(std::string("target groups: ") + sfa_last_error());
     }
@@ -497,6 +539,7 @@ int realtime_run(int argc, char **argv, double t0) {
     }
     if (trace) fclose(trace);
     if (targets) rep.print_targets();
+    if (r.lead >= 0) fprintf(stderr, "[realtime] reach: lead %d%s\ton-target columns: %ld\n", r.lead, r.stranded ? ", stranded" : "", (long)reach_cols);
     if (r.depth_cap > 0)
         fprintf(stderr, "[realtime] coverage: cap %d\t%ld intervals, %ld bases added\topen target columns at the end: %ld of %ld\n", r.depth_cap, (long)cover_intervals,
                 (long)cover_bases, (long)open_cols, (long)base_cols);

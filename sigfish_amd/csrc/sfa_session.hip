@@ -28,6 +28,7 @@
 #include "sdtw_session_open.hpp"
 #include "sdtw_session_cover.hpp"
 #include "sdtw_session_groupcover.hpp"
+#include "sdtw_session_reach.hpp"
 
 namespace sfa {
 // defined in sfa_align.hip, the unit that holds the plain kernels of sdtw_kernels.hpp
@@ -256,6 +257,22 @@ struct Coverage {  // sfa_session_coverage_config, sfa_session_coverage_add (cov
     }
 };
 
+struct Reach {  // sfa_session_targets_reach (reach_rules.hpp): the mask is sess::Targets', the anchors lie beside it
+    bool on = false;
+    DevBuf d_anchor;                      // [total_cols] i32: the anchor's entry of its contig's depth track
+    DevBuf d_runs, d_run_off, d_stats;    // of a call: the prepared runs, freed when the build is through; the build launch's CoverStats
+    PinBuf h_stats;                       // [0] the record's initial value, [1] what the launch left
+    int reserve(int64_t total_cols, size_t n_runs, int32_t n_jobs) {
+        return reserve_all(d_anchor, sfa::reach_bytes(total_cols), d_runs, sizeof(sfa::ReachRun) * (n_runs + 1), d_run_off, 4 * (static_cast<size_t>(n_jobs) + 1), d_stats,
+                           sizeof(sfa::CoverStats), h_stats, 2 * sizeof(sfa::CoverStats));
+    }
+    void free_all() {
+        on = false;
+        d_anchor = DevBuf{}, d_runs = DevBuf{}, d_run_off = DevBuf{}, d_stats = DevBuf{};
+        h_stats = PinBuf{};
+    }
+};
+
 struct GroupCover {  // sfa_session_group_coverage_config, sfa_session_group_coverage (group_cover_rules.hpp; the tracks are sess::Coverage's)
     int32_t cap = 0;                      // 0: off
     std::vector<int32_t> first;           // lowest column of every LIVE label, [n_groups + 1], -1: none (what open_first_cols reads)
@@ -328,6 +345,7 @@ struct sfa_session {
     sess::Open open;
     sess::Coverage cover;
     sess::GroupCover gcover;
+    sess::Reach reach;
     std::unique_ptr<sess::Spread> spread;  // SFA_SESSION_SPREAD on a group context: `c` is the group, everything above is unused
     int32_t name_first = 0, name_step = 1;  // a sub-session of a spread session: local slot l is the caller's slot l * step + first (messages)
 };
@@ -378,14 +396,34 @@ void reset_slot(sfa_session *s, int32_t sl) {
     if (s->autos.on()) s->autos.reset_slot(sl);
 }
 
-// The live mask from the base mask and the depth tracks (session_cover_mask_kernel), on the context's stream; the caller has
-// set the device and synchronises.  The launch in front resets the record the kernel's atomics merge into.
+// The live mask from the base mask and the depth tracks (session_cover_mask_kernel; on a reach session session_reach_live_kernel,
+// which reads the depth at the column's anchor), on the context's stream; the caller has set the device and synchronises.  The
+// launch in front resets the record the kernel's atomics merge into.
 int cover_enqueue_mask(sfa_session *s) {
     sfa_ctx *c = s->c;
     sess::Coverage &v = s->cover;
     sfa::CoverStats *hs = v.h_stats.as<sfa::CoverStats>();
     hs[0] = sfa::CoverStats{0ull, sfa::kNoColumn, sfa::kNoColumn};
     HIP_TRY(hipMemcpyAsync(v.d_stats.p, hs, sizeof(sfa::CoverStats), hipMemcpyHostToDevice, c->stream));
+    if (s->reach.on) {
+        sfa::SessionReachLiveArgs a;
+        a.base = s->targets.d_mask.as<uint32_t>();
+        a.anchor = s->reach.d_anchor.as<int32_t>();
+        a.live = v.d_live.as<uint32_t>();
+        a.depth = v.d_depth.as<uint32_t>();
+        a.cov_off = v.d_cov_off.as<int64_t>();
+        a.col_off = s->rows.d_col_off.as<int64_t>();
+        a.ref = c->model.tables();
+        a.stats = v.d_stats.as<sfa::CoverStats>();
+        a.total_cols = c->model.total_cols;
+        a.n_jobs = c->model.n_jobs;
+        a.n_words = static_cast<int32_t>(sfa::target_mask_words(c->model.total_cols));
+        a.cap = static_cast<uint32_t>(v.cap);
+        hipLaunchKernelGGL(sfa::session_reach_live_kernel, dim3(sfa::cover_mask_blocks(c->model.total_cols)), dim3(sfa::kCoverThreads), 0, c->stream, a);
+        KERNEL_TRY();
+        HIP_TRY(hipMemcpyAsync(hs + 1, v.d_stats.p, sizeof(sfa::CoverStats), hipMemcpyDeviceToHost, c->stream));
+        return SFA_OK;
+    }
     sfa::SessionCoverMaskArgs a;
     a.base = s->targets.d_mask.as<uint32_t>();
     a.live = v.d_live.as<uint32_t>();
@@ -1524,6 +1562,7 @@ int sfa_session_targets(sfa_session_t *s, const sfa_target_t *targets, int32_t n
         t.first_on = t.first_off = -1;
         std::vector<uint32_t>().swap(t.h_mask);
         t.d_mask = DevBuf{};  // (freed; the buffers of a call stay for the next mask)
+        s->reach.free_all();  // (a reach list's anchors go with its mask)
         cover_drop_mask(s);  // (a coverage cap lives on the mask: off with it; a group cap keeps the depth track)
         return SFA_OK;
     }
@@ -1542,6 +1581,7 @@ int sfa_session_targets(sfa_session_t *s, const sfa_target_t *targets, int32_t n
     const int64_t on_cols = sfa::target_mask(targets, n, m, &mask);
     if (int rc = t.reserve(c->model.total_cols)) return rc;
     if (int rc = sess::create_events(t.ev, 2)) return rc;
+    s->reach.free_all();  // (a plain mask replaces a reach list, before the mask is overwritten: no anchor outlives the mask it belongs to)
     t.h_mask.swap(mask);
     HIP_TRY(hipMemcpyAsync(t.d_mask.p, t.h_mask.data(), 4 * t.h_mask.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1549,7 +1589,113 @@ int sfa_session_targets(sfa_session_t *s, const sfa_target_t *targets, int32_t n
     t.first_on = sfa::target_first_of_class(t.h_mask, c->model.total_cols, true);
     t.first_off = sfa::target_first_of_class(t.h_mask, c->model.total_cols, false);
     t.on = true;
-    if (s->cover.on()) return cover_derive(s, who);  // (the depth is kept: the live mask of the new base mask)
+    if (s->cover.on()) return cover_derive(s, who);  // (the depth is kept: the live mask of the new base mask, read at the column's own coordinate)
+    return SFA_OK;
+}
+
+// ---- reach targets (reach_rules.hpp, sdtw_session_reach.hpp) ----
+
+size_t sfa_session_reach_bytes(const sfa_ref_t *ref, int flag) {
+    if (!ref || ref->num_ref <= 0 || !ref->ref_lengths) return 0;
+    int64_t cols = 0;
+    for (int32_t r = 0; r < ref->num_ref; ++r) {
+        if (ref->ref_lengths[r] <= 0) return 0;
+        cols += static_cast<int64_t>(ref->ref_lengths[r]) * ((flag & SFA_RNA) ? 1 : 2);
+    }
+    return sfa::reach_bytes(cols);
+}
+
+int sfa_session_targets_reach(sfa_session_t *s, const sfa_reach_target_t *targets, int32_t n) {
+    static const char *const who = "sfa_session_targets_reach";
+    if (!s || n < 0 || (n > 0 && !targets)) return fail(SFA_EINVAL, "%s: bad argument", who);
+    if (s->resweep)
+        return fail(SFA_EINVAL, "%s: the session was created with SFA_SESSION_RESWEEP: its carried row belongs to the reversed query, and what its minimum means has "
+                                "not been looked into",
+                    who);
+    if (n == 0) return sfa_session_targets(s, nullptr, 0);  // (targets off, the anchors freed: one path)
+    if (s->spread) {  // every sub-session holds the mask and the anchors, as in sfa_session_targets
+        if (int rc = spread_live(s, who)) return rc;
+        sess::Spread &sp = *s->spread;
+        std::vector<int> rcs(sp.subs.size(), 0);
+        const int rc = sfa::for_each_shard(s->c, [&](size_t r) { return sp.subs[r] ? (rcs[r] = sfa_session_targets_reach(sp.subs[r], targets, n)) : static_cast<int>(SFA_OK); });
+        size_t have = 0, failed = 0;
+        for (size_t r = 0; r < sp.subs.size(); ++r) have += sp.subs[r] != nullptr, failed += rcs[r] != SFA_OK;
+        if (failed != 0 && failed != have) sp.broken = true;
+        return rc;
+    }
+    sfa_ctx *c = s->c;
+    sess::Targets &t = s->targets;
+    sess::Reach &rc_ = s->reach;
+    if (c->model.total_cols >= INT32_MAX) return fail(SFA_ERANGE, "%s: the reference has %lld columns; the classes count them in 31 bits", who, (long long)c->model.total_cols);
+    const CoverModel cm(s);
+    char msg[224];
+    if (sfa::reach_list_error(targets, n, cm.m, msg, sizeof msg)) return fail(SFA_EINVAL, "%s: %s", who, msg);
+    sfa::ReachPrepared prep;
+    sfa::reach_prepare(targets, n, cm.m, &prep);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (a mask in use is not replaced under a kernel)
+    // (from here on the old mask is gone: an allocation or device failure leaves the session without targets -- and so without a
+    // mask cap, which lives on the mask -- never with half of two lists; include/sigfish_amd.h says so)
+    const auto give_up = [&](int rc) {
+        sfa_session_targets(s, nullptr, 0);
+        return rc;
+    };
+    if (int rc = t.reserve(c->model.total_cols)) return give_up(rc);
+    if (int rc = sess::create_events(t.ev, 2)) return give_up(rc);
+    if (int rc = rc_.reserve(c->model.total_cols, prep.runs.size(), c->model.n_jobs)) return give_up(rc);
+    hipStream_t st = c->stream;
+    const size_t words = sfa::target_mask_words(c->model.total_cols);
+    sfa::CoverStats *hs = rc_.h_stats.as<sfa::CoverStats>();
+    hs[0] = sfa::CoverStats{0ull, sfa::kNoColumn, sfa::kNoColumn};
+    sfa::SessionReachBuildArgs a;
+    a.runs = rc_.d_runs.as<sfa::ReachRun>();
+    a.run_off = rc_.d_run_off.as<int32_t>();
+    a.col_off = s->rows.d_col_off.as<int64_t>();
+    a.mask = t.d_mask.as<uint32_t>();
+    a.anchor = rc_.d_anchor.as<int32_t>();
+    a.stats = rc_.d_stats.as<sfa::CoverStats>();
+    a.total_cols = c->model.total_cols;
+    a.n_jobs = c->model.n_jobs;
+    a.n_words = static_cast<int32_t>(words);
+    const auto enqueue = [&]() -> int {  // (the uploads read pageable memory: they are through when the calls return)
+        HIP_TRY(hipMemcpyAsync(rc_.d_stats.p, hs, sizeof(sfa::CoverStats), hipMemcpyHostToDevice, st));
+        if (!prep.runs.empty()) HIP_TRY(hipMemcpyAsync(rc_.d_runs.p, prep.runs.data(), sizeof(sfa::ReachRun) * prep.runs.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(rc_.d_run_off.p, prep.run_off.data(), 4 * prep.run_off.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(t.d_mask.p, 0, 4 * words, st));  // (the spare word stays zero)
+        hipLaunchKernelGGL(sfa::session_reach_build_kernel, dim3(sfa::cover_mask_blocks(c->model.total_cols)), dim3(sfa::kCoverThreads), 0, st, a);
+        KERNEL_TRY();
+        HIP_TRY(hipMemcpyAsync(hs + 1, rc_.d_stats.p, sizeof(sfa::CoverStats), hipMemcpyDeviceToHost, st));
+        return SFA_OK;
+    };
+    if (int rc = enqueue()) return give_up(rc);
+    if (hipStreamSynchronize(st) != hipSuccess) return give_up(fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError())));
+    rc_.d_runs = DevBuf{}, rc_.d_run_off = DevBuf{};  // (the runs were the call's: only the anchors and the 16-byte record stay)
+    std::vector<uint32_t>().swap(t.h_mask);  // (the mask was built on the device: sfa_session_reach_tables copies it back)
+    t.on_cols = static_cast<int64_t>(hs[1].live);
+    t.first_on = hs[1].first_on == sfa::kNoColumn ? -1 : hs[1].first_on;
+    t.first_off = hs[1].first_off == sfa::kNoColumn ? -1 : hs[1].first_off;
+    t.on = true;
+    rc_.on = true;
+    if (s->cover.on()) return cover_derive(s, who);  // (the depth is kept: the live mask of the new base mask and its anchors)
+    return SFA_OK;
+}
+
+int sfa_session_reach_tables(sfa_session_t *s, uint32_t *mask, size_t n_words, int32_t *anchor, int64_t n_cols) {
+    static const char *const who = "sfa_session_reach_tables";
+    if (!s) return fail(SFA_EINVAL, "%s: null session", who);
+    if (s->spread) {
+        if (int rc = spread_live(s, who)) return rc;
+        return sfa_session_reach_tables(s->spread->subs[0], mask, n_words, anchor, n_cols);  // (shard 0 answers: every shard holds the same tables)
+    }
+    sfa_ctx *c = s->c;
+    if (!s->reach.on) return fail(SFA_EINVAL, "%s: the session has no reach targets (sfa_session_targets_reach)", who);
+    const size_t words = sfa::target_mask_words(c->model.total_cols);
+    if (mask && n_words != words) return fail(SFA_EINVAL, "%s: n_words is %zu; the mask has %zu words", who, n_words, words);
+    if (anchor && n_cols != c->model.total_cols) return fail(SFA_EINVAL, "%s: n_cols is %lld; a row has %lld columns", who, (long long)n_cols, (long long)c->model.total_cols);
+    HIP_TRY(hipSetDevice(c->device));
+    if (mask) HIP_TRY(hipMemcpyAsync(mask, s->targets.d_mask.p, 4 * words, hipMemcpyDeviceToHost, c->stream));
+    if (anchor) HIP_TRY(hipMemcpyAsync(anchor, s->reach.d_anchor.p, 4 * static_cast<size_t>(n_cols), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return SFA_OK;
 }
 

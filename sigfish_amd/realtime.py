@@ -205,7 +205,7 @@ AUTO_START_MAX_SAMPLES, MAX_SKIP_EVENTS = 131072, 4096  # the defaults of --auto
 
 
 def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False, resweep=False,
-           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None, by_name=False, quota=None, truth=None, depth_cap=None, group_cap=None):
+           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None, by_name=False, quota=None, truth=None, depth_cap=None, group_cap=None, lead=None, stranded=False):
     """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
     candidates=1..4 (--candidates): an eighth element, RESULT_DTYPE[4], the channel's candidates at the decision, best first.
     A `session` of the caller's is taken as it is, in this as in its raw mode: it must keep that many candidates already
@@ -249,8 +249,25 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     group open without a quota -- and the items gain the on_group as with a quota.  At the end of a tick the accepted reads'
     [pos_st, pos_end) go into ONE Session.add_coverage call, ascending channels (trace: `tick T cover n=K open=M`); the live table
     holds from the next tick on.  Then one Session.group_coverage call: a group whose every column is capped for the first time
-    is reported as `tick T full group=NAME`.  summary gains "group_cover": cap, intervals, bases and records (format_group_cover_summary)."""
+    is reported as `tick T full group=NAME`.  summary gains "group_cover": cap, intervals, bases and records (format_group_cover_summary).
+    lead=N (--lead N; needs mask targets=, 0 <= N <= 2^30; not with by_name / quota / group_cap, allowed with depth_cap and truth): the
+    session's targets are reach targets (Session.set_reach_targets) -- every interval with the lead N in front of it in the read's
+    direction.  stranded=True (--stranded; needs lead=): targets= is a REACH_TARGET_DTYPE array whose strands are kept
+    (api.read_reach_targets(path, names, N, stranded=True)); without it every target is for both strands.  Schedule, decision
+    rule, items and tags are unchanged; truth reads the intervals without their leads.  summary gains "reach": lead, stranded
+    and columns, the on-target columns (format_reach_summary)."""
     auto = skip < 0
+    if lead is not None or stranded:  # (before any session exists, each with the fix)
+        if targets is None:
+            raise api.SfaError("replay: lead / stranded widen targets in the read's direction: pass targets= with mode= and margin= with them")
+        if by_name or quota is not None or group_cap is not None:
+            raise api.SfaError("replay: lead / stranded are for mask targets: with by_name / quota / group_cap they are not built (groups work from labels)")
+        if lead is None:
+            raise api.SfaError("replay: stranded belongs to lead=: pass lead=N (0 for no lead-in) with it")
+        if isinstance(lead, bool) or not isinstance(lead, (int, np.integer)) or lead < 0 or lead > api.REACH_LEAD_MAX:
+            raise api.SfaError("replay: lead should be an integer 0..1073741824")
+        if stranded and not (isinstance(targets, np.ndarray) and targets.dtype == api.REACH_TARGET_DTYPE):
+            raise api.SfaError("replay: stranded=True takes targets= as a REACH_TARGET_DTYPE array (api.read_reach_targets(path, names, lead, stranded=True))")
     if group_cap is not None:  # (before any session exists, each with the fix)
         if isinstance(group_cap, bool) or not isinstance(group_cap, (int, np.integer)) or group_cap < 1 or group_cap > 1 << 30:
             raise api.SfaError("replay: group_cap should be an integer 1..1073741824 (None for no cap)")
@@ -293,6 +310,16 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
         targets = np.zeros(len(group_targets), api.TARGET_DTYPE)
         for f in ("contig", "begin", "end"):
             targets[f] = group_targets[f]
+    reach_targets = None
+    if lead is not None:  # the reach list for the session; `targets` stays the plain intervals (truth reads them)
+        src_t = targets if isinstance(targets, np.ndarray) and targets.dtype == api.REACH_TARGET_DTYPE else api._targets(targets)
+        reach_targets = np.zeros(len(src_t), api.REACH_TARGET_DTYPE)
+        targets = np.zeros(len(src_t), api.TARGET_DTYPE)
+        for f in ("contig", "begin", "end"):
+            reach_targets[f] = targets[f] = src_t[f]
+        reach_targets["lead"] = int(lead)
+        if stranded:
+            reach_targets["strand"] = src_t["strand"]
     if targets is None and (mode is not None or margin is not None):
         raise api.SfaError("replay: mode and margin belong to targets=")
     if targets is not None:  # (all of it before any session exists)
@@ -343,7 +370,11 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
             se.configure_raw(max_skip_events if auto else skip, norm, query, recal_points(norm, query, recalibrate, at_end), at_end)
             if auto:
                 se.configure_auto_start(chunk_samples if auto_start_every is None else auto_start_every, auto_start_max_samples)
-        if targets is not None:
+        if reach_targets is not None:
+            se.set_reach_targets(reach_targets)
+            if summary is not None:
+                summary["reach"] = dict(lead=int(lead), stranded=bool(stranded), columns=se.target_columns())
+        elif targets is not None:
             se.set_targets(targets)
         if by_name:
             se.set_target_groups(group_targets, len(group_names))
@@ -608,6 +639,12 @@ def format_group_cover_summary(summary, names):
     c = summary["group_cover"]
     return "[realtime] group cap %d\t%d intervals, %d bases added\n" % (c["cap"], c["intervals"], c["bases"]) + "".join(
         group_cover_line(n, int(c["records"][g]["columns"]), int(c["records"][g]["capped"]), int(c["records"][g]["depth_sum"])) for g, n in enumerate(names))
+
+
+def format_reach_summary(summary):
+    """the line `sigfish-amd realtime --lead` adds to its stderr, from summary["reach"]"""
+    c = summary["reach"]
+    return "[realtime] reach: lead %d%s\ton-target columns: %d\n" % (c["lead"], ", stranded" if c["stranded"] else "", c["columns"])
 
 
 def format_cover_summary(summary):

@@ -34,14 +34,18 @@ MARGINS = (0.0, 0.01, 0.02, 0.05, 0.1, 0.2, 0.4)
 MIN_EVENTS = (30, 50, 100, 200)
 
 
-def observe(al, reads, channels, chunk, query, targets, say):
-    """-> per read a list of (n_events, on, off, calibrated, samples sent) per tick, to the read's end (or until its query is full)"""
+def observe(al, reads, channels, chunk, query, targets, say, apply=None):
+    """-> per read a list of (n_events, on, off, calibrated, samples sent) per tick, to the read's end (or until its query is full).
+    apply(session): sets the session's targets in place of Session.set_targets(targets) (tools/session_reach_truth.py)"""
     records = [[] for _ in reads]
     nxt, on, sent = 0, [-1] * channels, [0] * channels
     ticks = 0
     with al.session(channels) as se:
         se.configure_raw(SKIP, NORM, query)
-        se.set_targets(targets)
+        if apply is None:
+            se.set_targets(targets)
+        else:
+            apply(se)
         while True:
             for c in range(channels):
                 if on[c] < 0 and nxt < len(reads):
