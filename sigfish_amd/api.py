@@ -432,11 +432,13 @@ class Aligner:
         return (rows, info, hs, qev) if return_events else (rows, info, hs)
 
     def inflate_device(self, streams, cap_factor=4, cap_extra=4096):
-        """The device-side DEFLATE decoder alone: list of zlib streams -> list of bytes (None where the decoder declined)."""
+        """The device-side DEFLATE decoder alone: list of zlib streams -> list of bytes (None where the decoder declined).  Stream i
+        gets a slot of len(stream) * cap_factor + cap_extra bytes, the slots back to back; cap_extra: one number, or one per stream."""
         n = len(streams)
         in_off = np.concatenate([[0], np.cumsum([len(x) for x in streams])]).astype(np.int64)
         blob = np.frombuffer(b"".join(streams) + b"\0" * 8, np.uint8)
-        out_off = np.concatenate([[0], np.cumsum([len(x) * cap_factor + cap_extra for x in streams])]).astype(np.int64)
+        extra = np.broadcast_to(np.asarray(cap_extra, np.int64), (n,))
+        out_off = np.concatenate([[0], np.cumsum([len(x) * cap_factor + int(e) for x, e in zip(streams, extra)])]).astype(np.int64)
         out = np.zeros(int(out_off[-1]) + 8, np.uint8)
         lens = np.zeros(max(n, 1), np.int32)
         _check(self._L.sfa_inflate_zlib_device(self._h, blob.ctypes.data_as(C.c_void_p), in_off.ctypes.data_as(_lib.i64p), n,
@@ -445,11 +447,13 @@ class Aligner:
         return [None if lens[i] < 0 else out[out_off[i]:out_off[i] + lens[i]].tobytes() for i in range(n)]
 
     def zstd_device(self, streams, cap_factor=4, cap_extra=4096):
-        """The device-side zstd decoder alone: list of zstd records -> list of bytes (None where the decoder declined)."""
+        """The device-side zstd decoder alone: list of zstd records -> list of bytes (None where the decoder declined).  Slots as
+        inflate_device's, each rounded up to 16 bytes."""
         n = len(streams)
         in_off = np.concatenate([[0], np.cumsum([len(x) for x in streams])]).astype(np.int64)
         blob = np.frombuffer(b"".join(streams) + b"\0" * 8, np.uint8)
-        out_off = np.concatenate([[0], np.cumsum([(len(x) * cap_factor + cap_extra + 15) & ~15 for x in streams])]).astype(np.int64)
+        extra = np.broadcast_to(np.asarray(cap_extra, np.int64), (n,))
+        out_off = np.concatenate([[0], np.cumsum([(len(x) * cap_factor + int(e) + 15) & ~15 for x, e in zip(streams, extra)])]).astype(np.int64)
         out = np.zeros(int(out_off[-1]) + 8, np.uint8)
         lens = np.zeros(max(n, 1), np.int32)
         _check(self._L.sfa_zstd_device(self._h, blob.ctypes.data_as(C.c_void_p), in_off.ctypes.data_as(_lib.i64p), n,

@@ -203,7 +203,7 @@ __device__ __forceinline__ void inf_build_fast(const uint16_t *count, const uint
 __device__ inline int inflate_zlib_lane(const uint8_t *in, int64_t n_in, uint8_t *out, int64_t cap, InflateLds &S) {
     if (n_in < 6) return -1;
     const uint32_t cmf = in[0], flg = in[1];
-    if ((cmf & 15) != 8 || ((cmf << 8) | flg) % 31 != 0 || (flg & 0x20)) return -1;  // deflate, header check, no preset dictionary
+    if ((cmf & 15u) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31 != 0 || (flg & 0x20u)) return -1;  // deflate, <= 32 KB window, no dictionary
     BitReader br;
     br.init(in + 2, n_in - 2 - 4);
     int64_t op = 0;

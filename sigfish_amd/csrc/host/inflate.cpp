@@ -106,7 +106,8 @@ inline uint32_t symbol_entry(int alphabet, int sym, uint32_t bits) {
 }
 
 // Canonical Huffman decode table: `primary` bits resolved directly, longer codes through subtables appended behind
-// the 2^primary first entries.  Unused slots stay kInvalid.  Returns false on an over-subscribed code.
+// the 2^primary first entries.  Unused slots stay kInvalid.  Returns false on an over-subscribed code and on an incomplete one
+// (with the two exceptions below).
 // Symbols are visited in code order (by length, then by value); the bit-reversed code -- the table index, DEFLATE packs
 // codes starting from their most significant bit -- is advanced with a reversed increment instead of being recomputed.
 bool build_table(const uint8_t *lens, int n_sym, int alphabet, int primary, uint32_t *table, int capacity) {
@@ -119,6 +120,10 @@ bool build_table(const uint8_t *lens, int n_sym, int alphabet, int primary, uint
         if (left < 0) return false;
         if (count[l]) max_len = l;
     }
+    // An incomplete code is refused as zlib's inflate and the device (blow5_kernels.hpp: inf_build) refuse it, whether or not the
+    // stream ever sends an unassigned pattern: only a literal/length or distance code that is a single code of one bit may be
+    // incomplete, and a code without any symbol (a block without matches; every pattern stays invalid).
+    if (left > 0 && max_len != 0 && (alphabet == 2 || max_len != 1)) return false;
     uint16_t offs[kMaxCodeLen + 2], sorted[288];
     offs[1] = 0;
     for (int l = 1; l <= kMaxCodeLen; ++l) offs[l + 1] = static_cast<uint16_t>(offs[l] + count[l]);

@@ -1,7 +1,12 @@
 // device_inflate_host.cpp -- TEST HARNESS.  The per-lane DEFLATE decoder of the device-side BLOW5 reader
 // (sigfish_amd/csrc/blow5_kernels.hpp: inflate_zlib_lane, the body of blow5_inflate_kernel) compiled for the HOST, so that it can
 // run under AddressSanitizer / UBSan (not available for GPU code on this pool) and against zlib on far more streams than a GPU
-// test budget allows.  usage: device_inflate_host [iterations] [seed]
+// test budget allows.  usage: device_inflate_host [iterations] [seed] [cases.bin]
+// cases.bin (written by tests/deflate_craft.py, flat_file(): crafted streams, answers from zlib): u32 count, then per case
+//   u32 kind (1: sound, decodes to `plain`; 0: refused; 2: sound for zlib, declined here by design -- bytes behind the stream),
+//   u32 plain bytes, u32 stream bytes, plain, stream.
+// Every record sits in a heap block of exactly its size plus the padding the device gives its input (random bytes: what lies behind a
+// record there is the next record), every output in a heap block of exactly its slot: a byte beside either is a sanitizer report.
 #define SFA_HOST_HARNESS
 #include "../../sigfish_amd/csrc/blow5_kernels.hpp"
 
@@ -9,11 +14,78 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <vector>
+
+namespace {
+constexpr size_t kInPad = 128;  // ctx::Blow5::reserve_inflate: the device's input buffer ends 128 bytes behind the last record
+
+// one stream through the lane decoder: input and output in exact-size heap blocks, decoder state as stale as the last record left it
+int decode(const uint8_t *stream, size_t n, uint8_t *out, int64_t cap, sfa::InflateLds &S) {
+    std::unique_ptr<uint8_t[]> in(new uint8_t[n + kInPad]);
+    if (n) memcpy(in.get(), stream, n);
+    for (size_t i = n; i < n + kInPad; ++i) in[i] = rand() & 255;
+    return sfa::inflate_zlib_lane(in.get(), static_cast<int64_t>(n), out, cap, S);
+}
+
+// the crafted cases; returns the number of failures, -1 where the file cannot be read
+int crafted(const char *path) {
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        printf("cannot open %s\n", path);
+        return -1;
+    }
+    uint32_t count = 0;
+    if (fread(&count, 4, 1, f) != 1) return -1;
+    int n_sound = 0, n_refused = 0, n_design = 0, bad = 0;
+    sfa::InflateLds S;
+    memset(&S, 0xa5, sizeof S);
+    for (uint32_t k = 0; k < count; ++k) {
+        uint32_t h[3];
+        if (fread(h, 4, 3, f) != 3) return -1;
+        std::vector<uint8_t> plain(h[1]), stream(h[2]);
+        if (h[1] && fread(plain.data(), 1, h[1], f) != h[1]) return -1;
+        if (h[2] && fread(stream.data(), 1, h[2], f) != h[2]) return -1;
+        bool ok;
+        int r;
+        if (h[0]) {
+            ++n_sound;
+            std::unique_ptr<uint8_t[]> out(new uint8_t[h[1] ? h[1] : 1]);  // exactly what it needs: not a byte more may be written
+            r = decode(stream.data(), stream.size(), out.get(), h[1], S);
+            ok = r == static_cast<int>(h[1]) && (h[1] == 0 || memcmp(out.get(), plain.data(), h[1]) == 0);
+            if (h[0] == 2) {  // zlib's bytes or declined
+                n_design += r == -1;
+                ok = ok || r == -1;
+            }
+            if (ok && h[1] > 0) {  // a slot one byte short declines
+                std::unique_ptr<uint8_t[]> small(new uint8_t[h[1] - 1 ? h[1] - 1 : 1]);
+                ok = decode(stream.data(), stream.size(), small.get(), h[1] - 1, S) == -1;
+            }
+        } else {  // room for anything a crafted text holds: refused for its own reason, not for a full slot
+            ++n_refused;
+            const int64_t cap = 1 << 17;
+            std::unique_ptr<uint8_t[]> out(new uint8_t[cap]);
+            r = decode(stream.data(), stream.size(), out.get(), cap, S);
+            ok = r == -1;
+        }
+        if (!ok) {
+            ++bad;
+            printf("FAIL crafted case %u (%s): %u plain, %u stream bytes, got %d\n", k, h[0] ? "sound" : "refused", h[1], h[2], r);
+        }
+    }
+    fclose(f);
+    printf("crafted: %d sound, %d refused, %d failures\n", n_sound, n_refused, bad);
+    printf("crafted: %d of the sound ones declined by design\n", n_design);
+    return bad;
+}
+}  // namespace
 
 int main(int argc, char **argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 4000;
     srand(argc > 2 ? atoi(argv[2]) : 1);
+    int bad_crafted = 0;
+    if (argc > 3 && (bad_crafted = crafted(argv[3])) < 0) return 2;
+    srand(argc > 2 ? atoi(argv[2]) : 1);  // (the random campaign draws what it drew before there were crafted cases)
     int bad = 0;
     for (int it = 0; it < iters; ++it) {
         const int n = rand() % (it % 50 == 0 ? 120000 : 9000);
@@ -63,5 +135,5 @@ int main(int argc, char **argv) {
         }
     }
     printf("%d iterations, %d failures\n", iters, bad);
-    return bad != 0;
+    return bad != 0 || bad_crafted != 0;
 }

@@ -109,7 +109,9 @@ def test_device_inflate_lane_decoder_on_the_host_with_sanitizers(tmp_path):
     """The per-lane DEFLATE decoder of the device-side BLOW5 reader (blow5_kernels.hpp: the body of blow5_inflate_kernel),
     compiled for the host: against zlib on 4 000 random streams (every block type, encoder setting and window size,
     arbitrary bytes behind the stream), too-small output slots, corrupted streams -- under ASan + UBSan, which the GPU pool
-    cannot run."""
+    cannot run.  In front of them the crafted streams of tests/deflate_craft.py (answers from zlib): every sound one decodes into
+    a heap block of exactly its size and is refused in one a byte smaller, every refused one is refused; the only sound streams
+    declined are the ones with bytes behind them (the lane decoder takes the Adler-32 from the end of the record)."""
     import shutil
     if not shutil.which("g++"):
         pytest.skip("no g++")
@@ -119,8 +121,18 @@ def test_device_inflate_lane_decoder_on_the_host_with_sanitizers(tmp_path):
     if build.returncode != 0 and b"sanitize" in build.stderr:
         pytest.skip("toolchain without sanitizer runtimes")
     assert build.returncode == 0, build.stderr.decode()[-2000:]
-    run = subprocess.run([exe, "4000", "3"], capture_output=True, timeout=900)
+    from tests import deflate_craft as D
+    from tests.test_deflate_craft_cpu import LANE_MAY_DECLINE
+    flat = str(tmp_path / "cases.bin")
+    D.flat_file(flat)
+    run = subprocess.run([exe, "4000", "3", flat], capture_output=True, timeout=900)
     assert run.returncode == 0 and b"4000 iterations, 0 failures" in run.stdout, (run.stdout + run.stderr).decode()[-3000:]
+    text = (run.stdout + run.stderr).decode()
+    n_sound = sum(1 for _, s in D.CASES if D.expected(s) is not None)
+    assert n_sound > 200 and len(D.CASES) - n_sound > 400
+    assert f"crafted: {n_sound} sound, {len(D.CASES) - n_sound} refused, 0 failures" in text, text[-3000:]
+    assert f"crafted: {len(LANE_MAY_DECLINE)} of the sound ones declined by design" in text, text[-3000:]
+    assert "ERROR: AddressSanitizer" not in text and "runtime error" not in text, text[-3000:]
 
 
 @pytest.mark.parametrize("sanitizers", [False, True])
