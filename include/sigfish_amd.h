@@ -520,7 +520,8 @@ size_t sfa_session_group_coverage_bytes(const sfa_ref_t *ref, int flag, int32_t 
  * The mask and the anchors are built on the device from a sorted form of the list prepared on the host.  Memory: the mask of
  * sfa_session_targets and 4 bytes per column per SESSION (sfa_session_reach_bytes), not counted by sfa_session_bytes; a session
  * that never calls sfa_session_targets_reach allocates nothing and launches what it launched before.
- * Target groups (sfa_session_target_groups, open classes, group caps) work from labels and know no reach. */
+ * Target groups (sfa_session_target_groups, open classes, group caps) work from labels; a label table with reach is set by
+ * sfa_session_target_groups_reach below.  The mask's anchors and a label table's are two tables: neither knows of the other. */
 typedef struct {
     int32_t contig, begin, end; /* [begin, end) in the coordinates rows report, as sfa_target_t */
     int32_t lead;               /* bases in front of the target, in the read's direction, that count as on target */
@@ -549,6 +550,50 @@ int sfa_session_reach_tables(sfa_session_t *s, uint32_t *mask, size_t n_words, i
 /* Device memory the anchors take on a session of a context made from (ref, flag): 4 bytes per column.  Host arithmetic; 0 for a
  * null or empty reference. */
 size_t sfa_session_reach_bytes(const sfa_ref_t *ref, int flag);
+
+/* ---- reach groups: named target groups with a lead-in (WHICH target will the read reach?) -------------------------------------
+ * A reach group target is a reach target with a group id in [0, n_groups), 1 <= n_groups <= 1023.  Admission and the ANCHOR of a
+ * column are those of the reach targets above, with the groups dropped: groups do not enter them.  The LABEL of a column is the
+ * lowest group id among the admitting targets whose own anchor (max(x, t.begin) on '+', min(x, t.end - 1) on '-') equals the
+ * column's anchor -- the target the read reaches first, ties to the lowest id -- or n_groups, the background, when nobody admits
+ * the column.  With every lead 0 and every strand 0 the table is sfa_session_target_groups' bit for bit; inside a target's body
+ * another group's lead-in never takes the label.
+ * The label table replaces the session's label table; its anchors (one int32 per column, an index into the contig's depth track,
+ * -1: background, -2: below ref_st_offset) are the label table's own and independent of a mask's.  sfa_session_group_bests,
+ * sfa_session_open_classes and sfa_session_group_count work unchanged on it.  Under a group cap
+ * (sfa_session_group_coverage_config) the live label of a column is its base label while the depth of its ANCHOR lies below the
+ * cap (-2: depth 0): a lead-in closes when the base it leads to is covered, not when it is itself.  sfa_session_group_coverage
+ * on a reach label table counts the forward jobs' BODY columns only, by base label -- a body column is one whose anchor is its
+ * own coordinate; a lead-in column is part of no record, so a group that has only '-' targets has an empty record, and so has the
+ * background.
+ * Both tables are built on the device from a sorted form of the list prepared on the host.  Memory: 2 + 4 bytes per column per
+ * SESSION (sfa_session_group_reach_bytes), not counted by sfa_session_bytes; a session that never calls
+ * sfa_session_target_groups_reach allocates nothing new and launches what it launched before. */
+typedef struct {
+    int32_t contig, begin, end; /* [begin, end) in the coordinates rows report, as sfa_target_t */
+    int32_t lead;               /* bases in front of the target, in the read's direction, that carry its label */
+    int32_t group;              /* 0 .. n_groups - 1 */
+    int8_t strand;              /* '+', '-', or 0: both */
+    int8_t pad[3];              /* zero */
+} sfa_reach_group_target_t;
+
+/* Sets the session's label table from a reach group list; it replaces whatever label table the session held, as a later
+ * sfa_session_target_groups replaces it in turn (and frees the group anchors).  n = 0 switches groups off, as
+ * sfa_session_target_groups(s, NULL, 0, 0) does.  Allowed at any time; the depth track of a group cap is kept and the live table
+ * is derived again.  On a spread session it goes to every sub-session.
+ * SFA_EINVAL, before anything is written: everything sfa_session_targets_reach refuses (same messages, a SFA_SESSION_RESWEEP
+ * session included), n_groups outside 1 .. 1023, a group id outside [0, n_groups).
+ * An allocation or device failure AFTER the list has passed leaves the session without groups, as
+ * sfa_session_target_groups(s, NULL, 0, 0) does -- a group cap goes with them.  During the call the prepared runs take 20 bytes
+ * each on the device; they are freed before it returns. */
+int sfa_session_target_groups_reach(sfa_session_t *s, const sfa_reach_group_target_t *targets, int32_t n, int32_t n_groups);
+/* The BASE label table (n_cols: total_columns; one uint16 per column) and its anchors (n_cols int32, as above) back from the
+ * device.  Either pointer may be NULL.  On a spread session shard 0 answers.
+ * SFA_EINVAL: no reach groups, n_cols other than total_columns. */
+int sfa_session_group_reach_tables(sfa_session_t *s, uint16_t *label, int32_t *anchor, int64_t n_cols);
+/* Device memory the two tables take on a session of a context made from (ref, flag): 2 + 4 bytes per column.  Host arithmetic;
+ * 0 for a null or empty reference. */
+size_t sfa_session_group_reach_bytes(const sfa_ref_t *ref, int flag);
 
 /* ---- truth: a target decision against where a read really came from (host only; no context, no device) --------------------------
  * A read's truth is the interval [begin, end) of `contig` its bases cover on the forward strand; contig < 0: the read belongs

@@ -11,6 +11,7 @@ from .api import (END, DTW, EVENT_DTYPE, INV, REF, RNA, RESULT_DTYPE, SESSION_NO
                   AUTO_NO_EVENT, AUTO_BEYOND_MAX, AUTO_AT_FINAL, session_keep_bytes, session_coverage_bytes, session_group_coverage_bytes, GROUP_COVER_DTYPE, map_offsets, BLOW5_INFLATE, BLOW5_FIELDS, BLOW5_STREAM, PRESS_NONE, PRESS_ZLIB, PRESS_ZSTD, zstd_decompress,
                   TARGET_DTYPE, CLASS_DTYPE, ENRICH, DEPLETE, target_decide, read_targets,
                   REACH_TARGET_DTYPE, REACH_NONE, REACH_BELOW_TRACK, REACH_LEAD_MAX, read_reach_targets, session_reach_bytes,
+                  REACH_GROUP_TARGET_DTYPE, read_reach_target_groups, session_group_reach_bytes,
                   GROUP_TARGET_DTYPE, GROUP_BEST_DTYPE, GROUP_HEAD_DTYPE, GROUP_MAX, group_decide, read_target_groups,
                   OPEN_CLASS_DTYPE, open_words, QuotaBook,
                   read_truth, truth_class, truth_edge, truth_group, truth_verdict, truth_group_verdict)
@@ -21,4 +22,5 @@ __all__ = ["Aligner", "Session", "session_bytes", "session_raw_bytes", "EventStr
            "GROUP_TARGET_DTYPE", "GROUP_BEST_DTYPE", "GROUP_HEAD_DTYPE", "GROUP_MAX", "group_decide", "read_target_groups",
            "OPEN_CLASS_DTYPE", "open_words", "QuotaBook",
            "REACH_TARGET_DTYPE", "REACH_NONE", "REACH_BELOW_TRACK", "REACH_LEAD_MAX", "read_reach_targets", "session_reach_bytes",
+           "REACH_GROUP_TARGET_DTYPE", "read_reach_target_groups", "session_group_reach_bytes",
            "read_truth", "truth_class", "truth_edge", "truth_group", "truth_verdict", "truth_group_verdict"]

@@ -64,6 +64,11 @@ class SfaReachTarget(C.Structure):
     _fields_ = [("contig", C.c_int32), ("begin", C.c_int32), ("end", C.c_int32), ("lead", C.c_int32), ("strand", C.c_int8), ("pad", C.c_int8 * 3)]
 
 
+class SfaReachGroupTarget(C.Structure):
+    _fields_ = [("contig", C.c_int32), ("begin", C.c_int32), ("end", C.c_int32), ("lead", C.c_int32), ("group", C.c_int32), ("strand", C.c_int8),
+                ("pad", C.c_int8 * 3)]
+
+
 class SfaClass(C.Structure):
     _fields_ = [("on_score", C.c_float), ("off_score", C.c_float), ("on_rid", C.c_int32), ("on_pos_end", C.c_int32), ("off_rid", C.c_int32),
                 ("off_pos_end", C.c_int32), ("on_strand", C.c_int8), ("off_strand", C.c_int8), ("pad", C.c_int8 * 2), ("n_events", C.c_int32),
@@ -108,6 +113,7 @@ SYMBOLS = ["sfa_init", "sfa_init_devices", "sfa_n_devices", "sfa_align_batch", "
            "sfa_session_coverage_config", "sfa_session_coverage_add", "sfa_session_coverage_depth", "sfa_session_coverage_bytes",
            "sfa_session_group_coverage_config", "sfa_session_group_coverage", "sfa_session_group_coverage_bytes",
            "sfa_session_targets_reach", "sfa_session_reach_tables", "sfa_session_reach_bytes",
+           "sfa_session_target_groups_reach", "sfa_session_group_reach_tables", "sfa_session_group_reach_bytes",
            "sfa_truth_class", "sfa_truth_edge", "sfa_truth_group", "sfa_truth_verdict", "sfa_truth_group_verdict"]
 
 _lib = None
@@ -262,6 +268,10 @@ def load():
     L.sfa_session_reach_tables.argtypes = [vp, C.POINTER(C.c_uint32), C.c_size_t, i32p, C.c_int64]
     L.sfa_session_reach_bytes.argtypes = [C.POINTER(SfaRef), C.c_int]
     L.sfa_session_reach_bytes.restype = C.c_size_t
+    L.sfa_session_target_groups_reach.argtypes = [vp, C.POINTER(SfaReachGroupTarget), C.c_int32, C.c_int32]
+    L.sfa_session_group_reach_tables.argtypes = [vp, C.POINTER(C.c_uint16), i32p, C.c_int64]
+    L.sfa_session_group_reach_bytes.argtypes = [C.POINTER(SfaRef), C.c_int]
+    L.sfa_session_group_reach_bytes.restype = C.c_size_t
     L.sfa_truth_class.argtypes = L.sfa_truth_edge.argtypes = [C.POINTER(SfaTarget), C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.sfa_truth_group.argtypes = [C.POINTER(SfaGroupTarget), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.sfa_truth_group.restype = C.c_int32

@@ -39,6 +39,9 @@ assert TARGET_DTYPE.itemsize == C.sizeof(_lib.SfaTarget) and CLASS_DTYPE.itemsiz
 ENRICH, DEPLETE = 0, 1  # the modes of target_decide
 REACH_TARGET_DTYPE = np.dtype([("contig", "<i4"), ("begin", "<i4"), ("end", "<i4"), ("lead", "<i4"), ("strand", "i1"), ("pad", "i1", (3,))])  # sfa_reach_target_t
 assert REACH_TARGET_DTYPE.itemsize == C.sizeof(_lib.SfaReachTarget) == 20
+REACH_GROUP_TARGET_DTYPE = np.dtype([("contig", "<i4"), ("begin", "<i4"), ("end", "<i4"), ("lead", "<i4"), ("group", "<i4"), ("strand", "i1"),
+                                     ("pad", "i1", (3,))])  # sfa_reach_group_target_t
+assert REACH_GROUP_TARGET_DTYPE.itemsize == C.sizeof(_lib.SfaReachGroupTarget) == 24
 REACH_NONE, REACH_BELOW_TRACK = -1, -2  # anchors of reach_tables(): off target; an anchor below st_offset (no depth is counted there)
 REACH_LEAD_MAX = 1 << 30
 GROUP_TARGET_DTYPE = np.dtype([("contig", "<i4"), ("begin", "<i4"), ("end", "<i4"), ("group", "<i4")])  # sfa_group_target_t
@@ -771,6 +774,32 @@ class Session:
         _check(self._L.sfa_session_target_groups(self._h, t.ctypes.data_as(C.POINTER(_lib.SfaGroupTarget)) if len(t) else None, len(t), int(n_groups)),
                "sfa_session_target_groups")
 
+    def set_reach_target_groups(self, targets, n_groups):
+        """The session's target groups from a reach group list (sfa_session_target_groups_reach): (contig, begin, end, lead,
+        group, strand) tuples -- strand as for set_reach_targets -- or a REACH_GROUP_TARGET_DTYPE array, 0 <= group < n_groups
+        <= 1023.  Admission and the anchor of a column are set_reach_targets'; the label of a column is the lowest group among
+        the admitting targets the read reaches first (whose own anchor is the column's), the background (n_groups) where nobody
+        admits it.  It replaces the label table of set_target_groups(), which replaces it in turn.  group_bests(), open_classes()
+        and group_count() work unchanged; under configure_group_coverage() a column stays live while the depth of its ANCHOR lies
+        below the cap, and group_coverage() counts the '+' jobs' body columns only.  An empty list switches groups off.
+        session_group_reach_bytes() of memory."""
+        self._live()
+        t = _reach_group_targets(targets)
+        _check(self._L.sfa_session_target_groups_reach(self._h, t.ctypes.data_as(C.POINTER(_lib.SfaReachGroupTarget)) if len(t) else None, len(t), int(n_groups)),
+               "sfa_session_target_groups_reach")
+
+    def group_reach_tables(self):
+        """The base label table and its anchors of a session with reach groups as the device holds them
+        (sfa_session_group_reach_tables) -> (uint16[total columns], int32[total columns]): the anchor of a column as an index into
+        its contig's depth track, REACH_NONE for a background column, REACH_BELOW_TRACK for an anchor below st_offset."""
+        self._live()
+        cols = int(np.sum(self._al.ref.ref_lengths)) * (1 if self._al.flag & RNA else 2)
+        label = np.zeros(cols, np.uint16)
+        anchor = np.zeros(cols, np.int32)
+        _check(self._L.sfa_session_group_reach_tables(self._h, label.ctypes.data_as(C.POINTER(C.c_uint16)), anchor.ctypes.data_as(_lib.i32p), cols),
+               "sfa_session_group_reach_tables")
+        return label, anchor
+
     def group_count(self):
         """n_groups of the session (0 without groups)."""
         self._live()
@@ -926,6 +955,18 @@ def _reach_targets(targets):
     return t
 
 
+def _reach_group_targets(targets):
+    if isinstance(targets, np.ndarray) and targets.dtype == REACH_GROUP_TARGET_DTYPE:
+        return np.ascontiguousarray(targets).reshape(-1)
+    t = np.zeros(len(targets), REACH_GROUP_TARGET_DTYPE)
+    for k, (contig, begin, end, lead, group, strand) in enumerate(targets):
+        code = 0 if strand in (None, 0, ".", "") else (ord(strand) if isinstance(strand, str) and len(strand) == 1 else int(strand))
+        if not -128 <= code <= 127:
+            raise SfaError(f"reach group target {k}: strand {strand!r} is none of None, '+', '-'")
+        t[k] = (int(contig), int(begin), int(end), int(lead), int(group), code, (0, 0, 0))
+    return t
+
+
 def _group_targets(intervals):
     if isinstance(intervals, np.ndarray) and intervals.dtype == GROUP_TARGET_DTYPE:
         return np.ascontiguousarray(intervals).reshape(-1)
@@ -1075,6 +1116,25 @@ def read_target_groups(path, names):
     return _group_targets(out), list(groups)
 
 
+def read_reach_target_groups(path, names, lead, stranded=False):
+    """A BED file as reach group targets for Session.set_reach_target_groups -> (REACH_GROUP_TARGET_DTYPE array, group names):
+    read_target_groups' dialect and numbering of the names (column 4), every target with the lead `lead` (0 .. 2^30).  stranded:
+    column 6 is the target's strand as in read_reach_targets; without it every target is for both strands."""
+    if isinstance(lead, bool) or not isinstance(lead, (int, np.integer)) or not 0 <= int(lead) <= REACH_LEAD_MAX:
+        raise SfaError(f"read_reach_target_groups: lead should be an integer 0..{REACH_LEAD_MAX}, not {lead!r}")
+    try:
+        plain, groups = read_target_groups(path, names)
+        strands = read_reach_targets(path, names, int(lead), stranded=True)["strand"] if stranded else 0
+    except SfaError as e:
+        raise SfaError(str(e).replace("read_target_groups:", "read_reach_target_groups:").replace("read_reach_targets:", "read_reach_target_groups:")) from None
+    t = np.zeros(len(plain), REACH_GROUP_TARGET_DTYPE)
+    for f in ("contig", "begin", "end", "group"):
+        t[f] = plain[f]
+    t["lead"] = int(lead)
+    t["strand"] = strands
+    return t, groups
+
+
 def read_truth(path, names):
     """A PAF file as the truth of replay(truth=) -> {read id: (contig index, begin, end)}, (-1, 0, 0) for a read that belongs nowhere
     (the twin of truth_rules.hpp's TruthTable; what `sigfish-amd eval` takes as truth): column 1 the read id, column 6 the contig's
@@ -1184,6 +1244,13 @@ def session_coverage_bytes(ref, flag=0):
     coordinate (ref_length + 1 per contig) and a second mask of total_columns / 8 bytes."""
     cref, _keep = ref._as_c()
     return int(_lib.load().sfa_session_coverage_bytes(C.byref(cref), int(flag)))
+
+
+def session_group_reach_bytes(ref, flag=0):
+    """Device memory Session.set_reach_target_groups takes for a RefModel (sfa_session_group_reach_bytes; host arithmetic): the
+    label table's 2 and the anchors' 4 bytes per column."""
+    cref, _keep = ref._as_c()
+    return int(_lib.load().sfa_session_group_reach_bytes(C.byref(cref), int(flag)))
 
 
 def session_reach_bytes(ref, flag=0):

@@ -86,6 +86,8 @@ struct RealtimeOpt {
     int32_t group_cap = 0;         // --group-cap N: a named group's columns close where accepted reads cover them N times (needs --by-name --enrich; 0: off)
     int32_t depth_cap = 0;         // --depth-cap N: target positions covered N times by accepted reads close (needs --targets --enrich, no --by-name; 0: off)
     int32_t lead = -1;             // --lead N: reach targets (sfa_session_targets_reach), N bases in front of every target in the read's direction (needs --targets, no --by-name; -1: off)
+    int32_t group_lead = -1;       // --group-lead N: reach groups (sfa_session_target_groups_reach), N bases in front of every named target carry its label; the mask gets the same lead (needs --by-name --enrich; -1: off)
+    bool group_stranded = false;   // --group-stranded: column 6 of the BED file is the target's strand (needs --group-lead)
     bool stranded = false;         // --stranded: column 6 of the BED file is the target's strand ('+', '-', '.'; needs --lead)
     float margin = 0.0f;           // --margin X: cost per query event between the classes (required with --targets: no default)
     std::string truth;             // --truth FILE.paf: where every read came from; lines gain tt / tv (tn / gv), the trace verdict lines (needs --targets)

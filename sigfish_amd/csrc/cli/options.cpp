@@ -20,7 +20,7 @@ enum LongOpt {
     O_KMER_MODEL = 256, O_RNA, O_DEBUG_BREAK, O_DTW_STD, O_INVERT, O_FULL_REF, O_FROM_END, O_PROFILE_CPU, O_ACCEL, O_PORE, O_DEVICE,
     O_SECONDARY, O_METH_MODEL, O_HOST_EVENTS, O_STREAMS, O_HOST_PARSE, O_GPU_PARSE, O_RANKS, O_SHARD, O_READ_RANGE, O_NO_HEADER,
     O_RANK_BUFFER, O_HOST_PATHS, O_DEVICE_PATHS, O_CHANNELS, O_CHUNK_SAMPLES, O_NORM_EVENTS, O_MIN_EVENTS, O_MIN_MAPQ, O_PACE,
-    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_BY_NAME, O_TRACE, O_QUOTA, O_TRUTH, O_DEPTH_CAP, O_GROUP_CAP, O_LEAD, O_STRANDED
+    O_RECALIBRATE, O_RECALIBRATE_AT_END, O_RESWEEP, O_CANDIDATES, O_SECONDARY_STRIPS, O_SPREAD, O_TARGETS, O_ENRICH, O_DEPLETE, O_MARGIN, O_BY_NAME, O_TRACE, O_QUOTA, O_TRUTH, O_DEPTH_CAP, O_GROUP_CAP, O_LEAD, O_STRANDED, O_GROUP_LEAD, O_GROUP_STRANDED
 };
 
 const option kLongOptions[] = {
@@ -120,7 +120,7 @@ const option kRealtimeOptions[] = {
     {"targets", required_argument, 0, O_TARGETS}, {"enrich", no_argument, 0, O_ENRICH}, {"deplete", no_argument, 0, O_DEPLETE},
     {"margin", required_argument, 0, O_MARGIN}, {"by-name", no_argument, 0, O_BY_NAME}, {"quota", required_argument, 0, O_QUOTA}, {"trace", required_argument, 0, O_TRACE},
     {"truth", required_argument, 0, O_TRUTH}, {"depth-cap", required_argument, 0, O_DEPTH_CAP}, {"group-cap", required_argument, 0, O_GROUP_CAP},
-    {"lead", required_argument, 0, O_LEAD}, {"stranded", no_argument, 0, O_STRANDED},
+    {"lead", required_argument, 0, O_LEAD}, {"stranded", no_argument, 0, O_STRANDED}, {"group-lead", required_argument, 0, O_GROUP_LEAD}, {"group-stranded", no_argument, 0, O_GROUP_STRANDED},
     {0, 0, 0, 0}};
 
 void realtime_help(FILE *fp, const RealtimeOpt &r) {
@@ -200,6 +200,12 @@ void realtime_help(FILE *fp, const RealtimeOpt &r) {
                 "                              --depth-cap a lead-in closes when the first base of the target it leads to is covered.  Schedule,\n"
                 "                              decision rule and tags are unchanged; the summary gains the on-target columns [off]\n");
     fprintf(fp, "   --stranded                 with --lead: column 6 of the BED file is the target's strand, '+', '-' or '.' for both [both]\n");
+    fprintf(fp, "   --group-lead INT           with --targets --by-name --enrich (optionally --quota, --group-cap, --truth; not with --lead,\n"
+                "                              --depth-cap, --deplete): the INT bases in front of every named target, in the read's direction, carry\n"
+                "                              the label of the target the read reaches first (sfa_session_target_groups_reach); the mask gets the\n"
+                "                              same lead.  With --group-cap a lead-in closes when the first base of the target it leads to is\n"
+                "                              covered.  Lines, tags and trace are --by-name's; the summary gains the labelled columns [off]\n");
+    fprintf(fp, "   --group-stranded           with --group-lead: column 6 of the BED file is the target's strand, '+', '-' or '.' for both [both]\n");
     fprintf(fp, "   --truth FILE.paf           with --targets: check every decision against where the read came from -- a PAF file, column 1 the\n"
                 "                              read id, 6 the contig (* for a read that belongs nowhere), 8 and 9 begin and end; a read that\n"
                 "                              shares a base with a target is truly on target.  Lines gain tt:A:<true class T|O, N: not in the\n"
@@ -219,7 +225,7 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     FILE *fp_help = stderr;
     int c, li = 0;
     bool secondary = false;
-    const char *recal = nullptr, *candidates = nullptr, *margin = nullptr, *quota = nullptr, *depth_cap = nullptr, *group_cap = nullptr, *lead = nullptr;
+    const char *recal = nullptr, *candidates = nullptr, *margin = nullptr, *quota = nullptr, *depth_cap = nullptr, *group_cap = nullptr, *lead = nullptr, *group_lead = nullptr;
     bool enrich = false, deplete = false;
     while ((c = getopt_long(argc, argv, "p:q:t:v:o:ahV", kRealtimeOptions, &li)) >= 0) {
         switch (c) {
@@ -267,6 +273,8 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
             case O_GROUP_CAP: group_cap = optarg; break;
             case O_LEAD: lead = optarg; break;
             case O_STRANDED: r.stranded = true; break;
+            case O_GROUP_LEAD: group_lead = optarg; break;
+            case O_GROUP_STRANDED: r.group_stranded = true; break;
             case O_TRACE: r.trace = optarg; break;
             default: realtime_help(stderr, r); exit(EXIT_FAILURE);
         }
@@ -297,6 +305,17 @@ RealtimeOpt parse_realtime_options(int argc, char **argv) {
     if (r.targets.empty() && (enrich || deplete || margin)) die("realtime: --enrich, --deplete and --margin belong to --targets FILE.bed");
     if (r.targets.empty() && r.by_name) die("realtime: --by-name belongs to --targets FILE.bed");
     if (r.targets.empty() && !r.truth.empty()) die("realtime: --truth checks target decisions: pass --targets FILE.bed with --enrich or --deplete and --margin with it");
+    if (group_lead || r.group_stranded) {
+        if (!r.by_name) die("realtime: --group-lead and --group-stranded widen named groups in the read's direction: pass --targets FILE.bed --by-name --enrich --margin X with them");
+        if (lead || r.stranded) die("realtime: --group-lead and --lead are two leads: with --by-name pass --group-lead alone (the mask gets the same lead)");
+        if (depth_cap) die("realtime: --group-lead with --depth-cap is not built: --depth-cap is for mask targets; the cap of named groups is --group-cap");
+        if (deplete) die("realtime: --group-lead with --deplete is not built: use --enrich");
+        if (!group_lead) die("realtime: --group-stranded belongs to --group-lead: pass --group-lead N (0 for no lead-in) with it");
+        char *e = nullptr;
+        const long long v = strtoll(group_lead, &e, 10);
+        if (e == group_lead || *e || v < 0 || v > (1 << 30)) die("realtime: --group-lead should be an integer 0..1073741824");
+        r.group_lead = static_cast<int32_t>(v);
+    }
     if (lead || r.stranded) {
         if (r.targets.empty()) die("realtime: --lead and --stranded widen targets in the read's direction: pass --targets FILE.bed with --enrich or --deplete and --margin with them");
         if (r.by_name || quota || group_cap) die("realtime: --lead and --stranded are for mask targets: with --by-name / --quota / --group-cap they are not built (groups work from labels)");

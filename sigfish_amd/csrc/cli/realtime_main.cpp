@@ -175,7 +175,7 @@ std::vector<sfa_target_t> read_targets(const std::string &path, const Reference 
 }
 
 // --stranded: column 6 of every interval line of the BED file, in the order read_targets keeps them: '+', '-', or 0 for '.'
-std::vector<int8_t> read_strands(const std::string &path) {
+std::vector<int8_t> read_strands(const std::string &path, const char *option = "--stranded") {
     std::ifstream in(path);
     if (!in) die("realtime: cannot open the targets file " + path);
     std::vector<int8_t> out;
@@ -195,7 +195,7 @@ std::vector<int8_t> read_strands(const std::string &path) {
             for (int k = 1; k < 6 && have; ++k) have = static_cast<bool>(f >> field);
             if (!have) field.clear();
         }
-        if (field.empty()) die("realtime: " + path + ":" + std::to_string(no) + ": --stranded needs a sixth column, the strand");
+        if (field.empty()) die("realtime: " + path + ":" + std::to_string(no) + ": " + option + " needs a sixth column, the strand");
         if (field != "+" && field != "-" && field != ".") die("realtime: " + path + ":" + std::to_string(no) + ": strand '" + field + "' is none of '+', '-', '.'");
         out.push_back(field == "." ? 0 : static_cast<int8_t>(field[0]));
     }
@@ -303,29 +303,40 @@ int realtime_run(int argc, char **argv, double t0) {
             die(std::string("session: ") + sfa_last_error());
     if (r.candidates > 0 && sfa_session_candidates_config(se, r.candidates) != SFA_OK) die(std::string("session: ") + sfa_last_error());
     const bool targets = !r.targets.empty();
-    int64_t reach_cols = 0;  // --lead: the on-target columns of the reach list
+    int64_t reach_cols = 0;  // --lead: the on-target columns of the reach list; --group-lead: the labelled columns, which are the same columns
     std::vector<std::string> group_names;
     std::vector<sfa_target_t> t;  // (--truth reads both lists again at every decision)
     std::vector<sfa_group_target_t> gt;
     if (targets) {
         t = read_targets(r.targets, ref, r.by_name ? &gt : nullptr, r.by_name ? &group_names : nullptr);
         if (t.empty()) die("realtime: the targets file " + r.targets + " holds no interval");
-        if (r.lead >= 0) {  // --lead: the same intervals as reach targets; `t` stays what --truth reads
-            std::vector<int8_t> strands;
-            if (r.stranded) strands = read_strands(r.targets);
+        const bool group_reach = r.group_lead >= 0;  // --group-lead: mask and labels from the one list with the one lead
+        std::vector<int8_t> strands;
+        if (r.stranded || r.group_stranded) strands = read_strands(r.targets, r.stranded ? "--stranded" : "--group-stranded");
+        if (r.lead >= 0 || group_reach) {  // --lead: the same intervals as reach targets; `t` stays what --truth reads
             std::vector<sfa_reach_target_t> rt(t.size());
             for (size_t k = 0; k < t.size(); ++k) {
                 rt[k] = sfa_reach_target_t{};
-                rt[k].contig = t[k].contig, rt[k].begin = t[k].begin, rt[k].end = t[k].end, rt[k].lead = r.lead;
-                rt[k].strand = r.stranded ? strands[k] : 0;
+                rt[k].contig = t[k].contig, rt[k].begin = t[k].begin, rt[k].end = t[k].end, rt[k].lead = group_reach ? r.group_lead : r.lead;
+                rt[k].strand = strands.empty() ? 0 : strands[k];
             }
             if (sfa_session_targets_reach(se, rt.data(), static_cast<int32_t>(rt.size())) != SFA_OK) die(std::string("targets: ") + sfa_last_error());
             reach_cols = sfa_session_target_columns(se);
         } else if (sfa_session_targets(se, t.data(), static_cast<int32_t>(t.size())) != SFA_OK) {
             die(std::string("targets: ") + sfa_last_error());
         }
-        if (r.by_name && sfa_session_target_groups(se, gt.data(), static_cast<int32_t>(gt.size()), static_cast<int32_t>(group_names.size())) != SFA_OK)
+        if (group_reach) {  // the labels of the same list: which named target the read reaches first; `gt` stays what --truth reads
+            std::vector<sfa_reach_group_target_t> rg(gt.size());
+            for (size_t k = 0; k < gt.size(); ++k) {
+                rg[k] = sfa_reach_group_target_t{};
+                rg[k].contig = gt[k].contig, rg[k].begin = gt[k].begin, rg[k].end = gt[k].end, rg[k].lead = r.group_lead, rg[k].group = gt[k].group;
+                rg[k].strand = strands.empty() ? 0 : strands[k];
+            }
+            if (sfa_session_target_groups_reach(se, rg.data(), static_cast<int32_t>(rg.size()), static_cast<int32_t>(group_names.size())) != SFA_OK)
+                die(std::string("target groups: ") + sfa_last_error());
+        } else if (r.by_name && sfa_session_target_groups(se, gt.data(), static_cast<int32_t>(gt.size()), static_cast<int32_t>(group_names.size())) != SFA_OK) {
             die(std::string("target groups: ") + sfa_last_error());
+        }
     }
     int64_t base_cols = 0, open_cols = 0, cover_bases = 0, cover_intervals = 0;  // --depth-cap
     if (r.depth_cap > 0) {
@@ -540,6 +551,7 @@ int realtime_run(int argc, char **argv, double t0) {
     if (trace) fclose(trace);
     if (targets) rep.print_targets();
     if (r.lead >= 0) fprintf(stderr, "[realtime] reach: lead %d%s\ton-target columns: %ld\n", r.lead, r.stranded ? ", stranded" : "", (long)reach_cols);
+    if (r.group_lead >= 0) fputs(replay::reach_group_line(r.group_lead, r.group_stranded, reach_cols).c_str(), stderr);
     if (r.depth_cap > 0)
         fprintf(stderr, "[realtime] coverage: cap %d\t%ld intervals, %ld bases added\topen target columns at the end: %ld of %ld\n", r.depth_cap, (long)cover_intervals,
                 (long)cover_bases, (long)open_cols, (long)base_cols);

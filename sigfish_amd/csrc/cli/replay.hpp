@@ -106,6 +106,14 @@ inline std::string quota_tags(int32_t on_group, const std::vector<std::string> &
     return "\tog:Z:" + (on_group >= 0 && static_cast<size_t>(on_group) < names.size() ? names[static_cast<size_t>(on_group)] : std::string("*"));
 }
 
+// ---- with --group-lead: the line the summary gains (Python twin: realtime.format_reach_group_summary).  The labelled columns
+// are the mask's on-target columns: a label is a group exactly where the reach mask of the same list has its bit ----
+inline std::string reach_group_line(int32_t lead, bool stranded, int64_t columns) {
+    char buf[128];
+    snprintf(buf, sizeof buf, "[realtime] reach groups: lead %d%s\tlabelled columns: %ld\n", lead, stranded ? ", stranded" : "", (long)columns);
+    return buf;
+}
+
 // ---- with --truth: the two tags a line gains behind all others, and with --by-name two more (Python twin: realtime.truth_tags) ----
 // tt:A: the read's true class (T, O; N: the read has no truth), tv:A: the verdict of the line's tc (C, W; N: either is N);
 // tn:Z: the true group's name (`*`: the background, `.`: the read has no truth), gv:A: the verdict of the line's tg

@@ -14,6 +14,7 @@
 //   sess::Open        sfa_session_open_classes: the lowest column of every label, and of a call the slot list, partial minima, results
 //   sess::Coverage    sfa_session_coverage_config: the depth tracks, the live mask, and of a sfa_session_coverage_add call the intervals
 //   sess::GroupCover  sfa_session_group_coverage_config: the live label table, its labels' first columns, the groups' depth records
+//   sess::GroupReach  sfa_session_target_groups_reach: the anchors beside a label table that was built from a reach group list
 //   sess::Spread      SFA_SESSION_SPREAD on a group context: one sub-session per shard, a call's entries dealt to them
 // The host rules -- which waves a call becomes, which points of the automatic start it passes -- are session_plan.hpp's; where a
 // spread session's slots live and how a call is dealt to the shards, session_spread.hpp's.
@@ -29,6 +30,7 @@
 #include "sdtw_session_cover.hpp"
 #include "sdtw_session_groupcover.hpp"
 #include "sdtw_session_reach.hpp"
+#include "sdtw_session_reachgroup.hpp"
 
 namespace sfa {
 // defined in sfa_align.hip, the unit that holds the plain kernels of sdtw_kernels.hpp
@@ -273,6 +275,27 @@ struct Reach {  // sfa_session_targets_reach (reach_rules.hpp): the mask is sess
     }
 };
 
+struct GroupReach {  // sfa_session_target_groups_reach (reach_group_rules.hpp): the label table is sess::Groups', its anchors lie beside it
+    bool on = false;
+    DevBuf d_anchor;                      // [total_cols] i32: the anchor's entry of its contig's depth track
+    DevBuf d_runs, d_run_off, d_first;    // of a call: the prepared runs, the lowest column of every label; freed when the build is through
+    PinBuf h_first;                       // [2][n_groups + 1]: the table's initial value, what the launch left
+    int reserve(int64_t total_cols, size_t n_runs, int32_t n_jobs, int32_t n_groups) {
+        const size_t e = static_cast<size_t>(n_groups) + 1;
+        return reserve_all(d_anchor, 4 * static_cast<size_t>(total_cols), d_runs, sizeof(sfa::ReachGroupRun) * (n_runs + 1), d_run_off, 4 * (static_cast<size_t>(n_jobs) + 1), d_first,
+                           4 * e, h_first, 2 * 4 * e);
+    }
+    void free_call() {
+        d_runs = DevBuf{}, d_run_off = DevBuf{}, d_first = DevBuf{};
+        h_first = PinBuf{};
+    }
+    void free_all() {
+        on = false;
+        d_anchor = DevBuf{};
+        free_call();
+    }
+};
+
 struct GroupCover {  // sfa_session_group_coverage_config, sfa_session_group_coverage (group_cover_rules.hpp; the tracks are sess::Coverage's)
     int32_t cap = 0;                      // 0: off
     std::vector<int32_t> first;           // lowest column of every LIVE label, [n_groups + 1], -1: none (what open_first_cols reads)
@@ -346,6 +369,7 @@ struct sfa_session {
     sess::Coverage cover;
     sess::GroupCover gcover;
     sess::Reach reach;
+    sess::GroupReach greach;
     std::unique_ptr<sess::Spread> spread;  // SFA_SESSION_SPREAD on a group context: `c` is the group, everything above is unused
     int32_t name_first = 0, name_step = 1;  // a sub-session of a spread session: local slot l is the caller's slot l * step + first (messages)
 };
@@ -466,7 +490,8 @@ void gcover_drop(sfa_session *s) {
     if (!s->cover.on()) s->cover.free_track();
 }
 
-// The live label table from the base table and the depth tracks (session_cover_label_kernel), on the context's stream; the
+// The live label table from the base table and the depth tracks (session_cover_label_kernel; on a reach label table
+// session_reach_label_live_kernel), on the context's stream; the
 // caller has set the device and synchronises.  The upload in front resets the table of firsts the kernel's atomics merge into.
 int gcover_enqueue_labels(sfa_session *s) {
     sfa_ctx *c = s->c;
@@ -475,6 +500,25 @@ int gcover_enqueue_labels(sfa_session *s) {
     int32_t *hf = gc.h_first.as<int32_t>();
     std::fill(hf, hf + entries, sfa::kNoColumn);
     HIP_TRY(hipMemcpyAsync(gc.d_first.p, hf, 4 * entries, hipMemcpyHostToDevice, c->stream));
+    if (s->greach.on) {  // (a reach label table: the depth is read at the column's anchor)
+        sfa::SessionReachLabelLiveArgs a;
+        a.base = s->groups.d_label.as<uint64_t>();
+        a.anchor = s->greach.d_anchor.as<int32_t>();
+        a.live = gc.d_live.as<uint16_t>();
+        a.depth = s->cover.d_depth.as<uint32_t>();
+        a.cov_off = s->cover.d_cov_off.as<int64_t>();
+        a.col_off = s->rows.d_col_off.as<int64_t>();
+        a.ref = c->model.tables();
+        a.first = gc.d_first.as<int32_t>();
+        a.total_cols = c->model.total_cols;
+        a.n_jobs = c->model.n_jobs;
+        a.n_groups = s->groups.n_groups;
+        a.cap = static_cast<uint32_t>(gc.cap);
+        hipLaunchKernelGGL(sfa::session_reach_label_live_kernel, dim3(sfa::group_cover_blocks(c->model.total_cols)), dim3(sfa::kGroupCoverThreads), 0, c->stream, a);
+        KERNEL_TRY();
+        HIP_TRY(hipMemcpyAsync(hf + entries, gc.d_first.p, 4 * entries, hipMemcpyDeviceToHost, c->stream));
+        return SFA_OK;
+    }
     sfa::SessionCoverLabelArgs a;
     a.base = s->groups.d_label.as<uint64_t>();
     a.live = gc.d_live.as<uint16_t>();
@@ -1970,19 +2014,36 @@ int sfa_session_group_coverage(sfa_session_t *s, sfa_group_cover_t *out, int32_t
     std::fill(hr, hr + entries, sfa::group_cover_none());
     HIP_TRY(hipEventRecord(gc.ev[0], st));
     HIP_TRY(hipMemcpyAsync(gc.d_rec.p, hr, sizeof(sfa_group_cover_t) * static_cast<size_t>(entries), hipMemcpyHostToDevice, st));  // the reset in front of the launch
-    sfa::SessionCoverGroupArgs a;
-    a.base = s->groups.d_label.as<uint64_t>();
-    a.depth = s->cover.d_depth.as<uint32_t>();
-    a.cov_off = s->cover.d_cov_off.as<int64_t>();
-    a.col_off = s->rows.d_col_off.as<int64_t>();
-    a.ref = c->model.tables();
-    a.rec = gc.d_rec.as<sfa_group_cover_t>();
-    a.total_cols = c->model.total_cols;
-    a.n_jobs = c->model.n_jobs;
-    a.n_groups = s->groups.n_groups;
-    a.cap = static_cast<uint32_t>(gc.cap);
-    hipLaunchKernelGGL(sfa::session_cover_group_kernel, dim3(sfa::group_cover_blocks(c->model.total_cols)), dim3(sfa::kGroupCoverThreads), 0, st, a);
-    KERNEL_TRY();
+    if (s->greach.on) {  // (a reach label table: the '+' jobs' body columns only)
+        sfa::SessionReachLabelGroupArgs a;
+        a.base = s->groups.d_label.as<uint64_t>();
+        a.anchor = s->greach.d_anchor.as<int32_t>();
+        a.depth = s->cover.d_depth.as<uint32_t>();
+        a.cov_off = s->cover.d_cov_off.as<int64_t>();
+        a.col_off = s->rows.d_col_off.as<int64_t>();
+        a.ref = c->model.tables();
+        a.rec = gc.d_rec.as<sfa_group_cover_t>();
+        a.total_cols = c->model.total_cols;
+        a.n_jobs = c->model.n_jobs;
+        a.n_groups = s->groups.n_groups;
+        a.cap = static_cast<uint32_t>(gc.cap);
+        hipLaunchKernelGGL(sfa::session_reach_label_group_kernel, dim3(sfa::group_cover_blocks(c->model.total_cols)), dim3(sfa::kGroupCoverThreads), 0, st, a);
+        KERNEL_TRY();
+    } else {
+        sfa::SessionCoverGroupArgs a;
+        a.base = s->groups.d_label.as<uint64_t>();
+        a.depth = s->cover.d_depth.as<uint32_t>();
+        a.cov_off = s->cover.d_cov_off.as<int64_t>();
+        a.col_off = s->rows.d_col_off.as<int64_t>();
+        a.ref = c->model.tables();
+        a.rec = gc.d_rec.as<sfa_group_cover_t>();
+        a.total_cols = c->model.total_cols;
+        a.n_jobs = c->model.n_jobs;
+        a.n_groups = s->groups.n_groups;
+        a.cap = static_cast<uint32_t>(gc.cap);
+        hipLaunchKernelGGL(sfa::session_cover_group_kernel, dim3(sfa::group_cover_blocks(c->model.total_cols)), dim3(sfa::kGroupCoverThreads), 0, st, a);
+        KERNEL_TRY();
+    }
     HIP_TRY(hipEventRecord(gc.ev[1], st));
     HIP_TRY(hipMemcpyAsync(hr + entries, gc.d_rec.p, sizeof(sfa_group_cover_t) * static_cast<size_t>(entries), hipMemcpyDeviceToHost, st));
     if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
@@ -2025,6 +2086,7 @@ int sfa_session_target_groups(sfa_session_t *s, const sfa_group_target_t *target
         g.n_groups = 0;
         std::vector<uint16_t>().swap(g.h_label);
         g.d_label = DevBuf{};  // (freed; the buffers of a call stay for the next table)
+        s->greach.free_all();  // (a reach list's group anchors go with its label table)
         if (s->gcover.on()) gcover_drop(s);  // (a group cap lives on the labels: off with them)
         return SFA_OK;
     }
@@ -2049,6 +2111,7 @@ int sfa_session_target_groups(sfa_session_t *s, const sfa_group_target_t *target
             return rc;
         }
     g.n_groups = 0;  // (off until the new table is up)
+    s->greach.free_all();  // (a plain table replaces a reach list, before the table is overwritten: no anchor outlives the table it belongs to)
     g.h_label.swap(label);
     const auto upload = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(g.d_label.p, g.h_label.data(), 2 * g.h_label.size(), hipMemcpyHostToDevice, c->stream));
@@ -2065,6 +2128,120 @@ int sfa_session_target_groups(sfa_session_t *s, const sfa_group_target_t *target
         if (rc) gcover_drop(s);
         return rc;
     }
+    return SFA_OK;
+}
+
+// ---- reach groups (reach_group_rules.hpp, sdtw_session_reachgroup.hpp) ----
+
+size_t sfa_session_group_reach_bytes(const sfa_ref_t *ref, int flag) {
+    if (!ref || ref->num_ref <= 0 || !ref->ref_lengths) return 0;
+    int64_t cols = 0;
+    for (int32_t r = 0; r < ref->num_ref; ++r) {
+        if (ref->ref_lengths[r] <= 0) return 0;
+        cols += static_cast<int64_t>(ref->ref_lengths[r]) * ((flag & SFA_RNA) ? 1 : 2);
+    }
+    return sfa::reach_group_bytes(cols);
+}
+
+int sfa_session_target_groups_reach(sfa_session_t *s, const sfa_reach_group_target_t *targets, int32_t n, int32_t n_groups) {
+    static const char *const who = "sfa_session_target_groups_reach";
+    if (!s || n < 0 || (n > 0 && !targets)) return fail(SFA_EINVAL, "%s: bad argument", who);
+    if (s->resweep)
+        return fail(SFA_EINVAL, "%s: the session was created with SFA_SESSION_RESWEEP: its carried row belongs to the reversed query, and what its minimum means has "
+                                "not been looked into",
+                    who);
+    if (n == 0) return sfa_session_target_groups(s, nullptr, 0, n_groups);  // (groups off, the anchors freed: one path)
+    if (s->spread) {  // every sub-session holds the table and its anchors, as in sfa_session_target_groups
+        if (int rc = spread_live(s, who)) return rc;
+        sess::Spread &sp = *s->spread;
+        std::vector<int> rcs(sp.subs.size(), 0);
+        const int rc =
+            sfa::for_each_shard(s->c, [&](size_t r) { return sp.subs[r] ? (rcs[r] = sfa_session_target_groups_reach(sp.subs[r], targets, n, n_groups)) : static_cast<int>(SFA_OK); });
+        size_t have = 0, failed = 0;
+        for (size_t r = 0; r < sp.subs.size(); ++r) have += sp.subs[r] != nullptr, failed += rcs[r] != SFA_OK;
+        if (failed != 0 && failed != have) sp.broken = true;
+        return rc;
+    }
+    sfa_ctx *c = s->c;
+    sess::Groups &g = s->groups;
+    sess::GroupReach &gr = s->greach;
+    if (c->model.total_cols >= INT32_MAX) return fail(SFA_ERANGE, "%s: the reference has %lld columns; the groups count them in 31 bits", who, (long long)c->model.total_cols);
+    const CoverModel cm(s);
+    char msg[256];
+    if (sfa::reach_group_list_error(targets, n, n_groups, cm.m, msg, sizeof msg)) return fail(SFA_EINVAL, "%s: %s", who, msg);
+    sfa::ReachGroupPrepared prep;
+    sfa::reach_group_prepare(targets, n, cm.m, &prep);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (a table in use is not replaced under a kernel)
+    // (from here on the old table is gone: an allocation or device failure leaves the session without groups -- and so without a
+    // group cap, which lives on the labels -- never with half of two lists; include/sigfish_amd.h says so)
+    const auto give_up = [&](int rc) {
+        sfa_session_target_groups(s, nullptr, 0, 0);
+        return rc;
+    };
+    s->open.first.clear();
+    g.n_groups = 0;  // (off until the new table is up)
+    std::vector<uint16_t>().swap(g.h_label);  // (the table is built on the device: sfa_session_group_reach_tables copies it back)
+    gr.on = false;
+    if (int rc = g.reserve(c->model.total_cols)) return give_up(rc);
+    if (int rc = sess::create_events(g.ev, 2)) return give_up(rc);
+    if (int rc = gr.reserve(c->model.total_cols, prep.runs.size(), c->model.n_jobs, n_groups)) return give_up(rc);
+    if (s->gcover.on())  // (the live table's tables follow the new n_groups)
+        if (int rc = s->gcover.reserve(c->model.total_cols, n_groups)) return give_up(rc);
+    hipStream_t st = c->stream;
+    const size_t entries = static_cast<size_t>(n_groups) + 1;
+    int32_t *hf = gr.h_first.as<int32_t>();
+    std::fill(hf, hf + entries, sfa::kNoColumn);
+    sfa::SessionReachLabelBuildArgs a;
+    a.runs = gr.d_runs.as<sfa::ReachGroupRun>();
+    a.run_off = gr.d_run_off.as<int32_t>();
+    a.col_off = s->rows.d_col_off.as<int64_t>();
+    a.label = g.d_label.as<uint16_t>();
+    a.anchor = gr.d_anchor.as<int32_t>();
+    a.first = gr.d_first.as<int32_t>();
+    a.total_cols = c->model.total_cols;
+    a.n_jobs = c->model.n_jobs;
+    a.n_groups = n_groups;
+    // the labels from the row's last quad on, the word behind the row with them: the background (the kernel writes the row's own)
+    const size_t tail = 4 * static_cast<size_t>(c->model.total_cols / 4), n_tail = 4 * sfa::group_label_words(c->model.total_cols) - tail;
+    const auto enqueue = [&]() -> int {  // (the uploads of the runs read pageable memory: they are through when the calls return)
+        HIP_TRY(hipMemcpyAsync(gr.d_first.p, hf, 4 * entries, hipMemcpyHostToDevice, st));
+        if (!prep.runs.empty()) HIP_TRY(hipMemcpyAsync(gr.d_runs.p, prep.runs.data(), sizeof(sfa::ReachGroupRun) * prep.runs.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(gr.d_run_off.p, prep.run_off.data(), 4 * prep.run_off.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(g.d_label.as<uint16_t>() + tail), static_cast<unsigned short>(n_groups), n_tail, st));
+        hipLaunchKernelGGL(sfa::session_reach_label_build_kernel, dim3(sfa::group_cover_blocks(c->model.total_cols)), dim3(sfa::kGroupCoverThreads), 0, st, a);
+        KERNEL_TRY();
+        HIP_TRY(hipMemcpyAsync(hf + entries, gr.d_first.p, 4 * entries, hipMemcpyDeviceToHost, st));
+        return SFA_OK;
+    };
+    if (int rc = enqueue()) return give_up(rc);
+    if (hipStreamSynchronize(st) != hipSuccess) return give_up(fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError())));
+    sfa::group_cover_firsts_for_open(hf + entries, n_groups, &s->open.first);  // (what sfa_session_open_classes needs once per label table)
+    gr.free_call();  // (the runs and the firsts were the call's: only the anchors stay)
+    g.n_groups = n_groups;
+    gr.on = true;
+    if (s->gcover.on()) {  // (the depth is kept: the live table of the new base table and its anchors)
+        const int rc = gcover_derive(s, who);
+        if (rc) return give_up(rc);
+    }
+    return SFA_OK;
+}
+
+int sfa_session_group_reach_tables(sfa_session_t *s, uint16_t *label, int32_t *anchor, int64_t n_cols) {
+    static const char *const who = "sfa_session_group_reach_tables";
+    if (!s) return fail(SFA_EINVAL, "%s: null session", who);
+    if (s->spread) {
+        if (int rc = spread_live(s, who)) return rc;
+        return sfa_session_group_reach_tables(s->spread->subs[0], label, anchor, n_cols);  // (shard 0 answers: every shard holds the same tables)
+    }
+    sfa_ctx *c = s->c;
+    if (!s->greach.on) return fail(SFA_EINVAL, "%s: the session has no reach groups (sfa_session_target_groups_reach)", who);
+    if ((label || anchor) && n_cols != c->model.total_cols)
+        return fail(SFA_EINVAL, "%s: n_cols is %lld; a row has %lld columns", who, (long long)n_cols, (long long)c->model.total_cols);
+    HIP_TRY(hipSetDevice(c->device));
+    if (label) HIP_TRY(hipMemcpyAsync(label, s->groups.d_label.p, 2 * static_cast<size_t>(n_cols), hipMemcpyDeviceToHost, c->stream));
+    if (anchor) HIP_TRY(hipMemcpyAsync(anchor, s->greach.d_anchor.p, 4 * static_cast<size_t>(n_cols), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return SFA_OK;
 }
 

@@ -205,7 +205,8 @@ AUTO_START_MAX_SAMPLES, MAX_SKIP_EVENTS = 131072, 4096  # the defaults of --auto
 
 
 def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_events, min_mapq, session=None, trace=None, recalibrate=(), at_end=False, resweep=False,
-           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None, by_name=False, quota=None, truth=None, depth_cap=None, group_cap=None, lead=None, stranded=False):
+           candidates=0, auto_start_every=None, auto_start_max_samples=AUTO_START_MAX_SAMPLES, max_skip_events=MAX_SKIP_EVENTS, sam=False, spread=False, targets=None, mode=None, margin=None, summary=None, by_name=False, quota=None, truth=None, depth_cap=None, group_cap=None, lead=None, stranded=False,
+           group_lead=None, group_stranded=False):
     """Generator of (tick, channel, read_index, row, info, span, reason), one per decided read, in tick then channel order.
     candidates=1..4 (--candidates): an eighth element, RESULT_DTYPE[4], the channel's candidates at the decision, best first.
     A `session` of the caller's is taken as it is, in this as in its raw mode: it must keep that many candidates already
@@ -255,8 +256,32 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     direction.  stranded=True (--stranded; needs lead=): targets= is a REACH_TARGET_DTYPE array whose strands are kept
     (api.read_reach_targets(path, names, N, stranded=True)); without it every target is for both strands.  Schedule, decision
     rule, items and tags are unchanged; truth reads the intervals without their leads.  summary gains "reach": lead, stranded
-    and columns, the on-target columns (format_reach_summary)."""
+    and columns, the on-target columns (format_reach_summary).
+    group_lead=N (--group-lead N; needs by_name=True and mode=ENRICH, 0 <= N <= 2^30; quota, group_cap and truth are optional with it;
+    not with lead, depth_cap or mode=DEPLETE): the session's label table is a reach label table
+    (Session.set_reach_target_groups) -- the N bases in front of every named target, in the read's direction, carry the label of
+    the target the read reaches first -- and its mask the reach mask of the same list with the same lead.  group_stranded=True
+    (--group-stranded; needs group_lead=): targets= is the pair api.read_reach_target_groups(path, names, N, stranded=True)
+    returns, whose strands are kept; without it every target is for both strands.  Items, tags, trace and the quota / cap
+    behaviour are by_name's, over the reach labels; under group_cap a lead-in closes when the base it leads to is covered.  summary
+    gains "reach_groups": lead, stranded and columns, the labelled columns (format_reach_group_summary)."""
     auto = skip < 0
+    if group_lead is not None or group_stranded:  # (before any session exists, each with the fix)
+        if not by_name:
+            raise api.SfaError("replay: group_lead / group_stranded widen named groups in the read's direction: pass targets=(group targets, names), by_name=True, "
+                               "mode=ENRICH and margin= with them")
+        if lead is not None or stranded:
+            raise api.SfaError("replay: group_lead and lead are two leads: with by_name pass group_lead alone (the mask gets the same lead)")
+        if depth_cap is not None:
+            raise api.SfaError("replay: group_lead with depth_cap is not built: depth_cap is for mask targets; the cap of named groups is group_cap")
+        if mode == api.DEPLETE:
+            raise api.SfaError("replay: group_lead with mode=DEPLETE is not built: use mode=ENRICH")
+        if group_lead is None:
+            raise api.SfaError("replay: group_stranded belongs to group_lead=: pass group_lead=N (0 for no lead-in) with it")
+        if isinstance(group_lead, bool) or not isinstance(group_lead, (int, np.integer)) or group_lead < 0 or group_lead > api.REACH_LEAD_MAX:
+            raise api.SfaError("replay: group_lead should be an integer 0..1073741824")
+        if group_stranded and not (isinstance(targets, (tuple, list)) and len(targets) == 2 and isinstance(targets[0], np.ndarray) and targets[0].dtype == api.REACH_GROUP_TARGET_DTYPE):
+            raise api.SfaError("replay: group_stranded=True takes targets= as the pair api.read_reach_target_groups(path, names, group_lead, stranded=True) returns")
     if lead is not None or stranded:  # (before any session exists, each with the fix)
         if targets is None:
             raise api.SfaError("replay: lead / stranded widen targets in the read's direction: pass targets= with mode= and margin= with them")
@@ -306,7 +331,20 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
     group_targets = group_names = None
     if by_name:
         group_targets, group_names = targets
+        reach_groups = None
+        if isinstance(group_targets, np.ndarray) and group_targets.dtype == api.REACH_GROUP_TARGET_DTYPE:  # (the strands are read only with group_stranded)
+            reach_groups = group_targets
+            group_targets = np.zeros(len(reach_groups), api.GROUP_TARGET_DTYPE)
+            for f in ("contig", "begin", "end", "group"):
+                group_targets[f] = reach_groups[f]
         group_targets = api._group_targets(group_targets)
+        if group_lead is not None:  # the two reach lists for the session; `targets` and `group_targets` stay the plain intervals (truth reads them)
+            reach_group_targets = np.zeros(len(group_targets), api.REACH_GROUP_TARGET_DTYPE)
+            for f in ("contig", "begin", "end", "group"):
+                reach_group_targets[f] = group_targets[f]
+            reach_group_targets["lead"] = int(group_lead)
+            if group_stranded:
+                reach_group_targets["strand"] = reach_groups["strand"]
         targets = np.zeros(len(group_targets), api.TARGET_DTYPE)
         for f in ("contig", "begin", "end"):
             targets[f] = group_targets[f]
@@ -374,9 +412,17 @@ def replay(aligner, reads, channels, chunk_samples, skip, norm, query, min_event
             se.set_reach_targets(reach_targets)
             if summary is not None:
                 summary["reach"] = dict(lead=int(lead), stranded=bool(stranded), columns=se.target_columns())
-        elif targets is not None:
+        elif targets is not None and group_lead is None:
             se.set_targets(targets)
-        if by_name:
+        if by_name and group_lead is not None:
+            reach_mask = np.zeros(len(reach_group_targets), api.REACH_TARGET_DTYPE)
+            for f in ("contig", "begin", "end", "lead", "strand"):
+                reach_mask[f] = reach_group_targets[f]
+            se.set_reach_targets(reach_mask)  # (in place of the plain mask: the same columns the labels name)
+            se.set_reach_target_groups(reach_group_targets, len(group_names))
+            if summary is not None:
+                summary["reach_groups"] = dict(lead=int(group_lead), stranded=bool(group_stranded), columns=se.target_columns())
+        elif by_name:
             se.set_target_groups(group_targets, len(group_names))
         cover = None
         if depth_cap is not None:
@@ -645,6 +691,12 @@ def format_reach_summary(summary):
     """the line `sigfish-amd realtime --lead` adds to its stderr, from summary["reach"]"""
     c = summary["reach"]
     return "[realtime] reach: lead %d%s\ton-target columns: %d\n" % (c["lead"], ", stranded" if c["stranded"] else "", c["columns"])
+
+
+def format_reach_group_summary(summary):
+    """the line `sigfish-amd realtime --group-lead` adds to its stderr, from summary["reach_groups"] (the twin of replay.hpp's reach_group_line)"""
+    c = summary["reach_groups"]
+    return "[realtime] reach groups: lead %d%s\tlabelled columns: %d\n" % (c["lead"], ", stranded" if c["stranded"] else "", c["columns"])
 
 
 def format_cover_summary(summary):
