@@ -78,6 +78,9 @@ struct EvStreamArgs {
 
 constexpr int kStreamTile = 32;
 
+__global__ void __launch_bounds__(64) ev_stream_kernel(const EvStreamArgs a);
+
+#ifdef SFA_DEFINE_SESSION_KERNELS  // the plain kernel: defined in exactly one translation unit (sfa_session.hip), as sdtw_session.hpp's
 __global__ void __launch_bounds__(64) ev_stream_kernel(const EvStreamArgs a) {
     __shared__ double ring_s[kEvRing][64];
     __shared__ double ring_q[kEvRing][64];
@@ -274,6 +277,7 @@ __global__ void __launch_bounds__(64) ev_stream_kernel(const EvStreamArgs a) {
         st->ring_q[r] = ring_q[r][lane];
     }
 }
+#endif
 
 // what a call brings back to the host per slot: counts and the normalisation the slot has now
 struct EvStreamOut {

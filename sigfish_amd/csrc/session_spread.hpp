@@ -4,7 +4,8 @@
 // shard, local slot numbers, the caller's indices for the way back), the offset tables of a ragged payload rebuilt per shard
 // (spread_offsets: ev_off, raw_off, map_off alike), and the refusals one session makes by itself -- a slot out of range, a slot
 // named twice -- made here for the whole call, before anything reaches a shard: a refused call changes no shard.
-// sfa_session.hip runs what this returns on the shards' sub-sessions and scatters their answers.
+// sfa_session.hip and sfa_session_targets.hip run what this returns on the shards' sub-sessions and scatter their answers (the
+// visits they share: sfa_session_state.hpp).
 #pragma once
 
 #include <cstdint>

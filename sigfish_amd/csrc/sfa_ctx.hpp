@@ -7,8 +7,10 @@
 //   sfa_align.hip    the alignment stage: planner -> launches (wave kernels, row strips) -> rows; the batch entry points
 //   sfa_maps.hip     event maps of the last call's rows, and the core sfa_session_event_maps shares with it (sdtw_path.hpp)
 //   sfa_session.hip  alignment sessions: a slot's sweep extended chunk by chunk below its carried row (sdtw_session.hpp)
-//                    -- its state one struct per feature (namespace sess), its host rules in session_plan.hpp (pure C++, as sfa_plan.hpp);
-//                    on a group context a session spread over the shards (session_spread.hpp: placement and partition)
+//                    -- its state one struct per feature (namespace sess, sfa_session_state.hpp), its host rules in session_plan.hpp
+//                    (pure C++, as sfa_plan.hpp); on a group context a session spread over the shards (session_spread.hpp)
+//   sfa_session_targets.hip  what a session knows about the reference beside its rows -- targets, groups, caps, reach lists --
+//                    and the query calls that read a slot's carried row with it (session_query.hpp: which entries launch)
 //   sfa_pre.hip      the stages in front of it on the device: raw samples / BLOW5 records in (events_kernels.hpp, blow5_kernels.hpp)
 // There is NO CPU fallback: every failure is reported through the return code + sfa_last_error().
 #pragma once

@@ -1,378 +1,16 @@
 // sfa_session.hip -- alignment sessions of the C-ABI (include/sigfish_amd.h): a slot's subsequence DTW extended chunk by chunk
 // (sdtw_session.hpp).  A session belongs to its context, runs on the context's stream and is freed with it at the latest.  Its
-// state is one struct per feature (namespace sess), each with its buffers, what it keeps between calls and reserve(), the sizes:
-//   sess::Rows        the carried rows, the slots' current rows, lengths, poison flags and call stamps
-//   sess::Sweep       what one sweep needs: events, staging, poison flags of the call (the raw path writes them too), partial results
-//   sess::Candidates  sfa_session_candidates_config: the lists behind every slot's row
-//   sess::Raw         raw mode (sfa_session_raw_config, events_stream.hpp): detector states, event tables, normalised queries, the
-//                     recalibration rule, the tables of a call -- samples go in, events and query stay on the device
-//   sess::AutoStart   sfa_session_raw_auto_start (events_auto_stream.hpp): retained samples, the slots' targets and skips
-//   sess::Keep        sfa_session_keep_events: the events of an event-mode session's slots, kept for their maps
-//   sess::Maps        sfa_session_event_maps: the scratch of a call (the core is sfa_maps.hip's), where every slot's query begins
-//   sess::Targets     sfa_session_targets: the column mask, and of a sfa_session_classes call the slot list, partial minima, results
-//   sess::Groups      sfa_session_target_groups: the label table, and of a sfa_session_group_bests call the slot list, keys, results
-//   sess::Open        sfa_session_open_classes: the lowest column of every label, and of a call the slot list, partial minima, results
-//   sess::Coverage    sfa_session_coverage_config: the depth tracks, the live mask, and of a sfa_session_coverage_add call the intervals
-//   sess::GroupCover  sfa_session_group_coverage_config: the live label table, its labels' first columns, the groups' depth records
-//   sess::GroupReach  sfa_session_target_groups_reach: the anchors beside a label table that was built from a reach group list
-//   sess::Spread      SFA_SESSION_SPREAD on a group context: one sub-session per shard, a call's entries dealt to them
-// The host rules -- which waves a call becomes, which points of the automatic start it passes -- are session_plan.hpp's; where a
-// spread session's slots live and how a call is dealt to the shards, session_spread.hpp's.
-#include "sfa_ctx.hpp"
-#define SFA_DEFINE_SESSION_KERNELS  // (this unit holds the plain kernel of sdtw_session.hpp)
-#include "sdtw_session.hpp"
-#include "events_stream.hpp"
+// state is one struct per feature (namespace sess, sfa_session_state.hpp, which lists them).  This unit holds creation, the sweep
+// behind both extend entry points, raw mode, the event maps and the spread sessions; targets, groups, caps, reach lists and the
+// query calls that read a slot's carried row are sfa_session_targets.hip's.
+#define SFA_DEFINE_SESSION_KERNELS  // (this unit holds the plain kernels of sdtw_session.hpp and events_stream.hpp)
+#include "sfa_session_state.hpp"
 #include "events_auto_stream.hpp"
-#include "session_spread.hpp"
-#include "sdtw_session_class.hpp"
-#include "sdtw_session_group.hpp"
-#include "sdtw_session_open.hpp"
-#include "sdtw_session_cover.hpp"
-#include "sdtw_session_groupcover.hpp"
-#include "sdtw_session_reach.hpp"
-#include "sdtw_session_reachgroup.hpp"
 
 namespace sfa {
 // defined in sfa_align.hip, the unit that holds the plain kernels of sdtw_kernels.hpp
 __global__ void sdtw_screen_kernel(const float *queries, const int64_t *q_off, const int n, uint8_t *bad, unsigned *count);
 }  // namespace sfa
-
-// ---- the session's state, one struct per feature that owns it (as namespace ctx of sfa_ctx.hpp) ----
-namespace sess {
-
-int create_events(Event *ev, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!ev[i].h && hipEventCreate(&ev[i].h) != hipSuccess) return fail(SFA_ENODEV, "hipEventCreate failed");
-    return SFA_OK;
-}
-
-struct Rows {  // the carried rows and the per-slot host state
-    DevBuf d_row_c, d_row_s;         // carried rows: costs, start columns
-    DevBuf d_col_off;                // [n_jobs] first column of every job inside a slot's row
-    std::vector<int64_t> h_col_off;
-    DevBuf d_rows;                   // [n_slots] the slots' current rows
-    PinBuf h_rows;
-    std::vector<int64_t> len;        // events every slot has received since its last reset
-    std::vector<uint8_t> poison;     // a chunk of the slot held a NaN / inf: no rows until reset
-    std::vector<int32_t> stamp;      // call in which the slot was named last (duplicates inside one call)
-    static int64_t slot_bytes(int64_t total_cols, bool track) { return total_cols * (track ? 8 : 4); }  // one row, updated in place: costs, start columns
-    int reserve(int64_t total_cols, int32_t n_slots, size_t n_jobs, bool track) {
-        const size_t plane = static_cast<size_t>(slot_bytes(total_cols, false)) * n_slots + 4 * 2 * sfa::kSessionPad, rows = sizeof(sfa_result_t) * n_slots;
-        len.assign(n_slots, 0), poison.assign(n_slots, 0), stamp.assign(n_slots, 0), h_col_off.resize(n_jobs);
-        if (int rc = reserve_all(d_row_c, plane, d_col_off, 8 * n_jobs, d_rows, rows, h_rows, rows)) return rc;
-        return track ? d_row_s.reserve(plane) : SFA_OK;
-    }
-};
-
-struct Sweep {  // of a call of the sweep
-    DevBuf d_events, d_stage, d_bad, d_count, d_pbest, d_psecond, d_pend, d_pst;
-    PinBuf h_stage, h_bad;
-    std::vector<sfa::Launch> launches;   // the call's plan (session_plan.hpp), its argument block per launch, bytes staged
-    std::vector<int32_t> call_slot;
-    std::vector<sfa::SessionArgs> args;
-    size_t staged = 0;
-    size_t keep_at = 0;  // where the keep kernel's tables lie in the staging (0: the call keeps nothing)
-    Event ev[4];  // first kernel, sweeps start / end, rows written
-    // the call's poison flags: the screen writes them, or the raw path's normalisation before the sweep (same n: nothing is dropped)
-    int reserve_bad(size_t n) { return reserve_all(d_bad, n, h_bad, n + 8); }
-    int reserve_count() { return d_count.reserve(64); }  // (the screen's counter: once, at creation)
-    int reserve(size_t stage_bytes, int64_t nq, size_t n, size_t n_part) {
-        if (int rc = reserve_bad(n)) return rc;
-        return reserve_all(h_stage, stage_bytes, d_stage, stage_bytes, d_events, sizeof(float) * static_cast<size_t>(std::max<int64_t>(nq, 1)), d_pbest,
-                           4 * n_part, d_psecond, 4 * n_part, d_pend, 4 * n_part, d_pst, 4 * n_part);
-    }
-};
-
-struct Candidates {  // sfa_session_candidates_config
-    int32_t n_cand = 0;   // candidates kept behind every slot's row (0: none, the plain kernels)
-    DevBuf d_cand, d_p5;  // [n_slots][4] the slots' candidates; of a call: [n][n_jobs] lists of kTop5Words words
-    PinBuf h_cand;
-    static size_t bytes(int32_t n_slots) { return sizeof(sfa_result_t) * 4 * static_cast<size_t>(n_slots); }
-    int reserve(int32_t n_slots) { return reserve_all(d_cand, bytes(n_slots), h_cand, bytes(n_slots)); }
-    int reserve_call(size_t n_part) { return n_cand > 0 ? d_p5.reserve(4 * sfa::kTop5Words * n_part) : SFA_OK; }
-};
-
-struct Raw {  // raw mode and its recalibration rule
-    bool on = false;
-    int32_t skip = 0, norm = 0, query = 0;  // (with the automatic start `skip` is the largest skip a slot may resolve)
-    struct Slot {
-        int64_t n = 0;                // samples received since the last reset
-        int32_t nev = 0, status = 0;  // its final events; bits of sfa_session_raw_info_t.status
-        float mean = 0.0f, sd = 0.0f;
-        int32_t window = 0;           // events the mean and sd span (0: not calibrated)
-        uint8_t fresh = 1;            // no chunk since the last reset: the next one initialises the detector state (ev_stream_kernel)
-        double scaling[3] = {0, 0, 0};  // latched by the first chunk after a reset
-    };
-    std::vector<Slot> slots;
-    DevBuf d_state, d_evtab, d_query;  // [n_slots] EvStreamSlot, [n_slots][skip + query] EvRecord, [n_slots][query] float
-    DevBuf d_window;                   // [n_slots] i32: the window a calibrated slot's normalisation spans (EvNormArgs.window)
-    int32_t recal_at[sfa::kRecalMaxPoints] = {0};  // sfa_session_raw_recalibrate: the points, their number, the flags
-    int32_t recal_n = 0;
-    uint32_t recal_flags = 0;
-    DevBuf d_raw, d_rstage, d_rout;    // of a call: samples, entry tables, EvStreamOut per entry
-    PinBuf h_rstage, h_rout;
-    std::vector<float> scale;          // ... its [n][2] offset and range / digitisation, the detector's argument block,
-    sfa::EvStreamArgs ea;              // where the automatic start's tables lie in the staging, the bytes staged
-    size_t o_have = 0, o_aent = 0, staged = 0;
-    Event ev_raw[3];                   // detector start / end, normalisation end
-    DevBuf d_span_in, d_span;          // of a sfa_session_query_span call: [slot n | q_events n (| skip n)] x i32, [n][2] u64
-    PinBuf h_span_in, h_span;
-    int32_t ev_cap() const { return skip + query; }
-    static int64_t evtab_bytes(int32_t skip_events, int32_t query_events) { return (static_cast<int64_t>(skip_events) + query_events) * static_cast<int64_t>(sizeof(sfa::EvRecord)); }
-    static int64_t slot_bytes(int32_t skip_ev, int32_t query_ev) { return evtab_bytes(skip_ev, query_ev) + 4 * static_cast<int64_t>(query_ev) + static_cast<int64_t>(sizeof(sfa::EvStreamSlot)); }
-    int reserve(int32_t n_slots, int32_t skip_events, int32_t query_events) {
-        const size_t ns = static_cast<size_t>(n_slots);
-        return reserve_all(d_state, sizeof(sfa::EvStreamSlot) * ns, d_evtab, static_cast<size_t>(evtab_bytes(skip_events, query_events)) * ns, d_query,
-                           4 * static_cast<size_t>(query_events) * ns, d_window, 4 * ns);
-    }
-    int reserve_call(size_t stage_bytes, int64_t total, size_t n) {
-        return reserve_all(h_rstage, stage_bytes, d_rstage, stage_bytes, d_raw, 2 * static_cast<size_t>(std::max<int64_t>(total, 1)), d_rout, sizeof(sfa::EvStreamOut) * n, h_rout,
-                           sizeof(sfa::EvStreamOut) * n);
-    }
-    int reserve_span(size_t in_bytes, size_t n) { return reserve_all(h_span_in, in_bytes, d_span_in, in_bytes, d_span, 16 * n, h_span, 16 * n); }
-    void reset_slot(int32_t sl) { slots[sl] = Slot{}; }
-};
-
-struct AutoStart {  // automatic query start (sfa_session_raw_auto_start)
-    int32_t every = 0, max_samples = 0;      // max_samples 0: off
-    struct Slot {
-        sfa::EvAutoSlot h{-1, -1, 0, sfa::kAutoPending};  // what the slot's device state holds (read back by each call)
-        int32_t k = 0;                                    // periodic points N_k it has passed
-        bool final_taken = false;                         // its final point has been taken
-    };
-    std::vector<Slot> slots;
-    int32_t n_pending = 0;                   // of a call: its slots with a pending point
-    std::vector<sfa::AutoPoints> call;       // [n_slots] of a call: what auto_points said for entry i (a call names a slot once: n <= n_slots)
-    DevBuf d_auto, d_keep, d_csum, d_aout;   // [n_slots] EvAutoSlot, [n_slots][max_samples] i16, of a call: prefix sums, EvAutoSlot per entry
-    PinBuf h_aout;
-    Event ev_auto[2];                        // retention + evaluation of a call: start, end
-    float ms = 0.0f;                         // ... their time in the last call (sfa_session_auto_ms)
-    bool on() const { return max_samples > 0; }
-    static int64_t keep_bytes(int32_t max) { return 2 * static_cast<int64_t>(max); }        // retention (int16)
-    static int64_t csum_bytes(int32_t max) { return 4 * (static_cast<int64_t>(max) + 1); }  // prefix sums of a slot with a pending point
-    static int64_t slot_bytes(int32_t max) { return keep_bytes(max) + static_cast<int64_t>(sizeof(sfa::EvAutoSlot)) + csum_bytes(max); }
-    int reserve(int32_t n_slots, int32_t max) {
-        return reserve_all(d_auto, sizeof(sfa::EvAutoSlot) * static_cast<size_t>(n_slots), d_keep, static_cast<size_t>(keep_bytes(max)) * n_slots);
-    }
-    int reserve_call(int32_t n_pending, size_t n) {
-        return reserve_all(d_csum, static_cast<size_t>(csum_bytes(max_samples)) * static_cast<size_t>(std::max(n_pending, 1)), d_aout, sizeof(sfa::EvAutoSlot) * n, h_aout,
-                           sizeof(sfa::EvAutoSlot) * n);
-    }
-    void reset_slot(int32_t sl) { slots[sl] = Slot{}; }
-};
-
-struct Keep {  // sfa_session_keep_events (event mode)
-    int32_t max_events = 0;  // 0: off
-    DevBuf d_keep, d_over;   // [n_slots][max_events] float, [n_slots] u8: the slot outgrew max_events
-    PinBuf h_over;
-    bool on() const { return max_events > 0; }
-    static int64_t slot_bytes(int32_t max) { return 4 * static_cast<int64_t>(max); }
-    int reserve(int32_t n_slots, int32_t max) {
-        const size_t ns = static_cast<size_t>(n_slots);
-        return reserve_all(d_keep, static_cast<size_t>(slot_bytes(max)) * ns, d_over, ns, h_over, ns);
-    }
-};
-
-struct Maps {  // sfa_session_event_maps
-    ctx::MapScratch scratch;      // moves, row table, device output of a call: the session's own, never the context's
-    std::vector<int64_t> q_off;   // [n_slots] where every slot's query begins behind the query base
-    std::vector<sfa::MapRow> band;  // of a call
-    int reserve(int32_t n_slots, size_t n_rows) {  // (the scratch grows slice by slice inside the core)
-        q_off.resize(static_cast<size_t>(n_slots));
-        band.assign(n_rows, sfa::MapRow{});
-        return SFA_OK;
-    }
-};
-
-struct Targets {  // sfa_session_targets, sfa_session_classes
-    bool on = false;
-    int64_t on_cols = 0;                  // on-target columns of a slot's row
-    int32_t first_on = -1, first_off = -1;  // lowest column of either class (-1: the class is empty)
-    std::vector<uint32_t> h_mask;         // of the last sfa_session_targets call (the upload is synchronous: pageable is fine)
-    DevBuf d_mask;                        // target_mask_words(total_cols) words
-    DevBuf d_slot, d_part, d_cls;         // of a call: [n] i32, [n][parts] ClassPartial, [n] sfa_class_t
-    PinBuf h_slot, h_cls;
-    std::vector<int32_t> live;            // ... which entries of the call were launched
-    Event ev[2];
-    static size_t mask_bytes(int64_t total_cols) { return 4 * sfa::target_mask_words(total_cols); }  // one bit per column, and a word
-    int reserve(int64_t total_cols) { return d_mask.reserve(mask_bytes(total_cols)); }
-    int reserve_call(size_t n, size_t parts) {
-        return reserve_all(d_slot, 4 * n, h_slot, 4 * n, d_part, sizeof(sfa::ClassPartial) * n * parts, d_cls, sizeof(sfa_class_t) * n, h_cls, sizeof(sfa_class_t) * n);
-    }
-};
-
-struct Groups {  // sfa_session_target_groups, sfa_session_group_bests
-    int32_t n_groups = 0;                 // 0: off
-    std::vector<uint16_t> h_label;        // of the last sfa_session_target_groups call (the upload is synchronous: pageable is fine)
-    DevBuf d_label;                       // group_label_words(total_cols) words of four labels
-    DevBuf d_slot, d_key, d_best, d_head;  // of a call: [n] i32, [n][n_groups + 1] u64, [n][n_groups + 1] sfa_group_best_t, [n] sfa_group_head_t
-    PinBuf h_slot, h_best, h_head;
-    std::vector<int32_t> live;            // ... which entries of the call were launched
-    Event ev[2];
-    bool on() const { return n_groups > 0; }
-    int reserve(int64_t total_cols) { return d_label.reserve(8 * sfa::group_label_words(total_cols)); }
-    int reserve_call(size_t n, size_t entries, bool bests) {
-        const size_t nb = bests ? sizeof(sfa_group_best_t) * n * entries : 0;
-        if (nb)
-            if (int rc = reserve_all(d_best, nb, h_best, nb)) return rc;
-        return reserve_all(d_slot, 4 * n, h_slot, 4 * n, d_key, 8 * n * entries, d_head, sizeof(sfa_group_head_t) * n, h_head, sizeof(sfa_group_head_t) * n);
-    }
-};
-
-struct Open {  // sfa_session_open_classes (the label table is sess::Groups')
-    std::vector<int32_t> first;           // lowest column of every label, [n_groups + 1]; empty: not looked for since the table was set
-    DevBuf d_slot, d_part, d_out;         // of a call: [n] i32, [n][parts] ClassPartial, [n] sfa_open_class_t
-    PinBuf h_slot, h_out;
-    std::vector<int32_t> live;            // ... which entries of the call were launched
-    Event ev[2];
-    int reserve(size_t n, size_t parts) {
-        return reserve_all(d_slot, 4 * n, h_slot, 4 * n, d_part, sizeof(sfa::ClassPartial) * n * parts, d_out, sizeof(sfa_open_class_t) * n, h_out, sizeof(sfa_open_class_t) * n);
-    }
-};
-
-struct Coverage {  // sfa_session_coverage_config, sfa_session_coverage_add (coverage_rules.hpp)
-    int32_t cap = 0;                      // 0: off
-    int64_t live_cols = 0;                // live on-target columns of a slot's row
-    int32_t first_on = -1, first_off = -1;  // lowest column of either class under the live mask (-1: the class is empty)
-    std::vector<int64_t> h_cov_off;       // [num_ref + 1] where every contig's track begins
-    DevBuf d_depth, d_live, d_cov_off;    // the tracks, the live mask (target_mask_words words), the offsets
-    DevBuf d_stats, d_iv;                 // the mask launch's CoverStats; of a call: [n] sfa_target_t
-    PinBuf h_stats, h_iv;                 // [0] the record's initial value, [1] what the launch left
-    Event ev[2];
-    float ms = 0.0f;                      // device time of the last add + mask
-    bool on() const { return cap > 0; }
-    // The tracks (d_depth, d_cov_off, h_cov_off, the intervals of a call, the events) are the session's ONE depth track: the mask's
-    // cap here and the group cap of sess::GroupCover share them.  Whichever is configured first reserves them; they go when both are off.
-    bool has_track() const { return !h_cov_off.empty(); }
-    int reserve_track(int64_t entries, int32_t num_ref) { return reserve_all(d_depth, 4 * static_cast<size_t>(entries), d_cov_off, 8 * (static_cast<size_t>(num_ref) + 1)); }
-    int reserve_mask(int64_t total_cols) { return reserve_all(d_live, 4 * sfa::target_mask_words(total_cols), d_stats, sizeof(sfa::CoverStats), h_stats, 2 * sizeof(sfa::CoverStats)); }
-    int reserve_call(size_t n) { return reserve_all(d_iv, sizeof(sfa_target_t) * n, h_iv, sizeof(sfa_target_t) * n); }
-    void free_mask() {  // the mask's cap and what only it uses
-        cap = 0, live_cols = 0, first_on = first_off = -1;
-        d_live = DevBuf{}, d_stats = DevBuf{};
-        h_stats = PinBuf{};
-    }
-    void free_track() {
-        std::vector<int64_t>().swap(h_cov_off);
-        d_depth = DevBuf{}, d_cov_off = DevBuf{}, d_iv = DevBuf{};
-        h_iv = PinBuf{};
-    }
-};
-
-struct Reach {  // sfa_session_targets_reach (reach_rules.hpp): the mask is sess::Targets', the anchors lie beside it
-    bool on = false;
-    DevBuf d_anchor;                      // [total_cols] i32: the anchor's entry of its contig's depth track
-    DevBuf d_runs, d_run_off, d_stats;    // of a call: the prepared runs, freed when the build is through; the build launch's CoverStats
-    PinBuf h_stats;                       // [0] the record's initial value, [1] what the launch left
-    int reserve(int64_t total_cols, size_t n_runs, int32_t n_jobs) {
-        return reserve_all(d_anchor, sfa::reach_bytes(total_cols), d_runs, sizeof(sfa::ReachRun) * (n_runs + 1), d_run_off, 4 * (static_cast<size_t>(n_jobs) + 1), d_stats,
-                           sizeof(sfa::CoverStats), h_stats, 2 * sizeof(sfa::CoverStats));
-    }
-    void free_all() {
-        on = false;
-        d_anchor = DevBuf{}, d_runs = DevBuf{}, d_run_off = DevBuf{}, d_stats = DevBuf{};
-        h_stats = PinBuf{};
-    }
-};
-
-struct GroupReach {  // sfa_session_target_groups_reach (reach_group_rules.hpp): the label table is sess::Groups', its anchors lie beside it
-    bool on = false;
-    DevBuf d_anchor;                      // [total_cols] i32: the anchor's entry of its contig's depth track
-    DevBuf d_runs, d_run_off, d_first;    // of a call: the prepared runs, the lowest column of every label; freed when the build is through
-    PinBuf h_first;                       // [2][n_groups + 1]: the table's initial value, what the launch left
-    int reserve(int64_t total_cols, size_t n_runs, int32_t n_jobs, int32_t n_groups) {
-        const size_t e = static_cast<size_t>(n_groups) + 1;
-        return reserve_all(d_anchor, 4 * static_cast<size_t>(total_cols), d_runs, sizeof(sfa::ReachGroupRun) * (n_runs + 1), d_run_off, 4 * (static_cast<size_t>(n_jobs) + 1), d_first,
-                           4 * e, h_first, 2 * 4 * e);
-    }
-    void free_call() {
-        d_runs = DevBuf{}, d_run_off = DevBuf{}, d_first = DevBuf{};
-        h_first = PinBuf{};
-    }
-    void free_all() {
-        on = false;
-        d_anchor = DevBuf{};
-        free_call();
-    }
-};
-
-struct GroupCover {  // sfa_session_group_coverage_config, sfa_session_group_coverage (group_cover_rules.hpp; the tracks are sess::Coverage's)
-    int32_t cap = 0;                      // 0: off
-    std::vector<int32_t> first;           // lowest column of every LIVE label, [n_groups + 1], -1: none (what open_first_cols reads)
-    DevBuf d_live;                        // the live label table: group_label_words(total_cols) words of four labels
-    DevBuf d_first, d_rec;                // [n_groups + 1] i32; [n_groups + 1] sfa_group_cover_t
-    PinBuf h_first, h_rec;                // [2][n_groups + 1]: the tables' initial values, what the launch left
-    Event ev[2];
-    bool on() const { return cap > 0; }
-    // bytes beside the tracks (sfa_session_group_coverage_bytes adds them): what reserve() asks for, through the one function
-    static size_t bytes(int64_t total_cols, int32_t n_groups) { return sfa::group_cover_bytes(total_cols, n_groups); }
-    int reserve(int64_t total_cols, int32_t n_groups) {
-        const size_t e = static_cast<size_t>(n_groups) + 1;
-        return reserve_all(d_live, 8 * sfa::group_label_words(total_cols), d_first, 4 * e, d_rec, sizeof(sfa_group_cover_t) * e, h_first, 2 * 4 * e, h_rec, 2 * sizeof(sfa_group_cover_t) * e);
-    }
-    void free_all() {
-        cap = 0;
-        std::vector<int32_t>().swap(first);
-        d_live = DevBuf{}, d_first = DevBuf{}, d_rec = DevBuf{};
-        h_first = PinBuf{}, h_rec = PinBuf{};
-    }
-};
-
-// SFA_SESSION_SPREAD on a group context: the session is one ordinary session per shard that holds slots (global slot i: local
-// slot i / G of subs[i % G]); every entry point deals its entries to them (session_spread.hpp), runs the shards side by side
-// (for_each_shard) and puts the answers back in the caller's order.  What a call packs or collects per shard lies here and is
-// reused from call to call: a tick allocates nothing once the buffers have grown to its size.
-struct Spread {
-    std::vector<sfa_session *> subs;  // [G]; nullptr: a trailing shard of a session with fewer slots than shards
-    sfa::SpreadPart part;             // of a call
-    struct Shard {                    // of a call, per shard: the payload packed, per-entry arguments gathered, answers
-        std::vector<float> events;
-        std::vector<int16_t> raw;
-        std::vector<double> scaling;
-        std::vector<uint8_t> end;
-        std::vector<sfa_result_t> rows;
-        std::vector<sfa_session_raw_info_t> info;
-        std::vector<sfa_session_auto_t> autos;
-        std::vector<int64_t> len;
-        std::vector<uint64_t> span;
-        std::vector<sfa_class_t> cls;
-        std::vector<sfa_group_best_t> gbest;
-        std::vector<sfa_group_head_t> ghead;
-        std::vector<sfa_open_class_t> ocls;
-        int32_t on_host = 0;
-    };
-    std::vector<Shard> shard;  // [G]
-    bool broken = false;       // a configuration call went through on some shards and failed on another: only sfa_session_destroy is left
-};
-
-}  // namespace sess
-
-// `delete` frees every buffer and event of the session, in whatever order the members stand.  That relies on two things only:
-// sfa_session_destroy has synchronised the context's stream (nothing of the session is in flight), and the stream itself is the
-// context's, which sfa_destroy frees after its sessions (sfa::destroy_sessions).
-struct sfa_session {
-    sfa_ctx *c = nullptr;
-    int32_t n_slots = 0;
-    bool track = true;     // start columns are carried (no SFA_SESSION_NO_START)
-    bool resweep = false;  // SFA_SESSION_RESWEEP: raw mode only; a slot is swept when its window changes, over the window's events
-    int32_t call_no = 0;
-    sess::Rows rows;
-    sess::Sweep sweep;
-    sess::Candidates cand;
-    sess::Raw raw;
-    sess::AutoStart autos;
-    sess::Keep keep;
-    sess::Maps maps;
-    sess::Targets targets;
-    sess::Groups groups;
-    sess::Open open;
-    sess::Coverage cover;
-    sess::GroupCover gcover;
-    sess::Reach reach;
-    sess::GroupReach greach;
-    std::unique_ptr<sess::Spread> spread;  // SFA_SESSION_SPREAD on a group context: `c` is the group, everything above is unused
-    int32_t name_first = 0, name_step = 1;  // a sub-session of a spread session: local slot l is the caller's slot l * step + first (messages)
-};
 
 namespace {
 
@@ -390,165 +28,12 @@ int32_t first_busy_slot(const sfa_session *s) {
     return -1;
 }
 
-int check_slots(const sfa_session *s, const int32_t *slot, int32_t n, const char *who) {
-    for (int32_t i = 0; i < n; ++i)
-        if (slot[i] < 0 || slot[i] >= s->n_slots) return fail(SFA_EINVAL, "%s: slot %d out of range (the session has %d)", who, slot[i], s->n_slots);
-    return SFA_OK;
-}
-
-// a new extend call: its number is what claim_slot stamps the slots it names with
-void begin_call(sfa_session *s) {
-    if (++s->call_no == INT32_MAX) {
-        std::fill(s->rows.stamp.begin(), s->rows.stamp.end(), 0);
-        s->call_no = 1;
-    }
-}
-
-// slot sl is named by the call: in range, and once only
-int claim_slot(sfa_session *s, int32_t sl, const char *who) {
-    if (int rc = check_slots(s, &sl, 1, who)) return rc;
-    if (s->rows.stamp[sl] == s->call_no) return fail(SFA_EINVAL, "%s: slot %d is named twice in one call", who, sl);
-    s->rows.stamp[sl] = s->call_no;
-    return SFA_OK;
-}
-
 // (a slot's next chunk is a first chunk: nothing of its carried row is read)
 void reset_slot(sfa_session *s, int32_t sl) {
     s->rows.len[sl] = 0;
     s->rows.poison[sl] = 0;
     if (s->raw.on) s->raw.reset_slot(sl);
     if (s->autos.on()) s->autos.reset_slot(sl);
-}
-
-// The live mask from the base mask and the depth tracks (session_cover_mask_kernel; on a reach session session_reach_live_kernel,
-// which reads the depth at the column's anchor), on the context's stream; the caller has set the device and synchronises.  The
-// launch in front resets the record the kernel's atomics merge into.
-int cover_enqueue_mask(sfa_session *s) {
-    sfa_ctx *c = s->c;
-    sess::Coverage &v = s->cover;
-    sfa::CoverStats *hs = v.h_stats.as<sfa::CoverStats>();
-    hs[0] = sfa::CoverStats{0ull, sfa::kNoColumn, sfa::kNoColumn};
-    HIP_TRY(hipMemcpyAsync(v.d_stats.p, hs, sizeof(sfa::CoverStats), hipMemcpyHostToDevice, c->stream));
-    if (s->reach.on) {
-        sfa::SessionReachLiveArgs a;
-        a.base = s->targets.d_mask.as<uint32_t>();
-        a.anchor = s->reach.d_anchor.as<int32_t>();
-        a.live = v.d_live.as<uint32_t>();
-        a.depth = v.d_depth.as<uint32_t>();
-        a.cov_off = v.d_cov_off.as<int64_t>();
-        a.col_off = s->rows.d_col_off.as<int64_t>();
-        a.ref = c->model.tables();
-        a.stats = v.d_stats.as<sfa::CoverStats>();
-        a.total_cols = c->model.total_cols;
-        a.n_jobs = c->model.n_jobs;
-        a.n_words = static_cast<int32_t>(sfa::target_mask_words(c->model.total_cols));
-        a.cap = static_cast<uint32_t>(v.cap);
-        hipLaunchKernelGGL(sfa::session_reach_live_kernel, dim3(sfa::cover_mask_blocks(c->model.total_cols)), dim3(sfa::kCoverThreads), 0, c->stream, a);
-        KERNEL_TRY();
-        HIP_TRY(hipMemcpyAsync(hs + 1, v.d_stats.p, sizeof(sfa::CoverStats), hipMemcpyDeviceToHost, c->stream));
-        return SFA_OK;
-    }
-    sfa::SessionCoverMaskArgs a;
-    a.base = s->targets.d_mask.as<uint32_t>();
-    a.live = v.d_live.as<uint32_t>();
-    a.depth = v.d_depth.as<uint32_t>();
-    a.cov_off = v.d_cov_off.as<int64_t>();
-    a.col_off = s->rows.d_col_off.as<int64_t>();
-    a.ref = c->model.tables();
-    a.stats = v.d_stats.as<sfa::CoverStats>();
-    a.total_cols = c->model.total_cols;
-    a.n_jobs = c->model.n_jobs;
-    a.n_words = static_cast<int32_t>(sfa::target_mask_words(c->model.total_cols));
-    a.cap = static_cast<uint32_t>(v.cap);
-    hipLaunchKernelGGL(sfa::session_cover_mask_kernel, dim3(sfa::cover_mask_blocks(c->model.total_cols)), dim3(sfa::kCoverThreads), 0, c->stream, a);
-    KERNEL_TRY();
-    HIP_TRY(hipMemcpyAsync(hs + 1, v.d_stats.p, sizeof(sfa::CoverStats), hipMemcpyDeviceToHost, c->stream));
-    return SFA_OK;
-}
-// ... and what it left, once the stream is through
-void cover_collect(sfa_session *s) {
-    sess::Coverage &v = s->cover;
-    const sfa::CoverStats &st = v.h_stats.as<sfa::CoverStats>()[1];
-    v.live_cols = static_cast<int64_t>(st.live);
-    v.first_on = st.first_on == sfa::kNoColumn ? -1 : st.first_on;
-    v.first_off = st.first_off == sfa::kNoColumn ? -1 : st.first_off;
-}
-int cover_derive(sfa_session *s, const char *who) {
-    if (int rc = cover_enqueue_mask(s)) return rc;
-    if (hipStreamSynchronize(s->c->stream) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
-    cover_collect(s);
-    return SFA_OK;
-}
-
-// The mask's cap goes, or the group cap; the one depth track goes with the last of them
-void cover_drop_mask(sfa_session *s) {
-    s->cover.free_mask();
-    if (!s->gcover.on()) s->cover.free_track();
-}
-void gcover_drop(sfa_session *s) {
-    s->gcover.free_all();
-    if (!s->cover.on()) s->cover.free_track();
-}
-
-// The live label table from the base table and the depth tracks (session_cover_label_kernel; on a reach label table
-// session_reach_label_live_kernel), on the context's stream; the
-// caller has set the device and synchronises.  The upload in front resets the table of firsts the kernel's atomics merge into.
-int gcover_enqueue_labels(sfa_session *s) {
-    sfa_ctx *c = s->c;
-    sess::GroupCover &gc = s->gcover;
-    const size_t entries = static_cast<size_t>(s->groups.n_groups) + 1;
-    int32_t *hf = gc.h_first.as<int32_t>();
-    std::fill(hf, hf + entries, sfa::kNoColumn);
-    HIP_TRY(hipMemcpyAsync(gc.d_first.p, hf, 4 * entries, hipMemcpyHostToDevice, c->stream));
-    if (s->greach.on) {  // (a reach label table: the depth is read at the column's anchor)
-        sfa::SessionReachLabelLiveArgs a;
-        a.base = s->groups.d_label.as<uint64_t>();
-        a.anchor = s->greach.d_anchor.as<int32_t>();
-        a.live = gc.d_live.as<uint16_t>();
-        a.depth = s->cover.d_depth.as<uint32_t>();
-        a.cov_off = s->cover.d_cov_off.as<int64_t>();
-        a.col_off = s->rows.d_col_off.as<int64_t>();
-        a.ref = c->model.tables();
-        a.first = gc.d_first.as<int32_t>();
-        a.total_cols = c->model.total_cols;
-        a.n_jobs = c->model.n_jobs;
-        a.n_groups = s->groups.n_groups;
-        a.cap = static_cast<uint32_t>(gc.cap);
-        hipLaunchKernelGGL(sfa::session_reach_label_live_kernel, dim3(sfa::group_cover_blocks(c->model.total_cols)), dim3(sfa::kGroupCoverThreads), 0, c->stream, a);
-        KERNEL_TRY();
-        HIP_TRY(hipMemcpyAsync(hf + entries, gc.d_first.p, 4 * entries, hipMemcpyDeviceToHost, c->stream));
-        return SFA_OK;
-    }
-    sfa::SessionCoverLabelArgs a;
-    a.base = s->groups.d_label.as<uint64_t>();
-    a.live = gc.d_live.as<uint16_t>();
-    a.depth = s->cover.d_depth.as<uint32_t>();
-    a.cov_off = s->cover.d_cov_off.as<int64_t>();
-    a.col_off = s->rows.d_col_off.as<int64_t>();
-    a.ref = c->model.tables();
-    a.first = gc.d_first.as<int32_t>();
-    a.total_cols = c->model.total_cols;
-    a.n_jobs = c->model.n_jobs;
-    a.n_groups = s->groups.n_groups;
-    a.cap = static_cast<uint32_t>(gc.cap);
-    hipLaunchKernelGGL(sfa::session_cover_label_kernel, dim3(sfa::group_cover_blocks(c->model.total_cols)), dim3(sfa::kGroupCoverThreads), 0, c->stream, a);
-    KERNEL_TRY();
-    HIP_TRY(hipMemcpyAsync(hf + entries, gc.d_first.p, 4 * entries, hipMemcpyDeviceToHost, c->stream));
-    return SFA_OK;
-}
-// ... and what it left, once the stream is through
-void gcover_collect(sfa_session *s) {
-    sess::GroupCover &gc = s->gcover;
-    sfa::group_cover_firsts_for_open(gc.h_first.as<int32_t>() + s->groups.n_groups + 1, s->groups.n_groups, &gc.first);
-}
-// the whole live table anew: the base table's bytes (the words behind the row with them), then the derive
-int gcover_derive(sfa_session *s, const char *who) {
-    sfa_ctx *c = s->c;
-    HIP_TRY(hipMemcpyAsync(s->gcover.d_live.p, s->groups.d_label.p, 8 * sfa::group_label_words(c->model.total_cols), hipMemcpyDeviceToDevice, c->stream));
-    if (int rc = gcover_enqueue_labels(s)) return rc;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
-    gcover_collect(s);
-    return SFA_OK;
 }
 
 // the sweep kernel of the session's kind (with candidates every piece of a long chunk keeps a list: the last one's stays)
@@ -1049,9 +534,10 @@ int session_maps_rows(sfa_session *s, const sfa_result_t *rows, const int32_t *s
 }
 
 // ---- spread sessions (SFA_SESSION_SPREAD on a group context): every entry point dealt to the shards' sub-sessions.  The rules
-// are session_spread.hpp's; here the prologue of each entry point: partition, the sub-calls side by side on the context's shard
-// threads (for_each_shard: shard 0 on the caller's), the answers back in the caller's order.  Calls that touch no device
-// (reset, lengths, the automatic start's records) visit the shards in turn on the caller's thread ----
+// are session_spread.hpp's, the visits (spread_deal, spread_run, spread_visit, spread_idle, spread_all) sfa_session_state.hpp's;
+// here the prologue of each entry point: partition, the sub-calls side by side on the context's shard threads (for_each_shard:
+// shard 0 on the caller's), the answers back in the caller's order.  Calls that touch no device (reset, lengths, the automatic
+// start's records) visit the shards in turn on the caller's thread ----
 
 int spread_create(sfa_ctx *g, int32_t n_slots, uint32_t flags, sfa_session **out) {
     if (n_slots <= 0) return fail(SFA_EINVAL, "sfa_session_create: n_slots must be positive, not %d", n_slots);
@@ -1080,53 +566,6 @@ int spread_create(sfa_ctx *g, int32_t n_slots, uint32_t flags, sfa_session **out
     }
     g->sessions.push_back(s.get());
     *out = s.release();
-    return SFA_OK;
-}
-
-int spread_live(const sfa_session *s, const char *who) {
-    if (s->spread->broken)
-        return fail(SFA_EINVAL, "%s: a configuration call of this spread session failed on one shard after others had taken it; the session takes nothing but "
-                                "sfa_session_destroy",
-                    who);
-    return SFA_OK;
-}
-
-// the call's entries by shard (left in spread->part), after the refusals a session makes by itself -- for the whole call, before
-// any shard hears of it
-int spread_deal(sfa_session *s, const int32_t *slot, int32_t n, bool once, const char *who) {
-    const sfa::SpreadRefusal bad = sfa::spread_partition(slot, n, s->n_slots, static_cast<int32_t>(s->c->shards.size()), once, &s->spread->part);
-    if (bad.why == sfa::kSpreadRange) return fail(SFA_EINVAL, "%s: slot %d out of range (the session has %d)", who, bad.slot, s->n_slots);
-    if (bad.why == sfa::kSpreadTwice) return fail(SFA_EINVAL, "%s: slot %d is named twice in one call", who, bad.slot);
-    return SFA_OK;
-}
-
-// fn(the shard's sub-session, its part of the call, its buffers) on every shard that has entries, side by side
-template <typename F>
-int spread_run(sfa_session *s, F fn) {
-    sess::Spread &sp = *s->spread;
-    return sfa::for_each_shard(s->c, [&](size_t r) { return sp.part.shard[r].n() == 0 ? static_cast<int>(SFA_OK) : fn(sp.subs[r], sp.part.shard[r], sp.shard[r]); });
-}
-// the same in turn on the caller's thread, for calls that are host arithmetic
-template <typename F>
-int spread_visit(sfa_session *s, F fn) {
-    sess::Spread &sp = *s->spread;
-    for (size_t r = 0; r < sp.subs.size(); ++r)
-        if (sp.part.shard[r].n() > 0)
-            if (int rc = fn(sp.subs[r], sp.part.shard[r], sp.shard[r])) return rc;
-    return SFA_OK;
-}
-
-// A shard an extend call has nothing for does what a session call does in front of its work (a batch submitted and never waited
-// for: its error is this call's) and leaves a profile that adds nothing: sfa_get_profile on the group is the slowest shard's
-// times and the summed counts of THIS call
-int spread_idle(sfa_ctx *c) {
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int rc = sfa::resolve_profile(c)) return rc;
-    sfa_profile_t pr{};
-    pr.segment_reruns = c->seg.seg_reruns;
-    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
-    c->prof = pr;
     return SFA_OK;
 }
 
@@ -1260,63 +699,6 @@ int spread_auto_start(sfa_session *s, const int32_t *slot, int32_t n, sfa_sessio
     });
 }
 
-int spread_classes(sfa_session *s, const int32_t *slot, int32_t n, sfa_class_t *out) {
-    static const char *const who = "sfa_session_classes";
-    if (int rc = spread_live(s, who)) return rc;
-    // (sub-session 0 exists: spread_create refuses n_slots <= 0, and shard 0 holds slot 0; every sub-session holds the same mask)
-    if (!s->spread->subs[0]->targets.on) return fail(SFA_EINVAL, "%s: the session has no targets (sfa_session_targets)", who);
-    if (int rc = spread_deal(s, slot, n, true, who)) return rc;
-    return sfa::for_each_shard(s->c, [&](size_t r) {
-        const sfa::SpreadShardPart &p = s->spread->part.shard[r];
-        sess::Spread::Shard &b = s->spread->shard[r];
-        if (p.n() == 0) return spread_idle(s->c->shards[r]);  // (the group's profile is this call's on every shard)
-        b.cls.resize(p.local.size());
-        if (int rc = sfa_session_classes(s->spread->subs[r], p.local.data(), p.n(), b.cls.data())) return rc;
-        sfa::spread_scatter(p, b.cls.data(), out);
-        return static_cast<int>(SFA_OK);
-    });
-}
-
-int spread_group_bests(sfa_session *s, const int32_t *slot, int32_t n, sfa_group_best_t *bests, sfa_group_head_t *heads) {
-    static const char *const who = "sfa_session_group_bests";
-    if (int rc = spread_live(s, who)) return rc;
-    // (sub-session 0 exists and every sub-session holds the same label table, as in spread_classes)
-    const int32_t entries = s->spread->subs[0]->groups.n_groups + 1;
-    if (entries == 1) return fail(SFA_EINVAL, "%s: the session has no groups (sfa_session_target_groups)", who);
-    if (int rc = spread_deal(s, slot, n, true, who)) return rc;
-    return sfa::for_each_shard(s->c, [&](size_t r) {
-        const sfa::SpreadShardPart &p = s->spread->part.shard[r];
-        sess::Spread::Shard &b = s->spread->shard[r];
-        if (p.n() == 0) return spread_idle(s->c->shards[r]);  // (the group's profile is this call's on every shard)
-        b.ghead.resize(p.local.size());
-        if (bests) b.gbest.resize(p.local.size() * static_cast<size_t>(entries));
-        if (int rc = sfa_session_group_bests(s->spread->subs[r], p.local.data(), p.n(), bests ? b.gbest.data() : nullptr, b.ghead.data())) return rc;
-        if (bests) sfa::spread_scatter(p, b.gbest.data(), bests, entries);
-        sfa::spread_scatter(p, b.ghead.data(), heads);
-        return static_cast<int>(SFA_OK);
-    });
-}
-
-int spread_open_classes(sfa_session *s, const int32_t *slot, int32_t n, const uint32_t *open, int32_t n_words, sfa_open_class_t *out) {
-    static const char *const who = "sfa_session_open_classes";
-    if (int rc = spread_live(s, who)) return rc;
-    // (sub-session 0 exists and every sub-session holds the same label table, as in spread_classes)
-    const int32_t n_groups = s->spread->subs[0]->groups.n_groups;
-    if (n_groups == 0) return fail(SFA_EINVAL, "%s: the session has no groups (sfa_session_target_groups)", who);
-    if (open && n_words != sfa::open_words(n_groups))
-        return fail(SFA_EINVAL, "%s: the bitmap of %d groups has %d words, not %d", who, n_groups, sfa::open_words(n_groups), n_words);
-    if (int rc = spread_deal(s, slot, n, true, who)) return rc;
-    return sfa::for_each_shard(s->c, [&](size_t r) {
-        const sfa::SpreadShardPart &p = s->spread->part.shard[r];
-        sess::Spread::Shard &b = s->spread->shard[r];
-        if (p.n() == 0) return spread_idle(s->c->shards[r]);  // (the group's profile is this call's on every shard)
-        b.ocls.resize(p.local.size());
-        if (int rc = sfa_session_open_classes(s->spread->subs[r], p.local.data(), p.n(), open, n_words, b.ocls.data())) return rc;
-        sfa::spread_scatter(p, b.ocls.data(), out);
-        return static_cast<int>(SFA_OK);
-    });
-}
-
 // the sub-session that owns *slot, which becomes its local number there (the one-slot calls: sfa_session_row, sfa_session_events)
 int spread_owner(sfa_session *s, int32_t *slot, const char *who, sfa_session **sub) {
     if (int rc = spread_live(s, who)) return rc;
@@ -1327,23 +709,16 @@ int spread_owner(sfa_session *s, int32_t *slot, const char *who, sfa_session **s
     return SFA_OK;
 }
 
-// A configuration call goes to every sub-session.  What it is refused for is the same on every shard -- the arguments, the
-// session's kind -- but for a slot in use, which is looked for on all of them first.  A shard that fails for a reason of its own
-// (memory) after others have taken the call leaves the session in two minds: it is broken
+// A configuration call that needs every slot empty: a slot in use is the one refusal that differs from shard to shard, so it is
+// looked for on all of them before any shard hears of the call (spread_all)
 template <typename F>
 int spread_config(sfa_session *s, const char *who, F fn) {
     if (int rc = spread_live(s, who)) return rc;
-    sess::Spread &sp = *s->spread;
-    for (const sfa_session *sub : sp.subs)
+    for (const sfa_session *sub : s->spread->subs)
         if (sub)
             if (const int32_t sl = first_busy_slot(sub); sl >= 0)
                 return fail(SFA_EINVAL, "%s: slot %d is not empty; a session is configured only while every slot is (sfa_session_reset)", who, slot_name(sub, sl));
-    std::vector<int> rcs(sp.subs.size(), 0);
-    const int rc = sfa::for_each_shard(s->c, [&](size_t r) { return sp.subs[r] ? (rcs[r] = fn(sp.subs[r])) : static_cast<int>(SFA_OK); });
-    size_t have = 0, failed = 0;
-    for (size_t r = 0; r < sp.subs.size(); ++r) have += sp.subs[r] != nullptr, failed += rcs[r] != SFA_OK;
-    if (failed != 0 && failed != have) sp.broken = true;
-    return rc;
+    return spread_all(s, who, fn);
 }
 
 int spread_event_maps(sfa_session *s, const sfa_result_t *rows, const int32_t *slot_of_row, int32_t n_rows, const int64_t *map_off, int32_t *pairs, int32_t *n_on_host) {
@@ -1365,54 +740,6 @@ int spread_event_maps(sfa_session *s, const sfa_result_t *rows, const int32_t *s
     return rc;
 }
 
-}  // namespace
-
-namespace {
-// a configuration call of a spread session: to every sub-session, as sfa_session_targets goes
-template <class F>
-int cover_spread_all(sfa_session *s, const char *who, F call) {
-    if (int rc = spread_live(s, who)) return rc;
-    sess::Spread &sp = *s->spread;
-    std::vector<int> rcs(sp.subs.size(), 0);
-    const int rc = sfa::for_each_shard(s->c, [&](size_t r) { return sp.subs[r] ? (rcs[r] = call(sp.subs[r])) : static_cast<int>(SFA_OK); });
-    size_t have = 0, failed = 0;
-    for (size_t r = 0; r < sp.subs.size(); ++r) have += sp.subs[r] != nullptr, failed += rcs[r] != SFA_OK;
-    if (failed != 0 && failed != have) sp.broken = true;
-    return rc;
-}
-
-// the reference model as the coverage rules read it (host tables; jobs are contig-major, '+' before '-': sfa_context.hip)
-struct CoverModel {
-    std::vector<int32_t> job_contig, ref_len;
-    std::vector<int8_t> job_strand;
-    sfa::TargetModel m;
-    CoverModel(const sfa_session *s) {
-        const sfa_ctx *c = s->c;
-        const int32_t nj = c->model.n_jobs, strands = nj / c->model.num_ref;
-        job_contig.resize(nj), job_strand.resize(nj), ref_len.resize(c->model.num_ref);
-        for (int32_t j = 0; j < nj; ++j) job_contig[j] = j / strands, job_strand[j] = (j % strands) ? '-' : '+';
-        for (int32_t r = 0; r < c->model.num_ref; ++r) ref_len[r] = c->model.h_job_len[static_cast<size_t>(r) * strands];
-        m = sfa::TargetModel{c->model.num_ref, nj, job_contig.data(), job_strand.data(), c->model.h_job_len.data(), s->rows.h_col_off.data(), ref_len.data(),
-                             c->model.h_ref_off.data(), c->model.total_cols};
-    }
-};
-
-// The session's one depth track, for whichever cap is configured: reserved and its offsets uploaded, and zeroed when `zero` (the
-// caller's: the other cap is off, so nobody's depth is lost).  The caller has set the device; the stream is idle.
-int cover_track_up(sfa_session *s, const bool zero) {
-    sfa_ctx *c = s->c;
-    sess::Coverage &v = s->cover;
-    const CoverModel cm(s);
-    std::vector<int64_t> cov_off;
-    sfa::coverage_offsets(cm.ref_len.data(), c->model.num_ref, &cov_off);
-    const bool fresh = !v.has_track();
-    if (int rc = v.reserve_track(cov_off.back(), c->model.num_ref)) return rc;
-    if (int rc = sess::create_events(v.ev, 2)) return rc;
-    v.h_cov_off.swap(cov_off);
-    HIP_TRY(hipMemcpyAsync(v.d_cov_off.p, v.h_cov_off.data(), 8 * v.h_cov_off.size(), hipMemcpyHostToDevice, c->stream));
-    if (zero || fresh) HIP_TRY(hipMemsetAsync(v.d_depth.p, 0, 4 * static_cast<size_t>(v.h_cov_off.back()), c->stream));
-    return SFA_OK;
-}
 }  // namespace
 
 namespace sfa {
@@ -1575,841 +902,6 @@ int sfa_session_extend(sfa_session_t *s, const int32_t *slot, const float *event
     if (s->spread) return spread_extend(s, slot, events, ev_off, n, out);
     if (int rc = extend_check(s, slot, events, ev_off, n)) return rc;
     return n == 0 ? static_cast<int>(SFA_OK) : extend_run(s, slot, events, ev_off, n, out);
-}
-
-// ---- target classes (target_rules.hpp, sdtw_session_class.hpp) ----
-
-int sfa_session_targets(sfa_session_t *s, const sfa_target_t *targets, int32_t n) {
-    static const char *const who = "sfa_session_targets";
-    if (!s || n < 0 || (n > 0 && !targets)) return fail(SFA_EINVAL, "%s: bad argument", who);
-    if (s->resweep)
-        return fail(SFA_EINVAL, "%s: the session was created with SFA_SESSION_RESWEEP: its carried row belongs to the reversed query, and what its minimum means has "
-                                "not been looked into",
-                    who);
-    if (s->spread) {  // every sub-session holds the mask (no slot needs to be empty: spread_config's check does not apply)
-        if (int rc = spread_live(s, who)) return rc;
-        sess::Spread &sp = *s->spread;
-        std::vector<int> rcs(sp.subs.size(), 0);
-        const int rc = sfa::for_each_shard(s->c, [&](size_t r) { return sp.subs[r] ? (rcs[r] = sfa_session_targets(sp.subs[r], targets, n)) : static_cast<int>(SFA_OK); });
-        size_t have = 0, failed = 0;
-        for (size_t r = 0; r < sp.subs.size(); ++r) have += sp.subs[r] != nullptr, failed += rcs[r] != SFA_OK;
-        if (failed != 0 && failed != have) sp.broken = true;
-        return rc;
-    }
-    sfa_ctx *c = s->c;
-    sess::Targets &t = s->targets;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // (a mask in use is not replaced under a kernel)
-    if (n == 0) {
-        t.on = false;
-        t.on_cols = 0;
-        t.first_on = t.first_off = -1;
-        std::vector<uint32_t>().swap(t.h_mask);
-        t.d_mask = DevBuf{};  // (freed; the buffers of a call stay for the next mask)
-        s->reach.free_all();  // (a reach list's anchors go with its mask)
-        cover_drop_mask(s);  // (a coverage cap lives on the mask: off with it; a group cap keeps the depth track)
-        return SFA_OK;
-    }
-    if (c->model.total_cols >= INT32_MAX) return fail(SFA_ERANGE, "%s: the reference has %lld columns; the classes count them in 31 bits", who, (long long)c->model.total_cols);
-    // the model's tables on the host: jobs are contig-major, '+' before '-' (sfa_context.hip)
-    const int32_t nj = c->model.n_jobs, strands = nj / c->model.num_ref;
-    std::vector<int32_t> job_contig(nj), ref_len(c->model.num_ref);
-    std::vector<int8_t> job_strand(nj);
-    for (int32_t j = 0; j < nj; ++j) job_contig[j] = j / strands, job_strand[j] = (j % strands) ? '-' : '+';
-    for (int32_t r = 0; r < c->model.num_ref; ++r) ref_len[r] = c->model.h_job_len[static_cast<size_t>(r) * strands];
-    const sfa::TargetModel m{c->model.num_ref, nj, job_contig.data(), job_strand.data(), c->model.h_job_len.data(), s->rows.h_col_off.data(), ref_len.data(),
-                             c->model.h_ref_off.data(), c->model.total_cols};
-    char msg[192];
-    if (sfa::target_list_error(targets, n, m, msg, sizeof msg)) return fail(SFA_EINVAL, "%s: %s", who, msg);
-    std::vector<uint32_t> mask;
-    const int64_t on_cols = sfa::target_mask(targets, n, m, &mask);
-    if (int rc = t.reserve(c->model.total_cols)) return rc;
-    if (int rc = sess::create_events(t.ev, 2)) return rc;
-    s->reach.free_all();  // (a plain mask replaces a reach list, before the mask is overwritten: no anchor outlives the mask it belongs to)
-    t.h_mask.swap(mask);
-    HIP_TRY(hipMemcpyAsync(t.d_mask.p, t.h_mask.data(), 4 * t.h_mask.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    t.on_cols = on_cols;
-    t.first_on = sfa::target_first_of_class(t.h_mask, c->model.total_cols, true);
-    t.first_off = sfa::target_first_of_class(t.h_mask, c->model.total_cols, false);
-    t.on = true;
-    if (s->cover.on()) return cover_derive(s, who);  // (the depth is kept: the live mask of the new base mask, read at the column's own coordinate)
-    return SFA_OK;
-}
-
-// ---- reach targets (reach_rules.hpp, sdtw_session_reach.hpp) ----
-
-size_t sfa_session_reach_bytes(const sfa_ref_t *ref, int flag) {
-    if (!ref || ref->num_ref <= 0 || !ref->ref_lengths) return 0;
-    int64_t cols = 0;
-    for (int32_t r = 0; r < ref->num_ref; ++r) {
-        if (ref->ref_lengths[r] <= 0) return 0;
-        cols += static_cast<int64_t>(ref->ref_lengths[r]) * ((flag & SFA_RNA) ? 1 : 2);
-    }
-    return sfa::reach_bytes(cols);
-}
-
-int sfa_session_targets_reach(sfa_session_t *s, const sfa_reach_target_t *targets, int32_t n) {
-    static const char *const who = "sfa_session_targets_reach";
-    if (!s || n < 0 || (n > 0 && !targets)) return fail(SFA_EINVAL, "%s: bad argument", who);
-    if (s->resweep)
-        return fail(SFA_EINVAL, "%s: the session was created with SFA_SESSION_RESWEEP: its carried row belongs to the reversed query, and what its minimum means has "
-                                "not been looked into",
-                    who);
-    if (n == 0) return sfa_session_targets(s, nullptr, 0);  // (targets off, the anchors freed: one path)
-    if (s->spread) {  // every sub-session holds the mask and the anchors, as in sfa_session_targets
-        if (int rc = spread_live(s, who)) return rc;
-        sess::Spread &sp = *s->spread;
-        std::vector<int> rcs(sp.subs.size(), 0);
-        const int rc = sfa::for_each_shard(s->c, [&](size_t r) { return sp.subs[r] ? (rcs[r] = sfa_session_targets_reach(sp.subs[r], targets, n)) : static_cast<int>(SFA_OK); });
-        size_t have = 0, failed = 0;
-        for (size_t r = 0; r < sp.subs.size(); ++r) have += sp.subs[r] != nullptr, failed += rcs[r] != SFA_OK;
-        if (failed != 0 && failed != have) sp.broken = true;
-        return rc;
-    }
-    sfa_ctx *c = s->c;
-    sess::Targets &t = s->targets;
-    sess::Reach &rc_ = s->reach;
-    if (c->model.total_cols >= INT32_MAX) return fail(SFA_ERANGE, "%s: the reference has %lld columns; the classes count them in 31 bits", who, (long long)c->model.total_cols);
-    const CoverModel cm(s);
-    char msg[224];
-    if (sfa::reach_list_error(targets, n, cm.m, msg, sizeof msg)) return fail(SFA_EINVAL, "%s: %s", who, msg);
-    sfa::ReachPrepared prep;
-    sfa::reach_prepare(targets, n, cm.m, &prep);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // (a mask in use is not replaced under a kernel)
-    // (from here on the old mask is gone: an allocation or device failure leaves the session without targets -- and so without a
-    // mask cap, which lives on the mask -- never with half of two lists; include/sigfish_amd.h says so)
-    const auto give_up = [&](int rc) {
-        sfa_session_targets(s, nullptr, 0);
-        return rc;
-    };
-    if (int rc = t.reserve(c->model.total_cols)) return give_up(rc);
-    if (int rc = sess::create_events(t.ev, 2)) return give_up(rc);
-    if (int rc = rc_.reserve(c->model.total_cols, prep.runs.size(), c->model.n_jobs)) return give_up(rc);
-    hipStream_t st = c->stream;
-    const size_t words = sfa::target_mask_words(c->model.total_cols);
-    sfa::CoverStats *hs = rc_.h_stats.as<sfa::CoverStats>();
-    hs[0] = sfa::CoverStats{0ull, sfa::kNoColumn, sfa::kNoColumn};
-    sfa::SessionReachBuildArgs a;
-    a.runs = rc_.d_runs.as<sfa::ReachRun>();
-    a.run_off = rc_.d_run_off.as<int32_t>();
-    a.col_off = s->rows.d_col_off.as<int64_t>();
-    a.mask = t.d_mask.as<uint32_t>();
-    a.anchor = rc_.d_anchor.as<int32_t>();
-    a.stats = rc_.d_stats.as<sfa::CoverStats>();
-    a.total_cols = c->model.total_cols;
-    a.n_jobs = c->model.n_jobs;
-    a.n_words = static_cast<int32_t>(words);
-    const auto enqueue = [&]() -> int {  // (the uploads read pageable memory: they are through when the calls return)
-        HIP_TRY(hipMemcpyAsync(rc_.d_stats.p, hs, sizeof(sfa::CoverStats), hipMemcpyHostToDevice, st));
-        if (!prep.runs.empty()) HIP_TRY(hipMemcpyAsync(rc_.d_runs.p, prep.runs.data(), sizeof(sfa::ReachRun) * prep.runs.size(), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(rc_.d_run_off.p, prep.run_off.data(), 4 * prep.run_off.size(), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(t.d_mask.p, 0, 4 * words, st));  // (the spare word stays zero)
-        hipLaunchKernelGGL(sfa::session_reach_build_kernel, dim3(sfa::cover_mask_blocks(c->model.total_cols)), dim3(sfa::kCoverThreads), 0, st, a);
-        KERNEL_TRY();
-        HIP_TRY(hipMemcpyAsync(hs + 1, rc_.d_stats.p, sizeof(sfa::CoverStats), hipMemcpyDeviceToHost, st));
-        return SFA_OK;
-    };
-    if (int rc = enqueue()) return give_up(rc);
-    if (hipStreamSynchronize(st) != hipSuccess) return give_up(fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError())));
-    rc_.d_runs = DevBuf{}, rc_.d_run_off = DevBuf{};  // (the runs were the call's: only the anchors and the 16-byte record stay)
-    std::vector<uint32_t>().swap(t.h_mask);  // (the mask was built on the device: sfa_session_reach_tables copies it back)
-    t.on_cols = static_cast<int64_t>(hs[1].live);
-    t.first_on = hs[1].first_on == sfa::kNoColumn ? -1 : hs[1].first_on;
-    t.first_off = hs[1].first_off == sfa::kNoColumn ? -1 : hs[1].first_off;
-    t.on = true;
-    rc_.on = true;
-    if (s->cover.on()) return cover_derive(s, who);  // (the depth is kept: the live mask of the new base mask and its anchors)
-    return SFA_OK;
-}
-
-int sfa_session_reach_tables(sfa_session_t *s, uint32_t *mask, size_t n_words, int32_t *anchor, int64_t n_cols) {
-    static const char *const who = "sfa_session_reach_tables";
-    if (!s) return fail(SFA_EINVAL, "%s: null session", who);
-    if (s->spread) {
-        if (int rc = spread_live(s, who)) return rc;
-        return sfa_session_reach_tables(s->spread->subs[0], mask, n_words, anchor, n_cols);  // (shard 0 answers: every shard holds the same tables)
-    }
-    sfa_ctx *c = s->c;
-    if (!s->reach.on) return fail(SFA_EINVAL, "%s: the session has no reach targets (sfa_session_targets_reach)", who);
-    const size_t words = sfa::target_mask_words(c->model.total_cols);
-    if (mask && n_words != words) return fail(SFA_EINVAL, "%s: n_words is %zu; the mask has %zu words", who, n_words, words);
-    if (anchor && n_cols != c->model.total_cols) return fail(SFA_EINVAL, "%s: n_cols is %lld; a row has %lld columns", who, (long long)n_cols, (long long)c->model.total_cols);
-    HIP_TRY(hipSetDevice(c->device));
-    if (mask) HIP_TRY(hipMemcpyAsync(mask, s->targets.d_mask.p, 4 * words, hipMemcpyDeviceToHost, c->stream));
-    if (anchor) HIP_TRY(hipMemcpyAsync(anchor, s->reach.d_anchor.p, 4 * static_cast<size_t>(n_cols), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SFA_OK;
-}
-
-int64_t sfa_session_target_columns(sfa_session_t *s) {
-    if (!s) return fail(SFA_EINVAL, "sfa_session_target_columns: null session");
-    if (s->spread) return sfa_session_target_columns(s->spread->subs[0]);  // (sub-session 0 always exists, as in spread_classes)
-    if (s->cover.on()) return s->cover.live_cols;
-    return s->targets.on ? s->targets.on_cols : 0;
-}
-
-int sfa_session_classes(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_class_t *out) {
-    static const char *const who = "sfa_session_classes";
-    if (!s || n < 0 || (n > 0 && (!slot || !out))) return fail(SFA_EINVAL, "%s: bad argument", who);
-    if (s->spread) return spread_classes(s, slot, n, out);
-    sess::Targets &t = s->targets;
-    if (!t.on) return fail(SFA_EINVAL, "%s: the session has no targets (sfa_session_targets)", who);
-    if (int rc = check_slots(s, slot, n, who)) return rc;
-    begin_call(s);  // (the stamps say which slots this call has named)
-    for (int32_t i = 0; i < n; ++i)
-        if (int rc = claim_slot(s, slot[i], who)) return rc;
-    if (n == 0) return SFA_OK;
-    sfa_ctx *c = s->c;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int rc = sfa::resolve_profile(c)) return rc;
-    sfa_class_t none{};
-    none.on_score = none.off_score = INFINITY;
-    none.on_rid = none.on_pos_end = none.off_rid = none.off_pos_end = -1;
-    t.live.clear();
-    for (int32_t i = 0; i < n; ++i)  // empty and poisoned slots are not launched
-        if (!s->rows.poison[slot[i]] && s->rows.len[slot[i]] > 0) t.live.push_back(i);
-    const int32_t m = static_cast<int32_t>(t.live.size()), parts = sfa::class_parts(c->model.total_cols);
-    // (every refusal in front of the first write to the caller's records)
-    if (static_cast<int64_t>(m) * parts > INT32_MAX) return fail(SFA_ERANGE, "%s: %d slots x %d parts of a row are more blocks than a launch takes", who, m, parts);
-    if (m > 0)
-        if (int rc = t.reserve_call(static_cast<size_t>(m), static_cast<size_t>(parts))) return rc;
-    for (int32_t i = 0; i < n; ++i) out[i] = none;
-    sfa_profile_t pr{};
-    pr.segment_reruns = c->seg.seg_reruns;
-    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
-    if (m > 0) {
-        int32_t *hs = t.h_slot.as<int32_t>();
-        for (int32_t k = 0; k < m; ++k) hs[k] = slot[t.live[k]];
-        hipStream_t st = c->stream;
-        HIP_TRY(hipMemcpyAsync(t.d_slot.p, hs, 4 * static_cast<size_t>(m), hipMemcpyHostToDevice, st));
-        sfa::SessionClassArgs a;
-        a.slot = t.d_slot.as<int32_t>();
-        a.rows = s->rows.d_row_c.as<float>() + sfa::kSessionPad;
-        a.mask = s->cover.on() ? s->cover.d_live.as<uint32_t>() : t.d_mask.as<uint32_t>();  // (the kernel is the same: another pointer)
-        a.part = t.d_part.as<sfa::ClassPartial>();
-        a.total_cols = c->model.total_cols;
-        a.n = m;
-        a.n_parts = parts;
-        sfa::SessionClassRowsArgs ra;
-        ra.part = a.part;
-        ra.col_off = s->rows.d_col_off.as<int64_t>();
-        ra.ref = c->model.tables();
-        ra.out = t.d_cls.as<sfa_class_t>();
-        ra.n = m;
-        ra.n_parts = parts;
-        ra.n_jobs = c->model.n_jobs;
-        ra.first_on = s->cover.on() ? s->cover.first_on : t.first_on;
-        ra.first_off = s->cover.on() ? s->cover.first_off : t.first_off;
-        HIP_TRY(hipEventRecord(t.ev[0], st));
-        hipLaunchKernelGGL(sfa::sdtw_session_class_kernel, dim3(static_cast<unsigned>(m) * parts), dim3(sfa::kClassThreads), 0, st, a);
-        KERNEL_TRY();
-        hipLaunchKernelGGL(sfa::sdtw_session_class_rows_kernel, dim3(m), dim3(64), 0, st, ra);
-        KERNEL_TRY();
-        HIP_TRY(hipEventRecord(t.ev[1], st));
-        HIP_TRY(hipMemcpyAsync(t.h_cls.p, t.d_cls.p, sizeof(sfa_class_t) * static_cast<size_t>(m), hipMemcpyDeviceToHost, st));
-        if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
-        pr.class_ms = pr.total_ms = ms;
-        for (int32_t k = 0; k < m; ++k) {
-            out[t.live[k]] = t.h_cls.as<sfa_class_t>()[k];
-            out[t.live[k]].n_events = static_cast<int32_t>(s->rows.len[slot[t.live[k]]]);
-        }
-    }
-    c->prof = pr;
-    return SFA_OK;
-}
-
-int sfa_target_decide(const sfa_class_t *cls, int32_t mode, int32_t min_events, float margin) {
-    return cls ? sfa::target_decide(*cls, mode, min_events, margin) : 0;
-}
-
-// ---- coverage caps (coverage_rules.hpp, sdtw_session_cover.hpp) ----
-
-size_t sfa_session_coverage_bytes(const sfa_ref_t *ref, int flag) {
-    if (!ref || ref->num_ref <= 0 || !ref->ref_lengths) return 0;
-    int64_t entries = 0, cols = 0;
-    for (int32_t r = 0; r < ref->num_ref; ++r) {
-        if (ref->ref_lengths[r] <= 0) return 0;
-        entries += sfa::coverage_track_len(ref->ref_lengths[r]);
-        cols += static_cast<int64_t>(ref->ref_lengths[r]) * ((flag & SFA_RNA) ? 1 : 2);
-    }
-    return sfa::coverage_bytes(entries, cols);
-}
-
-int sfa_session_coverage_config(sfa_session_t *s, int32_t cap) {
-    static const char *const who = "sfa_session_coverage_config";
-    if (!s) return fail(SFA_EINVAL, "%s: null session", who);
-    if (cap < 0 || cap > sfa::kCoverCapMax) return fail(SFA_EINVAL, "%s: cap must be 0 (off) .. %d, not %d", who, sfa::kCoverCapMax, cap);
-    if (s->spread) {
-        if (int rc = spread_live(s, who)) return rc;
-        if (cap > 0 && !s->spread->subs[0]->targets.on) return fail(SFA_EINVAL, "%s: the session has no targets (sfa_session_targets)", who);
-        return cover_spread_all(s, who, [&](sfa_session *sub) { return sfa_session_coverage_config(sub, cap); });
-    }
-    sfa_ctx *c = s->c;
-    sess::Coverage &v = s->cover;
-    if (cap > 0 && !s->targets.on) return fail(SFA_EINVAL, "%s: the session has no targets (sfa_session_targets)", who);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // (a mask in use is not replaced under a kernel)
-    if (cap == 0) {
-        cover_drop_mask(s);
-        return SFA_OK;
-    }
-    if (int rc = cover_track_up(s, !s->gcover.on())) return rc;  // (a group cap's depth is kept: the track is the session's one)
-    if (int rc = v.reserve_mask(c->model.total_cols)) {
-        cover_drop_mask(s);
-        return rc;
-    }
-    HIP_TRY(hipMemsetAsync(v.d_live.p, 0, 4 * sfa::target_mask_words(c->model.total_cols), c->stream));  // (the spare word stays zero)
-    v.cap = cap;
-    if (int rc = cover_derive(s, who)) {  // (without a group cap the depth is 0 everywhere: the live mask is the base mask)
-        cover_drop_mask(s);
-        return rc;
-    }
-    return SFA_OK;
-}
-
-int sfa_session_coverage_add(sfa_session_t *s, const sfa_target_t *iv, int32_t n, int64_t *open_columns) {
-    static const char *const who = "sfa_session_coverage_add";
-    if (!s || n < 0 || (n > 0 && !iv)) return fail(SFA_EINVAL, "%s: bad argument", who);
-    if (n > sfa::kCoverIntervalsMax) return fail(SFA_EINVAL, "%s: %d intervals in one call; at most %d", who, n, sfa::kCoverIntervalsMax);
-    sfa_session *first = s->spread ? s->spread->subs[0] : s;  // (sub-session 0 always exists; every sub-session holds the same state)
-    if (s->spread)
-        if (int rc = spread_live(s, who)) return rc;
-    if (!first->cover.on() && !first->gcover.on()) return fail(SFA_EINVAL, "%s: the session has no coverage cap (sfa_session_coverage_config)", who);
-    {
-        const CoverModel cm(first);
-        char msg[192];
-        if (sfa::coverage_list_error(iv, n, cm.m, msg, sizeof msg)) return fail(SFA_EINVAL, "%s: %s", who, msg);
-    }
-    if (s->spread) {
-        if (int rc = cover_spread_all(s, who, [&](sfa_session *sub) { return sfa_session_coverage_add(sub, iv, n, nullptr); })) return rc;
-        if (open_columns) *open_columns = sfa_session_target_columns(first);  // (shard 0's count: every shard holds the same mask)
-        return SFA_OK;
-    }
-    sfa_ctx *c = s->c;
-    sess::Coverage &v = s->cover;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    hipStream_t st = c->stream;
-    HIP_TRY(hipEventRecord(v.ev[0], st));
-    if (n > 0) {
-        if (int rc = v.reserve_call(static_cast<size_t>(n))) return rc;
-        memcpy(v.h_iv.p, iv, sizeof(sfa_target_t) * static_cast<size_t>(n));
-        HIP_TRY(hipMemcpyAsync(v.d_iv.p, v.h_iv.p, sizeof(sfa_target_t) * static_cast<size_t>(n), hipMemcpyHostToDevice, st));
-        sfa::SessionCoverAddArgs a;
-        a.iv = v.d_iv.as<sfa_target_t>();
-        a.cov_off = v.d_cov_off.as<int64_t>();
-        a.ref_len = c->model.d_ref_len.as<int32_t>();
-        a.ref_st_offset = c->model.d_ref_off.as<int32_t>();
-        a.depth = v.d_depth.as<uint32_t>();
-        a.n = n;
-        hipLaunchKernelGGL(sfa::session_cover_add_kernel, dim3(static_cast<unsigned>(n)), dim3(sfa::kCoverThreads), 0, st, a);
-        KERNEL_TRY();
-    }
-    // whichever of the live mask and the live labels are on, from the one track, in this call
-    if (v.on())
-        if (int rc = cover_enqueue_mask(s)) return rc;
-    if (s->gcover.on())
-        if (int rc = gcover_enqueue_labels(s)) return rc;
-    HIP_TRY(hipEventRecord(v.ev[1], st));
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
-    if (v.on()) cover_collect(s);
-    if (s->gcover.on()) gcover_collect(s);
-    HIP_TRY(hipEventElapsedTime(&v.ms, v.ev[0], v.ev[1]));
-    sfa_profile_t pr{};
-    pr.segment_reruns = c->seg.seg_reruns;
-    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
-    pr.class_ms = pr.total_ms = v.ms;
-    c->prof = pr;
-    if (open_columns) *open_columns = sfa_session_target_columns(s);  // (the live columns under a mask cap; without one the mask's own)
-    return SFA_OK;
-}
-
-int sfa_session_coverage_depth(sfa_session_t *s, int32_t contig, uint32_t *out, int32_t n) {
-    static const char *const who = "sfa_session_coverage_depth";
-    if (!s || !out) return fail(SFA_EINVAL, "%s: bad argument", who);
-    if (s->spread) {
-        if (int rc = spread_live(s, who)) return rc;
-        return sfa_session_coverage_depth(s->spread->subs[0], contig, out, n);  // (shard 0 answers, on the caller's thread as in for_each_shard)
-    }
-    sfa_ctx *c = s->c;
-    sess::Coverage &v = s->cover;
-    if (!v.on() && !s->gcover.on()) return fail(SFA_EINVAL, "%s: the session has no coverage cap (sfa_session_coverage_config)", who);
-    if (contig < 0 || contig >= c->model.num_ref) return fail(SFA_EINVAL, "%s: contig %d out of range (the reference has %d)", who, contig, c->model.num_ref);
-    const int64_t len = v.h_cov_off[static_cast<size_t>(contig) + 1] - v.h_cov_off[static_cast<size_t>(contig)];
-    if (n != len) return fail(SFA_EINVAL, "%s: contig %d has %lld entries (ref_length + 1), not %d", who, contig, static_cast<long long>(len), n);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(out, v.d_depth.as<uint32_t>() + v.h_cov_off[static_cast<size_t>(contig)], 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SFA_OK;
-}
-
-// ---- group caps (group_cover_rules.hpp, sdtw_session_groupcover.hpp) ----
-
-size_t sfa_session_group_coverage_bytes(const sfa_ref_t *ref, int flag, int32_t n_groups) {
-    if (!ref || ref->num_ref <= 0 || !ref->ref_lengths || n_groups < 1 || n_groups > sfa::kGroupMax) return 0;
-    int64_t entries = 0, cols = 0;
-    for (int32_t r = 0; r < ref->num_ref; ++r) {
-        if (ref->ref_lengths[r] <= 0) return 0;
-        entries += sfa::coverage_track_len(ref->ref_lengths[r]);
-        cols += static_cast<int64_t>(ref->ref_lengths[r]) * ((flag & SFA_RNA) ? 1 : 2);
-    }
-    return 4 * static_cast<size_t>(entries) + sess::GroupCover::bytes(cols, n_groups);
-}
-
-int sfa_session_group_coverage_config(sfa_session_t *s, int32_t cap) {
-    static const char *const who = "sfa_session_group_coverage_config";
-    if (!s) return fail(SFA_EINVAL, "%s: null session", who);
-    if (cap < 0 || cap > sfa::kGroupCapMax) return fail(SFA_EINVAL, "%s: cap must be 0 (off) .. %d, not %d", who, sfa::kGroupCapMax, cap);
-    if (s->spread) {
-        if (int rc = spread_live(s, who)) return rc;
-        if (cap > 0 && !s->spread->subs[0]->groups.on()) return fail(SFA_EINVAL, "%s: the session has no groups (sfa_session_target_groups)", who);
-        return cover_spread_all(s, who, [&](sfa_session *sub) { return sfa_session_group_coverage_config(sub, cap); });
-    }
-    sfa_ctx *c = s->c;
-    sess::GroupCover &gc = s->gcover;
-    if (cap > 0 && !s->groups.on()) return fail(SFA_EINVAL, "%s: the session has no groups (sfa_session_target_groups)", who);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // (a table in use is not replaced under a kernel)
-    if (cap == 0) {
-        gcover_drop(s);
-        return SFA_OK;
-    }
-    // (a mask cap's depth is kept: the track is the session's one.  Whatever fails from here on leaves the group cap off)
-    int rc = cover_track_up(s, !s->cover.on());
-    if (!rc) rc = gc.reserve(c->model.total_cols, s->groups.n_groups);
-    if (!rc) rc = sess::create_events(gc.ev, 2);
-    if (rc) {
-        gcover_drop(s);
-        return rc;
-    }
-    gc.cap = cap;
-    if (int rc = gcover_derive(s, who)) {
-        gcover_drop(s);
-        return rc;
-    }
-    return SFA_OK;
-}
-
-int sfa_session_group_coverage(sfa_session_t *s, sfa_group_cover_t *out, int32_t n) {
-    static const char *const who = "sfa_session_group_coverage";
-    if (!s || !out) return fail(SFA_EINVAL, "%s: bad argument", who);
-    if (s->spread) {
-        if (int rc = spread_live(s, who)) return rc;
-        return sfa_session_group_coverage(s->spread->subs[0], out, n);  // (shard 0 answers: every shard holds the same tables and tracks)
-    }
-    sfa_ctx *c = s->c;
-    sess::GroupCover &gc = s->gcover;
-    if (!gc.on()) return fail(SFA_EINVAL, "%s: the session has no group cap (sfa_session_group_coverage_config)", who);
-    const int32_t entries = s->groups.n_groups + 1;
-    if (n != entries) return fail(SFA_EINVAL, "%s: the session has %d entries (n_groups + 1), not %d", who, entries, n);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    hipStream_t st = c->stream;
-    sfa_group_cover_t *hr = gc.h_rec.as<sfa_group_cover_t>();
-    std::fill(hr, hr + entries, sfa::group_cover_none());
-    HIP_TRY(hipEventRecord(gc.ev[0], st));
-    HIP_TRY(hipMemcpyAsync(gc.d_rec.p, hr, sizeof(sfa_group_cover_t) * static_cast<size_t>(entries), hipMemcpyHostToDevice, st));  // the reset in front of the launch
-    if (s->greach.on) {  // (a reach label table: the '+' jobs' body columns only)
-        sfa::SessionReachLabelGroupArgs a;
-        a.base = s->groups.d_label.as<uint64_t>();
-        a.anchor = s->greach.d_anchor.as<int32_t>();
-        a.depth = s->cover.d_depth.as<uint32_t>();
-        a.cov_off = s->cover.d_cov_off.as<int64_t>();
-        a.col_off = s->rows.d_col_off.as<int64_t>();
-        a.ref = c->model.tables();
-        a.rec = gc.d_rec.as<sfa_group_cover_t>();
-        a.total_cols = c->model.total_cols;
-        a.n_jobs = c->model.n_jobs;
-        a.n_groups = s->groups.n_groups;
-        a.cap = static_cast<uint32_t>(gc.cap);
-        hipLaunchKernelGGL(sfa::session_reach_label_group_kernel, dim3(sfa::group_cover_blocks(c->model.total_cols)), dim3(sfa::kGroupCoverThreads), 0, st, a);
-        KERNEL_TRY();
-    } else {
-        sfa::SessionCoverGroupArgs a;
-        a.base = s->groups.d_label.as<uint64_t>();
-        a.depth = s->cover.d_depth.as<uint32_t>();
-        a.cov_off = s->cover.d_cov_off.as<int64_t>();
-        a.col_off = s->rows.d_col_off.as<int64_t>();
-        a.ref = c->model.tables();
-        a.rec = gc.d_rec.as<sfa_group_cover_t>();
-        a.total_cols = c->model.total_cols;
-        a.n_jobs = c->model.n_jobs;
-        a.n_groups = s->groups.n_groups;
-        a.cap = static_cast<uint32_t>(gc.cap);
-        hipLaunchKernelGGL(sfa::session_cover_group_kernel, dim3(sfa::group_cover_blocks(c->model.total_cols)), dim3(sfa::kGroupCoverThreads), 0, st, a);
-        KERNEL_TRY();
-    }
-    HIP_TRY(hipEventRecord(gc.ev[1], st));
-    HIP_TRY(hipMemcpyAsync(hr + entries, gc.d_rec.p, sizeof(sfa_group_cover_t) * static_cast<size_t>(entries), hipMemcpyDeviceToHost, st));
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, gc.ev[0], gc.ev[1]));
-    sfa_profile_t pr{};
-    pr.segment_reruns = c->seg.seg_reruns;
-    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
-    pr.class_ms = pr.total_ms = ms;
-    c->prof = pr;
-    memcpy(out, hr + entries, sizeof(sfa_group_cover_t) * static_cast<size_t>(entries));
-    return SFA_OK;
-}
-
-// ---- target groups (group_rules.hpp, sdtw_session_group.hpp) ----
-
-int sfa_session_target_groups(sfa_session_t *s, const sfa_group_target_t *targets, int32_t n, int32_t n_groups) {
-    static const char *const who = "sfa_session_target_groups";
-    if (!s || n < 0 || (n > 0 && !targets)) return fail(SFA_EINVAL, "%s: bad argument", who);
-    if (s->resweep)
-        return fail(SFA_EINVAL, "%s: the session was created with SFA_SESSION_RESWEEP: its carried row belongs to the reversed query, and what its minimum means has "
-                                "not been looked into",
-                    who);
-    if (s->spread) {  // every sub-session holds the table (no slot needs to be empty: spread_config's check does not apply)
-        if (int rc = spread_live(s, who)) return rc;
-        sess::Spread &sp = *s->spread;
-        std::vector<int> rcs(sp.subs.size(), 0);
-        const int rc = sfa::for_each_shard(s->c, [&](size_t r) { return sp.subs[r] ? (rcs[r] = sfa_session_target_groups(sp.subs[r], targets, n, n_groups)) : static_cast<int>(SFA_OK); });
-        size_t have = 0, failed = 0;
-        for (size_t r = 0; r < sp.subs.size(); ++r) have += sp.subs[r] != nullptr, failed += rcs[r] != SFA_OK;
-        if (failed != 0 && failed != have) sp.broken = true;
-        return rc;
-    }
-    sfa_ctx *c = s->c;
-    sess::Groups &g = s->groups;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // (a table in use is not replaced under a kernel)
-    s->open.first.clear();                     // (sfa_session_open_classes looks for the labels' first columns again)
-    if (n == 0) {
-        g.n_groups = 0;
-        std::vector<uint16_t>().swap(g.h_label);
-        g.d_label = DevBuf{};  // (freed; the buffers of a call stay for the next table)
-        s->greach.free_all();  // (a reach list's group anchors go with its label table)
-        if (s->gcover.on()) gcover_drop(s);  // (a group cap lives on the labels: off with them)
-        return SFA_OK;
-    }
-    if (c->model.total_cols >= INT32_MAX) return fail(SFA_ERANGE, "%s: the reference has %lld columns; the groups count them in 31 bits", who, (long long)c->model.total_cols);
-    // the model's tables on the host: jobs are contig-major, '+' before '-' (sfa_context.hip)
-    const int32_t nj = c->model.n_jobs, strands = nj / c->model.num_ref;
-    std::vector<int32_t> job_contig(nj), ref_len(c->model.num_ref);
-    std::vector<int8_t> job_strand(nj);
-    for (int32_t j = 0; j < nj; ++j) job_contig[j] = j / strands, job_strand[j] = (j % strands) ? '-' : '+';
-    for (int32_t r = 0; r < c->model.num_ref; ++r) ref_len[r] = c->model.h_job_len[static_cast<size_t>(r) * strands];
-    const sfa::TargetModel m{c->model.num_ref, nj, job_contig.data(), job_strand.data(), c->model.h_job_len.data(), s->rows.h_col_off.data(), ref_len.data(),
-                             c->model.h_ref_off.data(), c->model.total_cols};
-    char msg[256];
-    if (sfa::group_list_error(targets, n, n_groups, m, msg, sizeof msg)) return fail(SFA_EINVAL, "%s: %s", who, msg);
-    std::vector<uint16_t> label;
-    sfa::group_labels(targets, n, n_groups, m, &label);
-    if (int rc = g.reserve(c->model.total_cols)) return rc;
-    if (int rc = sess::create_events(g.ev, 2)) return rc;
-    if (s->gcover.on())  // (the live table's tables follow the new n_groups; a group cap never outlives a failure here)
-        if (int rc = s->gcover.reserve(c->model.total_cols, n_groups)) {
-            gcover_drop(s);
-            return rc;
-        }
-    g.n_groups = 0;  // (off until the new table is up)
-    s->greach.free_all();  // (a plain table replaces a reach list, before the table is overwritten: no anchor outlives the table it belongs to)
-    g.h_label.swap(label);
-    const auto upload = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(g.d_label.p, g.h_label.data(), 2 * g.h_label.size(), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return SFA_OK;
-    };
-    if (int rc = upload()) {
-        if (s->gcover.on()) gcover_drop(s);  // (no groups: no group cap)
-        return rc;
-    }
-    g.n_groups = n_groups;
-    if (s->gcover.on()) {  // (the depth is kept: the live table of the new base table)
-        const int rc = gcover_derive(s, who);
-        if (rc) gcover_drop(s);
-        return rc;
-    }
-    return SFA_OK;
-}
-
-// ---- reach groups (reach_group_rules.hpp, sdtw_session_reachgroup.hpp) ----
-
-size_t sfa_session_group_reach_bytes(const sfa_ref_t *ref, int flag) {
-    if (!ref || ref->num_ref <= 0 || !ref->ref_lengths) return 0;
-    int64_t cols = 0;
-    for (int32_t r = 0; r < ref->num_ref; ++r) {
-        if (ref->ref_lengths[r] <= 0) return 0;
-        cols += static_cast<int64_t>(ref->ref_lengths[r]) * ((flag & SFA_RNA) ? 1 : 2);
-    }
-    return sfa::reach_group_bytes(cols);
-}
-
-int sfa_session_target_groups_reach(sfa_session_t *s, const sfa_reach_group_target_t *targets, int32_t n, int32_t n_groups) {
-    static const char *const who = "sfa_session_target_groups_reach";
-    if (!s || n < 0 || (n > 0 && !targets)) return fail(SFA_EINVAL, "%s: bad argument", who);
-    if (s->resweep)
-        return fail(SFA_EINVAL, "%s: the session was created with SFA_SESSION_RESWEEP: its carried row belongs to the reversed query, and what its minimum means has "
-                                "not been looked into",
-                    who);
-    if (n == 0) return sfa_session_target_groups(s, nullptr, 0, n_groups);  // (groups off, the anchors freed: one path)
-    if (s->spread) {  // every sub-session holds the table and its anchors, as in sfa_session_target_groups
-        if (int rc = spread_live(s, who)) return rc;
-        sess::Spread &sp = *s->spread;
-        std::vector<int> rcs(sp.subs.size(), 0);
-        const int rc =
-            sfa::for_each_shard(s->c, [&](size_t r) { return sp.subs[r] ? (rcs[r] = sfa_session_target_groups_reach(sp.subs[r], targets, n, n_groups)) : static_cast<int>(SFA_OK); });
-        size_t have = 0, failed = 0;
-        for (size_t r = 0; r < sp.subs.size(); ++r) have += sp.subs[r] != nullptr, failed += rcs[r] != SFA_OK;
-        if (failed != 0 && failed != have) sp.broken = true;
-        return rc;
-    }
-    sfa_ctx *c = s->c;
-    sess::Groups &g = s->groups;
-    sess::GroupReach &gr = s->greach;
-    if (c->model.total_cols >= INT32_MAX) return fail(SFA_ERANGE, "%s: the reference has %lld columns; the groups count them in 31 bits", who, (long long)c->model.total_cols);
-    const CoverModel cm(s);
-    char msg[256];
-    if (sfa::reach_group_list_error(targets, n, n_groups, cm.m, msg, sizeof msg)) return fail(SFA_EINVAL, "%s: %s", who, msg);
-    sfa::ReachGroupPrepared prep;
-    sfa::reach_group_prepare(targets, n, cm.m, &prep);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // (a table in use is not replaced under a kernel)
-    // (from here on the old table is gone: an allocation or device failure leaves the session without groups -- and so without a
-    // group cap, which lives on the labels -- never with half of two lists; include/sigfish_amd.h says so)
-    const auto give_up = [&](int rc) {
-        sfa_session_target_groups(s, nullptr, 0, 0);
-        return rc;
-    };
-    s->open.first.clear();
-    g.n_groups = 0;  // (off until the new table is up)
-    std::vector<uint16_t>().swap(g.h_label);  // (the table is built on the device: sfa_session_group_reach_tables copies it back)
-    gr.on = false;
-    if (int rc = g.reserve(c->model.total_cols)) return give_up(rc);
-    if (int rc = sess::create_events(g.ev, 2)) return give_up(rc);
-    if (int rc = gr.reserve(c->model.total_cols, prep.runs.size(), c->model.n_jobs, n_groups)) return give_up(rc);
-    if (s->gcover.on())  // (the live table's tables follow the new n_groups)
-        if (int rc = s->gcover.reserve(c->model.total_cols, n_groups)) return give_up(rc);
-    hipStream_t st = c->stream;
-    const size_t entries = static_cast<size_t>(n_groups) + 1;
-    int32_t *hf = gr.h_first.as<int32_t>();
-    std::fill(hf, hf + entries, sfa::kNoColumn);
-    sfa::SessionReachLabelBuildArgs a;
-    a.runs = gr.d_runs.as<sfa::ReachGroupRun>();
-    a.run_off = gr.d_run_off.as<int32_t>();
-    a.col_off = s->rows.d_col_off.as<int64_t>();
-    a.label = g.d_label.as<uint16_t>();
-    a.anchor = gr.d_anchor.as<int32_t>();
-    a.first = gr.d_first.as<int32_t>();
-    a.total_cols = c->model.total_cols;
-    a.n_jobs = c->model.n_jobs;
-    a.n_groups = n_groups;
-    // the labels from the row's last quad on, the word behind the row with them: the background (the kernel writes the row's own)
-    const size_t tail = 4 * static_cast<size_t>(c->model.total_cols / 4), n_tail = 4 * sfa::group_label_words(c->model.total_cols) - tail;
-    const auto enqueue = [&]() -> int {  // (the uploads of the runs read pageable memory: they are through when the calls return)
-        HIP_TRY(hipMemcpyAsync(gr.d_first.p, hf, 4 * entries, hipMemcpyHostToDevice, st));
-        if (!prep.runs.empty()) HIP_TRY(hipMemcpyAsync(gr.d_runs.p, prep.runs.data(), sizeof(sfa::ReachGroupRun) * prep.runs.size(), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(gr.d_run_off.p, prep.run_off.data(), 4 * prep.run_off.size(), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(g.d_label.as<uint16_t>() + tail), static_cast<unsigned short>(n_groups), n_tail, st));
-        hipLaunchKernelGGL(sfa::session_reach_label_build_kernel, dim3(sfa::group_cover_blocks(c->model.total_cols)), dim3(sfa::kGroupCoverThreads), 0, st, a);
-        KERNEL_TRY();
-        HIP_TRY(hipMemcpyAsync(hf + entries, gr.d_first.p, 4 * entries, hipMemcpyDeviceToHost, st));
-        return SFA_OK;
-    };
-    if (int rc = enqueue()) return give_up(rc);
-    if (hipStreamSynchronize(st) != hipSuccess) return give_up(fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError())));
-    sfa::group_cover_firsts_for_open(hf + entries, n_groups, &s->open.first);  // (what sfa_session_open_classes needs once per label table)
-    gr.free_call();  // (the runs and the firsts were the call's: only the anchors stay)
-    g.n_groups = n_groups;
-    gr.on = true;
-    if (s->gcover.on()) {  // (the depth is kept: the live table of the new base table and its anchors)
-        const int rc = gcover_derive(s, who);
-        if (rc) return give_up(rc);
-    }
-    return SFA_OK;
-}
-
-int sfa_session_group_reach_tables(sfa_session_t *s, uint16_t *label, int32_t *anchor, int64_t n_cols) {
-    static const char *const who = "sfa_session_group_reach_tables";
-    if (!s) return fail(SFA_EINVAL, "%s: null session", who);
-    if (s->spread) {
-        if (int rc = spread_live(s, who)) return rc;
-        return sfa_session_group_reach_tables(s->spread->subs[0], label, anchor, n_cols);  // (shard 0 answers: every shard holds the same tables)
-    }
-    sfa_ctx *c = s->c;
-    if (!s->greach.on) return fail(SFA_EINVAL, "%s: the session has no reach groups (sfa_session_target_groups_reach)", who);
-    if ((label || anchor) && n_cols != c->model.total_cols)
-        return fail(SFA_EINVAL, "%s: n_cols is %lld; a row has %lld columns", who, (long long)n_cols, (long long)c->model.total_cols);
-    HIP_TRY(hipSetDevice(c->device));
-    if (label) HIP_TRY(hipMemcpyAsync(label, s->groups.d_label.p, 2 * static_cast<size_t>(n_cols), hipMemcpyDeviceToHost, c->stream));
-    if (anchor) HIP_TRY(hipMemcpyAsync(anchor, s->greach.d_anchor.p, 4 * static_cast<size_t>(n_cols), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SFA_OK;
-}
-
-int32_t sfa_session_group_count(sfa_session_t *s) {
-    if (!s) return fail(SFA_EINVAL, "sfa_session_group_count: null session");
-    if (s->spread) return sfa_session_group_count(s->spread->subs[0]);  // (sub-session 0 always exists, as in spread_classes)
-    return s->groups.n_groups;
-}
-
-int sfa_session_group_bests(sfa_session_t *s, const int32_t *slot, int32_t n, sfa_group_best_t *bests, sfa_group_head_t *heads) {
-    static const char *const who = "sfa_session_group_bests";
-    if (!s || n < 0 || (n > 0 && (!slot || !heads))) return fail(SFA_EINVAL, "%s: bad argument", who);
-    if (s->spread) return spread_group_bests(s, slot, n, bests, heads);
-    sess::Groups &g = s->groups;
-    if (!g.on()) return fail(SFA_EINVAL, "%s: the session has no groups (sfa_session_target_groups)", who);
-    if (int rc = check_slots(s, slot, n, who)) return rc;
-    begin_call(s);  // (the stamps say which slots this call has named)
-    for (int32_t i = 0; i < n; ++i)
-        if (int rc = claim_slot(s, slot[i], who)) return rc;
-    if (n == 0) return SFA_OK;
-    sfa_ctx *c = s->c;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int rc = sfa::resolve_profile(c)) return rc;
-    g.live.clear();
-    for (int32_t i = 0; i < n; ++i)  // empty and poisoned slots are not launched
-        if (!s->rows.poison[slot[i]] && s->rows.len[slot[i]] > 0) g.live.push_back(i);
-    const int32_t m = static_cast<int32_t>(g.live.size()), parts = sfa::class_parts(c->model.total_cols), entries = g.n_groups + 1;
-    // (every refusal in front of the first write to the caller's records)
-    if (static_cast<int64_t>(m) * parts > INT32_MAX) return fail(SFA_ERANGE, "%s: %d slots x %d parts of a row are more blocks than a launch takes", who, m, parts);
-    if (m > 0)
-        if (int rc = g.reserve_call(static_cast<size_t>(m), static_cast<size_t>(entries), bests != nullptr)) return rc;
-    sfa_group_best_t no_best{};
-    no_best.score = INFINITY;
-    no_best.rid = no_best.pos_end = -1;
-    for (int32_t i = 0; i < n; ++i) heads[i] = sfa::group_head_none();
-    if (bests)
-        for (size_t k = 0; k < static_cast<size_t>(n) * entries; ++k) bests[k] = no_best;
-    sfa_profile_t pr{};
-    pr.segment_reruns = c->seg.seg_reruns;
-    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
-    if (m > 0) {
-        int32_t *hs = g.h_slot.as<int32_t>();
-        for (int32_t k = 0; k < m; ++k) hs[k] = slot[g.live[k]];
-        hipStream_t st = c->stream;
-        const size_t n_keys = static_cast<size_t>(m) * entries;
-        HIP_TRY(hipMemcpyAsync(g.d_slot.p, hs, 4 * static_cast<size_t>(m), hipMemcpyHostToDevice, st));
-        sfa::SessionGroupArgs a;
-        a.slot = g.d_slot.as<int32_t>();
-        a.rows = s->rows.d_row_c.as<float>() + sfa::kSessionPad;
-        a.label = s->gcover.on() ? s->gcover.d_live.as<uint64_t>() : g.d_label.as<uint64_t>();  // (the kernel is the same: another pointer)
-        a.key = g.d_key.as<unsigned long long>();
-        a.total_cols = c->model.total_cols;
-        a.n = m;
-        a.n_parts = parts;
-        a.n_entries = entries;
-        sfa::SessionGroupRowsArgs ra;
-        ra.key = a.key;
-        ra.col_off = s->rows.d_col_off.as<int64_t>();
-        ra.ref = c->model.tables();
-        ra.best = bests ? g.d_best.as<sfa_group_best_t>() : nullptr;
-        ra.head = g.d_head.as<sfa_group_head_t>();
-        ra.n = m;
-        ra.n_entries = entries;
-        ra.n_jobs = c->model.n_jobs;
-        HIP_TRY(hipEventRecord(g.ev[0], st));
-        HIP_TRY(hipMemsetAsync(g.d_key.p, 0xff, 8 * n_keys, st));  // all-ones: no column met
-        hipLaunchKernelGGL(sfa::sdtw_session_group_kernel, dim3(static_cast<unsigned>(m) * parts), dim3(sfa::kClassThreads), 0, st, a);
-        KERNEL_TRY();
-        hipLaunchKernelGGL(sfa::sdtw_session_group_rows_kernel, dim3(m), dim3(64), 0, st, ra);
-        KERNEL_TRY();
-        HIP_TRY(hipEventRecord(g.ev[1], st));
-        HIP_TRY(hipMemcpyAsync(g.h_head.p, g.d_head.p, sizeof(sfa_group_head_t) * static_cast<size_t>(m), hipMemcpyDeviceToHost, st));
-        if (bests) HIP_TRY(hipMemcpyAsync(g.h_best.p, g.d_best.p, sizeof(sfa_group_best_t) * n_keys, hipMemcpyDeviceToHost, st));
-        if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, g.ev[0], g.ev[1]));
-        pr.class_ms = pr.total_ms = ms;
-        for (int32_t k = 0; k < m; ++k) {
-            heads[g.live[k]] = g.h_head.as<sfa_group_head_t>()[k];
-            heads[g.live[k]].n_events = static_cast<int32_t>(s->rows.len[slot[g.live[k]]]);
-            if (bests) memcpy(bests + static_cast<size_t>(g.live[k]) * entries, g.h_best.as<sfa_group_best_t>() + static_cast<size_t>(k) * entries, sizeof(sfa_group_best_t) * entries);
-        }
-    }
-    c->prof = pr;
-    return SFA_OK;
-}
-
-int sfa_group_decide(const sfa_group_head_t *h, int32_t min_events, float margin) { return h ? sfa::group_decide(*h, min_events, margin) : -1; }
-
-// ---- open and closed groups (quota_rules.hpp, sdtw_session_open.hpp) ----
-
-int sfa_session_open_classes(sfa_session_t *s, const int32_t *slot, int32_t n, const uint32_t *open, int32_t n_words, sfa_open_class_t *out) {
-    static const char *const who = "sfa_session_open_classes";
-    if (!s || n < 0 || (n > 0 && (!slot || !out))) return fail(SFA_EINVAL, "%s: bad argument", who);
-    if (s->spread) return spread_open_classes(s, slot, n, open, n_words, out);
-    sess::Groups &g = s->groups;
-    sess::Open &o = s->open;
-    if (!g.on()) return fail(SFA_EINVAL, "%s: the session has no groups (sfa_session_target_groups)", who);
-    if (open && n_words != sfa::open_words(g.n_groups))
-        return fail(SFA_EINVAL, "%s: the bitmap of %d groups has %d words, not %d", who, g.n_groups, sfa::open_words(g.n_groups), n_words);
-    if (int rc = check_slots(s, slot, n, who)) return rc;
-    begin_call(s);  // (the stamps say which slots this call has named)
-    for (int32_t i = 0; i < n; ++i)
-        if (int rc = claim_slot(s, slot[i], who)) return rc;
-    if (n == 0) return SFA_OK;
-    sfa_ctx *c = s->c;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int rc = sfa::resolve_profile(c)) return rc;
-    o.live.clear();
-    for (int32_t i = 0; i < n; ++i)  // empty and poisoned slots are not launched
-        if (!s->rows.poison[slot[i]] && s->rows.len[slot[i]] > 0) o.live.push_back(i);
-    const int32_t m = static_cast<int32_t>(o.live.size()), parts = sfa::class_parts(c->model.total_cols);
-    // (every refusal in front of the first write to the caller's records)
-    if (static_cast<int64_t>(m) * parts > INT32_MAX) return fail(SFA_ERANGE, "%s: %d slots x %d parts of a row are more blocks than a launch takes", who, m, parts);
-    if (m > 0) {
-        if (int rc = o.reserve(static_cast<size_t>(m), static_cast<size_t>(parts))) return rc;
-        if (int rc = sess::create_events(o.ev, 2)) return rc;
-    }
-    for (int32_t i = 0; i < n; ++i) out[i] = sfa::open_class_none();
-    sfa_profile_t pr{};
-    pr.segment_reruns = c->seg.seg_reruns;
-    pr.blow5_fallbacks = c->blow5.blow5_fallbacks;
-    if (m > 0) {
-        const bool capped = s->gcover.on();  // (the live table and its firsts, which the derive left: the kernels are the same)
-        if (!capped && o.first.empty()) sfa::open_label_firsts(g.h_label.data(), c->model.total_cols, g.n_groups, &o.first);
-        int32_t *hs = o.h_slot.as<int32_t>();
-        for (int32_t k = 0; k < m; ++k) hs[k] = slot[o.live[k]];
-        hipStream_t st = c->stream;
-        HIP_TRY(hipMemcpyAsync(o.d_slot.p, hs, 4 * static_cast<size_t>(m), hipMemcpyHostToDevice, st));
-        sfa::SessionOpenArgs a;
-        a.slot = o.d_slot.as<int32_t>();
-        a.rows = s->rows.d_row_c.as<float>() + sfa::kSessionPad;
-        a.label = capped ? s->gcover.d_live.as<uint64_t>() : g.d_label.as<uint64_t>();
-        a.part = o.d_part.as<sfa::ClassPartial>();
-        a.total_cols = c->model.total_cols;
-        a.n = m;
-        a.n_parts = parts;
-        sfa::open_normalise(open, g.n_groups, a.open);  // (the bitmap travels in the argument block: nothing is uploaded)
-        sfa::SessionOpenRowsArgs ra;
-        ra.part = a.part;
-        ra.col_off = s->rows.d_col_off.as<int64_t>();
-        ra.ref = c->model.tables();
-        ra.label = capped ? s->gcover.d_live.as<uint16_t>() : g.d_label.as<uint16_t>();
-        ra.out = o.d_out.as<sfa_open_class_t>();
-        ra.n = m;
-        ra.n_parts = parts;
-        ra.n_jobs = c->model.n_jobs;
-        sfa::open_first_cols(capped ? s->gcover.first : o.first, g.n_groups, a.open, &ra.first_on, &ra.first_off);
-        HIP_TRY(hipEventRecord(o.ev[0], st));
-        hipLaunchKernelGGL(sfa::sdtw_session_open_kernel, dim3(static_cast<unsigned>(m) * parts), dim3(sfa::kClassThreads), 0, st, a);
-        KERNEL_TRY();
-        hipLaunchKernelGGL(sfa::sdtw_session_open_rows_kernel, dim3(m), dim3(64), 0, st, ra);
-        KERNEL_TRY();
-        HIP_TRY(hipEventRecord(o.ev[1], st));
-        HIP_TRY(hipMemcpyAsync(o.h_out.p, o.d_out.p, sizeof(sfa_open_class_t) * static_cast<size_t>(m), hipMemcpyDeviceToHost, st));
-        if (hipStreamSynchronize(st) != hipSuccess) return fail(SFA_EKERNEL, "%s: the launches failed: %s", who, hipGetErrorString(hipGetLastError()));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, o.ev[0], o.ev[1]));
-        pr.class_ms = pr.total_ms = ms;
-        for (int32_t k = 0; k < m; ++k) {
-            out[o.live[k]] = o.h_out.as<sfa_open_class_t>()[k];
-            out[o.live[k]].cls.n_events = static_cast<int32_t>(s->rows.len[slot[o.live[k]]]);
-        }
-    }
-    c->prof = pr;
-    return SFA_OK;
 }
 
 // ---- event maps of a slot's row (the core: sfa_maps.hip) ----

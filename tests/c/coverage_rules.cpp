@@ -1,4 +1,4 @@
-// The host rules of a session's coverage cap (sigfish_amd/csrc/coverage_rules.hpp, the header sfa_session.hip and the kernels of
+// The host rules of a session's coverage cap (sigfish_amd/csrc/coverage_rules.hpp, the header sfa_session_targets.hip and the kernels of
 // sdtw_session_cover.hpp share) as a stand-alone host program, built from that header alone; tests/test_session_coverage_cpu.py
 // runs it plain and under ASan + UBSan and compares its answers with the numpy model of tests/coverage_model.py.
 //   selftest      the layout (coverage_offsets, coverage_span's clipping, coverage_entry at both ends of both strands), depth cap - 1

@@ -1,4 +1,4 @@
-// The host rules of a session's group cap (sigfish_amd/csrc/group_cover_rules.hpp, the header sfa_session.hip and the kernels of
+// The host rules of a session's group cap (sigfish_amd/csrc/group_cover_rules.hpp, the header sfa_session_targets.hip and the kernels of
 // sdtw_session_groupcover.hpp share) as a stand-alone host program, built from that header alone; tests/test_session_group_cover_cpu.py
 // runs it plain and under ASan + UBSan and compares its answers with the numpy model of tests/group_cover_model.py.
 //   selftest      the rule at its edges: depth cap - 1 open and cap closed side by side, a background column at any depth, a column

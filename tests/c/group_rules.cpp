@@ -1,4 +1,4 @@
-// The host rules of a session's target groups (sigfish_amd/csrc/group_rules.hpp, the header sfa_session.hip builds its label table
+// The host rules of a session's target groups (sigfish_amd/csrc/group_rules.hpp, the header sfa_session_targets.hip builds its label table
 // and decides with) as a stand-alone host program, built from that header alone; tests/test_session_groups_cpu.py runs it plain
 // and under ASan + UBSan.
 //   selftest                      the labels of every case against a loop that calls place_col (row_rules.hpp) for every column

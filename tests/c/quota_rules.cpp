@@ -1,4 +1,4 @@
-// The host rules of a session's open and closed groups (sigfish_amd/csrc/quota_rules.hpp, the header sfa_session.hip normalises
+// The host rules of a session's open and closed groups (sigfish_amd/csrc/quota_rules.hpp, the header sfa_session_targets.hip normalises
 // the bitmap with and the rows kernel builds its record with) as a stand-alone host program, built from that header alone;
 // tests/test_session_quota_cpu.py runs it plain and under ASan + UBSan.
 //   selftest      the record of every case against a per-column brute force (place_col of row_rules.hpp for every column and

@@ -1,4 +1,4 @@
-// The host rules of a session's reach groups (sigfish_amd/csrc/reach_group_rules.hpp, the header sfa_session.hip and the kernels of
+// The host rules of a session's reach groups (sigfish_amd/csrc/reach_group_rules.hpp, the header sfa_session_targets.hip and the kernels of
 // sdtw_session_reachgroup.hpp share) as a stand-alone host program, built from that header alone;
 // tests/test_reach_group_rules_cpu.py runs it plain and under ASan + UBSan.
 //   selftest      the list refusals; reach_group_tables against a second, brute-force statement (per column over every target, the

@@ -1,4 +1,4 @@
-// The host rules of a session's reach targets (sigfish_amd/csrc/reach_rules.hpp, the header sfa_session.hip and the kernels of
+// The host rules of a session's reach targets (sigfish_amd/csrc/reach_rules.hpp, the header sfa_session_targets.hip and the kernels of
 // sdtw_session_reach.hpp share) as a stand-alone host program, built from that header alone; tests/test_reach_model_cpu.py runs
 // it plain and under ASan + UBSan and compares its answers with the numpy model of tests/reach_model.py.
 //   selftest      the list refusals; reach_tables against a second, brute-force statement (per column over every target, the

@@ -1,4 +1,4 @@
-// The host rules of a session's target classes (sigfish_amd/csrc/target_rules.hpp, the header sfa_session.hip builds its mask and
+// The host rules of a session's target classes (sigfish_amd/csrc/target_rules.hpp, the header sfa_session_targets.hip builds its mask and
 // decides with) as a stand-alone host program, built from that header alone; tests/test_session_targets_cpu.py runs it plain and
 // under ASan + UBSan.
 //   selftest                      the mask of every case against a loop that calls place_col (row_rules.hpp) for every column and

@@ -1,4 +1,4 @@
-"""Spread sessions on the GPU (SFA_SESSION_SPREAD, session_spread.hpp, the prologues in sfa_session.hip): a session whose slots are
+"""Spread sessions on the GPU (SFA_SESSION_SPREAD, session_spread.hpp, the prologues in sfa_session.hip, sfa_session_targets.hip and sfa_session_state.hpp): a session whose slots are
 dealt over the shards of a group context.  The yardstick is always a PLAIN session on a single-device context fed the same calls:
 after every call every output of the spread session -- rows, lengths, statuses, candidates, spans, automatic-start records,
 row(), events(), maps -- is the plain session's, byte for byte; one leg compares with the oracle's rows as well, so the test is
